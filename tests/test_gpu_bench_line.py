@@ -25,8 +25,8 @@ def _bench(extra):
 SMALL = ["--enc-bits", "256", "--k", "13", "--steps", "3", "--warmup", "1"]
 
 
-def test_headline_line_small_shape():
-    d = _bench(SMALL + ["--headline-only"])
+def test_headline_line_small_shape(tmp_path):
+    d = _bench(SMALL + ["--headline-only", "--dump-outputs", str(tmp_path)])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
                 "roofline", "cpu_baseline"):
         assert key in d, key
@@ -42,6 +42,13 @@ def test_headline_line_small_shape():
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["connected_tail"]["field_mults_per_s_all_threads"] > 0
     assert set(d["phases_ms_per_proof"]) >= {"advice_commit", "products_commit", "quotient", "evaluations", "multiopen"}
     assert d["memory_gb"]["proving_key_streamed"] is False and d["counts"]["minimum_rows"] == 20
+    # --dump-outputs: the last timed proof, as many commitments and evaluations as the checked proof has, every word exact
+    import numpy as np
+
+    dumped = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(tmp_path)}
+    assert all(a.dtype == np.float64 and np.array_equal(a, np.floor(a)) and (a >= 0).all() and (a < 2.0 ** 32).all() for a in dumped.values())
+    assert sum(a.shape[0] for k, a in dumped.items() if k.startswith("commitments_")) == d["verification"]["commitments"]
+    assert sum(a.shape[0] * a.shape[1] for k, a in dumped.items() if k.startswith("evals_")) == d["verification"]["evaluations"]
 
 
 def test_headline_line_streamed_key_and_minimum_rows_9():

@@ -77,12 +77,56 @@ def test_pipelined_step_equals_serial_and_oracle(c2, cref):
     assert vo["ok"] is True, vo
 
 
+def _one_queue(torch, a, b):
+    """True when work on stream b waits behind stream a's: the two share a hardware queue, which runs its work in order"""
+    busy, done = torch.cuda.Event(), torch.cuda.Event()
+    with torch.cuda.stream(a):
+        torch.cuda._sleep(100_000_000)
+        busy.record(a)
+    with torch.cuda.stream(b):
+        torch.cuda._sleep(1000)
+        done.record(b)
+    done.synchronize()
+    shared = busy.query()
+    busy.synchronize()
+    return shared
+
+
+def _place_streams(wl, edge):
+    """A process opens few hardware queues (GPU_MAX_HW_QUEUES), so its streams share them, and a queue runs its work in order: a
+    removed edge can only show where the stream that no longer waits is on another queue than the work it should wait for.
+    ready / free: the witness stream is placed beside the commitment (main) stream and the transform stream.  ntt_ready: the
+    transform stream beside both (its reads would otherwise queue behind the commitment stream's own wait for K4)."""
+    import torch
+
+    main = torch.cuda.current_stream()
+
+    def pick(ok):
+        for _ in range(16):
+            s = torch.cuda.Stream()
+            if s.cuda_stream != main.cuda_stream and ok(s):
+                return s
+        pytest.fail("no placement of this process's streams lets the removed edge %r show" % edge)
+
+    if edge == "ntt_ready":
+        sw = pick(lambda s: _one_queue(torch, main, s))
+        sn = pick(lambda s: not _one_queue(torch, main, s) and not _one_queue(torch, sw, s))
+    else:
+        sw = pick(lambda s: not _one_queue(torch, main, s))
+        sn = pick(lambda s: not _one_queue(torch, sw, s))
+    wl.stream_w, wl.stream_n = sw, sn
+    wl.engw.set_stream(sw.cuda_stream)
+    wl.engn.set_stream(sn.cuda_stream)
+
+
 @pytest.mark.parametrize("edge", ["ready", "free", "ntt_ready"])
 def test_a_removed_event_edge_is_noticed(c2, edge):
     """ready: the commitment stream does not wait for K4; free: the witness stream overwrites a slot its readers still use;
     ntt_ready: the transform stream does not wait for K4.  Every kernel stays inside its buffers whatever it reads (the sort's
     position checks), so these runs are safe; what they must not be is `verified`."""
     _, _, wl = c2
+    assert wl.stream_w is not None and wl.stream_n is not None
+    _place_streams(wl, edge)
     wl.drop_edge = edge
     try:
         v = wl.verify_pipelined()
