@@ -377,6 +377,22 @@ int pz_keygen_columns_dev(pz_ctx* ctx, const pz_bases* bases_lagrange, uint64_t*
  * accepted): *n_bad = number of points that fail.  The check halo2curves' read_raw performs when ParamsKZG::read
  * loads a `params/kzg_bn254_{k}.srs` file (paillier_halo2_amd/srs.py reads that format). */
 int pz_g1_check_dev(pz_ctx* ctx, const uint64_t* d_points, size_t n, uint64_t* n_bad);
+/* BN254 pairing (the verifier's side of ParamsKZG; csrc/pz_pairing.hip).  halo2curves' tower: Fq2 = Fq[u]/(u^2 + 1),
+ * Fq6 = Fq2[v]/(v^3 - (9 + u)), Fq12 = Fq6[w]/(w^2 - v); G2 on the D-type twist y^2 = x^3 + 3/(9 + u) over Fq2.
+ * G2 affine points: 16 words x.c0, x.c1, y.c0, y.c1 (4 Montgomery words each, ParamsKZG RawBytes), identity = all zero.
+ * G1: the affine form above (8 words, (0, 0) = identity).  GT: 48 words, Fq12 c0.c0.c0, c0.c0.c1, c0.c1.c0, ... c1.c2.c1.
+ * e(P, Q) = f_{6x+2,Q}(P) l_{[6x+2]Q,pi(Q)}(P) l_{..,-pi^2(Q)}(P), raised to exactly (p^12 - 1)/r; a pair with an identity
+ * contributes 1.  The device entry points are asynchronous on the context's stream. */
+/* halo2curves' G2 generator */
+int pz_g2_generator(uint64_t out[16]);
+/* d_out[i] = [s_i] Q_i for n G2 points (on the twist; the result is undefined otherwise); scalars Fr Montgomery (4 words) */
+int pz_g2_mul_dev(pz_ctx* ctx, const uint64_t* d_g2, const uint64_t* d_scalars, size_t n, uint64_t* d_out);
+/* d_gt[i] = e(P_i, Q_i); all 48 words zero (not a GT element) if P_i or Q_i is off its curve or not canonical */
+int pz_pairing_dev(pz_ctx* ctx, const uint64_t* d_g1, const uint64_t* d_g2, size_t n, uint64_t* d_gt);
+/* n_checks products of pairs_per_check pairings (check i takes pairs i * pairs_per_check + j): d_ok[i] = 1 if
+ * prod_j e(P_ij, Q_ij) == 1, 0 if not, -1 if any input of that check is off its curve or not canonical.  No subgroup check. */
+int pz_pairing_check_dev(pz_ctx* ctx, const uint64_t* d_g1, const uint64_t* d_g2, size_t n_checks, uint32_t pairs_per_check,
+                         int32_t* d_ok);
 /* evaluation of n_cols coefficient-form polynomials (n coefficients each, device) at the point x:
  * d_out[col] = sum_i d_coeffs[col][i] * x^i   (the evals phase of create_proof / eval_polynomial). */
 int pz_poly_eval_dev(pz_ctx* ctx, const uint64_t* d_coeffs, size_t n_cols, size_t col_stride, size_t n,

@@ -414,6 +414,26 @@ class Engine:
         self._chk(self.L.pz_g1_check_dev(self.ctx, VP(d_points), n, C.byref(bad)), "pz_g1_check_dev")
         return bad.value
 
+    # ------------------------------------------------------------------ BN254 pairing (verifier side; pz.h)
+    def g2_generator(self) -> np.ndarray:
+        """halo2curves' G2 generator, 16 Montgomery words (x.c0, x.c1, y.c0, y.c1)"""
+        out = np.zeros(16, dtype=np.uint64)
+        self._chk(self.L.pz_g2_generator(_ptr(out)), "pz_g2_generator")
+        return out
+
+    def g2_mul_dev(self, d_g2: int, d_scalars: int, n: int, d_out: int):
+        """d_out[i] = [s_i] Q_i: n G2 affine points (16 words), Fr Montgomery scalars (4 words), device pointers"""
+        self._chk(self.L.pz_g2_mul_dev(self.ctx, VP(d_g2), VP(d_scalars), n, VP(d_out)), "pz_g2_mul_dev")
+
+    def pairing_dev(self, d_g1: int, d_g2: int, n: int, d_gt: int):
+        """d_gt[i] = e(P_i, Q_i), 48 words each (device pointers)"""
+        self._chk(self.L.pz_pairing_dev(self.ctx, VP(d_g1), VP(d_g2), n, VP(d_gt)), "pz_pairing_dev")
+
+    def pairing_check_dev(self, d_g1: int, d_g2: int, n_checks: int, pairs_per_check: int, d_ok: int):
+        """d_ok[i] (int32) = 1 if prod_j e(P_ij, Q_ij) == 1, 0 if not, -1 if an input is off its curve (device pointers)"""
+        self._chk(self.L.pz_pairing_check_dev(self.ctx, VP(d_g1), VP(d_g2), n_checks, pairs_per_check, VP(d_ok)),
+                  "pz_pairing_check_dev")
+
     def poly_eval_dev(self, d_coeffs: int, n_cols: int, col_stride_u64: int, n: int, x, d_out: int):
         self._chk(self.L.pz_poly_eval_dev(self.ctx, VP(d_coeffs), n_cols, col_stride_u64, n, _ptr(_np(x).reshape(4)),
                                           VP(d_out)), "pz_poly_eval_dev")

@@ -13,7 +13,8 @@ behaviour, SURVEY tag [D]; the reference ships no sample file, so the format is 
 RawBytes is exactly the C ABI's in-memory point layout (include/pz.h), so the point sections are handed to
 `pz_bases_load_g1` without conversion; `read` memory-maps them (a k = 26 file is 8.6 GB).  The reader checks
 sizes; on-curve validation of what it returns is `Engine.g1_check` (on the device), the analogue of the
-`is_on_curve` assertion inside halo2curves' `read_raw`.  G2 elements are opaque here (verifier side).
+`is_on_curve` assertion inside halo2curves' `read_raw`.  The G2 pair (g2, s_g2) is what a KZG verifier needs: `setup_g2`
+makes it for a toxic scalar as `ParamsKZG::setup` does; `paillier_halo2_amd.verifier` checks proofs against it.
 """
 from __future__ import annotations
 
@@ -41,6 +42,22 @@ class ParamsKZG:
 
 def file_size(k: int) -> int:
     return 4 + 2 * (64 << k) + 2 * G2_BYTES
+
+
+def setup_g2(eng, s) -> tuple:
+    """(g2, s_g2) of `ParamsKZG::setup` for the toxic scalar s (Fr Montgomery, 4 words: what `pz_srs_setup_g1_dev` takes), as the
+    128-byte RawBytes values `write_params_kzg` accepts: g2 = halo2curves' G2 generator (`pz_g2_generator`), s_g2 = [s] g2 computed
+    on the device (`pz_g2_mul_dev`)."""
+    g2 = eng.g2_generator()
+    d = eng.dev_alloc(2 * G2_BYTES + 32)
+    try:
+        eng.upload(d, g2)
+        eng.upload(d + G2_BYTES, np.ascontiguousarray(s, dtype=np.uint64).reshape(4))
+        eng.g2_mul_dev(d, d + G2_BYTES, 1, d + G2_BYTES + 32)
+        s_g2 = eng.download(d + G2_BYTES + 32, 16)
+    finally:
+        eng.dev_free(d)
+    return g2.astype("<u8").tobytes(), s_g2.astype("<u8").tobytes()
 
 
 def write_params_kzg(path: str, k: int, g, g_lagrange, g2: bytes = bytes(G2_BYTES), s_g2: bytes = bytes(G2_BYTES)) -> None:

@@ -1,0 +1,393 @@
+"""halo2's KZG / SHPLONK verifier for the proofs of this package, without the toxic scalar: the last step is a pairing check on the device.
+
+Per proof (what halo2-axiom's `verify_proof` does for these circuits [D]):
+  1. replay the Fiat-Shamir transcript (prover.HashTranscript's function) from the seed and the proof's own commitments and
+     evaluations: theta, beta, gamma, y, x, SHPLONK's y, v, u.  Nothing the prover recorded about its challenges is read.
+  2. h(x) (x^n - 1) == the constraint expression of the evaluations: the gates q (a + b c - d), the chunked permutation argument (delta
+     powers) and the lookups, restated here from the evaluations alone.
+  3. the h commitment sum_i x^(n i) [h_i] (three pieces).
+  4. SHPLONK's G1 terms A = L + z_0 u W2, B = -z_0 W2 with L = sum_k v^k z_k (sum_j y^j C_kj - [R_k(u)]) - Z_T(u) W1; the proof holds
+     iff e(A, [1]_2) e(B, [s]_2) == 1.
+
+verify_batch folds B proofs with random r_i (os.urandom) into sum r_i A_i, sum r_i B_i: ONE device MSM (K1, two scalar columns) over the
+key's fixed and sigma commitments (once, their scalars summed over the proofs), the generator and every proof's own commitments, then ONE
+2-pair pz_pairing_check_dev.  If that fails, or an identity of step 2 fails, the per-proof verdicts come from B independent checks in
+one pz_pairing_check_dev launch.  The transcript seed is the caller's bytes (not a digest of the verifying key).
+"""
+from __future__ import annotations
+
+import hashlib
+import os
+import struct
+from dataclasses import dataclass
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+
+from . import consts
+from .prover import CHUNK, DELTA, Domain, query_layout, rotation_points
+
+R = consts.FR_R
+H_PIECES = 3
+COMMITMENT_ROUNDS = ((("advice", "lookup_advice"), ("theta",)), (("perm_inputs", "perm_tables"), ("beta", "gamma")),
+                     (("perm_z", "lookup_z", "random"), ("y",)), (("h",), ("x",)))
+EVAL_FAMILIES = ("advice", "lookup_advice", "fixed", "sigma", "perm_z", "lookup_z", "perm_inputs", "perm_tables", "random")
+_MONT_INV = pow(consts.MONT_R, -1, R)
+
+
+@dataclass
+class VerifierParams:
+    """the verifier's side of ParamsKZG: g[0] (8 words), g2 and s_g2 (16 words each, Montgomery)"""
+    g0: np.ndarray
+    g2: np.ndarray
+    s_g2: np.ndarray
+
+    @classmethod
+    def from_parts(cls, g0, g2, s_g2) -> "VerifierParams":
+        w = lambda b: np.frombuffer(bytes(b), dtype="<u8").astype(np.uint64) if isinstance(b, (bytes, bytearray)) else \
+            np.ascontiguousarray(b, dtype=np.uint64).reshape(16)
+        p = cls(np.ascontiguousarray(g0, dtype=np.uint64).reshape(8), w(g2), w(s_g2))
+        if p.g2.shape != (16,) or p.s_g2.shape != (16,):
+            raise ValueError("g2 / s_g2 must be 16 words (128 RawBytes) each")
+        if not p.g2.any() or not p.s_g2.any():
+            raise ValueError("the params carry no G2 elements (g2 / s_g2 are zero): no KZG proof can be checked against them")
+        if not p.g0.any():
+            raise ValueError("g[0] is the identity")
+        return p
+
+    @classmethod
+    def from_params(cls, params) -> "VerifierParams":
+        """from srs.ParamsKZG (read_params_kzg)"""
+        return cls.from_parts(np.asarray(params.g[0]), params.g2, params.s_g2)
+
+
+@dataclass
+class VerifyingKey:
+    """the circuit's shape and the key's commitments (ProvingKey.vk_commitments(): fixed [n_adv + 2], sigma [m], affine)"""
+    k: int
+    blinding_factors: int
+    n_adv: int
+    n_lk: int
+    n_sets: int
+    fixed: np.ndarray
+    sigma: np.ndarray
+
+    @property
+    def m(self) -> int:
+        return self.n_adv + self.n_lk + 1
+
+    @classmethod
+    def from_proving_key(cls, pk) -> "VerifyingKey":
+        vk = pk.vk_commitments()
+        st = pk.st
+        return cls(st.k, st.blinding_factors, st.n_adv, st.n_lk, pk.n_sets, vk["fixed"], vk["sigma"])
+
+
+def _ints(a) -> List[List[int]]:
+    """(count, points, 4) Montgomery words -> canonical integers [[..]]"""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    rows = a.reshape(a.shape[0], -1, 4)
+    out = []
+    for row in rows:
+        vals = []
+        for w in row:
+            v = int(w[0]) | int(w[1]) << 64 | int(w[2]) << 128 | int(w[3]) << 192
+            vals.append(v * _MONT_INV % R)
+        out.append(vals)
+    return out
+
+
+def proof_from_record(rec: Dict[str, np.ndarray], prefix: str, vk: VerifyingKey):
+    """proof `prefix` ("p0/", ...) of a prover_job.read_proofs record -> (commitments, evals) in prover.Proof's shapes (the record's
+    lookup-advice evaluations carry the constants row last)"""
+    com = {k[len(prefix) + 2:]: np.asarray(v, dtype=np.uint64).reshape(-1, 8) for k, v in rec.items() if k.startswith(prefix + "c/")}
+    ev = {k[len(prefix) + 2:]: np.asarray(v, dtype=np.uint64).reshape(v.shape[0], -1, 4) for k, v in rec.items()
+          if k.startswith(prefix + "e/")}
+    if "lookup_advice" in ev:
+        ev["constants"] = ev["lookup_advice"][vk.n_lk:]
+        ev["lookup_advice"] = ev["lookup_advice"][:vk.n_lk]
+    return com, ev
+
+
+def record_seed(prefix: str) -> bytes:
+    """the compiled prover seeds proof `prefix` ("p<i>/")'s transcript with i as 8 little-endian bytes"""
+    return int(prefix[1:-1]).to_bytes(8, "little")
+
+
+def replay_transcript(seed: bytes, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarray]) -> Dict[str, int]:
+    h = hashlib.blake2b(bytes(seed), digest_size=64, person=b"Halo2-Transcript")
+    out: Dict[str, int] = {}
+
+    def items(tag, a, words):
+        a = np.ascontiguousarray(a, dtype="<u8").reshape(-1, words)
+        for row in a:
+            h.update(bytes([tag]) + struct.pack("<%dQ" % words, *(int(x) for x in row)))
+
+    def draw(name):
+        h.update(b"\x00")
+        out[name] = int.from_bytes(h.copy().digest(), "little") % R
+
+    for fams, names in COMMITMENT_ROUNDS:
+        for f in fams:
+            items(1, com[f], 8)
+        for nm in names:
+            draw(nm)
+    for f in EVAL_FAMILIES:
+        items(2, ev[f], 4)
+        if f == "lookup_advice" and "constants" in ev:
+            items(2, ev["constants"], 4)
+    draw("sh_y")
+    draw("sh_v")
+    items(1, com["w1"], 8)
+    draw("sh_u")
+    return out
+
+
+def _lagrange(k: int, bf: int, x: int) -> Tuple[int, int, int]:
+    """l_0(x), l_last(x), sum of the blinding rows' l_i(x)"""
+    n = 1 << k
+    w = consts.fr_omega(k)
+    xn1 = (pow(x, n, R) - 1) % R
+
+    def li(i):
+        wi = pow(w, i, R)
+        return xn1 * wi % R * pow(n * (x - wi) % R, -1, R) % R
+
+    u = n - (bf + 1)
+    return li(0), li(u), sum(li(i) for i in range(u + 1, n)) % R
+
+
+def constraint_expression(vk: VerifyingKey, e: Dict[str, List[List[int]]], beta: int, gamma: int, y: int, x: int) -> int:
+    """the constraint lines of these circuits at x folded by y (halo2's expressions in the order the prover folds them): equals
+    h(x) (x^n - 1) for an honest proof"""
+    A, Lk = vk.n_adv, vk.n_lk
+    l0, llast, lblind = _lagrange(vk.k, vk.blinding_factors, x)
+    lact = (1 - llast - lblind) % R
+    acc = 0
+
+    def line(v):
+        nonlocal acc
+        acc = (acc * y + v) % R
+
+    for j in range(A):                                   # q (a + b c - d) over four rows
+        a0, a1, a2, a3 = e["advice"][j]
+        line(e["fixed"][j][0] * (a0 + a1 * a2 - a3))
+    vals = [e["advice"][j][0] for j in range(A)] + [e["lookup_advice"][j][0] for j in range(Lk)] + [e["fixed"][A][0]]
+    m = len(vals)
+    S = -(-m // CHUNK)
+    z = e["perm_z"]
+    line(l0 * (1 - z[0][0]))
+    line(llast * (z[S - 1][0] * z[S - 1][0] - z[S - 1][0]))
+    for j in range(1, S):
+        line(l0 * (z[j][0] - z[j - 1][2]))
+    cur = beta * x % R
+    for j in range(S):
+        left, right = z[j][1], z[j][0]
+        for c in range(j * CHUNK, min(m, (j + 1) * CHUNK)):
+            left = left * (vals[c] + beta * e["sigma"][c][0] + gamma) % R
+            right = right * (vals[c] + cur + gamma) % R
+            cur = cur * DELTA % R
+        line(lact * (left - right))
+    tab = e["fixed"][A + 1][0]
+    for j in range(Lk):
+        a = e["lookup_advice"][j][0]
+        zx, zwx = e["lookup_z"][j]
+        ap, ap_prev = e["perm_inputs"][j]
+        sp = e["perm_tables"][j][0]
+        line(l0 * (1 - zx))
+        line(llast * (zx * zx - zx))
+        line(lact * (zwx * (ap + beta) % R * (sp + gamma) - zx * (a + beta) % R * (tab + gamma)))
+        line(l0 * (ap - sp))
+        line(lact * (ap - sp) % R * (ap - ap_prev))
+    return acc
+
+
+def _interp_eval(xs: Sequence[int], ys: Sequence[int], u: int) -> int:
+    """the interpolating polynomial of (xs, ys) at u (Lagrange form)"""
+    acc = 0
+    for i, xi in enumerate(xs):
+        num, den = 1, 1
+        for j, xj in enumerate(xs):
+            if j != i:
+                num = num * (u - xj) % R
+                den = den * (xi - xj) % R
+        acc = (acc + ys[i] * num * pow(den, -1, R)) % R
+    return acc
+
+
+@dataclass
+class _Terms:
+    ok: bool                      # transcript shape and the identity at x
+    vk_scalars: np.ndarray        # object array of ints: fixed (F) then sigma (m), coefficients of A
+    g_scalar: int                 # coefficient of g[0] in A
+    bases: np.ndarray             # (count, 8) the proof's own points
+    a_scalars: List[int]          # their coefficients in A
+    b_scalars: List[int]          # ... in B
+
+
+def _terms(vk: VerifyingKey, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarray], seed: bytes) -> _Terms:
+    A, Lk, m, S = vk.n_adv, vk.n_lk, vk.m, vk.n_sets
+    F = A + 2
+    shapes = {"advice": (A, 4), "lookup_advice": (Lk, 1), "fixed": (F, 1), "sigma": (m, 1), "perm_z": (S, 3), "lookup_z": (Lk, 2),
+              "perm_inputs": (Lk, 2), "perm_tables": (Lk, 1), "random": (1, 1)}
+    cshapes = {"advice": A, "lookup_advice": Lk, "perm_inputs": Lk, "perm_tables": Lk, "perm_z": S, "lookup_z": Lk, "random": 1,
+               "h": H_PIECES, "w1": 1, "w2": 1}
+    bad = _Terms(False, np.zeros(F + m, dtype=object), 0, np.zeros((0, 8), dtype=np.uint64), [], [])
+    try:
+        for f, (cnt, pts) in shapes.items():
+            if tuple(np.asarray(ev[f]).shape) != (cnt, pts, 4):
+                return bad
+        for f, cnt in cshapes.items():
+            if tuple(np.asarray(com[f]).shape) != (cnt, 8):
+                return bad
+    except KeyError:
+        return bad
+    ch = replay_transcript(seed, com, ev)
+    e = {f: _ints(ev[f]) for f in shapes}
+    x = ch["x"]
+    n = 1 << vk.k
+    xn = pow(x, n, R)
+    h_eval = constraint_expression(vk, e, ch["beta"], ch["gamma"], ch["y"], x) * pow(xn - 1, -1, R) % R
+    ok = True
+    if "h" in ev:                                          # a proof that states h(x) must state the expected one
+        ok = _ints(ev["h"]) == [[h_eval]]
+    e["h"] = [[h_eval]]
+    dom = Domain(vk.k, vk.blinding_factors)
+    points = rotation_points(dom, x)
+    sy, sv, su = ch["sh_y"], ch["sh_v"], ch["sh_u"]
+    zt = 1
+    for t in points:
+        zt = zt * (su - t) % R
+    vk_sc = np.zeros(F + m, dtype=object)
+    vk_sc[:] = 0
+    g_sc = 0
+    bases, a_sc, b_sc = [], [], []
+    z0 = None
+    for kk, (idx, members) in enumerate(query_layout(A, Lk, m, S)):
+        zk = 1
+        for t, pt in enumerate(points):
+            if t not in idx:
+                zk = zk * (su - pt) % R
+        if kk == 0:
+            z0 = zk
+        xs = [points[i] for i in idx]
+        folded = [sum(pow(sy, j, R) * e[f][i][q] for j, (f, i) in enumerate(members)) % R for q in range(len(xs))]
+        coef = pow(sv, kk, R) * zk % R
+        g_sc = (g_sc - coef * _interp_eval(xs, folded, su)) % R
+        for j, (f, i) in enumerate(members):
+            c = coef * pow(sy, j, R) % R
+            if f == "fixed":
+                vk_sc[i] = (vk_sc[i] + c) % R
+            elif f == "sigma":
+                vk_sc[F + i] = (vk_sc[F + i] + c) % R
+            elif f == "h":                                 # [h] = sum_i x^(n i) [h_i]
+                for p in range(H_PIECES):
+                    bases.append(com["h"][p])
+                    a_sc.append(c * pow(xn, p, R) % R)
+                    b_sc.append(0)
+            else:
+                bases.append(com[f][i])
+                a_sc.append(c)
+                b_sc.append(0)
+    bases.append(com["w1"][0])
+    a_sc.append((-zt) % R)
+    b_sc.append(0)
+    bases.append(com["w2"][0])
+    a_sc.append(z0 * su % R)
+    b_sc.append((-z0) % R)
+    return _Terms(ok, vk_sc, g_sc, np.stack([np.asarray(b, dtype=np.uint64).reshape(8) for b in bases]), a_sc, b_sc)
+
+
+def _mont(vals: Sequence[int]) -> np.ndarray:
+    out = np.zeros((len(vals), 4), dtype=np.uint64)
+    for i, v in enumerate(vals):
+        out[i] = consts.fr_mont_limbs(int(v))
+    return out
+
+
+def _fold_and_check(eng, params: VerifierParams, vk: VerifyingKey, terms: Sequence[_Terms], cols: Sequence[Sequence[int]]) -> List[int]:
+    """cols: per column of the MSM the weight of each proof (len(terms)) and whether it is the A or the B side -> pairing checks of
+    (A_c, B_c) pairs: column 2c is A, 2c + 1 is B; returns d_ok"""
+    F_m = len(terms[0].vk_scalars)
+    bases = np.concatenate([vk.fixed.reshape(-1, 8), vk.sigma.reshape(-1, 8), params.g0.reshape(1, 8)] + [t.bases for t in terms])
+    nb = bases.shape[0]
+    n_cols = len(cols)
+    sc = [[0] * nb for _ in range(n_cols)]
+    for c, (side, weights) in enumerate(cols):
+        row = sc[c]
+        off = F_m + 1
+        for t, wgt in zip(terms, weights):
+            if wgt:
+                if side == 0:
+                    for i in range(F_m):
+                        row[i] = (row[i] + wgt * t.vk_scalars[i]) % R
+                    row[F_m] = (row[F_m] + wgt * t.g_scalar) % R
+                src = t.a_scalars if side == 0 else t.b_scalars
+                for i, s in enumerate(src):
+                    row[off + i] = wgt * s % R
+            off += t.bases.shape[0]
+    scal = np.concatenate([_mont(r) for r in sc])
+    nbytes_b, nbytes_s = nb * 64, scal.nbytes
+    d = eng.dev_alloc(nbytes_b + nbytes_s + n_cols * 96 + n_cols * 64 + (n_cols // 2) * 2 * 128 + 4 * n_cols)
+    try:
+        d_b, d_s = d, d + nbytes_b
+        d_jac = d_s + nbytes_s
+        d_g1 = d_jac + n_cols * 96
+        d_g2 = d_g1 + n_cols * 64
+        d_ok = d_g2 + (n_cols // 2) * 2 * 128
+        eng.upload(d_b, bases)
+        eng.upload(d_s, scal)
+        tb = eng.load_bases_dev(d_b, nb)
+        try:
+            eng.msm_dev(tb, d_s, n_cols, nb, 4 * nb, d_jac)
+            aff = eng.g1_normalize(eng.download(d_jac, (n_cols, 12)))
+        finally:
+            tb.free()
+        n_checks = n_cols // 2
+        g2s = np.tile(np.concatenate([params.g2, params.s_g2]).reshape(1, 2, 16), (n_checks, 1, 1))
+        eng.upload(d_g1, np.ascontiguousarray(aff))
+        eng.upload(d_g2, g2s)
+        eng.pairing_check_dev(d_g1, d_g2, n_checks, 2, d_ok)
+        return [int(v) for v in eng.download(d_ok, n_checks, np.int32)]
+    finally:
+        eng.dev_free(d)
+
+
+def _as_parts(proof, vk: VerifyingKey):
+    if isinstance(proof, tuple):                      # (read_proofs record, "p<i>/")
+        return proof_from_record(proof[0], proof[1], vk)
+    return proof.commitments, proof.evals
+
+
+def verify_batch(eng, params: VerifierParams, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes]) -> Tuple[bool, List[bool]]:
+    """-> (every proof holds, per-proof verdicts).  proofs: prover.Proof objects or (prover_job.read_proofs record, "p<i>/") pairs; seeds:
+    the transcript seed of each (record_seed for the compiled prover's).  params: VerifierParams (or a srs.ParamsKZG, whose G2 elements must not be zero)."""
+    if not isinstance(params, VerifierParams):
+        params = VerifierParams.from_params(params)
+    assert len(proofs) == len(seeds) and len(proofs) > 0
+    terms = [_terms(vk, *_as_parts(p, vk), s) for p, s in zip(proofs, seeds)]
+    B = len(terms)
+    idents = [t.ok for t in terms]
+    live = [i for i in range(B) if terms[i].bases.shape[0]]
+    if not live:
+        return False, [False] * B
+    lt = [terms[i] for i in live]
+    if all(idents):
+        r = [int.from_bytes(os.urandom(32), "little") % R for _ in lt]
+        (ok,) = _fold_and_check(eng, params, vk, lt, [(0, r), (1, r)])
+        if ok == 1:
+            return True, [True] * B
+    # per proof: B independent checks in one launch
+    cols = []
+    for j in range(len(lt)):
+        w = [1 if q == j else 0 for q in range(len(lt))]
+        cols += [(0, w), (1, w)]
+    res = _fold_and_check(eng, params, vk, lt, cols)
+    per = [False] * B
+    for j, i in enumerate(live):
+        per[i] = idents[i] and res[j] == 1
+    return all(per), per
+
+
+def verify_proof(eng, params, vk: VerifyingKey, proof, seed: bytes) -> bool:
+    return verify_batch(eng, params, vk, [proof], [seed])[0]

@@ -153,6 +153,11 @@ extern "C" {
     pub fn pz_srs_setup_g1_dev(ctx: *mut pz_ctx, k: u32, s: *const u64, omega: *const u64, d_g: *mut u64,
                                d_g_lagrange: *mut u64) -> c_int;
     pub fn pz_g1_check_dev(ctx: *mut pz_ctx, d_points: *const u64, n: usize, n_bad: *mut u64) -> c_int;
+    pub fn pz_g2_generator(out: *mut u64) -> c_int;
+    pub fn pz_g2_mul_dev(ctx: *mut pz_ctx, d_g2: *const u64, d_scalars: *const u64, n: usize, d_out: *mut u64) -> c_int;
+    pub fn pz_pairing_dev(ctx: *mut pz_ctx, d_g1: *const u64, d_g2: *const u64, n: usize, d_gt: *mut u64) -> c_int;
+    pub fn pz_pairing_check_dev(ctx: *mut pz_ctx, d_g1: *const u64, d_g2: *const u64, n_checks: usize, pairs_per_check: u32,
+                                d_ok: *mut i32) -> c_int;
     pub fn pz_poly_eval_dev(ctx: *mut pz_ctx, d_coeffs: *const u64, n_cols: usize, col_stride: usize, n: usize,
                             x: *const u64, d_out: *mut u64) -> c_int;
     pub fn pz_poly_eval_multi_dev(ctx: *mut pz_ctx, d_coeffs: *const u64, n_cols: usize, col_stride: usize, n: usize,
