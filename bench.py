@@ -23,7 +23,10 @@ quotient evaluation, permutation/lookup product construction -- SURVEY.md sectio
 reference's Rust and is NOT in `value`; DESIGN.md section 6 says so next to the number.
 
 Contract: python bench.py --gpus N --steps K --warmup W ; for N>1 launched by torch.distributed.run,
-one rank per GPU, independent proofs per rank (weak scaling, no data-path collective).
+one rank per GPU, independent proofs per rank (weak scaling, no data-path collective).  Such a plain run of the connected line does
+what its headline needs and no more: setup, warm-up, the K timed proofs, --dump-outputs, the JSON line (verified: null).  `--full` adds
+everything else it measures or checks after the timed loop: the phase-by-phase proof, the checker leg, roofline_int (a digit count
+and a multiplier-issue probe of their own), the CPU baseline, and the fresh-message / compiled-prover / uniform-circuit / hot-path legs.
 `--workload msm22` instead times config c4: one 2^22-point MSM with Pippenger windows sharded over
 the ranks and an RCCL all-gather + fixed-order fold of the partial points.
 """
@@ -1531,10 +1534,10 @@ def connected_line(args, R):
                                            minimum_rows=args.minimum_rows, streamed_key=streamed, pipeline=pipeline, lookup_tile=lookup_tile)
     cnt = cw.counts()
     log("connected setup %.1fs: structure %s ms, keygen %.0f ms, %s" % (time.time() - t_all, {k_: round(v_) for k_, v_ in cw.structure_ms.items()}, cw.keygen_ms, cnt))
-    # digits K1 accumulates per proof (roofline_int): counted on the first witness, which the first proof then consumes
+    # digits K1 accumulates per proof (roofline_int, --full): counted on the first witness, which the first proof then consumes
     cw.produce()
     torch.cuda.synchronize()
-    digit_adds = count_digit_adds_cols(eng, torch, cw.slots[0], cw.A + cw.Lk, cw.n, cnt["msm_full"])
+    digit_adds = count_digit_adds_cols(eng, torch, cw.slots[0], cw.A + cw.Lk, cw.n, cnt["msm_full"]) if args.full else None
     cw.run(max(1, args.warmup), timed=False)      # (the first proof also grows the library's workspaces)
     barrier()
     engines = [eng] + ([cw.engw] if cw.engw is not eng else [])
@@ -1562,9 +1565,10 @@ def connected_line(args, R):
         return None
     if args.dump_outputs:       # the last timed proof (the next run replaces cw.last)
         log("dump-outputs: %d bytes of the last timed proof -> %s" % (dump_proof(args.dump_outputs, cw.last[0]), args.dump_outputs))
-    cw.run(1, timed=True)       # one more proof, synchronised phase by phase, OUTSIDE the timed region: where the time goes
+    if args.full:
+        cw.run(1, timed=True)   # one more proof, synchronised phase by phase, OUTSIDE the timed region: where the time goes
     ver, _cref = None, None
-    if not args.no_verify and not args.no_cpu_baseline:
+    if args.full and not args.no_verify and not args.no_cpu_baseline:
         from oracle import cref as _cref     # the checker leg (the one place bench.py may touch oracle/)
 
         _cref.build()
@@ -1619,15 +1623,9 @@ def connected_line(args, R):
             "note": "the connected loop's own k_msm_accumulate launches (HIP events on the library's stream): 32 B per scalar of every committed column + "
                     "64 B per base per launch; integer-multiply-issue bound by construction (v_mad_u64_u32) -- the HBM fraction is the metric's definition",
         },
-        "roofline_int": {
-            "bound": "v_mad_u64_u32 issue", "kernel": "k_msm_accumulate",
-            "achieved": (digit_adds * args.steps * MULT_PER_MADD / (acc_ms * 1e-3) / 1e12) if acc_ms > 0 else None,
-            "peak": mad_peak, "unit": "T multiplier instructions/s", "digit_adds_per_proof": digit_adds,
-            "multiplier_instructions_per_mixed_addition": MULT_PER_MADD,
-        },
         "breakdown_ms_per_proof": {"trace": trace_ms / args.steps, "expand": exp_ms / args.steps, "msm_all": msm_ms / args.steps,
                                    "msm_accumulate": acc_ms / args.steps, "ntt": ntt_ms / args.steps, "ntt_calls": ntt_n / args.steps},
-        "phases_ms_per_proof": cw.phase_ms(1), "counts": cnt, "memory_gb": cw.memory_gb,
+        "full": bool(args.full), "counts": cnt, "memory_gb": cw.memory_gb,
         "keygen_ms": cw.keygen_ms, "circuit_structure_ms": cw.structure_ms,
         "rccl_ranks": dist.get_world_size() if use_dist else 1, "backend": dist.get_backend() if use_dist else None,
     }
@@ -1637,13 +1635,21 @@ def connected_line(args, R):
         out["memory_gb"]["device_total"], out["memory_gb"]["device_free_after_timed_loop"] = total_b / 1e9, free_b / 1e9
     except Exception:
         pass
-    if out["roofline_int"]["achieved"]:
-        out["roofline_int"]["frac"] = out["roofline_int"]["achieved"] / mad_peak
+    if args.full:
+        out["roofline_int"] = {
+            "bound": "v_mad_u64_u32 issue", "kernel": "k_msm_accumulate",
+            "achieved": (digit_adds * args.steps * MULT_PER_MADD / (acc_ms * 1e-3) / 1e12) if acc_ms > 0 else None,
+            "peak": mad_peak, "unit": "T multiplier instructions/s", "digit_adds_per_proof": digit_adds,
+            "multiplier_instructions_per_mixed_addition": MULT_PER_MADD,
+        }
+        if out["roofline_int"]["achieved"]:
+            out["roofline_int"]["frac"] = out["roofline_int"]["achieved"] / mad_peak
+        out["phases_ms_per_proof"] = cw.phase_ms(1)
     out["config"]["env_switches"] = env_switches()
     if ver is not None and ver.get("verified") is False:
         out["comparable"] = False
     log("connected %.1fs: %.3f proofs/s (%.1f ms), verified %s" % (time.time() - t_all, value, dt / args.steps * 1e3, out["verified"]))
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         try:
             cc = dict(cnt)
             cc["n"] = n
@@ -1651,7 +1657,7 @@ def connected_line(args, R):
             out["cpu_baseline"].pop("checker", None)
         except Exception as ex:
             out["cpu_baseline"] = {"value": None, "error": repr(ex)}
-    extras = world == 1 and not args.headline_only and not os.environ.get("PZ_BENCH_SKIP")
+    extras = args.full and world == 1 and not args.headline_only and not os.environ.get("PZ_BENCH_SKIP")
     # ---- a NEW MESSAGE per proof with the reference's circuit: its bits are circuit structure (paillier.rs:50-55), so every step generates
     # the structure, runs keygen_vk + keygen_pk on its real selectors / sigma and then the connected proof.  The SRS is shared.
     if extras and headline_cfg and not args.no_fresh_key:
@@ -1847,7 +1853,10 @@ def main():
     ap.add_argument("--minimum-rows", type=int, default=20, help="the argument of halo2-lib's calculate_params: 20 on the reference's bench path "
                     "(bench.rs:161-171 -> bench_builder), 9 under MockProver (paillier.rs:167-171); fixes the column COUNT (layout.RowBudget)")
     ap.add_argument("--hot-path-headline", action="store_true", help="rounds 1-5's line: `value` = the hot path only (K3 + K4 + K1 + K2), not the connected proof")
-    ap.add_argument("--headline-only", action="store_true", help="the connected proof's timed loop, its check and the CPU baseline only (no fresh_message / "
+    ap.add_argument("--full", action="store_true", help="connected line: besides the headline (setup, warm-up, timed loop, --dump-outputs), everything "
+                    "else the benchmark measures or checks -- the phase-by-phase proof, the checker leg (verified), roofline_int, the CPU baseline "
+                    "and the fresh_message / compiled_prover / uniform circuit / hot_path_only legs; the --no-* and --headline-only switches trim it")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: the connected proof's timed loop, its check and the CPU baseline only (no fresh_message / "
                     "compiled_prover / uniform circuit / hot_path_only legs)")
     ap.add_argument("--no-hot-path", action="store_true", help="skip the hot_path_only leg")
     ap.add_argument("--full-hot-path", action="store_true", help="hot_path_only leg: also the C++ hot-path caller and the host-pointer binding")
@@ -1889,10 +1898,15 @@ def main():
 
     eng = pz.Engine(local)
     eng.bind_torch_stream()  # a real stream, current for torch too: the event waits of the pipeline order against it
-    # multiplier issue peak of this device, measured live (8 independent mads per lane and iteration)
-    from paillier_halo2_amd import probe   # libpz_probe.so: measurement only, outside the product ABI
+    # (--parallel columns splits ONE proof's hot-path columns over the ranks: a mode of the hot-path workload)
+    connected = args.workload in ("c2", "c2u", "c3", "c5") and not args.hot_path_headline and args.parallel != "columns"
+    # multiplier issue peak of this device, measured live (8 independent mads per lane and iteration); a plain connected run has no
+    # roofline_int to divide by it
+    mad_peak = None
+    if args.full or not connected:
+        from paillier_halo2_amd import probe   # libpz_probe.so: measurement only, outside the product ABI
 
-    mad_peak = max(8192 * 256 * 1024 * 8 / (probe.ubench_mad_indep(local, 8192, 1024) * 1e-3) / 1e12 for _ in range(3))
+        mad_peak = max(8192 * 256 * 1024 * 8 / (probe.ubench_mad_indep(local, 8192, 1024) * 1e-3) / 1e12 for _ in range(3))
 
     def barrier():
         torch.cuda.synchronize()
@@ -1939,8 +1953,7 @@ def main():
         return
 
     R = argparse.Namespace(rank=rank, world=world, local=local, use_dist=use_dist, log=log, eng=eng, mad_peak=mad_peak, barrier=barrier)
-    # (--parallel columns splits ONE proof's hot-path columns over the ranks: a mode of the hot-path workload)
-    if args.workload in ("c2", "c2u", "c3", "c5") and not args.hot_path_headline and args.parallel != "columns":
+    if connected:
         out = connected_line(args, R)
     else:
         out = hot_path_line(args, R)

@@ -26,7 +26,7 @@ SMALL = ["--enc-bits", "256", "--k", "13", "--steps", "3", "--warmup", "1"]
 
 
 def test_headline_line_small_shape(tmp_path):
-    d = _bench(SMALL + ["--headline-only", "--dump-outputs", str(tmp_path)])
+    d = _bench(SMALL + ["--full", "--headline-only", "--dump-outputs", str(tmp_path)])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
                 "roofline", "cpu_baseline"):
         assert key in d, key
@@ -73,10 +73,29 @@ def test_headline_line_through_the_rccl_group_of_one():
     assert d["value"] > 0 and d["config"]["scope"].startswith("one connected proof")
 
 
+def test_plain_line_is_the_headline_alone(tmp_path):
+    """without --full the line is the timed loop's alone: the contract's fields as a --full run states them, nothing measured or checked
+    after the loop, and --dump-outputs writes the same proof a --full run writes"""
+    plain, full = tmp_path / "plain", tmp_path / "full"
+    d = _bench(SMALL + ["--dump-outputs", str(plain)])
+    f = _bench(SMALL + ["--full", "--headline-only", "--no-cpu-baseline", "--dump-outputs", str(full)])
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data"):
+        assert d[key] == f[key], key
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6 and d["config"]["scope"] == f["config"]["scope"]
+    assert d["full"] is False and f["full"] is True and d["verified"] is None and d["roofline"]["launches"] == f["roofline"]["launches"]
+    for key in ("cpu_baseline", "roofline_int", "phases_ms_per_proof", "compiled_prover", "compiled_stepper"):
+        assert key not in d, key
+    import numpy as np
+
+    names = sorted(os.listdir(plain))
+    assert names and names == sorted(os.listdir(full))
+    assert all(np.array_equal(np.load(str(plain / nm)), np.load(str(full / nm))) for nm in names)
+
+
 def test_default_line_legs_small_shape():
-    """the default run's other legs are present for the headline configuration only; at a small custom shape the line still carries the
+    """a --full run's other legs are present for the headline configuration only; at a small custom shape the line still carries the
     compiled prover's figure (a child process over the C ABI) beside the headline"""
-    d = _bench(SMALL + ["--no-cpu-baseline"])
+    d = _bench(SMALL + ["--full", "--no-cpu-baseline"])
     assert "compiled_prover" in d and d["compiled_prover"]["quotient_degree_ok"] is True and d["compiled_prover"]["ms_per_step"] > 0
     assert d["compiled_stepper"]["quotient_degree_ok"] is True and "stepper" in d["compiled_stepper"]["via"]
     assert "hot_path_only" not in d and "fresh_message_cpp" not in d
@@ -85,7 +104,7 @@ def test_default_line_legs_small_shape():
 def test_c3_add_circuit_is_a_connected_line_too():
     """BASELINE config c3 (PaillierChip::add, /root/reference/src/paillier.rs:62-85 through bench.rs:77-117) as a connected proof: one key, distinct
     ciphertext pairs per proof, verified -- here at 256-bit / k = 12; `--hot-path-headline` keeps rounds 1-5's hot-path line"""
-    d = _bench(["--workload", "c3", "--enc-bits", "256", "--k", "12", "--steps", "3", "--warmup", "1", "--headline-only"])
+    d = _bench(["--workload", "c3", "--enc-bits", "256", "--k", "12", "--steps", "3", "--warmup", "1", "--full", "--headline-only"])
     assert d["verified"] is True and d["config"]["scope"].startswith("one connected proof") and "add" in d["metric"]
     assert d["config"]["mul_mod_steps"] == 1 and d["value"] > 0
     h = _bench(["--workload", "c3", "--enc-bits", "256", "--k", "12", "--steps", "3", "--warmup", "1", "--hot-path-headline", "--no-cpu-baseline", "--no-dropin",
