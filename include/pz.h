@@ -393,6 +393,33 @@ int pz_pairing_dev(pz_ctx* ctx, const uint64_t* d_g1, const uint64_t* d_g2, size
  * prod_j e(P_ij, Q_ij) == 1, 0 if not, -1 if any input of that check is off its curve or not canonical.  No subgroup check. */
 int pz_pairing_check_dev(pz_ctx* ctx, const uint64_t* d_g1, const uint64_t* d_g2, size_t n_checks, uint32_t pairs_per_check,
                          int32_t* d_ok);
+/* The device batch verifier (csrc/pz_verify.hip + pz_verify.cpp): halo2's KZG / SHPLONK verify_proof for the proofs of pz_proof_*, a
+ * batch at a time, with the same verdicts as paillier_halo2_amd/verifier.py::verify_batch.  No toxic scalar: the last step is
+ * pz_pairing_check_dev.
+ * pz_vk_create   the verifier's side of a key and its params, copied to the device once: the key's commitments fixed_affine
+ *                ((n_adv + 2) x 8, pz_pk_commitments' first array) and sigma_affine (m x 8, m = n_adv + n_lk + 1), g[0] of the params (8),
+ *                g2 and s_g2 (16 each, ParamsKZG RawBytes).  PZ_ERR_INVALID if g2 or s_g2 is zero, g[0] is the identity, n_adv or n_lk
+ *                is 0, k is outside 4..24 or blinding_factors + 2 > 2^k.  The key holds device memory of `ctx` (which must outlive it).
+ * pz_vk_info     a proof's words: commitment_words = 8 x (n_adv + 4 n_lk + n_sets + 6), evals_words = pz_pk_info's.
+ * pz_verify_batch  proofs: n_proofs x (commitment_words + evals_words) host words, each proof what the stepper hands back, in its phase
+ *                order: the commitments advice | lookup advice | A' | S' | permutation products | lookup products | random | h_0..h_2 |
+ *                W1 | W2, then pz_proof_evaluate's array (the constants row and the trailing h(x) included).  Proof i's transcript seed is
+ *                seeds[seed_offsets[i] .. seed_offsets[i + 1]) (n_proofs + 1 offsets; the caller's bytes, as prove_connected's 8-byte
+ *                little-endian index).  verdicts[i] = 1 if h(x) (x^n - 1) equals the constraint expression, the proof states that h(x),
+ *                evaluations are canonical and the opening's pairing check holds, else 0; *all_ok = every verdict is 1.
+ *                One fold with random weights (OS randomness) and one 2-pair check decide an all-good batch; otherwise (or when ab_affine
+ *                is asked for) n_proofs independent checks in one pz_pairing_check_dev launch give the verdicts.  Optional (NULL
+ *                allowed): h_evals n x 4 (the h(x) each proof implies, Montgomery), ab_affine n x 16 (each proof's SHPLONK points A then
+ *                B, unweighted).  A batch with bad proofs is PZ_OK; errors are malformed arguments and device failures only.  Host
+ *                pointers; synchronises.
+ * pz_vk_free     releases the key. */
+typedef struct pz_vk pz_vk;
+int pz_vk_create(pz_ctx* ctx, uint32_t k, uint32_t blinding_factors, size_t n_adv, size_t n_lk, const uint64_t* fixed_affine,
+                 const uint64_t* sigma_affine, const uint64_t g0_affine[8], const uint64_t g2[16], const uint64_t s_g2[16], pz_vk** out);
+int pz_vk_info(const pz_vk* vk, size_t* commitment_words, size_t* evals_words);
+int pz_verify_batch(pz_vk* vk, const uint64_t* proofs, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
+                    int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok);
+int pz_vk_free(pz_vk* vk);
 /* evaluation of n_cols coefficient-form polynomials (n coefficients each, device) at the point x:
  * d_out[col] = sum_i d_coeffs[col][i] * x^i   (the evals phase of create_proof / eval_polynomial). */
 int pz_poly_eval_dev(pz_ctx* ctx, const uint64_t* d_coeffs, size_t n_cols, size_t col_stride, size_t n,

@@ -92,6 +92,10 @@ SIGNATURES = {
     "pz_g2_mul_dev": (C.c_int, [VP, VP, VP, C.c_size_t, VP]),
     "pz_pairing_dev": (C.c_int, [VP, VP, VP, C.c_size_t, VP]),
     "pz_pairing_check_dev": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_uint32, VP]),
+    "pz_vk_create": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(VP)]),
+    "pz_vk_info": (C.c_int, [VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "pz_verify_batch": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(C.c_int)]),
+    "pz_vk_free": (C.c_int, [VP]),
     "pz_fr_batch_invert_dev": (C.c_int, [VP, VP, C.c_size_t]),
     "pz_fr_prefix_product_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP]),
     "pz_permutation_product_dev": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, C.c_size_t, C.c_uint32, VP, VP, VP, VP,

@@ -153,3 +153,26 @@ int pz_io_init(pz_ctx* ctx);
 int pz_upload_small_async(pz_ctx* ctx, void* d_dst, const void* src, size_t bytes);   // streams + events of the host-pointer pipelines; orders io_h2d after ctx->stream
 
 static inline unsigned pz_div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+// the device batch verifier (pz_verify.hip kernels, pz_verify.cpp orchestration).  Offsets in 4-word elements into a proof's
+// evaluation array (pz_proof_evaluate's), counts of a verifying key's shape; sets in verifier / prover.query_layout's order.
+#define PZ_VSETS_MAX 5
+struct pz_vshape {
+    uint32_t A, Lk, F, m, S;
+    uint32_t n_own;   // the proof's commitments = its own bases: A + 4 Lk + S + 6
+    uint32_t n_vkb;   // fixed | sigma | g0: F + m + 1
+    uint32_t n_ev;    // evaluation elements
+    uint32_t e_adv, e_lka, e_fix, e_sig, e_pz, e_lz, e_ap, e_sp, e_rnd, e_h;
+    uint32_t n_sets;
+    uint32_t set_start[PZ_VSETS_MAX], set_count[PZ_VSETS_MAX], set_npts[PZ_VSETS_MAX];
+};
+// a member of a query set: (evaluation element offset, destination); the destination's top two bits say which scalar array
+enum { PZ_VM_OWN = 0, PZ_VM_VK = 1, PZ_VM_H = 2 };
+// per-proof scalars the host derives after replaying the transcript (Montgomery, 4 words each)
+enum { VP_BETA = 0, VP_GAMMA, VP_Y, VP_BX, VP_L0, VP_LLAST, VP_LACT, VP_INV, VP_XN, VP_SY, VP_W1A, VP_W2A, VP_W2B, VP_COEF,
+       VP_LAG = VP_COEF + PZ_VSETS_MAX, VP_COUNT = VP_LAG + 4 * PZ_VSETS_MAX };
+int pz_verify_terms_launch(pz_ctx* ctx, const pz_vshape& s, size_t B, const uint32_t* d_members, const uint64_t* d_evals,
+                           const uint64_t* d_pp, const uint64_t* d_delta, uint64_t* d_h, int32_t* d_ident, uint64_t* d_own,
+                           uint64_t* d_vksc, uint64_t* d_gpart);
+int pz_verify_fold_launch(pz_ctx* ctx, const pz_vshape& s, size_t B, int mode, const uint64_t* d_r, uint64_t* d_vksc,
+                          const uint64_t* d_gpart, const uint64_t* d_own, uint64_t* d_cols);

@@ -47,6 +47,32 @@ class Bases:
             self.handle = None
 
 
+class VkHandle:
+    """A verifying key on the device (pz_vk): the key's commitments, g[0] and the G2 pair; frees itself."""
+
+    def __init__(self, engine: "Engine", handle: VP):
+        self.engine = engine
+        self.handle = handle
+        cw, ew = C.c_size_t(), C.c_size_t()
+        engine._chk(_lib.lib().pz_vk_info(handle, C.byref(cw), C.byref(ew)), "pz_vk_info")
+        self.commitment_words, self.evals_words = cw.value, ew.value
+
+    @property
+    def proof_words(self) -> int:
+        return self.commitment_words + self.evals_words
+
+    def free(self):
+        if self.handle is not None:
+            _lib.lib().pz_vk_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Engine:
     """One pz_ctx == one GPU (one process per GPU; ranks are joined by RCCL above this layer)."""
 
@@ -433,6 +459,35 @@ class Engine:
         """d_ok[i] (int32) = 1 if prod_j e(P_ij, Q_ij) == 1, 0 if not, -1 if an input is off its curve (device pointers)"""
         self._chk(self.L.pz_pairing_check_dev(self.ctx, VP(d_g1), VP(d_g2), n_checks, pairs_per_check, VP(d_ok)),
                   "pz_pairing_check_dev")
+
+    def vk_create(self, k: int, blinding_factors: int, n_adv: int, n_lk: int, fixed, sigma, g0, g2, s_g2) -> VkHandle:
+        """pz_vk_create: fixed (n_adv + 2, 8), sigma (m, 8), g0 (8), g2 / s_g2 (16 words or 128 RawBytes each)"""
+        w16 = lambda b: np.frombuffer(bytes(b), dtype="<u8").astype(np.uint64) if isinstance(b, (bytes, bytearray)) else _np(b).reshape(16)
+        f, sg, g, a, b = _np(fixed, 8), _np(sigma, 8), _np(g0).reshape(8), w16(g2), w16(s_g2)
+        if f.shape[0] != n_adv + 2 or sg.shape[0] != n_adv + n_lk + 1:
+            raise ValueError("fixed must hold n_adv + 2 points and sigma n_adv + n_lk + 1")
+        h = VP()
+        self._chk(self.L.pz_vk_create(self.ctx, k, blinding_factors, n_adv, n_lk, _ptr(f), _ptr(sg), _ptr(g), _ptr(a), _ptr(b), C.byref(h)),
+                  "pz_vk_create")
+        return VkHandle(self, h)
+
+    def verify_batch_dev(self, vk: VkHandle, proofs, seeds: Sequence[bytes], want_h: bool = False, want_ab: bool = False):
+        """pz_verify_batch: proofs (B, vk.proof_words) in the ABI layout -> (all_ok, verdicts [bool], h_evals (B, 4) or None,
+        ab_affine (B, 2, 8) or None)"""
+        pr = _np(proofs).reshape(-1, vk.proof_words)
+        B = pr.shape[0]
+        if len(seeds) != B:
+            raise ValueError("one seed per proof")
+        offs = np.zeros(B + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(sd) for sd in seeds])
+        blob = np.frombuffer(b"".join(bytes(sd) for sd in seeds) or b"\0", dtype=np.uint8)
+        verd = np.zeros(B, dtype=np.int32)
+        hev = np.zeros((B, 4), dtype=np.uint64) if want_h else None
+        ab = np.zeros((B, 2, 8), dtype=np.uint64) if want_ab else None
+        ok = C.c_int()
+        self._chk(self.L.pz_verify_batch(vk.handle, _ptr(pr), B, VP(blob.ctypes.data), _ptr(offs), VP(verd.ctypes.data),
+                                         _ptr(hev) if want_h else None, _ptr(ab) if want_ab else None, C.byref(ok)), "pz_verify_batch")
+        return bool(ok.value), [bool(v) for v in verd], hev, ab
 
     def poly_eval_dev(self, d_coeffs: int, n_cols: int, col_stride_u64: int, n: int, x, d_out: int):
         self._chk(self.L.pz_poly_eval_dev(self.ctx, VP(d_coeffs), n_cols, col_stride_u64, n, _ptr(_np(x).reshape(4)),

@@ -391,3 +391,59 @@ def verify_batch(eng, params: VerifierParams, vk: VerifyingKey, proofs: Sequence
 
 def verify_proof(eng, params, vk: VerifyingKey, proof, seed: bytes) -> bool:
     return verify_batch(eng, params, vk, [proof], [seed])[0]
+
+
+# ---- the device batch verifier (include/pz.h: pz_vk_create / pz_verify_batch): the same verdicts, Fr work in HIP ----------------------
+PROOF_COMMITMENTS = ("advice", "lookup_advice", "perm_inputs", "perm_tables", "perm_z", "lookup_z", "random", "h", "w1", "w2")
+PROOF_EVALS = ("advice", "lookup_advice", "constants", "fixed", "sigma", "perm_z", "lookup_z", "perm_inputs", "perm_tables", "random", "h")
+
+
+def native_key(eng, params, vk: VerifyingKey):
+    """-> engine.VkHandle of the key and the params' g[0], g2, s_g2 (pz_vk_create refuses zero G2 and an identity g[0])"""
+    if not isinstance(params, VerifierParams):
+        params = VerifierParams.from_params(params)
+    return eng.vk_create(vk.k, vk.blinding_factors, vk.n_adv, vk.n_lk, vk.fixed, vk.sigma, params.g0, params.g2, params.s_g2)
+
+
+def pack_proof(vk: VerifyingKey, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarray]):
+    """a proof's commitments and evaluations -> its words in pz_verify_batch's layout (the stepper's outputs in phase order), or None if a
+    family is missing or has the wrong shape"""
+    A, Lk, m, S = vk.n_adv, vk.n_lk, vk.m, vk.n_sets
+    cshapes = (A, Lk, Lk, Lk, S, Lk, 1, H_PIECES, 1, 1)
+    eshapes = ((A, 4), (Lk, 1), (1, 1), (A + 2, 1), (m, 1), (S, 3), (Lk, 2), (Lk, 2), (Lk, 1), (1, 1), (1, 1))
+    try:
+        parts = []
+        for f, cnt in zip(PROOF_COMMITMENTS, cshapes):
+            a = np.asarray(com[f], dtype=np.uint64)
+            if a.shape != (cnt, 8):
+                return None
+            parts.append(a.reshape(-1))
+        for f, (cnt, pts) in zip(PROOF_EVALS, eshapes):
+            a = np.asarray(ev[f], dtype=np.uint64)
+            if a.shape != (cnt, pts, 4):
+                return None
+            parts.append(a.reshape(-1))
+    except KeyError:
+        return None
+    return np.concatenate(parts)
+
+
+def verify_batch_native(eng, params, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes], handle=None) -> Tuple[bool, List[bool]]:
+    """verify_batch on the device batch verifier: the same arguments and (every proof holds, per-proof verdicts).  handle: a native_key
+    of (params, vk) to reuse; made and freed here otherwise."""
+    assert len(proofs) == len(seeds) and len(proofs) > 0
+    packed = [pack_proof(vk, *_as_parts(p, vk)) for p in proofs]
+    live = [i for i, w in enumerate(packed) if w is not None]
+    per = [False] * len(proofs)
+    if not live:
+        return False, per
+    own = handle is None
+    h = native_key(eng, params, vk) if own else handle
+    try:
+        _, got, _, _ = eng.verify_batch_dev(h, np.stack([packed[i] for i in live]), [seeds[i] for i in live])
+    finally:
+        if own:
+            h.free()
+    for i, v in zip(live, got):
+        per[i] = v
+    return all(per), per

@@ -15,6 +15,7 @@ use core::ffi::{c_char, c_int, c_void};
 #[repr(C)] pub struct pz_pk      { _p: [u8; 0] }
 #[repr(C)] pub struct pz_structure { _p: [u8; 0] }
 #[repr(C)] pub struct pz_proof   { _p: [u8; 0] }
+#[repr(C)] pub struct pz_vk      { _p: [u8; 0] }
 
 extern "C" {
     pub fn pz_init(n_devices: c_int, device_ids: *const c_int, out: *mut *mut pz_ctx) -> c_int;
@@ -158,6 +159,12 @@ extern "C" {
     pub fn pz_pairing_dev(ctx: *mut pz_ctx, d_g1: *const u64, d_g2: *const u64, n: usize, d_gt: *mut u64) -> c_int;
     pub fn pz_pairing_check_dev(ctx: *mut pz_ctx, d_g1: *const u64, d_g2: *const u64, n_checks: usize, pairs_per_check: u32,
                                 d_ok: *mut i32) -> c_int;
+    pub fn pz_vk_create(ctx: *mut pz_ctx, k: u32, blinding_factors: u32, n_adv: usize, n_lk: usize, fixed_affine: *const u64,
+                        sigma_affine: *const u64, g0_affine: *const u64, g2: *const u64, s_g2: *const u64, out: *mut *mut pz_vk) -> c_int;
+    pub fn pz_vk_info(vk: *const pz_vk, commitment_words: *mut usize, evals_words: *mut usize) -> c_int;
+    pub fn pz_verify_batch(vk: *mut pz_vk, proofs: *const u64, n_proofs: usize, seeds: *const u8, seed_offsets: *const usize,
+                           verdicts: *mut i32, h_evals: *mut u64, ab_affine: *mut u64, all_ok: *mut c_int) -> c_int;
+    pub fn pz_vk_free(vk: *mut pz_vk) -> c_int;
     pub fn pz_poly_eval_dev(ctx: *mut pz_ctx, d_coeffs: *const u64, n_cols: usize, col_stride: usize, n: usize,
                             x: *const u64, d_out: *mut u64) -> c_int;
     pub fn pz_poly_eval_multi_dev(ctx: *mut pz_ctx, d_coeffs: *const u64, n_cols: usize, col_stride: usize, n: usize,
