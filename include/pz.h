@@ -420,6 +420,35 @@ int pz_vk_info(const pz_vk* vk, size_t* commitment_words, size_t* evals_words);
 int pz_verify_batch(pz_vk* vk, const uint64_t* proofs, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
                     int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok);
 int pz_vk_free(pz_vk* vk);
+/* halo2 wire bytes (csrc/pz_wire.hip): what gen_proof returns and check_proof takes in the reference (bench.rs:173-178,
+ * a Vec<u8>), decoded and encoded on the device.  All integers little-endian.
+ *   G1 point, 32 bytes (halo2curves' G1Compressed [D]): the canonical (non-Montgomery) x; bit 7 of byte 31 = the parity of the canonical y;
+ *     bit 6 of byte 31 is 0 (x < p < 2^254); the identity is 32 zero bytes.  Decoding: y = (x^3 + 3)^((p+1)/4), accepted only if
+ *     y^2 = x^3 + 3, negated to the stated parity.  status: 0 ok, 1 not canonical (x >= p), 2 not on the curve; a refused point is written
+ *     as the identity.  No subgroup check (cofactor 1).
+ *   scalar, 32 bytes: the canonical value; a value >= r is refused (status 1).
+ *   proof: the transcript's absorption order -- the commitments of pz_verify_batch's layout WITHOUT W1 and W2 | pz_proof_evaluate's array
+ *     WITHOUT the trailing h(x) (halo2 does not send it; the verifier computes it) | W1 | W2:
+ *     32 x (commitment_words / 8 + evals_words / 4 - 1) bytes.
+ * pz_g1_compress_dev / pz_g1_decompress_dev   n points, device pointers (16-byte aligned), asynchronous on the context's stream.
+ * pz_g1_compress / pz_g1_decompress           host pointers, synchronise.  status (n) and n_bad (points with a status other than 0) may be NULL.
+ * pz_proof_wire_bytes     a proof's size on the wire.
+ * pz_proof_encode         n_proofs proofs in pz_verify_batch's word layout -> wire bytes (the h(x) slot is dropped).  Host pointers.
+ * pz_proof_decode         the reverse; the h(x) slot is written as zero; status[i] = the worst status of proof i's elements (its words are
+ *                         defined -- refused elements zero -- but must not be used when status[i] != 0).  Host pointers.
+ * pz_verify_batch_bytes   pz_verify_batch on n_proofs x pz_proof_wire_bytes bytes: the same verdicts as pz_verify_batch gives for the decoded
+ *                         proofs, but for the "proof states h(x)" test, which does not apply.  A proof that does not decode gets verdict 0
+ *                         (h_evals / ab_affine rows zero), the call stays PZ_OK, its points never reach the MSM and the other proofs are
+ *                         judged as if it were absent.  Every commitment that reaches the MSM is on the curve by construction. */
+int pz_g1_compress_dev(pz_ctx* ctx, const uint64_t* d_points, size_t n, uint8_t* d_bytes);
+int pz_g1_decompress_dev(pz_ctx* ctx, const uint8_t* d_bytes, size_t n, uint64_t* d_points, int32_t* d_status);
+int pz_g1_compress(pz_ctx* ctx, const uint64_t* points, size_t n, uint8_t* bytes);
+int pz_g1_decompress(pz_ctx* ctx, const uint8_t* bytes, size_t n, uint64_t* points, int32_t* status, uint64_t* n_bad);
+int pz_proof_wire_bytes(const pz_vk* vk, size_t* bytes);
+int pz_proof_encode(pz_vk* vk, const uint64_t* proofs_words, size_t n_proofs, uint8_t* out_bytes);
+int pz_proof_decode(pz_vk* vk, const uint8_t* bytes, size_t n_proofs, uint64_t* out_words, int32_t* status);
+int pz_verify_batch_bytes(pz_vk* vk, const uint8_t* bytes, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
+                          int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok);
 /* evaluation of n_cols coefficient-form polynomials (n coefficients each, device) at the point x:
  * d_out[col] = sum_i d_coeffs[col][i] * x^i   (the evals phase of create_proof / eval_polynomial). */
 int pz_poly_eval_dev(pz_ctx* ctx, const uint64_t* d_coeffs, size_t n_cols, size_t col_stride, size_t n,

@@ -96,6 +96,15 @@ SIGNATURES = {
     "pz_vk_info": (C.c_int, [VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "pz_verify_batch": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(C.c_int)]),
     "pz_vk_free": (C.c_int, [VP]),
+    # halo2 wire bytes (csrc/pz_wire.hip)
+    "pz_g1_compress_dev": (C.c_int, [VP, VP, C.c_size_t, VP]),
+    "pz_g1_decompress_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP]),
+    "pz_g1_compress": (C.c_int, [VP, VP, C.c_size_t, VP]),
+    "pz_g1_decompress": (C.c_int, [VP, VP, C.c_size_t, VP, VP, C.POINTER(C.c_uint64)]),
+    "pz_proof_wire_bytes": (C.c_int, [VP, C.POINTER(C.c_size_t)]),
+    "pz_proof_encode": (C.c_int, [VP, VP, C.c_size_t, VP]),
+    "pz_proof_decode": (C.c_int, [VP, VP, C.c_size_t, VP, VP]),
+    "pz_verify_batch_bytes": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(C.c_int)]),
     "pz_fr_batch_invert_dev": (C.c_int, [VP, VP, C.c_size_t]),
     "pz_fr_prefix_product_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP]),
     "pz_permutation_product_dev": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, C.c_size_t, C.c_uint32, VP, VP, VP, VP,

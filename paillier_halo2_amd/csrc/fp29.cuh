@@ -390,6 +390,29 @@ template <class T> __device__ __noinline__ F29<T> f29_inv(const F29<T>& a) {
     return acc;
 }
 
+// a^((p+1)/4) in the 261-domain: for p = 3 mod 4 (Fq; NOT Fr) the square root of a if a is a square, the root of -a otherwise --
+// the caller squares the candidate and compares (G1 decompression, pz_wire.hip).  252 exponent bits, 109 of them set; the same
+// shape as f29_inv: the exponent is a compile-time constant and a bit test drives the multiply, no per-lane table.
+template <class T> __device__ __noinline__ F29<T> f29_sqrt_candidate(const F29<T>& a) {
+    static_assert((P29<T>::P(0) & 3u) == 3u, "the (p+1)/4 root needs p = 3 mod 4");
+    F29<T> acc = f29_one<T>();
+    u32 e[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {   // (p + 1) >> 2; p[0] + 1 does not wrap (p[0] ends in ...11, not all ones)
+        const u32 lo = FieldParams<T>::P(i) + (i == 0 ? 1u : 0u), hi = i < 7 ? FieldParams<T>::P(i + 1) : 0u;
+        e[i] = (lo >> 2) | (hi << 30);
+    }
+    for (int i = 251; i >= 0; --i) {
+        acc = f29_sqr(acc);
+        u32 w = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (k == (i >> 5)) w = e[k];
+        if ((w >> (i & 31)) & 1) acc = f29_mul(acc, a);
+    }
+    return acc;
+}
+
 // A CONSTANT as f29_mulc takes it: c (the plain integer below p) and cq = floor(c * 2^261 / p), 9 + 9 limbs.  Built ONCE per table entry
 // from the Montgomery form t = c * 2^256 mod p the power tables hold (binary long division: 261 shift / compare / subtract steps).
 struct C18 {

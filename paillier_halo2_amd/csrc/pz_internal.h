@@ -176,3 +176,18 @@ int pz_verify_terms_launch(pz_ctx* ctx, const pz_vshape& s, size_t B, const uint
                            uint64_t* d_vksc, uint64_t* d_gpart);
 int pz_verify_fold_launch(pz_ctx* ctx, const pz_vshape& s, size_t B, int mode, const uint64_t* d_r, uint64_t* d_vksc,
                           const uint64_t* d_gpart, const uint64_t* d_own, uint64_t* d_cols);
+
+// halo2 wire bytes <-> words (pz_wire.hip).  Where element i of a launch lies: proof p = i / per, member j = i % per; its 32 wire bytes
+// at p * wire_stride + (j < split ? wire_off0 + 32 j : wire_off1 + 32 (j - split)), its words at p * word_stride + word_off + j * (its
+// size), its status at p * st_stride + st_off + j.  Byte offsets but for the status'.  skip_last: member per - 1 has no wire bytes.
+struct pz_wire_map {
+    size_t per, split;
+    size_t wire_stride, wire_off0, wire_off1;
+    size_t word_stride, word_off;
+    size_t st_stride, st_off;
+    int skip_last;
+};
+// a batch of B proofs between wire bytes (B x 32 (n_own + n_ev - 1)) and pz_verify_batch's words; decode fills d_elem_status
+// (B x (n_own + n_ev)) and d_status (B: each proof's worst element status).  Asynchronous on the context's stream.
+int pz_wire_proofs_launch(pz_ctx* ctx, const pz_vshape& s, size_t B, int decode, uint8_t* d_bytes, uint64_t* d_words, int32_t* d_elem_status,
+                          int32_t* d_status);

@@ -185,8 +185,10 @@ struct Replay {
     size_t inv0 = 0;   // its first entry in the batch's inversion list
 };
 
+// stated_h: the proofs carry h(x) as their last evaluation and must state the value the expression implies (pz_verify_batch); proofs that
+// came in as wire bytes do not send it (their slot is zero) and the comparison does not apply
 void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, const size_t* seed_off, int32_t* verdicts,
-            uint64_t* h_evals, uint64_t* ab_affine, int* all_ok) {
+            uint64_t* h_evals, uint64_t* ab_affine, int* all_ok, bool stated_h = true) {
     pz_ctx* ctx = vk->ctx;
     const pz_vshape& s = vk->s;
     const size_t cw = 8ull * s.n_own, ew = 4ull * s.n_ev, pw = cw + ew;
@@ -329,7 +331,7 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
     if (h_evals) memcpy(h_evals, hx.data(), B * 32);
     bool all_ident = true;
     for (size_t i = 0; i < B; ++i) {
-        good[i] = good[i] && ident[i] == 1;
+        good[i] = good[i] && (ident[i] == 1 || !stated_h);
         all_ident = all_ident && good[i];
     }
     uint32_t nwin = 0;
@@ -413,6 +415,29 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
     *all_ok = all;
 }
 
+// B proofs between host wire bytes and host words through the device codec (pz_wire.hip); decode also brings each proof's status back
+void wire_codec(pz_vk* vk, size_t B, bool decode, uint8_t* bytes, uint64_t* words, int32_t* status) {
+    pz_ctx* ctx = vk->ctx;
+    const pz_vshape& s = vk->s;
+    const size_t wire = 32ull * (s.n_own + s.n_ev - 1), pw = 8ull * s.n_own + 4ull * s.n_ev;
+    Dev d_bytes(ctx), d_words(ctx), d_st(ctx);
+    d_bytes.alloc(B * wire);
+    d_words.alloc(B * pw * 8);
+    d_st.alloc((B * (s.n_own + s.n_ev) + B) * 4);
+    int32_t* d_elem = d_st.p<int32_t>();
+    int32_t* d_proof = d_elem + B * (s.n_own + s.n_ev);
+    if (decode) {
+        ck(pz_upload(ctx, d_bytes.d, bytes, B * wire));
+        ck(pz_wire_proofs_launch(ctx, s, B, 1, d_bytes.p<uint8_t>(), d_words.p(), d_elem, d_proof));
+        ck(pz_download(ctx, words, d_words.d, B * pw * 8));
+        ck(pz_download(ctx, status, d_proof, B * 4));
+    } else {
+        ck(pz_upload(ctx, d_words.d, words, B * pw * 8));
+        ck(pz_wire_proofs_launch(ctx, s, B, 0, d_bytes.p<uint8_t>(), d_words.p(), nullptr, nullptr));
+        ck(pz_download(ctx, bytes, d_bytes.d, B * wire));
+    }
+}
+
 bool all_zero(const uint64_t* v, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (v[i]) return false;
@@ -488,6 +513,72 @@ extern "C" int pz_verify_batch(pz_vk* vk, const uint64_t* proofs, size_t n_proof
     *all_ok = 0;
     for (size_t i = 0; i < n_proofs; ++i) verdicts[i] = 0;
     return guarded([&] { verify(vk, proofs, n_proofs, seeds, seed_offsets, verdicts, h_evals, ab_affine, all_ok); });
+}
+
+extern "C" int pz_proof_wire_bytes(const pz_vk* vk, size_t* bytes) {
+    if (!vk || !bytes) return PZ_ERR_INVALID;
+    *bytes = 32ull * (vk->s.n_own + vk->s.n_ev - 1);
+    return PZ_OK;
+}
+
+extern "C" int pz_proof_encode(pz_vk* vk, const uint64_t* proofs_words, size_t n_proofs, uint8_t* out_bytes) {
+    if (!vk || !proofs_words || !n_proofs || !out_bytes) return PZ_ERR_INVALID;
+    if (n_proofs > (1u << 20)) return PZ_ERR_UNSUPPORTED;
+    pz_ctx* ctx = vk->ctx;
+    PZ_ENTER(ctx);
+    return guarded([&] { wire_codec(vk, n_proofs, false, out_bytes, const_cast<uint64_t*>(proofs_words), nullptr); });
+}
+
+extern "C" int pz_proof_decode(pz_vk* vk, const uint8_t* bytes, size_t n_proofs, uint64_t* out_words, int32_t* status) {
+    if (!vk || !bytes || !n_proofs || !out_words || !status) return PZ_ERR_INVALID;
+    if (n_proofs > (1u << 20)) return PZ_ERR_UNSUPPORTED;
+    pz_ctx* ctx = vk->ctx;
+    PZ_ENTER(ctx);
+    return guarded([&] { wire_codec(vk, n_proofs, true, const_cast<uint8_t*>(bytes), out_words, status); });
+}
+
+extern "C" int pz_verify_batch_bytes(pz_vk* vk, const uint8_t* bytes, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
+                                     int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok) {
+    if (!vk || !bytes || !n_proofs || !seed_offsets || !verdicts || !all_ok) return PZ_ERR_INVALID;
+    if (n_proofs > (1u << 20)) return PZ_ERR_UNSUPPORTED;
+    for (size_t i = 0; i < n_proofs; ++i)
+        if (seed_offsets[i + 1] < seed_offsets[i]) return PZ_ERR_INVALID;
+    if (seed_offsets[n_proofs] > seed_offsets[0] && !seeds) return PZ_ERR_INVALID;
+    pz_ctx* ctx = vk->ctx;
+    PZ_ENTER(ctx);
+    *all_ok = 0;
+    for (size_t i = 0; i < n_proofs; ++i) verdicts[i] = 0;
+    if (h_evals) memset(h_evals, 0, n_proofs * 32);
+    if (ab_affine) memset(ab_affine, 0, n_proofs * 128);
+    return guarded([&] {
+        const size_t pw = 8ull * vk->s.n_own + 4ull * vk->s.n_ev;
+        std::vector<uint64_t> words(n_proofs * pw);
+        std::vector<int32_t> st(n_proofs);
+        wire_codec(vk, n_proofs, true, const_cast<uint8_t*>(bytes), words.data(), st.data());
+        // the proofs that decoded, moved together with their seeds: a refused proof's words never reach verify()
+        std::vector<size_t> live, off(1, 0);
+        std::vector<uint8_t> sd;
+        for (size_t i = 0; i < n_proofs; ++i) {
+            if (st[i] != 0) continue;
+            if (live.size() != i) memmove(words.data() + live.size() * pw, words.data() + i * pw, pw * 8);
+            live.push_back(i);
+            if (seed_offsets[i + 1] > seed_offsets[i]) sd.insert(sd.end(), seeds + seed_offsets[i], seeds + seed_offsets[i + 1]);
+            off.push_back(sd.size());
+        }
+        const size_t L = live.size();
+        if (!L) return;
+        std::vector<int32_t> v(L, 0);
+        std::vector<uint64_t> hx(h_evals ? L * 4 : 0), ab(ab_affine ? L * 16 : 0);
+        int ok = 0;
+        verify(vk, words.data(), L, sd.data(), off.data(), v.data(), h_evals ? hx.data() : nullptr, ab_affine ? ab.data() : nullptr, &ok,
+               false);
+        for (size_t j = 0; j < L; ++j) {
+            verdicts[live[j]] = v[j];
+            if (h_evals) memcpy(h_evals + 4 * live[j], hx.data() + 4 * j, 32);
+            if (ab_affine) memcpy(ab_affine + 16 * live[j], ab.data() + 16 * j, 128);
+        }
+        *all_ok = ok && L == n_proofs;
+    });
 }
 
 extern "C" int pz_vk_free(pz_vk* vk) {

@@ -61,6 +61,13 @@ class VkHandle:
     def proof_words(self) -> int:
         return self.commitment_words + self.evals_words
 
+    @property
+    def wire_bytes(self) -> int:
+        """a proof's size as halo2 wire bytes (pz_proof_wire_bytes)"""
+        n = C.c_size_t()
+        self.engine._chk(_lib.lib().pz_proof_wire_bytes(self.handle, C.byref(n)), "pz_proof_wire_bytes")
+        return n.value
+
     def free(self):
         if self.handle is not None:
             _lib.lib().pz_vk_free(self.handle)
@@ -487,6 +494,65 @@ class Engine:
         ok = C.c_int()
         self._chk(self.L.pz_verify_batch(vk.handle, _ptr(pr), B, VP(blob.ctypes.data), _ptr(offs), VP(verd.ctypes.data),
                                          _ptr(hev) if want_h else None, _ptr(ab) if want_ab else None, C.byref(ok)), "pz_verify_batch")
+        return bool(ok.value), [bool(v) for v in verd], hev, ab
+
+    # ------------------------------------------------------------------ halo2 wire bytes (csrc/pz_wire.hip)
+    def g1_compress_dev(self, d_points: int, n: int, d_bytes: int):
+        self._chk(self.L.pz_g1_compress_dev(self.ctx, VP(d_points), n, VP(d_bytes)), "pz_g1_compress_dev")
+
+    def g1_decompress_dev(self, d_bytes: int, n: int, d_points: int, d_status: int):
+        self._chk(self.L.pz_g1_decompress_dev(self.ctx, VP(d_bytes), n, VP(d_points), VP(d_status)), "pz_g1_decompress_dev")
+
+    def g1_compress(self, points) -> np.ndarray:
+        """affine points (n, 8) -> (n, 32) uint8, halo2curves' compressed form"""
+        pts = _np(points, 8)
+        out = np.zeros((pts.shape[0], 32), dtype=np.uint8)
+        self._chk(self.L.pz_g1_compress(self.ctx, _ptr(pts), pts.shape[0], VP(out.ctypes.data)), "pz_g1_compress")
+        return out
+
+    def g1_decompress(self, data) -> Tuple[np.ndarray, np.ndarray]:
+        """n x 32 bytes -> (points (n, 8), status (n) int32: 0 ok, 1 not canonical, 2 not on the curve; a refused point is the identity)"""
+        b = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data,
+                                 dtype=np.uint8).reshape(-1, 32)
+        n = b.shape[0]
+        pts = np.zeros((n, 8), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.int32)
+        bad = C.c_uint64()
+        self._chk(self.L.pz_g1_decompress(self.ctx, VP(b.ctypes.data), n, _ptr(pts), VP(st.ctypes.data), C.byref(bad)), "pz_g1_decompress")
+        return pts, st
+
+    def proof_encode(self, vk: VkHandle, proofs) -> np.ndarray:
+        """pz_proof_encode: proofs (B, vk.proof_words) in pz_verify_batch's layout -> (B, vk.wire_bytes) uint8"""
+        pr = _np(proofs).reshape(-1, vk.proof_words)
+        out = np.zeros((pr.shape[0], vk.wire_bytes), dtype=np.uint8)
+        self._chk(self.L.pz_proof_encode(vk.handle, _ptr(pr), pr.shape[0], VP(out.ctypes.data)), "pz_proof_encode")
+        return out
+
+    def proof_decode(self, vk: VkHandle, data) -> Tuple[np.ndarray, np.ndarray]:
+        """pz_proof_decode: (B, vk.wire_bytes) uint8 -> (words (B, vk.proof_words), status (B) int32)"""
+        b = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1, vk.wire_bytes)
+        B = b.shape[0]
+        words = np.zeros((B, vk.proof_words), dtype=np.uint64)
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(self.L.pz_proof_decode(vk.handle, VP(b.ctypes.data), B, _ptr(words), VP(st.ctypes.data)), "pz_proof_decode")
+        return words, st
+
+    def verify_batch_bytes_dev(self, vk: VkHandle, data, seeds: Sequence[bytes], want_h: bool = False, want_ab: bool = False):
+        """pz_verify_batch_bytes: data (B, vk.wire_bytes) uint8 -> the tuple of verify_batch_dev"""
+        b = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1, vk.wire_bytes)
+        B = b.shape[0]
+        if len(seeds) != B:
+            raise ValueError("one seed per proof")
+        offs = np.zeros(B + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(sd) for sd in seeds])
+        blob = np.frombuffer(b"".join(bytes(sd) for sd in seeds) or b"\0", dtype=np.uint8)
+        verd = np.zeros(B, dtype=np.int32)
+        hev = np.zeros((B, 4), dtype=np.uint64) if want_h else None
+        ab = np.zeros((B, 2, 8), dtype=np.uint64) if want_ab else None
+        ok = C.c_int()
+        self._chk(self.L.pz_verify_batch_bytes(vk.handle, VP(b.ctypes.data), B, VP(blob.ctypes.data), _ptr(offs), VP(verd.ctypes.data),
+                                               _ptr(hev) if want_h else None, _ptr(ab) if want_ab else None, C.byref(ok)),
+                  "pz_verify_batch_bytes")
         return bool(ok.value), [bool(v) for v in verd], hev, ab
 
     def poly_eval_dev(self, d_coeffs: int, n_cols: int, col_stride_u64: int, n: int, x, d_out: int):

@@ -26,7 +26,14 @@
 //   pz_pk_create (the structure's host arrays, as halo2's Assembly would hand them over) and pz_proof_begin ... pz_proof_open_finish, one call
 //   per transcript round -- with the NEXT proof's witness written by a second host thread on a second context while the stepper runs
 //   (the two-context recipe of rust/pz-rt prove_pipelined).
+//
+// PZ_PROVE_WIRE=1 (job-file mode): ALSO write, next to the proof file, what a halo2 integrator exchanges (include/pz.h "halo2 wire bytes"):
+//   <proof file>.vk        the verifying key file: "PZVK", u32 version 1, k, blinding_factors, n_adv, n_lk, then the n_adv + 2 fixed and the
+//                          n_adv + n_lk + 1 sigma commitments compressed (pz_g1_compress)
+//   <proof file>.p<i>.bin  proof i as wire bytes (pz_proof_encode)
+//   host/verify_wire.cpp checks them.  The record file and stdout are the same with and without it.
 #include <chrono>
+#include <map>
 #include <thread>
 
 #include "create_proof.hpp"
@@ -320,8 +327,87 @@ static int stepper_main(Ctx& cx, int dev, Structure& st, const pz_bases* bl, con
     return degree_ok ? 0 : 1;
 }
 
+// PZ_PROVE_WIRE=1: the record file just written, again as a verifying key file and one file of wire bytes per proof
+static bool write_bytes(const std::string& path, const void* data, size_t n) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) { perror(path.c_str()); return false; }
+    const bool ok = fwrite(data, 1, n, f) == n;
+    return fclose(f) == 0 && ok;
+}
+
+static int write_wire_files(const char* job_path, const char* proof_path) {
+    uint64_t hdr[16];
+    FILE* jf = fopen(job_path, "rb");
+    if (!jf || fread(hdr, 8, 16, jf) != 16) { fprintf(stderr, "wire: job file\n"); return 2; }
+    fclose(jf);
+    const uint32_t k = (uint32_t)hdr[2], bf = (uint32_t)hdr[5], A = (uint32_t)hdr[6], Lk = (uint32_t)hdr[7];
+    const std::vector<uint64_t> w = slurp(proof_path);
+    std::map<std::string, std::vector<uint64_t>> rec;
+    for (size_t p = 0; p < w.size();) {
+        const uint64_t len = w[p++], nw = (len + 7) / 8;
+        if (len > 4096 || p + nw + 3 > w.size()) { fprintf(stderr, "wire: proof file\n"); return 2; }
+        const std::string name((const char*)(w.data() + p), len);
+        p += nw + 1;
+        const uint64_t count = w[p], per = w[p + 1];
+        p += 2;
+        if (per && count > (w.size() - p) / per) { fprintf(stderr, "wire: proof file\n"); return 2; }
+        rec[name].assign(w.begin() + p, w.begin() + p + count * per);
+        p += count * per;
+    }
+    const size_t F = A + 2, m = A + Lk + 1;
+    if (rec["vk/fixed"].size() != 8 * F || rec["vk/sigma"].size() != 8 * m) { fprintf(stderr, "wire: vk records\n"); return 2; }
+    pz_ctx* ctx = nullptr;
+    int dev = 0;
+    PZP_CK(pz_init(1, &dev, &ctx));
+    std::vector<uint64_t> pts = rec["vk/fixed"];
+    pts.insert(pts.end(), rec["vk/sigma"].begin(), rec["vk/sigma"].end());
+    std::vector<uint8_t> vkfile(24 + 32 * (F + m));
+    const uint32_t head[5] = {1, k, bf, A, Lk};
+    memcpy(vkfile.data(), "PZVK", 4);
+    memcpy(vkfile.data() + 4, head, 20);
+    PZP_CK(pz_g1_compress(ctx, pts.data(), F + m, vkfile.data() + 24));
+    if (!write_bytes(std::string(proof_path) + ".vk", vkfile.data(), vkfile.size())) return 2;
+    // the proof codec needs the key's shape only: the generators stand in for the params' g[0], g2, s_g2
+    uint64_t g1[8], g2[16];
+    PZP_CK(pz_g1_fixed_base_mul(ctx, pzh::FR_ONE.v, 1, g1));
+    PZP_CK(pz_g2_generator(g2));
+    pz_vk* vk = nullptr;
+    PZP_CK(pz_vk_create(ctx, k, bf, A, Lk, rec["vk/fixed"].data(), rec["vk/sigma"].data(), g1, g2, g2, &vk));
+    size_t cw = 0, ew = 0, wire = 0;
+    PZP_CK(pz_vk_info(vk, &cw, &ew));
+    PZP_CK(pz_proof_wire_bytes(vk, &wire));
+    static const char* const coms[10] = {"advice", "lookup_advice", "perm_inputs", "perm_tables", "perm_z", "lookup_z", "random", "h", "w1", "w2"};
+    static const char* const evs[10] = {"advice", "lookup_advice", "fixed", "sigma", "perm_z", "lookup_z", "perm_inputs", "perm_tables", "random", "h"};
+    for (size_t i = 0;; ++i) {
+        const std::string pre = "p" + std::to_string(i) + "/";
+        if (!rec.count(pre + "c/advice")) break;
+        std::vector<uint64_t> words;
+        for (const char* c : coms) words.insert(words.end(), rec[pre + "c/" + c].begin(), rec[pre + "c/" + c].end());
+        for (const char* e : evs) words.insert(words.end(), rec[pre + "e/" + e].begin(), rec[pre + "e/" + e].end());
+        if (words.size() != cw + ew) { fprintf(stderr, "wire: proof %zu does not have the key's shape\n", i); return 2; }
+        std::vector<uint8_t> bytes(wire);
+        PZP_CK(pz_proof_encode(vk, words.data(), 1, bytes.data()));
+        if (!write_bytes(std::string(proof_path) + ".p" + std::to_string(i) + ".bin", bytes.data(), bytes.size())) return 2;
+    }
+    pz_vk_free(vk);
+    pz_free(ctx);
+    return 0;
+}
+
+static int job_main(int argc, char** argv);
+
 int main(int argc, char** argv) {
     if (argc == 4 && !strcmp(argv[1], "--fresh")) return fresh_main(argv[2], argv[3]);
+    const int rc = job_main(argc, argv);
+    const char* we = getenv("PZ_PROVE_WIRE");
+    if (argc == 3 && (rc == 0 || rc == 1) && we && we[0] == '1') {
+        const int wrc = write_wire_files(argv[1], argv[2]);
+        if (wrc) return wrc;
+    }
+    return rc;
+}
+
+static int job_main(int argc, char** argv) {
     if (argc != 3) { fprintf(stderr, "usage: %s <job file> <proof file>  |  %s --fresh <params file> <proof file>\n", argv[0], argv[0]); return 2; }
     const std::vector<uint64_t> w = slurp(argv[1]);
     if (w.size() < 16 || w[0] != 0x435a50) { fprintf(stderr, "bad job file\n"); return 2; }

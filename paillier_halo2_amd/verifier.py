@@ -447,3 +447,118 @@ def verify_batch_native(eng, params, vk: VerifyingKey, proofs: Sequence, seeds: 
     for i, v in zip(live, got):
         per[i] = v
     return all(per), per
+
+
+# ---- halo2 wire bytes (include/pz.h: pz_g1_*compress, pz_proof_encode / decode, pz_verify_batch_bytes) ----------
+VK_MAGIC = b"PZVK"
+VK_VERSION = 1
+
+
+def _proof_shapes(vk: VerifyingKey):
+    A, Lk, m, S = vk.n_adv, vk.n_lk, vk.m, vk.n_sets
+    cshapes = (A, Lk, Lk, Lk, S, Lk, 1, H_PIECES, 1, 1)
+    eshapes = ((A, 4), (Lk, 1), (1, 1), (A + 2, 1), (m, 1), (S, 3), (Lk, 2), (Lk, 2), (Lk, 1), (1, 1), (1, 1))
+    return cshapes, eshapes
+
+
+def proof_size_bytes(vk: VerifyingKey) -> int:
+    """a proof as halo2 wire bytes: 32 per commitment and per evaluation; h(x) is not sent"""
+    cshapes, eshapes = _proof_shapes(vk)
+    return 32 * (sum(cshapes) + sum(c * p for c, p in eshapes) - 1)
+
+
+def _codec_key(eng, vk: VerifyingKey):
+    """a VkHandle for the proof codec alone: the wire layout depends on the key's shape only, so the generators stand in for the params"""
+    g1 = np.concatenate([consts.int_to_limbs(v * consts.MONT_R % consts.FQ_P, 4) for v in (1, 2)]).astype(np.uint64)
+    g2 = eng.g2_generator()
+    return eng.vk_create(vk.k, vk.blinding_factors, vk.n_adv, vk.n_lk, vk.fixed, vk.sigma, g1, g2, g2)
+
+
+def _with_key(eng, vk, handle, fn):
+    own = handle is None
+    h = _codec_key(eng, vk) if own else handle
+    try:
+        return fn(h)
+    finally:
+        if own:
+            h.free()
+
+
+def proof_to_bytes(eng, vk: VerifyingKey, proof, handle=None) -> bytes:
+    """a proof (prover.Proof or a (record, prefix) pair) -> its halo2 wire bytes, encoded on the device"""
+    com, ev = _as_parts(proof, vk)
+    ev = dict(ev)
+    ev.setdefault("h", np.zeros((1, 1, 4), dtype=np.uint64))      # not sent
+    words = pack_proof(vk, com, ev)
+    if words is None:
+        raise ValueError("the proof does not have the key's shape")
+    return _with_key(eng, vk, handle, lambda h: eng.proof_encode(h, words)[0].tobytes())
+
+
+def _unpack_words(vk: VerifyingKey, words: np.ndarray):
+    from .prover import Proof
+
+    cshapes, eshapes = _proof_shapes(vk)
+    com, ev, o = {}, {}, 0
+    for f, cnt in zip(PROOF_COMMITMENTS, cshapes):
+        com[f] = words[o:o + 8 * cnt].reshape(cnt, 8).copy()
+        o += 8 * cnt
+    for f, (cnt, pts) in zip(PROOF_EVALS, eshapes):
+        if f != "h":
+            ev[f] = words[o:o + 4 * cnt * pts].reshape(cnt, pts, 4).copy()
+        o += 4 * cnt * pts
+    return Proof(commitments=com, evals=ev)
+
+
+def proof_from_bytes(eng, vk: VerifyingKey, data: bytes, handle=None):
+    """halo2 wire bytes -> prover.Proof (its evals carry "constants" as a family of its own and no "h": the verifier computes h(x)).
+    ValueError if the length is wrong or an element does not decode."""
+    if len(data) != proof_size_bytes(vk):
+        raise ValueError("a proof of this key is %d bytes, got %d" % (proof_size_bytes(vk), len(data)))
+    words, st = _with_key(eng, vk, handle, lambda h: eng.proof_decode(h, np.frombuffer(bytes(data), dtype=np.uint8)))
+    if int(st[0]) != 0:
+        raise ValueError("the proof does not decode: %s" % ("an element is not canonical" if st[0] == 1 else "a point is not on the curve"))
+    return _unpack_words(vk, words[0])
+
+
+def vk_to_bytes(eng, vk: VerifyingKey) -> bytes:
+    """"PZVK", u32 version, k, blinding_factors, n_adv, n_lk, then the fixed and the sigma commitments compressed"""
+    pts = np.concatenate([np.asarray(vk.fixed, dtype=np.uint64).reshape(-1, 8), np.asarray(vk.sigma, dtype=np.uint64).reshape(-1, 8)])
+    if pts.shape[0] != 2 * vk.n_adv + vk.n_lk + 3:
+        raise ValueError("fixed must hold n_adv + 2 points and sigma n_adv + n_lk + 1")
+    return VK_MAGIC + struct.pack("<5I", VK_VERSION, vk.k, vk.blinding_factors, vk.n_adv, vk.n_lk) + eng.g1_compress(pts).tobytes()
+
+
+def vk_from_bytes(eng, data: bytes) -> VerifyingKey:
+    data = bytes(data)
+    if len(data) < 24 or data[:4] != VK_MAGIC:
+        raise ValueError("not a verifying key file")
+    ver, k, bf, A, Lk = struct.unpack("<5I", data[4:24])
+    if ver != VK_VERSION:
+        raise ValueError("verifying key file version %d" % ver)
+    n = 2 * A + Lk + 3
+    if len(data) != 24 + 32 * n:
+        raise ValueError("a key of this shape is %d bytes, got %d" % (24 + 32 * n, len(data)))
+    pts, st = eng.g1_decompress(data[24:])
+    if st.any():
+        raise ValueError("%d of the key's points do not decode" % int(np.count_nonzero(st)))
+    return VerifyingKey(k, bf, A, Lk, -(-(A + Lk + 1) // CHUNK), pts[:A + 2].copy(), pts[A + 2:].copy())
+
+
+def verify_batch_bytes(eng, params, vk: VerifyingKey, proofs: Sequence[bytes], seeds: Sequence[bytes], handle=None) -> Tuple[bool, List[bool]]:
+    """verify_batch for proofs that arrive as halo2 wire bytes (pz_verify_batch_bytes: decoded on the device; a proof that does not decode
+    is False and the others are judged without it).  ValueError if a proof's length is not proof_size_bytes(vk)."""
+    assert len(proofs) == len(seeds) and len(proofs) > 0
+    size = proof_size_bytes(vk)
+    for p in proofs:
+        if len(p) != size:
+            raise ValueError("a proof of this key is %d bytes, got %d" % (size, len(p)))
+    data = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8)
+    own = handle is None
+    h = native_key(eng, params, vk) if own else handle
+    try:
+        ok, per, _, _ = eng.verify_batch_bytes_dev(h, data, seeds)
+    finally:
+        if own:
+            h.free()
+    return ok, per

@@ -165,6 +165,15 @@ extern "C" {
     pub fn pz_verify_batch(vk: *mut pz_vk, proofs: *const u64, n_proofs: usize, seeds: *const u8, seed_offsets: *const usize,
                            verdicts: *mut i32, h_evals: *mut u64, ab_affine: *mut u64, all_ok: *mut c_int) -> c_int;
     pub fn pz_vk_free(vk: *mut pz_vk) -> c_int;
+    pub fn pz_g1_compress_dev(ctx: *mut pz_ctx, d_points: *const u64, n: usize, d_bytes: *mut u8) -> c_int;
+    pub fn pz_g1_decompress_dev(ctx: *mut pz_ctx, d_bytes: *const u8, n: usize, d_points: *mut u64, d_status: *mut i32) -> c_int;
+    pub fn pz_g1_compress(ctx: *mut pz_ctx, points: *const u64, n: usize, bytes: *mut u8) -> c_int;
+    pub fn pz_g1_decompress(ctx: *mut pz_ctx, bytes: *const u8, n: usize, points: *mut u64, status: *mut i32, n_bad: *mut u64) -> c_int;
+    pub fn pz_proof_wire_bytes(vk: *const pz_vk, bytes: *mut usize) -> c_int;
+    pub fn pz_proof_encode(vk: *mut pz_vk, proofs_words: *const u64, n_proofs: usize, out_bytes: *mut u8) -> c_int;
+    pub fn pz_proof_decode(vk: *mut pz_vk, bytes: *const u8, n_proofs: usize, out_words: *mut u64, status: *mut i32) -> c_int;
+    pub fn pz_verify_batch_bytes(vk: *mut pz_vk, bytes: *const u8, n_proofs: usize, seeds: *const u8, seed_offsets: *const usize,
+                                 verdicts: *mut i32, h_evals: *mut u64, ab_affine: *mut u64, all_ok: *mut c_int) -> c_int;
     pub fn pz_poly_eval_dev(ctx: *mut pz_ctx, d_coeffs: *const u64, n_cols: usize, col_stride: usize, n: usize,
                             x: *const u64, d_out: *mut u64) -> c_int;
     pub fn pz_poly_eval_multi_dev(ctx: *mut pz_ctx, d_coeffs: *const u64, n_cols: usize, col_stride: usize, n: usize,
