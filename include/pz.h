@@ -189,6 +189,15 @@ int pz_g1_fixed_base_mul(pz_ctx* ctx, const uint64_t* scalars, size_t n, uint64_
 /* device form of the same; out_affine is a device pointer */
 int pz_g1_fixed_base_mul_dev(pz_ctx* ctx, const uint64_t* d_scalars, size_t n, uint64_t* d_out_affine);
 
+/* Commitment of BYTE MASKS (csrc/pz_vkgen.hip): d_out_jac[col] = sum of P_i over the rows i < n where d_mask[col * mask_stride + i] != 0
+ * (any non-zero byte counts, as in pz_fr_from_mask_dev) -- commit_lagrange of a selector column, which halo2's Assembly holds as 0 / 1
+ * bytes, without widening it to 32-byte scalars and without the Pippenger sort: the set rows of a row chunk are compacted into a list
+ * and added as they are.  The group element equals pz_msm_g1_dev of the pz_fr_from_mask_dev columns (compare after pz_g1_normalize);
+ * repeated and cancelling bases are handled.  n <= n_points of the set; mask_stride in bytes, >= n; n_cols x 12 words out.  Device
+ * pointers, asynchronous on the context's stream. */
+int pz_g1_commit_mask_dev(pz_ctx* ctx, const pz_bases* bases, const uint8_t* d_mask, size_t n_cols, size_t n, size_t mask_stride,
+                          uint64_t* d_out_jac);
+
 /* ---------------------------------------------------------------------------------------------
  * K2 -- radix-2 NTT over Fr.  Replaces halo2curves `best_fft(a, omega, log_n)` reached from the
  * same call site through halo2-axiom EvaluationDomain::{ifft, fft, coeff_to_extended,
@@ -365,6 +374,12 @@ int pz_srs_lagrange_from_monomial_dev(pz_ctx* ctx, uint32_t k, const uint64_t om
  * synchronising entry point returns PZ_ERR_ASYNC). */
 int pz_permutation_sigma_dev(pz_ctx* ctx, const uint32_t* d_map_col, const uint32_t* d_map_row, size_t m, uint32_t k,
                              const uint64_t omega[4], const uint64_t delta[4], uint64_t* d_sigma, size_t sigma_stride);
+/* the same for the columns [col_lo, col_lo + n_cols) of an m_total-column permutation, written to d_sigma + (j - col_lo) * sigma_stride:
+ * sigma in tiles through one reusable buffer (pz_vk_keygen*).  d_map_col / d_map_row are those of the WHOLE permutation (m_total * 2^k
+ * entries each); images are checked against its m_total x 2^k cells, clamped and reported as PZ_ERR_ASYNC exactly as above. */
+int pz_permutation_sigma_part_dev(pz_ctx* ctx, const uint32_t* d_map_col, const uint32_t* d_map_row, size_t m_total, size_t col_lo,
+                                  size_t n_cols, uint32_t k, const uint64_t omega[4], const uint64_t delta[4], uint64_t* d_sigma,
+                                  size_t sigma_stride);
 /* keygen_vk + keygen_pk for n_cols Lagrange-form fixed columns (selectors, constants, table, sigma) on the device: their
  * commitments (commit_lagrange, n_cols x 12), then IN PLACE their coefficient form, and (d_ext != NULL) their values on the
  * extended coset (as pz_ntt_fr_extend_dev) -- the proving key's polynomials, resident in HBM for every later proof.
@@ -420,6 +435,23 @@ int pz_vk_info(const pz_vk* vk, size_t* commitment_words, size_t* evals_words);
 int pz_verify_batch(pz_vk* vk, const uint64_t* proofs, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
                     int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok);
 int pz_vk_free(pz_vk* vk);
+/* keygen_vk (csrc/pz_vk_keygen.cpp): the key's commitments from the circuit STRUCTURE alone -- halo2's keygen_vk, which the
+ * reference reaches at bench.rs:161-175 -- for a party that only verifies and will not trust a key file: no proving key is built, no transform
+ * runs, nothing stays resident.  Inputs as pz_pk_create[_dev] takes them (selectors u8 [n_adv][2^k], constants n_constants x 4 canonical words
+ * (host), map_col / map_row u32 [m][2^k], m = n_adv + n_lk + 1; the table column is 0 .. 2^lookup_bits - 1); outputs as pz_pk_commitments
+ * writes them (fixed_affine (n_adv + 2) x 8, sigma_affine m x 8, HOST), word for word what a key of pz_pk_create gives, so they go straight
+ * into pz_vk_create.  Selectors: pz_g1_commit_mask_dev; the constants and table columns: one small MSM; sigma: tiles of `tile` columns (0 = 64)
+ * through one buffer, pz_permutation_sigma_part_dev + pz_msm_g1_dev.  Device memory beyond the caller's arrays is O(tile 2^k) (at config c2,
+ * tile 64: 0.3 GB against the proving key's 116 + 30).  n_adv, n_lk >= 1; lookup_bits < k; 4 <= k <= 24; the bases cover 2^k points; an
+ * image outside the m x 2^k cells: PZ_ERR_ASYNC.  Synchronises.
+ * pz_vk_keygen_dev  selectors / map_col / map_row on the device (pz_circuit_structure_dev's arrays, or uploaded by the caller): only read.
+ * pz_vk_keygen      the same three in HOST memory, uploaded tile by tile. */
+int pz_vk_keygen_dev(pz_ctx* ctx, const pz_bases* bases_lagrange, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk,
+                     const uint8_t* d_selectors, const uint64_t* constants, size_t n_constants, const uint32_t* d_map_col,
+                     const uint32_t* d_map_row, size_t tile, uint64_t* fixed_affine, uint64_t* sigma_affine);
+int pz_vk_keygen(pz_ctx* ctx, const pz_bases* bases_lagrange, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk,
+                 const uint8_t* selectors, const uint64_t* constants, size_t n_constants, const uint32_t* map_col, const uint32_t* map_row,
+                 size_t tile, uint64_t* fixed_affine, uint64_t* sigma_affine);
 /* halo2 wire bytes (csrc/pz_wire.hip): what gen_proof returns and check_proof takes in the reference (bench.rs:173-178,
  * a Vec<u8>), decoded and encoded on the device.  All integers little-endian.
  *   G1 point, 32 bytes (halo2curves' G1Compressed [D]): the canonical (non-Montgomery) x; bit 7 of byte 31 = the parity of the canonical y;

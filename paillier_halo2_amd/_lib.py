@@ -47,6 +47,7 @@ SIGNATURES = {
     "pz_msm_g1": (C.c_int, [VP, VP, VP, C.c_size_t, VP]),
     "pz_msm_g1_batch": (C.c_int, [VP, VP, C.POINTER(VP), C.c_size_t, C.c_size_t, VP]),
     "pz_msm_g1_dev": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, VP]),
+    "pz_g1_commit_mask_dev": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, VP]),
     "pz_g1_sum": (C.c_int, [VP, VP, C.c_size_t, VP]),
     "pz_g1_sum_dev": (C.c_int, [VP, VP, C.c_size_t, VP]),
     "pz_msm_g1_multi": (C.c_int, [VP, VP, VP, VP, C.c_size_t, C.c_int, VP]),
@@ -84,6 +85,7 @@ SIGNATURES = {
     "pz_srs_setup_g1_dev": (C.c_int, [VP, C.c_uint32, VP, VP, VP, VP]),
     "pz_srs_lagrange_from_monomial_dev": (C.c_int, [VP, C.c_uint32, VP, VP, VP, VP]),
     "pz_permutation_sigma_dev": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_uint32, VP, VP, VP, C.c_size_t]),
+    "pz_permutation_sigma_part_dev": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, VP, VP, VP, C.c_size_t]),
     "pz_keygen_columns_dev": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, VP, VP, VP, VP, VP, VP, C.c_size_t]),
     "pz_poly_eval_dev": (C.c_int, [VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, VP, VP]),
     "pz_poly_eval_multi_dev": (C.c_int, [VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, VP, C.c_uint32, VP]),
@@ -96,6 +98,9 @@ SIGNATURES = {
     "pz_vk_info": (C.c_int, [VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "pz_verify_batch": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(C.c_int)]),
     "pz_vk_free": (C.c_int, [VP]),
+    # keygen_vk (csrc/pz_vk_keygen.cpp)
+    "pz_vk_keygen_dev": (C.c_int, [VP, VP, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, C.c_size_t, VP, VP, C.c_size_t, VP, VP]),
+    "pz_vk_keygen": (C.c_int, [VP, VP, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, C.c_size_t, VP, VP, C.c_size_t, VP, VP]),
     # halo2 wire bytes (csrc/pz_wire.hip)
     "pz_g1_compress_dev": (C.c_int, [VP, VP, C.c_size_t, VP]),
     "pz_g1_decompress_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP]),

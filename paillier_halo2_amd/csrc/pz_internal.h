@@ -152,6 +152,10 @@ int pz_io_init(pz_ctx* ctx);
 // pinned block of the context (ring of four; a block is reused only after the copy queued from it has completed)
 int pz_upload_small_async(pz_ctx* ctx, void* d_dst, const void* src, size_t bytes);   // streams + events of the host-pointer pipelines; orders io_h2d after ctx->stream
 
+// pz_permutation_sigma_part_dev for a range of columns given by its own part of the maps (pz_vkgen.hip; keygen_vk's host-pointer form)
+int pz_permutation_sigma_tile(pz_ctx* ctx, const uint32_t* d_mc, const uint32_t* d_mr, size_t m_total, size_t n_cols, uint32_t k,
+                              const uint64_t omega[4], const uint64_t delta[4], uint64_t* d_sigma, size_t sigma_stride);
+
 static inline unsigned pz_div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 // the device batch verifier (pz_verify.hip kernels, pz_verify.cpp orchestration).  Offsets in 4-word elements into a proof's

@@ -275,6 +275,10 @@ class Engine:
     def fr_convert_dev(self, d_a: int, n: int, to_mont: bool = True):
         self._chk(self.L.pz_fr_convert_dev(self.ctx, VP(d_a), n, int(to_mont)), "pz_fr_convert_dev")
 
+    def fr_from_mask_dev(self, d_mask: int, n: int, d_out: int):
+        """d_out[i] = d_mask[i] != 0 ? 1 : 0 (Montgomery), n elements (device pointers)"""
+        self._chk(self.L.pz_fr_from_mask_dev(self.ctx, VP(d_mask), n, VP(d_out)), "pz_fr_from_mask_dev")
+
     def paillier_encrypt_dev(self, limbs_n: int, n, g, m, r, d_steps: int, steps_cap: int):
         """steps stay on the device (d_steps: batch x steps_cap x 4 x 2*limbs_n u64). Returns (c, ng, nr)."""
         n, g, m, r = (_np(x).reshape(-1, limbs_n) for x in (n, g, m, r))
@@ -433,6 +437,50 @@ class Engine:
     def permutation_sigma_dev(self, d_map_col: int, d_map_row: int, m: int, k: int, omega, delta, d_sigma: int, sigma_stride_u64: int):
         self._chk(self.L.pz_permutation_sigma_dev(self.ctx, VP(d_map_col), VP(d_map_row), m, k, self._fr1(omega), self._fr1(delta),
                                                   VP(d_sigma), sigma_stride_u64), "pz_permutation_sigma_dev")
+
+    def permutation_sigma_part_dev(self, d_map_col: int, d_map_row: int, m_total: int, col_lo: int, n_cols: int, k: int, omega, delta,
+                                   d_sigma: int, sigma_stride_u64: int):
+        """columns [col_lo, col_lo + n_cols) of the m_total-column permutation (the map pointers are the whole permutation's)"""
+        self._chk(self.L.pz_permutation_sigma_part_dev(self.ctx, VP(d_map_col), VP(d_map_row), m_total, col_lo, n_cols, k, self._fr1(omega),
+                                                       self._fr1(delta), VP(d_sigma), sigma_stride_u64), "pz_permutation_sigma_part_dev")
+
+    def g1_commit_mask_dev(self, bases: Bases, d_mask: int, n_cols: int, n: int, mask_stride: int, d_out: int):
+        """d_out[col] (Jacobian, 12 words) = the sum of the bases at the rows where the column's mask byte is non-zero (device pointers)"""
+        self._chk(self.L.pz_g1_commit_mask_dev(self.ctx, bases.handle, VP(d_mask), n_cols, n, mask_stride, VP(d_out)), "pz_g1_commit_mask_dev")
+
+    def _vk_keygen(self, fn, name, bases_lagrange: Bases, k, lookup_bits, n_adv, n_lk, sel, constants, mc, mr, tile):
+        if isinstance(constants, np.ndarray) and constants.dtype == np.uint64 and constants.ndim == 2:
+            cw = np.ascontiguousarray(constants)
+        else:
+            cw = np.zeros((len(constants), 4), dtype=np.uint64)
+            for i, v in enumerate(constants):
+                v = int(v)
+                for j in range(4):
+                    cw[i, j] = (v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
+        m = n_adv + n_lk + 1
+        fixed, sigma = np.zeros((n_adv + 2, 8), dtype=np.uint64), np.zeros((m, 8), dtype=np.uint64)
+        self._chk(fn(self.ctx, bases_lagrange.handle, k, lookup_bits, n_adv, n_lk, VP(sel), _ptr(cw) if cw.size else VP(), cw.shape[0], VP(mc),
+                     VP(mr), tile, _ptr(fixed), _ptr(sigma)), name)
+        return fixed, sigma
+
+    def vk_keygen_dev(self, bases_lagrange: Bases, k: int, lookup_bits: int, n_adv: int, n_lk: int, d_selectors: int, constants,
+                      d_map_col: int, d_map_row: int, tile: int = 64) -> Tuple[np.ndarray, np.ndarray]:
+        """pz_vk_keygen_dev: the verifying key's commitments (fixed (n_adv + 2, 8), sigma (m, 8), affine) from the structure's DEVICE arrays;
+        constants: canonical integers (or their (n, 4) words)"""
+        return self._vk_keygen(self.L.pz_vk_keygen_dev, "pz_vk_keygen_dev", bases_lagrange, k, lookup_bits, n_adv, n_lk, d_selectors, constants,
+                               d_map_col, d_map_row, tile)
+
+    def vk_keygen(self, bases_lagrange: Bases, k: int, lookup_bits: int, n_adv: int, n_lk: int, selectors, constants, map_col, map_row,
+                  tile: int = 64) -> Tuple[np.ndarray, np.ndarray]:
+        """pz_vk_keygen: the same from HOST arrays (selectors uint8 [n_adv][2^k], map_col / map_row 32-bit [m][2^k]), uploaded tile by tile"""
+        n, m = 1 << k, n_adv + n_lk + 1
+        sel = np.ascontiguousarray(selectors, dtype=np.uint8)
+        mc = np.ascontiguousarray(map_col).view(np.uint32)
+        mr = np.ascontiguousarray(map_row).view(np.uint32)
+        if sel.shape != (n_adv, n) or mc.shape != (m, n) or mr.shape != (m, n):
+            raise ValueError("selectors must be [n_adv][2^k] bytes, map_col / map_row [m][2^k] 32-bit words")
+        return self._vk_keygen(self.L.pz_vk_keygen, "pz_vk_keygen", bases_lagrange, k, lookup_bits, n_adv, n_lk, sel.ctypes.data, constants,
+                               mc.ctypes.data, mr.ctypes.data, tile)
 
     def keygen_columns_dev(self, bases: Bases, d_cols: int, n_cols: int, col_stride_u64: int, k: int, log_e: int, omega_n, omega_n_inv,
                            n_inv, coset_gens, d_commit: int, d_ext: int = 0, ext_stride_u64: int = 0):

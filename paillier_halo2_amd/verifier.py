@@ -83,6 +83,35 @@ class VerifyingKey:
         return cls(st.k, st.blinding_factors, st.n_adv, st.n_lk, pk.n_sets, vk["fixed"], vk["sigma"])
 
 
+    @classmethod
+    def from_structure(cls, eng, st, bases_lagrange, tile: int = 64) -> "VerifyingKey":
+        """keygen_vk: the key from the circuit STRUCTURE alone (pz_vk_keygen[_dev]; no proving key is built, device memory O(tile 2^k)) --
+        the same object from_proving_key returns for a key made from `st`.  st: a CircuitStructure whose selectors / map_col / map_row
+        are torch tensors on the device (used where they are) or numpy arrays (uploaded tile by tile), or a NativeStructure (the device
+        arrays of a pz_circuit_structure_dev handle)."""
+        k, A, Lk = st.k, st.n_adv, st.n_lk
+        if hasattr(st, "d_selectors"):                      # a pz_structure handle's arrays
+            fixed, sigma = eng.vk_keygen_dev(bases_lagrange, k, st.lookup_bits, A, Lk, st.d_selectors, st.constants(), st.d_map_col,
+                                             st.d_map_row, tile)
+        else:
+            if getattr(st, "table", None) is not None:
+                raise ValueError("keygen_vk commits the table 0 .. 2^lookup_bits - 1; this structure carries another one")
+            consts_ = [int(v) % R for v in st.constants]
+            if hasattr(st.selectors, "is_cuda"):
+                import torch
+
+                sel = st.selectors.cuda().to(torch.uint8).contiguous()
+                mc, mr = st.map_col.cuda().to(torch.int32).contiguous(), st.map_row.cuda().to(torch.int32).contiguous()
+                if tuple(sel.shape) != (A, 1 << k) or tuple(mc.shape) != (A + Lk + 1, 1 << k) or mc.shape != mr.shape:
+                    raise ValueError("selectors must be [n_adv][2^k], map_col / map_row [m][2^k]")
+                torch.cuda.current_stream().synchronize()   # the conversions above may have run on another stream than the library's
+                fixed, sigma = eng.vk_keygen_dev(bases_lagrange, k, st.lookup_bits, A, Lk, sel.data_ptr(), consts_, mc.data_ptr(), mr.data_ptr(),
+                                                 tile)
+            else:
+                fixed, sigma = eng.vk_keygen(bases_lagrange, k, st.lookup_bits, A, Lk, st.selectors, consts_, st.map_col, st.map_row, tile)
+        return cls(k, st.blinding_factors, A, Lk, -(-(A + Lk + 1) // CHUNK), fixed, sigma)
+
+
 def _ints(a) -> List[List[int]]:
     """(count, points, 4) Montgomery words -> canonical integers [[..]]"""
     a = np.ascontiguousarray(a, dtype=np.uint64)

@@ -79,6 +79,8 @@ extern "C" {
                                       n_inv: *const u64, coset_gens: *const u64) -> c_int;
     pub fn pz_fr_convert_dev(ctx: *mut pz_ctx, d_a: *mut u64, n: usize, to_mont: c_int) -> c_int;
     pub fn pz_fr_from_mask_dev(ctx: *mut pz_ctx, d_mask: *const u8, n: usize, d_out: *mut u64) -> c_int;
+    pub fn pz_g1_commit_mask_dev(ctx: *mut pz_ctx, bases: *const pz_bases, d_mask: *const u8, n_cols: usize, n: usize,
+                                 mask_stride: usize, d_out_jac: *mut u64) -> c_int;
 
     // K3  (replaces num-bigint mul / div_rem inside BigUintChip::{mul_mod, pow_mod_fixed_exp})
     pub fn pz_mul_mod(ctx: *mut pz_ctx, limbs: u32, a: *const u64, b: *const u64, modulus: *const u64,
@@ -105,6 +107,9 @@ extern "C" {
                                              d_g: *const u64, d_g_lagrange: *mut u64) -> c_int;
     pub fn pz_permutation_sigma_dev(ctx: *mut pz_ctx, d_map_col: *const u32, d_map_row: *const u32, m: usize, k: u32,
                                     omega: *const u64, delta: *const u64, d_sigma: *mut u64, sigma_stride: usize) -> c_int;
+    pub fn pz_permutation_sigma_part_dev(ctx: *mut pz_ctx, d_map_col: *const u32, d_map_row: *const u32, m_total: usize,
+                                         col_lo: usize, n_cols: usize, k: u32, omega: *const u64, delta: *const u64,
+                                         d_sigma: *mut u64, sigma_stride: usize) -> c_int;
     pub fn pz_keygen_columns_dev(ctx: *mut pz_ctx, bases_lagrange: *const pz_bases, d_cols: *mut u64, n_cols: usize,
                                  col_stride: usize, k: u32, log_e: u32, omega_n: *const u64, omega_n_inv: *const u64,
                                  n_inv: *const u64, coset_gens: *const u64, d_commit_jac: *mut u64, d_ext: *mut u64,
@@ -165,6 +170,13 @@ extern "C" {
     pub fn pz_verify_batch(vk: *mut pz_vk, proofs: *const u64, n_proofs: usize, seeds: *const u8, seed_offsets: *const usize,
                            verdicts: *mut i32, h_evals: *mut u64, ab_affine: *mut u64, all_ok: *mut c_int) -> c_int;
     pub fn pz_vk_free(vk: *mut pz_vk) -> c_int;
+    // keygen_vk: the key's commitments from the circuit structure alone (no proving key)
+    pub fn pz_vk_keygen_dev(ctx: *mut pz_ctx, bases_lagrange: *const pz_bases, k: u32, lookup_bits: u32, n_adv: usize, n_lk: usize,
+                            d_selectors: *const u8, constants: *const u64, n_constants: usize, d_map_col: *const u32,
+                            d_map_row: *const u32, tile: usize, fixed_affine: *mut u64, sigma_affine: *mut u64) -> c_int;
+    pub fn pz_vk_keygen(ctx: *mut pz_ctx, bases_lagrange: *const pz_bases, k: u32, lookup_bits: u32, n_adv: usize, n_lk: usize,
+                        selectors: *const u8, constants: *const u64, n_constants: usize, map_col: *const u32, map_row: *const u32,
+                        tile: usize, fixed_affine: *mut u64, sigma_affine: *mut u64) -> c_int;
     pub fn pz_g1_compress_dev(ctx: *mut pz_ctx, d_points: *const u64, n: usize, d_bytes: *mut u8) -> c_int;
     pub fn pz_g1_decompress_dev(ctx: *mut pz_ctx, d_bytes: *const u8, n: usize, d_points: *mut u64, d_status: *mut i32) -> c_int;
     pub fn pz_g1_compress(ctx: *mut pz_ctx, points: *const u64, n: usize, bytes: *mut u8) -> c_int;
