@@ -481,6 +481,76 @@ int pz_proof_encode(pz_vk* vk, const uint64_t* proofs_words, size_t n_proofs, ui
 int pz_proof_decode(pz_vk* vk, const uint8_t* bytes, size_t n_proofs, uint64_t* out_words, int32_t* status);
 int pz_verify_batch_bytes(pz_vk* vk, const uint8_t* bytes, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
                           int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok);
+/* ParamsKZG files through the library (csrc/pz_params.hip + pz_params.cpp): halo2's ParamsKZG::{read_custom,
+ * write_custom, downsize} (the reference reaches them through gen_srs, bench.rs:161-171), every point decoded and checked on the device,
+ * plus a check that g, g_lagrange, g2 and s_g2 belong to ONE structured reference string.
+ *   G2 point, 64 bytes (halo2curves' G2Compressed [D], the convention of the G1 format above): bytes 0..31 the canonical x.c0, bytes 32..63
+ *     the canonical x.c1, both little-endian; bit 7 of byte 63 = the parity of the canonical y.c0; bit 6 of byte 63 is 0; the identity is 64
+ *     zero bytes.  Decoding: y = sqrt(x^3 + 3/(9 + u)) in Fq2 (the complex method over the (p+1)/4 root of Fq), accepted only if
+ *     y^2 equals it, negated to the stated parity.  status: 0 ok, 1 not canonical (c0 >= p or c1 >= p), 2 no twist point has this x; a
+ *     refused point is written as the identity.  y.c0 = 0: the two roots (0, +-y.c1) share the parity 0 and the format cannot tell them
+ *     apart; compression writes the bit 0, and decompression returns the root whose canonical y.c1 is EVEN whatever the bit says, so such
+ *     a point with an odd y.c1 comes back negated (no such point is known in the order-r subgroup; a file that holds one is refused by
+ *     pz_params_check's relation checks, not silently accepted).  No subgroup check in the codec: that is pz_g2_check.
+ *   pz_g2_check[_dev]  one status per point (16 words, int32): 0 in the order-r subgroup (the identity included), 1 not canonical, 2 off
+ *     the twist, 3 on the twist but [r]Q != O -- the twist's cofactor 2p - r is not 1 (it has the factors 10069 and 5864401), which is why
+ *     pz_pairing_check_dev's "no subgroup check" needs this in front of it for untrusted G2 input.  _dev: device pointers (16-byte
+ *     aligned), asynchronous; the others take host pointers and synchronise.  status / n_bad of pz_g2_decompress may be NULL.
+ *   file layouts (halo2's write_custom): u32 k | g[2^k] | g_lagrange[2^k] | g2 | s_g2, little-endian.  PZ_SERDE_RAW and
+ *     PZ_SERDE_RAW_UNCHECKED: points are this ABI's words (64 B G1, 128 B G2); PZ_SERDE_PROCESSED: the compressed forms (32 B, 64 B).
+ *   pz_params_file_bytes   the size of a file for k (1..28) in a format; no device work.
+ *   pz_params_decode   host bytes (may be a memory-mapped file) -> a params object on the device.  The G1 sections are uploaded in chunks
+ *     of a fixed number of points (PZ_PARAMS_CHUNK in the environment overrides it: tests) -- compressed points through ONE staging buffer
+ *     of a chunk, raw points straight to their place -- so a k = 26 file never has a second copy on the device.  PROCESSED and RAW check
+ *     every G1 point (its decompression status / pz_g1_check_dev) and that both G2 points are canonical and on the twist; any bad point:
+ *     PZ_ERR_INVALID, *n_bad (may be NULL) = their number, no object (halo2 panics there).  RAW_UNCHECKED checks sizes only.  A len that
+ *     is not pz_params_file_bytes of the header's k, or a k outside 1..28: PZ_ERR_INVALID (*n_bad = 0).
+ *   pz_params_from_dev  the same object from points already on the device (what pz_srs_setup_g1_dev and pz_g2_mul_dev produce): d_g and
+ *     d_g_lagrange (2^k affine points each) are COPIED; d_g_lagrange = NULL derives it (pz_srs_lagrange_from_monomial_dev).  g2, s_g2: host.
+ *   pz_params_info     k, g[0] (8 words), g2 and s_g2 (16 each): exactly what pz_vk_create takes.  Any output may be NULL.
+ *   pz_params_points   device pointers of g and g_lagrange, owned by the object (either may be NULL).
+ *   pz_params_bases    the window table of g (lagrange = 0) or g_lagrange (!= 0), built on the first request and owned by the object (do
+ *     not pz_bases_free it): MSMs over it equal those over pz_srs_load_g1 of the same points.
+ *   pz_params_encode   the object -> file bytes (host); PZ_ERR_CAPACITY if capacity < pz_params_file_bytes.  RAW_UNCHECKED writes what RAW
+ *     writes.
+ *   pz_params_downsize ParamsKZG::downsize: k_new <= k (else PZ_ERR_INVALID); g truncated, g_lagrange recomputed on the device for the
+ *     smaller domain, the G2 pair kept.  A new object.
+ *   pz_params_check    PZ_OK whatever the verdict (errors are device failures only).  *failed, bits:
+ *       PZ_PARAMS_BAD_G1        some point of g or g_lagrange is not canonical or off the curve
+ *       PZ_PARAMS_BAD_G2        g2 or s_g2 has a pz_g2_check status other than 0, or is the identity
+ *       PZ_PARAMS_BAD_G0        g[0] is the identity
+ *       PZ_PARAMS_BAD_POWERS    g is not a geometric sequence g[i+1] = [s] g[i] for the s of the G2 pair (s_g2 = [s] g2)
+ *       PZ_PARAMS_BAD_LAGRANGE  g_lagrange is not the Lagrange form of g over the 2^k domain
+ *     The three point checks always run.  POWERS and LAGRANGE run only if all three passed -- no unchecked point reaches an MSM or the
+ *     pairing -- and otherwise their bits are set in *skipped (may be NULL).  POWERS: with rho from OS randomness ONE 2-column MSM over g,
+ *     A = sum_{i<n-1} rho^i g[i] and -B = -sum_{i<n-1} rho^i g[i+1], then e(A, s_g2) e(-B, g2) == 1 (pz_pairing_check_dev).  LAGRANGE: with
+ *     tau, v_i = tau^i: MSM(g_lagrange, v) == MSM(g, iNTT(v)) after normalisation.  Each errs with probability about n / r.
+ *     What it does NOT prove: that nobody knows s.  A string that passes is well-formed for SOME s; whether that s was destroyed is a
+ *     matter of the ceremony that made the file, which no computation on the file can show. */
+typedef struct pz_params pz_params;
+#define PZ_SERDE_PROCESSED 0
+#define PZ_SERDE_RAW 1
+#define PZ_SERDE_RAW_UNCHECKED 2
+#define PZ_PARAMS_BAD_G1 1u
+#define PZ_PARAMS_BAD_G2 2u
+#define PZ_PARAMS_BAD_G0 4u
+#define PZ_PARAMS_BAD_POWERS 8u
+#define PZ_PARAMS_BAD_LAGRANGE 16u
+int pz_g2_compress(pz_ctx* ctx, const uint64_t* points, size_t n, uint8_t* bytes);
+int pz_g2_decompress(pz_ctx* ctx, const uint8_t* bytes, size_t n, uint64_t* points, int32_t* status, uint64_t* n_bad);
+int pz_g2_check_dev(pz_ctx* ctx, const uint64_t* d_points, size_t n, int32_t* d_status);
+int pz_g2_check(pz_ctx* ctx, const uint64_t* points, size_t n, int32_t* status);
+int pz_params_file_bytes(uint32_t k, int format, size_t* bytes);
+int pz_params_decode(pz_ctx* ctx, const uint8_t* bytes, size_t len, int format, pz_params** out, uint64_t* n_bad);
+int pz_params_from_dev(pz_ctx* ctx, uint32_t k, const uint64_t* d_g, const uint64_t* d_g_lagrange, const uint64_t g2[16],
+                       const uint64_t s_g2[16], pz_params** out);
+int pz_params_info(const pz_params* params, uint32_t* k, uint64_t g0_affine[8], uint64_t g2[16], uint64_t s_g2[16]);
+int pz_params_points(const pz_params* params, const uint64_t** d_g, const uint64_t** d_g_lagrange);
+int pz_params_bases(pz_params* params, int lagrange, const pz_bases** bases);
+int pz_params_encode(const pz_params* params, int format, uint8_t* out, size_t capacity);
+int pz_params_downsize(const pz_params* params, uint32_t k_new, pz_params** out);
+int pz_params_check(pz_params* params, uint32_t* failed, uint32_t* skipped);
+int pz_params_free(pz_params* params);
 /* evaluation of n_cols coefficient-form polynomials (n coefficients each, device) at the point x:
  * d_out[col] = sum_i d_coeffs[col][i] * x^i   (the evals phase of create_proof / eval_polynomial). */
 int pz_poly_eval_dev(pz_ctx* ctx, const uint64_t* d_coeffs, size_t n_cols, size_t col_stride, size_t n,

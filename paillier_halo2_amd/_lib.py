@@ -110,6 +110,21 @@ SIGNATURES = {
     "pz_proof_encode": (C.c_int, [VP, VP, C.c_size_t, VP]),
     "pz_proof_decode": (C.c_int, [VP, VP, C.c_size_t, VP, VP]),
     "pz_verify_batch_bytes": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(C.c_int)]),
+    # ParamsKZG files (csrc/pz_params.hip, pz_params.cpp)
+    "pz_g2_compress": (C.c_int, [VP, VP, C.c_size_t, VP]),
+    "pz_g2_decompress": (C.c_int, [VP, VP, C.c_size_t, VP, VP, C.POINTER(C.c_uint64)]),
+    "pz_g2_check_dev": (C.c_int, [VP, VP, C.c_size_t, VP]),
+    "pz_g2_check": (C.c_int, [VP, VP, C.c_size_t, VP]),
+    "pz_params_file_bytes": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_size_t)]),
+    "pz_params_decode": (C.c_int, [VP, VP, C.c_size_t, C.c_int, C.POINTER(VP), C.POINTER(C.c_uint64)]),
+    "pz_params_from_dev": (C.c_int, [VP, C.c_uint32, VP, VP, VP, VP, C.POINTER(VP)]),
+    "pz_params_info": (C.c_int, [VP, U32P, VP, VP, VP]),
+    "pz_params_points": (C.c_int, [VP, C.POINTER(VP), C.POINTER(VP)]),
+    "pz_params_bases": (C.c_int, [VP, C.c_int, C.POINTER(VP)]),
+    "pz_params_encode": (C.c_int, [VP, C.c_int, VP, C.c_size_t]),
+    "pz_params_downsize": (C.c_int, [VP, C.c_uint32, C.POINTER(VP)]),
+    "pz_params_check": (C.c_int, [VP, U32P, U32P]),
+    "pz_params_free": (C.c_int, [VP]),
     "pz_fr_batch_invert_dev": (C.c_int, [VP, VP, C.c_size_t]),
     "pz_fr_prefix_product_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP]),
     "pz_permutation_product_dev": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, C.c_size_t, C.c_uint32, VP, VP, VP, VP,
@@ -222,3 +237,15 @@ PZ_ERR_CAPACITY = -8
 PZ_ERR_MESSAGE_RANGE = -9
 PZ_ERR_ASYNC = -10
 PZ_ERR_INTERNAL = -11
+
+# ParamsKZG files: formats (halo2's SerdeFormat) and pz_params_check's verdict bits, mirrored from include/pz.h
+PZ_SERDE_PROCESSED = 0
+PZ_SERDE_RAW = 1
+PZ_SERDE_RAW_UNCHECKED = 2
+PZ_PARAMS_BAD_G1 = 1
+PZ_PARAMS_BAD_G2 = 2
+PZ_PARAMS_BAD_G0 = 4
+PZ_PARAMS_BAD_POWERS = 8
+PZ_PARAMS_BAD_LAGRANGE = 16
+PARAMS_CHECK_NAMES = {PZ_PARAMS_BAD_G1: "BAD_G1", PZ_PARAMS_BAD_G2: "BAD_G2", PZ_PARAMS_BAD_G0: "BAD_G0", PZ_PARAMS_BAD_POWERS: "BAD_POWERS",
+                      PZ_PARAMS_BAD_LAGRANGE: "BAD_LAGRANGE"}

@@ -156,6 +156,25 @@ int pz_upload_small_async(pz_ctx* ctx, void* d_dst, const void* src, size_t byte
 int pz_permutation_sigma_tile(pz_ctx* ctx, const uint32_t* d_mc, const uint32_t* d_mr, size_t m_total, size_t n_cols, uint32_t k,
                               const uint64_t omega[4], const uint64_t delta[4], uint64_t* d_sigma, size_t sigma_stride);
 
+// device buffers of one call of a host-composition entry point (pz_vk_keygen.cpp, pz_params.cpp), freed on every path out of it
+// (pz_dev_free waits for the queued work)
+struct pz_dev_bufs {
+    pz_ctx* c;
+    std::vector<void*> bufs;
+    explicit pz_dev_bufs(pz_ctx* c_) : c(c_) {}
+    int get(size_t bytes, void** out) {
+        *out = nullptr;
+        const int rc = pz_dev_alloc(c, bytes ? bytes : 1, out);
+        if (rc == PZ_OK) bufs.push_back(*out);
+        return rc;
+    }
+    ~pz_dev_bufs() {
+        for (void* d : bufs) pz_dev_free(c, d);
+    }
+};
+// n bytes of OS randomness (getrandom, /dev/urandom behind it): the verifier's fold weights, pz_params_check's rho and tau (pz_verify.cpp)
+bool pz_os_random(void* buf, size_t n);
+
 static inline unsigned pz_div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 // the device batch verifier (pz_verify.hip kernels, pz_verify.cpp orchestration).  Offsets in 4-word elements into a proof's

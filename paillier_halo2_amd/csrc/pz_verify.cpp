@@ -446,6 +446,8 @@ bool all_zero(const uint64_t* v, size_t n) {
 
 }  // namespace
 
+bool pz_os_random(void* buf, size_t n) { return os_random(buf, n); }
+
 extern "C" int pz_vk_create(pz_ctx* ctx, uint32_t k, uint32_t blinding_factors, size_t n_adv, size_t n_lk, const uint64_t* fixed_affine,
                             const uint64_t* sigma_affine, const uint64_t g0_affine[8], const uint64_t g2[16], const uint64_t s_g2[16],
                             pz_vk** out) {

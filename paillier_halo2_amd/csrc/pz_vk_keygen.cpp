@@ -11,21 +11,6 @@
 #include "pz_internal.h"
 
 namespace {
-struct DevBufs {   // device buffers of one call, freed on every path out of it (pz_dev_free waits for the queued work)
-    pz_ctx* c;
-    std::vector<void*> bufs;
-    explicit DevBufs(pz_ctx* c_) : c(c_) {}
-    int get(size_t bytes, void** out) {
-        *out = nullptr;
-        const int rc = pz_dev_alloc(c, bytes ? bytes : 1, out);
-        if (rc == PZ_OK) bufs.push_back(*out);
-        return rc;
-    }
-    ~DevBufs() {
-        for (void* d : bufs) pz_dev_free(c, d);
-    }
-};
-
 int vk_keygen(pz_ctx* ctx, const pz_bases* bl, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk, const uint8_t* selectors,
               const uint64_t* constants, size_t n_constants, const uint32_t* map_col, const uint32_t* map_row, size_t tile, bool on_device,
               uint64_t* fixed_affine, uint64_t* sigma_affine) {
@@ -41,7 +26,7 @@ int vk_keygen(pz_ctx* ctx, const pz_bases* bl, uint32_t k, uint32_t lookup_bits,
     if (tile > m) tile = m;
     PZ_ENTER(ctx);
     try {
-        DevBufs dev(ctx);
+        pz_dev_bufs dev(ctx);
         void *jac_f, *jac_s, *buf;
         PZCHK(dev.get(F * 96, &jac_f));
         PZCHK(dev.get(m * 96, &jac_s));

@@ -80,6 +80,78 @@ class VkHandle:
             pass
 
 
+class _BorrowedBases(Bases):
+    """a base table owned by a params object: valid while that object lives, not freed here"""
+
+    def __init__(self, engine: "Engine", handle: VP, owner):
+        super().__init__(engine, handle)
+        self.owner = owner
+
+    def free(self):
+        self.handle = None
+
+
+class ParamsHandle:
+    """A ParamsKZG on the device (pz_params): g, g_lagrange, the G2 pair and, on request, their window tables; frees itself."""
+
+    def __init__(self, engine: "Engine", handle: VP):
+        self.engine = engine
+        self.handle = handle
+        self._bases = {}
+        k = C.c_uint32()
+        engine._chk(_lib.lib().pz_params_info(handle, C.byref(k), None, None, None), "pz_params_info")
+        self.k = k.value
+
+    def info(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(g[0] (8 words), g2 (16), s_g2 (16)): what pz_vk_create takes"""
+        g0, g2, s_g2 = np.zeros(8, dtype=np.uint64), np.zeros(16, dtype=np.uint64), np.zeros(16, dtype=np.uint64)
+        self.engine._chk(_lib.lib().pz_params_info(self.handle, None, _ptr(g0), _ptr(g2), _ptr(s_g2)), "pz_params_info")
+        return g0, g2, s_g2
+
+    def points(self) -> Tuple[int, int]:
+        """device pointers of g and g_lagrange (2^k affine points each), owned by the object"""
+        a, b = VP(), VP()
+        self.engine._chk(_lib.lib().pz_params_points(self.handle, C.byref(a), C.byref(b)), "pz_params_points")
+        return a.value or 0, b.value or 0
+
+    def bases(self, lagrange: bool) -> Bases:
+        key = bool(lagrange)
+        if key not in self._bases:
+            h = VP()
+            self.engine._chk(_lib.lib().pz_params_bases(self.handle, int(key), C.byref(h)), "pz_params_bases")
+            self._bases[key] = _BorrowedBases(self.engine, h, self)
+        return self._bases[key]
+
+    def encode(self, fmt: int) -> np.ndarray:
+        out = np.zeros(self.engine.params_file_bytes(self.k, fmt), dtype=np.uint8)
+        self.engine._chk(_lib.lib().pz_params_encode(self.handle, fmt, VP(out.ctypes.data), out.size), "pz_params_encode")
+        return out
+
+    def downsize(self, k_new: int) -> "ParamsHandle":
+        h = VP()
+        self.engine._chk(_lib.lib().pz_params_downsize(self.handle, k_new, C.byref(h)), "pz_params_downsize")
+        return ParamsHandle(self.engine, h)
+
+    def check(self) -> Tuple[int, int]:
+        """(failed, skipped): pz_params_check's bit sets (PZ_PARAMS_BAD_*)"""
+        f, s = C.c_uint32(), C.c_uint32()
+        self.engine._chk(_lib.lib().pz_params_check(self.handle, C.byref(f), C.byref(s)), "pz_params_check")
+        return f.value, s.value
+
+    def free(self):
+        if self.handle is not None:
+            for b in self._bases.values():
+                b.free()
+            _lib.lib().pz_params_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Engine:
     """One pz_ctx == one GPU (one process per GPU; ranks are joined by RCCL above this layer)."""
 
@@ -602,6 +674,59 @@ class Engine:
                                                _ptr(hev) if want_h else None, _ptr(ab) if want_ab else None, C.byref(ok)),
                   "pz_verify_batch_bytes")
         return bool(ok.value), [bool(v) for v in verd], hev, ab
+
+    # ------------------------------------------------------------------ ParamsKZG files (csrc/pz_params.hip, pz_params.cpp)
+    def g2_compress(self, points) -> np.ndarray:
+        """G2 affine points (n, 16) -> (n, 64) uint8, halo2curves' compressed form"""
+        pts = _np(points, 16)
+        out = np.zeros((pts.shape[0], 64), dtype=np.uint8)
+        self._chk(self.L.pz_g2_compress(self.ctx, _ptr(pts), pts.shape[0], VP(out.ctypes.data)), "pz_g2_compress")
+        return out
+
+    def g2_decompress(self, data) -> Tuple[np.ndarray, np.ndarray]:
+        """n x 64 bytes -> (points (n, 16), status (n) int32: 0 ok, 1 not canonical, 2 no twist point has this x; refused = the identity)"""
+        b = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data,
+                                 dtype=np.uint8).reshape(-1, 64)
+        n = b.shape[0]
+        pts = np.zeros((n, 16), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.int32)
+        self._chk(self.L.pz_g2_decompress(self.ctx, VP(b.ctypes.data), n, _ptr(pts), VP(st.ctypes.data), None), "pz_g2_decompress")
+        return pts, st
+
+    def g2_check_dev(self, d_points: int, n: int, d_status: int):
+        self._chk(self.L.pz_g2_check_dev(self.ctx, VP(d_points), n, VP(d_status)), "pz_g2_check_dev")
+
+    def g2_check(self, points) -> np.ndarray:
+        """(n, 16) -> status (n) int32: 0 in the order-r subgroup, 1 not canonical, 2 off the twist, 3 on the twist but [r]Q != O"""
+        pts = _np(points, 16)
+        st = np.zeros(pts.shape[0], dtype=np.int32)
+        self._chk(self.L.pz_g2_check(self.ctx, _ptr(pts), pts.shape[0], VP(st.ctypes.data)), "pz_g2_check")
+        return st
+
+    def params_file_bytes(self, k: int, fmt: int) -> int:
+        n = C.c_size_t()
+        self._chk(self.L.pz_params_file_bytes(k, fmt, C.byref(n)), "pz_params_file_bytes")
+        return n.value
+
+    def params_decode(self, data, fmt: int) -> "ParamsHandle":
+        """pz_params_decode: file bytes (bytes, or a uint8 array such as a np.memmap) -> a params object on the device.  A refused
+        file raises PzError(PZ_ERR_INVALID) whose n_bad attribute is the number of bad points (0: a size or header problem)."""
+        b = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        h, bad = VP(), C.c_uint64()
+        rc = self.L.pz_params_decode(self.ctx, VP(b.ctypes.data), b.size, fmt, C.byref(h), C.byref(bad))
+        if rc != 0:
+            err = PzError(rc, "pz_params_decode", "%d bad points" % bad.value if bad.value else "")
+            err.n_bad = bad.value
+            raise err
+        return ParamsHandle(self, h)
+
+    def params_from_dev(self, k: int, d_g: int, d_g_lagrange: int, g2, s_g2) -> "ParamsHandle":
+        """pz_params_from_dev: 2^k device points each (copied; d_g_lagrange = 0 derives it); g2 / s_g2: 16 words or 128 RawBytes"""
+        w16 = lambda b: np.frombuffer(bytes(b), dtype="<u8").astype(np.uint64) if isinstance(b, (bytes, bytearray)) else _np(b).reshape(16)
+        a, b = w16(g2), w16(s_g2)
+        h = VP()
+        self._chk(self.L.pz_params_from_dev(self.ctx, k, VP(d_g), VP(d_g_lagrange), _ptr(a), _ptr(b), C.byref(h)), "pz_params_from_dev")
+        return ParamsHandle(self, h)
 
     def poly_eval_dev(self, d_coeffs: int, n_cols: int, col_stride_u64: int, n: int, x, d_out: int):
         self._chk(self.L.pz_poly_eval_dev(self.ctx, VP(d_coeffs), n_cols, col_stride_u64, n, _ptr(_np(x).reshape(4)),

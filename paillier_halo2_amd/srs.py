@@ -96,3 +96,87 @@ def read_params_kzg(path: str, expect_k: int | None = None) -> ParamsKZG:
     g = np.memmap(path, dtype="<u8", mode="r", offset=4, shape=(n, 8))
     gl = np.memmap(path, dtype="<u8", mode="r", offset=4 + 64 * n, shape=(n, 8))
     return ParamsKZG(k, g, gl, g2, s_g2)
+
+
+# ---- the params file through the library (include/pz.h: pz_params_*) ------------------------------------------
+# Everything above reads and writes RawBytes in Python and trusts what it reads.  The functions below hand the file's bytes to the C ABI:
+# every point is decoded and checked on the device, SerdeFormat::Processed files are read and written too, and Params.check() says whether
+# g, g_lagrange, g2 and s_g2 belong to one structured reference string.
+FORMAT_NAMES = {"processed": 0, "raw": 1, "raw_unchecked": 2}   # halo2's SerdeFormat; the values are include/pz.h's PZ_SERDE_*
+
+
+def _format(fmt) -> int:
+    if isinstance(fmt, str):
+        if fmt.lower() not in FORMAT_NAMES:
+            raise ValueError("format: processed | raw | raw_unchecked")
+        return FORMAT_NAMES[fmt.lower()]
+    if fmt not in FORMAT_NAMES.values():
+        raise ValueError("format: 0 (processed), 1 (raw) or 2 (raw_unchecked)")
+    return int(fmt)
+
+
+class Params:
+    """A ParamsKZG held by the library on the device (engine.ParamsHandle) with halo2's operations on it."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    @property
+    def k(self) -> int:
+        return self.handle.k
+
+    @classmethod
+    def from_dev(cls, eng, k: int, d_g: int, d_g_lagrange: int, g2, s_g2) -> "Params":
+        """from pz_srs_setup_g1_dev's device points and setup_g2's pair (d_g_lagrange = 0: derived from g on the device)"""
+        return cls(eng.params_from_dev(k, d_g, d_g_lagrange, g2, s_g2))
+
+    def check(self):
+        """-> (failed, skipped): sets of the names BAD_G1, BAD_G2, BAD_G0, BAD_POWERS, BAD_LAGRANGE.  An empty `failed` means the four
+        sections form one well-formed SRS for some s -- not that nobody knows s."""
+        from ._lib import PARAMS_CHECK_NAMES
+
+        f, s = self.handle.check()
+        names = lambda bits: {n for b, n in PARAMS_CHECK_NAMES.items() if bits & b}
+        return names(f), names(s)
+
+    def downsize(self, k: int) -> "Params":
+        """ParamsKZG::downsize: the first 2^k powers, g_lagrange recomputed for the smaller domain, the G2 pair kept"""
+        return Params(self.handle.downsize(k))
+
+    def write(self, path: str, fmt="raw") -> None:
+        """ParamsKZG::write_custom"""
+        data = self.handle.encode(_format(fmt))
+        with open(path, "wb") as f:
+            f.write(data.tobytes())
+
+    def bases(self, lagrange: bool):
+        """the window table of g (False) or g_lagrange (True) for the MSM entry points; owned by this object"""
+        return self.handle.bases(lagrange)
+
+    def verifier_params(self):
+        from .verifier import VerifierParams
+
+        return VerifierParams.from_parts(*self.handle.info())
+
+    def free(self):
+        self.handle.free()
+
+
+def load_params(eng, path: str, fmt=None) -> Params:
+    """ParamsKZG::read_custom through the C ABI: the file is memory-mapped and decoded on the device chunk by chunk; in the formats
+    "processed" and "raw" every point is checked and a bad one raises PzError (its n_bad = how many).  fmt = None takes the format from
+    the file's size, which is unambiguous for the k in its header ("raw" for a RawBytes file: pass "raw_unchecked" to skip the checks)."""
+    size = os.path.getsize(path)
+    if size < 4:
+        raise ValueError("truncated ParamsKZG file (no header)")
+    with open(path, "rb") as f:
+        (k,) = struct.unpack("<I", f.read(4))
+    if fmt is None:
+        if not 1 <= k <= 28:
+            raise ValueError("implausible k = %d in ParamsKZG header" % k)
+        sizes = {eng.params_file_bytes(k, v): v for v in (FORMAT_NAMES["processed"], FORMAT_NAMES["raw"])}
+        if size not in sizes:
+            raise ValueError("ParamsKZG file for k = %d must be %s bytes, found %d" % (k, " or ".join(str(b) for b in sorted(sizes)), size))
+        fmt = sizes[size]
+    data = np.memmap(path, dtype=np.uint8, mode="r")
+    return Params(eng.params_decode(data, _format(fmt)))

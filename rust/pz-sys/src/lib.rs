@@ -16,6 +16,7 @@ use core::ffi::{c_char, c_int, c_void};
 #[repr(C)] pub struct pz_structure { _p: [u8; 0] }
 #[repr(C)] pub struct pz_proof   { _p: [u8; 0] }
 #[repr(C)] pub struct pz_vk      { _p: [u8; 0] }
+#[repr(C)] pub struct pz_params  { _p: [u8; 0] }
 
 extern "C" {
     pub fn pz_init(n_devices: c_int, device_ids: *const c_int, out: *mut *mut pz_ctx) -> c_int;
@@ -186,6 +187,22 @@ extern "C" {
     pub fn pz_proof_decode(vk: *mut pz_vk, bytes: *const u8, n_proofs: usize, out_words: *mut u64, status: *mut i32) -> c_int;
     pub fn pz_verify_batch_bytes(vk: *mut pz_vk, bytes: *const u8, n_proofs: usize, seeds: *const u8, seed_offsets: *const usize,
                                  verdicts: *mut i32, h_evals: *mut u64, ab_affine: *mut u64, all_ok: *mut c_int) -> c_int;
+    // ParamsKZG files: the G2 codec and subgroup check, read_custom / write_custom / downsize and the consistency check of a params file
+    pub fn pz_g2_compress(ctx: *mut pz_ctx, points: *const u64, n: usize, bytes: *mut u8) -> c_int;
+    pub fn pz_g2_decompress(ctx: *mut pz_ctx, bytes: *const u8, n: usize, points: *mut u64, status: *mut i32, n_bad: *mut u64) -> c_int;
+    pub fn pz_g2_check_dev(ctx: *mut pz_ctx, d_points: *const u64, n: usize, d_status: *mut i32) -> c_int;
+    pub fn pz_g2_check(ctx: *mut pz_ctx, points: *const u64, n: usize, status: *mut i32) -> c_int;
+    pub fn pz_params_file_bytes(k: u32, format: c_int, bytes: *mut usize) -> c_int;
+    pub fn pz_params_decode(ctx: *mut pz_ctx, bytes: *const u8, len: usize, format: c_int, out: *mut *mut pz_params, n_bad: *mut u64) -> c_int;
+    pub fn pz_params_from_dev(ctx: *mut pz_ctx, k: u32, d_g: *const u64, d_g_lagrange: *const u64, g2: *const u64, s_g2: *const u64,
+                              out: *mut *mut pz_params) -> c_int;
+    pub fn pz_params_info(params: *const pz_params, k: *mut u32, g0_affine: *mut u64, g2: *mut u64, s_g2: *mut u64) -> c_int;
+    pub fn pz_params_points(params: *const pz_params, d_g: *mut *const u64, d_g_lagrange: *mut *const u64) -> c_int;
+    pub fn pz_params_bases(params: *mut pz_params, lagrange: c_int, bases: *mut *const pz_bases) -> c_int;
+    pub fn pz_params_encode(params: *const pz_params, format: c_int, out: *mut u8, capacity: usize) -> c_int;
+    pub fn pz_params_downsize(params: *const pz_params, k_new: u32, out: *mut *mut pz_params) -> c_int;
+    pub fn pz_params_check(params: *mut pz_params, failed: *mut u32, skipped: *mut u32) -> c_int;
+    pub fn pz_params_free(params: *mut pz_params) -> c_int;
     pub fn pz_poly_eval_dev(ctx: *mut pz_ctx, d_coeffs: *const u64, n_cols: usize, col_stride: usize, n: usize,
                             x: *const u64, d_out: *mut u64) -> c_int;
     pub fn pz_poly_eval_multi_dev(ctx: *mut pz_ctx, d_coeffs: *const u64, n_cols: usize, col_stride: usize, n: usize,
