@@ -790,6 +790,81 @@ int pz_proof_open_finish(pz_proof* proof, const uint64_t u[4], uint64_t* w2_affi
 int pz_proof_free(pz_proof* proof);
 
 /* ---------------------------------------------------------------------------------------------
+ * PUBLIC INPUTS (csrc/pz_public.hip): one optional instance column, n_instance in {0, 1} -- halo2-lib's
+ * assigned_instances / num_instance_columns [D], which the reference's drivers leave at zero, as every entry point above does.  With it a
+ * proof states that a GIVEN ciphertext c is the encryption under a GIVEN key (n, g), not only that some witness fits the shape.
+ *   - the instance column is the LAST column of the permutation, [advice | lookup advice | constants | instance], m' = m + 1 columns,
+ *     n_sets = ceil(m' / 2); the indices and delta powers of the other columns do not move.  Row i < n_public holds public value i, every
+ *     other row is zero, the blinding rows included (halo2 does not blind instance columns).  n_public <= max_rows.
+ *   - it is neither committed nor opened: a proof grows by one sigma evaluation and, when m' is odd, one permutation product.  The
+ *     verifier computes inst(x) = sum_{i < n_public} v_i l_i(x), l_i(x) = (x^n - 1)/n omega^i / (x - omega^i), itself and uses it as the
+ *     last permuted value; a challenge x with x^n = 1 gives verdict 0.
+ *   - transcript: the n_public values are absorbed as scalars (Montgomery words, like every other scalar) after the caller's seed and
+ *     before the first advice commitment; with no instance column nothing is absorbed and every existing transcript is unchanged.
+ *   - exposed values: little-endian limbs of limb_bits, n[limbs_n] | g[limbs_n] | c[2 limbs_n] for kind 0 and 2,
+ *     n | g | c1[limbs_n] | c2[limbs_n] | c[2 limbs_n] for kind 1 (add); m and r stay private.  (Kind 0 bakes the message's bits into the
+ *     key's shape -- the reference's property; kind 2, the uniform-shape circuit, is the zero-knowledge statement.)
+ * pz_circuit_public_cells  host only: the stream indices of the exposed advice cells in that order (arguments as pz_circuit_cells).
+ *                cells_out may be NULL (count only); PZ_ERR_CAPACITY if capacity < *n_public.
+ * pz_structure_expose      adds the column to a structure: the exposed cells' (column, row) through the break-point table, the instance
+ *                cells inserted into their copy cycles ON THE DEVICE (each the greatest cell of its class: the class's last cell maps to
+ *                it, it maps to the class's first; sized for the few hundred cells these circuits expose), d_map_col / d_map_row regrown to [m + 1][2^k] -- pz_structure_arrays returns the new
+ *                ones, the earlier pointers are dead.  Selectors and everything else are untouched.  Once per structure.
+ * pz_structure_public      n_instance, n_public and the DEVICE arrays d_cell_col / d_cell_row (u32, n_public each; NULL before expose).
+ * pz_public_gather_dev     out_words (HOST, n_public x 4 canonical words) = the exposed cells of a witness column block d_cols (columns
+ *                col_stride words apart, Montgomery): a prover reads the statement off its own witness.  Synchronises.  col_stride must be a
+ *                multiple of 4 and d_cols 16-byte aligned (PZ_ERR_INVALID otherwise).  The cell arrays are TRUSTED: every (column, row) must
+ *                lie inside the caller's column block (pz_structure_public's arrays do, for a block of n_adv columns of 2^k rows); they are
+ *                not checked against it.
+ * pz_instance_eval_dev     the verifier's kernel on its own: d_out[p] = inst_p(x_p) for n_proofs proofs; d_instances n_proofs x n_public x 4
+ *                canonical words, d_x / d_out n_proofs x 4 Montgomery words, omega the 2^k-th root, n_inv = 1 / 2^k (host, Montgomery).  One
+ *                field inversion per 1024 terms (batch inversion across a workgroup).  d_flags[p] (int32): bit 0 x_p lies on the domain
+ *                (a zero denominator, or x^n = 1), bit 1 a value >= r; d_out[p] is then meaningless.  Any n_public from 0 to 2^k.
+ *                Asynchronous on the context's stream.
+ * pz_pk_create_pub[_dev], pz_vk_keygen_pub[_dev], pz_vk_create_pub   the entry points above with n_instance and n_public; maps and
+ *                sigma_affine have m + n_instance columns; n_instance = 0 (then n_public must be 0) IS the old entry point.
+ *                pz_pk_info, pz_vk_info, pz_proof_wire_bytes, pz_proof_encode / _decode follow the key's m' and n_sets.
+ * pz_proof_begin_pub       pz_proof_begin plus instances (n_public x 4 canonical words, host): d_cols is [m'][2^k]; the constants column
+ *                AND the instance column are filled here.  A value >= r or a wrong n_public: PZ_ERR_INVALID.
+ * pz_verify_batch_pub, pz_verify_batch_bytes_pub   instances: n_proofs x n_public x 4 canonical words (host).  A value >= r gives verdict
+ *                0 for that proof; the others are judged without it.
+ * An OLD entry point (pz_proof_begin, pz_verify_batch, pz_verify_batch_bytes) on a key with an instance column, or a wrong n_public:
+ * PZ_ERR_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int pz_circuit_public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g, size_t n_steps_r,
+                            uint64_t* cells_out, size_t capacity, size_t* n_public);
+int pz_structure_expose(pz_structure* st);
+int pz_structure_public(const pz_structure* st, size_t* n_instance, size_t* n_public, const uint32_t** d_cell_col, const uint32_t** d_cell_row);
+int pz_public_gather_dev(pz_ctx* ctx, const uint64_t* d_cols, size_t col_stride, const uint32_t* d_cell_col, const uint32_t* d_cell_row,
+                         size_t n_public, uint64_t* out_words);
+int pz_instance_eval_dev(pz_ctx* ctx, uint32_t k, const uint64_t omega[4], const uint64_t n_inv[4], const uint64_t* d_instances,
+                         size_t n_public, size_t n_proofs, const uint64_t* d_x, uint64_t* d_out, int32_t* d_flags);
+int pz_pk_create_pub(pz_ctx* ctx, const pz_bases* bases_lagrange, const pz_bases* bases_monomial, uint32_t k, uint32_t lookup_bits,
+                     uint32_t blinding_factors, size_t max_rows, size_t n_adv, size_t n_lk, size_t n_instance, size_t n_public,
+                     const uint8_t* selectors, const uint64_t* constants, size_t n_constants, const uint32_t* map_col, const uint32_t* map_row,
+                     size_t tile, size_t ext_resident_cols, pz_pk** out);
+int pz_pk_create_pub_dev(pz_ctx* ctx, const pz_bases* bases_lagrange, const pz_bases* bases_monomial, uint32_t k, uint32_t lookup_bits,
+                         uint32_t blinding_factors, size_t max_rows, size_t n_adv, size_t n_lk, size_t n_instance, size_t n_public,
+                         const uint8_t* d_selectors, const uint64_t* constants, size_t n_constants, const uint32_t* d_map_col,
+                         const uint32_t* d_map_row, size_t tile, size_t ext_resident_cols, pz_pk** out);
+int pz_vk_keygen_pub_dev(pz_ctx* ctx, const pz_bases* bases_lagrange, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk,
+                         size_t n_instance, size_t n_public, const uint8_t* d_selectors, const uint64_t* constants, size_t n_constants,
+                         const uint32_t* d_map_col, const uint32_t* d_map_row, size_t tile, uint64_t* fixed_affine, uint64_t* sigma_affine);
+int pz_vk_keygen_pub(pz_ctx* ctx, const pz_bases* bases_lagrange, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk,
+                     size_t n_instance, size_t n_public, const uint8_t* selectors, const uint64_t* constants, size_t n_constants,
+                     const uint32_t* map_col, const uint32_t* map_row, size_t tile, uint64_t* fixed_affine, uint64_t* sigma_affine);
+int pz_vk_create_pub(pz_ctx* ctx, uint32_t k, uint32_t blinding_factors, size_t n_adv, size_t n_lk, size_t n_instance, size_t n_public,
+                     const uint64_t* fixed_affine, const uint64_t* sigma_affine, const uint64_t g0_affine[8], const uint64_t g2[16],
+                     const uint64_t s_g2[16], pz_vk** out);
+int pz_proof_begin_pub(pz_pk* pk, uint64_t* d_cols, uint64_t seed, const uint64_t* blinding, size_t n_blinding, const uint64_t* instances,
+                       size_t n_public, pz_proof** out, uint64_t* advice_affine);
+int pz_verify_batch_pub(pz_vk* vk, const uint64_t* instances, size_t n_public, const uint64_t* proofs, size_t n_proofs, const uint8_t* seeds,
+                        const size_t* seed_offsets, int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok);
+int pz_verify_batch_bytes_pub(pz_vk* vk, const uint64_t* instances, size_t n_public, const uint8_t* bytes, size_t n_proofs,
+                              const uint8_t* seeds, const size_t* seed_offsets, int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine,
+                              int* all_ok);
+
+/* ---------------------------------------------------------------------------------------------
  * measurement helpers (used by bench.py; not part of the reference surface).  Issue-rate microbenchmarks: libpz_probe.so.
  * ------------------------------------------------------------------------------------------- */
 /* HIP-event timing of the dominant kernel on the context's stream: accumulated since the last

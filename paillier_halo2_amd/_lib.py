@@ -172,6 +172,24 @@ SIGNATURES = {
     "pz_proof_open_begin": (C.c_int, [VP, VP, VP, VP]),
     "pz_proof_open_finish": (C.c_int, [VP, VP, VP, C.POINTER(C.c_int)]),
     "pz_proof_free": (C.c_int, [VP]),
+    # public inputs: the optional instance column (csrc/pz_public.hip)
+    "pz_circuit_public_cells": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "pz_structure_expose": (C.c_int, [VP]),
+    "pz_structure_public": (C.c_int, [VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(VP), C.POINTER(VP)]),
+    "pz_public_gather_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP, C.c_size_t, VP]),
+    "pz_instance_eval_dev": (C.c_int, [VP, C.c_uint32, VP, VP, VP, C.c_size_t, C.c_size_t, VP, VP, VP]),
+    "pz_pk_create_pub": (C.c_int, [VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, VP, VP,
+                                   C.c_size_t, VP, VP, C.c_size_t, C.c_size_t, C.POINTER(VP)]),
+    "pz_pk_create_pub_dev": (C.c_int, [VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, VP,
+                                       VP, C.c_size_t, VP, VP, C.c_size_t, C.c_size_t, C.POINTER(VP)]),
+    "pz_vk_keygen_pub_dev": (C.c_int, [VP, VP, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, VP, VP, C.c_size_t, VP, VP,
+                                       C.c_size_t, VP, VP]),
+    "pz_vk_keygen_pub": (C.c_int, [VP, VP, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, VP, VP, C.c_size_t, VP, VP,
+                                   C.c_size_t, VP, VP]),
+    "pz_vk_create_pub": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(VP)]),
+    "pz_proof_begin_pub": (C.c_int, [VP, VP, C.c_uint64, VP, C.c_size_t, VP, C.c_size_t, C.POINTER(VP), VP]),
+    "pz_verify_batch_pub": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(C.c_int)]),
+    "pz_verify_batch_bytes_pub": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(C.c_int)]),
     "pz_timing_enable": (C.c_int, [VP, C.c_int]),
     "pz_timing_reset": (C.c_int, [VP]),
     "pz_timing_get": (C.c_int, [VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),

@@ -299,6 +299,9 @@ class StructureArrays:
     result_cell: int
     n_steps_g: int
     n_steps_r: int
+    # stream indices of the cells a circuit with the instance column exposes, in the column's row order: the limb cells of
+    # n | g | c (encrypt, encrypt_uniform) or n | g | c1 | c2 | c (add) -- pz_circuit_public_cells gives the same list
+    public_cells: Optional[np.ndarray] = None
 
 
 def _exp_bits(e: int) -> List[int]:
@@ -525,14 +528,18 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         cat = lambda parts: torch.cat([p_ if isinstance(p_, torch.Tensor) else torch.as_tensor(p_, dtype=torch.int64).to(dev) for p_ in parts])
         src, lookup_src = cat(parts_src), cat(parts_lk)
     src[eq_cell] = -(1 + cid(1))          # assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
+    exposed = list(n_c) + list(g_c) + (list(x_c) + list(y_c) if kind == "add" else []) + list(res_c)
     return StructureArrays(n_cells=off, src=src, gate_mask=np.concatenate(parts_mask), lookup_src=lookup_src,
-                           constants=constants, result_cell=eq_cell, n_steps_g=n_steps[0], n_steps_r=n_steps[1])
+                           constants=constants, result_cell=eq_cell, n_steps_g=n_steps[0], n_steps_r=n_steps[1],
+                           public_cells=np.asarray(exposed, dtype=np.int64))
 
 
 def columns(sa: StructureArrays, k: int, lb: int, minimum_rows: int = layout.MINIMUM_ROWS_BENCH, blinding_factors: int = layout.BLINDING_FACTORS,
-            device: Optional[str] = None, keep_on_device: bool = False, break_rows: Optional[int] = None):
+            device: Optional[str] = None, keep_on_device: bool = False, break_rows: Optional[int] = None, expose: bool = False):
     """stream structure -> (CircuitStructure for prover.keygen, starts).  The permutation covers [advice | lookup advice | constants];
     every equality class becomes one cycle of sigma (cells in increasing (column, row) order).
+    expose: add the instance column as the permutation's LAST column (public inputs): row i of it joins the class
+    of sa.public_cells[i] -- as the greatest cell of that class, since the column is the last one.
     minimum_rows: the argument of the tester's calculate_params (layout.RowBudget): it fixes the NUMBER of advice / lookup-advice columns
     (20 on the reference's bench path, /root/reference/src/bench.rs:161-171; 9 under MockProver, src/paillier.rs:167-171); columns are
     FILLED to 2^k - (blinding_factors + 3) rows (break_rows overrides), so with 20 the last configured column can stay empty -- it is a
@@ -552,12 +559,14 @@ def columns(sa: StructureArrays, k: int, lb: int, minimum_rows: int = layout.MIN
     NC, NL, NK = sa.n_cells, sa.lookup_src.shape[0], len(sa.constants)
     A = rb.columns_for(NC, filled=A_used)
     Lk = rb.columns_for(NL)
-    m = A + Lk + 1
-    assert NK <= max_rows
+    NP = int(sa.public_cells.shape[0]) if expose else 0
+    m = A + Lk + 1 + (1 if expose else 0)
+    assert NK <= max_rows and NP <= max_rows
     if device is None:
         device = "cuda" if (torch.cuda.is_available() and NC > (1 << 22)) else "cpu"
     dev = torch.device(device)
-    T = NC + NL + NK + (A_used - 1)
+    T0 = NC + NL + NK + (A_used - 1)
+    T = T0 + NP                                   # ... | the instance cells
     st = torch.from_numpy(starts).to(dev)
     # ---- node -> flat position (column * n + row)
     pos = torch.empty(T, dtype=torch.int64, device=dev)
@@ -571,15 +580,19 @@ def columns(sa: StructureArrays, k: int, lb: int, minimum_rows: int = layout.MIN
     del t
     pos[NC + NL:NC + NL + NK] = (A + Lk) * n + torch.arange(NK, dtype=torch.int64, device=dev)
     j = torch.arange(1, A_used, dtype=torch.int64, device=dev)
-    pos[NC + NL + NK:] = (j - 1) * n + (st[j] - st[j - 1])
+    pos[NC + NL + NK:T0] = (j - 1) * n + (st[j] - st[j - 1])
+    if NP:
+        pos[T0:] = (A + Lk + 1) * n + torch.arange(NP, dtype=torch.int64, device=dev)
     # ---- what every node copies
     src = torch.arange(T, dtype=torch.int64, device=dev)
     s_adv = torch.as_tensor(sa.src).to(dev)
     src[:NC] = torch.where(s_adv < 0, NC + NL - 1 - s_adv, s_adv)          # -(1 + id) -> constant node NC + NL + id
     del s_adv
     src[NC:NC + NL] = torch.as_tensor(sa.lookup_src).to(dev)
-    src[NC + NL + NK:] = st[j]
+    src[NC + NL + NK:T0] = st[j]
     del j
+    if NP:
+        src[T0:] = torch.from_numpy(np.ascontiguousarray(sa.public_cells, dtype=np.int64)).to(dev)
     while True:                                                           # roots by pointer jumping (chains are a few links long)
         nxt = src[src]
         if torch.equal(nxt, src):
@@ -627,7 +640,12 @@ def columns(sa: StructureArrays, k: int, lb: int, minimum_rows: int = layout.MIN
         map_col = map_col.cpu().numpy().view(np.uint32)
         map_row = map_row.cpu().numpy().view(np.uint32)
         selectors = selectors.cpu().numpy()
+    public = None
+    if expose:
+        pc = pos[torch.from_numpy(np.ascontiguousarray(sa.public_cells, dtype=np.int64)).to(dev)].cpu().numpy()
+        public = [(int(p_) // n, int(p_) % n) for p_ in pc]
     cs = CircuitStructure(k=k, lookup_bits=lb, max_rows=max_rows, blinding_factors=blinding_factors, selectors=selectors, n_lk=Lk,
-                          constants=list(sa.constants), map_col=map_col, map_row=map_row, minimum_rows=minimum_rows, n_adv_used=A_used)
+                          constants=list(sa.constants), map_col=map_col, map_row=map_row, minimum_rows=minimum_rows, n_adv_used=A_used,
+                          n_instance=1 if expose else 0, public_cells=public)
     starts = np.concatenate([starts, np.full(A - A_used, NC, dtype=np.int64)])
     return cs, starts.astype(np.uint64)

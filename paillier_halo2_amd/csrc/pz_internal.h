@@ -175,13 +175,31 @@ struct pz_dev_bufs {
 // n bytes of OS randomness (getrandom, /dev/urandom behind it): the verifier's fold weights, pz_params_check's rho and tau (pz_verify.cpp)
 bool pz_os_random(void* buf, size_t n);
 
+// the circuit structure handle (pz_circuit_structure_dev, pz_structure.hip).  pz_structure_expose (pz_public.hip) adds the instance column:
+// d_map_col / d_map_row are then [m + 1][2^k] and d_cell_col / d_cell_row hold the (column, row) of the n_public exposed advice cells
+struct pz_structure {
+    pz_ctx* ctx = nullptr;
+    uint8_t* d_selectors = nullptr;
+    uint32_t *d_map_col = nullptr, *d_map_row = nullptr;
+    uint64_t* d_starts = nullptr;
+    std::vector<uint64_t> constants;   // canonical integers, 4 words each
+    std::vector<uint64_t> starts;      // host copy (n_adv + 1)
+    size_t n_adv = 0, n_used = 0, n_lk = 0, max_rows = 0, n_cells = 0, n_lookups = 0, n_steps_g = 0, n_steps_r = 0;
+    uint32_t k = 0;
+    int kind = 0;
+    uint32_t limbs_n = 0, limb_bits = 0, lookup_bits = 0;
+    size_t n_instance = 0, n_public = 0;
+    uint32_t *d_cell_col = nullptr, *d_cell_row = nullptr;
+};
+
 static inline unsigned pz_div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 // the device batch verifier (pz_verify.hip kernels, pz_verify.cpp orchestration).  Offsets in 4-word elements into a proof's
 // evaluation array (pz_proof_evaluate's), counts of a verifying key's shape; sets in verifier / prover.query_layout's order.
 #define PZ_VSETS_MAX 5
 struct pz_vshape {
-    uint32_t A, Lk, F, m, S;
+    uint32_t A, Lk, F, m, S;   // m counts the instance column when the key has one (n_inst = 1: the permutation's LAST column)
+    uint32_t n_inst;
     uint32_t n_own;   // the proof's commitments = its own bases: A + 4 Lk + S + 6
     uint32_t n_vkb;   // fixed | sigma | g0: F + m + 1
     uint32_t n_ev;    // evaluation elements
@@ -192,11 +210,16 @@ struct pz_vshape {
 // a member of a query set: (evaluation element offset, destination); the destination's top two bits say which scalar array
 enum { PZ_VM_OWN = 0, PZ_VM_VK = 1, PZ_VM_H = 2 };
 // per-proof scalars the host derives after replaying the transcript (Montgomery, 4 words each)
-enum { VP_BETA = 0, VP_GAMMA, VP_Y, VP_BX, VP_L0, VP_LLAST, VP_LACT, VP_INV, VP_XN, VP_SY, VP_W1A, VP_W2A, VP_W2B, VP_COEF,
+enum { VP_BETA = 0, VP_GAMMA, VP_Y, VP_BX, VP_L0, VP_LLAST, VP_LACT, VP_INV, VP_XN, VP_SY, VP_W1A, VP_W2A, VP_W2B, VP_INST, VP_COEF,
        VP_LAG = VP_COEF + PZ_VSETS_MAX, VP_COUNT = VP_LAG + 4 * PZ_VSETS_MAX };
 int pz_verify_terms_launch(pz_ctx* ctx, const pz_vshape& s, size_t B, const uint32_t* d_members, const uint64_t* d_evals,
                            const uint64_t* d_pp, const uint64_t* d_delta, uint64_t* d_h, int32_t* d_ident, uint64_t* d_own,
                            uint64_t* d_vksc, uint64_t* d_gpart);
+// the instance column at each proof's challenge (pz_public.hip): d_out[p * out_stride ..+4] = sum_{i<L} v_pi l_i(x_p) for B proofs, instances
+// canonical words [B][L][4], x Montgomery words at d_x + p * x_stride; d_flags[p]: bit 0 x_p lies on the domain, bit 1 a value >= r.
+// Strides in 64-bit words.  Asynchronous on the context's stream.
+int pz_instance_eval_launch(pz_ctx* ctx, uint32_t k, const uint64_t omega[4], const uint64_t n_inv[4], const uint64_t* d_instances, size_t L,
+                            size_t B, const uint64_t* d_x, size_t x_stride, uint64_t* d_out, size_t out_stride, int32_t* d_flags);
 int pz_verify_fold_launch(pz_ctx* ctx, const pz_vshape& s, size_t B, int mode, const uint64_t* d_r, uint64_t* d_vksc,
                           const uint64_t* d_gpart, const uint64_t* d_own, uint64_t* d_cols);
 

@@ -66,13 +66,14 @@ namespace {
 int pk_create(pz_ctx* ctx, const pz_bases* bases_lagrange, const pz_bases* bases_monomial, uint32_t k, uint32_t lookup_bits,
               uint32_t blinding_factors, size_t max_rows, size_t n_adv, size_t n_lk, const uint8_t* selectors, const uint64_t* constants,
               size_t n_constants, const uint32_t* map_col, const uint32_t* map_row, size_t tile, size_t ext_resident_cols, bool on_device,
-              pz_pk** out) {
+              size_t n_instance, size_t n_public, pz_pk** out) {
     if (!ctx || !bases_lagrange || !bases_monomial || !selectors || !map_col || !map_row || !out || (n_constants && !constants)) return PZ_ERR_INVALID;
     // (n_lk = 0: a circuit without range-check lookups is not a halo2-lib circuit; the composition assumes at least one lookup column)
     if (k < 4 || k > 24 || !n_adv || !n_lk || lookup_bits >= k || tile == 0 || tile % pzp::CHUNK) return PZ_ERR_INVALID;
     const size_t n = (size_t)1 << k;
     if (max_rows + blinding_factors + 1 > n || n_constants > max_rows) return PZ_ERR_INVALID;
-    if ((n_adv + n_lk + 1) > ((size_t)1 << 32) / n) return PZ_ERR_UNSUPPORTED;   // the copy-constraint map addresses cells with 32 bits
+    if (n_instance > 1 || (n_instance ? n_public == 0 || n_public > max_rows : n_public != 0)) return PZ_ERR_INVALID;
+    if ((n_adv + n_lk + 1 + n_instance) > ((size_t)1 << 32) / n) return PZ_ERR_UNSUPPORTED;   // the copy-constraint map addresses cells with 32 bits
     size_t np_l = 0, np_m = 0;
     if (pz_bases_info(bases_lagrange, &np_l, nullptr, nullptr) != PZ_OK || pz_bases_info(bases_monomial, &np_m, nullptr, nullptr) != PZ_OK) return PZ_ERR_INVALID;
     if (np_l < n || np_m < n) return PZ_ERR_INVALID;
@@ -84,6 +85,7 @@ int pk_create(pz_ctx* ctx, const pz_bases* bases_lagrange, const pz_bases* bases
     const int rc = guarded_raw([&] {
         pzp::Structure st;
         st.k = k; st.lookup_bits = lookup_bits; st.blinding_factors = blinding_factors; st.max_rows = max_rows; st.n_adv = n_adv; st.n_lk = n_lk;
+        st.n_instance = n_instance; st.n_public = n_public;
         const size_t m = st.m();
         st.constants.assign(constants, constants + 4 * n_constants);
         if (on_device) {
@@ -115,14 +117,30 @@ extern "C" int pz_pk_create(pz_ctx* ctx, const pz_bases* bases_lagrange, const p
                             const uint64_t* constants, size_t n_constants, const uint32_t* map_col, const uint32_t* map_row, size_t tile,
                             size_t ext_resident_cols, pz_pk** out) {
     return pk_create(ctx, bases_lagrange, bases_monomial, k, lookup_bits, blinding_factors, max_rows, n_adv, n_lk, selectors, constants, n_constants,
-                     map_col, map_row, tile, ext_resident_cols, false, out);
+                     map_col, map_row, tile, ext_resident_cols, false, 0, 0, out);
 }
 extern "C" int pz_pk_create_dev(pz_ctx* ctx, const pz_bases* bases_lagrange, const pz_bases* bases_monomial, uint32_t k, uint32_t lookup_bits,
                                 uint32_t blinding_factors, size_t max_rows, size_t n_adv, size_t n_lk, const uint8_t* d_selectors,
                                 const uint64_t* constants, size_t n_constants, const uint32_t* d_map_col, const uint32_t* d_map_row, size_t tile,
                                 size_t ext_resident_cols, pz_pk** out) {
     return pk_create(ctx, bases_lagrange, bases_monomial, k, lookup_bits, blinding_factors, max_rows, n_adv, n_lk, d_selectors, constants,
-                     n_constants, d_map_col, d_map_row, tile, ext_resident_cols, true, out);
+                     n_constants, d_map_col, d_map_row, tile, ext_resident_cols, true, 0, 0, out);
+}
+// the same with the optional instance column: map_col / map_row are u32 [m + n_instance][2^k]; n_instance = 0 (then n_public = 0) IS the
+// entry point above
+extern "C" int pz_pk_create_pub(pz_ctx* ctx, const pz_bases* bases_lagrange, const pz_bases* bases_monomial, uint32_t k, uint32_t lookup_bits,
+                                uint32_t blinding_factors, size_t max_rows, size_t n_adv, size_t n_lk, size_t n_instance, size_t n_public,
+                                const uint8_t* selectors, const uint64_t* constants, size_t n_constants, const uint32_t* map_col,
+                                const uint32_t* map_row, size_t tile, size_t ext_resident_cols, pz_pk** out) {
+    return pk_create(ctx, bases_lagrange, bases_monomial, k, lookup_bits, blinding_factors, max_rows, n_adv, n_lk, selectors, constants, n_constants,
+                     map_col, map_row, tile, ext_resident_cols, false, n_instance, n_public, out);
+}
+extern "C" int pz_pk_create_pub_dev(pz_ctx* ctx, const pz_bases* bases_lagrange, const pz_bases* bases_monomial, uint32_t k, uint32_t lookup_bits,
+                                    uint32_t blinding_factors, size_t max_rows, size_t n_adv, size_t n_lk, size_t n_instance, size_t n_public,
+                                    const uint8_t* d_selectors, const uint64_t* constants, size_t n_constants, const uint32_t* d_map_col,
+                                    const uint32_t* d_map_row, size_t tile, size_t ext_resident_cols, pz_pk** out) {
+    return pk_create(ctx, bases_lagrange, bases_monomial, k, lookup_bits, blinding_factors, max_rows, n_adv, n_lk, d_selectors, constants,
+                     n_constants, d_map_col, d_map_row, tile, ext_resident_cols, true, n_instance, n_public, out);
 }
 
 extern "C" int pz_pk_info(const pz_pk* pk, size_t* n_fixed, size_t* n_perm_cols, size_t* n_sets, size_t* blinding_words, size_t* evals_words_out) {
@@ -152,10 +170,15 @@ extern "C" int pz_pk_free(pz_pk* pk) {
     return PZ_OK;
 }
 
-extern "C" int pz_proof_begin(pz_pk* pk, uint64_t* d_cols, uint64_t seed, const uint64_t* blinding, size_t n_blinding, pz_proof** out,
-                              uint64_t* advice_affine) {
+namespace {
+// instances: n_public x 4 canonical words (host), NULL for a key without an instance column
+int proof_begin(pz_pk* pk, uint64_t* d_cols, uint64_t seed, const uint64_t* blinding, size_t n_blinding, const uint64_t* instances, size_t n_public,
+                pz_proof** out, uint64_t* advice_affine) {
     if (!pk || !pk->key || !d_cols || !out || !advice_affine) return PZ_ERR_INVALID;
     if (blinding ? n_blinding < pzp::blinding_words(*pk->key) : n_blinding != PZ_BLINDING_SEEDED_TEST_STREAM) return PZ_ERR_INVALID;
+    if (n_public != pk->key->st.n_public || (n_public && !instances)) return PZ_ERR_INVALID;
+    for (size_t i = 0; i < n_public; ++i)
+        if (pzh::ge_mod(instances + 4 * i)) return PZ_ERR_INVALID;   // a public value is a field element
     *out = nullptr;
     bool idle = false;
     if (!pk->busy.compare_exchange_strong(idle, true)) return PZ_ERR_INVALID;   // exactly one caller claims the key
@@ -166,6 +189,10 @@ extern "C" int pz_proof_begin(pz_pk* pk, uint64_t* d_cols, uint64_t seed, const 
     }
     const int rc = guarded_raw([&] {
         pr->se = new pzp::Session(pk->mem, *pk->key, pk->ws, d_cols, blinding ? pzp::Rng(blinding, n_blinding) : pzp::Rng(seed));
+        for (size_t i = 0; i < n_public; ++i) {
+            const pzh::Fr v = pzh::from_raw(instances + 4 * i);
+            pr->se->instances.insert(pr->se->instances.end(), v.v, v.v + 4);
+        }
         pr->se->advice(advice_affine);
     });
     if (rc != PZ_OK) {
@@ -176,6 +203,16 @@ extern "C" int pz_proof_begin(pz_pk* pk, uint64_t* d_cols, uint64_t seed, const 
     }
     *out = pr;
     return PZ_OK;
+}
+}   // namespace
+
+extern "C" int pz_proof_begin(pz_pk* pk, uint64_t* d_cols, uint64_t seed, const uint64_t* blinding, size_t n_blinding, pz_proof** out,
+                              uint64_t* advice_affine) {
+    return proof_begin(pk, d_cols, seed, blinding, n_blinding, nullptr, 0, out, advice_affine);   // (a key with an instance column: PZ_ERR_INVALID)
+}
+extern "C" int pz_proof_begin_pub(pz_pk* pk, uint64_t* d_cols, uint64_t seed, const uint64_t* blinding, size_t n_blinding, const uint64_t* instances,
+                                  size_t n_public, pz_proof** out, uint64_t* advice_affine) {
+    return proof_begin(pk, d_cols, seed, blinding, n_blinding, instances, n_public, out, advice_affine);
 }
 
 extern "C" int pz_proof_lookups(pz_proof* pr, const uint64_t theta[4], uint64_t* perm_inputs_affine, uint64_t* perm_tables_affine) {

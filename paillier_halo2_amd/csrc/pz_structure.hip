@@ -816,16 +816,7 @@ struct DevBufs {
 };
 }   // namespace
 
-struct pz_structure {
-    pz_ctx* ctx = nullptr;
-    u8* d_selectors = nullptr;
-    u32 *d_map_col = nullptr, *d_map_row = nullptr;
-    u64* d_starts = nullptr;
-    std::vector<u64> constants;   // canonical integers, 4 words each
-    std::vector<u64> starts;      // host copy (n_adv + 1)
-    size_t n_adv = 0, n_used = 0, n_lk = 0, max_rows = 0, n_cells = 0, n_lookups = 0, n_steps_g = 0, n_steps_r = 0;
-    uint32_t k = 0;
-};
+// (struct pz_structure: pz_internal.h -- csrc/pz_public.hip adds the instance column to it)
 
 extern "C" int pz_structure_free(pz_structure* st) {
     if (!st) return PZ_OK;
@@ -833,7 +824,8 @@ extern "C" int pz_structure_free(pz_structure* st) {
         std::lock_guard<std::recursive_mutex> lock(st->ctx->mu);
         (void)hipSetDevice(st->ctx->device);
         (void)hipStreamSynchronize(st->ctx->stream);
-        for (void* d : {(void*)st->d_selectors, (void*)st->d_map_col, (void*)st->d_map_row, (void*)st->d_starts})
+        for (void* d : {(void*)st->d_selectors, (void*)st->d_map_col, (void*)st->d_map_row, (void*)st->d_starts, (void*)st->d_cell_col,
+                        (void*)st->d_cell_row})
             if (d) (void)pz_hip_free(d);
     }
     delete st;
@@ -900,6 +892,7 @@ extern "C" int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n,
     std::unique_ptr<pz_structure> st(new (std::nothrow) pz_structure);
     if (!st) return PZ_ERR_OOM;
     st->k = k;
+    st->kind = kind; st->limbs_n = limbs_n; st->limb_bits = limb_bits; st->lookup_bits = lookup_bits;
     st->n_adv = (size_t)A; st->n_used = (size_t)A_used; st->n_lk = (size_t)Lk; st->max_rows = (size_t)max_rows;
     st->n_cells = (size_t)NC; st->n_lookups = (size_t)NL; st->n_steps_g = S.n_steps_g; st->n_steps_r = S.n_steps_r;
     for (const C256& c : S.constants) st->constants.insert(st->constants.end(), c.w, c.w + 4);

@@ -29,6 +29,7 @@ struct pz_vk {
     void* d_delta = nullptr;                  // delta^c, c < m
     void* d_members = nullptr;                // (evaluation offset, destination) per member of the query sets
     pz_bases* t_vk = nullptr;                 // K1 table of d_vkb (the per-proof checks' vk MSM)
+    size_t n_public = 0;                      // values of the instance column (s.n_inst = 1), else 0
 };
 
 namespace {
@@ -113,9 +114,10 @@ bool os_random(void* buf, size_t n) {
 }
 
 // the layout of a proof and of the query sets (prover.query_layout's order)
-void make_shape(size_t A, size_t Lk, pz_vk& vk, std::vector<uint32_t>& mem) {
+void make_shape(size_t A, size_t Lk, size_t n_instance, pz_vk& vk, std::vector<uint32_t>& mem) {
     pz_vshape& s = vk.s;
-    const uint32_t F = (uint32_t)A + 2, m = (uint32_t)(A + Lk + 1), S = (m + 1) / 2;
+    const uint32_t F = (uint32_t)A + 2, m = (uint32_t)(A + Lk + 1 + n_instance), S = (m + 1) / 2;
+    s.n_inst = (uint32_t)n_instance;
     s.A = (uint32_t)A;
     s.Lk = (uint32_t)Lk;
     s.F = F;
@@ -188,7 +190,7 @@ struct Replay {
 // stated_h: the proofs carry h(x) as their last evaluation and must state the value the expression implies (pz_verify_batch); proofs that
 // came in as wire bytes do not send it (their slot is zero) and the comparison does not apply
 void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, const size_t* seed_off, int32_t* verdicts,
-            uint64_t* h_evals, uint64_t* ab_affine, int* all_ok, bool stated_h = true) {
+            uint64_t* h_evals, uint64_t* ab_affine, int* all_ok, bool stated_h = true, const uint64_t* instances = nullptr) {
     pz_ctx* ctx = vk->ctx;
     const pz_vshape& s = vk->s;
     const size_t cw = 8ull * s.n_own, ew = 4ull * s.n_ev, pw = cw + ew;
@@ -197,6 +199,7 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
     const Fr w = pzh::omega(vk->k), one = pzh::FR_ONE, nf = pzh::from_u64(n);
     const Fr w_u = pzh::pow_u64(w, u_row), w_m1 = pzh::pow_u64(w, n - 1);
     const uint32_t c_ap = s.A + s.Lk, c_pz = s.A + 3 * s.Lk, c_h = c_pz + s.S + s.Lk + 1;
+    const size_t NP = vk->n_public;
 
     // 1. transcripts, then everything that needs an inversion, inverted at once
     std::vector<Replay> rp(B);
@@ -208,6 +211,14 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
         static const uint8_t none = 0;
         pzp::Transcript tr(seeds ? (const void*)(seeds + seed_off[i]) : (const void*)&none, seed_off[i + 1] - seed_off[i]);
         Replay& r = rp[i];
+        if (NP) {   // the statement: absorbed after the seed, before the first commitment; a value >= r is no statement (verdict 0)
+            std::vector<uint64_t> im(4 * NP, 0);
+            for (size_t j = 0; j < NP && r.canon; ++j) {
+                r.canon = canonical(instances + (i * NP + j) * 4);
+                if (r.canon) memcpy(im.data() + 4 * j, pzh::from_raw(instances + (i * NP + j) * 4).v, 32);
+            }
+            tr.common_scalars(im.data(), NP);
+        }
         tr.common_points(c, s.A + s.Lk);
         tr.squeeze("theta");
         tr.common_points(c + 8ull * c_ap, 2 * s.Lk);
@@ -322,12 +333,29 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
     ck(pz_dev_memset(ctx, d_gp.d, 0, B * PZ_VSETS_MAX * 32));
     ck(pz_dev_copy(ctx, d_bases.d, vk->d_vkb, s.n_vkb * 64ull));
     ck(pz_upload(ctx, d_bases.p() + 8ull * s.n_vkb, h_com.data(), h_com.size() * 8));
+    Dev d_inst(ctx), d_x(ctx), d_fl(ctx);
+    std::vector<int32_t> iflags(B, 0);
+    if (NP) {   // the instance column at every proof's x, straight into its scalar block
+        std::vector<uint64_t> xs(B * 4);
+        for (size_t i = 0; i < B; ++i) memcpy(xs.data() + 4 * i, rp[i].x.v, 32);
+        const Fr n_inv = pzh::inv(nf);
+        d_inst.alloc(B * NP * 32);
+        d_x.alloc(B * 32);
+        d_fl.alloc(B * 4);
+        ck(pz_upload(ctx, d_inst.d, instances, B * NP * 32));
+        ck(pz_upload(ctx, d_x.d, xs.data(), B * 32));
+        ck(pz_instance_eval_launch(ctx, vk->k, w.v, n_inv.v, d_inst.p(), NP, B, d_x.p(), 4, d_pp.p() + 4 * VP_INST, 4 * VP_COUNT, d_fl.p<int32_t>()));
+    }
     ck(pz_verify_terms_launch(ctx, s, B, (const uint32_t*)vk->d_members, d_ev.p(), d_pp.p(), (const uint64_t*)vk->d_delta, d_h.p(),
                               d_id.p<int32_t>(), d_own.p(), d_vksc.p(), d_gp.p()));
     std::vector<int32_t> ident(B);
     std::vector<uint64_t> hx(B * 4);
     ck(pz_download(ctx, ident.data(), d_id.d, B * 4));
     ck(pz_download(ctx, hx.data(), d_h.d, B * 32));
+    if (NP) {
+        ck(pz_download(ctx, iflags.data(), d_fl.d, B * 4));
+        for (size_t i = 0; i < B; ++i) good[i] = good[i] && iflags[i] == 0;   // x on the domain, or a value >= r
+    }
     if (h_evals) memcpy(h_evals, hx.data(), B * 32);
     bool all_ident = true;
     for (size_t i = 0; i < B; ++i) {
@@ -448,12 +476,14 @@ bool all_zero(const uint64_t* v, size_t n) {
 
 bool pz_os_random(void* buf, size_t n) { return os_random(buf, n); }
 
-extern "C" int pz_vk_create(pz_ctx* ctx, uint32_t k, uint32_t blinding_factors, size_t n_adv, size_t n_lk, const uint64_t* fixed_affine,
+namespace {
+int vk_create(pz_ctx* ctx, size_t n_instance, size_t n_public, uint32_t k, uint32_t blinding_factors, size_t n_adv, size_t n_lk, const uint64_t* fixed_affine,
                             const uint64_t* sigma_affine, const uint64_t g0_affine[8], const uint64_t g2[16], const uint64_t s_g2[16],
                             pz_vk** out) {
     if (!ctx || !fixed_affine || !sigma_affine || !g0_affine || !g2 || !s_g2 || !out) return PZ_ERR_INVALID;
     *out = nullptr;
     if (k < 4 || k > 24 || !n_adv || !n_lk || (uint64_t)blinding_factors + 2 > (1ull << k)) return PZ_ERR_INVALID;
+    if (n_instance > 1 || (n_instance ? n_public == 0 || n_public + blinding_factors + 1 > (1ull << k) : n_public != 0)) return PZ_ERR_INVALID;
     if (n_adv + n_lk >= (1u << 24)) return PZ_ERR_UNSUPPORTED;   // offsets and slots are 30-bit on the device
     if (all_zero(g2, 16) || all_zero(s_g2, 16) || all_zero(g0_affine, 8)) return PZ_ERR_INVALID;
     PZ_ENTER(ctx);
@@ -464,7 +494,8 @@ extern "C" int pz_vk_create(pz_ctx* ctx, uint32_t k, uint32_t blinding_factors, 
     vk->bf = blinding_factors;
     const int rc = guarded([&] {
         std::vector<uint32_t> mem;
-        make_shape(n_adv, n_lk, *vk, mem);
+        make_shape(n_adv, n_lk, n_instance, *vk, mem);
+        vk->n_public = n_public;
         const pz_vshape& s = vk->s;
         memcpy(vk->g2, g2, 128);
         memcpy(vk->g2 + 16, s_g2, 128);
@@ -496,6 +527,20 @@ extern "C" int pz_vk_create(pz_ctx* ctx, uint32_t k, uint32_t blinding_factors, 
     return PZ_OK;
 }
 
+}   // namespace
+
+extern "C" int pz_vk_create(pz_ctx* ctx, uint32_t k, uint32_t blinding_factors, size_t n_adv, size_t n_lk, const uint64_t* fixed_affine,
+                            const uint64_t* sigma_affine, const uint64_t g0_affine[8], const uint64_t g2[16], const uint64_t s_g2[16],
+                            pz_vk** out) {
+    return vk_create(ctx, 0, 0, k, blinding_factors, n_adv, n_lk, fixed_affine, sigma_affine, g0_affine, g2, s_g2, out);
+}
+// the same for a key with the optional instance column: sigma_affine is (m + n_instance) x 8
+extern "C" int pz_vk_create_pub(pz_ctx* ctx, uint32_t k, uint32_t blinding_factors, size_t n_adv, size_t n_lk, size_t n_instance, size_t n_public,
+                                const uint64_t* fixed_affine, const uint64_t* sigma_affine, const uint64_t g0_affine[8], const uint64_t g2[16],
+                                const uint64_t s_g2[16], pz_vk** out) {
+    return vk_create(ctx, n_instance, n_public, k, blinding_factors, n_adv, n_lk, fixed_affine, sigma_affine, g0_affine, g2, s_g2, out);
+}
+
 extern "C" int pz_vk_info(const pz_vk* vk, size_t* commitment_words, size_t* evals_words) {
     if (!vk) return PZ_ERR_INVALID;
     if (commitment_words) *commitment_words = 8ull * vk->s.n_own;
@@ -503,9 +548,11 @@ extern "C" int pz_vk_info(const pz_vk* vk, size_t* commitment_words, size_t* eva
     return PZ_OK;
 }
 
-extern "C" int pz_verify_batch(pz_vk* vk, const uint64_t* proofs, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
+namespace {
+int verify_batch(pz_vk* vk, const uint64_t* instances, size_t n_public, const uint64_t* proofs, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
                                int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok) {
     if (!vk || !proofs || !n_proofs || !seed_offsets || !verdicts || !all_ok) return PZ_ERR_INVALID;
+    if (n_public != vk->n_public || (n_public && !instances)) return PZ_ERR_INVALID;   // (an instance key through the old entry point too)
     if (n_proofs > (1u << 20)) return PZ_ERR_UNSUPPORTED;
     for (size_t i = 0; i < n_proofs; ++i)
         if (seed_offsets[i + 1] < seed_offsets[i]) return PZ_ERR_INVALID;
@@ -514,7 +561,20 @@ extern "C" int pz_verify_batch(pz_vk* vk, const uint64_t* proofs, size_t n_proof
     PZ_ENTER(ctx);
     *all_ok = 0;
     for (size_t i = 0; i < n_proofs; ++i) verdicts[i] = 0;
-    return guarded([&] { verify(vk, proofs, n_proofs, seeds, seed_offsets, verdicts, h_evals, ab_affine, all_ok); });
+    return guarded([&] { verify(vk, proofs, n_proofs, seeds, seed_offsets, verdicts, h_evals, ab_affine, all_ok, true, instances); });
+}
+
+}   // namespace
+
+extern "C" int pz_verify_batch(pz_vk* vk, const uint64_t* proofs, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
+                               int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok) {
+    return verify_batch(vk, nullptr, 0, proofs, n_proofs, seeds, seed_offsets, verdicts, h_evals, ab_affine, all_ok);
+}
+// instances: n_proofs x n_public x 4 canonical words (host).  A value >= r: verdict 0 for that proof, the others are judged without it
+extern "C" int pz_verify_batch_pub(pz_vk* vk, const uint64_t* instances, size_t n_public, const uint64_t* proofs, size_t n_proofs,
+                                   const uint8_t* seeds, const size_t* seed_offsets, int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine,
+                                   int* all_ok) {
+    return verify_batch(vk, instances, n_public, proofs, n_proofs, seeds, seed_offsets, verdicts, h_evals, ab_affine, all_ok);
 }
 
 extern "C" int pz_proof_wire_bytes(const pz_vk* vk, size_t* bytes) {
@@ -539,9 +599,11 @@ extern "C" int pz_proof_decode(pz_vk* vk, const uint8_t* bytes, size_t n_proofs,
     return guarded([&] { wire_codec(vk, n_proofs, true, const_cast<uint8_t*>(bytes), out_words, status); });
 }
 
-extern "C" int pz_verify_batch_bytes(pz_vk* vk, const uint8_t* bytes, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
+namespace {
+int verify_batch_bytes(pz_vk* vk, const uint64_t* instances, size_t n_public, const uint8_t* bytes, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
                                      int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok) {
     if (!vk || !bytes || !n_proofs || !seed_offsets || !verdicts || !all_ok) return PZ_ERR_INVALID;
+    if (n_public != vk->n_public || (n_public && !instances)) return PZ_ERR_INVALID;
     if (n_proofs > (1u << 20)) return PZ_ERR_UNSUPPORTED;
     for (size_t i = 0; i < n_proofs; ++i)
         if (seed_offsets[i + 1] < seed_offsets[i]) return PZ_ERR_INVALID;
@@ -560,10 +622,12 @@ extern "C" int pz_verify_batch_bytes(pz_vk* vk, const uint8_t* bytes, size_t n_p
         // the proofs that decoded, moved together with their seeds: a refused proof's words never reach verify()
         std::vector<size_t> live, off(1, 0);
         std::vector<uint8_t> sd;
+        std::vector<uint64_t> inst;   // the live proofs' statements, moved together like their seeds
         for (size_t i = 0; i < n_proofs; ++i) {
             if (st[i] != 0) continue;
             if (live.size() != i) memmove(words.data() + live.size() * pw, words.data() + i * pw, pw * 8);
             live.push_back(i);
+            if (n_public) inst.insert(inst.end(), instances + i * n_public * 4, instances + (i + 1) * n_public * 4);
             if (seed_offsets[i + 1] > seed_offsets[i]) sd.insert(sd.end(), seeds + seed_offsets[i], seeds + seed_offsets[i + 1]);
             off.push_back(sd.size());
         }
@@ -573,7 +637,7 @@ extern "C" int pz_verify_batch_bytes(pz_vk* vk, const uint8_t* bytes, size_t n_p
         std::vector<uint64_t> hx(h_evals ? L * 4 : 0), ab(ab_affine ? L * 16 : 0);
         int ok = 0;
         verify(vk, words.data(), L, sd.data(), off.data(), v.data(), h_evals ? hx.data() : nullptr, ab_affine ? ab.data() : nullptr, &ok,
-               false);
+               false, n_public ? inst.data() : nullptr);
         for (size_t j = 0; j < L; ++j) {
             verdicts[live[j]] = v[j];
             if (h_evals) memcpy(h_evals + 4 * live[j], hx.data() + 4 * j, 32);
@@ -581,6 +645,18 @@ extern "C" int pz_verify_batch_bytes(pz_vk* vk, const uint8_t* bytes, size_t n_p
         }
         *all_ok = ok && L == n_proofs;
     });
+}
+
+}   // namespace
+
+extern "C" int pz_verify_batch_bytes(pz_vk* vk, const uint8_t* bytes, size_t n_proofs, const uint8_t* seeds, const size_t* seed_offsets,
+                                     int32_t* verdicts, uint64_t* h_evals, uint64_t* ab_affine, int* all_ok) {
+    return verify_batch_bytes(vk, nullptr, 0, bytes, n_proofs, seeds, seed_offsets, verdicts, h_evals, ab_affine, all_ok);
+}
+extern "C" int pz_verify_batch_bytes_pub(pz_vk* vk, const uint64_t* instances, size_t n_public, const uint8_t* bytes, size_t n_proofs,
+                                         const uint8_t* seeds, const size_t* seed_offsets, int32_t* verdicts, uint64_t* h_evals,
+                                         uint64_t* ab_affine, int* all_ok) {
+    return verify_batch_bytes(vk, instances, n_public, bytes, n_proofs, seeds, seed_offsets, verdicts, h_evals, ab_affine, all_ok);
 }
 
 extern "C" int pz_vk_free(pz_vk* vk) {

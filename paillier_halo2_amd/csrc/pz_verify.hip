@@ -50,7 +50,8 @@ __device__ Fr expr_line(const pz_vshape& s, unsigned L, const uint64_t* ev, cons
         const Fr beta = ld(pp + 4 * VP_BETA), gamma = ld(pp + 4 * VP_GAMMA), bx = ld(pp + 4 * VP_BX);
         Fr left = e(s.e_pz + 3 * L + 1), right = e(s.e_pz + 3 * L);
         for (unsigned c = 2 * L; c < 2 * L + 2 && c < m; ++c) {
-            const Fr v = c < A ? e(s.e_adv + 4 * c) : c < A + Lk ? e(s.e_lka + (c - A)) : e(s.e_fix + A);
+            // (the instance column, last when the key has one, is not opened: its value at x comes from pz_public.hip's k_instance_eval)
+            const Fr v = c < A ? e(s.e_adv + 4 * c) : c < A + Lk ? e(s.e_lka + (c - A)) : c == A + Lk ? e(s.e_fix + A) : ld(pp + 4 * VP_INST);
             const Fr vg = fp_add(v, gamma);
             left = fp_mul(left, fp_add(vg, fp_mul(beta, e(s.e_sig + c))));
             right = fp_mul(right, fp_add(vg, fp_mul(bx, ld(delta + 4ull * c))));

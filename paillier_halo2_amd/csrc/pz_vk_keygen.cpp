@@ -13,10 +13,11 @@
 namespace {
 int vk_keygen(pz_ctx* ctx, const pz_bases* bl, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk, const uint8_t* selectors,
               const uint64_t* constants, size_t n_constants, const uint32_t* map_col, const uint32_t* map_row, size_t tile, bool on_device,
-              uint64_t* fixed_affine, uint64_t* sigma_affine) {
+              size_t n_instance, uint64_t* fixed_affine, uint64_t* sigma_affine) {
     if (!ctx || !bl || !selectors || !map_col || !map_row || !fixed_affine || !sigma_affine || (n_constants && !constants)) return PZ_ERR_INVALID;
     if (k < 4 || k > 24 || !n_adv || !n_lk || lookup_bits >= k) return PZ_ERR_INVALID;
-    const size_t n = (size_t)1 << k, A = n_adv, F = A + 2, m = n_adv + n_lk + 1;
+    if (n_instance > 1) return PZ_ERR_INVALID;
+    const size_t n = (size_t)1 << k, A = n_adv, F = A + 2, m = n_adv + n_lk + 1 + n_instance;   // the instance column: the permutation's last
     if (n_constants > n) return PZ_ERR_INVALID;
     if (m > ((size_t)1 << 32) / n) return PZ_ERR_UNSUPPORTED;   // the copy-constraint map addresses cells with 32 bits
     size_t np = 0;
@@ -90,12 +91,29 @@ int vk_keygen(pz_ctx* ctx, const pz_bases* bl, uint32_t k, uint32_t lookup_bits,
 extern "C" int pz_vk_keygen_dev(pz_ctx* ctx, const pz_bases* bases_lagrange, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk,
                                 const uint8_t* d_selectors, const uint64_t* constants, size_t n_constants, const uint32_t* d_map_col,
                                 const uint32_t* d_map_row, size_t tile, uint64_t* fixed_affine, uint64_t* sigma_affine) {
-    return vk_keygen(ctx, bases_lagrange, k, lookup_bits, n_adv, n_lk, d_selectors, constants, n_constants, d_map_col, d_map_row, tile, true,
+    return vk_keygen(ctx, bases_lagrange, k, lookup_bits, n_adv, n_lk, d_selectors, constants, n_constants, d_map_col, d_map_row, tile, true, 0,
                      fixed_affine, sigma_affine);
 }
 extern "C" int pz_vk_keygen(pz_ctx* ctx, const pz_bases* bases_lagrange, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk,
                             const uint8_t* selectors, const uint64_t* constants, size_t n_constants, const uint32_t* map_col,
                             const uint32_t* map_row, size_t tile, uint64_t* fixed_affine, uint64_t* sigma_affine) {
-    return vk_keygen(ctx, bases_lagrange, k, lookup_bits, n_adv, n_lk, selectors, constants, n_constants, map_col, map_row, tile, false,
+    return vk_keygen(ctx, bases_lagrange, k, lookup_bits, n_adv, n_lk, selectors, constants, n_constants, map_col, map_row, tile, false, 0,
                      fixed_affine, sigma_affine);
+}
+// the same for a structure with the optional instance column (map_col / map_row u32 [m + n_instance][2^k], sigma_affine (m + n_instance) x 8);
+// n_public only has to be consistent with n_instance: the key's commitments do not depend on it
+extern "C" int pz_vk_keygen_pub_dev(pz_ctx* ctx, const pz_bases* bases_lagrange, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk,
+                                    size_t n_instance, size_t n_public, const uint8_t* d_selectors, const uint64_t* constants, size_t n_constants,
+                                    const uint32_t* d_map_col, const uint32_t* d_map_row, size_t tile, uint64_t* fixed_affine,
+                                    uint64_t* sigma_affine) {
+    if (n_instance ? n_public == 0 : n_public != 0) return PZ_ERR_INVALID;
+    return vk_keygen(ctx, bases_lagrange, k, lookup_bits, n_adv, n_lk, d_selectors, constants, n_constants, d_map_col, d_map_row, tile, true,
+                     n_instance, fixed_affine, sigma_affine);
+}
+extern "C" int pz_vk_keygen_pub(pz_ctx* ctx, const pz_bases* bases_lagrange, uint32_t k, uint32_t lookup_bits, size_t n_adv, size_t n_lk,
+                                size_t n_instance, size_t n_public, const uint8_t* selectors, const uint64_t* constants, size_t n_constants,
+                                const uint32_t* map_col, const uint32_t* map_row, size_t tile, uint64_t* fixed_affine, uint64_t* sigma_affine) {
+    if (n_instance ? n_public == 0 : n_public != 0) return PZ_ERR_INVALID;
+    return vk_keygen(ctx, bases_lagrange, k, lookup_bits, n_adv, n_lk, selectors, constants, n_constants, map_col, map_row, tile, false,
+                     n_instance, fixed_affine, sigma_affine);
 }

@@ -520,7 +520,7 @@ class Engine:
         """d_out[col] (Jacobian, 12 words) = the sum of the bases at the rows where the column's mask byte is non-zero (device pointers)"""
         self._chk(self.L.pz_g1_commit_mask_dev(self.ctx, bases.handle, VP(d_mask), n_cols, n, mask_stride, VP(d_out)), "pz_g1_commit_mask_dev")
 
-    def _vk_keygen(self, fn, name, bases_lagrange: Bases, k, lookup_bits, n_adv, n_lk, sel, constants, mc, mr, tile):
+    def _vk_keygen(self, fn, name, bases_lagrange: Bases, k, lookup_bits, n_adv, n_lk, sel, constants, mc, mr, tile, n_instance=0, n_public=0):
         if isinstance(constants, np.ndarray) and constants.dtype == np.uint64 and constants.ndim == 2:
             cw = np.ascontiguousarray(constants)
         else:
@@ -529,30 +529,36 @@ class Engine:
                 v = int(v)
                 for j in range(4):
                     cw[i, j] = (v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
-        m = n_adv + n_lk + 1
+        m = n_adv + n_lk + 1 + n_instance
         fixed, sigma = np.zeros((n_adv + 2, 8), dtype=np.uint64), np.zeros((m, 8), dtype=np.uint64)
+        if n_instance:            # fn is then the _pub entry point (the callers pass it): two more arguments
+            self._chk(fn(self.ctx, bases_lagrange.handle, k, lookup_bits, n_adv, n_lk, n_instance, n_public, VP(sel), _ptr(cw) if cw.size else VP(),
+                         cw.shape[0], VP(mc), VP(mr), tile, _ptr(fixed), _ptr(sigma)), name)
+            return fixed, sigma
         self._chk(fn(self.ctx, bases_lagrange.handle, k, lookup_bits, n_adv, n_lk, VP(sel), _ptr(cw) if cw.size else VP(), cw.shape[0], VP(mc),
                      VP(mr), tile, _ptr(fixed), _ptr(sigma)), name)
         return fixed, sigma
 
     def vk_keygen_dev(self, bases_lagrange: Bases, k: int, lookup_bits: int, n_adv: int, n_lk: int, d_selectors: int, constants,
-                      d_map_col: int, d_map_row: int, tile: int = 64) -> Tuple[np.ndarray, np.ndarray]:
+                      d_map_col: int, d_map_row: int, tile: int = 64, n_instance: int = 0, n_public: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """pz_vk_keygen_dev: the verifying key's commitments (fixed (n_adv + 2, 8), sigma (m, 8), affine) from the structure's DEVICE arrays;
         constants: canonical integers (or their (n, 4) words)"""
-        return self._vk_keygen(self.L.pz_vk_keygen_dev, "pz_vk_keygen_dev", bases_lagrange, k, lookup_bits, n_adv, n_lk, d_selectors, constants,
-                               d_map_col, d_map_row, tile)
+        fn, name = (self.L.pz_vk_keygen_pub_dev, "pz_vk_keygen_pub_dev") if n_instance else (self.L.pz_vk_keygen_dev, "pz_vk_keygen_dev")
+        return self._vk_keygen(fn, name, bases_lagrange, k, lookup_bits, n_adv, n_lk, d_selectors, constants,
+                               d_map_col, d_map_row, tile, n_instance, n_public)
 
     def vk_keygen(self, bases_lagrange: Bases, k: int, lookup_bits: int, n_adv: int, n_lk: int, selectors, constants, map_col, map_row,
-                  tile: int = 64) -> Tuple[np.ndarray, np.ndarray]:
+                  tile: int = 64, n_instance: int = 0, n_public: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """pz_vk_keygen: the same from HOST arrays (selectors uint8 [n_adv][2^k], map_col / map_row 32-bit [m][2^k]), uploaded tile by tile"""
-        n, m = 1 << k, n_adv + n_lk + 1
+        n, m = 1 << k, n_adv + n_lk + 1 + n_instance
         sel = np.ascontiguousarray(selectors, dtype=np.uint8)
         mc = np.ascontiguousarray(map_col).view(np.uint32)
         mr = np.ascontiguousarray(map_row).view(np.uint32)
         if sel.shape != (n_adv, n) or mc.shape != (m, n) or mr.shape != (m, n):
             raise ValueError("selectors must be [n_adv][2^k] bytes, map_col / map_row [m][2^k] 32-bit words")
-        return self._vk_keygen(self.L.pz_vk_keygen, "pz_vk_keygen", bases_lagrange, k, lookup_bits, n_adv, n_lk, sel.ctypes.data, constants,
-                               mc.ctypes.data, mr.ctypes.data, tile)
+        fn, name = (self.L.pz_vk_keygen_pub, "pz_vk_keygen_pub") if n_instance else (self.L.pz_vk_keygen, "pz_vk_keygen")
+        return self._vk_keygen(fn, name, bases_lagrange, k, lookup_bits, n_adv, n_lk, sel.ctypes.data, constants,
+                               mc.ctypes.data, mr.ctypes.data, tile, n_instance, n_public)
 
     def keygen_columns_dev(self, bases: Bases, d_cols: int, n_cols: int, col_stride_u64: int, k: int, log_e: int, omega_n, omega_n_inv,
                            n_inv, coset_gens, d_commit: int, d_ext: int = 0, ext_stride_u64: int = 0):
@@ -587,20 +593,42 @@ class Engine:
         self._chk(self.L.pz_pairing_check_dev(self.ctx, VP(d_g1), VP(d_g2), n_checks, pairs_per_check, VP(d_ok)),
                   "pz_pairing_check_dev")
 
-    def vk_create(self, k: int, blinding_factors: int, n_adv: int, n_lk: int, fixed, sigma, g0, g2, s_g2) -> VkHandle:
-        """pz_vk_create: fixed (n_adv + 2, 8), sigma (m, 8), g0 (8), g2 / s_g2 (16 words or 128 RawBytes each)"""
+    def vk_create(self, k: int, blinding_factors: int, n_adv: int, n_lk: int, fixed, sigma, g0, g2, s_g2, n_instance: int = 0,
+                  n_public: int = 0) -> VkHandle:
+        """pz_vk_create[_pub]: fixed (n_adv + 2, 8), sigma (m, 8), g0 (8), g2 / s_g2 (16 words or 128 RawBytes each); m counts the instance
+        column when n_instance = 1"""
         w16 = lambda b: np.frombuffer(bytes(b), dtype="<u8").astype(np.uint64) if isinstance(b, (bytes, bytearray)) else _np(b).reshape(16)
         f, sg, g, a, b = _np(fixed, 8), _np(sigma, 8), _np(g0).reshape(8), w16(g2), w16(s_g2)
-        if f.shape[0] != n_adv + 2 or sg.shape[0] != n_adv + n_lk + 1:
-            raise ValueError("fixed must hold n_adv + 2 points and sigma n_adv + n_lk + 1")
+        if f.shape[0] != n_adv + 2 or sg.shape[0] != n_adv + n_lk + 1 + n_instance:
+            raise ValueError("fixed must hold n_adv + 2 points and sigma n_adv + n_lk + 1 (+ 1 with an instance column)")
         h = VP()
+        if n_instance:
+            self._chk(self.L.pz_vk_create_pub(self.ctx, k, blinding_factors, n_adv, n_lk, n_instance, n_public, _ptr(f), _ptr(sg), _ptr(g), _ptr(a),
+                                              _ptr(b), C.byref(h)), "pz_vk_create_pub")
+            return VkHandle(self, h)
         self._chk(self.L.pz_vk_create(self.ctx, k, blinding_factors, n_adv, n_lk, _ptr(f), _ptr(sg), _ptr(g), _ptr(a), _ptr(b), C.byref(h)),
                   "pz_vk_create")
         return VkHandle(self, h)
 
-    def verify_batch_dev(self, vk: VkHandle, proofs, seeds: Sequence[bytes], want_h: bool = False, want_ab: bool = False):
-        """pz_verify_batch: proofs (B, vk.proof_words) in the ABI layout -> (all_ok, verdicts [bool], h_evals (B, 4) or None,
-        ab_affine (B, 2, 8) or None)"""
+    @staticmethod
+    def _instance_words(instances, B: int) -> np.ndarray:
+        """B lists of public values (integers below 2^256) -> (B, L, 4) canonical words"""
+        L = len(instances[0])
+        if len(instances) != B or any(len(v) != L for v in instances):
+            raise ValueError("one list of public values per proof, all of one length")
+        w = np.zeros((B, L, 4), dtype=np.uint64)
+        for i, vals in enumerate(instances):
+            for j, v in enumerate(vals):
+                v = int(v)
+                if v < 0 or v >> 256:
+                    raise ValueError("a public value must fit 256 bits")
+                for q in range(4):
+                    w[i, j, q] = (v >> (64 * q)) & 0xFFFFFFFFFFFFFFFF
+        return w
+
+    def verify_batch_dev(self, vk: VkHandle, proofs, seeds: Sequence[bytes], want_h: bool = False, want_ab: bool = False, instances=None):
+        """pz_verify_batch[_pub]: proofs (B, vk.proof_words) in the ABI layout -> (all_ok, verdicts [bool], h_evals (B, 4) or None,
+        ab_affine (B, 2, 8) or None).  instances: per proof the list of its public values (a key with an instance column)"""
         pr = _np(proofs).reshape(-1, vk.proof_words)
         B = pr.shape[0]
         if len(seeds) != B:
@@ -612,6 +640,11 @@ class Engine:
         hev = np.zeros((B, 4), dtype=np.uint64) if want_h else None
         ab = np.zeros((B, 2, 8), dtype=np.uint64) if want_ab else None
         ok = C.c_int()
+        if instances is not None:
+            iw = self._instance_words(instances, B)
+            self._chk(self.L.pz_verify_batch_pub(vk.handle, _ptr(iw), iw.shape[1], _ptr(pr), B, VP(blob.ctypes.data), _ptr(offs), VP(verd.ctypes.data),
+                                                 _ptr(hev) if want_h else None, _ptr(ab) if want_ab else None, C.byref(ok)), "pz_verify_batch_pub")
+            return bool(ok.value), [bool(v) for v in verd], hev, ab
         self._chk(self.L.pz_verify_batch(vk.handle, _ptr(pr), B, VP(blob.ctypes.data), _ptr(offs), VP(verd.ctypes.data),
                                          _ptr(hev) if want_h else None, _ptr(ab) if want_ab else None, C.byref(ok)), "pz_verify_batch")
         return bool(ok.value), [bool(v) for v in verd], hev, ab
@@ -657,7 +690,7 @@ class Engine:
         self._chk(self.L.pz_proof_decode(vk.handle, VP(b.ctypes.data), B, _ptr(words), VP(st.ctypes.data)), "pz_proof_decode")
         return words, st
 
-    def verify_batch_bytes_dev(self, vk: VkHandle, data, seeds: Sequence[bytes], want_h: bool = False, want_ab: bool = False):
+    def verify_batch_bytes_dev(self, vk: VkHandle, data, seeds: Sequence[bytes], want_h: bool = False, want_ab: bool = False, instances=None):
         """pz_verify_batch_bytes: data (B, vk.wire_bytes) uint8 -> the tuple of verify_batch_dev"""
         b = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1, vk.wire_bytes)
         B = b.shape[0]
@@ -670,6 +703,12 @@ class Engine:
         hev = np.zeros((B, 4), dtype=np.uint64) if want_h else None
         ab = np.zeros((B, 2, 8), dtype=np.uint64) if want_ab else None
         ok = C.c_int()
+        if instances is not None:
+            iw = self._instance_words(instances, B)
+            self._chk(self.L.pz_verify_batch_bytes_pub(vk.handle, _ptr(iw), iw.shape[1], VP(b.ctypes.data), B, VP(blob.ctypes.data), _ptr(offs),
+                                                       VP(verd.ctypes.data), _ptr(hev) if want_h else None, _ptr(ab) if want_ab else None,
+                                                       C.byref(ok)), "pz_verify_batch_bytes_pub")
+            return bool(ok.value), [bool(v) for v in verd], hev, ab
         self._chk(self.L.pz_verify_batch_bytes(vk.handle, VP(b.ctypes.data), B, VP(blob.ctypes.data), _ptr(offs), VP(verd.ctypes.data),
                                                _ptr(hev) if want_h else None, _ptr(ab) if want_ab else None, C.byref(ok)),
                   "pz_verify_batch_bytes")

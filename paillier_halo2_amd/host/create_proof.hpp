@@ -60,7 +60,10 @@ struct Structure {   // what keygen derives from the circuit (INPUT)
     // when set they are used as they are and the host vectors above stay empty -- no host copy, no PCIe crossing
     const uint8_t* d_selectors = nullptr;
     const uint32_t *d_map_col = nullptr, *d_map_row = nullptr;
-    size_t m() const { return n_adv + n_lk + 1; }
+    // public inputs (csrc/pz_public.hip): n_instance = 1 adds the instance column as the permutation's LAST column, rows [0, n_public) the
+    // statement's values and zero above; it is neither committed nor opened
+    size_t n_instance = 0, n_public = 0;
+    size_t m() const { return n_adv + n_lk + 1 + n_instance; }
 };
 
 struct Part {   // a part of the quotient's domain (prover.py Domain._parts): part A = g <w_2n>, part B = g w_4n <w_n>
@@ -422,6 +425,7 @@ struct Session {
     std::vector<std::vector<uint64_t>> ev;
     pz_shplonk* state = nullptr;
     int phase = 0;
+    std::vector<uint64_t> instances;   // n_public x 4 words, Montgomery: the instance column's rows (a key with an instance column)
 
     Session(Ctx& cx_, ProvingKey& pk_, Workspace& w_, uint64_t* d_cols_, Rng rng_) : cx(cx_), pk(pk_), w(w_), d_cols(d_cols_), rng(rng_) {}
     ~Session() {
@@ -454,6 +458,11 @@ struct Session {
         const size_t n = d.n, W = pk.st.n_adv + pk.st.n_lk;
         blind_rows(cx, w, rng, d_cols, W, n, d.usable);
         PZP_CK(pz_dev_copy(cx.c, d_cols + W * n * 4, pk.const_lagrange, n * 32));
+        if (pk.st.n_instance) {   // the instance column, last of d_cols: not blinded, not committed (halo2's instance columns)
+            if (instances.size() != 4 * pk.st.n_public) PZP_FAIL(PZ_ERR_INVALID, "instances do not match the key's n_public");
+            PZP_CK(pz_dev_memset(cx.c, d_cols + (W + 1) * n * 4, 0, n * 32));
+            PZP_CK(pz_upload(cx.c, d_cols + (W + 1) * n * 4, instances.data(), instances.size() * 8));
+        }
         commit(pk.bl, d_cols, W, w.out12);
         if (after_launch) after_launch();
         affine(w.out12, W, out_affine);

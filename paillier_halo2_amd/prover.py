@@ -30,7 +30,7 @@ exist on the extended domain all at once -- only the grand products Z (which the
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -61,14 +61,22 @@ class CircuitStructure:
     table: Optional[Sequence[int]] = None      # default: 0 .. 2^lookup_bits - 1, then zeros
     minimum_rows: Optional[int] = None         # the calculate_params argument the column COUNT came from (layout.RowBudget; informational)
     n_adv_used: Optional[int] = None           # advice columns the cells fill (<= n_adv: K4's break-point table has n_adv_used + 1 entries)
+    # public inputs: n_instance = 1 adds the instance column as the permutation's LAST column (map_col / map_row
+    # then have m = n_adv + n_lk + 2 columns); public_cells: the (column, row) of the exposed advice cells, instance row i tied to cell i
+    n_instance: int = 0
+    public_cells: Optional[Sequence[Tuple[int, int]]] = None
 
     @property
     def n_adv(self) -> int:
         return int(self.selectors.shape[0])
 
     @property
+    def n_public(self) -> int:
+        return len(self.public_cells) if self.n_instance and self.public_cells is not None else 0
+
+    @property
     def m(self) -> int:
-        return self.n_adv + self.n_lk + 1
+        return self.n_adv + self.n_lk + 1 + self.n_instance
 
 
 def _torch():
@@ -405,9 +413,12 @@ class Workspace:
 
 
 def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 64, hooks=None, ws: Optional[Workspace] = None,
-                 timings: Optional[Dict[str, float]] = None, eng: Optional[Engine] = None) -> Proof:
+                 timings: Optional[Dict[str, float]] = None, eng: Optional[Engine] = None, instances: Optional[Sequence[int]] = None) -> Proof:
     """cols: int64 CUDA tensor [m][2^k][4]: the advice columns then the lookup-advice columns as K4 wrote them (rows >= max_rows
-    zero); the last column (constants) and the blinding rows are filled here; cols is consumed (it ends up in coefficient form).
+    zero); the constants column, the instance column (last; a structure with n_instance = 1) and the blinding rows are filled here; cols
+    is consumed (it ends up in coefficient form).
+    instances: the public values (integers below r, st.n_public of them) of a structure with an instance column: absorbed into the
+    transcript before the first commitment, written to rows [0, n_public) of the instance column (not blinded, not committed).
     tr: a Transcript (or plain Challenges).  Runs on the engine's stream (bind_torch_stream).
     seed: of the device generator the blinding values come from (tests and benches want reproducible proofs); None = 64 bits of OS
     randomness per proof (os.urandom) -- what a caller who needs the proof to be zero-knowledge passes.
@@ -470,9 +481,23 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
     def extend(src, cnt, dst, pt):
         eng.ntt_extend_dev(src.data_ptr(), cnt, 4 * n, dst.data_ptr(), 4 * pt["size"], k, pt["log_e"], M(d.omega), pt["gens"], None)
 
+    # ---- 0. the statement (a structure with an instance column): absorbed first, then the column's rows
+    if st.n_instance and not st.n_public:
+        raise ValueError("a structure with the instance column names its public cells (at least one)")
+    n_pub = st.n_public if st.n_instance else 0
+    if (len(instances) if instances is not None else 0) != n_pub:
+        raise ValueError("this key's statement has %d public values" % n_pub)
+    if n_pub:
+        if any(not 0 <= int(v) < FR for v in instances):
+            raise ValueError("a public value must be a field element")
+        inst_m = np.stack([M(int(v)) for v in instances]).astype(np.uint64)
+        tr.absorb_scalars(inst_m.reshape(n_pub, 1, 4))
     # ---- 1. advice: blinding rows, commitments -> theta
     cols[:W, u:] = _random_fr(gen, W, n - u)
     cols[W] = pk.const_lagrange
+    if st.n_instance:
+        cols[W + 1] = 0
+        cols[W + 1, :n_pub] = torch.from_numpy(inst_m.view(np.int64)).to(cols.device)
     if "advice" in hooks:
         hooks["advice"](cols)
     c_adv = commit(bl, cols, W, 4 * n)

@@ -47,16 +47,17 @@ class NativeKey:
             sel = st.selectors.to(torch.uint8).contiguous()
             mc, mr = st.map_col.to(torch.int32).contiguous(), st.map_row.to(torch.int32).contiguous()
             assert tuple(sel.shape) == (st.n_adv, n) and tuple(mc.shape) == (st.m, n) == tuple(mr.shape)
-            eng._chk(eng.L.pz_pk_create_dev(eng.ctx, bases_lagrange.handle, bases_monomial.handle, st.k, st.lookup_bits, st.blinding_factors,
-                                            st.max_rows, st.n_adv, st.n_lk, VP(sel.data_ptr()), _p(consts_w), len(st.constants), VP(mc.data_ptr()),
-                                            VP(mr.data_ptr()), tile, R, C.byref(h)), "pz_pk_create_dev")
+            eng._chk(eng.L.pz_pk_create_pub_dev(eng.ctx, bases_lagrange.handle, bases_monomial.handle, st.k, st.lookup_bits, st.blinding_factors,
+                                                st.max_rows, st.n_adv, st.n_lk, st.n_instance, st.n_public, VP(sel.data_ptr()), _p(consts_w),
+                                                len(st.constants), VP(mc.data_ptr()), VP(mr.data_ptr()), tile, R, C.byref(h)), "pz_pk_create_pub_dev")
         else:
             sel = np.ascontiguousarray(_host(st.selectors), dtype=np.uint8)
             mc = np.ascontiguousarray(_host(st.map_col)).view(np.uint32)
             mr = np.ascontiguousarray(_host(st.map_row)).view(np.uint32)
             assert sel.shape == (st.n_adv, n) and mc.shape == (st.m, n) == mr.shape
-            eng._chk(eng.L.pz_pk_create(eng.ctx, bases_lagrange.handle, bases_monomial.handle, st.k, st.lookup_bits, st.blinding_factors, st.max_rows,
-                                        st.n_adv, st.n_lk, _p(sel), _p(consts_w), len(st.constants), _p(mc), _p(mr), tile, R, C.byref(h)), "pz_pk_create")
+            eng._chk(eng.L.pz_pk_create_pub(eng.ctx, bases_lagrange.handle, bases_monomial.handle, st.k, st.lookup_bits, st.blinding_factors,
+                                            st.max_rows, st.n_adv, st.n_lk, st.n_instance, st.n_public, _p(sel), _p(consts_w), len(st.constants),
+                                            _p(mc), _p(mr), tile, R, C.byref(h)), "pz_pk_create_pub")
         self.handle = h
         out = [C.c_size_t() for _ in range(5)]
         eng._chk(eng.L.pz_pk_info(h, *[C.byref(x) for x in out]), "pz_pk_info")
@@ -71,12 +72,13 @@ class NativeKey:
         self.eng = eng
         self.st = CircuitStructure(k=ns.k, lookup_bits=ns.lookup_bits, max_rows=ns.max_rows, blinding_factors=ns.blinding_factors,
                                    selectors=np.zeros((ns.n_adv, 0), dtype=np.uint8), n_lk=ns.n_lk, constants=ns.constants(), map_col=None, map_row=None,
-                                   minimum_rows=ns.minimum_rows, n_adv_used=ns.n_adv_used)
+                                   minimum_rows=ns.minimum_rows, n_adv_used=ns.n_adv_used, n_instance=ns.n_instance,
+                                   public_cells=ns.public_cells() if ns.n_instance else None)
         h = VP()
         R = (1 << 64) - 1 if ext_resident_cols is None else int(ext_resident_cols)
-        eng._chk(eng.L.pz_pk_create_dev(eng.ctx, bases_lagrange.handle, bases_monomial.handle, ns.k, ns.lookup_bits, ns.blinding_factors, ns.max_rows,
-                                        ns.n_adv, ns.n_lk, VP(ns.d_selectors), VP(ns._constants), ns.n_constants, VP(ns.d_map_col), VP(ns.d_map_row),
-                                        tile, R, C.byref(h)), "pz_pk_create_dev")
+        eng._chk(eng.L.pz_pk_create_pub_dev(eng.ctx, bases_lagrange.handle, bases_monomial.handle, ns.k, ns.lookup_bits, ns.blinding_factors,
+                                            ns.max_rows, ns.n_adv, ns.n_lk, ns.n_instance, ns.n_public, VP(ns.d_selectors), VP(ns._constants),
+                                            ns.n_constants, VP(ns.d_map_col), VP(ns.d_map_row), tile, R, C.byref(h)), "pz_pk_create_pub_dev")
         self.handle = h
         out = [C.c_size_t() for _ in range(5)]
         eng._chk(eng.L.pz_pk_info(h, *[C.byref(x) for x in out]), "pz_pk_info")
@@ -94,9 +96,18 @@ class NativeKey:
             self.handle = None
 
 
-def create_proof(key: NativeKey, d_cols: int, tr, seed: int = 0, blinding: Optional[np.ndarray] = None) -> Proof:
+def _canon_words(vals) -> np.ndarray:
+    w = np.zeros((len(vals), 4), dtype=np.uint64)
+    for i, v in enumerate(vals):
+        w[i] = consts.int_to_limbs(int(v), 4)
+    return w
+
+
+def create_proof(key: NativeKey, d_cols: int, tr, seed: int = 0, blinding: Optional[np.ndarray] = None, instances=None) -> Proof:
     """d_cols: device pointer of [m][2^k][4] words (the K4 columns; consumed).  tr: prover.Transcript / HashTranscript / Challenges.
-    blinding: optional uint64 array of key.blinding_words caller-supplied random words (else the library's seeded stream)"""
+    blinding: optional uint64 array of key.blinding_words caller-supplied random words (else the library's seeded stream).
+    instances: the public values (integers below r) of a key with an instance column (pz_proof_begin_pub): absorbed into the transcript
+    before the first commitment"""
     eng, st, L = key.eng, key.st, key.eng.L
     if isinstance(tr, Challenges):
         tr = Transcript(tr)
@@ -106,10 +117,17 @@ def create_proof(key: NativeKey, d_cols: int, tr, seed: int = 0, blinding: Optio
     adv = z(A + Lk)
     bl = np.ascontiguousarray(blinding, dtype=np.uint64) if blinding is not None else None
     # no caller randomness: the library's seeded stream must be asked for by name (pz.h PZ_BLINDING_SEEDED_TEST_STREAM: tests, benches)
-    eng._chk(L.pz_proof_begin(key.handle, VP(d_cols), seed, _p(bl) if bl is not None else None, (1 << 64) - 1 if bl is None else bl.size, C.byref(h), _p(adv)),
-             "pz_proof_begin")
+    if instances is None:
+        eng._chk(L.pz_proof_begin(key.handle, VP(d_cols), seed, _p(bl) if bl is not None else None, (1 << 64) - 1 if bl is None else bl.size, C.byref(h),
+                                  _p(adv)), "pz_proof_begin")
+    else:
+        iw = _canon_words(instances)
+        eng._chk(L.pz_proof_begin_pub(key.handle, VP(d_cols), seed, _p(bl) if bl is not None else None, (1 << 64) - 1 if bl is None else bl.size,
+                                      _p(iw), iw.shape[0], C.byref(h), _p(adv)), "pz_proof_begin_pub")
     try:
         pr = Proof()
+        if instances is not None and len(instances):
+            tr.absorb_scalars(np.stack([M(int(v)) for v in instances]).astype(np.uint64).reshape(-1, 1, 4))
         tr.absorb_affine(adv)
         c_theta = M(tr.squeeze("theta"))         # (the limb arrays are named: a pointer into a temporary would dangle)
         ap, sp = z(Lk), z(Lk)
@@ -160,7 +178,9 @@ class NativeStructure:
     KINDS = {"encrypt": 0, "add": 1, "encrypt_uniform": 2}
 
     def __init__(self, eng: Engine, kind: str, enc_bits: int, limb_bits: int, lookup_bits: int, k: int, exp_g: int = 0, exp_r: int = 0,
-                 minimum_rows: int = 20, blinding_factors: int = 6):
+                 minimum_rows: int = 20, blinding_factors: int = 6, expose: bool = False):
+        """expose: add the instance column (pz_structure_expose): n, g and the ciphertext(s) become the statement; the maps then have
+        m = n_adv + n_lk + 2 columns"""
         self.eng, self.k, self.lookup_bits, self.blinding_factors, self.minimum_rows = eng, k, lookup_bits, blinding_factors, minimum_rows
         Ln = enc_bits // limb_bits
         ew = -(-Ln * limb_bits // 64)
@@ -173,10 +193,17 @@ class NativeStructure:
         eng._chk(eng.L.pz_structure_info(h, *[C.byref(x) for x in out]), "pz_structure_info")
         (self.n_adv, self.n_adv_used, self.n_lk, self.max_rows, self.n_constants, self.n_cells, self.n_lookups, self.n_steps_g,
          self.n_steps_r) = (int(x.value) for x in out)
+        self.n_instance = self.n_public = 0
+        self.d_cell_col = self.d_cell_row = 0
+        if expose:
+            eng._chk(eng.L.pz_structure_expose(h), "pz_structure_expose")
+            ni, npub, cc, cr = C.c_size_t(), C.c_size_t(), VP(), VP()
+            eng._chk(eng.L.pz_structure_public(h, C.byref(ni), C.byref(npub), C.byref(cc), C.byref(cr)), "pz_structure_public")
+            self.n_instance, self.n_public, self.d_cell_col, self.d_cell_row = int(ni.value), int(npub.value), int(cc.value or 0), int(cr.value or 0)
         ptrs = [VP() for _ in range(6)]
         eng._chk(eng.L.pz_structure_arrays(h, *[C.byref(x) for x in ptrs]), "pz_structure_arrays")
         self.d_selectors, self.d_map_col, self.d_map_row, self.d_starts, self._constants, self._starts_host = (int(x.value or 0) for x in ptrs)
-        self.m = self.n_adv + self.n_lk + 1
+        self.m = self.n_adv + self.n_lk + 1 + self.n_instance
 
     @staticmethod
     def _words(x: int, Ln: int):
@@ -201,6 +228,21 @@ class NativeStructure:
         for dst, src in ((sel, self.d_selectors), (mc, self.d_map_col), (mr, self.d_map_row)):
             self.eng._chk(self.eng.L.pz_download(self.eng.ctx, _p(dst), VP(src), dst.nbytes), "pz_download")
         return sel, mc, mr
+
+    def public_cells(self):
+        """-> [(column, row)] of the exposed advice cells, instance row i tied to cell i (downloaded)"""
+        cc, cr = np.zeros(self.n_public, dtype=np.uint32), np.zeros(self.n_public, dtype=np.uint32)
+        for dst, src in ((cc, self.d_cell_col), (cr, self.d_cell_row)):
+            self.eng._chk(self.eng.L.pz_download(self.eng.ctx, _p(dst), VP(src), dst.nbytes), "pz_download")
+        return [(int(a), int(b)) for a, b in zip(cc, cr)]
+
+    def gather_public(self, d_cols: int) -> list:
+        """the statement read off a witness: the exposed cells of the column block at d_cols ([..][2^k][4] words) as integers
+        (pz_public_gather_dev)"""
+        out = np.zeros((self.n_public, 4), dtype=np.uint64)
+        self.eng._chk(self.eng.L.pz_public_gather_dev(self.eng.ctx, VP(d_cols), 4 << self.k, VP(self.d_cell_col), VP(self.d_cell_row), self.n_public,
+                                                      _p(out)), "pz_public_gather_dev")
+        return [sum(int(w) << (64 * j) for j, w in enumerate(row)) for row in out]
 
     def key(self, bases_lagrange: Bases, bases_monomial: Bases, tile: int = 64, ext_resident_cols: Optional[int] = None) -> "NativeKey":
         """pz_pk_create_dev on the structure's own device arrays"""

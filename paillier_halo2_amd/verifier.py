@@ -20,7 +20,7 @@ import hashlib
 import os
 import struct
 from dataclasses import dataclass
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -71,16 +71,19 @@ class VerifyingKey:
     n_sets: int
     fixed: np.ndarray
     sigma: np.ndarray
+    n_instance: int = 0            # 1: the key's permutation ends with the instance column (public inputs)
+    n_public: int = 0              # values of the statement
 
     @property
     def m(self) -> int:
-        return self.n_adv + self.n_lk + 1
+        return self.n_adv + self.n_lk + 1 + self.n_instance
 
     @classmethod
     def from_proving_key(cls, pk) -> "VerifyingKey":
         vk = pk.vk_commitments()
         st = pk.st
-        return cls(st.k, st.blinding_factors, st.n_adv, st.n_lk, pk.n_sets, vk["fixed"], vk["sigma"])
+        return cls(st.k, st.blinding_factors, st.n_adv, st.n_lk, pk.n_sets, vk["fixed"], vk["sigma"], getattr(st, "n_instance", 0),
+                   getattr(st, "n_public", 0))
 
 
     @classmethod
@@ -90,9 +93,10 @@ class VerifyingKey:
         are torch tensors on the device (used where they are) or numpy arrays (uploaded tile by tile), or a NativeStructure (the device
         arrays of a pz_circuit_structure_dev handle)."""
         k, A, Lk = st.k, st.n_adv, st.n_lk
+        ni, npub = getattr(st, "n_instance", 0), getattr(st, "n_public", 0)
         if hasattr(st, "d_selectors"):                      # a pz_structure handle's arrays
             fixed, sigma = eng.vk_keygen_dev(bases_lagrange, k, st.lookup_bits, A, Lk, st.d_selectors, st.constants(), st.d_map_col,
-                                             st.d_map_row, tile)
+                                             st.d_map_row, tile, ni, npub)
         else:
             if getattr(st, "table", None) is not None:
                 raise ValueError("keygen_vk commits the table 0 .. 2^lookup_bits - 1; this structure carries another one")
@@ -102,14 +106,14 @@ class VerifyingKey:
 
                 sel = st.selectors.cuda().to(torch.uint8).contiguous()
                 mc, mr = st.map_col.cuda().to(torch.int32).contiguous(), st.map_row.cuda().to(torch.int32).contiguous()
-                if tuple(sel.shape) != (A, 1 << k) or tuple(mc.shape) != (A + Lk + 1, 1 << k) or mc.shape != mr.shape:
+                if tuple(sel.shape) != (A, 1 << k) or tuple(mc.shape) != (A + Lk + 1 + ni, 1 << k) or mc.shape != mr.shape:
                     raise ValueError("selectors must be [n_adv][2^k], map_col / map_row [m][2^k]")
                 torch.cuda.current_stream().synchronize()   # the conversions above may have run on another stream than the library's
                 fixed, sigma = eng.vk_keygen_dev(bases_lagrange, k, st.lookup_bits, A, Lk, sel.data_ptr(), consts_, mc.data_ptr(), mr.data_ptr(),
-                                                 tile)
+                                                 tile, ni, npub)
             else:
-                fixed, sigma = eng.vk_keygen(bases_lagrange, k, st.lookup_bits, A, Lk, st.selectors, consts_, st.map_col, st.map_row, tile)
-        return cls(k, st.blinding_factors, A, Lk, -(-(A + Lk + 1) // CHUNK), fixed, sigma)
+                fixed, sigma = eng.vk_keygen(bases_lagrange, k, st.lookup_bits, A, Lk, st.selectors, consts_, st.map_col, st.map_row, tile, ni, npub)
+        return cls(k, st.blinding_factors, A, Lk, -(-(A + Lk + 1 + ni) // CHUNK), fixed, sigma, ni, npub)
 
 
 def _ints(a) -> List[List[int]]:
@@ -143,9 +147,43 @@ def record_seed(prefix: str) -> bytes:
     return int(prefix[1:-1]).to_bytes(8, "little")
 
 
-def replay_transcript(seed: bytes, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarray]) -> Dict[str, int]:
+def public_inputs(kind: str, n: int, g: int, c: int, c1: Optional[int] = None, c2: Optional[int] = None, *, enc_bits: int, limb_bits: int) -> List[int]:
+    """the statement of a circuit with the instance column, in the column's row order: little-endian limbs of limb_bits,
+    n | g | c (kind "encrypt" / "encrypt_uniform": c = g^m r^n mod n^2) or n | g | c1 | c2 | c ("add": c = c1 c2 mod n^2); n, g, c1, c2 have
+    enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)"""
+    Ln = enc_bits // limb_bits
+    mask = (1 << limb_bits) - 1
+    limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
+    if kind == "add":
+        if c1 is None or c2 is None:
+            raise ValueError("the add statement names both ciphertexts c1 and c2")
+        parts = [(n, Ln), (g, Ln), (c1, Ln), (c2, Ln), (c, 2 * Ln)]
+    elif kind in ("encrypt", "encrypt_uniform"):
+        parts = [(n, Ln), (g, Ln), (c, 2 * Ln)]
+    else:
+        raise ValueError("kind must be encrypt, add or encrypt_uniform")
+    for v, cnt in parts:
+        if int(v) < 0 or int(v) >> (limb_bits * cnt):
+            raise ValueError("a value does not fit its %d limbs" % cnt)
+    return [x for v, cnt in parts for x in limbs(v, cnt)]
+
+
+def instance_eval(k: int, values: Sequence[int], x: int) -> int:
+    """the instance column at x: sum_i v_i l_i(x), l_i(x) = (x^n - 1)/n w^i / (x - w^i); x must not lie on the domain"""
+    n = 1 << k
+    w = consts.fr_omega(k)
+    acc, wi = 0, 1
+    for v in values:
+        acc = (acc + v * wi % R * pow((x - wi) % R, -1, R)) % R
+        wi = wi * w % R
+    return acc * ((pow(x, n, R) - 1) % R) % R * pow(n, -1, R) % R
+
+
+def replay_transcript(seed: bytes, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarray], instances: Optional[Sequence[int]] = None) -> Dict[str, int]:
     h = hashlib.blake2b(bytes(seed), digest_size=64, person=b"Halo2-Transcript")
     out: Dict[str, int] = {}
+    for v in instances or ():            # the statement: scalars (tag 2, Montgomery words) after the seed, before the first commitment
+        h.update(b"\x02" + struct.pack("<4Q", *(int(x) for x in consts.fr_mont_limbs(int(v)))))
 
     def items(tag, a, words):
         a = np.ascontiguousarray(a, dtype="<u8").reshape(-1, words)
@@ -186,9 +224,10 @@ def _lagrange(k: int, bf: int, x: int) -> Tuple[int, int, int]:
     return li(0), li(u), sum(li(i) for i in range(u + 1, n)) % R
 
 
-def constraint_expression(vk: VerifyingKey, e: Dict[str, List[List[int]]], beta: int, gamma: int, y: int, x: int) -> int:
+def constraint_expression(vk: VerifyingKey, e: Dict[str, List[List[int]]], beta: int, gamma: int, y: int, x: int,
+                          inst_x: Optional[int] = None) -> int:
     """the constraint lines of these circuits at x folded by y (halo2's expressions in the order the prover folds them): equals
-    h(x) (x^n - 1) for an honest proof"""
+    h(x) (x^n - 1) for an honest proof.  inst_x: the instance column at x (instance_eval), the last permuted value of a key that has one"""
     A, Lk = vk.n_adv, vk.n_lk
     l0, llast, lblind = _lagrange(vk.k, vk.blinding_factors, x)
     lact = (1 - llast - lblind) % R
@@ -202,6 +241,8 @@ def constraint_expression(vk: VerifyingKey, e: Dict[str, List[List[int]]], beta:
         a0, a1, a2, a3 = e["advice"][j]
         line(e["fixed"][j][0] * (a0 + a1 * a2 - a3))
     vals = [e["advice"][j][0] for j in range(A)] + [e["lookup_advice"][j][0] for j in range(Lk)] + [e["fixed"][A][0]]
+    if inst_x is not None:
+        vals.append(inst_x % R)
     m = len(vals)
     S = -(-m // CHUNK)
     z = e["perm_z"]
@@ -254,7 +295,7 @@ class _Terms:
     b_scalars: List[int]          # ... in B
 
 
-def _terms(vk: VerifyingKey, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarray], seed: bytes) -> _Terms:
+def _terms(vk: VerifyingKey, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarray], seed: bytes, instances: Optional[Sequence[int]] = None) -> _Terms:
     A, Lk, m, S = vk.n_adv, vk.n_lk, vk.m, vk.n_sets
     F = A + 2
     shapes = {"advice": (A, 4), "lookup_advice": (Lk, 1), "fixed": (F, 1), "sigma": (m, 1), "perm_z": (S, 3), "lookup_z": (Lk, 2),
@@ -271,12 +312,18 @@ def _terms(vk: VerifyingKey, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarra
                 return bad
     except KeyError:
         return bad
-    ch = replay_transcript(seed, com, ev)
+    inst = [int(v) for v in instances] if vk.n_instance else None
+    if inst is not None and any(not 0 <= v < R for v in inst):
+        return bad                                         # a value >= r is no statement
+    ch = replay_transcript(seed, com, ev, inst)
     e = {f: _ints(ev[f]) for f in shapes}
     x = ch["x"]
     n = 1 << vk.k
     xn = pow(x, n, R)
-    h_eval = constraint_expression(vk, e, ch["beta"], ch["gamma"], ch["y"], x) * pow(xn - 1, -1, R) % R
+    if xn == 1:
+        return bad                                         # a challenge on the domain
+    inst_x = instance_eval(vk.k, inst, x) if inst is not None else None
+    h_eval = constraint_expression(vk, e, ch["beta"], ch["gamma"], ch["y"], x, inst_x) * pow(xn - 1, -1, R) % R
     ok = True
     if "h" in ev:                                          # a proof that states h(x) must state the expected one
         ok = _ints(ev["h"]) == [[h_eval]]
@@ -388,13 +435,26 @@ def _as_parts(proof, vk: VerifyingKey):
     return proof.commitments, proof.evals
 
 
-def verify_batch(eng, params: VerifierParams, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes]) -> Tuple[bool, List[bool]]:
+def _check_instances(vk: VerifyingKey, instances, B: int):
+    """-> one list of public values per proof (None for a key without the instance column); ValueError on a wrong count"""
+    if not vk.n_instance:
+        if instances is not None:
+            raise ValueError("this key has no instance column")
+        return [None] * B
+    if instances is None or len(instances) != B or any(len(v) != vk.n_public for v in instances):
+        raise ValueError("this key's statement has %d public values per proof" % vk.n_public)
+    return [list(v) for v in instances]
+
+
+def verify_batch(eng, params: VerifierParams, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes], instances=None) -> Tuple[bool, List[bool]]:
     """-> (every proof holds, per-proof verdicts).  proofs: prover.Proof objects or (prover_job.read_proofs record, "p<i>/") pairs; seeds:
-    the transcript seed of each (record_seed for the compiled prover's).  params: VerifierParams (or a srs.ParamsKZG, whose G2 elements must not be zero)."""
+    the transcript seed of each (record_seed for the compiled prover's).  params: VerifierParams (or a srs.ParamsKZG, whose G2 elements must not be zero).
+    instances: per proof the list of its public values (public_inputs) when the key has an instance column."""
     if not isinstance(params, VerifierParams):
         params = VerifierParams.from_params(params)
     assert len(proofs) == len(seeds) and len(proofs) > 0
-    terms = [_terms(vk, *_as_parts(p, vk), s) for p, s in zip(proofs, seeds)]
+    inst = _check_instances(vk, instances, len(proofs))
+    terms = [_terms(vk, *_as_parts(p, vk), s, iv) for p, s, iv in zip(proofs, seeds, inst)]
     B = len(terms)
     idents = [t.ok for t in terms]
     live = [i for i in range(B) if terms[i].bases.shape[0]]
@@ -418,8 +478,8 @@ def verify_batch(eng, params: VerifierParams, vk: VerifyingKey, proofs: Sequence
     return all(per), per
 
 
-def verify_proof(eng, params, vk: VerifyingKey, proof, seed: bytes) -> bool:
-    return verify_batch(eng, params, vk, [proof], [seed])[0]
+def verify_proof(eng, params, vk: VerifyingKey, proof, seed: bytes, instances=None) -> bool:
+    return verify_batch(eng, params, vk, [proof], [seed], None if instances is None else [instances])[0]
 
 
 # ---- the device batch verifier (include/pz.h: pz_vk_create / pz_verify_batch): the same verdicts, Fr work in HIP ----------------------
@@ -431,7 +491,8 @@ def native_key(eng, params, vk: VerifyingKey):
     """-> engine.VkHandle of the key and the params' g[0], g2, s_g2 (pz_vk_create refuses zero G2 and an identity g[0])"""
     if not isinstance(params, VerifierParams):
         params = VerifierParams.from_params(params)
-    return eng.vk_create(vk.k, vk.blinding_factors, vk.n_adv, vk.n_lk, vk.fixed, vk.sigma, params.g0, params.g2, params.s_g2)
+    return eng.vk_create(vk.k, vk.blinding_factors, vk.n_adv, vk.n_lk, vk.fixed, vk.sigma, params.g0, params.g2, params.s_g2, vk.n_instance,
+                         vk.n_public)
 
 
 def pack_proof(vk: VerifyingKey, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarray]):
@@ -457,10 +518,11 @@ def pack_proof(vk: VerifyingKey, com: Dict[str, np.ndarray], ev: Dict[str, np.nd
     return np.concatenate(parts)
 
 
-def verify_batch_native(eng, params, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes], handle=None) -> Tuple[bool, List[bool]]:
+def verify_batch_native(eng, params, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes], handle=None, instances=None) -> Tuple[bool, List[bool]]:
     """verify_batch on the device batch verifier: the same arguments and (every proof holds, per-proof verdicts).  handle: a native_key
     of (params, vk) to reuse; made and freed here otherwise."""
     assert len(proofs) == len(seeds) and len(proofs) > 0
+    inst = _check_instances(vk, instances, len(proofs))
     packed = [pack_proof(vk, *_as_parts(p, vk)) for p in proofs]
     live = [i for i, w in enumerate(packed) if w is not None]
     per = [False] * len(proofs)
@@ -469,7 +531,8 @@ def verify_batch_native(eng, params, vk: VerifyingKey, proofs: Sequence, seeds: 
     own = handle is None
     h = native_key(eng, params, vk) if own else handle
     try:
-        _, got, _, _ = eng.verify_batch_dev(h, np.stack([packed[i] for i in live]), [seeds[i] for i in live])
+        _, got, _, _ = eng.verify_batch_dev(h, np.stack([packed[i] for i in live]), [seeds[i] for i in live],
+                                            instances=[inst[i] for i in live] if vk.n_instance else None)
     finally:
         if own:
             h.free()
@@ -481,6 +544,7 @@ def verify_batch_native(eng, params, vk: VerifyingKey, proofs: Sequence, seeds: 
 # ---- halo2 wire bytes (include/pz.h: pz_g1_*compress, pz_proof_encode / decode, pz_verify_batch_bytes) ----------
 VK_MAGIC = b"PZVK"
 VK_VERSION = 1
+VK_VERSION_PUB = 2        # a key with the instance column: two more header words, n_instance and n_public
 
 
 def _proof_shapes(vk: VerifyingKey):
@@ -500,7 +564,7 @@ def _codec_key(eng, vk: VerifyingKey):
     """a VkHandle for the proof codec alone: the wire layout depends on the key's shape only, so the generators stand in for the params"""
     g1 = np.concatenate([consts.int_to_limbs(v * consts.MONT_R % consts.FQ_P, 4) for v in (1, 2)]).astype(np.uint64)
     g2 = eng.g2_generator()
-    return eng.vk_create(vk.k, vk.blinding_factors, vk.n_adv, vk.n_lk, vk.fixed, vk.sigma, g1, g2, g2)
+    return eng.vk_create(vk.k, vk.blinding_factors, vk.n_adv, vk.n_lk, vk.fixed, vk.sigma, g1, g2, g2, vk.n_instance, vk.n_public)
 
 
 def _with_key(eng, vk, handle, fn):
@@ -551,10 +615,14 @@ def proof_from_bytes(eng, vk: VerifyingKey, data: bytes, handle=None):
 
 
 def vk_to_bytes(eng, vk: VerifyingKey) -> bytes:
-    """"PZVK", u32 version, k, blinding_factors, n_adv, n_lk, then the fixed and the sigma commitments compressed"""
+    """"PZVK", u32 version, k, blinding_factors, n_adv, n_lk, then the fixed and the sigma commitments compressed.  A key with the instance
+    column is version 2: n_instance and n_public follow n_lk (a key without it gives version 1, byte for byte what it always gave)"""
     pts = np.concatenate([np.asarray(vk.fixed, dtype=np.uint64).reshape(-1, 8), np.asarray(vk.sigma, dtype=np.uint64).reshape(-1, 8)])
-    if pts.shape[0] != 2 * vk.n_adv + vk.n_lk + 3:
-        raise ValueError("fixed must hold n_adv + 2 points and sigma n_adv + n_lk + 1")
+    if pts.shape[0] != 2 * vk.n_adv + vk.n_lk + 3 + vk.n_instance:
+        raise ValueError("fixed must hold n_adv + 2 points and sigma n_adv + n_lk + 1 (+ 1 with an instance column)")
+    if vk.n_instance:
+        return VK_MAGIC + struct.pack("<7I", VK_VERSION_PUB, vk.k, vk.blinding_factors, vk.n_adv, vk.n_lk, vk.n_instance, vk.n_public) + \
+            eng.g1_compress(pts).tobytes()
     return VK_MAGIC + struct.pack("<5I", VK_VERSION, vk.k, vk.blinding_factors, vk.n_adv, vk.n_lk) + eng.g1_compress(pts).tobytes()
 
 
@@ -563,21 +631,30 @@ def vk_from_bytes(eng, data: bytes) -> VerifyingKey:
     if len(data) < 24 or data[:4] != VK_MAGIC:
         raise ValueError("not a verifying key file")
     ver, k, bf, A, Lk = struct.unpack("<5I", data[4:24])
-    if ver != VK_VERSION:
+    hdr, ni, npub = 24, 0, 0
+    if ver == VK_VERSION_PUB:
+        if len(data) < 32:
+            raise ValueError("not a verifying key file")
+        ni, npub = struct.unpack("<2I", data[24:32])
+        hdr = 32
+        if ni != 1 or npub == 0:
+            raise ValueError("a version-2 key has one instance column and at least one public value")
+    elif ver != VK_VERSION:
         raise ValueError("verifying key file version %d" % ver)
-    n = 2 * A + Lk + 3
-    if len(data) != 24 + 32 * n:
-        raise ValueError("a key of this shape is %d bytes, got %d" % (24 + 32 * n, len(data)))
-    pts, st = eng.g1_decompress(data[24:])
+    n = 2 * A + Lk + 3 + ni
+    if len(data) != hdr + 32 * n:
+        raise ValueError("a key of this shape is %d bytes, got %d" % (hdr + 32 * n, len(data)))
+    pts, st = eng.g1_decompress(data[hdr:])
     if st.any():
         raise ValueError("%d of the key's points do not decode" % int(np.count_nonzero(st)))
-    return VerifyingKey(k, bf, A, Lk, -(-(A + Lk + 1) // CHUNK), pts[:A + 2].copy(), pts[A + 2:].copy())
+    return VerifyingKey(k, bf, A, Lk, -(-(A + Lk + 1 + ni) // CHUNK), pts[:A + 2].copy(), pts[A + 2:].copy(), ni, npub)
 
 
-def verify_batch_bytes(eng, params, vk: VerifyingKey, proofs: Sequence[bytes], seeds: Sequence[bytes], handle=None) -> Tuple[bool, List[bool]]:
+def verify_batch_bytes(eng, params, vk: VerifyingKey, proofs: Sequence[bytes], seeds: Sequence[bytes], handle=None, instances=None) -> Tuple[bool, List[bool]]:
     """verify_batch for proofs that arrive as halo2 wire bytes (pz_verify_batch_bytes: decoded on the device; a proof that does not decode
     is False and the others are judged without it).  ValueError if a proof's length is not proof_size_bytes(vk)."""
     assert len(proofs) == len(seeds) and len(proofs) > 0
+    inst = _check_instances(vk, instances, len(proofs))
     size = proof_size_bytes(vk)
     for p in proofs:
         if len(p) != size:
@@ -586,7 +663,7 @@ def verify_batch_bytes(eng, params, vk: VerifyingKey, proofs: Sequence[bytes], s
     own = handle is None
     h = native_key(eng, params, vk) if own else handle
     try:
-        ok, per, _, _ = eng.verify_batch_bytes_dev(h, data, seeds)
+        ok, per, _, _ = eng.verify_batch_bytes_dev(h, data, seeds, instances=inst if vk.n_instance else None)
     finally:
         if own:
             h.free()

@@ -187,6 +187,42 @@ extern "C" {
     pub fn pz_proof_decode(vk: *mut pz_vk, bytes: *const u8, n_proofs: usize, out_words: *mut u64, status: *mut i32) -> c_int;
     pub fn pz_verify_batch_bytes(vk: *mut pz_vk, bytes: *const u8, n_proofs: usize, seeds: *const u8, seed_offsets: *const usize,
                                  verdicts: *mut i32, h_evals: *mut u64, ab_affine: *mut u64, all_ok: *mut c_int) -> c_int;
+    // public inputs: one optional instance column (n, g and the ciphertext as the statement); DESIGN.md section 15.5
+    pub fn pz_circuit_public_cells(kind: c_int, limbs_n: u32, limb_bits: u32, lookup_bits: u32, n_steps_g: usize, n_steps_r: usize,
+                                   cells_out: *mut u64, capacity: usize, n_public: *mut usize) -> c_int;
+    pub fn pz_structure_expose(st: *mut pz_structure) -> c_int;
+    pub fn pz_structure_public(st: *const pz_structure, n_instance: *mut usize, n_public: *mut usize, d_cell_col: *mut *const u32,
+                               d_cell_row: *mut *const u32) -> c_int;
+    pub fn pz_public_gather_dev(ctx: *mut pz_ctx, d_cols: *const u64, col_stride: usize, d_cell_col: *const u32, d_cell_row: *const u32,
+                                n_public: usize, out_words: *mut u64) -> c_int;
+    pub fn pz_instance_eval_dev(ctx: *mut pz_ctx, k: u32, omega: *const u64, n_inv: *const u64, d_instances: *const u64, n_public: usize,
+                                n_proofs: usize, d_x: *const u64, d_out: *mut u64, d_flags: *mut i32) -> c_int;
+    pub fn pz_pk_create_pub(ctx: *mut pz_ctx, bases_lagrange: *const pz_bases, bases_monomial: *const pz_bases, k: u32, lookup_bits: u32,
+                            blinding_factors: u32, max_rows: usize, n_adv: usize, n_lk: usize, n_instance: usize, n_public: usize,
+                            selectors: *const u8, constants: *const u64, n_constants: usize, map_col: *const u32, map_row: *const u32,
+                            tile: usize, ext_resident_cols: usize, out: *mut *mut pz_pk) -> c_int;
+    pub fn pz_pk_create_pub_dev(ctx: *mut pz_ctx, bases_lagrange: *const pz_bases, bases_monomial: *const pz_bases, k: u32, lookup_bits: u32,
+                                blinding_factors: u32, max_rows: usize, n_adv: usize, n_lk: usize, n_instance: usize, n_public: usize,
+                                d_selectors: *const u8, constants: *const u64, n_constants: usize, d_map_col: *const u32,
+                                d_map_row: *const u32, tile: usize, ext_resident_cols: usize, out: *mut *mut pz_pk) -> c_int;
+    pub fn pz_vk_keygen_pub_dev(ctx: *mut pz_ctx, bases_lagrange: *const pz_bases, k: u32, lookup_bits: u32, n_adv: usize, n_lk: usize,
+                                n_instance: usize, n_public: usize, d_selectors: *const u8, constants: *const u64, n_constants: usize,
+                                d_map_col: *const u32, d_map_row: *const u32, tile: usize, fixed_affine: *mut u64,
+                                sigma_affine: *mut u64) -> c_int;
+    pub fn pz_vk_keygen_pub(ctx: *mut pz_ctx, bases_lagrange: *const pz_bases, k: u32, lookup_bits: u32, n_adv: usize, n_lk: usize,
+                            n_instance: usize, n_public: usize, selectors: *const u8, constants: *const u64, n_constants: usize,
+                            map_col: *const u32, map_row: *const u32, tile: usize, fixed_affine: *mut u64, sigma_affine: *mut u64) -> c_int;
+    pub fn pz_vk_create_pub(ctx: *mut pz_ctx, k: u32, blinding_factors: u32, n_adv: usize, n_lk: usize, n_instance: usize, n_public: usize,
+                            fixed_affine: *const u64, sigma_affine: *const u64, g0_affine: *const u64, g2: *const u64, s_g2: *const u64,
+                            out: *mut *mut pz_vk) -> c_int;
+    pub fn pz_proof_begin_pub(pk: *mut pz_pk, d_cols: *mut u64, seed: u64, blinding: *const u64, n_blinding: usize, instances: *const u64,
+                              n_public: usize, out: *mut *mut pz_proof, advice_affine: *mut u64) -> c_int;
+    pub fn pz_verify_batch_pub(vk: *mut pz_vk, instances: *const u64, n_public: usize, proofs: *const u64, n_proofs: usize, seeds: *const u8,
+                               seed_offsets: *const usize, verdicts: *mut i32, h_evals: *mut u64, ab_affine: *mut u64,
+                               all_ok: *mut c_int) -> c_int;
+    pub fn pz_verify_batch_bytes_pub(vk: *mut pz_vk, instances: *const u64, n_public: usize, bytes: *const u8, n_proofs: usize,
+                                     seeds: *const u8, seed_offsets: *const usize, verdicts: *mut i32, h_evals: *mut u64,
+                                     ab_affine: *mut u64, all_ok: *mut c_int) -> c_int;
     // ParamsKZG files: the G2 codec and subgroup check, read_custom / write_custom / downsize and the consistency check of a params file
     pub fn pz_g2_compress(ctx: *mut pz_ctx, points: *const u64, n: usize, bytes: *mut u8) -> c_int;
     pub fn pz_g2_decompress(ctx: *mut pz_ctx, bytes: *const u8, n: usize, points: *mut u64, status: *mut i32, n_bad: *mut u64) -> c_int;
