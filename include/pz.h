@@ -422,6 +422,10 @@ int pz_pairing_check_dev(pz_ctx* ctx, const uint64_t* d_g1, const uint64_t* d_g2
  *                seeds[seed_offsets[i] .. seed_offsets[i + 1]) (n_proofs + 1 offsets; the caller's bytes, as prove_connected's 8-byte
  *                little-endian index).  verdicts[i] = 1 if h(x) (x^n - 1) equals the constraint expression, the proof states that h(x),
  *                evaluations are canonical and the opening's pairing check holds, else 0; *all_ok = every verdict is 1.
+ *                The words come unchecked, and pz_verify_batch is never laxer than pz_verify_batch_bytes: every commitment of a proof
+ *                must be the identity (0, 0) or have canonical coordinates (below p) on the curve -- pz_g1_check_dev's rule, the wire
+ *                decoder's statuses 1 and 2, pz_pairing_check_dev's -1, halo2's `read` -- or that proof alone gets verdict 0 (one launch
+ *                over the batch's commitments before the fold; the other proofs are judged without it).
  *                One fold with random weights (OS randomness) and one 2-pair check decide an all-good batch; otherwise (or when ab_affine
  *                is asked for) n_proofs independent checks in one pz_pairing_check_dev launch give the verdicts.  Optional (NULL
  *                allowed): h_evals n x 4 (the h(x) each proof implies, Montgomery), ab_affine n x 16 (each proof's SHPLONK points A then

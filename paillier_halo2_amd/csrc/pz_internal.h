@@ -220,6 +220,9 @@ int pz_verify_terms_launch(pz_ctx* ctx, const pz_vshape& s, size_t B, const uint
 // Strides in 64-bit words.  Asynchronous on the context's stream.
 int pz_instance_eval_launch(pz_ctx* ctx, uint32_t k, const uint64_t omega[4], const uint64_t n_inv[4], const uint64_t* d_instances, size_t L,
                             size_t B, const uint64_t* d_x, size_t x_stride, uint64_t* d_out, size_t out_stride, int32_t* d_flags);
+// pz_g1_check_dev's predicate (pz_msm.hip: the identity, or canonical coordinates on the curve) over n_groups x group affine points:
+// d_flags[g] = 1 if a point of group g fails it, else 0.  Asynchronous on the context's stream.
+int pz_g1_check_groups_launch(pz_ctx* ctx, const uint64_t* d_points, size_t n_groups, size_t group, int32_t* d_flags);
 int pz_verify_fold_launch(pz_ctx* ctx, const pz_vshape& s, size_t B, int mode, const uint64_t* d_r, uint64_t* d_vksc,
                           const uint64_t* d_gpart, const uint64_t* d_own, uint64_t* d_cols);
 

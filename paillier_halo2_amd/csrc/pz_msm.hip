@@ -1855,25 +1855,41 @@ extern "C" int pz_srs_lagrange_from_monomial_dev(pz_ctx* ctx, uint32_t k, const 
 }
 
 // on-curve check of affine points (identity (0,0) accepted): the is_on_curve assertion of halo2curves' read_raw
+__device__ __forceinline__ bool g1_point_ok(const G1Affine& p) {
+    if (aff_is_inf(p)) return true;
+    // coordinates must be canonical (< p) and satisfy y^2 = x^3 + 3
+    Fq three = fp_add(fp_add(fp_one<FqTag>(), fp_one<FqTag>()), fp_one<FqTag>());
+    Fq rhs = fp_add(fp_mul(fp_sqr(p.x), p.x), three);
+    Fq rx = p.x, ry = p.y;
+    fp_reduce_once(rx);
+    fp_reduce_once(ry);
+    bool canon = true;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) canon = canon && rx.v[k] == p.x.v[k] && ry.v[k] == p.y.v[k];
+    Fq d = fp_sub(fp_sqr(p.y), rhs);
+    return canon && fp_is_zero(d);
+}
+
 __global__ __launch_bounds__(256) void k_g1_check(const G1Affine* __restrict__ pts, size_t n, unsigned long long* bad) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    G1Affine p = aff_load(pts + i);
-    bool ok = aff_is_inf(p);
-    if (!ok) {
-        // coordinates must be canonical (< p) and satisfy y^2 = x^3 + 3
-        Fq three = fp_add(fp_add(fp_one<FqTag>(), fp_one<FqTag>()), fp_one<FqTag>());
-        Fq rhs = fp_add(fp_mul(fp_sqr(p.x), p.x), three);
-        Fq rx = p.x, ry = p.y;
-        fp_reduce_once(rx);
-        fp_reduce_once(ry);
-        bool canon = true;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) canon = canon && rx.v[k] == p.x.v[k] && ry.v[k] == p.y.v[k];
-        Fq d = fp_sub(fp_sqr(p.y), rhs);
-        ok = canon && fp_is_zero(d);
-    }
-    if (!ok) atomicAdd(bad, 1ull);
+    if (!g1_point_ok(aff_load(pts + i))) atomicAdd(bad, 1ull);
+}
+
+// the same predicate over n points in groups of `group` consecutive ones: flags[i / group] becomes 1 if point i fails
+__global__ __launch_bounds__(256) void k_g1_check_groups(const G1Affine* __restrict__ pts, size_t n, size_t group, int32_t* __restrict__ flags) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!g1_point_ok(aff_load(pts + i))) atomicOr(flags + i / group, 1);
+}
+
+int pz_g1_check_groups_launch(pz_ctx* ctx, const uint64_t* d_points, size_t n_groups, size_t group, int32_t* d_flags) {
+    const size_t n = n_groups * group;
+    if (!n) return PZ_OK;
+    HIPCHK(ctx, hipMemsetAsync(d_flags, 0, n_groups * sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(k_g1_check_groups, dim3(pz_div_up(n, 256)), dim3(256), 0, ctx->stream, (const G1Affine*)d_points, n, group, d_flags);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
 }
 
 extern "C" int pz_g1_check_dev(pz_ctx* ctx, const uint64_t* d_points, size_t n, uint64_t* n_bad) {

@@ -3,6 +3,8 @@
 // over the whole batch; everything per member of a proof runs in pz_verify.hip's kernels, the MSM is K1 and the check pz_pairing_check_dev.
 // paillier_halo2_amd/verifier.py::verify_batch states the same verdicts in Python integers.
 //
+// Every proof's commitments are held to the wire decoder's rule for a point first (one launch: the identity, or canonical coordinates on
+// the curve); a proof that fails it, states a non-canonical evaluation or misses the identity at x is refused without touching the rest.
 // Happy path: one fold with random weights into K1's two columns over [fixed | sigma | g0 | every proof's commitments], ONE MSM, ONE
 // 2-pair check.  Otherwise (a failed fold, a failed identity, or the caller asks for each proof's A and B) per-proof checks without a
 // B x (all bases) matrix: one B-column MSM over the key's bases and g0, one 2-column MSM per proof over its own commitments (a sub-range
@@ -333,6 +335,11 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
     ck(pz_dev_memset(ctx, d_gp.d, 0, B * PZ_VSETS_MAX * 32));
     ck(pz_dev_copy(ctx, d_bases.d, vk->d_vkb, s.n_vkb * 64ull));
     ck(pz_upload(ctx, d_bases.p() + 8ull * s.n_vkb, h_com.data(), h_com.size() * 8));
+    // the caller's commitments come unchecked: one launch holds every one to what the wire decoder asks of a point (the identity, or
+    // canonical coordinates on the curve); a proof with a commitment that fails is refused, the others are judged without it
+    Dev d_cfl(ctx);
+    d_cfl.alloc(B * 4);
+    ck(pz_g1_check_groups_launch(ctx, d_bases.p() + 8ull * s.n_vkb, B, s.n_own, d_cfl.p<int32_t>()));
     Dev d_inst(ctx), d_x(ctx), d_fl(ctx);
     std::vector<int32_t> iflags(B, 0);
     if (NP) {   // the instance column at every proof's x, straight into its scalar block
@@ -348,9 +355,10 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
     }
     ck(pz_verify_terms_launch(ctx, s, B, (const uint32_t*)vk->d_members, d_ev.p(), d_pp.p(), (const uint64_t*)vk->d_delta, d_h.p(),
                               d_id.p<int32_t>(), d_own.p(), d_vksc.p(), d_gp.p()));
-    std::vector<int32_t> ident(B);
+    std::vector<int32_t> ident(B), cflags(B);
     std::vector<uint64_t> hx(B * 4);
     ck(pz_download(ctx, ident.data(), d_id.d, B * 4));
+    ck(pz_download(ctx, cflags.data(), d_cfl.d, B * 4));
     ck(pz_download(ctx, hx.data(), d_h.d, B * 32));
     if (NP) {
         ck(pz_download(ctx, iflags.data(), d_fl.d, B * 4));
@@ -359,7 +367,7 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
     if (h_evals) memcpy(h_evals, hx.data(), B * 32);
     bool all_ident = true;
     for (size_t i = 0; i < B; ++i) {
-        good[i] = good[i] && (ident[i] == 1 || !stated_h);
+        good[i] = good[i] && cflags[i] == 0 && (ident[i] == 1 || !stated_h);
         all_ident = all_ident && good[i];
     }
     uint32_t nwin = 0;

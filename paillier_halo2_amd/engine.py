@@ -170,6 +170,10 @@ class Engine:
             detail = self.L.pz_last_hip_error(self.ctx).decode() if self.ctx else ""
             raise PzError(rc, where, detail)
 
+    def last_hip_error(self) -> str:
+        """pz_last_hip_error: the text of the context's last failed HIP call or device-side complaint, "" if there was none"""
+        return self.L.pz_last_hip_error(self.ctx).decode() if self.ctx else ""
+
     def close(self):
         if self.ctx:
             self.L.pz_free(self.ctx)

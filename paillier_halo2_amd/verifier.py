@@ -12,7 +12,9 @@ Per proof (what halo2-axiom's `verify_proof` does for these circuits [D]):
 verify_batch folds B proofs with random r_i (os.urandom) into sum r_i A_i, sum r_i B_i: ONE device MSM (K1, two scalar columns) over the
 key's fixed and sigma commitments (once, their scalars summed over the proofs), the generator and every proof's own commitments, then ONE
 2-pair pz_pairing_check_dev.  If that fails, or an identity of step 2 fails, the per-proof verdicts come from B independent checks in
-one pz_pairing_check_dev launch.  The transcript seed is the caller's bytes (not a digest of the verifying key).
+one pz_pairing_check_dev launch.  A proof with a commitment that is off the curve or has a coordinate that is not canonical (the identity
+(0, 0) apart), or with an evaluation >= r, is False by itself and takes no part in the rest.  The transcript seed is the caller's bytes
+(not a digest of the verifying key).
 """
 from __future__ import annotations
 
@@ -33,6 +35,7 @@ COMMITMENT_ROUNDS = ((("advice", "lookup_advice"), ("theta",)), (("perm_inputs",
                      (("perm_z", "lookup_z", "random"), ("y",)), (("h",), ("x",)))
 EVAL_FAMILIES = ("advice", "lookup_advice", "fixed", "sigma", "perm_z", "lookup_z", "perm_inputs", "perm_tables", "random")
 _MONT_INV = pow(consts.MONT_R, -1, R)
+_MONT_INV_Q = pow(consts.MONT_R, -1, consts.FQ_P)
 
 
 @dataclass
@@ -128,6 +131,27 @@ def _ints(a) -> List[List[int]]:
             vals.append(v * _MONT_INV % R)
         out.append(vals)
     return out
+
+
+def _points_ok(a) -> bool:
+    """pz_g1_check_dev's rule for every row of (count, 8) Montgomery words: the identity (0, 0), or canonical coordinates (below p) of a
+    point on y^2 = x^3 + 3 -- what the wire decoder and halo2's `read` ask of a commitment"""
+    p = consts.FQ_P
+    for row in np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 8):
+        xm, ym = consts.limbs_to_int(row[:4]), consts.limbs_to_int(row[4:])
+        if xm == 0 and ym == 0:
+            continue
+        if xm >= p or ym >= p:
+            return False
+        x, y = xm * _MONT_INV_Q % p, ym * _MONT_INV_Q % p
+        if (y * y - x * x * x - 3) % p:
+            return False
+    return True
+
+
+def _evals_canonical(a) -> bool:
+    """every evaluation's Montgomery words are below r"""
+    return all(consts.limbs_to_int(w) < R for w in np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4))
 
 
 def proof_from_record(rec: Dict[str, np.ndarray], prefix: str, vk: VerifyingKey):
@@ -311,6 +335,10 @@ def _terms(vk: VerifyingKey, com: Dict[str, np.ndarray], ev: Dict[str, np.ndarra
             if tuple(np.asarray(com[f]).shape) != (cnt, 8):
                 return bad
     except KeyError:
+        return bad
+    # words nobody has decoded: a commitment off the curve or with a coordinate that is not canonical, or an evaluation >= r, refuses
+    # the proof (the device verifier's rule, pz_verify_batch; never laxer than the wire decoder)
+    if not all(_points_ok(com[f]) for f in cshapes) or not all(_evals_canonical(ev[f]) for f in ev if f in shapes or f in ("constants", "h")):
         return bad
     inst = [int(v) for v in instances] if vk.n_instance else None
     if inst is not None and any(not 0 <= v < R for v in inst):

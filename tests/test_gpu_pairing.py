@@ -157,3 +157,48 @@ def test_pairing_check_1024(eng, dev):
           % ((t1 - t0) * 1e3, n, (t2 - t1) * 1e3, n / (t2 - t1)))
     assert one[0] == want[0]
     assert got.tolist() == want
+
+
+@pytest.mark.parametrize("m", [1, 3, 5])
+def test_pairing_check_pairs_and_ragged_count(eng, dev, m):
+    """pz_pairing_check_dev beyond the verifier's one use (2 pairs): pairs_per_check in {1, 3, 5}, n_checks in {1, 63, 65} (below, at
+    and past the 64-lane workgroup; the kernel strides its per-pair state by n_checks).  Points of known logs, [a_j] G from K1's
+    fixed-base kernel and [b_j] G2 from pz_g2_mul_dev; the expected result in integers: 1 exactly when sum_j a_j b_j == 0 (mod r)."""
+    rng = random.Random(15 + m)
+    for n in (1, 63, 65):
+        a = [[rng.randrange(1, B.R) for _ in range(m)] for _ in range(n)]
+        b = [[rng.randrange(1, B.R) for _ in range(m)] for _ in range(n)]
+        for i in range(0, n, 2):                 # about half the checks hold: the last a_j solved (m = 1: only the identity solves it)
+            a[i][m - 1] = -sum(a[i][j] * b[i][j] for j in range(m - 1)) * pow(b[i][m - 1], -1, B.R) % B.R
+        if n > 3 and m > 1:
+            # check 1: every pair has an identity on one side (G1, G2 or both): each contributes 1 and the check holds trivially
+            a[1] = [0, rng.randrange(1, B.R)] + [0] * (m - 2)
+            b[1] = [rng.randrange(1, B.R), 0] + [0] * (m - 2)
+            # check 2: one live pair e([a] G, [b] G2) with a b != 0 next to identity pairs: must be 0, not 1
+            a[2] = [0] * (m - 1) + [rng.randrange(1, B.R)]
+            b[2] = [0] * (m - 1) + [rng.randrange(1, B.R)]
+            # check 4: the live pair is trivial on the G1 side only
+            a[4] = [0] * m
+        want = [1 if sum(x * y for x, y in zip(a[i], b[i])) % B.R == 0 else 0 for i in range(n)]
+        if m == 1:                               # one pair: a live pair is 0, an identity pair is 1
+            assert want == [1 if i % 2 == 0 else 0 for i in range(n)] and all(a[i][0] == 0 for i in range(0, n, 2))
+        else:
+            assert want[0] == 1 and (n < 3 or (want[1], want[2], want[3], want[4]) == (1, 0, 0, 1))
+        if n == 65:
+            a[64][m - 1] = rng.randrange(1, B.R)
+        g1 = eng.g1_fixed_base_mul(np.array([B.fr_words(s) for row in a for s in row], dtype=np.uint64))
+        g1 = np.ascontiguousarray(g1, dtype=np.uint64).reshape(n, m, 8)
+        g2 = g2_mul_dev(eng, dev, [B.G2] * (n * m), [s for row in b for s in row]).reshape(n, m, 16)
+        assert not g1[a_is_zero(a)].any() and not g2[a_is_zero(b)].any()      # log 0 is the all-zero identity
+        if n == 65:                              # a point off its curve in the last pair of check 64: -1 for that check alone
+            x, y = B._from_words(g1[64, m - 1, :4]), B._from_words(g1[64, m - 1, 4:])
+            g1[64, m - 1] = B.g1_words((x, (y + 1) % B.P))
+            want[64] = -1
+        d_ok = dev.empty(n * 4)
+        eng.upload(d_ok, np.full(n, 7, dtype=np.int32))
+        eng.pairing_check_dev(dev.put(g1), dev.put(g2), n, m, d_ok)
+        assert eng.download(d_ok, n, np.int32).tolist() == want, (m, n)
+
+
+def a_is_zero(rows):
+    return np.array([[v == 0 for v in row] for row in rows], dtype=bool)
