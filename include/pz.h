@@ -869,6 +869,29 @@ int pz_verify_batch_bytes_pub(pz_vk* vk, const uint64_t* instances, size_t n_pub
                               int* all_ok);
 
 /* ---------------------------------------------------------------------------------------------
+ * KEY BINDING (host/key_digest.hpp): the verifying key's digest at the head of the Fiat-Shamir transcript, where
+ * halo2 absorbs vk.transcript_repr.  Opt-in: without it every transcript starts from the caller's seed alone and every proof, key and file
+ * is byte for byte what it was.
+ *   D = BLAKE2b-512, personalisation the 16 bytes "PZ-Key-Digest-v1", over six little-endian u64 -- k, blinding_factors, n_adv, n_lk,
+ *   n_instance, n_public -- then fixed_affine ((n_adv + 2) x 8 words) and sigma_affine ((n_adv + n_lk + 1 + n_instance) x 8 words), both as
+ *   pz_pk_commitments, pz_vk_keygen* and pz_vk_create[_pub] carry them (Montgomery words, little-endian).  lookup_bits is pinned by the table
+ *   column's commitment; the params are not part of it.  A BOUND transcript is the unbound one with D || seed for its seed bytes.
+ * pz_key_digest   host only: no context, no device.  n_instance = 0 with n_public != 0, or a null pointer: PZ_ERR_INVALID.
+ * pz_pk_digest, pz_vk_digest   the key's D, computed on the first request and kept in the object.  The prover stepper (pz_proof_*) never
+ *                 sees the transcript: its caller asks pz_pk_digest and seeds with D || seed.
+ * pz_vk_bind      on != 0: pz_verify_batch, pz_verify_batch_pub, pz_verify_batch_bytes and pz_verify_batch_bytes_pub replay every proof from
+ *                 D || seed; 0 (the default of a new key): from the seed alone.  A proof made one way does not verify the other way
+ *                 (verdict 0, not an error).
+ * pz_vk_is_bound  *on = 1 or 0.
+ * ------------------------------------------------------------------------------------------- */
+int pz_key_digest(uint32_t k, uint32_t blinding_factors, size_t n_adv, size_t n_lk, size_t n_instance, size_t n_public,
+                  const uint64_t* fixed_affine, const uint64_t* sigma_affine, uint8_t out[64]);
+int pz_pk_digest(const pz_pk* pk, uint8_t out[64]);
+int pz_vk_digest(const pz_vk* vk, uint8_t out[64]);
+int pz_vk_bind(pz_vk* vk, int on);
+int pz_vk_is_bound(const pz_vk* vk, int* on);
+
+/* ---------------------------------------------------------------------------------------------
  * measurement helpers (used by bench.py; not part of the reference surface).  Issue-rate microbenchmarks: libpz_probe.so.
  * ------------------------------------------------------------------------------------------- */
 /* HIP-event timing of the dominant kernel on the context's stream: accumulated since the last

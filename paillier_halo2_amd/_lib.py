@@ -190,6 +190,12 @@ SIGNATURES = {
     "pz_proof_begin_pub": (C.c_int, [VP, VP, C.c_uint64, VP, C.c_size_t, VP, C.c_size_t, C.POINTER(VP), VP]),
     "pz_verify_batch_pub": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(C.c_int)]),
     "pz_verify_batch_bytes_pub": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, VP, VP, VP, VP, VP, C.POINTER(C.c_int)]),
+    # key binding: the verifying key's digest at the head of the transcript (host/key_digest.hpp)
+    "pz_key_digest": (C.c_int, [C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, VP, VP, VP]),
+    "pz_pk_digest": (C.c_int, [VP, VP]),
+    "pz_vk_digest": (C.c_int, [VP, VP]),
+    "pz_vk_bind": (C.c_int, [VP, C.c_int]),
+    "pz_vk_is_bound": (C.c_int, [VP, C.POINTER(C.c_int)]),
     "pz_timing_enable": (C.c_int, [VP, C.c_int]),
     "pz_timing_reset": (C.c_int, [VP]),
     "pz_timing_get": (C.c_int, [VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),

@@ -8,6 +8,7 @@
 
 #include <atomic>
 #include <memory>
+#include <mutex>
 #include <new>
 
 struct pz_pk {
@@ -17,6 +18,10 @@ struct pz_pk {
     // one proof in flight per key (it owns the workspace).  Claimed by an atomic test-and-set: pz.h invites calls from any thread
     // (halo2's rayon workers), and two pz_proof_begin on one key must not both pass the check
     std::atomic<bool> busy{false};
+    // the key's digest (host/key_digest.hpp), computed on the first pz_pk_digest
+    mutable std::mutex digest_mu;
+    mutable bool have_digest = false;
+    mutable uint8_t digest[pzh::KEY_DIGEST_BYTES] = {};
 };
 struct pz_proof {
     pz_pk* pk;
@@ -157,6 +162,18 @@ extern "C" int pz_pk_commitments(const pz_pk* pk, uint64_t* fixed_affine, uint64
     if (!pk || !pk->key || !fixed_affine || !sigma_affine) return PZ_ERR_INVALID;
     memcpy(fixed_affine, pk->key->fixed_commit.data(), pk->key->fixed_commit.size() * 8);
     memcpy(sigma_affine, pk->key->sigma_commit.data(), pk->key->sigma_commit.size() * 8);
+    return PZ_OK;
+}
+
+// what the caller seeds a bound transcript with (in front of its own seed): the stepper itself never sees the transcript
+extern "C" int pz_pk_digest(const pz_pk* pk, uint8_t out[64]) {
+    if (!pk || !pk->key || !out) return PZ_ERR_INVALID;
+    std::lock_guard<std::mutex> g(pk->digest_mu);
+    if (!pk->have_digest) {
+        pzp::key_digest(*pk->key, pk->digest);
+        pk->have_digest = true;
+    }
+    memcpy(out, pk->digest, pzh::KEY_DIGEST_BYTES);
     return PZ_OK;
 }
 

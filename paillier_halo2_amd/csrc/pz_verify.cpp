@@ -13,10 +13,12 @@
 #include <errno.h>
 #include <sys/random.h>
 
+#include <mutex>
 #include <new>
 #include <vector>
 
 #include "pz_internal.h"
+#include "../host/key_digest.hpp"
 #include "../host/transcript.hpp"
 
 using pzh::Fr;
@@ -32,6 +34,10 @@ struct pz_vk {
     void* d_members = nullptr;                // (evaluation offset, destination) per member of the query sets
     pz_bases* t_vk = nullptr;                 // K1 table of d_vkb (the per-proof checks' vk MSM)
     size_t n_public = 0;                      // values of the instance column (s.n_inst = 1), else 0
+    std::vector<uint64_t> commitments;        // fixed | sigma as the caller gave them: what the key's digest is taken over
+    std::mutex digest_mu;                     // the digest is computed on the first request (pz_vk_digest, or a bound verification)
+    bool have_digest = false, bound = false;  // bound: every proof's replay starts from digest || seed (pz_vk_bind)
+    uint8_t digest[pzh::KEY_DIGEST_BYTES] = {};
 };
 
 namespace {
@@ -182,6 +188,17 @@ void make_shape(size_t A, size_t Lk, size_t n_instance, pz_vk& vk, std::vector<u
     s.n_sets = ns;
 }
 
+// the key's digest, computed once per key object
+const uint8_t* vk_digest(pz_vk* vk) {
+    std::lock_guard<std::mutex> g(vk->digest_mu);
+    if (!vk->have_digest) {
+        const pz_vshape& s = vk->s;
+        pzh::key_digest(vk->k, vk->bf, s.A, s.Lk, s.n_inst, vk->n_public, vk->commitments.data(), vk->commitments.data() + 8ull * s.F, vk->digest);
+        vk->have_digest = true;
+    }
+    return vk->digest;
+}
+
 // what the host derives for one proof once the transcript is replayed
 struct Replay {
     Fr beta, gamma, y, x, sy, sv, su;
@@ -204,6 +221,7 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
     const size_t NP = vk->n_public;
 
     // 1. transcripts, then everything that needs an inversion, inverted at once
+    const uint8_t* bind = vk->bound ? vk_digest(vk) : nullptr;   // a bound key: digest || seed where the seed alone stood
     std::vector<Replay> rp(B);
     std::vector<Fr> inv;
     std::vector<std::vector<Fr>> pts(B);
@@ -211,7 +229,7 @@ void verify(pz_vk* vk, const uint64_t* proofs, size_t B, const uint8_t* seeds, c
         const uint64_t* c = proofs + i * pw;
         const uint64_t* e = c + cw;
         static const uint8_t none = 0;
-        pzp::Transcript tr(seeds ? (const void*)(seeds + seed_off[i]) : (const void*)&none, seed_off[i + 1] - seed_off[i]);
+        pzp::Transcript tr(bind, seeds ? (const void*)(seeds + seed_off[i]) : (const void*)&none, seed_off[i + 1] - seed_off[i]);
         Replay& r = rp[i];
         if (NP) {   // the statement: absorbed after the seed, before the first commitment; a value >= r is no statement (verdict 0)
             std::vector<uint64_t> im(4 * NP, 0);
@@ -511,6 +529,7 @@ int vk_create(pz_ctx* ctx, size_t n_instance, size_t n_public, uint32_t k, uint3
         memcpy(vkb.data(), fixed_affine, 64ull * s.F);
         memcpy(vkb.data() + 8ull * s.F, sigma_affine, 64ull * s.m);
         memcpy(vkb.data() + 8ull * (s.F + s.m), g0_affine, 64);
+        vk->commitments.assign(vkb.begin(), vkb.begin() + 8ull * (s.F + s.m));
         std::vector<uint64_t> delta(4ull * s.m);
         const Fr dl = pzh::delta();
         Fr dc = pzh::FR_ONE;
@@ -665,6 +684,34 @@ extern "C" int pz_verify_batch_bytes_pub(pz_vk* vk, const uint64_t* instances, s
                                          const uint8_t* seeds, const size_t* seed_offsets, int32_t* verdicts, uint64_t* h_evals,
                                          uint64_t* ab_affine, int* all_ok) {
     return verify_batch_bytes(vk, instances, n_public, bytes, n_proofs, seeds, seed_offsets, verdicts, h_evals, ab_affine, all_ok);
+}
+
+// the key's digest and the opt-in binding of every verification to it (host/key_digest.hpp)
+extern "C" int pz_key_digest(uint32_t k, uint32_t blinding_factors, size_t n_adv, size_t n_lk, size_t n_instance, size_t n_public,
+                             const uint64_t* fixed_affine, const uint64_t* sigma_affine, uint8_t out[64]) {
+    if (!fixed_affine || !sigma_affine || !out) return PZ_ERR_INVALID;
+    if (!n_instance && n_public) return PZ_ERR_INVALID;
+    pzh::key_digest(k, blinding_factors, n_adv, n_lk, n_instance, n_public, fixed_affine, sigma_affine, out);
+    return PZ_OK;
+}
+
+extern "C" int pz_vk_digest(const pz_vk* vk, uint8_t out[64]) {
+    if (!vk || !out) return PZ_ERR_INVALID;
+    memcpy(out, vk_digest(const_cast<pz_vk*>(vk)), pzh::KEY_DIGEST_BYTES);
+    return PZ_OK;
+}
+
+extern "C" int pz_vk_bind(pz_vk* vk, int on) {
+    if (!vk) return PZ_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lock(vk->ctx->mu);   // not under a verification in flight on this key's context
+    vk->bound = on != 0;
+    return PZ_OK;
+}
+
+extern "C" int pz_vk_is_bound(const pz_vk* vk, int* on) {
+    if (!vk || !on) return PZ_ERR_INVALID;
+    *on = vk->bound ? 1 : 0;
+    return PZ_OK;
 }
 
 extern "C" int pz_vk_free(pz_vk* vk) {

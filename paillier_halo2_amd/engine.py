@@ -68,6 +68,22 @@ class VkHandle:
         self.engine._chk(_lib.lib().pz_proof_wire_bytes(self.handle, C.byref(n)), "pz_proof_wire_bytes")
         return n.value
 
+    def digest(self) -> bytes:
+        """pz_vk_digest: the key's 64-byte digest (prover.key_digest's function; computed once per handle)"""
+        out = (C.c_uint8 * 64)()
+        self.engine._chk(_lib.lib().pz_vk_digest(self.handle, out), "pz_vk_digest")
+        return bytes(out)
+
+    def bind(self, on: bool = True):
+        """pz_vk_bind: every verification through this handle replays each proof from digest || seed (off: from the seed alone)"""
+        self.engine._chk(_lib.lib().pz_vk_bind(self.handle, 1 if on else 0), "pz_vk_bind")
+
+    @property
+    def bound(self) -> bool:
+        on = C.c_int()
+        self.engine._chk(_lib.lib().pz_vk_is_bound(self.handle, C.byref(on)), "pz_vk_is_bound")
+        return bool(on.value)
+
     def free(self):
         if self.handle is not None:
             _lib.lib().pz_vk_free(self.handle)

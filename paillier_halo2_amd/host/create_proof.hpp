@@ -22,6 +22,7 @@
 
 #include "../../include/pz.h"
 #include "fr_host.hpp"
+#include "key_digest.hpp"
 #include "transcript.hpp"
 
 namespace pzp {
@@ -149,6 +150,12 @@ struct ProvingKey {
     std::vector<uint64_t> fixed_commit, sigma_commit;   // affine, 8 words each
     explicit ProvingKey(Structure&& s) : st(std::move(s)), dom(st.k, st.blinding_factors) {}
 };
+
+// the key's digest (key_digest.hpp): what a bound transcript is seeded with in front of the caller's seed
+inline void key_digest(const ProvingKey& pk, uint8_t out[pzh::KEY_DIGEST_BYTES]) {
+    pzh::key_digest(pk.st.k, pk.st.blinding_factors, pk.st.n_adv, pk.st.n_lk, pk.st.n_instance, pk.st.n_public, pk.fixed_commit.data(),
+                    pk.sigma_commit.data(), out);
+}
 
 inline void upload_mont(Ctx& cx, uint64_t* d, const std::vector<Fr>& v) {
     PZP_CK(pz_upload(cx.c, d, v.data(), v.size() * 32));

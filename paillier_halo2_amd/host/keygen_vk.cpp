@@ -8,7 +8,8 @@
 //   (the message m and the modulus n, hexadecimal: only their bits shape the circuit), add takes none
 //   out.vk: "PZVK", u32 version 1, k, blinding_factors, n_adv, n_lk, then the n_adv + 2 fixed and the n_adv + n_lk + 1 sigma commitments,
 //   32 compressed bytes each -- the file verify_wire reads and prove_connected writes with PZ_PROVE_WIRE=1, byte for byte
-// stdout: one JSON line {"k", "n_adv", "n_lk", "structure_ms", "vk_ms"}.  Exit 0 ok, 2 on malformed arguments or files or a library error.
+// stdout: one JSON line {"k", "n_adv", "n_lk", "structure_ms", "vk_ms", "digest"}; digest: the key's 64-byte digest in hexadecimal
+// (pz_key_digest: what a bound transcript starts from, equal to pz_pk_digest of the prover's key).  Exit 0 ok, 2 on malformed arguments or files or a library error.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -116,6 +117,7 @@ int main(int argc, char** argv) {
     size_t n_adv = 0, n_lk = 0, n_constants = 0;
     double structure_ms = 0, vk_ms = 0;
     std::vector<uint8_t> vkfile;
+    uint8_t digest[64] = {0};
     if (rc == PZ_OK) {
         where = "pz_circuit_structure_dev";
         const double t0 = now_ms();
@@ -143,6 +145,10 @@ int main(int argc, char** argv) {
                                   pts.data() + 8 * F);
             vk_ms = now_ms() - t0;
             if (rc == PZ_OK) {
+                where = "pz_key_digest";
+                rc = pz_key_digest((uint32_t)k, (uint32_t)bf, n_adv, n_lk, 0, 0, pts.data(), pts.data() + 8 * F, digest);
+            }
+            if (rc == PZ_OK) {
                 vkfile.resize(24 + 32 * (F + m));
                 const uint32_t head[5] = {1, (uint32_t)k, (uint32_t)bf, (uint32_t)n_adv, (uint32_t)n_lk};
                 memcpy(vkfile.data(), "PZVK", 4);
@@ -161,6 +167,9 @@ int main(int argc, char** argv) {
     if (!f) return fail("cannot write the key file");
     const bool ok = fwrite(vkfile.data(), 1, vkfile.size(), f) == vkfile.size();
     if (fclose(f) != 0 || !ok) return fail("cannot write the key file");
-    printf("{\"k\": %u, \"n_adv\": %zu, \"n_lk\": %zu, \"structure_ms\": %.2f, \"vk_ms\": %.2f}\n", (unsigned)k, n_adv, n_lk, structure_ms, vk_ms);
+    char hex[129];
+    for (int i = 0; i < 64; ++i) snprintf(hex + 2 * i, 3, "%02x", digest[i]);
+    printf("{\"k\": %u, \"n_adv\": %zu, \"n_lk\": %zu, \"structure_ms\": %.2f, \"vk_ms\": %.2f, \"digest\": \"%s\"}\n", (unsigned)k, n_adv, n_lk,
+           structure_ms, vk_ms, hex);
     return 0;
 }

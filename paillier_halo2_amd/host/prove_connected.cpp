@@ -32,6 +32,10 @@
 //                          n_adv + n_lk + 1 sigma commitments compressed (pz_g1_compress)
 //   <proof file>.p<i>.bin  proof i as wire bytes (pz_proof_encode)
 //   host/verify_wire.cpp checks them.  The record file and stdout are the same with and without it.
+//
+// PZ_PROVE_BIND=1 (every mode): each proof's transcript is BOUND to its key -- seeded with the key's 64-byte digest (host/key_digest.hpp;
+//   pz_pk_digest under PZ_PROVE_VIA_STEPPER=1; with --fresh the digest of that step's key) in front of the proof index -- and verifies only
+//   under PZ_VERIFY_BIND=1 (verify_connected, verify_wire).  Unset: the seed is the index alone, as it always was.
 #include <chrono>
 #include <map>
 #include <thread>
@@ -67,6 +71,13 @@ struct Out {
         fwrite(data, 8, count * per, f);
     }
 };
+
+// proof `index`'s transcript: seeded with the index as 8 little-endian bytes, behind the key's digest when the proofs are bound
+static bool bind_proofs() {
+    const char* e = getenv("PZ_PROVE_BIND");
+    return e && e[0] == '1';
+}
+static Transcript seeded_transcript(const uint8_t* key_digest, uint64_t index) { return Transcript(key_digest, &index, 8); }
 
 static double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -130,6 +141,7 @@ static int fresh_main(const char* params_path, const char* proof_path) {
     const size_t ext_res = sk && *sk ? strtoull(sk, nullptr, 10) : EXT_ALL;
     double sum_after_first = 0, structure_ms = 0, keygen_ms = 0, witness_ms = 0, prove_ms = 0;
     size_t last_adv = 0, last_lk = 0;
+    const bool bind = bind_proofs();
     for (size_t si = 0; si < steps; ++si) {
         const uint64_t *vn = &w[13 + si * 4 * Ln], *vg = vn + Ln, *vm = vg + Ln, *vr = vm + Ln;
         PZP_CK(pz_sync(cx.c));
@@ -184,7 +196,9 @@ static int fresh_main(const char* params_path, const char* proof_path) {
                                           pk->st.max_rows, pk->st.max_rows, n));
         PZP_CK(pz_sync(cx.c));
         const double t3 = now_ms();
-        Transcript tr((uint64_t)si);
+        uint8_t kd[pzh::KEY_DIGEST_BYTES];
+        if (bind) key_digest(*pk, kd);     // this step's key
+        Transcript tr = seeded_transcript(bind ? kd : nullptr, si);
         Proof pr = create_proof(cx, *pk, ws, d_cols, tr, seed + si);
         PZP_CK(pz_sync(cx.c));
         const double t4 = now_ms();
@@ -240,6 +254,9 @@ static int stepper_main(Ctx& cx, int dev, Structure& st, const pz_bases* bl, con
     PZP_CK(pz_pk_info(pk, &F, &m_, &S, &bw, &ew));
     std::vector<uint64_t> vkf(8 * F), vks(8 * m);
     PZP_CK(pz_pk_commitments(pk, vkf.data(), vks.data()));
+    const bool bind = bind_proofs();
+    uint8_t kd[pzh::KEY_DIGEST_BYTES];
+    if (bind) PZP_CK(pz_pk_digest(pk, kd));   // the stepper never sees the transcript: its caller seeds with the key's digest
     Out out{fopen(proof_path, "wb")};
     if (!out.f) { perror(proof_path); return 2; }
     out.rec("vk/fixed", 0, F, 8, vkf.data());
@@ -265,7 +282,7 @@ static int stepper_main(Ctx& cx, int dev, Structure& st, const pz_bases* bl, con
                 PZP_CK(pz_sync(cw.c));
             });
         uint64_t* d_cols = d_slot[pi & 1];
-        Transcript tr((uint64_t)pi);
+        Transcript tr = seeded_transcript(bind ? kd : nullptr, pi);
         pz_proof* pr = nullptr;
         std::vector<uint64_t> adv(8 * (A + Lk)), ap(8 * Lk), sp(8 * Lk), cz(8 * S), czl(8 * Lk), crnd(8), ch(24), ev(ew), w1(8), w2(8);
         PZP_CK(pz_proof_begin(pk, d_cols, seed + pi, nullptr, PZ_BLINDING_SEEDED_TEST_STREAM, &pr, adv.data()));
@@ -496,6 +513,9 @@ static int job_main(int argc, char** argv) {
     PZP_CK(pz_sync(cx.c));
     const double keygen_ms = now_ms() - t_keygen;
     Workspace ws = make_workspace(cx, *pk, tile);
+    const bool bind = bind_proofs();
+    uint8_t kd[pzh::KEY_DIGEST_BYTES];
+    if (bind) key_digest(*pk, kd);
     // two witness slots: proof i + 1's K3 + K4 run on a second context under proof i's advice commitments (PZ_PROVE_PIPELINE=0: one
     // context, one slot, everything in order)
     const char* pe = getenv("PZ_PROVE_PIPELINE");
@@ -558,7 +578,7 @@ static int job_main(int argc, char** argv) {
         }
         PZP_CK(pz_sync(cx.c));
         const double t1 = now_ms();
-        Transcript tr((uint64_t)pi);
+        Transcript tr = seeded_transcript(bind ? kd : nullptr, pi);
         std::function<void()> hook;
         if (pipeline && pi + 1 < proofs) hook = [&, pi] { produce(pi + 1); };
         Proof pr = create_proof(cx, *pk, ws, d_cols, tr, seed + pi, hook);

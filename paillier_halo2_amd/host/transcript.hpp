@@ -18,13 +18,19 @@ using pzh::Fr;
 // BLAKE2b-512 personalised "Halo2-Transcript", one domain byte in front of every item (0 challenge, 1 point, 2 scalar), a challenge = the
 // digest of a CLONE of the running state read as a 512-bit little-endian integer mod r (`from_uniform_bytes`).  Not its byte format: a field
 // element enters as the 4 Montgomery words it crosses include/pz.h in (x then y for a point), families in this prover's order, and the
-// seed stands where halo2 absorbs the verifying key's digest.  paillier_halo2_amd/prover.py::HashTranscript is the same function;
-// oracle/verifier.py::replay_challenges re-derives every challenge from a proof's commitments and evaluations.
+// seed stands where halo2 absorbs the verifying key's digest: a BOUND transcript (key_digest.hpp) starts from the
+// key's 64-byte digest followed by the caller's seed, an unbound one from the seed alone.  paillier_halo2_amd/prover.py::HashTranscript is
+// the same function; oracle/verifier.py::replay_challenges re-derives every challenge from a proof's commitments and evaluations.
 struct Transcript {
     pzh::Blake2b h{"Halo2-Transcript"};
     std::vector<std::pair<std::string, Fr>> drawn;       // (name, canonical value as 4 words): what the checker compares its replay with
     Transcript(const void* seed, size_t bytes) { h.update(seed, bytes); }
     explicit Transcript(uint64_t seed) { h.update(&seed, 8); }
+    // key_digest: 64 bytes (pzh::key_digest / pz_pk_digest / pz_vk_digest), or NULL for the unbound transcript of the constructors above
+    Transcript(const uint8_t* key_digest, const void* seed, size_t bytes) {
+        if (key_digest) h.update(key_digest, 64);
+        h.update(seed, bytes);
+    }
     void items(uint8_t tag, const uint64_t* v, size_t count, size_t words) {
         std::vector<uint8_t> buf(count * (1 + 8 * words));
         uint8_t* o = buf.data();

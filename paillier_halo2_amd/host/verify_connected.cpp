@@ -7,11 +7,14 @@
 //   params file: srs.write_params_kzg's ParamsKZG (u32 k, g, g_lagrange, g2, s_g2): only g[0], g2 and s_g2 are read -- never a secret
 //   proof file: prove_connected's records: "vk/fixed", "vk/sigma" and each proof's "p<i>/c/..." and "p<i>/e/..."; proof i's transcript
 //   seed is i as 8 little-endian bytes
+// PZ_VERIFY_BIND=1: the proofs are BOUND to the key (prove_connected's PZ_PROVE_BIND=1; pz_vk_bind): each replay starts from the key's digest
+//   followed by that seed.  Bound proofs without it, or unbound proofs with it, do not verify (exit 1).
 // stdout: one JSON line {"proofs", "verified", "per_proof", "ms"}.  Exit 0 if every proof verified, 1 if any did not, 2 on bad input or a
 // library error.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -104,6 +107,8 @@ int main(int argc, char** argv) {
         pz_free(ctx);
         return 2;
     }
+    if (const char* be = getenv("PZ_VERIFY_BIND"))   // the proofs were made bound to their key (prove_connected's PZ_PROVE_BIND=1)
+        if (be[0] == '1') pz_vk_bind(vk, 1);
     size_t cw = 0, ew = 0;
     pz_vk_info(vk, &cw, &ew);
     // each proof in the ABI layout: the stepper's outputs in phase order, the records concatenated as they are

@@ -7,11 +7,14 @@
 //   32 compressed bytes each (prove_connected with PZ_PROVE_WIRE=1 writes it; verifier.vk_to_bytes is the same format)
 //   params file: srs.write_params_kzg's ParamsKZG (u32 k, g, g_lagrange, g2, s_g2): only g[0], g2 and s_g2 are read -- never a secret
 //   proof bytes files: one proof each, pz_proof_wire_bytes long; proof i's transcript seed is i as 8 little-endian bytes
+// PZ_VERIFY_BIND=1: the proofs are BOUND to the key (prove_connected's PZ_PROVE_BIND=1; pz_vk_bind): each replay starts from the key's digest
+//   followed by that seed.  Bound proofs without it, or unbound proofs with it, do not verify (exit 1).
 // stdout: one JSON line {"proofs", "verified", "per_proof", "ms"}.  Exit 0 if every proof verified, 1 if any did not, 2 on bad input (a vk
 // file whose points do not decode included) or a library error.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -82,6 +85,8 @@ int main(int argc, char** argv) {
         pz_free(ctx);
         return 2;
     }
+    if (const char* be = getenv("PZ_VERIFY_BIND"))   // the proofs were made bound to their key (prove_connected's PZ_PROVE_BIND=1)
+        if (be[0] == '1') pz_vk_bind(vk, 1);
     size_t wire = 0;
     pz_proof_wire_bytes(vk, &wire);
     std::vector<uint8_t> bytes, seeds;

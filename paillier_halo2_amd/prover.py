@@ -263,6 +263,37 @@ class ProvingKey:
         jac = lambda t: e.g1_normalize(t.cpu().numpy().view(np.uint64))
         return {"fixed": jac(self.fixed_commit), "sigma": jac(self.sigma_commit)}
 
+    def digest(self) -> bytes:
+        """the key's 64-byte digest (key_digest): HashTranscript(seed, key_digest=pk.digest()) is the bound transcript"""
+        if getattr(self, "_digest", None) is None:
+            vk, st = self.vk_commitments(), self.st
+            self._digest = key_digest(st.k, st.blinding_factors, st.n_adv, st.n_lk, vk["fixed"], vk["sigma"], getattr(st, "n_instance", 0),
+                                      getattr(st, "n_public", 0))
+        return self._digest
+
+
+KEY_DIGEST_PERSONAL = b"PZ-Key-Digest-v1"
+
+
+def key_digest(k: int, bf: int, n_adv: int, n_lk: int, fixed, sigma, n_instance: int = 0, n_public: int = 0) -> bytes:
+    """The verifying key's digest (include/pz.h pz_key_digest, host/key_digest.hpp), restated with hashlib -- no call
+    into the library: BLAKE2b-512 personalised "PZ-Key-Digest-v1" over six little-endian u64 (k, blinding_factors, n_adv, n_lk, n_instance,
+    n_public), the (n_adv + 2) x 8 words of `fixed` and the (n_adv + n_lk + 1 + n_instance) x 8 words of `sigma`, both as vk_commitments()
+    carries them (Montgomery words, little-endian)."""
+    import hashlib
+    import struct
+
+    f = np.ascontiguousarray(fixed, dtype="<u8").reshape(-1)
+    s = np.ascontiguousarray(sigma, dtype="<u8").reshape(-1)
+    if f.size != 8 * (n_adv + 2) or s.size != 8 * (n_adv + n_lk + 1 + n_instance):
+        raise ValueError("fixed must hold n_adv + 2 points and sigma n_adv + n_lk + 1 (+ 1 with an instance column)")
+    if not n_instance and n_public:
+        raise ValueError("public values need the instance column")
+    h = hashlib.blake2b(struct.pack("<6Q", k, bf, n_adv, n_lk, n_instance, n_public), digest_size=64, person=KEY_DIGEST_PERSONAL)
+    h.update(f.tobytes())
+    h.update(s.tobytes())
+    return h.digest()
+
 
 def keygen(eng: Engine, st: CircuitStructure, bases_lagrange: Bases, bases_monomial: Bases, cosets: int = 3,
            ext_resident_cols: Optional[int] = None) -> ProvingKey:
@@ -309,16 +340,22 @@ class HashTranscript(Transcript):
     clone of the running state read as a 512-bit little-endian integer mod r -- and in its DATAFLOW: every phase's commitments are brought to
     the host in affine form (a synchronising download: the prover cannot start the next phase before the challenge exists).  Not halo2's
     byte format: a field element enters as the 4 Montgomery words it crosses include/pz.h in (x then y for a point), families in this
-    prover's order, and `seed` stands where halo2 absorbs the verifying key's digest.  host/transcript.hpp is the same function (checked
-    value for value by tests/test_cpp_host_field.py); oracle/verifier.py::replay_challenges re-derives every challenge from a proof."""
+    prover's order, and `seed` stands where halo2 absorbs the verifying key's digest: with key_digest (ProvingKey.digest(), NativeKey.digest(),
+    VerifyingKey.digest()) the transcript is BOUND to the key -- it hashes key_digest + seed where the unbound one hashes seed, nothing after
+    it moves -- and only a verifier with bind_key=True and the same key accepts the proof.  host/transcript.hpp is
+    the same function (checked value for value by tests/test_cpp_host_field.py); oracle/verifier.py::replay_challenges re-derives every
+    challenge from a proof (a bound one from key_digest + seed)."""
 
     PERSONAL = b"Halo2-Transcript"
 
-    def __init__(self, seed: bytes = b"pz"):
+    def __init__(self, seed: bytes = b"pz", key_digest: Optional[bytes] = None):
         import hashlib
 
-        self.seed = bytes(seed)
-        self.h = hashlib.blake2b(self.seed, digest_size=64, person=self.PERSONAL)
+        self.seed = bytes(seed)                      # the caller's seed: what Challenges.transcript_seed keeps
+        self.key_digest = None if key_digest is None else bytes(key_digest)
+        if self.key_digest is not None and len(self.key_digest) != 64:
+            raise ValueError("a key digest is 64 bytes")
+        self.h = hashlib.blake2b((self.key_digest or b"") + self.seed, digest_size=64, person=self.PERSONAL)
         self.drawn: Dict[str, int] = {}
 
     def _items(self, tag: int, a: np.ndarray, words: int):
@@ -419,7 +456,8 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
     is consumed (it ends up in coefficient form).
     instances: the public values (integers below r, st.n_public of them) of a structure with an instance column: absorbed into the
     transcript before the first commitment, written to rows [0, n_public) of the instance column (not blinded, not committed).
-    tr: a Transcript (or plain Challenges).  Runs on the engine's stream (bind_torch_stream).
+    tr: a Transcript (or plain Challenges); HashTranscript(seed, key_digest=pk.digest()) makes the proof BOUND to this key (verified with
+    bind_key=True only).  Runs on the engine's stream (bind_torch_stream).
     seed: of the device generator the blinding values come from (tests and benches want reproducible proofs); None = 64 bits of OS
     randomness per proof (os.urandom) -- what a caller who needs the proof to be zero-knowledge passes.
     hooks: optional dict of callables name -> f(tensors) applied to intermediate device buffers (the tests' tamper points).

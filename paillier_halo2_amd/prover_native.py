@@ -90,6 +90,12 @@ class NativeKey:
         self.eng._chk(self.eng.L.pz_pk_commitments(self.handle, _p(f), _p(s)), "pz_pk_commitments")
         return {"fixed": f, "sigma": s}
 
+    def digest(self) -> bytes:
+        """pz_pk_digest: the key's 64-byte digest -- HashTranscript(seed, key_digest=key.digest()) is the bound transcript"""
+        out = (C.c_uint8 * 64)()
+        self.eng._chk(self.eng.L.pz_pk_digest(self.handle, out), "pz_pk_digest")
+        return bytes(out)
+
     def free(self):
         if self.handle:
             self.eng._chk(self.eng.L.pz_pk_free(self.handle), "pz_pk_free")
@@ -104,7 +110,8 @@ def _canon_words(vals) -> np.ndarray:
 
 
 def create_proof(key: NativeKey, d_cols: int, tr, seed: int = 0, blinding: Optional[np.ndarray] = None, instances=None) -> Proof:
-    """d_cols: device pointer of [m][2^k][4] words (the K4 columns; consumed).  tr: prover.Transcript / HashTranscript / Challenges.
+    """d_cols: device pointer of [m][2^k][4] words (the K4 columns; consumed).  tr: prover.Transcript / HashTranscript / Challenges; a BOUND
+    proof is one whose transcript is HashTranscript(seed, key_digest=key.digest()) -- the stepper itself never sees the transcript.
     blinding: optional uint64 array of key.blinding_words caller-supplied random words (else the library's seeded stream).
     instances: the public values (integers below r) of a key with an instance column (pz_proof_begin_pub): absorbed into the transcript
     before the first commitment"""

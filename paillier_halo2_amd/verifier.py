@@ -13,8 +13,9 @@ verify_batch folds B proofs with random r_i (os.urandom) into sum r_i A_i, sum r
 key's fixed and sigma commitments (once, their scalars summed over the proofs), the generator and every proof's own commitments, then ONE
 2-pair pz_pairing_check_dev.  If that fails, or an identity of step 2 fails, the per-proof verdicts come from B independent checks in
 one pz_pairing_check_dev launch.  A proof with a commitment that is off the curve or has a coordinate that is not canonical (the identity
-(0, 0) apart), or with an evaluation >= r, is False by itself and takes no part in the rest.  The transcript seed is the caller's bytes
-(not a digest of the verifying key).
+(0, 0) apart), or with an evaluation >= r, is False by itself and takes no part in the rest.  The transcript seed is the caller's bytes;
+with bind_key=True every verifier here replays from VerifyingKey.digest() + seed instead: the proof must have
+been made with HashTranscript(seed, key_digest=...) of the SAME key, and a proof made without it is False.
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import consts
-from .prover import CHUNK, DELTA, Domain, query_layout, rotation_points
+from .prover import CHUNK, DELTA, Domain, key_digest, query_layout, rotation_points
 
 R = consts.FR_R
 H_PIECES = 3
@@ -80,6 +81,11 @@ class VerifyingKey:
     @property
     def m(self) -> int:
         return self.n_adv + self.n_lk + 1 + self.n_instance
+
+    def digest(self) -> bytes:
+        """the key's 64-byte digest (prover.key_digest; equal to pz_pk_digest / pz_vk_digest of the same key): what a bound transcript starts
+        from.  Computable from a PZVK file's contents alone"""
+        return key_digest(self.k, self.blinding_factors, self.n_adv, self.n_lk, self.fixed, self.sigma, self.n_instance, self.n_public)
 
     @classmethod
     def from_proving_key(cls, pk) -> "VerifyingKey":
@@ -474,14 +480,19 @@ def _check_instances(vk: VerifyingKey, instances, B: int):
     return [list(v) for v in instances]
 
 
-def verify_batch(eng, params: VerifierParams, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes], instances=None) -> Tuple[bool, List[bool]]:
+def verify_batch(eng, params: VerifierParams, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes], instances=None,
+                 bind_key: bool = False) -> Tuple[bool, List[bool]]:
     """-> (every proof holds, per-proof verdicts).  proofs: prover.Proof objects or (prover_job.read_proofs record, "p<i>/") pairs; seeds:
     the transcript seed of each (record_seed for the compiled prover's).  params: VerifierParams (or a srs.ParamsKZG, whose G2 elements must not be zero).
-    instances: per proof the list of its public values (public_inputs) when the key has an instance column."""
+    instances: per proof the list of its public values (public_inputs) when the key has an instance column.
+    bind_key: replay every transcript from vk.digest() + seed (proofs made with HashTranscript(seed, key_digest=...))."""
     if not isinstance(params, VerifierParams):
         params = VerifierParams.from_params(params)
     assert len(proofs) == len(seeds) and len(proofs) > 0
     inst = _check_instances(vk, instances, len(proofs))
+    if bind_key:
+        D = vk.digest()
+        seeds = [D + bytes(sd) for sd in seeds]
     terms = [_terms(vk, *_as_parts(p, vk), s, iv) for p, s, iv in zip(proofs, seeds, inst)]
     B = len(terms)
     idents = [t.ok for t in terms]
@@ -506,8 +517,8 @@ def verify_batch(eng, params: VerifierParams, vk: VerifyingKey, proofs: Sequence
     return all(per), per
 
 
-def verify_proof(eng, params, vk: VerifyingKey, proof, seed: bytes, instances=None) -> bool:
-    return verify_batch(eng, params, vk, [proof], [seed], None if instances is None else [instances])[0]
+def verify_proof(eng, params, vk: VerifyingKey, proof, seed: bytes, instances=None, bind_key: bool = False) -> bool:
+    return verify_batch(eng, params, vk, [proof], [seed], None if instances is None else [instances], bind_key=bind_key)[0]
 
 
 # ---- the device batch verifier (include/pz.h: pz_vk_create / pz_verify_batch): the same verdicts, Fr work in HIP ----------------------
@@ -546,9 +557,23 @@ def pack_proof(vk: VerifyingKey, com: Dict[str, np.ndarray], ev: Dict[str, np.nd
     return np.concatenate(parts)
 
 
-def verify_batch_native(eng, params, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes], handle=None, instances=None) -> Tuple[bool, List[bool]]:
+def _bound(handle, bind_key: bool, fn):
+    """fn() with the handle's binding (pz_vk_bind) set to bind_key; a caller's handle gets its own setting back"""
+    was = handle.bound
+    if was != bool(bind_key):
+        handle.bind(bind_key)
+    try:
+        return fn()
+    finally:
+        if was != bool(bind_key):
+            handle.bind(was)
+
+
+def verify_batch_native(eng, params, vk: VerifyingKey, proofs: Sequence, seeds: Sequence[bytes], handle=None, instances=None,
+                        bind_key: bool = False) -> Tuple[bool, List[bool]]:
     """verify_batch on the device batch verifier: the same arguments and (every proof holds, per-proof verdicts).  handle: a native_key
-    of (params, vk) to reuse; made and freed here otherwise."""
+    of (params, vk) to reuse; made and freed here otherwise.  bind_key: pz_vk_bind for this call (the library hashes its own digest of the
+    key in front of every seed)."""
     assert len(proofs) == len(seeds) and len(proofs) > 0
     inst = _check_instances(vk, instances, len(proofs))
     packed = [pack_proof(vk, *_as_parts(p, vk)) for p in proofs]
@@ -559,8 +584,8 @@ def verify_batch_native(eng, params, vk: VerifyingKey, proofs: Sequence, seeds: 
     own = handle is None
     h = native_key(eng, params, vk) if own else handle
     try:
-        _, got, _, _ = eng.verify_batch_dev(h, np.stack([packed[i] for i in live]), [seeds[i] for i in live],
-                                            instances=[inst[i] for i in live] if vk.n_instance else None)
+        _, got, _, _ = _bound(h, bind_key, lambda: eng.verify_batch_dev(h, np.stack([packed[i] for i in live]), [seeds[i] for i in live],
+                                                                        instances=[inst[i] for i in live] if vk.n_instance else None))
     finally:
         if own:
             h.free()
@@ -678,9 +703,11 @@ def vk_from_bytes(eng, data: bytes) -> VerifyingKey:
     return VerifyingKey(k, bf, A, Lk, -(-(A + Lk + 1 + ni) // CHUNK), pts[:A + 2].copy(), pts[A + 2:].copy(), ni, npub)
 
 
-def verify_batch_bytes(eng, params, vk: VerifyingKey, proofs: Sequence[bytes], seeds: Sequence[bytes], handle=None, instances=None) -> Tuple[bool, List[bool]]:
+def verify_batch_bytes(eng, params, vk: VerifyingKey, proofs: Sequence[bytes], seeds: Sequence[bytes], handle=None, instances=None,
+                       bind_key: bool = False) -> Tuple[bool, List[bool]]:
     """verify_batch for proofs that arrive as halo2 wire bytes (pz_verify_batch_bytes: decoded on the device; a proof that does not decode
-    is False and the others are judged without it).  ValueError if a proof's length is not proof_size_bytes(vk)."""
+    is False and the others are judged without it).  ValueError if a proof's length is not proof_size_bytes(vk).  bind_key: pz_vk_bind for
+    this call."""
     assert len(proofs) == len(seeds) and len(proofs) > 0
     inst = _check_instances(vk, instances, len(proofs))
     size = proof_size_bytes(vk)
@@ -691,7 +718,7 @@ def verify_batch_bytes(eng, params, vk: VerifyingKey, proofs: Sequence[bytes], s
     own = handle is None
     h = native_key(eng, params, vk) if own else handle
     try:
-        ok, per, _, _ = eng.verify_batch_bytes_dev(h, data, seeds, instances=inst if vk.n_instance else None)
+        ok, per, _, _ = _bound(h, bind_key, lambda: eng.verify_batch_bytes_dev(h, data, seeds, instances=inst if vk.n_instance else None))
     finally:
         if own:
             h.free()

@@ -140,6 +140,14 @@ impl DeviceKey {
         check(unsafe { pz_pk_commitments(self.pk, f.as_mut_ptr(), s.as_mut_ptr()) });
         (f, s)
     }
+    /// the key's 64-byte digest (pz_pk_digest; computed once, kept in the key): a transcript that absorbs it in front of the per-proof seed
+    /// binds its proof to THIS key -- the place where halo2 absorbs vk.transcript_repr; the verifier's side is
+    /// pz_vk_bind
+    pub fn digest(&self) -> [u8; 64] {
+        let mut d = [0u8; 64];
+        check(unsafe { pz_pk_digest(self.pk, d.as_mut_ptr()) });
+        d
+    }
 }
 impl Drop for DeviceKey {
     fn drop(&mut self) {

@@ -223,6 +223,13 @@ extern "C" {
     pub fn pz_verify_batch_bytes_pub(vk: *mut pz_vk, instances: *const u64, n_public: usize, bytes: *const u8, n_proofs: usize,
                                      seeds: *const u8, seed_offsets: *const usize, verdicts: *mut i32, h_evals: *mut u64,
                                      ab_affine: *mut u64, all_ok: *mut c_int) -> c_int;
+    // key binding: the verifying key's digest at the head of the Fiat-Shamir transcript (opt-in)
+    pub fn pz_key_digest(k: u32, blinding_factors: u32, n_adv: usize, n_lk: usize, n_instance: usize, n_public: usize,
+                         fixed_affine: *const u64, sigma_affine: *const u64, out: *mut u8) -> c_int;
+    pub fn pz_pk_digest(pk: *const pz_pk, out: *mut u8) -> c_int;
+    pub fn pz_vk_digest(vk: *const pz_vk, out: *mut u8) -> c_int;
+    pub fn pz_vk_bind(vk: *mut pz_vk, on: c_int) -> c_int;
+    pub fn pz_vk_is_bound(vk: *const pz_vk, on: *mut c_int) -> c_int;
     // ParamsKZG files: the G2 codec and subgroup check, read_custom / write_custom / downsize and the consistency check of a params file
     pub fn pz_g2_compress(ctx: *mut pz_ctx, points: *const u64, n: usize, bytes: *mut u8) -> c_int;
     pub fn pz_g2_decompress(ctx: *mut pz_ctx, bytes: *const u8, n: usize, points: *mut u64, status: *mut i32, n_bad: *mut u64) -> c_int;
