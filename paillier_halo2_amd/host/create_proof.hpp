@@ -528,7 +528,10 @@ struct Session {
         };
         to_coeff(d_cols, m); to_coeff(w.Ap, Lk); to_coeff(w.Sp, Lk); to_coeff(w.Z, S); to_coeff(w.Zl, Lk);
         const size_t n_perm_lines = 2 + (S - 1) + S;
-        const Fr y_lines = pow_small(y, n_perm_lines);
+        // the gate lines on part A alone (prover.py, "the gate lines on part A"): h_G = G / Z_H has degree <= 2n - 3, so part A's 2n
+        // points give its coefficients [g_0 | g_1]; it joins the other lines' quotient as coefficients, times the power of y the Horner
+        // over all lines gives the gate group
+        const Fr y_gate = pow_small(y, n_perm_lines + 5 * Lk);
         for (int pi = 0; pi < 2; ++pi) {
             const Part& pt = d.parts[pi];
             const size_t Np = pt.size;
@@ -550,7 +553,7 @@ struct Session {
                 const size_t cnt = m - c0 < tile ? m - c0 : tile;
                 extend(d_cols + c0 * n * 4, cnt, w.ext[pi]);
                 const size_t na = c0 >= A ? 0 : (A - c0 < cnt ? A - c0 : cnt);
-                if (na)
+                if (na && pi == 0)
                     PZP_CK(pz_quotient_gate_dev(cx.c, w.ext[pi], 4 * Np, key_tile(pk.fixed_coeff, pk.fixed_ext[pi], pk.res_fixed, 0, c0, na), 4 * Np, na,
                                                 lg, rot, y.v, hg));
                 PZP_CK(pz_quotient_permutation_part_dev(cx.c, w.ext[pi], 4 * Np, key_tile(pk.sigma_coeff, pk.sigma_ext[pi], pk.res_sigma, 1, c0, cnt),
@@ -560,7 +563,7 @@ struct Session {
                                                         y.v, hp));
             }
             uint64_t* hq = w.hp[pi];
-            PZP_CK(pz_fr_lincomb_dev(cx.c, w.hh[pi], 2, 4 * Np, Np, y_lines.v, hq, 0));
+            PZP_CK(pz_dev_copy(cx.c, hq, hp, Np * 32));
             for (size_t l0_ = 0; l0_ < Lk; l0_ += w.lt) {
                 const size_t cnt = Lk - l0_ < w.lt ? Lk - l0_ : w.lt;
                 extend(d_cols + (A + l0_) * n * 4, cnt, w.lk_ext[pi][0]);
@@ -575,6 +578,11 @@ struct Session {
             PZP_CK(pz_ntt_fr_dev(cx.c, hq, 1, 4 * Np, pt.omega_inv.v, lg, nullptr, pt.size_inv.v));
             const Fr cg_inv = pzh::inv(pt.coset_g);
             PZP_CK(pz_fr_distribute_powers_dev(cx.c, hq, 1, 4 * Np, Np, cg_inv.v, nullptr));
+            if (pi == 0) {   // h_G the same way back, in place
+                PZP_CK(pz_quotient_finish_dev(cx.c, hg, k, pt.log_e, pt.coset_g.v, pt.omega.v));
+                PZP_CK(pz_ntt_fr_dev(cx.c, hg, 1, 4 * Np, pt.omega_inv.v, lg, nullptr, pt.size_inv.v));
+                PZP_CK(pz_fr_distribute_powers_dev(cx.c, hg, 1, 4 * Np, Np, cg_inv.v, nullptr));
+            }
         }
         // the quotient from three cosets (prover.py): [U | h_1] on part A, V on part B
         pieces = w.h;
@@ -596,6 +604,11 @@ struct Session {
             PZP_CK(pz_dev_copy(cx.c, t0, pieces + 2 * n * 4, n * 32));
             PZP_CK(pz_dev_copy(cx.c, t1, U, n * 32));
             PZP_CK(pz_fr_lincomb_dev(cx.c, w.tmp, 2, 4 * n, n, mg2n.v, pieces, 0));                  // h_0 = U - g^2n h_2
+            for (size_t i = 0; i < 2; ++i) {                                                          // pieces[i] += y_gate g_i
+                PZP_CK(pz_dev_copy(cx.c, t0, w.hh[0] + i * n * 4, n * 32));
+                PZP_CK(pz_dev_copy(cx.c, t1, pieces + i * n * 4, n * 32));
+                PZP_CK(pz_fr_lincomb_dev(cx.c, w.tmp, 2, 4 * n, n, y_gate.v, pieces + i * n * 4, 0));
+            }
         }
         commit(pk.bm, pieces, 3, w.out12);
         affine(w.out12, 3, out_h);
@@ -699,10 +712,12 @@ struct Session {
         PZP_CK(pz_shplonk_finish_dev(cx.c, st_, shu.v, w.w1, w.w2));
         commit(pk.bm, w.w2, 1, w.out12);
         affine(w.out12, 1, out_w2);
-        uint64_t top[12];
+        // deg h <= 3n - 4, and deg h_G <= 2n - 3 (w.hh[0] still holds [g_0 | g_1]): an unsatisfied gate shows in the latter
+        uint64_t top[12 + 8];
         PZP_CK(pz_download(cx.c, top, pieces + (3 * n - 3) * 4, 96));
+        PZP_CK(pz_download(cx.c, top + 12, w.hh[0] + (2 * n - 2) * 4, 64));
         done(6);
-        for (int i = 0; i < 12; ++i)
+        for (int i = 0; i < 12 + 8; ++i)
             if (top[i]) return false;
         return true;
     }

@@ -579,6 +579,11 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
         to_coeff(t, cnt)
     n_perm_lines = 2 + (S - 1) + S
     lt = ws.lk_ext[0][0].shape[0]
+    # the gate lines on part A.  Their numerator G has degree <= 3n - 3 and vanishes on the whole domain, so h_G = G / Z_H has degree
+    # <= 2n - 3: the 2n points of part A give its 2n coefficients [g_0 | g_1] with no wrap-around, and only the permutation and lookup
+    # lines (degree 4n - 4) need part B.  The two quotients are joined as coefficients, the gate's times the power of y the Horner
+    # over all lines gives the gate group.  (cosets = 4: one part, one Horner, as halo2 has it.)
+    split_gate = len(d.parts) == 2
     for pi, pt in enumerate(d.parts):           # the parts of the quotient's domain: one (halo2's 4n coset) or two (three cosets of <w_n>)
         Np, lg, rot = pt["size"], k + pt["log_e"], pt["E"]
         cg, om = M(pt["coset_g"]), M(pt["omega"])
@@ -603,7 +608,7 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
             cnt = min(tile, m - c0)
             extend(cols[c0:c0 + cnt], cnt, ext, pt)
             na = max(0, min(A, c0 + cnt) - c0)  # advice columns of this tile carry the custom gate
-            if na:
+            if na and (pi == 0 or not split_gate):
                 eng.quotient_gate_dev(ext.data_ptr(), 4 * Np, key_tile(pk.fixed_coeff, pk.fixed_ext, Rf, 0, c0, na), 4 * Np, na, lg, rot, y, hg.data_ptr())
             set_lo, nsets = c0 // CHUNK, -(-cnt // CHUNK)
             eng.quotient_permutation_part_dev(ext.data_ptr(), 4 * Np, key_tile(pk.sigma_coeff, pk.sigma_ext, Rs, 1, c0, cnt), 4 * Np, z_ext.data_ptr(), 4 * Np, S, set_lo,
@@ -611,7 +616,10 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
                                               hp.data_ptr())
         # h = hg * y^(permutation lines) + hp, then the lookup lines on top
         hq = ws.hp[pi]
-        eng.fr_lincomb_dev(ws.hh[pi].data_ptr(), 2, 4 * Np, Np, M(pow(y_i, n_perm_lines, FR)), hq.data_ptr())
+        if split_gate:
+            hq.copy_(hp)
+        else:
+            eng.fr_lincomb_dev(ws.hh[pi].data_ptr(), 2, 4 * Np, Np, M(pow(y_i, n_perm_lines, FR)), hq.data_ptr())
         for l0_ in range(0, Lk, lt):
             cnt = min(lt, Lk - l0_)
             e_in, e_ap, e_sp, e_zl = ws.lk_ext[pi]
@@ -625,6 +633,10 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
         # back to coefficients on this part: the quotient modulo X^size - coset_g^size
         eng.ntt_dev(hq.data_ptr(), 1, 4 * Np, M(pt["omega_inv"]), lg, None, M(pt["size_inv"]))
         eng.fr_distribute_powers_dev(hq.data_ptr(), 1, 4 * Np, Np, M(pow(pt["coset_g"], -1, FR)))
+        if split_gate and pi == 0:              # h_G the same way back, in place: [g_0 | g_1]
+            eng.quotient_finish_dev(hg.data_ptr(), k, pt["log_e"], cg, om)
+            eng.ntt_dev(hg.data_ptr(), 1, 4 * Np, M(pt["omega_inv"]), lg, None, M(pt["size_inv"]))
+            eng.fr_distribute_powers_dev(hg.data_ptr(), 1, 4 * Np, Np, M(pow(pt["coset_g"], -1, FR)))
     h = ws.h
     pieces = h.view(d.E, n, 4)                  # h(X) = sum_i X^(n i) h_i(X); degree <= 3n - 4
     if len(d.parts) == 1:
@@ -646,6 +658,12 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
         t01[0].copy_(pieces[2]); t01[1].copy_(U)
         eng.fr_lincomb_dev(t01.data_ptr(), 2, 4 * n, n, M(-g2n % FR), pieces[0].data_ptr())            # h_0 = U - g^2n h_2
         pieces[3].zero_()
+        # the join: pieces[i] += y^(permutation lines + lookup lines) g_i
+        c_gate = M(pow(y_i, n_perm_lines + 5 * Lk, FR))
+        gq = ws.hh[0][0]
+        for i in range(2):
+            t01[0].copy_(gq[i * n:(i + 1) * n]); t01[1].copy_(pieces[i])
+            eng.fr_lincomb_dev(t01.data_ptr(), 2, 4 * n, n, c_gate, pieces[i].data_ptr())
     c_h = commit(bm, pieces, d.E - 1, 4 * n)
     (a_h,) = tr.absorb_points(eng, c_h)
     x_i = tr.squeeze("x")
@@ -720,5 +738,7 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
     top = host(h[3 * n - 3:] if len(d.parts) == 1 else h[3 * n - 3:3 * n])
     pr.h_top = top
     pr.h_degree_ok = not top.any()
+    if split_gate:                              # deg h_G <= 2n - 3: an unsatisfied gate shows here, no longer in the other lines' top
+        pr.h_degree_ok = pr.h_degree_ok and not host(ws.hh[0][0][2 * n - 2:2 * n]).any()
     phase("finalise")
     return pr
