@@ -649,6 +649,44 @@ int pz_quotient_lookup_dev(pz_ctx* ctx, const uint64_t* d_input_ext, size_t inpu
                            uint32_t log_ext, uint32_t rot_step, const uint64_t* d_l0, const uint64_t* d_l_last,
                            const uint64_t* d_l_active, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
                            uint64_t* d_h);
+/* The SPLIT forms of the two line kernels (the prover's two-coset quotient).  The lines that carry l_active
+ * times a grand product's recurrence -- the product line of every permutation set, the third line of every lookup -- go to a second
+ * accumulator d_h_d WITHOUT the factor l_active; d_h_low takes the remaining lines.  Both accumulators step through the powers of y
+ * the unsplit form steps through, so d_h_low + l_active * d_h_d equals the unsplit d_h point for point, call by call.  Arguments as
+ * in pz_quotient_permutation_part_dev / pz_quotient_lookup_dev (the permutation form reads no l_active row); d_h_low and d_h_d are
+ * distinct arrays of 2^log_ext elements, both read and written. */
+int pz_quotient_permutation_split_dev(pz_ctx* ctx, const uint64_t* d_cols_ext, size_t col_stride, const uint64_t* d_sigma_ext,
+                                      size_t sigma_stride, const uint64_t* d_z_ext, size_t z_stride, uint32_t n_sets_total,
+                                      uint32_t set_lo, uint32_t n_sets, uint32_t chunk_len, uint32_t m_cols, int head, uint32_t log_ext,
+                                      uint32_t rot_step, uint32_t last_rotation, const uint64_t* d_l0, const uint64_t* d_l_last,
+                                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t delta[4],
+                                      const uint64_t coset_g[4], const uint64_t omega_ext[4], const uint64_t y[4], uint64_t* d_h_low,
+                                      uint64_t* d_h_d);
+int pz_quotient_lookup_split_dev(pz_ctx* ctx, const uint64_t* d_input_ext, size_t input_stride, const uint64_t* d_table_ext,
+                                 const uint64_t* d_perm_input_ext, size_t perm_input_stride, const uint64_t* d_perm_table_ext,
+                                 size_t perm_table_stride, const uint64_t* d_z_ext, size_t z_stride, uint32_t n_lookups,
+                                 uint32_t log_ext, uint32_t rot_step, const uint64_t* d_l0, const uint64_t* d_l_last,
+                                 const uint64_t* d_l_active, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
+                                 uint64_t* d_h_low, uint64_t* d_h_d);
+/* The values of that second accumulator on the domain H itself, from the LAGRANGE forms (no transform; call it before they become
+ * coefficients):  d_out[i] = sum_j y^(S-1-j + 5 n_lookups) D_j(omega^i) + sum_l y^(5 (n_lookups-1-l) + 2) D^lk_l(omega^i) for the rows
+ * row_lo <= i < 2^log_n, zero below row_lo, with S = ceil(m / chunk_len),
+ *   D_j  = z_j(omega X) prod_c (v_c + beta sigma_c + gamma) - z_j(X) prod_c (v_c + beta delta^c X + gamma)   (c over set j's columns),
+ *   D^lk = z(omega X)(a' + beta)(s' + gamma) - z(X)(a + beta)(s + gamma);
+ * row 2^log_n - 1 reads z(omega^0).  With row_lo = the usable rows these are ALL the non-zero values of D on H: on the active rows
+ * the recurrence that built the products makes every D_j and D^lk vanish.  One lane per (set or lookup, row): the cost of
+ * 2^log_n - row_lo rows (at most 65535).  d_cols / d_sigma: [m][2^log_n], d_z: [S][..], the lookup arrays [n_lookups][..], d_table one
+ * column (all NULL-able when n_lookups = 0); strides in 64-bit words; challenges canonical, Montgomery form. */
+int pz_quotient_d_rows_dev(pz_ctx* ctx, const uint64_t* d_cols, size_t col_stride, const uint64_t* d_sigma, size_t sigma_stride,
+                           const uint64_t* d_z, size_t z_stride, uint32_t m, uint32_t chunk_len, const uint64_t* d_input,
+                           size_t input_stride, const uint64_t* d_table, const uint64_t* d_perm_input, size_t perm_input_stride,
+                           const uint64_t* d_perm_table, size_t perm_table_stride, const uint64_t* d_zl, size_t zl_stride,
+                           uint32_t n_lookups, uint32_t log_n, size_t row_lo, const uint64_t omega[4], const uint64_t beta[4],
+                           const uint64_t gamma[4], const uint64_t delta[4], const uint64_t y[4], uint64_t* d_out);
+/* d_out[col][i] = d_a[col][i] * d_row[i], i < n (a column times a row of values on the same points, e.g. the accumulator above
+ * times l_active); d_out may be d_a. */
+int pz_fr_mul_row_dev(pz_ctx* ctx, const uint64_t* d_a, size_t n_cols, size_t col_stride, size_t n, const uint64_t* d_row,
+                      uint64_t* d_out, size_t out_stride);
 /* division by the vanishing polynomial on the extended coset: d_h[i] /= (coset_g * omega_ext^i)^(2^log_n) - 1,
  * i < 2^(log_n + log_e) (the divisor takes 2^log_e distinct values; log_e = 0: the points are ONE coset of the 2^log_n-th roots and
  * the divisor is the constant coset_g^n - 1 -- the prover evaluates a quotient of degree < 3n on three such cosets instead of halo2's

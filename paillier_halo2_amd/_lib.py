@@ -143,6 +143,15 @@ SIGNATURES = {
                                                    VP, VP, VP, VP, VP]),
     "pz_quotient_lookup_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_uint32, VP, VP, VP, VP, VP, VP, VP]),
+    "pz_quotient_permutation_split_dev": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, VP, VP, VP, VP, VP,
+                                                    VP, VP, VP, VP, VP]),
+    "pz_quotient_lookup_split_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint32,
+                                               C.c_uint32, C.c_uint32, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "pz_quotient_d_rows_dev": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint32, C.c_uint32, VP, C.c_size_t, VP,
+                                         VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t, C.c_uint32, C.c_uint32, C.c_size_t, VP, VP, VP, VP,
+                                         VP, VP]),
+    "pz_fr_mul_row_dev": (C.c_int, [VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, VP, VP, C.c_size_t]),
     "pz_quotient_finish_dev": (C.c_int, [VP, VP, C.c_uint32, C.c_uint32, VP, VP]),
     "pz_fr_distribute_powers_dev": (C.c_int, [VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, VP, VP]),
     "pz_fr_lincomb_dev": (C.c_int, [VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, VP, VP, C.c_int]),

@@ -696,6 +696,7 @@ struct PermQ {
     S29 y, gamma, delta, beta266;   // challenges as SGPR-resident limbs (host_fr_shl): y, gamma, delta times 2^261, beta times 2^266
     S29 bx266;                      // beta * delta^(index of the call's first column) times 2^266: the identity term's start
     S29 y_chain, y_sets;            // y^(n_sets_total - 1) and y^n_sets times 2^261: the Horner steps of a whole GROUP of lines
+    S29 y_sets_d;                   // split form: the second accumulator's one step, y^n_sets times the head lines' powers of y if head
 };
 // On the 29-bit field (fp29.cuh): ~210 instructions per product instead of ~380 on saturated 32-bit limbs.  Domains: memory
 // holds x * 2^256; f29_mul divides by 2^261, so in every product exactly one operand carries the extra 2^5 -- a challenge
@@ -706,7 +707,10 @@ struct PermQ {
 // beta * delta^c * X of the second row is the first row's negated and the product cur * delta per column is paid once for the pair
 // (3.5 instead of 4 products per row and column; the kernel is at its VALU floor -- profiles/r04_pmc_tail_sq_counters.txt -- so only
 // fewer products shorten it).
-__global__ __launch_bounds__(256) void k_quotient_permutation(PermQ q, Fr* __restrict__ h) {
+// SPLIT (pz_quotient_permutation_split_dev): the sets' group goes to a second accumulator hd WITHOUT its factor l_active, h takes the
+// head lines alone; both step through the same powers of y (hd takes the head lines' steps together with its sets' step, y_sets_d), so
+// h + l_active * hd is the unsplit h point for point, whatever the two accumulators held before the call.
+template <bool SPLIT> __global__ __launch_bounds__(256) void k_quotient_permutation(PermQ q, Fr* __restrict__ h, Fr* __restrict__ hd) {
     const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t half = q.N >> 1;
     if (i0 >= half) return;
@@ -785,21 +789,26 @@ __global__ __launch_bounds__(256) void k_quotient_permutation(PermQ q, Fr* __res
     }
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        acc[r] = f29_mul2_s(acc[r], q.y_sets.v, hs[r], f29_load_shl5<FrTag>(q.lactive + row[r]));
+        if (SPLIT) {
+            f29_store<0>(hd + row[r], f29_mul2_s(f29_load<FrTag>(hd + row[r]), q.y_sets_d.v, hs[r], f29_one<FrTag>()));
+            acc[r] = f29_mul_s(acc[r], q.y_sets.v);
+        } else {
+            acc[r] = f29_mul2_s(acc[r], q.y_sets.v, hs[r], f29_load_shl5<FrTag>(q.lactive + row[r]));
+        }
         f29_store<0>(h + row[r], acc[r]);
     }
 }
 
-extern "C" int pz_quotient_permutation_part_dev(pz_ctx* ctx, const uint64_t* d_cols_ext, size_t col_stride,
-                                                const uint64_t* d_sigma_ext, size_t sigma_stride, const uint64_t* d_z_ext,
-                                                size_t z_stride, uint32_t n_sets_total, uint32_t set_lo, uint32_t n_sets,
-                                                uint32_t chunk_len, uint32_t m_cols, int head, uint32_t log_ext, uint32_t rot_step,
-                                                uint32_t last_rotation, const uint64_t* d_l0, const uint64_t* d_l_last,
-                                                const uint64_t* d_l_active, const uint64_t beta[4], const uint64_t gamma[4],
-                                                const uint64_t delta[4], const uint64_t coset_g[4], const uint64_t omega_ext[4],
-                                                const uint64_t y[4], uint64_t* d_h) {
-    if (!ctx || !d_cols_ext || !d_sigma_ext || !d_z_ext || !d_l0 || !d_l_last || !d_l_active || !beta || !gamma || !delta ||
-        !coset_g || !omega_ext || !y || !d_h)
+// d_hd == nullptr: the unsplit form (d_l_active required); otherwise the split form (d_l_active unused)
+static int quotient_permutation_launch(pz_ctx* ctx, const uint64_t* d_cols_ext, size_t col_stride, const uint64_t* d_sigma_ext,
+                                       size_t sigma_stride, const uint64_t* d_z_ext, size_t z_stride, uint32_t n_sets_total,
+                                       uint32_t set_lo, uint32_t n_sets, uint32_t chunk_len, uint32_t m_cols, int head, uint32_t log_ext,
+                                       uint32_t rot_step, uint32_t last_rotation, const uint64_t* d_l0, const uint64_t* d_l_last,
+                                       const uint64_t* d_l_active, const uint64_t beta[4], const uint64_t gamma[4],
+                                       const uint64_t delta[4], const uint64_t coset_g[4], const uint64_t omega_ext[4],
+                                       const uint64_t y[4], uint64_t* d_h, uint64_t* d_hd) {
+    if (!ctx || !d_cols_ext || !d_sigma_ext || !d_z_ext || !d_l0 || !d_l_last || (!d_l_active && !d_hd) || !beta || !gamma || !delta ||
+        !coset_g || !omega_ext || !y || !d_h || d_h == d_hd)
         return PZ_ERR_INVALID;
     if (log_ext > 28 || log_ext == 0 || n_sets == 0 || chunk_len == 0 || m_cols == 0 || col_stride % 4 || sigma_stride % 4 || z_stride % 4)
         return PZ_ERR_INVALID;
@@ -827,12 +836,43 @@ extern "C" int pz_quotient_permutation_part_dev(pz_ctx* ctx, const uint64_t* d_c
     q.y_chain = host_fr_shl(yp, 5);
     host_fr_pow(y, n_sets, yp);
     q.y_sets = host_fr_shl(yp, 5);
+    // with the head lines the first accumulator also steps y twice (boundary lines) and y^(n_sets_total - 1) (the chaining group)
+    host_fr_pow(y, n_sets + (head ? 2 + (n_sets_total > 1 ? n_sets_total - 1 : 0) : 0), yp);
+    q.y_sets_d = host_fr_shl(yp, 5);
     void* xp;
     PZCHK(pz_get_pow_table(ctx, omega_ext, N, &xp, coset_g));   // X_i = coset_g * omega_ext^i, cached across calls
     q.xpow = (const Fr*)xp;
-    hipLaunchKernelGGL(k_quotient_permutation, dim3(pz_div_up(N / 2, 256)), dim3(256), 0, ctx->stream, q, (Fr*)d_h);   // a thread per row PAIR
+    // a thread per row PAIR
+    if (d_hd) hipLaunchKernelGGL(k_quotient_permutation<true>, dim3(pz_div_up(N / 2, 256)), dim3(256), 0, ctx->stream, q, (Fr*)d_h, (Fr*)d_hd);
+    else hipLaunchKernelGGL(k_quotient_permutation<false>, dim3(pz_div_up(N / 2, 256)), dim3(256), 0, ctx->stream, q, (Fr*)d_h, (Fr*)nullptr);
     HIPCHK(ctx, hipGetLastError());
     return PZ_OK;
+}
+extern "C" int pz_quotient_permutation_part_dev(pz_ctx* ctx, const uint64_t* d_cols_ext, size_t col_stride,
+                                                const uint64_t* d_sigma_ext, size_t sigma_stride, const uint64_t* d_z_ext,
+                                                size_t z_stride, uint32_t n_sets_total, uint32_t set_lo, uint32_t n_sets,
+                                                uint32_t chunk_len, uint32_t m_cols, int head, uint32_t log_ext, uint32_t rot_step,
+                                                uint32_t last_rotation, const uint64_t* d_l0, const uint64_t* d_l_last,
+                                                const uint64_t* d_l_active, const uint64_t beta[4], const uint64_t gamma[4],
+                                                const uint64_t delta[4], const uint64_t coset_g[4], const uint64_t omega_ext[4],
+                                                const uint64_t y[4], uint64_t* d_h) {
+    if (!d_l_active) return PZ_ERR_INVALID;
+    return quotient_permutation_launch(ctx, d_cols_ext, col_stride, d_sigma_ext, sigma_stride, d_z_ext, z_stride, n_sets_total, set_lo, n_sets,
+                                       chunk_len, m_cols, head, log_ext, rot_step, last_rotation, d_l0, d_l_last, d_l_active, beta, gamma, delta,
+                                       coset_g, omega_ext, y, d_h, nullptr);
+}
+extern "C" int pz_quotient_permutation_split_dev(pz_ctx* ctx, const uint64_t* d_cols_ext, size_t col_stride,
+                                                 const uint64_t* d_sigma_ext, size_t sigma_stride, const uint64_t* d_z_ext,
+                                                 size_t z_stride, uint32_t n_sets_total, uint32_t set_lo, uint32_t n_sets,
+                                                 uint32_t chunk_len, uint32_t m_cols, int head, uint32_t log_ext, uint32_t rot_step,
+                                                 uint32_t last_rotation, const uint64_t* d_l0, const uint64_t* d_l_last,
+                                                 const uint64_t beta[4], const uint64_t gamma[4], const uint64_t delta[4],
+                                                 const uint64_t coset_g[4], const uint64_t omega_ext[4], const uint64_t y[4],
+                                                 uint64_t* d_h_low, uint64_t* d_h_d) {
+    if (!d_h_d) return PZ_ERR_INVALID;
+    return quotient_permutation_launch(ctx, d_cols_ext, col_stride, d_sigma_ext, sigma_stride, d_z_ext, z_stride, n_sets_total, set_lo, n_sets,
+                                       chunk_len, m_cols, head, log_ext, rot_step, last_rotation, d_l0, d_l_last, nullptr, beta, gamma, delta,
+                                       coset_g, omega_ext, y, d_h_low, d_h_d);
 }
 extern "C" int pz_quotient_permutation_dev(pz_ctx* ctx, const uint64_t* d_cols_ext, size_t col_stride,
                                            const uint64_t* d_sigma_ext, size_t sigma_stride, const uint64_t* d_z_ext,
@@ -857,10 +897,13 @@ struct LookQ {
     size_t as, aps, sps, zs, N;
     unsigned n_lookups, step;
     S29 beta, gamma, y;   // times 2^261, SGPR-resident limbs (host_fr_shl)
+    S29 y2, y3;           // y^2 and y^3 times 2^261: the steps of the split form's second accumulator
 };
 // (29-bit field, domains as in k_quotient_permutation: beta, gamma, y and the l_* rows carry 2^261; every line of the argument is
 // one f29_mul2 with acc * y)
-__global__ __launch_bounds__(256) void k_quotient_lookup(LookQ q, Fr* __restrict__ h) {
+// SPLIT (pz_quotient_lookup_split_dev): each lookup's product line goes to the second accumulator hd without its factor l_active (hd steps
+// y^3, takes the line, steps y^2: the five powers of y of the lookup's five lines); h keeps the other four and steps once in its place
+template <bool SPLIT> __global__ __launch_bounds__(256) void k_quotient_lookup(LookQ q, Fr* __restrict__ h, Fr* __restrict__ hd) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= q.N) return;
     const size_t mask = q.N - 1;
@@ -868,7 +911,8 @@ __global__ __launch_bounds__(256) void k_quotient_lookup(LookQ q, Fr* __restrict
     const Fr29 one = fr29_one256();
     const Fr29 l0 = f29_load_shl5<FrTag>(q.l0 + i), ll = f29_load_shl5<FrTag>(q.llast + i), la = f29_load_shl5<FrTag>(q.lactive + i);
     const Fr29 sg = f29_add_s(f29_load_shl5<FrTag>(q.s + i), q.gamma.v);   // (s + gamma) 2^261
-    Fr29 acc = f29_load<FrTag>(h + i);
+    Fr29 acc = f29_load<FrTag>(h + i), accd;
+    if (SPLIT) accd = f29_load<FrTag>(hd + i);
     for (unsigned k = 0; k < q.n_lookups; ++k) {
         const Fr zf = fp_load<FrTag>(q.z + (size_t)k * q.zs + i);
         const Fr29 z = f29_from_fp(zf), zn = f29_load<FrTag>(q.z + (size_t)k * q.zs + i_next);
@@ -880,7 +924,12 @@ __global__ __launch_bounds__(256) void k_quotient_lookup(LookQ q, Fr* __restrict
         // 9 * 2^30 * 2^30 + 2^59.8 < 2^64; value < 8p), and z * that is back in the 256-domain
         const Fr29 f1 = f29_mul(f29_add_s(f29_from_fp_shl5(apf), q.beta.v), f29_add_s(f29_from_fp_shl5(spf), q.gamma.v));
         const Fr29 f2 = f29_mul(f29_add_s(f29_load_shl5<FrTag>(q.a + (size_t)k * q.as + i), q.beta.v), sg);
-        acc = f29_mul2_s(acc, q.y.v, f29_sub<2, 29>(f29_mul(zn, f1), f29_mul(z, f2)), la);
+        if (SPLIT) {
+            accd = f29_mul_s(f29_mul2_s(accd, q.y3.v, f29_sub<2, 29>(f29_mul(zn, f1), f29_mul(z, f2)), f29_one<FrTag>()), q.y2.v);
+            acc = f29_mul_s(acc, q.y.v);
+        } else {
+            acc = f29_mul2_s(acc, q.y.v, f29_sub<2, 29>(f29_mul(zn, f1), f29_mul(z, f2)), la);
+        }
         const Fr29 ams = f29_carry(f29_sub<2, 29>(ap, sp));   // a' - s' + 2p, limbs < 2^29 + 8
         acc = f29_mul2_s(acc, q.y.v, ams, l0);
         // (a' - a'(w^-1 X)) * 2^261 from the shl5 images (values below 32p each; + 64p keeps every limb and the value positive)
@@ -888,16 +937,16 @@ __global__ __launch_bounds__(256) void k_quotient_lookup(LookQ q, Fr* __restrict
         acc = f29_mul2_s(acc, q.y.v, f29_mul(ams, dprev), la);
     }
     f29_store<0>(h + i, acc);
+    if (SPLIT) f29_store<0>(hd + i, accd);
 }
 
-extern "C" int pz_quotient_lookup_dev(pz_ctx* ctx, const uint64_t* d_input_ext, size_t input_stride, const uint64_t* d_table_ext,
-                                      const uint64_t* d_perm_input_ext, size_t perm_input_stride,
-                                      const uint64_t* d_perm_table_ext, size_t perm_table_stride, const uint64_t* d_z_ext,
-                                      size_t z_stride, uint32_t n_lookups, uint32_t log_ext, uint32_t rot_step,
-                                      const uint64_t* d_l0, const uint64_t* d_l_last, const uint64_t* d_l_active,
-                                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], uint64_t* d_h) {
+static int quotient_lookup_launch(pz_ctx* ctx, const uint64_t* d_input_ext, size_t input_stride, const uint64_t* d_table_ext,
+                                  const uint64_t* d_perm_input_ext, size_t perm_input_stride, const uint64_t* d_perm_table_ext,
+                                  size_t perm_table_stride, const uint64_t* d_z_ext, size_t z_stride, uint32_t n_lookups, uint32_t log_ext,
+                                  uint32_t rot_step, const uint64_t* d_l0, const uint64_t* d_l_last, const uint64_t* d_l_active,
+                                  const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], uint64_t* d_h, uint64_t* d_hd) {
     if (!ctx || !d_input_ext || !d_table_ext || !d_perm_input_ext || !d_perm_table_ext || !d_z_ext || !d_l0 || !d_l_last ||
-        !d_l_active || !beta || !gamma || !y || !d_h)
+        !d_l_active || !beta || !gamma || !y || !d_h || d_h == d_hd)
         return PZ_ERR_INVALID;
     if (log_ext > 28 || input_stride % 4 || perm_input_stride % 4 || perm_table_stride % 4 || z_stride % 4) return PZ_ERR_INVALID;
     const size_t N = (size_t)1 << log_ext;
@@ -914,7 +963,145 @@ extern "C" int pz_quotient_lookup_dev(pz_ctx* ctx, const uint64_t* d_input_ext, 
     q.as = input_stride / 4; q.aps = perm_input_stride / 4; q.sps = perm_table_stride / 4; q.zs = z_stride / 4; q.N = N;
     q.n_lookups = n_lookups; q.step = rot_step;
     q.beta = host_fr_shl(beta, 5); q.gamma = host_fr_shl(gamma, 5); q.y = host_fr_shl(y, 5);
-    hipLaunchKernelGGL(k_quotient_lookup, dim3(pz_div_up(N, 256)), dim3(256), 0, ctx->stream, q, (Fr*)d_h);
+    uint64_t yp[4];
+    host_fr_mul(y, y, yp);
+    q.y2 = host_fr_shl(yp, 5);
+    host_fr_mul(yp, y, yp);
+    q.y3 = host_fr_shl(yp, 5);
+    if (d_hd) hipLaunchKernelGGL(k_quotient_lookup<true>, dim3(pz_div_up(N, 256)), dim3(256), 0, ctx->stream, q, (Fr*)d_h, (Fr*)d_hd);
+    else hipLaunchKernelGGL(k_quotient_lookup<false>, dim3(pz_div_up(N, 256)), dim3(256), 0, ctx->stream, q, (Fr*)d_h, (Fr*)nullptr);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+extern "C" int pz_quotient_lookup_dev(pz_ctx* ctx, const uint64_t* d_input_ext, size_t input_stride, const uint64_t* d_table_ext,
+                                      const uint64_t* d_perm_input_ext, size_t perm_input_stride,
+                                      const uint64_t* d_perm_table_ext, size_t perm_table_stride, const uint64_t* d_z_ext,
+                                      size_t z_stride, uint32_t n_lookups, uint32_t log_ext, uint32_t rot_step,
+                                      const uint64_t* d_l0, const uint64_t* d_l_last, const uint64_t* d_l_active,
+                                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], uint64_t* d_h) {
+    return quotient_lookup_launch(ctx, d_input_ext, input_stride, d_table_ext, d_perm_input_ext, perm_input_stride, d_perm_table_ext,
+                                  perm_table_stride, d_z_ext, z_stride, n_lookups, log_ext, rot_step, d_l0, d_l_last, d_l_active, beta, gamma, y,
+                                  d_h, nullptr);
+}
+extern "C" int pz_quotient_lookup_split_dev(pz_ctx* ctx, const uint64_t* d_input_ext, size_t input_stride, const uint64_t* d_table_ext,
+                                            const uint64_t* d_perm_input_ext, size_t perm_input_stride,
+                                            const uint64_t* d_perm_table_ext, size_t perm_table_stride, const uint64_t* d_z_ext,
+                                            size_t z_stride, uint32_t n_lookups, uint32_t log_ext, uint32_t rot_step,
+                                            const uint64_t* d_l0, const uint64_t* d_l_last, const uint64_t* d_l_active,
+                                            const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], uint64_t* d_h_low,
+                                            uint64_t* d_h_d) {
+    if (!d_h_d) return PZ_ERR_INVALID;
+    return quotient_lookup_launch(ctx, d_input_ext, input_stride, d_table_ext, d_perm_input_ext, perm_input_stride, d_perm_table_ext,
+                                  perm_table_stride, d_z_ext, z_stride, n_lookups, log_ext, rot_step, d_l0, d_l_last, d_l_active, beta, gamma, y,
+                                  d_h_low, d_h_d);
+}
+
+// ---------------------------------------------------------------------------------------------- the product lines on the domain itself
+// D = sum_j y^(S-1-j+5 Lk) D_j + sum_l y^(5 (Lk-1-l)+2) D^lk_l, the product lines of both arguments WITHOUT their factor l_active and
+// with the weights halo2's Horner gives them, on rows [row_lo, n) of the domain H (the Lagrange forms: no transform).  On the active
+// rows D vanishes by the products' recurrence, so these few values are all of D on H: with the 2n points of part A they determine D
+// (degree <= 3n - 3) and part B is never evaluated.  Row n - 1 reads z(w^0).
+struct DRowsQ {
+    const Fr *cols, *sigma, *z, *a, *s, *ap, *sp, *zl, *wpow, *dpow, *ypow;
+    size_t cs, ss, zs, as, aps, sps, zls, n, row_lo;
+    unsigned m, chunk_len, n_sets, n_lookups;
+    Fr beta, gamma;
+};
+// one lane per (set or lookup, row): blockIdx.y = row - row_lo; the workgroup's 256 weighted terms are summed in LDS -> part[blockIdx.y][blockIdx.x]
+__global__ __launch_bounds__(256) void k_quotient_d_rows(DRowsQ q, Fr* __restrict__ part) {
+    __shared__ Fr s_t[256];
+    const unsigned t = blockIdx.x * 256 + threadIdx.x;
+    const size_t i = q.row_lo + blockIdx.y, i_next = (i + 1) & (q.n - 1);
+    Fr term = fp_zero<FrTag>();
+    if (t < q.n_sets) {
+        const unsigned c0 = t * q.chunk_len;
+        Fr left = fp_load<FrTag>(q.z + (size_t)t * q.zs + i_next), right = fp_load<FrTag>(q.z + (size_t)t * q.zs + i);
+        const Fr bw = fp_mul(q.beta, fp_load<FrTag>(q.wpow + i));   // beta w^i
+        for (unsigned c = c0; c < c0 + q.chunk_len && c < q.m; ++c) {
+            const Fr v = fp_add(fp_load<FrTag>(q.cols + (size_t)c * q.cs + i), q.gamma);
+            left = fp_mul(left, fp_add(v, fp_mul(q.beta, fp_load<FrTag>(q.sigma + (size_t)c * q.ss + i))));
+            right = fp_mul(right, fp_add(v, fp_mul(bw, fp_load<FrTag>(q.dpow + c))));
+        }
+        term = fp_mul(fp_sub(left, right), fp_load<FrTag>(q.ypow + (q.n_sets - 1 - t) + 5u * q.n_lookups));
+    } else if (t - q.n_sets < q.n_lookups) {
+        const unsigned l = t - q.n_sets;
+        const Fr zn = fp_load<FrTag>(q.zl + (size_t)l * q.zls + i_next), z = fp_load<FrTag>(q.zl + (size_t)l * q.zls + i);
+        const Fr f1 = fp_mul(fp_add(fp_load<FrTag>(q.ap + (size_t)l * q.aps + i), q.beta), fp_add(fp_load<FrTag>(q.sp + (size_t)l * q.sps + i), q.gamma));
+        const Fr f2 = fp_mul(fp_add(fp_load<FrTag>(q.a + (size_t)l * q.as + i), q.beta), fp_add(fp_load<FrTag>(q.s + i), q.gamma));
+        term = fp_mul(fp_sub(fp_mul(zn, f1), fp_mul(z, f2)), fp_load<FrTag>(q.ypow + 5u * (q.n_lookups - 1 - l) + 2u));
+    }
+    s_t[threadIdx.x] = term;
+    __syncthreads();
+    for (unsigned off = 128; off; off >>= 1) {
+        if (threadIdx.x < off) s_t[threadIdx.x] = fp_add(s_t[threadIdx.x], s_t[threadIdx.x + off]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) fp_store(part + (size_t)blockIdx.y * gridDim.x + blockIdx.x, s_t[0]);
+}
+// out[row_lo + r] = sum_b part[r][b]  (a handful of workgroups per row)
+__global__ void k_quotient_d_rows_sum(const Fr* __restrict__ part, unsigned nb, size_t rows, size_t row_lo, Fr* __restrict__ out) {
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    Fr acc = fp_zero<FrTag>();
+    for (unsigned b = 0; b < nb; ++b) acc = fp_add(acc, fp_load<FrTag>(part + r * nb + b));
+    fp_store(out + row_lo + r, acc);
+}
+
+extern "C" int pz_quotient_d_rows_dev(pz_ctx* ctx, const uint64_t* d_cols, size_t col_stride, const uint64_t* d_sigma, size_t sigma_stride,
+                                      const uint64_t* d_z, size_t z_stride, uint32_t m, uint32_t chunk_len, const uint64_t* d_input,
+                                      size_t input_stride, const uint64_t* d_table, const uint64_t* d_perm_input, size_t perm_input_stride,
+                                      const uint64_t* d_perm_table, size_t perm_table_stride, const uint64_t* d_zl, size_t zl_stride,
+                                      uint32_t n_lookups, uint32_t log_n, size_t row_lo, const uint64_t omega[4], const uint64_t beta[4],
+                                      const uint64_t gamma[4], const uint64_t delta[4], const uint64_t y[4], uint64_t* d_out) {
+    if (!ctx || !d_cols || !d_sigma || !d_z || !omega || !beta || !gamma || !delta || !y || !d_out || m == 0 || chunk_len == 0 || log_n > 26)
+        return PZ_ERR_INVALID;
+    if (n_lookups && (!d_input || !d_table || !d_perm_input || !d_perm_table || !d_zl)) return PZ_ERR_INVALID;
+    const size_t n = (size_t)1 << log_n;
+    const size_t n_sets = ((size_t)m + chunk_len - 1) / chunk_len;
+    if (row_lo >= n || n - row_lo > 65535 || m > 0xffffffu || n_lookups > 0xffffffu) return PZ_ERR_INVALID;
+    if (col_stride % 4 || sigma_stride % 4 || z_stride % 4 || input_stride % 4 || perm_input_stride % 4 || perm_table_stride % 4 || zl_stride % 4)
+        return PZ_ERR_INVALID;
+    if ((m > 1 && (col_stride < 4 * n || sigma_stride < 4 * n)) || (n_sets > 1 && z_stride < 4 * n)) return PZ_ERR_INVALID;
+    if (n_lookups > 1 && (input_stride < 4 * n || perm_input_stride < 4 * n || perm_table_stride < 4 * n || zl_stride < 4 * n)) return PZ_ERR_INVALID;
+    if (!host_fr_canonical(beta) || !host_fr_canonical(gamma) || !host_fr_canonical(delta) || !host_fr_canonical(y)) return PZ_ERR_INVALID;
+    PZ_ENTER(ctx);
+    const size_t rows = n - row_lo;
+    const unsigned nb = pz_div_up(n_sets + n_lookups, 256);
+    void *wp, *dp, *yp, *part;
+    PZCHK(pz_get_pow_table(ctx, omega, n, &wp));
+    PZCHK(pz_get_pow_table(ctx, delta, m, &dp));
+    PZCHK(pz_get_pow_table(ctx, y, n_sets + 5 * (size_t)n_lookups, &yp));
+    PZCHK(pz_ws_get(ctx, WS_MISC, rows * nb * 32, &part));
+    DRowsQ q;
+    q.cols = (const Fr*)d_cols; q.sigma = (const Fr*)d_sigma; q.z = (const Fr*)d_z; q.a = (const Fr*)d_input; q.s = (const Fr*)d_table;
+    q.ap = (const Fr*)d_perm_input; q.sp = (const Fr*)d_perm_table; q.zl = (const Fr*)d_zl;
+    q.wpow = (const Fr*)wp; q.dpow = (const Fr*)dp; q.ypow = (const Fr*)yp;
+    q.cs = col_stride / 4; q.ss = sigma_stride / 4; q.zs = z_stride / 4; q.as = input_stride / 4; q.aps = perm_input_stride / 4;
+    q.sps = perm_table_stride / 4; q.zls = zl_stride / 4; q.n = n; q.row_lo = row_lo;
+    q.m = m; q.chunk_len = chunk_len; q.n_sets = (unsigned)n_sets; q.n_lookups = n_lookups;
+    q.beta = fr_from_u64(beta); q.gamma = fr_from_u64(gamma);
+    HIPCHK(ctx, hipMemsetAsync(d_out, 0, n * 32, ctx->stream));
+    hipLaunchKernelGGL(k_quotient_d_rows, dim3(nb, (unsigned)rows), dim3(256), 0, ctx->stream, q, (Fr*)part);
+    hipLaunchKernelGGL(k_quotient_d_rows_sum, dim3(pz_div_up(rows, 64)), dim3(64), 0, ctx->stream, (const Fr*)part, nb, rows, row_lo, (Fr*)d_out);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- out[c][i] = a[c][i] * row[i]
+// (out may be a itself: every element is read before its slot is written)
+__global__ __launch_bounds__(256) void k_mul_row_cols(const Fr* a, size_t cs, size_t n, const Fr* __restrict__ row, Fr* out, size_t os) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fp_store(out + (size_t)blockIdx.y * os + i, fp_mul(fp_load<FrTag>(a + (size_t)blockIdx.y * cs + i), fp_load<FrTag>(row + i)));
+}
+extern "C" int pz_fr_mul_row_dev(pz_ctx* ctx, const uint64_t* d_a, size_t n_cols, size_t col_stride, size_t n, const uint64_t* d_row,
+                                 uint64_t* d_out, size_t out_stride) {
+    if (!ctx || col_stride % 4 || out_stride % 4 || (n_cols > 1 && (col_stride < 4 * n || out_stride < 4 * n))) return PZ_ERR_INVALID;
+    if (n_cols == 0 || n == 0) return PZ_OK;
+    if (!d_a || !d_row || !d_out || n_cols > 65535) return PZ_ERR_INVALID;
+    PZ_ENTER(ctx);
+    hipLaunchKernelGGL(k_mul_row_cols, dim3(pz_div_up(n, 256), (unsigned)n_cols), dim3(256), 0, ctx->stream, (const Fr*)d_a, col_stride / 4, n,
+                       (const Fr*)d_row, (Fr*)d_out, out_stride / 4);
     HIPCHK(ctx, hipGetLastError());
     return PZ_OK;
 }

@@ -876,6 +876,43 @@ class Engine:
             VP(d_perm_table_ext), perm_table_stride_u64, VP(d_z_ext), z_stride_u64, n_lookups, log_ext, rot_step, VP(d_l0),
             VP(d_l_last), VP(d_l_active), self._fr1(beta), self._fr1(gamma), self._fr1(y), VP(d_h)), "pz_quotient_lookup_dev")
 
+    def quotient_permutation_split_dev(self, d_cols_ext: int, col_stride_u64: int, d_sigma_ext: int, sigma_stride_u64: int, d_z_ext: int,
+                                       z_stride_u64: int, n_sets_total: int, set_lo: int, n_sets: int, chunk_len: int, m_cols: int,
+                                       head: bool, log_ext: int, rot_step: int, last_rotation: int, d_l0: int, d_l_last: int,
+                                       beta, gamma, delta, coset_g, omega_ext, y, d_h_low: int, d_h_d: int):
+        """quotient_permutation_part_dev with the sets' product lines in a second accumulator, without l_active (pz.h)"""
+        self._chk(self.L.pz_quotient_permutation_split_dev(
+            self.ctx, VP(d_cols_ext), col_stride_u64, VP(d_sigma_ext), sigma_stride_u64, VP(d_z_ext), z_stride_u64, n_sets_total, set_lo,
+            n_sets, chunk_len, m_cols, int(head), log_ext, rot_step, last_rotation, VP(d_l0), VP(d_l_last),
+            self._fr1(beta), self._fr1(gamma), self._fr1(delta), self._fr1(coset_g), self._fr1(omega_ext), self._fr1(y), VP(d_h_low),
+            VP(d_h_d)), "pz_quotient_permutation_split_dev")
+
+    def quotient_lookup_split_dev(self, d_input_ext: int, input_stride_u64: int, d_table_ext: int, d_perm_input_ext: int,
+                                  perm_input_stride_u64: int, d_perm_table_ext: int, perm_table_stride_u64: int, d_z_ext: int,
+                                  z_stride_u64: int, n_lookups: int, log_ext: int, rot_step: int, d_l0: int, d_l_last: int,
+                                  d_l_active: int, beta, gamma, y, d_h_low: int, d_h_d: int):
+        """quotient_lookup_dev with each lookup's product line in a second accumulator, without l_active (pz.h)"""
+        self._chk(self.L.pz_quotient_lookup_split_dev(
+            self.ctx, VP(d_input_ext), input_stride_u64, VP(d_table_ext), VP(d_perm_input_ext), perm_input_stride_u64,
+            VP(d_perm_table_ext), perm_table_stride_u64, VP(d_z_ext), z_stride_u64, n_lookups, log_ext, rot_step, VP(d_l0),
+            VP(d_l_last), VP(d_l_active), self._fr1(beta), self._fr1(gamma), self._fr1(y), VP(d_h_low), VP(d_h_d)),
+            "pz_quotient_lookup_split_dev")
+
+    def quotient_d_rows_dev(self, d_cols: int, col_stride_u64: int, d_sigma: int, sigma_stride_u64: int, d_z: int, z_stride_u64: int,
+                            m: int, chunk_len: int, d_input: int, input_stride_u64: int, d_table: int, d_perm_input: int,
+                            perm_input_stride_u64: int, d_perm_table: int, perm_table_stride_u64: int, d_zl: int, zl_stride_u64: int,
+                            n_lookups: int, log_n: int, row_lo: int, omega, beta, gamma, delta, y, d_out: int):
+        """the product lines' weighted sum D on rows [row_lo, 2^log_n) of the domain, from the Lagrange forms (pz.h)"""
+        self._chk(self.L.pz_quotient_d_rows_dev(
+            self.ctx, VP(d_cols), col_stride_u64, VP(d_sigma), sigma_stride_u64, VP(d_z), z_stride_u64, m, chunk_len, VP(d_input),
+            input_stride_u64, VP(d_table), VP(d_perm_input), perm_input_stride_u64, VP(d_perm_table), perm_table_stride_u64, VP(d_zl),
+            zl_stride_u64, n_lookups, log_n, row_lo, self._fr1(omega), self._fr1(beta), self._fr1(gamma), self._fr1(delta),
+            self._fr1(y), VP(d_out)), "pz_quotient_d_rows_dev")
+
+    def fr_mul_row_dev(self, d_a: int, n_cols: int, col_stride_u64: int, n: int, d_row: int, d_out: int, out_stride_u64: int):
+        self._chk(self.L.pz_fr_mul_row_dev(self.ctx, VP(d_a), n_cols, col_stride_u64, n, VP(d_row), VP(d_out), out_stride_u64),
+                  "pz_fr_mul_row_dev")
+
     def quotient_finish_dev(self, d_h: int, log_n: int, log_e: int, coset_g, omega_ext):
         self._chk(self.L.pz_quotient_finish_dev(self.ctx, VP(d_h), log_n, log_e, self._fr1(coset_g), self._fr1(omega_ext)),
                   "pz_quotient_finish_dev")

@@ -311,7 +311,7 @@ struct Proof {
 };
 
 struct Workspace {
-    uint64_t *Ap, *Sp, *Zl, *Z, *z_ext[2], *ext[2], *lk_ext[2][4], *hh[2], *hp[2], *h, *tmp, *rnd, *hcomb, *w1, *w2, *blind, *out12, *evals;
+    uint64_t *Ap, *Sp, *Zl, *Z, *z_ext, *ext[2], *lk_ext[4], *hh, *hp[2], *gq, *dvec, *d2, *h, *tmp, *rnd, *hcomb, *w1, *w2, *blind, *out12, *evals;
     uint64_t* key_ext[2] = {nullptr, nullptr};   // streamed proving key: the tile of selectors / of sigma columns re-extended per step
     size_t tile, lt;
 };
@@ -325,19 +325,21 @@ inline Workspace make_workspace(Ctx& cx, const ProvingKey& pk, size_t tile = 64)
     w.lt = tile < Lk ? tile : Lk;
     w.Ap = cx.alloc(cx.cols(Lk) * n * 4); w.Sp = cx.alloc(cx.cols(Lk) * n * 4); w.Zl = cx.alloc(cx.cols(Lk) * n * 4);
     w.Z = cx.alloc(cx.cols(S) * n * 4);
-    // the grand products on the quotient's domain: all sets of ONE part at once (the chaining lines read z_{j-1} beside z_j); the parts are
-    // worked one after the other, so one buffer of the larger part serves both
-    const size_t big = d.parts[0].size > d.parts[1].size ? d.parts[0].size : d.parts[1].size;
-    w.z_ext[0] = w.z_ext[1] = cx.alloc(cx.cols(S) * big * 4);
+    // only part A of the quotient's domain is evaluated line by line (Session::quotient): the grand products of all sets there (the
+    // chaining lines read z_{j-1} beside z_j), the tiles, and three accumulators (gate | Low | D); part B carries ONE column
+    const size_t NA = d.parts[0].size, NB = d.parts[1].size;
+    w.z_ext = cx.alloc(cx.cols(S) * NA * 4);
     if (pk.streamed)
-        for (int q = 0; q < 2; ++q) w.key_ext[q] = cx.alloc(tile * big * 4);
-    for (int pi = 0; pi < 2; ++pi) {
-        const size_t Np = d.parts[pi].size;
-        w.ext[pi] = cx.alloc(tile * Np * 4);
-        for (int q = 0; q < 4; ++q) w.lk_ext[pi][q] = cx.alloc(w.lt * Np * 4);
-        w.hh[pi] = cx.alloc(2 * Np * 4);
-        w.hp[pi] = cx.alloc(Np * 4);
-    }
+        for (int q = 0; q < 2; ++q) w.key_ext[q] = cx.alloc(tile * NA * 4);
+    w.ext[0] = cx.alloc(tile * NA * 4);
+    w.ext[1] = cx.alloc(NB * 4);
+    for (int q = 0; q < 4; ++q) w.lk_ext[q] = cx.alloc(w.lt * NA * 4);
+    w.hh = cx.alloc(3 * NA * 4);
+    w.hp[0] = cx.alloc(NA * 4);
+    w.hp[1] = cx.alloc(NB * 4);
+    w.gq = cx.alloc(NA * 4);
+    w.dvec = cx.alloc(n * 4);
+    w.d2 = cx.alloc(n * 4);
     w.h = cx.alloc(4 * n * 4);
     w.tmp = cx.alloc(2 * n * 4);
     w.rnd = cx.alloc(n * 4);
@@ -526,89 +528,107 @@ struct Session {
             for (size_t c0 = 0; c0 < cnt; c0 += tile)
                 PZP_CK(pz_ntt_fr_dev(cx.c, t + c0 * n * 4, cnt - c0 < tile ? cnt - c0 : tile, 4 * n, d.omega_inv.v, k, nullptr, d.n_inv.v));
         };
+        // the product lines on the blinding rows of the domain itself (D on H), while the Lagrange forms exist
+        PZP_CK(pz_quotient_d_rows_dev(cx.c, d_cols, 4 * n, pk.sigma_lagrange, 4 * n, w.Z, 4 * n, (uint32_t)m, CHUNK, d_cols + A * n * 4, 4 * n,
+                                      pk.table_lagrange, w.Ap, 4 * n, w.Sp, 4 * n, w.Zl, 4 * n, (uint32_t)Lk, k, d.usable, d.omega.v, beta.v, gamma.v,
+                                      delta.v, y.v, w.dvec));
         to_coeff(d_cols, m); to_coeff(w.Ap, Lk); to_coeff(w.Sp, Lk); to_coeff(w.Z, S); to_coeff(w.Zl, Lk);
         const size_t n_perm_lines = 2 + (S - 1) + S;
-        // the gate lines on part A alone (prover.py, "the gate lines on part A"): h_G = G / Z_H has degree <= 2n - 3, so part A's 2n
-        // points give its coefficients [g_0 | g_1]; it joins the other lines' quotient as coefficients, times the power of y the Horner
-        // over all lines gives the gate group
+        // Only part A is evaluated line by line (prover.py, "Three cosets").  The numerator is Gate y^.. + Low + l_active D: D = the
+        // y-weighted product lines without their factor l_active, Low = every other permutation and lookup line.  (Gate y^.. + Low) / Z_H
+        // has degree <= 2n - 3: part A's 2n points give its coefficients [q_0 | q_1].  D (degree <= 3n - 3) is known on part A and on H
+        // (w.dvec), which determines it; l_active D / Z_H goes through the three-coset join with ONE column extended to part B.
         const Fr y_gate = pow_small(y, n_perm_lines + 5 * Lk);
-        for (int pi = 0; pi < 2; ++pi) {
-            const Part& pt = d.parts[pi];
-            const size_t Np = pt.size;
-            const unsigned lg = k + pt.log_e, rot = 1u << pt.log_e;
-            auto extend = [&](const uint64_t* src, size_t cnt, uint64_t* dst) {
-                PZP_CK(pz_ntt_fr_extend_dev(cx.c, src, cnt, 4 * n, dst, 4 * Np, k, pt.log_e, d.omega.v, pt.gens.data(), nullptr));
-            };
-            for (size_t s0 = 0; s0 < S; s0 += tile) extend(w.Z + s0 * n * 4, S - s0 < tile ? S - s0 : tile, w.z_ext[pi] + s0 * Np * 4);
-            PZP_CK(pz_dev_memset(cx.c, w.hh[pi], 0, 2 * Np * 32));
-            uint64_t *hg = w.hh[pi], *hp = w.hh[pi] + Np * 4;
-            const uint64_t *l0 = pk.l_ext[pi], *llast = pk.l_ext[pi] + Np * 4, *lact = pk.l_ext[pi] + 2 * Np * 4;
+        const Part &ptA = d.parts[0], &ptB = d.parts[1];
+        auto extend = [&](const Part& pt, const uint64_t* src, size_t cnt, uint64_t* dst) {
+            PZP_CK(pz_ntt_fr_extend_dev(cx.c, src, cnt, 4 * n, dst, 4 * pt.size, k, pt.log_e, d.omega.v, pt.gens.data(), nullptr));
+        };
+        auto to_coeff_part = [&](const Part& pt, uint64_t* t) {   // values on a part -> the polynomial modulo X^size - coset_g^size
+            PZP_CK(pz_ntt_fr_dev(cx.c, t, 1, 4 * pt.size, pt.omega_inv.v, k + pt.log_e, nullptr, pt.size_inv.v));
+            const Fr cg_inv = pzh::inv(pt.coset_g);
+            PZP_CK(pz_fr_distribute_powers_dev(cx.c, t, 1, 4 * pt.size, pt.size, cg_inv.v, nullptr));
+        };
+        uint64_t *t0 = w.tmp, *t1 = w.tmp + n * 4;
+        auto axpy = [&](const uint64_t* a, const Fr& c, const uint64_t* b, uint64_t* out) {   // out = c a + b (n elements)
+            PZP_CK(pz_dev_copy(cx.c, t0, a, n * 32));
+            PZP_CK(pz_dev_copy(cx.c, t1, b, n * 32));
+            PZP_CK(pz_fr_lincomb_dev(cx.c, w.tmp, 2, 4 * n, n, c.v, out, 0));
+        };
+        {
+            const size_t Np = ptA.size;
+            const unsigned lg = k + ptA.log_e, rot = 1u << ptA.log_e;
+            for (size_t s0 = 0; s0 < S; s0 += tile) extend(ptA, w.Z + s0 * n * 4, S - s0 < tile ? S - s0 : tile, w.z_ext + s0 * Np * 4);
+            PZP_CK(pz_dev_memset(cx.c, w.hh, 0, 3 * Np * 32));
+            uint64_t *hg = w.hh, *hlow = w.hh + Np * 4, *hd = w.hh + 2 * Np * 4;
+            const uint64_t *l0 = pk.l_ext[0], *llast = pk.l_ext[0] + Np * 4, *lact = pk.l_ext[0] + 2 * Np * 4;
             // the extended forms of key columns [c0, c0 + cnt): resident, or (streamed proving key) re-extended into the tile buffer
             auto key_tile = [&](const uint64_t* coeff, const uint64_t* resident, size_t res, int which, size_t c0, size_t cnt) -> const uint64_t* {
                 if (c0 + cnt <= res) return resident + c0 * Np * 4;
-                extend(coeff + c0 * n * 4, cnt, w.key_ext[which]);
+                extend(ptA, coeff + c0 * n * 4, cnt, w.key_ext[which]);
                 return w.key_ext[which];
             };
             for (size_t c0 = 0; c0 < m; c0 += tile) {
                 const size_t cnt = m - c0 < tile ? m - c0 : tile;
-                extend(d_cols + c0 * n * 4, cnt, w.ext[pi]);
+                extend(ptA, d_cols + c0 * n * 4, cnt, w.ext[0]);
                 const size_t na = c0 >= A ? 0 : (A - c0 < cnt ? A - c0 : cnt);
-                if (na && pi == 0)
-                    PZP_CK(pz_quotient_gate_dev(cx.c, w.ext[pi], 4 * Np, key_tile(pk.fixed_coeff, pk.fixed_ext[pi], pk.res_fixed, 0, c0, na), 4 * Np, na,
+                if (na)
+                    PZP_CK(pz_quotient_gate_dev(cx.c, w.ext[0], 4 * Np, key_tile(pk.fixed_coeff, pk.fixed_ext[0], pk.res_fixed, 0, c0, na), 4 * Np, na,
                                                 lg, rot, y.v, hg));
-                PZP_CK(pz_quotient_permutation_part_dev(cx.c, w.ext[pi], 4 * Np, key_tile(pk.sigma_coeff, pk.sigma_ext[pi], pk.res_sigma, 1, c0, cnt),
-                                                        4 * Np, w.z_ext[pi], 4 * Np,
-                                                        (uint32_t)S, (uint32_t)(c0 / CHUNK), (uint32_t)((cnt + CHUNK - 1) / CHUNK), CHUNK, (uint32_t)cnt,
-                                                        c0 == 0, lg, rot, bf + 1, l0, llast, lact, beta.v, gamma.v, delta.v, pt.coset_g.v, pt.omega.v,
-                                                        y.v, hp));
+                PZP_CK(pz_quotient_permutation_split_dev(cx.c, w.ext[0], 4 * Np, key_tile(pk.sigma_coeff, pk.sigma_ext[0], pk.res_sigma, 1, c0, cnt),
+                                                         4 * Np, w.z_ext, 4 * Np, (uint32_t)S, (uint32_t)(c0 / CHUNK),
+                                                         (uint32_t)((cnt + CHUNK - 1) / CHUNK), CHUNK, (uint32_t)cnt, c0 == 0, lg, rot, bf + 1, l0,
+                                                         llast, beta.v, gamma.v, delta.v, ptA.coset_g.v, ptA.omega.v, y.v, hlow, hd));
             }
-            uint64_t* hq = w.hp[pi];
-            PZP_CK(pz_dev_copy(cx.c, hq, hp, Np * 32));
             for (size_t l0_ = 0; l0_ < Lk; l0_ += w.lt) {
                 const size_t cnt = Lk - l0_ < w.lt ? Lk - l0_ : w.lt;
-                extend(d_cols + (A + l0_) * n * 4, cnt, w.lk_ext[pi][0]);
-                extend(w.Ap + l0_ * n * 4, cnt, w.lk_ext[pi][1]);
-                extend(w.Sp + l0_ * n * 4, cnt, w.lk_ext[pi][2]);
-                extend(w.Zl + l0_ * n * 4, cnt, w.lk_ext[pi][3]);
-                PZP_CK(pz_quotient_lookup_dev(cx.c, w.lk_ext[pi][0], 4 * Np, pk.table_ext[pi], w.lk_ext[pi][1], 4 * Np,
-                                              w.lk_ext[pi][2], 4 * Np, w.lk_ext[pi][3], 4 * Np, (uint32_t)cnt, lg, rot, l0, llast, lact, beta.v, gamma.v,
-                                              y.v, hq));
+                extend(ptA, d_cols + (A + l0_) * n * 4, cnt, w.lk_ext[0]);
+                extend(ptA, w.Ap + l0_ * n * 4, cnt, w.lk_ext[1]);
+                extend(ptA, w.Sp + l0_ * n * 4, cnt, w.lk_ext[2]);
+                extend(ptA, w.Zl + l0_ * n * 4, cnt, w.lk_ext[3]);
+                PZP_CK(pz_quotient_lookup_split_dev(cx.c, w.lk_ext[0], 4 * Np, pk.table_ext[0], w.lk_ext[1], 4 * Np, w.lk_ext[2], 4 * Np,
+                                                    w.lk_ext[3], 4 * Np, (uint32_t)cnt, lg, rot, l0, llast, lact, beta.v, gamma.v, y.v, hlow, hd));
             }
-            PZP_CK(pz_quotient_finish_dev(cx.c, hq, k, pt.log_e, pt.coset_g.v, pt.omega.v));
-            PZP_CK(pz_ntt_fr_dev(cx.c, hq, 1, 4 * Np, pt.omega_inv.v, lg, nullptr, pt.size_inv.v));
-            const Fr cg_inv = pzh::inv(pt.coset_g);
-            PZP_CK(pz_fr_distribute_powers_dev(cx.c, hq, 1, 4 * Np, Np, cg_inv.v, nullptr));
-            if (pi == 0) {   // h_G the same way back, in place
-                PZP_CK(pz_quotient_finish_dev(cx.c, hg, k, pt.log_e, pt.coset_g.v, pt.omega.v));
-                PZP_CK(pz_ntt_fr_dev(cx.c, hg, 1, 4 * Np, pt.omega_inv.v, lg, nullptr, pt.size_inv.v));
-                PZP_CK(pz_fr_distribute_powers_dev(cx.c, hg, 1, 4 * Np, Np, cg_inv.v, nullptr));
+            // (Gate y^(permutation + lookup lines) + Low) / Z_H -> [q_0 | q_1]
+            PZP_CK(pz_fr_lincomb_dev(cx.c, w.hh, 2, 4 * Np, Np, y_gate.v, w.gq, 0));
+            PZP_CK(pz_quotient_finish_dev(cx.c, w.gq, k, ptA.log_e, ptA.coset_g.v, ptA.omega.v));
+            to_coeff_part(ptA, w.gq);
+            // l_active D on part A, then D itself back to coefficients there: [U_D | D_1], U_D = D_0 + g^2n D_2
+            PZP_CK(pz_fr_mul_row_dev(cx.c, hd, 1, 4 * Np, Np, lact, w.hp[0], 4 * Np));
+            to_coeff_part(ptA, hd);
+        }
+        const Fr g2n = pow_small(pzh::mul(d.coset_g, d.coset_g), n);
+        const Fr lam = pow_small(ptB.coset_g, n);
+        const Fr m1 = pzh::neg(pzh::FR_ONE), mg2n = pzh::neg(g2n);
+        {
+            // D on H -> D mod (X^n - 1) = V_D = D_0 + D_1 + D_2;  D_2 = (V_D - U_D - D_1) / (1 - g^2n)
+            PZP_CK(pz_ntt_fr_dev(cx.c, w.dvec, 1, 4 * n, d.omega_inv.v, k, nullptr, d.n_inv.v));
+            const uint64_t *U_D = w.hh + 2 * ptA.size * 4, *D_1 = U_D + n * 4;
+            axpy(U_D, pzh::FR_ONE, D_1, w.d2);
+            axpy(w.d2, m1, w.dvec, w.d2);
+            const Fr scale = pzh::inv(pzh::add(pzh::FR_ONE, mg2n));
+            PZP_CK(pz_fr_distribute_powers_dev(cx.c, w.d2, 1, 4 * n, n, pzh::FR_ONE.v, scale.v));
+            // on part B (X^n = lam, lam^2 = -g^2n): D = U_D - 2 g^2n D_2 + lam D_1: one column to extend
+            axpy(w.d2, pzh::add(mg2n, mg2n), U_D, w.hp[1]);
+            axpy(D_1, lam, w.hp[1], w.hp[1]);
+            extend(ptB, w.hp[1], 1, w.ext[1]);
+            PZP_CK(pz_fr_mul_row_dev(cx.c, w.ext[1], 1, 4 * n, n, pk.l_ext[1] + 2 * ptB.size * 4, w.hp[1], 4 * n));
+            for (int pi = 0; pi < 2; ++pi) {
+                const Part& pt = d.parts[pi];
+                PZP_CK(pz_quotient_finish_dev(cx.c, w.hp[pi], k, pt.log_e, pt.coset_g.v, pt.omega.v));
+                to_coeff_part(pt, w.hp[pi]);
             }
         }
         // the quotient from three cosets (prover.py): [U | h_1] on part A, V on part B
         pieces = w.h;
         {
-            const Fr g2n = pow_small(pzh::mul(d.coset_g, d.coset_g), n);
-            const Fr lam = pow_small(d.parts[1].coset_g, n);
             uint64_t *U = w.hp[0], *h1 = w.hp[0] + n * 4, *V = w.hp[1];
-            uint64_t *t0 = w.tmp, *t1 = w.tmp + n * 4;
-            PZP_CK(pz_dev_copy(cx.c, pieces + n * 4, h1, n * 32));
-            PZP_CK(pz_dev_copy(cx.c, t0, h1, n * 32));
-            PZP_CK(pz_dev_copy(cx.c, t1, V, n * 32));
-            const Fr mlam = pzh::neg(lam), m1 = pzh::neg(pzh::FR_ONE), mg2n = pzh::neg(g2n);
-            PZP_CK(pz_fr_lincomb_dev(cx.c, w.tmp, 2, 4 * n, n, mlam.v, pieces + 2 * n * 4, 0));      // T = V - lam h_1
-            PZP_CK(pz_dev_copy(cx.c, t0, pieces + 2 * n * 4, n * 32));
-            PZP_CK(pz_dev_copy(cx.c, t1, U, n * 32));
-            PZP_CK(pz_fr_lincomb_dev(cx.c, w.tmp, 2, 4 * n, n, m1.v, pieces + 2 * n * 4, 0));        // U - T
+            axpy(h1, pzh::neg(lam), V, pieces + 2 * n * 4);                        // T = V - lam h_1
+            axpy(pieces + 2 * n * 4, m1, U, pieces + 2 * n * 4);                  // U - T
             const Fr half = pzh::inv(pzh::add(g2n, g2n));
             PZP_CK(pz_fr_distribute_powers_dev(cx.c, pieces + 2 * n * 4, 1, 4 * n, n, pzh::FR_ONE.v, half.v));   // h_2
-            PZP_CK(pz_dev_copy(cx.c, t0, pieces + 2 * n * 4, n * 32));
-            PZP_CK(pz_dev_copy(cx.c, t1, U, n * 32));
-            PZP_CK(pz_fr_lincomb_dev(cx.c, w.tmp, 2, 4 * n, n, mg2n.v, pieces, 0));                  // h_0 = U - g^2n h_2
-            for (size_t i = 0; i < 2; ++i) {                                                          // pieces[i] += y_gate g_i
-                PZP_CK(pz_dev_copy(cx.c, t0, w.hh[0] + i * n * 4, n * 32));
-                PZP_CK(pz_dev_copy(cx.c, t1, pieces + i * n * 4, n * 32));
-                PZP_CK(pz_fr_lincomb_dev(cx.c, w.tmp, 2, 4 * n, n, y_gate.v, pieces + i * n * 4, 0));
-            }
+            axpy(pieces + 2 * n * 4, mg2n, U, pieces);                            // h_0 = U - g^2n h_2
+            axpy(w.gq, pzh::FR_ONE, pieces, pieces);                              // pieces[i] += q_i
+            axpy(w.gq + n * 4, pzh::FR_ONE, h1, pieces + n * 4);
         }
         commit(pk.bm, pieces, 3, w.out12);
         affine(w.out12, 3, out_h);
@@ -712,12 +732,14 @@ struct Session {
         PZP_CK(pz_shplonk_finish_dev(cx.c, st_, shu.v, w.w1, w.w2));
         commit(pk.bm, w.w2, 1, w.out12);
         affine(w.out12, 1, out_w2);
-        // deg h <= 3n - 4, and deg h_G <= 2n - 3 (w.hh[0] still holds [g_0 | g_1]): an unsatisfied gate shows in the latter
-        uint64_t top[12 + 8];
+        // deg h <= 3n - 4; deg (Gate y^.. + Low) / Z_H <= 2n - 3 (w.gq still holds [q_0 | q_1]): an unsatisfied gate or a product that
+        // does not close shows there; deg D <= 3n - 3 (the top two coefficients of D_2): a product that breaks its recurrence on an active row
+        uint64_t top[12 + 8 + 8];
         PZP_CK(pz_download(cx.c, top, pieces + (3 * n - 3) * 4, 96));
-        PZP_CK(pz_download(cx.c, top + 12, w.hh[0] + (2 * n - 2) * 4, 64));
+        PZP_CK(pz_download(cx.c, top + 12, w.gq + (2 * n - 2) * 4, 64));
+        PZP_CK(pz_download(cx.c, top + 20, w.d2 + (n - 2) * 4, 64));
         done(6);
-        for (int i = 0; i < 12 + 8; ++i)
+        for (int i = 0; i < 12 + 8 + 8; ++i)
             if (top[i]) return false;
         return true;
     }

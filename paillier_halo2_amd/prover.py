@@ -434,13 +434,19 @@ class Workspace:
         big = max(pt["size"] for pt in d.parts)
         self._z_ext_flat = _zeros_cap(S, big, 4).view(-1)
         self.z_ext = [self._z_ext_flat[: S * pt["size"] * 4].view(S, pt["size"], 4) for pt in d.parts]
-        self.ext = [_zeros(tile, pt["size"], 4) for pt in d.parts]
+        # three cosets: only part A is evaluated line by line; part B carries ONE column (create_proof, "Three cosets")
+        two = len(d.parts) == 2
+        self.ext = [_zeros(tile if pi == 0 else 1, pt["size"], 4) for pi, pt in enumerate(d.parts)]
         # streamed proving key: the tile of selectors and the tile of sigma columns, re-extended beside the advice tile (one buffer each)
         if pk.streamed:
             self._key_tiles = [_zeros(tile, big, 4).view(-1) for _ in range(2)]
             self.key_ext = [[kt[: tile * pt["size"] * 4].view(tile, pt["size"], 4) for kt in self._key_tiles] for pt in d.parts]
-        self.lk_ext = [[_zeros(lt, pt["size"], 4) for _ in range(4)] for pt in d.parts]
-        self.hh = [_zeros(2, pt["size"], 4) for pt in d.parts]
+        self.lk_ext = [[_zeros(lt, pt["size"], 4) for _ in range(4)] for pt in d.parts[:1]]
+        self.hh = [_zeros(3 if two else 2, pt["size"], 4) for pt in d.parts[:1]]      # gate | Low (or the permutation lines) | D
+        if two:
+            self.gq = _zeros(d.parts[0]["size"], 4)   # (Gate y^.. + Low) / Z_H: values on part A, then its 2n coefficients
+            self.dvec = _zeros(n, 4)                  # D on H (pz_quotient_d_rows_dev), then D mod X^n - 1
+            self.d2 = _zeros(n, 4)                    # D_2: its top two coefficients vanish for products built by their recurrence
         self.hp = [_zeros(pt["size"], 4) for pt in d.parts]
         self.h = _zeros(N, 4)                     # the quotient's coefficients: pieces h_0, h_1, h_2 (and the vanishing h_3 with 4 cosets)
         self.tmp = _zeros(2, n, 4)
@@ -575,95 +581,147 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
     y = M(y_i)
     phase("products_commit")
     # ---- 4. quotient.  Lagrange -> coefficients for everything the proof opens (in place: the Lagrange forms are done with)
+    if len(d.parts) == 2:                       # the product lines on the blinding rows of the domain itself, while the Lagrange forms exist
+        dvec = ws.dvec
+        eng.quotient_d_rows_dev(cols.data_ptr(), 4 * n, pk.sigma_lagrange.data_ptr(), 4 * n, Z.data_ptr(), 4 * n, m, CHUNK, lk_in.data_ptr(), 4 * n,
+                                pk.table_lagrange.data_ptr(), Ap.data_ptr(), 4 * n, Sp.data_ptr(), 4 * n, Zl.data_ptr(), 4 * n, Lk, k, u, M(d.omega),
+                                beta, gamma, M(DELTA), y, dvec.data_ptr())
     for t, cnt in ((cols, m), (Ap, Lk), (Sp, Lk), (Z, S), (Zl, Lk)):
         to_coeff(t, cnt)
     n_perm_lines = 2 + (S - 1) + S
     lt = ws.lk_ext[0][0].shape[0]
-    # the gate lines on part A.  Their numerator G has degree <= 3n - 3 and vanishes on the whole domain, so h_G = G / Z_H has degree
-    # <= 2n - 3: the 2n points of part A give its 2n coefficients [g_0 | g_1] with no wrap-around, and only the permutation and lookup
-    # lines (degree 4n - 4) need part B.  The two quotients are joined as coefficients, the gate's times the power of y the Horner
-    # over all lines gives the gate group.  (cosets = 4: one part, one Horner, as halo2 has it.)
-    split_gate = len(d.parts) == 2
-    for pi, pt in enumerate(d.parts):           # the parts of the quotient's domain: one (halo2's 4n coset) or two (three cosets of <w_n>)
+    Rf, Rs = pk.ext_resident
+    h = ws.h
+    pieces = h.view(d.E, n, 4)                  # h(X) = sum_i X^(n i) h_i(X); degree <= 3n - 4
+
+    def key_tile(pi, coeff, resident, R_, which, c0, cnt):
+        """the extended forms of key columns [c0, c0 + cnt): resident, or (streamed proving key) re-extended into the tile buffer"""
+        if not pk.streamed or c0 + cnt <= R_:
+            return resident[pi][c0].data_ptr()
+        buf = ws.key_ext[pi][which]
+        extend(coeff[c0:c0 + cnt], cnt, buf, d.parts[pi])
+        return buf.data_ptr()
+
+    def to_coeff_part(t, pt):                   # values on a part -> the polynomial modulo X^size - coset_g^size, in place
+        eng.ntt_dev(t.data_ptr(), 1, 4 * pt["size"], M(pt["omega_inv"]), k + pt["log_e"], None, M(pt["size_inv"]))
+        eng.fr_distribute_powers_dev(t.data_ptr(), 1, 4 * pt["size"], pt["size"], M(pow(pt["coset_g"], -1, FR)))
+
+    t01 = ws.tmp
+
+    def axpy(a, c, b, out):                     # out = c a + b  (n elements; c an integer)
+        t01[0].copy_(a); t01[1].copy_(b)
+        eng.fr_lincomb_dev(t01.data_ptr(), 2, 4 * n, n, M(c % FR), out.data_ptr())
+
+    if len(d.parts) == 1:
+        # cosets = 4: halo2's own domain as one part, one Horner over all lines
+        pt = d.parts[0]
         Np, lg, rot = pt["size"], k + pt["log_e"], pt["E"]
         cg, om = M(pt["coset_g"]), M(pt["omega"])
-        z_ext = ws.z_ext[pi]                    # all sets: the chaining lines read z_{j-1} beside z_j
+        z_ext = ws.z_ext[0]                     # all sets: the chaining lines read z_{j-1} beside z_j
         for s0 in range(0, S, tile):
             extend(Z[s0:s0 + tile], min(tile, S - s0), z_ext[s0:s0 + tile], pt)
-        ws.hh[pi].zero_()
-        hg, hp = ws.hh[pi][0], ws.hh[pi][1]     # gate lines / permutation lines, folded apart and joined below: one pass over the tiles
-        ext = ws.ext[pi]
-        l0, llast, lact = (pk.l_ext[pi][i].data_ptr() for i in range(3))
-        Rf, Rs = pk.ext_resident
-
-        def key_tile(coeff, resident, R_, which, c0, cnt):
-            """the extended forms of key columns [c0, c0 + cnt): resident, or (streamed proving key) re-extended into the tile buffer"""
-            if not pk.streamed or c0 + cnt <= R_:
-                return resident[pi][c0].data_ptr()
-            buf = ws.key_ext[pi][which]
-            extend(coeff[c0:c0 + cnt], cnt, buf, pt)
-            return buf.data_ptr()
-
+        ws.hh[0].zero_()
+        hg, hp = ws.hh[0][0], ws.hh[0][1]       # gate lines / permutation lines, folded apart and joined below: one pass over the tiles
+        ext = ws.ext[0]
+        l0, llast, lact = (pk.l_ext[0][i].data_ptr() for i in range(3))
         for c0 in range(0, m, tile):
             cnt = min(tile, m - c0)
             extend(cols[c0:c0 + cnt], cnt, ext, pt)
             na = max(0, min(A, c0 + cnt) - c0)  # advice columns of this tile carry the custom gate
-            if na and (pi == 0 or not split_gate):
-                eng.quotient_gate_dev(ext.data_ptr(), 4 * Np, key_tile(pk.fixed_coeff, pk.fixed_ext, Rf, 0, c0, na), 4 * Np, na, lg, rot, y, hg.data_ptr())
+            if na:
+                eng.quotient_gate_dev(ext.data_ptr(), 4 * Np, key_tile(0, pk.fixed_coeff, pk.fixed_ext, Rf, 0, c0, na), 4 * Np, na, lg, rot, y, hg.data_ptr())
             set_lo, nsets = c0 // CHUNK, -(-cnt // CHUNK)
-            eng.quotient_permutation_part_dev(ext.data_ptr(), 4 * Np, key_tile(pk.sigma_coeff, pk.sigma_ext, Rs, 1, c0, cnt), 4 * Np, z_ext.data_ptr(), 4 * Np, S, set_lo,
+            eng.quotient_permutation_part_dev(ext.data_ptr(), 4 * Np, key_tile(0, pk.sigma_coeff, pk.sigma_ext, Rs, 1, c0, cnt), 4 * Np, z_ext.data_ptr(), 4 * Np, S, set_lo,
                                               nsets, CHUNK, cnt, c0 == 0, lg, rot, bf + 1, l0, llast, lact, beta, gamma, M(DELTA), cg, om, y,
                                               hp.data_ptr())
         # h = hg * y^(permutation lines) + hp, then the lookup lines on top
-        hq = ws.hp[pi]
-        if split_gate:
-            hq.copy_(hp)
-        else:
-            eng.fr_lincomb_dev(ws.hh[pi].data_ptr(), 2, 4 * Np, Np, M(pow(y_i, n_perm_lines, FR)), hq.data_ptr())
+        hq = ws.hp[0]
+        eng.fr_lincomb_dev(ws.hh[0].data_ptr(), 2, 4 * Np, Np, M(pow(y_i, n_perm_lines, FR)), hq.data_ptr())
         for l0_ in range(0, Lk, lt):
             cnt = min(lt, Lk - l0_)
-            e_in, e_ap, e_sp, e_zl = ws.lk_ext[pi]
+            e_in, e_ap, e_sp, e_zl = ws.lk_ext[0]
             extend(cols[A + l0_:A + l0_ + cnt], cnt, e_in, pt)
             extend(Ap[l0_:l0_ + cnt], cnt, e_ap, pt)
             extend(Sp[l0_:l0_ + cnt], cnt, e_sp, pt)
             extend(Zl[l0_:l0_ + cnt], cnt, e_zl, pt)
-            eng.quotient_lookup_dev(e_in.data_ptr(), 4 * Np, pk.table_ext[pi].data_ptr(), e_ap.data_ptr(), 4 * Np, e_sp.data_ptr(), 4 * Np,
+            eng.quotient_lookup_dev(e_in.data_ptr(), 4 * Np, pk.table_ext[0].data_ptr(), e_ap.data_ptr(), 4 * Np, e_sp.data_ptr(), 4 * Np,
                                     e_zl.data_ptr(), 4 * Np, cnt, lg, rot, l0, llast, lact, beta, gamma, y, hq.data_ptr())
         eng.quotient_finish_dev(hq.data_ptr(), k, pt["log_e"], cg, om)
-        # back to coefficients on this part: the quotient modulo X^size - coset_g^size
-        eng.ntt_dev(hq.data_ptr(), 1, 4 * Np, M(pt["omega_inv"]), lg, None, M(pt["size_inv"]))
-        eng.fr_distribute_powers_dev(hq.data_ptr(), 1, 4 * Np, Np, M(pow(pt["coset_g"], -1, FR)))
-        if split_gate and pi == 0:              # h_G the same way back, in place: [g_0 | g_1]
-            eng.quotient_finish_dev(hg.data_ptr(), k, pt["log_e"], cg, om)
-            eng.ntt_dev(hg.data_ptr(), 1, 4 * Np, M(pt["omega_inv"]), lg, None, M(pt["size_inv"]))
-            eng.fr_distribute_powers_dev(hg.data_ptr(), 1, 4 * Np, Np, M(pow(pt["coset_g"], -1, FR)))
-    h = ws.h
-    pieces = h.view(d.E, n, 4)                  # h(X) = sum_i X^(n i) h_i(X); degree <= 3n - 4
-    if len(d.parts) == 1:
-        h.copy_(ws.hp[0])                       # halo2's domain: the 4n coefficients themselves (piece 3 and the top of piece 2 vanish)
+        to_coeff_part(hq, pt)
+        h.copy_(hq)                             # the 4n coefficients themselves (piece 3 and the top of piece 2 vanish)
     else:
+        # Three cosets, of which only part A (g <w_2n>, 2n points) is ever evaluated line by line.  The numerator is
+        # Gate y^.. + Low + l_active D:  D = the y-weighted product lines of both arguments without their factor l_active, Low = every other
+        # permutation and lookup line.  Gate and Low have degree <= 3n - 3 and vanish on the domain, so (Gate y^.. + Low) / Z_H has degree
+        # <= 2n - 3 and part A gives its 2n coefficients with no wrap-around.  D (degree <= 3n - 3) is known on part A and on H itself
+        # (d_rows above: zero on the active rows), which determines it; l_active D / Z_H (degree <= 3n - 4) then goes through the
+        # three-coset join with ONE column extended to part B (DESIGN.md section 6.3).
+        ptA, ptB = d.parts
+        Np, lg, rot = ptA["size"], k + ptA["log_e"], ptA["E"]
+        cg, om = M(ptA["coset_g"]), M(ptA["omega"])
+        z_ext = ws.z_ext[0]
+        for s0 in range(0, S, tile):
+            extend(Z[s0:s0 + tile], min(tile, S - s0), z_ext[s0:s0 + tile], ptA)
+        ws.hh[0].zero_()
+        hg, hlow, hd = ws.hh[0][0], ws.hh[0][1], ws.hh[0][2]
+        ext = ws.ext[0]
+        l0, llast, lact = (pk.l_ext[0][i].data_ptr() for i in range(3))
+        for c0 in range(0, m, tile):
+            cnt = min(tile, m - c0)
+            extend(cols[c0:c0 + cnt], cnt, ext, ptA)
+            na = max(0, min(A, c0 + cnt) - c0)
+            if na:
+                eng.quotient_gate_dev(ext.data_ptr(), 4 * Np, key_tile(0, pk.fixed_coeff, pk.fixed_ext, Rf, 0, c0, na), 4 * Np, na, lg, rot, y, hg.data_ptr())
+            set_lo, nsets = c0 // CHUNK, -(-cnt // CHUNK)
+            eng.quotient_permutation_split_dev(ext.data_ptr(), 4 * Np, key_tile(0, pk.sigma_coeff, pk.sigma_ext, Rs, 1, c0, cnt), 4 * Np, z_ext.data_ptr(), 4 * Np, S,
+                                               set_lo, nsets, CHUNK, cnt, c0 == 0, lg, rot, bf + 1, l0, llast, beta, gamma, M(DELTA), cg, om, y,
+                                               hlow.data_ptr(), hd.data_ptr())
+        for l0_ in range(0, Lk, lt):
+            cnt = min(lt, Lk - l0_)
+            e_in, e_ap, e_sp, e_zl = ws.lk_ext[0]
+            extend(cols[A + l0_:A + l0_ + cnt], cnt, e_in, ptA)
+            extend(Ap[l0_:l0_ + cnt], cnt, e_ap, ptA)
+            extend(Sp[l0_:l0_ + cnt], cnt, e_sp, ptA)
+            extend(Zl[l0_:l0_ + cnt], cnt, e_zl, ptA)
+            eng.quotient_lookup_split_dev(e_in.data_ptr(), 4 * Np, pk.table_ext[0].data_ptr(), e_ap.data_ptr(), 4 * Np, e_sp.data_ptr(), 4 * Np,
+                                          e_zl.data_ptr(), 4 * Np, cnt, lg, rot, l0, llast, lact, beta, gamma, y, hlow.data_ptr(), hd.data_ptr())
+        # (Gate y^(permutation + lookup lines) + Low) / Z_H -> its 2n coefficients [q_0 | q_1]
+        gq = ws.gq
+        eng.fr_lincomb_dev(ws.hh[0].data_ptr(), 2, 4 * Np, Np, M(pow(y_i, n_perm_lines + 5 * Lk, FR)), gq.data_ptr())
+        eng.quotient_finish_dev(gq.data_ptr(), k, ptA["log_e"], cg, om)
+        to_coeff_part(gq, ptA)
+        # l_active D on part A, then D itself back to coefficients there: [U_D | D_1], U_D = D_0 + g^2n D_2
+        eng.fr_mul_row_dev(hd.data_ptr(), 1, 4 * Np, Np, lact, ws.hp[0].data_ptr(), 4 * Np)
+        to_coeff_part(hd, ptA)
+        # D on H -> D mod (X^n - 1) = V_D = D_0 + D_1 + D_2;  D_2 = (V_D - U_D - D_1) / (1 - g^2n)
+        g2n = pow(d.coset_g, 2 * n, FR)
+        lam = pow(ptB["coset_g"], n, FR)
+        eng.ntt_dev(dvec.data_ptr(), 1, 4 * n, M(d.omega_inv), k, None, M(d.n_inv))
+        U_D, D_1, D_2, D_B = hd[:n], hd[n:], ws.d2, ws.hp[1]
+        axpy(U_D, 1, D_1, D_2)
+        axpy(D_2, -1, dvec, D_2)
+        eng.fr_distribute_powers_dev(D_2.data_ptr(), 1, 4 * n, n, M(1), M(pow(1 - g2n, -1, FR)))
+        # on part B (X^n = lam, lam^2 = -g^2n): D = D_0 + lam D_1 - g^2n D_2 = U_D - 2 g^2n D_2 + lam D_1: one column to extend
+        axpy(D_2, -2 * g2n, U_D, D_B)
+        axpy(D_1, lam, D_B, D_B)
+        extB = ws.ext[1]
+        extend(D_B.view(1, n, 4), 1, extB, ptB)
+        eng.fr_mul_row_dev(extB.data_ptr(), 1, 4 * n, n, pk.l_ext[1][2].data_ptr(), ws.hp[1].data_ptr(), 4 * n)
+        for pi, pt in enumerate(d.parts):
+            eng.quotient_finish_dev(ws.hp[pi].data_ptr(), k, pt["log_e"], M(pt["coset_g"]), M(pt["omega"]))
+            to_coeff_part(ws.hp[pi], pt)
         # the quotient from three cosets.  With deg h < 3n:  on part A (g <w_2n>) X^2n = g^2n, so the 2n coefficients found there are
         # [U | h_1] with U = h_0 + g^2n h_2;  on part B (the coset of <w_n> by c = g w_4n) X^n = c^n =: lam (lam^2 = -g^2n), so the n
         # coefficients found there are V = h_0 + lam h_1 - g^2n h_2.  Hence h_2 = (U - V + lam h_1) / (2 g^2n), h_0 = U - g^2n h_2.
-        g2n = pow(d.coset_g, 2 * n, FR)
-        lam = pow(d.parts[1]["coset_g"], n, FR)
         U, h1, V = ws.hp[0][:n], ws.hp[0][n:], ws.hp[1]
-        pieces[1].copy_(h1)
-        t01 = ws.tmp
-        t01[0].copy_(h1); t01[1].copy_(V)
-        eng.fr_lincomb_dev(t01.data_ptr(), 2, 4 * n, n, M(-lam % FR), pieces[2].data_ptr())            # T = V - lam h_1
-        t01[0].copy_(pieces[2]); t01[1].copy_(U)
-        eng.fr_lincomb_dev(t01.data_ptr(), 2, 4 * n, n, M(FR - 1), pieces[2].data_ptr())               # U - T
-        eng.fr_distribute_powers_dev(pieces[2].data_ptr(), 1, 4 * n, n, M(1), M(pow(2 * g2n, -1, FR)))     # h_2
-        t01[0].copy_(pieces[2]); t01[1].copy_(U)
-        eng.fr_lincomb_dev(t01.data_ptr(), 2, 4 * n, n, M(-g2n % FR), pieces[0].data_ptr())            # h_0 = U - g^2n h_2
+        axpy(h1, -lam, V, pieces[2])                                                                    # T = V - lam h_1
+        axpy(pieces[2], -1, U, pieces[2])                                                               # U - T
+        eng.fr_distribute_powers_dev(pieces[2].data_ptr(), 1, 4 * n, n, M(1), M(pow(2 * g2n, -1, FR)))  # h_2
+        axpy(pieces[2], -g2n, U, pieces[0])                                                             # h_0 = U - g^2n h_2
         pieces[3].zero_()
-        # the join: pieces[i] += y^(permutation lines + lookup lines) g_i
-        c_gate = M(pow(y_i, n_perm_lines + 5 * Lk, FR))
-        gq = ws.hh[0][0]
-        for i in range(2):
-            t01[0].copy_(gq[i * n:(i + 1) * n]); t01[1].copy_(pieces[i])
-            eng.fr_lincomb_dev(t01.data_ptr(), 2, 4 * n, n, c_gate, pieces[i].data_ptr())
+        # the join: pieces[i] = l_active D / Z_H's + q_i
+        axpy(gq[:n], 1, pieces[0], pieces[0])
+        axpy(gq[n:], 1, h1, pieces[1])
     c_h = commit(bm, pieces, d.E - 1, 4 * n)
     (a_h,) = tr.absorb_points(eng, c_h)
     x_i = tr.squeeze("x")
@@ -738,7 +796,10 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
     top = host(h[3 * n - 3:] if len(d.parts) == 1 else h[3 * n - 3:3 * n])
     pr.h_top = top
     pr.h_degree_ok = not top.any()
-    if split_gate:                              # deg h_G <= 2n - 3: an unsatisfied gate shows here, no longer in the other lines' top
-        pr.h_degree_ok = pr.h_degree_ok and not host(ws.hh[0][0][2 * n - 2:2 * n]).any()
+    if len(d.parts) == 2:
+        # deg (Gate y^.. + Low) / Z_H <= 2n - 3: an unsatisfied gate, a product that does not close or a permuted column out of order shows
+        # here;  deg D <= 3n - 3 (the top two coefficients of D_2): a product that breaks its recurrence on an active row shows there,
+        # D then being non-zero on a row of H where it was taken as zero
+        pr.h_degree_ok = pr.h_degree_ok and not host(ws.gq[2 * n - 2:2 * n]).any() and not host(ws.d2[n - 2:n]).any()
     phase("finalise")
     return pr

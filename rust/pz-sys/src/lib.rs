@@ -289,6 +289,26 @@ extern "C" {
                                   perm_table_stride: usize, d_z_ext: *const u64, z_stride: usize, n_lookups: u32, log_ext: u32,
                                   rot_step: u32, d_l0: *const u64, d_l_last: *const u64, d_l_active: *const u64,
                                   beta: *const u64, gamma: *const u64, y: *const u64, d_h: *mut u64) -> c_int;
+    pub fn pz_quotient_permutation_split_dev(ctx: *mut pz_ctx, d_cols_ext: *const u64, col_stride: usize, d_sigma_ext: *const u64,
+                                             sigma_stride: usize, d_z_ext: *const u64, z_stride: usize, n_sets_total: u32,
+                                             set_lo: u32, n_sets: u32, chunk_len: u32, m_cols: u32, head: c_int, log_ext: u32,
+                                             rot_step: u32, last_rotation: u32, d_l0: *const u64, d_l_last: *const u64,
+                                             beta: *const u64, gamma: *const u64, delta: *const u64, coset_g: *const u64,
+                                             omega_ext: *const u64, y: *const u64, d_h_low: *mut u64, d_h_d: *mut u64) -> c_int;
+    pub fn pz_quotient_lookup_split_dev(ctx: *mut pz_ctx, d_input_ext: *const u64, input_stride: usize, d_table_ext: *const u64,
+                                        d_perm_input_ext: *const u64, perm_input_stride: usize, d_perm_table_ext: *const u64,
+                                        perm_table_stride: usize, d_z_ext: *const u64, z_stride: usize, n_lookups: u32, log_ext: u32,
+                                        rot_step: u32, d_l0: *const u64, d_l_last: *const u64, d_l_active: *const u64,
+                                        beta: *const u64, gamma: *const u64, y: *const u64, d_h_low: *mut u64,
+                                        d_h_d: *mut u64) -> c_int;
+    pub fn pz_quotient_d_rows_dev(ctx: *mut pz_ctx, d_cols: *const u64, col_stride: usize, d_sigma: *const u64, sigma_stride: usize,
+                                  d_z: *const u64, z_stride: usize, m: u32, chunk_len: u32, d_input: *const u64, input_stride: usize,
+                                  d_table: *const u64, d_perm_input: *const u64, perm_input_stride: usize, d_perm_table: *const u64,
+                                  perm_table_stride: usize, d_zl: *const u64, zl_stride: usize, n_lookups: u32, log_n: u32,
+                                  row_lo: usize, omega: *const u64, beta: *const u64, gamma: *const u64, delta: *const u64,
+                                  y: *const u64, d_out: *mut u64) -> c_int;
+    pub fn pz_fr_mul_row_dev(ctx: *mut pz_ctx, d_a: *const u64, n_cols: usize, col_stride: usize, n: usize, d_row: *const u64,
+                             d_out: *mut u64, out_stride: usize) -> c_int;
     pub fn pz_quotient_finish_dev(ctx: *mut pz_ctx, d_h: *mut u64, log_n: u32, log_e: u32, coset_g: *const u64,
                                   omega_ext: *const u64) -> c_int;
     pub fn pz_fr_distribute_powers_dev(ctx: *mut pz_ctx, d_a: *mut u64, n_cols: usize, col_stride: usize, n: usize,
