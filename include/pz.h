@@ -282,6 +282,20 @@ int pz_paillier_encrypt_uniform_dev(pz_ctx* ctx, uint32_t limbs_n, size_t batch,
                                     const uint64_t* g, const uint64_t* m, const uint64_t* r, uint64_t* d_steps_out, size_t steps_cap,
                                     uint32_t* n_steps_g, uint32_t* n_steps_r, uint64_t* c_out);
 
+/* Tally: C = c_1 * ... * c_count mod n^2, PaillierChip::add (paillier.rs:62-85) folded over `count` FULL-WIDTH ciphertexts
+ * (2*limbs_n limbs each, cts = count x 2*limbs_n words) as a product tree, 2 <= count <= 65536 (else PZ_ERR_INVALID):
+ *   cur = [c_1 .. c_count]; while len(cur) > 1: nxt = [mul_mod(cur[2j], cur[2j+1]) for j < len(cur)/2], an odd last element is
+ *   carried up without a product; cur = nxt.
+ * The count - 1 records a|b|q|r are numbered in the order this loop creates them (level-major); c_out = the root.  n^2 is formed
+ * on the device; one launch per level on the context's stream, no host synchronisation between levels.  steps_out (steps_cap >=
+ * count - 1 records, else PZ_ERR_CAPACITY) may be NULL: the value only.  A ciphertext >= n^2 is PZ_ERR_RANGE (the chain kernel's
+ * range bit: the circuit's r < n^2 check of such a value cannot hold), n = 0 is PZ_ERR_ZERO_MODULUS.  Same host / device split and
+ * buffer conventions as pz_paillier_encrypt[_dev]. */
+int pz_paillier_tally(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts, uint64_t* steps_out,
+                      size_t steps_cap, uint64_t* c_out);
+int pz_paillier_tally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts, uint64_t* d_steps_out,
+                          size_t steps_cap, uint64_t* c_out);
+
 /* ---------------------------------------------------------------------------------------------
  * K4 -- expansion of a step trace into advice-column cells (Fr Montgomery, 32 B each), i.e. the
  * values halo2-lib's Context would hold after BigUintChip emitted the constraints of every
@@ -308,12 +322,21 @@ int pz_witness_expand_dev(pz_ctx* ctx, uint32_t limbs, uint32_t limb_bits, uint3
  * mul_mod steps); the final mul_mod; assign_integer(res, 2*enc_bits); assert_equal_fresh.  Layout and per-operation cell
  * patterns: paillier_halo2_amd/layout.py::circuit_cells, DESIGN.md section 4 (dependency-derived, SURVEY tag [D]).
  * kind = 2: the uniform-shape encrypt circuit of pz_paillier_encrypt_uniform (g^m as pow_mod: num_to_bits of m's limbs, per
- * bit mul_mod + limb-wise select + square_mod; n_steps_g = 2 * limbs_n * limb_bits). */
+ * bit mul_mod + limb-wise select + square_mod; n_steps_g = 2 * limbs_n * limb_bits).
+ * kind = 3: the tally of B = n_steps_g + 1 ciphertexts (pz_paillier_tally), n_steps_r = 0 (anything else: PZ_ERR_INVALID):
+ * assign_integer(n); assign_integer(c_i, 2*enc_bits) for i = 1..B; square + refresh of n, once; the B - 1 mul_mod blocks of the
+ * product tree in record order; assign_integer(res, 2*enc_bits); assert_equal_fresh(root, res).  No load_zero, no g, no pow_mod
+ * constants. */
 int pz_circuit_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g,
                      size_t n_steps_r, size_t* advice_cells, size_t* lookup_cells);
 /* inputs (HOST): n | g | x | y as ceil(limbs_n*limb_bits/64) 64-bit words each, then res as ceil(2*limbs_n*limb_bits/64)
  * words.  d_steps (device): the n_steps_g + n_steps_r + 1 step records K3 produced (add: one record); the circuit's
- * result c is the last record's remainder.  d_modulus: n^2 (device).  d_lookup may be NULL.
+ * result c is the last record's remainder.  kind 3: inputs = n | c_1 .. c_B | res, ceil(limbs_n*limb_bits/64) words, then B times
+ * ceil(2*limbs_n*limb_bits/64), then as many for res; d_steps holds EXACTLY B - 1 = n_steps_g records, the fields a|b|q|r of
+ * ceil(2*limbs_n*limb_bits/64) words each.  pz_paillier_tally_dev writes fields of 2*ceil(limbs_n*limb_bits/64) words: the same where
+ * 64 divides limbs_n*limb_bits (every 64-bit-limb shape), so its device buffer is passed as it stands; otherwise (264-bit n in 88-bit
+ * limbs: 10 words against 9) the records are REPACKED to this width first, as host/paillier_chip.hpp's tally does.  The host inputs
+ * of a large tally (B ciphertexts) are staged through pinned memory that grows to their size.  d_modulus: n^2 (device).  d_lookup may be NULL.
  * rows / col_stride cut the streams into the circuit's columns: cell c goes to column c / rows, row c % rows, columns
  * col_stride elements apart (rows = 2^k - blinding rows, col_stride = 2^k: every column is then a 2^k-row Lagrange vector
  * the commitment, product and NTT entry points take as it stands; rows above `rows` are not written).  0, 0 = dense. */
@@ -794,11 +817,18 @@ int pz_shplonk_free(pz_ctx* ctx, pz_shplonk* state);
  * pz_structure_arrays: DEVICE pointers d_selectors u8 [n_adv][2^k], d_map_col / d_map_row u32 [m][2^k] (m = n_adv + n_lk + 1),
  * d_col_starts u64 [n_adv + 1] (what pz_circuit_expand_cols_dev takes); HOST pointers constants (n_constants x 4 words, canonical)
  * and col_starts_host.  All owned by the structure, valid until pz_structure_free.  Any output may be NULL.
+ * pz_circuit_structure_tally_dev: the structure of the tally circuit (kind 3 of pz_circuit_cells) of `count` ciphertexts, 2 <= count <=
+ * 65536 (else PZ_ERR_INVALID): its shape is count and the key size alone, so there are no exponents.  Block t's operand limbs are tied to
+ * the remainder cells of the block that produced them or to the limb cells of assign_integer(c_i), by the product tree of
+ * pz_paillier_tally.  An ordinary pz_structure (n_steps_g = count - 1, n_steps_r = 0): pz_structure_expose, pz_pk_create[_pub]_dev,
+ * pz_vk_keygen[_pub]_dev and the pz_proof_* stepper take it as it is.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pz_structure pz_structure;
 int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
                              const uint64_t* exp_g, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
                              pz_structure** out);
+int pz_circuit_structure_tally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                   size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_structure_info(const pz_structure* st, size_t* n_adv, size_t* n_adv_filled, size_t* n_lk, size_t* max_rows, size_t* n_constants,
                       size_t* n_cells, size_t* n_lookups, size_t* n_steps_g, size_t* n_steps_r);
 int pz_structure_arrays(const pz_structure* st, const uint8_t** d_selectors, const uint32_t** d_map_col, const uint32_t** d_map_row,
@@ -844,14 +874,17 @@ int pz_proof_free(pz_proof* proof);
  *   - transcript: the n_public values are absorbed as scalars (Montgomery words, like every other scalar) after the caller's seed and
  *     before the first advice commitment; with no instance column nothing is absorbed and every existing transcript is unchanged.
  *   - exposed values: little-endian limbs of limb_bits, n[limbs_n] | g[limbs_n] | c[2 limbs_n] for kind 0 and 2,
- *     n | g | c1[limbs_n] | c2[limbs_n] | c[2 limbs_n] for kind 1 (add); m and r stay private.  (Kind 0 bakes the message's bits into the
+ *     n | g | c1[limbs_n] | c2[limbs_n] | c[2 limbs_n] for kind 1 (add); m and r stay private.  Kind 3 (tally of B = n_steps_g + 1):
+ *     n[limbs_n] | c_1[2 limbs_n] | .. | c_B[2 limbs_n] | C[2 limbs_n].  (Kind 0 bakes the message's bits into the
  *     key's shape -- the reference's property; kind 2, the uniform-shape circuit, is the zero-knowledge statement.)
  * pz_circuit_public_cells  host only: the stream indices of the exposed advice cells in that order (arguments as pz_circuit_cells).
  *                cells_out may be NULL (count only); PZ_ERR_CAPACITY if capacity < *n_public.
  * pz_structure_expose      adds the column to a structure: the exposed cells' (column, row) through the break-point table, the instance
  *                cells inserted into their copy cycles ON THE DEVICE (each the greatest cell of its class: the class's last cell maps to
- *                it, it maps to the class's first; sized for the few hundred cells these circuits expose), d_map_col / d_map_row regrown to [m + 1][2^k] -- pz_structure_arrays returns the new
- *                ones, the earlier pointers are dead.  Selectors and everything else are untouched.  Once per structure.
+ *                it, it maps to the class's first; the n_public rows are grouped by class with one host sort, so a tally's tens of
+ *                thousands of cells cost O(n_public log n_public)), d_map_col / d_map_row regrown to [m + 1][2^k] -- pz_structure_arrays
+ *                returns the new ones, the earlier pointers are dead.  Selectors and everything else are untouched.  Once per structure.
+ *                PZ_ERR_UNSUPPORTED if n_public exceeds max_rows, the column's usable rows (a tally of too many ciphertexts for this k).
  * pz_structure_public      n_instance, n_public and the DEVICE arrays d_cell_col / d_cell_row (u32, n_public each; NULL before expose).
  * pz_public_gather_dev     out_words (HOST, n_public x 4 canonical words) = the exposed cells of a witness column block d_cols (columns
  *                col_stride words apart, Montgomery): a prover reads the statement off its own witness.  Synchronises.  col_stride must be a

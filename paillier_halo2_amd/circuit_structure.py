@@ -300,7 +300,8 @@ class StructureArrays:
     n_steps_g: int
     n_steps_r: int
     # stream indices of the cells a circuit with the instance column exposes, in the column's row order: the limb cells of
-    # n | g | c (encrypt, encrypt_uniform) or n | g | c1 | c2 | c (add) -- pz_circuit_public_cells gives the same list
+    # n | g | c (encrypt, encrypt_uniform), n | g | c1 | c2 | c (add) or n | c_1 | .. | c_B | C (tally) -- pz_circuit_public_cells gives
+    # the same list
     public_cells: Optional[np.ndarray] = None
 
 
@@ -308,10 +309,13 @@ def _exp_bits(e: int) -> List[int]:
     return [(e >> i) & 1 for i in range(e.bit_length())]
 
 
-def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: int = 0, exp_r: int = 0, device: Optional[str] = None) -> StructureArrays:
+def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: int = 0, exp_r: int = 0, device: Optional[str] = None,
+                     count: Optional[int] = None) -> StructureArrays:
     """kind 'encrypt': exp_g = the message m, exp_r = the modulus n -- only their BITS are used, as in the reference's circuit
     (pow_mod_fixed_exp, paillier.rs:50-55); kind 'add': no exponents; kind 'encrypt_uniform' (the uniform-shape circuit, SURVEY 8f rank
-    4): exp_g is ignored -- the message's bits are witness cells, ONE structure serves every message of a key.
+    4): exp_g is ignored -- the message's bits are witness cells, ONE structure serves every message of a key; kind 'tally': count = B
+    full-width ciphertexts multiplied in layout.tally_tree's order, no exponents -- the shape is B and the key
+    size alone.
     device: None -> numpy arrays; a torch device ("cuda") -> the template is tiled THERE and `src` / `lookup_src` are tensors on it (at
     config c2 the tiled arrays are 3.2 GB: 0.9 s of host numpy against a few ms; `columns` takes either)."""
     dev = None
@@ -346,12 +350,22 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             constants.append(v)
         return const_id[v]
 
-    # ---- prefix: the four assign_integer, square, refresh, load_zero (global indices from 0)
+    if kind not in ("encrypt", "encrypt_uniform", "add", "tally"):
+        raise ValueError(f"unknown circuit kind {kind!r}")
+    if (kind == "tally") != (count is not None):
+        raise ValueError("count belongs to kind 'tally', which needs it")
+    tree = layout.tally_tree(count) if kind == "tally" else None      # (refuses a count outside 2 .. TALLY_MAX)
+    # ---- prefix: the four assign_integer (tally: n, then the B ciphertexts at full width), square, refresh, load_zero (not in a
+    # tally: nothing is extended there); global indices from 0
     w = _Walk()
     n_c = _assign(w, Ln, limb_bits, lb)
-    g_c = _assign(w, Ln, limb_bits, lb)
-    x_c = _assign(w, Ln, limb_bits, lb)
-    y_c = _assign(w, Ln, limb_bits, lb)
+    if kind == "tally":
+        ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
+        g_c = x_c = y_c = []
+    else:
+        g_c = _assign(w, Ln, limb_bits, lb)
+        x_c = _assign(w, Ln, limb_bits, lb)
+        y_c = _assign(w, Ln, limb_bits, lb)
     prod = _mul_cells(w, n_c, n_c, 2 * Ln - 1)
     inc = layout.refresh_aux(limb_bits, Ln, Ln)
     w.putc(0)
@@ -372,7 +386,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     for c in cur:
         holder = _range_check(w, c, limb_bits, lb)
         fresh.append(c if c is not None else holder)
-    zero = w.putc(0)
+    zero = w.putc(0) if kind != "tally" else None
     ext_l = lambda limbs: list(limbs) + [zero] * (L - len(limbs))
     parts_src: List[np.ndarray] = []
     parts_mask: List[np.ndarray] = []
@@ -508,6 +522,15 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             results.append(table[acc_blk + 2])
         gm, rn = results
         off, rfin = blocks(off, np.asarray(gm, dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
+    elif kind == "tally":
+        # operand limbs of block t: the remainder cells of the block that produced the operand, or the ciphertext's assigned limbs
+        nb = len(tree)
+        r_of = off + tm.cells * np.arange(nb, dtype=np.int64)[:, None] + tm.r_cells[None, :]
+        table = np.concatenate([r_of, np.asarray(ct_c[::-1], dtype=np.int64)])     # index -(1 + i) -> c_(i+1)
+        tr = np.asarray(tree, dtype=np.int64)
+        off, rfin = blocks(off, table[tr[:, 0]], table[tr[:, 1]])
+        rfin = rfin[-1:]
+        n_steps[0] = nb
     else:
         off, rfin = blocks(off, np.asarray(ext_l(x_c), dtype=np.int64)[None, :], np.asarray(ext_l(y_c), dtype=np.int64)[None, :])
     c_limbs = rfin[0].tolist()
@@ -528,7 +551,10 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         cat = lambda parts: torch.cat([p_ if isinstance(p_, torch.Tensor) else torch.as_tensor(p_, dtype=torch.int64).to(dev) for p_ in parts])
         src, lookup_src = cat(parts_src), cat(parts_lk)
     src[eq_cell] = -(1 + cid(1))          # assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
-    exposed = list(n_c) + list(g_c) + (list(x_c) + list(y_c) if kind == "add" else []) + list(res_c)
+    if kind == "tally":
+        exposed = list(n_c) + [c for ct in ct_c for c in ct] + list(res_c)
+    else:
+        exposed = list(n_c) + list(g_c) + (list(x_c) + list(y_c) if kind == "add" else []) + list(res_c)
     return StructureArrays(n_cells=off, src=src, gate_mask=np.concatenate(parts_mask), lookup_src=lookup_src,
                            constants=constants, result_cell=eq_cell, n_steps_g=n_steps[0], n_steps_r=n_steps[1],
                            public_cells=np.asarray(exposed, dtype=np.int64))
@@ -561,7 +587,9 @@ def columns(sa: StructureArrays, k: int, lb: int, minimum_rows: int = layout.MIN
     Lk = rb.columns_for(NL)
     NP = int(sa.public_cells.shape[0]) if expose else 0
     m = A + Lk + 1 + (1 if expose else 0)
-    assert NK <= max_rows and NP <= max_rows
+    assert NK <= max_rows
+    if NP > max_rows:
+        raise ValueError(f"{NP} public values do not fit the instance column's {max_rows} usable rows")
     if device is None:
         device = "cuda" if (torch.cuda.is_available() and NC > (1 << 22)) else "cpu"
     dev = torch.device(device)

@@ -898,6 +898,78 @@ template <int E> __global__ __launch_bounds__(64) void k_mul_mod(const MulDesc* 
     if (st && lane_id() == 0) atomicOr(D.status, st);
 }
 
+// ---- the product tree of a tally (pz_paillier_tally): prod c_i mod n^2 as ceil(log2 B) levels of independent mul_mods.  One launch
+// per level, ordered by the stream alone -- no workgroup waits for another.  One team per product (the last levels are a handful of
+// products: latency-bound, like a chain step).  A workgroup finds its operands from its index: element e of the level's list is
+// `elems + e * stride` for e < n_regular (level 0: the ciphertext array; above: the remainders of the records one level down) and
+// `tail` for the odd element carried up without a product; it writes its own record in place.  The Barrett constants of n^2 are
+// computed once (k_tally_setup: the reciprocal is 64 * 64 * E steps of restoring division) and read by every workgroup:
+// mod = M' | mu | n^2 (C words each) | shift | ok.
+template <int E> __global__ __launch_bounds__(64) void k_tally_setup(const u64* __restrict__ n, unsigned Ln, u64* __restrict__ mod,
+                                                                      u32* __restrict__ status) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[2 * C];
+    BarrettCtx<E> B;
+    B.sm = s_scratch;
+    B.limbs = 2 * Ln;
+    B.s = 0;
+    LD<E> m = ld_load<E>(n, Ln), lo, hi;
+    ld_mul(lo, hi, m, m);
+    const bool ok = barrett_setup(B, lo);
+    if (ok) {
+        ld_store(mod, B.M, C);
+        ld_store(mod + C, B.mu, C);
+        ld_store(mod + 2 * C, lo, C);
+    }
+    if (lane_id() == 0) {
+        mod[3 * C] = ok ? B.s : 0;
+        mod[3 * C + 1] = ok ? 1 : 0;
+        if (!ok) atomicOr(status, (u32)ST_ZERO_MOD);
+    }
+}
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_tally_level(const u64* __restrict__ mod, const u64* __restrict__ elems,
+                                                                                  size_t stride, unsigned n_regular, const u64* __restrict__ tail,
+                                                                                  u64* __restrict__ recs, unsigned L, u32* __restrict__ status) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (mod[3 * C + 1] == 0) return;   // zero modulus (the same word for every workgroup of every level)
+    const unsigned wave = threadIdx.x >> 6;
+    TeamCtx<E> T;
+    T.buf = s_team;
+    T.w = wave;
+    T.parity = 0;
+    TeamMul<E> tmul{&T};
+    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
+        u64* z = (u64*)s_team;
+        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
+        __syncthreads();
+    }
+    BarrettCtx<E> B;
+    B.sm = s_scratch[wave];
+    B.limbs = L;
+    B.s = (unsigned)mod[3 * C];
+    B.M = ld_load<E>(mod, C);
+    B.mu = ld_load<E>(mod + C, C);
+    const LD<E> n2 = ld_load<E>(mod + 2 * C, C);
+    const size_t ia = 2 * (size_t)blockIdx.x, ib = ia + 1;       // (only b can be the carried element: it is the list's last)
+    const LD<E> a = ld_load<E>(elems + ia * stride, L);
+    const LD<E> b = ld_load<E>(ib < n_regular ? elems + ib * stride : tail, L);
+    unsigned st = ST_OK;
+    LD<E> d;
+    if (!ld_sub(d, a, n2) || !ld_sub(d, b, n2)) st |= ST_RANGE;   // an operand >= n^2: the circuit's r < n^2 check of whatever made it fails
+    LD<E> q, r;
+    st |= mul_mod(B, q, r, a, b, tmul);
+    if (wave == 0) {   // the four waves of the team hold the same values: one of them writes
+        u64* o = recs + (size_t)blockIdx.x * 4 * L;
+        ld_store(o, a, L);
+        ld_store(o + L, b, L);
+        ld_store(o + 2 * L, q, L);
+        ld_store(o + 3 * L, r, L);
+    }
+    if (st && lane_id() == 0) atomicOr(status, st);
+}
+
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
@@ -1247,4 +1319,80 @@ extern "C" int pz_paillier_encrypt_uniform_dev(pz_ctx* ctx, uint32_t limbs_n, si
                                                size_t steps_cap, uint32_t* n_steps_g, uint32_t* n_steps_r, uint64_t* c_out) {
     if (m_bits == 0) return PZ_ERR_INVALID;
     return encrypt_impl(ctx, limbs_n, batch, n, g, m, r, d_steps_out, 1, steps_cap, n_steps_g, n_steps_r, c_out, m_bits);
+}
+
+// PaillierChip::add folded over `count` ciphertexts (paillier.rs:62-85, one mul_mod each) as a product tree: level 0 multiplies
+// (c_1, c_2), (c_3, c_4), ...; an odd last element is carried up without a product; records are numbered level-major.
+#define K3_TALLY_MAX 65536
+static int tally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, const uint64_t* n, const uint64_t* cts, uint64_t* steps_out,
+                      int steps_on_device, size_t steps_cap, uint64_t* c_out) {
+    if (!ctx || !n || !cts || !c_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 2 || count > K3_TALLY_MAX) return PZ_ERR_INVALID;
+    const unsigned L = 2 * Ln;
+    if (L > 128) return PZ_ERR_UNSUPPORTED;
+    if (steps_out && steps_cap < count - 1) return PZ_ERR_CAPACITY;
+    PZ_ENTER(ctx);
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, rec = 4 * (size_t)L;
+    const unsigned C = L <= 64 ? 64 : 128;
+    const size_t in_bytes = (nb + count * lb + 255) & ~(size_t)255, mod_bytes = ((size_t)3 * C + 2) * 8;
+    void* d;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, in_bytes + mod_bytes + 256, &d));
+    char* p = (char*)d;
+    u64* d_n = (u64*)p;
+    u64* d_cts = (u64*)(p + nb);
+    u64* d_mod = (u64*)(p + in_bytes);
+    u32* d_status = (u32*)(p + in_bytes + mod_bytes + 64);
+    u64* d_steps = steps_on_device ? steps_out : nullptr;
+    if (!d_steps) {   // value only, or a host trace: the records live in a workspace (the levels read each other's remainders there)
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_B, (count - 1) * rec * 8, &t));
+        d_steps = (u64*)t;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_n, n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_cts, cts, count * lb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_status, 0, 4, ctx->stream));
+    const u64* root = nullptr;
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        if (C == 64) hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
+        else hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
+        HIPCHK(ctx, hipGetLastError());
+        // the level's list: n_regular strided elements, then (len > n_regular) the carried one
+        const u64 *elems = d_cts, *tail = nullptr;
+        size_t len = count, stride = L, n_regular = count, rec_off = 0;
+        while (len > 1) {
+            const size_t blocks = len / 2;
+            u64* out = d_steps + rec_off * rec;
+            if (C == 64)
+                hipLaunchKernelGGL(k_tally_level<1>, dim3((unsigned)blocks), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, elems, stride,
+                                   (unsigned)n_regular, tail, out, L, d_status);
+            else
+                hipLaunchKernelGGL(k_tally_level<2>, dim3((unsigned)blocks), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, elems, stride,
+                                   (unsigned)n_regular, tail, out, L, d_status);
+            HIPCHK(ctx, hipGetLastError());
+            const u64* last = n_regular == len ? elems + (len - 1) * stride : tail;
+            tail = (len & 1) ? last : nullptr;
+            elems = out + 3 * (size_t)L;
+            stride = rec;
+            n_regular = blocks;
+            len = blocks + (len & 1);
+            rec_off += blocks;
+        }
+        root = elems;   // the last level is one product of two elements: its remainder
+    }
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(c_out, root, lb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&st, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (steps_out && !steps_on_device)
+        HIPCHK(ctx, hipMemcpyAsync(steps_out, d_steps, (count - 1) * rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return status_to_rc(ctx, st);
+}
+extern "C" int pz_paillier_tally(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts,
+                                 uint64_t* steps_out, size_t steps_cap, uint64_t* c_out) {
+    return tally_impl(ctx, limbs_n, count, n, cts, steps_out, 0, steps_cap, c_out);
+}
+extern "C" int pz_paillier_tally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts,
+                                     uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out) {
+    return tally_impl(ctx, limbs_n, count, n, cts, d_steps_out, 1, steps_cap, c_out);
 }

@@ -10,6 +10,8 @@
 //                                          (column, row) through the break-point table and the instance cells join their copy cycles
 //   k_public_gather                        a prover reads the statement off its own witness columns
 // Fr arithmetic: fp.cuh only.  Workgroups of 256 lanes; the field is exact, so no lane count or tree shape changes a result.
+#include <algorithm>
+
 #include "fp.cuh"
 #include "pz_internal.h"
 
@@ -172,10 +174,11 @@ __global__ __launch_bounds__(64) void k_public_find(const uint32_t* __restrict__
 
 // column m of the (m + 1)-column maps.  Row r >= L: identity.  Row i < L, the instance cell (m, i), is the greatest cell of its class: the
 // class's former last cell maps to it and it maps to the class's first.  Exposed cells that share a class (equal e) chain in row order.
-// Every lane of a row < L scans all L entries of e: O(L^2) reads, sized for the few hundred cells these circuits expose (4 or 6 times
-// limbs_n), not for thousands.
+// link[2 r] is the next row of r's class (LINK_NONE: r is its last), link[2 r + 1] is nonzero where an earlier row shares the class:
+// class_links groups the rows by e on the host, so a lane reads its own two words and a tally's tens of thousands of cells cost O(L).
+constexpr uint32_t LINK_NONE = 0xffffffffu;
 __global__ __launch_bounds__(256) void k_public_link(uint32_t* __restrict__ map_col, uint32_t* __restrict__ map_row, uint64_t n, uint32_t m, size_t L,
-                                                     const uint64_t* __restrict__ e, const uint64_t* __restrict__ f) {
+                                                     const uint64_t* __restrict__ e, const uint64_t* __restrict__ f, const uint32_t* __restrict__ link) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const uint64_t self = (uint64_t)m * n + r;
@@ -184,27 +187,32 @@ __global__ __launch_bounds__(256) void k_public_link(uint32_t* __restrict__ map_
         map_row[self] = (uint32_t)r;
         return;
     }
-    const uint64_t ei = e[r];
-    bool has_prev = false, has_next = false;
-    uint64_t next = 0;
-    for (size_t j = 0; j < L; ++j) {
-        if (j == r || e[j] != ei) continue;
-        if (j < r) has_prev = true;
-        else if (!has_next) {
-            has_next = true;
-            next = j;
-        }
-    }
-    if (has_next) {
+    const uint32_t next = link[2 * r];
+    if (next != LINK_NONE) {
         map_col[self] = m;
-        map_row[self] = (uint32_t)next;
+        map_row[self] = next;
     } else {
         map_col[self] = (uint32_t)(f[r] / n);
         map_row[self] = (uint32_t)(f[r] % n);
     }
-    if (!has_prev) {
+    if (!link[2 * r + 1]) {
+        const uint64_t ei = e[r];
         map_col[ei] = m;
         map_row[ei] = (uint32_t)r;
+    }
+}
+
+// the rows of each class (equal e) in increasing order: a sort of the L row numbers by (e, row)
+void class_links(const std::vector<uint64_t>& e, std::vector<uint32_t>& link) {
+    const size_t L = e.size();
+    std::vector<uint32_t> order(L);
+    for (size_t i = 0; i < L; ++i) order[i] = (uint32_t)i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return e[a] != e[b] ? e[a] < e[b] : a < b; });
+    link.assign(2 * L, 0);
+    for (size_t i = 0; i < L; ++i) {
+        const uint32_t r = order[i];
+        link[2 * r] = i + 1 < L && e[order[i + 1]] == e[r] ? order[i + 1] : LINK_NONE;
+        link[2 * r + 1] = i > 0 && e[order[i - 1]] == e[r];
     }
 }
 
@@ -220,9 +228,10 @@ W4 w4_of(const uint64_t v[4]) { return W4{{v[0], v[1], v[2], v[3]}}; }
 
 // stream indices of the exposed cells: n | g | c (encrypt, encrypt_uniform) or n | g | c1 | c2 | c (add), little-endian limbs.  The four
 // assign_integer at the head of the stream put their limbs_n limb cells first; res is the assign_integer(2 limbs_n) in front of the final
-// assert_equal_fresh, the last two operations of the stream.
+// assert_equal_fresh, the last two operations of the stream.  Tally (kind 3, n_steps_g + 1 ciphertexts): n | c_1 | .. | c_B | C, the
+// ciphertexts' 2 limbs_n limb cells at the head of their assign_integer blocks, which follow n's.
 int public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g, size_t n_steps_r, std::vector<uint64_t>& cells) {
-    if (kind < 0 || kind > 2 || limbs_n == 0) return PZ_ERR_INVALID;
+    if (kind < 0 || kind > 3 || limbs_n == 0) return PZ_ERR_INVALID;
     size_t total = 0, a_in = 0, a_res = 0, a_eq = 0;
     PZCHK(pz_circuit_cells(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, &total, nullptr));
     PZCHK(pz_op_cells(0, limbs_n, limb_bits, lookup_bits, &a_in, nullptr));
@@ -231,6 +240,13 @@ int public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup
     if (total < 4 * a_in + a_res + a_eq) return PZ_ERR_INTERNAL;
     const size_t res = total - a_res - a_eq;
     cells.clear();
+    if (kind == 3) {
+        for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(j);
+        for (size_t i = 0; i <= n_steps_g; ++i)
+            for (uint32_t j = 0; j < 2 * limbs_n; ++j) cells.push_back(a_in + i * a_res + j);
+        for (uint32_t j = 0; j < 2 * limbs_n; ++j) cells.push_back(res + j);
+        return PZ_OK;
+    }
     const unsigned heads = kind == 1 ? 4 : 2;   // n, g (, x = c1, y = c2)
     for (unsigned h = 0; h < heads; ++h)
         for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(h * a_in + j);
@@ -296,7 +312,8 @@ extern "C" int pz_structure_expose(pz_structure* st) {
         return PZ_ERR_OOM;
     }
     const size_t L = cells.size(), m = st->n_adv + st->n_lk + 1, n = (size_t)1 << st->k;
-    if (L == 0 || L > st->max_rows || cells.back() >= st->n_cells) return PZ_ERR_INTERNAL;
+    if (L > st->max_rows) return PZ_ERR_UNSUPPORTED;   // (a tally of many ciphertexts: the statement must fit the column's usable rows)
+    if (L == 0 || cells.back() >= st->n_cells) return PZ_ERR_INTERNAL;
     if (m + 1 > ((size_t)1 << 32) / n) return PZ_ERR_UNSUPPORTED;   // the copy-constraint map addresses cells with 32 bits
     // device buffers of this call (released on every path out) and the structure's new arrays (handed over at the end)
     struct Bufs {
@@ -311,8 +328,9 @@ extern "C" int pz_structure_expose(pz_structure* st) {
             return PZ_OK;
         }
     } tmp;
-    void *d_cells, *d_e, *d_f, *d_err, *cc, *cr, *mc, *mr;
+    void *d_cells, *d_e, *d_f, *d_err, *d_link, *cc, *cr, *mc, *mr;
     PZCHK(tmp.get(ctx, L * 8, &d_cells)); PZCHK(tmp.get(ctx, L * 8, &d_e)); PZCHK(tmp.get(ctx, L * 8, &d_f)); PZCHK(tmp.get(ctx, 4, &d_err));
+    PZCHK(tmp.get(ctx, L * 8, &d_link));
     PZCHK(tmp.get(ctx, L * 4, &cc)); PZCHK(tmp.get(ctx, L * 4, &cr));
     PZCHK(tmp.get(ctx, (m + 1) * n * 4, &mc)); PZCHK(tmp.get(ctx, (m + 1) * n * 4, &mr));
     HIPCHK(ctx, hipMemcpyAsync(d_cells, cells.data(), L * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -325,13 +343,24 @@ extern "C" int pz_structure_expose(pz_structure* st) {
     hipLaunchKernelGGL(k_public_find, dim3(pz_div_up(L, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)st->d_map_col, (const uint32_t*)st->d_map_row,
                        (uint64_t)n, (uint64_t)(m * n), (const uint32_t*)cc, (const uint32_t*)cr, L, (uint64_t*)d_e, (uint64_t*)d_f, (unsigned*)d_err);
     HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_public_link, dim3(pz_div_up(n, 256)), dim3(256), 0, ctx->stream, (uint32_t*)mc, (uint32_t*)mr, (uint64_t)n, (uint32_t)m, L,
-                       (const uint64_t*)d_e, (const uint64_t*)d_f);
-    HIPCHK(ctx, hipGetLastError());
+    // the classes' last cells come back once: grouping the exposed rows by class is a sort of L keys, done on the host
     unsigned err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<uint32_t> link;
+    try {
+        std::vector<uint64_t> e(L);
+        HIPCHK(ctx, hipMemcpyAsync(e.data(), d_e, L * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (err) return PZ_ERR_INTERNAL;
+        class_links(e, link);
+    } catch (const std::bad_alloc&) {
+        return PZ_ERR_OOM;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_link, link.data(), L * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_public_link, dim3(pz_div_up(n, 256)), dim3(256), 0, ctx->stream, (uint32_t*)mc, (uint32_t*)mr, (uint64_t)n, (uint32_t)m, L,
+                       (const uint64_t*)d_e, (const uint64_t*)d_f, (const uint32_t*)d_link);
+    HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (err) return PZ_ERR_INTERNAL;
     // the (m + 1)-column maps replace the structure's (the old ones are released with this call's scratch); the cell positions stay
     for (void*& d : tmp.v) {
         if (d == mc) d = st->d_map_col;

@@ -423,14 +423,23 @@ struct Stream {
     }
 };
 
-int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, Stream& S) {
+// kind 3 (the tally): `count` ciphertexts assigned at full width after n, no load_zero, the count - 1 blocks of
+// the product tree (level by level the neighbours of the current list, an odd last element carried up), res, assert_equal_fresh
+int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, Stream& S) {
     const unsigned L = 2 * Ln;
     S.tmpls.reserve(2);                  // (references to the templates stay valid when the uniform circuit adds the second one)
     S.tmpls.push_back(block_template(L, W, lb));
     const Template& tm = S.tmpls[0];
-    // ---- prefix: the four assign_integer, square, refresh, load_zero
+    // ---- prefix: the four assign_integer (tally: n, then the ciphertexts), square, refresh, load_zero (not in a tally)
     Walk w(0);
-    const std::vector<i64> n_c = assign(w, Ln, W, lb), g_c = assign(w, Ln, W, lb), x_c = assign(w, Ln, W, lb), y_c = assign(w, Ln, W, lb);
+    const std::vector<i64> n_c = assign(w, Ln, W, lb);
+    std::vector<i64> g_c, x_c, y_c;
+    std::vector<std::vector<i64>> ct_c;
+    if (kind == 3) {
+        for (size_t i = 0; i < count; ++i) ct_c.push_back(assign(w, L, W, lb));
+    } else {
+        g_c = assign(w, Ln, W, lb); x_c = assign(w, Ln, W, lb); y_c = assign(w, Ln, W, lb);
+    }
     const std::vector<i64> prod = mul_cells(w, n_c, n_c, 2 * Ln - 1);
     std::vector<u8> inc(4 * Ln + 8);
     uint32_t n_inc = 0;
@@ -459,7 +468,7 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
         S.fresh.push_back(c != NONE ? c : holder);
     }
     if (S.fresh.size() != L) return PZ_ERR_UNSUPPORTED;   // the refreshed n^2 has l + r limbs for every shape of this circuit
-    const i64 zero = w.putc(c_small(0));
+    const i64 zero = kind == 3 ? NONE : w.putc(c_small(0));
     auto ext_l = [&](const std::vector<i64>& limbs) {
         std::vector<i64> v(limbs);
         v.resize(L, zero);
@@ -470,6 +479,7 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
     auto r_of = [&](i64 boff, const Template& T, i64 blk, size_t which) { return boff + blk * (i64)T.cells + T.r_cells[which]; };
 
     std::vector<i64> gm, rn;   // the cells holding g^m and r^n
+    i64 root_off = 0;          // the block whose remainder is the circuit's result
     if (kind == 0 || kind == 2) {
         struct Chain { std::vector<i64> base; const u64* e; };
         Chain chains[2] = {{ext_l(g_c), exp_g}, {ext_l(y_c), exp_r}};
@@ -561,12 +571,40 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             if (ns) off = S.blocks(off, 0, std::move(a), std::move(b), {}, ns);
             (ci == 0 ? gm : rn) = res;
         }
+    } else if (kind == 3) {
+        // operands as (producing block | -(1 + ciphertext)); blocks are numbered as the loop creates them: level-major
+        std::vector<i64> cur(count), a_blk, b_blk;
+        for (size_t i = 0; i < count; ++i) cur[i] = -(1 + (i64)i);
+        while (cur.size() > 1) {
+            std::vector<i64> nxt;
+            for (size_t j = 0; j + 1 < cur.size(); j += 2) {
+                nxt.push_back((i64)a_blk.size());
+                a_blk.push_back(cur[j]); b_blk.push_back(cur[j + 1]);
+            }
+            if (cur.size() & 1) nxt.push_back(cur.back());
+            cur.swap(nxt);
+        }
+        const i64 ns = (i64)a_blk.size();
+        auto operand = [&](i64 blk, unsigned j) -> i64 { return blk < 0 ? ct_c[(size_t)(-blk - 1)][j] : r_of(off, tm, blk, j); };
+        std::vector<i64> a((size_t)ns * L), b((size_t)ns * L);
+        for (i64 q = 0; q < ns; ++q)
+            for (unsigned j = 0; j < L; ++j) {
+                a[(size_t)q * L + j] = operand(a_blk[(size_t)q], j);
+                b[(size_t)q * L + j] = operand(b_blk[(size_t)q], j);
+            }
+        S.n_steps_g = (size_t)ns;
+        const i64 tree_off = off;
+        off = S.blocks(off, 0, std::move(a), std::move(b), {}, ns);
+        root_off = tree_off + (ns - 1) * (i64)tm.cells;     // the root is the last block
     } else {
         gm = ext_l(x_c);
         rn = ext_l(y_c);
     }
-    const i64 fin_off = off;
-    off = S.blocks(off, 0, std::vector<i64>(gm), std::vector<i64>(rn), {}, 1);
+    if (kind != 3) {
+        root_off = off;
+        off = S.blocks(off, 0, std::vector<i64>(gm), std::vector<i64>(rn), {}, 1);
+    }
+    const i64 fin_off = root_off;
     // ---- suffix: assign_integer(res), assert_equal_fresh
     Walk ws(off);
     const std::vector<i64> res_c = assign(ws, L, W, lb);
@@ -859,12 +897,12 @@ extern "C" int pz_structure_arrays(const pz_structure* st, const uint8_t** d_sel
     return PZ_OK;
 }
 
-extern "C" int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
-                                        const uint64_t* exp_g, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
-                                        pz_structure** out) {
-    if (!ctx || !out || kind < 0 || kind > 2 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, const uint64_t* exp_g,
+                          const uint64_t* exp_r, size_t count, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
+    if (!ctx || !out || kind < 0 || kind > 3 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+    if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
     if (limb_bits < 16 || limb_bits > 90 || lookup_bits == 0 || lookup_bits >= k || k < 4 || k > 24 || lookup_bits >= limb_bits) return PZ_ERR_INVALID;
-    if ((kind != 1 && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
+    if ((kind != 1 && kind != 3 && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
     const i64 n = (i64)1 << k;
     const i64 unusable = (i64)blinding_factors + 3;
     if (unusable + 8 > n || (i64)minimum_rows >= n) return PZ_ERR_INVALID;
@@ -872,7 +910,7 @@ extern "C" int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n,
     PZ_ENTER(ctx);
     Stream S;
     try {
-        PZCHK(build_stream(kind, limbs_n, limb_bits, lookup_bits, exp_g, exp_r, S));
+        PZCHK(build_stream(kind, limbs_n, limb_bits, lookup_bits, exp_g, exp_r, count, S));
     } catch (const std::bad_alloc&) {
         return PZ_ERR_OOM;
     }
@@ -1018,4 +1056,15 @@ extern "C" int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n,
     guard.armed = false;
     *out = st.release();
     return PZ_OK;
+}
+
+extern "C" int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
+                                        const uint64_t* exp_g, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
+                                        pz_structure** out) {
+    if (kind < 0 || kind > 2) return PZ_ERR_INVALID;   // (the tally has an entry point of its own: this one has no place for its count)
+    return structure_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, k, exp_g, exp_r, 0, minimum_rows, blinding_factors, out);
+}
+extern "C" int pz_circuit_structure_tally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                              size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
+    return structure_impl(ctx, 3, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, minimum_rows, blinding_factors, out);
 }

@@ -706,13 +706,16 @@ extern "C" int pz_witness_expand_dev(pz_ctx* ctx, uint32_t limbs, uint32_t limb_
 struct CircP {
     ExpP e;                         // shape of the mul_mod steps (L = 2 Ln): range-check parameters, limb width
     unsigned Ln, nf, words_n, kind;
+    unsigned n_in;                  // Ln-limb inputs assigned here: n | g | x | y (kinds 0..2) or n alone (kind 3, the tally)
+    size_t res_off;                 // word offset of res inside `inputs`
+    size_t a_cts, l_cts;            // kind 3: the count assign_integer(c_i, 2 Ln limbs) blocks (k_circuit_assign_many)
     unsigned rc_adv, rc_lk;         // range_check(limb, W)
     size_t a_assign[4], a_square, a_refresh, a_zero, a_pow[2], a_res, a_eq;   // advice offsets of the segments
     size_t l_assign[4], l_refresh, l_res;                                      // lookup offsets
     unsigned char inc[CIRC_MAXF];
 };
 
-__global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __restrict__ inputs /* n | g | x | y | res */,
+__global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __restrict__ inputs /* n | g | x | y | res; kind 3: n | c_1 .. c_B | res */,
                                                       const u64* __restrict__ cval /* the circuit's result, L64 words */,
                                                       Fr* __restrict__ advice, Fr* __restrict__ lookup) {
     const CellPtr adv = adv_ptr(C.e, advice, 0), lk{lookup, 0, C.e.rows, C.e.pad, nullptr, 0};
@@ -727,9 +730,9 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
     const bool wide = W > 64;
     const unsigned D = 2 * Ln - 1;
 #define LIMB(X, i) u_make((X)[i][0], (X)[i][1])
-    for (unsigned t = tid; t < 4 * Ln; t += blockDim.x) limb_extract(inputs + (size_t)(t / Ln) * C.words_n, C.words_n, t % Ln, W, s_in[t / Ln][t % Ln]);
+    for (unsigned t = tid; t < C.n_in * Ln; t += blockDim.x) limb_extract(inputs + (size_t)(t / Ln) * C.words_n, C.words_n, t % Ln, W, s_in[t / Ln][t % Ln]);
     for (unsigned t = tid; t < nf; t += blockDim.x) {
-        limb_extract(inputs + 4 * (size_t)C.words_n, C.e.L64, t, W, s_res[t]);
+        limb_extract(inputs + C.res_off, C.e.L64, t, W, s_res[t]);
         limb_extract(cval, C.e.L64, t, W, s_c[t]);
     }
     __syncthreads();
@@ -783,6 +786,7 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
     __syncthreads();
     // ---- assign_integer of n, g, x, y (Ln limbs) and of res (2 Ln limbs)
     for (unsigned which = 0; which < 5; ++which) {
+        if (which >= C.n_in && which < 4) continue;
         const unsigned nl = which < 4 ? Ln : nf;
         const u64(*X)[2] = which < 4 ? s_in[which] : s_res;
         const CellPtr a = adv + (which < 4 ? C.a_assign[which] : C.a_res);
@@ -821,8 +825,8 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
             fp_store(lk + C.l_refresh + t, cv_to_fr(rc_lk_cell(LIMB(s_fresh, t / C.rc_lk), W, lb, t % C.rc_lk)));
     // ---- load_zero; assign_constant(1) + load_zero of both pow_mod_fixed_exp
     if (tid == 0) {
-        fp_store(adv + C.a_zero, fp_zero<FrTag>());
-        if (C.kind != 1)
+        if (C.kind != 3) fp_store(adv + C.a_zero, fp_zero<FrTag>());   // (the tally extends nothing: no load_zero)
+        if (C.kind != 1 && C.kind != 3)
             for (int k = 0; k < 2; ++k) {
                 fp_store(adv + C.a_pow[k], fp_one<FrTag>());
                 fp_store(adv + C.a_pow[k] + 1, fp_zero<FrTag>());
@@ -843,6 +847,27 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
         fp_store(adv + C.a_eq + 2 + t, v);
     }
 #undef LIMB
+}
+
+// ---- tally (kind 3): assign_integer of the B ciphertexts, grid.x = ciphertext -- limbs, then per limb the range check's cells; the
+// shared array holds ONE integer, whatever B is.  vals: grid.x integers of P.L64 words.
+__global__ __launch_bounds__(256) void k_circuit_assign_many(ExpP P, unsigned nl, unsigned rc_adv, unsigned rc_lk, const u64* __restrict__ vals,
+                                                             size_t a0, size_t l0, Fr* __restrict__ advice, Fr* __restrict__ lookup) {
+    __shared__ u64 s_x[CIRC_MAXF][2];
+    const unsigned W = P.W, lb = P.lb, tid = threadIdx.x;
+    const CellPtr a = adv_ptr(P, advice, a0 + (size_t)blockIdx.x * nl * (1 + rc_adv));
+    const CellPtr l{lookup, l0 + (size_t)blockIdx.x * nl * rc_lk, P.rows, P.pad, nullptr, 0};
+    for (unsigned t = tid; t < nl; t += blockDim.x) limb_extract(vals + (size_t)blockIdx.x * P.L64, P.L64, t, W, s_x[t]);
+    __syncthreads();
+    for (unsigned t = tid; t < nl * (1 + rc_adv); t += blockDim.x) {
+        Fr v;
+        if (t < nl) v = fr_from_u(u_make(s_x[t][0], s_x[t][1]));
+        else v = cv_to_fr(rc_adv_cell(u_make(s_x[(t - nl) / rc_adv][0], s_x[(t - nl) / rc_adv][1]), W, lb, (t - nl) % rc_adv));
+        fp_store(a + t, v);
+    }
+    if (l)
+        for (unsigned t = tid; t < nl * rc_lk; t += blockDim.x)
+            fp_store(l + t, cv_to_fr(rc_lk_cell(u_make(s_x[t / rc_lk][0], s_x[t / rc_lk][1]), W, lb, t % rc_lk)));
 }
 
 // ---- uniform-shape circuit: FlexGate::num_to_bits of the message's limbs and the limb-wise select after
@@ -949,7 +974,8 @@ static int refresh_aux_host(unsigned W, unsigned nl, unsigned nr, unsigned char*
 
 static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t ng, size_t nr, CircP& C,
                                size_t* adv_total, size_t* lk_total, size_t step_off[3]) {
-    if (kind < 0 || kind > 2) return PZ_ERR_INVALID;
+    if (kind < 0 || kind > 3) return PZ_ERR_INVALID;
+    if (kind == 3 && (ng < 1 || ng > 65535 || nr)) return PZ_ERR_INVALID;   // the tally of ng + 1 ciphertexts: ng mul_mod blocks
     if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
     memset(&C, 0, sizeof C);
     PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
@@ -962,7 +988,14 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
     if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
     size_t a = 0, l = 0;
     const size_t asg_a = (size_t)limbs_n * (1 + C.rc_adv), asg_l = (size_t)limbs_n * C.rc_lk;
-    for (int k = 0; k < 4; ++k) { C.a_assign[k] = a; C.l_assign[k] = l; a += asg_a; l += asg_l; }
+    C.n_in = kind == 3 ? 1 : 4;
+    for (unsigned k = 0; k < C.n_in; ++k) { C.a_assign[k] = a; C.l_assign[k] = l; a += asg_a; l += asg_l; }
+    C.res_off = 4 * (size_t)C.words_n;
+    if (kind == 3) {   // n | c_1 .. c_B | res: the ciphertexts are full-width integers (2 Ln limbs)
+        C.a_cts = a; C.l_cts = l;
+        a += (ng + 1) * 2 * asg_a; l += (ng + 1) * 2 * asg_l;
+        C.res_off = C.words_n + (ng + 1) * (size_t)C.e.L64;
+    }
     C.a_square = a;
     a += 1;
     for (unsigned i = 0; i < 2 * limbs_n - 1; ++i) a += 1 + 3 * ((size_t)i + 1);
@@ -971,8 +1004,8 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
     for (unsigned i = 0; i < C.nf; ++i) a += ((size_t)C.inc[i] + 1) * 22 + (size_t)C.inc[i] * 4;
     a += (size_t)C.nf * C.rc_adv;
     l += (size_t)C.nf * C.rc_lk;
-    C.a_zero = a; a += 1;
     size_t lstep[3] = {0, 0, 0};
+    if (kind != 3) { C.a_zero = a; a += 1; }   // (the tally extends nothing: no load_zero, no pow_mod constants)
     if (kind == 0) {
         C.a_pow[0] = a; a += 2; step_off[0] = a; lstep[0] = l; a += ng * C.e.cells; l += ng * C.e.lookups;
         C.a_pow[1] = a; a += 2; step_off[1] = a; lstep[1] = l; a += nr * C.e.cells; l += nr * C.e.lookups;
@@ -984,8 +1017,11 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
         a += (size_t)limbs_n * (7 * (size_t)limb_bits - 2) + m_bits * (2 * C.e.cells + 8 * (size_t)C.e.L);
         l += ng * C.e.lookups;
         C.a_pow[1] = a; a += 2; step_off[1] = a; lstep[1] = l; a += nr * C.e.cells; l += nr * C.e.lookups;
+    } else if (kind == 3) {   // the product tree's ng blocks, in record order; no further step
+        step_off[0] = a; lstep[0] = l; a += ng * C.e.cells; l += ng * C.e.lookups;
     } else if (ng || nr) return PZ_ERR_INVALID;
-    step_off[2] = a; lstep[2] = l; a += C.e.cells; l += C.e.lookups;
+    step_off[2] = a; lstep[2] = l;
+    if (kind != 3) { a += C.e.cells; l += C.e.lookups; }
     C.a_res = a; C.l_res = l;
     a += 2 * asg_a; l += 2 * asg_l;
     C.a_eq = a;
@@ -1113,15 +1149,17 @@ static int circuit_expand_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t
         C.e.bp_stride = col_stride;
     }
     PZ_ENTER(ctx);
-    const size_t in_words = 4 * (size_t)C.words_n + C.e.L64;
+    const size_t in_words = C.res_off + C.e.L64;
     void* d_in;
     PZCHK(pz_ws_get(ctx, WS_MISC, in_words * 8 + 64, &d_in));
-    // `inputs` is the caller's (pageable) memory and may go away when this returns: the few hundred bytes go through a pinned
-    // staging block of the context, so the copy is truly asynchronous and reads nothing of the caller's afterwards
+    // `inputs` is the caller's (pageable) memory and may go away when this returns: it goes through a pinned staging block of the
+    // context, so the copy is truly asynchronous and reads nothing of the caller's afterwards.  Kinds 0 to 2: a few hundred bytes.
+    // Kind 3 carries the B ciphertexts (525 KB at B = 1024, 33 MB at B = 65536 for a 2048-bit key): one host memcpy of that size per
+    // call, and the staging block grows to it once (grow-only, so a second tally of the size allocates nothing)
     PZCHK(pz_upload_small_async(ctx, d_in, inputs, in_words * 8));
     pz_timer tm(ctx, PZ_T_EXPAND);
     const size_t rec = 4 * (size_t)C.e.L64;   // words per step record
-    const size_t runs[3] = {kind != 1 ? n_steps_g : 0, kind != 1 ? n_steps_r : 0, 1};
+    const size_t runs[3] = {kind != 1 ? n_steps_g : 0, kind != 1 ? n_steps_r : 0, kind != 3 ? (size_t)1 : 0};
     size_t first = 0;
     for (int k = 0; k < 3; ++k) {
         if (runs[k]) {
@@ -1154,7 +1192,10 @@ static int circuit_expand_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t
         }
         first += runs[k];
     }
-    // the circuit's result c = remainder of the last step (the final mul_mod)
+    if (kind == 3)
+        hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)(n_steps_g + 1)), dim3(256), 0, ctx->stream, C.e, C.nf, C.rc_adv, C.rc_lk,
+                           (const u64*)d_in + C.words_n, C.a_cts, C.l_cts, (Fr*)d_advice, (Fr*)d_lookup);
+    // the circuit's result c = remainder of the last step (the final mul_mod; the tally's root)
     const uint64_t* d_c = d_steps + (first - 1) * rec + 3 * (size_t)C.e.L64;
     hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, (const u64*)d_in, (const u64*)d_c, (Fr*)d_advice,
                        (Fr*)d_lookup);

@@ -466,6 +466,29 @@ class Engine:
                   "pz_paillier_encrypt_uniform_dev")
         return c, ng, nr
 
+    def paillier_tally(self, limbs_n: int, n, cts, want_steps: bool = True):
+        """product tree of B full-width ciphertexts (pz.h pz_paillier_tally): cts is (B, 2*limbs_n).  Returns (C (2*limbs_n,),
+        steps (B - 1, 4, 2*limbs_n) in level-major order, or None)."""
+        L = 2 * limbs_n
+        n = _np(n).reshape(limbs_n)
+        cts = _np(cts).reshape(-1, L)
+        count = cts.shape[0]
+        steps = np.zeros((max(count - 1, 1), 4, L), dtype=np.uint64) if want_steps else None
+        c = np.zeros(L, dtype=np.uint64)
+        self._chk(self.L.pz_paillier_tally(self.ctx, limbs_n, count, _ptr(n), _ptr(cts), _ptr(steps) if want_steps else VP(),
+                                           max(count - 1, 0), _ptr(c)), "pz_paillier_tally")
+        return c, (steps[: count - 1] if want_steps else None)
+
+    def paillier_tally_dev(self, limbs_n: int, n, cts, d_steps: int, steps_cap: int):
+        """the same with the B - 1 records left on the device for K4 (d_steps: steps_cap x 4 x 2*limbs_n u64).  Returns C."""
+        L = 2 * limbs_n
+        n = _np(n).reshape(limbs_n)
+        cts = _np(cts).reshape(-1, L)
+        c = np.zeros(L, dtype=np.uint64)
+        self._chk(self.L.pz_paillier_tally_dev(self.ctx, limbs_n, cts.shape[0], _ptr(n), _ptr(cts), VP(d_steps), steps_cap, _ptr(c)),
+                  "pz_paillier_tally_dev")
+        return c
+
     # ------------------------------------------------------------------ K4: witness expansion
     def witness_cells_per_step(self, limbs: int, limb_bits: int, lookup_bits: int) -> Tuple[int, int]:
         a = C.c_size_t()
@@ -500,7 +523,8 @@ class Engine:
 
     def circuit_expand_dev(self, kind: int, limbs_n: int, limb_bits: int, lookup_bits: int, inputs, d_steps: int, n_steps_g: int,
                            n_steps_r: int, d_modulus: int, d_advice: int, d_lookup: int = 0, rows: int = 0, col_stride: int = 0):
-        """inputs: host uint64 array n | g | x | y | res (pz.h); writes the whole circuit's cell stream, dense or cut into
+        """inputs: host uint64 array n | g | x | y | res, or n | c_1 .. c_B | res for kind 3 (the tally: n_steps_g = B - 1, n_steps_r = 0;
+        pz.h); writes the whole circuit's cell stream, dense or cut into
         columns of `rows` cells stored `col_stride` elements apart"""
         inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
         self._chk(self.L.pz_circuit_expand_dev(self.ctx, kind, limbs_n, limb_bits, lookup_bits, _ptr(inp), VP(d_steps), n_steps_g,

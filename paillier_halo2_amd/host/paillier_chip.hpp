@@ -14,6 +14,7 @@
 //   paillier.rs:11-20 PaillierChip / construct                 pz::PaillierChip / construct
 //   paillier.rs:22-30 get_biguint                              PaillierChip::get_biguint
 //   paillier.rs:32-60 encrypt, :62-85 add                      PaillierChip::encrypt / add
+//   (add folded over B full-width ciphertexts)                 PaillierChip::tally, pz::paillier_tally_test
 //   paillier.rs:87-97 paillier_enc_native / _add_native        pz::paillier_enc_native / paillier_add_native
 //   bench.rs:11-31    input structs, :33-117 drivers           pz::PaillierEncryptionInput ... paillier_enc_test ...
 //
@@ -306,6 +307,41 @@ class PaillierChip {  // paillier.rs:11-15
         auto c2e = c2.extend_limbs(n2.num_limbs() - c2.num_limbs(), zero_value);
         return biguint->mul_mod(ctx, c1e, c2e, n2);
     }
+
+    // The tally: prod cts mod n^2 -- `add` folded over FULL-WIDTH ciphertexts (n2.num_limbs() limbs each, so
+    // nothing is extended and there is no load_zero), n^2 hoisted once as encrypt does (paillier.rs:39-45), the products in
+    // pz_paillier_tally's tree order: level by level the neighbours of the current list, an odd last element carried up.
+    Result<AssignedBigUint<Fresh>> tally(Context& ctx, const EncryptionPublicKeyAssigned& pk_enc,
+                                         const std::vector<AssignedBigUint<Fresh>>& cts) const {
+        using R = Result<AssignedBigUint<Fresh>>;
+        if (cts.size() < 2) return R::Err(PZ_ERR_INVALID, "tally: fewer than two ciphertexts");
+        auto n2m = biguint->square(ctx, pk_enc.n);
+        if (!n2m.ok) return R::Err(n2m.err.status, n2m.err.msg);
+        RefreshAux aux = RefreshAux::new_(biguint->limb_bits, pk_enc.n.num_limbs(), pk_enc.n.num_limbs());
+        auto n2r = biguint->refresh(ctx, n2m.val, aux);
+        if (!n2r.ok) return R::Err(n2r.err.status, n2r.err.msg);
+        const AssignedBigUint<Fresh>& n2 = n2r.val;
+        const unsigned L = n2.num_limbs(), Wd = n2.num_words(), wn = pk_enc.n.num_words(), wk = 2 * wn;   // K3 works on 2 * wn words
+        std::vector<uint64_t> nv = pk_enc.n.words(), cv;
+        for (const auto& c : cts) {
+            if (c.num_limbs() != L) return R::Err(PZ_ERR_INVALID, "tally: a ciphertext is not assigned at full width");
+            std::vector<uint64_t> w = c.value().to_limbs(wk);
+            cv.insert(cv.end(), w.begin(), w.end());
+        }
+        const size_t ns = cts.size() - 1;
+        std::vector<uint64_t> rec(ns * 4 * wk), root(wk);
+        int rc = pz_paillier_tally(ctx.raw(), wn, cts.size(), nv.data(), cv.data(), rec.data(), ns, root.data());
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_tally: ") + pz_strerror(rc));
+        // the tape holds Wd words per integer (Wd < 2 * wn where limb_bits does not divide 64: the words above are zero)
+        std::vector<uint64_t> steps;
+        for (size_t f = 0; f < ns * 4; ++f) {
+            if (BigUint::from_limbs(rec.data() + f * wk, wk).bits() > (size_t)L * biguint->limb_bits)
+                return R::Err(PZ_ERR_RANGE, "a step's integer does not fit the assigned limb count");
+            steps.insert(steps.end(), rec.begin() + f * wk, rec.begin() + f * wk + Wd);
+        }
+        ctx.push_steps(steps, Wd, L, biguint->limb_bits, n2.value());
+        return R::Ok(AssignedBigUint<Fresh>(BigUint::from_limbs(root.data(), wk), L, biguint->limb_bits));
+    }
 };
 
 // paillier.rs:87-92: (g^m * r^n) mod n^2 -- one pz_paillier_encrypt call without a trace
@@ -366,6 +402,26 @@ inline void paillier_enc_add_test(Context& ctx, const RangeChip& range, const Pa
     biguint_chip.assert_equal_fresh(ctx, res, res_assigned).unwrap();
 }
 
+// the tally's driver beside the reference's two: assign n, assign every c_i at 2 * enc_bits, tally, assign res, assert_equal_fresh
+struct PaillierTallyInput {
+    unsigned limb_bits, enc_bits;
+    BigUint n;
+    std::vector<BigUint> cts;
+    BigUint res;
+};
+inline void paillier_tally_test(Context& ctx, const RangeChip& range, const PaillierTallyInput& input) {
+    BigUintChip biguint_chip = BigUintChip::construct(&range, input.limb_bits);
+    PaillierChip paillier_chip = PaillierChip::construct(&biguint_chip, input.enc_bits);
+    auto n_assigned = biguint_chip.assign_integer(ctx, input.n, input.enc_bits).unwrap();
+    EncryptionPublicKeyAssigned pk_enc{n_assigned, {}};   // g plays no part in an addition
+    std::vector<AssignedBigUint<Fresh>> cts;
+    for (const BigUint& c : input.cts) cts.push_back(biguint_chip.assign_integer(ctx, c, input.enc_bits * 2).unwrap());
+    auto root = paillier_chip.tally(ctx, pk_enc, cts).unwrap();
+    auto res_assigned = biguint_chip.assign_integer(ctx, input.res, input.enc_bits * 2).unwrap();
+    if (root.value() != res_assigned.value()) throw std::runtime_error("assertion failed: `(left == right)` (paillier_tally_test)");
+    biguint_chip.assert_equal_fresh(ctx, root, res_assigned).unwrap();
+}
+
 // K4 over the mul_mod steps alone (the bulk of the stream; the caller places the buffers)
 inline int synthesize_witness(Context& ctx, const RangeChip& range, uint64_t* d_steps, uint64_t* d_modulus, uint64_t* d_advice,
                               uint64_t* d_lookup) {
@@ -393,6 +449,26 @@ inline int synthesize_circuit(Context& ctx, int kind, unsigned enc_bits, const B
     in.insert(in.end(), w.begin(), w.end());
     return pz_circuit_expand_dev(ctx.raw(), kind, Ln, W, ctx.lookup_bits(), in.data(), d_steps, n_steps_g, n_steps_r, d_modulus,
                                  d_advice, d_lookup, 0, 0);
+}
+
+// the tally's tape (paillier_tally_test) expanded on the device: circuit kind 3, inputs n | c_1 .. c_B | res
+inline int synthesize_tally_circuit(Context& ctx, unsigned enc_bits, const BigUint& n, const std::vector<BigUint>& cts, const BigUint& res,
+                                    uint64_t* d_steps, uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup) {
+    const unsigned W = ctx.limb_bits(), Ln = enc_bits / W, wn = (Ln * W + 63) / 64, wr = (2 * Ln * W + 63) / 64;
+    if (cts.size() < 2 || ctx.n_steps() != cts.size() - 1) return PZ_ERR_INVALID;
+    size_t a = 0, l = 0;
+    int rc = pz_circuit_cells(3, Ln, W, ctx.lookup_bits(), cts.size() - 1, 0, &a, &l);
+    if (rc != PZ_OK) return rc;
+    if (a != ctx.advice_cells() || l != ctx.lookup_cells()) return PZ_ERR_INVALID;   // the tape is not this driver's
+    std::vector<uint64_t> in = n.to_limbs(wn);
+    for (const BigUint& c : cts) {
+        std::vector<uint64_t> w = c.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    std::vector<uint64_t> w = res.to_limbs(wr);
+    in.insert(in.end(), w.begin(), w.end());
+    return pz_circuit_expand_dev(ctx.raw(), 3, Ln, W, ctx.lookup_bits(), in.data(), d_steps, cts.size() - 1, 0, d_modulus, d_advice,
+                                 d_lookup, 0, 0);
 }
 
 }  // namespace pz

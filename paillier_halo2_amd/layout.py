@@ -174,10 +174,42 @@ class CircuitCells:
     seg: dict   # name -> (advice offset, lookup offset), in emission order
 
 
-def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_steps_g: int = 0, n_steps_r: int = 0) -> CircuitCells:
+TALLY_MAX = 65536     # ciphertexts of one tally (pz.h pz_paillier_tally)
+
+
+def tally_tree(count: int):
+    """The product tree of a tally: level by level the neighbours of the current list are multiplied, an odd
+    last element is carried up without a product.  -> [(a, b)] per mul_mod block in level-major order; an operand >= 0 is the
+    block that produced it, -(1 + i) the ciphertext c_(i+1)."""
+    if not 2 <= count <= TALLY_MAX:
+        raise ValueError(f"a tally takes 2 .. {TALLY_MAX} ciphertexts, not {count}")
+    cur = [-(1 + i) for i in range(count)]
+    blocks = []
+    while len(cur) > 1:
+        nxt = []
+        for j in range(len(cur) // 2):
+            nxt.append(len(blocks))
+            blocks.append((cur[2 * j], cur[2 * j + 1]))
+        if len(cur) & 1:
+            nxt.append(cur[-1])
+        cur = nxt
+    return blocks
+
+
+def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_steps_g: int = 0, n_steps_r: int = 0,
+                  count: int | None = None) -> CircuitCells:
     """The whole cell stream of paillier_enc_test (bench.rs:33-75, kind 'encrypt') or paillier_enc_add_test
-    (bench.rs:77-117, kind 'add'), operation by operation in call order -- what pz_circuit_expand_dev writes."""
+    (bench.rs:77-117, kind 'add'), operation by operation in call order -- what pz_circuit_expand_dev writes.
+    kind 'tally' (count = B ciphertexts): assign n, assign c_1 .. c_B at full width, square + refresh once, the B - 1 blocks of
+    tally_tree, assign res, assert_equal_fresh -- no load_zero, no g, no pow_mod constants."""
     Ln, L = limbs_n, 2 * limbs_n
+    if kind == "tally":
+        if count is None or not 2 <= count <= TALLY_MAX:
+            raise ValueError(f"a tally takes count = 2 .. {TALLY_MAX} ciphertexts, not {count}")
+        if n_steps_g not in (0, count - 1) or n_steps_r:
+            raise ValueError("a tally of count ciphertexts has count - 1 steps")
+    elif count is not None:
+        raise ValueError("count belongs to kind 'tally'")
     mm = mul_mod_cells(L, limb_bits, lookup_bits)
     seg, a, l = {}, 0, 0
 
@@ -187,11 +219,19 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         a += da
         l += dl
 
-    for name in ("assign_n", "assign_g", "assign_x", "assign_y"):
-        put(name, *assign_cells(Ln, limb_bits, lookup_bits))
+    if kind == "tally":
+        put("assign_n", *assign_cells(Ln, limb_bits, lookup_bits))
+        ca, cl = assign_cells(L, limb_bits, lookup_bits)
+        put("assign_cts", count * ca, count * cl)
+    else:
+        for name in ("assign_n", "assign_g", "assign_x", "assign_y"):
+            put(name, *assign_cells(Ln, limb_bits, lookup_bits))
     put("square", square_cells(Ln))
     put("refresh", *refresh_cells(refresh_aux(limb_bits, Ln, Ln), limb_bits, lookup_bits))
-    put("load_zero", 1)
+    if kind == "tally":
+        put("tree", (count - 1) * mm.advice, (count - 1) * mm.lookup)
+    else:
+        put("load_zero", 1)
     if kind == "encrypt":
         put("pow_g", 2 + n_steps_g * mm.advice, n_steps_g * mm.lookup)
         put("pow_r", 2 + n_steps_r * mm.advice, n_steps_r * mm.lookup)
@@ -202,7 +242,8 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         assert n_steps_g in (0, 2 * m_bits)
         put("pow_g", 2 + Ln * (7 * limb_bits - 2) + m_bits * (2 * mm.advice + 8 * L), 2 * m_bits * mm.lookup)
         put("pow_r", 2 + n_steps_r * mm.advice, n_steps_r * mm.lookup)
-    put("final", mm.advice, mm.lookup)
+    if kind != "tally":
+        put("final", mm.advice, mm.lookup)
     put("assign_res", *assign_cells(L, limb_bits, lookup_bits))
     put("assert_equal", assert_equal_cells(L))
     seg["end"] = (a, l)

@@ -180,21 +180,29 @@ def create_proof(key: NativeKey, d_cols: int, tr, seed: int = 0, blinding: Optio
 class NativeStructure:
     """pz_structure: the circuit structure of the reference's drivers generated by the library on the device (csrc/pz_structure.hip,
     include/pz.h pz_circuit_structure_dev) -- the compiled counterpart of circuit_structure.stream_structure + columns.
-    kind: "encrypt" | "add" | "encrypt_uniform"; exp_g / exp_r: the message m and the modulus n (integers; only their bits are used)."""
+    kind: "encrypt" | "add" | "encrypt_uniform"; exp_g / exp_r: the message m and the modulus n (integers; only their bits are used).
+    kind "tally" (pz_circuit_structure_tally_dev): count = the number of ciphertexts; no exponents -- one structure serves every tally of
+    that size."""
 
-    KINDS = {"encrypt": 0, "add": 1, "encrypt_uniform": 2}
+    KINDS = {"encrypt": 0, "add": 1, "encrypt_uniform": 2, "tally": 3}
 
     def __init__(self, eng: Engine, kind: str, enc_bits: int, limb_bits: int, lookup_bits: int, k: int, exp_g: int = 0, exp_r: int = 0,
-                 minimum_rows: int = 20, blinding_factors: int = 6, expose: bool = False):
-        """expose: add the instance column (pz_structure_expose): n, g and the ciphertext(s) become the statement; the maps then have
-        m = n_adv + n_lk + 2 columns"""
+                 minimum_rows: int = 20, blinding_factors: int = 6, expose: bool = False, count: Optional[int] = None):
+        """expose: add the instance column (pz_structure_expose): n, g and the ciphertext(s) become the statement (tally: n, the c_i and
+        their product); the maps then have m = n_adv + n_lk + 2 columns"""
+        if (kind == "tally") != (count is not None):
+            raise ValueError("count belongs to kind 'tally', which needs it")
         self.eng, self.k, self.lookup_bits, self.blinding_factors, self.minimum_rows = eng, k, lookup_bits, blinding_factors, minimum_rows
         Ln = enc_bits // limb_bits
         ew = -(-Ln * limb_bits // 64)
         wg, wr = self._words(exp_g, ew), self._words(exp_r, ew)
         h = VP()
-        eng._chk(eng.L.pz_circuit_structure_dev(eng.ctx, self.KINDS[kind], Ln, limb_bits, lookup_bits, k, _p(wg), _p(wr), minimum_rows,
-                                                blinding_factors, C.byref(h)), "pz_circuit_structure_dev")
+        if kind == "tally":
+            eng._chk(eng.L.pz_circuit_structure_tally_dev(eng.ctx, Ln, limb_bits, lookup_bits, k, int(count), minimum_rows, blinding_factors,
+                                                          C.byref(h)), "pz_circuit_structure_tally_dev")
+        else:
+            eng._chk(eng.L.pz_circuit_structure_dev(eng.ctx, self.KINDS[kind], Ln, limb_bits, lookup_bits, k, _p(wg), _p(wr), minimum_rows,
+                                                    blinding_factors, C.byref(h)), "pz_circuit_structure_dev")
         self.handle = h
         out = [C.c_size_t() for _ in range(9)]
         eng._chk(eng.L.pz_structure_info(h, *[C.byref(x) for x in out]), "pz_structure_info")

@@ -177,10 +177,13 @@ def record_seed(prefix: str) -> bytes:
     return int(prefix[1:-1]).to_bytes(8, "little")
 
 
-def public_inputs(kind: str, n: int, g: int, c: int, c1: Optional[int] = None, c2: Optional[int] = None, *, enc_bits: int, limb_bits: int) -> List[int]:
+def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int] = None, c2: Optional[int] = None, *, enc_bits: int, limb_bits: int,
+                  cts: Optional[Sequence[int]] = None) -> List[int]:
     """the statement of a circuit with the instance column, in the column's row order: little-endian limbs of limb_bits,
     n | g | c (kind "encrypt" / "encrypt_uniform": c = g^m r^n mod n^2) or n | g | c1 | c2 | c ("add": c = c1 c2 mod n^2); n, g, c1, c2 have
-    enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)"""
+    enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)
+    kind "tally": n | c_1 | .. | c_B | c with cts = [c_1 .. c_B] at full width (twice n's limbs each) and c their product mod n^2; g plays
+    no part in an addition and is ignored."""
     Ln = enc_bits // limb_bits
     mask = (1 << limb_bits) - 1
     limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
@@ -190,8 +193,14 @@ def public_inputs(kind: str, n: int, g: int, c: int, c1: Optional[int] = None, c
         parts = [(n, Ln), (g, Ln), (c1, Ln), (c2, Ln), (c, 2 * Ln)]
     elif kind in ("encrypt", "encrypt_uniform"):
         parts = [(n, Ln), (g, Ln), (c, 2 * Ln)]
+    elif kind == "tally":
+        if cts is None or len(cts) < 2:
+            raise ValueError("the tally statement names its ciphertexts: cts = [c_1 .. c_B], B >= 2")
+        parts = [(n, Ln)] + [(ci, 2 * Ln) for ci in cts] + [(c, 2 * Ln)]
     else:
-        raise ValueError("kind must be encrypt, add or encrypt_uniform")
+        raise ValueError("kind must be encrypt, add, encrypt_uniform or tally")
+    if cts is not None and kind != "tally":
+        raise ValueError("cts belongs to kind 'tally'")
     for v, cnt in parts:
         if int(v) < 0 or int(v) >> (limb_bits * cnt):
             raise ValueError("a value does not fit its %d limbs" % cnt)
