@@ -296,6 +296,24 @@ int pz_paillier_tally(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_
 int pz_paillier_tally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts, uint64_t* d_steps_out,
                           size_t steps_cap, uint64_t* c_out);
 
+/* Weighted tally: C = c_1^w_1 * ... * c_count^w_count mod n^2 = Enc(sum w_i m_i), Paillier's scalar homomorphism folded into the tally.
+ * 1 <= count <= 65536, 1 <= w_bits <= 64 (else PZ_ERR_INVALID); weights = count 64-bit words (HOST), each below 2^w_bits (else
+ * PZ_ERR_MESSAGE_RANGE, checked before any launch); cts as pz_paillier_tally.
+ *   power_i = BigUintChip::pow_mod(c_i, w_i) over EXACTLY w_bits in-circuit bits, LSB first (the uniform schedule of
+ *   pz_paillier_encrypt_uniform's g^m): per bit the step (acc, sq) then the step (sq, sq), acc takes the product only where the bit is
+ *   set; acc starts at 1, sq at c_i.  The trailing square of every chain is kept: it is the dependency's pow_mod as it stands.
+ *   Then the product tree of pz_paillier_tally over power_1 .. power_count (count = 1: no tree, C = power_1).
+ * Records a|b|q|r: first the chains' 2 * count * w_bits, chain-major (chain i, bit j at 2 (i w_bits + j) and the next), then the
+ * tree's count - 1 in level-major order; c_out = the root.  One team per chain (one launch for all chains: no workgroup waits on
+ * another), one launch per tree level, all on the context's stream without host synchronisation in between; n^2 and its Barrett
+ * constants are formed once.  steps_out (steps_cap >= 2 count w_bits + count - 1 records, else PZ_ERR_CAPACITY) may be NULL: the value
+ * only.  A ciphertext >= n^2 is PZ_ERR_RANGE, n = 0 is PZ_ERR_ZERO_MODULUS.  Same host / device split and buffer conventions as
+ * pz_paillier_tally[_dev].  (PZ_ABI_VERSION stays 7: these are additions, nothing existing changes.) */
+int pz_paillier_wtally(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
+                       const uint64_t* weights, uint64_t* steps_out, size_t steps_cap, uint64_t* c_out);
+int pz_paillier_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
+                           const uint64_t* weights, uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out);
+
 /* ---------------------------------------------------------------------------------------------
  * K4 -- expansion of a step trace into advice-column cells (Fr Montgomery, 32 B each), i.e. the
  * values halo2-lib's Context would hold after BigUintChip emitted the constraints of every
@@ -326,7 +344,12 @@ int pz_witness_expand_dev(pz_ctx* ctx, uint32_t limbs, uint32_t limb_bits, uint3
  * kind = 3: the tally of B = n_steps_g + 1 ciphertexts (pz_paillier_tally), n_steps_r = 0 (anything else: PZ_ERR_INVALID):
  * assign_integer(n); assign_integer(c_i, 2*enc_bits) for i = 1..B; square + refresh of n, once; the B - 1 mul_mod blocks of the
  * product tree in record order; assign_integer(res, 2*enc_bits); assert_equal_fresh(root, res).  No load_zero, no g, no pow_mod
- * constants. */
+ * constants.
+ * kind = 4: the weighted tally (pz_paillier_wtally) of B = n_steps_r + 1 ciphertexts with W = n_steps_g / (2 B) bits per weight
+ * (n_steps_g must be a multiple of 2 B and W in 1 .. 64, else PZ_ERR_INVALID): assign_integer(n); assign_integer(c_i, 2*enc_bits) for
+ * i = 1..B; load_witness(w_i) for i = 1..B (B consecutive cells, no gate); square + refresh of n, once; per ciphertext
+ * assign_constant(1), load_zero, num_to_bits(w_i, W) (7 W - 2 cells, tied to the load_witness cell) and W blocks of mul_mod(acc, sq),
+ * limb-wise select, square_mod(sq); the B - 1 mul_mod blocks of the tree over the powers; assign_integer(res); assert_equal_fresh. */
 int pz_circuit_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g,
                      size_t n_steps_r, size_t* advice_cells, size_t* lookup_cells);
 /* inputs (HOST): n | g | x | y as ceil(limbs_n*limb_bits/64) 64-bit words each, then res as ceil(2*limbs_n*limb_bits/64)
@@ -336,7 +359,10 @@ int pz_circuit_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lo
  * ceil(2*limbs_n*limb_bits/64) words each.  pz_paillier_tally_dev writes fields of 2*ceil(limbs_n*limb_bits/64) words: the same where
  * 64 divides limbs_n*limb_bits (every 64-bit-limb shape), so its device buffer is passed as it stands; otherwise (264-bit n in 88-bit
  * limbs: 10 words against 9) the records are REPACKED to this width first, as host/paillier_chip.hpp's tally does.  The host inputs
- * of a large tally (B ciphertexts) are staged through pinned memory that grows to their size.  d_modulus: n^2 (device).  d_lookup may be NULL.
+ * of a large tally (B ciphertexts) are staged through pinned memory that grows to their size.  kind 4: inputs = n | c_1 .. c_B |
+ * w_1 .. w_B | res with ONE 64-bit word per weight (a weight >= 2^W: PZ_ERR_MESSAGE_RANGE); d_steps holds the 2 B W chain records, then
+ * the B - 1 tree records (pz_paillier_wtally_dev's order; repacked like kind 3's where the widths differ).  d_modulus: n^2 (device).
+ * d_lookup may be NULL.
  * rows / col_stride cut the streams into the circuit's columns: cell c goes to column c / rows, row c % rows, columns
  * col_stride elements apart (rows = 2^k - blinding rows, col_stride = 2^k: every column is then a 2^k-row Lagrange vector
  * the commitment, product and NTT entry points take as it stands; rows above `rows` are not written).  0, 0 = dense. */
@@ -822,6 +848,10 @@ int pz_shplonk_free(pz_ctx* ctx, pz_shplonk* state);
  * the remainder cells of the block that produced them or to the limb cells of assign_integer(c_i), by the product tree of
  * pz_paillier_tally.  An ordinary pz_structure (n_steps_g = count - 1, n_steps_r = 0): pz_structure_expose, pz_pk_create[_pub]_dev,
  * pz_vk_keygen[_pub]_dev and the pz_proof_* stepper take it as it is.
+ * pz_circuit_structure_wtally_dev: the structure of the weighted tally (kind 4) of `count` ciphertexts (1 .. 65536) and w_bits (1 .. 64)
+ * bits per weight: its shape is count, w_bits and the key size alone -- ONE key serves every weight vector and every set of ciphertexts.
+ * The weight's load_witness cell is tied to its chain's num_to_bits accumulator, a chain's first sq to assign_integer(c_i)'s limbs, the
+ * tree's leaves to the chains' last select outputs.  An ordinary pz_structure (n_steps_g = 2 count w_bits, n_steps_r = count - 1).
  * ------------------------------------------------------------------------------------------- */
 typedef struct pz_structure pz_structure;
 int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
@@ -829,6 +859,8 @@ int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t l
                              pz_structure** out);
 int pz_circuit_structure_tally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                    size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
+int pz_circuit_structure_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                    uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_structure_info(const pz_structure* st, size_t* n_adv, size_t* n_adv_filled, size_t* n_lk, size_t* max_rows, size_t* n_constants,
                       size_t* n_cells, size_t* n_lookups, size_t* n_steps_g, size_t* n_steps_r);
 int pz_structure_arrays(const pz_structure* st, const uint8_t** d_selectors, const uint32_t** d_map_col, const uint32_t** d_map_row,
@@ -875,7 +907,8 @@ int pz_proof_free(pz_proof* proof);
  *     before the first advice commitment; with no instance column nothing is absorbed and every existing transcript is unchanged.
  *   - exposed values: little-endian limbs of limb_bits, n[limbs_n] | g[limbs_n] | c[2 limbs_n] for kind 0 and 2,
  *     n | g | c1[limbs_n] | c2[limbs_n] | c[2 limbs_n] for kind 1 (add); m and r stay private.  Kind 3 (tally of B = n_steps_g + 1):
- *     n[limbs_n] | c_1[2 limbs_n] | .. | c_B[2 limbs_n] | C[2 limbs_n].  (Kind 0 bakes the message's bits into the
+ *     n[limbs_n] | c_1[2 limbs_n] | .. | c_B[2 limbs_n] | C[2 limbs_n].  Kind 4 (weighted tally of B = n_steps_r + 1): n | c_1 | .. | c_B |
+ *     w_1 | .. | w_B | C, a weight being ONE value (its load_witness cell), n_public = limbs_n + (B + 1) 2 limbs_n + B.  (Kind 0 bakes the message's bits into the
  *     key's shape -- the reference's property; kind 2, the uniform-shape circuit, is the zero-knowledge statement.)
  * pz_circuit_public_cells  host only: the stream indices of the exposed advice cells in that order (arguments as pz_circuit_cells).
  *                cells_out may be NULL (count only); PZ_ERR_CAPACITY if capacity < *n_public.

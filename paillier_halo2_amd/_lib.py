@@ -69,6 +69,8 @@ SIGNATURES = {
     "pz_paillier_encrypt_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP]),
     "pz_paillier_tally": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_tally_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, C.c_size_t, VP]),
+    "pz_paillier_wtally": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, C.c_size_t, VP]),
+    "pz_paillier_wtally_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_encrypt_uniform": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP]),
     "pz_paillier_encrypt_uniform_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP]),
     "pz_witness_cells_per_step": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t),
@@ -165,6 +167,8 @@ SIGNATURES = {
     # patch point D as entry points: keygen + create_proof, one call per transcript round
     "pz_circuit_structure_dev": (C.c_int, [VP, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, VP, VP, C.c_size_t, C.c_uint32, C.POINTER(VP)]),
     "pz_circuit_structure_tally_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(VP)]),
+    "pz_circuit_structure_wtally_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32,
+                                                 C.POINTER(VP)]),
     "pz_structure_info": (C.c_int, [VP] + [C.POINTER(C.c_size_t)] * 9),
     "pz_structure_arrays": (C.c_int, [VP] + [C.POINTER(VP)] * 6),
     "pz_structure_free": (C.c_int, [VP]),

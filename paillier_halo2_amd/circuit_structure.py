@@ -300,8 +300,8 @@ class StructureArrays:
     n_steps_g: int
     n_steps_r: int
     # stream indices of the cells a circuit with the instance column exposes, in the column's row order: the limb cells of
-    # n | g | c (encrypt, encrypt_uniform), n | g | c1 | c2 | c (add) or n | c_1 | .. | c_B | C (tally) -- pz_circuit_public_cells gives
-    # the same list
+    # n | g | c (encrypt, encrypt_uniform), n | g | c1 | c2 | c (add), n | c_1 | .. | c_B | C (tally) or n | c_1 | .. | c_B | w_1 | .. |
+    # w_B | C (wtally: a weight is ONE cell) -- pz_circuit_public_cells gives the same list
     public_cells: Optional[np.ndarray] = None
 
 
@@ -310,12 +310,14 @@ def _exp_bits(e: int) -> List[int]:
 
 
 def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: int = 0, exp_r: int = 0, device: Optional[str] = None,
-                     count: Optional[int] = None) -> StructureArrays:
+                     count: Optional[int] = None, w_bits: Optional[int] = None) -> StructureArrays:
     """kind 'encrypt': exp_g = the message m, exp_r = the modulus n -- only their BITS are used, as in the reference's circuit
     (pow_mod_fixed_exp, paillier.rs:50-55); kind 'add': no exponents; kind 'encrypt_uniform' (the uniform-shape circuit, SURVEY 8f rank
     4): exp_g is ignored -- the message's bits are witness cells, ONE structure serves every message of a key; kind 'tally': count = B
     full-width ciphertexts multiplied in layout.tally_tree's order, no exponents -- the shape is B and the key
-    size alone.
+    size alone; kind 'wtally': count = B full-width ciphertexts, each raised to a w_bits-bit weight held in ONE witness cell (pow_mod
+    over in-circuit bits, the uniform circuit's block), the powers multiplied in layout.wtally_tree's order
+    -- the shape is B, w_bits and the key size alone.
     device: None -> numpy arrays; a torch device ("cuda") -> the template is tiled THERE and `src` / `lookup_src` are tensors on it (at
     config c2 the tiled arrays are 3.2 GB: 0.9 s of host numpy against a few ms; `columns` takes either)."""
     dev = None
@@ -350,18 +352,25 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             constants.append(v)
         return const_id[v]
 
-    if kind not in ("encrypt", "encrypt_uniform", "add", "tally"):
+    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally"):
         raise ValueError(f"unknown circuit kind {kind!r}")
-    if (kind == "tally") != (count is not None):
-        raise ValueError("count belongs to kind 'tally', which needs it")
+    if (kind in ("tally", "wtally")) != (count is not None):
+        raise ValueError("count belongs to kinds 'tally' and 'wtally', which need it")
+    if (kind == "wtally") != (w_bits is not None):
+        raise ValueError("w_bits belongs to kind 'wtally', which needs it")
+    if kind == "wtally" and not 1 <= w_bits <= layout.WTALLY_MAX_BITS:
+        raise ValueError(f"a weight has w_bits = 1 .. {layout.WTALLY_MAX_BITS} bits, not {w_bits}")
     tree = layout.tally_tree(count) if kind == "tally" else None      # (refuses a count outside 2 .. TALLY_MAX)
+    if kind == "wtally":
+        tree = layout.wtally_tree(count)                              # (1 .. TALLY_MAX; one ciphertext has no tree)
     # ---- prefix: the four assign_integer (tally: n, then the B ciphertexts at full width), square, refresh, load_zero (not in a
     # tally: nothing is extended there); global indices from 0
     w = _Walk()
     n_c = _assign(w, Ln, limb_bits, lb)
-    if kind == "tally":
+    if kind in ("tally", "wtally"):
         ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
         g_c = x_c = y_c = []
+        wt_c = [w.put() for _ in range(count)] if kind == "wtally" else []     # load_witness(w_i): one cell each, no gate
     else:
         g_c = _assign(w, Ln, limb_bits, lb)
         x_c = _assign(w, Ln, limb_bits, lb)
@@ -386,7 +395,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     for c in cur:
         holder = _range_check(w, c, limb_bits, lb)
         fresh.append(c if c is not None else holder)
-    zero = w.putc(0) if kind != "tally" else None
+    zero = w.putc(0) if kind not in ("tally", "wtally") else None
     ext_l = lambda limbs: list(limbs) + [zero] * (L - len(limbs))
     parts_src: List[np.ndarray] = []
     parts_mask: List[np.ndarray] = []
@@ -431,8 +440,75 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         parts_lk.append(tile(bases, tm.lk))
         return off + ns * tm.cells, bases[:, None] + tm.r_cells[None, :]      # r cells of every block
 
+    def bit_chain(off: int, ut: _Template, ut_const: np.ndarray, ut_mask: np.ndarray, word_cell: int, nbits: int, acc_cells: np.ndarray,
+                  sq_cells: np.ndarray):
+        """num_to_bits(word_cell, nbits), then nbits blocks of the uniform template chained through acc (select outputs) and sq (square
+        remainders) -> (off, the last acc cells, the last sq cells)"""
+        wb = _Walk(off)
+        bit_cells = [wb.put()]
+        if nbits > 1:
+            wb.gate(bit_cells[0])
+        acc_cell = bit_cells[0]
+        for i in range(1, nbits):
+            bit_cells.append(wb.put())
+            wb.putc(1 << i)
+            acc_cell = wb.put()
+            if i < nbits - 1:
+                wb.gate(acc_cell)
+        wb.pair(word_cell, acc_cell)        # (nbits = 1: the accumulator IS the bit)
+        for bc in bit_cells:
+            g_ = wb.putc(0)
+            wb.gate(g_)
+            wb.put(bc); wb.put(bc); wb.put(bc)
+        off = flush(wb)
+        bases = off + ut.cells * np.arange(nbits, dtype=np.int64)
+        new_acc = bases[:, None] + ut.r_cells[None, :L]
+        new_sq = bases[:, None] + ut.r_cells[None, L:]
+        a_cells = np.concatenate([acc_cells[None, :], new_acc[:-1]])
+        b_cells = np.concatenate([sq_cells[None, :], new_sq[:-1]])
+        assigns = []
+        for kind_, cells_ in (("a", a_cells), ("b", b_cells)):
+            pos, j = ut.ext[kind_]
+            assigns.append((pos, cells_[:, j]))
+        pos, j = ut.ext["n"]
+        assigns.append((pos, fresh_arr[j]))
+        pos, _ = ut.ext["s"]
+        assigns.append((pos, np.repeat(np.asarray(bit_cells, dtype=np.int64)[:, None], len(pos), axis=1)))
+        assigns.append((ut.const_pos, -(1 + ut_const)))
+        parts_src.append(tile(bases, ut.self_or_local, assigns))
+        parts_mask.append(np.tile(ut_mask, nbits))
+        parts_lk.append(tile(bases, ut.lk))
+        return off + nbits * ut.cells, new_acc[-1], new_sq[-1]
+
     n_steps = [0, 0]
-    if kind in ("encrypt", "encrypt_uniform"):
+    if kind == "wtally":
+        # per ciphertext pow_mod(c_i, w_i) over w_bits in-circuit bits: [1, 0], num_to_bits of the weight's cell, the bit blocks; the
+        # chain starts from its OWN [one, zero ..] and from assign_integer(c_i)'s limb cells.  Its power is the last select's outputs.
+        ut = _uniform_template(L, limb_bits, lb)
+        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
+        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
+        ut_mask[ut.gates] = 1
+        powers = []
+        for i in range(count):
+            wc = _Walk(off)
+            one = wc.putc(1)
+            z2 = wc.putc(0)
+            off = flush(wc)
+            off, acc, _ = bit_chain(off, ut, ut_const, ut_mask, wt_c[i], w_bits, np.asarray([one] + [z2] * (L - 1), dtype=np.int64),
+                                    np.asarray(ct_c[i], dtype=np.int64))
+            powers.append(acc)
+        n_steps[0] = 2 * count * w_bits
+        nb = len(tree)
+        if nb:
+            r_of = off + tm.cells * np.arange(nb, dtype=np.int64)[:, None] + tm.r_cells[None, :]
+            table = np.concatenate([r_of, np.asarray(powers[::-1], dtype=np.int64)])     # index -(1 + i) -> the power of c_(i+1)
+            tr = np.asarray(tree, dtype=np.int64)
+            off, rfin = blocks(off, table[tr[:, 0]], table[tr[:, 1]])
+            rfin = rfin[-1:]
+        else:
+            rfin = powers[0][None, :]
+        n_steps[1] = nb
+    elif kind in ("encrypt", "encrypt_uniform"):
         results = []
         chains = [(ext_l(g_c), exp_g), (ext_l(y_c), exp_r)]
         if kind == "encrypt_uniform":
@@ -450,42 +526,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
             sq_cells = np.asarray(ext_l(g_c), dtype=np.int64)
             for li in range(Ln):
-                wb = _Walk(off)
-                bit_cells = [wb.put()]
-                wb.gate(bit_cells[0])
-                acc_cell = bit_cells[0]
-                for i in range(1, W_):
-                    bit_cells.append(wb.put())
-                    wb.putc(1 << i)
-                    acc_cell = wb.put()
-                    if i < W_ - 1:
-                        wb.gate(acc_cell)
-                wb.pair(x_c[li], acc_cell)
-                for bc in bit_cells:
-                    g_ = wb.putc(0)
-                    wb.gate(g_)
-                    wb.put(bc); wb.put(bc); wb.put(bc)
-                off = flush(wb)
-                # the limb's W_ bits: blocks chained through acc (select outputs) and sq (square remainders)
-                bases = off + ut.cells * np.arange(W_, dtype=np.int64)
-                new_acc = bases[:, None] + ut.r_cells[None, :L]
-                new_sq = bases[:, None] + ut.r_cells[None, L:]
-                a_cells = np.concatenate([acc_cells[None, :], new_acc[:-1]])
-                b_cells = np.concatenate([sq_cells[None, :], new_sq[:-1]])
-                assigns = []
-                for kind_, cells_ in (("a", a_cells), ("b", b_cells)):
-                    pos, j = ut.ext[kind_]
-                    assigns.append((pos, cells_[:, j]))
-                pos, j = ut.ext["n"]
-                assigns.append((pos, fresh_arr[j]))
-                pos, _ = ut.ext["s"]
-                assigns.append((pos, np.repeat(np.asarray(bit_cells, dtype=np.int64)[:, None], len(pos), axis=1)))
-                assigns.append((ut.const_pos, -(1 + ut_const)))
-                parts_src.append(tile(bases, ut.self_or_local, assigns))
-                parts_mask.append(np.tile(ut_mask, W_))
-                parts_lk.append(tile(bases, ut.lk))
-                off += W_ * ut.cells
-                acc_cells, sq_cells = new_acc[-1], new_sq[-1]
+                off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, x_c[li], W_, acc_cells, sq_cells)
             n_steps[0] = 2 * Ln * W_
             results.append(acc_cells)
             chains = [None, chains[1]]
@@ -551,8 +592,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         cat = lambda parts: torch.cat([p_ if isinstance(p_, torch.Tensor) else torch.as_tensor(p_, dtype=torch.int64).to(dev) for p_ in parts])
         src, lookup_src = cat(parts_src), cat(parts_lk)
     src[eq_cell] = -(1 + cid(1))          # assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
-    if kind == "tally":
-        exposed = list(n_c) + [c for ct in ct_c for c in ct] + list(res_c)
+    if kind in ("tally", "wtally"):
+        exposed = list(n_c) + [c for ct in ct_c for c in ct] + list(wt_c) + list(res_c)
     else:
         exposed = list(n_c) + list(g_c) + (list(x_c) + list(y_c) if kind == "add" else []) + list(res_c)
     return StructureArrays(n_cells=off, src=src, gate_mask=np.concatenate(parts_mask), lookup_src=lookup_src,

@@ -970,6 +970,72 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_tally_level(c
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
+// ---- the chains of a weighted tally (pz_paillier_wtally): power_i = c_i^w_i mod n^2 by BigUintChip::pow_mod's uniform schedule over
+// exactly w_bits bits, LSB first: (acc, sq) then (sq, sq) for EVERY bit, acc takes the product only where the bit is set.  One team
+// per chain runs both steps of every bit itself: no ticket, no hand-off, no workgroup waits on another (k_pow_mod_chain's two
+// workgroups per chain buy latency when chains are few; here they are many and short).  The Barrett constants come from
+// k_tally_setup, computed once for all chains.  recs (may be null: the value only): chain i, bit j at records 2 (i w_bits + j) and
+// the next; powers: L limbs per chain, the level-0 list of the product tree.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_wtally_pow(const u64* __restrict__ mod, const u64* __restrict__ cts,
+                                                                                 const u64* __restrict__ weights, unsigned w_bits,
+                                                                                 u64* __restrict__ recs, u64* __restrict__ powers, unsigned L,
+                                                                                 u32* __restrict__ status) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (mod[3 * C + 1] == 0) return;   // zero modulus (the same word for every workgroup)
+    const unsigned wave = threadIdx.x >> 6;
+    TeamCtx<E> T;
+    T.buf = s_team;
+    T.w = wave;
+    T.parity = 0;
+    TeamMul<E> tmul{&T};
+    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
+        u64* z = (u64*)s_team;
+        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
+        __syncthreads();
+    }
+    BarrettCtx<E> B;
+    B.sm = s_scratch[wave];
+    B.limbs = L;
+    B.s = (unsigned)mod[3 * C];
+    B.M = ld_load<E>(mod, C);
+    B.mu = ld_load<E>(mod + C, C);
+    const LD<E> n2 = ld_load<E>(mod + 2 * C, C);
+    const size_t chain = blockIdx.x;
+    const u64 w = weights[chain];
+    LD<E> sq = ld_load<E>(cts + chain * L, L);
+    LD<E> acc = ld_small<E>(1);
+    unsigned st = ST_OK;
+    {
+        LD<E> d;
+        if (!ld_sub(d, sq, n2)) st |= ST_RANGE;   // a ciphertext >= n^2
+    }
+    const bool writer = wave == 0 && recs != nullptr;   // the four waves of the team hold the same values: one of them writes
+    for (unsigned j = 0; j < w_bits; ++j) {
+        u64* o = writer ? recs + (chain * w_bits + j) * 8 * (size_t)L : nullptr;   // this bit's two records
+        LD<E> q, r;
+        st |= mul_mod(B, q, r, acc, sq, tmul);
+        if (writer) {
+            ld_store(o, acc, L);
+            ld_store(o + L, sq, L);
+            ld_store(o + 2 * L, q, L);
+            ld_store(o + 3 * L, r, L);
+        }
+        if ((w >> j) & 1) acc = r;   // select(bit, muled, acc)
+        st |= mul_mod(B, q, r, sq, sq, tmul);
+        if (writer) {
+            ld_store(o + 4 * L, sq, L);
+            ld_store(o + 5 * L, sq, L);
+            ld_store(o + 6 * L, q, L);
+            ld_store(o + 7 * L, r, L);
+        }
+        sq = r;
+    }
+    if (wave == 0) ld_store(powers + chain * L, acc, L);
+    if (st && lane_id() == 0) atomicOr(status, st);
+}
+
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
@@ -1324,6 +1390,35 @@ extern "C" int pz_paillier_encrypt_uniform_dev(pz_ctx* ctx, uint32_t limbs_n, si
 // PaillierChip::add folded over `count` ciphertexts (paillier.rs:62-85, one mul_mod each) as a product tree: level 0 multiplies
 // (c_1, c_2), (c_3, c_4), ...; an odd last element is carried up without a product; records are numbered level-major.
 #define K3_TALLY_MAX 65536
+// the product tree over `count` elements of L limbs at `elems` (stride L): one k_tally_level launch per level on the context's stream,
+// the count - 1 records written to d_steps in level-major order.  *root = the last level's remainder (count = 1: the element itself).
+static int tally_levels(pz_ctx* ctx, unsigned C, const u64* d_mod, const u64* elems, size_t count, unsigned L, u64* d_steps, u32* d_status,
+                        const u64** root) {
+    const size_t rec = 4 * (size_t)L;
+    // the level's list: n_regular strided elements, then (len > n_regular) the carried one
+    const u64* tail = nullptr;
+    size_t len = count, stride = L, n_regular = count, rec_off = 0;
+    while (len > 1) {
+        const size_t blocks = len / 2;
+        u64* out = d_steps + rec_off * rec;
+        if (C == 64)
+            hipLaunchKernelGGL(k_tally_level<1>, dim3((unsigned)blocks), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, elems, stride,
+                               (unsigned)n_regular, tail, out, L, d_status);
+        else
+            hipLaunchKernelGGL(k_tally_level<2>, dim3((unsigned)blocks), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, elems, stride,
+                               (unsigned)n_regular, tail, out, L, d_status);
+        HIPCHK(ctx, hipGetLastError());
+        const u64* last = n_regular == len ? elems + (len - 1) * stride : tail;
+        tail = (len & 1) ? last : nullptr;
+        elems = out + 3 * (size_t)L;
+        stride = rec;
+        n_regular = blocks;
+        len = blocks + (len & 1);
+        rec_off += blocks;
+    }
+    *root = elems;   // the last level is one product of two elements: its remainder
+    return PZ_OK;
+}
 static int tally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, const uint64_t* n, const uint64_t* cts, uint64_t* steps_out,
                       int steps_on_device, size_t steps_cap, uint64_t* c_out) {
     if (!ctx || !n || !cts || !c_out || Ln == 0) return PZ_ERR_INVALID;
@@ -1357,28 +1452,7 @@ static int tally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, const uint64_t* n,
         if (C == 64) hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
         else hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
         HIPCHK(ctx, hipGetLastError());
-        // the level's list: n_regular strided elements, then (len > n_regular) the carried one
-        const u64 *elems = d_cts, *tail = nullptr;
-        size_t len = count, stride = L, n_regular = count, rec_off = 0;
-        while (len > 1) {
-            const size_t blocks = len / 2;
-            u64* out = d_steps + rec_off * rec;
-            if (C == 64)
-                hipLaunchKernelGGL(k_tally_level<1>, dim3((unsigned)blocks), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, elems, stride,
-                                   (unsigned)n_regular, tail, out, L, d_status);
-            else
-                hipLaunchKernelGGL(k_tally_level<2>, dim3((unsigned)blocks), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, elems, stride,
-                                   (unsigned)n_regular, tail, out, L, d_status);
-            HIPCHK(ctx, hipGetLastError());
-            const u64* last = n_regular == len ? elems + (len - 1) * stride : tail;
-            tail = (len & 1) ? last : nullptr;
-            elems = out + 3 * (size_t)L;
-            stride = rec;
-            n_regular = blocks;
-            len = blocks + (len & 1);
-            rec_off += blocks;
-        }
-        root = elems;   // the last level is one product of two elements: its remainder
+        PZCHK(tally_levels(ctx, C, d_mod, d_cts, count, L, d_steps, d_status, &root));
     }
     u32 st = 0;
     HIPCHK(ctx, hipMemcpyAsync(c_out, root, lb, hipMemcpyDeviceToHost, ctx->stream));
@@ -1395,4 +1469,81 @@ extern "C" int pz_paillier_tally(pz_ctx* ctx, uint32_t limbs_n, size_t count, co
 extern "C" int pz_paillier_tally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts,
                                      uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out) {
     return tally_impl(ctx, limbs_n, count, n, cts, d_steps_out, 1, steps_cap, c_out);
+}
+
+// The weighted tally: C = prod c_i^w_i mod n^2 -- per ciphertext BigUintChip::pow_mod over w_bits in-circuit bits (k_wtally_pow, one
+// team per chain), then the tally's product tree over the powers.  Records: the chains' 2 * count * w_bits chain-major, then the tree's
+// count - 1.  Every launch goes on the context's stream; the host synchronises once, at the end.
+static int wtally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
+                       const uint64_t* weights, uint64_t* steps_out, int steps_on_device, size_t steps_cap, uint64_t* c_out) {
+    if (!ctx || !n || !cts || !weights || !c_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_TALLY_MAX || w_bits < 1 || w_bits > 64) return PZ_ERR_INVALID;
+    const unsigned L = 2 * Ln;
+    if (L > 128) return PZ_ERR_UNSUPPORTED;
+    const size_t n_chain = 2 * count * w_bits, n_tree = count - 1;
+    if (steps_out && steps_cap < n_chain + n_tree) return PZ_ERR_CAPACITY;
+    if (w_bits < 64)   // before any launch: the circuit's num_to_bits of such a weight cannot hold
+        for (size_t i = 0; i < count; ++i)
+            if (weights[i] >> w_bits) return PZ_ERR_MESSAGE_RANGE;
+    PZ_ENTER(ctx);
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, rec = 4 * (size_t)L;
+    const unsigned C = L <= 64 ? 64 : 128;
+    // n | c_1 .. c_count | w_1 .. w_count | the powers | Barrett constants | status
+    const size_t in_bytes = (nb + count * lb + count * 8 + 255) & ~(size_t)255, pow_bytes = (count * lb + 255) & ~(size_t)255;
+    const size_t mod_bytes = ((size_t)3 * C + 2) * 8;
+    void* d;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, in_bytes + pow_bytes + mod_bytes + 256, &d));
+    char* p = (char*)d;
+    u64* d_n = (u64*)p;
+    u64* d_cts = (u64*)(p + nb);
+    u64* d_w = (u64*)(p + nb + count * lb);
+    u64* d_pow = (u64*)(p + in_bytes);
+    u64* d_mod = (u64*)(p + in_bytes + pow_bytes);
+    u32* d_status = (u32*)(p + in_bytes + pow_bytes + mod_bytes + 64);
+    u64* d_steps = steps_on_device ? steps_out : nullptr;
+    u64* d_tree = d_steps ? d_steps + n_chain * rec : nullptr;
+    if (!d_steps && (steps_out || n_tree)) {
+        // a host trace: all records live in a workspace; the value only: the tree's alone (its levels read each other's remainders
+        // there) -- the chains then write no records at all
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_B, ((steps_out ? n_chain : 0) + n_tree) * rec * 8 + 8, &t));
+        if (steps_out) {
+            d_steps = (u64*)t;
+            d_tree = d_steps + n_chain * rec;
+        } else d_tree = (u64*)t;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_n, n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_cts, cts, count * lb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_w, weights, count * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_status, 0, 4, ctx->stream));
+    const u64* root = nullptr;
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        if (C == 64) {
+            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
+            hipLaunchKernelGGL(k_wtally_pow<1>, dim3((unsigned)count), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, d_cts, d_w, w_bits, d_steps,
+                               d_pow, L, d_status);
+        } else {
+            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
+            hipLaunchKernelGGL(k_wtally_pow<2>, dim3((unsigned)count), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, d_cts, d_w, w_bits, d_steps,
+                               d_pow, L, d_status);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        PZCHK(tally_levels(ctx, C, d_mod, d_pow, count, L, d_tree, d_status, &root));
+    }
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(c_out, root, lb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&st, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (steps_out && !steps_on_device)
+        HIPCHK(ctx, hipMemcpyAsync(steps_out, d_steps, (n_chain + n_tree) * rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return status_to_rc(ctx, st);
+}
+extern "C" int pz_paillier_wtally(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
+                                  const uint64_t* weights, uint64_t* steps_out, size_t steps_cap, uint64_t* c_out) {
+    return wtally_impl(ctx, limbs_n, count, w_bits, n, cts, weights, steps_out, 0, steps_cap, c_out);
+}
+extern "C" int pz_paillier_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
+                                      const uint64_t* weights, uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out) {
+    return wtally_impl(ctx, limbs_n, count, w_bits, n, cts, weights, d_steps_out, 1, steps_cap, c_out);
 }

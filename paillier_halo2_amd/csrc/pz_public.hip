@@ -231,7 +231,7 @@ W4 w4_of(const uint64_t v[4]) { return W4{{v[0], v[1], v[2], v[3]}}; }
 // assert_equal_fresh, the last two operations of the stream.  Tally (kind 3, n_steps_g + 1 ciphertexts): n | c_1 | .. | c_B | C, the
 // ciphertexts' 2 limbs_n limb cells at the head of their assign_integer blocks, which follow n's.
 int public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g, size_t n_steps_r, std::vector<uint64_t>& cells) {
-    if (kind < 0 || kind > 3 || limbs_n == 0) return PZ_ERR_INVALID;
+    if (kind < 0 || kind > 4 || limbs_n == 0) return PZ_ERR_INVALID;
     size_t total = 0, a_in = 0, a_res = 0, a_eq = 0;
     PZCHK(pz_circuit_cells(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, &total, nullptr));
     PZCHK(pz_op_cells(0, limbs_n, limb_bits, lookup_bits, &a_in, nullptr));
@@ -240,10 +240,15 @@ int public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup
     if (total < 4 * a_in + a_res + a_eq) return PZ_ERR_INTERNAL;
     const size_t res = total - a_res - a_eq;
     cells.clear();
-    if (kind == 3) {
+    if (kind == 3 || kind == 4) {
+        // (kind 4, the weighted tally of n_steps_r + 1: ... | c_B | w_1 | .. | w_B | C, the weights' load_witness cells follow the
+        // ciphertexts' blocks, one cell each)
+        const size_t count = kind == 3 ? n_steps_g + 1 : n_steps_r + 1;
         for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(j);
-        for (size_t i = 0; i <= n_steps_g; ++i)
+        for (size_t i = 0; i < count; ++i)
             for (uint32_t j = 0; j < 2 * limbs_n; ++j) cells.push_back(a_in + i * a_res + j);
+        if (kind == 4)
+            for (size_t i = 0; i < count; ++i) cells.push_back(a_in + count * a_res + i);
         for (uint32_t j = 0; j < 2 * limbs_n; ++j) cells.push_back(res + j);
         return PZ_OK;
     }

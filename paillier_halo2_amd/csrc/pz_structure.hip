@@ -425,9 +425,13 @@ struct Stream {
 
 // kind 3 (the tally): `count` ciphertexts assigned at full width after n, no load_zero, the count - 1 blocks of
 // the product tree (level by level the neighbours of the current list, an odd last element carried up), res, assert_equal_fresh
-int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, Stream& S) {
+// kind 4 (the weighted tally): as kind 3 up to the refresh, with `count` load_witness cells (the weights) after
+// the ciphertexts; then per ciphertext pow_mod over w_bits in-circuit bits -- [1, 0], num_to_bits of the weight's cell, w_bits uniform
+// blocks from the chain's OWN one / zero and assign_integer(c_i)'s limbs --, the count - 1 tree blocks over the powers (the last
+// select's outputs of every chain), res, assert_equal_fresh.  Two parts per chain (its head, its blocks).
+int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, unsigned w_bits, Stream& S) {
     const unsigned L = 2 * Ln;
-    S.tmpls.reserve(2);                  // (references to the templates stay valid when the uniform circuit adds the second one)
+    S.tmpls.reserve(2);                  // (references to the templates stay valid when a circuit with in-circuit bits adds the second one)
     S.tmpls.push_back(block_template(L, W, lb));
     const Template& tm = S.tmpls[0];
     // ---- prefix: the four assign_integer (tally: n, then the ciphertexts), square, refresh, load_zero (not in a tally)
@@ -435,8 +439,11 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
     const std::vector<i64> n_c = assign(w, Ln, W, lb);
     std::vector<i64> g_c, x_c, y_c;
     std::vector<std::vector<i64>> ct_c;
-    if (kind == 3) {
+    std::vector<i64> wt_c;
+    if (kind == 3 || kind == 4) {
         for (size_t i = 0; i < count; ++i) ct_c.push_back(assign(w, L, W, lb));
+        if (kind == 4)
+            for (size_t i = 0; i < count; ++i) wt_c.push_back(w.put());   // load_witness(w_i): one cell, no gate
     } else {
         g_c = assign(w, Ln, W, lb); x_c = assign(w, Ln, W, lb); y_c = assign(w, Ln, W, lb);
     }
@@ -468,7 +475,7 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
         S.fresh.push_back(c != NONE ? c : holder);
     }
     if (S.fresh.size() != L) return PZ_ERR_UNSUPPORTED;   // the refreshed n^2 has l + r limbs for every shape of this circuit
-    const i64 zero = kind == 3 ? NONE : w.putc(c_small(0));
+    const i64 zero = kind >= 3 ? NONE : w.putc(c_small(0));
     auto ext_l = [&](const std::vector<i64>& limbs) {
         std::vector<i64> v(limbs);
         v.resize(L, zero);
@@ -478,8 +485,48 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
     S.bind_template_constants(0);
     auto r_of = [&](i64 boff, const Template& T, i64 blk, size_t which) { return boff + blk * (i64)T.cells + T.r_cells[which]; };
 
+    // num_to_bits(word_cell, nbits) at `off`, then nbits blocks of the uniform template (S.tmpls[1]) chained through acc (select outputs)
+    // and sq (square remainders); acc_cells / sq_cells: the chain's state, in and out
+    auto bit_chain = [&](i64 off_, Walk& wb, i64 word_cell, unsigned nbits, std::vector<i64>& acc_cells, std::vector<i64>& sq_cells) -> i64 {
+        const Template& ut = S.tmpls[1];
+        std::vector<i64> bit_cells{wb.put()};
+        if (nbits > 1) wb.gate(bit_cells[0]);
+        i64 acc_cell = bit_cells[0];
+        for (unsigned i = 1; i < nbits; ++i) {
+            bit_cells.push_back(wb.put());
+            wb.putc(c_pow2(i));
+            acc_cell = wb.put();
+            if (i < nbits - 1) wb.gate(acc_cell);
+        }
+        wb.pair(word_cell, acc_cell);   // (nbits = 1: the accumulator IS the bit)
+        for (i64 bc : bit_cells) {
+            const i64 g_ = wb.putc(c_small(0));
+            wb.gate(g_);
+            wb.put(bc); wb.put(bc); wb.put(bc);
+        }
+        off_ = S.flush(wb);
+        std::vector<i64> a((size_t)nbits * L), b((size_t)nbits * L), s_(nbits);
+        for (unsigned t = 0; t < nbits; ++t) {
+            for (unsigned j = 0; j < L; ++j) {
+                a[(size_t)t * L + j] = t == 0 ? acc_cells[j] : r_of(off_, ut, t - 1, j);
+                b[(size_t)t * L + j] = t == 0 ? sq_cells[j] : r_of(off_, ut, t - 1, L + j);
+            }
+            s_[t] = bit_cells[t];
+        }
+        for (unsigned j = 0; j < L; ++j) {
+            acc_cells[j] = r_of(off_, ut, nbits - 1, j);
+            sq_cells[j] = r_of(off_, ut, nbits - 1, L + j);
+        }
+        return S.blocks(off_, 1, std::move(a), std::move(b), std::move(s_), nbits);
+    };
+
     std::vector<i64> gm, rn;   // the cells holding g^m and r^n
-    i64 root_off = 0;          // the block whose remainder is the circuit's result
+    std::vector<i64> root_c;   // the cells holding the circuit's result
+    auto block_r = [&](i64 boff) {
+        std::vector<i64> v(L);
+        for (unsigned j = 0; j < L; ++j) v[j] = r_of(boff, tm, 0, j);
+        return v;
+    };
     if (kind == 0 || kind == 2) {
         struct Chain { std::vector<i64> base; const u64* e; };
         Chain chains[2] = {{ext_l(g_c), exp_g}, {ext_l(y_c), exp_r}};
@@ -489,7 +536,6 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             // (mul_mod, select, square_mod) block -- the same shape for every message
             S.tmpls.push_back(uniform_template(L, W, lb));
             S.bind_template_constants(1);
-            const Template& ut = S.tmpls[1];
             Walk wc(off);
             const i64 one = wc.putc(c_small(1)), z2 = wc.putc(c_small(0));
             off = S.flush(wc);
@@ -497,36 +543,7 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             acc_cells[0] = one;
             for (unsigned li = 0; li < Ln; ++li) {
                 Walk wb(off);
-                std::vector<i64> bit_cells{wb.put()};
-                wb.gate(bit_cells[0]);
-                i64 acc_cell = bit_cells[0];
-                for (unsigned i = 1; i < W; ++i) {
-                    bit_cells.push_back(wb.put());
-                    wb.putc(c_pow2(i));
-                    acc_cell = wb.put();
-                    if (i < W - 1) wb.gate(acc_cell);
-                }
-                wb.pair(x_c[li], acc_cell);
-                for (i64 bc : bit_cells) {
-                    const i64 g_ = wb.putc(c_small(0));
-                    wb.gate(g_);
-                    wb.put(bc); wb.put(bc); wb.put(bc);
-                }
-                off = S.flush(wb);
-                // the limb's W bits: blocks chained through acc (select outputs) and sq (square remainders)
-                std::vector<i64> a((size_t)W * L), b((size_t)W * L), s(W);
-                for (unsigned t = 0; t < W; ++t) {
-                    for (unsigned j = 0; j < L; ++j) {
-                        a[(size_t)t * L + j] = t == 0 ? acc_cells[j] : r_of(off, ut, t - 1, j);
-                        b[(size_t)t * L + j] = t == 0 ? sq_cells[j] : r_of(off, ut, t - 1, L + j);
-                    }
-                    s[t] = bit_cells[t];
-                }
-                for (unsigned j = 0; j < L; ++j) {
-                    acc_cells[j] = r_of(off, ut, W - 1, j);
-                    sq_cells[j] = r_of(off, ut, W - 1, L + j);
-                }
-                off = S.blocks(off, 1, std::move(a), std::move(b), std::move(s), W);
+                off = bit_chain(off, wb, x_c[li], W, acc_cells, sq_cells);
             }
             S.n_steps_g = 2 * (size_t)Ln * W;
             gm = acc_cells;
@@ -595,23 +612,61 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
         S.n_steps_g = (size_t)ns;
         const i64 tree_off = off;
         off = S.blocks(off, 0, std::move(a), std::move(b), {}, ns);
-        root_off = tree_off + (ns - 1) * (i64)tm.cells;     // the root is the last block
+        root_c = block_r(tree_off + (ns - 1) * (i64)tm.cells);     // the root is the last block
+    } else if (kind == 4) {
+        S.tmpls.push_back(uniform_template(L, W, lb));
+        S.bind_template_constants(1);
+        std::vector<std::vector<i64>> powers;
+        for (size_t i = 0; i < count; ++i) {
+            Walk wb(off);   // the chain's head: assign_constant(1), load_zero, then num_to_bits
+            const i64 one = wb.putc(c_small(1)), z2 = wb.putc(c_small(0));
+            std::vector<i64> acc_cells(L, z2), sq_cells = ct_c[i];
+            acc_cells[0] = one;
+            off = bit_chain(off, wb, wt_c[i], w_bits, acc_cells, sq_cells);
+            powers.push_back(acc_cells);
+        }
+        S.n_steps_g = 2 * count * w_bits;
+        // the tree over the powers: operands as (producing block | -(1 + chain)), level-major as in kind 3
+        std::vector<i64> cur(count), a_blk, b_blk;
+        for (size_t i = 0; i < count; ++i) cur[i] = -(1 + (i64)i);
+        while (cur.size() > 1) {
+            std::vector<i64> nxt;
+            for (size_t j = 0; j + 1 < cur.size(); j += 2) {
+                nxt.push_back((i64)a_blk.size());
+                a_blk.push_back(cur[j]); b_blk.push_back(cur[j + 1]);
+            }
+            if (cur.size() & 1) nxt.push_back(cur.back());
+            cur.swap(nxt);
+        }
+        const i64 ns = (i64)a_blk.size();
+        S.n_steps_r = (size_t)ns;
+        if (ns) {
+            auto operand = [&](i64 blk, unsigned j) -> i64 { return blk < 0 ? powers[(size_t)(-blk - 1)][j] : r_of(off, tm, blk, j); };
+            std::vector<i64> a((size_t)ns * L), b((size_t)ns * L);
+            for (i64 q = 0; q < ns; ++q)
+                for (unsigned j = 0; j < L; ++j) {
+                    a[(size_t)q * L + j] = operand(a_blk[(size_t)q], j);
+                    b[(size_t)q * L + j] = operand(b_blk[(size_t)q], j);
+                }
+            const i64 tree_off = off;
+            off = S.blocks(off, 0, std::move(a), std::move(b), {}, ns);
+            root_c = block_r(tree_off + (ns - 1) * (i64)tm.cells);
+        } else root_c = powers[0];   // one ciphertext: no tree, the root is the power
     } else {
         gm = ext_l(x_c);
         rn = ext_l(y_c);
     }
-    if (kind != 3) {
-        root_off = off;
+    if (kind < 3) {
+        root_c = block_r(off);
         off = S.blocks(off, 0, std::vector<i64>(gm), std::vector<i64>(rn), {}, 1);
     }
-    const i64 fin_off = root_off;
     // ---- suffix: assign_integer(res), assert_equal_fresh
     Walk ws(off);
     const std::vector<i64> res_c = assign(ws, L, W, lb);
     ws.putc(c_small(0));
     i64 eq_cell = ws.putc(c_small(1));
     for (unsigned j = 0; j < L; ++j) {
-        is_equal(ws, r_of(fin_off, tm, 0, j), res_c[j]);
+        is_equal(ws, root_c[j], res_c[j]);
         const i64 g = ws.putc(c_small(0));
         ws.gate(g);
         ws.put(eq_cell); ws.put();
@@ -898,11 +953,13 @@ extern "C" int pz_structure_arrays(const pz_structure* st, const uint8_t** d_sel
 }
 
 static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, const uint64_t* exp_g,
-                          const uint64_t* exp_r, size_t count, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    if (!ctx || !out || kind < 0 || kind > 3 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+                          const uint64_t* exp_r, size_t count, uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors,
+                          pz_structure** out) {
+    if (!ctx || !out || kind < 0 || kind > 4 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
     if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
+    if (kind == 4 && (count < 1 || count > 65536 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
     if (limb_bits < 16 || limb_bits > 90 || lookup_bits == 0 || lookup_bits >= k || k < 4 || k > 24 || lookup_bits >= limb_bits) return PZ_ERR_INVALID;
-    if ((kind != 1 && kind != 3 && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
+    if (((kind == 0 || kind == 2) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
     const i64 n = (i64)1 << k;
     const i64 unusable = (i64)blinding_factors + 3;
     if (unusable + 8 > n || (i64)minimum_rows >= n) return PZ_ERR_INVALID;
@@ -910,7 +967,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     PZ_ENTER(ctx);
     Stream S;
     try {
-        PZCHK(build_stream(kind, limbs_n, limb_bits, lookup_bits, exp_g, exp_r, count, S));
+        PZCHK(build_stream(kind, limbs_n, limb_bits, lookup_bits, exp_g, exp_r, count, w_bits, S));
     } catch (const std::bad_alloc&) {
         return PZ_ERR_OOM;
     }
@@ -1062,9 +1119,13 @@ extern "C" int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n,
                                         const uint64_t* exp_g, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
                                         pz_structure** out) {
     if (kind < 0 || kind > 2) return PZ_ERR_INVALID;   // (the tally has an entry point of its own: this one has no place for its count)
-    return structure_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, k, exp_g, exp_r, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, k, exp_g, exp_r, 0, 0, minimum_rows, blinding_factors, out);
 }
 extern "C" int pz_circuit_structure_tally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                               size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 3, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 3, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, minimum_rows, blinding_factors, out);
+}
+extern "C" int pz_circuit_structure_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                               uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
+    return structure_impl(ctx, 4, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, w_bits, minimum_rows, blinding_factors, out);
 }

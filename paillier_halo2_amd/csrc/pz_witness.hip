@@ -221,6 +221,8 @@ struct ExpP {
     unsigned bp_ncols;
     size_t pair_stride, odd_off;   // != 0: steps come in pairs (uniform-shape circuit): step s sits at
                                    // cell0 + (s / 2) * pair_stride + (s & 1) * odd_off instead of cell0 + s * cells
+    size_t chain_steps, chain_stride;   // != 0 (with pair_stride): the pairs come in chains of chain_steps steps, chain_stride cells apart
+                                        // (weighted tally): step s is step s % chain_steps of the chain at cell0 + (s / chain_steps) * chain_stride
 };
 
 __device__ __forceinline__ CellPtr adv_ptr(const ExpP& P, Fr* advice, size_t idx) {
@@ -327,7 +329,9 @@ __global__ __launch_bounds__(EXP_THREADS) void k_witness_expand(ExpP P, const u6
     const bool wide = W > 64;
     const size_t step = blockIdx.x;
     const u64* st = steps + step * 4 * (size_t)P.L64;
-    const CellPtr adv = adv_ptr(P, advice, P.cell0 + (P.pair_stride ? (step >> 1) * P.pair_stride + (step & 1) * P.odd_off : step * P.cells));
+    const size_t cstep = P.chain_steps ? step % P.chain_steps : step;
+    const CellPtr adv = adv_ptr(P, advice, P.cell0 + (P.chain_steps ? step / P.chain_steps * P.chain_stride : 0) +
+                                               (P.pair_stride ? (cstep >> 1) * P.pair_stride + (cstep & 1) * P.odd_off : cstep * P.cells));
     const CellPtr lk{lookup, P.lk0 + step * P.lookups, P.rows, P.pad, nullptr, 0};
     const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const U192 MAXV = u_make(P.max_w[0], P.max_w[1], P.max_w[2]);
@@ -706,16 +710,19 @@ extern "C" int pz_witness_expand_dev(pz_ctx* ctx, uint32_t limbs, uint32_t limb_
 struct CircP {
     ExpP e;                         // shape of the mul_mod steps (L = 2 Ln): range-check parameters, limb width
     unsigned Ln, nf, words_n, kind;
-    unsigned n_in;                  // Ln-limb inputs assigned here: n | g | x | y (kinds 0..2) or n alone (kind 3, the tally)
+    unsigned n_in;                  // Ln-limb inputs assigned here: n | g | x | y (kinds 0..2) or n alone (kinds 3 and 4, the tallies)
     size_t res_off;                 // word offset of res inside `inputs`
-    size_t a_cts, l_cts;            // kind 3: the count assign_integer(c_i, 2 Ln limbs) blocks (k_circuit_assign_many)
+    size_t a_cts, l_cts;            // kinds 3, 4: the count assign_integer(c_i, 2 Ln limbs) blocks (k_circuit_assign_many)
+    size_t n_cts;                   // kinds 3, 4: the number of ciphertexts
+    unsigned w_bits;                // kind 4: bits per weight
+    size_t a_wts;                   // kind 4: the count load_witness(w_i) cells
     unsigned rc_adv, rc_lk;         // range_check(limb, W)
     size_t a_assign[4], a_square, a_refresh, a_zero, a_pow[2], a_res, a_eq;   // advice offsets of the segments
     size_t l_assign[4], l_refresh, l_res;                                      // lookup offsets
     unsigned char inc[CIRC_MAXF];
 };
 
-__global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __restrict__ inputs /* n | g | x | y | res; kind 3: n | c_1 .. c_B | res */,
+__global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __restrict__ inputs /* n | g | x | y | res; kind 3: n | c_1 .. c_B | res; kind 4: n | c_1 .. c_B | w_1 .. w_B | res */,
                                                       const u64* __restrict__ cval /* the circuit's result, L64 words */,
                                                       Fr* __restrict__ advice, Fr* __restrict__ lookup) {
     const CellPtr adv = adv_ptr(C.e, advice, 0), lk{lookup, 0, C.e.rows, C.e.pad, nullptr, 0};
@@ -825,8 +832,8 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
             fp_store(lk + C.l_refresh + t, cv_to_fr(rc_lk_cell(LIMB(s_fresh, t / C.rc_lk), W, lb, t % C.rc_lk)));
     // ---- load_zero; assign_constant(1) + load_zero of both pow_mod_fixed_exp
     if (tid == 0) {
-        if (C.kind != 3) fp_store(adv + C.a_zero, fp_zero<FrTag>());   // (the tally extends nothing: no load_zero)
-        if (C.kind != 1 && C.kind != 3)
+        if (C.kind < 3) fp_store(adv + C.a_zero, fp_zero<FrTag>());   // (the tallies extend nothing: no load_zero)
+        if (C.kind == 0 || C.kind == 2)
             for (int k = 0; k < 2; ++k) {
                 fp_store(adv + C.a_pow[k], fp_one<FrTag>());
                 fp_store(adv + C.a_pow[k] + 1, fp_zero<FrTag>());
@@ -872,6 +879,18 @@ __global__ __launch_bounds__(256) void k_circuit_assign_many(ExpP P, unsigned nl
 
 // ---- uniform-shape circuit: FlexGate::num_to_bits of the message's limbs and the limb-wise select after
 // every mul_mod(acc, sq) of pow_mod.  grid.x = limb of m (num_to_bits) / exponent bit (select).
+// cell t of num_to_bits(x, nbits): the inner product of the bits with the powers of two (1 + 3 (nbits - 1) cells), then assert_bit
+// of every bit ([0, b, b, b]) -- 7 nbits - 2 cells
+__device__ __forceinline__ Fr num_to_bits_cell(const U192& x, unsigned nbits, unsigned t) {
+    const unsigned nip = 1 + 3 * (nbits - 1);
+    if (t == 0) return fr_from_u(u_lowbits(x, 1));
+    if (t < nip) {
+        const unsigned i = (t - 1) / 3 + 1, w = (t - 1) % 3;
+        return w == 0 ? fr_from_u(u_lowbits(u_shr(x, i), 1)) : w == 1 ? fr_from_u(u_shl(u_make(1), i)) : fr_from_u(u_lowbits(x, i + 1));
+    }
+    const unsigned i = (t - nip) / 4, w = (t - nip) % 4;
+    return w == 0 ? fp_zero<FrTag>() : fr_from_u(u_lowbits(u_shr(x, i), 1));
+}
 __global__ __launch_bounds__(256) void k_circuit_bits(ExpP P, unsigned Ln, unsigned words_n, const u64* __restrict__ m_words,
                                                       size_t cell_base, size_t limb_stride, Fr* __restrict__ advice) {
     const unsigned li = blockIdx.x, W = P.W;
@@ -879,31 +898,27 @@ __global__ __launch_bounds__(256) void k_circuit_bits(ExpP P, unsigned Ln, unsig
     limb_extract(m_words, words_n, li, W, lw);
     const U192 x = u_make(lw[0], lw[1]);
     const CellPtr a = adv_ptr(P, advice, cell_base + (size_t)li * limb_stride);
-    const unsigned nip = 1 + 3 * (W - 1);
-    for (unsigned t = threadIdx.x; t < nip + 4 * W; t += blockDim.x) {
-        Fr v;
-        if (t == 0) v = fr_from_u(u_lowbits(x, 1));
-        else if (t < nip) {
-            const unsigned i = (t - 1) / 3 + 1, w = (t - 1) % 3;
-            v = w == 0 ? fr_from_u(u_lowbits(u_shr(x, i), 1)) : w == 1 ? fr_from_u(u_shl(u_make(1), i)) : fr_from_u(u_lowbits(x, i + 1));
-        } else {
-            const unsigned i = (t - nip) / 4, w = (t - nip) % 4;
-            v = w == 0 ? fp_zero<FrTag>() : fr_from_u(u_lowbits(u_shr(x, i), 1));
-        }
-        fp_store(a + t, v);
-    }
+    for (unsigned t = threadIdx.x; t < 7 * W - 2; t += blockDim.x) fp_store(a + t, num_to_bits_cell(x, W, t));
 }
-__global__ __launch_bounds__(256) void k_circuit_select(ExpP P, unsigned Ln, unsigned words_n, const u64* __restrict__ m_words,
-                                                        const u64* __restrict__ steps, size_t cell_base, size_t limb_stride,
-                                                        size_t bit_stride, size_t nbits_cells, Fr* __restrict__ advice) {
-    const unsigned i = blockIdx.x, W = P.W, L = P.L;        // exponent bit i = limb li, bit bi
-    const unsigned li = i / W, bi = i % W;
-    u64 lw[2];
-    limb_extract(m_words, words_n, li, W, lw);
-    const unsigned bit = (unsigned)(u_lowbits(u_shr(u_make(lw[0], lw[1]), bi), 1).w[0]);
-    const u64* st = steps + (size_t)(2 * i) * 4 * P.L64;    // the mul_mod(acc, sq) step: a = acc, r = muled
-    // cells of this bit: after its limb's num_to_bits block and its mul_mod step
-    const CellPtr a = adv_ptr(P, advice, cell_base + (size_t)li * limb_stride + nbits_cells + (size_t)bi * bit_stride + P.cells);
+// the many-chain form (weighted tally, kind 4): grid.x = chain.  Chain i's exponent is the ONE word weights[i]; the block writes the
+// load_witness cell of w_i (a_wts + i) and, at cell_base + i * chain_stride, the chain's head: assign_constant(1), load_zero, then
+// num_to_bits(w_i, nbits)
+__global__ __launch_bounds__(256) void k_circuit_bits_many(ExpP P, unsigned nbits, const u64* __restrict__ weights, size_t a_wts, size_t cell_base,
+                                                           size_t chain_stride, Fr* __restrict__ advice) {
+    const size_t i = blockIdx.x;
+    const U192 x = u_make(weights[i]);
+    const CellPtr a = adv_ptr(P, advice, cell_base + i * chain_stride);
+    if (threadIdx.x == 0) {
+        fp_store(adv_ptr(P, advice, a_wts + i), fr_from_u(x));
+        fp_store(a, fp_one<FrTag>());
+        fp_store(a + 1, fp_zero<FrTag>());
+    }
+    for (unsigned t = threadIdx.x; t < 7 * nbits - 2; t += blockDim.x) fp_store(a + 2 + t, num_to_bits_cell(x, nbits, t));
+}
+// the limb-wise select(bit, muled, acc) after the mul_mod(acc, sq) step `st` (a = acc, r = muled): 8 cells per limb
+// [d | 1 | acc | muled | acc | bit | d | out], d = muled - acc
+__device__ __forceinline__ void select_cells(const ExpP& P, const u64* __restrict__ st, unsigned bit, const CellPtr& a) {
+    const unsigned W = P.W, L = P.L;
     for (unsigned t = threadIdx.x; t < 8 * L; t += blockDim.x) {
         const unsigned limb = t / 8, p = t % 8;
         u64 aw[2], mw[2];
@@ -922,6 +937,30 @@ __global__ __launch_bounds__(256) void k_circuit_select(ExpP P, unsigned Ln, uns
         }
         fp_store(a + t, v);
     }
+}
+__global__ __launch_bounds__(256) void k_circuit_select(ExpP P, unsigned Ln, unsigned words_n, const u64* __restrict__ m_words,
+                                                        const u64* __restrict__ steps, size_t cell_base, size_t limb_stride,
+                                                        size_t bit_stride, size_t nbits_cells, Fr* __restrict__ advice) {
+    const unsigned i = blockIdx.x, W = P.W;                 // exponent bit i = limb li, bit bi
+    const unsigned li = i / W, bi = i % W;
+    u64 lw[2];
+    limb_extract(m_words, words_n, li, W, lw);
+    const unsigned bit = (unsigned)(u_lowbits(u_shr(u_make(lw[0], lw[1]), bi), 1).w[0]);
+    const u64* st = steps + (size_t)(2 * i) * 4 * P.L64;    // the mul_mod(acc, sq) step: a = acc, r = muled
+    // cells of this bit: after its limb's num_to_bits block and its mul_mod step
+    const CellPtr a = adv_ptr(P, advice, cell_base + (size_t)li * limb_stride + nbits_cells + (size_t)bi * bit_stride + P.cells);
+    select_cells(P, st, bit, a);
+}
+// the many-chain form (weighted tally, kind 4): grid.x = chain * nbits + bit.  `steps` holds the chains' records chain-major (2 nbits
+// each); chain i sits at cell_base + i * chain_stride, its bit blocks head_cells (= [1, 0] + num_to_bits) further on
+__global__ __launch_bounds__(256) void k_circuit_select_many(ExpP P, unsigned nbits, const u64* __restrict__ weights, const u64* __restrict__ steps,
+                                                             size_t cell_base, size_t chain_stride, size_t bit_stride, size_t head_cells,
+                                                             Fr* __restrict__ advice) {
+    const size_t i = blockIdx.x / nbits;
+    const unsigned bi = blockIdx.x % nbits;
+    const unsigned bit = (unsigned)((weights[i] >> bi) & 1);
+    const u64* st = steps + (size_t)(2 * (size_t)blockIdx.x) * 4 * P.L64;
+    select_cells(P, st, bit, adv_ptr(P, advice, cell_base + i * chain_stride + head_cells + (size_t)bi * bit_stride + P.cells));
 }
 
 // RefreshAux::new(limb_bits, l, r).increased_limbs_vec with the maximal limb values tracked as bit lengths + exact
@@ -974,8 +1013,10 @@ static int refresh_aux_host(unsigned W, unsigned nl, unsigned nr, unsigned char*
 
 static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t ng, size_t nr, CircP& C,
                                size_t* adv_total, size_t* lk_total, size_t step_off[3]) {
-    if (kind < 0 || kind > 3) return PZ_ERR_INVALID;
+    if (kind < 0 || kind > 4) return PZ_ERR_INVALID;
     if (kind == 3 && (ng < 1 || ng > 65535 || nr)) return PZ_ERR_INVALID;   // the tally of ng + 1 ciphertexts: ng mul_mod blocks
+    // the weighted tally of B = nr + 1 ciphertexts: nr tree blocks, ng = 2 B W chain records
+    if (kind == 4 && (nr > 65535 || ng == 0 || ng % (2 * (nr + 1)) || ng / (2 * (nr + 1)) > 64)) return PZ_ERR_INVALID;
     if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
     memset(&C, 0, sizeof C);
     PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
@@ -988,13 +1029,20 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
     if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
     size_t a = 0, l = 0;
     const size_t asg_a = (size_t)limbs_n * (1 + C.rc_adv), asg_l = (size_t)limbs_n * C.rc_lk;
-    C.n_in = kind == 3 ? 1 : 4;
+    C.n_in = kind >= 3 ? 1 : 4;
     for (unsigned k = 0; k < C.n_in; ++k) { C.a_assign[k] = a; C.l_assign[k] = l; a += asg_a; l += asg_l; }
     C.res_off = 4 * (size_t)C.words_n;
-    if (kind == 3) {   // n | c_1 .. c_B | res: the ciphertexts are full-width integers (2 Ln limbs)
+    if (kind >= 3) {   // n | c_1 .. c_B | res: the ciphertexts are full-width integers (2 Ln limbs)
+        C.n_cts = kind == 3 ? ng + 1 : nr + 1;
         C.a_cts = a; C.l_cts = l;
-        a += (ng + 1) * 2 * asg_a; l += (ng + 1) * 2 * asg_l;
-        C.res_off = C.words_n + (ng + 1) * (size_t)C.e.L64;
+        a += C.n_cts * 2 * asg_a; l += C.n_cts * 2 * asg_l;
+        C.res_off = C.words_n + C.n_cts * (size_t)C.e.L64;
+        if (kind == 4) {   // ... | w_1 .. w_B | res: one 64-bit word and one load_witness cell per weight
+            C.w_bits = (unsigned)(ng / (2 * C.n_cts));
+            C.a_wts = a;
+            a += C.n_cts;
+            C.res_off += C.n_cts;
+        }
     }
     C.a_square = a;
     a += 1;
@@ -1005,7 +1053,7 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
     a += (size_t)C.nf * C.rc_adv;
     l += (size_t)C.nf * C.rc_lk;
     size_t lstep[3] = {0, 0, 0};
-    if (kind != 3) { C.a_zero = a; a += 1; }   // (the tally extends nothing: no load_zero, no pow_mod constants)
+    if (kind < 3) { C.a_zero = a; a += 1; }   // (the tallies extend nothing: no load_zero, no pow_mod_fixed_exp constants)
     if (kind == 0) {
         C.a_pow[0] = a; a += 2; step_off[0] = a; lstep[0] = l; a += ng * C.e.cells; l += ng * C.e.lookups;
         C.a_pow[1] = a; a += 2; step_off[1] = a; lstep[1] = l; a += nr * C.e.cells; l += nr * C.e.lookups;
@@ -1019,9 +1067,17 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
         C.a_pow[1] = a; a += 2; step_off[1] = a; lstep[1] = l; a += nr * C.e.cells; l += nr * C.e.lookups;
     } else if (kind == 3) {   // the product tree's ng blocks, in record order; no further step
         step_off[0] = a; lstep[0] = l; a += ng * C.e.cells; l += ng * C.e.lookups;
+    } else if (kind == 4) {
+        // per chain [1, 0 | num_to_bits | per bit: mul_mod, select (8 cells per limb), square_mod]; step_off[0] is the FIRST CHAIN'S
+        // HEAD (its [1, 0]); then the tree's nr blocks in record order
+        const size_t W = C.w_bits;
+        step_off[0] = a; lstep[0] = l;
+        a += C.n_cts * (2 + 7 * W - 2 + W * (2 * C.e.cells + 8 * (size_t)C.e.L));
+        l += ng * C.e.lookups;
+        step_off[1] = a; lstep[1] = l; a += nr * C.e.cells; l += nr * C.e.lookups;
     } else if (ng || nr) return PZ_ERR_INVALID;
     step_off[2] = a; lstep[2] = l;
-    if (kind != 3) { a += C.e.cells; l += C.e.lookups; }
+    if (kind < 3) { a += C.e.cells; l += C.e.lookups; }
     C.a_res = a; C.l_res = l;
     a += 2 * asg_a; l += 2 * asg_l;
     C.a_eq = a;
@@ -1156,10 +1212,14 @@ static int circuit_expand_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t
     // context, so the copy is truly asynchronous and reads nothing of the caller's afterwards.  Kinds 0 to 2: a few hundred bytes.
     // Kind 3 carries the B ciphertexts (525 KB at B = 1024, 33 MB at B = 65536 for a 2048-bit key): one host memcpy of that size per
     // call, and the staging block grows to it once (grow-only, so a second tally of the size allocates nothing)
+    const u64* wts = kind == 4 ? inputs + C.res_off - C.n_cts : nullptr;   // the weights, one word each, in front of res
+    if (kind == 4 && C.w_bits < 64)
+        for (size_t i = 0; i < C.n_cts; ++i)
+            if (wts[i] >> C.w_bits) return PZ_ERR_MESSAGE_RANGE;   // num_to_bits of such a weight cannot hold
     PZCHK(pz_upload_small_async(ctx, d_in, inputs, in_words * 8));
     pz_timer tm(ctx, PZ_T_EXPAND);
     const size_t rec = 4 * (size_t)C.e.L64;   // words per step record
-    const size_t runs[3] = {kind != 1 ? n_steps_g : 0, kind != 1 ? n_steps_r : 0, kind != 3 ? (size_t)1 : 0};
+    const size_t runs[3] = {kind != 1 ? n_steps_g : 0, kind != 1 ? n_steps_r : 0, kind < 3 ? (size_t)1 : 0};
     size_t first = 0;
     for (int k = 0; k < 3; ++k) {
         if (runs[k]) {
@@ -1187,16 +1247,43 @@ static int circuit_expand_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t
                 first += runs[k];
                 continue;
             }
+            if (kind == 4 && k == 0) {
+                // the chains: every chain is [1, 0 | num_to_bits(w_i) | W x (mul_mod, select, square_mod)], chain_stride cells apart;
+                // one launch each for the heads, the selects and the 2 B W steps, whatever B is
+                const size_t W = C.w_bits, head = 2 + 7 * W - 2, bit_stride = 2 * C.e.cells + 8 * (size_t)C.e.L;
+                const size_t chain_stride = head + W * bit_stride;
+                const u64* d_w = (const u64*)d_in + C.res_off - C.n_cts;
+                hipLaunchKernelGGL(k_circuit_bits_many, dim3((unsigned)C.n_cts), dim3(256), 0, ctx->stream, C.e, (unsigned)W, d_w, C.a_wts, so[0],
+                                   chain_stride, (Fr*)d_advice);
+                hipLaunchKernelGGL(k_circuit_select_many, dim3((unsigned)(C.n_cts * W)), dim3(256), 0, ctx->stream, C.e, (unsigned)W, d_w, d_steps,
+                                   so[0], chain_stride, bit_stride, head, (Fr*)d_advice);
+                ExpP Q = P;
+                Q.cell0 = so[0] + head;
+                Q.pair_stride = bit_stride;
+                Q.odd_off = C.e.cells + 8 * (size_t)C.e.L;
+                Q.chain_steps = 2 * W;
+                Q.chain_stride = chain_stride;
+                hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)runs[0]), dim3(EXP_THREADS), 0, ctx->stream, Q, d_steps, d_modulus,
+                                   (Fr*)d_advice, (Fr*)d_lookup);
+                first += runs[k];
+                continue;
+            }
             hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)runs[k]), dim3(EXP_THREADS), 0, ctx->stream, P, d_steps + first * rec,
                                d_modulus, (Fr*)d_advice, (Fr*)d_lookup);
         }
         first += runs[k];
     }
-    if (kind == 3)
-        hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)(n_steps_g + 1)), dim3(256), 0, ctx->stream, C.e, C.nf, C.rc_adv, C.rc_lk,
+    if (kind >= 3)
+        hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)C.n_cts), dim3(256), 0, ctx->stream, C.e, C.nf, C.rc_adv, C.rc_lk,
                            (const u64*)d_in + C.words_n, C.a_cts, C.l_cts, (Fr*)d_advice, (Fr*)d_lookup);
     // the circuit's result c = remainder of the last step (the final mul_mod; the tally's root)
     const uint64_t* d_c = d_steps + (first - 1) * rec + 3 * (size_t)C.e.L64;
+    if (kind == 4 && C.n_cts == 1) {
+        // one ciphertext has no tree: the result is the chain's last select output -- the product of the last (acc, sq) step where the
+        // weight's top bit is set, its acc otherwise
+        const bool top = (wts[0] >> (C.w_bits - 1)) & 1;
+        d_c = d_steps + (n_steps_g - 2) * rec + (top ? 3 : 0) * (size_t)C.e.L64;
+    }
     hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, (const u64*)d_in, (const u64*)d_c, (Fr*)d_advice,
                        (Fr*)d_lookup);
     HIPCHK(ctx, hipGetLastError());

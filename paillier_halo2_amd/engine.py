@@ -489,6 +489,36 @@ class Engine:
                   "pz_paillier_tally_dev")
         return c
 
+    def paillier_wtally(self, limbs_n: int, n, cts, weights, w_bits: int, want_steps: bool = True):
+        """prod c_i^w_i mod n^2 (pz.h pz_paillier_wtally): cts is (B, 2*limbs_n), weights B integers below 2^w_bits.  Returns
+        (C (2*limbs_n,), steps (2 B w_bits + B - 1, 4, 2*limbs_n) -- the chains' records chain-major, then the tree's -- or None)."""
+        L = 2 * limbs_n
+        n = _np(n).reshape(limbs_n)
+        cts = _np(cts).reshape(-1, L)
+        wts = np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1)
+        count = cts.shape[0]
+        if wts.shape[0] != count:
+            raise ValueError("one weight per ciphertext")
+        ns = 2 * count * w_bits + count - 1
+        steps = np.zeros((max(ns, 1), 4, L), dtype=np.uint64) if want_steps else None
+        c = np.zeros(L, dtype=np.uint64)
+        self._chk(self.L.pz_paillier_wtally(self.ctx, limbs_n, count, w_bits, _ptr(n), _ptr(cts), _ptr(wts), _ptr(steps) if want_steps else VP(),
+                                            max(ns, 0), _ptr(c)), "pz_paillier_wtally")
+        return c, (steps[:ns] if want_steps else None)
+
+    def paillier_wtally_dev(self, limbs_n: int, n, cts, weights, w_bits: int, d_steps: int, steps_cap: int):
+        """the same with the records left on the device for K4 (d_steps: steps_cap x 4 x 2*limbs_n u64).  Returns C."""
+        L = 2 * limbs_n
+        n = _np(n).reshape(limbs_n)
+        cts = _np(cts).reshape(-1, L)
+        wts = np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1)
+        if wts.shape[0] != cts.shape[0]:
+            raise ValueError("one weight per ciphertext")
+        c = np.zeros(L, dtype=np.uint64)
+        self._chk(self.L.pz_paillier_wtally_dev(self.ctx, limbs_n, cts.shape[0], w_bits, _ptr(n), _ptr(cts), _ptr(wts), VP(d_steps), steps_cap,
+                                                _ptr(c)), "pz_paillier_wtally_dev")
+        return c
+
     # ------------------------------------------------------------------ K4: witness expansion
     def witness_cells_per_step(self, limbs: int, limb_bits: int, lookup_bits: int) -> Tuple[int, int]:
         a = C.c_size_t()
@@ -524,8 +554,8 @@ class Engine:
     def circuit_expand_dev(self, kind: int, limbs_n: int, limb_bits: int, lookup_bits: int, inputs, d_steps: int, n_steps_g: int,
                            n_steps_r: int, d_modulus: int, d_advice: int, d_lookup: int = 0, rows: int = 0, col_stride: int = 0):
         """inputs: host uint64 array n | g | x | y | res, or n | c_1 .. c_B | res for kind 3 (the tally: n_steps_g = B - 1, n_steps_r = 0;
-        pz.h); writes the whole circuit's cell stream, dense or cut into
-        columns of `rows` cells stored `col_stride` elements apart"""
+        pz.h), or n | c_1 .. c_B | w_1 .. w_B | res for kind 4 (the weighted tally: n_steps_g = 2 B W, n_steps_r = B - 1); writes the
+        whole circuit's cell stream, dense or cut into columns of `rows` cells stored `col_stride` elements apart"""
         inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
         self._chk(self.L.pz_circuit_expand_dev(self.ctx, kind, limbs_n, limb_bits, lookup_bits, _ptr(inp), VP(d_steps), n_steps_g,
                                                n_steps_r, VP(d_modulus), VP(d_advice), VP(d_lookup), rows, col_stride),

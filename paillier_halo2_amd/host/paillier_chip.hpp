@@ -15,6 +15,7 @@
 //   paillier.rs:22-30 get_biguint                              PaillierChip::get_biguint
 //   paillier.rs:32-60 encrypt, :62-85 add                      PaillierChip::encrypt / add
 //   (add folded over B full-width ciphertexts)                 PaillierChip::tally, pz::paillier_tally_test
+//   (c^w and prod c_i^w_i: the scalar homomorphism)            PaillierChip::mul_scalar / weighted_tally, pz::paillier_wtally_test (15.8)
 //   paillier.rs:87-97 paillier_enc_native / _add_native        pz::paillier_enc_native / paillier_add_native
 //   bench.rs:11-31    input structs, :33-117 drivers           pz::PaillierEncryptionInput ... paillier_enc_test ...
 //
@@ -66,7 +67,8 @@ class Context {
     Context(const Context&) = delete;
     pz_ctx* raw() { return ctx_; }
     // ---- the operation tape: what the reference's Context would hold, operation by operation
-    enum Op { ASSIGN = 0, SQUARE = 1, REFRESH = 2, CONST_CELL = 3, MUL_MOD = 4, ASSERT_EQUAL = 5 };
+    // (0 .. 5 are pz_op_cells' operations; the three after them push a cell count of their own: record_cells)
+    enum Op { ASSIGN = 0, SQUARE = 1, REFRESH = 2, CONST_CELL = 3, MUL_MOD = 4, ASSERT_EQUAL = 5, LOAD_WITNESS = 6, NUM_TO_BITS = 7, SELECT = 8 };
     struct OpRec {
         Op op;
         unsigned limbs;      // limb count the operation works on
@@ -83,6 +85,12 @@ class Context {
         if (!ops_.empty() && ops_.back().op == op && op == MUL_MOD && ops_.back().limbs == limbs) ops_.back().count += count;
         else ops_.push_back(OpRec{op, limbs, count});
     }
+    // an operation of the weighted tally that pz_op_cells does not know: `cells` advice cells, no lookups
+    void record_cells(Op op, unsigned limbs, size_t cells) {
+        advice_cells_ += cells;
+        ops_.push_back(OpRec{op, limbs, 1});
+    }
+    size_t load_witness() { record_cells(LOAD_WITNESS, 1, 1); return witness_cells_++; }   // ctx.load_witness(v): one advice cell, no gate
     size_t load_zero() { record(CONST_CELL, 1); return zero_cells_++; }            // paillier.rs:47 ctx.load_zero(): one advice cell
     size_t load_constant_one() { record(CONST_CELL, 1); return zero_cells_++; }    // assign_constant(1) of pow_mod_fixed_exp
     const std::vector<OpRec>& ops() const { return ops_; }
@@ -109,7 +117,7 @@ class Context {
 
   private:
     pz_ctx* ctx_ = nullptr;
-    size_t zero_cells_ = 0, advice_cells_ = 0, lookup_cells_ = 0;
+    size_t zero_cells_ = 0, witness_cells_ = 0, advice_cells_ = 0, lookup_cells_ = 0;
     unsigned L_ = 0, W_ = 64, words_ = 0, lookup_bits_ = 0;
     std::vector<OpRec> ops_;
     BigUint modulus_;
@@ -252,6 +260,12 @@ class BigUintChip {
     }
 };
 
+// a weight of the weighted tally: the value ctx.load_witness put into one advice cell
+struct AssignedWeight {
+    uint64_t value = 0;
+    size_t cell = 0;
+};
+
 struct EncryptionPublicKeyAssigned {  // paillier.rs:6-9
     AssignedBigUint<Fresh> n, g;
 };
@@ -342,6 +356,70 @@ class PaillierChip {  // paillier.rs:11-15
         ctx.push_steps(steps, Wd, L, biguint->limb_bits, n2.value());
         return R::Ok(AssignedBigUint<Fresh>(BigUint::from_limbs(root.data(), wk), L, biguint->limb_bits));
     }
+
+    // The weighted tally: prod cts[i]^weights[i] mod n^2 = Enc(sum w_i m_i).  n^2 hoisted once; per ciphertext
+    // BigUintChip::pow_mod over w_bits in-circuit bits -- assign_constant(1), load_zero, num_to_bits(w_i, w_bits), then per bit
+    // mul_mod(acc, sq), the limb-wise select, square_mod(sq) --; then the tally's product tree over the powers (one ciphertext: none).
+    // One pz_paillier_wtally call computes every record; the tape takes them in the circuit's order.
+    Result<AssignedBigUint<Fresh>> weighted_tally(Context& ctx, const EncryptionPublicKeyAssigned& pk_enc,
+                                                  const std::vector<AssignedBigUint<Fresh>>& cts, const std::vector<AssignedWeight>& weights,
+                                                  unsigned w_bits) const {
+        using R = Result<AssignedBigUint<Fresh>>;
+        if (cts.empty() || cts.size() != weights.size()) return R::Err(PZ_ERR_INVALID, "weighted_tally: one weight per ciphertext, at least one");
+        if (w_bits < 1 || w_bits > 64) return R::Err(PZ_ERR_INVALID, "weighted_tally: w_bits outside 1 .. 64");
+        auto n2m = biguint->square(ctx, pk_enc.n);
+        if (!n2m.ok) return R::Err(n2m.err.status, n2m.err.msg);
+        RefreshAux aux = RefreshAux::new_(biguint->limb_bits, pk_enc.n.num_limbs(), pk_enc.n.num_limbs());
+        auto n2r = biguint->refresh(ctx, n2m.val, aux);
+        if (!n2r.ok) return R::Err(n2r.err.status, n2r.err.msg);
+        const AssignedBigUint<Fresh>& n2 = n2r.val;
+        const unsigned L = n2.num_limbs(), Wd = n2.num_words(), wn = pk_enc.n.num_words(), wk = 2 * wn;   // K3 works on 2 * wn words
+        std::vector<uint64_t> nv = pk_enc.n.words(), cv, wv;
+        for (const auto& c : cts) {
+            if (c.num_limbs() != L) return R::Err(PZ_ERR_INVALID, "weighted_tally: a ciphertext is not assigned at full width");
+            std::vector<uint64_t> w = c.value().to_limbs(wk);
+            cv.insert(cv.end(), w.begin(), w.end());
+        }
+        for (const AssignedWeight& w : weights) wv.push_back(w.value);
+        const size_t B = cts.size(), n_chain = 2 * B * w_bits, ns = n_chain + B - 1;
+        std::vector<uint64_t> rec(ns * 4 * wk), root(wk);
+        int rc = pz_paillier_wtally(ctx.raw(), wn, B, w_bits, nv.data(), cv.data(), wv.data(), rec.data(), ns, root.data());
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_wtally: ") + pz_strerror(rc));
+        // the tape holds Wd words per integer (Wd < 2 * wn where limb_bits does not divide 64: the words above are zero)
+        auto steps_of = [&](size_t first, size_t count, std::vector<uint64_t>& out) {
+            out.clear();
+            for (size_t f = first * 4; f < (first + count) * 4; ++f) {
+                if (BigUint::from_limbs(rec.data() + f * wk, wk).bits() > (size_t)L * biguint->limb_bits) return false;
+                out.insert(out.end(), rec.begin() + f * wk, rec.begin() + f * wk + Wd);
+            }
+            return true;
+        };
+        std::vector<uint64_t> steps;
+        for (size_t i = 0; i < B; ++i) {
+            (void)ctx.load_constant_one();
+            (void)ctx.load_zero();
+            ctx.record_cells(Context::NUM_TO_BITS, 1, 7 * (size_t)w_bits - 2);
+            for (unsigned j = 0; j < w_bits; ++j) {
+                const size_t at = 2 * (i * w_bits + j);
+                if (!steps_of(at, 1, steps)) return R::Err(PZ_ERR_RANGE, "a step's integer does not fit the assigned limb count");
+                ctx.push_steps(steps, Wd, L, biguint->limb_bits, n2.value());
+                ctx.record_cells(Context::SELECT, L, 8 * (size_t)L);
+                if (!steps_of(at + 1, 1, steps)) return R::Err(PZ_ERR_RANGE, "a step's integer does not fit the assigned limb count");
+                ctx.push_steps(steps, Wd, L, biguint->limb_bits, n2.value());
+            }
+        }
+        if (B > 1) {
+            if (!steps_of(n_chain, B - 1, steps)) return R::Err(PZ_ERR_RANGE, "a step's integer does not fit the assigned limb count");
+            ctx.push_steps(steps, Wd, L, biguint->limb_bits, n2.value());
+        }
+        return R::Ok(AssignedBigUint<Fresh>(BigUint::from_limbs(root.data(), wk), L, biguint->limb_bits));
+    }
+
+    // c^w mod n^2 = Enc(w m): the weighted tally of one ciphertext
+    Result<AssignedBigUint<Fresh>> mul_scalar(Context& ctx, const EncryptionPublicKeyAssigned& pk_enc, const AssignedBigUint<Fresh>& c,
+                                              const AssignedWeight& w, unsigned w_bits) const {
+        return weighted_tally(ctx, pk_enc, {c}, {w}, w_bits);
+    }
 };
 
 // paillier.rs:87-92: (g^m * r^n) mod n^2 -- one pz_paillier_encrypt call without a trace
@@ -422,6 +500,30 @@ inline void paillier_tally_test(Context& ctx, const RangeChip& range, const Pail
     biguint_chip.assert_equal_fresh(ctx, root, res_assigned).unwrap();
 }
 
+// the weighted tally's driver: assign n, assign every c_i at 2 * enc_bits, load_witness every w_i, weighted_tally, assign res,
+// assert_equal_fresh
+struct PaillierWTallyInput {
+    unsigned limb_bits, enc_bits, w_bits;
+    BigUint n;
+    std::vector<BigUint> cts;
+    std::vector<uint64_t> weights;
+    BigUint res;
+};
+inline void paillier_wtally_test(Context& ctx, const RangeChip& range, const PaillierWTallyInput& input) {
+    BigUintChip biguint_chip = BigUintChip::construct(&range, input.limb_bits);
+    PaillierChip paillier_chip = PaillierChip::construct(&biguint_chip, input.enc_bits);
+    auto n_assigned = biguint_chip.assign_integer(ctx, input.n, input.enc_bits).unwrap();
+    EncryptionPublicKeyAssigned pk_enc{n_assigned, {}};   // g plays no part here
+    std::vector<AssignedBigUint<Fresh>> cts;
+    for (const BigUint& c : input.cts) cts.push_back(biguint_chip.assign_integer(ctx, c, input.enc_bits * 2).unwrap());
+    std::vector<AssignedWeight> weights;
+    for (uint64_t w : input.weights) weights.push_back(AssignedWeight{w, ctx.load_witness()});
+    auto root = paillier_chip.weighted_tally(ctx, pk_enc, cts, weights, input.w_bits).unwrap();
+    auto res_assigned = biguint_chip.assign_integer(ctx, input.res, input.enc_bits * 2).unwrap();
+    if (root.value() != res_assigned.value()) throw std::runtime_error("assertion failed: `(left == right)` (paillier_wtally_test)");
+    biguint_chip.assert_equal_fresh(ctx, root, res_assigned).unwrap();
+}
+
 // K4 over the mul_mod steps alone (the bulk of the stream; the caller places the buffers)
 inline int synthesize_witness(Context& ctx, const RangeChip& range, uint64_t* d_steps, uint64_t* d_modulus, uint64_t* d_advice,
                               uint64_t* d_lookup) {
@@ -469,6 +571,28 @@ inline int synthesize_tally_circuit(Context& ctx, unsigned enc_bits, const BigUi
     in.insert(in.end(), w.begin(), w.end());
     return pz_circuit_expand_dev(ctx.raw(), 3, Ln, W, ctx.lookup_bits(), in.data(), d_steps, cts.size() - 1, 0, d_modulus, d_advice,
                                  d_lookup, 0, 0);
+}
+
+// the weighted tally's tape (paillier_wtally_test) expanded on the device: circuit kind 4, inputs n | c_1 .. c_B | w_1 .. w_B | res
+inline int synthesize_wtally_circuit(Context& ctx, unsigned enc_bits, unsigned w_bits, const BigUint& n, const std::vector<BigUint>& cts,
+                                     const std::vector<uint64_t>& weights, const BigUint& res, uint64_t* d_steps, uint64_t* d_modulus,
+                                     uint64_t* d_advice, uint64_t* d_lookup) {
+    const unsigned W = ctx.limb_bits(), Ln = enc_bits / W, wn = (Ln * W + 63) / 64, wr = (2 * Ln * W + 63) / 64;
+    const size_t B = cts.size(), ng = 2 * B * w_bits;
+    if (B < 1 || weights.size() != B || ctx.n_steps() != ng + B - 1) return PZ_ERR_INVALID;
+    size_t a = 0, l = 0;
+    int rc = pz_circuit_cells(4, Ln, W, ctx.lookup_bits(), ng, B - 1, &a, &l);
+    if (rc != PZ_OK) return rc;
+    if (a != ctx.advice_cells() || l != ctx.lookup_cells()) return PZ_ERR_INVALID;   // the tape is not this driver's
+    std::vector<uint64_t> in = n.to_limbs(wn);
+    for (const BigUint& c : cts) {
+        std::vector<uint64_t> w = c.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    in.insert(in.end(), weights.begin(), weights.end());
+    std::vector<uint64_t> w = res.to_limbs(wr);
+    in.insert(in.end(), w.begin(), w.end());
+    return pz_circuit_expand_dev(ctx.raw(), 4, Ln, W, ctx.lookup_bits(), in.data(), d_steps, ng, B - 1, d_modulus, d_advice, d_lookup, 0, 0);
 }
 
 }  // namespace pz

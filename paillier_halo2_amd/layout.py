@@ -196,20 +196,43 @@ def tally_tree(count: int):
     return blocks
 
 
+WTALLY_MAX_BITS = 64  # width of a weight of the weighted tally (pz.h pz_paillier_wtally): one 64-bit word
+
+
+def wtally_tree(count: int):
+    """tally_tree over the B powers c_i^w_i of a weighted tally; B = 1 has no tree (the root is the power itself)"""
+    if not 1 <= count <= TALLY_MAX:
+        raise ValueError(f"a weighted tally takes 1 .. {TALLY_MAX} ciphertexts, not {count}")
+    return tally_tree(count) if count > 1 else []
+
+
 def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_steps_g: int = 0, n_steps_r: int = 0,
-                  count: int | None = None) -> CircuitCells:
+                  count: int | None = None, w_bits: int | None = None) -> CircuitCells:
     """The whole cell stream of paillier_enc_test (bench.rs:33-75, kind 'encrypt') or paillier_enc_add_test
     (bench.rs:77-117, kind 'add'), operation by operation in call order -- what pz_circuit_expand_dev writes.
     kind 'tally' (count = B ciphertexts): assign n, assign c_1 .. c_B at full width, square + refresh once, the B - 1 blocks of
-    tally_tree, assign res, assert_equal_fresh -- no load_zero, no g, no pow_mod constants."""
+    tally_tree, assign res, assert_equal_fresh -- no load_zero, no g, no pow_mod constants.
+    kind 'wtally' (count = B ciphertexts, w_bits = W bits per weight): assign n, assign c_1 .. c_B at full
+    width, load_witness(w_1 .. w_B), square + refresh once, per ciphertext pow_mod(c_i, w_i) over W in-circuit bits ([1, 0],
+    num_to_bits, W blocks of mul_mod + select + square_mod), the B - 1 blocks of the tree over the powers, assign res,
+    assert_equal_fresh."""
     Ln, L = limbs_n, 2 * limbs_n
     if kind == "tally":
         if count is None or not 2 <= count <= TALLY_MAX:
             raise ValueError(f"a tally takes count = 2 .. {TALLY_MAX} ciphertexts, not {count}")
         if n_steps_g not in (0, count - 1) or n_steps_r:
             raise ValueError("a tally of count ciphertexts has count - 1 steps")
+    elif kind == "wtally":
+        if count is None or not 1 <= count <= TALLY_MAX:
+            raise ValueError(f"a weighted tally takes count = 1 .. {TALLY_MAX} ciphertexts, not {count}")
+        if w_bits is None or not 1 <= w_bits <= WTALLY_MAX_BITS:
+            raise ValueError(f"a weight has w_bits = 1 .. {WTALLY_MAX_BITS} bits, not {w_bits}")
+        if n_steps_g not in (0, 2 * count * w_bits) or n_steps_r not in (0, count - 1):
+            raise ValueError("a weighted tally has 2 * count * w_bits chain steps and count - 1 tree steps")
     elif count is not None:
-        raise ValueError("count belongs to kind 'tally'")
+        raise ValueError("count belongs to kinds 'tally' and 'wtally'")
+    if w_bits is not None and kind != "wtally":
+        raise ValueError("w_bits belongs to kind 'wtally'")
     mm = mul_mod_cells(L, limb_bits, lookup_bits)
     seg, a, l = {}, 0, 0
 
@@ -219,16 +242,22 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         a += da
         l += dl
 
-    if kind == "tally":
+    if kind in ("tally", "wtally"):
         put("assign_n", *assign_cells(Ln, limb_bits, lookup_bits))
         ca, cl = assign_cells(L, limb_bits, lookup_bits)
         put("assign_cts", count * ca, count * cl)
+        if kind == "wtally":
+            put("weights", count)
     else:
         for name in ("assign_n", "assign_g", "assign_x", "assign_y"):
             put(name, *assign_cells(Ln, limb_bits, lookup_bits))
     put("square", square_cells(Ln))
     put("refresh", *refresh_cells(refresh_aux(limb_bits, Ln, Ln), limb_bits, lookup_bits))
     if kind == "tally":
+        put("tree", (count - 1) * mm.advice, (count - 1) * mm.lookup)
+    elif kind == "wtally":
+        # per chain: assign_constant(1), load_zero, num_to_bits (7 W - 2 cells), W blocks of mul_mod + select + square_mod
+        put("chains", count * (2 + 7 * w_bits - 2 + w_bits * (2 * mm.advice + 8 * L)), count * 2 * w_bits * mm.lookup)
         put("tree", (count - 1) * mm.advice, (count - 1) * mm.lookup)
     else:
         put("load_zero", 1)
@@ -242,7 +271,7 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         assert n_steps_g in (0, 2 * m_bits)
         put("pow_g", 2 + Ln * (7 * limb_bits - 2) + m_bits * (2 * mm.advice + 8 * L), 2 * m_bits * mm.lookup)
         put("pow_r", 2 + n_steps_r * mm.advice, n_steps_r * mm.lookup)
-    if kind != "tally":
+    if kind not in ("tally", "wtally"):
         put("final", mm.advice, mm.lookup)
     put("assign_res", *assign_cells(L, limb_bits, lookup_bits))
     put("assert_equal", assert_equal_cells(L))

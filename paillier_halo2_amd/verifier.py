@@ -178,12 +178,14 @@ def record_seed(prefix: str) -> bytes:
 
 
 def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int] = None, c2: Optional[int] = None, *, enc_bits: int, limb_bits: int,
-                  cts: Optional[Sequence[int]] = None) -> List[int]:
+                  cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None) -> List[int]:
     """the statement of a circuit with the instance column, in the column's row order: little-endian limbs of limb_bits,
     n | g | c (kind "encrypt" / "encrypt_uniform": c = g^m r^n mod n^2) or n | g | c1 | c2 | c ("add": c = c1 c2 mod n^2); n, g, c1, c2 have
     enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)
     kind "tally": n | c_1 | .. | c_B | c with cts = [c_1 .. c_B] at full width (twice n's limbs each) and c their product mod n^2; g plays
-    no part in an addition and is ignored."""
+    no part in an addition and is ignored.
+    kind "wtally": n | c_1 | .. | c_B | w_1 | .. | w_B | c with c = prod c_i^w_i mod n^2, B >= 1; a weight is ONE value (one cell of
+    the circuit, below 2^64), not limbs."""
     Ln = enc_bits // limb_bits
     mask = (1 << limb_bits) - 1
     limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
@@ -197,14 +199,25 @@ def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int]
         if cts is None or len(cts) < 2:
             raise ValueError("the tally statement names its ciphertexts: cts = [c_1 .. c_B], B >= 2")
         parts = [(n, Ln)] + [(ci, 2 * Ln) for ci in cts] + [(c, 2 * Ln)]
+    elif kind == "wtally":
+        if cts is None or weights is None or len(cts) < 1 or len(weights) != len(cts):
+            raise ValueError("the weighted tally's statement names its ciphertexts and one weight each: cts = [c_1 .. c_B], weights = [w_1 .. w_B]")
+        if any(int(v) < 0 or int(v) >> 64 for v in weights):
+            raise ValueError("a weight does not fit 64 bits")
+        parts = [(n, Ln)] + [(ci, 2 * Ln) for ci in cts] + [(c, 2 * Ln)]
     else:
-        raise ValueError("kind must be encrypt, add, encrypt_uniform or tally")
-    if cts is not None and kind != "tally":
-        raise ValueError("cts belongs to kind 'tally'")
+        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally or wtally")
+    if cts is not None and kind not in ("tally", "wtally"):
+        raise ValueError("cts belongs to kinds 'tally' and 'wtally'")
+    if weights is not None and kind != "wtally":
+        raise ValueError("weights belongs to kind 'wtally'")
     for v, cnt in parts:
         if int(v) < 0 or int(v) >> (limb_bits * cnt):
             raise ValueError("a value does not fit its %d limbs" % cnt)
-    return [x for v, cnt in parts for x in limbs(v, cnt)]
+    out = [x for v, cnt in parts for x in limbs(v, cnt)]
+    if kind == "wtally":      # the weights stand between the ciphertexts and the result
+        out[-2 * Ln:-2 * Ln] = [int(v) for v in weights]
+    return out
 
 
 def instance_eval(k: int, values: Sequence[int], x: int) -> int:

@@ -99,6 +99,11 @@ extern "C" {
                              steps_out: *mut u64, steps_cap: usize, c_out: *mut u64) -> c_int;
     pub fn pz_paillier_tally_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, n: *const u64, cts: *const u64,
                                  d_steps_out: *mut u64, steps_cap: usize, c_out: *mut u64) -> c_int;
+    // the weighted tally: prod c_i^w_i -- 2 * count * w_bits chain records (chain-major), then the tree's count - 1
+    pub fn pz_paillier_wtally(ctx: *mut pz_ctx, limbs_n: u32, count: usize, w_bits: u32, n: *const u64, cts: *const u64,
+                              weights: *const u64, steps_out: *mut u64, steps_cap: usize, c_out: *mut u64) -> c_int;
+    pub fn pz_paillier_wtally_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, w_bits: u32, n: *const u64, cts: *const u64,
+                                  weights: *const u64, d_steps_out: *mut u64, steps_cap: usize, c_out: *mut u64) -> c_int;
 
     // uniform-shape variant (NOT the reference's circuit) -- g^m over m_bits in-circuit exponent bits
     pub fn pz_paillier_encrypt_uniform(ctx: *mut pz_ctx, limbs_n: u32, batch: usize, m_bits: u32, n: *const u64, g: *const u64,
@@ -134,6 +139,8 @@ extern "C" {
                                     exp_r: *const u64, minimum_rows: usize, blinding_factors: u32, out: *mut *mut pz_structure) -> c_int;
     pub fn pz_circuit_structure_tally_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, k: u32, count: usize,
                                           minimum_rows: usize, blinding_factors: u32, out: *mut *mut pz_structure) -> c_int;
+    pub fn pz_circuit_structure_wtally_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, k: u32, count: usize,
+                                           w_bits: u32, minimum_rows: usize, blinding_factors: u32, out: *mut *mut pz_structure) -> c_int;
     pub fn pz_structure_info(st: *const pz_structure, n_adv: *mut usize, n_adv_filled: *mut usize, n_lk: *mut usize, max_rows: *mut usize,
                              n_constants: *mut usize, n_cells: *mut usize, n_lookups: *mut usize, n_steps_g: *mut usize,
                              n_steps_r: *mut usize) -> c_int;
