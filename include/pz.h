@@ -164,6 +164,18 @@ int pz_msm_g1_batch(pz_ctx* ctx, const pz_bases* bases, const uint64_t* const* s
  * one large MSM gives each rank a disjoint window range and sums the partial points. */
 int pz_msm_g1_dev(pz_ctx* ctx, const pz_bases* bases, const uint64_t* d_scalars, size_t n_cols, size_t n,
                   size_t col_stride, uint32_t win_lo, uint32_t win_hi, uint64_t* d_out_jac);
+/* pz_msm_g1_dev with a DENSITY HINT for a batch of columns (more than 8 per call; fewer ignore it).  The digit sort has a
+ * variant for columns of short scalars (witness cells: few non-zero digits) and one for full-width scalars; without a hint
+ * (PZ_MSM_AUTO == pz_msm_g1_dev) both are queued and the device picks one per launch from the number of non-zero digits.  A
+ * caller that knows what its columns hold says so: PZ_MSM_SPARSE queues the single-pass scatter alone and sorts in
+ * column-sized slices, PZ_MSM_DENSE queues the two-step scatter alone.  The hint chooses launches and sizes, never results:
+ * the group element is the same under every hint (compare after pz_g1_normalize), a wrong hint only costs time.  Any other
+ * value of `density` is PZ_ERR_INVALID. */
+#define PZ_MSM_AUTO 0
+#define PZ_MSM_SPARSE 1
+#define PZ_MSM_DENSE 2
+int pz_msm_g1_dev_ex(pz_ctx* ctx, const pz_bases* bases, const uint64_t* d_scalars, size_t n_cols, size_t n,
+                     size_t col_stride, uint32_t win_lo, uint32_t win_hi, int density, uint64_t* d_out_jac);
 /* sum of n Jacobian points (host in/out): the fixed-order fold of per-rank partial MSMs. */
 int pz_g1_sum(pz_ctx* ctx, const uint64_t* jac /* n x 12 */, size_t n, uint64_t out_jac[12]);
 /* device form: d_jac (n x 12) and d_out_jac (12) are device pointers; asynchronous on the context's stream.  d_out_jac

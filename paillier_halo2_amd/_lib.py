@@ -47,6 +47,7 @@ SIGNATURES = {
     "pz_msm_g1": (C.c_int, [VP, VP, VP, C.c_size_t, VP]),
     "pz_msm_g1_batch": (C.c_int, [VP, VP, C.POINTER(VP), C.c_size_t, C.c_size_t, VP]),
     "pz_msm_g1_dev": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, VP]),
+    "pz_msm_g1_dev_ex": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, VP]),
     "pz_g1_commit_mask_dev": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, VP]),
     "pz_g1_sum": (C.c_int, [VP, VP, C.c_size_t, VP]),
     "pz_g1_sum_dev": (C.c_int, [VP, VP, C.c_size_t, VP]),

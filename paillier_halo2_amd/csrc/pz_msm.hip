@@ -41,7 +41,7 @@ struct MsmP {
     size_t cap;        // entry capacity per column = n * (win_hi - win_lo)
     size_t max_items;  // work items per column (upper bound) = B + cap / chunk
     unsigned chunk;    // entries per work item, MSM_CHUNK_MIN..MSM_CHUNK_MAX
-    unsigned spt;      // scalars per thread of the sort passes: a slice is SORT_THREADS * spt scalars (msm_spt_for)
+    unsigned spt;      // scalars per thread of the sort passes: a slice is SORT_THREADS * spt scalars (msm_spt_for, msm_spt_sparse)
 };
 
 // Which scatter runs is decided ON THE DEVICE from the launch's number of non-zero digits (summed by the scan kernels): the
@@ -761,7 +761,10 @@ __global__ __launch_bounds__(SORT_THREADS) void k_msm_scatter(const Fr* __restri
     size_t col;
     unsigned slice;
     if (!sort_block_coords(n_slices, n_cols, slice, col)) return;
-    const u32* in = slice_hist + (col * n_slices + slice) * (size_t)p.B;
+    // slice_hist == nullptr: the column is ONE slice (sparse launches, msm_spt_sparse) -- every slice offset is zero, k_msm_totals
+    // did not run and the histogram still holds counts: the cursors are the bucket offsets themselves
+    const bool sliced = slice_hist != nullptr;
+    const u32* in = sliced ? slice_hist + (col * n_slices + slice) * (size_t)p.B : offs;
     const u32* o = offs + col * (p.B + 1);
     // eight buckets per thread in flight (a plain loop waited for each pair of loads: 32 round trips per workgroup, the
     // whole cost of the pass for a single column cut into many slices)
@@ -771,7 +774,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_msm_scatter(const Fr* __restri
         for (unsigned k = 0; k < 8; ++k) {
             const unsigned b = b0 + k * SORT_THREADS, bc = b < p.B ? b : p.B - 1;
             va[k] = o[bc];
-            vb[k] = in[bc];
+            vb[k] = sliced ? in[bc] : 0u;
         }
 #pragma unroll
         for (unsigned k = 0; k < 8; ++k) {
@@ -1420,8 +1423,32 @@ static unsigned msm_spt_for(size_t n_cols, size_t n) {
     return spt;
 }
 
+// ... of a column batch the caller declared SPARSE (pz_msm_g1_dev_ex: witness-like columns of short scalars).  Such a column
+// leaves ~24 000 entries, so the fixed traffic above IS the sort (640 KB of counters against 512 KB of
+// scalars per 8192-scalar slice), and the single-pass scatter's write frontier, which made larger slices slower on full-width
+// columns, is short.  A slice grows up to MSM_SPARSE_SLICE scalars (PZ_MSM_SPARSE_SLICE overrides, for the A/B) -- the whole
+// column where it fits: then k_msm_totals is not launched at all -- while the launch keeps the 512 workgroups of msm_spt_for.
+// Measured on the 3034 advice columns of a c2 proof (profiles/sparse_sort_slice_ab.txt; hist .. scatter): 8192: 21.3 ms,
+// 32768: 17.9, the whole column of 2^17: 18.0 (device-chosen scatter and 8192, the launches without a hint: 23.7) -- beyond
+// 32768 the bookkeeping saved is small against a workgroup that walks 128 scalars per thread with four waves per SIMD.
+#ifndef MSM_SPARSE_SLICE
+#define MSM_SPARSE_SLICE (1u << 15)
+#endif
+static unsigned msm_spt_sparse(size_t n_cols, size_t n) {
+    static long env = -1;
+    if (env < 0) {
+        const char* e = getenv("PZ_MSM_SPARSE_SLICE");
+        env = e ? atol(e) : 0;
+    }
+    const size_t slice = env >= (long)SORT_SLICE && env <= (1l << 24) ? (size_t)env : (size_t)MSM_SPARSE_SLICE;
+    unsigned spt = SORT_PER_THREAD;
+    while ((size_t)SORT_THREADS * spt * 2 <= slice && (size_t)SORT_THREADS * spt < n) spt <<= 1;   // no larger than the column needs
+    while (spt > 1 && n_cols * pz_div_up(n, (size_t)SORT_THREADS * spt) < 512) spt >>= 1;
+    return spt;
+}
+
 static int msm_group(pz_ctx* ctx, const pz_bases* bases, const Fr* d_scalars, size_t nc, size_t n, size_t cs,
-                     unsigned win_lo, unsigned win_hi, unsigned chunk, G1Jac* d_out) {
+                     unsigned win_lo, unsigned win_hi, unsigned chunk, int density, G1Jac* d_out) {
     MsmP p;
     p.n = n;
     p.n_table = bases->n;
@@ -1435,8 +1462,21 @@ static int msm_group(pz_ctx* ctx, const pz_bases* bases, const Fr* d_scalars, si
     if (p.B + n * (size_t)(win_hi - win_lo) / chunk > 65535u * 256u) return PZ_ERR_CAPACITY;  // grid.y of k_msm_accumulate
     p.max_items = p.B + p.cap / chunk;
     void *hist, *offs, *heavy, *items, *entries, *partials, *na, *nb, *totals, *fold, *iord;
-    p.spt = msm_spt_for(nc, n);
+    // PZ_MSM_SCATTER=one / two force the single-pass / the two-step scatter (A/B); default: chosen on the device per launch
+    static int scatter_mode = -1;   // 0 auto, 1 one, 2 two
+    if (scatter_mode < 0) {
+        const char* e = getenv("PZ_MSM_SCATTER");
+        scatter_mode = (e && !strcmp(e, "one")) ? 1 : (e && !strcmp(e, "two")) ? 2 : 0;
+    }
+    // the caller's density hint (pz_msm_g1_dev_ex) picks launches and slice sizes of a COLUMN BATCH, never results: either scatter
+    // sorts any column, a wrong hint only costs time.  The few-column path and a forced variant (above) ignore it.
+    const bool batch = nc > MSM_SLICE_MAX_COLS;
+    const bool hint_sparse = batch && scatter_mode == 0 && density == PZ_MSM_SPARSE;
+    const bool hint_dense = batch && scatter_mode == 0 && density == PZ_MSM_DENSE;
+    p.spt = hint_sparse ? msm_spt_sparse(nc, n) : msm_spt_for(nc, n);
     const unsigned n_slices = pz_div_up(n, (size_t)SORT_THREADS * p.spt);
+    // a sparse column in ONE slice: its histogram is the column's totals and every slice offset is zero -- no k_msm_totals
+    const bool one_slice = hint_sparse && n_slices == 1;
     PZCHK(pz_ws_get(ctx, WS_HIST, nc * (size_t)n_slices * p.B * 4, &hist));
     PZCHK(pz_ws_get(ctx, WS_CURSOR, nc * (size_t)(p.B + 1) * 4, &heavy));
     // few columns: k_msm_totals_few / k_msm_items_few instead of k_msm_totals / k_msm_scan (one workgroup per column)
@@ -1456,15 +1496,9 @@ static int msm_group(pz_ctx* ctx, const pz_bases* bases, const Fr* d_scalars, si
     PZCHK(pz_ws_get(ctx, WS_OFFS, nc * (p.B + 1) * 4, &offs));
     PZCHK(pz_ws_get(ctx, WS_ITEMS, nc * (p.B + 1) * 4, &items));
     PZCHK(pz_ws_get(ctx, WS_ENTRIES, nc * p.cap * 4 + 16, &entries));
-    // PZ_MSM_SCATTER=one / two force the single-pass / the two-step scatter (A/B); default: chosen on the device per launch
-    static int scatter_mode = -1;   // 0 auto, 1 one, 2 two
-    if (scatter_mode < 0) {
-        const char* e = getenv("PZ_MSM_SCATTER");
-        scatter_mode = (e && !strcmp(e, "one")) ? 1 : (e && !strcmp(e, "two")) ? 2 : 0;
-    }
     // the staged entry holds a 24-bit table index; a few columns have too few slices for the 256-thread coarse step (a rank's
     // 2^19-point share of c4: 110 + 41 us against 111 for the single pass) unless forced
-    const bool two_pass = scatter_mode != 1 && p.c == 16 && (size_t)p.nwin * p.n_table <= ((size_t)1 << 24) &&
+    const bool two_pass = scatter_mode != 1 && !hint_sparse && p.c == 16 && (size_t)p.nwin * p.n_table <= ((size_t)1 << 24) &&
                           (nc > MSM_SLICE_MAX_COLS || scatter_mode == 2);
     {
         const size_t part_bytes = nc * p.max_items * sizeof(G1X29Raw), stage_bytes = two_pass ? nc * p.cap * 4 + 16 : 0;
@@ -1493,15 +1527,18 @@ static int msm_group(pz_ctx* ctx, const pz_bases* bases, const Fr* d_scalars, si
                                (const u32*)blk_itm, (const u32*)blk_bins, (u32*)offs, (u32*)items, item_order, item_bucket,
                                (unsigned long long*)dsel);
         } else {
-            hipLaunchKernelGGL(k_msm_totals, dim3(pz_div_up(p.B, 256), (unsigned)nc), dim3(256), 0, st, (u32*)hist, n_slices, p,
-                               (u32*)totals);
-            hipLaunchKernelGGL(k_msm_scan, dim3((unsigned)nc), dim3(SCAN_THREADS), 0, st, (const u32*)totals, p, (u32*)offs, (u32*)items,
-                               (u32*)heavy, heavy_cnt, (u32*)fold, fold_cnt, item_order, item_bucket, (unsigned long long*)dsel);
+            if (!one_slice)
+                hipLaunchKernelGGL(k_msm_totals, dim3(pz_div_up(p.B, 256), (unsigned)nc), dim3(256), 0, st, (u32*)hist, n_slices, p,
+                                   (u32*)totals);
+            hipLaunchKernelGGL(k_msm_scan, dim3((unsigned)nc), dim3(SCAN_THREADS), 0, st, (const u32*)(one_slice ? hist : totals), p,
+                               (u32*)offs, (u32*)items, (u32*)heavy, heavy_cnt, (u32*)fold, fold_cnt, item_order, item_bucket,
+                               (unsigned long long*)dsel);
         }
-        // dense launch (>= 0.4 of the digits non-zero: full-width scalars) -> two-step; sparse (witness columns) -> single pass
+        // dense launch (>= 0.4 of the digits non-zero: full-width scalars) -> two-step; sparse (witness columns) -> single pass.
+        // With a hint only the hinted variant is queued, and thr makes it take the launch whatever the digit total is.
         ScatterSel sel;
         sel.total = (const unsigned long long*)dsel;
-        sel.thr = !two_pass ? ~0ull : scatter_mode == 2 ? 0ull : (unsigned long long)(0.4 * (double)nc * (double)p.cap);
+        sel.thr = !two_pass ? ~0ull : (scatter_mode == 2 || hint_dense) ? 0ull : (unsigned long long)(0.4 * (double)nc * (double)p.cap);
         sel.err = ctx->async_err_d;
         if (two_pass) {
             // the staging list lives in the partial sums' buffer: k_msm_accumulate writes those after the list is consumed
@@ -1510,9 +1547,9 @@ static int msm_group(pz_ctx* ctx, const pz_bases* bases, const Fr* d_scalars, si
             hipLaunchKernelGGL(k_msm_scatter_fine, dim3(p.B >> SORT_FINE_LOG, (unsigned)nc), dim3(FINE_THREADS), 0, st, p, (const u32*)offs,
                                (const u32*)partials, (u32*)entries, sel);
         }
-        if (scatter_mode != 2 || !two_pass)
-            hipLaunchKernelGGL(k_msm_scatter, gs, dim3(SORT_THREADS), 0, st, d_scalars, cs, p, (const u32*)hist, n_slices,
-                               (const u32*)offs, (u32*)entries, nc, sel);
+        if (!two_pass || (scatter_mode != 2 && !hint_dense))
+            hipLaunchKernelGGL(k_msm_scatter, gs, dim3(SORT_THREADS), 0, st, d_scalars, cs, p, one_slice ? (const u32*)nullptr : (const u32*)hist,
+                               n_slices, (const u32*)offs, (u32*)entries, nc, sel);
     }
     {
         pz_timer tacc(ctx, PZ_T_MSM_ACC);
@@ -1579,7 +1616,13 @@ static int msm_group(pz_ctx* ctx, const pz_bases* bases, const Fr* d_scalars, si
 
 extern "C" int pz_msm_g1_dev(pz_ctx* ctx, const pz_bases* bases, const uint64_t* d_scalars, size_t n_cols, size_t n,
                              size_t col_stride, uint32_t win_lo, uint32_t win_hi, uint64_t* d_out_jac) {
+    return pz_msm_g1_dev_ex(ctx, bases, d_scalars, n_cols, n, col_stride, win_lo, win_hi, PZ_MSM_AUTO, d_out_jac);
+}
+
+extern "C" int pz_msm_g1_dev_ex(pz_ctx* ctx, const pz_bases* bases, const uint64_t* d_scalars, size_t n_cols, size_t n,
+                                size_t col_stride, uint32_t win_lo, uint32_t win_hi, int density, uint64_t* d_out_jac) {
     if (!ctx || !bases || (n_cols && (!d_scalars || !d_out_jac))) return PZ_ERR_INVALID;
+    if (density != PZ_MSM_AUTO && density != PZ_MSM_SPARSE && density != PZ_MSM_DENSE) return PZ_ERR_INVALID;
     if (n > bases->n || win_lo > win_hi || win_hi > bases->nwin) return PZ_ERR_INVALID;
     if (col_stride % 4 || (n_cols > 1 && col_stride < 4 * n)) return PZ_ERR_INVALID;
     if (n_cols == 0) return PZ_OK;
@@ -1600,8 +1643,8 @@ extern "C" int pz_msm_g1_dev(pz_ctx* ctx, const pz_bases* bases, const uint64_t*
     const size_t digits = n * (size_t)(win_hi - win_lo);
     const unsigned chunk = msm_chunk_for(n_cols, digits, bases->c);
     const size_t part_col = (digits / chunk) * sizeof(G1X29Raw);   // shared with the two-pass scatter's staging list (4 B per digit)
-    const size_t per_col = digits * 4 + (part_col > digits * 4 ? part_col : digits * 4) + (digits / chunk) * 8 +
-                           (size_t)(1u << (bases->c - 1)) * (180 + 4 * (size_t)pz_div_up(n, (size_t)SORT_THREADS * msm_spt_for(1, n)));   // spt of the smallest group (a halved group recomputes it): an upper bound on the slices
+    size_t per_col = digits * 4 + (part_col > digits * 4 ? part_col : digits * 4) + (digits / chunk) * 8 +
+                     (size_t)(1u << (bases->c - 1)) * (180 + 4 * (size_t)pz_div_up(n, (size_t)SORT_THREADS * msm_spt_for(1, n)));   // spt of the smallest group (a halved group recomputes it): an upper bound on the slices
     // group size: sized for 288 GB of HBM -- by default up to 48 GiB of sort / partial-sum workspace per launch
     // sequence (PZ_MSM_WS_GIB overrides), so the latency-bound tree levels are paid once per ~2000 columns
     size_t ws_budget = pz_msm_ws_gib() << 30;
@@ -1623,9 +1666,19 @@ extern "C" int pz_msm_g1_dev(pz_ctx* ctx, const pz_bases* bases, const uint64_t*
     if (group == 0) group = 1;
     if (group > n_cols) group = n_cols;
     if (group > 4096) group = 4096;
+    if (density == PZ_MSM_SPARSE && group > MSM_SLICE_MAX_COLS) {
+        // a sparse batch has no staging list and the slices msm_spt_sparse gives a group of this size (a larger group has no
+        // more of them per column): size the group again from that.  A smaller last group may hold more slices per column, by
+        // the 512-workgroup rule at most ~1024 histograms (128 MB) in all.
+        const size_t slices = pz_div_up(n, (size_t)SORT_THREADS * msm_spt_sparse(group, n));
+        per_col = digits * 4 + part_col + (digits / chunk) * 8 + (size_t)(1u << (bases->c - 1)) * (180 + 4 * slices);
+        group = ws_budget / per_col;
+        if (group > n_cols) group = n_cols;
+        if (group > 4096) group = 4096;
+    }
     for (size_t c0 = 0; c0 < n_cols;) {
         const size_t nc = n_cols - c0 < group ? n_cols - c0 : group;
-        const int rc = msm_group(ctx, bases, (const Fr*)d_scalars + c0 * cs, nc, n, cs, win_lo, win_hi, chunk, (G1Jac*)d_out_jac + c0);
+        const int rc = msm_group(ctx, bases, (const Fr*)d_scalars + c0 * cs, nc, n, cs, win_lo, win_hi, chunk, density, (G1Jac*)d_out_jac + c0);
         if (rc == PZ_ERR_OOM && group > 1) {
             // the cached free-memory figure was stale (someone else allocated since): halve the group, ask again next call
             ctx->mem_avail = 0;

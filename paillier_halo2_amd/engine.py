@@ -15,6 +15,9 @@ import numpy as np
 from . import _lib
 from ._lib import PzError, VP
 
+# pz_msm_g1_dev_ex's density hint (include/pz.h PZ_MSM_*)
+MSM_AUTO, MSM_SPARSE, MSM_DENSE = 0, 1, 2
+
 
 def _np(a, shape_last: Optional[int] = None) -> np.ndarray:
     arr = np.ascontiguousarray(a, dtype=np.uint64)
@@ -261,11 +264,13 @@ class Engine:
         return out
 
     def msm_dev(self, bases: Bases, d_scalars: int, n_cols: int, n: int, col_stride_u64: int, d_out: int,
-                win_lo: int = 0, win_hi: Optional[int] = None):
+                win_lo: int = 0, win_hi: Optional[int] = None, density: Optional[int] = None):
+        """density: None (MSM_AUTO: the device picks the sort variant per launch), MSM_SPARSE (columns of short scalars) or
+        MSM_DENSE (full-width scalars) -- pz_msm_g1_dev_ex's hint: it chooses launches, never results"""
         if win_hi is None:
             win_hi = bases.n_windows
-        self._chk(self.L.pz_msm_g1_dev(self.ctx, bases.handle, VP(d_scalars), n_cols, n, col_stride_u64, win_lo,
-                                       win_hi, VP(d_out)), "pz_msm_g1_dev")
+        self._chk(self.L.pz_msm_g1_dev_ex(self.ctx, bases.handle, VP(d_scalars), n_cols, n, col_stride_u64, win_lo,
+                                          win_hi, MSM_AUTO if density is None else int(density), VP(d_out)), "pz_msm_g1_dev_ex")
 
     @staticmethod
     def msm_multi(engines: Sequence["Engine"], bases: Sequence[Bases], d_scalars: Sequence[int], n_per_ctx: Sequence[int],

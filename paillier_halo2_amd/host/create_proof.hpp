@@ -447,11 +447,13 @@ struct Session {
         phase = -1;   // in progress: re-entering or skipping ahead is refused until done(p)
     }
     void done(int p) { phase = p + 1; }
-    void commit(const pz_bases* b, const uint64_t* t, size_t count, uint64_t* out) {
+    // density: what the batch holds, for the digit sort (pz_msm_g1_dev_ex) -- the advice and permuted lookup columns are short scalars
+    // (PZ_MSM_SPARSE), everything else full-width (PZ_MSM_DENSE).  The hint chooses launches, never results.
+    void commit(const pz_bases* b, const uint64_t* t, size_t count, uint64_t* out, int density) {
         uint32_t nw = 0, cb = 0;
         size_t np = 0;
         PZP_CK(pz_bases_info(b, &np, &cb, &nw));
-        PZP_CK(pz_msm_g1_dev(cx.c, b, t, count, pk.dom.n, 4 * pk.dom.n, 0, nw, out));
+        PZP_CK(pz_msm_g1_dev_ex(cx.c, b, t, count, pk.dom.n, 4 * pk.dom.n, 0, nw, density, out));
     }
     void affine(const uint64_t* d_jac, size_t count, uint64_t* out) {   // the synchronising download of a phase's commitments
         std::vector<uint64_t> jac(12 * count);
@@ -472,7 +474,7 @@ struct Session {
             PZP_CK(pz_dev_memset(cx.c, d_cols + (W + 1) * n * 4, 0, n * 32));
             PZP_CK(pz_upload(cx.c, d_cols + (W + 1) * n * 4, instances.data(), instances.size() * 8));
         }
-        commit(pk.bl, d_cols, W, w.out12);
+        commit(pk.bl, d_cols, W, w.out12, PZ_MSM_SPARSE);
         if (after_launch) after_launch();
         affine(w.out12, W, out_affine);
         done(0);
@@ -486,8 +488,8 @@ struct Session {
         PZP_CK(pz_lookup_permute_dev(cx.c, lk_in, Lk, 4 * n, pk.table_lagrange, d.usable, pk.st.lookup_bits, w.Ap, w.Sp, 4 * n));
         blind_rows(cx, w, rng, w.Ap, Lk, n, d.usable);
         blind_rows(cx, w, rng, w.Sp, Lk, n, d.usable);
-        commit(pk.bl, w.Ap, Lk, w.out12);
-        commit(pk.bl, w.Sp, Lk, w.out12 + Lk * 12);
+        commit(pk.bl, w.Ap, Lk, w.out12, PZ_MSM_SPARSE);
+        commit(pk.bl, w.Sp, Lk, w.out12 + Lk * 12, PZ_MSM_SPARSE);
         affine(w.out12, Lk, out_inputs);
         affine(w.out12 + Lk * 12, Lk, out_tables);
         done(1);
@@ -507,9 +509,9 @@ struct Session {
                                      4 * n));
         blind_rows(cx, w, rng, w.Zl, Lk, n, u + 1);
         blind_rows(cx, w, rng, w.rnd, 1, n, 0);
-        commit(pk.bl, w.Z, S, w.out12);
-        commit(pk.bl, w.Zl, Lk, w.out12 + S * 12);
-        commit(pk.bm, w.rnd, 1, w.out12 + (S + Lk) * 12);
+        commit(pk.bl, w.Z, S, w.out12, PZ_MSM_DENSE);
+        commit(pk.bl, w.Zl, Lk, w.out12 + S * 12, PZ_MSM_DENSE);
+        commit(pk.bm, w.rnd, 1, w.out12 + (S + Lk) * 12, PZ_MSM_DENSE);
         affine(w.out12, S, out_z);
         affine(w.out12 + S * 12, Lk, out_zl);
         affine(w.out12 + (S + Lk) * 12, 1, out_random);
@@ -630,7 +632,7 @@ struct Session {
             axpy(w.gq, pzh::FR_ONE, pieces, pieces);                              // pieces[i] += q_i
             axpy(w.gq + n * 4, pzh::FR_ONE, h1, pieces + n * 4);
         }
-        commit(pk.bm, pieces, 3, w.out12);
+        commit(pk.bm, pieces, 3, w.out12, PZ_MSM_DENSE);
         affine(w.out12, 3, out_h);
         done(3);
     }
@@ -719,7 +721,7 @@ struct Session {
         }
         PZP_CK(pz_shplonk_begin_dev(cx.c, n, (uint32_t)sets.size(), set_n_polys.data(), polys.data(), set_n_points.data(), point_idx.data(), 6,
                                     points.data(), evals_flat.data(), shy.v, shv.v, w.w1, &state));
-        commit(pk.bm, w.w1, 1, w.out12);
+        commit(pk.bm, w.w1, 1, w.out12, PZ_MSM_DENSE);
         affine(w.out12, 1, out_w1);
         done(5);
     }
@@ -730,7 +732,7 @@ struct Session {
         pz_shplonk* st_ = state;
         state = nullptr;                                   // pz_shplonk_finish_dev frees it on every path
         PZP_CK(pz_shplonk_finish_dev(cx.c, st_, shu.v, w.w1, w.w2));
-        commit(pk.bm, w.w2, 1, w.out12);
+        commit(pk.bm, w.w2, 1, w.out12, PZ_MSM_DENSE);
         affine(w.out12, 1, out_w2);
         // deg h <= 3n - 4; deg (Gate y^.. + Low) / Z_H <= 2n - 3 (w.gq still holds [q_0 | q_1]): an unsatisfied gate or a product that
         // does not close shows there; deg D <= 3n - 3 (the top two coefficients of D_2): a product that breaks its recurrence on an active row

@@ -35,7 +35,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import consts
-from .engine import Bases, Engine
+from .engine import MSM_DENSE, MSM_SPARSE, Bases, Engine
 
 FR = consts.FR_R
 M = consts.fr_mont_limbs
@@ -505,16 +505,22 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
 
     eng2, split_cols = hooks.get("commit_engine"), int(hooks.get("commit_split", 512))
 
-    def commit(bases, t, count, stride_u64):
+    # what a committed batch holds, for the digit sort (Engine.msm_dev density): the advice and permuted lookup columns are short scalars,
+    # the rest full-width.  A hint chooses launches, never results; hooks["density_hints"] = False leaves every choice to the device.
+    hints = bool(hooks.get("density_hints", True))
+    SPARSE, DENSE = (MSM_SPARSE, MSM_DENSE) if hints else (None, None)
+
+    def commit(bases, t, count, stride_u64, density):
         out = _zeros(count, 12)
         if eng2 is None or count < 2 * split_cols:
-            eng.msm_dev(bases, t.data_ptr(), count, n, stride_u64, out.data_ptr())
+            eng.msm_dev(bases, t.data_ptr(), count, n, stride_u64, out.data_ptr(), density=density)
             return out
         # EXPERIMENT (hooks["commit_engine"]; measured and not adopted): column groups alternate between two contexts, so
         # that one group's memory-bound sort / latency-bound tree can run beside the other's multiplier-bound accumulation
         eng2.wait_for(eng)
         for i, c0 in enumerate(range(0, count, split_cols)):
-            (eng if i % 2 == 0 else eng2).msm_dev(bases, t[c0].data_ptr(), min(split_cols, count - c0), n, stride_u64, out[c0].data_ptr())
+            (eng if i % 2 == 0 else eng2).msm_dev(bases, t[c0].data_ptr(), min(split_cols, count - c0), n, stride_u64, out[c0].data_ptr(),
+                                                  density=density)
         eng.wait_for(eng2)
         return out
 
@@ -544,7 +550,7 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
         cols[W + 1, :n_pub] = torch.from_numpy(inst_m.view(np.int64)).to(cols.device)
     if "advice" in hooks:
         hooks["advice"](cols)
-    c_adv = commit(bl, cols, W, 4 * n)
+    c_adv = commit(bl, cols, W, 4 * n, SPARSE)
     if "after_advice_launch" in hooks:      # the caller's chance to queue independent work (the NEXT proof's witness on another context)
         hooks["after_advice_launch"]()      # while this proof's largest commitment batch runs and before the host waits for it
     (a_adv,) = tr.absorb_points(eng, c_adv)
@@ -558,7 +564,7 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
         hooks["permuted"](Ap, Sp)
     Ap[:, u:] = _random_fr(gen, Lk, n - u)
     Sp[:, u:] = _random_fr(gen, Lk, n - u)
-    c_ap, c_sp = commit(bl, Ap, Lk, 4 * n), commit(bl, Sp, Lk, 4 * n)
+    c_ap, c_sp = commit(bl, Ap, Lk, 4 * n, SPARSE), commit(bl, Sp, Lk, 4 * n, SPARSE)
     a_ap, a_sp = tr.absorb_points(eng, c_ap, c_sp)
     beta_i, gamma_i = tr.squeeze("beta"), tr.squeeze("gamma")
     beta, gamma = M(beta_i), M(gamma_i)
@@ -572,10 +578,10 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
     Zl[:, u + 1:] = _random_fr(gen, Lk, n - u - 1)
     if "products" in hooks:
         hooks["products"](Z, Zl)
-    c_z, c_zl = commit(bl, Z, S, 4 * n), commit(bl, Zl, Lk, 4 * n)
+    c_z, c_zl = commit(bl, Z, S, 4 * n, DENSE), commit(bl, Zl, Lk, 4 * n, DENSE)
     rnd = ws.rnd
     rnd.copy_(_random_fr(gen, 1, n))
-    c_rnd = commit(bm, rnd, 1, 4 * n)
+    c_rnd = commit(bm, rnd, 1, 4 * n, DENSE)
     a_z, a_zl, a_rnd = tr.absorb_points(eng, c_z, c_zl, c_rnd)
     y_i = tr.squeeze("y")
     y = M(y_i)
@@ -722,7 +728,7 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
         # the join: pieces[i] = l_active D / Z_H's + q_i
         axpy(gq[:n], 1, pieces[0], pieces[0])
         axpy(gq[n:], 1, h1, pieces[1])
-    c_h = commit(bm, pieces, d.E - 1, 4 * n)
+    c_h = commit(bm, pieces, d.E - 1, 4 * n, DENSE)
     (a_h,) = tr.absorb_points(eng, c_h)
     x_i = tr.squeeze("x")
     phase("quotient")
@@ -777,11 +783,11 @@ def create_proof(pk: ProvingKey, cols, tr, seed: Optional[int] = 0, tile: int = 
         sets.append((ptrs, idx, np.concatenate(rows)))
     w1, w2 = ws.w1, ws.w2
     state = eng.shplonk_begin_dev(n, sets, np.stack([M(p) for p in xs]), M(shy), M(shv), w1.data_ptr())
-    c_w1 = commit(bm, w1.view(1, n, 4), 1, 4 * n)
+    c_w1 = commit(bm, w1.view(1, n, 4), 1, 4 * n, DENSE)
     (a_w1,) = tr.absorb_points(eng, c_w1)
     shu = tr.squeeze("sh_u")
     eng.shplonk_finish_dev(state, M(shu), w1.data_ptr(), w2.data_ptr())
-    c_w2 = commit(bm, w2.view(1, n, 4), 1, 4 * n)
+    c_w2 = commit(bm, w2.view(1, n, 4), 1, 4 * n, DENSE)
     eng.sync()
     phase("multiopen")
     # ---- the proof (the affine forms are the ones the transcript absorbed phase by phase: normalised once)

@@ -56,6 +56,9 @@ extern "C" {
                            n_cols: usize, n: usize, out_jac: *mut u64) -> c_int;
     pub fn pz_msm_g1_dev(ctx: *mut pz_ctx, bases: *const pz_bases, d_scalars: *const u64, n_cols: usize,
                          n: usize, col_stride: usize, win_lo: u32, win_hi: u32, d_out_jac: *mut u64) -> c_int;
+    pub fn pz_msm_g1_dev_ex(ctx: *mut pz_ctx, bases: *const pz_bases, d_scalars: *const u64, n_cols: usize,
+                            n: usize, col_stride: usize, win_lo: u32, win_hi: u32, density: c_int,
+                            d_out_jac: *mut u64) -> c_int;   // density: PZ_MSM_AUTO 0 / PZ_MSM_SPARSE 1 / PZ_MSM_DENSE 2
     pub fn pz_g1_sum(ctx: *mut pz_ctx, jac: *const u64, n: usize, out_jac: *mut u64) -> c_int;
     pub fn pz_g1_sum_dev(ctx: *mut pz_ctx, d_jac: *const u64, n: usize, d_out_jac: *mut u64) -> c_int;
     pub fn pz_msm_g1_multi(ctxs: *const *mut pz_ctx, bases: *const *const pz_bases, d_scalars: *const *const u64, n_per_ctx: *const usize,
