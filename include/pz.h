@@ -326,6 +326,34 @@ int pz_paillier_wtally(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_b
 int pz_paillier_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
                            const uint64_t* weights, uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out);
 
+/* Decryption with randomness recovery, for the key holder.  The secret key is a handle: n, g, lambda and d = n^-1 mod lambda
+ * (HOST words, limbs_n each; d is the caller's -- paillier_halo2_amd/keys.py::secret_from_primes computes it).
+ *   pz_paillier_sk_create  forms n^2 and the Barrett constants of n^2 and of n once, derives on the device x = L(g^lambda mod n^2),
+ *       mu = x^(lambda-1) mod n and ginv = (g mod n)^(lambda-1) mod n (both orders divide lambda: no inversion routine), and checks
+ *       g^lambda mod n^2 = 1 (mod n), x mu = 1 (mod n), n d = 1 (mod lambda) and 0 < d < lambda < n: anything else is PZ_ERR_INVALID
+ *       (lambda + 1, d + 1, g = 1 ...).  n = 0: PZ_ERR_ZERO_MODULUS; 2 * limbs_n > 128: PZ_ERR_UNSUPPORTED.  Synchronises.  The staging
+ *       copies of lambda - 1 and x in the shared workspaces are overwritten before it returns.
+ *   pz_paillier_sk_params  mu and ginv (HOST, limbs_n words each), for tests and bindings.
+ *   pz_paillier_sk_free    overwrites the handle's device memory (lambda, d, mu) in stream order, then releases it.  NULL is PZ_OK.
+ *   pz_paillier_decrypt    1 <= count <= 65536 (else PZ_ERR_INVALID) ciphertexts of 2 * limbs_n words (HOST).  Per ciphertext
+ *       u = c^lambda mod n^2; flags_out[i] bit 0 is set if u mod n != 1 (c is no unit: its m and r are written as zero), else
+ *       m = floor(u / n) mu mod n and, if r_out is not NULL, r = ((c mod n) ginv^m)^d mod n with c = g^m r^n mod n^2 (an r >= n used at
+ *       encryption comes back reduced mod n: it encrypts to the same c).  A c >= n^2 sets bit 1 of its flag, zeros its outputs and
+ *       makes the call PZ_ERR_RANGE (the other entries are still written).  m_out, r_out: count x limbs_n words; flags_out: count
+ *       bytes.  One launch per power over all ciphertexts (c^lambda; ginv^m, skipped when ginv = 1; the d-th power), a fixed-window
+ *       schedule set by limbs_n and the bit length of n alone, the table entry chosen by reading all of them under a mask.
+ *   pz_paillier_decrypt_dev  the same with DEVICE pointers, asynchronous on the context's stream: it returns once the launches are
+ *       queued, and what the host form reports as PZ_ERR_RANGE is bit 1 of an entry's flag here. */
+typedef struct pz_paillier_sk pz_paillier_sk;
+int pz_paillier_sk_create(pz_ctx* ctx, uint32_t limbs_n, const uint64_t* n, const uint64_t* g, const uint64_t* lambda,
+                          const uint64_t* d, pz_paillier_sk** out);
+int pz_paillier_sk_params(const pz_paillier_sk* sk, uint64_t* mu_out, uint64_t* ginv_out);
+int pz_paillier_sk_free(pz_ctx* ctx, pz_paillier_sk* sk);
+int pz_paillier_decrypt(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* cts, uint64_t* m_out, uint64_t* r_out,
+                        uint8_t* flags_out);
+int pz_paillier_decrypt_dev(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* d_cts, uint64_t* d_m_out,
+                            uint64_t* d_r_out, uint8_t* d_flags_out);
+
 /* ---------------------------------------------------------------------------------------------
  * K4 -- expansion of a step trace into advice-column cells (Fr Montgomery, 32 B each), i.e. the
  * values halo2-lib's Context would hold after BigUintChip emitted the constraints of every
@@ -361,7 +389,10 @@ int pz_witness_expand_dev(pz_ctx* ctx, uint32_t limbs, uint32_t limb_bits, uint3
  * (n_steps_g must be a multiple of 2 B and W in 1 .. 64, else PZ_ERR_INVALID): assign_integer(n); assign_integer(c_i, 2*enc_bits) for
  * i = 1..B; load_witness(w_i) for i = 1..B (B consecutive cells, no gate); square + refresh of n, once; per ciphertext
  * assign_constant(1), load_zero, num_to_bits(w_i, W) (7 W - 2 cells, tied to the load_witness cell) and W blocks of mul_mod(acc, sq),
- * limb-wise select, square_mod(sq); the B - 1 mul_mod blocks of the tree over the powers; assign_integer(res); assert_equal_fresh. */
+ * limb-wise select, square_mod(sq); the B - 1 mul_mod blocks of the tree over the powers; assign_integer(res); assert_equal_fresh.
+ * kind = 5: "decrypt" -- kind 2's circuit cell for cell from the same records (x = the plaintext m, y = the recovered randomness r of
+ * pz_paillier_decrypt); its STATEMENT alone differs (pz_circuit_public_cells: n | g | m | c).  Accepted wherever kind 2 is:
+ * pz_circuit_cells, pz_circuit_expand[_cols]_dev, pz_circuit_public_cells, pz_circuit_structure_dev (exp_g ignored, exp_r = n). */
 int pz_circuit_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g,
                      size_t n_steps_r, size_t* advice_cells, size_t* lookup_cells);
 /* inputs (HOST): n | g | x | y as ceil(limbs_n*limb_bits/64) 64-bit words each, then res as ceil(2*limbs_n*limb_bits/64)
@@ -922,6 +953,8 @@ int pz_proof_free(pz_proof* proof);
  *     n[limbs_n] | c_1[2 limbs_n] | .. | c_B[2 limbs_n] | C[2 limbs_n].  Kind 4 (weighted tally of B = n_steps_r + 1): n | c_1 | .. | c_B |
  *     w_1 | .. | w_B | C, a weight being ONE value (its load_witness cell), n_public = limbs_n + (B + 1) 2 limbs_n + B.  (Kind 0 bakes the message's bits into the
  *     key's shape -- the reference's property; kind 2, the uniform-shape circuit, is the zero-knowledge statement.)
+ *     Kind 5 (decrypt): n[limbs_n] | g[limbs_n] | m[limbs_n] | c[2 limbs_n], n_public = 5 limbs_n -- "c decrypts to m": there is an r with
+ *     c = g^m r^n mod n^2.  The circuit does not compare m with n: the verifier must, on the two public values (m >= n says nothing).
  * pz_circuit_public_cells  host only: the stream indices of the exposed advice cells in that order (arguments as pz_circuit_cells).
  *                cells_out may be NULL (count only); PZ_ERR_CAPACITY if capacity < *n_public.
  * pz_structure_expose      adds the column to a structure: the exposed cells' (column, row) through the break-point table, the instance

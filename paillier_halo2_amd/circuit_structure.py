@@ -300,7 +300,7 @@ class StructureArrays:
     n_steps_g: int
     n_steps_r: int
     # stream indices of the cells a circuit with the instance column exposes, in the column's row order: the limb cells of
-    # n | g | c (encrypt, encrypt_uniform), n | g | c1 | c2 | c (add), n | c_1 | .. | c_B | C (tally) or n | c_1 | .. | c_B | w_1 | .. |
+    # n | g | c (encrypt, encrypt_uniform), n | g | m | c (decrypt), n | g | c1 | c2 | c (add), n | c_1 | .. | c_B | C (tally) or n | c_1 | .. | c_B | w_1 | .. |
     # w_B | C (wtally: a weight is ONE cell) -- pz_circuit_public_cells gives the same list
     public_cells: Optional[np.ndarray] = None
 
@@ -317,7 +317,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     full-width ciphertexts multiplied in layout.tally_tree's order, no exponents -- the shape is B and the key
     size alone; kind 'wtally': count = B full-width ciphertexts, each raised to a w_bits-bit weight held in ONE witness cell (pow_mod
     over in-circuit bits, the uniform circuit's block), the powers multiplied in layout.wtally_tree's order
-    -- the shape is B, w_bits and the key size alone.
+    -- the shape is B, w_bits and the key size alone; kind 'decrypt': 'encrypt_uniform' with the message's limb cells exposed between
+    g's and the result's (the statement n | g | m | c).
     device: None -> numpy arrays; a torch device ("cuda") -> the template is tiled THERE and `src` / `lookup_src` are tensors on it (at
     config c2 the tiled arrays are 3.2 GB: 0.9 s of host numpy against a few ms; `columns` takes either)."""
     dev = None
@@ -352,8 +353,10 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             constants.append(v)
         return const_id[v]
 
-    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally"):
+    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt"):
         raise ValueError(f"unknown circuit kind {kind!r}")
+    # 'decrypt' (circuit kind 5) is the uniform-shape circuit cell for cell: the exposed list alone differs
+    statement, kind = kind, ("encrypt_uniform" if kind == "decrypt" else kind)
     if (kind in ("tally", "wtally")) != (count is not None):
         raise ValueError("count belongs to kinds 'tally' and 'wtally', which need it")
     if (kind == "wtally") != (w_bits is not None):
@@ -595,7 +598,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     if kind in ("tally", "wtally"):
         exposed = list(n_c) + [c for ct in ct_c for c in ct] + list(wt_c) + list(res_c)
     else:
-        exposed = list(n_c) + list(g_c) + (list(x_c) + list(y_c) if kind == "add" else []) + list(res_c)
+        mid = list(x_c) + list(y_c) if kind == "add" else list(x_c) if statement == "decrypt" else []
+        exposed = list(n_c) + list(g_c) + mid + list(res_c)
     return StructureArrays(n_cells=off, src=src, gate_mask=np.concatenate(parts_mask), lookup_src=lookup_src,
                            constants=constants, result_cell=eq_cell, n_steps_g=n_steps[0], n_steps_r=n_steps[1],
                            public_cells=np.asarray(exposed, dtype=np.int64))

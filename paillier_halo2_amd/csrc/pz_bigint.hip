@@ -904,17 +904,17 @@ template <int E> __global__ __launch_bounds__(64) void k_mul_mod(const MulDesc* 
 // `elems + e * stride` for e < n_regular (level 0: the ciphertext array; above: the remainders of the records one level down) and
 // `tail` for the odd element carried up without a product; it writes its own record in place.  The Barrett constants of n^2 are
 // computed once (k_tally_setup: the reciprocal is 64 * 64 * E steps of restoring division) and read by every workgroup:
-// mod = M' | mu | n^2 (C words each) | shift | ok.
-template <int E> __global__ __launch_bounds__(64) void k_tally_setup(const u64* __restrict__ n, unsigned Ln, u64* __restrict__ mod,
-                                                                      u32* __restrict__ status) {
+// mod = M' | mu | n^2 (C words each) | shift | ok.  (square = 0: the same block for n itself -- the decryption's second modulus.)
+template <int E> __global__ __launch_bounds__(64) void k_tally_setup(const u64* __restrict__ n, unsigned Ln, unsigned square,
+                                                                      u64* __restrict__ mod, u32* __restrict__ status) {
     constexpr unsigned C = 64 * E;
     __shared__ u64 s_scratch[2 * C];
     BarrettCtx<E> B;
     B.sm = s_scratch;
-    B.limbs = 2 * Ln;
+    B.limbs = square ? 2 * Ln : Ln;
     B.s = 0;
-    LD<E> m = ld_load<E>(n, Ln), lo, hi;
-    ld_mul(lo, hi, m, m);
+    LD<E> m = ld_load<E>(n, Ln), lo = m, hi;
+    if (square) ld_mul(lo, hi, m, m);
     const bool ok = barrett_setup(B, lo);
     if (ok) {
         ld_store(mod, B.M, C);
@@ -1449,8 +1449,8 @@ static int tally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, const uint64_t* n,
     const u64* root = nullptr;
     {
         pz_timer tm(ctx, PZ_T_TRACE);
-        if (C == 64) hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
-        else hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
+        if (C == 64) hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod, d_status);
+        else hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod, d_status);
         HIPCHK(ctx, hipGetLastError());
         PZCHK(tally_levels(ctx, C, d_mod, d_cts, count, L, d_steps, d_status, &root));
     }
@@ -1520,11 +1520,11 @@ static int wtally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t w_bits, 
     {
         pz_timer tm(ctx, PZ_T_TRACE);
         if (C == 64) {
-            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
+            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod, d_status);
             hipLaunchKernelGGL(k_wtally_pow<1>, dim3((unsigned)count), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, d_cts, d_w, w_bits, d_steps,
                                d_pow, L, d_status);
         } else {
-            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, d_mod, d_status);
+            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod, d_status);
             hipLaunchKernelGGL(k_wtally_pow<2>, dim3((unsigned)count), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, d_cts, d_w, w_bits, d_steps,
                                d_pow, L, d_status);
         }
@@ -1546,4 +1546,397 @@ extern "C" int pz_paillier_wtally(pz_ctx* ctx, uint32_t limbs_n, size_t count, u
 extern "C" int pz_paillier_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
                                       const uint64_t* weights, uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out) {
     return wtally_impl(ctx, limbs_n, count, w_bits, n, cts, weights, d_steps_out, 1, steps_cap, c_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// decryption (pz_paillier_sk_*, pz_paillier_decrypt[_dev])
+// ------------------------------------------------------------------------------------------------
+// The powers of a decryption carry SECRET exponents (lambda, d, the plaintext), and nothing of them is proved, so no records are written
+// and the schedule is a fixed-window one: the exponent is cut into ceil(nbits / w) windows of w bits, most significant first, nbits the
+// bit length of n (public); every window below the top one does w squarings and ONE product by a table entry (the table's 1 for a zero
+// window).  The table base^0 .. base^(2^w - 1) lives in the team's LDS; an entry is chosen by reading ALL 2^w entries and keeping one
+// lane-wise under a mask, so neither the instruction stream nor an address depends on the exponent.  (What a mul_mod does with its
+// VALUES is K3's as everywhere: the Barrett correction's trip count follows the operands.)  One team per chain, one launch per power
+// over all chains, no ticket, no spin, no hand-off: k_wtally_pow's shape.
+// Entry flags: bit 0 the ciphertext is no unit (c^lambda mod n != 1), bit 1 it is >= n^2, bit 2 an internal check failed.
+#define K3_DEC_WINDOW 5   // 64 decryptions with r at 2048 bits: 59.0 ms against 60.5 (w = 4) and 95.7 (w = 1), profiles/decrypt_probe.jsonl
+enum { DEC_POW = 0, DEC_LFN = 1 };
+enum { DEC_F_NOT_UNIT = 1, DEC_F_RANGE = 2, DEC_F_INTERNAL = 4 };
+struct DecPow {
+    const u64* modP;     // Barrett block (k_tally_setup's layout at THIS instantiation's capacity) of the power's modulus
+    const u64* modN;     // DEC_LFN: the same for n
+    const u64* base;     // chain i: base + i * base_stride, base_limbs limbs, below the modulus
+    const u64* exp;      // chain i: exp + i * exp_stride, exp_limbs limbs, below 2^nbits
+    const u64* aux;      // DEC_POW, may be null: the power is multiplied by aux + i * Lp (mod the modulus)
+    const u64* mu;       // DEC_LFN: Ln limbs
+    u64 *out0, *out1;    // DEC_POW: out0 + i * Lp the power (zero where flags[i] != 0).  DEC_LFN: out0 + i * Ln the plaintext
+                         // floor(u / n) * mu mod n (zero where flagged), out1 + i * Ln the base mod n
+    uint8_t* flags;      // DEC_POW: read (may be null); DEC_LFN: written
+    size_t base_stride, exp_stride;
+    u32 base_limbs, exp_limbs, nbits, w, mode, Lp, Ln;
+};
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_dec_pow(const DecPow A) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    extern __shared__ u64 s_table[];   // 2^w entries of Lp limbs
+    if (A.modP[3 * C + 1] == 0) return;   // zero modulus (pz_paillier_sk_create refuses it: no handle reaches here with one)
+    const unsigned wave = threadIdx.x >> 6, lane = lane_id();
+    TeamCtx<E> T;
+    T.buf = s_team;
+    T.w = wave;
+    T.parity = 0;
+    TeamMul<E> tmul{&T};
+    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
+        u64* z = (u64*)s_team;
+        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
+        __syncthreads();
+    }
+    BarrettCtx<E> B;
+    B.sm = s_scratch[wave];
+    B.limbs = A.Lp;
+    B.s = (unsigned)A.modP[3 * C];
+    B.M = ld_load<E>(A.modP, C);
+    B.mu = ld_load<E>(A.modP + C, C);
+    const size_t chain = blockIdx.x;
+    const unsigned Lp = A.Lp, Ln = A.Ln, nent = 1u << A.w;
+    const LD<E> base = ld_load<E>(A.base + chain * A.base_stride, A.base_limbs);
+    {   // a base >= the modulus (a ciphertext >= n^2: public).  The four waves hold the same values: the team leaves together
+        LD<E> d;
+        if (!ld_sub(d, base, ld_load<E>(A.modP + 2 * C, C))) {
+            if (wave == 0) {
+                const unsigned Lo = A.mode == DEC_LFN ? Ln : Lp;
+                ld_store(A.out0 + chain * Lo, ld_zero<E>(), Lo);
+                if (A.mode == DEC_LFN) {
+                    ld_store(A.out1 + chain * Lo, ld_zero<E>(), Lo);
+                    if (lane == 0) A.flags[chain] = DEC_F_RANGE;
+                }
+            }
+            return;
+        }
+    }
+    unsigned st = ST_OK;
+    const LD<E> one = ld_small<E>(1);
+    {   // the table: entry k = base^k
+        LD<E> cur = one;
+        for (unsigned k = 0; k < nent; ++k) {
+            if (wave == 0) ld_store(s_table + (size_t)k * Lp, cur, Lp);
+            if (k + 1 < nent) {
+                LD<E> q, r;
+                st |= mul_mod(B, q, r, cur, base, tmul);
+                cur = r;
+            }
+        }
+        __syncthreads();
+    }
+    const u64* ex = A.exp + chain * A.exp_stride;
+    // window at bit p (a position: public), and the entry it names, read under a mask from all of them
+    auto pick = [&](unsigned p) {
+        const unsigned wi = p >> 6, sh = p & 63;
+        const u64 lo = wi < A.exp_limbs ? ex[wi] : 0, hi = wi + 1 < A.exp_limbs ? ex[wi + 1] : 0;
+        u64 v = lo >> sh;
+        if (sh) v |= hi << (64 - sh);
+        u32 idx = (u32)v & (nent - 1);
+        asm volatile("" : "+v"(idx));   // a per-lane value from here on: nothing below can become a branch or an address
+        LD<E> r = ld_zero<E>();
+        for (unsigned k = 0; k < nent; ++k) {
+            const u64 keep = 0ull - (u64)(idx == k);
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const unsigned t = lane * E + e;
+                const u64 v2 = t < Lp ? s_table[(size_t)k * Lp + t] : 0;
+                r.v[e] |= v2 & keep;
+            }
+        }
+        return r;
+    };
+    const unsigned nwin = (A.nbits + A.w - 1) / A.w;
+    LD<E> acc = pick((nwin - 1) * A.w);
+    for (unsigned i = nwin - 1; i-- > 0;) {
+        LD<E> q, r;
+        for (unsigned s = 0; s < A.w; ++s) {
+            st |= mul_mod(B, q, r, acc, acc, tmul);
+            acc = r;
+        }
+        st |= mul_mod(B, q, r, acc, pick(i * A.w), tmul);
+        acc = r;
+    }
+    if (A.mode == DEC_POW) {
+        if (A.aux) {
+            LD<E> q, r;
+            st |= mul_mod(B, q, r, acc, ld_load<E>(A.aux + chain * Lp, Lp), tmul);
+            acc = r;
+        }
+        if (A.flags && A.flags[chain]) acc = ld_zero<E>();
+        if (wave == 0) ld_store(A.out0 + chain * Lp, acc, Lp);
+        if (st && A.flags && wave == 0 && lane == 0) A.flags[chain] |= DEC_F_INTERNAL;   // (the key derivation passes none: its checks catch a wrong mu)
+        return;
+    }
+    // u = acc = c^lambda mod n^2: u mod n must be 1; plaintext = floor(u / n) * mu mod n
+    BarrettCtx<E> N;
+    N.sm = s_scratch[wave];
+    N.limbs = Lp;
+    N.s = (unsigned)A.modN[3 * C];
+    N.M = ld_load<E>(A.modN, C);
+    N.mu = ld_load<E>(A.modN + C, C);
+    LD<E> x, rem, q, m, cn;
+    st |= mul_mod(N, x, rem, acc, one, tmul);
+    bool ne = false;
+#pragma unroll
+    for (int e = 0; e < E; ++e) ne |= rem.v[e] != one.v[e];
+    const bool bad = __ballot(ne) != 0;
+    st |= mul_mod(N, q, m, x, ld_load<E>(A.mu, Ln), tmul);
+    st |= mul_mod(N, q, cn, base, one, tmul);
+    if (bad) m = ld_zero<E>();
+    if (wave == 0) {
+        ld_store(A.out0 + chain * Ln, m, Ln);
+        ld_store(A.out1 + chain * Ln, cn, Ln);
+        if (lane == 0) A.flags[chain] = (uint8_t)((bad ? DEC_F_NOT_UNIT : 0) | (st ? DEC_F_INTERNAL : 0));
+    }
+}
+
+// The key handle.  One device block: Barrett constants of n^2 (at the capacity C of 2 * limbs_n limbs), of n at C and of n at 64
+// limbs (the powers mod n always fit one limb per lane: limbs_n <= 64), then n | lambda | d | mu | ginv.  mu and ginv are kept on the
+// host as well (pz_paillier_sk_params has no context to fetch them with).
+struct pz_paillier_sk {
+    uint32_t Ln = 0, nbits = 0;
+    unsigned C = 64;
+    u64* d_block = nullptr;
+    size_t block_bytes = 0;
+    u64 *d_mod2 = nullptr, *d_modn_c = nullptr, *d_modn = nullptr, *d_n = nullptr, *d_lam = nullptr, *d_d = nullptr, *d_mu = nullptr, *d_ginv = nullptr;
+    std::vector<u64> h_mu, h_ginv;
+    bool ginv_one = false;
+};
+static unsigned dec_window() {   // PZ_K3_DEC_WINDOW (1 .. 5) is a measurement hook, honoured only with PZ_K3_TEST_HOOKS=1 like the others
+    const char* on = getenv("PZ_K3_TEST_HOOKS");
+    if (!(on && on[0] == '1')) return K3_DEC_WINDOW;
+    const unsigned w = env_u32("PZ_K3_DEC_WINDOW", K3_DEC_WINDOW);
+    return w >= 1 && w <= 5 ? w : K3_DEC_WINDOW;
+}
+static int launch_dec_pow(pz_ctx* ctx, unsigned C, size_t chains, const DecPow& a) {
+    const size_t table = ((size_t)8 << a.w) * a.Lp;
+    if (C == 64) hipLaunchKernelGGL(k_dec_pow<1>, dim3((unsigned)chains), dim3(64 * K3_TEAM), table, ctx->stream, a);
+    else hipLaunchKernelGGL(k_dec_pow<2>, dim3((unsigned)chains), dim3(64 * K3_TEAM), table, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+static int cmp_limbs(const uint64_t* a, const uint64_t* b, uint32_t n) {
+    for (uint32_t i = n; i-- > 0;)
+        if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+    return 0;
+}
+static bool is_small(const uint64_t* a, uint32_t n, uint64_t v) {
+    for (uint32_t i = 1; i < n; ++i)
+        if (a[i]) return false;
+    return a[0] == v;
+}
+// overwrite in stream order, then release (pz_dev_free waits for the queued work)
+static int sk_release(pz_ctx* ctx, pz_paillier_sk* sk) {
+    int rc = PZ_OK;
+    if (sk->d_block) {
+        if (hipMemsetAsync(sk->d_block, 0, sk->block_bytes, ctx->stream) != hipSuccess) rc = PZ_ERR_HIP;
+        const int rf = pz_dev_free(ctx, sk->d_block);
+        if (rc == PZ_OK) rc = rf;
+    }
+    std::fill(sk->h_mu.begin(), sk->h_mu.end(), 0);
+    std::fill(sk->h_ginv.begin(), sk->h_ginv.end(), 0);
+    delete sk;
+    return rc;
+}
+static int sk_create_impl(pz_ctx* ctx, pz_paillier_sk* sk, const uint64_t* n, const uint64_t* g, const uint64_t* lambda, const uint64_t* d) {
+    const uint32_t Ln = sk->Ln;
+    const unsigned L = 2 * Ln, C = sk->C;
+    const size_t nb = (size_t)Ln * 8, blk = (size_t)3 * C + 2, blk1 = 3 * 64 + 2;
+    sk->block_bytes = (2 * blk + blk1 + 5 * (size_t)Ln) * 8;
+    void* dv;
+    PZCHK(pz_dev_alloc(ctx, sk->block_bytes, &dv));
+    sk->d_block = (u64*)dv;
+    sk->d_mod2 = sk->d_block;
+    sk->d_modn_c = sk->d_mod2 + blk;
+    sk->d_modn = C == 64 ? sk->d_modn_c : sk->d_modn_c + blk;
+    sk->d_n = sk->d_modn_c + blk + blk1;
+    sk->d_lam = sk->d_n + Ln;
+    sk->d_d = sk->d_lam + Ln;
+    sk->d_mu = sk->d_d + Ln;
+    sk->d_ginv = sk->d_mu + Ln;
+    // staging (shared workspace, overwritten below): g | lambda - 1 | 1 | x | g mod n | x mu mod n | n d mod lambda | flag | status | descs
+    std::vector<u64> lam1(lambda, lambda + Ln), one(Ln, 0);
+    for (uint32_t i = 0; i < Ln && lam1[i]-- == 0; ++i) {}
+    one[0] = 1;
+    const size_t stage_bytes = 7 * nb + 128 + 2 * sizeof(MulDesc);
+    void* ws;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, stage_bytes, &ws));
+    char* p = (char*)ws;
+    u64 *s_g = (u64*)p, *s_lam1 = s_g + Ln, *s_one = s_lam1 + Ln, *s_x = s_one + Ln, *s_gn = s_x + Ln, *s_c1 = s_gn + Ln, *s_c2 = s_c1 + Ln;
+    uint8_t* s_flag = (uint8_t*)(p + 7 * nb);
+    u32* s_status = (u32*)(p + 7 * nb + 64);
+    MulDesc* s_desc = (MulDesc*)(p + 7 * nb + 128);
+    struct Wipe {   // on every path out: the staging copies are overwritten and the queue drained (lam1 goes through pageable memory)
+        pz_ctx* c; void* p; size_t n; std::vector<u64>& h;
+        ~Wipe() {
+            (void)hipMemsetAsync(p, 0, n, c->stream);
+            (void)hipStreamSynchronize(c->stream);
+            std::fill(h.begin(), h.end(), 0);
+        }
+    } wipe{ctx, ws, stage_bytes, lam1};
+    HIPCHK(ctx, hipMemsetAsync(p + 7 * nb, 0, 128, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(sk->d_n, n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(sk->d_lam, lambda, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(sk->d_d, d, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s_g, g, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s_lam1, lam1.data(), nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s_one, one.data(), nb, hipMemcpyHostToDevice, ctx->stream));
+    if (C == 64) {
+        hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 1u, sk->d_mod2, s_status);
+        hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 0u, sk->d_modn_c, s_status);
+    } else {
+        hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 1u, sk->d_mod2, s_status);
+        hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 0u, sk->d_modn_c, s_status);
+        hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 0u, sk->d_modn, s_status);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    const unsigned w = dec_window();
+    DecPow a{};
+    // x = L(g^lambda mod n^2) (the plaintext of g under mu = 1), g mod n, and the flag g^lambda mod n != 1
+    a.modP = sk->d_mod2; a.modN = sk->d_modn_c; a.base = s_g; a.base_limbs = Ln; a.exp = sk->d_lam; a.exp_limbs = Ln; a.mu = s_one;
+    a.out0 = s_x; a.out1 = s_gn; a.flags = s_flag; a.nbits = sk->nbits; a.w = w; a.mode = DEC_LFN; a.Lp = L; a.Ln = Ln;
+    PZCHK(launch_dec_pow(ctx, C, 1, a));
+    // mu = x^(lambda - 1), ginv = (g mod n)^(lambda - 1) mod n: both orders divide lambda
+    DecPow b{};
+    b.modP = sk->d_modn; b.base = s_x; b.base_stride = Ln; b.base_limbs = Ln; b.exp = s_lam1; b.exp_limbs = Ln; b.out0 = sk->d_mu;
+    b.nbits = sk->nbits; b.w = w; b.mode = DEC_POW; b.Lp = Ln; b.Ln = Ln;
+    PZCHK(launch_dec_pow(ctx, 64, 2, b));
+    // x mu mod n and n d mod lambda, both to be 1
+    MulDesc md[2] = {};
+    md[0].a = s_x; md[0].b = sk->d_mu; md[0].modulus = sk->d_n; md[0].r = s_c1;
+    md[1].a = sk->d_n; md[1].b = sk->d_d; md[1].modulus = sk->d_lam; md[1].r = s_c2;
+    for (auto& m : md) {
+        m.status = s_status;
+        m.limbs_a = m.limbs_b = m.limbs_mod = m.L = Ln;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(s_desc, md, sizeof md, hipMemcpyHostToDevice, ctx->stream));
+    PZCHK(launch_muls(ctx, s_desc, 2, Ln));
+    std::vector<u64> c1(Ln), c2(Ln);
+    sk->h_mu.assign(Ln, 0);
+    sk->h_ginv.assign(Ln, 0);
+    uint8_t flag = 0;
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(c1.data(), s_c1, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(c2.data(), s_c2, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(sk->h_mu.data(), sk->d_mu, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(sk->h_ginv.data(), sk->d_ginv, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&flag, s_flag, 1, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&st, s_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    PZCHK(status_to_rc(ctx, st));
+    if (flag & DEC_F_INTERNAL) {
+        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: internal consistency check failed (key derivation)");
+        return PZ_ERR_HIP;
+    }
+    if (flag || !is_small(c1.data(), Ln, 1) || !is_small(c2.data(), Ln, 1)) return PZ_ERR_INVALID;
+    sk->ginv_one = is_small(sk->h_ginv.data(), Ln, 1);
+    return PZ_OK;
+}
+extern "C" int pz_paillier_sk_create(pz_ctx* ctx, uint32_t limbs_n, const uint64_t* n, const uint64_t* g, const uint64_t* lambda,
+                                     const uint64_t* d, pz_paillier_sk** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !n || !g || !lambda || !d || !out || limbs_n == 0) return PZ_ERR_INVALID;
+    if (2 * (uint64_t)limbs_n > 128) return PZ_ERR_UNSUPPORTED;
+    if (is_small(n, limbs_n, 0)) return PZ_ERR_ZERO_MODULUS;
+    // 0 < d < lambda < n: what fixes the powers' schedule at the bit length of n
+    if (is_small(lambda, limbs_n, 0) || cmp_limbs(lambda, n, limbs_n) >= 0 || cmp_limbs(d, lambda, limbs_n) >= 0) return PZ_ERR_INVALID;
+    PZ_ENTER(ctx);
+    pz_paillier_sk* sk = new pz_paillier_sk;
+    sk->Ln = limbs_n;
+    sk->C = 2 * limbs_n <= 64 ? 64 : 128;
+    for (uint32_t i = limbs_n; i-- > 0;)
+        if (n[i]) {
+            sk->nbits = i * 64 + (64 - __builtin_clzll(n[i]));
+            break;
+        }
+    const int rc = sk_create_impl(ctx, sk, n, g, lambda, d);
+    if (rc != PZ_OK) {
+        (void)sk_release(ctx, sk);
+        return rc;
+    }
+    *out = sk;
+    return PZ_OK;
+}
+extern "C" int pz_paillier_sk_params(const pz_paillier_sk* sk, uint64_t* mu_out, uint64_t* ginv_out) {
+    if (!sk || !mu_out || !ginv_out) return PZ_ERR_INVALID;
+    memcpy(mu_out, sk->h_mu.data(), (size_t)sk->Ln * 8);
+    memcpy(ginv_out, sk->h_ginv.data(), (size_t)sk->Ln * 8);
+    return PZ_OK;
+}
+extern "C" int pz_paillier_sk_free(pz_ctx* ctx, pz_paillier_sk* sk) {
+    if (!ctx) return PZ_ERR_INVALID;
+    if (!sk) return PZ_OK;
+    PZ_ENTER(ctx);
+    return sk_release(ctx, sk);
+}
+
+// m_i = L(c_i^lambda mod n^2) mu mod n and, if asked for, the randomness r_i = ((c_i mod n) ginv^m_i)^d mod n: one launch per power
+// over all ciphertexts (c^lambda; ginv^m unless ginv = 1 -- g is public; the d-th power), all on the context's stream.
+static int decrypt_impl(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* cts, uint64_t* m_out, uint64_t* r_out,
+                        uint8_t* flags_out, int on_device) {
+    if (!ctx || !sk || !cts || !m_out || !flags_out) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_TALLY_MAX) return PZ_ERR_INVALID;
+    PZ_ENTER(ctx);
+    const uint32_t Ln = sk->Ln;
+    const unsigned L = 2 * Ln;
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8;
+    // c mod n | (c mod n) ginv^m | host form: the ciphertexts, m, r, the flags
+    const size_t io_bytes = on_device ? 0 : count * (lb + 2 * nb) + ((count + 7) & ~(size_t)7);
+    void* ws;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, 2 * count * nb + io_bytes + 64, &ws));
+    u64 *d_cn = (u64*)ws, *d_v = d_cn + count * Ln;
+    const u64* d_cts = cts;
+    u64 *d_m = m_out, *d_r = r_out;
+    uint8_t* d_flags = flags_out;
+    if (!on_device) {
+        u64* q = d_v + count * Ln;
+        d_cts = q;
+        d_m = q + count * L;
+        d_r = d_m + count * Ln;
+        d_flags = (uint8_t*)(d_r + count * Ln);
+        HIPCHK(ctx, hipMemcpyAsync(q, cts, count * lb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const unsigned w = dec_window();
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        DecPow a{};
+        a.modP = sk->d_mod2; a.modN = sk->d_modn_c; a.base = d_cts; a.base_stride = L; a.base_limbs = L; a.exp = sk->d_lam; a.exp_limbs = Ln;
+        a.mu = sk->d_mu; a.out0 = d_m; a.out1 = d_cn; a.flags = d_flags; a.nbits = sk->nbits; a.w = w; a.mode = DEC_LFN; a.Lp = L; a.Ln = Ln;
+        PZCHK(launch_dec_pow(ctx, sk->C, count, a));
+        if (r_out) {
+            DecPow b{};
+            b.modP = sk->d_modn; b.base_limbs = Ln; b.exp_limbs = Ln; b.nbits = sk->nbits; b.w = w; b.mode = DEC_POW; b.Lp = Ln; b.Ln = Ln;
+            if (!sk->ginv_one) {
+                b.base = sk->d_ginv; b.exp = d_m; b.exp_stride = Ln; b.aux = d_cn; b.out0 = d_v; b.flags = d_flags;
+                PZCHK(launch_dec_pow(ctx, 64, count, b));
+            }
+            b.base = sk->ginv_one ? d_cn : d_v; b.base_stride = Ln; b.exp = sk->d_d; b.exp_stride = 0; b.aux = nullptr; b.out0 = d_r; b.flags = d_flags;
+            PZCHK(launch_dec_pow(ctx, 64, count, b));
+        }
+    }
+    if (on_device) return PZ_OK;
+    HIPCHK(ctx, hipMemcpyAsync(m_out, d_m, count * nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (r_out) HIPCHK(ctx, hipMemcpyAsync(r_out, d_r, count * nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(flags_out, d_flags, count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned any = 0;
+    for (size_t i = 0; i < count; ++i) any |= flags_out[i];
+    if (any & DEC_F_INTERNAL) {
+        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: internal consistency check failed (decryption)");
+        return PZ_ERR_HIP;
+    }
+    return (any & DEC_F_RANGE) ? PZ_ERR_RANGE : PZ_OK;
+}
+extern "C" int pz_paillier_decrypt(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* cts, uint64_t* m_out,
+                                   uint64_t* r_out, uint8_t* flags_out) {
+    return decrypt_impl(ctx, sk, count, cts, m_out, r_out, flags_out, 0);
+}
+extern "C" int pz_paillier_decrypt_dev(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* d_cts, uint64_t* d_m_out,
+                                       uint64_t* d_r_out, uint8_t* d_flags_out) {
+    return decrypt_impl(ctx, sk, count, d_cts, d_m_out, d_r_out, d_flags_out, 1);
 }

@@ -229,9 +229,9 @@ W4 w4_of(const uint64_t v[4]) { return W4{{v[0], v[1], v[2], v[3]}}; }
 // stream indices of the exposed cells: n | g | c (encrypt, encrypt_uniform) or n | g | c1 | c2 | c (add), little-endian limbs.  The four
 // assign_integer at the head of the stream put their limbs_n limb cells first; res is the assign_integer(2 limbs_n) in front of the final
 // assert_equal_fresh, the last two operations of the stream.  Tally (kind 3, n_steps_g + 1 ciphertexts): n | c_1 | .. | c_B | C, the
-// ciphertexts' 2 limbs_n limb cells at the head of their assign_integer blocks, which follow n's.
+// ciphertexts' 2 limbs_n limb cells at the head of their assign_integer blocks, which follow n's.  Decrypt (kind 5): n | g | m | c.
 int public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g, size_t n_steps_r, std::vector<uint64_t>& cells) {
-    if (kind < 0 || kind > 4 || limbs_n == 0) return PZ_ERR_INVALID;
+    if (kind < 0 || kind > 5 || limbs_n == 0) return PZ_ERR_INVALID;
     size_t total = 0, a_in = 0, a_res = 0, a_eq = 0;
     PZCHK(pz_circuit_cells(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, &total, nullptr));
     PZCHK(pz_op_cells(0, limbs_n, limb_bits, lookup_bits, &a_in, nullptr));
@@ -255,6 +255,8 @@ int public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup
     const unsigned heads = kind == 1 ? 4 : 2;   // n, g (, x = c1, y = c2)
     for (unsigned h = 0; h < heads; ++h)
         for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(h * a_in + j);
+    if (kind == 5)   // "decrypt": n | g | m | c -- the message, the third assign_integer, moves into the statement; r stays private
+        for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(2 * a_in + j);
     for (uint32_t j = 0; j < 2 * limbs_n; ++j) cells.push_back(res + j);
     return PZ_OK;
 }

@@ -955,7 +955,9 @@ extern "C" int pz_structure_arrays(const pz_structure* st, const uint8_t** d_sel
 static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, const uint64_t* exp_g,
                           const uint64_t* exp_r, size_t count, uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors,
                           pz_structure** out) {
-    if (!ctx || !out || kind < 0 || kind > 4 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+    if (!ctx || !out || kind < 0 || kind > 5 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+    const int handle_kind = kind;   // kind 5 ("decrypt") is kind 2's circuit under another statement: pz_structure_expose alone tells them apart
+    if (kind == 5) kind = 2;
     if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
     if (kind == 4 && (count < 1 || count > 65536 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
     if (limb_bits < 16 || limb_bits > 90 || lookup_bits == 0 || lookup_bits >= k || k < 4 || k > 24 || lookup_bits >= limb_bits) return PZ_ERR_INVALID;
@@ -987,7 +989,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     std::unique_ptr<pz_structure> st(new (std::nothrow) pz_structure);
     if (!st) return PZ_ERR_OOM;
     st->k = k;
-    st->kind = kind; st->limbs_n = limbs_n; st->limb_bits = limb_bits; st->lookup_bits = lookup_bits;
+    st->kind = handle_kind; st->limbs_n = limbs_n; st->limb_bits = limb_bits; st->lookup_bits = lookup_bits;
     st->n_adv = (size_t)A; st->n_used = (size_t)A_used; st->n_lk = (size_t)Lk; st->max_rows = (size_t)max_rows;
     st->n_cells = (size_t)NC; st->n_lookups = (size_t)NL; st->n_steps_g = S.n_steps_g; st->n_steps_r = S.n_steps_r;
     for (const C256& c : S.constants) st->constants.insert(st->constants.end(), c.w, c.w + 4);
@@ -1118,7 +1120,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
 extern "C" int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
                                         const uint64_t* exp_g, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
                                         pz_structure** out) {
-    if (kind < 0 || kind > 2) return PZ_ERR_INVALID;   // (the tally has an entry point of its own: this one has no place for its count)
+    if ((kind < 0 || kind > 2) && kind != 5) return PZ_ERR_INVALID;   // (the tallies have entry points of their own: this one has no place for their count)
     return structure_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, k, exp_g, exp_r, 0, 0, minimum_rows, blinding_factors, out);
 }
 extern "C" int pz_circuit_structure_tally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,

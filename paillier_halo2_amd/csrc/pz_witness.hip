@@ -1013,7 +1013,8 @@ static int refresh_aux_host(unsigned W, unsigned nl, unsigned nr, unsigned char*
 
 static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t ng, size_t nr, CircP& C,
                                size_t* adv_total, size_t* lk_total, size_t step_off[3]) {
-    if (kind < 0 || kind > 4) return PZ_ERR_INVALID;
+    if (kind < 0 || kind > 5) return PZ_ERR_INVALID;
+    if (kind == 5) kind = 2;   // "decrypt": kind 2's cells exactly (its statement alone differs: pz_circuit_public_cells)
     if (kind == 3 && (ng < 1 || ng > 65535 || nr)) return PZ_ERR_INVALID;   // the tally of ng + 1 ciphertexts: ng mul_mod blocks
     // the weighted tally of B = nr + 1 ciphertexts: nr tree blocks, ng = 2 B W chain records
     if (kind == 4 && (nr > 65535 || ng == 0 || ng % (2 * (nr + 1)) || ng / (2 * (nr + 1)) > 64)) return PZ_ERR_INVALID;
@@ -1191,6 +1192,7 @@ static int circuit_expand_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t
                                const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride,
                                const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows) {
     if (!ctx || !inputs || !d_steps || !d_modulus || !d_advice) return PZ_ERR_INVALID;
+    if (kind == 5) kind = 2;   // the same cells from the same records (make_circuit_params)
     if ((rows == 0) != (col_stride == 0) || col_stride < rows) return PZ_ERR_INVALID;
     CircP C;
     size_t a, l, so[6];

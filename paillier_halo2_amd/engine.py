@@ -524,6 +524,30 @@ class Engine:
                                                 _ptr(c)), "pz_paillier_wtally_dev")
         return c
 
+    def paillier_sk(self, limbs_n: int, n, g, lam, d) -> "PaillierSecretKey":
+        """a secret key handle (pz.h pz_paillier_sk_create): n, g, lambda and d = n^-1 mod lambda as integers or limbs_n-word arrays
+        (keys.secret_from_primes gives all four).  The key is validated on the device; free() wipes the handle's device memory."""
+        return PaillierSecretKey(self, limbs_n, n, g, lam, d)
+
+    def paillier_decrypt(self, sk: "PaillierSecretKey", cts, want_r: bool = True):
+        """decrypt B ciphertexts (cts: (B, 2*limbs_n) words) under sk (pz.h pz_paillier_decrypt).  Returns (m (B, limbs_n),
+        r (B, limbs_n) or None, flags (B,) uint8: bit 0 = not a unit, m and r zero)."""
+        Ln = sk.limbs_n
+        cts = _np(cts).reshape(-1, 2 * Ln)
+        count = cts.shape[0]
+        m = np.zeros((count, Ln), dtype=np.uint64)
+        r = np.zeros((count, Ln), dtype=np.uint64) if want_r else None
+        flags = np.zeros(count, dtype=np.uint8)
+        self._chk(self.L.pz_paillier_decrypt(self.ctx, sk.handle, count, _ptr(cts), _ptr(m), _ptr(r) if want_r else VP(), VP(flags.ctypes.data)),
+                  "pz_paillier_decrypt")
+        return m, r, flags
+
+    def paillier_decrypt_dev(self, sk: "PaillierSecretKey", count: int, d_cts: int, d_m: int, d_r: int, d_flags: int):
+        """the same on DEVICE buffers (addresses; d_r may be 0), asynchronous on the context's stream: bit 1 of a flag marks a
+        ciphertext >= n^2 (pz.h pz_paillier_decrypt_dev)."""
+        self._chk(self.L.pz_paillier_decrypt_dev(self.ctx, sk.handle, count, VP(d_cts), VP(d_m), VP(d_r) if d_r else VP(), VP(d_flags)),
+                  "pz_paillier_decrypt_dev")
+
     # ------------------------------------------------------------------ K4: witness expansion
     def witness_cells_per_step(self, limbs: int, limb_bits: int, lookup_bits: int) -> Tuple[int, int]:
         a = C.c_size_t()
@@ -1072,3 +1096,33 @@ class Engine:
 
 
 T_MSM_ACC, T_NTT, T_TRACE, T_EXPAND, T_MSM_ALL, T_MSM_SORT, T_MSM_TREE = 0, 1, 2, 3, 4, 5, 6
+
+
+class PaillierSecretKey:
+    """pz_paillier_sk: lambda, d and mu live on the device; free() overwrites them before the memory is released"""
+
+    def __init__(self, eng: "Engine", limbs_n: int, n, g, lam, d):
+        def words(x):
+            if isinstance(x, int):
+                if x < 0 or x >> (64 * limbs_n):
+                    raise ValueError("a key value does not fit limbs_n words")
+                return np.array([(x >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(limbs_n)], dtype=np.uint64)
+            return _np(x).reshape(limbs_n)
+
+        self.eng, self.limbs_n = eng, limbs_n
+        self.handle = VP()
+        a = [words(x) for x in (n, g, lam, d)]
+        eng._chk(eng.L.pz_paillier_sk_create(eng.ctx, limbs_n, *[_ptr(x) for x in a], C.byref(self.handle)), "pz_paillier_sk_create")
+
+    def params(self):
+        """(mu, ginv) as integers: mu = L(g^lambda mod n^2)^-1 mod n, ginv = g^-1 mod n"""
+        mu = np.zeros(self.limbs_n, dtype=np.uint64)
+        gi = np.zeros(self.limbs_n, dtype=np.uint64)
+        self.eng._chk(self.eng.L.pz_paillier_sk_params(self.handle, _ptr(mu), _ptr(gi)), "pz_paillier_sk_params")
+        to_int = lambda a: sum(int(v) << (64 * i) for i, v in enumerate(a.tolist()))
+        return to_int(mu), to_int(gi)
+
+    def free(self):
+        if self.handle:
+            self.eng._chk(self.eng.L.pz_paillier_sk_free(self.eng.ctx, self.handle), "pz_paillier_sk_free")
+            self.handle = VP()

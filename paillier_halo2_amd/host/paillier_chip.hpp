@@ -16,6 +16,7 @@
 //   paillier.rs:32-60 encrypt, :62-85 add                      PaillierChip::encrypt / add
 //   (add folded over B full-width ciphertexts)                 PaillierChip::tally, pz::paillier_tally_test
 //   (c^w and prod c_i^w_i: the scalar homomorphism)            PaillierChip::mul_scalar / weighted_tally, pz::paillier_wtally_test (15.8)
+//   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
 //   paillier.rs:87-97 paillier_enc_native / _add_native        pz::paillier_enc_native / paillier_add_native
 //   bench.rs:11-31    input structs, :33-117 drivers           pz::PaillierEncryptionInput ... paillier_enc_test ...
 //
@@ -266,6 +267,43 @@ struct AssignedWeight {
     size_t cell = 0;
 };
 
+// The key holder's secret key as a device handle (pz_paillier_sk_create: validated there; lambda, d and mu stay on the device and are
+// overwritten when the handle goes).  d = n^-1 mod lambda is the caller's.
+class PaillierSecretKey {
+  public:
+    static Result<std::shared_ptr<PaillierSecretKey>> create(Context& ctx, const BigUint& n, const BigUint& g, const BigUint& lambda,
+                                                             const BigUint& d) {
+        using R = Result<std::shared_ptr<PaillierSecretKey>>;
+        const size_t Ln = std::max<size_t>(1, n.l.size());
+        if (g.l.size() > Ln || lambda.l.size() > Ln || d.l.size() > Ln) return R::Err(PZ_ERR_INVALID, "a key value is wider than n");
+        std::vector<uint64_t> nv = n.to_limbs(Ln), gv = g.to_limbs(Ln), lv = lambda.to_limbs(Ln), dv = d.to_limbs(Ln);
+        pz_paillier_sk* h = nullptr;
+        int rc = pz_paillier_sk_create(ctx.raw(), (uint32_t)Ln, nv.data(), gv.data(), lv.data(), dv.data(), &h);
+        std::fill(lv.begin(), lv.end(), 0);
+        std::fill(dv.begin(), dv.end(), 0);
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_sk_create: ") + pz_strerror(rc));
+        return R::Ok(std::shared_ptr<PaillierSecretKey>(new PaillierSecretKey(ctx.raw(), h, (unsigned)Ln, n, g)));
+    }
+    ~PaillierSecretKey() { (void)pz_paillier_sk_free(ctx_, sk_); }
+    PaillierSecretKey(const PaillierSecretKey&) = delete;
+    const pz_paillier_sk* raw() const { return sk_; }
+    unsigned words() const { return Ln_; }
+    const BigUint& n() const { return n_; }
+    const BigUint& g() const { return g_; }
+
+  private:
+    PaillierSecretKey(pz_ctx* c, pz_paillier_sk* h, unsigned Ln, const BigUint& n, const BigUint& g) : ctx_(c), sk_(h), Ln_(Ln), n_(n), g_(g) {}
+    pz_ctx* ctx_;
+    pz_paillier_sk* sk_;
+    unsigned Ln_;
+    BigUint n_, g_;
+};
+// one decryption: the plaintext, the randomness with c = g^m r^n mod n^2, and whether c was a unit at all (if not, m = r = 0)
+struct Decryption {
+    BigUint m, r;
+    bool unit = false;
+};
+
 struct EncryptionPublicKeyAssigned {  // paillier.rs:6-9
     AssignedBigUint<Fresh> n, g;
 };
@@ -415,6 +453,31 @@ class PaillierChip {  // paillier.rs:11-15
         return R::Ok(AssignedBigUint<Fresh>(BigUint::from_limbs(root.data(), wk), L, biguint->limb_bits));
     }
 
+    // Decryption with randomness recovery, the key holder's step after `tally`: one pz_paillier_decrypt call
+    // over all ciphertexts.  Nothing goes on the tape: the proof that c decrypts to m is the uniform-shape circuit run on the (m, r)
+    // returned here, under the statement n | g | m | c (circuit kind 5).
+    Result<std::vector<Decryption>> decrypt(Context& ctx, const PaillierSecretKey& sk, const std::vector<BigUint>& cts, bool want_r = true) const {
+        using R = Result<std::vector<Decryption>>;
+        const unsigned Ln = sk.words();
+        std::vector<uint64_t> cv;
+        for (const BigUint& c : cts) {
+            if (c.l.size() > 2 * (size_t)Ln) return R::Err(PZ_ERR_RANGE, "decrypt: a ciphertext is wider than n^2");
+            std::vector<uint64_t> w = c.to_limbs(2 * Ln);
+            cv.insert(cv.end(), w.begin(), w.end());
+        }
+        std::vector<uint64_t> m(cts.size() * Ln), r(want_r ? cts.size() * Ln : 0);
+        std::vector<uint8_t> flags(cts.size());
+        int rc = pz_paillier_decrypt(ctx.raw(), sk.raw(), cts.size(), cv.data(), m.data(), want_r ? r.data() : nullptr, flags.data());
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_decrypt: ") + pz_strerror(rc));
+        std::vector<Decryption> out(cts.size());
+        for (size_t i = 0; i < cts.size(); ++i) {
+            out[i].m = BigUint::from_limbs(m.data() + i * Ln, Ln);
+            if (want_r) out[i].r = BigUint::from_limbs(r.data() + i * Ln, Ln);
+            out[i].unit = flags[i] == 0;
+        }
+        return R::Ok(out);
+    }
+
     // c^w mod n^2 = Enc(w m): the weighted tally of one ciphertext
     Result<AssignedBigUint<Fresh>> mul_scalar(Context& ctx, const EncryptionPublicKeyAssigned& pk_enc, const AssignedBigUint<Fresh>& c,
                                               const AssignedWeight& w, unsigned w_bits) const {
@@ -522,6 +585,27 @@ inline void paillier_wtally_test(Context& ctx, const RangeChip& range, const Pai
     auto res_assigned = biguint_chip.assign_integer(ctx, input.res, input.enc_bits * 2).unwrap();
     if (root.value() != res_assigned.value()) throw std::runtime_error("assertion failed: `(left == right)` (paillier_wtally_test)");
     biguint_chip.assert_equal_fresh(ctx, root, res_assigned).unwrap();
+}
+
+// decryption's driver: make the key handle, decrypt every ciphertext, hold the plaintexts to the expected ones and every recovered
+// (m, r) to its ciphertext by re-encrypting it (paillier_enc_native) -- throws on any mismatch, like the drivers above
+struct PaillierDecryptionInput {
+    BigUint n, g, lambda, d;
+    std::vector<BigUint> cts, ms;
+};
+inline void paillier_decrypt_test(Context& ctx, const RangeChip& range, const PaillierDecryptionInput& input) {
+    BigUintChip biguint_chip = BigUintChip::construct(&range, 64);
+    PaillierChip paillier_chip = PaillierChip::construct(&biguint_chip, (unsigned)input.n.bits());
+    auto sk = PaillierSecretKey::create(ctx, input.n, input.g, input.lambda, input.d).unwrap();
+    std::vector<Decryption> dec = paillier_chip.decrypt(ctx, *sk, input.cts).unwrap();
+    std::vector<Decryption> plain = paillier_chip.decrypt(ctx, *sk, input.cts, false).unwrap();
+    if (dec.size() != input.ms.size()) throw std::runtime_error("paillier_decrypt_test: one expected plaintext per ciphertext");
+    for (size_t i = 0; i < dec.size(); ++i) {
+        if (!dec[i].unit || dec[i].m != input.ms[i] || plain[i].m != input.ms[i])
+            throw std::runtime_error("assertion failed: `(left == right)` (paillier_decrypt_test: plaintext)");
+        if (paillier_enc_native(ctx, input.n, input.g, dec[i].m, dec[i].r) != input.cts[i])
+            throw std::runtime_error("assertion failed: `(left == right)` (paillier_decrypt_test: re-encryption)");
+    }
 }
 
 // K4 over the mul_mod steps alone (the bulk of the stream; the caller places the buffers)

@@ -215,8 +215,11 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
     kind 'wtally' (count = B ciphertexts, w_bits = W bits per weight): assign n, assign c_1 .. c_B at full
     width, load_witness(w_1 .. w_B), square + refresh once, per ciphertext pow_mod(c_i, w_i) over W in-circuit bits ([1, 0],
     num_to_bits, W blocks of mul_mod + select + square_mod), the B - 1 blocks of the tree over the powers, assign res,
-    assert_equal_fresh."""
+    assert_equal_fresh.
+    kind 'decrypt' (circuit kind 5): 'encrypt_uniform' cell for cell -- its statement alone differs."""
     Ln, L = limbs_n, 2 * limbs_n
+    if kind == "decrypt":
+        kind = "encrypt_uniform"
     if kind == "tally":
         if count is None or not 2 <= count <= TALLY_MAX:
             raise ValueError(f"a tally takes count = 2 .. {TALLY_MAX} ciphertexts, not {count}")

@@ -180,12 +180,12 @@ def create_proof(key: NativeKey, d_cols: int, tr, seed: int = 0, blinding: Optio
 class NativeStructure:
     """pz_structure: the circuit structure of the reference's drivers generated by the library on the device (csrc/pz_structure.hip,
     include/pz.h pz_circuit_structure_dev) -- the compiled counterpart of circuit_structure.stream_structure + columns.
-    kind: "encrypt" | "add" | "encrypt_uniform"; exp_g / exp_r: the message m and the modulus n (integers; only their bits are used).
+    kind: "encrypt" | "add" | "encrypt_uniform" | "decrypt" (the uniform circuit with the statement n | g | m | c); exp_g / exp_r: the message m and the modulus n (integers; only their bits are used).
     kind "tally" (pz_circuit_structure_tally_dev): count = the number of ciphertexts; no exponents -- one structure serves every tally of
     that size.  kind "wtally" (pz_circuit_structure_wtally_dev): count ciphertexts, w_bits bits per weight -- one structure serves every
     weight vector and every set of ciphertexts of that shape."""
 
-    KINDS = {"encrypt": 0, "add": 1, "encrypt_uniform": 2, "tally": 3, "wtally": 4}
+    KINDS = {"encrypt": 0, "add": 1, "encrypt_uniform": 2, "tally": 3, "wtally": 4, "decrypt": 5}
 
     def __init__(self, eng: Engine, kind: str, enc_bits: int, limb_bits: int, lookup_bits: int, k: int, exp_g: int = 0, exp_r: int = 0,
                  minimum_rows: int = 20, blinding_factors: int = 6, expose: bool = False, count: Optional[int] = None,

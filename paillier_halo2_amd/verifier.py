@@ -178,14 +178,17 @@ def record_seed(prefix: str) -> bytes:
 
 
 def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int] = None, c2: Optional[int] = None, *, enc_bits: int, limb_bits: int,
-                  cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None) -> List[int]:
+                  cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None, m: Optional[int] = None) -> List[int]:
     """the statement of a circuit with the instance column, in the column's row order: little-endian limbs of limb_bits,
     n | g | c (kind "encrypt" / "encrypt_uniform": c = g^m r^n mod n^2) or n | g | c1 | c2 | c ("add": c = c1 c2 mod n^2); n, g, c1, c2 have
     enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)
     kind "tally": n | c_1 | .. | c_B | c with cts = [c_1 .. c_B] at full width (twice n's limbs each) and c their product mod n^2; g plays
     no part in an addition and is ignored.
     kind "wtally": n | c_1 | .. | c_B | w_1 | .. | w_B | c with c = prod c_i^w_i mod n^2, B >= 1; a weight is ONE value (one cell of
-    the circuit, below 2^64), not limbs."""
+    the circuit, below 2^64), not limbs.
+    kind "decrypt": n | g | m | c -- "c decrypts to m under (n, g)", i.e. there is an r with c = g^m r^n mod n^2.  The circuit does not
+    compare m with n: the verifier does, HERE (both are public), and an m >= n is refused -- with it the statement says nothing
+    about Dec(c)."""
     Ln = enc_bits // limb_bits
     mask = (1 << limb_bits) - 1
     limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
@@ -195,6 +198,12 @@ def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int]
         parts = [(n, Ln), (g, Ln), (c1, Ln), (c2, Ln), (c, 2 * Ln)]
     elif kind in ("encrypt", "encrypt_uniform"):
         parts = [(n, Ln), (g, Ln), (c, 2 * Ln)]
+    elif kind == "decrypt":
+        if m is None:
+            raise ValueError("the decrypt statement names the plaintext m")
+        if not 0 <= int(m) < int(n):
+            raise ValueError("the decrypt statement needs 0 <= m < n")
+        parts = [(n, Ln), (g, Ln), (m, Ln), (c, 2 * Ln)]
     elif kind == "tally":
         if cts is None or len(cts) < 2:
             raise ValueError("the tally statement names its ciphertexts: cts = [c_1 .. c_B], B >= 2")
@@ -206,7 +215,9 @@ def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int]
             raise ValueError("a weight does not fit 64 bits")
         parts = [(n, Ln)] + [(ci, 2 * Ln) for ci in cts] + [(c, 2 * Ln)]
     else:
-        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally or wtally")
+        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally or decrypt")
+    if m is not None and kind != "decrypt":
+        raise ValueError("m belongs to kind 'decrypt'")
     if cts is not None and kind not in ("tally", "wtally"):
         raise ValueError("cts belongs to kinds 'tally' and 'wtally'")
     if weights is not None and kind != "wtally":

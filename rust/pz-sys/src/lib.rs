@@ -17,6 +17,7 @@ use core::ffi::{c_char, c_int, c_void};
 #[repr(C)] pub struct pz_proof   { _p: [u8; 0] }
 #[repr(C)] pub struct pz_vk      { _p: [u8; 0] }
 #[repr(C)] pub struct pz_params  { _p: [u8; 0] }
+#[repr(C)] pub struct pz_paillier_sk { _p: [u8; 0] }
 
 extern "C" {
     pub fn pz_init(n_devices: c_int, device_ids: *const c_int, out: *mut *mut pz_ctx) -> c_int;
@@ -107,6 +108,16 @@ extern "C" {
                               weights: *const u64, steps_out: *mut u64, steps_cap: usize, c_out: *mut u64) -> c_int;
     pub fn pz_paillier_wtally_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, w_bits: u32, n: *const u64, cts: *const u64,
                                   weights: *const u64, d_steps_out: *mut u64, steps_cap: usize, c_out: *mut u64) -> c_int;
+    // decryption with randomness recovery (the key holder): a validated key handle, then m_i and r_i with c_i = g^m_i r_i^n mod n^2.
+    // flags_out[i] bit 0: c_i is no unit (m_i = r_i = 0); the _dev form reports a c_i >= n^2 as bit 1 instead of PZ_ERR_RANGE
+    pub fn pz_paillier_sk_create(ctx: *mut pz_ctx, limbs_n: u32, n: *const u64, g: *const u64, lambda: *const u64, d: *const u64,
+                                 out: *mut *mut pz_paillier_sk) -> c_int;
+    pub fn pz_paillier_sk_params(sk: *const pz_paillier_sk, mu_out: *mut u64, ginv_out: *mut u64) -> c_int;
+    pub fn pz_paillier_sk_free(ctx: *mut pz_ctx, sk: *mut pz_paillier_sk) -> c_int;
+    pub fn pz_paillier_decrypt(ctx: *mut pz_ctx, sk: *const pz_paillier_sk, count: usize, cts: *const u64, m_out: *mut u64, r_out: *mut u64,
+                               flags_out: *mut u8) -> c_int;
+    pub fn pz_paillier_decrypt_dev(ctx: *mut pz_ctx, sk: *const pz_paillier_sk, count: usize, d_cts: *const u64, d_m_out: *mut u64,
+                                   d_r_out: *mut u64, d_flags_out: *mut u8) -> c_int;
 
     // uniform-shape variant (NOT the reference's circuit) -- g^m over m_bits in-circuit exponent bits
     pub fn pz_paillier_encrypt_uniform(ctx: *mut pz_ctx, limbs_n: u32, batch: usize, m_bits: u32, n: *const u64, g: *const u64,
