@@ -326,6 +326,31 @@ int pz_paillier_wtally(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_b
 int pz_paillier_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
                            const uint64_t* weights, uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out);
 
+/* Ballot: c_i = g^m_i * r_i^n mod n^2 for i = 1..count under ONE key (n, g) -- the values of circuit kind 6 ("ballot": every c_i holds
+ * a message below 2^m_bits, and for count >= 2 the messages add up to a public S).  1 <= count <= 1024,
+ * 1 <= m_bits <= 64 (else PZ_ERR_INVALID); n, g: limbs_n words each; ms = count 64-bit words, ONE per message; rs = count x limbs_n
+ * words; c_out = count x 2*limbs_n words (all HOST).  Per entry, in this order:
+ *   gm_i = BigUintChip::pow_mod(g, m_i) over EXACTLY m_bits in-circuit bits, LSB first (pz_paillier_wtally's chain on the base g): per
+ *   bit the step (acc, sq) then the step (sq, sq), acc takes the product only where the bit is set; the trailing square is kept;
+ *   rn_i = pow_mod_fixed_exp(r_i, n): per bit of n, LSB first, the step (cur, cur), then on a set bit the step (acc, cur) -- nr =
+ *   bits(n) + popcount(n) steps, the same for every entry (n is public: its bits shape the circuit, as in pz_paillier_encrypt);
+ *   the step (gm_i, rn_i), whose remainder is c_i.
+ * Records a|b|q|r of 2*limbs_n words per field, ciphertext-major: entry i at records i * (2 m_bits + nr + 1) and on.  *n_steps_r (may
+ * be NULL) = nr, ONE value.  steps_out (steps_cap >= count * (2 m_bits + nr + 1) records, else PZ_ERR_CAPACITY) may be NULL: the
+ * values only.  Refusals, in this order: a null pointer, limbs_n = 0, count or m_bits out of range: PZ_ERR_INVALID; 2*limbs_n > 128:
+ * PZ_ERR_UNSUPPORTED; a short steps_cap: PZ_ERR_CAPACITY; a message >= 2^m_bits: PZ_ERR_MESSAGE_RANGE; n = 0: PZ_ERR_ZERO_MODULUS --
+ * all before any launch.  r_i is not compared with n and r_i = 0 is not refused (neither does the circuit: kind 2's property).
+ * One team per ciphertext, ONE launch for all entries, no workgroup waits on another; n^2 and its Barrett constants are formed once.
+ * The messages and the r_i are secrets: a message's bit reaches the accumulator as a lane-wise mask, no branch or address depends on
+ * m_i or r_i (the value-dependent trip count of mul_mod's Barrett correction remains, as in every K3 entry point), and the staged
+ * copies of ms and rs (host form: of the records too) in the context's workspace are overwritten before the call returns.
+ * _dev: d_steps_out is a DEVICE buffer; everything else as above.  (PZ_ABI_VERSION stays 7: additions.) */
+int pz_paillier_ballot(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t m_bits, const uint64_t* n, const uint64_t* g,
+                       const uint64_t* ms, const uint64_t* rs, uint64_t* steps_out, size_t steps_cap, uint32_t* n_steps_r, uint64_t* c_out);
+int pz_paillier_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t m_bits, const uint64_t* n, const uint64_t* g,
+                           const uint64_t* ms, const uint64_t* rs, uint64_t* d_steps_out, size_t steps_cap, uint32_t* n_steps_r,
+                           uint64_t* c_out);
+
 /* Decryption with randomness recovery, for the key holder.  The secret key is a handle: n, g, lambda and d = n^-1 mod lambda
  * (HOST words, limbs_n each; d is the caller's -- paillier_halo2_amd/keys.py::secret_from_primes computes it).
  *   pz_paillier_sk_create  forms n^2 and the Barrett constants of n^2 and of n once, derives on the device x = L(g^lambda mod n^2),
@@ -412,6 +437,37 @@ int pz_circuit_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lo
 int pz_circuit_expand_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits,
                           const uint64_t* inputs, const uint64_t* d_steps, size_t n_steps_g, size_t n_steps_r,
                           const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride);
+
+/* Circuit kind 6, "ballot" (DESIGN.md section 15.10): under the key (n, g) the K = count ciphertexts c_1 .. c_K (1 .. 1024) each encrypt a
+ * value m_i < 2^b, b = m_bits (1 .. 64), and for K >= 2 their sum is the public S.  Its shape is K, b and the records of ONE r^n chain
+ * (n_steps_r = bits(n) + popcount(n) >= 1), which do not fit n_steps_g / n_steps_r: the by-kind entry points refuse kind 6 and these take
+ * the three numbers (anything out of range: PZ_ERR_INVALID).  The stream, in emission order: assign_integer(n), assign_integer(g);
+ * load_witness(m_1 .. m_K) (K consecutive cells, no gate); for K >= 2 FlexGate::sum(m_1 .. m_K) = m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..
+ * (1 + 3 (K - 1) cells, gate windows every 3 cells, the last s is S); assign_integer(r_i) for i = 1..K; square + refresh of n, once;
+ * load_zero; per ciphertext pow_mod(g_ext, m_i) over exactly b bits (assign_constant(1), load_zero, num_to_bits(m_i, b) of 7 b - 2 cells
+ * tied to the load_witness cell, then b blocks of mul_mod(acc, sq), limb-wise select, square_mod(sq): kind 4's chain with the trailing
+ * square), pow_mod_fixed_exp(r_i_ext, n) ([1, 0], then the n_steps_r mul_mod blocks) and mul_mod(gm_i, rn_i); then per ciphertext
+ * assign_integer(res_i, 2*enc_bits) and assert_equal_fresh(c_i, res_i).  The circuit neither compares r_i with n nor refuses r_i = 0.
+ *   pz_ballot_cells         the stream's advice / lookup cell counts (host logic).
+ *   pz_ballot_expand_dev    the values.  inputs (HOST): n | g (ceil(limbs_n*limb_bits/64) words each) | m_1 .. m_K (ONE word each; a
+ *       message >= 2^b: PZ_ERR_MESSAGE_RANGE) | r_1 .. r_K (as n) | res_1 .. res_K (ceil(2*limbs_n*limb_bits/64) words each).  d_steps
+ *       (device): the K (2 b + n_steps_r + 1) records of pz_paillier_ballot_dev, ciphertext-major, fields of ceil(2*limbs_n*limb_bits/64)
+ *       words (repacked first where that differs from 2*ceil(limbs_n*limb_bits/64), as for kinds 3 and 4).  d_modulus: n^2 (device).
+ *       rows / col_stride as pz_circuit_expand_dev.
+ *   pz_ballot_expand_cols_dev  the same with the advice cells in break-point columns, as pz_circuit_expand_cols_dev.
+ *   pz_ballot_public_cells  the stream indices of the exposed cells in statement order: n | g | c_1 | .. | c_K (the limb cells of n's,
+ *       g's and every res_i's assign_integer) and, for K >= 2, S (the sum's last cell): n_public = 2 limbs_n + K 2 limbs_n + (K >= 2). */
+int pz_ballot_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
+                    size_t* advice_cells, size_t* lookup_cells);
+int pz_ballot_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                         size_t n_steps_r, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice,
+                         uint64_t* d_lookup, size_t rows, size_t col_stride);
+int pz_ballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                              size_t n_steps_r, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus,
+                              uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows,
+                              size_t lookup_rows, size_t col_stride);
+int pz_ballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
+                           uint64_t* cells_out, size_t capacity, size_t* n_public);
 
 /* The same stream with the ADVICE cells in halo2-lib's break-point column layout -- what the dependency's assign_with_constraints
  * [D] does with the Context's cell list when it fills the basic-gate columns (reached from bench.rs:161-171 through keygen /
@@ -895,6 +951,13 @@ int pz_shplonk_free(pz_ctx* ctx, pz_shplonk* state);
  * bits per weight: its shape is count, w_bits and the key size alone -- ONE key serves every weight vector and every set of ciphertexts.
  * The weight's load_witness cell is tied to its chain's num_to_bits accumulator, a chain's first sq to assign_integer(c_i)'s limbs, the
  * tree's leaves to the chains' last select outputs.  An ordinary pz_structure (n_steps_g = 2 count w_bits, n_steps_r = count - 1).
+ * pz_circuit_structure_ballot_dev: the structure of the ballot (kind 6, pz_ballot_cells) of `count` ciphertexts (1 .. 1024) and m_bits
+ * (1 .. 64) bits per message under the key whose modulus is exp_r (ceil(limbs_n * limb_bits / 64) words: its bits shape every r^n chain,
+ * as in kind 2): ONE key serves every ballot of an election.  A message's load_witness cell is tied to its chain's num_to_bits
+ * accumulator and to its operand in the sum, every g-chain's first sq to assign_integer(g)'s limbs extended by the load_zero cell, every
+ * r-chain's base to assign_integer(r_i)'s, the final block's operands to the chains' results, each assert_equal_fresh's bit to the
+ * constant 1.  An ordinary pz_structure (n_steps_g = 2 m_bits, n_steps_r = the records of ONE r^n chain); pz_structure_expose works on it
+ * (statement: pz_ballot_public_cells).
  * ------------------------------------------------------------------------------------------- */
 typedef struct pz_structure pz_structure;
 int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
@@ -904,6 +967,8 @@ int pz_circuit_structure_tally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_
                                    size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_circuit_structure_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                     uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
+int pz_circuit_structure_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                    uint32_t m_bits, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_structure_info(const pz_structure* st, size_t* n_adv, size_t* n_adv_filled, size_t* n_lk, size_t* max_rows, size_t* n_constants,
                       size_t* n_cells, size_t* n_lookups, size_t* n_steps_g, size_t* n_steps_r);
 int pz_structure_arrays(const pz_structure* st, const uint8_t** d_selectors, const uint32_t** d_map_col, const uint32_t** d_map_row,

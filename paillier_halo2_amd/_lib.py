@@ -72,7 +72,9 @@ SIGNATURES = {
     "pz_paillier_tally_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_wtally": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_wtally_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, C.c_size_t, VP]),
-    "pz_paillier_sk_create": (C.c_int, [VP, C.c_uint32, VP, VP, VP, VP, C.POINTER(VP)]),
+    "pz_paillier_ballot": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
+    "pz_paillier_ballot_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
+    "pz_paillier_sk_create":(C.c_int, [VP, C.c_uint32, VP, VP, VP, VP, C.POINTER(VP)]),
     "pz_paillier_sk_params": (C.c_int, [VP, VP, VP]),
     "pz_paillier_sk_free": (C.c_int, [VP, VP]),
     "pz_paillier_decrypt": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP]),
@@ -173,6 +175,16 @@ SIGNATURES = {
     # patch point D as entry points: keygen + create_proof, one call per transcript round
     "pz_circuit_structure_dev": (C.c_int, [VP, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, VP, VP, C.c_size_t, C.c_uint32, C.POINTER(VP)]),
     "pz_circuit_structure_tally_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(VP)]),
+    "pz_circuit_structure_ballot_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, VP, C.c_size_t,
+                                                  C.c_uint32, C.POINTER(VP)]),
+    "pz_ballot_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, C.POINTER(C.c_size_t),
+                                  C.POINTER(C.c_size_t)]),
+    "pz_ballot_expand_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, C.c_size_t,
+                                       C.c_size_t]),
+    "pz_ballot_expand_cols_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, VP,
+                                            C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "pz_ballot_public_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, VP, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
     "pz_circuit_structure_wtally_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32,
                                                  C.POINTER(VP)]),
     "pz_structure_info": (C.c_int, [VP] + [C.POINTER(C.c_size_t)] * 9),

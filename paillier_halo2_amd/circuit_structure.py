@@ -301,7 +301,8 @@ class StructureArrays:
     n_steps_r: int
     # stream indices of the cells a circuit with the instance column exposes, in the column's row order: the limb cells of
     # n | g | c (encrypt, encrypt_uniform), n | g | m | c (decrypt), n | g | c1 | c2 | c (add), n | c_1 | .. | c_B | C (tally) or n | c_1 | .. | c_B | w_1 | .. |
-    # w_B | C (wtally: a weight is ONE cell) -- pz_circuit_public_cells gives the same list
+    # w_B | C (wtally: a weight is ONE cell) -- pz_circuit_public_cells gives the same list -- or n | g | c_1 | .. | c_K | S (ballot: S is
+    # the sum's last cell, present for K >= 2; pz_ballot_public_cells)
     public_cells: Optional[np.ndarray] = None
 
 
@@ -310,7 +311,7 @@ def _exp_bits(e: int) -> List[int]:
 
 
 def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: int = 0, exp_r: int = 0, device: Optional[str] = None,
-                     count: Optional[int] = None, w_bits: Optional[int] = None) -> StructureArrays:
+                     count: Optional[int] = None, w_bits: Optional[int] = None, m_bits: Optional[int] = None) -> StructureArrays:
     """kind 'encrypt': exp_g = the message m, exp_r = the modulus n -- only their BITS are used, as in the reference's circuit
     (pow_mod_fixed_exp, paillier.rs:50-55); kind 'add': no exponents; kind 'encrypt_uniform' (the uniform-shape circuit, SURVEY 8f rank
     4): exp_g is ignored -- the message's bits are witness cells, ONE structure serves every message of a key; kind 'tally': count = B
@@ -318,7 +319,9 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     size alone; kind 'wtally': count = B full-width ciphertexts, each raised to a w_bits-bit weight held in ONE witness cell (pow_mod
     over in-circuit bits, the uniform circuit's block), the powers multiplied in layout.wtally_tree's order
     -- the shape is B, w_bits and the key size alone; kind 'decrypt': 'encrypt_uniform' with the message's limb cells exposed between
-    g's and the result's (the statement n | g | m | c).
+    g's and the result's (the statement n | g | m | c); kind 'ballot' (circuit kind 6):
+    count = K ciphertexts under one key, each message ONE witness cell decomposed into m_bits in-circuit bits (the uniform circuit's
+    block), exp_r = the modulus n (its bits shape every r^n chain), for K >= 2 the sum of the messages -- the shape is K, m_bits and n.
     device: None -> numpy arrays; a torch device ("cuda") -> the template is tiled THERE and `src` / `lookup_src` are tensors on it (at
     config c2 the tiled arrays are 3.2 GB: 0.9 s of host numpy against a few ms; `columns` takes either)."""
     dev = None
@@ -353,12 +356,21 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             constants.append(v)
         return const_id[v]
 
-    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt"):
+    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot"):
         raise ValueError(f"unknown circuit kind {kind!r}")
     # 'decrypt' (circuit kind 5) is the uniform-shape circuit cell for cell: the exposed list alone differs
     statement, kind = kind, ("encrypt_uniform" if kind == "decrypt" else kind)
-    if (kind in ("tally", "wtally")) != (count is not None):
-        raise ValueError("count belongs to kinds 'tally' and 'wtally', which need it")
+    if (kind in ("tally", "wtally", "ballot")) != (count is not None):
+        raise ValueError("count belongs to kinds 'tally', 'wtally' and 'ballot', which need it")
+    if (kind == "ballot") != (m_bits is not None):
+        raise ValueError("m_bits belongs to kind 'ballot', which needs it")
+    if kind == "ballot":
+        if not 1 <= count <= layout.BALLOT_MAX:
+            raise ValueError(f"a ballot takes count = 1 .. {layout.BALLOT_MAX} ciphertexts, not {count}")
+        if not 1 <= m_bits <= layout.BALLOT_MAX_BITS:
+            raise ValueError(f"a ballot's message has m_bits = 1 .. {layout.BALLOT_MAX_BITS} bits, not {m_bits}")
+        if exp_r < 1:
+            raise ValueError("a ballot's structure needs exp_r = the modulus n")
     if (kind == "wtally") != (w_bits is not None):
         raise ValueError("w_bits belongs to kind 'wtally', which needs it")
     if kind == "wtally" and not 1 <= w_bits <= layout.WTALLY_MAX_BITS:
@@ -374,6 +386,19 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
         g_c = x_c = y_c = []
         wt_c = [w.put() for _ in range(count)] if kind == "wtally" else []     # load_witness(w_i): one cell each, no gate
+    elif kind == "ballot":
+        g_c = _assign(w, Ln, limb_bits, lb)
+        ms_c = [w.put() for _ in range(count)]                                 # load_witness(m_i): one cell each, no gate
+        sum_c = None
+        if count >= 2:
+            # FlexGate::sum: m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..; a window every 3 cells, the operands copies of the cells above
+            sum_c = w.put(ms_c[0])
+            for i in range(1, count):
+                w.gate(sum_c)
+                w.putc(1)
+                w.put(ms_c[i])
+                sum_c = w.put()
+        rs_c = [_assign(w, Ln, limb_bits, lb) for _ in range(count)]
     else:
         g_c = _assign(w, Ln, limb_bits, lb)
         x_c = _assign(w, Ln, limb_bits, lb)
@@ -483,8 +508,55 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         parts_lk.append(tile(bases, ut.lk))
         return off + nbits * ut.cells, new_acc[-1], new_sq[-1]
 
+    def fixed_chain(off: int, base_limbs, e: int):
+        """pow_mod_fixed_exp(base, e): [1, 0], then per bit of e the squaring step (cur, cur) and on a set bit (acc, cur).  Which BLOCK
+        produced each operand is structure: block indices are assigned first, the operand cells follow from them.
+        -> (off, the power's cells, the number of blocks)"""
+        wc = _Walk(off)
+        one = wc.putc(1)
+        z2 = wc.putc(0)
+        off = flush(wc)
+        bits = _exp_bits(e)
+        ns = len(bits) + sum(bits)
+        a_blk = np.empty(ns, dtype=np.int64)      # producing block of operand a (-1: the base, -2: the constant one)
+        b_blk = np.empty(ns, dtype=np.int64)
+        sq_blk, acc_blk, t = -1, -2, 0
+        for bit in bits:
+            a_blk[t] = b_blk[t] = sq_blk
+            cur_blk, sq_blk = sq_blk, t
+            t += 1
+            if bit:
+                a_blk[t], b_blk[t] = acc_blk, cur_blk
+                acc_blk = t
+                t += 1
+        r_of = off + tm.cells * np.arange(ns, dtype=np.int64)[:, None] + tm.r_cells[None, :]
+        special = np.stack([np.asarray([one] + [z2] * (L - 1), dtype=np.int64), np.asarray(base_limbs, dtype=np.int64)])   # -2, -1
+        table = np.concatenate([special, r_of]) if ns else special
+        if ns:
+            off, _ = blocks(off, table[a_blk + 2], table[b_blk + 2])
+        return off, table[acc_blk + 2], ns
+
     n_steps = [0, 0]
-    if kind == "wtally":
+    if kind == "ballot":
+        # per ciphertext: pow_mod(g_ext, m_i) over m_bits in-circuit bits (the weighted tally's chain on the base g, extended by the
+        # load_zero cell), pow_mod_fixed_exp(r_i_ext, n), the final mul_mod; then per ciphertext assign res_i + assert_equal_fresh
+        ut = _uniform_template(L, limb_bits, lb)
+        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
+        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
+        ut_mask[ut.gates] = 1
+        c_cells = []
+        for i in range(count):
+            wc = _Walk(off)
+            one = wc.putc(1)
+            z2 = wc.putc(0)
+            off = flush(wc)
+            off, gm, _ = bit_chain(off, ut, ut_const, ut_mask, ms_c[i], m_bits, np.asarray([one] + [z2] * (L - 1), dtype=np.int64),
+                                   np.asarray(ext_l(g_c), dtype=np.int64))
+            off, rn, n_steps[1] = fixed_chain(off, ext_l(rs_c[i]), exp_r)
+            off, rfin = blocks(off, np.asarray(gm, dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
+            c_cells.append(rfin[0].tolist())
+        n_steps[0] = 2 * m_bits
+    elif kind == "wtally":
         # per ciphertext pow_mod(c_i, w_i) over w_bits in-circuit bits: [1, 0], num_to_bits of the weight's cell, the bit blocks; the
         # chain starts from its OWN [one, zero ..] and from assign_integer(c_i)'s limb cells.  Its power is the last select's outputs.
         ut = _uniform_template(L, limb_bits, lb)
@@ -536,34 +608,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         for ci, chain in enumerate(chains):
             if chain is None:
                 continue
-            base_limbs, e = chain
-            wc = _Walk(off)
-            one = wc.putc(1)
-            z2 = wc.putc(0)
-            off = flush(wc)
-            bits = _exp_bits(e)
-            # pow_mod_fixed_exp's schedule: per bit the squaring step (cur, cur); on a set bit then (acc, cur).  Which BLOCK produced
-            # each operand is structure: block indices are assigned first, the operand cells follow from them
-            ns = len(bits) + sum(bits)
-            n_steps[ci] = ns
-            a_blk = np.empty(ns, dtype=np.int64)      # producing block of operand a (-1: the base, -2: the constant one)
-            b_blk = np.empty(ns, dtype=np.int64)
-            sq_blk, acc_blk, t = -1, -2, 0
-            for bit in bits:
-                a_blk[t] = b_blk[t] = sq_blk
-                cur_blk, sq_blk = sq_blk, t
-                t += 1
-                if bit:
-                    a_blk[t], b_blk[t] = acc_blk, cur_blk
-                    acc_blk = t
-                    t += 1
-            r_of = off + tm.cells * np.arange(ns, dtype=np.int64)[:, None] + tm.r_cells[None, :]
-            special = np.stack([np.asarray([one] + [z2] * (L - 1), dtype=np.int64), np.asarray(base_limbs, dtype=np.int64)])   # -2, -1
-            table = np.concatenate([special, r_of]) if ns else special
-            a_cells, b_cells = table[a_blk + 2], table[b_blk + 2]
-            if ns:
-                off, _ = blocks(off, a_cells, b_cells)
-            results.append(table[acc_blk + 2])
+            off, power, n_steps[ci] = fixed_chain(off, *chain)
+            results.append(power)
         gm, rn = results
         off, rfin = blocks(off, np.asarray(gm, dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
     elif kind == "tally":
@@ -577,25 +623,32 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         n_steps[0] = nb
     else:
         off, rfin = blocks(off, np.asarray(ext_l(x_c), dtype=np.int64)[None, :], np.asarray(ext_l(y_c), dtype=np.int64)[None, :])
-    c_limbs = rfin[0].tolist()
+    roots = c_cells if kind == "ballot" else [rfin[0].tolist()]      # the ballot: one result per ciphertext
     ws = _Walk(off)
-    res_c = _assign(ws, L, limb_bits, lb)
-    g0 = ws.putc(0)
-    eq_cell = ws.putc(1)
-    for cc, rc in zip(c_limbs, res_c):
-        _is_equal(ws, cc, rc)
-        g = ws.putc(0)
-        ws.gate(g)
-        ws.put(eq_cell); ws.put()
-        eq_cell = ws.put()
+    res_all, eq_cells = [], []
+    for c_limbs in roots:
+        res_c = _assign(ws, L, limb_bits, lb)
+        g0 = ws.putc(0)
+        eq_cell = ws.putc(1)
+        for cc, rc in zip(c_limbs, res_c):
+            _is_equal(ws, cc, rc)
+            g = ws.putc(0)
+            ws.gate(g)
+            ws.put(eq_cell); ws.put()
+            eq_cell = ws.put()
+        res_all += res_c
+        eq_cells.append(eq_cell)
     off = flush(ws)
     if dev is None:
         src, lookup_src = np.concatenate(parts_src), np.concatenate(parts_lk)
     else:
         cat = lambda parts: torch.cat([p_ if isinstance(p_, torch.Tensor) else torch.as_tensor(p_, dtype=torch.int64).to(dev) for p_ in parts])
         src, lookup_src = cat(parts_src), cat(parts_lk)
-    src[eq_cell] = -(1 + cid(1))          # assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
-    if kind in ("tally", "wtally"):
+    for eq_cell in eq_cells:
+        src[eq_cell] = -(1 + cid(1))      # assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
+    if kind == "ballot":
+        exposed = list(n_c) + list(g_c) + res_all + ([sum_c] if sum_c is not None else [])
+    elif kind in ("tally", "wtally"):
         exposed = list(n_c) + [c for ct in ct_c for c in ct] + list(wt_c) + list(res_c)
     else:
         mid = list(x_c) + list(y_c) if kind == "add" else list(x_c) if statement == "decrypt" else []

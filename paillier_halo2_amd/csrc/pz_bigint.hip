@@ -1036,6 +1036,92 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_wtally_pow(co
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
+// ---- the entries of a ballot (pz_paillier_ballot): c_i = g^m_i r_i^n mod n^2 for K messages under ONE key.  One team per ciphertext
+// runs the entry's whole schedule itself -- g^m_i by BigUintChip::pow_mod over exactly m_bits bits (k_wtally_pow's loop), r_i^n by
+// pow_mod_fixed_exp over n's bits, LSB first (the square of EVERY bit, then the product where the bit is set), and the final product --
+// so K entries are one launch with no ticket, no spin, no hand-off.  The Barrett constants come from k_tally_setup, once for all.
+// m_i and r_i are SECRET: the message's bit reaches the accumulator as a lane-wise mask over both candidates (k_dec_pow's read of its
+// table), never as a branch or an address; n's bits are public and steer the second loop.  (What a mul_mod does with its VALUES is
+// K3's as everywhere: the Barrett correction's trip count follows the operands.)
+// recs (may be null: the values only): entry i at records i * per .. + per, per = 2 m_bits + nr + 1: the g-chain's, the r-chain's, the
+// final one.  per is the host's count of the same bits the loop reads; a disagreement is ST_INTERNAL, never a write past the entry.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_ballot_enc(const u64* __restrict__ mod, const u64* __restrict__ n,
+                                                                                 const u64* __restrict__ g, const u64* __restrict__ ms,
+                                                                                 const u64* __restrict__ rs, unsigned m_bits, unsigned n_bits,
+                                                                                 unsigned per, u64* __restrict__ recs, u64* __restrict__ c_out,
+                                                                                 unsigned Ln, u32* __restrict__ status) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (mod[3 * C + 1] == 0) return;   // zero modulus (the same word for every workgroup)
+    const unsigned wave = threadIdx.x >> 6, L = 2 * Ln;
+    TeamCtx<E> T;
+    T.buf = s_team;
+    T.w = wave;
+    T.parity = 0;
+    TeamMul<E> tmul{&T};
+    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
+        u64* z = (u64*)s_team;
+        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
+        __syncthreads();
+    }
+    BarrettCtx<E> B;
+    B.sm = s_scratch[wave];
+    B.limbs = L;
+    B.s = (unsigned)mod[3 * C];
+    B.M = ld_load<E>(mod, C);
+    B.mu = ld_load<E>(mod + C, C);
+    const size_t entry = blockIdx.x;
+    const bool writer = wave == 0 && recs != nullptr;   // the four waves of the team hold the same values: one of them writes
+    u64* const base = writer ? recs + entry * per * 4 * (size_t)L : nullptr;
+    unsigned idx = 0, st = ST_OK;
+    auto step = [&](LD<E>& r, const LD<E>& a, const LD<E>& b) {   // one recorded mul_mod
+        LD<E> q;
+        st |= mul_mod(B, q, r, a, b, tmul);
+        if (writer && idx < per) {
+            u64* o = base + (size_t)idx * 4 * L;
+            ld_store(o, a, L);
+            ld_store(o + L, b, L);
+            ld_store(o + 2 * L, q, L);
+            ld_store(o + 3 * L, r, L);
+        }
+        ++idx;
+    };
+    LD<E> gm = ld_small<E>(1);
+    {
+        const u64 m = ms[entry];
+        LD<E> sq = ld_load<E>(g, Ln);
+        for (unsigned j = 0; j < m_bits; ++j) {
+            LD<E> r;
+            step(r, gm, sq);
+            u64 keep = 0ull - ((m >> j) & 1);   // select(bit, muled, acc) under a mask
+            asm volatile("" : "+v"(keep));      // a per-lane value from here on: nothing below can become a branch
+#pragma unroll
+            for (int e = 0; e < E; ++e) gm.v[e] = (r.v[e] & keep) | (gm.v[e] & ~keep);
+            step(r, sq, sq);
+            sq = r;
+        }
+    }
+    LD<E> rn = ld_small<E>(1);
+    {
+        LD<E> sq = ld_load<E>(rs + entry * Ln, Ln);
+        for (unsigned i = 0; i < n_bits; ++i) {
+            const LD<E> cur = sq;
+            step(sq, cur, cur);
+            if ((n[i >> 6] >> (i & 63)) & 1) {   // (n is the public key)
+                LD<E> r;
+                step(r, rn, cur);
+                rn = r;
+            }
+        }
+    }
+    LD<E> c;
+    step(c, gm, rn);
+    if (idx != per) st |= ST_INTERNAL;
+    if (wave == 0) ld_store(c_out + entry * L, c, L);
+    if (st && lane_id() == 0) atomicOr(status, st);
+}
+
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
@@ -1546,6 +1632,115 @@ extern "C" int pz_paillier_wtally(pz_ctx* ctx, uint32_t limbs_n, size_t count, u
 extern "C" int pz_paillier_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
                                       const uint64_t* weights, uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out) {
     return wtally_impl(ctx, limbs_n, count, w_bits, n, cts, weights, d_steps_out, 1, steps_cap, c_out);
+}
+
+// The ballot: c_i = g^m_i r_i^n mod n^2 for `count` messages of m_bits bits under one key (k_ballot_enc, one team per ciphertext, one
+// launch).  Records ciphertext-major, 2 m_bits + nr + 1 per entry.  The messages and the r_i are secrets: their staged copies (and, in
+// the host form, the staged records, which repeat them) are overwritten before the call returns, on every path past the staging.
+#define K3_BALLOT_MAX 1024
+struct BallotArgs {
+    uint32_t Ln, m_bits, n_bits, per;
+    size_t count;
+    const uint64_t *n, *g, *ms, *rs;
+    uint64_t *steps_out, *c_out;
+    int steps_on_device;
+    u64 *d_n, *d_g, *d_ms, *d_rs, *d_c, *d_mod, *d_steps;
+    u32* d_status;
+};
+static int ballot_run(pz_ctx* ctx, const BallotArgs& a) {
+    const unsigned L = 2 * a.Ln, C = L <= 64 ? 64 : 128;
+    const size_t nb = (size_t)a.Ln * 8, lb = (size_t)L * 8;
+    HIPCHK(ctx, hipMemcpyAsync(a.d_n, a.n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_g, a.g, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_ms, a.ms, a.count * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_rs, a.rs, a.count * nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(a.d_status, 0, 4, ctx->stream));
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        if (C == 64) {
+            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, a.d_n, a.Ln, 1u, a.d_mod, a.d_status);
+            hipLaunchKernelGGL(k_ballot_enc<1>, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, ctx->stream, a.d_mod, a.d_n, a.d_g, a.d_ms,
+                               a.d_rs, a.m_bits, a.n_bits, a.per, a.d_steps, a.d_c, a.Ln, a.d_status);
+        } else {
+            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, a.d_n, a.Ln, 1u, a.d_mod, a.d_status);
+            hipLaunchKernelGGL(k_ballot_enc<2>, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, ctx->stream, a.d_mod, a.d_n, a.d_g, a.d_ms,
+                               a.d_rs, a.m_bits, a.n_bits, a.per, a.d_steps, a.d_c, a.Ln, a.d_status);
+        }
+        HIPCHK(ctx, hipGetLastError());
+    }
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(a.c_out, a.d_c, a.count * lb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&st, a.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (a.steps_out && !a.steps_on_device)
+        HIPCHK(ctx, hipMemcpyAsync(a.steps_out, a.d_steps, a.count * a.per * 4 * lb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return status_to_rc(ctx, st);
+}
+static int ballot_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t m_bits, const uint64_t* n, const uint64_t* g, const uint64_t* ms,
+                       const uint64_t* rs, uint64_t* steps_out, int steps_on_device, size_t steps_cap, uint32_t* n_steps_r, uint64_t* c_out) {
+    if (!ctx || !n || !g || !ms || !rs || !c_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_BALLOT_MAX || m_bits < 1 || m_bits > 64) return PZ_ERR_INVALID;
+    const unsigned L = 2 * Ln;
+    if (L > 128) return PZ_ERR_UNSUPPORTED;
+    // n's bits are public structure of the circuit (pow_mod_fixed_exp): the records of one r^n chain are counted here
+    uint32_t n_bits = 0, nr = 0;
+    for (int top = (int)Ln - 1; top >= 0; --top)
+        if (n[top]) {
+            n_bits = (uint32_t)top * 64 + (64 - __builtin_clzll(n[top]));
+            break;
+        }
+    for (uint32_t k = 0; k < Ln; ++k) nr += (uint32_t)__builtin_popcountll(n[k]);
+    nr += n_bits;
+    const uint32_t per = 2 * m_bits + nr + 1;
+    if (steps_out && steps_cap < count * per) return PZ_ERR_CAPACITY;
+    if (m_bits < 64)   // before any launch: the circuit's num_to_bits of such a message cannot hold
+        for (size_t i = 0; i < count; ++i)
+            if (ms[i] >> m_bits) return PZ_ERR_MESSAGE_RANGE;
+    if (n_bits == 0) return PZ_ERR_ZERO_MODULUS;
+    PZ_ENTER(ctx);
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8;
+    const unsigned C = L <= 64 ? 64 : 128;
+    // n | g | m_1 .. m_count | r_1 .. r_count | c_1 .. c_count | Barrett constants | status
+    const size_t pub_bytes = (2 * nb + 255) & ~(size_t)255, sec_bytes = (count * 8 + count * nb + 255) & ~(size_t)255;
+    const size_t c_bytes = (count * lb + 255) & ~(size_t)255, mod_bytes = ((size_t)3 * C + 2) * 8;
+    void* d;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, pub_bytes + sec_bytes + c_bytes + mod_bytes + 256, &d));
+    char* p = (char*)d;
+    BallotArgs a{};
+    a.Ln = Ln; a.m_bits = m_bits; a.n_bits = n_bits; a.per = per; a.count = count;
+    a.n = n; a.g = g; a.ms = ms; a.rs = rs; a.steps_out = steps_out; a.c_out = c_out; a.steps_on_device = steps_on_device;
+    a.d_n = (u64*)p;
+    a.d_g = (u64*)(p + nb);
+    a.d_ms = (u64*)(p + pub_bytes);
+    a.d_rs = a.d_ms + count;
+    a.d_c = (u64*)(p + pub_bytes + sec_bytes);
+    a.d_mod = (u64*)(p + pub_bytes + sec_bytes + c_bytes);
+    a.d_status = (u32*)(p + pub_bytes + sec_bytes + c_bytes + mod_bytes + 64);
+    a.d_steps = steps_on_device ? steps_out : nullptr;
+    const size_t rec_bytes = steps_out && !steps_on_device ? count * per * 4 * lb : 0;
+    if (rec_bytes) {
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_B, rec_bytes, &t));
+        a.d_steps = (u64*)t;
+    }
+    const int rc = ballot_run(ctx, a);
+    hipError_t e = hipMemsetAsync(a.d_ms, 0, sec_bytes, ctx->stream);
+    if (e == hipSuccess && rec_bytes) e = hipMemsetAsync(a.d_steps, 0, rec_bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (rc != PZ_OK) return rc;
+    HIPCHK(ctx, e);
+    if (n_steps_r) *n_steps_r = nr;
+    return PZ_OK;
+}
+extern "C" int pz_paillier_ballot(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t m_bits, const uint64_t* n, const uint64_t* g,
+                                  const uint64_t* ms, const uint64_t* rs, uint64_t* steps_out, size_t steps_cap, uint32_t* n_steps_r,
+                                  uint64_t* c_out) {
+    return ballot_impl(ctx, limbs_n, count, m_bits, n, g, ms, rs, steps_out, 0, steps_cap, n_steps_r, c_out);
+}
+extern "C" int pz_paillier_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t m_bits, const uint64_t* n, const uint64_t* g,
+                                      const uint64_t* ms, const uint64_t* rs, uint64_t* d_steps_out, size_t steps_cap, uint32_t* n_steps_r,
+                                      uint64_t* c_out) {
+    return ballot_impl(ctx, limbs_n, count, m_bits, n, g, ms, rs, d_steps_out, 1, steps_cap, n_steps_r, c_out);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -261,6 +261,28 @@ int public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup
     return PZ_OK;
 }
 
+// the ballot (kind 6, `count` ciphertexts of m_bits-bit messages, n_steps_r records per r^n chain): n | g | c_1 | .. | c_K, then for
+// K >= 2 the sum S.  n's and g's limb cells head the stream; the sum's last cell is the one in front of assign_integer(r_1); res_i is
+// the assign_integer(2 limbs_n) in front of entry i's assert_equal_fresh, the K pairs closing the stream.
+int ballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
+                        std::vector<uint64_t>& cells) {
+    if (limbs_n == 0) return PZ_ERR_INVALID;
+    size_t total = 0, a_in = 0, a_res = 0, a_eq = 0;
+    PZCHK(pz_ballot_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, &total, nullptr));
+    PZCHK(pz_op_cells(0, limbs_n, limb_bits, lookup_bits, &a_in, nullptr));
+    PZCHK(pz_op_cells(0, 2 * limbs_n, limb_bits, lookup_bits, &a_res, nullptr));
+    PZCHK(pz_op_cells(5, 2 * limbs_n, limb_bits, lookup_bits, &a_eq, nullptr));
+    if (total < 2 * a_in + count * (a_res + a_eq)) return PZ_ERR_INTERNAL;
+    const size_t res = total - count * (a_res + a_eq);
+    cells.clear();
+    for (unsigned h = 0; h < 2; ++h)
+        for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(h * a_in + j);
+    for (size_t i = 0; i < count; ++i)
+        for (uint32_t j = 0; j < 2 * limbs_n; ++j) cells.push_back(res + i * (a_res + a_eq) + j);
+    if (count >= 2) cells.push_back(2 * a_in + count + 3 * (count - 1));
+    return PZ_OK;
+}
+
 }   // namespace
 
 int pz_instance_eval_launch(pz_ctx* ctx, uint32_t k, const uint64_t omega[4], const uint64_t n_inv[4], const uint64_t* d_instances, size_t L,
@@ -308,13 +330,33 @@ extern "C" int pz_circuit_public_cells(int kind, uint32_t limbs_n, uint32_t limb
     return PZ_OK;
 }
 
+extern "C" int pz_ballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
+                                      uint64_t* cells_out, size_t capacity, size_t* n_public) {
+    if (!n_public) return PZ_ERR_INVALID;
+    std::vector<uint64_t> cells;
+    try {
+        PZCHK(ballot_public_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, cells));
+    } catch (const std::bad_alloc&) {
+        return PZ_ERR_OOM;
+    }
+    *n_public = cells.size();
+    if (cells_out) {
+        if (capacity < cells.size()) return PZ_ERR_CAPACITY;
+        memcpy(cells_out, cells.data(), cells.size() * 8);
+    }
+    return PZ_OK;
+}
+
 extern "C" int pz_structure_expose(pz_structure* st) {
     if (!st || !st->ctx || st->n_instance) return PZ_ERR_INVALID;
     pz_ctx* ctx = st->ctx;
     PZ_ENTER(ctx);
     std::vector<uint64_t> cells;
     try {
-        PZCHK(public_cells(st->kind, st->limbs_n, st->limb_bits, st->lookup_bits, st->n_steps_g, st->n_steps_r, cells));
+        if (st->kind == 6)
+            PZCHK(ballot_public_cells(st->limbs_n, st->limb_bits, st->lookup_bits, st->count, (uint32_t)(st->n_steps_g / 2), st->n_steps_r, cells));
+        else
+            PZCHK(public_cells(st->kind, st->limbs_n, st->limb_bits, st->lookup_bits, st->n_steps_g, st->n_steps_r, cells));
     } catch (const std::bad_alloc&) {
         return PZ_ERR_OOM;
     }

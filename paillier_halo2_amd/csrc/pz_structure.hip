@@ -429,6 +429,9 @@ struct Stream {
 // the ciphertexts; then per ciphertext pow_mod over w_bits in-circuit bits -- [1, 0], num_to_bits of the weight's cell, w_bits uniform
 // blocks from the chain's OWN one / zero and assign_integer(c_i)'s limbs --, the count - 1 tree blocks over the powers (the last
 // select's outputs of every chain), res, assert_equal_fresh.  Two parts per chain (its head, its blocks).
+// kind 6 (the ballot): n, g, `count` load_witness cells (the messages), for count >= 2 FlexGate::sum over them,
+// assign_integer(r_i) for every entry, square + refresh, load_zero; per entry pow_mod(g_ext, m_i) over w_bits (= m_bits) in-circuit bits,
+// pow_mod_fixed_exp(r_i_ext, exp_r = n) and the final block; then per entry res_i and assert_equal_fresh.  Five parts per entry.
 int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, unsigned w_bits, Stream& S) {
     const unsigned L = 2 * Ln;
     S.tmpls.reserve(2);                  // (references to the templates stay valid when a circuit with in-circuit bits adds the second one)
@@ -440,7 +443,23 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
     std::vector<i64> g_c, x_c, y_c;
     std::vector<std::vector<i64>> ct_c;
     std::vector<i64> wt_c;
-    if (kind == 3 || kind == 4) {
+    std::vector<std::vector<i64>> rs_c;
+    i64 sum_c = NONE;
+    if (kind == 6) {
+        g_c = assign(w, Ln, W, lb);
+        for (size_t i = 0; i < count; ++i) wt_c.push_back(w.put());   // load_witness(m_i): one cell, no gate
+        if (count >= 2) {
+            // FlexGate::sum: m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..; a window every 3 cells, the operands copies of the cells above
+            sum_c = w.put(wt_c[0]);
+            for (size_t i = 1; i < count; ++i) {
+                w.gate(sum_c);
+                w.putc(c_small(1));
+                w.put(wt_c[i]);
+                sum_c = w.put();
+            }
+        }
+        for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, Ln, W, lb));
+    } else if (kind == 3 || kind == 4) {
         for (size_t i = 0; i < count; ++i) ct_c.push_back(assign(w, L, W, lb));
         if (kind == 4)
             for (size_t i = 0; i < count; ++i) wt_c.push_back(w.put());   // load_witness(w_i): one cell, no gate
@@ -475,7 +494,7 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
         S.fresh.push_back(c != NONE ? c : holder);
     }
     if (S.fresh.size() != L) return PZ_ERR_UNSUPPORTED;   // the refreshed n^2 has l + r limbs for every shape of this circuit
-    const i64 zero = kind >= 3 ? NONE : w.putc(c_small(0));
+    const i64 zero = kind == 3 || kind == 4 ? NONE : w.putc(c_small(0));
     auto ext_l = [&](const std::vector<i64>& limbs) {
         std::vector<i64> v(limbs);
         v.resize(L, zero);
@@ -522,6 +541,45 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
 
     std::vector<i64> gm, rn;   // the cells holding g^m and r^n
     std::vector<i64> root_c;   // the cells holding the circuit's result
+    std::vector<std::vector<i64>> roots;   // kind 6: one result per entry
+    // pow_mod_fixed_exp(base, e) at `off`: [1, 0], then per bit of e the squaring step (cur, cur) and on a set bit (acc, cur).  Which BLOCK
+    // produced each operand is structure: block indices first, the operand cells follow from them (-1: the base, -2: the constant one).
+    // -> the number of blocks; res = the power's cells
+    auto fixed_chain = [&](const std::vector<i64>& base, const u64* e, std::vector<i64>& res) -> i64 {
+        Walk wc(off);
+        const i64 one = wc.putc(c_small(1)), z2 = wc.putc(c_small(0));
+        off = S.flush(wc);
+        int top = (int)((Ln * W + 63) / 64) - 1;      // the exponent: ceil(limbs_n * limb_bits / 64) words
+        while (top >= 0 && e[top] == 0) --top;
+        const size_t bits = top < 0 ? 0 : (size_t)top * 64 + (64 - __builtin_clzll(e[top]));
+        std::vector<i64> a_blk, b_blk;
+        i64 sq_blk = -1, acc_blk = -2, t = 0;
+        for (size_t bi = 0; bi < bits; ++bi) {
+            a_blk.push_back(sq_blk); b_blk.push_back(sq_blk);
+            const i64 cur_blk = sq_blk;
+            sq_blk = t++;
+            if ((e[bi / 64] >> (bi % 64)) & 1) {
+                a_blk.push_back(acc_blk); b_blk.push_back(cur_blk);
+                acc_blk = t++;
+            }
+        }
+        const i64 ns = t;
+        auto operand = [&](i64 blk, unsigned j) -> i64 {
+            if (blk == -2) return j == 0 ? one : z2;
+            if (blk == -1) return base[j];
+            return r_of(off, tm, blk, j);
+        };
+        std::vector<i64> a((size_t)ns * L), b((size_t)ns * L);
+        for (i64 q = 0; q < ns; ++q)
+            for (unsigned j = 0; j < L; ++j) {
+                a[(size_t)q * L + j] = operand(a_blk[(size_t)q], j);
+                b[(size_t)q * L + j] = operand(b_blk[(size_t)q], j);
+            }
+        res.resize(L);
+        for (unsigned j = 0; j < L; ++j) res[j] = operand(acc_blk, j);
+        if (ns) off = S.blocks(off, 0, std::move(a), std::move(b), {}, ns);
+        return ns;
+    };
     auto block_r = [&](i64 boff) {
         std::vector<i64> v(L);
         for (unsigned j = 0; j < L; ++j) v[j] = r_of(boff, tm, 0, j);
@@ -549,45 +607,22 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             gm = acc_cells;
             first_chain = 1;
         }
-        for (int ci = first_chain; ci < 2; ++ci) {
-            Walk wc(off);
-            const i64 one = wc.putc(c_small(1)), z2 = wc.putc(c_small(0));
-            off = S.flush(wc);
-            // pow_mod_fixed_exp's schedule: per bit the squaring step (cur, cur); on a set bit then (acc, cur).  Which BLOCK produced
-            // each operand is structure: block indices first, the operand cells follow from them (-1: the base, -2: the constant one)
-            const u64* e = chains[ci].e;
-            int top = (int)((Ln * W + 63) / 64) - 1;      // the exponent: ceil(limbs_n * limb_bits / 64) words
-            while (top >= 0 && e[top] == 0) --top;
-            const size_t bits = top < 0 ? 0 : (size_t)top * 64 + (64 - __builtin_clzll(e[top]));
-            std::vector<i64> a_blk, b_blk;
-            i64 sq_blk = -1, acc_blk = -2, t = 0;
-            for (size_t bi = 0; bi < bits; ++bi) {
-                a_blk.push_back(sq_blk); b_blk.push_back(sq_blk);
-                const i64 cur_blk = sq_blk;
-                sq_blk = t++;
-                if ((e[bi / 64] >> (bi % 64)) & 1) {
-                    a_blk.push_back(acc_blk); b_blk.push_back(cur_blk);
-                    acc_blk = t++;
-                }
-            }
-            const i64 ns = t;
-            (ci == 0 ? S.n_steps_g : S.n_steps_r) = (size_t)ns;
-            auto operand = [&](i64 blk, unsigned j) -> i64 {
-                if (blk == -2) return j == 0 ? one : z2;
-                if (blk == -1) return chains[ci].base[j];
-                return r_of(off, tm, blk, j);
-            };
-            std::vector<i64> a((size_t)ns * L), b((size_t)ns * L);
-            for (i64 q = 0; q < ns; ++q)
-                for (unsigned j = 0; j < L; ++j) {
-                    a[(size_t)q * L + j] = operand(a_blk[(size_t)q], j);
-                    b[(size_t)q * L + j] = operand(b_blk[(size_t)q], j);
-                }
-            std::vector<i64> res(L);
-            for (unsigned j = 0; j < L; ++j) res[j] = operand(acc_blk, j);
-            if (ns) off = S.blocks(off, 0, std::move(a), std::move(b), {}, ns);
-            (ci == 0 ? gm : rn) = res;
+        for (int ci = first_chain; ci < 2; ++ci)
+            (ci == 0 ? S.n_steps_g : S.n_steps_r) = (size_t)fixed_chain(chains[ci].base, chains[ci].e, ci == 0 ? gm : rn);
+    } else if (kind == 6) {
+        S.tmpls.push_back(uniform_template(L, W, lb));
+        S.bind_template_constants(1);
+        for (size_t i = 0; i < count; ++i) {
+            Walk wb(off);   // the g-chain's head: assign_constant(1), load_zero, then num_to_bits
+            const i64 one = wb.putc(c_small(1)), z2 = wb.putc(c_small(0));
+            std::vector<i64> acc_cells(L, z2), sq_cells = ext_l(g_c);
+            acc_cells[0] = one;
+            off = bit_chain(off, wb, wt_c[i], w_bits, acc_cells, sq_cells);
+            S.n_steps_r = (size_t)fixed_chain(ext_l(rs_c[i]), exp_r, rn);
+            roots.push_back(block_r(off));
+            off = S.blocks(off, 0, std::vector<i64>(acc_cells), std::vector<i64>(rn), {}, 1);
         }
+        S.n_steps_g = 2 * (size_t)w_bits;
     } else if (kind == 3) {
         // operands as (producing block | -(1 + ciphertext)); blocks are numbered as the loop creates them: level-major
         std::vector<i64> cur(count), a_blk, b_blk;
@@ -660,23 +695,28 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
         root_c = block_r(off);
         off = S.blocks(off, 0, std::vector<i64>(gm), std::vector<i64>(rn), {}, 1);
     }
-    // ---- suffix: assign_integer(res), assert_equal_fresh
+    // ---- suffix: assign_integer(res), assert_equal_fresh (the ballot: once per entry)
+    if (kind != 6) roots.push_back(root_c);
     Walk ws(off);
-    const std::vector<i64> res_c = assign(ws, L, W, lb);
-    ws.putc(c_small(0));
-    i64 eq_cell = ws.putc(c_small(1));
-    for (unsigned j = 0; j < L; ++j) {
-        is_equal(ws, root_c[j], res_c[j]);
-        const i64 g = ws.putc(c_small(0));
-        ws.gate(g);
-        ws.put(eq_cell); ws.put();
-        eq_cell = ws.put();
+    std::vector<i64> eq_cells;
+    for (const std::vector<i64>& root : roots) {
+        const std::vector<i64> res_c = assign(ws, L, W, lb);
+        ws.putc(c_small(0));
+        i64 eq_cell = ws.putc(c_small(1));
+        for (unsigned j = 0; j < L; ++j) {
+            is_equal(ws, root[j], res_c[j]);
+            const i64 g = ws.putc(c_small(0));
+            ws.gate(g);
+            ws.put(eq_cell); ws.put();
+            eq_cell = ws.put();
+        }
+        eq_cells.push_back(eq_cell);
     }
     off = S.flush(ws);
     // assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
     Part& last = S.parts.back();
-    last.src[(size_t)(eq_cell - last.cell_off)] = -(1 + (i64)S.cid(c_small(1)));
-    S.result_cell = eq_cell;
+    for (i64 eq_cell : eq_cells) last.src[(size_t)(eq_cell - last.cell_off)] = -(1 + (i64)S.cid(c_small(1)));
+    S.result_cell = eq_cells.back();
     return PZ_OK;
 }
 
@@ -955,13 +995,14 @@ extern "C" int pz_structure_arrays(const pz_structure* st, const uint8_t** d_sel
 static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, const uint64_t* exp_g,
                           const uint64_t* exp_r, size_t count, uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors,
                           pz_structure** out) {
-    if (!ctx || !out || kind < 0 || kind > 5 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+    if (!ctx || !out || kind < 0 || kind > 6 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
     const int handle_kind = kind;   // kind 5 ("decrypt") is kind 2's circuit under another statement: pz_structure_expose alone tells them apart
     if (kind == 5) kind = 2;
     if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
     if (kind == 4 && (count < 1 || count > 65536 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
     if (limb_bits < 16 || limb_bits > 90 || lookup_bits == 0 || lookup_bits >= k || k < 4 || k > 24 || lookup_bits >= limb_bits) return PZ_ERR_INVALID;
-    if (((kind == 0 || kind == 2) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
+    if (kind == 6 && (count < 1 || count > 1024 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
+    if (((kind == 0 || kind == 2 || kind == 6) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
     const i64 n = (i64)1 << k;
     const i64 unusable = (i64)blinding_factors + 3;
     if (unusable + 8 > n || (i64)minimum_rows >= n) return PZ_ERR_INVALID;
@@ -989,6 +1030,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     std::unique_ptr<pz_structure> st(new (std::nothrow) pz_structure);
     if (!st) return PZ_ERR_OOM;
     st->k = k;
+    st->count = kind == 6 ? count : 0;
     st->kind = handle_kind; st->limbs_n = limbs_n; st->limb_bits = limb_bits; st->lookup_bits = lookup_bits;
     st->n_adv = (size_t)A; st->n_used = (size_t)A_used; st->n_lk = (size_t)Lk; st->max_rows = (size_t)max_rows;
     st->n_cells = (size_t)NC; st->n_lookups = (size_t)NL; st->n_steps_g = S.n_steps_g; st->n_steps_r = S.n_steps_r;
@@ -1130,4 +1172,10 @@ extern "C" int pz_circuit_structure_tally_dev(pz_ctx* ctx, uint32_t limbs_n, uin
 extern "C" int pz_circuit_structure_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                                uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
     return structure_impl(ctx, 4, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, w_bits, minimum_rows, blinding_factors, out);
+}
+// the ballot (kind 6): count ciphertexts (1 .. 1024) of m_bits-bit messages (1 .. 64) under the key whose modulus is exp_r
+extern "C" int pz_circuit_structure_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                               uint32_t m_bits, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
+                                               pz_structure** out) {
+    return structure_impl(ctx, 6, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, m_bits, minimum_rows, blinding_factors, out);
 }

@@ -223,6 +223,9 @@ struct ExpP {
                                    // cell0 + (s / 2) * pair_stride + (s & 1) * odd_off instead of cell0 + s * cells
     size_t chain_steps, chain_stride;   // != 0 (with pair_stride): the pairs come in chains of chain_steps steps, chain_stride cells apart
                                         // (weighted tally): step s is step s % chain_steps of the chain at cell0 + (s / chain_steps) * chain_stride
+    size_t chain_recs, rec0;            // chain_recs != 0 (with chain_steps; ballot): a chain's records lie chain_recs apart in `steps` and this
+                                        // launch expands those from rec0 on: step s reads (and numbers its lookups by) record
+                                        // (s / chain_steps) * chain_recs + rec0 + s % chain_steps instead of record s
 };
 
 __device__ __forceinline__ CellPtr adv_ptr(const ExpP& P, Fr* advice, size_t idx) {
@@ -328,11 +331,12 @@ __global__ __launch_bounds__(EXP_THREADS) void k_witness_expand(ExpP P, const u6
     const unsigned L = P.L, D = P.D, lb = P.lb, W = P.W;
     const bool wide = W > 64;
     const size_t step = blockIdx.x;
-    const u64* st = steps + step * 4 * (size_t)P.L64;
     const size_t cstep = P.chain_steps ? step % P.chain_steps : step;
+    const size_t recno = P.chain_recs ? step / P.chain_steps * P.chain_recs + P.rec0 + cstep : step;
+    const u64* st = steps + recno * 4 * (size_t)P.L64;
     const CellPtr adv = adv_ptr(P, advice, P.cell0 + (P.chain_steps ? step / P.chain_steps * P.chain_stride : 0) +
                                                (P.pair_stride ? (cstep >> 1) * P.pair_stride + (cstep & 1) * P.odd_off : cstep * P.cells));
-    const CellPtr lk{lookup, P.lk0 + step * P.lookups, P.rows, P.pad, nullptr, 0};
+    const CellPtr lk{lookup, P.lk0 + recno * P.lookups, P.rows, P.pad, nullptr, 0};
     const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const U192 MAXV = u_make(P.max_w[0], P.max_w[1], P.max_w[2]);
     const U192 BASE = u_shl(u_make(1), W);
@@ -794,6 +798,7 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
     // ---- assign_integer of n, g, x, y (Ln limbs) and of res (2 Ln limbs)
     for (unsigned which = 0; which < 5; ++which) {
         if (which >= C.n_in && which < 4) continue;
+        if (which == 4 && C.kind == 6) continue;   // (the ballot's K results are k_ballot_misc's)
         const unsigned nl = which < 4 ? Ln : nf;
         const u64(*X)[2] = which < 4 ? s_in[which] : s_res;
         const CellPtr a = adv + (which < 4 ? C.a_assign[which] : C.a_res);
@@ -832,17 +837,19 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
             fp_store(lk + C.l_refresh + t, cv_to_fr(rc_lk_cell(LIMB(s_fresh, t / C.rc_lk), W, lb, t % C.rc_lk)));
     // ---- load_zero; assign_constant(1) + load_zero of both pow_mod_fixed_exp
     if (tid == 0) {
-        if (C.kind < 3) fp_store(adv + C.a_zero, fp_zero<FrTag>());   // (the tallies extend nothing: no load_zero)
+        if (C.kind < 3 || C.kind == 6) fp_store(adv + C.a_zero, fp_zero<FrTag>());   // (the tallies extend nothing: no load_zero)
         if (C.kind == 0 || C.kind == 2)
             for (int k = 0; k < 2; ++k) {
                 fp_store(adv + C.a_pow[k], fp_one<FrTag>());
                 fp_store(adv + C.a_pow[k] + 1, fp_zero<FrTag>());
             }
-        fp_store(adv + C.a_eq, fp_zero<FrTag>());
-        fp_store(adv + C.a_eq + 1, fp_one<FrTag>());
+        if (C.kind != 6) {
+            fp_store(adv + C.a_eq, fp_zero<FrTag>());
+            fp_store(adv + C.a_eq + 1, fp_one<FrTag>());
+        }
     }
     // ---- assert_equal_fresh(c, res)
-    for (unsigned t = tid; t < 16 * nf; t += blockDim.x) {
+    for (unsigned t = tid; t < (C.kind != 6 ? 16 * nf : 0u); t += blockDim.x) {
         const unsigned i = t / 16, p = t % 16;
         Fr v;
         if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, i), LIMB(s_res, i), p));
@@ -951,15 +958,16 @@ __global__ __launch_bounds__(256) void k_circuit_select(ExpP P, unsigned Ln, uns
     const CellPtr a = adv_ptr(P, advice, cell_base + (size_t)li * limb_stride + nbits_cells + (size_t)bi * bit_stride + P.cells);
     select_cells(P, st, bit, a);
 }
-// the many-chain form (weighted tally, kind 4): grid.x = chain * nbits + bit.  `steps` holds the chains' records chain-major (2 nbits
-// each); chain i sits at cell_base + i * chain_stride, its bit blocks head_cells (= [1, 0] + num_to_bits) further on
+// the many-chain form (weighted tally, kind 4; ballot): grid.x = chain * nbits + bit.  `steps` holds the chains' records chain-major,
+// chain_recs apart (2 nbits where nothing else lies between them); chain i sits at cell_base + i * chain_stride, its bit blocks
+// head_cells (= [1, 0] + num_to_bits) further on
 __global__ __launch_bounds__(256) void k_circuit_select_many(ExpP P, unsigned nbits, const u64* __restrict__ weights, const u64* __restrict__ steps,
-                                                             size_t cell_base, size_t chain_stride, size_t bit_stride, size_t head_cells,
-                                                             Fr* __restrict__ advice) {
+                                                             size_t chain_recs, size_t cell_base, size_t chain_stride, size_t bit_stride,
+                                                             size_t head_cells, Fr* __restrict__ advice) {
     const size_t i = blockIdx.x / nbits;
     const unsigned bi = blockIdx.x % nbits;
     const unsigned bit = (unsigned)((weights[i] >> bi) & 1);
-    const u64* st = steps + (size_t)(2 * (size_t)blockIdx.x) * 4 * P.L64;
+    const u64* st = steps + (i * chain_recs + 2 * (size_t)bi) * 4 * P.L64;
     select_cells(P, st, bit, adv_ptr(P, advice, cell_base + i * chain_stride + head_cells + (size_t)bi * bit_stride + P.cells));
 }
 
@@ -1258,7 +1266,7 @@ static int circuit_expand_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t
                 hipLaunchKernelGGL(k_circuit_bits_many, dim3((unsigned)C.n_cts), dim3(256), 0, ctx->stream, C.e, (unsigned)W, d_w, C.a_wts, so[0],
                                    chain_stride, (Fr*)d_advice);
                 hipLaunchKernelGGL(k_circuit_select_many, dim3((unsigned)(C.n_cts * W)), dim3(256), 0, ctx->stream, C.e, (unsigned)W, d_w, d_steps,
-                                   so[0], chain_stride, bit_stride, head, (Fr*)d_advice);
+                                   2 * W, so[0], chain_stride, bit_stride, head, (Fr*)d_advice);
                 ExpP Q = P;
                 Q.cell0 = so[0] + head;
                 Q.pair_stride = bit_stride;
@@ -1307,6 +1315,229 @@ extern "C" int pz_circuit_expand_cols_dev(pz_ctx* ctx, int kind, uint32_t limbs_
     if (!d_col_starts || lookup_rows == 0 || lookup_rows > col_stride) return PZ_ERR_INVALID;
     return circuit_expand_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, inputs, d_steps, n_steps_g, n_steps_r, d_modulus, d_advice,
                                d_lookup, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows);
+}
+
+// ---- the ballot (circuit kind 6): K ciphertexts under one key.  Stream: assign n, g; load_witness(m_1 .. m_K);
+// K >= 2: FlexGate::sum (1 + 3 (K - 1) cells); assign r_1 .. r_K; square + refresh, load_zero; per entry [1, 0 | num_to_bits(m_i, b) |
+// b x (mul_mod, select, square_mod) | 1, 0 | nr x mul_mod | mul_mod]; per entry assign res_i (2 Ln limbs) + assert_equal_fresh.
+// inputs: n | g | m_1 .. m_K (one word each) | r_1 .. r_K | res_1 .. res_K.  Records: entry-major, 2 b + nr + 1 each.
+#define BALLOT_MAX 1024
+struct BallotP {
+    size_t K, per, a_msgs, a_sum, a_rs, l_rs, a_ent, l_ent, ent_stride, head, bit_stride, a_res, l_res, res_stride;
+    size_t in_ms, in_rs, in_res;   // word offsets inside `inputs`
+    unsigned b, nr;
+};
+static int make_ballot_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, uint32_t m_bits, size_t n_steps_r, CircP& C,
+                              BallotP& B, size_t* adv_total, size_t* lk_total) {
+    if (count < 1 || count > BALLOT_MAX || m_bits < 1 || m_bits > 64 || n_steps_r < 1 || n_steps_r > 0x7fffffffu) return PZ_ERR_INVALID;
+    if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
+    memset(&C, 0, sizeof C);
+    memset(&B, 0, sizeof B);
+    PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
+    C.Ln = limbs_n;
+    C.kind = 6;
+    C.words_n = (limbs_n * limb_bits + 63) / 64;
+    C.rc_adv = C.e.rc64_adv;
+    C.rc_lk = C.e.rc64_lk;
+    PZCHK(refresh_aux_host(limb_bits, limbs_n, limbs_n, C.inc, &C.nf));
+    if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
+    B.K = count; B.b = m_bits; B.nr = (unsigned)n_steps_r;
+    B.per = 2 * (size_t)m_bits + n_steps_r + 1;
+    size_t a = 0, l = 0;
+    const size_t asg_a = (size_t)limbs_n * (1 + C.rc_adv), asg_l = (size_t)limbs_n * C.rc_lk;
+    C.n_in = 2;
+    for (unsigned k = 0; k < 2; ++k) { C.a_assign[k] = a; C.l_assign[k] = l; a += asg_a; l += asg_l; }
+    B.a_msgs = a; a += count;
+    B.a_sum = a; a += count >= 2 ? 1 + 3 * (count - 1) : 0;
+    B.a_rs = a; B.l_rs = l; a += count * asg_a; l += count * asg_l;
+    C.a_square = a;
+    a += 1;
+    for (unsigned i = 0; i < 2 * limbs_n - 1; ++i) a += 1 + 3 * ((size_t)i + 1);
+    C.a_refresh = a; C.l_refresh = l;
+    a += 1;
+    for (unsigned i = 0; i < C.nf; ++i) a += ((size_t)C.inc[i] + 1) * 22 + (size_t)C.inc[i] * 4;
+    a += (size_t)C.nf * C.rc_adv;
+    l += (size_t)C.nf * C.rc_lk;
+    C.a_zero = a; a += 1;
+    B.head = 2 + 7 * (size_t)m_bits - 2;
+    B.bit_stride = 2 * C.e.cells + 8 * (size_t)C.e.L;
+    B.ent_stride = B.head + m_bits * B.bit_stride + 2 + (n_steps_r + 1) * C.e.cells;
+    B.a_ent = a; B.l_ent = l;
+    a += count * B.ent_stride; l += count * B.per * C.e.lookups;
+    B.res_stride = 2 * asg_a + 2 + 16 * (size_t)C.nf;
+    B.a_res = a; B.l_res = l;
+    a += count * B.res_stride; l += count * 2 * asg_l;
+    B.in_ms = 2 * (size_t)C.words_n;
+    B.in_rs = B.in_ms + count;
+    B.in_res = B.in_rs + count * C.words_n;
+    C.res_off = B.in_res;   // (k_circuit_misc reads a result it does not write for this kind: res_1, valid memory)
+    *adv_total = a;
+    *lk_total = l;
+    return PZ_OK;
+}
+// grid.x = entry i: the [1, 0] of its pow_mod_fixed_exp, assign_integer(res_i) and assert_equal_fresh(c_i, res_i), c_i the remainder of the
+// entry's last record; block 0 also writes FlexGate::sum's cells m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..
+__global__ __launch_bounds__(256) void k_ballot_misc(CircP C, BallotP B, const u64* __restrict__ inputs, const u64* __restrict__ steps,
+                                                     Fr* __restrict__ advice, Fr* __restrict__ lookup) {
+    __shared__ u64 s_res[CIRC_MAXF][2], s_c[CIRC_MAXF][2];
+    __shared__ u64 s_pre[BALLOT_MAX][2];     // prefix sums of the messages (below 2^74)
+    __shared__ unsigned char s_eq[CIRC_MAXF + 1];
+    const size_t i = blockIdx.x;
+    const unsigned nf = C.nf, W = C.e.W, lb = C.e.lb, tid = threadIdx.x;
+    const u64* cval = steps + (i * B.per + B.per - 1) * 4 * (size_t)C.e.L64 + 3 * (size_t)C.e.L64;
+#define LIMB(X, i) u_make((X)[i][0], (X)[i][1])
+    for (unsigned t = tid; t < nf; t += blockDim.x) {
+        limb_extract(inputs + B.in_res + i * C.e.L64, C.e.L64, t, W, s_res[t]);
+        limb_extract(cval, C.e.L64, t, W, s_c[t]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned eq = 1;
+        s_eq[0] = 1;
+        for (unsigned t = 0; t < nf; ++t) {
+            eq &= u_eq(LIMB(s_c, t), LIMB(s_res, t)) ? 1u : 0u;
+            s_eq[t + 1] = (unsigned char)eq;
+        }
+        if (i == 0 && B.K >= 2) {
+            U192 s = u_make(0);
+            for (size_t t = 0; t < B.K; ++t) {
+                s = u_add(s, u_make(inputs[B.in_ms + t]));
+                s_pre[t][0] = s.w[0]; s_pre[t][1] = s.w[1];
+            }
+        }
+        const CellPtr p = adv_ptr(C.e, advice, B.a_ent + i * B.ent_stride + B.head + B.b * B.bit_stride);
+        fp_store(p, fp_one<FrTag>());
+        fp_store(p + 1, fp_zero<FrTag>());
+    }
+    __syncthreads();
+    if (i == 0 && B.K >= 2) {
+        const CellPtr a = adv_ptr(C.e, advice, B.a_sum);
+        for (size_t t = tid; t < 1 + 3 * (B.K - 1); t += blockDim.x) {
+            Fr v;
+            if (t == 0) v = fr_from_u(u_make(inputs[B.in_ms]));
+            else {
+                const size_t m = (t - 1) / 3 + 1, w = (t - 1) % 3;
+                v = w == 0 ? fp_one<FrTag>() : w == 1 ? fr_from_u(u_make(inputs[B.in_ms + m])) : fr_from_u(LIMB(s_pre, m));
+            }
+            fp_store(a + t, v);
+        }
+    }
+    const CellPtr a = adv_ptr(C.e, advice, B.a_res + i * B.res_stride);
+    const CellPtr l{lookup, B.l_res + i * nf * C.rc_lk, C.e.rows, C.e.pad, nullptr, 0};
+    for (unsigned t = tid; t < nf * (1 + C.rc_adv); t += blockDim.x) {
+        Fr v;
+        if (t < nf) v = fr_from_u(LIMB(s_res, t));
+        else v = cv_to_fr(rc_adv_cell(LIMB(s_res, (t - nf) / C.rc_adv), W, lb, (t - nf) % C.rc_adv));
+        fp_store(a + t, v);
+    }
+    if (l)
+        for (unsigned t = tid; t < nf * C.rc_lk; t += blockDim.x) fp_store(l + t, cv_to_fr(rc_lk_cell(LIMB(s_res, t / C.rc_lk), W, lb, t % C.rc_lk)));
+    const CellPtr e = a + (size_t)nf * (1 + C.rc_adv);
+    if (tid == 0) {
+        fp_store(e, fp_zero<FrTag>());
+        fp_store(e + 1, fp_one<FrTag>());
+    }
+    for (unsigned t = tid; t < 16 * nf; t += blockDim.x) {
+        const unsigned j = t / 16, p = t % 16;
+        Fr v;
+        if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, j), LIMB(s_res, j), p));
+        else {
+            const unsigned eq = u_eq(LIMB(s_c, j), LIMB(s_res, j)) ? 1u : 0u, in = s_eq[j], out = s_eq[j + 1];
+            v = p == 12 ? fp_zero<FrTag>() : p == 13 ? (in ? fp_one<FrTag>() : fp_zero<FrTag>())
+                : p == 14 ? (eq ? fp_one<FrTag>() : fp_zero<FrTag>()) : (out ? fp_one<FrTag>() : fp_zero<FrTag>());
+        }
+        fp_store(e + 2 + t, v);
+    }
+#undef LIMB
+}
+
+extern "C" int pz_ballot_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
+                               size_t* advice_cells, size_t* lookup_cells) {
+    CircP C;
+    BallotP B;
+    size_t a, l;
+    PZCHK(make_ballot_params(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, C, B, &a, &l));
+    if (advice_cells) *advice_cells = a;
+    if (lookup_cells) *lookup_cells = l;
+    return PZ_OK;
+}
+
+static int ballot_expand_impl(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                              size_t n_steps_r, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice,
+                              uint64_t* d_lookup, size_t rows, size_t col_stride, const uint64_t* d_col_starts, size_t n_adv_cols,
+                              size_t max_rows) {
+    if (!ctx || !inputs || !d_steps || !d_modulus || !d_advice) return PZ_ERR_INVALID;
+    if ((rows == 0) != (col_stride == 0) || col_stride < rows) return PZ_ERR_INVALID;
+    CircP C;
+    BallotP B;
+    size_t a, l;
+    PZCHK(make_ballot_params(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, C, B, &a, &l));
+    C.e.rows = rows;
+    C.e.pad = col_stride - rows;
+    if (d_col_starts) {
+        if (n_adv_cols == 0 || n_adv_cols > 0xffffffffu || max_rows < 8 || max_rows > col_stride) return PZ_ERR_INVALID;
+        C.e.bp_starts = (const u64*)d_col_starts;
+        C.e.bp_ncols = (unsigned)n_adv_cols;
+        C.e.bp_div = max_rows - 1;
+        C.e.bp_stride = col_stride;
+    }
+    if (m_bits < 64)
+        for (size_t i = 0; i < count; ++i)
+            if (inputs[B.in_ms + i] >> m_bits) return PZ_ERR_MESSAGE_RANGE;   // num_to_bits of such a message cannot hold
+    PZ_ENTER(ctx);
+    const size_t in_words = B.in_res + count * C.e.L64;
+    void* d_in;
+    PZCHK(pz_ws_get(ctx, WS_MISC, in_words * 8 + 64, &d_in));
+    PZCHK(pz_upload_small_async(ctx, d_in, inputs, in_words * 8));
+    pz_timer tm(ctx, PZ_T_EXPAND);
+    const u64* in = (const u64*)d_in;
+    Fr *adv = (Fr*)d_advice, *lk = (Fr*)d_lookup;
+    // n, g, square, refresh, load_zero (the first record's remainder stands in for the result this kind does not write there)
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, d_steps + 3 * (size_t)C.e.L64, adv, lk);
+    // assign_integer(r_i): Ln limbs from words_n words each
+    ExpP R = C.e;
+    R.L64 = C.words_n;
+    hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)count), dim3(256), 0, ctx->stream, R, C.Ln, C.rc_adv, C.rc_lk, in + B.in_rs, B.a_rs,
+                       B.l_rs, adv, lk);
+    // per entry: the load_witness cell and the chain's head; the selects; the g-chain's record pairs; the r-chain's and the final record
+    hipLaunchKernelGGL(k_circuit_bits_many, dim3((unsigned)count), dim3(256), 0, ctx->stream, C.e, m_bits, in + B.in_ms, B.a_msgs, B.a_ent,
+                       B.ent_stride, adv);
+    hipLaunchKernelGGL(k_circuit_select_many, dim3((unsigned)(count * m_bits)), dim3(256), 0, ctx->stream, C.e, m_bits, in + B.in_ms, d_steps,
+                       B.per, B.a_ent, B.ent_stride, B.bit_stride, B.head, adv);
+    ExpP Q = C.e;
+    Q.cell0 = B.a_ent + B.head;
+    Q.lk0 = B.l_ent;
+    Q.pair_stride = B.bit_stride;
+    Q.odd_off = C.e.cells + 8 * (size_t)C.e.L;
+    Q.chain_steps = 2 * (size_t)m_bits;
+    Q.chain_stride = B.ent_stride;
+    Q.chain_recs = B.per;
+    hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(count * Q.chain_steps)), dim3(EXP_THREADS), 0, ctx->stream, Q, d_steps, d_modulus, adv, lk);
+    ExpP T = C.e;
+    T.cell0 = B.a_ent + B.head + m_bits * B.bit_stride + 2;
+    T.lk0 = B.l_ent;
+    T.chain_steps = n_steps_r + 1;
+    T.chain_stride = B.ent_stride;
+    T.chain_recs = B.per;
+    T.rec0 = 2 * (size_t)m_bits;
+    hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(count * T.chain_steps)), dim3(EXP_THREADS), 0, ctx->stream, T, d_steps, d_modulus, adv, lk);
+    hipLaunchKernelGGL(k_ballot_misc, dim3((unsigned)count), dim3(256), 0, ctx->stream, C, B, in, d_steps, adv, lk);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+extern "C" int pz_ballot_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                                    size_t n_steps_r, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus,
+                                    uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride) {
+    return ballot_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, inputs, d_steps, d_modulus, d_advice, d_lookup,
+                              rows, col_stride, nullptr, 0, 0);
+}
+extern "C" int pz_ballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                                         size_t n_steps_r, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus,
+                                         uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts, size_t n_adv_cols,
+                                         size_t max_rows, size_t lookup_rows, size_t col_stride) {
+    if (!d_col_starts || lookup_rows == 0 || lookup_rows > col_stride) return PZ_ERR_INVALID;
+    return ballot_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, inputs, d_steps, d_modulus, d_advice, d_lookup,
+                              lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows);
 }
 
 // host-pointer form (SURVEY.md section 8b `pz_witness_expand`): stages the trace up, expands on the device in groups

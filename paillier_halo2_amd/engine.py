@@ -524,6 +524,44 @@ class Engine:
                                                 _ptr(c)), "pz_paillier_wtally_dev")
         return c
 
+    @staticmethod
+    def ballot_steps_r(n) -> int:
+        """records of ONE r^n chain of a ballot: bits(n) + popcount(n) (n as an integer or 64-bit words)"""
+        if not isinstance(n, int):
+            n = sum(int(l) << (64 * k) for k, l in enumerate(_np(n).reshape(-1).tolist()))
+        return n.bit_length() + bin(n).count("1")
+
+    def _ballot_args(self, limbs_n: int, n, g, ms, rs):
+        n, g = _np(n).reshape(limbs_n), _np(g).reshape(limbs_n)
+        rs = _np(rs).reshape(-1, limbs_n)
+        ms = np.ascontiguousarray(ms, dtype=np.uint64).reshape(-1)
+        if ms.shape[0] != rs.shape[0]:
+            raise ValueError("one message and one r per ciphertext")
+        return n, g, ms, rs
+
+    def paillier_ballot(self, limbs_n: int, n, g, ms, rs, m_bits: int, want_steps: bool = True):
+        """c_i = g^m_i r_i^n mod n^2 for K messages below 2^m_bits under one key (pz.h pz_paillier_ballot): ms K integers, rs
+        (K, limbs_n).  Returns (c (K, 2*limbs_n), steps (K, 2 m_bits + nr + 1, 4, 2*limbs_n) or None, nr = the records of one r^n chain)."""
+        L = 2 * limbs_n
+        n, g, ms, rs = self._ballot_args(limbs_n, n, g, ms, rs)
+        count = ms.shape[0]
+        per = 2 * m_bits + self.ballot_steps_r(n) + 1
+        steps = np.zeros((max(count, 1), per, 4, L), dtype=np.uint64) if want_steps else None
+        c = np.zeros((max(count, 1), L), dtype=np.uint64)
+        nr = C.c_uint32()
+        self._chk(self.L.pz_paillier_ballot(self.ctx, limbs_n, count, m_bits, _ptr(n), _ptr(g), _ptr(ms), _ptr(rs),
+                                            _ptr(steps) if want_steps else VP(), count * per, C.byref(nr), _ptr(c)), "pz_paillier_ballot")
+        return c, steps, nr.value
+
+    def paillier_ballot_dev(self, limbs_n: int, n, g, ms, rs, m_bits: int, d_steps: int, steps_cap: int):
+        """the same with the records left on the device for K4 (d_steps: steps_cap x 4 x 2*limbs_n u64).  Returns (c, nr)."""
+        n, g, ms, rs = self._ballot_args(limbs_n, n, g, ms, rs)
+        c = np.zeros((max(ms.shape[0], 1), 2 * limbs_n), dtype=np.uint64)
+        nr = C.c_uint32()
+        self._chk(self.L.pz_paillier_ballot_dev(self.ctx, limbs_n, ms.shape[0], m_bits, _ptr(n), _ptr(g), _ptr(ms), _ptr(rs), VP(d_steps),
+                                                steps_cap, C.byref(nr), _ptr(c)), "pz_paillier_ballot_dev")
+        return c, nr.value
+
     def paillier_sk(self, limbs_n: int, n, g, lam, d) -> "PaillierSecretKey":
         """a secret key handle (pz.h pz_paillier_sk_create): n, g, lambda and d = n^-1 mod lambda as integers or limbs_n-word arrays
         (keys.secret_from_primes gives all four).  The key is validated on the device; free() wipes the handle's device memory."""
@@ -599,6 +637,38 @@ class Engine:
         self._chk(self.L.pz_circuit_expand_cols_dev(self.ctx, kind, limbs_n, limb_bits, lookup_bits, _ptr(inp), VP(d_steps), n_steps_g,
                                                     n_steps_r, VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts), n_adv_cols,
                                                     max_rows, lookup_rows, col_stride), "pz_circuit_expand_cols_dev")
+
+    # the ballot (circuit kind 6, pz.h pz_ballot_*): its shape is (count, m_bits, n_steps_r), which the by-kind calls have no place for
+    def ballot_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, m_bits: int, n_steps_r: int):
+        a = C.c_size_t()
+        l = C.c_size_t()
+        self._chk(self.L.pz_ballot_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, C.byref(a), C.byref(l)), "pz_ballot_cells")
+        return a.value, l.value
+
+    def ballot_public_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, m_bits: int, n_steps_r: int):
+        """stream indices of the exposed cells in statement order: n | g | c_1 .. c_K | S (K >= 2)"""
+        out = np.zeros(2 * limbs_n * (count + 1) + 1, dtype=np.uint64)
+        npub = C.c_size_t()
+        self._chk(self.L.pz_ballot_public_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, _ptr(out), out.shape[0],
+                                                C.byref(npub)), "pz_ballot_public_cells")
+        return out[: npub.value]
+
+    def ballot_expand_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, m_bits: int, n_steps_r: int, inputs, d_steps: int,
+                          d_modulus: int, d_advice: int, d_lookup: int = 0, rows: int = 0, col_stride: int = 0):
+        """inputs: host uint64 array n | g | m_1 .. m_K (one word each) | r_1 .. r_K | res_1 .. res_K; d_steps: the K (2 m_bits + n_steps_r
+        + 1) records of paillier_ballot_dev; writes the ballot's cell stream, dense or cut into columns"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        self._chk(self.L.pz_ballot_expand_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, _ptr(inp), VP(d_steps),
+                                              VP(d_modulus), VP(d_advice), VP(d_lookup), rows, col_stride), "pz_ballot_expand_dev")
+
+    def ballot_expand_cols_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, m_bits: int, n_steps_r: int, inputs,
+                               d_steps: int, d_modulus: int, d_advice: int, d_lookup: int, d_col_starts: int, n_adv_cols: int, max_rows: int,
+                               lookup_rows: int, col_stride: int):
+        """the same with the advice cells in break-point columns (circuit_expand_cols_dev's conventions)"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        self._chk(self.L.pz_ballot_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, _ptr(inp), VP(d_steps),
+                                                   VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts), n_adv_cols, max_rows,
+                                                   lookup_rows, col_stride), "pz_ballot_expand_cols_dev")
 
     # ------------------------------------------------------------------ "next" rows: SRS setup, evaluation at a point
     def srs_setup_g1_dev(self, k: int, s, omega, d_g: int = 0, d_g_lagrange: int = 0):

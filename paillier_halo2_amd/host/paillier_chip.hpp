@@ -16,6 +16,7 @@
 //   paillier.rs:32-60 encrypt, :62-85 add                      PaillierChip::encrypt / add
 //   (add folded over B full-width ciphertexts)                 PaillierChip::tally, pz::paillier_tally_test
 //   (c^w and prod c_i^w_i: the scalar homomorphism)            PaillierChip::mul_scalar / weighted_tally, pz::paillier_wtally_test (15.8)
+//   (K ciphertexts of small values with a public sum)          PaillierChip::ballot, pz::paillier_ballot_test (15.10)
 //   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
 //   paillier.rs:87-97 paillier_enc_native / _add_native        pz::paillier_enc_native / paillier_add_native
 //   bench.rs:11-31    input structs, :33-117 drivers           pz::PaillierEncryptionInput ... paillier_enc_test ...
@@ -69,7 +70,8 @@ class Context {
     pz_ctx* raw() { return ctx_; }
     // ---- the operation tape: what the reference's Context would hold, operation by operation
     // (0 .. 5 are pz_op_cells' operations; the three after them push a cell count of their own: record_cells)
-    enum Op { ASSIGN = 0, SQUARE = 1, REFRESH = 2, CONST_CELL = 3, MUL_MOD = 4, ASSERT_EQUAL = 5, LOAD_WITNESS = 6, NUM_TO_BITS = 7, SELECT = 8 };
+    enum Op { ASSIGN = 0, SQUARE = 1, REFRESH = 2, CONST_CELL = 3, MUL_MOD = 4, ASSERT_EQUAL = 5, LOAD_WITNESS = 6, NUM_TO_BITS = 7, SELECT = 8,
+              SUM = 9 };
     struct OpRec {
         Op op;
         unsigned limbs;      // limb count the operation works on
@@ -92,6 +94,7 @@ class Context {
         ops_.push_back(OpRec{op, limbs, 1});
     }
     size_t load_witness() { record_cells(LOAD_WITNESS, 1, 1); return witness_cells_++; }   // ctx.load_witness(v): one advice cell, no gate
+    void sum(size_t terms) { record_cells(SUM, 1, 1 + 3 * (terms - 1)); }         // FlexGate::sum over `terms` >= 2 cells: a | 1 | b | a + b | ..
     size_t load_zero() { record(CONST_CELL, 1); return zero_cells_++; }            // paillier.rs:47 ctx.load_zero(): one advice cell
     size_t load_constant_one() { record(CONST_CELL, 1); return zero_cells_++; }    // assign_constant(1) of pow_mod_fixed_exp
     const std::vector<OpRec>& ops() const { return ops_; }
@@ -453,6 +456,76 @@ class PaillierChip {  // paillier.rs:11-15
         return R::Ok(AssignedBigUint<Fresh>(BigUint::from_limbs(root.data(), wk), L, biguint->limb_bits));
     }
 
+    // The ballot: c_i = g^m_i r_i^n mod n^2 for K messages under one key.  n^2 hoisted once, load_zero; per
+    // ciphertext pow_mod(g_ext, m_i) over m_bits in-circuit bits (the weighted tally's chain, the trailing square kept),
+    // pow_mod_fixed_exp(r_i_ext, n) and the final mul_mod.  One pz_paillier_ballot call computes every record; the tape takes them in the
+    // circuit's order, which is the call's.  The messages' load_witness cells, their sum and the r_i are assigned by the caller
+    // (paillier_ballot_test), in front of this.
+    Result<std::vector<AssignedBigUint<Fresh>>> ballot(Context& ctx, const EncryptionPublicKeyAssigned& pk_enc, const std::vector<AssignedWeight>& ms,
+                                                       const std::vector<AssignedBigUint<Fresh>>& rs, unsigned m_bits) const {
+        using R = Result<std::vector<AssignedBigUint<Fresh>>>;
+        if (ms.empty() || ms.size() != rs.size() || ms.size() > 1024) return R::Err(PZ_ERR_INVALID, "ballot: one r per message, 1 .. 1024 of them");
+        if (m_bits < 1 || m_bits > 64) return R::Err(PZ_ERR_INVALID, "ballot: m_bits outside 1 .. 64");
+        auto n2m = biguint->square(ctx, pk_enc.n);
+        if (!n2m.ok) return R::Err(n2m.err.status, n2m.err.msg);
+        RefreshAux aux = RefreshAux::new_(biguint->limb_bits, pk_enc.n.num_limbs(), pk_enc.n.num_limbs());
+        auto n2r = biguint->refresh(ctx, n2m.val, aux);
+        if (!n2r.ok) return R::Err(n2r.err.status, n2r.err.msg);
+        const AssignedBigUint<Fresh>& n2 = n2r.val;
+        (void)ctx.load_zero();
+        const unsigned L = n2.num_limbs(), Wd = n2.num_words(), wn = pk_enc.n.num_words(), wk = 2 * wn;   // K3 works on 2 * wn words
+        std::vector<uint64_t> nv = pk_enc.n.words(), gv = pk_enc.g.value().to_limbs(wn), mv, rv;
+        for (const AssignedWeight& m : ms) mv.push_back(m.value);
+        for (const auto& r : rs) {
+            if (r.num_limbs() != pk_enc.n.num_limbs()) return R::Err(PZ_ERR_INVALID, "ballot: an r is not assigned at n's width");
+            std::vector<uint64_t> w = r.value().to_limbs(wn);
+            rv.insert(rv.end(), w.begin(), w.end());
+        }
+        const BigUint n_biguint = get_biguint(pk_enc.n);
+        size_t nr = n_biguint.bits();
+        for (uint64_t w : nv) nr += (size_t)__builtin_popcountll(w);
+        const size_t K = ms.size(), per = 2 * (size_t)m_bits + nr + 1;
+        std::vector<uint64_t> rec(K * per * 4 * wk), cv(K * wk);
+        uint32_t nr_lib = 0;
+        int rc = pz_paillier_ballot(ctx.raw(), wn, K, m_bits, nv.data(), gv.data(), mv.data(), rv.data(), rec.data(), K * per, &nr_lib, cv.data());
+        std::fill(mv.begin(), mv.end(), 0);
+        std::fill(rv.begin(), rv.end(), 0);
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_ballot: ") + pz_strerror(rc));
+        if (nr_lib != nr) return R::Err(PZ_ERR_INTERNAL, "ballot: the library counts another r^n chain");
+        // the tape holds Wd words per integer (Wd < 2 * wn where limb_bits does not divide 64: the words above are zero)
+        auto steps_of = [&](size_t first, size_t count, std::vector<uint64_t>& out) {
+            out.clear();
+            for (size_t f = first * 4; f < (first + count) * 4; ++f) {
+                if (BigUint::from_limbs(rec.data() + f * wk, wk).bits() > (size_t)L * biguint->limb_bits) return false;
+                out.insert(out.end(), rec.begin() + f * wk, rec.begin() + f * wk + Wd);
+            }
+            return true;
+        };
+        const char* wide = "a step's integer does not fit the assigned limb count";
+        std::vector<uint64_t> steps;
+        std::vector<AssignedBigUint<Fresh>> out;
+        for (size_t i = 0; i < K; ++i) {
+            (void)ctx.load_constant_one();
+            (void)ctx.load_zero();
+            ctx.record_cells(Context::NUM_TO_BITS, 1, 7 * (size_t)m_bits - 2);
+            for (unsigned j = 0; j < m_bits; ++j) {
+                const size_t at = i * per + 2 * j;
+                if (!steps_of(at, 1, steps)) return R::Err(PZ_ERR_RANGE, wide);
+                ctx.push_steps(steps, Wd, L, biguint->limb_bits, n2.value());
+                ctx.record_cells(Context::SELECT, L, 8 * (size_t)L);
+                if (!steps_of(at + 1, 1, steps)) return R::Err(PZ_ERR_RANGE, wide);
+                ctx.push_steps(steps, Wd, L, biguint->limb_bits, n2.value());
+            }
+            (void)ctx.load_constant_one();
+            (void)ctx.load_zero();
+            if (!steps_of(i * per + 2 * m_bits, nr + 1, steps)) return R::Err(PZ_ERR_RANGE, wide);   // the r^n chain, then the final block
+            ctx.push_steps(steps, Wd, L, biguint->limb_bits, n2.value());
+            out.push_back(AssignedBigUint<Fresh>(BigUint::from_limbs(cv.data() + i * wk, wk), L, biguint->limb_bits));
+        }
+        std::fill(rec.begin(), rec.end(), 0);
+        return R::Ok(out);
+    }
+
     // Decryption with randomness recovery, the key holder's step after `tally`: one pz_paillier_decrypt call
     // over all ciphertexts.  Nothing goes on the tape: the proof that c decrypts to m is the uniform-shape circuit run on the (m, r)
     // returned here, under the statement n | g | m | c (circuit kind 5).
@@ -587,6 +660,34 @@ inline void paillier_wtally_test(Context& ctx, const RangeChip& range, const Pai
     biguint_chip.assert_equal_fresh(ctx, root, res_assigned).unwrap();
 }
 
+// the ballot's driver: assign n, g, load_witness every m_i, for K >= 2 their sum, assign every r_i, ballot, then per ciphertext assign
+// res_i and assert_equal_fresh
+struct PaillierBallotInput {
+    unsigned limb_bits, enc_bits, m_bits;
+    BigUint n, g;
+    std::vector<uint64_t> ms;
+    std::vector<BigUint> rs, res;
+};
+inline void paillier_ballot_test(Context& ctx, const RangeChip& range, const PaillierBallotInput& input) {
+    BigUintChip biguint_chip = BigUintChip::construct(&range, input.limb_bits);
+    PaillierChip paillier_chip = PaillierChip::construct(&biguint_chip, input.enc_bits);
+    auto n_assigned = biguint_chip.assign_integer(ctx, input.n, input.enc_bits).unwrap();
+    auto g_assigned = biguint_chip.assign_integer(ctx, input.g, input.enc_bits).unwrap();
+    EncryptionPublicKeyAssigned pk_enc{n_assigned, g_assigned};
+    std::vector<AssignedWeight> ms;
+    for (uint64_t m : input.ms) ms.push_back(AssignedWeight{m, ctx.load_witness()});
+    if (ms.size() >= 2) ctx.sum(ms.size());
+    std::vector<AssignedBigUint<Fresh>> rs;
+    for (const BigUint& r : input.rs) rs.push_back(biguint_chip.assign_integer(ctx, r, input.enc_bits).unwrap());
+    auto cts = paillier_chip.ballot(ctx, pk_enc, ms, rs, input.m_bits).unwrap();
+    if (cts.size() != input.res.size()) throw std::runtime_error("paillier_ballot_test: one expected ciphertext per message");
+    for (size_t i = 0; i < cts.size(); ++i) {
+        auto res_assigned = biguint_chip.assign_integer(ctx, input.res[i], input.enc_bits * 2).unwrap();
+        if (cts[i].value() != res_assigned.value()) throw std::runtime_error("assertion failed: `(left == right)` (paillier_ballot_test)");
+        biguint_chip.assert_equal_fresh(ctx, cts[i], res_assigned).unwrap();
+    }
+}
+
 // decryption's driver: make the key handle, decrypt every ciphertext, hold the plaintexts to the expected ones and every recovered
 // (m, r) to its ciphertext by re-encrypting it (paillier_enc_native) -- throws on any mismatch, like the drivers above
 struct PaillierDecryptionInput {
@@ -677,6 +778,31 @@ inline int synthesize_wtally_circuit(Context& ctx, unsigned enc_bits, unsigned w
     std::vector<uint64_t> w = res.to_limbs(wr);
     in.insert(in.end(), w.begin(), w.end());
     return pz_circuit_expand_dev(ctx.raw(), 4, Ln, W, ctx.lookup_bits(), in.data(), d_steps, ng, B - 1, d_modulus, d_advice, d_lookup, 0, 0);
+}
+
+// the ballot's tape (paillier_ballot_test) expanded on the device: circuit kind 6, inputs n | g | m_1 .. m_K | r_1 .. r_K | res_1 .. res_K
+inline int synthesize_ballot_circuit(Context& ctx, unsigned enc_bits, unsigned m_bits, size_t n_steps_r, const BigUint& n, const BigUint& g,
+                                     const std::vector<uint64_t>& ms, const std::vector<BigUint>& rs, const std::vector<BigUint>& res,
+                                     uint64_t* d_steps, uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup) {
+    const unsigned W = ctx.limb_bits(), Ln = enc_bits / W, wn = (Ln * W + 63) / 64, wr = (2 * Ln * W + 63) / 64;
+    const size_t K = ms.size();
+    if (K < 1 || rs.size() != K || res.size() != K || ctx.n_steps() != K * (2 * (size_t)m_bits + n_steps_r + 1)) return PZ_ERR_INVALID;
+    size_t a = 0, l = 0;
+    int rc = pz_ballot_cells(Ln, W, ctx.lookup_bits(), K, m_bits, n_steps_r, &a, &l);
+    if (rc != PZ_OK) return rc;
+    if (a != ctx.advice_cells() || l != ctx.lookup_cells()) return PZ_ERR_INVALID;   // the tape is not this driver's
+    std::vector<uint64_t> in = n.to_limbs(wn), w = g.to_limbs(wn);
+    in.insert(in.end(), w.begin(), w.end());
+    in.insert(in.end(), ms.begin(), ms.end());
+    for (const BigUint& r : rs) {
+        w = r.to_limbs(wn);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    for (const BigUint& c : res) {
+        w = c.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    return pz_ballot_expand_dev(ctx.raw(), Ln, W, ctx.lookup_bits(), K, m_bits, n_steps_r, in.data(), d_steps, d_modulus, d_advice, d_lookup, 0, 0);
 }
 
 }  // namespace pz

@@ -206,8 +206,12 @@ def wtally_tree(count: int):
     return tally_tree(count) if count > 1 else []
 
 
+BALLOT_MAX = 1024       # ciphertexts of one ballot (pz.h pz_paillier_ballot)
+BALLOT_MAX_BITS = 64    # width of a ballot entry's message: one 64-bit word
+
+
 def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_steps_g: int = 0, n_steps_r: int = 0,
-                  count: int | None = None, w_bits: int | None = None) -> CircuitCells:
+                  count: int | None = None, w_bits: int | None = None, m_bits: int | None = None) -> CircuitCells:
     """The whole cell stream of paillier_enc_test (bench.rs:33-75, kind 'encrypt') or paillier_enc_add_test
     (bench.rs:77-117, kind 'add'), operation by operation in call order -- what pz_circuit_expand_dev writes.
     kind 'tally' (count = B ciphertexts): assign n, assign c_1 .. c_B at full width, square + refresh once, the B - 1 blocks of
@@ -216,7 +220,11 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
     width, load_witness(w_1 .. w_B), square + refresh once, per ciphertext pow_mod(c_i, w_i) over W in-circuit bits ([1, 0],
     num_to_bits, W blocks of mul_mod + select + square_mod), the B - 1 blocks of the tree over the powers, assign res,
     assert_equal_fresh.
-    kind 'decrypt' (circuit kind 5): 'encrypt_uniform' cell for cell -- its statement alone differs."""
+    kind 'decrypt' (circuit kind 5): 'encrypt_uniform' cell for cell -- its statement alone differs.
+    kind 'ballot' (circuit kind 6; count = K ciphertexts, m_bits = b bits per message, n_steps_r = the records
+    of ONE r^n chain): assign n, g, load_witness(m_1 .. m_K), for K >= 2 FlexGate::sum of them (1 + 3 (K - 1) cells), assign r_1 .. r_K,
+    square + refresh once, load_zero, per ciphertext pow_mod(g, m_i) over b in-circuit bits, pow_mod_fixed_exp(r_i, n) and the final
+    mul_mod, then per ciphertext assign res_i and assert_equal_fresh."""
     Ln, L = limbs_n, 2 * limbs_n
     if kind == "decrypt":
         kind = "encrypt_uniform"
@@ -232,10 +240,19 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
             raise ValueError(f"a weight has w_bits = 1 .. {WTALLY_MAX_BITS} bits, not {w_bits}")
         if n_steps_g not in (0, 2 * count * w_bits) or n_steps_r not in (0, count - 1):
             raise ValueError("a weighted tally has 2 * count * w_bits chain steps and count - 1 tree steps")
+    elif kind == "ballot":
+        if count is None or not 1 <= count <= BALLOT_MAX:
+            raise ValueError(f"a ballot takes count = 1 .. {BALLOT_MAX} ciphertexts, not {count}")
+        if m_bits is None or not 1 <= m_bits <= BALLOT_MAX_BITS:
+            raise ValueError(f"a ballot's message has m_bits = 1 .. {BALLOT_MAX_BITS} bits, not {m_bits}")
+        if n_steps_g not in (0, 2 * m_bits) or n_steps_r < 1:
+            raise ValueError("a ballot entry has 2 * m_bits g-chain steps and n_steps_r >= 1 steps of one r^n chain")
     elif count is not None:
-        raise ValueError("count belongs to kinds 'tally' and 'wtally'")
+        raise ValueError("count belongs to kinds 'tally', 'wtally' and 'ballot'")
     if w_bits is not None and kind != "wtally":
         raise ValueError("w_bits belongs to kind 'wtally'")
+    if m_bits is not None and kind != "ballot":
+        raise ValueError("m_bits belongs to kind 'ballot'")
     mm = mul_mod_cells(L, limb_bits, lookup_bits)
     seg, a, l = {}, 0, 0
 
@@ -245,7 +262,15 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         a += da
         l += dl
 
-    if kind in ("tally", "wtally"):
+    if kind == "ballot":
+        na, nl = assign_cells(Ln, limb_bits, lookup_bits)
+        put("assign_n", na, nl)
+        put("assign_g", na, nl)
+        put("messages", count)
+        if count >= 2:
+            put("sum", 1 + 3 * (count - 1))
+        put("assign_rs", count * na, count * nl)
+    elif kind in ("tally", "wtally"):
         put("assign_n", *assign_cells(Ln, limb_bits, lookup_bits))
         ca, cl = assign_cells(L, limb_bits, lookup_bits)
         put("assign_cts", count * ca, count * cl)
@@ -274,6 +299,15 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         assert n_steps_g in (0, 2 * m_bits)
         put("pow_g", 2 + Ln * (7 * limb_bits - 2) + m_bits * (2 * mm.advice + 8 * L), 2 * m_bits * mm.lookup)
         put("pow_r", 2 + n_steps_r * mm.advice, n_steps_r * mm.lookup)
+    if kind == "ballot":
+        # per entry: [1, 0], num_to_bits (7 b - 2 cells), b blocks of mul_mod + select + square_mod; [1, 0] and the r^n chain's blocks;
+        # the final block.  Then per entry assign res_i at full width and assert_equal_fresh
+        steps = 2 * m_bits + n_steps_r + 1
+        put("entries", count * (2 + 7 * m_bits - 2 + m_bits * 8 * L + 2 + steps * mm.advice), count * steps * mm.lookup)
+        ra, rl = assign_cells(L, limb_bits, lookup_bits)
+        put("results", count * (ra + assert_equal_cells(L)), count * rl)
+        seg["end"] = (a, l)
+        return CircuitCells(a, l, seg)
     if kind not in ("tally", "wtally"):
         put("final", mm.advice, mm.lookup)
     put("assign_res", *assign_cells(L, limb_bits, lookup_bits))

@@ -177,8 +177,9 @@ def record_seed(prefix: str) -> bytes:
     return int(prefix[1:-1]).to_bytes(8, "little")
 
 
-def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int] = None, c2: Optional[int] = None, *, enc_bits: int, limb_bits: int,
-                  cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None, m: Optional[int] = None) -> List[int]:
+def public_inputs(kind: str, n: int, g: Optional[int], c: Optional[int] = None, c1: Optional[int] = None, c2: Optional[int] = None, *, enc_bits: int,
+                  limb_bits: int, cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None, m: Optional[int] = None,
+                  total: Optional[int] = None) -> List[int]:
     """the statement of a circuit with the instance column, in the column's row order: little-endian limbs of limb_bits,
     n | g | c (kind "encrypt" / "encrypt_uniform": c = g^m r^n mod n^2) or n | g | c1 | c2 | c ("add": c = c1 c2 mod n^2); n, g, c1, c2 have
     enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)
@@ -188,7 +189,11 @@ def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int]
     the circuit, below 2^64), not limbs.
     kind "decrypt": n | g | m | c -- "c decrypts to m under (n, g)", i.e. there is an r with c = g^m r^n mod n^2.  The circuit does not
     compare m with n: the verifier does, HERE (both are public), and an m >= n is refused -- with it the statement says nothing
-    about Dec(c)."""
+    about Dec(c).
+    kind "ballot": n | g | c_1 | .. | c_K | S -- "every c_i of cts encrypts a value below 2^m_bits under (n, g), and the values add up to
+    S = total"; m_bits is the circuit's shape, not part of the statement.  One ciphertext has no S (it would be the message): a total
+    given with K = 1 is refused, and so is a total missing with K >= 2.  S is ONE value.  A c_i >= n^2 is no ciphertext and is refused
+    here (the circuit proves c_i = a remainder mod n^2, so no proof exists for one).  No single result c."""
     Ln = enc_bits // limb_bits
     mask = (1 << limb_bits) - 1
     limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
@@ -214,12 +219,26 @@ def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int]
         if any(int(v) < 0 or int(v) >> 64 for v in weights):
             raise ValueError("a weight does not fit 64 bits")
         parts = [(n, Ln)] + [(ci, 2 * Ln) for ci in cts] + [(c, 2 * Ln)]
+    elif kind == "ballot":
+        if cts is None or len(cts) < 1 or g is None or c is not None:
+            raise ValueError("the ballot statement names n, g and its ciphertexts cts = [c_1 .. c_K], K >= 1, and no single result c")
+        if (total is not None) != (len(cts) >= 2):
+            raise ValueError("the ballot statement carries the sum `total` exactly when it has two or more ciphertexts")
+        if total is not None and (int(total) < 0 or int(total) >= consts.FR_R):
+            raise ValueError("the total is one field value")
+        if any(int(ci) >= int(n) * int(n) for ci in cts):
+            raise ValueError("a ballot's ciphertext is below n^2")
+        parts = [(n, Ln), (g, Ln)] + [(ci, 2 * Ln) for ci in cts]
     else:
-        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally or decrypt")
+        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt or ballot")
+    if c is None and kind != "ballot":
+        raise ValueError("the statement names its result c")
+    if total is not None and kind != "ballot":
+        raise ValueError("total belongs to kind 'ballot'")
     if m is not None and kind != "decrypt":
         raise ValueError("m belongs to kind 'decrypt'")
-    if cts is not None and kind not in ("tally", "wtally"):
-        raise ValueError("cts belongs to kinds 'tally' and 'wtally'")
+    if cts is not None and kind not in ("tally", "wtally", "ballot"):
+        raise ValueError("cts belongs to kinds 'tally', 'wtally' and 'ballot'")
     if weights is not None and kind != "wtally":
         raise ValueError("weights belongs to kind 'wtally'")
     for v, cnt in parts:
@@ -228,6 +247,8 @@ def public_inputs(kind: str, n: int, g: Optional[int], c: int, c1: Optional[int]
     out = [x for v, cnt in parts for x in limbs(v, cnt)]
     if kind == "wtally":      # the weights stand between the ciphertexts and the result
         out[-2 * Ln:-2 * Ln] = [int(v) for v in weights]
+    if total is not None:
+        out.append(int(total))
     return out
 
 

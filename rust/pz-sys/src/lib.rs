@@ -108,6 +108,12 @@ extern "C" {
                               weights: *const u64, steps_out: *mut u64, steps_cap: usize, c_out: *mut u64) -> c_int;
     pub fn pz_paillier_wtally_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, w_bits: u32, n: *const u64, cts: *const u64,
                                   weights: *const u64, d_steps_out: *mut u64, steps_cap: usize, c_out: *mut u64) -> c_int;
+    // the ballot: c_i = g^m_i r_i^n for count messages of m_bits bits under one key -- 2 * m_bits + n_steps_r + 1 records per entry,
+    // ciphertext-major; *n_steps_r = the records of ONE r^n chain; ms: one word per message
+    pub fn pz_paillier_ballot(ctx: *mut pz_ctx, limbs_n: u32, count: usize, m_bits: u32, n: *const u64, g: *const u64, ms: *const u64,
+                              rs: *const u64, steps_out: *mut u64, steps_cap: usize, n_steps_r: *mut u32, c_out: *mut u64) -> c_int;
+    pub fn pz_paillier_ballot_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, m_bits: u32, n: *const u64, g: *const u64, ms: *const u64,
+                                  rs: *const u64, d_steps_out: *mut u64, steps_cap: usize, n_steps_r: *mut u32, c_out: *mut u64) -> c_int;
     // decryption with randomness recovery (the key holder): a validated key handle, then m_i and r_i with c_i = g^m_i r_i^n mod n^2.
     // flags_out[i] bit 0: c_i is no unit (m_i = r_i = 0); the _dev form reports a c_i >= n^2 as bit 1 instead of PZ_ERR_RANGE
     pub fn pz_paillier_sk_create(ctx: *mut pz_ctx, limbs_n: u32, n: *const u64, g: *const u64, lambda: *const u64, d: *const u64,
@@ -155,6 +161,21 @@ extern "C" {
                                           minimum_rows: usize, blinding_factors: u32, out: *mut *mut pz_structure) -> c_int;
     pub fn pz_circuit_structure_wtally_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, k: u32, count: usize,
                                            w_bits: u32, minimum_rows: usize, blinding_factors: u32, out: *mut *mut pz_structure) -> c_int;
+    pub fn pz_circuit_structure_ballot_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, k: u32, count: usize,
+                                           m_bits: u32, exp_r: *const u64, minimum_rows: usize, blinding_factors: u32,
+                                           out: *mut *mut pz_structure) -> c_int;
+    // circuit kind 6 ("ballot"): its shape is (count, m_bits, n_steps_r); inputs n | g | m_1 .. m_K | r_1 .. r_K | res_1 .. res_K
+    pub fn pz_ballot_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, m_bits: u32, n_steps_r: usize,
+                           advice_cells: *mut usize, lookup_cells: *mut usize) -> c_int;
+    pub fn pz_ballot_expand_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, m_bits: u32,
+                                n_steps_r: usize, inputs: *const u64, d_steps: *const u64, d_modulus: *const u64, d_advice: *mut u64,
+                                d_lookup: *mut u64, rows: usize, col_stride: usize) -> c_int;
+    pub fn pz_ballot_expand_cols_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, m_bits: u32,
+                                     n_steps_r: usize, inputs: *const u64, d_steps: *const u64, d_modulus: *const u64, d_advice: *mut u64,
+                                     d_lookup: *mut u64, d_col_starts: *const u64, n_adv_cols: usize, max_rows: usize, lookup_rows: usize,
+                                     col_stride: usize) -> c_int;
+    pub fn pz_ballot_public_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, m_bits: u32, n_steps_r: usize,
+                                  cells_out: *mut u64, capacity: usize, n_public: *mut usize) -> c_int;
     pub fn pz_structure_info(st: *const pz_structure, n_adv: *mut usize, n_adv_filled: *mut usize, n_lk: *mut usize, max_rows: *mut usize,
                              n_constants: *mut usize, n_cells: *mut usize, n_lookups: *mut usize, n_steps_g: *mut usize,
                              n_steps_r: *mut usize) -> c_int;
