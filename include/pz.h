@@ -379,6 +379,43 @@ int pz_paillier_decrypt(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, con
 int pz_paillier_decrypt_dev(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* d_cts, uint64_t* d_m_out,
                             uint64_t* d_r_out, uint8_t* d_flags_out);
 
+/* T-of-T threshold decryption.  A dealer splits theta = lambda (lambda^-1 mod n) additively into T shares
+ * (paillier_halo2_amd/keys.py::deal_shares, PaillierChip::deal_shares); the public threshold key holds n, g, a base v, h_i = v^theta_i
+ * mod n^2 and mu2 = (2a)^-1 mod n with 1 + a n = g^theta mod n^2.  Nothing below ever sees lambda.
+ *   pz_paillier_partial   one trustee's partial decryptions of `count` ciphertexts (1 .. 1024, else PZ_ERR_INVALID) under its share
+ *       theta < 2^e_bits, 1 <= e_bits <= 128 limbs_n (else PZ_ERR_INVALID): h = v^theta and u_j = (c_j^2)^theta mod n^2.  n: limbs_n
+ *       words; v, theta, every c_j, h_out and every u_j: 2*limbs_n words (all HOST).  Chain 0 is BigUintChip::pow_mod(v, theta), chain
+ *       j = 1 .. count is pow_mod(s_j, theta) with s_j = c_j^2 mod n^2, each over EXACTLY e_bits bits, LSB first (pz_paillier_wtally's
+ *       chain): per bit the step (acc, sq) then the step (sq, sq), acc takes the product only where the bit is set; the trailing square
+ *       is kept.  Records a|b|q|r of 2*limbs_n words per field: first the `count` squaring records (c_j, c_j, q, s_j), then chain i
+ *       (0 .. count) at records count + i 2 e_bits and on -- count + (count + 1) 2 e_bits in all (steps_cap below that: PZ_ERR_CAPACITY;
+ *       steps_out may be NULL: the values only).  Refusals, in this order and all before any launch: a null pointer, limbs_n = 0, count
+ *       or e_bits out of range: PZ_ERR_INVALID; 2*limbs_n > 128: PZ_ERR_UNSUPPORTED; a short steps_cap: PZ_ERR_CAPACITY; theta >=
+ *       2^e_bits: PZ_ERR_MESSAGE_RANGE; n = 0: PZ_ERR_ZERO_MODULUS.  A v or c_j >= n^2 is PZ_ERR_RANGE (found on the device).
+ *       One team per chain, ONE launch of count + 1 teams (a team squares its own ciphertext first), no workgroup waits on another; n^2
+ *       and its Barrett constants are formed once.  theta is a SECRET: bit t is read from word t / 64, an address that depends on t
+ *       alone, and reaches the accumulator as a lane-wise mask; no branch or trip count depends on it (the value-dependent trip count of
+ *       mul_mod's Barrett correction remains, as in every K3 entry point); the staged copy of theta (host form: of the records too) in
+ *       the context's workspace is overwritten before the call returns.
+ *   pz_paillier_partial_dev   d_steps_out is a DEVICE buffer; everything else as above.
+ *   pz_paillier_combine   m_j = L(U_j) mu2 mod n with U_j = prod_i u_ij mod n^2 over the `trustees` (1 .. 256) partials of each of `count`
+ *       (1 .. 1024) ciphertexts; partials trustee-major (trustees x count x 2*limbs_n words), n and mu2 limbs_n words, m_out count x
+ *       limbs_n words, flags_out count bytes (all HOST).  Flag bit 0: U mod n != 1 (the partials do not belong together; the entry's m is
+ *       zero); bit 1: a partial >= n^2 (m zero; the call returns PZ_ERR_RANGE after writing every entry).  One team per ciphertext, one
+ *       launch.  Nothing here is secret.
+ *   pz_paillier_combine_dev   d_partials, d_m_out and d_flags_out are DEVICE buffers (n and mu2 stay HOST words); the work is queued on
+ *       the context's stream and the call returns without waiting: the flags are the caller's to read.  (PZ_ABI_VERSION stays 7:
+ *       additions.) */
+int pz_paillier_partial(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t e_bits, const uint64_t* n, const uint64_t* v,
+                        const uint64_t* theta, const uint64_t* cts, uint64_t* steps_out, size_t steps_cap, uint64_t* h_out, uint64_t* u_out);
+int pz_paillier_partial_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t e_bits, const uint64_t* n, const uint64_t* v,
+                            const uint64_t* theta, const uint64_t* cts, uint64_t* d_steps_out, size_t steps_cap, uint64_t* h_out,
+                            uint64_t* u_out);
+int pz_paillier_combine(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
+                        const uint64_t* partials, uint64_t* m_out, uint8_t* flags_out);
+int pz_paillier_combine_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
+                            const uint64_t* d_partials, uint64_t* d_m_out, uint8_t* d_flags_out);
+
 /* ---------------------------------------------------------------------------------------------
  * K4 -- expansion of a step trace into advice-column cells (Fr Montgomery, 32 B each), i.e. the
  * values halo2-lib's Context would hold after BigUintChip emitted the constraints of every
@@ -468,6 +505,33 @@ int pz_ballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits,
                               size_t lookup_rows, size_t col_stride);
 int pz_ballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
                            uint64_t* cells_out, size_t capacity, size_t* n_public);
+
+/* Circuit kind 7, "partial" (DESIGN.md section 15.11): one trustee's partial decryptions of K = count ciphertexts (1 .. 1024) under the
+ * public threshold key's base v and its own h: there is ONE theta < 2^(2 enc_bits) with h = v^theta and u_j = (c_j^2)^theta mod n^2 for
+ * every j.  Its shape is K and the key size alone; the by-kind entry points refuse kind 7 and these take `count` (out of range:
+ * PZ_ERR_INVALID).  The stream, in emission order: assign_integer(n); assign_integer of v, theta, c_1 .. c_K at full width (2 limbs_n
+ * limbs); square + refresh of n, once; load_zero; pow_mod(v, theta) exactly as kind 2 emits pow_mod -- [1, 0], then per limb of theta
+ * num_to_bits(limb, limb_bits) and that limb's blocks of mul_mod(acc, sq), limb-wise select, square_mod(sq) --; per ciphertext
+ * mul_mod(c_j, c_j) and pow_mod(s_j, theta) the same way; then assign_integer(h) + assert_equal_fresh, and the same for every u_j.  The
+ * circuit compares nothing with n^2: a verifier refuses v, h, c_j or u_j >= n^2 outside it.
+ *   pz_partial_cells         the stream's advice / lookup cell counts (host logic).
+ *   pz_partial_expand_dev    the values.  inputs (HOST): n (ceil(limbs_n*limb_bits/64) words) | v | theta | c_1 .. c_K | h | u_1 .. u_K
+ *       (ceil(2*limbs_n*limb_bits/64) words each; theta >= 2^(2*limbs_n*limb_bits): PZ_ERR_MESSAGE_RANGE).  d_steps (device): the
+ *       K + (K + 1) 2 E records of pz_paillier_partial_dev with e_bits = E = 2*limbs_n*limb_bits, as they are, fields of
+ *       ceil(2*limbs_n*limb_bits/64) words (repacked first where that differs from 2*ceil(limbs_n*limb_bits/64), as for kinds 3, 4 and
+ *       6).  d_modulus: n^2 (device).  rows / col_stride as pz_circuit_expand_dev.
+ *   pz_partial_expand_cols_dev  the same with the advice cells in break-point columns, as pz_circuit_expand_cols_dev.
+ *   pz_partial_public_cells  the stream indices of the exposed cells in statement order: n | v | h | c_1 | u_1 | .. | c_K | u_K (the limb
+ *       cells of the assign_integer of each): n_public = limbs_n + (2 + 2 K) 2 limbs_n. */
+int pz_partial_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t* advice_cells, size_t* lookup_cells);
+int pz_partial_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, const uint64_t* inputs,
+                          const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows,
+                          size_t col_stride);
+int pz_partial_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, const uint64_t* inputs,
+                               const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup,
+                               const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride);
+int pz_partial_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint64_t* cells_out, size_t capacity,
+                            size_t* n_public);
 
 /* The same stream with the ADVICE cells in halo2-lib's break-point column layout -- what the dependency's assign_with_constraints
  * [D] does with the Context's cell list when it fills the basic-gate columns (reached from bench.rs:161-171 through keygen /
@@ -958,6 +1022,12 @@ int pz_shplonk_free(pz_ctx* ctx, pz_shplonk* state);
  * r-chain's base to assign_integer(r_i)'s, the final block's operands to the chains' results, each assert_equal_fresh's bit to the
  * constant 1.  An ordinary pz_structure (n_steps_g = 2 m_bits, n_steps_r = the records of ONE r^n chain); pz_structure_expose works on it
  * (statement: pz_ballot_public_cells).
+ * pz_circuit_structure_partial_dev: the structure of a trustee's partial decryptions (kind 7, pz_partial_cells) of `count` ciphertexts
+ * (1 .. 1024): ONE key serves every trustee and every set of ciphertexts of that count.  Every chain's num_to_bits accumulators are
+ * tied to assign_integer(theta)'s limb cells, chain 0's first sq to assign_integer(v)'s, each squaring block's two operands to
+ * assign_integer(c_j)'s, chain j's first sq to that block's remainder, each chain's last select outputs to the assert_equal_fresh against
+ * h / u_j, each assert_equal_fresh's bit to the constant 1.  An ordinary pz_structure (n_steps_g = the 2 E records of ONE chain,
+ * n_steps_r = 0); pz_structure_expose works on it (statement: pz_partial_public_cells).
  * ------------------------------------------------------------------------------------------- */
 typedef struct pz_structure pz_structure;
 int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
@@ -969,6 +1039,8 @@ int pz_circuit_structure_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb
                                     uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_circuit_structure_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                     uint32_t m_bits, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
+int pz_circuit_structure_partial_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                     size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_structure_info(const pz_structure* st, size_t* n_adv, size_t* n_adv_filled, size_t* n_lk, size_t* max_rows, size_t* n_constants,
                       size_t* n_cells, size_t* n_lookups, size_t* n_steps_g, size_t* n_steps_r);
 int pz_structure_arrays(const pz_structure* st, const uint8_t** d_selectors, const uint32_t** d_map_col, const uint32_t** d_map_row,

@@ -74,6 +74,10 @@ SIGNATURES = {
     "pz_paillier_wtally_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_ballot": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
     "pz_paillier_ballot_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
+    "pz_paillier_partial": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
+    "pz_paillier_partial_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
+    "pz_paillier_combine": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP]),
+    "pz_paillier_combine_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP]),
     "pz_paillier_sk_create":(C.c_int, [VP, C.c_uint32, VP, VP, VP, VP, C.POINTER(VP)]),
     "pz_paillier_sk_params": (C.c_int, [VP, VP, VP]),
     "pz_paillier_sk_free": (C.c_int, [VP, VP]),
@@ -185,6 +189,13 @@ SIGNATURES = {
                                             C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "pz_ballot_public_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, VP, C.c_size_t,
                                          C.POINTER(C.c_size_t)]),
+    "pz_circuit_structure_partial_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32,
+                                                   C.POINTER(VP)]),
+    "pz_partial_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "pz_partial_expand_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, C.c_size_t, C.c_size_t]),
+    "pz_partial_expand_cols_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, VP, C.c_size_t, C.c_size_t,
+                                             C.c_size_t, C.c_size_t]),
+    "pz_partial_public_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "pz_circuit_structure_wtally_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32,
                                                  C.POINTER(VP)]),
     "pz_structure_info": (C.c_int, [VP] + [C.POINTER(C.c_size_t)] * 9),

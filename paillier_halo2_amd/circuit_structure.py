@@ -302,7 +302,8 @@ class StructureArrays:
     # stream indices of the cells a circuit with the instance column exposes, in the column's row order: the limb cells of
     # n | g | c (encrypt, encrypt_uniform), n | g | m | c (decrypt), n | g | c1 | c2 | c (add), n | c_1 | .. | c_B | C (tally) or n | c_1 | .. | c_B | w_1 | .. |
     # w_B | C (wtally: a weight is ONE cell) -- pz_circuit_public_cells gives the same list -- or n | g | c_1 | .. | c_K | S (ballot: S is
-    # the sum's last cell, present for K >= 2; pz_ballot_public_cells)
+    # the sum's last cell, present for K >= 2; pz_ballot_public_cells) -- or n | v | h | c_1 | u_1 | .. | c_K | u_K (partial;
+    # pz_partial_public_cells)
     public_cells: Optional[np.ndarray] = None
 
 
@@ -321,7 +322,9 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     -- the shape is B, w_bits and the key size alone; kind 'decrypt': 'encrypt_uniform' with the message's limb cells exposed between
     g's and the result's (the statement n | g | m | c); kind 'ballot' (circuit kind 6):
     count = K ciphertexts under one key, each message ONE witness cell decomposed into m_bits in-circuit bits (the uniform circuit's
-    block), exp_r = the modulus n (its bits shape every r^n chain), for K >= 2 the sum of the messages -- the shape is K, m_bits and n.
+    block), exp_r = the modulus n (its bits shape every r^n chain), for K >= 2 the sum of the messages -- the shape is K, m_bits and n;
+    kind 'partial' (circuit kind 7): count = K ciphertexts one trustee opens under ONE share theta, an
+    assign_integer of 2 Ln limbs every chain decomposes (kind 2's pow_mod walk over all its limbs) -- the shape is K and the key size.
     device: None -> numpy arrays; a torch device ("cuda") -> the template is tiled THERE and `src` / `lookup_src` are tensors on it (at
     config c2 the tiled arrays are 3.2 GB: 0.9 s of host numpy against a few ms; `columns` takes either)."""
     dev = None
@@ -356,12 +359,14 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             constants.append(v)
         return const_id[v]
 
-    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot"):
+    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial"):
         raise ValueError(f"unknown circuit kind {kind!r}")
     # 'decrypt' (circuit kind 5) is the uniform-shape circuit cell for cell: the exposed list alone differs
     statement, kind = kind, ("encrypt_uniform" if kind == "decrypt" else kind)
-    if (kind in ("tally", "wtally", "ballot")) != (count is not None):
-        raise ValueError("count belongs to kinds 'tally', 'wtally' and 'ballot', which need it")
+    if (kind in ("tally", "wtally", "ballot", "partial")) != (count is not None):
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot' and 'partial', which need it")
+    if kind == "partial" and not 1 <= count <= layout.PARTIAL_MAX:
+        raise ValueError(f"a trustee opens count = 1 .. {layout.PARTIAL_MAX} ciphertexts in one proof, not {count}")
     if (kind == "ballot") != (m_bits is not None):
         raise ValueError("m_bits belongs to kind 'ballot', which needs it")
     if kind == "ballot":
@@ -386,6 +391,10 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
         g_c = x_c = y_c = []
         wt_c = [w.put() for _ in range(count)] if kind == "wtally" else []     # load_witness(w_i): one cell each, no gate
+    elif kind == "partial":
+        v_c = _assign(w, L, limb_bits, lb)
+        th_c = _assign(w, L, limb_bits, lb)
+        ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
     elif kind == "ballot":
         g_c = _assign(w, Ln, limb_bits, lb)
         ms_c = [w.put() for _ in range(count)]                                 # load_witness(m_i): one cell each, no gate
@@ -537,7 +546,34 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         return off, table[acc_blk + 2], ns
 
     n_steps = [0, 0]
-    if kind == "ballot":
+    if kind == "partial":
+        # pow_mod(v, theta), then per ciphertext the block mul_mod(c_j, c_j) and pow_mod(s_j, theta): kind 2's walk over ALL 2 Ln limbs
+        # of theta -- every chain's num_to_bits decomposes the SAME limb cells; a chain's power is its last select's outputs
+        ut = _uniform_template(L, limb_bits, lb)
+        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
+        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
+        ut_mask[ut.gates] = 1
+
+        def theta_chain(off: int, base_cells):
+            wc = _Walk(off)
+            one = wc.putc(1)
+            z2 = wc.putc(0)
+            off = flush(wc)
+            acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
+            sq_cells = np.asarray(base_cells, dtype=np.int64)
+            for li in range(L):
+                off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, th_c[li], limb_bits, acc_cells, sq_cells)
+            return off, acc_cells.tolist()
+
+        off, h_cells = theta_chain(off, v_c)
+        c_cells = [h_cells]
+        for j in range(count):
+            ct = np.asarray(ct_c[j], dtype=np.int64)[None, :]
+            off, s_cells = blocks(off, ct, ct)
+            off, u_cells = theta_chain(off, s_cells[0])
+            c_cells.append(u_cells)
+        n_steps[0] = 2 * L * limb_bits
+    elif kind == "ballot":
         # per ciphertext: pow_mod(g_ext, m_i) over m_bits in-circuit bits (the weighted tally's chain on the base g, extended by the
         # load_zero cell), pow_mod_fixed_exp(r_i_ext, n), the final mul_mod; then per ciphertext assign res_i + assert_equal_fresh
         ut = _uniform_template(L, limb_bits, lb)
@@ -623,7 +659,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         n_steps[0] = nb
     else:
         off, rfin = blocks(off, np.asarray(ext_l(x_c), dtype=np.int64)[None, :], np.asarray(ext_l(y_c), dtype=np.int64)[None, :])
-    roots = c_cells if kind == "ballot" else [rfin[0].tolist()]      # the ballot: one result per ciphertext
+    roots = c_cells if kind in ("ballot", "partial") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
     ws = _Walk(off)
     res_all, eq_cells = [], []
     for c_limbs in roots:
@@ -646,7 +682,11 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         src, lookup_src = cat(parts_src), cat(parts_lk)
     for eq_cell in eq_cells:
         src[eq_cell] = -(1 + cid(1))      # assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
-    if kind == "ballot":
+    if kind == "partial":
+        exposed = list(n_c) + list(v_c) + res_all[:L]
+        for j in range(count):
+            exposed += list(ct_c[j]) + res_all[(j + 1) * L:(j + 2) * L]
+    elif kind == "ballot":
         exposed = list(n_c) + list(g_c) + res_all + ([sum_c] if sum_c is not None else [])
     elif kind in ("tally", "wtally"):
         exposed = list(n_c) + [c for ct in ct_c for c in ct] + list(wt_c) + list(res_c)

@@ -1122,6 +1122,160 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_ballot_enc(co
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
+// ---- a trustee's partial decryptions (pz_paillier_partial): h = v^theta and u_j = (c_j^2)^theta mod n^2 for K ciphertexts under ONE
+// secret share theta of e_bits bits.  K + 1 teams in one launch: team 0 runs pow_mod(v, theta), team j >= 1 first squares c_j itself
+// (record j - 1) and then runs pow_mod(s_j, theta) -- k_wtally_pow's chain, (acc, sq) then (sq, sq) for EVERY bit, the trailing square
+// kept -- so no team waits for another: no ticket, no spin, no hand-off.  The Barrett constants come from k_tally_setup, once for all.
+// theta is SECRET and e_bits long (many words): bit t is read from word t / 64, an address that follows the loop counter alone, and
+// reaches the accumulator as a lane-wise mask over both candidates (k_ballot_enc's select), never as a branch.  Every trip count is a
+// launch argument.  (What a mul_mod does with its VALUES is K3's as everywhere: the Barrett correction's trip count follows the operands.)
+// recs (may be null: the values only): the K squaring records, then chain i (0 .. K), bit t at records K + 2 (i e_bits + t) and the next.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_partial_pow(const u64* __restrict__ mod, const u64* __restrict__ v,
+                                                                                  const u64* __restrict__ cts, const u64* __restrict__ theta,
+                                                                                  unsigned e_bits, unsigned count, u64* __restrict__ recs,
+                                                                                  u64* __restrict__ h_out, u64* __restrict__ u_out, unsigned L,
+                                                                                  u32* __restrict__ status) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (mod[3 * C + 1] == 0) return;   // zero modulus (the same word for every workgroup)
+    const unsigned wave = threadIdx.x >> 6;
+    TeamCtx<E> T;
+    T.buf = s_team;
+    T.w = wave;
+    T.parity = 0;
+    TeamMul<E> tmul{&T};
+    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
+        u64* z = (u64*)s_team;
+        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
+        __syncthreads();
+    }
+    BarrettCtx<E> B;
+    B.sm = s_scratch[wave];
+    B.limbs = L;
+    B.s = (unsigned)mod[3 * C];
+    B.M = ld_load<E>(mod, C);
+    B.mu = ld_load<E>(mod + C, C);
+    const size_t chain = blockIdx.x;   // 0: the key's base v; j >= 1: ciphertext j - 1
+    if (chain > count) return;
+    const bool writer = wave == 0 && recs != nullptr;   // the four waves of the team hold the same values: one of them writes
+    auto record = [&](u64* o, const LD<E>& a, const LD<E>& b, const LD<E>& q, const LD<E>& r) {
+        ld_store(o, a, L);
+        ld_store(o + L, b, L);
+        ld_store(o + 2 * L, q, L);
+        ld_store(o + 3 * L, r, L);
+    };
+    unsigned st = ST_OK;
+    LD<E> sq = ld_load<E>(chain == 0 ? v : cts + (chain - 1) * L, L);
+    {
+        LD<E> d;
+        if (!ld_sub(d, sq, ld_load<E>(mod + 2 * C, C))) st |= ST_RANGE;   // v or a ciphertext >= n^2 (both public)
+    }
+    if (chain != 0) {   // s_j = c_j^2: the chain's base
+        LD<E> q, r;
+        st |= mul_mod(B, q, r, sq, sq, tmul);
+        if (writer) record(recs + (chain - 1) * 4 * (size_t)L, sq, sq, q, r);
+        sq = r;
+    }
+    LD<E> acc = ld_small<E>(1);
+    u64* o = writer ? recs + ((size_t)count + chain * 2 * (size_t)e_bits) * 4 * L : nullptr;
+    for (unsigned t = 0; t < e_bits; ++t) {
+        LD<E> q, r;
+        st |= mul_mod(B, q, r, acc, sq, tmul);
+        if (writer) record(o, acc, sq, q, r);
+        u64 keep = 0ull - ((theta[t >> 6] >> (t & 63)) & 1);   // select(bit, muled, acc) under a mask; the word's address is t's alone
+        asm volatile("" : "+v"(keep));                          // a per-lane value from here on: nothing below can become a branch
+#pragma unroll
+        for (int e = 0; e < E; ++e) acc.v[e] = (r.v[e] & keep) | (acc.v[e] & ~keep);
+        st |= mul_mod(B, q, r, sq, sq, tmul);
+        if (writer) {
+            record(o + 4 * (size_t)L, sq, sq, q, r);
+            o += 8 * (size_t)L;
+        }
+        sq = r;
+    }
+    if (wave == 0) ld_store(chain == 0 ? h_out : u_out + (chain - 1) * L, acc, L);
+    if (st && lane_id() == 0) atomicOr(status, st);
+}
+
+// ---- the combiner of a threshold decryption (pz_paillier_combine): per ciphertext U = prod_i u_i mod n^2 over the T trustees' partials
+// (T - 1 products, one team per ciphertext, one launch), then decryption's last step on U: U mod n must be 1, m = floor(U / n) mu2 mod n
+// (k_dec_pow's DEC_LFN tail, the same three mul_mods by n's Barrett block at this capacity).  Nothing here is secret: the partials are
+// published with their proofs.  partials trustee-major: trustee i, ciphertext j at (i count + j) L.  flags: bit 0 U mod n != 1 (m = 0),
+// bit 1 a partial >= n^2 (m = 0, no product is formed), bit 2 an internal check failed.
+enum { CMB_F_NOT_ONE = 1, CMB_F_RANGE = 2, CMB_F_INTERNAL = 4 };
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_partial_combine(const u64* __restrict__ mod2, const u64* __restrict__ modn,
+                                                                                      const u64* __restrict__ partials, unsigned count,
+                                                                                      unsigned trustees, const u64* __restrict__ mu2,
+                                                                                      u64* __restrict__ m_out, uint8_t* __restrict__ flags,
+                                                                                      unsigned Ln) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (mod2[3 * C + 1] == 0 || modn[3 * C + 1] == 0) return;   // zero modulus (refused on the host: no launch reaches here with one)
+    const unsigned wave = threadIdx.x >> 6, lane = lane_id(), L = 2 * Ln;
+    TeamCtx<E> T;
+    T.buf = s_team;
+    T.w = wave;
+    T.parity = 0;
+    TeamMul<E> tmul{&T};
+    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
+        u64* z = (u64*)s_team;
+        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
+        __syncthreads();
+    }
+    const size_t j = blockIdx.x;
+    if (j >= count) return;
+    {   // a partial >= n^2 (public).  The four waves hold the same values: the team leaves together
+        const LD<E> n2 = ld_load<E>(mod2 + 2 * C, C);
+        bool over = false;
+        for (unsigned i = 0; i < trustees; ++i) {
+            LD<E> d;
+            over |= !ld_sub(d, ld_load<E>(partials + ((size_t)i * count + j) * L, L), n2);
+        }
+        if (over) {
+            if (wave == 0) {
+                ld_store(m_out + j * Ln, ld_zero<E>(), Ln);
+                if (lane == 0) flags[j] = CMB_F_RANGE;
+            }
+            return;
+        }
+    }
+    BarrettCtx<E> B;
+    B.sm = s_scratch[wave];
+    B.limbs = L;
+    B.s = (unsigned)mod2[3 * C];
+    B.M = ld_load<E>(mod2, C);
+    B.mu = ld_load<E>(mod2 + C, C);
+    unsigned st = ST_OK;
+    LD<E> U = ld_load<E>(partials + j * L, L);
+    for (unsigned i = 1; i < trustees; ++i) {
+        LD<E> q, r;
+        st |= mul_mod(B, q, r, U, ld_load<E>(partials + ((size_t)i * count + j) * L, L), tmul);
+        U = r;
+    }
+    // U mod n must be 1; plaintext = floor(U / n) * mu2 mod n
+    BarrettCtx<E> N;
+    N.sm = s_scratch[wave];
+    N.limbs = L;
+    N.s = (unsigned)modn[3 * C];
+    N.M = ld_load<E>(modn, C);
+    N.mu = ld_load<E>(modn + C, C);
+    const LD<E> one = ld_small<E>(1);
+    LD<E> x, rem, q, m;
+    st |= mul_mod(N, x, rem, U, one, tmul);
+    bool ne = false;
+#pragma unroll
+    for (int e = 0; e < E; ++e) ne |= rem.v[e] != one.v[e];
+    const bool bad = __ballot(ne) != 0;
+    st |= mul_mod(N, q, m, x, ld_load<E>(mu2, Ln), tmul);
+    if (bad) m = ld_zero<E>();
+    if (wave == 0) {
+        ld_store(m_out + j * Ln, m, Ln);
+        if (lane == 0) flags[j] = (uint8_t)((bad ? CMB_F_NOT_ONE : 0) | (st ? CMB_F_INTERNAL : 0));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
@@ -1741,6 +1895,183 @@ extern "C" int pz_paillier_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t coun
                                       const uint64_t* ms, const uint64_t* rs, uint64_t* d_steps_out, size_t steps_cap, uint32_t* n_steps_r,
                                       uint64_t* c_out) {
     return ballot_impl(ctx, limbs_n, count, m_bits, n, g, ms, rs, d_steps_out, 1, steps_cap, n_steps_r, c_out);
+}
+
+// A trustee's partial decryptions: h = v^theta, u_j = (c_j^2)^theta mod n^2 for `count` ciphertexts under one share
+// (k_partial_pow, count + 1 teams, one launch).  Records: the count squarings, then chain i at count + i 2 e_bits.  theta is the
+// trustee's secret: its staged copy (and, in the host form, the staged records, whose quotients and accumulators follow its bits) are
+// overwritten before the call returns, on every path past the staging.
+#define K3_PARTIAL_MAX 1024
+static bool is_zero_limbs(const uint64_t* a, uint32_t n) {
+    uint64_t any = 0;
+    for (uint32_t i = 0; i < n; ++i) any |= a[i];
+    return any == 0;
+}
+struct PartialArgs {
+    uint32_t Ln, e_bits;
+    size_t count, n_rec;
+    const uint64_t *n, *v, *theta, *cts;
+    uint64_t *steps_out, *h_out, *u_out;
+    int steps_on_device;
+    u64 *d_n, *d_v, *d_cts, *d_theta, *d_out, *d_mod, *d_steps;
+    u32* d_status;
+};
+static int partial_run(pz_ctx* ctx, const PartialArgs& a) {
+    const unsigned L = 2 * a.Ln, C = L <= 64 ? 64 : 128;
+    const size_t nb = (size_t)a.Ln * 8, lb = (size_t)L * 8;
+    HIPCHK(ctx, hipMemcpyAsync(a.d_n, a.n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_v, a.v, lb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_cts, a.cts, a.count * lb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_theta, a.theta, lb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(a.d_status, 0, 4, ctx->stream));
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        const dim3 grid((unsigned)a.count + 1), block(64 * K3_TEAM);
+        if (C == 64) {
+            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, a.d_n, a.Ln, 1u, a.d_mod, a.d_status);
+            hipLaunchKernelGGL(k_partial_pow<1>, grid, block, 0, ctx->stream, a.d_mod, a.d_v, a.d_cts, a.d_theta, a.e_bits, (unsigned)a.count,
+                               a.d_steps, a.d_out, a.d_out + L, L, a.d_status);
+        } else {
+            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, a.d_n, a.Ln, 1u, a.d_mod, a.d_status);
+            hipLaunchKernelGGL(k_partial_pow<2>, grid, block, 0, ctx->stream, a.d_mod, a.d_v, a.d_cts, a.d_theta, a.e_bits, (unsigned)a.count,
+                               a.d_steps, a.d_out, a.d_out + L, L, a.d_status);
+        }
+        HIPCHK(ctx, hipGetLastError());
+    }
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(a.h_out, a.d_out, lb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.u_out, a.d_out + L, a.count * lb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&st, a.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (a.steps_out && !a.steps_on_device)
+        HIPCHK(ctx, hipMemcpyAsync(a.steps_out, a.d_steps, a.n_rec * 4 * lb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return status_to_rc(ctx, st);
+}
+static int partial_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t e_bits, const uint64_t* n, const uint64_t* v, const uint64_t* theta,
+                        const uint64_t* cts, uint64_t* steps_out, int steps_on_device, size_t steps_cap, uint64_t* h_out, uint64_t* u_out) {
+    if (!ctx || !n || !v || !theta || !cts || !h_out || !u_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_PARTIAL_MAX || e_bits < 1 || e_bits > 128 * (uint64_t)Ln) return PZ_ERR_INVALID;
+    if (2 * (uint64_t)Ln > 128) return PZ_ERR_UNSUPPORTED;
+    const unsigned L = 2 * Ln;
+    const size_t n_rec = count + (count + 1) * 2 * (size_t)e_bits;
+    if (steps_out && steps_cap < n_rec) return PZ_ERR_CAPACITY;
+    for (uint32_t k = e_bits / 64; k < L; ++k)   // before any launch: the chain reads e_bits bits and the circuit's decomposition no more
+        if (k == e_bits / 64 ? theta[k] >> (e_bits & 63) : theta[k]) return PZ_ERR_MESSAGE_RANGE;
+    if (is_zero_limbs(n, Ln)) return PZ_ERR_ZERO_MODULUS;
+    PZ_ENTER(ctx);
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8;
+    const unsigned C = L <= 64 ? 64 : 128;
+    // n | v | c_1 .. c_count | theta | h | u_1 .. u_count | Barrett constants | status
+    const size_t pub_bytes = (nb + lb + count * lb + 255) & ~(size_t)255, sec_bytes = (lb + 255) & ~(size_t)255;
+    const size_t out_bytes = ((count + 1) * lb + 255) & ~(size_t)255, mod_bytes = ((size_t)3 * C + 2) * 8;
+    void* d;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, pub_bytes + sec_bytes + out_bytes + mod_bytes + 256, &d));
+    char* p = (char*)d;
+    PartialArgs a{};
+    a.Ln = Ln; a.e_bits = e_bits; a.count = count; a.n_rec = n_rec;
+    a.n = n; a.v = v; a.theta = theta; a.cts = cts; a.steps_out = steps_out; a.h_out = h_out; a.u_out = u_out;
+    a.steps_on_device = steps_on_device;
+    a.d_n = (u64*)p;
+    a.d_v = (u64*)(p + nb);
+    a.d_cts = (u64*)(p + nb + lb);
+    a.d_theta = (u64*)(p + pub_bytes);
+    a.d_out = (u64*)(p + pub_bytes + sec_bytes);
+    a.d_mod = (u64*)(p + pub_bytes + sec_bytes + out_bytes);
+    a.d_status = (u32*)(p + pub_bytes + sec_bytes + out_bytes + mod_bytes + 64);
+    a.d_steps = steps_on_device ? steps_out : nullptr;
+    const size_t rec_bytes = steps_out && !steps_on_device ? n_rec * 4 * lb : 0;
+    if (rec_bytes) {
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_B, rec_bytes, &t));
+        a.d_steps = (u64*)t;
+    }
+    const int rc = partial_run(ctx, a);
+    hipError_t e = hipMemsetAsync(a.d_theta, 0, sec_bytes, ctx->stream);
+    if (e == hipSuccess && rec_bytes) e = hipMemsetAsync(a.d_steps, 0, rec_bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (rc != PZ_OK) return rc;
+    HIPCHK(ctx, e);
+    return PZ_OK;
+}
+extern "C" int pz_paillier_partial(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t e_bits, const uint64_t* n, const uint64_t* v,
+                                   const uint64_t* theta, const uint64_t* cts, uint64_t* steps_out, size_t steps_cap, uint64_t* h_out,
+                                   uint64_t* u_out) {
+    return partial_impl(ctx, limbs_n, count, e_bits, n, v, theta, cts, steps_out, 0, steps_cap, h_out, u_out);
+}
+extern "C" int pz_paillier_partial_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t e_bits, const uint64_t* n, const uint64_t* v,
+                                       const uint64_t* theta, const uint64_t* cts, uint64_t* d_steps_out, size_t steps_cap, uint64_t* h_out,
+                                       uint64_t* u_out) {
+    return partial_impl(ctx, limbs_n, count, e_bits, n, v, theta, cts, d_steps_out, 1, steps_cap, h_out, u_out);
+}
+
+// The combiner: m_j = L(prod_i u_ij mod n^2) mu2 mod n (k_partial_combine, one team per ciphertext, one launch).  n and mu2 are the
+// public threshold key's (HOST words in both forms); the host form stages the partials and fetches m and the flags, the device form
+// queues everything on the context's stream and returns.
+static int combine_impl(pz_ctx* ctx, uint32_t Ln, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
+                        const uint64_t* partials, uint64_t* m_out, uint8_t* flags_out, int on_device) {
+    if (!ctx || !n || !mu2 || !partials || !m_out || !flags_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_PARTIAL_MAX || trustees < 1 || trustees > 256) return PZ_ERR_INVALID;
+    if (2 * (uint64_t)Ln > 128) return PZ_ERR_UNSUPPORTED;
+    if (is_zero_limbs(n, Ln)) return PZ_ERR_ZERO_MODULUS;
+    PZ_ENTER(ctx);
+    const unsigned L = 2 * Ln, C = L <= 64 ? 64 : 128;
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, mod_words = (size_t)3 * C + 2;
+    // n | mu2 | Barrett constants of n^2 and of n | status | host form: the partials, m, the flags
+    const size_t key_bytes = (2 * nb + 255) & ~(size_t)255, mod_bytes = 2 * mod_words * 8 + 64;
+    const size_t io_bytes = on_device ? 0 : trustees * count * lb + count * nb + ((count + 7) & ~(size_t)7);
+    void* ws;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, key_bytes + mod_bytes + io_bytes + 64, &ws));
+    char* p = (char*)ws;
+    u64 *d_n = (u64*)p, *d_mu2 = d_n + Ln, *d_mod2 = (u64*)(p + key_bytes), *d_modn = d_mod2 + mod_words;
+    u32* d_status = (u32*)(d_modn + mod_words);
+    const u64* d_parts = partials;
+    u64* d_m = m_out;
+    uint8_t* d_flags = flags_out;
+    if (!on_device) {
+        u64* q = (u64*)(p + key_bytes + mod_bytes);
+        d_parts = q;
+        d_m = q + trustees * count * L;
+        d_flags = (uint8_t*)(d_m + count * Ln);
+        HIPCHK(ctx, hipMemcpyAsync(q, partials, trustees * count * lb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_n, n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_mu2, mu2, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_status, 0, 4, ctx->stream));
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        const dim3 grid((unsigned)count), block(64 * K3_TEAM);
+        if (C == 64) {
+            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod2, d_status);
+            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 0u, d_modn, d_status);
+            hipLaunchKernelGGL(k_partial_combine<1>, grid, block, 0, ctx->stream, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)trustees,
+                               d_mu2, d_m, d_flags, Ln);
+        } else {
+            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod2, d_status);
+            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 0u, d_modn, d_status);
+            hipLaunchKernelGGL(k_partial_combine<2>, grid, block, 0, ctx->stream, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)trustees,
+                               d_mu2, d_m, d_flags, Ln);
+        }
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (on_device) return PZ_OK;
+    HIPCHK(ctx, hipMemcpyAsync(m_out, d_m, count * nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(flags_out, d_flags, count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned any = 0;
+    for (size_t i = 0; i < count; ++i) any |= flags_out[i];
+    if (any & CMB_F_INTERNAL) {
+        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: internal consistency check failed (combination)");
+        return PZ_ERR_HIP;
+    }
+    return (any & CMB_F_RANGE) ? PZ_ERR_RANGE : PZ_OK;
+}
+extern "C" int pz_paillier_combine(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
+                                   const uint64_t* partials, uint64_t* m_out, uint8_t* flags_out) {
+    return combine_impl(ctx, limbs_n, count, trustees, n, mu2, partials, m_out, flags_out, 0);
+}
+extern "C" int pz_paillier_combine_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
+                                       const uint64_t* d_partials, uint64_t* d_m_out, uint8_t* d_flags_out) {
+    return combine_impl(ctx, limbs_n, count, trustees, n, mu2, d_partials, d_m_out, d_flags_out, 1);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -283,6 +283,30 @@ int ballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bi
     return PZ_OK;
 }
 
+// a trustee's partial decryptions (kind 7, `count` ciphertexts): n | v | h | c_1 | u_1 | .. | c_K | u_K.  n's limb cells head the stream;
+// v, theta and the c_j are the full-width assign_integer blocks that follow (theta is the witness: not exposed); h and the u_j are the
+// assign_integer(2 limbs_n) in front of each of the count + 1 assert_equal_fresh closing the stream.
+int partial_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, std::vector<uint64_t>& cells) {
+    if (limbs_n == 0) return PZ_ERR_INVALID;
+    size_t total = 0, a_in = 0, a_wide = 0, a_eq = 0;
+    PZCHK(pz_partial_cells(limbs_n, limb_bits, lookup_bits, count, &total, nullptr));
+    PZCHK(pz_op_cells(0, limbs_n, limb_bits, lookup_bits, &a_in, nullptr));
+    PZCHK(pz_op_cells(0, 2 * limbs_n, limb_bits, lookup_bits, &a_wide, nullptr));
+    PZCHK(pz_op_cells(5, 2 * limbs_n, limb_bits, lookup_bits, &a_eq, nullptr));
+    if (total < a_in + (count + 2) * a_wide + (count + 1) * (a_wide + a_eq)) return PZ_ERR_INTERNAL;
+    const size_t res = total - (count + 1) * (a_wide + a_eq);
+    const uint32_t L = 2 * limbs_n;
+    cells.clear();
+    for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(j);
+    for (uint32_t j = 0; j < L; ++j) cells.push_back(a_in + j);
+    for (uint32_t j = 0; j < L; ++j) cells.push_back(res + j);
+    for (size_t i = 1; i <= count; ++i) {
+        for (uint32_t j = 0; j < L; ++j) cells.push_back(a_in + (1 + i) * a_wide + j);
+        for (uint32_t j = 0; j < L; ++j) cells.push_back(res + i * (a_wide + a_eq) + j);
+    }
+    return PZ_OK;
+}
+
 }   // namespace
 
 int pz_instance_eval_launch(pz_ctx* ctx, uint32_t k, const uint64_t omega[4], const uint64_t n_inv[4], const uint64_t* d_instances, size_t L,
@@ -347,6 +371,23 @@ extern "C" int pz_ballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint
     return PZ_OK;
 }
 
+extern "C" int pz_partial_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint64_t* cells_out,
+                                       size_t capacity, size_t* n_public) {
+    if (!n_public) return PZ_ERR_INVALID;
+    std::vector<uint64_t> cells;
+    try {
+        PZCHK(partial_public_cells(limbs_n, limb_bits, lookup_bits, count, cells));
+    } catch (const std::bad_alloc&) {
+        return PZ_ERR_OOM;
+    }
+    *n_public = cells.size();
+    if (cells_out) {
+        if (capacity < cells.size()) return PZ_ERR_CAPACITY;
+        memcpy(cells_out, cells.data(), cells.size() * 8);
+    }
+    return PZ_OK;
+}
+
 extern "C" int pz_structure_expose(pz_structure* st) {
     if (!st || !st->ctx || st->n_instance) return PZ_ERR_INVALID;
     pz_ctx* ctx = st->ctx;
@@ -355,6 +396,8 @@ extern "C" int pz_structure_expose(pz_structure* st) {
     try {
         if (st->kind == 6)
             PZCHK(ballot_public_cells(st->limbs_n, st->limb_bits, st->lookup_bits, st->count, (uint32_t)(st->n_steps_g / 2), st->n_steps_r, cells));
+        else if (st->kind == 7)
+            PZCHK(partial_public_cells(st->limbs_n, st->limb_bits, st->lookup_bits, st->count, cells));
         else
             PZCHK(public_cells(st->kind, st->limbs_n, st->limb_bits, st->lookup_bits, st->n_steps_g, st->n_steps_r, cells));
     } catch (const std::bad_alloc&) {

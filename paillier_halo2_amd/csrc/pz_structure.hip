@@ -432,6 +432,9 @@ struct Stream {
 // kind 6 (the ballot): n, g, `count` load_witness cells (the messages), for count >= 2 FlexGate::sum over them,
 // assign_integer(r_i) for every entry, square + refresh, load_zero; per entry pow_mod(g_ext, m_i) over w_bits (= m_bits) in-circuit bits,
 // pow_mod_fixed_exp(r_i_ext, exp_r = n) and the final block; then per entry res_i and assert_equal_fresh.  Five parts per entry.
+// kind 7 (a trustee's partial decryptions): n, then v, theta and `count` ciphertexts at full width, square +
+// refresh, load_zero; pow_mod(v, theta) as kind 2 emits it with theta's 2 Ln limb cells as the num_to_bits inputs; per ciphertext the
+// block mul_mod(c_j, c_j) and pow_mod(s_j, theta) from its remainder; then assign_integer + assert_equal_fresh for h and for every u_j.
 int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, unsigned w_bits, Stream& S) {
     const unsigned L = 2 * Ln;
     S.tmpls.reserve(2);                  // (references to the templates stay valid when a circuit with in-circuit bits adds the second one)
@@ -459,6 +462,10 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             }
         }
         for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, Ln, W, lb));
+    } else if (kind == 7) {
+        g_c = assign(w, L, W, lb);   // v: the key's base, full width
+        x_c = assign(w, L, W, lb);   // theta: the share, 2 Ln limbs
+        for (size_t i = 0; i < count; ++i) ct_c.push_back(assign(w, L, W, lb));
     } else if (kind == 3 || kind == 4) {
         for (size_t i = 0; i < count; ++i) ct_c.push_back(assign(w, L, W, lb));
         if (kind == 4)
@@ -623,6 +630,29 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             off = S.blocks(off, 0, std::vector<i64>(acc_cells), std::vector<i64>(rn), {}, 1);
         }
         S.n_steps_g = 2 * (size_t)w_bits;
+    } else if (kind == 7) {
+        S.tmpls.push_back(uniform_template(L, W, lb));
+        S.bind_template_constants(1);
+        // pow_mod(base, theta): kind 2's walk over ALL 2 Ln limbs of theta -- every chain decomposes the SAME limb cells
+        auto theta_chain = [&](const std::vector<i64>& base) {
+            Walk wc(off);
+            const i64 one = wc.putc(c_small(1)), z2 = wc.putc(c_small(0));
+            off = S.flush(wc);
+            std::vector<i64> acc_cells(L, z2), sq_cells = base;
+            acc_cells[0] = one;
+            for (unsigned li = 0; li < L; ++li) {
+                Walk wb(off);
+                off = bit_chain(off, wb, x_c[li], W, acc_cells, sq_cells);
+            }
+            roots.push_back(acc_cells);
+        };
+        theta_chain(g_c);
+        for (size_t i = 0; i < count; ++i) {
+            const std::vector<i64> s_c = block_r(off);   // s_j = c_j^2: the chain's base
+            off = S.blocks(off, 0, std::vector<i64>(ct_c[i]), std::vector<i64>(ct_c[i]), {}, 1);
+            theta_chain(s_c);
+        }
+        S.n_steps_g = 2 * (size_t)L * W;
     } else if (kind == 3) {
         // operands as (producing block | -(1 + ciphertext)); blocks are numbered as the loop creates them: level-major
         std::vector<i64> cur(count), a_blk, b_blk;
@@ -696,7 +726,7 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
         off = S.blocks(off, 0, std::vector<i64>(gm), std::vector<i64>(rn), {}, 1);
     }
     // ---- suffix: assign_integer(res), assert_equal_fresh (the ballot: once per entry)
-    if (kind != 6) roots.push_back(root_c);
+    if (kind < 6) roots.push_back(root_c);
     Walk ws(off);
     std::vector<i64> eq_cells;
     for (const std::vector<i64>& root : roots) {
@@ -995,13 +1025,14 @@ extern "C" int pz_structure_arrays(const pz_structure* st, const uint8_t** d_sel
 static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, const uint64_t* exp_g,
                           const uint64_t* exp_r, size_t count, uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors,
                           pz_structure** out) {
-    if (!ctx || !out || kind < 0 || kind > 6 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+    if (!ctx || !out || kind < 0 || kind > 7 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
     const int handle_kind = kind;   // kind 5 ("decrypt") is kind 2's circuit under another statement: pz_structure_expose alone tells them apart
     if (kind == 5) kind = 2;
     if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
     if (kind == 4 && (count < 1 || count > 65536 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
     if (limb_bits < 16 || limb_bits > 90 || lookup_bits == 0 || lookup_bits >= k || k < 4 || k > 24 || lookup_bits >= limb_bits) return PZ_ERR_INVALID;
     if (kind == 6 && (count < 1 || count > 1024 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
+    if (kind == 7 && (count < 1 || count > 1024)) return PZ_ERR_INVALID;
     if (((kind == 0 || kind == 2 || kind == 6) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
     const i64 n = (i64)1 << k;
     const i64 unusable = (i64)blinding_factors + 3;
@@ -1030,7 +1061,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     std::unique_ptr<pz_structure> st(new (std::nothrow) pz_structure);
     if (!st) return PZ_ERR_OOM;
     st->k = k;
-    st->count = kind == 6 ? count : 0;
+    st->count = kind >= 6 ? count : 0;
     st->kind = handle_kind; st->limbs_n = limbs_n; st->limb_bits = limb_bits; st->lookup_bits = lookup_bits;
     st->n_adv = (size_t)A; st->n_used = (size_t)A_used; st->n_lk = (size_t)Lk; st->max_rows = (size_t)max_rows;
     st->n_cells = (size_t)NC; st->n_lookups = (size_t)NL; st->n_steps_g = S.n_steps_g; st->n_steps_r = S.n_steps_r;
@@ -1178,4 +1209,9 @@ extern "C" int pz_circuit_structure_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, ui
                                                uint32_t m_bits, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
                                                pz_structure** out) {
     return structure_impl(ctx, 6, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, m_bits, minimum_rows, blinding_factors, out);
+}
+// a trustee's partial decryptions (kind 7): count ciphertexts (1 .. 1024) opened under one share; the shape is count and the key size alone
+extern "C" int pz_circuit_structure_partial_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                                size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
+    return structure_impl(ctx, 7, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, minimum_rows, blinding_factors, out);
 }

@@ -798,7 +798,7 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
     // ---- assign_integer of n, g, x, y (Ln limbs) and of res (2 Ln limbs)
     for (unsigned which = 0; which < 5; ++which) {
         if (which >= C.n_in && which < 4) continue;
-        if (which == 4 && C.kind == 6) continue;   // (the ballot's K results are k_ballot_misc's)
+        if (which == 4 && C.kind >= 6) continue;   // (the ballot's K results are k_ballot_misc's, a trustee's K + 1 k_partial_misc's)
         const unsigned nl = which < 4 ? Ln : nf;
         const u64(*X)[2] = which < 4 ? s_in[which] : s_res;
         const CellPtr a = adv + (which < 4 ? C.a_assign[which] : C.a_res);
@@ -837,19 +837,19 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
             fp_store(lk + C.l_refresh + t, cv_to_fr(rc_lk_cell(LIMB(s_fresh, t / C.rc_lk), W, lb, t % C.rc_lk)));
     // ---- load_zero; assign_constant(1) + load_zero of both pow_mod_fixed_exp
     if (tid == 0) {
-        if (C.kind < 3 || C.kind == 6) fp_store(adv + C.a_zero, fp_zero<FrTag>());   // (the tallies extend nothing: no load_zero)
+        if (C.kind < 3 || C.kind >= 6) fp_store(adv + C.a_zero, fp_zero<FrTag>());   // (the tallies extend nothing: no load_zero)
         if (C.kind == 0 || C.kind == 2)
             for (int k = 0; k < 2; ++k) {
                 fp_store(adv + C.a_pow[k], fp_one<FrTag>());
                 fp_store(adv + C.a_pow[k] + 1, fp_zero<FrTag>());
             }
-        if (C.kind != 6) {
+        if (C.kind < 6) {
             fp_store(adv + C.a_eq, fp_zero<FrTag>());
             fp_store(adv + C.a_eq + 1, fp_one<FrTag>());
         }
     }
     // ---- assert_equal_fresh(c, res)
-    for (unsigned t = tid; t < (C.kind != 6 ? 16 * nf : 0u); t += blockDim.x) {
+    for (unsigned t = tid; t < (C.kind < 6 ? 16 * nf : 0u); t += blockDim.x) {
         const unsigned i = t / 16, p = t % 16;
         Fr v;
         if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, i), LIMB(s_res, i), p));
@@ -1538,6 +1538,217 @@ extern "C" int pz_ballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t
     if (!d_col_starts || lookup_rows == 0 || lookup_rows > col_stride) return PZ_ERR_INVALID;
     return ballot_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, inputs, d_steps, d_modulus, d_advice, d_lookup,
                               lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows);
+}
+
+// ---- a trustee's partial decryptions (circuit kind 7): K ciphertexts opened under ONE share theta.  Stream:
+// assign n; assign v, theta, c_1 .. c_K at full width; square + refresh, load_zero; chain 0 = pow_mod(v, theta) as kind 2 emits it
+// ([1, 0], then per limb of theta num_to_bits and W x (mul_mod, select, square_mod)) over ALL 2 Ln limbs; per ciphertext the block
+// mul_mod(c_j, c_j) and chain j = pow_mod(s_j, theta); then assign h + assert_equal_fresh and the same for every u_j.
+// inputs: n | v | theta | c_1 .. c_K | h | u_1 .. u_K.  Records (pz_paillier_partial_dev): the K squarings, then chain i at K + i 2 E,
+// E = 2 Ln W bits.  Lookups follow the STREAM: chain 0's, then per ciphertext its squaring's and its chain's.
+#define PARTIAL_MAX 1024
+struct PartialP {
+    size_t K, E, a_wide, l_wide, a_ch, l_ch, nbc, bit_stride, limb_stride, chain_cells, a_res, l_res, res_stride;
+    size_t in_v, in_theta, in_cts, in_res;   // word offsets inside `inputs`
+    unsigned top;                            // theta's bit E - 1: a chain's result is its last product (1) or its last accumulator (0)
+};
+static int make_partial_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, CircP& C, PartialP& B, size_t* adv_total,
+                               size_t* lk_total) {
+    if (count < 1 || count > PARTIAL_MAX) return PZ_ERR_INVALID;
+    if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
+    memset(&C, 0, sizeof C);
+    memset(&B, 0, sizeof B);
+    PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
+    C.Ln = limbs_n;
+    C.kind = 7;
+    C.words_n = (limbs_n * limb_bits + 63) / 64;
+    C.rc_adv = C.e.rc64_adv;
+    C.rc_lk = C.e.rc64_lk;
+    PZCHK(refresh_aux_host(limb_bits, limbs_n, limbs_n, C.inc, &C.nf));
+    if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
+    const size_t W = limb_bits, L = C.e.L;
+    B.K = count;
+    B.E = L * W;
+    size_t a = 0, l = 0;
+    const size_t asg_a = (size_t)limbs_n * (1 + C.rc_adv), asg_l = (size_t)limbs_n * C.rc_lk;
+    C.n_in = 1;
+    C.a_assign[0] = a; C.l_assign[0] = l; a += asg_a; l += asg_l;
+    B.a_wide = a; B.l_wide = l;
+    a += (count + 2) * 2 * asg_a; l += (count + 2) * 2 * asg_l;
+    C.a_square = a;
+    a += 1;
+    for (unsigned i = 0; i < 2 * limbs_n - 1; ++i) a += 1 + 3 * ((size_t)i + 1);
+    C.a_refresh = a; C.l_refresh = l;
+    a += 1;
+    for (unsigned i = 0; i < C.nf; ++i) a += ((size_t)C.inc[i] + 1) * 22 + (size_t)C.inc[i] * 4;
+    a += (size_t)C.nf * C.rc_adv;
+    l += (size_t)C.nf * C.rc_lk;
+    C.a_zero = a; a += 1;
+    B.nbc = 7 * W - 2;
+    B.bit_stride = 2 * C.e.cells + 8 * L;
+    B.limb_stride = B.nbc + W * B.bit_stride;
+    B.chain_cells = 2 + L * B.limb_stride;
+    B.a_ch = a; B.l_ch = l;
+    a += (count + 1) * B.chain_cells + count * C.e.cells;
+    l += (count + (count + 1) * 2 * B.E) * C.e.lookups;
+    B.res_stride = 2 * asg_a + 2 + 16 * (size_t)C.nf;
+    B.a_res = a; B.l_res = l;
+    a += (count + 1) * B.res_stride; l += (count + 1) * 2 * asg_l;
+    B.in_v = C.words_n;
+    B.in_theta = B.in_v + C.e.L64;
+    B.in_cts = B.in_theta + C.e.L64;
+    B.in_res = B.in_cts + count * C.e.L64;
+    C.res_off = B.in_res;   // (k_circuit_misc reads a result it does not write for this kind: h, valid memory)
+    *adv_total = a;
+    *lk_total = l;
+    return PZ_OK;
+}
+// grid.x = chain i (0: the base v, j >= 1: ciphertext j): the [1, 0] at the chain's head, assign_integer of h / u_i and
+// assert_equal_fresh(chain i's result, h / u_i), the result taken from the chain's last (acc, sq) record
+__global__ __launch_bounds__(256) void k_partial_misc(CircP C, PartialP B, const u64* __restrict__ inputs, const u64* __restrict__ steps,
+                                                      Fr* __restrict__ advice, Fr* __restrict__ lookup) {
+    __shared__ u64 s_res[CIRC_MAXF][2], s_c[CIRC_MAXF][2];
+    __shared__ unsigned char s_eq[CIRC_MAXF + 1];
+    const size_t i = blockIdx.x;
+    const unsigned nf = C.nf, W = C.e.W, lb = C.e.lb, tid = threadIdx.x;
+    const u64* cval = steps + (B.K + (i + 1) * 2 * B.E - 2) * 4 * (size_t)C.e.L64 + (B.top ? 3 : 0) * (size_t)C.e.L64;
+#define LIMB(X, i) u_make((X)[i][0], (X)[i][1])
+    for (unsigned t = tid; t < nf; t += blockDim.x) {
+        limb_extract(inputs + B.in_res + i * C.e.L64, C.e.L64, t, W, s_res[t]);
+        limb_extract(cval, C.e.L64, t, W, s_c[t]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned eq = 1;
+        s_eq[0] = 1;
+        for (unsigned t = 0; t < nf; ++t) {
+            eq &= u_eq(LIMB(s_c, t), LIMB(s_res, t)) ? 1u : 0u;
+            s_eq[t + 1] = (unsigned char)eq;
+        }
+        const CellPtr p = adv_ptr(C.e, advice, B.a_ch + i * (B.chain_cells + C.e.cells));
+        fp_store(p, fp_one<FrTag>());
+        fp_store(p + 1, fp_zero<FrTag>());
+    }
+    __syncthreads();
+    const CellPtr a = adv_ptr(C.e, advice, B.a_res + i * B.res_stride);
+    const CellPtr l{lookup, B.l_res + i * nf * C.rc_lk, C.e.rows, C.e.pad, nullptr, 0};
+    for (unsigned t = tid; t < nf * (1 + C.rc_adv); t += blockDim.x) {
+        Fr v;
+        if (t < nf) v = fr_from_u(LIMB(s_res, t));
+        else v = cv_to_fr(rc_adv_cell(LIMB(s_res, (t - nf) / C.rc_adv), W, lb, (t - nf) % C.rc_adv));
+        fp_store(a + t, v);
+    }
+    if (l)
+        for (unsigned t = tid; t < nf * C.rc_lk; t += blockDim.x) fp_store(l + t, cv_to_fr(rc_lk_cell(LIMB(s_res, t / C.rc_lk), W, lb, t % C.rc_lk)));
+    const CellPtr e = a + (size_t)nf * (1 + C.rc_adv);
+    if (tid == 0) {
+        fp_store(e, fp_zero<FrTag>());
+        fp_store(e + 1, fp_one<FrTag>());
+    }
+    for (unsigned t = tid; t < 16 * nf; t += blockDim.x) {
+        const unsigned j = t / 16, p = t % 16;
+        Fr v;
+        if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, j), LIMB(s_res, j), p));
+        else {
+            const unsigned eq = u_eq(LIMB(s_c, j), LIMB(s_res, j)) ? 1u : 0u, in = s_eq[j], out = s_eq[j + 1];
+            v = p == 12 ? fp_zero<FrTag>() : p == 13 ? (in ? fp_one<FrTag>() : fp_zero<FrTag>())
+                : p == 14 ? (eq ? fp_one<FrTag>() : fp_zero<FrTag>()) : (out ? fp_one<FrTag>() : fp_zero<FrTag>());
+        }
+        fp_store(e + 2 + t, v);
+    }
+#undef LIMB
+}
+
+extern "C" int pz_partial_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t* advice_cells,
+                                size_t* lookup_cells) {
+    CircP C;
+    PartialP B;
+    size_t a, l;
+    PZCHK(make_partial_params(limbs_n, limb_bits, lookup_bits, count, C, B, &a, &l));
+    if (advice_cells) *advice_cells = a;
+    if (lookup_cells) *lookup_cells = l;
+    return PZ_OK;
+}
+
+static int partial_expand_impl(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, const uint64_t* inputs,
+                               const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows,
+                               size_t col_stride, const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows) {
+    if (!ctx || !inputs || !d_steps || !d_modulus || !d_advice) return PZ_ERR_INVALID;
+    if ((rows == 0) != (col_stride == 0) || col_stride < rows) return PZ_ERR_INVALID;
+    CircP C;
+    PartialP B;
+    size_t a, l;
+    PZCHK(make_partial_params(limbs_n, limb_bits, lookup_bits, count, C, B, &a, &l));
+    C.e.rows = rows;
+    C.e.pad = col_stride - rows;
+    if (d_col_starts) {
+        if (n_adv_cols == 0 || n_adv_cols > 0xffffffffu || max_rows < 8 || max_rows > col_stride) return PZ_ERR_INVALID;
+        C.e.bp_starts = (const u64*)d_col_starts;
+        C.e.bp_ncols = (unsigned)n_adv_cols;
+        C.e.bp_div = max_rows - 1;
+        C.e.bp_stride = col_stride;
+    }
+    const size_t E = B.E, L64 = C.e.L64;
+    const u64* theta = inputs + B.in_theta;
+    for (size_t k = E / 64; k < L64; ++k)   // theta >= 2^E: num_to_bits of its limbs cannot hold
+        if (k == E / 64 ? theta[k] >> (E & 63) : theta[k]) return PZ_ERR_MESSAGE_RANGE;
+    B.top = (unsigned)((theta[(E - 1) / 64] >> ((E - 1) & 63)) & 1);
+    PZ_ENTER(ctx);
+    const size_t in_words = B.in_res + (count + 1) * L64;
+    void* d_in;
+    PZCHK(pz_ws_get(ctx, WS_MISC, in_words * 8 + 64, &d_in));
+    PZCHK(pz_upload_small_async(ctx, d_in, inputs, in_words * 8));
+    pz_timer tm(ctx, PZ_T_EXPAND);
+    const u64* in = (const u64*)d_in;
+    Fr *adv = (Fr*)d_advice, *lk = (Fr*)d_lookup;
+    const size_t rec = 4 * L64;   // words per step record
+    const unsigned W = limb_bits, Lf = C.e.L;
+    // n, square, refresh, load_zero (the first record's remainder stands in for the result this kind does not write there)
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, d_steps + 3 * L64, adv, lk);
+    // assign_integer of v, theta and the c_j: 2 Ln limbs from L64 words each
+    hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)(count + 2)), dim3(256), 0, ctx->stream, C.e, C.nf, C.rc_adv, C.rc_lk, in + B.in_v,
+                       B.a_wide, B.l_wide, adv, lk);
+    // chain by chain (kind 2's walk, limb by limb inside one launch): the squaring block in front of it, theta's num_to_bits per limb, the
+    // selects, the chain's 2 E records in (mul_mod, square_mod) pairs
+    for (size_t i = 0; i <= count; ++i) {
+        const size_t head = B.a_ch + i * (B.chain_cells + C.e.cells), lk_chain = B.l_ch + i * (2 * E + 1) * C.e.lookups;
+        const u64* d_chain = d_steps + (count + i * 2 * E) * rec;
+        if (i) {
+            ExpP S = C.e;
+            S.cell0 = head - C.e.cells;
+            S.lk0 = lk_chain - C.e.lookups;
+            hipLaunchKernelGGL(k_witness_expand, dim3(1), dim3(EXP_THREADS), 0, ctx->stream, S, d_steps + (i - 1) * rec, d_modulus, adv, lk);
+        }
+        hipLaunchKernelGGL(k_circuit_bits, dim3(Lf), dim3(256), 0, ctx->stream, C.e, Lf, (unsigned)L64, in + B.in_theta, head + 2, B.limb_stride,
+                           adv);
+        hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)E), dim3(256), 0, ctx->stream, C.e, Lf, (unsigned)L64, in + B.in_theta, d_chain,
+                           head + 2, B.limb_stride, B.bit_stride, B.nbc, adv);
+        ExpP Q = C.e;
+        Q.cell0 = head + 2 + B.nbc;
+        Q.lk0 = lk_chain;
+        Q.pair_stride = B.bit_stride;
+        Q.odd_off = C.e.cells + 8 * (size_t)Lf;
+        Q.chain_steps = 2 * (size_t)W;
+        Q.chain_stride = B.limb_stride;
+        hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(2 * E)), dim3(EXP_THREADS), 0, ctx->stream, Q, d_chain, d_modulus, adv, lk);
+    }
+    hipLaunchKernelGGL(k_partial_misc, dim3((unsigned)(count + 1)), dim3(256), 0, ctx->stream, C, B, in, d_steps, adv, lk);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+extern "C" int pz_partial_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count,
+                                     const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice,
+                                     uint64_t* d_lookup, size_t rows, size_t col_stride) {
+    return partial_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, inputs, d_steps, d_modulus, d_advice, d_lookup, rows, col_stride,
+                               nullptr, 0, 0);
+}
+extern "C" int pz_partial_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count,
+                                          const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice,
+                                          uint64_t* d_lookup, const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows,
+                                          size_t lookup_rows, size_t col_stride) {
+    if (!d_col_starts || lookup_rows == 0 || lookup_rows > col_stride) return PZ_ERR_INVALID;
+    return partial_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, inputs, d_steps, d_modulus, d_advice, d_lookup, lookup_rows,
+                               col_stride, d_col_starts, n_adv_cols, max_rows);
 }
 
 // host-pointer form (SURVEY.md section 8b `pz_witness_expand`): stages the trace up, expands on the device in groups

@@ -586,6 +586,67 @@ class Engine:
         self._chk(self.L.pz_paillier_decrypt_dev(self.ctx, sk.handle, count, VP(d_cts), VP(d_m), VP(d_r) if d_r else VP(), VP(d_flags)),
                   "pz_paillier_decrypt_dev")
 
+    # T-of-T threshold decryption (pz.h pz_paillier_partial / pz_paillier_combine; keys.deal_shares deals the key)
+    @staticmethod
+    def partial_records(count: int, e_bits: int) -> int:
+        """records of one trustee's partial decryptions: the count squarings, then count + 1 chains of 2 e_bits"""
+        return count + (count + 1) * 2 * e_bits
+
+    def _partial_args(self, limbs_n: int, n, v, theta, cts):
+        L = 2 * limbs_n
+        return _np(n).reshape(limbs_n), _np(v).reshape(L), _np(theta).reshape(L), _np(cts).reshape(-1, L)
+
+    def paillier_partial(self, limbs_n: int, n, v, theta, cts, e_bits: int, want_steps: bool = True):
+        """one trustee's partial decryptions h = v^theta, u_j = (c_j^2)^theta mod n^2 over exactly e_bits bits of its share theta:
+        v, theta (2*limbs_n,) words, cts (K, 2*limbs_n).  Returns (h (2*limbs_n,), u (K, 2*limbs_n), steps (K + (K + 1) 2 e_bits, 4,
+        2*limbs_n) or None)."""
+        L = 2 * limbs_n
+        n, v, theta, cts = self._partial_args(limbs_n, n, v, theta, cts)
+        count = cts.shape[0]
+        n_rec = self.partial_records(count, e_bits)
+        steps = np.zeros((n_rec, 4, L), dtype=np.uint64) if want_steps else None
+        h = np.zeros(L, dtype=np.uint64)
+        u = np.zeros((max(count, 1), L), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_partial(self.ctx, limbs_n, count, e_bits, _ptr(n), _ptr(v), _ptr(theta), _ptr(cts),
+                                             _ptr(steps) if want_steps else VP(), n_rec, _ptr(h), _ptr(u)), "pz_paillier_partial")
+        return h, u, steps
+
+    def paillier_partial_dev(self, limbs_n: int, n, v, theta, cts, e_bits: int, d_steps: int, steps_cap: int):
+        """the same with the records left on the device for K4 (d_steps: steps_cap x 4 x 2*limbs_n u64).  Returns (h, u)."""
+        L = 2 * limbs_n
+        n, v, theta, cts = self._partial_args(limbs_n, n, v, theta, cts)
+        h = np.zeros(L, dtype=np.uint64)
+        u = np.zeros((max(cts.shape[0], 1), L), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_partial_dev(self.ctx, limbs_n, cts.shape[0], e_bits, _ptr(n), _ptr(v), _ptr(theta), _ptr(cts), VP(d_steps),
+                                                 steps_cap, _ptr(h), _ptr(u)), "pz_paillier_partial_dev")
+        return h, u
+
+    def paillier_combine(self, limbs_n: int, n, mu2, partials):
+        """m_j = L(prod_i u_ij mod n^2) mu2 mod n: partials (T, K, 2*limbs_n) words, trustee-major.  Returns (m (K, limbs_n), flags (K,)
+        uint8: bit 0 = the product is not 1 mod n, m zero; bit 1 = a partial >= n^2: PzError PZ_ERR_RANGE, which then carries every
+        entry as written in its `m` and `flags` attributes)."""
+        parts = _np(partials)
+        if parts.ndim != 3 or parts.shape[2] != 2 * limbs_n:
+            raise ValueError("partials: (trustees, count, 2*limbs_n) words")
+        trustees, count = parts.shape[0], parts.shape[1]
+        n, mu2 = _np(n).reshape(limbs_n), _np(mu2).reshape(limbs_n)
+        m = np.zeros((max(count, 1), limbs_n), dtype=np.uint64)
+        flags = np.zeros(max(count, 1), dtype=np.uint8)
+        rc = self.L.pz_paillier_combine(self.ctx, limbs_n, count, trustees, _ptr(n), _ptr(mu2), _ptr(parts), _ptr(m), VP(flags.ctypes.data))
+        try:
+            self._chk(rc, "pz_paillier_combine")
+        except PzError as e:
+            if e.status == _lib.PZ_ERR_RANGE:
+                e.m, e.flags = m, flags
+            raise
+        return m, flags
+
+    def paillier_combine_dev(self, limbs_n: int, n, mu2, count: int, trustees: int, d_partials: int, d_m: int, d_flags: int):
+        """the same on DEVICE buffers (addresses), asynchronous on the context's stream (pz.h pz_paillier_combine_dev)"""
+        n, mu2 = _np(n).reshape(limbs_n), _np(mu2).reshape(limbs_n)
+        self._chk(self.L.pz_paillier_combine_dev(self.ctx, limbs_n, count, trustees, _ptr(n), _ptr(mu2), VP(d_partials), VP(d_m), VP(d_flags)),
+                  "pz_paillier_combine_dev")
+
     # ------------------------------------------------------------------ K4: witness expansion
     def witness_cells_per_step(self, limbs: int, limb_bits: int, lookup_bits: int) -> Tuple[int, int]:
         a = C.c_size_t()
@@ -669,6 +730,38 @@ class Engine:
         self._chk(self.L.pz_ballot_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, _ptr(inp), VP(d_steps),
                                                    VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts), n_adv_cols, max_rows,
                                                    lookup_rows, col_stride), "pz_ballot_expand_cols_dev")
+
+    # a trustee's partial decryptions (circuit kind 7, pz.h pz_partial_*): its shape is count and the key size alone
+    def partial_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int):
+        a = C.c_size_t()
+        l = C.c_size_t()
+        self._chk(self.L.pz_partial_cells(limbs_n, limb_bits, lookup_bits, count, C.byref(a), C.byref(l)), "pz_partial_cells")
+        return a.value, l.value
+
+    def partial_public_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int):
+        """stream indices of the exposed cells in statement order: n | v | h | c_1 | u_1 | .. | c_K | u_K"""
+        out = np.zeros(limbs_n + (2 + 2 * count) * 2 * limbs_n, dtype=np.uint64)
+        npub = C.c_size_t()
+        self._chk(self.L.pz_partial_public_cells(limbs_n, limb_bits, lookup_bits, count, _ptr(out), out.shape[0], C.byref(npub)),
+                  "pz_partial_public_cells")
+        return out[: npub.value]
+
+    def partial_expand_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, inputs, d_steps: int, d_modulus: int,
+                           d_advice: int, d_lookup: int = 0, rows: int = 0, col_stride: int = 0):
+        """inputs: host uint64 array n | v | theta | c_1 .. c_K | h | u_1 .. u_K; d_steps: the K + (K + 1) 2 E records of
+        paillier_partial_dev with e_bits = E = 2 limbs_n limb_bits; writes the circuit's cell stream, dense or cut into columns"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        self._chk(self.L.pz_partial_expand_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, _ptr(inp), VP(d_steps), VP(d_modulus),
+                                               VP(d_advice), VP(d_lookup), rows, col_stride), "pz_partial_expand_dev")
+
+    def partial_expand_cols_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, inputs, d_steps: int, d_modulus: int,
+                                d_advice: int, d_lookup: int, d_col_starts: int, n_adv_cols: int, max_rows: int, lookup_rows: int,
+                                col_stride: int):
+        """the same with the advice cells in break-point columns (circuit_expand_cols_dev's conventions)"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        self._chk(self.L.pz_partial_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, _ptr(inp), VP(d_steps), VP(d_modulus),
+                                                    VP(d_advice), VP(d_lookup), VP(d_col_starts), n_adv_cols, max_rows, lookup_rows,
+                                                    col_stride), "pz_partial_expand_cols_dev")
 
     # ------------------------------------------------------------------ "next" rows: SRS setup, evaluation at a point
     def srs_setup_g1_dev(self, k: int, s, omega, d_g: int = 0, d_g_lagrange: int = 0):

@@ -1,6 +1,7 @@
 // biguint.hpp -- minimal host-side arbitrary-precision unsigned integer for the C++ mirror of the
 // reference's chip interface.  It only carries VALUES between API calls (limb split / join, equality,
-// n*n, hex I/O); every modular multiplication / exponentiation of the hot path goes through the C ABI
+// n*n, hex I/O) and the setup arithmetic of a key dealer (difference, quotient, gcd, inverse: a handful of
+// calls per key); every modular multiplication / exponentiation of the hot path goes through the C ABI
 // (include/pz.h) to the HIP kernels.  Little-endian u64 limbs, like num-bigint's BigUint semantics the
 // reference uses (Cargo.toml:12).
 #pragma once
@@ -118,6 +119,57 @@ class BigUint {
         }
         r.trim();
         return r;
+    }
+    // ---- setup arithmetic of a key dealer (PaillierChip's threshold keys): schoolbook, never on a hot path
+    friend BigUint operator-(const BigUint& a, const BigUint& b) {  // a >= b
+        if (a < b) throw std::range_error("negative difference");
+        BigUint r;
+        uint64_t borrow = 0;
+        for (size_t i = 0; i < a.l.size(); ++i) {
+            const uint64_t y = i < b.l.size() ? b.l[i] : 0, d = a.l[i] - y - borrow;
+            borrow = (a.l[i] < y || (a.l[i] == y && borrow)) ? 1 : 0;
+            r.l.push_back(d);
+        }
+        r.trim();
+        return r;
+    }
+    static void divmod(const BigUint& a, const BigUint& b, BigUint& q, BigUint& r) {  // restoring division, bit by bit
+        if (b.is_zero()) throw std::domain_error("division by zero");
+        q = BigUint();
+        r = BigUint();
+        q.l.assign(a.l.size(), 0);
+        for (size_t i = a.bits(); i-- > 0;) {
+            r = r << 1;
+            if (a.bit(i)) r = r + BigUint(1);
+            if (!(r < b)) {
+                r = r - b;
+                q.l[i / 64] |= 1ull << (i % 64);
+            }
+        }
+        q.trim();
+    }
+    friend BigUint operator/(const BigUint& a, const BigUint& b) { BigUint q, r; divmod(a, b, q, r); return q; }
+    friend BigUint operator%(const BigUint& a, const BigUint& b) { BigUint q, r; divmod(a, b, q, r); return r; }
+    static BigUint gcd(BigUint a, BigUint b) {
+        while (!b.is_zero()) {
+            BigUint t = a % b;
+            a = b;
+            b = t;
+        }
+        return a;
+    }
+    // a^-1 mod m by the extended Euclidean algorithm (coefficients kept mod m); throws if gcd(a, m) != 1
+    static BigUint mod_inverse(const BigUint& a, const BigUint& m) {
+        BigUint r0 = m, r1 = a % m, t0, t1(1);
+        while (!r1.is_zero()) {
+            BigUint q, r2;
+            divmod(r0, r1, q, r2);
+            const BigUint qt = (q * t1) % m, t2 = t0 < qt ? t0 + m - qt : t0 - qt;
+            r0 = r1; r1 = r2;
+            t0 = t1; t1 = t2;
+        }
+        if (r0 != BigUint(1)) throw std::domain_error("not invertible");
+        return t0 % m;
     }
 };
 

@@ -18,6 +18,7 @@
 //   (c^w and prod c_i^w_i: the scalar homomorphism)            PaillierChip::mul_scalar / weighted_tally, pz::paillier_wtally_test (15.8)
 //   (K ciphertexts of small values with a public sum)          PaillierChip::ballot, pz::paillier_ballot_test (15.10)
 //   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
+//   (T trustees holding additive shares of the exponent)      pz::ThresholdKey, pz::deal_shares, PaillierChip::partial_decrypt / combine (15.11)
 //   paillier.rs:87-97 paillier_enc_native / _add_native        pz::paillier_enc_native / paillier_add_native
 //   bench.rs:11-31    input structs, :33-117 drivers           pz::PaillierEncryptionInput ... paillier_enc_test ...
 //
@@ -27,6 +28,7 @@
 // cell streams on the device (synthesize_circuit -> pz_circuit_expand_dev).  Results<> carry plonk::Error's role; unwrap() throws where Rust
 // would panic; value mismatches throw like the reference's assert_eq! (paillier.rs:158-163).
 #pragma once
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -307,6 +309,20 @@ struct Decryption {
     bool unit = false;
 };
 
+// T-of-T threshold decryption.  The PUBLIC threshold key: hs[i] = v^theta_i mod n^2 is what trustee i's proofs
+// (circuit kind 7) are checked against, mu2 = (2a)^-1 mod n with 1 + a n = g^theta mod n^2 is the combiner's last factor
+struct ThresholdKey {
+    BigUint n, g, v;
+    std::vector<BigUint> hs;
+    BigUint mu2;
+    bool v_order_proved = false;   // the dealer checked ord v = n lambda / 2 (it can for safe primes only)
+};
+// one trustee's answer: h = v^theta (equal to its hs entry) and u_j = (c_j^2)^theta mod n^2
+struct PartialDecryption {
+    BigUint h;
+    std::vector<BigUint> us;
+};
+
 struct EncryptionPublicKeyAssigned {  // paillier.rs:6-9
     AssignedBigUint<Fresh> n, g;
 };
@@ -551,12 +567,140 @@ class PaillierChip {  // paillier.rs:11-15
         return R::Ok(out);
     }
 
+    // A trustee's partial decryptions: h = v^theta and u_j = (c_j^2)^theta mod n^2 over the circuit's own
+    // 2 * enc_bits exponent bits, one pz_paillier_partial call for all ciphertexts.  Nothing goes on the tape: the proof is circuit kind 7
+    // run on the records of pz_paillier_partial_dev.  theta is the trustee's secret: the staged words are overwritten here too.
+    Result<PartialDecryption> partial_decrypt(Context& ctx, const BigUint& n, const BigUint& v, const BigUint& theta,
+                                              const std::vector<BigUint>& cts) const {
+        using R = Result<PartialDecryption>;
+        const size_t Ln = std::max<size_t>(1, n.l.size()), L = 2 * Ln;
+        if (cts.empty() || cts.size() > 1024) return R::Err(PZ_ERR_INVALID, "partial_decrypt: 1 .. 1024 ciphertexts");
+        if (2 * (size_t)enc_bits > 128 * Ln) return R::Err(PZ_ERR_INVALID, "partial_decrypt: enc_bits is wider than n's words");
+        if (v.l.size() > L || theta.l.size() > L) return R::Err(PZ_ERR_RANGE, "partial_decrypt: v or theta is wider than n^2");
+        std::vector<uint64_t> cv;
+        for (const BigUint& c : cts) {
+            if (c.l.size() > L) return R::Err(PZ_ERR_RANGE, "partial_decrypt: a ciphertext is wider than n^2");
+            std::vector<uint64_t> w = c.to_limbs(L);
+            cv.insert(cv.end(), w.begin(), w.end());
+        }
+        std::vector<uint64_t> nv = n.to_limbs(Ln), vv = v.to_limbs(L), tv = theta.to_limbs(L), h(L), u(cts.size() * L);
+        int rc = pz_paillier_partial(ctx.raw(), (uint32_t)Ln, cts.size(), 2 * enc_bits, nv.data(), vv.data(), tv.data(), cv.data(), nullptr, 0,
+                                     h.data(), u.data());
+        std::fill(tv.begin(), tv.end(), 0);
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_partial: ") + pz_strerror(rc));
+        PartialDecryption out;
+        out.h = BigUint::from_limbs(h.data(), L);
+        for (size_t j = 0; j < cts.size(); ++j) out.us.push_back(BigUint::from_limbs(u.data() + j * L, L));
+        return R::Ok(out);
+    }
+
+    // The combiner: m_j = L(prod_i u_ij mod n^2) mu2 mod n over the T trustees' partials (partials[i] = trustee i's us), one
+    // pz_paillier_combine call.  `unit` is false (and m zero) where the product is not 1 mod n: the partials do not belong together.
+    Result<std::vector<Decryption>> combine(Context& ctx, const ThresholdKey& key, const std::vector<std::vector<BigUint>>& partials) const {
+        using R = Result<std::vector<Decryption>>;
+        const size_t Ln = std::max<size_t>(1, key.n.l.size()), L = 2 * Ln, T = partials.size(), K = T ? partials[0].size() : 0;
+        if (T < 1 || T > 256 || K < 1 || K > 1024) return R::Err(PZ_ERR_INVALID, "combine: 1 .. 256 trustees, 1 .. 1024 ciphertexts");
+        if (key.mu2.l.size() > Ln) return R::Err(PZ_ERR_RANGE, "combine: mu2 is wider than n");
+        std::vector<uint64_t> pv;
+        for (const auto& row : partials) {
+            if (row.size() != K) return R::Err(PZ_ERR_INVALID, "combine: every trustee answers every ciphertext");
+            for (const BigUint& u : row) {
+                if (u.l.size() > L) return R::Err(PZ_ERR_RANGE, "combine: a partial is wider than n^2");
+                std::vector<uint64_t> w = u.to_limbs(L);
+                pv.insert(pv.end(), w.begin(), w.end());
+            }
+        }
+        std::vector<uint64_t> nv = key.n.to_limbs(Ln), mv = key.mu2.to_limbs(Ln), m(K * Ln);
+        std::vector<uint8_t> flags(K);
+        int rc = pz_paillier_combine(ctx.raw(), (uint32_t)Ln, K, T, nv.data(), mv.data(), pv.data(), m.data(), flags.data());
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_combine: ") + pz_strerror(rc));
+        std::vector<Decryption> out(K);
+        for (size_t j = 0; j < K; ++j) {
+            out[j].m = BigUint::from_limbs(m.data() + j * Ln, Ln);
+            out[j].unit = flags[j] == 0;
+        }
+        return R::Ok(out);
+    }
+
     // c^w mod n^2 = Enc(w m): the weighted tally of one ciphertext
     Result<AssignedBigUint<Fresh>> mul_scalar(Context& ctx, const EncryptionPublicKeyAssigned& pk_enc, const AssignedBigUint<Fresh>& c,
                                               const AssignedWeight& w, unsigned w_bits) const {
         return weighted_tally(ctx, pk_enc, {c}, {w}, w_bits);
     }
 };
+
+// The dealer of a T-of-T threshold key (keys.py::deal_shares is the same in Python integers): theta = lambda
+// (lambda^-1 mod n), theta_1 .. theta_{T-1} = rand(n lambda), theta_T = (theta - their sum) mod n lambda; v = w^2 mod n^2 for a drawn w;
+// h_i = v^theta_i and g^theta through PaillierChip::partial_decrypt (the device's chains), mu2 = (2a)^-1 mod n.  rand(k): uniform in
+// [0, k), from the caller's CSPRNG.  safe_primes: the caller's word that (p - 1) / 2 and (q - 1) / 2 are prime (this mirror has no
+// primality test): v is then resampled until v^(N/2) = 1 and v^((N/2)/l) != 1 for l in {p, q, (p - 1) / 2, (q - 1) / 2}, N = n lambda,
+// and the key says v_order_proved.  Refuses p = q, even or tiny primes, gcd(n, phi(n)) != 1, a g whose order n does not divide, and
+// trustees outside 1 .. 256 (PZ_ERR_INVALID).  The dealer forgets p, q, lambda, theta and the shares it hands out.
+inline BigUint paillier_add_native(Context& ctx, const BigUint& n, const BigUint& c1, const BigUint& c2);
+struct DealtShares {
+    ThresholdKey key;
+    std::vector<BigUint> shares;
+};
+inline Result<DealtShares> deal_shares(Context& ctx, const PaillierChip& chip, const BigUint& p, const BigUint& q, size_t trustees,
+                                       const std::function<BigUint(const BigUint&)>& rand, bool safe_primes = false,
+                                       const BigUint* g_in = nullptr) {
+    using R = Result<DealtShares>;
+    const BigUint one(1), two(2);
+    if (trustees < 1 || trustees > 256) return R::Err(PZ_ERR_INVALID, "deal_shares: trustees outside 1 .. 256");
+    if (p < BigUint(3) || q < BigUint(3) || p == q || !p.bit(0) || !q.bit(0)) return R::Err(PZ_ERR_INVALID, "deal_shares: p and q must be distinct odd primes");
+    const BigUint n = p * q, n2 = n * n, p1 = p - one, q1 = q - one;
+    if (BigUint::gcd(n, p1 * q1) != one) return R::Err(PZ_ERR_INVALID, "deal_shares: gcd(n, phi(n)) != 1");
+    const BigUint lambda = (p1 * q1) / BigUint::gcd(p1, q1), N = n * lambda, theta = lambda * BigUint::mod_inverse(lambda, n);
+    DealtShares out;
+    out.key.n = n;
+    out.key.g = g_in ? *g_in : n + one;
+    if (out.key.g.is_zero() || !(out.key.g < n2)) return R::Err(PZ_ERR_INVALID, "deal_shares: g outside (0, n^2)");
+    const std::vector<BigUint> unit{one};
+    auto power = [&](const BigUint& base, const BigUint& e) { return chip.partial_decrypt(ctx, n, base, e, unit); };   // base^e mod n^2
+    // 1 + a n = g^theta mod n^2 with a a unit mod n: n divides the order of g
+    auto gt = power(out.key.g, theta);
+    if (!gt.ok) return R::Err(gt.err.status, gt.err.msg);
+    BigUint a, rem;
+    BigUint::divmod(gt.val.h, n, a, rem);
+    if (rem != one || BigUint::gcd(a % n, n) != one) return R::Err(PZ_ERR_INVALID, "deal_shares: n does not divide the order of g");
+    out.key.mu2 = BigUint::mod_inverse((two * a) % n, n);
+    BigUint sum;
+    for (size_t i = 0; i + 1 < trustees; ++i) {
+        out.shares.push_back(rand(N) % N);
+        sum = (sum + out.shares.back()) % N;
+    }
+    out.shares.push_back((theta + N - sum) % N);
+    const BigUint pp = p1 / two, qq = q1 / two, half = N / two;
+    for (;;) {
+        const BigUint w = rand(n2) % n2;
+        if (w < two || BigUint::gcd(w, n) != one) continue;
+        const BigUint v = paillier_add_native(ctx, n, w, w);   // w^2 mod n^2
+        if (v == one) continue;
+        bool good = true;
+        if (safe_primes) {
+            auto full = power(v, half);
+            if (!full.ok) return R::Err(full.err.status, full.err.msg);
+            good = full.val.h == one;
+            for (const BigUint* l : {&p, &q, &pp, &qq}) {
+                if (!good) break;
+                auto part = power(v, half / *l);
+                if (!part.ok) return R::Err(part.err.status, part.err.msg);
+                good = part.val.h != one;
+            }
+        }
+        if (good) {
+            out.key.v = v;
+            break;
+        }
+    }
+    out.key.v_order_proved = safe_primes;
+    for (const BigUint& s : out.shares) {
+        auto h = power(out.key.v, s);
+        if (!h.ok) return R::Err(h.err.status, h.err.msg);
+        out.key.hs.push_back(h.val.h);
+    }
+    return R::Ok(out);
+}
 
 // paillier.rs:87-92: (g^m * r^n) mod n^2 -- one pz_paillier_encrypt call without a trace
 inline BigUint paillier_enc_native(Context& ctx, const BigUint& n, const BigUint& g, const BigUint& m, const BigUint& r) {

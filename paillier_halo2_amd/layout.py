@@ -208,6 +208,7 @@ def wtally_tree(count: int):
 
 BALLOT_MAX = 1024       # ciphertexts of one ballot (pz.h pz_paillier_ballot)
 BALLOT_MAX_BITS = 64    # width of a ballot entry's message: one 64-bit word
+PARTIAL_MAX = 1024      # ciphertexts one trustee opens in one proof (pz.h pz_paillier_partial)
 
 
 def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_steps_g: int = 0, n_steps_r: int = 0,
@@ -224,7 +225,10 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
     kind 'ballot' (circuit kind 6; count = K ciphertexts, m_bits = b bits per message, n_steps_r = the records
     of ONE r^n chain): assign n, g, load_witness(m_1 .. m_K), for K >= 2 FlexGate::sum of them (1 + 3 (K - 1) cells), assign r_1 .. r_K,
     square + refresh once, load_zero, per ciphertext pow_mod(g, m_i) over b in-circuit bits, pow_mod_fixed_exp(r_i, n) and the final
-    mul_mod, then per ciphertext assign res_i and assert_equal_fresh."""
+    mul_mod, then per ciphertext assign res_i and assert_equal_fresh.
+    kind 'partial' (circuit kind 7; count = K ciphertexts one trustee opens): assign n, assign v, theta and
+    c_1 .. c_K at full width, square + refresh once, load_zero, pow_mod(v, theta) over all 2 Ln limbs of theta as kind 2 emits pow_mod,
+    per ciphertext mul_mod(c_j, c_j) and pow_mod(s_j, theta), then assign + assert_equal_fresh for h and every u_j."""
     Ln, L = limbs_n, 2 * limbs_n
     if kind == "decrypt":
         kind = "encrypt_uniform"
@@ -247,8 +251,13 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
             raise ValueError(f"a ballot's message has m_bits = 1 .. {BALLOT_MAX_BITS} bits, not {m_bits}")
         if n_steps_g not in (0, 2 * m_bits) or n_steps_r < 1:
             raise ValueError("a ballot entry has 2 * m_bits g-chain steps and n_steps_r >= 1 steps of one r^n chain")
+    elif kind == "partial":
+        if count is None or not 1 <= count <= PARTIAL_MAX:
+            raise ValueError(f"a trustee opens count = 1 .. {PARTIAL_MAX} ciphertexts in one proof, not {count}")
+        if n_steps_g not in (0, 2 * L * limb_bits) or n_steps_r:
+            raise ValueError("a partial decryption's chain has 2 * (2 * limbs_n * limb_bits) steps")
     elif count is not None:
-        raise ValueError("count belongs to kinds 'tally', 'wtally' and 'ballot'")
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot' and 'partial'")
     if w_bits is not None and kind != "wtally":
         raise ValueError("w_bits belongs to kind 'wtally'")
     if m_bits is not None and kind != "ballot":
@@ -262,7 +271,13 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         a += da
         l += dl
 
-    if kind == "ballot":
+    if kind == "partial":
+        put("assign_n", *assign_cells(Ln, limb_bits, lookup_bits))
+        ca, cl = assign_cells(L, limb_bits, lookup_bits)
+        put("assign_v", ca, cl)
+        put("assign_theta", ca, cl)
+        put("assign_cts", count * ca, count * cl)
+    elif kind == "ballot":
         na, nl = assign_cells(Ln, limb_bits, lookup_bits)
         put("assign_n", na, nl)
         put("assign_g", na, nl)
@@ -306,6 +321,16 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         put("entries", count * (2 + 7 * m_bits - 2 + m_bits * 8 * L + 2 + steps * mm.advice), count * steps * mm.lookup)
         ra, rl = assign_cells(L, limb_bits, lookup_bits)
         put("results", count * (ra + assert_equal_cells(L)), count * rl)
+        seg["end"] = (a, l)
+        return CircuitCells(a, l, seg)
+    if kind == "partial":
+        # per chain: [1, 0], then per limb of theta num_to_bits (7 W - 2 cells) and W blocks of mul_mod + select + square_mod; a
+        # squaring block in front of every chain but the first.  Then assign + assert_equal_fresh for h and every u_j
+        e_bits = L * limb_bits
+        chain = 2 + L * (7 * limb_bits - 2) + e_bits * (2 * mm.advice + 8 * L)
+        put("chains", (count + 1) * chain + count * mm.advice, (count + (count + 1) * 2 * e_bits) * mm.lookup)
+        ra, rl = assign_cells(L, limb_bits, lookup_bits)
+        put("results", (count + 1) * (ra + assert_equal_cells(L)), (count + 1) * rl)
         seg["end"] = (a, l)
         return CircuitCells(a, l, seg)
     if kind not in ("tally", "wtally"):

@@ -177,9 +177,10 @@ def record_seed(prefix: str) -> bytes:
     return int(prefix[1:-1]).to_bytes(8, "little")
 
 
-def public_inputs(kind: str, n: int, g: Optional[int], c: Optional[int] = None, c1: Optional[int] = None, c2: Optional[int] = None, *, enc_bits: int,
-                  limb_bits: int, cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None, m: Optional[int] = None,
-                  total: Optional[int] = None) -> List[int]:
+def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] = None, c1: Optional[int] = None, c2: Optional[int] = None, *,
+                  enc_bits: int, limb_bits: int, cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None,
+                  m: Optional[int] = None, total: Optional[int] = None, v: Optional[int] = None, h: Optional[int] = None,
+                  partials: Optional[Sequence[int]] = None) -> List[int]:
     """the statement of a circuit with the instance column, in the column's row order: little-endian limbs of limb_bits,
     n | g | c (kind "encrypt" / "encrypt_uniform": c = g^m r^n mod n^2) or n | g | c1 | c2 | c ("add": c = c1 c2 mod n^2); n, g, c1, c2 have
     enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)
@@ -193,7 +194,11 @@ def public_inputs(kind: str, n: int, g: Optional[int], c: Optional[int] = None, 
     kind "ballot": n | g | c_1 | .. | c_K | S -- "every c_i of cts encrypts a value below 2^m_bits under (n, g), and the values add up to
     S = total"; m_bits is the circuit's shape, not part of the statement.  One ciphertext has no S (it would be the message): a total
     given with K = 1 is refused, and so is a total missing with K >= 2.  S is ONE value.  A c_i >= n^2 is no ciphertext and is refused
-    here (the circuit proves c_i = a remainder mod n^2, so no proof exists for one).  No single result c."""
+    here (the circuit proves c_i = a remainder mod n^2, so no proof exists for one).  No single result c.
+    kind "partial": n | v | h | c_1 | u_1 | .. | c_K | u_K -- "the trustee whose public share is h = v^theta opened every c_j of cts to
+    u_j = (c_j^2)^theta mod n^2 (partials) with that one theta"; v and h come from the public threshold key (keys.ThresholdKey.v, .hs[i]).
+    The circuit compares nothing with n^2: the verifier does, HERE, and a v, h, c_j or u_j >= n^2 is refused, as are cts and partials of
+    different lengths.  No g and no single result c."""
     Ln = enc_bits // limb_bits
     mask = (1 << limb_bits) - 1
     limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
@@ -229,16 +234,28 @@ def public_inputs(kind: str, n: int, g: Optional[int], c: Optional[int] = None, 
         if any(int(ci) >= int(n) * int(n) for ci in cts):
             raise ValueError("a ballot's ciphertext is below n^2")
         parts = [(n, Ln), (g, Ln)] + [(ci, 2 * Ln) for ci in cts]
+    elif kind == "partial":
+        if v is None or h is None or cts is None or partials is None or len(cts) < 1 or g is not None or c is not None:
+            raise ValueError("the partial statement names n, v, h, cts = [c_1 .. c_K] and partials = [u_1 .. u_K], K >= 1, and neither g nor c")
+        if len(partials) != len(cts):
+            raise ValueError("the partial statement has one partial decryption per ciphertext")
+        if any(not 0 <= int(x) < int(n) * int(n) for x in [v, h] + list(cts) + list(partials)):
+            raise ValueError("v, h, every ciphertext and every partial decryption are below n^2")
+        parts = [(n, Ln), (v, 2 * Ln), (h, 2 * Ln)]
+        for ci, ui in zip(cts, partials):
+            parts += [(ci, 2 * Ln), (ui, 2 * Ln)]
     else:
-        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt or ballot")
-    if c is None and kind != "ballot":
+        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt, ballot or partial")
+    if c is None and kind not in ("ballot", "partial"):
         raise ValueError("the statement names its result c")
+    if (v is not None or h is not None or partials is not None) and kind != "partial":
+        raise ValueError("v, h and partials belong to kind 'partial'")
     if total is not None and kind != "ballot":
         raise ValueError("total belongs to kind 'ballot'")
     if m is not None and kind != "decrypt":
         raise ValueError("m belongs to kind 'decrypt'")
-    if cts is not None and kind not in ("tally", "wtally", "ballot"):
-        raise ValueError("cts belongs to kinds 'tally', 'wtally' and 'ballot'")
+    if cts is not None and kind not in ("tally", "wtally", "ballot", "partial"):
+        raise ValueError("cts belongs to kinds 'tally', 'wtally', 'ballot' and 'partial'")
     if weights is not None and kind != "wtally":
         raise ValueError("weights belongs to kind 'wtally'")
     for v, cnt in parts:

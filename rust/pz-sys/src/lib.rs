@@ -114,6 +114,17 @@ extern "C" {
                               rs: *const u64, steps_out: *mut u64, steps_cap: usize, n_steps_r: *mut u32, c_out: *mut u64) -> c_int;
     pub fn pz_paillier_ballot_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, m_bits: u32, n: *const u64, g: *const u64, ms: *const u64,
                                   rs: *const u64, d_steps_out: *mut u64, steps_cap: usize, n_steps_r: *mut u32, c_out: *mut u64) -> c_int;
+    // T-of-T threshold decryption: one trustee's partial decryptions h = v^theta, u_j = (c_j^2)^theta mod n^2 over
+    // exactly e_bits bits of its secret share theta (records: the count squarings, then chain i at count + i 2 e_bits), and the combiner
+    // m_j = L(prod_i u_ij mod n^2) mu2 mod n over trustee-major partials; flags bit 0: the product is not 1 mod n, bit 1: a partial >= n^2
+    pub fn pz_paillier_partial(ctx: *mut pz_ctx, limbs_n: u32, count: usize, e_bits: u32, n: *const u64, v: *const u64, theta: *const u64,
+                               cts: *const u64, steps_out: *mut u64, steps_cap: usize, h_out: *mut u64, u_out: *mut u64) -> c_int;
+    pub fn pz_paillier_partial_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, e_bits: u32, n: *const u64, v: *const u64, theta: *const u64,
+                                   cts: *const u64, d_steps_out: *mut u64, steps_cap: usize, h_out: *mut u64, u_out: *mut u64) -> c_int;
+    pub fn pz_paillier_combine(ctx: *mut pz_ctx, limbs_n: u32, count: usize, trustees: usize, n: *const u64, mu2: *const u64,
+                               partials: *const u64, m_out: *mut u64, flags_out: *mut u8) -> c_int;
+    pub fn pz_paillier_combine_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, trustees: usize, n: *const u64, mu2: *const u64,
+                                   d_partials: *const u64, d_m_out: *mut u64, d_flags_out: *mut u8) -> c_int;
     // decryption with randomness recovery (the key holder): a validated key handle, then m_i and r_i with c_i = g^m_i r_i^n mod n^2.
     // flags_out[i] bit 0: c_i is no unit (m_i = r_i = 0); the _dev form reports a c_i >= n^2 as bit 1 instead of PZ_ERR_RANGE
     pub fn pz_paillier_sk_create(ctx: *mut pz_ctx, limbs_n: u32, n: *const u64, g: *const u64, lambda: *const u64, d: *const u64,
@@ -176,6 +187,20 @@ extern "C" {
                                      col_stride: usize) -> c_int;
     pub fn pz_ballot_public_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, m_bits: u32, n_steps_r: usize,
                                   cells_out: *mut u64, capacity: usize, n_public: *mut usize) -> c_int;
+    // circuit kind 7 ("partial"): its shape is count and the key size; inputs n | v | theta | c_1 .. c_K | h | u_1 .. u_K
+    pub fn pz_circuit_structure_partial_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, k: u32, count: usize,
+                                            minimum_rows: usize, blinding_factors: u32, out: *mut *mut pz_structure) -> c_int;
+    pub fn pz_partial_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, advice_cells: *mut usize,
+                            lookup_cells: *mut usize) -> c_int;
+    pub fn pz_partial_expand_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, inputs: *const u64,
+                                 d_steps: *const u64, d_modulus: *const u64, d_advice: *mut u64, d_lookup: *mut u64, rows: usize,
+                                 col_stride: usize) -> c_int;
+    pub fn pz_partial_expand_cols_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, inputs: *const u64,
+                                      d_steps: *const u64, d_modulus: *const u64, d_advice: *mut u64, d_lookup: *mut u64,
+                                      d_col_starts: *const u64, n_adv_cols: usize, max_rows: usize, lookup_rows: usize,
+                                      col_stride: usize) -> c_int;
+    pub fn pz_partial_public_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, cells_out: *mut u64, capacity: usize,
+                                   n_public: *mut usize) -> c_int;
     pub fn pz_structure_info(st: *const pz_structure, n_adv: *mut usize, n_adv_filled: *mut usize, n_lk: *mut usize, max_rows: *mut usize,
                              n_constants: *mut usize, n_cells: *mut usize, n_lookups: *mut usize, n_steps_g: *mut usize,
                              n_steps_r: *mut usize) -> c_int;
