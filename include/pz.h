@@ -416,6 +416,51 @@ int pz_paillier_combine(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t trus
 int pz_paillier_combine_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
                             const uint64_t* d_partials, uint64_t* d_m_out, uint8_t* d_flags_out);
 
+/* t-of-T threshold decryption with Shamir shares.  A dealer shares theta by a polynomial f of degree t - 1
+ * over Z_(n lambda), f(0) = theta, trustee i holds s_i = f(i) (paillier_halo2_amd/keys.py::deal_shamir, pz::deal_shamir); the trustees
+ * open exactly as above (pz_paillier_partial, circuit kind 7: a share is a number below n lambda either way).  Any t of them combine:
+ * with Delta = T! and the integers mu_i = Delta prod_{j in S, j != i} j / (j - i), A = prod_{mu_i > 0} u_i^mu_i and B = prod_{mu_i < 0}
+ * u_i^|mu_i| satisfy A = B (1 + x n) mod n^2, so x = ((A - B mod n^2) / n) (B mod n)^-1 mod n and m = x mu2 mod n with the key's
+ * mu2 = (2 a Delta)^-1 mod n: no inverse mod n^2, one inverse of an n-sized value mod n.
+ *   pz_bigint_mod_inverse   inv_j = x_j^-1 mod `mod` for `count` (1 .. 65536) values of `limbs` words under ONE odd modulus (mod: limbs
+ *       words; xs, inv_out: count x limbs words; flags_out: count bytes; all HOST).  Refusals, in this order and all before any launch:
+ *       a null pointer, limbs = 0, count out of range: PZ_ERR_INVALID; limbs > 128: PZ_ERR_UNSUPPORTED; mod = 0: PZ_ERR_ZERO_MODULUS;
+ *       mod even or mod = 1: PZ_ERR_INVALID.  flags_out[j] bit 0: gcd(x_j, mod) != 1 (x_j = 0 included), the output is zero; bit 1:
+ *       x_j >= mod, the output is zero and the call returns PZ_ERR_RANGE after writing every entry; bit 2: the iteration bound ran out
+ *       (cannot happen for an odd modulus; PZ_ERR_HIP).  The result is canonical, in [0, mod).  One wavefront per value runs a
+ *       right-shift binary extended Euclid of at most 2 bitlen(mod) + 4 steps, a bound taken from the modulus alone.  Nothing here is
+ *       secret: branches and trip counts follow the operands.
+ *   pz_bigint_mod_inverse_dev   d_xs, d_inv_out and d_flags_out are DEVICE buffers (mod stays HOST words); the work is queued on the
+ *       context's stream and the call returns without waiting: the flags are the caller's to read.
+ *   pz_paillier_combine_t   the combiner for `members` (1 .. 256) partials of each of `count` (1 .. 1024) ciphertexts.  partials
+ *       member-major (members x count x 2*limbs_n words), as pz_paillier_combine has them; exps: members x exp_words (1 .. 64) words, the
+ *       magnitudes |mu_i|; neg: one sign byte (0 or 1) per member; n and mu2 limbs_n words; m_out count x limbs_n words; flags_out count
+ *       bytes (all HOST).  Refusals, in this order and all before any launch: a null pointer, limbs_n = 0, count, members or exp_words
+ *       out of range: PZ_ERR_INVALID; 2*limbs_n > 128: PZ_ERR_UNSUPPORTED; n = 0: PZ_ERR_ZERO_MODULUS; a zero exponent: PZ_ERR_INVALID;
+ *       a sign byte > 1: PZ_ERR_INVALID.  n must be odd (an even n ends in flag bit 2).  Flag bit 0: A mod n != B mod n (the partials
+ *       do not belong together or are too few; m zero); bit 1: a partial >= n^2 (m zero; PZ_ERR_RANGE after writing every entry); bit
+ *       2: an internal check failed (PZ_ERR_HIP); bit 3: B mod n is not a unit (m zero).  With every exponent 1, no negative sign and a
+ *       T-of-T key's mu2 this is pz_paillier_combine, bit for bit.  One team per ciphertext, one launch; A and B are interleaved
+ *       (Straus) chains over the longest exponent's bits.  Nothing here is secret.
+ *   pz_paillier_combine_t_dev   d_partials, d_m_out and d_flags_out are DEVICE buffers (n, mu2, exps and neg stay HOST); asynchronous
+ *       on the context's stream.
+ *   pz_shamir_lagrange   host logic, no context: for the `members` (1 .. trustees) distinct ids (1 .. trustees <= 256) of a combination,
+ *       |mu_i| into exps_out (members x exp_words words, in the order of ids) and its sign into neg_out (1: negative).  Anything else:
+ *       PZ_ERR_INVALID.  *words_needed (may be NULL) receives the words of the longest magnitude; exp_words below that: PZ_ERR_CAPACITY
+ *       with nothing written to exps_out.  |mu_i| < (T!)^2 < 2^3368: 64 words always suffice.  (PZ_ABI_VERSION stays 7: additions.) */
+int pz_bigint_mod_inverse(pz_ctx* ctx, uint32_t limbs, size_t count, const uint64_t* mod, const uint64_t* xs, uint64_t* inv_out,
+                          uint8_t* flags_out);
+int pz_bigint_mod_inverse_dev(pz_ctx* ctx, uint32_t limbs, size_t count, const uint64_t* mod, const uint64_t* d_xs, uint64_t* d_inv_out,
+                              uint8_t* d_flags_out);
+int pz_paillier_combine_t(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t members, const uint64_t* n, const uint64_t* mu2,
+                          const uint64_t* exps, uint32_t exp_words, const uint8_t* neg, const uint64_t* partials, uint64_t* m_out,
+                          uint8_t* flags_out);
+int pz_paillier_combine_t_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t members, const uint64_t* n, const uint64_t* mu2,
+                              const uint64_t* exps, uint32_t exp_words, const uint8_t* neg, const uint64_t* d_partials, uint64_t* d_m_out,
+                              uint8_t* d_flags_out);
+int pz_shamir_lagrange(uint32_t trustees, size_t members, const uint32_t* ids, uint64_t* exps_out, uint32_t exp_words, uint8_t* neg_out,
+                       uint32_t* words_needed);
+
 /* ---------------------------------------------------------------------------------------------
  * K4 -- expansion of a step trace into advice-column cells (Fr Montgomery, 32 B each), i.e. the
  * values halo2-lib's Context would hold after BigUintChip emitted the constraints of every

@@ -78,6 +78,11 @@ SIGNATURES = {
     "pz_paillier_partial_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
     "pz_paillier_combine": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP]),
     "pz_paillier_combine_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP]),
+    "pz_bigint_mod_inverse": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, VP]),
+    "pz_bigint_mod_inverse_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, VP]),
+    "pz_paillier_combine_t": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, C.c_uint32, VP, VP, VP, VP]),
+    "pz_paillier_combine_t_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, C.c_uint32, VP, VP, VP, VP]),
+    "pz_shamir_lagrange": (C.c_int, [C.c_uint32, C.c_size_t, VP, VP, C.c_uint32, VP, VP]),
     "pz_paillier_sk_create":(C.c_int, [VP, C.c_uint32, VP, VP, VP, VP, C.POINTER(VP)]),
     "pz_paillier_sk_params": (C.c_int, [VP, VP, VP]),
     "pz_paillier_sk_free": (C.c_int, [VP, VP]),

@@ -1276,6 +1276,194 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_partial_combi
     }
 }
 
+// ---- the modular inverse (pz_bigint_mod_inverse, and the t-of-T combiner's one inverse).  One wavefront owns one value:
+// there is no product in it, so no team, no LDS and no barrier.  A right-shift binary extended Euclid over (u, v, x1, x2) with
+// x1 x = u and x2 x = v (mod m), v odd throughout (m is odd).  One step: u = 0 ends it (gcd = v, the inverse is x2 where v = 1); an even u
+// is halved with x1; otherwise the smaller of u and v goes to v, u takes the (even) difference, x1 the difference of the coefficients
+// mod m, and both are halved at once.  Every step takes at least one bit off bitlen(u) + bitlen(v) <= 2 bitlen(m), so 2 bitlen(m) + 4
+// steps always suffice for x < m and an odd m; the bound is the caller's (a launch argument, derived from the modulus length alone), and
+// a wave that exhausts it (an even m can) leaves with INV_ITER: no loop here is unbounded on any input.  Every branch is wave-uniform:
+// parity is lane 0's low bit, comparisons are ld_sub's borrow, zero tests are ballots.  Nothing here is secret: the trip count and the
+// branches follow the operands, which are public values (a modulus n and what published partials combine to).
+//
+// a >> 1 with carry_in as the new top bit of the capacity.  (x + m) / 2 needs it: at limbs = 64 E the sum does not fit the capacity and
+// ld_add's carry-out IS bit 64 * 64 E of it.
+template <int E> __device__ __forceinline__ LD<E> ld_shr1(const LD<E>& a, bool carry_in) {
+    u64 nxt = shfl_down1(a.v[0]);   // the next lane's first limb; lane 63 reads 0
+    if (lane_id() == 63) nxt = carry_in ? 1ull : 0ull;
+    LD<E> y;
+#pragma unroll
+    for (int e = 0; e < E; ++e) y.v[e] = (a.v[e] >> 1) | ((e + 1 < E ? a.v[e + 1] : nxt) << 63);
+    return y;
+}
+template <int E> __device__ __forceinline__ bool ld_odd(const LD<E>& a) { return (__builtin_amdgcn_readfirstlane((u32)a.v[0]) & 1u) != 0; }
+// x / 2 mod m for x < m, m odd
+template <int E> __device__ __forceinline__ LD<E> ld_half_mod(const LD<E>& x, const LD<E>& m) {
+    if (!ld_odd(x)) return ld_shr1(x, false);
+    LD<E> s;
+    const bool c = ld_add(s, x, m, false);
+    return ld_shr1(s, c);
+}
+enum { INV_OK = 0, INV_NOT_UNIT = 1, INV_ITER = 4 };
+// inv = x^-1 mod m for x < m; returns INV_OK, INV_NOT_UNIT (gcd(x, m) != 1, x = 0 included: inv = 0) or INV_ITER (max_iters ran out: inv = 0)
+template <int E> __device__ __forceinline__ unsigned ld_inv_mod(LD<E>& inv, const LD<E>& x, const LD<E>& m, unsigned max_iters) {
+    const LD<E> one = ld_small<E>(1);
+    LD<E> u = x, v = m, x1 = one, x2 = ld_zero<E>();
+    inv = ld_zero<E>();
+    for (unsigned it = 0; it < max_iters; ++it) {
+        if (ld_is_zero(u)) {
+            bool ne = false;
+#pragma unroll
+            for (int e = 0; e < E; ++e) ne |= v.v[e] != one.v[e];
+            if (__ballot(ne) != 0) return INV_NOT_UNIT;
+            inv = x2;
+            return INV_OK;
+        }
+        if (ld_odd(u)) {
+            LD<E> d;
+            if (ld_sub(d, u, v)) {   // u < v: they change places
+                (void)ld_sub(d, v, u);
+                v = u;
+                const LD<E> t = x1;
+                x1 = x2;
+                x2 = t;
+            }
+            u = d;
+            if (ld_sub(d, x1, x2)) (void)ld_add(d, d, m, false);   // x1 - x2 + 2^capacity + m: the carry-out is that 2^capacity
+            x1 = d;
+        }
+        u = ld_shr1(u, false);
+        x1 = ld_half_mod(x1, m);
+    }
+    return INV_ITER;
+}
+
+// xs, inv_out: count x limbs words; flags: bit 0 not a unit, bit 1 x >= mod, bit 2 the iteration bound ran out (output zero in each case).
+// Four independent waves per workgroup, one value each; nothing is shared between them.
+#define K3_INV_WAVES 4
+template <int E> __global__ __launch_bounds__(64 * K3_INV_WAVES) void k_mod_inverse(const u64* __restrict__ mod, const u64* __restrict__ xs,
+                                                                                     u64* __restrict__ inv_out, uint8_t* __restrict__ flags,
+                                                                                     unsigned limbs, unsigned count, unsigned max_iters) {
+    const size_t j = (size_t)blockIdx.x * K3_INV_WAVES + (threadIdx.x >> 6);
+    if (j >= count) return;
+    const LD<E> m = ld_load<E>(mod, limbs), x = ld_load<E>(xs + j * limbs, limbs);
+    LD<E> inv = ld_zero<E>(), d;
+    unsigned f = 2;   // x >= mod
+    if (ld_sub(d, x, m)) f = ld_inv_mod(inv, x, m, max_iters);
+    ld_store(inv_out + j * limbs, inv, limbs);
+    if (lane_id() == 0) flags[j] = (uint8_t)f;
+}
+
+// ---- the t-of-T combiner (pz_paillier_combine_t): per ciphertext A = prod_{neg_i = 0} u_i^e_i and B = prod_{neg_i = 1}
+// u_i^e_i mod n^2 over the members' partials and the magnitudes e_i = |mu_i| of their Lagrange exponents, each as ONE interleaved
+// (Straus) left-to-right chain -- per bit one squaring of the accumulator, then one product per member of that sign whose bit is set --
+// then the tail: A = B mod n must hold (honest partials give A = B (1 + x n)), x = ((A - B mod n^2) / n) (B mod n)^-1 mod n, m = x mu2
+// mod n.  One team per ciphertext, A then B, one launch; no workgroup waits on another.  The exponents, the signs and max_bits are
+// public and the same for every wave of every team, so branching on them is allowed and the four waves of a team execute the same
+// sequence of mul_mods (the team product has a workgroup barrier); the inverse runs redundantly in the four waves on the same values,
+// so they leave it together too.  An accumulator that is still 1 takes its first factor by assignment and is not squared: with every
+// exponent 1 and no negative sign this is k_partial_combine's product, bit for bit.
+// partials member-major: member i, ciphertext j at (i count + j) L.  flags: bits 0 .. 2 as k_partial_combine, bit 3 B mod n is no unit.
+enum { CMB_F_NOT_UNIT = 8 };
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_combine_t(const u64* __restrict__ mod2, const u64* __restrict__ modn,
+                                                                                const u64* __restrict__ partials, unsigned count,
+                                                                                unsigned members, const u64* __restrict__ exps,
+                                                                                unsigned exp_words, const uint8_t* __restrict__ neg,
+                                                                                unsigned max_bits, unsigned inv_iters,
+                                                                                const u64* __restrict__ mu2, u64* __restrict__ m_out,
+                                                                                uint8_t* __restrict__ flags, unsigned Ln) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (mod2[3 * C + 1] == 0 || modn[3 * C + 1] == 0) return;   // zero modulus (refused on the host: no launch reaches here with one)
+    const unsigned wave = threadIdx.x >> 6, lane = lane_id(), L = 2 * Ln;
+    TeamCtx<E> T;
+    T.buf = s_team;
+    T.w = wave;
+    T.parity = 0;
+    TeamMul<E> tmul{&T};
+    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
+        u64* z = (u64*)s_team;
+        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
+        __syncthreads();
+    }
+    const size_t j = blockIdx.x;
+    if (j >= count) return;
+    const LD<E> n2 = ld_load<E>(mod2 + 2 * C, C);
+    {   // a partial >= n^2 (public).  The four waves hold the same values: the team leaves together
+        bool over = false;
+        for (unsigned i = 0; i < members; ++i) {
+            LD<E> d;
+            over |= !ld_sub(d, ld_load<E>(partials + ((size_t)i * count + j) * L, L), n2);
+        }
+        if (over) {
+            if (wave == 0) {
+                ld_store(m_out + j * Ln, ld_zero<E>(), Ln);
+                if (lane == 0) flags[j] = CMB_F_RANGE;
+            }
+            return;
+        }
+    }
+    BarrettCtx<E> B;
+    B.sm = s_scratch[wave];
+    B.limbs = L;
+    B.s = (unsigned)mod2[3 * C];
+    B.M = ld_load<E>(mod2, C);
+    B.mu = ld_load<E>(mod2 + C, C);
+    unsigned st = ST_OK;
+    LD<E> A = ld_zero<E>(), Bv = A;
+    for (unsigned sign = 0; sign < 2; ++sign) {
+        LD<E> acc = ld_small<E>(1);
+        bool started = false;
+        for (unsigned bit = max_bits; bit-- > 0;) {
+            LD<E> q, r;
+            if (started) {
+                st |= mul_mod(B, q, r, acc, acc, tmul);
+                acc = r;
+            }
+            for (unsigned i = 0; i < members; ++i) {
+                const u32 take = (neg[i] == sign) & (u32)((exps[(size_t)i * exp_words + (bit >> 6)] >> (bit & 63)) & 1);
+                if (!__builtin_amdgcn_readfirstlane(take)) continue;   // the same word for every lane of every wave: a scalar branch
+                const LD<E> u = ld_load<E>(partials + ((size_t)i * count + j) * L, L);
+                if (started) {
+                    st |= mul_mod(B, q, r, acc, u, tmul);
+                    acc = r;
+                } else {
+                    acc = u;
+                    started = true;
+                }
+            }
+        }
+        if (sign == 0) A = acc; else Bv = acc;
+    }
+    // the tail: A = B mod n must hold; x = ((A - B mod n^2) / n) (B mod n)^-1 mod n; plaintext = x mu2 mod n
+    BarrettCtx<E> N;
+    N.sm = s_scratch[wave];
+    N.limbs = L;
+    N.s = (unsigned)modn[3 * C];
+    N.M = ld_load<E>(modn, C);
+    N.mu = ld_load<E>(modn + C, C);
+    const LD<E> one = ld_small<E>(1);
+    LD<E> q, ra, rb, D, x, rem, inv, t, m;
+    st |= mul_mod(N, q, ra, A, one, tmul);
+    st |= mul_mod(N, q, rb, Bv, one, tmul);
+    bool ne = false;
+#pragma unroll
+    for (int e = 0; e < E; ++e) ne |= ra.v[e] != rb.v[e];
+    const bool bad = __ballot(ne) != 0;
+    if (ld_sub(D, A, Bv)) (void)ld_add(D, D, n2, false);   // A - B + 2^capacity + n^2: the carry-out is that 2^capacity
+    st |= mul_mod(N, x, rem, D, one, tmul);   // an exact division where A = B mod n
+    const unsigned fi = ld_inv_mod(inv, rb, ld_load<E>(modn + 2 * C, C), inv_iters);
+    st |= mul_mod(N, q, t, x, inv, tmul);
+    st |= mul_mod(N, q, m, t, ld_load<E>(mu2, Ln), tmul);
+    if (bad || fi != INV_OK) m = ld_zero<E>();
+    if (wave == 0) {
+        ld_store(m_out + j * Ln, m, Ln);
+        if (lane == 0)
+            flags[j] = (uint8_t)((bad ? CMB_F_NOT_ONE : 0) | ((st || (fi & INV_ITER)) ? CMB_F_INTERNAL : 0) | ((fi & INV_NOT_UNIT) ? CMB_F_NOT_UNIT : 0));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
@@ -2072,6 +2260,154 @@ extern "C" int pz_paillier_combine(pz_ctx* ctx, uint32_t limbs_n, size_t count, 
 extern "C" int pz_paillier_combine_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
                                        const uint64_t* d_partials, uint64_t* d_m_out, uint8_t* d_flags_out) {
     return combine_impl(ctx, limbs_n, count, trustees, n, mu2, d_partials, d_m_out, d_flags_out, 1);
+}
+
+// Batch modular inverse under ONE odd modulus: k_mod_inverse, one wave per value.  The modulus is HOST words in both
+// forms; the iteration bound of every wave is 2 bitlen(mod) + 4, from the modulus alone.
+#define K3_INV_MAX 65536
+static unsigned bitlen_limbs(const uint64_t* a, uint32_t n) {
+    for (uint32_t i = n; i-- > 0;)
+        if (a[i]) return 64 * i + (64 - (unsigned)__builtin_clzll(a[i]));
+    return 0;
+}
+static int mod_inverse_impl(pz_ctx* ctx, uint32_t limbs, size_t count, const uint64_t* mod, const uint64_t* xs, uint64_t* inv_out,
+                            uint8_t* flags_out, int on_device) {
+    if (!ctx || !mod || !xs || !inv_out || !flags_out || limbs == 0 || count < 1 || count > K3_INV_MAX) return PZ_ERR_INVALID;
+    if (limbs > 128) return PZ_ERR_UNSUPPORTED;
+    if (is_zero_limbs(mod, limbs)) return PZ_ERR_ZERO_MODULUS;
+    if (!(mod[0] & 1) || (mod[0] == 1 && is_zero_limbs(mod + 1, limbs - 1))) return PZ_ERR_INVALID;
+    PZ_ENTER(ctx);
+    const size_t vb = (size_t)limbs * 8, mod_bytes = (vb + 255) & ~(size_t)255;
+    const size_t io_bytes = on_device ? 0 : 2 * count * vb + ((count + 7) & ~(size_t)7);
+    void* ws;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, mod_bytes + io_bytes, &ws));
+    u64* d_mod = (u64*)ws;
+    const u64* d_xs = xs;
+    u64* d_inv = inv_out;
+    uint8_t* d_flags = flags_out;
+    if (!on_device) {
+        u64* q = (u64*)((char*)ws + mod_bytes);
+        d_xs = q;
+        d_inv = q + count * limbs;
+        d_flags = (uint8_t*)(d_inv + count * limbs);
+        HIPCHK(ctx, hipMemcpyAsync(q, xs, count * vb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_mod, mod, vb, hipMemcpyHostToDevice, ctx->stream));
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        const dim3 grid((unsigned)((count + K3_INV_WAVES - 1) / K3_INV_WAVES)), block(64 * K3_INV_WAVES);
+        const unsigned iters = 2 * bitlen_limbs(mod, limbs) + 4;
+        if (limbs <= 64)
+            hipLaunchKernelGGL(k_mod_inverse<1>, grid, block, 0, ctx->stream, d_mod, d_xs, d_inv, d_flags, limbs, (unsigned)count, iters);
+        else
+            hipLaunchKernelGGL(k_mod_inverse<2>, grid, block, 0, ctx->stream, d_mod, d_xs, d_inv, d_flags, limbs, (unsigned)count, iters);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (on_device) return PZ_OK;
+    HIPCHK(ctx, hipMemcpyAsync(inv_out, d_inv, count * vb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(flags_out, d_flags, count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned any = 0;
+    for (size_t i = 0; i < count; ++i) any |= flags_out[i];
+    if (any & 4) {
+        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: the modular inverse's iteration bound ran out");
+        return PZ_ERR_HIP;
+    }
+    return (any & 2) ? PZ_ERR_RANGE : PZ_OK;
+}
+extern "C" int pz_bigint_mod_inverse(pz_ctx* ctx, uint32_t limbs, size_t count, const uint64_t* mod, const uint64_t* xs, uint64_t* inv_out,
+                                     uint8_t* flags_out) {
+    return mod_inverse_impl(ctx, limbs, count, mod, xs, inv_out, flags_out, 0);
+}
+extern "C" int pz_bigint_mod_inverse_dev(pz_ctx* ctx, uint32_t limbs, size_t count, const uint64_t* mod, const uint64_t* d_xs,
+                                         uint64_t* d_inv_out, uint8_t* d_flags_out) {
+    return mod_inverse_impl(ctx, limbs, count, mod, d_xs, d_inv_out, d_flags_out, 1);
+}
+
+// The t-of-T combiner: k_combine_t, one team per ciphertext, one launch.  n, mu2, the exponents and the signs are
+// public HOST values in both forms; the chain length (the longest exponent) is found here and passed to the launch.
+static int combine_t_impl(pz_ctx* ctx, uint32_t Ln, size_t count, size_t members, const uint64_t* n, const uint64_t* mu2,
+                          const uint64_t* exps, uint32_t exp_words, const uint8_t* neg, const uint64_t* partials, uint64_t* m_out,
+                          uint8_t* flags_out, int on_device) {
+    if (!ctx || !n || !mu2 || !exps || !neg || !partials || !m_out || !flags_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_PARTIAL_MAX || members < 1 || members > 256 || exp_words < 1 || exp_words > 64) return PZ_ERR_INVALID;
+    if (2 * (uint64_t)Ln > 128) return PZ_ERR_UNSUPPORTED;
+    if (is_zero_limbs(n, Ln)) return PZ_ERR_ZERO_MODULUS;
+    unsigned max_bits = 0;
+    for (size_t i = 0; i < members; ++i) {
+        const unsigned b = bitlen_limbs(exps + i * exp_words, exp_words);
+        if (b == 0) return PZ_ERR_INVALID;
+        max_bits = b > max_bits ? b : max_bits;
+    }
+    for (size_t i = 0; i < members; ++i)
+        if (neg[i] > 1) return PZ_ERR_INVALID;
+    PZ_ENTER(ctx);
+    const unsigned L = 2 * Ln, C = L <= 64 ? 64 : 128;
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, mod_words = (size_t)3 * C + 2;
+    // n | mu2 | exponents | signs | Barrett constants of n^2 and of n | status | host form: the partials, m, the flags
+    const size_t exp_bytes = members * exp_words * 8, neg_bytes = (members + 7) & ~(size_t)7;
+    const size_t key_bytes = (2 * nb + exp_bytes + neg_bytes + 255) & ~(size_t)255, mod_bytes = 2 * mod_words * 8 + 64;
+    const size_t io_bytes = on_device ? 0 : members * count * lb + count * nb + ((count + 7) & ~(size_t)7);
+    void* ws;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, key_bytes + mod_bytes + io_bytes + 64, &ws));
+    char* p = (char*)ws;
+    u64 *d_n = (u64*)p, *d_mu2 = d_n + Ln, *d_exps = d_mu2 + Ln;
+    uint8_t* d_neg = (uint8_t*)(d_exps + members * exp_words);
+    u64 *d_mod2 = (u64*)(p + key_bytes), *d_modn = d_mod2 + mod_words;
+    u32* d_status = (u32*)(d_modn + mod_words);
+    const u64* d_parts = partials;
+    u64* d_m = m_out;
+    uint8_t* d_flags = flags_out;
+    if (!on_device) {
+        u64* q = (u64*)(p + key_bytes + mod_bytes);
+        d_parts = q;
+        d_m = q + members * count * L;
+        d_flags = (uint8_t*)(d_m + count * Ln);
+        HIPCHK(ctx, hipMemcpyAsync(q, partials, members * count * lb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_n, n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_mu2, mu2, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_exps, exps, exp_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_neg, neg, members, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_status, 0, 4, ctx->stream));
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        const dim3 grid((unsigned)count), block(64 * K3_TEAM);
+        const unsigned iters = 2 * bitlen_limbs(n, Ln) + 4;
+        if (C == 64) {
+            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod2, d_status);
+            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 0u, d_modn, d_status);
+            hipLaunchKernelGGL(k_combine_t<1>, grid, block, 0, ctx->stream, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)members, d_exps,
+                               exp_words, d_neg, max_bits, iters, d_mu2, d_m, d_flags, Ln);
+        } else {
+            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod2, d_status);
+            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 0u, d_modn, d_status);
+            hipLaunchKernelGGL(k_combine_t<2>, grid, block, 0, ctx->stream, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)members, d_exps,
+                               exp_words, d_neg, max_bits, iters, d_mu2, d_m, d_flags, Ln);
+        }
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (on_device) return PZ_OK;
+    HIPCHK(ctx, hipMemcpyAsync(m_out, d_m, count * nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(flags_out, d_flags, count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned any = 0;
+    for (size_t i = 0; i < count; ++i) any |= flags_out[i];
+    if (any & CMB_F_INTERNAL) {
+        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: internal consistency check failed (t-of-T combination)");
+        return PZ_ERR_HIP;
+    }
+    return (any & CMB_F_RANGE) ? PZ_ERR_RANGE : PZ_OK;
+}
+extern "C" int pz_paillier_combine_t(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t members, const uint64_t* n, const uint64_t* mu2,
+                                     const uint64_t* exps, uint32_t exp_words, const uint8_t* neg, const uint64_t* partials,
+                                     uint64_t* m_out, uint8_t* flags_out) {
+    return combine_t_impl(ctx, limbs_n, count, members, n, mu2, exps, exp_words, neg, partials, m_out, flags_out, 0);
+}
+extern "C" int pz_paillier_combine_t_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t members, const uint64_t* n, const uint64_t* mu2,
+                                         const uint64_t* exps, uint32_t exp_words, const uint8_t* neg, const uint64_t* d_partials,
+                                         uint64_t* d_m_out, uint8_t* d_flags_out) {
+    return combine_t_impl(ctx, limbs_n, count, members, n, mu2, exps, exp_words, neg, d_partials, d_m_out, d_flags_out, 1);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -647,6 +647,90 @@ class Engine:
         self._chk(self.L.pz_paillier_combine_dev(self.ctx, limbs_n, count, trustees, _ptr(n), _ptr(mu2), VP(d_partials), VP(d_m), VP(d_flags)),
                   "pz_paillier_combine_dev")
 
+    # t-of-T threshold decryption with Shamir shares
+    def mod_inverse(self, limbs: int, mod, xs):
+        """inv_j = x_j^-1 mod `mod` for a batch under ONE odd modulus (pz.h pz_bigint_mod_inverse): mod (limbs,) words, xs (count, limbs).
+        Returns (inv (count, limbs), flags (count,) uint8: bit 0 = not a unit, the output zero; bit 1 = x >= mod: PzError PZ_ERR_RANGE,
+        which then carries every entry as written in its `inv` and `flags` attributes)."""
+        mod, xs = _np(mod).reshape(limbs), _np(xs).reshape(-1, limbs)
+        count = xs.shape[0]
+        inv = np.zeros((max(count, 1), limbs), dtype=np.uint64)
+        flags = np.zeros(max(count, 1), dtype=np.uint8)
+        rc = self.L.pz_bigint_mod_inverse(self.ctx, limbs, count, _ptr(mod), _ptr(xs), _ptr(inv), VP(flags.ctypes.data))
+        try:
+            self._chk(rc, "pz_bigint_mod_inverse")
+        except PzError as e:
+            if e.status == _lib.PZ_ERR_RANGE:
+                e.inv, e.flags = inv, flags
+            raise
+        return inv, flags
+
+    def mod_inverse_dev(self, limbs: int, mod, count: int, d_xs: int, d_inv: int, d_flags: int):
+        """the same on DEVICE buffers (addresses), asynchronous on the context's stream (pz.h pz_bigint_mod_inverse_dev)"""
+        mod = _np(mod).reshape(limbs)
+        self._chk(self.L.pz_bigint_mod_inverse_dev(self.ctx, limbs, count, _ptr(mod), VP(d_xs), VP(d_inv), VP(d_flags)),
+                  "pz_bigint_mod_inverse_dev")
+
+    @staticmethod
+    def shamir_lagrange(trustees: int, ids):
+        """the Lagrange exponents of a combination by the members `ids` (pz.h pz_shamir_lagrange; host logic, needs no context): returns
+        (exps (members, words) uint64 magnitudes with `words` the longest one's, neg (members,) uint8 signs).  keys.lagrange_exponents is
+        the same in Python integers."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        cap = 64
+        exps = np.zeros((max(len(ids), 1), cap), dtype=np.uint64)
+        neg = np.zeros(max(len(ids), 1), dtype=np.uint8)
+        need = C.c_uint32(0)
+        rc = _lib.lib().pz_shamir_lagrange(trustees, len(ids), VP(ids.ctypes.data), _ptr(exps), cap, VP(neg.ctypes.data), C.byref(need))
+        if rc != 0:
+            raise PzError(rc, "pz_shamir_lagrange")
+        return np.ascontiguousarray(exps[:, : need.value]), neg
+
+    @staticmethod
+    def _key_words(limbs_n: int, key):
+        """(n words, mu2 words, trustees) of a keys.ShamirKey or of a tuple (n, mu2, trustees) of integers or word arrays"""
+        n, mu2, trustees = (key.n, key.mu2, key.trustees) if hasattr(key, "mu2") else key
+
+        def words(x):
+            if isinstance(x, int):
+                if x < 0 or x >> (64 * limbs_n):
+                    raise ValueError("a key value does not fit limbs_n words")
+                return np.array([(x >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(limbs_n)], dtype=np.uint64)
+            return _np(x).reshape(limbs_n)
+
+        return words(n), words(mu2), int(trustees)
+
+    def paillier_combine_t(self, limbs_n: int, key, ids, partials):
+        """open K ciphertexts from the partials of the members `ids` (any `threshold` distinct trustee ids, 1-based) of a t-of-T key:
+        key a keys.ShamirKey or (n, mu2, trustees); partials (members, K, 2*limbs_n) words in the order of ids.  The exponents come from
+        pz_shamir_lagrange.  Returns (m (K, limbs_n), flags (K,) uint8: bit 0 = the partials do not belong together or are too few, bit 3
+        = B mod n is no unit, m zero in both cases; bit 1 = a partial >= n^2: PzError PZ_ERR_RANGE, which then carries every entry as
+        written in its `m` and `flags` attributes)."""
+        parts = _np(partials)
+        if parts.ndim != 3 or parts.shape[2] != 2 * limbs_n or parts.shape[0] != len(ids):
+            raise ValueError("partials: (len(ids), count, 2*limbs_n) words")
+        n, mu2, trustees = self._key_words(limbs_n, key)
+        exps, neg = self.shamir_lagrange(trustees, ids)
+        members, count = parts.shape[0], parts.shape[1]
+        m = np.zeros((max(count, 1), limbs_n), dtype=np.uint64)
+        flags = np.zeros(max(count, 1), dtype=np.uint8)
+        rc = self.L.pz_paillier_combine_t(self.ctx, limbs_n, count, members, _ptr(n), _ptr(mu2), _ptr(exps), exps.shape[1],
+                                          VP(neg.ctypes.data), _ptr(parts), _ptr(m), VP(flags.ctypes.data))
+        try:
+            self._chk(rc, "pz_paillier_combine_t")
+        except PzError as e:
+            if e.status == _lib.PZ_ERR_RANGE:
+                e.m, e.flags = m, flags
+            raise
+        return m, flags
+
+    def paillier_combine_t_dev(self, limbs_n: int, key, ids, count: int, d_partials: int, d_m: int, d_flags: int):
+        """the same on DEVICE buffers (addresses), asynchronous on the context's stream (pz.h pz_paillier_combine_t_dev)"""
+        n, mu2, trustees = self._key_words(limbs_n, key)
+        exps, neg = self.shamir_lagrange(trustees, ids)
+        self._chk(self.L.pz_paillier_combine_t_dev(self.ctx, limbs_n, count, len(ids), _ptr(n), _ptr(mu2), _ptr(exps), exps.shape[1],
+                                                   VP(neg.ctypes.data), VP(d_partials), VP(d_m), VP(d_flags)), "pz_paillier_combine_t_dev")
+
     # ------------------------------------------------------------------ K4: witness expansion
     def witness_cells_per_step(self, limbs: int, limb_bits: int, lookup_bits: int) -> Tuple[int, int]:
         a = C.c_size_t()

@@ -148,6 +148,43 @@ class BigUint {
         }
         q.trim();
     }
+    // by one word: the factorials and small products of the Lagrange exponents (pz_shamir_lagrange), the dealer's polynomial points
+    BigUint mul_small(uint64_t m) const {
+        BigUint r;
+        if (m == 0) return r;
+        unsigned __int128 c = 0;
+        for (uint64_t v : l) {
+            c += (unsigned __int128)v * m;
+            r.l.push_back((uint64_t)c);
+            c >>= 64;
+        }
+        if (c) r.l.push_back((uint64_t)c);
+        return r;
+    }
+    BigUint divmod_small(uint64_t d, uint64_t& rem) const {
+        if (d == 0) throw std::domain_error("division by zero");
+        BigUint q;
+        q.l.assign(l.size(), 0);
+        unsigned __int128 r = 0;
+        for (size_t i = l.size(); i-- > 0;) {
+            r = (r << 64) | l[i];
+            q.l[i] = (uint64_t)(r / d);
+            r %= d;
+        }
+        rem = (uint64_t)r;
+        q.trim();
+        return q;
+    }
+    // r mod m for r < m 2^(k + 1): k + 1 conditional subtractions (a Horner step s i + a with s, a < m and i < 2^k lands there)
+    static BigUint reduce_near(BigUint r, const BigUint& m, unsigned k) {
+        if (m.is_zero()) throw std::domain_error("division by zero");
+        for (unsigned j = k + 1; j-- > 0;) {
+            const BigUint t = m << j;
+            if (!(r < t)) r = r - t;
+        }
+        if (!(r < m)) throw std::range_error("reduce_near: the operand was not below m 2^(k + 1)");
+        return r;
+    }
     friend BigUint operator/(const BigUint& a, const BigUint& b) { BigUint q, r; divmod(a, b, q, r); return q; }
     friend BigUint operator%(const BigUint& a, const BigUint& b) { BigUint q, r; divmod(a, b, q, r); return r; }
     static BigUint gcd(BigUint a, BigUint b) {

@@ -19,6 +19,7 @@
 //   (K ciphertexts of small values with a public sum)          PaillierChip::ballot, pz::paillier_ballot_test (15.10)
 //   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
 //   (T trustees holding additive shares of the exponent)      pz::ThresholdKey, pz::deal_shares, PaillierChip::partial_decrypt / combine (15.11)
+//   (any t of T trustees holding Shamir shares of it)          pz::ShamirKey, pz::deal_shamir, PaillierChip::combine_t / mod_inverse (15.12)
 //   paillier.rs:87-97 paillier_enc_native / _add_native        pz::paillier_enc_native / paillier_add_native
 //   bench.rs:11-31    input structs, :33-117 drivers           pz::PaillierEncryptionInput ... paillier_enc_test ...
 //
@@ -322,6 +323,15 @@ struct PartialDecryption {
     BigUint h;
     std::vector<BigUint> us;
 };
+// t-of-T threshold decryption.  The PUBLIC key: hs[i - 1] = v^(s_i) mod n^2 for trustee i's Shamir share s_i,
+// mu2 = (2 a trustees!)^-1 mod n the last factor of PaillierChip::combine_t over any `threshold` of the partials
+struct ShamirKey {
+    BigUint n, g, v;
+    std::vector<BigUint> hs;
+    BigUint mu2;
+    size_t trustees = 0, threshold = 0;
+    bool v_order_proved = false;
+};
 
 struct EncryptionPublicKeyAssigned {  // paillier.rs:6-9
     AssignedBigUint<Fresh> n, g;
@@ -622,6 +632,64 @@ class PaillierChip {  // paillier.rs:11-15
         return R::Ok(out);
     }
 
+    // The t-of-T combiner: the members `ids` (distinct trustee ids, 1-based; any key.threshold of them) answer
+    // with partials[k] = member ids[k]'s us; the Lagrange exponents come from pz_shamir_lagrange, the plaintexts from one
+    // pz_paillier_combine_t call.  `unit` is false (and m zero) where the partials do not belong together, are too few, or B mod n is no unit.
+    Result<std::vector<Decryption>> combine_t(Context& ctx, const ShamirKey& key, const std::vector<uint32_t>& ids,
+                                              const std::vector<std::vector<BigUint>>& partials) const {
+        using R = Result<std::vector<Decryption>>;
+        const size_t Ln = std::max<size_t>(1, key.n.l.size()), L = 2 * Ln, M = partials.size(), K = M ? partials[0].size() : 0;
+        if (M < 1 || M > 256 || M != ids.size() || K < 1 || K > 1024)
+            return R::Err(PZ_ERR_INVALID, "combine_t: 1 .. 256 members with an id each, 1 .. 1024 ciphertexts");
+        if (key.mu2.l.size() > Ln) return R::Err(PZ_ERR_RANGE, "combine_t: mu2 is wider than n");
+        const uint32_t cap = 64;
+        std::vector<uint64_t> exps(M * cap);
+        std::vector<uint8_t> neg(M);
+        int rc = pz_shamir_lagrange((uint32_t)key.trustees, M, ids.data(), exps.data(), cap, neg.data(), nullptr);
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_shamir_lagrange: ") + pz_strerror(rc));
+        std::vector<uint64_t> pv;
+        for (const auto& row : partials) {
+            if (row.size() != K) return R::Err(PZ_ERR_INVALID, "combine_t: every member answers every ciphertext");
+            for (const BigUint& u : row) {
+                if (u.l.size() > L) return R::Err(PZ_ERR_RANGE, "combine_t: a partial is wider than n^2");
+                std::vector<uint64_t> w = u.to_limbs(L);
+                pv.insert(pv.end(), w.begin(), w.end());
+            }
+        }
+        std::vector<uint64_t> nv = key.n.to_limbs(Ln), mv = key.mu2.to_limbs(Ln), m(K * Ln);
+        std::vector<uint8_t> flags(K);
+        rc = pz_paillier_combine_t(ctx.raw(), (uint32_t)Ln, K, M, nv.data(), mv.data(), exps.data(), cap, neg.data(), pv.data(), m.data(),
+                                   flags.data());
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_combine_t: ") + pz_strerror(rc));
+        std::vector<Decryption> out(K);
+        for (size_t j = 0; j < K; ++j) {
+            out[j].m = BigUint::from_limbs(m.data() + j * Ln, Ln);
+            out[j].unit = flags[j] == 0;
+        }
+        return R::Ok(out);
+    }
+
+    // x^-1 mod `mod` for a batch under one odd modulus, one pz_bigint_mod_inverse call; an x without an inverse (zero included) comes
+    // back as zero, which is no value's inverse.  An x >= mod is PZ_ERR_RANGE.
+    Result<std::vector<BigUint>> mod_inverse(Context& ctx, const BigUint& mod, const std::vector<BigUint>& xs) const {
+        using R = Result<std::vector<BigUint>>;
+        const size_t L = std::max<size_t>(1, mod.l.size());
+        if (xs.empty() || xs.size() > 65536) return R::Err(PZ_ERR_INVALID, "mod_inverse: 1 .. 65536 values");
+        std::vector<uint64_t> xv;
+        for (const BigUint& x : xs) {
+            if (x.l.size() > L) return R::Err(PZ_ERR_RANGE, "mod_inverse: a value is wider than the modulus");
+            std::vector<uint64_t> w = x.to_limbs(L);
+            xv.insert(xv.end(), w.begin(), w.end());
+        }
+        std::vector<uint64_t> mv = mod.to_limbs(L), inv(xs.size() * L);
+        std::vector<uint8_t> flags(xs.size());
+        int rc = pz_bigint_mod_inverse(ctx.raw(), (uint32_t)L, xs.size(), mv.data(), xv.data(), inv.data(), flags.data());
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_bigint_mod_inverse: ") + pz_strerror(rc));
+        std::vector<BigUint> out;
+        for (size_t j = 0; j < xs.size(); ++j) out.push_back(BigUint::from_limbs(inv.data() + j * L, L));
+        return R::Ok(out);
+    }
+
     // c^w mod n^2 = Enc(w m): the weighted tally of one ciphertext
     Result<AssignedBigUint<Fresh>> mul_scalar(Context& ctx, const EncryptionPublicKeyAssigned& pk_enc, const AssignedBigUint<Fresh>& c,
                                               const AssignedWeight& w, unsigned w_bits) const {
@@ -670,6 +738,81 @@ inline Result<DealtShares> deal_shares(Context& ctx, const PaillierChip& chip, c
         sum = (sum + out.shares.back()) % N;
     }
     out.shares.push_back((theta + N - sum) % N);
+    const BigUint pp = p1 / two, qq = q1 / two, half = N / two;
+    for (;;) {
+        const BigUint w = rand(n2) % n2;
+        if (w < two || BigUint::gcd(w, n) != one) continue;
+        const BigUint v = paillier_add_native(ctx, n, w, w);   // w^2 mod n^2
+        if (v == one) continue;
+        bool good = true;
+        if (safe_primes) {
+            auto full = power(v, half);
+            if (!full.ok) return R::Err(full.err.status, full.err.msg);
+            good = full.val.h == one;
+            for (const BigUint* l : {&p, &q, &pp, &qq}) {
+                if (!good) break;
+                auto part = power(v, half / *l);
+                if (!part.ok) return R::Err(part.err.status, part.err.msg);
+                good = part.val.h != one;
+            }
+        }
+        if (good) {
+            out.key.v = v;
+            break;
+        }
+    }
+    out.key.v_order_proved = safe_primes;
+    for (const BigUint& s : out.shares) {
+        auto h = power(out.key.v, s);
+        if (!h.ok) return R::Err(h.err.status, h.err.msg);
+        out.key.hs.push_back(h.val.h);
+    }
+    return R::Ok(out);
+}
+
+// The dealer of a t-of-T key (keys.py::deal_shamir is the same in Python integers): a_1 .. a_{t-1} =
+// rand(n lambda), f(X) = theta + sum a_k X^k, s_i = f(i) mod n lambda by Horner's rule on the host; v chosen and, on the caller's word
+// about safe primes, order-checked exactly as deal_shares does; h_i = v^(s_i) and g^theta from the device's chains; mu2 =
+// (2 a trustees!)^-1 mod n.  Refuses what deal_shares refuses, a threshold outside 1 .. trustees and primes that do not exceed the
+// number of trustees (trustees! must be a unit mod n): PZ_ERR_INVALID.  The dealer forgets p, q, lambda, theta, f and the shares.
+struct DealtShamir {
+    ShamirKey key;
+    std::vector<BigUint> shares;
+};
+inline Result<DealtShamir> deal_shamir(Context& ctx, const PaillierChip& chip, const BigUint& p, const BigUint& q, size_t trustees,
+                                       size_t threshold, const std::function<BigUint(const BigUint&)>& rand, bool safe_primes = false,
+                                       const BigUint* g_in = nullptr) {
+    using R = Result<DealtShamir>;
+    const BigUint one(1), two(2);
+    if (trustees < 1 || trustees > 256) return R::Err(PZ_ERR_INVALID, "deal_shamir: trustees outside 1 .. 256");
+    if (threshold < 1 || threshold > trustees) return R::Err(PZ_ERR_INVALID, "deal_shamir: threshold outside 1 .. trustees");
+    if (p < BigUint(3) || q < BigUint(3) || p == q || !p.bit(0) || !q.bit(0)) return R::Err(PZ_ERR_INVALID, "deal_shamir: p and q must be distinct odd primes");
+    if (!(BigUint(trustees) < p) || !(BigUint(trustees) < q)) return R::Err(PZ_ERR_INVALID, "deal_shamir: the primes must exceed the number of trustees");
+    const BigUint n = p * q, n2 = n * n, p1 = p - one, q1 = q - one;
+    if (BigUint::gcd(n, p1 * q1) != one) return R::Err(PZ_ERR_INVALID, "deal_shamir: gcd(n, phi(n)) != 1");
+    const BigUint lambda = (p1 * q1) / BigUint::gcd(p1, q1), N = n * lambda, theta = lambda * BigUint::mod_inverse(lambda, n);
+    DealtShamir out;
+    out.key.n = n;
+    out.key.g = g_in ? *g_in : n + one;
+    out.key.trustees = trustees;
+    out.key.threshold = threshold;
+    if (out.key.g.is_zero() || !(out.key.g < n2)) return R::Err(PZ_ERR_INVALID, "deal_shamir: g outside (0, n^2)");
+    const std::vector<BigUint> unit{one};
+    auto power = [&](const BigUint& base, const BigUint& e) { return chip.partial_decrypt(ctx, n, base, e, unit); };   // base^e mod n^2
+    auto gt = power(out.key.g, theta);
+    if (!gt.ok) return R::Err(gt.err.status, gt.err.msg);
+    BigUint a, rem, delta(1);
+    BigUint::divmod(gt.val.h, n, a, rem);
+    if (rem != one || BigUint::gcd(a % n, n) != one) return R::Err(PZ_ERR_INVALID, "deal_shamir: n does not divide the order of g");
+    for (size_t f = 2; f <= trustees; ++f) delta = delta.mul_small(f) % n;
+    out.key.mu2 = BigUint::mod_inverse((((two * a) % n) * delta) % n, n);
+    std::vector<BigUint> coeffs{theta % N};
+    for (size_t k = 1; k < threshold; ++k) coeffs.push_back(rand(N) % N);
+    for (size_t i = 1; i <= trustees; ++i) {
+        BigUint s;
+        for (size_t k = coeffs.size(); k-- > 0;) s = BigUint::reduce_near(s.mul_small(i) + coeffs[k], N, 9);   // s i + a < 257 N < N 2^10
+        out.shares.push_back(s);
+    }
     const BigUint pp = p1 / two, qq = q1 / two, half = N / two;
     for (;;) {
         const BigUint w = rand(n2) % n2;

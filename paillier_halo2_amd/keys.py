@@ -1,6 +1,8 @@
 """Paillier secret keys as Python integers: what Engine.paillier_sk (pz.h pz_paillier_sk_create) takes, and the dealer of a T-of-T
 threshold key (deal_shares): additive shares of the decryption exponent for Engine.paillier_partial and the
-public ThresholdKey for Engine.paillier_combine and the verifier of circuit kind 'partial'.
+public ThresholdKey for Engine.paillier_combine and the verifier of circuit kind 'partial'; and of a t-of-T key (deal_shamir,
+lagrange_exponents; section 15.12): Shamir shares for the same Engine.paillier_partial and the public ShamirKey for
+Engine.paillier_combine_t.
 
 The library derives mu and g^-1 on the device and validates the key there; the one value it does not derive is d = n^-1 mod lambda,
 the exponent that recovers an encryption's randomness: it is the caller's, and this helper computes it."""
@@ -104,4 +106,85 @@ def deal_shares(p: int, q: int, trustees: int, g: Optional[int] = None,
             break
     a = (pow(g, theta, n2) - 1) // n
     key = ThresholdKey(n=n, g=g, v=v, hs=tuple(pow(v, s, n2) for s in shares), mu2=pow(2 * a, -1, n), v_order_proved=safe)
+    return key, shares
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# t-of-T threshold keys: the dealer shares theta by a polynomial of degree t - 1 over Z_(n lam)
+# ---------------------------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class ShamirKey:
+    """the PUBLIC t-of-T key: hs[i - 1] = v^(s_i) mod n^2 is what trustee i's proofs (circuit kind 'partial') are checked against, as
+    with a ThresholdKey; mu2 = (2 a trustees!)^-1 mod n with 1 + a n = g^theta mod n^2 is the last factor of Engine.paillier_combine_t
+    over any `threshold` of the `trustees` partials.  v_order_proved as in ThresholdKey."""
+    n: int
+    g: int
+    v: int
+    hs: Tuple[int, ...]
+    mu2: int
+    trustees: int
+    threshold: int
+    v_order_proved: bool
+
+
+def lagrange_exponents(trustees: int, ids) -> List[int]:
+    """mu_i = trustees! * prod_{j in ids, j != i} j / (j - i) for every i of ids, in their order, as signed integers (each IS an integer:
+    asserted).  sum_i mu_i f(i) = trustees! f(0) for every polynomial f of degree below len(ids).  ids: distinct, 1 .. trustees <= 256:
+    ValueError otherwise.  (pz.h pz_shamir_lagrange is the same in C; this restates it independently in Python integers.)"""
+    ids = list(ids)
+    if isinstance(trustees, bool) or not isinstance(trustees, int) or not 1 <= trustees <= MAX_TRUSTEES:
+        raise ValueError(f"trustees must be 1 .. {MAX_TRUSTEES}, not {trustees!r}")
+    if not ids or len(set(ids)) != len(ids) or any(isinstance(i, bool) or not isinstance(i, int) or not 1 <= i <= trustees for i in ids):
+        raise ValueError("ids must be distinct integers in 1 .. trustees")
+    delta = math.factorial(trustees)
+    out = []
+    for i in ids:
+        num, den = delta, 1
+        for j in ids:
+            if j != i:
+                num *= j
+                den *= j - i
+        assert num % den == 0, "a Lagrange exponent is an integer"
+        out.append(num // den)
+    return out
+
+
+def deal_shamir(p: int, q: int, trustees: int, threshold: int, g: Optional[int] = None,
+                rand: Callable[[int], int] = secrets.randbelow) -> Tuple[ShamirKey, List[int]]:
+    """The dealer of a t-of-T key: (public ShamirKey, [s_1 .. s_T]) for the key with primes p and q.  With N = n lam and theta =
+    lam (lam^-1 mod n): a_1 .. a_{t-1} = rand(N) each, f(X) = theta + sum a_k X^k, s_i = f(i) mod N; v is chosen and, for safe primes,
+    order-checked exactly as deal_shares does; mu2 = (2 a trustees!)^-1 mod n.  Any t - 1 shares are independent of theta.  Refuses what
+    deal_shares refuses, a threshold outside 1 .. trustees, and primes that do not exceed trustees (trustees! must be a unit mod n):
+    ValueError.  The dealer must forget p, q, lam, theta, the polynomial and the shares it hands out."""
+    n, g, lam, _ = secret_from_primes(p, q, g)
+    if isinstance(trustees, bool) or not isinstance(trustees, int) or not 1 <= trustees <= MAX_TRUSTEES:
+        raise ValueError(f"trustees must be 1 .. {MAX_TRUSTEES}, not {trustees!r}")
+    if isinstance(threshold, bool) or not isinstance(threshold, int) or not 1 <= threshold <= trustees:
+        raise ValueError(f"threshold must be 1 .. trustees, not {threshold!r}")
+    if min(p, q) <= trustees:
+        raise ValueError("trustees! is not a unit mod n: the primes must exceed the number of trustees")
+    n2, N = n * n, n * lam
+    theta = lam * pow(lam, -1, n)
+    coeffs = [theta] + [rand(N) for _ in range(threshold - 1)]
+    shares = []
+    for i in range(1, trustees + 1):
+        s = 0
+        for a in reversed(coeffs):          # Horner
+            s = (s * i + a) % N
+        shares.append(s)
+    pp, qq = (p - 1) // 2, (q - 1) // 2
+    safe = _is_prime(pp) and _is_prime(qq) and pp != qq
+    half = N // 2
+    while True:
+        w = rand(n2)
+        if w < 2 or math.gcd(w, n) != 1:
+            continue
+        v = w * w % n2
+        if v == 1:
+            continue
+        if not safe or (pow(v, half, n2) == 1 and all(pow(v, half // l, n2) != 1 for l in (p, q, pp, qq))):
+            break
+    a = (pow(g, theta, n2) - 1) // n
+    key = ShamirKey(n=n, g=g, v=v, hs=tuple(pow(v, s, n2) for s in shares), mu2=pow(2 * a * math.factorial(trustees), -1, n),
+                    trustees=trustees, threshold=threshold, v_order_proved=safe)
     return key, shares

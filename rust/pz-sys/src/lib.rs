@@ -125,6 +125,21 @@ extern "C" {
                                partials: *const u64, m_out: *mut u64, flags_out: *mut u8) -> c_int;
     pub fn pz_paillier_combine_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, trustees: usize, n: *const u64, mu2: *const u64,
                                    d_partials: *const u64, d_m_out: *mut u64, d_flags_out: *mut u8) -> c_int;
+    // t-of-T threshold decryption with Shamir shares: a batch modular inverse under one odd modulus (flags bit 0:
+    // not a unit, bit 1: x >= mod), the combiner over signed Lagrange exponents given as magnitudes and sign bytes (flags bits 0 .. 2 as
+    // pz_paillier_combine, bit 3: B mod n is no unit), and the exponents themselves (host logic, no context)
+    pub fn pz_bigint_mod_inverse(ctx: *mut pz_ctx, limbs: u32, count: usize, modulus: *const u64, xs: *const u64, inv_out: *mut u64,
+                                 flags_out: *mut u8) -> c_int;
+    pub fn pz_bigint_mod_inverse_dev(ctx: *mut pz_ctx, limbs: u32, count: usize, modulus: *const u64, d_xs: *const u64, d_inv_out: *mut u64,
+                                     d_flags_out: *mut u8) -> c_int;
+    pub fn pz_paillier_combine_t(ctx: *mut pz_ctx, limbs_n: u32, count: usize, members: usize, n: *const u64, mu2: *const u64,
+                                 exps: *const u64, exp_words: u32, neg: *const u8, partials: *const u64, m_out: *mut u64,
+                                 flags_out: *mut u8) -> c_int;
+    pub fn pz_paillier_combine_t_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, members: usize, n: *const u64, mu2: *const u64,
+                                     exps: *const u64, exp_words: u32, neg: *const u8, d_partials: *const u64, d_m_out: *mut u64,
+                                     d_flags_out: *mut u8) -> c_int;
+    pub fn pz_shamir_lagrange(trustees: u32, members: usize, ids: *const u32, exps_out: *mut u64, exp_words: u32, neg_out: *mut u8,
+                              words_needed: *mut u32) -> c_int;
     // decryption with randomness recovery (the key holder): a validated key handle, then m_i and r_i with c_i = g^m_i r_i^n mod n^2.
     // flags_out[i] bit 0: c_i is no unit (m_i = r_i = 0); the _dev form reports a c_i >= n^2 as bit 1 instead of PZ_ERR_RANGE
     pub fn pz_paillier_sk_create(ctx: *mut pz_ctx, limbs_n: u32, n: *const u64, g: *const u64, lambda: *const u64, d: *const u64,
