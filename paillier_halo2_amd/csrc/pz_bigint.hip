@@ -672,6 +672,87 @@ __device__ __forceinline__ unsigned mul_mod(const BarrettCtx<E>& B, LD<E>& q, LD
 }
 
 // ------------------------------------------------------------------------------------------------
+// what the kernels share.  Every helper is forceinline and takes its contexts by reference (see ld_mul_team: a TeamCtx / BarrettCtx
+// whose address reaches a real call lives in scratch memory).
+// ------------------------------------------------------------------------------------------------
+// The Barrett block of a modulus, written once by k_tally_setup and read by every team: M' | mu | modulus (C words each) | shift | ok.
+__host__ __device__ constexpr size_t mod_block_words(unsigned C) { return (size_t)3 * C + 2; }
+template <int E, class W> __device__ __forceinline__ W* block_mu(W* blk) { return blk + 64 * E; }
+template <int E, class W> __device__ __forceinline__ W* block_modulus(W* blk) { return blk + 2 * 64 * E; }
+template <int E, class W> __device__ __forceinline__ W* block_shift(W* blk) { return blk + mod_block_words(64 * E) - 2; }
+template <int E, class W> __device__ __forceinline__ W* block_ok(W* blk) { return blk + mod_block_words(64 * E) - 1; }   // 0: a zero modulus
+
+// this wave's place in its team (the workgroup); the exchange rows are zero outside the ranges the products write (TeamBuf::row)
+template <int E> __device__ __forceinline__ void team_init(TeamCtx<E>& T, TeamBuf<E> (&buf)[2]) {
+    T.buf = buf;
+    T.w = threadIdx.x >> 6;
+    T.parity = 0;
+    u64* z = (u64*)buf;
+    for (unsigned t = threadIdx.x; t < sizeof(buf) / 8; t += blockDim.x) z[t] = 0;
+    __syncthreads();
+}
+// the constants of a block's modulus for operands of `limbs` limbs; scratch: this wave's 2 * 64 * E words of LDS
+template <int E> __device__ __forceinline__ void barrett_from_block(BarrettCtx<E>& B, const u64* blk, unsigned limbs, volatile u64* scratch) {
+    B.sm = scratch;
+    B.limbs = limbs;
+    B.s = (unsigned)*block_shift<E>(blk);
+    B.M = ld_load<E>(blk, 64 * E);
+    B.mu = ld_load<E>(block_mu<E>(blk), 64 * E);
+}
+// one step's record: a | b | q | r, L limbs each
+template <int E> __device__ __forceinline__ void rec_store(u64* o, const LD<E>& a, const LD<E>& b, const LD<E>& q, const LD<E>& r, unsigned L) {
+    ld_store(o, a, L);
+    ld_store(o + L, b, L);
+    ld_store(o + 2 * L, q, L);
+    ld_store(o + 3 * L, r, L);
+}
+// acc = bit ? r : acc under a lane-wise mask over both candidates: a SECRET bit never becomes a branch or an address
+template <int E> __device__ __forceinline__ void ld_select(LD<E>& acc, const LD<E>& r, u64 bit) {
+    u64 keep = 0ull - (bit & 1);
+    asm volatile("" : "+v"(keep));   // a per-lane value from here on: nothing below can become a branch
+#pragma unroll
+    for (int e = 0; e < E; ++e) acc.v[e] = (r.v[e] & keep) | (acc.v[e] & ~keep);
+}
+// BigUintChip::pow_mod's uniform schedule over exactly `bits` bits of exp, LSB first: (acc, sq) then (sq, sq) for EVERY bit, acc takes
+// the product only where the bit is set (ld_select: the exponent may be secret; bit t is read from word t / 64, an address that follows
+// the loop counter alone).  acc *= sq^exp, sq leaves as the trailing square.  rec (may be null: the values only): two records per bit.
+// Returns status bits.
+template <int E>
+__device__ __forceinline__ unsigned pow_mod_uniform(const BarrettCtx<E>& B, TeamCtx<E>& T, LD<E>& acc, LD<E>& sq, const u64* exp, unsigned bits,
+                                                    u64* rec) {
+    const size_t L = B.limbs;
+    unsigned st = ST_OK;
+    for (unsigned t = 0; t < bits; ++t) {
+        LD<E> q, r;
+        st |= mul_mod(B, q, r, acc, sq, TeamMul<E>{&T});
+        if (rec) rec_store(rec, acc, sq, q, r, B.limbs);
+        ld_select(acc, r, exp[t >> 6] >> (t & 63));
+        st |= mul_mod(B, q, r, sq, sq, TeamMul<E>{&T});
+        if (rec) {
+            rec_store(rec + 4 * L, sq, sq, q, r, B.limbs);
+            rec += 8 * L;
+        }
+        sq = r;
+    }
+    return st;
+}
+// decryption's last step on U = c^lambda (or the partials' product) mod n^2, by n's Barrett context at this capacity: U mod n must be 1,
+// m = floor(U / n) * mu mod n (zero where it is not).  Returns whether U mod n != 1.
+template <int E>
+__device__ __forceinline__ bool lfn_tail(const BarrettCtx<E>& N, TeamCtx<E>& T, LD<E>& m, const LD<E>& U, const u64* mu, unsigned Ln, unsigned& st) {
+    const LD<E> one = ld_small<E>(1);
+    LD<E> x, rem, q;
+    st |= mul_mod(N, x, rem, U, one, TeamMul<E>{&T});
+    bool ne = false;
+#pragma unroll
+    for (int e = 0; e < E; ++e) ne |= rem.v[e] != one.v[e];
+    const bool bad = __ballot(ne) != 0;
+    st |= mul_mod(N, q, m, x, ld_load<E>(mu, Ln), TeamMul<E>{&T});
+    if (bad) m = ld_zero<E>();
+    return bad;
+}
+
+// ------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------
 struct ChainDesc {
@@ -718,9 +799,7 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_pow_mod_chain
 #endif
     const unsigned wave = threadIdx.x >> 6;
     TeamCtx<E> T;
-    T.buf = s_team;
-    T.w = wave;
-    T.parity = 0;
+    team_init(T, s_team);
     TeamMul<E> tmul{&T};
     const bool writer = wave == 0;   // the four waves of the team hold the same values: one of them writes
     BarrettCtx<E> B;
@@ -728,11 +807,6 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_pow_mod_chain
     B.limbs = D.L;
     B.s = 0;
     unsigned st = ST_OK;
-    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
-        u64* z = (u64*)s_team;
-        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
-        __syncthreads();
-    }
     LD<E> m = ld_load<E>(D.modulus, D.limbs_mod);
     if (D.square_modulus) {
         LD<E> lo, hi;
@@ -787,13 +861,7 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_pow_mod_chain
                     if (lane_id() == 0) __hip_atomic_store(D.ready, i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
                 }
-                if (writer && D.steps && sq_slot < D.steps_cap) {
-                    u64* o = D.steps + (size_t)sq_slot * 4 * D.L;
-                    ld_store(o, sq, D.L);
-                    ld_store(o + D.L, sq, D.L);
-                    ld_store(o + 2 * D.L, q, D.L);
-                    ld_store(o + 3 * D.L, r, D.L);
-                }
+                if (writer && D.steps && sq_slot < D.steps_cap) rec_store(D.steps + (size_t)sq_slot * 4 * D.L, sq, sq, q, r, D.L);
                 sq = r;
             } else if (bit || uni) {
                 // wait for square i (every wave polls for itself: no workgroup barrier on this path); the squarer never waits for
@@ -819,13 +887,7 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_pow_mod_chain
                 }
                 LD<E> q, r;
                 st |= mul_mod(B, q, r, acc, cur, tmul);
-                if (writer && D.steps && mul_slot < D.steps_cap) {
-                    u64* o = D.steps + (size_t)mul_slot * 4 * D.L;
-                    ld_store(o, acc, D.L);
-                    ld_store(o + D.L, cur, D.L);
-                    ld_store(o + 2 * D.L, q, D.L);
-                    ld_store(o + 3 * D.L, r, D.L);
-                }
+                if (writer && D.steps && mul_slot < D.steps_cap) rec_store(D.steps + (size_t)mul_slot * 4 * D.L, acc, cur, q, r, D.L);
                 if (bit) acc = r;   // select(bit, muled, acc)
                 // a wave whose wait ran out has said so BEFORE this step's product barriers; every wave reads the flag after them,
                 // so the whole team leaves at the same step (a wave leaving alone would hang the others at the next barrier)
@@ -889,12 +951,7 @@ template <int E> __global__ __launch_bounds__(64) void k_mul_mod(const MulDesc* 
     st |= mul_mod(B, q, r, a, b, SoloMul<E>());
     if (D.q) ld_store(D.q, q, D.L);
     if (D.r) ld_store(D.r, r, D.L);
-    if (D.step) {
-        ld_store(D.step, a, D.L);
-        ld_store(D.step + D.L, b, D.L);
-        ld_store(D.step + 2 * D.L, q, D.L);
-        ld_store(D.step + 3 * D.L, r, D.L);
-    }
+    if (D.step) rec_store(D.step, a, b, q, r, D.L);
     if (st && lane_id() == 0) atomicOr(D.status, st);
 }
 
@@ -918,12 +975,12 @@ template <int E> __global__ __launch_bounds__(64) void k_tally_setup(const u64* 
     const bool ok = barrett_setup(B, lo);
     if (ok) {
         ld_store(mod, B.M, C);
-        ld_store(mod + C, B.mu, C);
-        ld_store(mod + 2 * C, lo, C);
+        ld_store(block_mu<E>(mod), B.mu, C);
+        ld_store(block_modulus<E>(mod), lo, C);
     }
     if (lane_id() == 0) {
-        mod[3 * C] = ok ? B.s : 0;
-        mod[3 * C + 1] = ok ? 1 : 0;
+        *block_shift<E>(mod) = ok ? B.s : 0;
+        *block_ok<E>(mod) = ok ? 1 : 0;
         if (!ok) atomicOr(status, (u32)ST_ZERO_MOD);
     }
 }
@@ -933,25 +990,14 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_tally_level(c
     constexpr unsigned C = 64 * E;
     __shared__ u64 s_scratch[K3_TEAM][2 * C];
     __shared__ TeamBuf<E> s_team[2];
-    if (mod[3 * C + 1] == 0) return;   // zero modulus (the same word for every workgroup of every level)
+    if (*block_ok<E>(mod) == 0) return;   // zero modulus (the same word for every workgroup of every level)
     const unsigned wave = threadIdx.x >> 6;
     TeamCtx<E> T;
-    T.buf = s_team;
-    T.w = wave;
-    T.parity = 0;
+    team_init(T, s_team);
     TeamMul<E> tmul{&T};
-    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
-        u64* z = (u64*)s_team;
-        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
-        __syncthreads();
-    }
     BarrettCtx<E> B;
-    B.sm = s_scratch[wave];
-    B.limbs = L;
-    B.s = (unsigned)mod[3 * C];
-    B.M = ld_load<E>(mod, C);
-    B.mu = ld_load<E>(mod + C, C);
-    const LD<E> n2 = ld_load<E>(mod + 2 * C, C);
+    barrett_from_block(B, mod, L, s_scratch[wave]);
+    const LD<E> n2 = ld_load<E>(block_modulus<E>(mod), C);
     const size_t ia = 2 * (size_t)blockIdx.x, ib = ia + 1;       // (only b can be the carried element: it is the list's last)
     const LD<E> a = ld_load<E>(elems + ia * stride, L);
     const LD<E> b = ld_load<E>(ib < n_regular ? elems + ib * stride : tail, L);
@@ -960,13 +1006,7 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_tally_level(c
     if (!ld_sub(d, a, n2) || !ld_sub(d, b, n2)) st |= ST_RANGE;   // an operand >= n^2: the circuit's r < n^2 check of whatever made it fails
     LD<E> q, r;
     st |= mul_mod(B, q, r, a, b, tmul);
-    if (wave == 0) {   // the four waves of the team hold the same values: one of them writes
-        u64* o = recs + (size_t)blockIdx.x * 4 * L;
-        ld_store(o, a, L);
-        ld_store(o + L, b, L);
-        ld_store(o + 2 * L, q, L);
-        ld_store(o + 3 * L, r, L);
-    }
+    if (wave == 0) rec_store(recs + (size_t)blockIdx.x * 4 * L, a, b, q, r, L);   // the four waves of the team hold the same values: one of them writes
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
@@ -983,61 +1023,28 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_wtally_pow(co
     constexpr unsigned C = 64 * E;
     __shared__ u64 s_scratch[K3_TEAM][2 * C];
     __shared__ TeamBuf<E> s_team[2];
-    if (mod[3 * C + 1] == 0) return;   // zero modulus (the same word for every workgroup)
+    if (*block_ok<E>(mod) == 0) return;   // zero modulus (the same word for every workgroup)
     const unsigned wave = threadIdx.x >> 6;
     TeamCtx<E> T;
-    T.buf = s_team;
-    T.w = wave;
-    T.parity = 0;
-    TeamMul<E> tmul{&T};
-    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
-        u64* z = (u64*)s_team;
-        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
-        __syncthreads();
-    }
+    team_init(T, s_team);
     BarrettCtx<E> B;
-    B.sm = s_scratch[wave];
-    B.limbs = L;
-    B.s = (unsigned)mod[3 * C];
-    B.M = ld_load<E>(mod, C);
-    B.mu = ld_load<E>(mod + C, C);
-    const LD<E> n2 = ld_load<E>(mod + 2 * C, C);
+    barrett_from_block(B, mod, L, s_scratch[wave]);
     const size_t chain = blockIdx.x;
-    const u64 w = weights[chain];
     LD<E> sq = ld_load<E>(cts + chain * L, L);
     LD<E> acc = ld_small<E>(1);
     unsigned st = ST_OK;
     {
         LD<E> d;
-        if (!ld_sub(d, sq, n2)) st |= ST_RANGE;   // a ciphertext >= n^2
+        if (!ld_sub(d, sq, ld_load<E>(block_modulus<E>(mod), C))) st |= ST_RANGE;   // a ciphertext >= n^2
     }
     const bool writer = wave == 0 && recs != nullptr;   // the four waves of the team hold the same values: one of them writes
-    for (unsigned j = 0; j < w_bits; ++j) {
-        u64* o = writer ? recs + (chain * w_bits + j) * 8 * (size_t)L : nullptr;   // this bit's two records
-        LD<E> q, r;
-        st |= mul_mod(B, q, r, acc, sq, tmul);
-        if (writer) {
-            ld_store(o, acc, L);
-            ld_store(o + L, sq, L);
-            ld_store(o + 2 * L, q, L);
-            ld_store(o + 3 * L, r, L);
-        }
-        if ((w >> j) & 1) acc = r;   // select(bit, muled, acc)
-        st |= mul_mod(B, q, r, sq, sq, tmul);
-        if (writer) {
-            ld_store(o + 4 * L, sq, L);
-            ld_store(o + 5 * L, sq, L);
-            ld_store(o + 6 * L, q, L);
-            ld_store(o + 7 * L, r, L);
-        }
-        sq = r;
-    }
+    st |= pow_mod_uniform(B, T, acc, sq, weights + chain, w_bits, writer ? recs + chain * w_bits * 8 * (size_t)L : nullptr);
     if (wave == 0) ld_store(powers + chain * L, acc, L);
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
 // ---- the entries of a ballot (pz_paillier_ballot): c_i = g^m_i r_i^n mod n^2 for K messages under ONE key.  One team per ciphertext
-// runs the entry's whole schedule itself -- g^m_i by BigUintChip::pow_mod over exactly m_bits bits (k_wtally_pow's loop), r_i^n by
+// runs the entry's whole schedule itself -- g^m_i by BigUintChip::pow_mod over exactly m_bits bits (pow_mod_uniform), r_i^n by
 // pow_mod_fixed_exp over n's bits, LSB first (the square of EVERY bit, then the product where the bit is set), and the final product --
 // so K entries are one launch with no ticket, no spin, no hand-off.  The Barrett constants come from k_tally_setup, once for all.
 // m_i and r_i are SECRET: the message's bit reaches the accumulator as a lane-wise mask over both candidates (k_dec_pow's read of its
@@ -1053,54 +1060,30 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_ballot_enc(co
     constexpr unsigned C = 64 * E;
     __shared__ u64 s_scratch[K3_TEAM][2 * C];
     __shared__ TeamBuf<E> s_team[2];
-    if (mod[3 * C + 1] == 0) return;   // zero modulus (the same word for every workgroup)
+    if (*block_ok<E>(mod) == 0) return;   // zero modulus (the same word for every workgroup)
     const unsigned wave = threadIdx.x >> 6, L = 2 * Ln;
     TeamCtx<E> T;
-    T.buf = s_team;
-    T.w = wave;
-    T.parity = 0;
+    team_init(T, s_team);
     TeamMul<E> tmul{&T};
-    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
-        u64* z = (u64*)s_team;
-        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
-        __syncthreads();
-    }
     BarrettCtx<E> B;
-    B.sm = s_scratch[wave];
-    B.limbs = L;
-    B.s = (unsigned)mod[3 * C];
-    B.M = ld_load<E>(mod, C);
-    B.mu = ld_load<E>(mod + C, C);
+    barrett_from_block(B, mod, L, s_scratch[wave]);
     const size_t entry = blockIdx.x;
-    const bool writer = wave == 0 && recs != nullptr;   // the four waves of the team hold the same values: one of them writes
+    // the four waves of the team hold the same values: one of them writes.  (A per below the g-chain's own count is the disagreement
+    // the last lines flag: no record is written then.)
+    const bool writer = wave == 0 && recs != nullptr && 2 * m_bits <= per;
     u64* const base = writer ? recs + entry * per * 4 * (size_t)L : nullptr;
     unsigned idx = 0, st = ST_OK;
     auto step = [&](LD<E>& r, const LD<E>& a, const LD<E>& b) {   // one recorded mul_mod
         LD<E> q;
         st |= mul_mod(B, q, r, a, b, tmul);
-        if (writer && idx < per) {
-            u64* o = base + (size_t)idx * 4 * L;
-            ld_store(o, a, L);
-            ld_store(o + L, b, L);
-            ld_store(o + 2 * L, q, L);
-            ld_store(o + 3 * L, r, L);
-        }
+        if (writer && idx < per) rec_store(base + (size_t)idx * 4 * L, a, b, q, r, L);
         ++idx;
     };
     LD<E> gm = ld_small<E>(1);
     {
-        const u64 m = ms[entry];
         LD<E> sq = ld_load<E>(g, Ln);
-        for (unsigned j = 0; j < m_bits; ++j) {
-            LD<E> r;
-            step(r, gm, sq);
-            u64 keep = 0ull - ((m >> j) & 1);   // select(bit, muled, acc) under a mask
-            asm volatile("" : "+v"(keep));      // a per-lane value from here on: nothing below can become a branch
-#pragma unroll
-            for (int e = 0; e < E; ++e) gm.v[e] = (r.v[e] & keep) | (gm.v[e] & ~keep);
-            step(r, sq, sq);
-            sq = r;
-        }
+        st |= pow_mod_uniform(B, T, gm, sq, ms + entry, m_bits, base);
+        idx = 2 * m_bits;
     }
     LD<E> rn = ld_small<E>(1);
     {
@@ -1124,10 +1107,10 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_ballot_enc(co
 
 // ---- a trustee's partial decryptions (pz_paillier_partial): h = v^theta and u_j = (c_j^2)^theta mod n^2 for K ciphertexts under ONE
 // secret share theta of e_bits bits.  K + 1 teams in one launch: team 0 runs pow_mod(v, theta), team j >= 1 first squares c_j itself
-// (record j - 1) and then runs pow_mod(s_j, theta) -- k_wtally_pow's chain, (acc, sq) then (sq, sq) for EVERY bit, the trailing square
+// (record j - 1) and then runs pow_mod(s_j, theta) -- pow_mod_uniform: (acc, sq) then (sq, sq) for EVERY bit, the trailing square
 // kept -- so no team waits for another: no ticket, no spin, no hand-off.  The Barrett constants come from k_tally_setup, once for all.
 // theta is SECRET and e_bits long (many words): bit t is read from word t / 64, an address that follows the loop counter alone, and
-// reaches the accumulator as a lane-wise mask over both candidates (k_ballot_enc's select), never as a branch.  Every trip count is a
+// reaches the accumulator as a lane-wise mask over both candidates (pow_mod_uniform's ld_select), never as a branch.  Every trip count is a
 // launch argument.  (What a mul_mod does with its VALUES is K3's as everywhere: the Barrett correction's trip count follows the operands.)
 // recs (may be null: the values only): the K squaring records, then chain i (0 .. K), bit t at records K + 2 (i e_bits + t) and the next.
 template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_partial_pow(const u64* __restrict__ mod, const u64* __restrict__ v,
@@ -1138,72 +1121,55 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_partial_pow(c
     constexpr unsigned C = 64 * E;
     __shared__ u64 s_scratch[K3_TEAM][2 * C];
     __shared__ TeamBuf<E> s_team[2];
-    if (mod[3 * C + 1] == 0) return;   // zero modulus (the same word for every workgroup)
+    if (*block_ok<E>(mod) == 0) return;   // zero modulus (the same word for every workgroup)
     const unsigned wave = threadIdx.x >> 6;
     TeamCtx<E> T;
-    T.buf = s_team;
-    T.w = wave;
-    T.parity = 0;
-    TeamMul<E> tmul{&T};
-    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
-        u64* z = (u64*)s_team;
-        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
-        __syncthreads();
-    }
+    team_init(T, s_team);
     BarrettCtx<E> B;
-    B.sm = s_scratch[wave];
-    B.limbs = L;
-    B.s = (unsigned)mod[3 * C];
-    B.M = ld_load<E>(mod, C);
-    B.mu = ld_load<E>(mod + C, C);
+    barrett_from_block(B, mod, L, s_scratch[wave]);
     const size_t chain = blockIdx.x;   // 0: the key's base v; j >= 1: ciphertext j - 1
     if (chain > count) return;
     const bool writer = wave == 0 && recs != nullptr;   // the four waves of the team hold the same values: one of them writes
-    auto record = [&](u64* o, const LD<E>& a, const LD<E>& b, const LD<E>& q, const LD<E>& r) {
-        ld_store(o, a, L);
-        ld_store(o + L, b, L);
-        ld_store(o + 2 * L, q, L);
-        ld_store(o + 3 * L, r, L);
-    };
     unsigned st = ST_OK;
     LD<E> sq = ld_load<E>(chain == 0 ? v : cts + (chain - 1) * L, L);
     {
         LD<E> d;
-        if (!ld_sub(d, sq, ld_load<E>(mod + 2 * C, C))) st |= ST_RANGE;   // v or a ciphertext >= n^2 (both public)
+        if (!ld_sub(d, sq, ld_load<E>(block_modulus<E>(mod), C))) st |= ST_RANGE;   // v or a ciphertext >= n^2 (both public)
     }
     if (chain != 0) {   // s_j = c_j^2: the chain's base
         LD<E> q, r;
-        st |= mul_mod(B, q, r, sq, sq, tmul);
-        if (writer) record(recs + (chain - 1) * 4 * (size_t)L, sq, sq, q, r);
+        st |= mul_mod(B, q, r, sq, sq, TeamMul<E>{&T});
+        if (writer) rec_store(recs + (chain - 1) * 4 * (size_t)L, sq, sq, q, r, L);
         sq = r;
     }
     LD<E> acc = ld_small<E>(1);
-    u64* o = writer ? recs + ((size_t)count + chain * 2 * (size_t)e_bits) * 4 * L : nullptr;
-    for (unsigned t = 0; t < e_bits; ++t) {
-        LD<E> q, r;
-        st |= mul_mod(B, q, r, acc, sq, tmul);
-        if (writer) record(o, acc, sq, q, r);
-        u64 keep = 0ull - ((theta[t >> 6] >> (t & 63)) & 1);   // select(bit, muled, acc) under a mask; the word's address is t's alone
-        asm volatile("" : "+v"(keep));                          // a per-lane value from here on: nothing below can become a branch
-#pragma unroll
-        for (int e = 0; e < E; ++e) acc.v[e] = (r.v[e] & keep) | (acc.v[e] & ~keep);
-        st |= mul_mod(B, q, r, sq, sq, tmul);
-        if (writer) {
-            record(o + 4 * (size_t)L, sq, sq, q, r);
-            o += 8 * (size_t)L;
-        }
-        sq = r;
-    }
+    st |= pow_mod_uniform(B, T, acc, sq, theta, e_bits, writer ? recs + ((size_t)count + chain * 2 * (size_t)e_bits) * 4 * L : nullptr);
     if (wave == 0) ld_store(chain == 0 ? h_out : u_out + (chain - 1) * L, acc, L);
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
 // ---- the combiner of a threshold decryption (pz_paillier_combine): per ciphertext U = prod_i u_i mod n^2 over the T trustees' partials
 // (T - 1 products, one team per ciphertext, one launch), then decryption's last step on U: U mod n must be 1, m = floor(U / n) mu2 mod n
-// (k_dec_pow's DEC_LFN tail, the same three mul_mods by n's Barrett block at this capacity).  Nothing here is secret: the partials are
+// (lfn_tail, shared with k_dec_pow's DEC_LFN, by n's Barrett block at this capacity).  Nothing here is secret: the partials are
 // published with their proofs.  partials trustee-major: trustee i, ciphertext j at (i count + j) L.  flags: bit 0 U mod n != 1 (m = 0),
 // bit 1 a partial >= n^2 (m = 0, no product is formed), bit 2 an internal check failed.
 enum { CMB_F_NOT_ONE = 1, CMB_F_RANGE = 2, CMB_F_INTERNAL = 4 };
+// whether all `members` partials of ciphertext j are below n^2 (public).  Where one is not: m_j = 0 and CMB_F_RANGE, and the caller
+// returns -- the four waves hold the same values, so the team leaves together
+template <int E>
+__device__ __forceinline__ bool partials_in_range(const LD<E>& n2, const u64* partials, unsigned members, unsigned count, size_t j, unsigned Ln,
+                                                  u64* m_out, uint8_t* flags) {
+    bool over = false;
+    for (unsigned i = 0; i < members; ++i) {
+        LD<E> d;
+        over |= !ld_sub(d, ld_load<E>(partials + ((size_t)i * count + j) * 2 * Ln, 2 * Ln), n2);
+    }
+    if (over && threadIdx.x < 64) {
+        ld_store(m_out + j * Ln, ld_zero<E>(), Ln);
+        if (lane_id() == 0) flags[j] = CMB_F_RANGE;
+    }
+    return !over;
+}
 template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_partial_combine(const u64* __restrict__ mod2, const u64* __restrict__ modn,
                                                                                       const u64* __restrict__ partials, unsigned count,
                                                                                       unsigned trustees, const u64* __restrict__ mu2,
@@ -1212,64 +1178,26 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_partial_combi
     constexpr unsigned C = 64 * E;
     __shared__ u64 s_scratch[K3_TEAM][2 * C];
     __shared__ TeamBuf<E> s_team[2];
-    if (mod2[3 * C + 1] == 0 || modn[3 * C + 1] == 0) return;   // zero modulus (refused on the host: no launch reaches here with one)
+    if (*block_ok<E>(mod2) == 0 || *block_ok<E>(modn) == 0) return;   // zero modulus (refused on the host: no launch reaches here with one)
     const unsigned wave = threadIdx.x >> 6, lane = lane_id(), L = 2 * Ln;
     TeamCtx<E> T;
-    T.buf = s_team;
-    T.w = wave;
-    T.parity = 0;
-    TeamMul<E> tmul{&T};
-    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
-        u64* z = (u64*)s_team;
-        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
-        __syncthreads();
-    }
+    team_init(T, s_team);
     const size_t j = blockIdx.x;
     if (j >= count) return;
-    {   // a partial >= n^2 (public).  The four waves hold the same values: the team leaves together
-        const LD<E> n2 = ld_load<E>(mod2 + 2 * C, C);
-        bool over = false;
-        for (unsigned i = 0; i < trustees; ++i) {
-            LD<E> d;
-            over |= !ld_sub(d, ld_load<E>(partials + ((size_t)i * count + j) * L, L), n2);
-        }
-        if (over) {
-            if (wave == 0) {
-                ld_store(m_out + j * Ln, ld_zero<E>(), Ln);
-                if (lane == 0) flags[j] = CMB_F_RANGE;
-            }
-            return;
-        }
-    }
+    if (!partials_in_range(ld_load<E>(block_modulus<E>(mod2), C), partials, trustees, count, j, Ln, m_out, flags)) return;
     BarrettCtx<E> B;
-    B.sm = s_scratch[wave];
-    B.limbs = L;
-    B.s = (unsigned)mod2[3 * C];
-    B.M = ld_load<E>(mod2, C);
-    B.mu = ld_load<E>(mod2 + C, C);
+    barrett_from_block(B, mod2, L, s_scratch[wave]);
     unsigned st = ST_OK;
     LD<E> U = ld_load<E>(partials + j * L, L);
     for (unsigned i = 1; i < trustees; ++i) {
         LD<E> q, r;
-        st |= mul_mod(B, q, r, U, ld_load<E>(partials + ((size_t)i * count + j) * L, L), tmul);
+        st |= mul_mod(B, q, r, U, ld_load<E>(partials + ((size_t)i * count + j) * L, L), TeamMul<E>{&T});
         U = r;
     }
-    // U mod n must be 1; plaintext = floor(U / n) * mu2 mod n
     BarrettCtx<E> N;
-    N.sm = s_scratch[wave];
-    N.limbs = L;
-    N.s = (unsigned)modn[3 * C];
-    N.M = ld_load<E>(modn, C);
-    N.mu = ld_load<E>(modn + C, C);
-    const LD<E> one = ld_small<E>(1);
-    LD<E> x, rem, q, m;
-    st |= mul_mod(N, x, rem, U, one, tmul);
-    bool ne = false;
-#pragma unroll
-    for (int e = 0; e < E; ++e) ne |= rem.v[e] != one.v[e];
-    const bool bad = __ballot(ne) != 0;
-    st |= mul_mod(N, q, m, x, ld_load<E>(mu2, Ln), tmul);
-    if (bad) m = ld_zero<E>();
+    barrett_from_block(N, modn, L, s_scratch[wave]);
+    LD<E> m;
+    const bool bad = lfn_tail(N, T, m, U, mu2, Ln, st);
     if (wave == 0) {
         ld_store(m_out + j * Ln, m, Ln);
         if (lane == 0) flags[j] = (uint8_t)((bad ? CMB_F_NOT_ONE : 0) | (st ? CMB_F_INTERNAL : 0));
@@ -1375,41 +1303,17 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_combine_t(con
     constexpr unsigned C = 64 * E;
     __shared__ u64 s_scratch[K3_TEAM][2 * C];
     __shared__ TeamBuf<E> s_team[2];
-    if (mod2[3 * C + 1] == 0 || modn[3 * C + 1] == 0) return;   // zero modulus (refused on the host: no launch reaches here with one)
+    if (*block_ok<E>(mod2) == 0 || *block_ok<E>(modn) == 0) return;   // zero modulus (refused on the host: no launch reaches here with one)
     const unsigned wave = threadIdx.x >> 6, lane = lane_id(), L = 2 * Ln;
     TeamCtx<E> T;
-    T.buf = s_team;
-    T.w = wave;
-    T.parity = 0;
+    team_init(T, s_team);
     TeamMul<E> tmul{&T};
-    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
-        u64* z = (u64*)s_team;
-        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
-        __syncthreads();
-    }
     const size_t j = blockIdx.x;
     if (j >= count) return;
-    const LD<E> n2 = ld_load<E>(mod2 + 2 * C, C);
-    {   // a partial >= n^2 (public).  The four waves hold the same values: the team leaves together
-        bool over = false;
-        for (unsigned i = 0; i < members; ++i) {
-            LD<E> d;
-            over |= !ld_sub(d, ld_load<E>(partials + ((size_t)i * count + j) * L, L), n2);
-        }
-        if (over) {
-            if (wave == 0) {
-                ld_store(m_out + j * Ln, ld_zero<E>(), Ln);
-                if (lane == 0) flags[j] = CMB_F_RANGE;
-            }
-            return;
-        }
-    }
+    const LD<E> n2 = ld_load<E>(block_modulus<E>(mod2), C);
+    if (!partials_in_range(n2, partials, members, count, j, Ln, m_out, flags)) return;
     BarrettCtx<E> B;
-    B.sm = s_scratch[wave];
-    B.limbs = L;
-    B.s = (unsigned)mod2[3 * C];
-    B.M = ld_load<E>(mod2, C);
-    B.mu = ld_load<E>(mod2 + C, C);
+    barrett_from_block(B, mod2, L, s_scratch[wave]);
     unsigned st = ST_OK;
     LD<E> A = ld_zero<E>(), Bv = A;
     for (unsigned sign = 0; sign < 2; ++sign) {
@@ -1438,11 +1342,7 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_combine_t(con
     }
     // the tail: A = B mod n must hold; x = ((A - B mod n^2) / n) (B mod n)^-1 mod n; plaintext = x mu2 mod n
     BarrettCtx<E> N;
-    N.sm = s_scratch[wave];
-    N.limbs = L;
-    N.s = (unsigned)modn[3 * C];
-    N.M = ld_load<E>(modn, C);
-    N.mu = ld_load<E>(modn + C, C);
+    barrett_from_block(N, modn, L, s_scratch[wave]);
     const LD<E> one = ld_small<E>(1);
     LD<E> q, ra, rb, D, x, rem, inv, t, m;
     st |= mul_mod(N, q, ra, A, one, tmul);
@@ -1453,7 +1353,7 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_combine_t(con
     const bool bad = __ballot(ne) != 0;
     if (ld_sub(D, A, Bv)) (void)ld_add(D, D, n2, false);   // A - B + 2^capacity + n^2: the carry-out is that 2^capacity
     st |= mul_mod(N, x, rem, D, one, tmul);   // an exact division where A = B mod n
-    const unsigned fi = ld_inv_mod(inv, rb, ld_load<E>(modn + 2 * C, C), inv_iters);
+    const unsigned fi = ld_inv_mod(inv, rb, ld_load<E>(block_modulus<E>(modn), C), inv_iters);
     st |= mul_mod(N, q, t, x, inv, tmul);
     st |= mul_mod(N, q, m, t, ld_load<E>(mu2, Ln), tmul);
     if (bad || fi != INV_OK) m = ld_zero<E>();
@@ -1538,21 +1438,63 @@ static void chain_handoff_set(ChainDesc& d, const ChainHandoff& h, size_t i, uns
     d.spin_limit = h.hooks.spin_limit;
     d.test_no_publish = h.hooks.test_no_publish;
 }
+// the capacity (limbs) of the instantiation that serves operands of L limbs: E = 1 up to 64, E = 2 above
+static unsigned capacity(unsigned L) { return L <= 64 ? 64 : 128; }
+// one launch on the context's stream of kernel<E> at capacity C = 64 E, checked; `lds`: dynamic LDS bytes
+#define K3_LAUNCH(ctx, kernel, C, grid, block, lds, ...)                                                 \
+    do {                                                                                                 \
+        if ((C) == 64) hipLaunchKernelGGL(kernel<1>, grid, block, lds, (ctx)->stream, __VA_ARGS__);      \
+        else hipLaunchKernelGGL(kernel<2>, grid, block, lds, (ctx)->stream, __VA_ARGS__);                \
+        HIPCHK(ctx, hipGetLastError());                                                                  \
+    } while (0)
+// the Barrett block (mod_block_words(C) words at d_block) of n (Ln limbs), or of n^2 where square != 0
+static int launch_barrett_setup(pz_ctx* ctx, unsigned C, const u64* d_n, unsigned Ln, unsigned square, u64* d_block, u32* d_status) {
+    K3_LAUNCH(ctx, k_tally_setup, C, dim3(1), dim3(64), 0, d_n, Ln, square, d_block, d_status);
+    return PZ_OK;
+}
 static int launch_chains(pz_ctx* ctx, const ChainDesc* d_descs, size_t n, unsigned L, const ChainHandoff& h) {
     // per launch: 2 m workgroups for m chains; who squares and who multiplies is decided by arrival (k_pow_mod_chain)
     for (size_t l = 0, off = 0; off < n; ++l, off += h.per_launch) {
         const size_t m = n - off < h.per_launch ? n - off : h.per_launch;
         u32* ticket = (u32*)(h.counters + l * 64);
-        if (L <= 64) hipLaunchKernelGGL(k_pow_mod_chain<1>, dim3((unsigned)(2 * m)), dim3(64 * K3_TEAM), 0, ctx->stream, d_descs + off, (unsigned)m, ticket);
-        else hipLaunchKernelGGL(k_pow_mod_chain<2>, dim3((unsigned)(2 * m)), dim3(64 * K3_TEAM), 0, ctx->stream, d_descs + off, (unsigned)m, ticket);
-        HIPCHK(ctx, hipGetLastError());
+        K3_LAUNCH(ctx, k_pow_mod_chain, capacity(L), dim3((unsigned)(2 * m)), dim3(64 * K3_TEAM), 0, d_descs + off, (unsigned)m, ticket);
     }
     return PZ_OK;
 }
 static int launch_muls(pz_ctx* ctx, const MulDesc* d_descs, size_t n, unsigned L) {
-    if (L <= 64) hipLaunchKernelGGL(k_mul_mod<1>, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_descs);
-    else hipLaunchKernelGGL(k_mul_mod<2>, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_descs);
-    HIPCHK(ctx, hipGetLastError());
+    K3_LAUNCH(ctx, k_mul_mod, capacity(L), dim3((unsigned)n), dim3(64), 0, d_descs);
+    return PZ_OK;
+}
+static unsigned bitlen_limbs(const uint64_t* a, uint32_t n) {
+    for (uint32_t i = n; i-- > 0;)
+        if (a[i]) return 64 * i + (64 - (unsigned)__builtin_clzll(a[i]));
+    return 0;
+}
+// records of pow_mod_fixed_exp over the exponent e: a square per bit and a product per set bit
+static size_t fixed_exp_steps(const uint64_t* e, uint32_t limbs) {
+    size_t need = bitlen_limbs(e, limbs);
+    for (uint32_t i = 0; i < limbs; ++i) need += (size_t)__builtin_popcountll(e[i]);
+    return need;
+}
+// the epilogue of a traced call: the result, the status word and -- for a host trace (steps_out non-null) -- the records come back,
+// the stream is drained once and the status mapped
+static int fetch_and_status(pz_ctx* ctx, void* result, const void* d_result, size_t result_bytes, const u32* d_status, void* steps_out,
+                            const void* d_steps, size_t steps_bytes) {
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(result, d_result, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&st, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (steps_out) HIPCHK(ctx, hipMemcpyAsync(steps_out, d_steps, steps_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return status_to_rc(ctx, st);
+}
+// the epilogue of a call that staged SECRETS (d_secret; in the host form d_recs too, whose records repeat them): both are overwritten
+// and the stream drained on every path past the staging, whatever the run returned; the run's error wins over the wipe's
+static int wipe_secrets_and_sync(pz_ctx* ctx, int rc, void* d_secret, size_t secret_bytes, void* d_recs, size_t rec_bytes) {
+    hipError_t e = hipMemsetAsync(d_secret, 0, secret_bytes, ctx->stream);
+    if (e == hipSuccess && rec_bytes) e = hipMemsetAsync(d_recs, 0, rec_bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (rc != PZ_OK) return rc;
+    HIPCHK(ctx, e);
     return PZ_OK;
 }
 
@@ -1583,12 +1525,8 @@ extern "C" int pz_mul_mod(pz_ctx* ctx, uint32_t limbs, const uint64_t* a, const 
     h.square_modulus = 0;
     HIPCHK(ctx, hipMemcpyAsync(d_desc, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
     PZCHK(launch_muls(ctx, d_desc, 1, limbs));
-    u32 st = 0;
     HIPCHK(ctx, hipMemcpyAsync(q, base + 3 * lb, lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(r, base + 4 * lb, lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&st, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return status_to_rc(ctx, st);
+    return fetch_and_status(ctx, r, base + 4 * lb, lb, d_status, nullptr, nullptr, 0);
 }
 
 extern "C" int pz_paillier_trace(pz_ctx* ctx, uint32_t limbs_n2, const uint64_t* n2, const uint64_t* base,
@@ -1600,14 +1538,7 @@ extern "C" int pz_paillier_trace(pz_ctx* ctx, uint32_t limbs_n2, const uint64_t*
     PZ_ENTER(ctx);
     const unsigned L = limbs_n2;
     const size_t lb = (size_t)L * 8, eb = (size_t)exp_limbs * 8;
-    // steps needed = bits(exp) + popcount(exp)
-    size_t need = 0;
-    {
-        int top = (int)exp_limbs - 1;
-        while (top >= 0 && exp[top] == 0) --top;
-        if (top >= 0) need = (size_t)top * 64 + (64 - __builtin_clzll(exp[top]));
-        for (uint32_t i = 0; i < exp_limbs; ++i) need += (size_t)__builtin_popcountll(exp[i]);
-    }
+    const size_t need = fixed_exp_steps(exp, exp_limbs);
     const size_t cap = steps_out ? *n_steps : 0;
     if (steps_out && cap < need) return PZ_ERR_CAPACITY;
     void *d_in, *d_steps = nullptr;
@@ -1667,16 +1598,8 @@ static int encrypt_impl(pz_ctx* ctx, uint32_t Ln, size_t batch, const uint64_t* 
     // circuit, paillier.rs:50,54)
     std::vector<uint32_t> ng(batch), nr(batch);
     for (size_t i = 0; i < batch; ++i) {
-        auto count = [&](const uint64_t* e) {
-            size_t need = 0;
-            int top = (int)Ln - 1;
-            while (top >= 0 && e[top] == 0) --top;
-            if (top >= 0) need = (size_t)top * 64 + (64 - __builtin_clzll(e[top]));
-            for (uint32_t k = 0; k < Ln; ++k) need += (size_t)__builtin_popcountll(e[k]);
-            return (uint32_t)need;
-        };
-        ng[i] = uniform_m_bits ? 2 * uniform_m_bits : count(m + i * Ln);
-        nr[i] = count(n + i * Ln);
+        ng[i] = uniform_m_bits ? 2 * uniform_m_bits : (uint32_t)fixed_exp_steps(m + i * Ln, Ln);
+        nr[i] = (uint32_t)fixed_exp_steps(n + i * Ln, Ln);
         if (uniform_m_bits) {   // the message must fit the bits the circuit decomposes
             for (uint32_t b = uniform_m_bits; b < 64 * Ln; ++b)
                 if ((m[i * Ln + (b >> 6)] >> (b & 63)) & 1) return PZ_ERR_MESSAGE_RANGE;
@@ -1768,21 +1691,17 @@ static int encrypt_impl(pz_ctx* ctx, uint32_t Ln, size_t batch, const uint64_t* 
         PZCHK(launch_chains(ctx, d_ch, 2 * batch, L, hb));
         PZCHK(launch_muls(ctx, d_mu, batch, L));
     }
-    u32 st = 0;
-    HIPCHK(ctx, hipMemcpyAsync(c_out, d_c, batch * lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&st, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (steps_out && !steps_on_device)
+    if (steps_out && !steps_on_device)   // every instance's own count of records, not the whole capacity
         for (size_t i = 0; i < batch; ++i) {
             size_t cnt = (size_t)ng[i] + nr[i] + 1;
             HIPCHK(ctx, hipMemcpyAsync(steps_out + i * steps_cap * 4 * L, d_steps + i * steps_cap * 4 * L,
                                        cnt * 4 * lb, hipMemcpyDeviceToHost, ctx->stream));
         }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < batch; ++i) {
         if (n_steps_g) n_steps_g[i] = ng[i];
         if (n_steps_r) n_steps_r[i] = nr[i];
     }
-    return status_to_rc(ctx, st);
+    return fetch_and_status(ctx, c_out, d_c, batch * lb, d_status, nullptr, nullptr, 0);
 }
 
 extern "C" int pz_paillier_encrypt(pz_ctx* ctx, uint32_t limbs_n, size_t batch, const uint64_t* n, const uint64_t* g,
@@ -1829,13 +1748,8 @@ static int tally_levels(pz_ctx* ctx, unsigned C, const u64* d_mod, const u64* el
     while (len > 1) {
         const size_t blocks = len / 2;
         u64* out = d_steps + rec_off * rec;
-        if (C == 64)
-            hipLaunchKernelGGL(k_tally_level<1>, dim3((unsigned)blocks), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, elems, stride,
-                               (unsigned)n_regular, tail, out, L, d_status);
-        else
-            hipLaunchKernelGGL(k_tally_level<2>, dim3((unsigned)blocks), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, elems, stride,
-                               (unsigned)n_regular, tail, out, L, d_status);
-        HIPCHK(ctx, hipGetLastError());
+        K3_LAUNCH(ctx, k_tally_level, C, dim3((unsigned)blocks), dim3(64 * K3_TEAM), 0, d_mod, elems, stride, (unsigned)n_regular, tail, out, L,
+                  d_status);
         const u64* last = n_regular == len ? elems + (len - 1) * stride : tail;
         tail = (len & 1) ? last : nullptr;
         elems = out + 3 * (size_t)L;
@@ -1856,8 +1770,8 @@ static int tally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, const uint64_t* n,
     if (steps_out && steps_cap < count - 1) return PZ_ERR_CAPACITY;
     PZ_ENTER(ctx);
     const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, rec = 4 * (size_t)L;
-    const unsigned C = L <= 64 ? 64 : 128;
-    const size_t in_bytes = (nb + count * lb + 255) & ~(size_t)255, mod_bytes = ((size_t)3 * C + 2) * 8;
+    const unsigned C = capacity(L);
+    const size_t in_bytes = (nb + count * lb + 255) & ~(size_t)255, mod_bytes = mod_block_words(C) * 8;
     void* d;
     PZCHK(pz_ws_get(ctx, WS_BIG_A, in_bytes + mod_bytes + 256, &d));
     char* p = (char*)d;
@@ -1877,18 +1791,10 @@ static int tally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, const uint64_t* n,
     const u64* root = nullptr;
     {
         pz_timer tm(ctx, PZ_T_TRACE);
-        if (C == 64) hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod, d_status);
-        else hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod, d_status);
-        HIPCHK(ctx, hipGetLastError());
+        PZCHK(launch_barrett_setup(ctx, C, d_n, Ln, 1, d_mod, d_status));
         PZCHK(tally_levels(ctx, C, d_mod, d_cts, count, L, d_steps, d_status, &root));
     }
-    u32 st = 0;
-    HIPCHK(ctx, hipMemcpyAsync(c_out, root, lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&st, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (steps_out && !steps_on_device)
-        HIPCHK(ctx, hipMemcpyAsync(steps_out, d_steps, (count - 1) * rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return status_to_rc(ctx, st);
+    return fetch_and_status(ctx, c_out, root, lb, d_status, steps_on_device ? nullptr : steps_out, d_steps, (count - 1) * rec * 8);
 }
 extern "C" int pz_paillier_tally(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts,
                                  uint64_t* steps_out, size_t steps_cap, uint64_t* c_out) {
@@ -1915,10 +1821,10 @@ static int wtally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t w_bits, 
             if (weights[i] >> w_bits) return PZ_ERR_MESSAGE_RANGE;
     PZ_ENTER(ctx);
     const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, rec = 4 * (size_t)L;
-    const unsigned C = L <= 64 ? 64 : 128;
+    const unsigned C = capacity(L);
     // n | c_1 .. c_count | w_1 .. w_count | the powers | Barrett constants | status
     const size_t in_bytes = (nb + count * lb + count * 8 + 255) & ~(size_t)255, pow_bytes = (count * lb + 255) & ~(size_t)255;
-    const size_t mod_bytes = ((size_t)3 * C + 2) * 8;
+    const size_t mod_bytes = mod_block_words(C) * 8;
     void* d;
     PZCHK(pz_ws_get(ctx, WS_BIG_A, in_bytes + pow_bytes + mod_bytes + 256, &d));
     char* p = (char*)d;
@@ -1947,25 +1853,11 @@ static int wtally_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t w_bits, 
     const u64* root = nullptr;
     {
         pz_timer tm(ctx, PZ_T_TRACE);
-        if (C == 64) {
-            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod, d_status);
-            hipLaunchKernelGGL(k_wtally_pow<1>, dim3((unsigned)count), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, d_cts, d_w, w_bits, d_steps,
-                               d_pow, L, d_status);
-        } else {
-            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod, d_status);
-            hipLaunchKernelGGL(k_wtally_pow<2>, dim3((unsigned)count), dim3(64 * K3_TEAM), 0, ctx->stream, d_mod, d_cts, d_w, w_bits, d_steps,
-                               d_pow, L, d_status);
-        }
-        HIPCHK(ctx, hipGetLastError());
+        PZCHK(launch_barrett_setup(ctx, C, d_n, Ln, 1, d_mod, d_status));
+        K3_LAUNCH(ctx, k_wtally_pow, C, dim3((unsigned)count), dim3(64 * K3_TEAM), 0, d_mod, d_cts, d_w, w_bits, d_steps, d_pow, L, d_status);
         PZCHK(tally_levels(ctx, C, d_mod, d_pow, count, L, d_tree, d_status, &root));
     }
-    u32 st = 0;
-    HIPCHK(ctx, hipMemcpyAsync(c_out, root, lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&st, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (steps_out && !steps_on_device)
-        HIPCHK(ctx, hipMemcpyAsync(steps_out, d_steps, (n_chain + n_tree) * rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return status_to_rc(ctx, st);
+    return fetch_and_status(ctx, c_out, root, lb, d_status, steps_on_device ? nullptr : steps_out, d_steps, (n_chain + n_tree) * rec * 8);
 }
 extern "C" int pz_paillier_wtally(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t w_bits, const uint64_t* n, const uint64_t* cts,
                                   const uint64_t* weights, uint64_t* steps_out, size_t steps_cap, uint64_t* c_out) {
@@ -1990,7 +1882,7 @@ struct BallotArgs {
     u32* d_status;
 };
 static int ballot_run(pz_ctx* ctx, const BallotArgs& a) {
-    const unsigned L = 2 * a.Ln, C = L <= 64 ? 64 : 128;
+    const unsigned L = 2 * a.Ln, C = capacity(L);
     const size_t nb = (size_t)a.Ln * 8, lb = (size_t)L * 8;
     HIPCHK(ctx, hipMemcpyAsync(a.d_n, a.n, nb, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(a.d_g, a.g, nb, hipMemcpyHostToDevice, ctx->stream));
@@ -1999,24 +1891,12 @@ static int ballot_run(pz_ctx* ctx, const BallotArgs& a) {
     HIPCHK(ctx, hipMemsetAsync(a.d_status, 0, 4, ctx->stream));
     {
         pz_timer tm(ctx, PZ_T_TRACE);
-        if (C == 64) {
-            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, a.d_n, a.Ln, 1u, a.d_mod, a.d_status);
-            hipLaunchKernelGGL(k_ballot_enc<1>, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, ctx->stream, a.d_mod, a.d_n, a.d_g, a.d_ms,
-                               a.d_rs, a.m_bits, a.n_bits, a.per, a.d_steps, a.d_c, a.Ln, a.d_status);
-        } else {
-            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, a.d_n, a.Ln, 1u, a.d_mod, a.d_status);
-            hipLaunchKernelGGL(k_ballot_enc<2>, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, ctx->stream, a.d_mod, a.d_n, a.d_g, a.d_ms,
-                               a.d_rs, a.m_bits, a.n_bits, a.per, a.d_steps, a.d_c, a.Ln, a.d_status);
-        }
-        HIPCHK(ctx, hipGetLastError());
+        PZCHK(launch_barrett_setup(ctx, C, a.d_n, a.Ln, 1, a.d_mod, a.d_status));
+        K3_LAUNCH(ctx, k_ballot_enc, C, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, a.d_mod, a.d_n, a.d_g, a.d_ms, a.d_rs, a.m_bits, a.n_bits,
+                  a.per, a.d_steps, a.d_c, a.Ln, a.d_status);
     }
-    u32 st = 0;
-    HIPCHK(ctx, hipMemcpyAsync(a.c_out, a.d_c, a.count * lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&st, a.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (a.steps_out && !a.steps_on_device)
-        HIPCHK(ctx, hipMemcpyAsync(a.steps_out, a.d_steps, a.count * a.per * 4 * lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return status_to_rc(ctx, st);
+    return fetch_and_status(ctx, a.c_out, a.d_c, a.count * lb, a.d_status, a.steps_on_device ? nullptr : a.steps_out, a.d_steps,
+                            a.count * a.per * 4 * lb);
 }
 static int ballot_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t m_bits, const uint64_t* n, const uint64_t* g, const uint64_t* ms,
                        const uint64_t* rs, uint64_t* steps_out, int steps_on_device, size_t steps_cap, uint32_t* n_steps_r, uint64_t* c_out) {
@@ -2025,14 +1905,7 @@ static int ballot_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t m_bits, 
     const unsigned L = 2 * Ln;
     if (L > 128) return PZ_ERR_UNSUPPORTED;
     // n's bits are public structure of the circuit (pow_mod_fixed_exp): the records of one r^n chain are counted here
-    uint32_t n_bits = 0, nr = 0;
-    for (int top = (int)Ln - 1; top >= 0; --top)
-        if (n[top]) {
-            n_bits = (uint32_t)top * 64 + (64 - __builtin_clzll(n[top]));
-            break;
-        }
-    for (uint32_t k = 0; k < Ln; ++k) nr += (uint32_t)__builtin_popcountll(n[k]);
-    nr += n_bits;
+    const uint32_t n_bits = bitlen_limbs(n, Ln), nr = (uint32_t)fixed_exp_steps(n, Ln);
     const uint32_t per = 2 * m_bits + nr + 1;
     if (steps_out && steps_cap < count * per) return PZ_ERR_CAPACITY;
     if (m_bits < 64)   // before any launch: the circuit's num_to_bits of such a message cannot hold
@@ -2041,10 +1914,9 @@ static int ballot_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t m_bits, 
     if (n_bits == 0) return PZ_ERR_ZERO_MODULUS;
     PZ_ENTER(ctx);
     const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8;
-    const unsigned C = L <= 64 ? 64 : 128;
     // n | g | m_1 .. m_count | r_1 .. r_count | c_1 .. c_count | Barrett constants | status
     const size_t pub_bytes = (2 * nb + 255) & ~(size_t)255, sec_bytes = (count * 8 + count * nb + 255) & ~(size_t)255;
-    const size_t c_bytes = (count * lb + 255) & ~(size_t)255, mod_bytes = ((size_t)3 * C + 2) * 8;
+    const size_t c_bytes = (count * lb + 255) & ~(size_t)255, mod_bytes = mod_block_words(capacity(L)) * 8;
     void* d;
     PZCHK(pz_ws_get(ctx, WS_BIG_A, pub_bytes + sec_bytes + c_bytes + mod_bytes + 256, &d));
     char* p = (char*)d;
@@ -2065,12 +1937,7 @@ static int ballot_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t m_bits, 
         PZCHK(pz_ws_get(ctx, WS_BIG_B, rec_bytes, &t));
         a.d_steps = (u64*)t;
     }
-    const int rc = ballot_run(ctx, a);
-    hipError_t e = hipMemsetAsync(a.d_ms, 0, sec_bytes, ctx->stream);
-    if (e == hipSuccess && rec_bytes) e = hipMemsetAsync(a.d_steps, 0, rec_bytes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (rc != PZ_OK) return rc;
-    HIPCHK(ctx, e);
+    PZCHK(wipe_secrets_and_sync(ctx, ballot_run(ctx, a), a.d_ms, sec_bytes, a.d_steps, rec_bytes));
     if (n_steps_r) *n_steps_r = nr;
     return PZ_OK;
 }
@@ -2105,7 +1972,7 @@ struct PartialArgs {
     u32* d_status;
 };
 static int partial_run(pz_ctx* ctx, const PartialArgs& a) {
-    const unsigned L = 2 * a.Ln, C = L <= 64 ? 64 : 128;
+    const unsigned L = 2 * a.Ln, C = capacity(L);
     const size_t nb = (size_t)a.Ln * 8, lb = (size_t)L * 8;
     HIPCHK(ctx, hipMemcpyAsync(a.d_n, a.n, nb, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(a.d_v, a.v, lb, hipMemcpyHostToDevice, ctx->stream));
@@ -2114,26 +1981,13 @@ static int partial_run(pz_ctx* ctx, const PartialArgs& a) {
     HIPCHK(ctx, hipMemsetAsync(a.d_status, 0, 4, ctx->stream));
     {
         pz_timer tm(ctx, PZ_T_TRACE);
-        const dim3 grid((unsigned)a.count + 1), block(64 * K3_TEAM);
-        if (C == 64) {
-            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, a.d_n, a.Ln, 1u, a.d_mod, a.d_status);
-            hipLaunchKernelGGL(k_partial_pow<1>, grid, block, 0, ctx->stream, a.d_mod, a.d_v, a.d_cts, a.d_theta, a.e_bits, (unsigned)a.count,
-                               a.d_steps, a.d_out, a.d_out + L, L, a.d_status);
-        } else {
-            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, a.d_n, a.Ln, 1u, a.d_mod, a.d_status);
-            hipLaunchKernelGGL(k_partial_pow<2>, grid, block, 0, ctx->stream, a.d_mod, a.d_v, a.d_cts, a.d_theta, a.e_bits, (unsigned)a.count,
-                               a.d_steps, a.d_out, a.d_out + L, L, a.d_status);
-        }
-        HIPCHK(ctx, hipGetLastError());
+        PZCHK(launch_barrett_setup(ctx, C, a.d_n, a.Ln, 1, a.d_mod, a.d_status));
+        K3_LAUNCH(ctx, k_partial_pow, C, dim3((unsigned)a.count + 1), dim3(64 * K3_TEAM), 0, a.d_mod, a.d_v, a.d_cts, a.d_theta, a.e_bits,
+                  (unsigned)a.count, a.d_steps, a.d_out, a.d_out + L, L, a.d_status);
     }
-    u32 st = 0;
     HIPCHK(ctx, hipMemcpyAsync(a.h_out, a.d_out, lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(a.u_out, a.d_out + L, a.count * lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&st, a.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (a.steps_out && !a.steps_on_device)
-        HIPCHK(ctx, hipMemcpyAsync(a.steps_out, a.d_steps, a.n_rec * 4 * lb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return status_to_rc(ctx, st);
+    return fetch_and_status(ctx, a.u_out, a.d_out + L, a.count * lb, a.d_status, a.steps_on_device ? nullptr : a.steps_out, a.d_steps,
+                            a.n_rec * 4 * lb);
 }
 static int partial_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t e_bits, const uint64_t* n, const uint64_t* v, const uint64_t* theta,
                         const uint64_t* cts, uint64_t* steps_out, int steps_on_device, size_t steps_cap, uint64_t* h_out, uint64_t* u_out) {
@@ -2148,10 +2002,9 @@ static int partial_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t e_bits,
     if (is_zero_limbs(n, Ln)) return PZ_ERR_ZERO_MODULUS;
     PZ_ENTER(ctx);
     const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8;
-    const unsigned C = L <= 64 ? 64 : 128;
     // n | v | c_1 .. c_count | theta | h | u_1 .. u_count | Barrett constants | status
     const size_t pub_bytes = (nb + lb + count * lb + 255) & ~(size_t)255, sec_bytes = (lb + 255) & ~(size_t)255;
-    const size_t out_bytes = ((count + 1) * lb + 255) & ~(size_t)255, mod_bytes = ((size_t)3 * C + 2) * 8;
+    const size_t out_bytes = ((count + 1) * lb + 255) & ~(size_t)255, mod_bytes = mod_block_words(capacity(L)) * 8;
     void* d;
     PZCHK(pz_ws_get(ctx, WS_BIG_A, pub_bytes + sec_bytes + out_bytes + mod_bytes + 256, &d));
     char* p = (char*)d;
@@ -2173,13 +2026,7 @@ static int partial_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t e_bits,
         PZCHK(pz_ws_get(ctx, WS_BIG_B, rec_bytes, &t));
         a.d_steps = (u64*)t;
     }
-    const int rc = partial_run(ctx, a);
-    hipError_t e = hipMemsetAsync(a.d_theta, 0, sec_bytes, ctx->stream);
-    if (e == hipSuccess && rec_bytes) e = hipMemsetAsync(a.d_steps, 0, rec_bytes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (rc != PZ_OK) return rc;
-    HIPCHK(ctx, e);
-    return PZ_OK;
+    return wipe_secrets_and_sync(ctx, partial_run(ctx, a), a.d_theta, sec_bytes, a.d_steps, rec_bytes);
 }
 extern "C" int pz_paillier_partial(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t e_bits, const uint64_t* n, const uint64_t* v,
                                    const uint64_t* theta, const uint64_t* cts, uint64_t* steps_out, size_t steps_cap, uint64_t* h_out,
@@ -2195,22 +2042,28 @@ extern "C" int pz_paillier_partial_dev(pz_ctx* ctx, uint32_t limbs_n, size_t cou
 // The combiner: m_j = L(prod_i u_ij mod n^2) mu2 mod n (k_partial_combine, one team per ciphertext, one launch).  n and mu2 are the
 // public threshold key's (HOST words in both forms); the host form stages the partials and fetches m and the flags, the device form
 // queues everything on the context's stream and returns.
-static int combine_impl(pz_ctx* ctx, uint32_t Ln, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
-                        const uint64_t* partials, uint64_t* m_out, uint8_t* flags_out, int on_device) {
-    if (!ctx || !n || !mu2 || !partials || !m_out || !flags_out || Ln == 0) return PZ_ERR_INVALID;
-    if (count < 1 || count > K3_PARTIAL_MAX || trustees < 1 || trustees > 256) return PZ_ERR_INVALID;
-    if (2 * (uint64_t)Ln > 128) return PZ_ERR_UNSUPPORTED;
-    if (is_zero_limbs(n, Ln)) return PZ_ERR_ZERO_MODULUS;
+// The t-of-T combiner shares all of it (combine_run) and adds its public exponents and signs (CombineExps; null: k_partial_combine).
+struct CombineExps {
+    const uint64_t* exps;   // members x exp_words HOST words
+    uint32_t exp_words;
+    const uint8_t* neg;     // members HOST bytes
+    unsigned max_bits;      // the longest exponent: the chain length
+};
+static int combine_run(pz_ctx* ctx, uint32_t Ln, size_t count, size_t members, const uint64_t* n, const uint64_t* mu2, const CombineExps* x,
+                       const uint64_t* partials, uint64_t* m_out, uint8_t* flags_out, int on_device) {
     PZ_ENTER(ctx);
-    const unsigned L = 2 * Ln, C = L <= 64 ? 64 : 128;
-    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, mod_words = (size_t)3 * C + 2;
-    // n | mu2 | Barrett constants of n^2 and of n | status | host form: the partials, m, the flags
-    const size_t key_bytes = (2 * nb + 255) & ~(size_t)255, mod_bytes = 2 * mod_words * 8 + 64;
-    const size_t io_bytes = on_device ? 0 : trustees * count * lb + count * nb + ((count + 7) & ~(size_t)7);
+    const unsigned L = 2 * Ln, C = capacity(L);
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, mod_words = mod_block_words(C);
+    // n | mu2 | t-of-T: exponents | signs | Barrett constants of n^2 and of n | status | host form: the partials, m, the flags
+    const size_t exp_bytes = x ? members * x->exp_words * 8 : 0, neg_bytes = x ? (members + 7) & ~(size_t)7 : 0;
+    const size_t key_bytes = (2 * nb + exp_bytes + neg_bytes + 255) & ~(size_t)255, mod_bytes = 2 * mod_words * 8 + 64;
+    const size_t io_bytes = on_device ? 0 : members * count * lb + count * nb + ((count + 7) & ~(size_t)7);
     void* ws;
     PZCHK(pz_ws_get(ctx, WS_BIG_A, key_bytes + mod_bytes + io_bytes + 64, &ws));
     char* p = (char*)ws;
-    u64 *d_n = (u64*)p, *d_mu2 = d_n + Ln, *d_mod2 = (u64*)(p + key_bytes), *d_modn = d_mod2 + mod_words;
+    u64 *d_n = (u64*)p, *d_mu2 = d_n + Ln, *d_exps = d_mu2 + Ln;
+    uint8_t* d_neg = (uint8_t*)d_exps + exp_bytes;
+    u64 *d_mod2 = (u64*)(p + key_bytes), *d_modn = d_mod2 + mod_words;
     u32* d_status = (u32*)(d_modn + mod_words);
     const u64* d_parts = partials;
     u64* d_m = m_out;
@@ -2218,28 +2071,27 @@ static int combine_impl(pz_ctx* ctx, uint32_t Ln, size_t count, size_t trustees,
     if (!on_device) {
         u64* q = (u64*)(p + key_bytes + mod_bytes);
         d_parts = q;
-        d_m = q + trustees * count * L;
+        d_m = q + members * count * L;
         d_flags = (uint8_t*)(d_m + count * Ln);
-        HIPCHK(ctx, hipMemcpyAsync(q, partials, trustees * count * lb, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(q, partials, members * count * lb, hipMemcpyHostToDevice, ctx->stream));
     }
     HIPCHK(ctx, hipMemcpyAsync(d_n, n, nb, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_mu2, mu2, nb, hipMemcpyHostToDevice, ctx->stream));
+    if (x) {
+        HIPCHK(ctx, hipMemcpyAsync(d_exps, x->exps, exp_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_neg, x->neg, members, hipMemcpyHostToDevice, ctx->stream));
+    }
     HIPCHK(ctx, hipMemsetAsync(d_status, 0, 4, ctx->stream));
     {
         pz_timer tm(ctx, PZ_T_TRACE);
         const dim3 grid((unsigned)count), block(64 * K3_TEAM);
-        if (C == 64) {
-            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod2, d_status);
-            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 0u, d_modn, d_status);
-            hipLaunchKernelGGL(k_partial_combine<1>, grid, block, 0, ctx->stream, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)trustees,
-                               d_mu2, d_m, d_flags, Ln);
-        } else {
-            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod2, d_status);
-            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 0u, d_modn, d_status);
-            hipLaunchKernelGGL(k_partial_combine<2>, grid, block, 0, ctx->stream, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)trustees,
-                               d_mu2, d_m, d_flags, Ln);
-        }
-        HIPCHK(ctx, hipGetLastError());
+        PZCHK(launch_barrett_setup(ctx, C, d_n, Ln, 1, d_mod2, d_status));
+        PZCHK(launch_barrett_setup(ctx, C, d_n, Ln, 0, d_modn, d_status));
+        if (x)
+            K3_LAUNCH(ctx, k_combine_t, C, grid, block, 0, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)members, d_exps, x->exp_words, d_neg,
+                      x->max_bits, 2 * bitlen_limbs(n, Ln) + 4, d_mu2, d_m, d_flags, Ln);
+        else
+            K3_LAUNCH(ctx, k_partial_combine, C, grid, block, 0, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)members, d_mu2, d_m, d_flags, Ln);
     }
     if (on_device) return PZ_OK;
     HIPCHK(ctx, hipMemcpyAsync(m_out, d_m, count * nb, hipMemcpyDeviceToHost, ctx->stream));
@@ -2248,10 +2100,18 @@ static int combine_impl(pz_ctx* ctx, uint32_t Ln, size_t count, size_t trustees,
     unsigned any = 0;
     for (size_t i = 0; i < count; ++i) any |= flags_out[i];
     if (any & CMB_F_INTERNAL) {
-        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: internal consistency check failed (combination)");
+        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: internal consistency check failed (%scombination)", x ? "t-of-T " : "");
         return PZ_ERR_HIP;
     }
     return (any & CMB_F_RANGE) ? PZ_ERR_RANGE : PZ_OK;
+}
+static int combine_impl(pz_ctx* ctx, uint32_t Ln, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
+                        const uint64_t* partials, uint64_t* m_out, uint8_t* flags_out, int on_device) {
+    if (!ctx || !n || !mu2 || !partials || !m_out || !flags_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_PARTIAL_MAX || trustees < 1 || trustees > 256) return PZ_ERR_INVALID;
+    if (2 * (uint64_t)Ln > 128) return PZ_ERR_UNSUPPORTED;
+    if (is_zero_limbs(n, Ln)) return PZ_ERR_ZERO_MODULUS;
+    return combine_run(ctx, Ln, count, trustees, n, mu2, nullptr, partials, m_out, flags_out, on_device);
 }
 extern "C" int pz_paillier_combine(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t trustees, const uint64_t* n, const uint64_t* mu2,
                                    const uint64_t* partials, uint64_t* m_out, uint8_t* flags_out) {
@@ -2265,11 +2125,6 @@ extern "C" int pz_paillier_combine_dev(pz_ctx* ctx, uint32_t limbs_n, size_t cou
 // Batch modular inverse under ONE odd modulus: k_mod_inverse, one wave per value.  The modulus is HOST words in both
 // forms; the iteration bound of every wave is 2 bitlen(mod) + 4, from the modulus alone.
 #define K3_INV_MAX 65536
-static unsigned bitlen_limbs(const uint64_t* a, uint32_t n) {
-    for (uint32_t i = n; i-- > 0;)
-        if (a[i]) return 64 * i + (64 - (unsigned)__builtin_clzll(a[i]));
-    return 0;
-}
 static int mod_inverse_impl(pz_ctx* ctx, uint32_t limbs, size_t count, const uint64_t* mod, const uint64_t* xs, uint64_t* inv_out,
                             uint8_t* flags_out, int on_device) {
     if (!ctx || !mod || !xs || !inv_out || !flags_out || limbs == 0 || count < 1 || count > K3_INV_MAX) return PZ_ERR_INVALID;
@@ -2297,11 +2152,7 @@ static int mod_inverse_impl(pz_ctx* ctx, uint32_t limbs, size_t count, const uin
         pz_timer tm(ctx, PZ_T_TRACE);
         const dim3 grid((unsigned)((count + K3_INV_WAVES - 1) / K3_INV_WAVES)), block(64 * K3_INV_WAVES);
         const unsigned iters = 2 * bitlen_limbs(mod, limbs) + 4;
-        if (limbs <= 64)
-            hipLaunchKernelGGL(k_mod_inverse<1>, grid, block, 0, ctx->stream, d_mod, d_xs, d_inv, d_flags, limbs, (unsigned)count, iters);
-        else
-            hipLaunchKernelGGL(k_mod_inverse<2>, grid, block, 0, ctx->stream, d_mod, d_xs, d_inv, d_flags, limbs, (unsigned)count, iters);
-        HIPCHK(ctx, hipGetLastError());
+        K3_LAUNCH(ctx, k_mod_inverse, capacity(limbs), grid, block, 0, d_mod, d_xs, d_inv, d_flags, limbs, (unsigned)count, iters);
     }
     if (on_device) return PZ_OK;
     HIPCHK(ctx, hipMemcpyAsync(inv_out, d_inv, count * vb, hipMemcpyDeviceToHost, ctx->stream));
@@ -2341,63 +2192,8 @@ static int combine_t_impl(pz_ctx* ctx, uint32_t Ln, size_t count, size_t members
     }
     for (size_t i = 0; i < members; ++i)
         if (neg[i] > 1) return PZ_ERR_INVALID;
-    PZ_ENTER(ctx);
-    const unsigned L = 2 * Ln, C = L <= 64 ? 64 : 128;
-    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, mod_words = (size_t)3 * C + 2;
-    // n | mu2 | exponents | signs | Barrett constants of n^2 and of n | status | host form: the partials, m, the flags
-    const size_t exp_bytes = members * exp_words * 8, neg_bytes = (members + 7) & ~(size_t)7;
-    const size_t key_bytes = (2 * nb + exp_bytes + neg_bytes + 255) & ~(size_t)255, mod_bytes = 2 * mod_words * 8 + 64;
-    const size_t io_bytes = on_device ? 0 : members * count * lb + count * nb + ((count + 7) & ~(size_t)7);
-    void* ws;
-    PZCHK(pz_ws_get(ctx, WS_BIG_A, key_bytes + mod_bytes + io_bytes + 64, &ws));
-    char* p = (char*)ws;
-    u64 *d_n = (u64*)p, *d_mu2 = d_n + Ln, *d_exps = d_mu2 + Ln;
-    uint8_t* d_neg = (uint8_t*)(d_exps + members * exp_words);
-    u64 *d_mod2 = (u64*)(p + key_bytes), *d_modn = d_mod2 + mod_words;
-    u32* d_status = (u32*)(d_modn + mod_words);
-    const u64* d_parts = partials;
-    u64* d_m = m_out;
-    uint8_t* d_flags = flags_out;
-    if (!on_device) {
-        u64* q = (u64*)(p + key_bytes + mod_bytes);
-        d_parts = q;
-        d_m = q + members * count * L;
-        d_flags = (uint8_t*)(d_m + count * Ln);
-        HIPCHK(ctx, hipMemcpyAsync(q, partials, members * count * lb, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d_n, n, nb, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_mu2, mu2, nb, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_exps, exps, exp_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_neg, neg, members, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(d_status, 0, 4, ctx->stream));
-    {
-        pz_timer tm(ctx, PZ_T_TRACE);
-        const dim3 grid((unsigned)count), block(64 * K3_TEAM);
-        const unsigned iters = 2 * bitlen_limbs(n, Ln) + 4;
-        if (C == 64) {
-            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod2, d_status);
-            hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 0u, d_modn, d_status);
-            hipLaunchKernelGGL(k_combine_t<1>, grid, block, 0, ctx->stream, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)members, d_exps,
-                               exp_words, d_neg, max_bits, iters, d_mu2, d_m, d_flags, Ln);
-        } else {
-            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 1u, d_mod2, d_status);
-            hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, d_n, Ln, 0u, d_modn, d_status);
-            hipLaunchKernelGGL(k_combine_t<2>, grid, block, 0, ctx->stream, d_mod2, d_modn, d_parts, (unsigned)count, (unsigned)members, d_exps,
-                               exp_words, d_neg, max_bits, iters, d_mu2, d_m, d_flags, Ln);
-        }
-        HIPCHK(ctx, hipGetLastError());
-    }
-    if (on_device) return PZ_OK;
-    HIPCHK(ctx, hipMemcpyAsync(m_out, d_m, count * nb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(flags_out, d_flags, count, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    unsigned any = 0;
-    for (size_t i = 0; i < count; ++i) any |= flags_out[i];
-    if (any & CMB_F_INTERNAL) {
-        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: internal consistency check failed (t-of-T combination)");
-        return PZ_ERR_HIP;
-    }
-    return (any & CMB_F_RANGE) ? PZ_ERR_RANGE : PZ_OK;
+    const CombineExps x{exps, exp_words, neg, max_bits};
+    return combine_run(ctx, Ln, count, members, n, mu2, &x, partials, m_out, flags_out, on_device);
 }
 extern "C" int pz_paillier_combine_t(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_t members, const uint64_t* n, const uint64_t* mu2,
                                      const uint64_t* exps, uint32_t exp_words, const uint8_t* neg, const uint64_t* partials,
@@ -2442,30 +2238,19 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_dec_pow(const
     __shared__ u64 s_scratch[K3_TEAM][2 * C];
     __shared__ TeamBuf<E> s_team[2];
     extern __shared__ u64 s_table[];   // 2^w entries of Lp limbs
-    if (A.modP[3 * C + 1] == 0) return;   // zero modulus (pz_paillier_sk_create refuses it: no handle reaches here with one)
+    if (*block_ok<E>(A.modP) == 0) return;   // zero modulus (pz_paillier_sk_create refuses it: no handle reaches here with one)
     const unsigned wave = threadIdx.x >> 6, lane = lane_id();
     TeamCtx<E> T;
-    T.buf = s_team;
-    T.w = wave;
-    T.parity = 0;
+    team_init(T, s_team);
     TeamMul<E> tmul{&T};
-    {   // the exchange rows are zero outside the ranges the products write (TeamBuf::row)
-        u64* z = (u64*)s_team;
-        for (unsigned t = threadIdx.x; t < sizeof(s_team) / 8; t += blockDim.x) z[t] = 0;
-        __syncthreads();
-    }
     BarrettCtx<E> B;
-    B.sm = s_scratch[wave];
-    B.limbs = A.Lp;
-    B.s = (unsigned)A.modP[3 * C];
-    B.M = ld_load<E>(A.modP, C);
-    B.mu = ld_load<E>(A.modP + C, C);
+    barrett_from_block(B, A.modP, A.Lp, s_scratch[wave]);
     const size_t chain = blockIdx.x;
     const unsigned Lp = A.Lp, Ln = A.Ln, nent = 1u << A.w;
     const LD<E> base = ld_load<E>(A.base + chain * A.base_stride, A.base_limbs);
     {   // a base >= the modulus (a ciphertext >= n^2: public).  The four waves hold the same values: the team leaves together
         LD<E> d;
-        if (!ld_sub(d, base, ld_load<E>(A.modP + 2 * C, C))) {
+        if (!ld_sub(d, base, ld_load<E>(block_modulus<E>(A.modP), C))) {
             if (wave == 0) {
                 const unsigned Lo = A.mode == DEC_LFN ? Ln : Lp;
                 ld_store(A.out0 + chain * Lo, ld_zero<E>(), Lo);
@@ -2534,22 +2319,12 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_dec_pow(const
         if (st && A.flags && wave == 0 && lane == 0) A.flags[chain] |= DEC_F_INTERNAL;   // (the key derivation passes none: its checks catch a wrong mu)
         return;
     }
-    // u = acc = c^lambda mod n^2: u mod n must be 1; plaintext = floor(u / n) * mu mod n
+    // u = acc = c^lambda mod n^2: the plaintext, and the base mod n
     BarrettCtx<E> N;
-    N.sm = s_scratch[wave];
-    N.limbs = Lp;
-    N.s = (unsigned)A.modN[3 * C];
-    N.M = ld_load<E>(A.modN, C);
-    N.mu = ld_load<E>(A.modN + C, C);
-    LD<E> x, rem, q, m, cn;
-    st |= mul_mod(N, x, rem, acc, one, tmul);
-    bool ne = false;
-#pragma unroll
-    for (int e = 0; e < E; ++e) ne |= rem.v[e] != one.v[e];
-    const bool bad = __ballot(ne) != 0;
-    st |= mul_mod(N, q, m, x, ld_load<E>(A.mu, Ln), tmul);
+    barrett_from_block(N, A.modN, Lp, s_scratch[wave]);
+    LD<E> m, q, cn;
+    const bool bad = lfn_tail(N, T, m, acc, A.mu, Ln, st);
     st |= mul_mod(N, q, cn, base, one, tmul);
-    if (bad) m = ld_zero<E>();
     if (wave == 0) {
         ld_store(A.out0 + chain * Ln, m, Ln);
         ld_store(A.out1 + chain * Ln, cn, Ln);
@@ -2577,9 +2352,7 @@ static unsigned dec_window() {   // PZ_K3_DEC_WINDOW (1 .. 5) is a measurement h
 }
 static int launch_dec_pow(pz_ctx* ctx, unsigned C, size_t chains, const DecPow& a) {
     const size_t table = ((size_t)8 << a.w) * a.Lp;
-    if (C == 64) hipLaunchKernelGGL(k_dec_pow<1>, dim3((unsigned)chains), dim3(64 * K3_TEAM), table, ctx->stream, a);
-    else hipLaunchKernelGGL(k_dec_pow<2>, dim3((unsigned)chains), dim3(64 * K3_TEAM), table, ctx->stream, a);
-    HIPCHK(ctx, hipGetLastError());
+    K3_LAUNCH(ctx, k_dec_pow, C, dim3((unsigned)chains), dim3(64 * K3_TEAM), table, a);
     return PZ_OK;
 }
 static int cmp_limbs(const uint64_t* a, const uint64_t* b, uint32_t n) {
@@ -2608,7 +2381,7 @@ static int sk_release(pz_ctx* ctx, pz_paillier_sk* sk) {
 static int sk_create_impl(pz_ctx* ctx, pz_paillier_sk* sk, const uint64_t* n, const uint64_t* g, const uint64_t* lambda, const uint64_t* d) {
     const uint32_t Ln = sk->Ln;
     const unsigned L = 2 * Ln, C = sk->C;
-    const size_t nb = (size_t)Ln * 8, blk = (size_t)3 * C + 2, blk1 = 3 * 64 + 2;
+    const size_t nb = (size_t)Ln * 8, blk = mod_block_words(C), blk1 = mod_block_words(64);
     sk->block_bytes = (2 * blk + blk1 + 5 * (size_t)Ln) * 8;
     void* dv;
     PZCHK(pz_dev_alloc(ctx, sk->block_bytes, &dv));
@@ -2648,15 +2421,9 @@ static int sk_create_impl(pz_ctx* ctx, pz_paillier_sk* sk, const uint64_t* n, co
     HIPCHK(ctx, hipMemcpyAsync(s_g, g, nb, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(s_lam1, lam1.data(), nb, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(s_one, one.data(), nb, hipMemcpyHostToDevice, ctx->stream));
-    if (C == 64) {
-        hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 1u, sk->d_mod2, s_status);
-        hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 0u, sk->d_modn_c, s_status);
-    } else {
-        hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 1u, sk->d_mod2, s_status);
-        hipLaunchKernelGGL(k_tally_setup<2>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 0u, sk->d_modn_c, s_status);
-        hipLaunchKernelGGL(k_tally_setup<1>, dim3(1), dim3(64), 0, ctx->stream, sk->d_n, Ln, 0u, sk->d_modn, s_status);
-    }
-    HIPCHK(ctx, hipGetLastError());
+    PZCHK(launch_barrett_setup(ctx, C, sk->d_n, Ln, 1, sk->d_mod2, s_status));
+    PZCHK(launch_barrett_setup(ctx, C, sk->d_n, Ln, 0, sk->d_modn_c, s_status));
+    if (C != 64) PZCHK(launch_barrett_setup(ctx, 64, sk->d_n, Ln, 0, sk->d_modn, s_status));   // (C = 64: d_modn is d_modn_c)
     const unsigned w = dec_window();
     DecPow a{};
     // x = L(g^lambda mod n^2) (the plaintext of g under mu = 1), g mod n, and the flag g^lambda mod n != 1
@@ -2710,12 +2477,8 @@ extern "C" int pz_paillier_sk_create(pz_ctx* ctx, uint32_t limbs_n, const uint64
     PZ_ENTER(ctx);
     pz_paillier_sk* sk = new pz_paillier_sk;
     sk->Ln = limbs_n;
-    sk->C = 2 * limbs_n <= 64 ? 64 : 128;
-    for (uint32_t i = limbs_n; i-- > 0;)
-        if (n[i]) {
-            sk->nbits = i * 64 + (64 - __builtin_clzll(n[i]));
-            break;
-        }
+    sk->C = capacity(2 * limbs_n);
+    sk->nbits = bitlen_limbs(n, limbs_n);
     const int rc = sk_create_impl(ctx, sk, n, g, lambda, d);
     if (rc != PZ_OK) {
         (void)sk_release(ctx, sk);
