@@ -461,6 +461,41 @@ int pz_paillier_combine_t_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, size_
 int pz_shamir_lagrange(uint32_t trustees, size_t members, const uint32_t* ids, uint64_t* exps_out, uint32_t exp_words, uint8_t* neg_out,
                        uint32_t* words_needed);
 
+/* Prime generation for Paillier keys: what keys.secret_from_primes / deal_shares / deal_shamir and the C++ dealers
+ * take as arguments.  Every candidate is its own odd modulus: 16 lanes hold one candidate (four per wavefront), products are Montgomery
+ * products of `limbs` outer steps, and a candidate's constants come from Newton steps and doublings, never from a division.
+ *   pz_bigint_is_prime   Miller-Rabin on `count` (1 .. 65536) candidates of `limbs` (1 .. 32) words over `rounds` (1 .. 64) bases shared by
+ *       all candidates (cands: count x limbs words; bases: rounds words, each >= 2; flags_out: count bytes; witness_out: count words; all
+ *       HOST).  Refusals, in this order and all before any launch: a null pointer, limbs = 0, count or rounds out of range, a base < 2:
+ *       PZ_ERR_INVALID; limbs > 32: PZ_ERR_UNSUPPORTED.  c < 2 or an even c > 2: flag 0, witness 0xFFFFFFFF; c = 2: flag 1, witness
+ *       0xFFFFFFFF.  Otherwise, with c - 1 = d 2^s and a = bases[k] mod c, round k passes if a is 0, 1 or c - 1, else if a^d is 1 or c - 1,
+ *       else if one of the next s - 1 squarings gives c - 1.  witness_out[j] is the index of the first round that fails, or `rounds` if
+ *       none does; flags_out[j] = 1 iff witness_out[j] = rounds.  Candidates may be SECRET (a prime found is key material): no branch and
+ *       no address of the kernel depends on a candidate -- every group runs all 64 limbs exponent bits of every round, the bits act
+ *       through lane masks and the verdict is a predicate; the device staging is overwritten before the call returns.
+ *   pz_bigint_is_prime_dev   d_cands, d_flags_out and d_witness_out are DEVICE buffers (bases stay HOST words); the work is queued on the
+ *       context's stream and the call returns without waiting.
+ *   pz_prime_sieve   the trial-division sieve alone over the `window` (1 .. 2^20) candidates c_i = start + stride i: mask_out[i] = 1 iff no
+ *       odd prime p below 2^16 (6541 of them) divides c_i and -- with safe = 1 -- none divides (c_i - 1) / 2, i.e. c_i != 1 mod p.  safe = 0:
+ *       stride 2, start odd; safe = 1: stride 4, start = 3 mod 4.  start: limbs words, mask_out: window bytes (HOST).  Refusals, in this
+ *       order and all before any launch: a null pointer, limbs = 0, window out of range, safe > 1: PZ_ERR_INVALID; limbs > 32:
+ *       PZ_ERR_UNSUPPORTED; start below 2^32 (so that no candidate is a sieve prime) or of the wrong residue: PZ_ERR_INVALID;
+ *       start + stride (window - 1) does not fit limbs words: PZ_ERR_RANGE.  Not constant time in start.
+ *   pz_prime_search   the `want` (1 .. 64) smallest offsets i of that window whose c_i survives the sieve and passes all `rounds` rounds of
+ *       pz_bigint_is_prime over `bases` -- and, with safe = 1, whose (c_i - 1) / 2 passes them too -- ascending in offsets_out (want
+ *       words); *found_out may be less than want, and an empty result is PZ_OK with *found_out = 0.  *survivors_out (may be NULL) receives
+ *       the sieve's survivor count.  Refusals: those of the two calls above, a null offsets_out or found_out and want out of range
+ *       (PZ_ERR_INVALID) first.  Survivors are tested in ascending batches, round 0 before the others, until want are found.  Every device
+ *       buffer that held the start, residues, survivors or candidates is overwritten before the call returns.  (PZ_ABI_VERSION stays 7:
+ *       additions.) */
+int pz_bigint_is_prime(pz_ctx* ctx, uint32_t limbs, size_t count, const uint64_t* cands, uint32_t rounds, const uint64_t* bases,
+                       uint8_t* flags_out, uint32_t* witness_out);
+int pz_bigint_is_prime_dev(pz_ctx* ctx, uint32_t limbs, size_t count, const uint64_t* d_cands, uint32_t rounds, const uint64_t* bases,
+                           uint8_t* d_flags_out, uint32_t* d_witness_out);
+int pz_prime_sieve(pz_ctx* ctx, uint32_t limbs, const uint64_t* start, size_t window, uint32_t safe, uint8_t* mask_out);
+int pz_prime_search(pz_ctx* ctx, uint32_t limbs, const uint64_t* start, size_t window, uint32_t safe, uint32_t rounds,
+                    const uint64_t* bases, uint32_t want, uint32_t* offsets_out, uint32_t* found_out, size_t* survivors_out);
+
 /* ---------------------------------------------------------------------------------------------
  * K4 -- expansion of a step trace into advice-column cells (Fr Montgomery, 32 B each), i.e. the
  * values halo2-lib's Context would hold after BigUintChip emitted the constraints of every

@@ -83,6 +83,10 @@ SIGNATURES = {
     "pz_paillier_combine_t": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, C.c_uint32, VP, VP, VP, VP]),
     "pz_paillier_combine_t_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, C.c_uint32, VP, VP, VP, VP]),
     "pz_shamir_lagrange": (C.c_int, [C.c_uint32, C.c_size_t, VP, VP, C.c_uint32, VP, VP]),
+    "pz_bigint_is_prime": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, C.c_uint32, VP, VP, VP]),
+    "pz_bigint_is_prime_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, C.c_uint32, VP, VP, VP]),
+    "pz_prime_sieve": (C.c_int, [VP, C.c_uint32, VP, C.c_size_t, C.c_uint32, VP]),
+    "pz_prime_search": (C.c_int, [VP, C.c_uint32, VP, C.c_size_t, C.c_uint32, C.c_uint32, VP, C.c_uint32, VP, VP, VP]),
     "pz_paillier_sk_create":(C.c_int, [VP, C.c_uint32, VP, VP, VP, VP, C.POINTER(VP)]),
     "pz_paillier_sk_params": (C.c_int, [VP, VP, VP]),
     "pz_paillier_sk_free": (C.c_int, [VP, VP]),

@@ -36,7 +36,7 @@ struct pz_wsbuf {
 };
 
 enum { WS_HIST = 0, WS_OFFS, WS_CURSOR, WS_ITEMS, WS_ENTRIES, WS_PARTIALS, WS_NODES_A, WS_NODES_B, WS_NTT_TMP,
-       WS_IO_A, WS_IO_B, WS_IO_C, WS_BIG_A, WS_BIG_B, WS_BIG_C, WS_MISC, WS_TOTALS, WS_ORDER, WS_SH_C, WS_SH_SMALL, WS_ROWC, WS_SEL, WS_K3, WS_MULTI, WS_PAIR, WS_COUNT };
+       WS_IO_A, WS_IO_B, WS_IO_C, WS_BIG_A, WS_BIG_B, WS_BIG_C, WS_MISC, WS_TOTALS, WS_ORDER, WS_SH_C, WS_SH_SMALL, WS_ROWC, WS_SEL, WS_K3, WS_MULTI, WS_PAIR, WS_PRIME_TAB, WS_PRIME_SIEVE, WS_PRIME_MR, WS_COUNT };
 
 struct pz_event_pair {
     hipEvent_t a, b;
@@ -84,6 +84,7 @@ struct pz_ctx {
     // pz_dev_arena: one reserved block of device memory this context's allocations (pz_dev_alloc and the library's own buffers)
     // are carved from, so that a caller who builds and drops a proving key per message makes no driver allocation call after start-up
     struct pz_arena* arena = nullptr;
+    bool prime_table_ready = false;   // the sieve primes (the odd primes below 2^16) are in ws[WS_PRIME_TAB] (pz_prime.hip)
     std::recursive_mutex mu;   // one context is serialised internally: entry points may be called from any thread
 };
 

@@ -671,6 +671,44 @@ class Engine:
         self._chk(self.L.pz_bigint_mod_inverse_dev(self.ctx, limbs, count, _ptr(mod), VP(d_xs), VP(d_inv), VP(d_flags)),
                   "pz_bigint_mod_inverse_dev")
 
+    # prime generation for Paillier keys
+    def is_prime(self, limbs: int, cands, bases):
+        """Miller-Rabin on a batch, every candidate its own modulus (pz.h pz_bigint_is_prime): cands (count, limbs) words, bases (rounds,)
+        words >= 2 shared by all candidates.  Returns (flags (count,) uint8: 1 = passed every round, witness (count,) uint32: the first
+        failing round, rounds if none, 0xFFFFFFFF for c < 3 and even c)."""
+        cands, bases = _np(cands).reshape(-1, limbs), _np(bases).reshape(-1)
+        count = cands.shape[0]
+        flags = np.zeros(max(count, 1), dtype=np.uint8)
+        witness = np.zeros(max(count, 1), dtype=np.uint32)
+        self._chk(self.L.pz_bigint_is_prime(self.ctx, limbs, count, _ptr(cands), len(bases), _ptr(bases), VP(flags.ctypes.data),
+                                            VP(witness.ctypes.data)), "pz_bigint_is_prime")
+        return flags, witness
+
+    def is_prime_dev(self, limbs: int, count: int, d_cands: int, bases, d_flags: int, d_witness: int):
+        """the same on DEVICE buffers (addresses), asynchronous on the context's stream (pz.h pz_bigint_is_prime_dev)"""
+        bases = _np(bases).reshape(-1)
+        self._chk(self.L.pz_bigint_is_prime_dev(self.ctx, limbs, count, VP(d_cands), len(bases), _ptr(bases), VP(d_flags), VP(d_witness)),
+                  "pz_bigint_is_prime_dev")
+
+    def prime_sieve(self, limbs: int, start, window: int, safe: bool = False):
+        """mask (window,) uint8 of the trial-division sieve over c_i = start + stride i (pz.h pz_prime_sieve): 1 = no odd prime below 2^16
+        divides c_i (nor, with safe, (c_i - 1) / 2).  stride 2, start odd; with safe stride 4, start = 3 mod 4."""
+        start = _np(start).reshape(limbs)
+        mask = np.zeros(max(window, 1), dtype=np.uint8)
+        self._chk(self.L.pz_prime_sieve(self.ctx, limbs, _ptr(start), window, int(safe), VP(mask.ctypes.data)), "pz_prime_sieve")
+        return mask
+
+    def prime_search(self, limbs: int, start, window: int, safe: bool, bases, want: int = 1):
+        """the `want` smallest offsets i of the window whose c_i = start + stride i survives the sieve and passes every round over
+        `bases` -- with safe, whose (c_i - 1) / 2 passes too (pz.h pz_prime_search).  Returns (offsets (found,) uint32 ascending,
+        survivors: the sieve's count); found may be less than want, or zero."""
+        start, bases = _np(start).reshape(limbs), _np(bases).reshape(-1)
+        offsets = np.zeros(max(want, 1), dtype=np.uint32)
+        found, survivors = C.c_uint32(0), C.c_size_t(0)
+        self._chk(self.L.pz_prime_search(self.ctx, limbs, _ptr(start), window, int(safe), len(bases), _ptr(bases), want,
+                                         VP(offsets.ctypes.data), C.byref(found), C.byref(survivors)), "pz_prime_search")
+        return offsets[: found.value].copy(), int(survivors.value)
+
     @staticmethod
     def shamir_lagrange(trustees: int, ids):
         """the Lagrange exponents of a combination by the members `ids` (pz.h pz_shamir_lagrange; host logic, needs no context): returns

@@ -20,6 +20,8 @@
 //   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
 //   (T trustees holding additive shares of the exponent)      pz::ThresholdKey, pz::deal_shares, PaillierChip::partial_decrypt / combine (15.11)
 //   (any t of T trustees holding Shamir shares of it)          pz::ShamirKey, pz::deal_shamir, PaillierChip::combine_t / mod_inverse (15.12)
+//   (the primes every key above starts from)                   PaillierChip::is_probable_prime / prime_search, pz::generate_prime,
+//                                                                pz::generate_key, pz::primes_are_safe (15.16)
 //   paillier.rs:87-97 paillier_enc_native / _add_native        pz::paillier_enc_native / paillier_add_native
 //   bench.rs:11-31    input structs, :33-117 drivers           pz::PaillierEncryptionInput ... paillier_enc_test ...
 //
@@ -690,6 +692,42 @@ class PaillierChip {  // paillier.rs:11-15
         return R::Ok(out);
     }
 
+    // Miller-Rabin on the device, every value its own modulus (pz_bigint_is_prime): true where x passes every
+    // round over `bases` (1 .. 64 words, each >= 2).  Values of up to 2048 bits; a wider one is PZ_ERR_RANGE.
+    Result<std::vector<bool>> is_probable_prime(Context& ctx, const std::vector<BigUint>& xs, const std::vector<uint64_t>& bases) const {
+        using R = Result<std::vector<bool>>;
+        if (xs.empty() || xs.size() > 65536) return R::Err(PZ_ERR_INVALID, "is_probable_prime: 1 .. 65536 values");
+        size_t L = 1;
+        for (const BigUint& x : xs) L = std::max(L, x.l.size());
+        if (L > 32) return R::Err(PZ_ERR_RANGE, "is_probable_prime: a value is wider than 2048 bits");
+        std::vector<uint64_t> xv;
+        for (const BigUint& x : xs) {
+            std::vector<uint64_t> w = x.to_limbs(L);
+            xv.insert(xv.end(), w.begin(), w.end());
+        }
+        std::vector<uint8_t> flags(xs.size());
+        std::vector<uint32_t> witness(xs.size());
+        int rc = pz_bigint_is_prime(ctx.raw(), (uint32_t)L, xs.size(), xv.data(), (uint32_t)bases.size(), bases.data(), flags.data(), witness.data());
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_bigint_is_prime: ") + pz_strerror(rc));
+        return R::Ok(std::vector<bool>(flags.begin(), flags.end()));
+    }
+    // the `want` smallest offsets i of the window start + stride i (stride 2; 4 with safe) that survive the sieve and every round -- with
+    // safe, whose (c - 1) / 2 passes too (pz_prime_search).  Fewer than want, or none, is Ok.
+    Result<std::vector<uint32_t>> prime_search(Context& ctx, const BigUint& start, size_t limbs, size_t window, bool safe,
+                                               const std::vector<uint64_t>& bases, uint32_t want) const {
+        using R = Result<std::vector<uint32_t>>;
+        if (limbs < 1 || limbs > 32 || start.l.size() > limbs) return R::Err(PZ_ERR_RANGE, "prime_search: the start does not fit 1 .. 32 words");
+        if (want < 1 || want > 64) return R::Err(PZ_ERR_INVALID, "prime_search: want outside 1 .. 64");
+        std::vector<uint64_t> sv = start.to_limbs(limbs);
+        std::vector<uint32_t> offs(want);
+        uint32_t found = 0;
+        int rc = pz_prime_search(ctx.raw(), (uint32_t)limbs, sv.data(), window, safe ? 1 : 0, (uint32_t)bases.size(), bases.data(), want, offs.data(),
+                                 &found, nullptr);
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_prime_search: ") + pz_strerror(rc));
+        offs.resize(found);
+        return R::Ok(offs);
+    }
+
     // c^w mod n^2 = Enc(w m): the weighted tally of one ciphertext
     Result<AssignedBigUint<Fresh>> mul_scalar(Context& ctx, const EncryptionPublicKeyAssigned& pk_enc, const AssignedBigUint<Fresh>& c,
                                               const AssignedWeight& w, unsigned w_bits) const {
@@ -700,8 +738,8 @@ class PaillierChip {  // paillier.rs:11-15
 // The dealer of a T-of-T threshold key (keys.py::deal_shares is the same in Python integers): theta = lambda
 // (lambda^-1 mod n), theta_1 .. theta_{T-1} = rand(n lambda), theta_T = (theta - their sum) mod n lambda; v = w^2 mod n^2 for a drawn w;
 // h_i = v^theta_i and g^theta through PaillierChip::partial_decrypt (the device's chains), mu2 = (2a)^-1 mod n.  rand(k): uniform in
-// [0, k), from the caller's CSPRNG.  safe_primes: the caller's word that (p - 1) / 2 and (q - 1) / 2 are prime (this mirror has no
-// primality test): v is then resampled until v^(N/2) = 1 and v^((N/2)/l) != 1 for l in {p, q, (p - 1) / 2, (q - 1) / 2}, N = n lambda,
+// [0, k), from the caller's CSPRNG.  safe_primes: the caller's word that (p - 1) / 2 and (q - 1) / 2 are prime (pz::primes_are_safe derives it on
+// the device): v is then resampled until v^(N/2) = 1 and v^((N/2)/l) != 1 for l in {p, q, (p - 1) / 2, (q - 1) / 2}, N = n lambda,
 // and the key says v_order_proved.  Refuses p = q, even or tiny primes, gcd(n, phi(n)) != 1, a g whose order n does not divide, and
 // trustees outside 1 .. 256 (PZ_ERR_INVALID).  The dealer forgets p, q, lambda, theta and the shares it hands out.
 inline BigUint paillier_add_native(Context& ctx, const BigUint& n, const BigUint& c1, const BigUint& c2);
@@ -843,6 +881,74 @@ inline Result<DealtShamir> deal_shamir(Context& ctx, const PaillierChip& chip, c
         out.key.hs.push_back(h.val.h);
     }
     return R::Ok(out);
+}
+
+// Prime generation (keys.py::generate_prime / generate_key are the same in Python integers).  rand(k): uniform in
+// [0, k), from the caller's CSPRNG, as in deal_shares.  The search itself runs on the device: there is no host primality test.
+inline std::vector<uint64_t> prime_bases(unsigned rounds, const std::function<BigUint(const BigUint&)>& rand) {
+    std::vector<uint64_t> out;
+    for (unsigned k = 0; k < rounds; ++k) out.push_back(rand(BigUint(1) << 64).to_limbs(1)[0] | 2);
+    return out;
+}
+// offsets one search covers, as keys.default_window: a power of two in 2^10 .. 2^20 around 4 bits (plain) or bits^2 / 8 (safe)
+inline size_t prime_default_window(unsigned bits, bool safe) {
+    const size_t want = safe ? (size_t)bits * bits / 8 : 4 * (size_t)bits;
+    size_t w = 1 << 10;
+    while (w < want && w < ((size_t)1 << 20)) w <<= 1;
+    return w;
+}
+// a probable prime of exactly `bits` (40 .. 2048) bits with its two top bits set; with safe, (p - 1) / 2 is a probable prime too.  Per
+// window a fresh start (top two bits and the residue forced: odd, or 3 mod 4 with safe) and fresh bases rand(2^64) | 2; the loop draws
+// again until a window yields a prime.  window = 0: prime_default_window.
+inline Result<BigUint> generate_prime(Context& ctx, const PaillierChip& chip, unsigned bits, bool safe, unsigned rounds,
+                                      const std::function<BigUint(const BigUint&)>& rand, size_t window = 0) {
+    using R = Result<BigUint>;
+    if (bits < 40 || bits > 2048) return R::Err(PZ_ERR_INVALID, "generate_prime: bits outside 40 .. 2048");
+    if (rounds < 1 || rounds > 64) return R::Err(PZ_ERR_INVALID, "generate_prime: rounds outside 1 .. 64");
+    if (window > ((size_t)1 << 20)) return R::Err(PZ_ERR_INVALID, "generate_prime: window above 2^20");
+    const uint64_t stride = safe ? 4 : 2, residue = safe ? 3 : 1;
+    if (window == 0) window = prime_default_window(bits, safe);
+    const size_t limbs = (bits + 63) / 64;
+    const BigUint top = BigUint(3) << (bits - 2), bound = BigUint(1) << bits;
+    for (;;) {
+        std::vector<uint64_t> w = (rand(BigUint(1) << (bits - 2)) + top).to_limbs(limbs);
+        w[0] = (w[0] & ~(stride - 1)) | residue;
+        const BigUint start = BigUint::from_limbs(w.data(), limbs);
+        if (!(start + BigUint(stride * (window - 1)) < bound)) continue;   // the window would leave the bit length: draw again
+        auto offs = chip.prime_search(ctx, start, limbs, window, safe, prime_bases(rounds, rand), 1);
+        if (!offs.ok) return R::Err(offs.err.status, offs.err.msg);
+        if (!offs.val.empty()) return R::Ok(start + BigUint(stride * offs.val[0]));
+    }
+}
+// (p, q) for deal_shares / deal_shamir: p != q of bits / 2 and bits - bits / 2 bits, n = p q of exactly `bits` bits, gcd(n, phi(n)) = 1;
+// with safe both are safe primes (and (p - 1) / 2 != (q - 1) / 2 follows), which is what the dealers' safe_primes argument asserts
+struct PrimePair {
+    BigUint p, q;
+};
+inline Result<PrimePair> generate_key(Context& ctx, const PaillierChip& chip, unsigned bits, bool safe, unsigned rounds,
+                                      const std::function<BigUint(const BigUint&)>& rand, size_t window = 0) {
+    using R = Result<PrimePair>;
+    const BigUint one(1);
+    for (;;) {
+        auto p = generate_prime(ctx, chip, bits / 2, safe, rounds, rand, window);
+        if (!p.ok) return R::Err(p.err.status, p.err.msg);
+        auto q = generate_prime(ctx, chip, bits - bits / 2, safe, rounds, rand, window);
+        if (!q.ok) return R::Err(q.err.status, q.err.msg);
+        const BigUint n = p.val * q.val;
+        if (p.val != q.val && n.bits() == bits && BigUint::gcd(n, (p.val - one) * (q.val - one)) == one) return R::Ok(PrimePair{p.val, q.val});
+    }
+}
+// what a caller of deal_shares / deal_shamir passes as safe_primes: p, q, (p - 1) / 2 and (q - 1) / 2 all pass `rounds` rounds on the
+// device over fresh bases, and p != q
+inline Result<bool> primes_are_safe(Context& ctx, const PaillierChip& chip, const BigUint& p, const BigUint& q, unsigned rounds,
+                                    const std::function<BigUint(const BigUint&)>& rand) {
+    using R = Result<bool>;
+    if (rounds < 1 || rounds > 64) return R::Err(PZ_ERR_INVALID, "primes_are_safe: rounds outside 1 .. 64");
+    if (p < BigUint(5) || q < BigUint(5) || p == q) return R::Ok(false);
+    const BigUint one(1), two(2);
+    auto res = chip.is_probable_prime(ctx, {p, q, (p - one) / two, (q - one) / two}, prime_bases(rounds, rand));
+    if (!res.ok) return R::Err(res.err.status, res.err.msg);
+    return R::Ok(res.val[0] && res.val[1] && res.val[2] && res.val[3]);
 }
 
 // paillier.rs:87-92: (g^m * r^n) mod n^2 -- one pz_paillier_encrypt call without a trace

@@ -2,7 +2,8 @@
 threshold key (deal_shares): additive shares of the decryption exponent for Engine.paillier_partial and the
 public ThresholdKey for Engine.paillier_combine and the verifier of circuit kind 'partial'; and of a t-of-T key (deal_shamir,
 lagrange_exponents; section 15.12): Shamir shares for the same Engine.paillier_partial and the public ShamirKey for
-Engine.paillier_combine_t.
+Engine.paillier_combine_t; and the generator of the primes all of them start from (is_probable_prime, generate_prime, generate_key;
+section 15.16), which runs on the device: Engine.is_prime and Engine.prime_search.
 
 The library derives mu and g^-1 on the device and validates the key there; the one value it does not derive is d = n^-1 mod lambda,
 the exponent that recovers an encryption's randomness: it is the caller's, and this helper computes it."""
@@ -52,7 +53,8 @@ class ThresholdKey:
 
 
 def _is_prime(x: int) -> bool:
-    """Miller-Rabin over the first twelve primes (deterministic below 3.3e24) and 24 more fixed bases above"""
+    """Miller-Rabin over the first twelve primes (deterministic below 318665857834031151167461, the least strong pseudoprime to all
+    twelve) and 24 more fixed bases from there on"""
     if x < 2:
         return False
     small = (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37)
@@ -62,7 +64,7 @@ def _is_prime(x: int) -> bool:
     d, r = x - 1, 0
     while d % 2 == 0:
         d, r = d // 2, r + 1
-    bases = small if x < 3317044064679887385961981 else small + tuple(range(41, 137, 4))
+    bases = small if x < 318665857834031151167461 else small + tuple(range(41, 137, 4))
     for a in bases:
         y = pow(a, d, x)
         if y in (1, x - 1):
@@ -188,3 +190,78 @@ def deal_shamir(p: int, q: int, trustees: int, threshold: int, g: Optional[int] 
     key = ShamirKey(n=n, g=g, v=v, hs=tuple(pow(v, s, n2) for s in shares), mu2=pow(2 * a * math.factorial(trustees), -1, n),
                     trustees=trustees, threshold=threshold, v_order_proved=safe)
     return key, shares
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# prime generation: the search runs on the device -- an engine is required, there is no CPU fallback
+# ---------------------------------------------------------------------------------------------------------------------------------
+MAX_PRIME_BITS = 2048        # 32 words: what pz_bigint_is_prime / pz_prime_search take
+MIN_PRIME_BITS = 40          # a window's start must exceed 2^32, with room for the window below 2^bits
+MAX_WINDOW = 1 << 20
+
+
+def _words(x: int, limbs: int) -> List[int]:
+    return [(x >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(limbs)]
+
+
+def _bases(rounds: int, rand: Callable[[int], int]) -> List[int]:
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= 64:
+        raise ValueError(f"rounds must be 1 .. 64, not {rounds!r}")
+    return [rand(64) | 2 for _ in range(rounds)]
+
+
+def is_probable_prime(engine, xs, rounds: int = 32, rand: Callable[[int], int] = secrets.randbits) -> List[bool]:
+    """Miller-Rabin on the device for every integer of xs (0 <= x < 2^2048) over `rounds` bases rand(64) | 2 drawn for this call
+    (rand(k): k random bits, by default secrets.randbits): True where x passes every round.  One Engine.is_prime call."""
+    xs = list(xs)
+    if not xs or any(isinstance(x, bool) or not isinstance(x, int) or x < 0 or x.bit_length() > MAX_PRIME_BITS for x in xs):
+        raise ValueError(f"xs: a non-empty list of integers in [0, 2^{MAX_PRIME_BITS})")
+    limbs = max(1, max((x.bit_length() + 63) // 64 for x in xs))
+    flags, _ = engine.is_prime(limbs, [_words(x, limbs) for x in xs], _bases(rounds, rand))
+    return [bool(f) for f in flags]
+
+
+def default_window(bits: int, safe: bool) -> int:
+    """offsets one search covers: about eight expected gaps between primes of `bits` bits at stride 2 (a gap is ~0.35 bits offsets),
+    about two and a half expected gaps between safe primes at stride 4 (~0.05 bits^2 offsets), as powers of two within 2^10 .. 2^20"""
+    want = bits * bits // 8 if safe else 4 * bits
+    return min(MAX_WINDOW, max(1 << 10, 1 << (want - 1).bit_length()))
+
+
+def generate_prime(engine, bits: int, safe: bool = False, rounds: int = 32, rand: Callable[[int], int] = secrets.randbits,
+                   window: Optional[int] = None) -> int:
+    """A probable prime of exactly `bits` bits with its two top bits set (so that the product of two has exactly the sum of their
+    bits), found on the device; with safe, (p - 1) / 2 is a probable prime too.  Per window a fresh start rand(bits) with the top two
+    bits and the residue forced (odd; 3 mod 4 with safe) and fresh bases; Engine.prime_search returns the smallest offset that
+    survives the sieve and every round, and the loop draws again until a window yields one.  window defaults to default_window."""
+    if isinstance(bits, bool) or not isinstance(bits, int) or not MIN_PRIME_BITS <= bits <= MAX_PRIME_BITS:
+        raise ValueError(f"bits must be {MIN_PRIME_BITS} .. {MAX_PRIME_BITS}, not {bits!r}")
+    stride, residue = (4, 3) if safe else (2, 1)
+    if window is None:
+        window = default_window(bits, safe)
+    if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= MAX_WINDOW:
+        raise ValueError(f"window must be 1 .. {MAX_WINDOW}, not {window!r}")
+    limbs = (bits + 63) // 64
+    while True:
+        start = (rand(bits) & ((1 << bits) - 1)) | (3 << (bits - 2))
+        start = start - start % stride + residue
+        if start + stride * (window - 1) >> bits:
+            continue                                        # the window would leave the bit length: draw again
+        offsets, _ = engine.prime_search(limbs, _words(start, limbs), window, safe, _bases(rounds, rand), 1)
+        if len(offsets):
+            return start + stride * int(offsets[0])
+
+
+def generate_key(engine, bits: int, safe: bool = False, rounds: int = 32, rand: Callable[[int], int] = secrets.randbits,
+                 window: Optional[int] = None) -> Tuple[int, int]:
+    """(p, q) for secret_from_primes, deal_shares and deal_shamir: probable primes of bits // 2 and bits - bits // 2 bits from
+    generate_prime with p != q, n = p q of exactly `bits` bits and gcd(n, phi(n)) = 1; with safe both are safe primes and
+    (p - 1) / 2 != (q - 1) / 2, which is what gives the dealers' keys v_order_proved = True."""
+    if isinstance(bits, bool) or not isinstance(bits, int) or bits < 2 * MIN_PRIME_BITS:
+        raise ValueError(f"bits must be {2 * MIN_PRIME_BITS} .. {2 * MAX_PRIME_BITS}, not {bits!r}")
+    while True:
+        p = generate_prime(engine, bits // 2, safe, rounds, rand, window)
+        q = generate_prime(engine, bits - bits // 2, safe, rounds, rand, window)
+        n = p * q
+        if p != q and n.bit_length() == bits and math.gcd(n, (p - 1) * (q - 1)) == 1:
+            return p, q

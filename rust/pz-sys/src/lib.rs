@@ -140,6 +140,16 @@ extern "C" {
                                      d_flags_out: *mut u8) -> c_int;
     pub fn pz_shamir_lagrange(trustees: u32, members: usize, ids: *const u32, exps_out: *mut u64, exp_words: u32, neg_out: *mut u8,
                               words_needed: *mut u32) -> c_int;
+    // prime generation for Paillier keys: Miller-Rabin over shared bases with every candidate its own modulus
+    // (witness_out[j]: the first failing round, or rounds; 0xFFFFFFFF for c < 3 and even c), the trial-division sieve over the window
+    // start + stride i (stride 2, or 4 with safe = 1), and the search for the `want` smallest offsets that pass both
+    pub fn pz_bigint_is_prime(ctx: *mut pz_ctx, limbs: u32, count: usize, cands: *const u64, rounds: u32, bases: *const u64,
+                              flags_out: *mut u8, witness_out: *mut u32) -> c_int;
+    pub fn pz_bigint_is_prime_dev(ctx: *mut pz_ctx, limbs: u32, count: usize, d_cands: *const u64, rounds: u32, bases: *const u64,
+                                  d_flags_out: *mut u8, d_witness_out: *mut u32) -> c_int;
+    pub fn pz_prime_sieve(ctx: *mut pz_ctx, limbs: u32, start: *const u64, window: usize, safe: u32, mask_out: *mut u8) -> c_int;
+    pub fn pz_prime_search(ctx: *mut pz_ctx, limbs: u32, start: *const u64, window: usize, safe: u32, rounds: u32, bases: *const u64,
+                           want: u32, offsets_out: *mut u32, found_out: *mut u32, survivors_out: *mut usize) -> c_int;
     // decryption with randomness recovery (the key holder): a validated key handle, then m_i and r_i with c_i = g^m_i r_i^n mod n^2.
     // flags_out[i] bit 0: c_i is no unit (m_i = r_i = 0); the _dev form reports a c_i >= n^2 as bit 1 instead of PZ_ERR_RANGE
     pub fn pz_paillier_sk_create(ctx: *mut pz_ctx, limbs_n: u32, n: *const u64, g: *const u64, lambda: *const u64, d: *const u64,
