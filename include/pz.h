@@ -351,6 +351,40 @@ int pz_paillier_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t
                            const uint64_t* ms, const uint64_t* rs, uint64_t* d_steps_out, size_t steps_cap, uint32_t* n_steps_r,
                            uint64_t* c_out);
 
+/* The mix: a verifiable shuffle's values.  A mixer takes c_1 .. c_K under the key n and publishes
+ * c'_i = c_perm(i) * r_i^n mod n^2: the same plaintexts, re-randomised, in an order nobody else can follow.  K = count is a power of two
+ * in 1 .. 1024; n: limbs_n words; cts = count x 2*limbs_n words; rs = count x limbs_n words; mixed_out = count x 2*limbs_n words (HOST).
+ * The permutation arrives as the switch bits of a Benes network over the K positions (pz_mix_route makes them from perm):
+ *   d = log2 K, 2d - 1 layers l = 0 .. 2d - 2 (none for K = 1); layer l acts on bit beta(l) = l for l < d and 2d - 2 - l above;
+ *   switch s of a layer is the s-th position j, ascending, with bit beta clear, its partner j' = j | 2^beta; with bit b the switch
+ *   leaves out[j] = b ? in[j'] : in[j] and out[j'] = b ? in[j] : in[j'].  Values stay in place: no wire shuffle between layers.
+ *   bits: (2d - 1) * K / 2 bytes, layer-major, each 0 or 1 (may be NULL for K = 1).  ANY bits give SOME permutation.
+ * routes_out (may be NULL): every layer's outputs, routes[l][position][2*limbs_n], (2d - 1) * K * 2*limbs_n words.  steps_out
+ * (steps_cap >= count * (nr + 1) records, else PZ_ERR_CAPACITY; may be NULL: the values only): records a|b|q|r of 2*limbs_n words per
+ * field, output-major -- output i's nr = bits(n) + popcount(n) records of pow_mod_fixed_exp(r_i, n) (per bit of n, LSB first, the step
+ * (cur, cur), then on a set bit the step (acc, cur): pz_paillier_ballot's r-chain), then the step (d_i, rn_i), d_i the last layer's
+ * value at position i (c_1 for K = 1), whose remainder is c'_i.
+ * Refusals, in this order: a null pointer, limbs_n = 0, a count that is no power of two in 1 .. 1024: PZ_ERR_INVALID; 2*limbs_n > 128:
+ * PZ_ERR_UNSUPPORTED; a short steps_cap: PZ_ERR_CAPACITY; a bit byte above 1: PZ_ERR_MESSAGE_RANGE; n = 0: PZ_ERR_ZERO_MODULUS -- all
+ * before any launch.  A c_j >= n^2: PZ_ERR_RANGE (found by the kernel).  No output buffer is written on a refusal.  r_i is not compared
+ * with n and r_i = 0 is not refused (c'_i = 0 then: verifier.public_inputs("mix") refuses such a list).
+ * One launch per layer over its K / 2 switches, then ONE launch of K teams for the r^n chains and products; no workgroup waits on
+ * another; n^2 and its Barrett constants are formed once.  The bits, the r_i and the route layers are SECRET: a switch reads both
+ * inputs and writes both outputs under a lane-wise mask made from its bit, no address or branch depends on a bit or on r_i (the
+ * value-dependent trip count of mul_mod's Barrett correction remains, as in every K3 entry point), and the staged bits and r_i (host
+ * form: the staged routes and records too) in the context's workspace are overwritten before the call returns.
+ * _dev: d_routes_out and d_steps_out are DEVICE buffers (either may be NULL; the kernels have written them by the time a c_j >= n^2
+ * is reported); everything else as above.
+ *   pz_mix_route   host logic, no context: the switch bits of perm (perm[i] = the index of the input that output position i
+ *       receives), by the looping algorithm; bits_out: (2d - 1) * K / 2 bytes (may be NULL for K = 1).  A count that is no power of
+ *       two in 1 .. 1024, a perm that is no permutation of 0 .. K - 1, a null pointer: PZ_ERR_INVALID, bits_out untouched.  Its working
+ *       memory is overwritten before it returns.  (PZ_ABI_VERSION stays 7: additions.) */
+int pz_paillier_mix(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts, const uint8_t* bits,
+                    const uint64_t* rs, uint64_t* routes_out, uint64_t* steps_out, size_t steps_cap, uint64_t* mixed_out);
+int pz_paillier_mix_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts, const uint8_t* bits,
+                        const uint64_t* rs, uint64_t* d_routes_out, uint64_t* d_steps_out, size_t steps_cap, uint64_t* mixed_out);
+int pz_mix_route(size_t count, const uint32_t* perm, uint8_t* bits_out);
+
 /* Decryption with randomness recovery, for the key holder.  The secret key is a handle: n, g, lambda and d = n^-1 mod lambda
  * (HOST words, limbs_n each; d is the caller's -- paillier_halo2_amd/keys.py::secret_from_primes computes it).
  *   pz_paillier_sk_create  forms n^2 and the Barrett constants of n^2 and of n once, derives on the device x = L(g^lambda mod n^2),
@@ -612,6 +646,41 @@ int pz_partial_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits
                                const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride);
 int pz_partial_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint64_t* cells_out, size_t capacity,
                             size_t* n_public);
+
+/* Circuit kind 8, "mix" (DESIGN.md section 15.17): the list c'_1 .. c'_K is a re-randomised permutation of the list c_1 .. c_K under the
+ * key n -- there are a permutation pi and r_i with c'_i = c_pi(i) r_i^n mod n^2 for every i.  K = count is a power of two in 1 .. 1024.
+ * Its shape is K and the records of ONE r^n chain (n_steps_r = bits(n) + popcount(n) >= 1); the by-kind entry points refuse kind 8 and
+ * these take the two numbers (anything out of range: PZ_ERR_INVALID).  The stream, in emission order: assign_integer(n);
+ * assign_integer(c_j) at full width (2 limbs_n limbs) for j = 1 .. K; assign_integer(r_i) for i = 1 .. K; square + refresh of n, once;
+ * load_zero; the Benes network of pz_paillier_mix layer by layer and switch by switch -- assert_bit of the switch's bit ([0, b, b, b]),
+ * then per limb t select(in[j'][t], in[j][t], b) and select(in[j][t], in[j'][t], b), 8 cells each with gate windows at 0 and 4: 4 + 16
+ * * 2 limbs_n cells a switch --; per output [1, 0], the n_steps_r mul_mod blocks of pow_mod_fixed_exp(r_i extended by the load_zero
+ * cell, n) and mul_mod(d_i, rn_i); then per output assign_integer(c'_i) at full width and assert_equal_fresh.  The selects' sel cells
+ * are tied to their switch's bit cell, their operands to the limb cells they read (layer 0: the assigned c_j; above: the previous
+ * layer's outputs), the final block's operands to the last layer's outputs and the chain's result, each assert_equal_fresh's bit to
+ * the constant 1: whatever the bits, a network of conditional swaps under bits in {0, 1} is SOME permutation.  The circuit neither
+ * compares r_i with n nor refuses r_i = 0, and K is a power of two (DESIGN.md section 15.17 lists what is absent).
+ *   pz_mix_cells         the stream's advice / lookup cell counts (host logic).
+ *   pz_mix_expand_dev    the values.  inputs (HOST): n (ceil(limbs_n*limb_bits/64) words) | c_1 .. c_K (ceil(2*limbs_n*limb_bits/64)
+ *       words each) | r_1 .. r_K (as n) | res_1 .. res_K (as the c_j).  bits (HOST): the switch bytes as pz_paillier_mix took them (a
+ *       byte above 1: PZ_ERR_MESSAGE_RANGE; may be NULL for K = 1).  d_routes, d_steps (device): the route layers and the K (n_steps_r +
+ *       1) records of pz_paillier_mix_dev AS THEY ARE, fields of 2*ceil(limbs_n*limb_bits/64) words (where that differs from
+ *       ceil(2*limbs_n*limb_bits/64) the records are repacked on the device first; d_routes may be NULL for K = 1).  d_modulus: n^2
+ *       (device).  rows / col_stride as pz_circuit_expand_dev.
+ *   pz_mix_expand_cols_dev  the same with the advice cells in break-point columns, as pz_circuit_expand_cols_dev.
+ *   pz_mix_public_cells  the stream indices of the exposed cells in statement order: n | c_1 | .. | c_K | c'_1 | .. | c'_K (the limb cells
+ *       of the assign_integer of each): n_public = limbs_n + 2 K 2 limbs_n. */
+int pz_mix_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r, size_t* advice_cells,
+                 size_t* lookup_cells);
+int pz_mix_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
+                      const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
+                      const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride);
+int pz_mix_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
+                           const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
+                           const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts,
+                           size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride);
+int pz_mix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r, uint64_t* cells_out,
+                        size_t capacity, size_t* n_public);
 
 /* The same stream with the ADVICE cells in halo2-lib's break-point column layout -- what the dependency's assign_with_constraints
  * [D] does with the Context's cell list when it fills the basic-gate columns (reached from bench.rs:161-171 through keygen /
@@ -1108,6 +1177,12 @@ int pz_shplonk_free(pz_ctx* ctx, pz_shplonk* state);
  * assign_integer(c_j)'s, chain j's first sq to that block's remainder, each chain's last select outputs to the assert_equal_fresh against
  * h / u_j, each assert_equal_fresh's bit to the constant 1.  An ordinary pz_structure (n_steps_g = the 2 E records of ONE chain,
  * n_steps_r = 0); pz_structure_expose works on it (statement: pz_partial_public_cells).
+ * pz_circuit_structure_mix_dev: the structure of the mix (kind 8, pz_mix_cells) of `count` = 2^d ciphertexts (1 .. 1024) under the key
+ * whose modulus is exp_r (ceil(limbs_n * limb_bits / 64) words: its bits shape every r^n chain): ONE key serves every mixer of an
+ * election.  Every select's sel cell is tied to its switch's bit cell, its operands to the limb cells they read, every r-chain's base
+ * to assign_integer(r_i)'s limbs extended by the load_zero cell, the final block's operands to the last layer's outputs and the
+ * chain's result, each assert_equal_fresh's bit to the constant 1.  An ordinary pz_structure (n_steps_g = 0, n_steps_r = the records
+ * of ONE r^n chain); pz_structure_expose works on it (statement: pz_mix_public_cells).
  * ------------------------------------------------------------------------------------------- */
 typedef struct pz_structure pz_structure;
 int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
@@ -1119,6 +1194,8 @@ int pz_circuit_structure_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb
                                     uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_circuit_structure_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                     uint32_t m_bits, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
+int pz_circuit_structure_mix_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                 const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_circuit_structure_partial_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                      size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_structure_info(const pz_structure* st, size_t* n_adv, size_t* n_adv_filled, size_t* n_lk, size_t* max_rows, size_t* n_constants,

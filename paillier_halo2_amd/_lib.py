@@ -74,6 +74,9 @@ SIGNATURES = {
     "pz_paillier_wtally_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_ballot": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
     "pz_paillier_ballot_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
+    "pz_paillier_mix": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
+    "pz_paillier_mix_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
+    "pz_mix_route": (C.c_int, [C.c_size_t, VP, VP]),
     "pz_paillier_partial": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
     "pz_paillier_partial_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
     "pz_paillier_combine": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP]),
@@ -207,6 +210,14 @@ SIGNATURES = {
     "pz_partial_public_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "pz_circuit_structure_wtally_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32,
                                                  C.POINTER(VP)]),
+    "pz_circuit_structure_mix_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, VP, C.c_size_t, C.c_uint32,
+                                               C.POINTER(VP)]),
+    "pz_mix_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "pz_mix_expand_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP, VP, VP, C.c_size_t,
+                                    C.c_size_t]),
+    "pz_mix_expand_cols_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP, VP, VP, VP,
+                                         C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "pz_mix_public_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "pz_structure_info": (C.c_int, [VP] + [C.POINTER(C.c_size_t)] * 9),
     "pz_structure_arrays": (C.c_int, [VP] + [C.POINTER(VP)] * 6),
     "pz_structure_free": (C.c_int, [VP]),

@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import layout
+from . import layout, mix
 from .prover import CircuitStructure
 
 
@@ -303,7 +303,7 @@ class StructureArrays:
     # n | g | c (encrypt, encrypt_uniform), n | g | m | c (decrypt), n | g | c1 | c2 | c (add), n | c_1 | .. | c_B | C (tally) or n | c_1 | .. | c_B | w_1 | .. |
     # w_B | C (wtally: a weight is ONE cell) -- pz_circuit_public_cells gives the same list -- or n | g | c_1 | .. | c_K | S (ballot: S is
     # the sum's last cell, present for K >= 2; pz_ballot_public_cells) -- or n | v | h | c_1 | u_1 | .. | c_K | u_K (partial;
-    # pz_partial_public_cells)
+    # pz_partial_public_cells) -- or n | c_1 | .. | c_K | c'_1 | .. | c'_K (mix; pz_mix_public_cells)
     public_cells: Optional[np.ndarray] = None
 
 
@@ -324,7 +324,10 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     count = K ciphertexts under one key, each message ONE witness cell decomposed into m_bits in-circuit bits (the uniform circuit's
     block), exp_r = the modulus n (its bits shape every r^n chain), for K >= 2 the sum of the messages -- the shape is K, m_bits and n;
     kind 'partial' (circuit kind 7): count = K ciphertexts one trustee opens under ONE share theta, an
-    assign_integer of 2 Ln limbs every chain decomposes (kind 2's pow_mod walk over all its limbs) -- the shape is K and the key size.
+    assign_integer of 2 Ln limbs every chain decomposes (kind 2's pow_mod walk over all its limbs) -- the shape is K and the key size;
+    kind 'mix' (circuit kind 8): count = K = 2^d ciphertexts go through the Benes network of mix.py (per switch
+    assert_bit of a fresh bit cell, then per limb the two selects under it) and leave as d_i r_i^n mod n^2, exp_r = the modulus n (its
+    bits shape every r^n chain) -- the shape is K and n.
     device: None -> numpy arrays; a torch device ("cuda") -> the template is tiled THERE and `src` / `lookup_src` are tensors on it (at
     config c2 the tiled arrays are 3.2 GB: 0.9 s of host numpy against a few ms; `columns` takes either)."""
     dev = None
@@ -359,12 +362,17 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             constants.append(v)
         return const_id[v]
 
-    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial"):
+    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial", "mix"):
         raise ValueError(f"unknown circuit kind {kind!r}")
     # 'decrypt' (circuit kind 5) is the uniform-shape circuit cell for cell: the exposed list alone differs
     statement, kind = kind, ("encrypt_uniform" if kind == "decrypt" else kind)
-    if (kind in ("tally", "wtally", "ballot", "partial")) != (count is not None):
-        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot' and 'partial', which need it")
+    if (kind in ("tally", "wtally", "ballot", "partial", "mix")) != (count is not None):
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial' and 'mix', which need it")
+    if kind == "mix":
+        if not mix.is_count(count):
+            raise ValueError(f"a mix takes count = 1, 2, 4 .. {mix.MIX_MAX} ciphertexts, not {count}")
+        if exp_r < 1:
+            raise ValueError("a mix's structure needs exp_r = the modulus n")
     if kind == "partial" and not 1 <= count <= layout.PARTIAL_MAX:
         raise ValueError(f"a trustee opens count = 1 .. {layout.PARTIAL_MAX} ciphertexts in one proof, not {count}")
     if (kind == "ballot") != (m_bits is not None):
@@ -395,6 +403,9 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         v_c = _assign(w, L, limb_bits, lb)
         th_c = _assign(w, L, limb_bits, lb)
         ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
+    elif kind == "mix":
+        ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
+        rs_c = [_assign(w, Ln, limb_bits, lb) for _ in range(count)]
     elif kind == "ballot":
         g_c = _assign(w, Ln, limb_bits, lb)
         ms_c = [w.put() for _ in range(count)]                                 # load_witness(m_i): one cell each, no gate
@@ -573,6 +584,46 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             off, u_cells = theta_chain(off, s_cells[0])
             c_cells.append(u_cells)
         n_steps[0] = 2 * L * limb_bits
+    elif kind == "mix":
+        # the network, layer by layer and switch by switch: assert_bit of the switch's own bit cell ([0, b, b, b]: the first b is the
+        # bit's home, the other two copy it), then per limb select(in[j'], in[j], b) and select(in[j], in[j'], b) -- 8 cells each
+        # [d | 1 | y | x | y | b | d | out], windows at 0 and 4.  The operands are the previous layer's out cells (layer 0: the
+        # assigned ciphertexts' limbs); values stay in place
+        wn = _Walk(off)
+
+        def select(x, y, s):
+            c_d = wn.put()
+            wn.gate(c_d)
+            wn.putc(1); wn.put(y); wn.put(x)
+            g_ = wn.put(y)
+            wn.gate(g_)
+            wn.put(s); wn.put(c_d)
+            return wn.put()
+
+        cur_c = [list(c) for c in ct_c]
+        for beta in mix.layer_bits(count):
+            nxt_c = [None] * count
+            for j in range(count):
+                if j >> beta & 1:
+                    continue
+                jp = j | (1 << beta)
+                g_ = wn.putc(0)
+                wn.gate(g_)
+                b_c = wn.put()
+                wn.put(b_c); wn.put(b_c)
+                lo_c, hi_c = [], []
+                for t_ in range(L):
+                    lo_c.append(select(cur_c[jp][t_], cur_c[j][t_], b_c))
+                    hi_c.append(select(cur_c[j][t_], cur_c[jp][t_], b_c))
+                nxt_c[j], nxt_c[jp] = lo_c, hi_c
+            cur_c = nxt_c
+        off = flush(wn)
+        # per output: pow_mod_fixed_exp(r_i_ext, n) and the block mul_mod(d_i, rn_i)
+        c_cells = []
+        for i in range(count):
+            off, rn, n_steps[1] = fixed_chain(off, ext_l(rs_c[i]), exp_r)
+            off, rfin = blocks(off, np.asarray(cur_c[i], dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
+            c_cells.append(rfin[0].tolist())
     elif kind == "ballot":
         # per ciphertext: pow_mod(g_ext, m_i) over m_bits in-circuit bits (the weighted tally's chain on the base g, extended by the
         # load_zero cell), pow_mod_fixed_exp(r_i_ext, n), the final mul_mod; then per ciphertext assign res_i + assert_equal_fresh
@@ -659,7 +710,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         n_steps[0] = nb
     else:
         off, rfin = blocks(off, np.asarray(ext_l(x_c), dtype=np.int64)[None, :], np.asarray(ext_l(y_c), dtype=np.int64)[None, :])
-    roots = c_cells if kind in ("ballot", "partial") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
+    roots = c_cells if kind in ("ballot", "partial", "mix") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
     ws = _Walk(off)
     res_all, eq_cells = [], []
     for c_limbs in roots:
@@ -686,6 +737,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         exposed = list(n_c) + list(v_c) + res_all[:L]
         for j in range(count):
             exposed += list(ct_c[j]) + res_all[(j + 1) * L:(j + 2) * L]
+    elif kind == "mix":
+        exposed = list(n_c) + [c for ct in ct_c for c in ct] + res_all
     elif kind == "ballot":
         exposed = list(n_c) + list(g_c) + res_all + ([sum_c] if sum_c is not None else [])
     elif kind in ("tally", "wtally"):

@@ -1105,6 +1105,85 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_ballot_enc(co
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
+// ---- a mixer's shuffle (pz_paillier_mix): one layer of the Benes network over `count` integers of L limbs that stay
+// in place.  One launch per layer, ordered by the stream alone; one wave per switch.  Switch s of a layer on bit beta is the s-th
+// position j with that bit clear, its partner j | 2^beta: both follow from s and beta.  The switch's bit is SECRET (the bits are the
+// permutation): the wave reads BOTH inputs and writes BOTH outputs, each output chosen limb-wise under ld_select's mask -- no address and
+// no branch depends on the bit, whose own address is the switch's index.  in / out: count x L words; a layer never runs in place.
+template <int E> __global__ __launch_bounds__(64) void k_mix_route(const u64* __restrict__ in, u64* __restrict__ out,
+                                                                    const uint8_t* __restrict__ layer_bits, unsigned beta, unsigned half,
+                                                                    unsigned L) {
+    const unsigned s = blockIdx.x;
+    if (s >= half) return;
+    const unsigned low = s & ((1u << beta) - 1u);
+    const size_t j = ((size_t)(s >> beta) << (beta + 1)) | low, jp = j | ((size_t)1 << beta);
+    const LD<E> a = ld_load<E>(in + j * L, L), b = ld_load<E>(in + jp * L, L);
+    const u64 bit = layer_bits[s];
+    LD<E> lo = a, hi = b;
+    ld_select(lo, b, bit);
+    ld_select(hi, a, bit);
+    ld_store(out + j * L, lo, L);
+    ld_store(out + jp * L, hi, L);
+}
+
+// ---- a mixer's re-randomisation (pz_paillier_mix): c'_i = d_i r_i^n mod n^2, d_i the network's output at position i.  k_ballot_enc
+// without its g-chain: one team per output runs r_i^n by pow_mod_fixed_exp over n's PUBLIC bits (the square of every bit, then the
+// product where the bit is set) and the product with d_i, all `count` outputs in one launch, no team waits on another.  r_i and d_i are
+// SECRET (d_i's position in the input list is the permutation); d_i's address follows the team's index alone.  The Barrett constants
+// come from k_tally_setup, once.  A d_i >= n^2 (an input >= n^2: every input reaches one output) is ST_RANGE.
+// recs (may be null: the values only): output i at records i * per .. + per, per = nr + 1: the chain's, then (d_i, rn_i, q, c'_i).  The
+// record index is held against per before every store; a disagreement is ST_INTERNAL, never a write past the output's own records.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_mix_rerand(const u64* __restrict__ mod, const u64* __restrict__ n,
+                                                                                 const u64* __restrict__ routed, const u64* __restrict__ rs,
+                                                                                 unsigned n_bits, unsigned per, unsigned count,
+                                                                                 u64* __restrict__ recs, u64* __restrict__ c_out, unsigned Ln,
+                                                                                 u32* __restrict__ status) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (*block_ok<E>(mod) == 0) return;   // zero modulus (the same word for every workgroup)
+    if (blockIdx.x >= count) return;
+    const unsigned wave = threadIdx.x >> 6, L = 2 * Ln;
+    TeamCtx<E> T;
+    team_init(T, s_team);
+    TeamMul<E> tmul{&T};
+    BarrettCtx<E> B;
+    barrett_from_block(B, mod, L, s_scratch[wave]);
+    const size_t entry = blockIdx.x;
+    const bool writer = wave == 0 && recs != nullptr;   // the four waves of the team hold the same values: one of them writes
+    u64* const base = writer ? recs + entry * per * 4 * (size_t)L : nullptr;
+    unsigned idx = 0, st = ST_OK;
+    auto step = [&](LD<E>& r, const LD<E>& a, const LD<E>& b) {   // one recorded mul_mod
+        LD<E> q;
+        st |= mul_mod(B, q, r, a, b, tmul);
+        if (writer && idx < per) rec_store(base + (size_t)idx * 4 * L, a, b, q, r, L);
+        ++idx;
+    };
+    const LD<E> d = ld_load<E>(routed + entry * L, L);
+    {
+        LD<E> t;
+        if (!ld_sub(t, d, ld_load<E>(block_modulus<E>(mod), C))) st |= ST_RANGE;   // an input >= n^2
+    }
+    LD<E> rn = ld_small<E>(1);
+    {
+        LD<E> sq = ld_load<E>(rs + entry * Ln, Ln);
+        for (unsigned i = 0; i < n_bits; ++i) {
+            const LD<E> cur = sq;
+            step(sq, cur, cur);
+            if ((n[i >> 6] >> (i & 63)) & 1) {   // (n is the public key)
+                LD<E> r;
+                step(r, rn, cur);
+                rn = r;
+            }
+        }
+    }
+    LD<E> c;
+    step(c, d, rn);
+    if (idx != per) st |= ST_INTERNAL;
+    if (wave == 0) ld_store(c_out + entry * L, c, L);
+    if (st && lane_id() == 0) atomicOr(status, st);
+}
+
 // ---- a trustee's partial decryptions (pz_paillier_partial): h = v^theta and u_j = (c_j^2)^theta mod n^2 for K ciphertexts under ONE
 // secret share theta of e_bits bits.  K + 1 teams in one launch: team 0 runs pow_mod(v, theta), team j >= 1 first squares c_j itself
 // (record j - 1) and then runs pow_mod(s_j, theta) -- pow_mod_uniform: (acc, sq) then (sq, sq) for EVERY bit, the trailing square
@@ -1950,6 +2029,119 @@ extern "C" int pz_paillier_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t coun
                                       const uint64_t* ms, const uint64_t* rs, uint64_t* d_steps_out, size_t steps_cap, uint32_t* n_steps_r,
                                       uint64_t* c_out) {
     return ballot_impl(ctx, limbs_n, count, m_bits, n, g, ms, rs, d_steps_out, 1, steps_cap, n_steps_r, c_out);
+}
+
+// The mix: c'_i = c_perm(i) r_i^n mod n^2 for `count` = 2^d ciphertexts under one key.  The 2d - 1 layers of the
+// Benes network (k_mix_route, one launch each, layer l on bit l for l < d and 2d - 2 - l above) move the inputs to their outputs, then
+// k_mix_rerand runs the `count` r^n chains and final products in one launch.  routes: every layer's outputs, (2d - 1) x count x L words;
+// records output-major, nr + 1 per output.  The switch bits, the r_i and the route layers (which show the permutation) are secrets:
+// the staged bits and r_i, and in the host form the staged routes and records, are overwritten before the call returns, on every path
+// past the staging.
+#define K3_MIX_MAX 1024
+struct MixArgs {
+    uint32_t Ln, n_bits, per, layers;
+    size_t count;
+    const uint64_t *n, *cts, *rs;
+    const uint8_t* bits;
+    uint64_t *routes_out, *steps_out, *mixed_out;
+    int on_device;
+    u64 *d_n, *d_cts, *d_rs, *d_routes, *d_c, *d_mod, *d_steps;
+    uint8_t* d_bits;
+    u32* d_status;
+};
+static int mix_run(pz_ctx* ctx, const MixArgs& a) {
+    const unsigned L = 2 * a.Ln, C = capacity(L), half = (unsigned)(a.count / 2), d = (a.layers + 1) / 2;
+    const size_t nb = (size_t)a.Ln * 8, lb = (size_t)L * 8, layer_words = a.count * L;
+    HIPCHK(ctx, hipMemcpyAsync(a.d_n, a.n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_cts, a.cts, a.count * lb, hipMemcpyHostToDevice, ctx->stream));
+    if (a.layers) HIPCHK(ctx, hipMemcpyAsync(a.d_bits, a.bits, (size_t)a.layers * half, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_rs, a.rs, a.count * nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(a.d_status, 0, 4, ctx->stream));
+    const u64* routed = a.d_cts;   // count = 1: no switch, the output is the input
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        PZCHK(launch_barrett_setup(ctx, C, a.d_n, a.Ln, 1, a.d_mod, a.d_status));
+        for (unsigned l = 0; l < a.layers; ++l) {
+            const unsigned beta = l < d ? l : a.layers - 1 - l;
+            u64* out = a.d_routes + l * layer_words;
+            K3_LAUNCH(ctx, k_mix_route, C, dim3(half), dim3(64), 0, routed, out, a.d_bits + (size_t)l * half, beta, half, L);
+            routed = out;
+        }
+        K3_LAUNCH(ctx, k_mix_rerand, C, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, a.d_mod, a.d_n, routed, a.d_rs, a.n_bits, a.per,
+                  (unsigned)a.count, a.d_steps, a.d_c, a.Ln, a.d_status);
+    }
+    // the status first: nothing reaches the caller's buffers from a refused call
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&st, a.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    PZCHK(status_to_rc(ctx, st));
+    HIPCHK(ctx, hipMemcpyAsync(a.mixed_out, a.d_c, a.count * lb, hipMemcpyDeviceToHost, ctx->stream));
+    if (!a.on_device) {
+        if (a.routes_out && a.layers)
+            HIPCHK(ctx, hipMemcpyAsync(a.routes_out, a.d_routes, a.layers * layer_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (a.steps_out) HIPCHK(ctx, hipMemcpyAsync(a.steps_out, a.d_steps, a.count * a.per * 4 * lb, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PZ_OK;
+}
+static int mix_impl(pz_ctx* ctx, uint32_t Ln, size_t count, const uint64_t* n, const uint64_t* cts, const uint8_t* bits, const uint64_t* rs,
+                    uint64_t* routes_out, uint64_t* steps_out, int on_device, size_t steps_cap, uint64_t* mixed_out) {
+    if (!ctx || !n || !cts || !rs || !mixed_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_MIX_MAX || (count & (count - 1)) != 0 || (!bits && count > 1)) return PZ_ERR_INVALID;
+    const unsigned L = 2 * Ln;
+    if (L > 128) return PZ_ERR_UNSUPPORTED;
+    // n's bits are public structure of the circuit (pow_mod_fixed_exp): the records of one r^n chain are counted here
+    const uint32_t n_bits = bitlen_limbs(n, Ln), nr = (uint32_t)fixed_exp_steps(n, Ln), per = nr + 1;
+    if (steps_out && steps_cap < count * per) return PZ_ERR_CAPACITY;
+    uint32_t layers = 0;
+    for (size_t c = count; c > 1; c >>= 1) layers += 2;
+    if (layers) --layers;
+    const size_t n_switch = (size_t)layers * (count / 2);
+    {   // before any launch: a switch bit is 0 or 1 (every byte is looked at, whatever the others hold)
+        unsigned any = 0;
+        for (size_t i = 0; i < n_switch; ++i) any |= bits[i];
+        if (any > 1) return PZ_ERR_MESSAGE_RANGE;
+    }
+    if (n_bits == 0) return PZ_ERR_ZERO_MODULUS;
+    PZ_ENTER(ctx);
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, route_bytes = (size_t)layers * count * lb;
+    const bool ws_routes = layers && !(on_device && routes_out);
+    // n | c_1 .. c_count | bits | r_1 .. r_count | the route layers (unless the caller's device buffer takes them) | c'_1 .. c'_count |
+    // Barrett constants | status
+    const size_t pub_bytes = (nb + count * lb + 255) & ~(size_t)255, bit_bytes = (n_switch + 255) & ~(size_t)255;
+    const size_t sec_bytes = bit_bytes + ((count * nb + (ws_routes ? route_bytes : 0) + 255) & ~(size_t)255);
+    const size_t c_bytes = (count * lb + 255) & ~(size_t)255, mod_bytes = mod_block_words(capacity(L)) * 8;
+    void* d;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, pub_bytes + sec_bytes + c_bytes + mod_bytes + 256, &d));
+    char* p = (char*)d;
+    MixArgs a{};
+    a.Ln = Ln; a.n_bits = n_bits; a.per = per; a.layers = layers; a.count = count;
+    a.n = n; a.cts = cts; a.rs = rs; a.bits = bits; a.routes_out = routes_out; a.steps_out = steps_out; a.mixed_out = mixed_out;
+    a.on_device = on_device;
+    a.d_n = (u64*)p;
+    a.d_cts = (u64*)(p + nb);
+    a.d_bits = (uint8_t*)(p + pub_bytes);
+    a.d_rs = (u64*)(p + pub_bytes + bit_bytes);
+    a.d_routes = ws_routes ? a.d_rs + count * Ln : routes_out;
+    a.d_c = (u64*)(p + pub_bytes + sec_bytes);
+    a.d_mod = (u64*)(p + pub_bytes + sec_bytes + c_bytes);
+    a.d_status = (u32*)(p + pub_bytes + sec_bytes + c_bytes + mod_bytes + 64);
+    a.d_steps = on_device ? steps_out : nullptr;
+    const size_t rec_bytes = steps_out && !on_device ? count * per * 4 * lb : 0;
+    if (rec_bytes) {
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_B, rec_bytes, &t));
+        a.d_steps = (u64*)t;
+    }
+    return wipe_secrets_and_sync(ctx, mix_run(ctx, a), a.d_bits, sec_bytes, a.d_steps, rec_bytes);
+}
+extern "C" int pz_paillier_mix(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts, const uint8_t* bits,
+                               const uint64_t* rs, uint64_t* routes_out, uint64_t* steps_out, size_t steps_cap, uint64_t* mixed_out) {
+    return mix_impl(ctx, limbs_n, count, n, cts, bits, rs, routes_out, steps_out, 0, steps_cap, mixed_out);
+}
+extern "C" int pz_paillier_mix_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts, const uint8_t* bits,
+                                   const uint64_t* rs, uint64_t* d_routes_out, uint64_t* d_steps_out, size_t steps_cap, uint64_t* mixed_out) {
+    return mix_impl(ctx, limbs_n, count, n, cts, bits, rs, d_routes_out, d_steps_out, 1, steps_cap, mixed_out);
 }
 
 // A trustee's partial decryptions: h = v^theta, u_j = (c_j^2)^theta mod n^2 for `count` ciphertexts under one share

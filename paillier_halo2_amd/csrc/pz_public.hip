@@ -307,6 +307,28 @@ int partial_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_b
     return PZ_OK;
 }
 
+// the mix (kind 8, `count` = 2^d ciphertexts, n_steps_r records per r^n chain): n | c_1 | .. | c_K | c'_1 | .. | c'_K.  n's limb cells head the
+// stream, the c_j are the full-width assign_integer blocks that follow; c'_i is the assign_integer(2 limbs_n) in front of output i's
+// assert_equal_fresh, the K pairs closing the stream.
+int mix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r, std::vector<uint64_t>& cells) {
+    if (limbs_n == 0) return PZ_ERR_INVALID;
+    size_t total = 0, a_in = 0, a_wide = 0, a_eq = 0;
+    PZCHK(pz_mix_cells(limbs_n, limb_bits, lookup_bits, count, n_steps_r, &total, nullptr));
+    PZCHK(pz_op_cells(0, limbs_n, limb_bits, lookup_bits, &a_in, nullptr));
+    PZCHK(pz_op_cells(0, 2 * limbs_n, limb_bits, lookup_bits, &a_wide, nullptr));
+    PZCHK(pz_op_cells(5, 2 * limbs_n, limb_bits, lookup_bits, &a_eq, nullptr));
+    if (total < a_in + count * a_wide + count * (a_wide + a_eq)) return PZ_ERR_INTERNAL;
+    const size_t res = total - count * (a_wide + a_eq);
+    const uint32_t L = 2 * limbs_n;
+    cells.clear();
+    for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(j);
+    for (size_t i = 0; i < count; ++i)
+        for (uint32_t j = 0; j < L; ++j) cells.push_back(a_in + i * a_wide + j);
+    for (size_t i = 0; i < count; ++i)
+        for (uint32_t j = 0; j < L; ++j) cells.push_back(res + i * (a_wide + a_eq) + j);
+    return PZ_OK;
+}
+
 }   // namespace
 
 int pz_instance_eval_launch(pz_ctx* ctx, uint32_t k, const uint64_t omega[4], const uint64_t n_inv[4], const uint64_t* d_instances, size_t L,
@@ -388,6 +410,23 @@ extern "C" int pz_partial_public_cells(uint32_t limbs_n, uint32_t limb_bits, uin
     return PZ_OK;
 }
 
+extern "C" int pz_mix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
+                                   uint64_t* cells_out, size_t capacity, size_t* n_public) {
+    if (!n_public) return PZ_ERR_INVALID;
+    std::vector<uint64_t> cells;
+    try {
+        PZCHK(mix_public_cells(limbs_n, limb_bits, lookup_bits, count, n_steps_r, cells));
+    } catch (const std::bad_alloc&) {
+        return PZ_ERR_OOM;
+    }
+    *n_public = cells.size();
+    if (cells_out) {
+        if (capacity < cells.size()) return PZ_ERR_CAPACITY;
+        memcpy(cells_out, cells.data(), cells.size() * 8);
+    }
+    return PZ_OK;
+}
+
 extern "C" int pz_structure_expose(pz_structure* st) {
     if (!st || !st->ctx || st->n_instance) return PZ_ERR_INVALID;
     pz_ctx* ctx = st->ctx;
@@ -398,6 +437,8 @@ extern "C" int pz_structure_expose(pz_structure* st) {
             PZCHK(ballot_public_cells(st->limbs_n, st->limb_bits, st->lookup_bits, st->count, (uint32_t)(st->n_steps_g / 2), st->n_steps_r, cells));
         else if (st->kind == 7)
             PZCHK(partial_public_cells(st->limbs_n, st->limb_bits, st->lookup_bits, st->count, cells));
+        else if (st->kind == 8)
+            PZCHK(mix_public_cells(st->limbs_n, st->limb_bits, st->lookup_bits, st->count, st->n_steps_r, cells));
         else
             PZCHK(public_cells(st->kind, st->limbs_n, st->limb_bits, st->lookup_bits, st->n_steps_g, st->n_steps_r, cells));
     } catch (const std::bad_alloc&) {

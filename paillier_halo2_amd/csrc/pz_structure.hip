@@ -435,6 +435,10 @@ struct Stream {
 // kind 7 (a trustee's partial decryptions): n, then v, theta and `count` ciphertexts at full width, square +
 // refresh, load_zero; pow_mod(v, theta) as kind 2 emits it with theta's 2 Ln limb cells as the num_to_bits inputs; per ciphertext the
 // block mul_mod(c_j, c_j) and pow_mod(s_j, theta) from its remainder; then assign_integer + assert_equal_fresh for h and for every u_j.
+// kind 8 (the mix): n, `count` = 2^d ciphertexts at full width, assign_integer(r_i) for every output, square +
+// refresh, load_zero; the Benes network as ONE walked part -- per layer and switch assert_bit of the switch's own bit cell, then per
+// limb select(in[j'], in[j], b) and select(in[j], in[j'], b), the operands the previous layer's outputs --; per output
+// pow_mod_fixed_exp(r_i_ext, exp_r = n) and the block mul_mod(d_i, rn_i); then per output res_i and assert_equal_fresh.
 int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, unsigned w_bits, Stream& S) {
     const unsigned L = 2 * Ln;
     S.tmpls.reserve(2);                  // (references to the templates stay valid when a circuit with in-circuit bits adds the second one)
@@ -461,6 +465,9 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
                 sum_c = w.put();
             }
         }
+        for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, Ln, W, lb));
+    } else if (kind == 8) {
+        for (size_t i = 0; i < count; ++i) ct_c.push_back(assign(w, L, W, lb));
         for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, Ln, W, lb));
     } else if (kind == 7) {
         g_c = assign(w, L, W, lb);   // v: the key's base, full width
@@ -630,6 +637,45 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             off = S.blocks(off, 0, std::vector<i64>(acc_cells), std::vector<i64>(rn), {}, 1);
         }
         S.n_steps_g = 2 * (size_t)w_bits;
+    } else if (kind == 8) {
+        Walk wn(off);
+        auto select = [&](i64 x, i64 y, i64 s) {   // FlexGate::select(x, y, s): [d | 1 | y | x | y | s | d | out], windows at 0 and 4
+            const i64 c_d = wn.put();
+            wn.gate(c_d);
+            wn.putc(c_small(1)); wn.put(y); wn.put(x);
+            const i64 g = wn.put(y);
+            wn.gate(g);
+            wn.put(s); wn.put(c_d);
+            return wn.put();
+        };
+        unsigned d = 0;
+        while (((size_t)1 << d) < count) ++d;
+        const unsigned layers = count > 1 ? 2 * d - 1 : 0;
+        std::vector<std::vector<i64>> cur_c = ct_c;
+        for (unsigned ly = 0; ly < layers; ++ly) {
+            const unsigned beta = ly < d ? ly : layers - 1 - ly;
+            std::vector<std::vector<i64>> nxt_c(count);
+            for (size_t j = 0; j < count; ++j) {
+                if ((j >> beta) & 1) continue;
+                const size_t jp = j | ((size_t)1 << beta);
+                const i64 g = wn.putc(c_small(0));   // assert_bit: [0, b, b, b], the first b the bit's own cell
+                wn.gate(g);
+                const i64 b_c = wn.put();
+                wn.put(b_c); wn.put(b_c);
+                nxt_c[j].resize(L); nxt_c[jp].resize(L);
+                for (unsigned t = 0; t < L; ++t) {
+                    nxt_c[j][t] = select(cur_c[jp][t], cur_c[j][t], b_c);
+                    nxt_c[jp][t] = select(cur_c[j][t], cur_c[jp][t], b_c);
+                }
+            }
+            cur_c.swap(nxt_c);
+        }
+        off = S.flush(wn);
+        for (size_t i = 0; i < count; ++i) {
+            S.n_steps_r = (size_t)fixed_chain(ext_l(rs_c[i]), exp_r, rn);
+            roots.push_back(block_r(off));
+            off = S.blocks(off, 0, std::vector<i64>(cur_c[i]), std::vector<i64>(rn), {}, 1);
+        }
     } else if (kind == 7) {
         S.tmpls.push_back(uniform_template(L, W, lb));
         S.bind_template_constants(1);
@@ -1025,7 +1071,7 @@ extern "C" int pz_structure_arrays(const pz_structure* st, const uint8_t** d_sel
 static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, const uint64_t* exp_g,
                           const uint64_t* exp_r, size_t count, uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors,
                           pz_structure** out) {
-    if (!ctx || !out || kind < 0 || kind > 7 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+    if (!ctx || !out || kind < 0 || kind > 8 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
     const int handle_kind = kind;   // kind 5 ("decrypt") is kind 2's circuit under another statement: pz_structure_expose alone tells them apart
     if (kind == 5) kind = 2;
     if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
@@ -1033,7 +1079,8 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     if (limb_bits < 16 || limb_bits > 90 || lookup_bits == 0 || lookup_bits >= k || k < 4 || k > 24 || lookup_bits >= limb_bits) return PZ_ERR_INVALID;
     if (kind == 6 && (count < 1 || count > 1024 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
     if (kind == 7 && (count < 1 || count > 1024)) return PZ_ERR_INVALID;
-    if (((kind == 0 || kind == 2 || kind == 6) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
+    if (kind == 8 && (count < 1 || count > 1024 || (count & (count - 1)) != 0)) return PZ_ERR_INVALID;
+    if (((kind == 0 || kind == 2 || kind == 6 || kind == 8) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
     const i64 n = (i64)1 << k;
     const i64 unusable = (i64)blinding_factors + 3;
     if (unusable + 8 > n || (i64)minimum_rows >= n) return PZ_ERR_INVALID;
@@ -1214,4 +1261,9 @@ extern "C" int pz_circuit_structure_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, ui
 extern "C" int pz_circuit_structure_partial_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                                 size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
     return structure_impl(ctx, 7, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, minimum_rows, blinding_factors, out);
+}
+// the mix (kind 8): count = 2^d ciphertexts (1 .. 1024) under the key whose modulus is exp_r; the shape is count and n alone
+extern "C" int pz_circuit_structure_mix_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                            const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
+    return structure_impl(ctx, 8, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, 0, minimum_rows, blinding_factors, out);
 }

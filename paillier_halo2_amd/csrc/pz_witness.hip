@@ -1751,6 +1751,260 @@ extern "C" int pz_partial_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_
                                col_stride, d_col_starts, n_adv_cols, max_rows);
 }
 
+// ---- the mix (circuit kind 8): K = 2^d ciphertexts through the Benes network, then c'_i = d_i r_i^n mod n^2.
+// Stream: assign n; assign c_1 .. c_K at full width; assign r_1 .. r_K; square + refresh, load_zero; per layer and switch [0, b, b, b]
+// and per limb select(in[j'], in[j], b), select(in[j], in[j'], b); per output [1, 0 | nr x mul_mod | mul_mod]; per output assign res_i
+// (2 Ln limbs) + assert_equal_fresh.  inputs: n | c_1 .. c_K | r_1 .. r_K | res_1 .. res_K.  Routes, bits and records are
+// pz_paillier_mix_dev's, as it leaves them: fields of 2 ceil(Ln W / 64) words.
+#define MIX_MAX 1024
+struct MixP {
+    size_t K, half, layers, per, a_cts, l_cts, a_rs, l_rs, a_net, sw_cells, a_out, l_out, out_stride, a_res, l_res, res_stride;
+    size_t in_cts, in_rs, in_res;   // word offsets inside `inputs`
+    unsigned d, rw;                 // log2 K; words per field of a route or record as K3 writes them
+};
+static int make_mix_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, size_t n_steps_r, CircP& C, MixP& B,
+                           size_t* adv_total, size_t* lk_total) {
+    if (count < 1 || count > MIX_MAX || (count & (count - 1)) != 0 || n_steps_r < 1 || n_steps_r > 0x7fffffffu) return PZ_ERR_INVALID;
+    if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
+    memset(&C, 0, sizeof C);
+    memset(&B, 0, sizeof B);
+    PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
+    C.Ln = limbs_n;
+    C.kind = 8;
+    C.words_n = (limbs_n * limb_bits + 63) / 64;
+    C.rc_adv = C.e.rc64_adv;
+    C.rc_lk = C.e.rc64_lk;
+    PZCHK(refresh_aux_host(limb_bits, limbs_n, limbs_n, C.inc, &C.nf));
+    if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
+    B.K = count; B.half = count / 2; B.per = n_steps_r + 1; B.rw = 2 * C.words_n;
+    while (((size_t)1 << B.d) < count) ++B.d;
+    B.layers = count > 1 ? 2 * (size_t)B.d - 1 : 0;
+    size_t a = 0, l = 0;
+    const size_t asg_a = (size_t)limbs_n * (1 + C.rc_adv), asg_l = (size_t)limbs_n * C.rc_lk;
+    C.n_in = 1;
+    C.a_assign[0] = a; C.l_assign[0] = l; a += asg_a; l += asg_l;
+    B.a_cts = a; B.l_cts = l; a += count * 2 * asg_a; l += count * 2 * asg_l;
+    B.a_rs = a; B.l_rs = l; a += count * asg_a; l += count * asg_l;
+    C.a_square = a;
+    a += 1;
+    for (unsigned i = 0; i < 2 * limbs_n - 1; ++i) a += 1 + 3 * ((size_t)i + 1);
+    C.a_refresh = a; C.l_refresh = l;
+    a += 1;
+    for (unsigned i = 0; i < C.nf; ++i) a += ((size_t)C.inc[i] + 1) * 22 + (size_t)C.inc[i] * 4;
+    a += (size_t)C.nf * C.rc_adv;
+    l += (size_t)C.nf * C.rc_lk;
+    C.a_zero = a; a += 1;
+    B.sw_cells = 4 + 16 * (size_t)C.e.L;
+    B.a_net = a; a += B.layers * B.half * B.sw_cells;
+    B.out_stride = 2 + B.per * C.e.cells;
+    B.a_out = a; B.l_out = l;
+    a += count * B.out_stride; l += count * B.per * C.e.lookups;
+    B.res_stride = 2 * asg_a + 2 + 16 * (size_t)C.nf;
+    B.a_res = a; B.l_res = l;
+    a += count * B.res_stride; l += count * 2 * asg_l;
+    B.in_cts = C.words_n;
+    B.in_rs = B.in_cts + count * C.e.L64;
+    B.in_res = B.in_rs + count * C.words_n;
+    C.res_off = B.in_res;   // (k_circuit_misc reads a result it does not write for this kind: res_1, valid memory)
+    *adv_total = a;
+    *lk_total = l;
+    return PZ_OK;
+}
+// one thread per (switch, limb): the limb's two selects -- [d | 1 | y | x | y | b | d | out] for (x, y) = (in[j'], in[j]) and then for
+// (in[j], in[j']) -- and, from the thread of limb 0, the switch's [0, b, b, b].  in: the layer below (layer 0: the ciphertexts inside
+// `inputs`, fields of in_words words), out: this layer of the routes; bits: this layer's.
+__global__ __launch_bounds__(256) void k_mix_switch(ExpP P, unsigned beta, unsigned half, const u64* __restrict__ in, unsigned in_words,
+                                                    const u64* __restrict__ out, unsigned out_words, const unsigned char* __restrict__ bits,
+                                                    size_t cell_base, size_t sw_cells, Fr* __restrict__ advice) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned L = P.L, W = P.W;
+    if (g >= (size_t)half * L) return;
+    const unsigned s = (unsigned)(g / L), t = (unsigned)(g % L);
+    const size_t j = ((size_t)(s >> beta) << (beta + 1)) | (s & ((1u << beta) - 1u)), jp = j | ((size_t)1 << beta);
+    const unsigned b = bits[s];
+    const Fr fb = fr_from_u(u_make(b));
+    const CellPtr a = adv_ptr(P, advice, cell_base + (size_t)s * sw_cells);
+    if (t == 0) {
+        fp_store(a, fp_zero<FrTag>());
+        fp_store(a + 1, fb);
+        fp_store(a + 2, fb);
+        fp_store(a + 3, fb);
+    }
+    u64 w[4][2];
+    limb_extract(in + j * in_words, in_words, t, W, w[0]);
+    limb_extract(in + jp * in_words, in_words, t, W, w[1]);
+    limb_extract(out + j * out_words, out_words, t, W, w[2]);
+    limb_extract(out + jp * out_words, out_words, t, W, w[3]);
+    const U192 vj = u_make(w[0][0], w[0][1]), vjp = u_make(w[1][0], w[1][1]);
+    const Fr fj = fr_from_u(vj), fjp = fr_from_u(vjp), d = fr_from_s(s_sub(vjp, vj)), nd = fr_from_s(s_sub(vj, vjp)), one = fp_one<FrTag>();
+    const CellPtr c = a + 4 + 16 * (size_t)t;
+    fp_store(c, d);      fp_store(c + 1, one); fp_store(c + 2, fj);   fp_store(c + 3, fjp);
+    fp_store(c + 4, fj); fp_store(c + 5, fb);  fp_store(c + 6, d);    fp_store(c + 7, fr_from_u(u_make(w[2][0], w[2][1])));
+    fp_store(c + 8, nd);   fp_store(c + 9, one); fp_store(c + 10, fjp); fp_store(c + 11, fj);
+    fp_store(c + 12, fjp); fp_store(c + 13, fb); fp_store(c + 14, nd);  fp_store(c + 15, fr_from_u(u_make(w[3][0], w[3][1])));
+}
+// the records' fields from rw words (as K3 writes them) to L64 (as k_witness_expand reads them), where the two differ
+__global__ __launch_bounds__(256) void k_mix_repack(const u64* __restrict__ src, unsigned rw, u64* __restrict__ dst, unsigned L64, size_t fields) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= fields * L64) return;
+    const size_t f = g / L64;
+    const unsigned k = (unsigned)(g % L64);
+    dst[g] = k < rw ? src[f * rw + k] : 0;
+}
+// grid.x = output i: the [1, 0] of its pow_mod_fixed_exp, assign_integer(res_i) and assert_equal_fresh(c'_i, res_i), c'_i the remainder of
+// the output's last record (fields of L64 words)
+__global__ __launch_bounds__(256) void k_mix_misc(CircP C, MixP B, const u64* __restrict__ inputs, const u64* __restrict__ steps,
+                                                  Fr* __restrict__ advice, Fr* __restrict__ lookup) {
+    __shared__ u64 s_res[CIRC_MAXF][2], s_c[CIRC_MAXF][2];
+    __shared__ unsigned char s_eq[CIRC_MAXF + 1];
+    const size_t i = blockIdx.x;
+    const unsigned nf = C.nf, W = C.e.W, lb = C.e.lb, tid = threadIdx.x;
+    const u64* cval = steps + (i * B.per + B.per - 1) * 4 * (size_t)C.e.L64 + 3 * (size_t)C.e.L64;
+#define LIMB(X, i) u_make((X)[i][0], (X)[i][1])
+    for (unsigned t = tid; t < nf; t += blockDim.x) {
+        limb_extract(inputs + B.in_res + i * C.e.L64, C.e.L64, t, W, s_res[t]);
+        limb_extract(cval, C.e.L64, t, W, s_c[t]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned eq = 1;
+        s_eq[0] = 1;
+        for (unsigned t = 0; t < nf; ++t) {
+            eq &= u_eq(LIMB(s_c, t), LIMB(s_res, t)) ? 1u : 0u;
+            s_eq[t + 1] = (unsigned char)eq;
+        }
+        const CellPtr p = adv_ptr(C.e, advice, B.a_out + i * B.out_stride);
+        fp_store(p, fp_one<FrTag>());
+        fp_store(p + 1, fp_zero<FrTag>());
+    }
+    __syncthreads();
+    const CellPtr a = adv_ptr(C.e, advice, B.a_res + i * B.res_stride);
+    const CellPtr l{lookup, B.l_res + i * nf * C.rc_lk, C.e.rows, C.e.pad, nullptr, 0};
+    for (unsigned t = tid; t < nf * (1 + C.rc_adv); t += blockDim.x) {
+        Fr v;
+        if (t < nf) v = fr_from_u(LIMB(s_res, t));
+        else v = cv_to_fr(rc_adv_cell(LIMB(s_res, (t - nf) / C.rc_adv), W, lb, (t - nf) % C.rc_adv));
+        fp_store(a + t, v);
+    }
+    if (l)
+        for (unsigned t = tid; t < nf * C.rc_lk; t += blockDim.x) fp_store(l + t, cv_to_fr(rc_lk_cell(LIMB(s_res, t / C.rc_lk), W, lb, t % C.rc_lk)));
+    const CellPtr e = a + (size_t)nf * (1 + C.rc_adv);
+    if (tid == 0) {
+        fp_store(e, fp_zero<FrTag>());
+        fp_store(e + 1, fp_one<FrTag>());
+    }
+    for (unsigned t = tid; t < 16 * nf; t += blockDim.x) {
+        const unsigned j = t / 16, p = t % 16;
+        Fr v;
+        if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, j), LIMB(s_res, j), p));
+        else {
+            const unsigned eq = u_eq(LIMB(s_c, j), LIMB(s_res, j)) ? 1u : 0u, in = s_eq[j], out = s_eq[j + 1];
+            v = p == 12 ? fp_zero<FrTag>() : p == 13 ? (in ? fp_one<FrTag>() : fp_zero<FrTag>())
+                : p == 14 ? (eq ? fp_one<FrTag>() : fp_zero<FrTag>()) : (out ? fp_one<FrTag>() : fp_zero<FrTag>());
+        }
+        fp_store(e + 2 + t, v);
+    }
+#undef LIMB
+}
+
+extern "C" int pz_mix_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r, size_t* advice_cells,
+                            size_t* lookup_cells) {
+    CircP C;
+    MixP B;
+    size_t a, l;
+    PZCHK(make_mix_params(limbs_n, limb_bits, lookup_bits, count, n_steps_r, C, B, &a, &l));
+    if (advice_cells) *advice_cells = a;
+    if (lookup_cells) *lookup_cells = l;
+    return PZ_OK;
+}
+
+static int mix_expand_impl(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
+                           const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
+                           const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride,
+                           const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows) {
+    if (!ctx || !inputs || !d_steps || !d_modulus || !d_advice) return PZ_ERR_INVALID;
+    if ((rows == 0) != (col_stride == 0) || col_stride < rows) return PZ_ERR_INVALID;
+    CircP C;
+    MixP B;
+    size_t a, l;
+    PZCHK(make_mix_params(limbs_n, limb_bits, lookup_bits, count, n_steps_r, C, B, &a, &l));
+    if (B.layers && (!bits || !d_routes)) return PZ_ERR_INVALID;
+    C.e.rows = rows;
+    C.e.pad = col_stride - rows;
+    if (d_col_starts) {
+        if (n_adv_cols == 0 || n_adv_cols > 0xffffffffu || max_rows < 8 || max_rows > col_stride) return PZ_ERR_INVALID;
+        C.e.bp_starts = (const u64*)d_col_starts;
+        C.e.bp_ncols = (unsigned)n_adv_cols;
+        C.e.bp_div = max_rows - 1;
+        C.e.bp_stride = col_stride;
+    }
+    const size_t n_switch = B.layers * B.half;
+    for (size_t i = 0; i < n_switch; ++i)
+        if (bits[i] > 1) return PZ_ERR_MESSAGE_RANGE;   // assert_bit of such a byte cannot hold
+    PZ_ENTER(ctx);
+    const size_t in_words = B.in_res + count * C.e.L64;
+    void* d_in;
+    PZCHK(pz_ws_get(ctx, WS_MISC, in_words * 8 + n_switch + 64, &d_in));
+    PZCHK(pz_upload_small_async(ctx, d_in, inputs, in_words * 8));
+    const unsigned char* d_bits = (const unsigned char*)d_in + in_words * 8;
+    if (n_switch) PZCHK(pz_upload_small_async(ctx, (void*)d_bits, bits, n_switch));
+    const u64* recs = (const u64*)d_steps;
+    const size_t fields = count * B.per * 4;
+    if (B.rw != C.e.L64) {   // K3's fields are whole words of n twice over; K4's are the words 2 Ln limbs take
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_C, fields * C.e.L64 * 8, &t));
+        hipLaunchKernelGGL(k_mix_repack, dim3((unsigned)((fields * C.e.L64 + 255) / 256)), dim3(256), 0, ctx->stream, recs, B.rw, (u64*)t, C.e.L64,
+                           fields);
+        recs = (const u64*)t;
+    }
+    pz_timer tm(ctx, PZ_T_EXPAND);
+    const u64* in = (const u64*)d_in;
+    Fr *adv = (Fr*)d_advice, *lk = (Fr*)d_lookup;
+    // n, square, refresh, load_zero (the first record's remainder stands in for the result this kind does not write there)
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, recs + 3 * (size_t)C.e.L64, adv, lk);
+    // assign_integer(c_j): 2 Ln limbs from L64 words each; assign_integer(r_i): Ln limbs from words_n words each
+    hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)count), dim3(256), 0, ctx->stream, C.e, C.nf, C.rc_adv, C.rc_lk, in + B.in_cts, B.a_cts,
+                       B.l_cts, adv, lk);
+    ExpP R = C.e;
+    R.L64 = C.words_n;
+    hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)count), dim3(256), 0, ctx->stream, R, C.Ln, C.rc_adv, C.rc_lk, in + B.in_rs, B.a_rs,
+                       B.l_rs, adv, lk);
+    // the network, layer by layer: a layer reads the one below (layer 0: the ciphertexts) and its own
+    const size_t layer_words = count * B.rw;
+    for (size_t ly = 0; ly < B.layers; ++ly) {
+        const unsigned beta = (unsigned)(ly < B.d ? ly : B.layers - 1 - ly);
+        const u64* below = ly ? (const u64*)d_routes + (ly - 1) * layer_words : in + B.in_cts;
+        hipLaunchKernelGGL(k_mix_switch, dim3((unsigned)((B.half * C.e.L + 255) / 256)), dim3(256), 0, ctx->stream, C.e, beta, (unsigned)B.half,
+                           below, ly ? B.rw : C.e.L64, (const u64*)d_routes + ly * layer_words, B.rw, d_bits + ly * B.half,
+                           B.a_net + ly * B.half * B.sw_cells, B.sw_cells, adv);
+    }
+    // per output: the r-chain's records and the final one
+    ExpP T = C.e;
+    T.cell0 = B.a_out + 2;
+    T.lk0 = B.l_out;
+    T.chain_steps = B.per;
+    T.chain_stride = B.out_stride;
+    T.chain_recs = B.per;
+    hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(count * B.per)), dim3(EXP_THREADS), 0, ctx->stream, T, recs, d_modulus, adv, lk);
+    hipLaunchKernelGGL(k_mix_misc, dim3((unsigned)count), dim3(256), 0, ctx->stream, C, B, in, recs, adv, lk);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+extern "C" int pz_mix_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
+                                 const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
+                                 const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride) {
+    return mix_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, n_steps_r, inputs, bits, d_routes, d_steps, d_modulus, d_advice, d_lookup,
+                           rows, col_stride, nullptr, 0, 0);
+}
+extern "C" int pz_mix_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
+                                      const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
+                                      const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts,
+                                      size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride) {
+    if (!d_col_starts || lookup_rows == 0 || lookup_rows > col_stride) return PZ_ERR_INVALID;
+    return mix_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, n_steps_r, inputs, bits, d_routes, d_steps, d_modulus, d_advice, d_lookup,
+                           lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows);
+}
+
 // host-pointer form (SURVEY.md section 8b `pz_witness_expand`): stages the trace up, expands on the device in groups
 // of steps and copies the cell streams back; the prover pipeline keeps everything resident and uses the _dev form.
 extern "C" int pz_witness_expand(pz_ctx* ctx, uint32_t limbs, uint32_t limb_bits, uint32_t lookup_bits, const uint64_t* steps,

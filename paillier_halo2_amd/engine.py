@@ -562,6 +562,58 @@ class Engine:
                                                 steps_cap, C.byref(nr), _ptr(c)), "pz_paillier_ballot_dev")
         return c, nr.value
 
+    # the mix: shuffle and re-randomise K = 2^d ciphertexts under one key
+    @staticmethod
+    def mix_route(perm) -> np.ndarray:
+        """the switch bits of a mixer's permutation (pz.h pz_mix_route; host logic, needs no context): perm[i] = the index of the input
+        that output position i receives.  Returns the (2d - 1) K / 2 bytes of the Benes network, layer-major.  mix.benes_route is the
+        same in Python integers."""
+        perm = np.ascontiguousarray(perm, dtype=np.uint32).reshape(-1)
+        count = perm.shape[0]
+        d = max(count.bit_length() - 1, 0)
+        bits = np.zeros(max((2 * d - 1) * (count // 2), 1), dtype=np.uint8)
+        rc = _lib.lib().pz_mix_route(count, VP(perm.ctypes.data), VP(bits.ctypes.data))
+        if rc != 0:
+            raise PzError(rc, "pz_mix_route")
+        return bits[: max(2 * d - 1, 0) * (count // 2)]
+
+    @staticmethod
+    def _mix_args(limbs_n: int, n, cts, bits, rs):
+        n = _np(n).reshape(limbs_n)
+        cts, rs = _np(cts).reshape(-1, 2 * limbs_n), _np(rs).reshape(-1, limbs_n)
+        if cts.shape[0] != rs.shape[0]:
+            raise ValueError("one r per ciphertext")
+        return n, cts, np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1), rs
+
+    @staticmethod
+    def mix_layers(count: int) -> int:
+        """layers of the network over count positions: 2 log2(count) - 1, none for one position"""
+        return max(2 * (count.bit_length() - 1) - 1, 0)
+
+    def paillier_mix(self, limbs_n: int, n, cts, bits, rs, want_steps: bool = True, want_routes: bool = True):
+        """c'_i = c_perm(i) r_i^n mod n^2 (pz.h pz_paillier_mix): cts (K, 2*limbs_n), bits the network's switch bytes (mix_route), rs
+        (K, limbs_n).  Returns (mixed (K, 2*limbs_n), routes (2d - 1, K, 2*limbs_n) or None, steps (K, nr + 1, 4, 2*limbs_n) or None)."""
+        L = 2 * limbs_n
+        n, cts, bits, rs = self._mix_args(limbs_n, n, cts, bits, rs)
+        count = cts.shape[0]
+        per = self.ballot_steps_r(n) + 1
+        routes = np.zeros((max(self.mix_layers(count), 1), max(count, 1), L), dtype=np.uint64) if want_routes else None
+        steps = np.zeros((max(count, 1), per, 4, L), dtype=np.uint64) if want_steps else None
+        mixed = np.zeros((max(count, 1), L), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_mix(self.ctx, limbs_n, count, _ptr(n), _ptr(cts), VP(bits.ctypes.data), _ptr(rs),
+                                         _ptr(routes) if want_routes else VP(), _ptr(steps) if want_steps else VP(), count * per,
+                                         _ptr(mixed)), "pz_paillier_mix")
+        return mixed, (routes[: self.mix_layers(count)] if want_routes else None), steps
+
+    def paillier_mix_dev(self, limbs_n: int, n, cts, bits, rs, d_routes: int, d_steps: int, steps_cap: int):
+        """the same with the route layers and the records left on the device (d_routes: (2d - 1) x K x 2*limbs_n u64, d_steps: steps_cap
+        x 4 x 2*limbs_n u64; either may be 0).  Returns mixed."""
+        n, cts, bits, rs = self._mix_args(limbs_n, n, cts, bits, rs)
+        mixed = np.zeros((max(cts.shape[0], 1), 2 * limbs_n), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_mix_dev(self.ctx, limbs_n, cts.shape[0], _ptr(n), _ptr(cts), VP(bits.ctypes.data), _ptr(rs),
+                                             VP(d_routes), VP(d_steps), steps_cap, _ptr(mixed)), "pz_paillier_mix_dev")
+        return mixed
+
     def paillier_sk(self, limbs_n: int, n, g, lam, d) -> "PaillierSecretKey":
         """a secret key handle (pz.h pz_paillier_sk_create): n, g, lambda and d = n^-1 mod lambda as integers or limbs_n-word arrays
         (keys.secret_from_primes gives all four).  The key is validated on the device; free() wipes the handle's device memory."""
@@ -884,6 +936,41 @@ class Engine:
         self._chk(self.L.pz_partial_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, _ptr(inp), VP(d_steps), VP(d_modulus),
                                                     VP(d_advice), VP(d_lookup), VP(d_col_starts), n_adv_cols, max_rows, lookup_rows,
                                                     col_stride), "pz_partial_expand_cols_dev")
+
+    # the mix (circuit kind 8, pz.h pz_mix_*): its shape is count = 2^d and the records of one r^n chain
+    def mix_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, n_steps_r: int):
+        a = C.c_size_t()
+        l = C.c_size_t()
+        self._chk(self.L.pz_mix_cells(limbs_n, limb_bits, lookup_bits, count, n_steps_r, C.byref(a), C.byref(l)), "pz_mix_cells")
+        return a.value, l.value
+
+    def mix_public_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, n_steps_r: int):
+        """stream indices of the exposed cells in statement order: n | c_1 .. c_K | c'_1 .. c'_K"""
+        out = np.zeros(limbs_n + 2 * max(count, 1) * 2 * limbs_n, dtype=np.uint64)
+        npub = C.c_size_t()
+        self._chk(self.L.pz_mix_public_cells(limbs_n, limb_bits, lookup_bits, count, n_steps_r, _ptr(out), out.shape[0], C.byref(npub)),
+                  "pz_mix_public_cells")
+        return out[: npub.value]
+
+    def mix_expand_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, n_steps_r: int, inputs, bits, d_routes: int,
+                       d_steps: int, d_modulus: int, d_advice: int, d_lookup: int = 0, rows: int = 0, col_stride: int = 0):
+        """inputs: host uint64 array n | c_1 .. c_K | r_1 .. r_K | res_1 .. res_K; bits: the switch bytes paillier_mix_dev took; d_routes,
+        d_steps: the route layers and the K (n_steps_r + 1) records it left; writes the mix's cell stream, dense or cut into columns"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+        self._chk(self.L.pz_mix_expand_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, n_steps_r, _ptr(inp), VP(bits.ctypes.data),
+                                           VP(d_routes), VP(d_steps), VP(d_modulus), VP(d_advice), VP(d_lookup), rows, col_stride),
+                  "pz_mix_expand_dev")
+
+    def mix_expand_cols_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, n_steps_r: int, inputs, bits, d_routes: int,
+                            d_steps: int, d_modulus: int, d_advice: int, d_lookup: int, d_col_starts: int, n_adv_cols: int, max_rows: int,
+                            lookup_rows: int, col_stride: int):
+        """the same with the advice cells in break-point columns (circuit_expand_cols_dev's conventions)"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+        self._chk(self.L.pz_mix_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, n_steps_r, _ptr(inp), VP(bits.ctypes.data),
+                                                VP(d_routes), VP(d_steps), VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts),
+                                                n_adv_cols, max_rows, lookup_rows, col_stride), "pz_mix_expand_cols_dev")
 
     # ------------------------------------------------------------------ "next" rows: SRS setup, evaluation at a point
     def srs_setup_g1_dev(self, k: int, s, omega, d_g: int = 0, d_g_lagrange: int = 0):

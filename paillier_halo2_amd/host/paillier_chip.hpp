@@ -17,6 +17,7 @@
 //   (add folded over B full-width ciphertexts)                 PaillierChip::tally, pz::paillier_tally_test
 //   (c^w and prod c_i^w_i: the scalar homomorphism)            PaillierChip::mul_scalar / weighted_tally, pz::paillier_wtally_test (15.8)
 //   (K ciphertexts of small values with a public sum)          PaillierChip::ballot, pz::paillier_ballot_test (15.10)
+//   (K ciphertexts shuffled and re-randomised: a mixer's step) pz::benes_route (benes.hpp), PaillierChip::mix, pz::paillier_mix_test (15.17)
 //   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
 //   (T trustees holding additive shares of the exponent)      pz::ThresholdKey, pz::deal_shares, PaillierChip::partial_decrypt / combine (15.11)
 //   (any t of T trustees holding Shamir shares of it)          pz::ShamirKey, pz::deal_shamir, PaillierChip::combine_t / mod_inverse (15.12)
@@ -38,6 +39,7 @@
 #include <vector>
 
 #include "../../include/pz.h"
+#include "benes.hpp"
 #include "biguint.hpp"
 
 namespace pz {
@@ -76,7 +78,7 @@ class Context {
     // ---- the operation tape: what the reference's Context would hold, operation by operation
     // (0 .. 5 are pz_op_cells' operations; the three after them push a cell count of their own: record_cells)
     enum Op { ASSIGN = 0, SQUARE = 1, REFRESH = 2, CONST_CELL = 3, MUL_MOD = 4, ASSERT_EQUAL = 5, LOAD_WITNESS = 6, NUM_TO_BITS = 7, SELECT = 8,
-              SUM = 9 };
+              SUM = 9, SWITCH = 10 };
     struct OpRec {
         Op op;
         unsigned limbs;      // limb count the operation works on
@@ -100,6 +102,8 @@ class Context {
     }
     size_t load_witness() { record_cells(LOAD_WITNESS, 1, 1); return witness_cells_++; }   // ctx.load_witness(v): one advice cell, no gate
     void sum(size_t terms) { record_cells(SUM, 1, 1 + 3 * (terms - 1)); }         // FlexGate::sum over `terms` >= 2 cells: a | 1 | b | a + b | ..
+    // one switch of the mix's network over `limbs`-limb integers: assert_bit's [0, b, b, b], then per limb two selects of 8 cells
+    void conditional_swap(unsigned limbs) { record_cells(SWITCH, limbs, 4 + 16 * (size_t)limbs); }
     size_t load_zero() { record(CONST_CELL, 1); return zero_cells_++; }            // paillier.rs:47 ctx.load_zero(): one advice cell
     size_t load_constant_one() { record(CONST_CELL, 1); return zero_cells_++; }    // assign_constant(1) of pow_mod_fixed_exp
     const std::vector<OpRec>& ops() const { return ops_; }
@@ -551,6 +555,88 @@ class PaillierChip {  // paillier.rs:11-15
             out.push_back(AssignedBigUint<Fresh>(BigUint::from_limbs(cv.data() + i * wk, wk), L, biguint->limb_bits));
         }
         std::fill(rec.begin(), rec.end(), 0);
+        return R::Ok(out);
+    }
+
+    // The mix: c'_i = c_perm(i) r_i^n mod n^2 for K = 2^d ciphertexts under one key -- perm[i] is the index of
+    // the input that output i receives.  n^2 hoisted once, load_zero; the Benes network switch by switch (benes_route gives the bits);
+    // per output pow_mod_fixed_exp(r_i_ext, n) and mul_mod(d_i, rn_i).  One pz_paillier_mix call computes every route layer and record;
+    // the tape takes the records in the circuit's order, which is the call's.  The ciphertexts and the r_i are assigned by the caller
+    // (paillier_mix_test), in front of this.  wit (may be null) keeps the bits and the route layers, which the expansion of the tape
+    // needs (synthesize_mix_circuit) and which are the mixer's secrets: the caller wipes them.
+    struct MixWitness {
+        std::vector<uint8_t> bits;        // (2d - 1) K / 2 switch bytes, layer-major
+        std::vector<uint64_t> routes;     // (2d - 1) x K x 2 wn words: every layer's outputs, as pz_paillier_mix leaves them
+        void wipe() {
+            std::fill(bits.begin(), bits.end(), 0);
+            std::fill(routes.begin(), routes.end(), 0);
+        }
+    };
+    Result<std::vector<AssignedBigUint<Fresh>>> mix(Context& ctx, const AssignedBigUint<Fresh>& n, const std::vector<AssignedBigUint<Fresh>>& cts,
+                                                    const std::vector<uint32_t>& perm, const std::vector<AssignedBigUint<Fresh>>& rs,
+                                                    MixWitness* wit) const {
+        using R = Result<std::vector<AssignedBigUint<Fresh>>>;
+        const size_t K = cts.size();
+        if (!benes_is_count(K) || rs.size() != K || perm.size() != K) return R::Err(PZ_ERR_INVALID, "mix: 1, 2, 4 .. 1024 ciphertexts, one r and one index each");
+        std::vector<uint8_t> bits;
+        if (!benes_route(K, perm.data(), bits)) return R::Err(PZ_ERR_INVALID, "mix: perm is no permutation of 0 .. K - 1");
+        auto n2m = biguint->square(ctx, n);
+        if (!n2m.ok) return R::Err(n2m.err.status, n2m.err.msg);
+        RefreshAux aux = RefreshAux::new_(biguint->limb_bits, n.num_limbs(), n.num_limbs());
+        auto n2r = biguint->refresh(ctx, n2m.val, aux);
+        if (!n2r.ok) return R::Err(n2r.err.status, n2r.err.msg);
+        const AssignedBigUint<Fresh>& n2 = n2r.val;
+        (void)ctx.load_zero();
+        const unsigned L = n2.num_limbs(), Wd = n2.num_words(), wn = n.num_words(), wk = 2 * wn;   // K3 works on 2 * wn words
+        std::vector<uint64_t> nv = n.words(), cv, rv;
+        for (const auto& c : cts) {
+            if (c.num_limbs() != L) return R::Err(PZ_ERR_INVALID, "mix: a ciphertext is not assigned at full width");
+            std::vector<uint64_t> w = c.value().to_limbs(wk);
+            cv.insert(cv.end(), w.begin(), w.end());
+        }
+        for (const auto& r : rs) {
+            if (r.num_limbs() != n.num_limbs()) return R::Err(PZ_ERR_INVALID, "mix: an r is not assigned at n's width");
+            std::vector<uint64_t> w = r.value().to_limbs(wn);
+            rv.insert(rv.end(), w.begin(), w.end());
+        }
+        size_t nr = n.value().bits();
+        for (uint64_t w : nv) nr += (size_t)__builtin_popcountll(w);
+        const size_t per = nr + 1, layers = benes_layers(K);
+        std::vector<uint64_t> routes(layers * K * wk + 1), rec(K * per * 4 * wk), mv(K * wk);
+        int rc = pz_paillier_mix(ctx.raw(), wn, K, nv.data(), cv.data(), bits.data(), rv.data(), routes.data(), rec.data(), K * per, mv.data());
+        std::fill(rv.begin(), rv.end(), 0);
+        auto fail = [&](int st, const std::string& m) {
+            std::fill(bits.begin(), bits.end(), 0);
+            std::fill(routes.begin(), routes.end(), 0);
+            std::fill(rec.begin(), rec.end(), 0);
+            return R::Err(st, m);
+        };
+        if (rc != PZ_OK) return fail(rc, std::string("pz_paillier_mix: ") + pz_strerror(rc));
+        for (size_t s = 0; s < layers * (K / 2); ++s) ctx.conditional_swap(L);
+        // the tape holds Wd words per integer (Wd < 2 * wn where limb_bits does not divide 64: the words above are zero)
+        std::vector<uint64_t> steps;
+        std::vector<AssignedBigUint<Fresh>> out;
+        for (size_t i = 0; i < K; ++i) {
+            (void)ctx.load_constant_one();
+            (void)ctx.load_zero();
+            steps.clear();
+            for (size_t f = i * per * 4; f < (i + 1) * per * 4; ++f) {
+                if (BigUint::from_limbs(rec.data() + f * wk, wk).bits() > (size_t)L * biguint->limb_bits)
+                    return fail(PZ_ERR_RANGE, "a step's integer does not fit the assigned limb count");
+                steps.insert(steps.end(), rec.begin() + f * wk, rec.begin() + f * wk + Wd);
+            }
+            ctx.push_steps(steps, Wd, L, biguint->limb_bits, n2.value());   // the r^n chain, then the final block
+            out.push_back(AssignedBigUint<Fresh>(BigUint::from_limbs(mv.data() + i * wk, wk), L, biguint->limb_bits));
+        }
+        std::fill(rec.begin(), rec.end(), 0);
+        std::fill(steps.begin(), steps.end(), 0);
+        routes.resize(layers * K * wk);
+        if (wit) {
+            wit->bits = bits;
+            wit->routes = routes;
+        }
+        std::fill(bits.begin(), bits.end(), 0);
+        std::fill(routes.begin(), routes.end(), 0);
         return R::Ok(out);
     }
 
@@ -1081,6 +1167,30 @@ inline void paillier_ballot_test(Context& ctx, const RangeChip& range, const Pai
     }
 }
 
+// the mix's driver: assign n, every c_j at full width, every r_i, mix, then per output assign res_i and assert_equal_fresh
+struct PaillierMixInput {
+    unsigned limb_bits, enc_bits;
+    BigUint n;
+    std::vector<BigUint> cts;
+    std::vector<uint32_t> perm;
+    std::vector<BigUint> rs, res;
+};
+inline void paillier_mix_test(Context& ctx, const RangeChip& range, const PaillierMixInput& input, PaillierChip::MixWitness* wit) {
+    BigUintChip biguint_chip = BigUintChip::construct(&range, input.limb_bits);
+    PaillierChip paillier_chip = PaillierChip::construct(&biguint_chip, input.enc_bits);
+    auto n_assigned = biguint_chip.assign_integer(ctx, input.n, input.enc_bits).unwrap();
+    std::vector<AssignedBigUint<Fresh>> cts, rs;
+    for (const BigUint& c : input.cts) cts.push_back(biguint_chip.assign_integer(ctx, c, input.enc_bits * 2).unwrap());
+    for (const BigUint& r : input.rs) rs.push_back(biguint_chip.assign_integer(ctx, r, input.enc_bits).unwrap());
+    auto mixed = paillier_chip.mix(ctx, n_assigned, cts, input.perm, rs, wit).unwrap();
+    if (mixed.size() != input.res.size()) throw std::runtime_error("paillier_mix_test: one expected output per input");
+    for (size_t i = 0; i < mixed.size(); ++i) {
+        auto res_assigned = biguint_chip.assign_integer(ctx, input.res[i], input.enc_bits * 2).unwrap();
+        if (mixed[i].value() != res_assigned.value()) throw std::runtime_error("assertion failed: `(left == right)` (paillier_mix_test)");
+        biguint_chip.assert_equal_fresh(ctx, mixed[i], res_assigned).unwrap();
+    }
+}
+
 // decryption's driver: make the key handle, decrypt every ciphertext, hold the plaintexts to the expected ones and every recovered
 // (m, r) to its ciphertext by re-encrypting it (paillier_enc_native) -- throws on any mismatch, like the drivers above
 struct PaillierDecryptionInput {
@@ -1196,6 +1306,45 @@ inline int synthesize_ballot_circuit(Context& ctx, unsigned enc_bits, unsigned m
         in.insert(in.end(), w.begin(), w.end());
     }
     return pz_ballot_expand_dev(ctx.raw(), Ln, W, ctx.lookup_bits(), K, m_bits, n_steps_r, in.data(), d_steps, d_modulus, d_advice, d_lookup, 0, 0);
+}
+
+// the mix's tape (paillier_mix_test) expanded on the device: circuit kind 8, inputs n | c_1 .. c_K | r_1 .. r_K | res_1 .. res_K, the switch
+// bits and route layers of `wit`.  The records and routes go up with fields of 2 * ceil(Ln W / 64) words, as pz_paillier_mix_dev leaves
+// them.  d_work: device memory for both, (K (n_steps_r + 1) 4 + layers K) 2 wn words.
+inline int synthesize_mix_circuit(Context& ctx, unsigned enc_bits, size_t n_steps_r, const BigUint& n, const std::vector<BigUint>& cts,
+                                  const std::vector<BigUint>& rs, const std::vector<BigUint>& res, const PaillierChip::MixWitness& wit,
+                                  uint64_t* d_work, uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup) {
+    const unsigned W = ctx.limb_bits(), Ln = enc_bits / W, wn = (Ln * W + 63) / 64, wr = (2 * Ln * W + 63) / 64, wk = 2 * wn;
+    const size_t K = cts.size(), per = n_steps_r + 1, layers = benes_layers(K);
+    if (!benes_is_count(K) || rs.size() != K || res.size() != K || ctx.n_steps() != K * per || ctx.words() != wr) return PZ_ERR_INVALID;
+    if (wit.bits.size() != layers * (K / 2) || wit.routes.size() != layers * K * wk) return PZ_ERR_INVALID;
+    size_t a = 0, l = 0;
+    int rc = pz_mix_cells(Ln, W, ctx.lookup_bits(), K, n_steps_r, &a, &l);
+    if (rc != PZ_OK) return rc;
+    if (a != ctx.advice_cells() || l != ctx.lookup_cells()) return PZ_ERR_INVALID;   // the tape is not this driver's
+    std::vector<uint64_t> in = n.to_limbs(wn), w;
+    for (const BigUint& c : cts) {
+        w = c.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    for (const BigUint& r : rs) {
+        w = r.to_limbs(wn);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    for (const BigUint& c : res) {
+        w = c.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    const std::vector<uint64_t>& tp = ctx.tape();
+    std::vector<uint64_t> rec(K * per * 4 * wk, 0);
+    for (size_t f = 0; f < K * per * 4; ++f) std::copy(tp.begin() + f * wr, tp.begin() + (f + 1) * wr, rec.begin() + f * wk);
+    uint64_t* d_routes = d_work + rec.size();
+    rc = pz_upload(ctx.raw(), d_work, rec.data(), rec.size() * 8);
+    std::fill(rec.begin(), rec.end(), 0);
+    if (rc == PZ_OK && !wit.routes.empty()) rc = pz_upload(ctx.raw(), d_routes, wit.routes.data(), wit.routes.size() * 8);
+    if (rc != PZ_OK) return rc;
+    return pz_mix_expand_dev(ctx.raw(), Ln, W, ctx.lookup_bits(), K, n_steps_r, in.data(), wit.bits.empty() ? nullptr : wit.bits.data(),
+                             layers ? d_routes : nullptr, d_work, d_modulus, d_advice, d_lookup, 0, 0);
 }
 
 }  // namespace pz

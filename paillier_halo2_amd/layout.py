@@ -209,6 +209,7 @@ def wtally_tree(count: int):
 BALLOT_MAX = 1024       # ciphertexts of one ballot (pz.h pz_paillier_ballot)
 BALLOT_MAX_BITS = 64    # width of a ballot entry's message: one 64-bit word
 PARTIAL_MAX = 1024      # ciphertexts one trustee opens in one proof (pz.h pz_paillier_partial)
+MIX_MAX = 1024          # ciphertexts of one mix, a power of two (pz.h pz_paillier_mix)
 
 
 def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_steps_g: int = 0, n_steps_r: int = 0,
@@ -228,7 +229,11 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
     mul_mod, then per ciphertext assign res_i and assert_equal_fresh.
     kind 'partial' (circuit kind 7; count = K ciphertexts one trustee opens): assign n, assign v, theta and
     c_1 .. c_K at full width, square + refresh once, load_zero, pow_mod(v, theta) over all 2 Ln limbs of theta as kind 2 emits pow_mod,
-    per ciphertext mul_mod(c_j, c_j) and pow_mod(s_j, theta), then assign + assert_equal_fresh for h and every u_j."""
+    per ciphertext mul_mod(c_j, c_j) and pow_mod(s_j, theta), then assign + assert_equal_fresh for h and every u_j.
+    kind 'mix' (circuit kind 8; count = K = 2^d ciphertexts, n_steps_r = the records of ONE r^n chain): assign
+    n, assign c_1 .. c_K at full width, assign r_1 .. r_K, square + refresh once, load_zero, the (2d - 1) K / 2 switches of the network
+    (assert_bit's 4 cells, then per limb two selects of 8 cells), per output [1, 0], the r^n chain's blocks and the final mul_mod, then
+    per output assign res_i and assert_equal_fresh."""
     Ln, L = limbs_n, 2 * limbs_n
     if kind == "decrypt":
         kind = "encrypt_uniform"
@@ -256,8 +261,13 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
             raise ValueError(f"a trustee opens count = 1 .. {PARTIAL_MAX} ciphertexts in one proof, not {count}")
         if n_steps_g not in (0, 2 * L * limb_bits) or n_steps_r:
             raise ValueError("a partial decryption's chain has 2 * (2 * limbs_n * limb_bits) steps")
+    elif kind == "mix":
+        if count is None or not (1 <= count <= MIX_MAX and count & (count - 1) == 0):
+            raise ValueError(f"a mix takes count = 1, 2, 4 .. {MIX_MAX} ciphertexts, not {count}")
+        if n_steps_g or n_steps_r < 1:
+            raise ValueError("a mix has no g-chain and n_steps_r >= 1 steps of one r^n chain")
     elif count is not None:
-        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot' and 'partial'")
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial' and 'mix'")
     if w_bits is not None and kind != "wtally":
         raise ValueError("w_bits belongs to kind 'wtally'")
     if m_bits is not None and kind != "ballot":
@@ -277,6 +287,12 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         put("assign_v", ca, cl)
         put("assign_theta", ca, cl)
         put("assign_cts", count * ca, count * cl)
+    elif kind == "mix":
+        na, nl = assign_cells(Ln, limb_bits, lookup_bits)
+        ca, cl = assign_cells(L, limb_bits, lookup_bits)
+        put("assign_n", na, nl)
+        put("assign_cts", count * ca, count * cl)
+        put("assign_rs", count * na, count * nl)
     elif kind == "ballot":
         na, nl = assign_cells(Ln, limb_bits, lookup_bits)
         put("assign_n", na, nl)
@@ -319,6 +335,16 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         # the final block.  Then per entry assign res_i at full width and assert_equal_fresh
         steps = 2 * m_bits + n_steps_r + 1
         put("entries", count * (2 + 7 * m_bits - 2 + m_bits * 8 * L + 2 + steps * mm.advice), count * steps * mm.lookup)
+        ra, rl = assign_cells(L, limb_bits, lookup_bits)
+        put("results", count * (ra + assert_equal_cells(L)), count * rl)
+        seg["end"] = (a, l)
+        return CircuitCells(a, l, seg)
+    if kind == "mix":
+        # per switch assert_bit (4 cells) and per limb two selects (8 cells each); per output [1, 0], the chain's blocks and the final
+        # block; then per output assign res_i at full width and assert_equal_fresh
+        layers = 2 * (count.bit_length() - 1) - 1 if count > 1 else 0
+        put("network", layers * (count // 2) * (4 + 16 * L))
+        put("outputs", count * (2 + (n_steps_r + 1) * mm.advice), count * (n_steps_r + 1) * mm.lookup)
         ra, rl = assign_cells(L, limb_bits, lookup_bits)
         put("results", count * (ra + assert_equal_cells(L)), count * rl)
         seg["end"] = (a, l)

@@ -186,17 +186,18 @@ class NativeStructure:
     weight vector and every set of ciphertexts of that shape.  kind "ballot" (pz_circuit_structure_ballot_dev): count ciphertexts of
     m_bits-bit messages under the key whose modulus is exp_r -- one structure serves every ballot of that key.  kind "partial"
     (pz_circuit_structure_partial_dev): count ciphertexts one trustee opens -- one structure serves every trustee of every key of that
-    size."""
+    size.  kind "mix" (pz_circuit_structure_mix_dev): count = 2^d ciphertexts shuffled and re-randomised under the key whose modulus is
+    exp_r -- one structure serves every mixer of that key."""
 
-    KINDS = {"encrypt": 0, "add": 1, "encrypt_uniform": 2, "tally": 3, "wtally": 4, "decrypt": 5, "ballot": 6, "partial": 7}
+    KINDS = {"encrypt": 0, "add": 1, "encrypt_uniform": 2, "tally": 3, "wtally": 4, "decrypt": 5, "ballot": 6, "partial": 7, "mix": 8}
 
     def __init__(self, eng: Engine, kind: str, enc_bits: int, limb_bits: int, lookup_bits: int, k: int, exp_g: int = 0, exp_r: int = 0,
                  minimum_rows: int = 20, blinding_factors: int = 6, expose: bool = False, count: Optional[int] = None,
                  w_bits: Optional[int] = None, m_bits: Optional[int] = None):
         """expose: add the instance column (pz_structure_expose): n, g and the ciphertext(s) become the statement (tally: n, the c_i and
         their product); the maps then have m = n_adv + n_lk + 2 columns"""
-        if (kind in ("tally", "wtally", "ballot", "partial")) != (count is not None):
-            raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot' and 'partial', which need it")
+        if (kind in ("tally", "wtally", "ballot", "partial", "mix")) != (count is not None):
+            raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial' and 'mix', which need it")
         if (kind == "wtally") != (w_bits is not None):
             raise ValueError("w_bits belongs to kind 'wtally', which needs it")
         if (kind == "ballot") != (m_bits is not None):
@@ -215,6 +216,9 @@ class NativeStructure:
         elif kind == "partial":
             eng._chk(eng.L.pz_circuit_structure_partial_dev(eng.ctx, Ln, limb_bits, lookup_bits, k, int(count), minimum_rows, blinding_factors,
                                                             C.byref(h)), "pz_circuit_structure_partial_dev")
+        elif kind == "mix":
+            eng._chk(eng.L.pz_circuit_structure_mix_dev(eng.ctx, Ln, limb_bits, lookup_bits, k, int(count), _p(wr), minimum_rows,
+                                                        blinding_factors, C.byref(h)), "pz_circuit_structure_mix_dev")
         elif kind == "ballot":
             eng._chk(eng.L.pz_circuit_structure_ballot_dev(eng.ctx, Ln, limb_bits, lookup_bits, k, int(count), int(m_bits), _p(wr), minimum_rows,
                                                            blinding_factors, C.byref(h)), "pz_circuit_structure_ballot_dev")

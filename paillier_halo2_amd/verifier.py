@@ -180,7 +180,7 @@ def record_seed(prefix: str) -> bytes:
 def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] = None, c1: Optional[int] = None, c2: Optional[int] = None, *,
                   enc_bits: int, limb_bits: int, cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None,
                   m: Optional[int] = None, total: Optional[int] = None, v: Optional[int] = None, h: Optional[int] = None,
-                  partials: Optional[Sequence[int]] = None) -> List[int]:
+                  partials: Optional[Sequence[int]] = None, mixed: Optional[Sequence[int]] = None) -> List[int]:
     """the statement of a circuit with the instance column, in the column's row order: little-endian limbs of limb_bits,
     n | g | c (kind "encrypt" / "encrypt_uniform": c = g^m r^n mod n^2) or n | g | c1 | c2 | c ("add": c = c1 c2 mod n^2); n, g, c1, c2 have
     enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)
@@ -198,7 +198,12 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
     kind "partial": n | v | h | c_1 | u_1 | .. | c_K | u_K -- "the trustee whose public share is h = v^theta opened every c_j of cts to
     u_j = (c_j^2)^theta mod n^2 (partials) with that one theta"; v and h come from the public threshold key (keys.ThresholdKey.v, .hs[i]).
     The circuit compares nothing with n^2: the verifier does, HERE, and a v, h, c_j or u_j >= n^2 is refused, as are cts and partials of
-    different lengths.  No g and no single result c."""
+    different lengths.  No g and no single result c.
+    kind "mix": n | c_1 | .. | c_K | c'_1 | .. | c'_K -- "the list mixed is a re-randomised permutation of the list cts under the key
+    n": there are a permutation pi and r_i with c'_i = c_pi(i) r_i^n mod n^2.  K is a power of two (1 .. 1024); lists of different
+    lengths are refused, and so is any c_j or c'_i >= n^2 (no ciphertext) and any c'_i = 0 -- what a mixer's r_i = 0 leaves: a vote
+    destroyed in plain sight, which the circuit does not exclude (any other non-unit output needs a factor of n).  No g and no
+    single result c."""
     Ln = enc_bits // limb_bits
     mask = (1 << limb_bits) - 1
     limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
@@ -244,9 +249,23 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
         parts = [(n, Ln), (v, 2 * Ln), (h, 2 * Ln)]
         for ci, ui in zip(cts, partials):
             parts += [(ci, 2 * Ln), (ui, 2 * Ln)]
+    elif kind == "mix":
+        if cts is None or mixed is None or g is not None or c is not None:
+            raise ValueError("the mix statement names n, cts = [c_1 .. c_K] and mixed = [c'_1 .. c'_K], and neither g nor c")
+        if len(mixed) != len(cts):
+            raise ValueError("the mix statement has one output per input")
+        if not (1 <= len(cts) <= 1024 and len(cts) & (len(cts) - 1) == 0):
+            raise ValueError("a mix takes 1, 2, 4 .. 1024 ciphertexts")
+        if any(not 0 <= int(x) < int(n) * int(n) for x in list(cts) + list(mixed)):
+            raise ValueError("every input and every output of a mix is below n^2")
+        if any(int(x) == 0 for x in mixed):
+            raise ValueError("an output of a mix is not 0: a mixer's r_i = 0 destroys the ciphertext")
+        parts = [(n, Ln)] + [(ci, 2 * Ln) for ci in cts] + [(ci, 2 * Ln) for ci in mixed]
     else:
-        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt, ballot or partial")
-    if c is None and kind not in ("ballot", "partial"):
+        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt, ballot, partial or mix")
+    if mixed is not None and kind != "mix":
+        raise ValueError("mixed belongs to kind 'mix'")
+    if c is None and kind not in ("ballot", "partial", "mix"):
         raise ValueError("the statement names its result c")
     if (v is not None or h is not None or partials is not None) and kind != "partial":
         raise ValueError("v, h and partials belong to kind 'partial'")
@@ -254,8 +273,8 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
         raise ValueError("total belongs to kind 'ballot'")
     if m is not None and kind != "decrypt":
         raise ValueError("m belongs to kind 'decrypt'")
-    if cts is not None and kind not in ("tally", "wtally", "ballot", "partial"):
-        raise ValueError("cts belongs to kinds 'tally', 'wtally', 'ballot' and 'partial'")
+    if cts is not None and kind not in ("tally", "wtally", "ballot", "partial", "mix"):
+        raise ValueError("cts belongs to kinds 'tally', 'wtally', 'ballot', 'partial' and 'mix'")
     if weights is not None and kind != "wtally":
         raise ValueError("weights belongs to kind 'wtally'")
     for v, cnt in parts:

@@ -114,6 +114,14 @@ extern "C" {
                               rs: *const u64, steps_out: *mut u64, steps_cap: usize, n_steps_r: *mut u32, c_out: *mut u64) -> c_int;
     pub fn pz_paillier_ballot_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, m_bits: u32, n: *const u64, g: *const u64, ms: *const u64,
                                   rs: *const u64, d_steps_out: *mut u64, steps_cap: usize, n_steps_r: *mut u32, c_out: *mut u64) -> c_int;
+    // the mix: c'_i = c_perm(i) r_i^n mod n^2 for count = 2^d ciphertexts; bits: the (2d - 1) count / 2 switch
+    // bytes of the Benes network, layer-major (pz_mix_route makes them from perm); routes_out: every layer's outputs; records
+    // output-major, bits(n) + popcount(n) + 1 per output.  The bits, the r_i and the routes are the mixer's secrets.
+    pub fn pz_paillier_mix(ctx: *mut pz_ctx, limbs_n: u32, count: usize, n: *const u64, cts: *const u64, bits: *const u8, rs: *const u64,
+                           routes_out: *mut u64, steps_out: *mut u64, steps_cap: usize, mixed_out: *mut u64) -> c_int;
+    pub fn pz_paillier_mix_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, n: *const u64, cts: *const u64, bits: *const u8, rs: *const u64,
+                               d_routes_out: *mut u64, d_steps_out: *mut u64, steps_cap: usize, mixed_out: *mut u64) -> c_int;
+    pub fn pz_mix_route(count: usize, perm: *const u32, bits_out: *mut u8) -> c_int;
     // T-of-T threshold decryption: one trustee's partial decryptions h = v^theta, u_j = (c_j^2)^theta mod n^2 over
     // exactly e_bits bits of its secret share theta (records: the count squarings, then chain i at count + i 2 e_bits), and the combiner
     // m_j = L(prod_i u_ij mod n^2) mu2 mod n over trustee-major partials; flags bit 0: the product is not 1 mod n, bit 1: a partial >= n^2
@@ -226,6 +234,21 @@ extern "C" {
                                       col_stride: usize) -> c_int;
     pub fn pz_partial_public_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, cells_out: *mut u64, capacity: usize,
                                    n_public: *mut usize) -> c_int;
+    pub fn pz_circuit_structure_mix_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, k: u32, count: usize,
+                                        exp_r: *const u64, minimum_rows: usize, blinding_factors: u32, out: *mut *mut pz_structure) -> c_int;
+    // circuit kind 8 ("mix"): its shape is (count = 2^d, n_steps_r); inputs n | c_1 .. c_K | r_1 .. r_K | res_1 .. res_K; bits, d_routes and
+    // d_steps as pz_paillier_mix_dev took and left them
+    pub fn pz_mix_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, n_steps_r: usize, advice_cells: *mut usize,
+                        lookup_cells: *mut usize) -> c_int;
+    pub fn pz_mix_expand_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, n_steps_r: usize,
+                             inputs: *const u64, bits: *const u8, d_routes: *const u64, d_steps: *const u64, d_modulus: *const u64,
+                             d_advice: *mut u64, d_lookup: *mut u64, rows: usize, col_stride: usize) -> c_int;
+    pub fn pz_mix_expand_cols_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, n_steps_r: usize,
+                                  inputs: *const u64, bits: *const u8, d_routes: *const u64, d_steps: *const u64, d_modulus: *const u64,
+                                  d_advice: *mut u64, d_lookup: *mut u64, d_col_starts: *const u64, n_adv_cols: usize, max_rows: usize,
+                                  lookup_rows: usize, col_stride: usize) -> c_int;
+    pub fn pz_mix_public_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, n_steps_r: usize, cells_out: *mut u64,
+                               capacity: usize, n_public: *mut usize) -> c_int;
     pub fn pz_structure_info(st: *const pz_structure, n_adv: *mut usize, n_adv_filled: *mut usize, n_lk: *mut usize, max_rows: *mut usize,
                              n_constants: *mut usize, n_cells: *mut usize, n_lookups: *mut usize, n_steps_g: *mut usize,
                              n_steps_r: *mut usize) -> c_int;

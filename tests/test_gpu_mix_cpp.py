@@ -1,0 +1,32 @@
+"""The mix in the C++ host mirror (paillier_halo2_amd/host/benes.hpp: pz::benes_route; paillier_chip.hpp: PaillierChip::mix,
+paillier_mix_test, synthesize_mix_circuit) driven by tests/cpp/test_mix.cpp over the C ABI alone."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _build(force=False):
+    import paillier_halo2_amd as pz
+
+    pz.build()          # the library the program links
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-f", "mix.mk"] + (["-B"] if force else []), stdout=subprocess.DEVNULL)
+    return os.path.join(ROOT, "tests", "cpp", "test_mix")
+
+
+def test_mix_mirror_builds_and_routes():
+    """CPU: the mirror with the mix compiles and links against the C ABI; its routing checks need no device"""
+    exe = _build(force=True)
+    p = subprocess.run([exe, "--route-only"], capture_output=True, text=True, timeout=300)
+    print(p.stdout[-3000:], p.stderr[-2000:])
+    assert p.returncode == 0 and "ALL OK" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_mix_mirror_on_the_device():
+    p = subprocess.run([_build()], capture_output=True, text=True, timeout=300)
+    print(p.stdout[-3000:], p.stderr[-2000:])
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    assert "ALL OK" in p.stdout
