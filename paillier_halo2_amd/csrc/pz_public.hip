@@ -359,72 +359,49 @@ extern "C" int pz_instance_eval_dev(pz_ctx* ctx, uint32_t k, const uint64_t omeg
     return pz_instance_eval_launch(ctx, k, omega, n_inv, d_instances, n_public, n_proofs, d_x, 4, d_out, 4, d_flags);
 }
 
+// the statement's cells of any kind, an allocation failure as a status.  count (and m_bits) are the ballot's, the partial decryption's
+// and the mix's; n_steps_g is the by-kind circuits'
+static int statement_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_g,
+                           size_t n_steps_r, std::vector<uint64_t>& cells) {
+    try {
+        if (kind == 6) return ballot_public_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, cells);
+        if (kind == 7) return partial_public_cells(limbs_n, limb_bits, lookup_bits, count, cells);
+        if (kind == 8) return mix_public_cells(limbs_n, limb_bits, lookup_bits, count, n_steps_r, cells);
+        return public_cells(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, cells);
+    } catch (const std::bad_alloc&) {
+        return PZ_ERR_OOM;
+    }
+}
+// the tail of the four pz_*_public_cells entry points: the count always, the cells where the caller gave room
+static int public_cells_out(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_g,
+                            size_t n_steps_r, uint64_t* cells_out, size_t capacity, size_t* n_public) {
+    if (!n_public) return PZ_ERR_INVALID;
+    std::vector<uint64_t> cells;
+    PZCHK(statement_cells(kind, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_g, n_steps_r, cells));
+    *n_public = cells.size();
+    if (cells_out) {
+        if (capacity < cells.size()) return PZ_ERR_CAPACITY;
+        memcpy(cells_out, cells.data(), cells.size() * 8);
+    }
+    return PZ_OK;
+}
+
 extern "C" int pz_circuit_public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g, size_t n_steps_r,
                                        uint64_t* cells_out, size_t capacity, size_t* n_public) {
-    if (!n_public) return PZ_ERR_INVALID;
-    std::vector<uint64_t> cells;
-    try {
-        PZCHK(public_cells(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, cells));
-    } catch (const std::bad_alloc&) {
-        return PZ_ERR_OOM;
-    }
-    *n_public = cells.size();
-    if (cells_out) {
-        if (capacity < cells.size()) return PZ_ERR_CAPACITY;
-        memcpy(cells_out, cells.data(), cells.size() * 8);
-    }
-    return PZ_OK;
+    if (kind > 5) return PZ_ERR_INVALID;   // (kinds 6 to 8 have entry points of their own)
+    return public_cells_out(kind, limbs_n, limb_bits, lookup_bits, 0, 0, n_steps_g, n_steps_r, cells_out, capacity, n_public);
 }
-
 extern "C" int pz_ballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
                                       uint64_t* cells_out, size_t capacity, size_t* n_public) {
-    if (!n_public) return PZ_ERR_INVALID;
-    std::vector<uint64_t> cells;
-    try {
-        PZCHK(ballot_public_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, cells));
-    } catch (const std::bad_alloc&) {
-        return PZ_ERR_OOM;
-    }
-    *n_public = cells.size();
-    if (cells_out) {
-        if (capacity < cells.size()) return PZ_ERR_CAPACITY;
-        memcpy(cells_out, cells.data(), cells.size() * 8);
-    }
-    return PZ_OK;
+    return public_cells_out(6, limbs_n, limb_bits, lookup_bits, count, m_bits, 0, n_steps_r, cells_out, capacity, n_public);
 }
-
 extern "C" int pz_partial_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint64_t* cells_out,
                                        size_t capacity, size_t* n_public) {
-    if (!n_public) return PZ_ERR_INVALID;
-    std::vector<uint64_t> cells;
-    try {
-        PZCHK(partial_public_cells(limbs_n, limb_bits, lookup_bits, count, cells));
-    } catch (const std::bad_alloc&) {
-        return PZ_ERR_OOM;
-    }
-    *n_public = cells.size();
-    if (cells_out) {
-        if (capacity < cells.size()) return PZ_ERR_CAPACITY;
-        memcpy(cells_out, cells.data(), cells.size() * 8);
-    }
-    return PZ_OK;
+    return public_cells_out(7, limbs_n, limb_bits, lookup_bits, count, 0, 0, 0, cells_out, capacity, n_public);
 }
-
 extern "C" int pz_mix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
                                    uint64_t* cells_out, size_t capacity, size_t* n_public) {
-    if (!n_public) return PZ_ERR_INVALID;
-    std::vector<uint64_t> cells;
-    try {
-        PZCHK(mix_public_cells(limbs_n, limb_bits, lookup_bits, count, n_steps_r, cells));
-    } catch (const std::bad_alloc&) {
-        return PZ_ERR_OOM;
-    }
-    *n_public = cells.size();
-    if (cells_out) {
-        if (capacity < cells.size()) return PZ_ERR_CAPACITY;
-        memcpy(cells_out, cells.data(), cells.size() * 8);
-    }
-    return PZ_OK;
+    return public_cells_out(8, limbs_n, limb_bits, lookup_bits, count, 0, 0, n_steps_r, cells_out, capacity, n_public);
 }
 
 extern "C" int pz_structure_expose(pz_structure* st) {
@@ -432,18 +409,8 @@ extern "C" int pz_structure_expose(pz_structure* st) {
     pz_ctx* ctx = st->ctx;
     PZ_ENTER(ctx);
     std::vector<uint64_t> cells;
-    try {
-        if (st->kind == 6)
-            PZCHK(ballot_public_cells(st->limbs_n, st->limb_bits, st->lookup_bits, st->count, (uint32_t)(st->n_steps_g / 2), st->n_steps_r, cells));
-        else if (st->kind == 7)
-            PZCHK(partial_public_cells(st->limbs_n, st->limb_bits, st->lookup_bits, st->count, cells));
-        else if (st->kind == 8)
-            PZCHK(mix_public_cells(st->limbs_n, st->limb_bits, st->lookup_bits, st->count, st->n_steps_r, cells));
-        else
-            PZCHK(public_cells(st->kind, st->limbs_n, st->limb_bits, st->lookup_bits, st->n_steps_g, st->n_steps_r, cells));
-    } catch (const std::bad_alloc&) {
-        return PZ_ERR_OOM;
-    }
+    PZCHK(statement_cells(st->kind, st->limbs_n, st->limb_bits, st->lookup_bits, st->count, (uint32_t)(st->n_steps_g / 2), st->n_steps_g,
+                          st->n_steps_r, cells));   // (the ballot's m_bits: its g-chains take 2 m_bits records)
     const size_t L = cells.size(), m = st->n_adv + st->n_lk + 1, n = (size_t)1 << st->k;
     if (L > st->max_rows) return PZ_ERR_UNSUPPORTED;   // (a tally of many ciphertexts: the statement must fit the column's usable rows)
     if (L == 0 || cells.back() >= st->n_cells) return PZ_ERR_INTERNAL;

@@ -677,13 +677,19 @@ static int make_params(uint32_t L, uint32_t limb_bits, uint32_t lb, ExpP& P) {
     return PZ_OK;
 }
 
+// the tail of every cell-count entry point: the builder's refusal, or the two counts to whoever asked for them
+static int put_cells(int rc, const size_t& a, const size_t& l, size_t* advice_cells, size_t* lookup_cells) {
+    PZCHK(rc);
+    if (advice_cells) *advice_cells = a;
+    if (lookup_cells) *lookup_cells = l;
+    return PZ_OK;
+}
+
 extern "C" int pz_witness_cells_per_step(uint32_t limbs, uint32_t limb_bits, uint32_t lookup_bits,
                                          size_t* advice_cells, size_t* lookup_cells) {
     ExpP P;
-    PZCHK(make_params(limbs, limb_bits, lookup_bits, P));
-    if (advice_cells) *advice_cells = P.cells;
-    if (lookup_cells) *lookup_cells = P.lookups;
-    return PZ_OK;
+    const int rc = make_params(limbs, limb_bits, lookup_bits, P);
+    return put_cells(rc, P.cells, P.lookups, advice_cells, lookup_cells);
 }
 
 extern "C" int pz_witness_expand_dev(pz_ctx* ctx, uint32_t limbs, uint32_t limb_bits, uint32_t lookup_bits,
@@ -707,27 +713,96 @@ extern "C" int pz_witness_expand_dev(pz_ctx* ctx, uint32_t limbs, uint32_t limb_
 // pow_mod_fixed_exp, the assignment of res and assert_equal_fresh -- in the layout of
 // paillier_halo2_amd/layout.py::circuit_cells (values: oracle/pyref.py::expand_circuit_cells).  A few thousand to a few
 // hundred thousand cells per proof: one workgroup, the serial carry chain of refresh on one lane.
+//
+// Every kind's stream is put together from the same pieces, described here once; the block comment above a kind names only what is
+// its own.
+//   * k_circuit_misc (one workgroup): assign_integer of the Ln-limb inputs that head the stream, square(n) + refresh, the single
+//     constant cells, and -- for the kinds with ONE result -- the result block.
+//   * k_circuit_assign_many: a run of equally wide assign_integer blocks, one workgroup each.
+//   * the result block (result_block): assign_integer(res) followed by assert_equal_fresh(c, res), c the value the records computed.
+//     Kinds with a result per entry write them with k_circuit_results, one workgroup each, together with the [1, 0] head of the
+//     entry's pow_mod_fixed_exp.
+//   * an exponent chain [1, 0 | num_to_bits | bits x (mul_mod, select, square_mod)]: k_circuit_bits[_many] for the head,
+//     k_circuit_select[_many] for the selects, launch_chains for the record pairs; runs of whole mul_mod blocks go through
+//     launch_runs.  nbits_cells and bit_stride name the chain's geometry.
+//   * host: circ_base and square_refresh_cells open every parameter builder, expand_enter and expand_stage every expansion.
 // ------------------------------------------------------------------------------------------------
 #define CIRC_MAXF 256   // fresh limbs of n^2 (2 Ln)
 #define CIRC_MAXJ 3     // pieces a product limb is cut into (2W + log2(Ln) bits -> at most 3 limbs)
+#define LIMB(X, i) u_make((X)[i][0], (X)[i][1])
 
 struct CircP {
     ExpP e;                         // shape of the mul_mod steps (L = 2 Ln): range-check parameters, limb width
     unsigned Ln, nf, words_n, kind;
-    unsigned n_in;                  // Ln-limb inputs assigned here: n | g | x | y (kinds 0..2) or n alone (kinds 3 and 4, the tallies)
-    size_t res_off;                 // word offset of res inside `inputs`
+    unsigned n_in;                  // Ln-limb inputs assigned here: n | g | x | y (kinds 0..2), n | g (ballot) or n alone
+    bool no_res;                    // no result block in k_circuit_misc: the kind has one per entry (k_circuit_results)
+    bool has_zero;                  // load_zero behind refresh (the tallies extend nothing: none)
+    size_t res_off;                 // word offset of res inside `inputs` (unless no_res)
     size_t a_cts, l_cts;            // kinds 3, 4: the count assign_integer(c_i, 2 Ln limbs) blocks (k_circuit_assign_many)
     size_t n_cts;                   // kinds 3, 4: the number of ciphertexts
     unsigned w_bits;                // kind 4: bits per weight
     size_t a_wts;                   // kind 4: the count load_witness(w_i) cells
     unsigned rc_adv, rc_lk;         // range_check(limb, W)
-    size_t a_assign[4], a_square, a_refresh, a_zero, a_pow[2], a_res, a_eq;   // advice offsets of the segments
-    size_t l_assign[4], l_refresh, l_res;                                      // lookup offsets
+    size_t a_assign[4], a_square, a_refresh, a_zero, a_pow[2], a_res;   // advice offsets of the segments
+    size_t l_assign[4], l_refresh, l_res;                               // lookup offsets
     unsigned char inc[CIRC_MAXF];
 };
 
+// assign_integer of the nl limbs X: the limbs, then per limb the cells of its range check; the lookup cells likewise.  Every thread of
+// the block calls it.
+__device__ __forceinline__ void assign_integer_cells(const CircP& C, const u64 (*X)[2], unsigned nl, const CellPtr& a, const CellPtr& l) {
+    const unsigned W = C.e.W, lb = C.e.lb;
+    for (unsigned t = threadIdx.x; t < nl * (1 + C.rc_adv); t += blockDim.x) {
+        Fr v;
+        if (t < nl) v = fr_from_u(LIMB(X, t));
+        else v = cv_to_fr(rc_adv_cell(LIMB(X, (t - nl) / C.rc_adv), W, lb, (t - nl) % C.rc_adv));
+        fp_store(a + t, v);
+    }
+    if (l)
+        for (unsigned t = threadIdx.x; t < nl * C.rc_lk; t += blockDim.x) fp_store(l + t, cv_to_fr(rc_lk_cell(LIMB(X, t / C.rc_lk), W, lb, t % C.rc_lk)));
+}
+
+// The result block at advice cell a / lookup cell l: assign_integer(res), then assert_equal_fresh(c, res) = [0, 1] and per limb the 12
+// cells of is_equal and [0, running bit, this limb's bit, running bit].  res, cval: L64 words each; s_res, s_c, s_eq: the block's shared
+// limb arrays (CIRC_MAXF limbs; CIRC_MAXF + 1 bytes).  Every thread of the block calls it (two barriers inside).
+__device__ __forceinline__ void result_block(const CircP& C, const u64* __restrict__ res, const u64* __restrict__ cval, u64 (*s_res)[2],
+                                             u64 (*s_c)[2], unsigned char* s_eq, const CellPtr& a, const CellPtr& l) {
+    const unsigned nf = C.nf, tid = threadIdx.x;
+    for (unsigned t = tid; t < nf; t += blockDim.x) {
+        limb_extract(res, C.e.L64, t, C.e.W, s_res[t]);
+        limb_extract(cval, C.e.L64, t, C.e.W, s_c[t]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned eq = 1;
+        s_eq[0] = 1;
+        for (unsigned i = 0; i < nf; ++i) {
+            eq &= u_eq(LIMB(s_c, i), LIMB(s_res, i)) ? 1u : 0u;
+            s_eq[i + 1] = (unsigned char)eq;
+        }
+    }
+    __syncthreads();
+    assign_integer_cells(C, s_res, nf, a, l);
+    const CellPtr e = a + (size_t)nf * (1 + C.rc_adv);
+    if (tid == 0) {
+        fp_store(e, fp_zero<FrTag>());
+        fp_store(e + 1, fp_one<FrTag>());
+    }
+    for (unsigned t = tid; t < 16 * nf; t += blockDim.x) {
+        const unsigned i = t / 16, p = t % 16;
+        Fr v;
+        if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, i), LIMB(s_res, i), p));
+        else {
+            const unsigned eq = u_eq(LIMB(s_c, i), LIMB(s_res, i)) ? 1u : 0u, in = s_eq[i], out = s_eq[i + 1];
+            v = p == 12 ? fp_zero<FrTag>() : p == 13 ? (in ? fp_one<FrTag>() : fp_zero<FrTag>())
+                : p == 14 ? (eq ? fp_one<FrTag>() : fp_zero<FrTag>()) : (out ? fp_one<FrTag>() : fp_zero<FrTag>());
+        }
+        fp_store(e + 2 + t, v);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __restrict__ inputs /* n | g | x | y | res; kind 3: n | c_1 .. c_B | res; kind 4: n | c_1 .. c_B | w_1 .. w_B | res */,
-                                                      const u64* __restrict__ cval /* the circuit's result, L64 words */,
+                                                      const u64* __restrict__ cval /* the circuit's result, L64 words (unless C.no_res) */,
                                                       Fr* __restrict__ advice, Fr* __restrict__ lookup) {
     const CellPtr adv = adv_ptr(C.e, advice, 0), lk{lookup, 0, C.e.rows, C.e.pad, nullptr, 0};
     __shared__ u64 s_in[4][EXP_MAXL / 2 + 1][2];       // limbs of n, g, x, y
@@ -740,12 +815,7 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
     const unsigned Ln = C.Ln, nf = C.nf, W = C.e.W, lb = C.e.lb, tid = threadIdx.x;
     const bool wide = W > 64;
     const unsigned D = 2 * Ln - 1;
-#define LIMB(X, i) u_make((X)[i][0], (X)[i][1])
     for (unsigned t = tid; t < C.n_in * Ln; t += blockDim.x) limb_extract(inputs + (size_t)(t / Ln) * C.words_n, C.words_n, t % Ln, W, s_in[t / Ln][t % Ln]);
-    for (unsigned t = tid; t < nf; t += blockDim.x) {
-        limb_extract(inputs + C.res_off, C.e.L64, t, W, s_res[t]);
-        limb_extract(cval, C.e.L64, t, W, s_c[t]);
-    }
     __syncthreads();
     // ---- square(n): one lane per product limb, cells written as the row is summed
     if (tid == 0) fp_store(adv + C.a_square, fp_zero<FrTag>());
@@ -765,7 +835,7 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
     }
     for (unsigned i = D + tid; i < nf; i += blockDim.x) { s_sq[i][0] = 0; s_sq[i][1] = 0; s_sq[i][2] = 0; }
     __syncthreads();
-    // ---- serial chains: refresh's carries, assert_equal_fresh's running bit
+    // ---- serial chain: refresh's carries
     if (tid == 0) {
         unsigned off = 1;
         for (unsigned i = 0; i < nf; ++i) {
@@ -787,31 +857,10 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
             s_fresh[i][0] = s_sq[i][0]; s_fresh[i][1] = s_sq[i][1];
         }
         s_roff[nf] = off;
-        unsigned eq = 1;
-        s_eq[0] = 1;
-        for (unsigned i = 0; i < nf; ++i) {
-            eq &= u_eq(LIMB(s_c, i), LIMB(s_res, i)) ? 1u : 0u;
-            s_eq[i + 1] = (unsigned char)eq;
-        }
     }
     __syncthreads();
-    // ---- assign_integer of n, g, x, y (Ln limbs) and of res (2 Ln limbs)
-    for (unsigned which = 0; which < 5; ++which) {
-        if (which >= C.n_in && which < 4) continue;
-        if (which == 4 && C.kind >= 6) continue;   // (the ballot's K results are k_ballot_misc's, a trustee's K + 1 k_partial_misc's)
-        const unsigned nl = which < 4 ? Ln : nf;
-        const u64(*X)[2] = which < 4 ? s_in[which] : s_res;
-        const CellPtr a = adv + (which < 4 ? C.a_assign[which] : C.a_res);
-        const CellPtr l = lk + (which < 4 ? C.l_assign[which] : C.l_res);
-        for (unsigned t = tid; t < nl * (1 + C.rc_adv); t += blockDim.x) {
-            Fr v;
-            if (t < nl) v = fr_from_u(LIMB(X, t));
-            else v = cv_to_fr(rc_adv_cell(LIMB(X, (t - nl) / C.rc_adv), W, lb, (t - nl) % C.rc_adv));
-            fp_store(a + t, v);
-        }
-        if (l)
-            for (unsigned t = tid; t < nl * C.rc_lk; t += blockDim.x) fp_store(l + t, cv_to_fr(rc_lk_cell(LIMB(X, t / C.rc_lk), W, lb, t % C.rc_lk)));
-    }
+    // ---- assign_integer of n, g, x, y (Ln limbs)
+    for (unsigned which = 0; which < C.n_in; ++which) assign_integer_cells(C, s_in[which], Ln, adv + C.a_assign[which], lk + C.l_assign[which]);
     // ---- refresh
     if (tid == 0) fp_store(adv + C.a_refresh, fp_zero<FrTag>());
     for (unsigned i = 0; i < nf; ++i) {
@@ -837,57 +886,80 @@ __global__ __launch_bounds__(256) void k_circuit_misc(CircP C, const u64* __rest
             fp_store(lk + C.l_refresh + t, cv_to_fr(rc_lk_cell(LIMB(s_fresh, t / C.rc_lk), W, lb, t % C.rc_lk)));
     // ---- load_zero; assign_constant(1) + load_zero of both pow_mod_fixed_exp
     if (tid == 0) {
-        if (C.kind < 3 || C.kind >= 6) fp_store(adv + C.a_zero, fp_zero<FrTag>());   // (the tallies extend nothing: no load_zero)
+        if (C.has_zero) fp_store(adv + C.a_zero, fp_zero<FrTag>());
         if (C.kind == 0 || C.kind == 2)
             for (int k = 0; k < 2; ++k) {
                 fp_store(adv + C.a_pow[k], fp_one<FrTag>());
                 fp_store(adv + C.a_pow[k] + 1, fp_zero<FrTag>());
             }
-        if (C.kind < 6) {
-            fp_store(adv + C.a_eq, fp_zero<FrTag>());
-            fp_store(adv + C.a_eq + 1, fp_one<FrTag>());
-        }
     }
-    // ---- assert_equal_fresh(c, res)
-    for (unsigned t = tid; t < (C.kind < 6 ? 16 * nf : 0u); t += blockDim.x) {
-        const unsigned i = t / 16, p = t % 16;
-        Fr v;
-        if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, i), LIMB(s_res, i), p));
-        else {
-            const unsigned e = u_eq(LIMB(s_c, i), LIMB(s_res, i)) ? 1u : 0u, in = s_eq[i], out = s_eq[i + 1];
-            v = p == 12 ? fp_zero<FrTag>() : p == 13 ? (in ? fp_one<FrTag>() : fp_zero<FrTag>())
-                : p == 14 ? (e ? fp_one<FrTag>() : fp_zero<FrTag>()) : (out ? fp_one<FrTag>() : fp_zero<FrTag>());
-        }
-        fp_store(adv + C.a_eq + 2 + t, v);
-    }
-#undef LIMB
+    // ---- assign_integer(res) (2 Ln limbs), assert_equal_fresh(c, res)
+    if (!C.no_res) result_block(C, inputs + C.res_off, cval, s_res, s_c, s_eq, adv + C.a_res, lk + C.l_res);
 }
 
-// ---- tally (kind 3): assign_integer of the B ciphertexts, grid.x = ciphertext -- limbs, then per limb the range check's cells; the
-// shared array holds ONE integer, whatever B is.  vals: grid.x integers of P.L64 words.
-__global__ __launch_bounds__(256) void k_circuit_assign_many(ExpP P, unsigned nl, unsigned rc_adv, unsigned rc_lk, const u64* __restrict__ vals,
-                                                             size_t a0, size_t l0, Fr* __restrict__ advice, Fr* __restrict__ lookup) {
+// ---- a run of assign_integer blocks, grid.x = integer: the nl limbs of integer i (words words each inside `vals`) at advice cell
+// a0 + i * nl * (1 + rc_adv) / lookup cell l0 + i * nl * rc_lk; the shared array holds ONE integer, however many there are
+__global__ __launch_bounds__(256) void k_circuit_assign_many(CircP C, unsigned nl, unsigned words, const u64* __restrict__ vals, size_t a0, size_t l0,
+                                                             Fr* __restrict__ advice, Fr* __restrict__ lookup) {
     __shared__ u64 s_x[CIRC_MAXF][2];
-    const unsigned W = P.W, lb = P.lb, tid = threadIdx.x;
-    const CellPtr a = adv_ptr(P, advice, a0 + (size_t)blockIdx.x * nl * (1 + rc_adv));
-    const CellPtr l{lookup, l0 + (size_t)blockIdx.x * nl * rc_lk, P.rows, P.pad, nullptr, 0};
-    for (unsigned t = tid; t < nl; t += blockDim.x) limb_extract(vals + (size_t)blockIdx.x * P.L64, P.L64, t, W, s_x[t]);
+    const CellPtr a = adv_ptr(C.e, advice, a0 + (size_t)blockIdx.x * nl * (1 + C.rc_adv));
+    const CellPtr l{lookup, l0 + (size_t)blockIdx.x * nl * C.rc_lk, C.e.rows, C.e.pad, nullptr, 0};
+    for (unsigned t = threadIdx.x; t < nl; t += blockDim.x) limb_extract(vals + (size_t)blockIdx.x * words, words, t, C.e.W, s_x[t]);
     __syncthreads();
-    for (unsigned t = tid; t < nl * (1 + rc_adv); t += blockDim.x) {
+    assign_integer_cells(C, s_x, nl, a, l);
+}
+
+// ---- the result blocks of a kind with one result per entry, and the [1, 0] heads that go with them: block i of k_circuit_results
+struct ResP {
+    size_t in_res, in_stride;        // res_i: L64 words at word in_res + i * in_stride of `inputs`
+    size_t rec0, rec_stride;         // the value computed for it: field `field` of record rec0 + i * rec_stride
+    unsigned field;                  // 3: the record's remainder; 0: its first operand
+    size_t a_head, head_stride;      // the [1, 0] of a pow_mod_fixed_exp at advice cell a_head + i * head_stride
+    size_t a_res, l_res, res_stride; // block i at advice cell a_res + i * res_stride / lookup cell l_res + i * nf * rc_lk
+    size_t sum_n, in_ms, a_sum;      // ballot, sum_n >= 2: block 0 also writes FlexGate::sum of the sum_n one-word messages at in_ms
+};
+// FlexGate::sum's cells m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | .. ; s_pre: n prefix sums (below 2^74).  Every thread of the block calls it.
+__device__ __forceinline__ void flex_sum_cells(const u64* __restrict__ ms, size_t n, u64 (*s_pre)[2], const CellPtr& a) {
+    if (threadIdx.x == 0) {
+        U192 s = u_make(0);
+        for (size_t t = 0; t < n; ++t) {
+            s = u_add(s, u_make(ms[t]));
+            s_pre[t][0] = s.w[0]; s_pre[t][1] = s.w[1];
+        }
+    }
+    __syncthreads();
+    for (size_t t = threadIdx.x; t < 1 + 3 * (n - 1); t += blockDim.x) {
         Fr v;
-        if (t < nl) v = fr_from_u(u_make(s_x[t][0], s_x[t][1]));
-        else v = cv_to_fr(rc_adv_cell(u_make(s_x[(t - nl) / rc_adv][0], s_x[(t - nl) / rc_adv][1]), W, lb, (t - nl) % rc_adv));
+        if (t == 0) v = fr_from_u(u_make(ms[0]));
+        else {
+            const size_t m = (t - 1) / 3 + 1, w = (t - 1) % 3;
+            v = w == 0 ? fp_one<FrTag>() : w == 1 ? fr_from_u(u_make(ms[m])) : fr_from_u(LIMB(s_pre, m));
+        }
         fp_store(a + t, v);
     }
-    if (l)
-        for (unsigned t = tid; t < nl * rc_lk; t += blockDim.x)
-            fp_store(l + t, cv_to_fr(rc_lk_cell(u_make(s_x[t / rc_lk][0], s_x[t / rc_lk][1]), W, lb, t % rc_lk)));
+}
+// grid.x = entry.  Dynamic shared memory: 16 bytes per message of the ballot's sum (R.sum_n >= 2), none otherwise.
+__global__ __launch_bounds__(256) void k_circuit_results(CircP C, ResP R, const u64* __restrict__ inputs, const u64* __restrict__ steps,
+                                                         Fr* __restrict__ advice, Fr* __restrict__ lookup) {
+    __shared__ u64 s_res[CIRC_MAXF][2], s_c[CIRC_MAXF][2];
+    __shared__ unsigned char s_eq[CIRC_MAXF + 1];
+    extern __shared__ u64 s_pre[][2];
+    const size_t i = blockIdx.x;
+    if (threadIdx.x == 0) {
+        const CellPtr p = adv_ptr(C.e, advice, R.a_head + i * R.head_stride);
+        fp_store(p, fp_one<FrTag>());
+        fp_store(p + 1, fp_zero<FrTag>());
+    }
+    if (i == 0 && R.sum_n >= 2) flex_sum_cells(inputs + R.in_ms, R.sum_n, s_pre, adv_ptr(C.e, advice, R.a_sum));
+    result_block(C, inputs + R.in_res + i * R.in_stride, steps + ((R.rec0 + i * R.rec_stride) * 4 + R.field) * (size_t)C.e.L64, s_res, s_c, s_eq,
+                 adv_ptr(C.e, advice, R.a_res + i * R.res_stride), CellPtr{lookup, R.l_res + i * C.nf * C.rc_lk, C.e.rows, C.e.pad, nullptr, 0});
 }
 
 // ---- uniform-shape circuit: FlexGate::num_to_bits of the message's limbs and the limb-wise select after
 // every mul_mod(acc, sq) of pow_mod.  grid.x = limb of m (num_to_bits) / exponent bit (select).
 // cell t of num_to_bits(x, nbits): the inner product of the bits with the powers of two (1 + 3 (nbits - 1) cells), then assert_bit
 // of every bit ([0, b, b, b]) -- 7 nbits - 2 cells
+__host__ __device__ static inline size_t nbits_cells(size_t nbits) { return 7 * nbits - 2; }
 __device__ __forceinline__ Fr num_to_bits_cell(const U192& x, unsigned nbits, unsigned t) {
     const unsigned nip = 1 + 3 * (nbits - 1);
     if (t == 0) return fr_from_u(u_lowbits(x, 1));
@@ -905,7 +977,7 @@ __global__ __launch_bounds__(256) void k_circuit_bits(ExpP P, unsigned Ln, unsig
     limb_extract(m_words, words_n, li, W, lw);
     const U192 x = u_make(lw[0], lw[1]);
     const CellPtr a = adv_ptr(P, advice, cell_base + (size_t)li * limb_stride);
-    for (unsigned t = threadIdx.x; t < 7 * W - 2; t += blockDim.x) fp_store(a + t, num_to_bits_cell(x, W, t));
+    for (unsigned t = threadIdx.x; t < nbits_cells(W); t += blockDim.x) fp_store(a + t, num_to_bits_cell(x, W, t));
 }
 // the many-chain form (weighted tally, kind 4): grid.x = chain.  Chain i's exponent is the ONE word weights[i]; the block writes the
 // load_witness cell of w_i (a_wts + i) and, at cell_base + i * chain_stride, the chain's head: assign_constant(1), load_zero, then
@@ -920,7 +992,7 @@ __global__ __launch_bounds__(256) void k_circuit_bits_many(ExpP P, unsigned nbit
         fp_store(a, fp_one<FrTag>());
         fp_store(a + 1, fp_zero<FrTag>());
     }
-    for (unsigned t = threadIdx.x; t < 7 * nbits - 2; t += blockDim.x) fp_store(a + 2 + t, num_to_bits_cell(x, nbits, t));
+    for (unsigned t = threadIdx.x; t < nbits_cells(nbits); t += blockDim.x) fp_store(a + 2 + t, num_to_bits_cell(x, nbits, t));
 }
 // the limb-wise select(bit, muled, acc) after the mul_mod(acc, sq) step `st` (a = acc, r = muled): 8 cells per limb
 // [d | 1 | acc | muled | acc | bit | d | out], d = muled - acc
@@ -1019,6 +1091,67 @@ static int refresh_aux_host(unsigned W, unsigned nl, unsigned nr, unsigned char*
     return PZ_OK;
 }
 
+// ---- the parts every kind's parameter builder is made of
+// what all kinds start from: the mul_mod shape at 2 Ln limbs, n's word count, the range check of a limb, refresh's limb counts
+static int circ_base(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, unsigned kind, CircP& C) {
+    if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
+    memset(&C, 0, sizeof C);
+    PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
+    C.Ln = limbs_n;
+    C.kind = kind;
+    C.words_n = (limbs_n * limb_bits + 63) / 64;
+    C.rc_adv = C.e.rc64_adv;
+    C.rc_lk = C.e.rc64_lk;
+    PZCHK(refresh_aux_host(limb_bits, limbs_n, limbs_n, C.inc, &C.nf));
+    if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
+    return PZ_OK;
+}
+// cells of assign_integer(Ln limbs); a full-width integer (2 Ln limbs) takes twice as many
+static size_t asg_adv(const CircP& C) { return (size_t)C.Ln * (1 + C.rc_adv); }
+static size_t asg_lk(const CircP& C) { return (size_t)C.Ln * C.rc_lk; }
+// assert_equal_fresh of two integers of nf limbs
+static size_t equal_cells(size_t nf) { return 2 + 16 * nf; }
+// a result block: assign_integer(2 Ln limbs) + assert_equal_fresh
+static size_t res_cells(const CircP& C) { return 2 * asg_adv(C) + equal_cells(C.nf); }
+// the n_in Ln-limb inputs that head every stream
+static void assign_inputs(CircP& C, unsigned n_in, size_t& a, size_t& l) {
+    C.n_in = n_in;
+    for (unsigned k = 0; k < n_in; ++k) { C.a_assign[k] = a; C.l_assign[k] = l; a += asg_adv(C); l += asg_lk(C); }
+}
+static size_t square_cells(uint32_t limbs) {
+    size_t a = 1;
+    for (unsigned i = 0; i + 1 < 2 * limbs; ++i) a += 1 + 3 * ((size_t)i + 1);
+    return a;
+}
+static void refresh_cells(const unsigned char* inc, unsigned nf, unsigned rc_adv, unsigned rc_lk, size_t& a, size_t& l) {
+    a += 1;
+    for (unsigned i = 0; i < nf; ++i) a += ((size_t)inc[i] + 1) * 22 + (size_t)inc[i] * 4;
+    a += (size_t)nf * rc_adv;
+    l += (size_t)nf * rc_lk;
+}
+// square(n) and refresh at the running offsets (a, l), which move past them
+static void square_refresh_cells(CircP& C, size_t& a, size_t& l) {
+    C.a_square = a;
+    a += square_cells(C.Ln);
+    C.a_refresh = a; C.l_refresh = l;
+    refresh_cells(C.inc, C.nf, C.rc_adv, C.rc_lk, a, l);
+}
+// load_zero at the running offset
+static void load_zero_cell(CircP& C, size_t& a) {
+    C.has_zero = true;
+    C.a_zero = a;
+    a += 1;
+}
+// an exponent bit of a chain: mul_mod, select (8 cells per limb), square_mod
+static size_t bit_stride(const CircP& C) { return 2 * C.e.cells + 8 * (size_t)C.e.L; }
+// `count` result blocks at the running offsets, their res_i side by side from word in_res of `inputs`; the misc kernel writes none
+static void result_blocks(CircP& C, ResP& R, size_t count, size_t in_res, size_t& a, size_t& l) {
+    C.no_res = true;
+    R.in_res = in_res; R.in_stride = C.e.L64;
+    R.a_res = a; R.l_res = l; R.res_stride = res_cells(C);
+    a += count * R.res_stride; l += count * 2 * asg_lk(C);
+}
+
 static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t ng, size_t nr, CircP& C,
                                size_t* adv_total, size_t* lk_total, size_t step_off[3]) {
     if (kind < 0 || kind > 5) return PZ_ERR_INVALID;
@@ -1026,20 +1159,10 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
     if (kind == 3 && (ng < 1 || ng > 65535 || nr)) return PZ_ERR_INVALID;   // the tally of ng + 1 ciphertexts: ng mul_mod blocks
     // the weighted tally of B = nr + 1 ciphertexts: nr tree blocks, ng = 2 B W chain records
     if (kind == 4 && (nr > 65535 || ng == 0 || ng % (2 * (nr + 1)) || ng / (2 * (nr + 1)) > 64)) return PZ_ERR_INVALID;
-    if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
-    memset(&C, 0, sizeof C);
-    PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
-    C.Ln = limbs_n;
-    C.kind = (unsigned)kind;
-    C.words_n = (limbs_n * limb_bits + 63) / 64;
-    C.rc_adv = C.e.rc64_adv;
-    C.rc_lk = C.e.rc64_lk;
-    PZCHK(refresh_aux_host(limb_bits, limbs_n, limbs_n, C.inc, &C.nf));
-    if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
+    PZCHK(circ_base(limbs_n, limb_bits, lb, (unsigned)kind, C));
     size_t a = 0, l = 0;
-    const size_t asg_a = (size_t)limbs_n * (1 + C.rc_adv), asg_l = (size_t)limbs_n * C.rc_lk;
-    C.n_in = kind >= 3 ? 1 : 4;
-    for (unsigned k = 0; k < C.n_in; ++k) { C.a_assign[k] = a; C.l_assign[k] = l; a += asg_a; l += asg_l; }
+    const size_t asg_a = asg_adv(C), asg_l = asg_lk(C);
+    assign_inputs(C, kind >= 3 ? 1 : 4, a, l);
     C.res_off = 4 * (size_t)C.words_n;
     if (kind >= 3) {   // n | c_1 .. c_B | res: the ciphertexts are full-width integers (2 Ln limbs)
         C.n_cts = kind == 3 ? ng + 1 : nr + 1;
@@ -1053,16 +1176,9 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
             C.res_off += C.n_cts;
         }
     }
-    C.a_square = a;
-    a += 1;
-    for (unsigned i = 0; i < 2 * limbs_n - 1; ++i) a += 1 + 3 * ((size_t)i + 1);
-    C.a_refresh = a; C.l_refresh = l;
-    a += 1;
-    for (unsigned i = 0; i < C.nf; ++i) a += ((size_t)C.inc[i] + 1) * 22 + (size_t)C.inc[i] * 4;
-    a += (size_t)C.nf * C.rc_adv;
-    l += (size_t)C.nf * C.rc_lk;
+    square_refresh_cells(C, a, l);
     size_t lstep[3] = {0, 0, 0};
-    if (kind < 3) { C.a_zero = a; a += 1; }   // (the tallies extend nothing: no load_zero, no pow_mod_fixed_exp constants)
+    if (kind < 3) load_zero_cell(C, a);   // (the tallies extend nothing: no load_zero, no pow_mod_fixed_exp constants)
     if (kind == 0) {
         C.a_pow[0] = a; a += 2; step_off[0] = a; lstep[0] = l; a += ng * C.e.cells; l += ng * C.e.lookups;
         C.a_pow[1] = a; a += 2; step_off[1] = a; lstep[1] = l; a += nr * C.e.cells; l += nr * C.e.lookups;
@@ -1071,7 +1187,7 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
         const size_t m_bits = (size_t)limbs_n * limb_bits;
         if (ng != 2 * m_bits) return PZ_ERR_INVALID;
         C.a_pow[0] = a; a += 2; step_off[0] = a; lstep[0] = l;
-        a += (size_t)limbs_n * (7 * (size_t)limb_bits - 2) + m_bits * (2 * C.e.cells + 8 * (size_t)C.e.L);
+        a += (size_t)limbs_n * nbits_cells(limb_bits) + m_bits * bit_stride(C);
         l += ng * C.e.lookups;
         C.a_pow[1] = a; a += 2; step_off[1] = a; lstep[1] = l; a += nr * C.e.cells; l += nr * C.e.lookups;
     } else if (kind == 3) {   // the product tree's ng blocks, in record order; no further step
@@ -1081,16 +1197,14 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
         // HEAD (its [1, 0]); then the tree's nr blocks in record order
         const size_t W = C.w_bits;
         step_off[0] = a; lstep[0] = l;
-        a += C.n_cts * (2 + 7 * W - 2 + W * (2 * C.e.cells + 8 * (size_t)C.e.L));
+        a += C.n_cts * (2 + nbits_cells(W) + W * bit_stride(C));
         l += ng * C.e.lookups;
         step_off[1] = a; lstep[1] = l; a += nr * C.e.cells; l += nr * C.e.lookups;
     } else if (ng || nr) return PZ_ERR_INVALID;
     step_off[2] = a; lstep[2] = l;
     if (kind < 3) { a += C.e.cells; l += C.e.lookups; }
     C.a_res = a; C.l_res = l;
-    a += 2 * asg_a; l += 2 * asg_l;
-    C.a_eq = a;
-    a += 2 + 16 * (size_t)C.nf;
+    a += res_cells(C); l += 2 * asg_l;
     *adv_total = a;
     *lk_total = l;
     // step_off[0..2]: advice offsets of the three runs of mul_mod steps (g^m, r^n, final); [3..5]: their lookup offsets
@@ -1121,18 +1235,12 @@ extern "C" int pz_op_cells(int op, uint32_t limbs, uint32_t limb_bits, uint32_t 
     rc_counts(limb_bits, lookup_bits, k, rem, rc_a, rc_l);
     switch (op) {
         case 0: a = (size_t)limbs * (1 + rc_a); l = (size_t)limbs * rc_l; break;
-        case 1:
-            a = 1;
-            for (unsigned i = 0; i + 1 < 2 * limbs; ++i) a += 1 + 3 * ((size_t)i + 1);
-            break;
+        case 1: a = square_cells(limbs); break;
         case 2: {
             unsigned char inc[CIRC_MAXF];
             unsigned n = 0;
             PZCHK(refresh_aux_host(limb_bits, limbs, limbs, inc, &n));
-            a = 1;
-            for (unsigned i = 0; i < n; ++i) a += ((size_t)inc[i] + 1) * 22 + (size_t)inc[i] * 4;
-            a += (size_t)n * rc_a;
-            l = (size_t)n * rc_l;
+            refresh_cells(inc, n, rc_a, rc_l, a, l);
             break;
         }
         case 3: a = 1; break;
@@ -1143,22 +1251,18 @@ extern "C" int pz_op_cells(int op, uint32_t limbs, uint32_t limb_bits, uint32_t 
             l = P.lookups;
             break;
         }
-        case 5: a = 2 + 16 * (size_t)limbs; break;
+        case 5: a = equal_cells(limbs); break;
         default: return PZ_ERR_INVALID;
     }
-    if (advice_cells) *advice_cells = a;
-    if (lookup_cells) *lookup_cells = l;
-    return PZ_OK;
+    return put_cells(PZ_OK, a, l, advice_cells, lookup_cells);
 }
 
 extern "C" int pz_circuit_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g,
                                 size_t n_steps_r, size_t* advice_cells, size_t* lookup_cells) {
     CircP C;
     size_t a, l, so[6];
-    PZCHK(make_circuit_params(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, C, &a, &l, so));
-    if (advice_cells) *advice_cells = a;
-    if (lookup_cells) *lookup_cells = l;
-    return PZ_OK;
+    const int rc = make_circuit_params(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, C, &a, &l, so);
+    return put_cells(rc, a, l, advice_cells, lookup_cells);
 }
 
 // halo2-lib's column break rule (assign_with_constraints of the dependency [D]), from the selector mask of the advice stream: walking
@@ -1195,107 +1299,145 @@ extern "C" int pz_circuit_break_points(const uint8_t* gate_mask, size_t n_cells,
     return PZ_OK;
 }
 
-static int circuit_expand_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits,
-                               const uint64_t* inputs, const uint64_t* d_steps, size_t n_steps_g, size_t n_steps_r,
-                               const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride,
-                               const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows) {
-    if (!ctx || !inputs || !d_steps || !d_modulus || !d_advice) return PZ_ERR_INVALID;
+// ---- what every expansion entry point takes besides its kind's own counts, and the steps all of them open with
+struct ExpandArgs {
+    pz_ctx* ctx;
+    const uint64_t *inputs, *d_steps, *d_modulus;
+    uint64_t *d_advice, *d_lookup;
+    bool cols;                      // the break-point column form: d_col_starts is required and `rows` are the lookup columns' rows
+    size_t rows, col_stride;
+    const uint64_t* d_col_starts;
+    size_t n_adv_cols, max_rows;
+};
+// the refusals in front of the kind's parameter builder
+static int expand_check(const ExpandArgs& A) {
+    if (A.cols && (!A.d_col_starts || A.rows == 0 || A.rows > A.col_stride)) return PZ_ERR_INVALID;
+    if (!A.ctx || !A.inputs || !A.d_steps || !A.d_modulus || !A.d_advice) return PZ_ERR_INVALID;
+    if ((A.rows == 0) != (A.col_stride == 0) || A.col_stride < A.rows) return PZ_ERR_INVALID;
+    return PZ_OK;
+}
+// behind it: the column cut and the break points of the streams
+static int expand_layout(const ExpandArgs& A, CircP& C) {
+    C.e.rows = A.rows;
+    C.e.pad = A.col_stride - A.rows;
+    if (A.d_col_starts) {
+        if (A.n_adv_cols == 0 || A.n_adv_cols > 0xffffffffu || A.max_rows < 8 || A.max_rows > A.col_stride) return PZ_ERR_INVALID;
+        C.e.bp_starts = (const u64*)A.d_col_starts;
+        C.e.bp_ncols = (unsigned)A.n_adv_cols;
+        C.e.bp_div = A.max_rows - 1;
+        C.e.bp_stride = A.col_stride;
+    }
+    return PZ_OK;
+}
+// `inputs` (in_words words) and then `tail` (tail_bytes bytes; the mix's switch bits) to the device, behind the kind's own checks of
+// them.  `inputs` is the caller's (pageable) memory and may go away when the entry point returns: it goes through a pinned staging
+// block of the context, so the copy is truly asynchronous and reads nothing of the caller's afterwards.  Kinds 0 to 2: a few hundred
+// bytes.  Kind 3 carries the B ciphertexts (525 KB at B = 1024, 33 MB at B = 65536 for a 2048-bit key): one host memcpy of that size
+// per call, and the staging block grows to it once (grow-only, so a second tally of the size allocates nothing)
+static int expand_stage(const ExpandArgs& A, size_t in_words, const void* tail, size_t tail_bytes, const u64** d_in) {
+    void* d;
+    PZCHK(pz_ws_get(A.ctx, WS_MISC, in_words * 8 + tail_bytes + 64, &d));
+    PZCHK(pz_upload_small_async(A.ctx, d, A.inputs, in_words * 8));
+    if (tail_bytes) PZCHK(pz_upload_small_async(A.ctx, (char*)d + in_words * 8, tail, tail_bytes));
+    *d_in = (const u64*)d;
+    return PZ_OK;
+}
+// `chains` runs of n whole mul_mod blocks: run i starts at advice cell cell0 + i * chain_stride and expands the records
+// rec0 + i * rec_stride .. of `recs`; a block's lookups are numbered by its record, from lk0
+static void launch_runs(const ExpandArgs& A, const CircP& C, size_t cell0, size_t lk0, const u64* recs, size_t n, size_t chains = 1,
+                        size_t chain_stride = 0, size_t rec_stride = 0, size_t rec0 = 0) {
+    ExpP Q = C.e;
+    Q.cell0 = cell0;
+    Q.lk0 = lk0;
+    if (rec_stride) { Q.chain_steps = n; Q.chain_stride = chain_stride; Q.chain_recs = rec_stride; Q.rec0 = rec0; }   // (else: one dense run)
+    hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(chains * n)), dim3(EXP_THREADS), 0, A.ctx->stream, Q, recs, (const u64*)A.d_modulus,
+                       (Fr*)A.d_advice, (Fr*)A.d_lookup);
+}
+// the (mul_mod, square_mod) record pairs of `chains` exponent chains of nbits bits: chain i's num_to_bits block stands at advice cell
+// a_bits + i * chain_stride, its 2 nbits records from record i * rec_stride of `recs` on
+static void launch_chains(const ExpandArgs& A, const CircP& C, size_t a_bits, size_t lk0, const u64* recs, size_t nbits, size_t chains,
+                          size_t chain_stride, size_t rec_stride) {
+    ExpP Q = C.e;
+    Q.cell0 = a_bits + nbits_cells(nbits);
+    Q.lk0 = lk0;
+    Q.pair_stride = bit_stride(C);
+    Q.odd_off = C.e.cells + 8 * (size_t)C.e.L;   // the square_mod of a pair: behind the mul_mod and the select
+    Q.chain_steps = 2 * nbits;
+    Q.chain_stride = chain_stride;
+    Q.chain_recs = rec_stride;
+    hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(chains * 2 * nbits)), dim3(EXP_THREADS), 0, A.ctx->stream, Q, recs,
+                       (const u64*)A.d_modulus, (Fr*)A.d_advice, (Fr*)A.d_lookup);
+}
+// a run of `count` assign_integer blocks of nl limbs each, the integers `words` words apart from word in_off of the staged inputs
+static void launch_assign(const ExpandArgs& A, const CircP& C, const u64* in, size_t in_off, unsigned nl, unsigned words, size_t count, size_t a0,
+                          size_t l0) {
+    hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)count), dim3(256), 0, A.ctx->stream, C, nl, words, in + in_off, a0, l0, (Fr*)A.d_advice,
+                       (Fr*)A.d_lookup);
+}
+// `count` result blocks with their heads (ResP); the ballot's sum takes 16 bytes of shared memory per message
+static void launch_results(const ExpandArgs& A, const CircP& C, const ResP& R, size_t count, const u64* in, const u64* recs) {
+    hipLaunchKernelGGL(k_circuit_results, dim3((unsigned)count), dim3(256), R.sum_n >= 2 ? R.sum_n * 16 : 0, A.ctx->stream, C, R, in, recs,
+                       (Fr*)A.d_advice, (Fr*)A.d_lookup);
+}
+
+// ---- the by-kind circuits (kinds 0 .. 5): one result, written by k_circuit_misc.  Kind 2 (and 5): g^m as an exponent chain per limb of m;
+// kind 3: B full-width ciphertexts and the product tree's blocks; kind 4: a one-word weight and a chain per ciphertext, then the tree
+static int circuit_expand_impl(const ExpandArgs& A, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g,
+                               size_t n_steps_r) {
+    PZCHK(expand_check(A));
     if (kind == 5) kind = 2;   // the same cells from the same records (make_circuit_params)
-    if ((rows == 0) != (col_stride == 0) || col_stride < rows) return PZ_ERR_INVALID;
     CircP C;
     size_t a, l, so[6];
     PZCHK(make_circuit_params(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, C, &a, &l, so));
-    C.e.rows = rows;
-    C.e.pad = col_stride - rows;
-    if (d_col_starts) {
-        if (n_adv_cols == 0 || n_adv_cols > 0xffffffffu || max_rows < 8 || max_rows > col_stride) return PZ_ERR_INVALID;
-        C.e.bp_starts = (const u64*)d_col_starts;
-        C.e.bp_ncols = (unsigned)n_adv_cols;
-        C.e.bp_div = max_rows - 1;
-        C.e.bp_stride = col_stride;
-    }
-    PZ_ENTER(ctx);
-    const size_t in_words = C.res_off + C.e.L64;
-    void* d_in;
-    PZCHK(pz_ws_get(ctx, WS_MISC, in_words * 8 + 64, &d_in));
-    // `inputs` is the caller's (pageable) memory and may go away when this returns: it goes through a pinned staging block of the
-    // context, so the copy is truly asynchronous and reads nothing of the caller's afterwards.  Kinds 0 to 2: a few hundred bytes.
-    // Kind 3 carries the B ciphertexts (525 KB at B = 1024, 33 MB at B = 65536 for a 2048-bit key): one host memcpy of that size per
-    // call, and the staging block grows to it once (grow-only, so a second tally of the size allocates nothing)
-    const u64* wts = kind == 4 ? inputs + C.res_off - C.n_cts : nullptr;   // the weights, one word each, in front of res
+    PZCHK(expand_layout(A, C));
+    const u64* wts = kind == 4 ? A.inputs + C.res_off - C.n_cts : nullptr;   // the weights, one word each, in front of res
     if (kind == 4 && C.w_bits < 64)
         for (size_t i = 0; i < C.n_cts; ++i)
             if (wts[i] >> C.w_bits) return PZ_ERR_MESSAGE_RANGE;   // num_to_bits of such a weight cannot hold
-    PZCHK(pz_upload_small_async(ctx, d_in, inputs, in_words * 8));
+    pz_ctx* ctx = A.ctx;
+    PZ_ENTER(ctx);
+    const u64* in;
+    PZCHK(expand_stage(A, C.res_off + C.e.L64, nullptr, 0, &in));
     pz_timer tm(ctx, PZ_T_EXPAND);
+    const u64* d_steps = A.d_steps;
+    Fr* adv = (Fr*)A.d_advice;
     const size_t rec = 4 * (size_t)C.e.L64;   // words per step record
     const size_t runs[3] = {kind != 1 ? n_steps_g : 0, kind != 1 ? n_steps_r : 0, kind < 3 ? (size_t)1 : 0};
     size_t first = 0;
-    for (int k = 0; k < 3; ++k) {
-        if (runs[k]) {
-            ExpP P = C.e;
-            P.cell0 = so[k];
-            P.lk0 = so[3 + k];
-            if (kind == 2 && k == 0) {
-                // the g^m steps come in (mul_mod, square_mod) pairs with the select cells in between and a num_to_bits block
-                // in front of every limb's 64 bits: launch limb by limb
-                const size_t W = limb_bits, nbc = 7 * W - 2, bit_stride = 2 * C.e.cells + 8 * (size_t)C.e.L;
-                const size_t limb_stride = nbc + W * bit_stride;
-                hipLaunchKernelGGL(k_circuit_bits, dim3(limbs_n), dim3(256), 0, ctx->stream, C.e, limbs_n, C.words_n,
-                                   (const u64*)d_in + 2 * (size_t)C.words_n, so[0], limb_stride, (Fr*)d_advice);
-                hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)(limbs_n * W)), dim3(256), 0, ctx->stream, C.e, limbs_n, C.words_n,
-                                   (const u64*)d_in + 2 * (size_t)C.words_n, d_steps, so[0], limb_stride, bit_stride, nbc, (Fr*)d_advice);
-                for (unsigned li = 0; li < limbs_n; ++li) {
-                    ExpP Q = P;
-                    Q.cell0 = so[0] + li * limb_stride + nbc;
-                    Q.lk0 = so[3] + (size_t)li * 2 * W * C.e.lookups;
-                    Q.pair_stride = bit_stride;
-                    Q.odd_off = C.e.cells + 8 * (size_t)C.e.L;
-                    hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(2 * W)), dim3(EXP_THREADS), 0, ctx->stream, Q,
-                                       d_steps + (size_t)li * 2 * W * rec, d_modulus, (Fr*)d_advice, (Fr*)d_lookup);
-                }
-                first += runs[k];
-                continue;
-            }
-            if (kind == 4 && k == 0) {
-                // the chains: every chain is [1, 0 | num_to_bits(w_i) | W x (mul_mod, select, square_mod)], chain_stride cells apart;
-                // one launch each for the heads, the selects and the 2 B W steps, whatever B is
-                const size_t W = C.w_bits, head = 2 + 7 * W - 2, bit_stride = 2 * C.e.cells + 8 * (size_t)C.e.L;
-                const size_t chain_stride = head + W * bit_stride;
-                const u64* d_w = (const u64*)d_in + C.res_off - C.n_cts;
-                hipLaunchKernelGGL(k_circuit_bits_many, dim3((unsigned)C.n_cts), dim3(256), 0, ctx->stream, C.e, (unsigned)W, d_w, C.a_wts, so[0],
-                                   chain_stride, (Fr*)d_advice);
-                hipLaunchKernelGGL(k_circuit_select_many, dim3((unsigned)(C.n_cts * W)), dim3(256), 0, ctx->stream, C.e, (unsigned)W, d_w, d_steps,
-                                   2 * W, so[0], chain_stride, bit_stride, head, (Fr*)d_advice);
-                ExpP Q = P;
-                Q.cell0 = so[0] + head;
-                Q.pair_stride = bit_stride;
-                Q.odd_off = C.e.cells + 8 * (size_t)C.e.L;
-                Q.chain_steps = 2 * W;
-                Q.chain_stride = chain_stride;
-                hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)runs[0]), dim3(EXP_THREADS), 0, ctx->stream, Q, d_steps, d_modulus,
-                                   (Fr*)d_advice, (Fr*)d_lookup);
-                first += runs[k];
-                continue;
-            }
-            hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)runs[k]), dim3(EXP_THREADS), 0, ctx->stream, P, d_steps + first * rec,
-                               d_modulus, (Fr*)d_advice, (Fr*)d_lookup);
-        }
-        first += runs[k];
+    for (int k = 0; k < 3; first += runs[k], ++k) {
+        if (!runs[k]) continue;
+        if (kind == 2 && k == 0) {
+            // a num_to_bits block in front of every limb's W bits: the pairs are launched limb by limb
+            const size_t W = limb_bits, limb_stride = nbits_cells(W) + W * bit_stride(C);
+            const u64* d_m = in + 2 * (size_t)C.words_n;
+            hipLaunchKernelGGL(k_circuit_bits, dim3(limbs_n), dim3(256), 0, ctx->stream, C.e, limbs_n, C.words_n, d_m, so[0], limb_stride, adv);
+            hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)(limbs_n * W)), dim3(256), 0, ctx->stream, C.e, limbs_n, C.words_n, d_m, d_steps, so[0],
+                               limb_stride, bit_stride(C), nbits_cells(W), adv);
+            for (unsigned li = 0; li < limbs_n; ++li)
+                launch_chains(A, C, so[0] + li * limb_stride, so[3] + (size_t)li * 2 * W * C.e.lookups, d_steps + (size_t)li * 2 * W * rec, W, 1, 0,
+                              2 * W);
+        } else if (kind == 4 && k == 0) {
+            // step_off[0] is the first chain's [1, 0]; one launch each for the heads, the selects and the 2 B W records, whatever B is
+            const size_t W = C.w_bits, head = 2 + nbits_cells(W), chain_stride = head + W * bit_stride(C);
+            const u64* d_w = in + C.res_off - C.n_cts;
+            hipLaunchKernelGGL(k_circuit_bits_many, dim3((unsigned)C.n_cts), dim3(256), 0, ctx->stream, C.e, (unsigned)W, d_w, C.a_wts, so[0],
+                               chain_stride, adv);
+            hipLaunchKernelGGL(k_circuit_select_many, dim3((unsigned)(C.n_cts * W)), dim3(256), 0, ctx->stream, C.e, (unsigned)W, d_w, d_steps,
+                               2 * W, so[0], chain_stride, bit_stride(C), head, adv);
+            launch_chains(A, C, so[0] + 2, so[3], d_steps, W, C.n_cts, chain_stride, 2 * W);
+        } else
+            launch_runs(A, C, so[k], so[3 + k], d_steps + first * rec, runs[k]);
     }
-    if (kind >= 3)
-        hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)C.n_cts), dim3(256), 0, ctx->stream, C.e, C.nf, C.rc_adv, C.rc_lk,
-                           (const u64*)d_in + C.words_n, C.a_cts, C.l_cts, (Fr*)d_advice, (Fr*)d_lookup);
+    if (kind >= 3) launch_assign(A, C, in, C.words_n, C.nf, C.e.L64, C.n_cts, C.a_cts, C.l_cts);
     // the circuit's result c = remainder of the last step (the final mul_mod; the tally's root)
-    const uint64_t* d_c = d_steps + (first - 1) * rec + 3 * (size_t)C.e.L64;
+    const u64* d_c = d_steps + (first - 1) * rec + 3 * (size_t)C.e.L64;
     if (kind == 4 && C.n_cts == 1) {
         // one ciphertext has no tree: the result is the chain's last select output -- the product of the last (acc, sq) step where the
         // weight's top bit is set, its acc otherwise
         const bool top = (wts[0] >> (C.w_bits - 1)) & 1;
         d_c = d_steps + (n_steps_g - 2) * rec + (top ? 3 : 0) * (size_t)C.e.L64;
     }
-    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, (const u64*)d_in, (const u64*)d_c, (Fr*)d_advice,
-                       (Fr*)d_lookup);
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, d_c, adv, (Fr*)A.d_lookup);
     HIPCHK(ctx, hipGetLastError());
     return PZ_OK;
 }
@@ -1304,151 +1446,56 @@ extern "C" int pz_circuit_expand_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, ui
                                      const uint64_t* inputs, const uint64_t* d_steps, size_t n_steps_g, size_t n_steps_r,
                                      const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows,
                                      size_t col_stride) {
-    return circuit_expand_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, inputs, d_steps, n_steps_g, n_steps_r, d_modulus, d_advice,
-                               d_lookup, rows, col_stride, nullptr, 0, 0);
+    return circuit_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, false, rows, col_stride, nullptr, 0, 0}, kind, limbs_n,
+                               limb_bits, lookup_bits, n_steps_g, n_steps_r);
 }
 extern "C" int pz_circuit_expand_cols_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits,
                                           const uint64_t* inputs, const uint64_t* d_steps, size_t n_steps_g, size_t n_steps_r,
                                           const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup,
                                           const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows, size_t lookup_rows,
                                           size_t col_stride) {
-    if (!d_col_starts || lookup_rows == 0 || lookup_rows > col_stride) return PZ_ERR_INVALID;
-    return circuit_expand_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, inputs, d_steps, n_steps_g, n_steps_r, d_modulus, d_advice,
-                               d_lookup, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows);
+    return circuit_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, true, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows},
+                               kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r);
 }
 
 // ---- the ballot (circuit kind 6): K ciphertexts under one key.  Stream: assign n, g; load_witness(m_1 .. m_K);
-// K >= 2: FlexGate::sum (1 + 3 (K - 1) cells); assign r_1 .. r_K; square + refresh, load_zero; per entry [1, 0 | num_to_bits(m_i, b) |
-// b x (mul_mod, select, square_mod) | 1, 0 | nr x mul_mod | mul_mod]; per entry assign res_i (2 Ln limbs) + assert_equal_fresh.
+// K >= 2: FlexGate::sum (1 + 3 (K - 1) cells); assign r_1 .. r_K; square + refresh, load_zero; per entry [the chain of m_i, b bits |
+// 1, 0 | nr x mul_mod | mul_mod]; per entry a result block (res_i against the remainder of the entry's last record).
 // inputs: n | g | m_1 .. m_K (one word each) | r_1 .. r_K | res_1 .. res_K.  Records: entry-major, 2 b + nr + 1 each.
 #define BALLOT_MAX 1024
 struct BallotP {
-    size_t K, per, a_msgs, a_sum, a_rs, l_rs, a_ent, l_ent, ent_stride, head, bit_stride, a_res, l_res, res_stride;
-    size_t in_ms, in_rs, in_res;   // word offsets inside `inputs`
-    unsigned b, nr;
+    size_t K, per, a_msgs, a_rs, l_rs, a_ent, l_ent, ent_stride, head;
+    size_t in_ms, in_rs;   // word offsets inside `inputs`
+    ResP res;              // with the sum: block 0 of k_circuit_results writes it
 };
 static int make_ballot_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, uint32_t m_bits, size_t n_steps_r, CircP& C,
                               BallotP& B, size_t* adv_total, size_t* lk_total) {
     if (count < 1 || count > BALLOT_MAX || m_bits < 1 || m_bits > 64 || n_steps_r < 1 || n_steps_r > 0x7fffffffu) return PZ_ERR_INVALID;
-    if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
-    memset(&C, 0, sizeof C);
+    PZCHK(circ_base(limbs_n, limb_bits, lb, 6, C));
     memset(&B, 0, sizeof B);
-    PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
-    C.Ln = limbs_n;
-    C.kind = 6;
-    C.words_n = (limbs_n * limb_bits + 63) / 64;
-    C.rc_adv = C.e.rc64_adv;
-    C.rc_lk = C.e.rc64_lk;
-    PZCHK(refresh_aux_host(limb_bits, limbs_n, limbs_n, C.inc, &C.nf));
-    if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
-    B.K = count; B.b = m_bits; B.nr = (unsigned)n_steps_r;
+    B.K = count;
     B.per = 2 * (size_t)m_bits + n_steps_r + 1;
-    size_t a = 0, l = 0;
-    const size_t asg_a = (size_t)limbs_n * (1 + C.rc_adv), asg_l = (size_t)limbs_n * C.rc_lk;
-    C.n_in = 2;
-    for (unsigned k = 0; k < 2; ++k) { C.a_assign[k] = a; C.l_assign[k] = l; a += asg_a; l += asg_l; }
-    B.a_msgs = a; a += count;
-    B.a_sum = a; a += count >= 2 ? 1 + 3 * (count - 1) : 0;
-    B.a_rs = a; B.l_rs = l; a += count * asg_a; l += count * asg_l;
-    C.a_square = a;
-    a += 1;
-    for (unsigned i = 0; i < 2 * limbs_n - 1; ++i) a += 1 + 3 * ((size_t)i + 1);
-    C.a_refresh = a; C.l_refresh = l;
-    a += 1;
-    for (unsigned i = 0; i < C.nf; ++i) a += ((size_t)C.inc[i] + 1) * 22 + (size_t)C.inc[i] * 4;
-    a += (size_t)C.nf * C.rc_adv;
-    l += (size_t)C.nf * C.rc_lk;
-    C.a_zero = a; a += 1;
-    B.head = 2 + 7 * (size_t)m_bits - 2;
-    B.bit_stride = 2 * C.e.cells + 8 * (size_t)C.e.L;
-    B.ent_stride = B.head + m_bits * B.bit_stride + 2 + (n_steps_r + 1) * C.e.cells;
-    B.a_ent = a; B.l_ent = l;
-    a += count * B.ent_stride; l += count * B.per * C.e.lookups;
-    B.res_stride = 2 * asg_a + 2 + 16 * (size_t)C.nf;
-    B.a_res = a; B.l_res = l;
-    a += count * B.res_stride; l += count * 2 * asg_l;
     B.in_ms = 2 * (size_t)C.words_n;
     B.in_rs = B.in_ms + count;
-    B.in_res = B.in_rs + count * C.words_n;
-    C.res_off = B.in_res;   // (k_circuit_misc reads a result it does not write for this kind: res_1, valid memory)
+    size_t a = 0, l = 0;
+    assign_inputs(C, 2, a, l);
+    B.a_msgs = a; a += count;
+    B.res.sum_n = count; B.res.in_ms = B.in_ms;
+    B.res.a_sum = a; a += count >= 2 ? 1 + 3 * (count - 1) : 0;
+    B.a_rs = a; B.l_rs = l; a += count * asg_adv(C); l += count * asg_lk(C);
+    square_refresh_cells(C, a, l);
+    load_zero_cell(C, a);
+    B.head = 2 + nbits_cells(m_bits);
+    B.ent_stride = B.head + m_bits * bit_stride(C) + 2 + (n_steps_r + 1) * C.e.cells;
+    B.a_ent = a; B.l_ent = l;
+    a += count * B.ent_stride; l += count * B.per * C.e.lookups;
+    // the [1, 0] of r_i^n stands behind the g-chain
+    B.res.a_head = B.a_ent + B.head + m_bits * bit_stride(C); B.res.head_stride = B.ent_stride;
+    B.res.rec0 = B.per - 1; B.res.rec_stride = B.per; B.res.field = 3;
+    result_blocks(C, B.res, count, B.in_rs + count * C.words_n, a, l);
     *adv_total = a;
     *lk_total = l;
     return PZ_OK;
-}
-// grid.x = entry i: the [1, 0] of its pow_mod_fixed_exp, assign_integer(res_i) and assert_equal_fresh(c_i, res_i), c_i the remainder of the
-// entry's last record; block 0 also writes FlexGate::sum's cells m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..
-__global__ __launch_bounds__(256) void k_ballot_misc(CircP C, BallotP B, const u64* __restrict__ inputs, const u64* __restrict__ steps,
-                                                     Fr* __restrict__ advice, Fr* __restrict__ lookup) {
-    __shared__ u64 s_res[CIRC_MAXF][2], s_c[CIRC_MAXF][2];
-    __shared__ u64 s_pre[BALLOT_MAX][2];     // prefix sums of the messages (below 2^74)
-    __shared__ unsigned char s_eq[CIRC_MAXF + 1];
-    const size_t i = blockIdx.x;
-    const unsigned nf = C.nf, W = C.e.W, lb = C.e.lb, tid = threadIdx.x;
-    const u64* cval = steps + (i * B.per + B.per - 1) * 4 * (size_t)C.e.L64 + 3 * (size_t)C.e.L64;
-#define LIMB(X, i) u_make((X)[i][0], (X)[i][1])
-    for (unsigned t = tid; t < nf; t += blockDim.x) {
-        limb_extract(inputs + B.in_res + i * C.e.L64, C.e.L64, t, W, s_res[t]);
-        limb_extract(cval, C.e.L64, t, W, s_c[t]);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned eq = 1;
-        s_eq[0] = 1;
-        for (unsigned t = 0; t < nf; ++t) {
-            eq &= u_eq(LIMB(s_c, t), LIMB(s_res, t)) ? 1u : 0u;
-            s_eq[t + 1] = (unsigned char)eq;
-        }
-        if (i == 0 && B.K >= 2) {
-            U192 s = u_make(0);
-            for (size_t t = 0; t < B.K; ++t) {
-                s = u_add(s, u_make(inputs[B.in_ms + t]));
-                s_pre[t][0] = s.w[0]; s_pre[t][1] = s.w[1];
-            }
-        }
-        const CellPtr p = adv_ptr(C.e, advice, B.a_ent + i * B.ent_stride + B.head + B.b * B.bit_stride);
-        fp_store(p, fp_one<FrTag>());
-        fp_store(p + 1, fp_zero<FrTag>());
-    }
-    __syncthreads();
-    if (i == 0 && B.K >= 2) {
-        const CellPtr a = adv_ptr(C.e, advice, B.a_sum);
-        for (size_t t = tid; t < 1 + 3 * (B.K - 1); t += blockDim.x) {
-            Fr v;
-            if (t == 0) v = fr_from_u(u_make(inputs[B.in_ms]));
-            else {
-                const size_t m = (t - 1) / 3 + 1, w = (t - 1) % 3;
-                v = w == 0 ? fp_one<FrTag>() : w == 1 ? fr_from_u(u_make(inputs[B.in_ms + m])) : fr_from_u(LIMB(s_pre, m));
-            }
-            fp_store(a + t, v);
-        }
-    }
-    const CellPtr a = adv_ptr(C.e, advice, B.a_res + i * B.res_stride);
-    const CellPtr l{lookup, B.l_res + i * nf * C.rc_lk, C.e.rows, C.e.pad, nullptr, 0};
-    for (unsigned t = tid; t < nf * (1 + C.rc_adv); t += blockDim.x) {
-        Fr v;
-        if (t < nf) v = fr_from_u(LIMB(s_res, t));
-        else v = cv_to_fr(rc_adv_cell(LIMB(s_res, (t - nf) / C.rc_adv), W, lb, (t - nf) % C.rc_adv));
-        fp_store(a + t, v);
-    }
-    if (l)
-        for (unsigned t = tid; t < nf * C.rc_lk; t += blockDim.x) fp_store(l + t, cv_to_fr(rc_lk_cell(LIMB(s_res, t / C.rc_lk), W, lb, t % C.rc_lk)));
-    const CellPtr e = a + (size_t)nf * (1 + C.rc_adv);
-    if (tid == 0) {
-        fp_store(e, fp_zero<FrTag>());
-        fp_store(e + 1, fp_one<FrTag>());
-    }
-    for (unsigned t = tid; t < 16 * nf; t += blockDim.x) {
-        const unsigned j = t / 16, p = t % 16;
-        Fr v;
-        if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, j), LIMB(s_res, j), p));
-        else {
-            const unsigned eq = u_eq(LIMB(s_c, j), LIMB(s_res, j)) ? 1u : 0u, in = s_eq[j], out = s_eq[j + 1];
-            v = p == 12 ? fp_zero<FrTag>() : p == 13 ? (in ? fp_one<FrTag>() : fp_zero<FrTag>())
-                : p == 14 ? (eq ? fp_one<FrTag>() : fp_zero<FrTag>()) : (out ? fp_one<FrTag>() : fp_zero<FrTag>());
-        }
-        fp_store(e + 2 + t, v);
-    }
-#undef LIMB
 }
 
 extern "C" int pz_ballot_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
@@ -1456,207 +1503,97 @@ extern "C" int pz_ballot_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lo
     CircP C;
     BallotP B;
     size_t a, l;
-    PZCHK(make_ballot_params(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, C, B, &a, &l));
-    if (advice_cells) *advice_cells = a;
-    if (lookup_cells) *lookup_cells = l;
-    return PZ_OK;
+    const int rc = make_ballot_params(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, C, B, &a, &l);
+    return put_cells(rc, a, l, advice_cells, lookup_cells);
 }
 
-static int ballot_expand_impl(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
-                              size_t n_steps_r, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice,
-                              uint64_t* d_lookup, size_t rows, size_t col_stride, const uint64_t* d_col_starts, size_t n_adv_cols,
-                              size_t max_rows) {
-    if (!ctx || !inputs || !d_steps || !d_modulus || !d_advice) return PZ_ERR_INVALID;
-    if ((rows == 0) != (col_stride == 0) || col_stride < rows) return PZ_ERR_INVALID;
+static int ballot_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                              size_t n_steps_r) {
+    PZCHK(expand_check(A));
     CircP C;
     BallotP B;
     size_t a, l;
     PZCHK(make_ballot_params(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, C, B, &a, &l));
-    C.e.rows = rows;
-    C.e.pad = col_stride - rows;
-    if (d_col_starts) {
-        if (n_adv_cols == 0 || n_adv_cols > 0xffffffffu || max_rows < 8 || max_rows > col_stride) return PZ_ERR_INVALID;
-        C.e.bp_starts = (const u64*)d_col_starts;
-        C.e.bp_ncols = (unsigned)n_adv_cols;
-        C.e.bp_div = max_rows - 1;
-        C.e.bp_stride = col_stride;
-    }
+    PZCHK(expand_layout(A, C));
     if (m_bits < 64)
         for (size_t i = 0; i < count; ++i)
-            if (inputs[B.in_ms + i] >> m_bits) return PZ_ERR_MESSAGE_RANGE;   // num_to_bits of such a message cannot hold
+            if (A.inputs[B.in_ms + i] >> m_bits) return PZ_ERR_MESSAGE_RANGE;   // num_to_bits of such a message cannot hold
+    pz_ctx* ctx = A.ctx;
     PZ_ENTER(ctx);
-    const size_t in_words = B.in_res + count * C.e.L64;
-    void* d_in;
-    PZCHK(pz_ws_get(ctx, WS_MISC, in_words * 8 + 64, &d_in));
-    PZCHK(pz_upload_small_async(ctx, d_in, inputs, in_words * 8));
+    const u64* in;
+    PZCHK(expand_stage(A, B.res.in_res + count * C.e.L64, nullptr, 0, &in));
     pz_timer tm(ctx, PZ_T_EXPAND);
-    const u64* in = (const u64*)d_in;
-    Fr *adv = (Fr*)d_advice, *lk = (Fr*)d_lookup;
-    // n, g, square, refresh, load_zero (the first record's remainder stands in for the result this kind does not write there)
-    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, d_steps + 3 * (size_t)C.e.L64, adv, lk);
+    const u64* d_steps = A.d_steps;
+    Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
+    // n, g, square, refresh, load_zero
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, (const u64*)nullptr, adv, lk);
     // assign_integer(r_i): Ln limbs from words_n words each
-    ExpP R = C.e;
-    R.L64 = C.words_n;
-    hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)count), dim3(256), 0, ctx->stream, R, C.Ln, C.rc_adv, C.rc_lk, in + B.in_rs, B.a_rs,
-                       B.l_rs, adv, lk);
+    launch_assign(A, C, in, B.in_rs, C.Ln, C.words_n, count, B.a_rs, B.l_rs);
     // per entry: the load_witness cell and the chain's head; the selects; the g-chain's record pairs; the r-chain's and the final record
     hipLaunchKernelGGL(k_circuit_bits_many, dim3((unsigned)count), dim3(256), 0, ctx->stream, C.e, m_bits, in + B.in_ms, B.a_msgs, B.a_ent,
                        B.ent_stride, adv);
     hipLaunchKernelGGL(k_circuit_select_many, dim3((unsigned)(count * m_bits)), dim3(256), 0, ctx->stream, C.e, m_bits, in + B.in_ms, d_steps,
-                       B.per, B.a_ent, B.ent_stride, B.bit_stride, B.head, adv);
-    ExpP Q = C.e;
-    Q.cell0 = B.a_ent + B.head;
-    Q.lk0 = B.l_ent;
-    Q.pair_stride = B.bit_stride;
-    Q.odd_off = C.e.cells + 8 * (size_t)C.e.L;
-    Q.chain_steps = 2 * (size_t)m_bits;
-    Q.chain_stride = B.ent_stride;
-    Q.chain_recs = B.per;
-    hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(count * Q.chain_steps)), dim3(EXP_THREADS), 0, ctx->stream, Q, d_steps, d_modulus, adv, lk);
-    ExpP T = C.e;
-    T.cell0 = B.a_ent + B.head + m_bits * B.bit_stride + 2;
-    T.lk0 = B.l_ent;
-    T.chain_steps = n_steps_r + 1;
-    T.chain_stride = B.ent_stride;
-    T.chain_recs = B.per;
-    T.rec0 = 2 * (size_t)m_bits;
-    hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(count * T.chain_steps)), dim3(EXP_THREADS), 0, ctx->stream, T, d_steps, d_modulus, adv, lk);
-    hipLaunchKernelGGL(k_ballot_misc, dim3((unsigned)count), dim3(256), 0, ctx->stream, C, B, in, d_steps, adv, lk);
+                       B.per, B.a_ent, B.ent_stride, bit_stride(C), B.head, adv);
+    launch_chains(A, C, B.a_ent + 2, B.l_ent, d_steps, m_bits, count, B.ent_stride, B.per);
+    launch_runs(A, C, B.res.a_head + 2, B.l_ent, d_steps, n_steps_r + 1, count, B.ent_stride, B.per, 2 * (size_t)m_bits);
+    launch_results(A, C, B.res, count, in, d_steps);
     HIPCHK(ctx, hipGetLastError());
     return PZ_OK;
 }
 extern "C" int pz_ballot_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
                                     size_t n_steps_r, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus,
                                     uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride) {
-    return ballot_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, inputs, d_steps, d_modulus, d_advice, d_lookup,
-                              rows, col_stride, nullptr, 0, 0);
+    return ballot_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, false, rows, col_stride, nullptr, 0, 0}, limbs_n, limb_bits,
+                              lookup_bits, count, m_bits, n_steps_r);
 }
 extern "C" int pz_ballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
                                          size_t n_steps_r, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus,
                                          uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts, size_t n_adv_cols,
                                          size_t max_rows, size_t lookup_rows, size_t col_stride) {
-    if (!d_col_starts || lookup_rows == 0 || lookup_rows > col_stride) return PZ_ERR_INVALID;
-    return ballot_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, inputs, d_steps, d_modulus, d_advice, d_lookup,
-                              lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows);
+    return ballot_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, true, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows},
+                              limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r);
 }
 
 // ---- a trustee's partial decryptions (circuit kind 7): K ciphertexts opened under ONE share theta.  Stream:
 // assign n; assign v, theta, c_1 .. c_K at full width; square + refresh, load_zero; chain 0 = pow_mod(v, theta) as kind 2 emits it
-// ([1, 0], then per limb of theta num_to_bits and W x (mul_mod, select, square_mod)) over ALL 2 Ln limbs; per ciphertext the block
-// mul_mod(c_j, c_j) and chain j = pow_mod(s_j, theta); then assign h + assert_equal_fresh and the same for every u_j.
+// ([1, 0], then per limb of theta a chain of W bits) over ALL 2 Ln limbs; per ciphertext the block mul_mod(c_j, c_j) and chain j =
+// pow_mod(s_j, theta); then K + 1 result blocks: h, u_1 .. u_K against the chains' results, each taken from its chain's last
+// (acc, sq) record -- the product where theta's top bit is set, the accumulator otherwise.
 // inputs: n | v | theta | c_1 .. c_K | h | u_1 .. u_K.  Records (pz_paillier_partial_dev): the K squarings, then chain i at K + i 2 E,
 // E = 2 Ln W bits.  Lookups follow the STREAM: chain 0's, then per ciphertext its squaring's and its chain's.
 #define PARTIAL_MAX 1024
 struct PartialP {
-    size_t K, E, a_wide, l_wide, a_ch, l_ch, nbc, bit_stride, limb_stride, chain_cells, a_res, l_res, res_stride;
-    size_t in_v, in_theta, in_cts, in_res;   // word offsets inside `inputs`
-    unsigned top;                            // theta's bit E - 1: a chain's result is its last product (1) or its last accumulator (0)
+    size_t K, E, a_wide, l_wide, a_ch, l_ch, limb_stride, chain_cells;
+    size_t in_v, in_theta;   // word offsets inside `inputs`
+    ResP res;
 };
 static int make_partial_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, CircP& C, PartialP& B, size_t* adv_total,
                                size_t* lk_total) {
     if (count < 1 || count > PARTIAL_MAX) return PZ_ERR_INVALID;
-    if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
-    memset(&C, 0, sizeof C);
+    PZCHK(circ_base(limbs_n, limb_bits, lb, 7, C));
     memset(&B, 0, sizeof B);
-    PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
-    C.Ln = limbs_n;
-    C.kind = 7;
-    C.words_n = (limbs_n * limb_bits + 63) / 64;
-    C.rc_adv = C.e.rc64_adv;
-    C.rc_lk = C.e.rc64_lk;
-    PZCHK(refresh_aux_host(limb_bits, limbs_n, limbs_n, C.inc, &C.nf));
-    if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
     const size_t W = limb_bits, L = C.e.L;
     B.K = count;
     B.E = L * W;
+    B.in_v = C.words_n;
+    B.in_theta = B.in_v + C.e.L64;
     size_t a = 0, l = 0;
-    const size_t asg_a = (size_t)limbs_n * (1 + C.rc_adv), asg_l = (size_t)limbs_n * C.rc_lk;
-    C.n_in = 1;
-    C.a_assign[0] = a; C.l_assign[0] = l; a += asg_a; l += asg_l;
+    assign_inputs(C, 1, a, l);
     B.a_wide = a; B.l_wide = l;
-    a += (count + 2) * 2 * asg_a; l += (count + 2) * 2 * asg_l;
-    C.a_square = a;
-    a += 1;
-    for (unsigned i = 0; i < 2 * limbs_n - 1; ++i) a += 1 + 3 * ((size_t)i + 1);
-    C.a_refresh = a; C.l_refresh = l;
-    a += 1;
-    for (unsigned i = 0; i < C.nf; ++i) a += ((size_t)C.inc[i] + 1) * 22 + (size_t)C.inc[i] * 4;
-    a += (size_t)C.nf * C.rc_adv;
-    l += (size_t)C.nf * C.rc_lk;
-    C.a_zero = a; a += 1;
-    B.nbc = 7 * W - 2;
-    B.bit_stride = 2 * C.e.cells + 8 * L;
-    B.limb_stride = B.nbc + W * B.bit_stride;
+    a += (count + 2) * 2 * asg_adv(C); l += (count + 2) * 2 * asg_lk(C);
+    square_refresh_cells(C, a, l);
+    load_zero_cell(C, a);
+    B.limb_stride = nbits_cells(W) + W * bit_stride(C);
     B.chain_cells = 2 + L * B.limb_stride;
     B.a_ch = a; B.l_ch = l;
     a += (count + 1) * B.chain_cells + count * C.e.cells;
     l += (count + (count + 1) * 2 * B.E) * C.e.lookups;
-    B.res_stride = 2 * asg_a + 2 + 16 * (size_t)C.nf;
-    B.a_res = a; B.l_res = l;
-    a += (count + 1) * B.res_stride; l += (count + 1) * 2 * asg_l;
-    B.in_v = C.words_n;
-    B.in_theta = B.in_v + C.e.L64;
-    B.in_cts = B.in_theta + C.e.L64;
-    B.in_res = B.in_cts + count * C.e.L64;
-    C.res_off = B.in_res;   // (k_circuit_misc reads a result it does not write for this kind: h, valid memory)
+    B.res.a_head = B.a_ch; B.res.head_stride = B.chain_cells + C.e.cells;
+    B.res.rec0 = count + 2 * B.E - 2; B.res.rec_stride = 2 * B.E;   // (the field depends on theta: partial_expand_impl)
+    result_blocks(C, B.res, count + 1, B.in_theta + (1 + count) * C.e.L64, a, l);
     *adv_total = a;
     *lk_total = l;
     return PZ_OK;
-}
-// grid.x = chain i (0: the base v, j >= 1: ciphertext j): the [1, 0] at the chain's head, assign_integer of h / u_i and
-// assert_equal_fresh(chain i's result, h / u_i), the result taken from the chain's last (acc, sq) record
-__global__ __launch_bounds__(256) void k_partial_misc(CircP C, PartialP B, const u64* __restrict__ inputs, const u64* __restrict__ steps,
-                                                      Fr* __restrict__ advice, Fr* __restrict__ lookup) {
-    __shared__ u64 s_res[CIRC_MAXF][2], s_c[CIRC_MAXF][2];
-    __shared__ unsigned char s_eq[CIRC_MAXF + 1];
-    const size_t i = blockIdx.x;
-    const unsigned nf = C.nf, W = C.e.W, lb = C.e.lb, tid = threadIdx.x;
-    const u64* cval = steps + (B.K + (i + 1) * 2 * B.E - 2) * 4 * (size_t)C.e.L64 + (B.top ? 3 : 0) * (size_t)C.e.L64;
-#define LIMB(X, i) u_make((X)[i][0], (X)[i][1])
-    for (unsigned t = tid; t < nf; t += blockDim.x) {
-        limb_extract(inputs + B.in_res + i * C.e.L64, C.e.L64, t, W, s_res[t]);
-        limb_extract(cval, C.e.L64, t, W, s_c[t]);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned eq = 1;
-        s_eq[0] = 1;
-        for (unsigned t = 0; t < nf; ++t) {
-            eq &= u_eq(LIMB(s_c, t), LIMB(s_res, t)) ? 1u : 0u;
-            s_eq[t + 1] = (unsigned char)eq;
-        }
-        const CellPtr p = adv_ptr(C.e, advice, B.a_ch + i * (B.chain_cells + C.e.cells));
-        fp_store(p, fp_one<FrTag>());
-        fp_store(p + 1, fp_zero<FrTag>());
-    }
-    __syncthreads();
-    const CellPtr a = adv_ptr(C.e, advice, B.a_res + i * B.res_stride);
-    const CellPtr l{lookup, B.l_res + i * nf * C.rc_lk, C.e.rows, C.e.pad, nullptr, 0};
-    for (unsigned t = tid; t < nf * (1 + C.rc_adv); t += blockDim.x) {
-        Fr v;
-        if (t < nf) v = fr_from_u(LIMB(s_res, t));
-        else v = cv_to_fr(rc_adv_cell(LIMB(s_res, (t - nf) / C.rc_adv), W, lb, (t - nf) % C.rc_adv));
-        fp_store(a + t, v);
-    }
-    if (l)
-        for (unsigned t = tid; t < nf * C.rc_lk; t += blockDim.x) fp_store(l + t, cv_to_fr(rc_lk_cell(LIMB(s_res, t / C.rc_lk), W, lb, t % C.rc_lk)));
-    const CellPtr e = a + (size_t)nf * (1 + C.rc_adv);
-    if (tid == 0) {
-        fp_store(e, fp_zero<FrTag>());
-        fp_store(e + 1, fp_one<FrTag>());
-    }
-    for (unsigned t = tid; t < 16 * nf; t += blockDim.x) {
-        const unsigned j = t / 16, p = t % 16;
-        Fr v;
-        if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, j), LIMB(s_res, j), p));
-        else {
-            const unsigned eq = u_eq(LIMB(s_c, j), LIMB(s_res, j)) ? 1u : 0u, in = s_eq[j], out = s_eq[j + 1];
-            v = p == 12 ? fp_zero<FrTag>() : p == 13 ? (in ? fp_one<FrTag>() : fp_zero<FrTag>())
-                : p == 14 ? (eq ? fp_one<FrTag>() : fp_zero<FrTag>()) : (out ? fp_one<FrTag>() : fp_zero<FrTag>());
-        }
-        fp_store(e + 2 + t, v);
-    }
-#undef LIMB
 }
 
 extern "C" int pz_partial_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t* advice_cells,
@@ -1664,148 +1601,101 @@ extern "C" int pz_partial_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t l
     CircP C;
     PartialP B;
     size_t a, l;
-    PZCHK(make_partial_params(limbs_n, limb_bits, lookup_bits, count, C, B, &a, &l));
-    if (advice_cells) *advice_cells = a;
-    if (lookup_cells) *lookup_cells = l;
-    return PZ_OK;
+    const int rc = make_partial_params(limbs_n, limb_bits, lookup_bits, count, C, B, &a, &l);
+    return put_cells(rc, a, l, advice_cells, lookup_cells);
 }
 
-static int partial_expand_impl(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, const uint64_t* inputs,
-                               const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows,
-                               size_t col_stride, const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows) {
-    if (!ctx || !inputs || !d_steps || !d_modulus || !d_advice) return PZ_ERR_INVALID;
-    if ((rows == 0) != (col_stride == 0) || col_stride < rows) return PZ_ERR_INVALID;
+static int partial_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count) {
+    PZCHK(expand_check(A));
     CircP C;
     PartialP B;
     size_t a, l;
     PZCHK(make_partial_params(limbs_n, limb_bits, lookup_bits, count, C, B, &a, &l));
-    C.e.rows = rows;
-    C.e.pad = col_stride - rows;
-    if (d_col_starts) {
-        if (n_adv_cols == 0 || n_adv_cols > 0xffffffffu || max_rows < 8 || max_rows > col_stride) return PZ_ERR_INVALID;
-        C.e.bp_starts = (const u64*)d_col_starts;
-        C.e.bp_ncols = (unsigned)n_adv_cols;
-        C.e.bp_div = max_rows - 1;
-        C.e.bp_stride = col_stride;
-    }
+    PZCHK(expand_layout(A, C));
     const size_t E = B.E, L64 = C.e.L64;
-    const u64* theta = inputs + B.in_theta;
+    const u64* theta = A.inputs + B.in_theta;
     for (size_t k = E / 64; k < L64; ++k)   // theta >= 2^E: num_to_bits of its limbs cannot hold
         if (k == E / 64 ? theta[k] >> (E & 63) : theta[k]) return PZ_ERR_MESSAGE_RANGE;
-    B.top = (unsigned)((theta[(E - 1) / 64] >> ((E - 1) & 63)) & 1);
+    B.res.field = (theta[(E - 1) / 64] >> ((E - 1) & 63)) & 1 ? 3 : 0;
+    pz_ctx* ctx = A.ctx;
     PZ_ENTER(ctx);
-    const size_t in_words = B.in_res + (count + 1) * L64;
-    void* d_in;
-    PZCHK(pz_ws_get(ctx, WS_MISC, in_words * 8 + 64, &d_in));
-    PZCHK(pz_upload_small_async(ctx, d_in, inputs, in_words * 8));
+    const u64* in;
+    PZCHK(expand_stage(A, B.res.in_res + (count + 1) * L64, nullptr, 0, &in));
     pz_timer tm(ctx, PZ_T_EXPAND);
-    const u64* in = (const u64*)d_in;
-    Fr *adv = (Fr*)d_advice, *lk = (Fr*)d_lookup;
+    const u64* d_steps = A.d_steps;
+    Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
     const size_t rec = 4 * L64;   // words per step record
     const unsigned W = limb_bits, Lf = C.e.L;
-    // n, square, refresh, load_zero (the first record's remainder stands in for the result this kind does not write there)
-    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, d_steps + 3 * L64, adv, lk);
+    // n, square, refresh, load_zero
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, (const u64*)nullptr, adv, lk);
     // assign_integer of v, theta and the c_j: 2 Ln limbs from L64 words each
-    hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)(count + 2)), dim3(256), 0, ctx->stream, C.e, C.nf, C.rc_adv, C.rc_lk, in + B.in_v,
-                       B.a_wide, B.l_wide, adv, lk);
+    launch_assign(A, C, in, B.in_v, C.nf, (unsigned)L64, count + 2, B.a_wide, B.l_wide);
     // chain by chain (kind 2's walk, limb by limb inside one launch): the squaring block in front of it, theta's num_to_bits per limb, the
     // selects, the chain's 2 E records in (mul_mod, square_mod) pairs
     for (size_t i = 0; i <= count; ++i) {
         const size_t head = B.a_ch + i * (B.chain_cells + C.e.cells), lk_chain = B.l_ch + i * (2 * E + 1) * C.e.lookups;
         const u64* d_chain = d_steps + (count + i * 2 * E) * rec;
-        if (i) {
-            ExpP S = C.e;
-            S.cell0 = head - C.e.cells;
-            S.lk0 = lk_chain - C.e.lookups;
-            hipLaunchKernelGGL(k_witness_expand, dim3(1), dim3(EXP_THREADS), 0, ctx->stream, S, d_steps + (i - 1) * rec, d_modulus, adv, lk);
-        }
+        if (i) launch_runs(A, C, head - C.e.cells, lk_chain - C.e.lookups, d_steps + (i - 1) * rec, 1);
         hipLaunchKernelGGL(k_circuit_bits, dim3(Lf), dim3(256), 0, ctx->stream, C.e, Lf, (unsigned)L64, in + B.in_theta, head + 2, B.limb_stride,
                            adv);
         hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)E), dim3(256), 0, ctx->stream, C.e, Lf, (unsigned)L64, in + B.in_theta, d_chain,
-                           head + 2, B.limb_stride, B.bit_stride, B.nbc, adv);
-        ExpP Q = C.e;
-        Q.cell0 = head + 2 + B.nbc;
-        Q.lk0 = lk_chain;
-        Q.pair_stride = B.bit_stride;
-        Q.odd_off = C.e.cells + 8 * (size_t)Lf;
-        Q.chain_steps = 2 * (size_t)W;
-        Q.chain_stride = B.limb_stride;
-        hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(2 * E)), dim3(EXP_THREADS), 0, ctx->stream, Q, d_chain, d_modulus, adv, lk);
+                           head + 2, B.limb_stride, bit_stride(C), nbits_cells(W), adv);
+        launch_chains(A, C, head + 2, lk_chain, d_chain, W, Lf, B.limb_stride, 2 * (size_t)W);
     }
-    hipLaunchKernelGGL(k_partial_misc, dim3((unsigned)(count + 1)), dim3(256), 0, ctx->stream, C, B, in, d_steps, adv, lk);
+    launch_results(A, C, B.res, count + 1, in, d_steps);
     HIPCHK(ctx, hipGetLastError());
     return PZ_OK;
 }
 extern "C" int pz_partial_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count,
                                      const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice,
                                      uint64_t* d_lookup, size_t rows, size_t col_stride) {
-    return partial_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, inputs, d_steps, d_modulus, d_advice, d_lookup, rows, col_stride,
-                               nullptr, 0, 0);
+    return partial_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, false, rows, col_stride, nullptr, 0, 0}, limbs_n, limb_bits,
+                               lookup_bits, count);
 }
 extern "C" int pz_partial_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count,
                                           const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice,
                                           uint64_t* d_lookup, const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows,
                                           size_t lookup_rows, size_t col_stride) {
-    if (!d_col_starts || lookup_rows == 0 || lookup_rows > col_stride) return PZ_ERR_INVALID;
-    return partial_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, inputs, d_steps, d_modulus, d_advice, d_lookup, lookup_rows,
-                               col_stride, d_col_starts, n_adv_cols, max_rows);
+    return partial_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, true, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows},
+                               limbs_n, limb_bits, lookup_bits, count);
 }
 
 // ---- the mix (circuit kind 8): K = 2^d ciphertexts through the Benes network, then c'_i = d_i r_i^n mod n^2.
 // Stream: assign n; assign c_1 .. c_K at full width; assign r_1 .. r_K; square + refresh, load_zero; per layer and switch [0, b, b, b]
-// and per limb select(in[j'], in[j], b), select(in[j], in[j'], b); per output [1, 0 | nr x mul_mod | mul_mod]; per output assign res_i
-// (2 Ln limbs) + assert_equal_fresh.  inputs: n | c_1 .. c_K | r_1 .. r_K | res_1 .. res_K.  Routes, bits and records are
-// pz_paillier_mix_dev's, as it leaves them: fields of 2 ceil(Ln W / 64) words.
+// and per limb select(in[j'], in[j], b), select(in[j], in[j'], b); per output [1, 0 | nr x mul_mod | mul_mod]; per output a result
+// block (res_i against the remainder of the output's last record).  inputs: n | c_1 .. c_K | r_1 .. r_K | res_1 .. res_K.  Routes,
+// bits and records are pz_paillier_mix_dev's, as it leaves them: fields of 2 ceil(Ln W / 64) words.
 #define MIX_MAX 1024
 struct MixP {
-    size_t K, half, layers, per, a_cts, l_cts, a_rs, l_rs, a_net, sw_cells, a_out, l_out, out_stride, a_res, l_res, res_stride;
-    size_t in_cts, in_rs, in_res;   // word offsets inside `inputs`
+    size_t K, half, layers, per, a_cts, l_cts, a_rs, l_rs, a_net, sw_cells, a_out, l_out, out_stride;
+    size_t in_cts, in_rs;           // word offsets inside `inputs`
     unsigned d, rw;                 // log2 K; words per field of a route or record as K3 writes them
+    ResP res;
 };
 static int make_mix_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, size_t n_steps_r, CircP& C, MixP& B,
                            size_t* adv_total, size_t* lk_total) {
     if (count < 1 || count > MIX_MAX || (count & (count - 1)) != 0 || n_steps_r < 1 || n_steps_r > 0x7fffffffu) return PZ_ERR_INVALID;
-    if (limbs_n < 1 || 2 * limbs_n > CIRC_MAXF || 2 * limbs_n > EXP_MAXL) return PZ_ERR_UNSUPPORTED;
-    memset(&C, 0, sizeof C);
+    PZCHK(circ_base(limbs_n, limb_bits, lb, 8, C));
     memset(&B, 0, sizeof B);
-    PZCHK(make_params(2 * limbs_n, limb_bits, lb, C.e));
-    C.Ln = limbs_n;
-    C.kind = 8;
-    C.words_n = (limbs_n * limb_bits + 63) / 64;
-    C.rc_adv = C.e.rc64_adv;
-    C.rc_lk = C.e.rc64_lk;
-    PZCHK(refresh_aux_host(limb_bits, limbs_n, limbs_n, C.inc, &C.nf));
-    if (C.nf != 2 * limbs_n) return PZ_ERR_UNSUPPORTED;   // the chip's mul_mod needs n^2 at the operands' limb count
     B.K = count; B.half = count / 2; B.per = n_steps_r + 1; B.rw = 2 * C.words_n;
     while (((size_t)1 << B.d) < count) ++B.d;
     B.layers = count > 1 ? 2 * (size_t)B.d - 1 : 0;
+    B.in_cts = C.words_n;
+    B.in_rs = B.in_cts + count * C.e.L64;
     size_t a = 0, l = 0;
-    const size_t asg_a = (size_t)limbs_n * (1 + C.rc_adv), asg_l = (size_t)limbs_n * C.rc_lk;
-    C.n_in = 1;
-    C.a_assign[0] = a; C.l_assign[0] = l; a += asg_a; l += asg_l;
-    B.a_cts = a; B.l_cts = l; a += count * 2 * asg_a; l += count * 2 * asg_l;
-    B.a_rs = a; B.l_rs = l; a += count * asg_a; l += count * asg_l;
-    C.a_square = a;
-    a += 1;
-    for (unsigned i = 0; i < 2 * limbs_n - 1; ++i) a += 1 + 3 * ((size_t)i + 1);
-    C.a_refresh = a; C.l_refresh = l;
-    a += 1;
-    for (unsigned i = 0; i < C.nf; ++i) a += ((size_t)C.inc[i] + 1) * 22 + (size_t)C.inc[i] * 4;
-    a += (size_t)C.nf * C.rc_adv;
-    l += (size_t)C.nf * C.rc_lk;
-    C.a_zero = a; a += 1;
+    assign_inputs(C, 1, a, l);
+    B.a_cts = a; B.l_cts = l; a += count * 2 * asg_adv(C); l += count * 2 * asg_lk(C);
+    B.a_rs = a; B.l_rs = l; a += count * asg_adv(C); l += count * asg_lk(C);
+    square_refresh_cells(C, a, l);
+    load_zero_cell(C, a);
     B.sw_cells = 4 + 16 * (size_t)C.e.L;
     B.a_net = a; a += B.layers * B.half * B.sw_cells;
     B.out_stride = 2 + B.per * C.e.cells;
     B.a_out = a; B.l_out = l;
     a += count * B.out_stride; l += count * B.per * C.e.lookups;
-    B.res_stride = 2 * asg_a + 2 + 16 * (size_t)C.nf;
-    B.a_res = a; B.l_res = l;
-    a += count * B.res_stride; l += count * 2 * asg_l;
-    B.in_cts = C.words_n;
-    B.in_rs = B.in_cts + count * C.e.L64;
-    B.in_res = B.in_rs + count * C.words_n;
-    C.res_off = B.in_res;   // (k_circuit_misc reads a result it does not write for this kind: res_1, valid memory)
+    B.res.a_head = B.a_out; B.res.head_stride = B.out_stride;
+    B.res.rec0 = B.per - 1; B.res.rec_stride = B.per; B.res.field = 3;
+    result_blocks(C, B.res, count, B.in_rs + count * C.words_n, a, l);
     *adv_total = a;
     *lk_total = l;
     return PZ_OK;
@@ -1851,104 +1741,34 @@ __global__ __launch_bounds__(256) void k_mix_repack(const u64* __restrict__ src,
     const unsigned k = (unsigned)(g % L64);
     dst[g] = k < rw ? src[f * rw + k] : 0;
 }
-// grid.x = output i: the [1, 0] of its pow_mod_fixed_exp, assign_integer(res_i) and assert_equal_fresh(c'_i, res_i), c'_i the remainder of
-// the output's last record (fields of L64 words)
-__global__ __launch_bounds__(256) void k_mix_misc(CircP C, MixP B, const u64* __restrict__ inputs, const u64* __restrict__ steps,
-                                                  Fr* __restrict__ advice, Fr* __restrict__ lookup) {
-    __shared__ u64 s_res[CIRC_MAXF][2], s_c[CIRC_MAXF][2];
-    __shared__ unsigned char s_eq[CIRC_MAXF + 1];
-    const size_t i = blockIdx.x;
-    const unsigned nf = C.nf, W = C.e.W, lb = C.e.lb, tid = threadIdx.x;
-    const u64* cval = steps + (i * B.per + B.per - 1) * 4 * (size_t)C.e.L64 + 3 * (size_t)C.e.L64;
-#define LIMB(X, i) u_make((X)[i][0], (X)[i][1])
-    for (unsigned t = tid; t < nf; t += blockDim.x) {
-        limb_extract(inputs + B.in_res + i * C.e.L64, C.e.L64, t, W, s_res[t]);
-        limb_extract(cval, C.e.L64, t, W, s_c[t]);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned eq = 1;
-        s_eq[0] = 1;
-        for (unsigned t = 0; t < nf; ++t) {
-            eq &= u_eq(LIMB(s_c, t), LIMB(s_res, t)) ? 1u : 0u;
-            s_eq[t + 1] = (unsigned char)eq;
-        }
-        const CellPtr p = adv_ptr(C.e, advice, B.a_out + i * B.out_stride);
-        fp_store(p, fp_one<FrTag>());
-        fp_store(p + 1, fp_zero<FrTag>());
-    }
-    __syncthreads();
-    const CellPtr a = adv_ptr(C.e, advice, B.a_res + i * B.res_stride);
-    const CellPtr l{lookup, B.l_res + i * nf * C.rc_lk, C.e.rows, C.e.pad, nullptr, 0};
-    for (unsigned t = tid; t < nf * (1 + C.rc_adv); t += blockDim.x) {
-        Fr v;
-        if (t < nf) v = fr_from_u(LIMB(s_res, t));
-        else v = cv_to_fr(rc_adv_cell(LIMB(s_res, (t - nf) / C.rc_adv), W, lb, (t - nf) % C.rc_adv));
-        fp_store(a + t, v);
-    }
-    if (l)
-        for (unsigned t = tid; t < nf * C.rc_lk; t += blockDim.x) fp_store(l + t, cv_to_fr(rc_lk_cell(LIMB(s_res, t / C.rc_lk), W, lb, t % C.rc_lk)));
-    const CellPtr e = a + (size_t)nf * (1 + C.rc_adv);
-    if (tid == 0) {
-        fp_store(e, fp_zero<FrTag>());
-        fp_store(e + 1, fp_one<FrTag>());
-    }
-    for (unsigned t = tid; t < 16 * nf; t += blockDim.x) {
-        const unsigned j = t / 16, p = t % 16;
-        Fr v;
-        if (p < 12) v = cv_to_fr(is_equal_cell(LIMB(s_c, j), LIMB(s_res, j), p));
-        else {
-            const unsigned eq = u_eq(LIMB(s_c, j), LIMB(s_res, j)) ? 1u : 0u, in = s_eq[j], out = s_eq[j + 1];
-            v = p == 12 ? fp_zero<FrTag>() : p == 13 ? (in ? fp_one<FrTag>() : fp_zero<FrTag>())
-                : p == 14 ? (eq ? fp_one<FrTag>() : fp_zero<FrTag>()) : (out ? fp_one<FrTag>() : fp_zero<FrTag>());
-        }
-        fp_store(e + 2 + t, v);
-    }
-#undef LIMB
-}
-
 extern "C" int pz_mix_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r, size_t* advice_cells,
                             size_t* lookup_cells) {
     CircP C;
     MixP B;
     size_t a, l;
-    PZCHK(make_mix_params(limbs_n, limb_bits, lookup_bits, count, n_steps_r, C, B, &a, &l));
-    if (advice_cells) *advice_cells = a;
-    if (lookup_cells) *lookup_cells = l;
-    return PZ_OK;
+    const int rc = make_mix_params(limbs_n, limb_bits, lookup_bits, count, n_steps_r, C, B, &a, &l);
+    return put_cells(rc, a, l, advice_cells, lookup_cells);
 }
 
-static int mix_expand_impl(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
-                           const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
-                           const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride,
-                           const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows) {
-    if (!ctx || !inputs || !d_steps || !d_modulus || !d_advice) return PZ_ERR_INVALID;
-    if ((rows == 0) != (col_stride == 0) || col_stride < rows) return PZ_ERR_INVALID;
+static int mix_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
+                           const uint8_t* bits, const uint64_t* d_routes) {
+    PZCHK(expand_check(A));
     CircP C;
     MixP B;
     size_t a, l;
     PZCHK(make_mix_params(limbs_n, limb_bits, lookup_bits, count, n_steps_r, C, B, &a, &l));
     if (B.layers && (!bits || !d_routes)) return PZ_ERR_INVALID;
-    C.e.rows = rows;
-    C.e.pad = col_stride - rows;
-    if (d_col_starts) {
-        if (n_adv_cols == 0 || n_adv_cols > 0xffffffffu || max_rows < 8 || max_rows > col_stride) return PZ_ERR_INVALID;
-        C.e.bp_starts = (const u64*)d_col_starts;
-        C.e.bp_ncols = (unsigned)n_adv_cols;
-        C.e.bp_div = max_rows - 1;
-        C.e.bp_stride = col_stride;
-    }
+    PZCHK(expand_layout(A, C));
     const size_t n_switch = B.layers * B.half;
     for (size_t i = 0; i < n_switch; ++i)
         if (bits[i] > 1) return PZ_ERR_MESSAGE_RANGE;   // assert_bit of such a byte cannot hold
+    pz_ctx* ctx = A.ctx;
     PZ_ENTER(ctx);
-    const size_t in_words = B.in_res + count * C.e.L64;
-    void* d_in;
-    PZCHK(pz_ws_get(ctx, WS_MISC, in_words * 8 + n_switch + 64, &d_in));
-    PZCHK(pz_upload_small_async(ctx, d_in, inputs, in_words * 8));
-    const unsigned char* d_bits = (const unsigned char*)d_in + in_words * 8;
-    if (n_switch) PZCHK(pz_upload_small_async(ctx, (void*)d_bits, bits, n_switch));
-    const u64* recs = (const u64*)d_steps;
+    const size_t in_words = B.res.in_res + count * C.e.L64;
+    const u64* in;
+    PZCHK(expand_stage(A, in_words, bits, n_switch, &in));   // the switch bits behind the inputs
+    const unsigned char* d_bits = (const unsigned char*)(in + in_words);
+    const u64* recs = A.d_steps;
     const size_t fields = count * B.per * 4;
     if (B.rw != C.e.L64) {   // K3's fields are whole words of n twice over; K4's are the words 2 Ln limbs take
         void* t;
@@ -1958,17 +1778,12 @@ static int mix_expand_impl(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, ui
         recs = (const u64*)t;
     }
     pz_timer tm(ctx, PZ_T_EXPAND);
-    const u64* in = (const u64*)d_in;
-    Fr *adv = (Fr*)d_advice, *lk = (Fr*)d_lookup;
-    // n, square, refresh, load_zero (the first record's remainder stands in for the result this kind does not write there)
-    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, recs + 3 * (size_t)C.e.L64, adv, lk);
+    Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
+    // n, square, refresh, load_zero
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, (const u64*)nullptr, adv, lk);
     // assign_integer(c_j): 2 Ln limbs from L64 words each; assign_integer(r_i): Ln limbs from words_n words each
-    hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)count), dim3(256), 0, ctx->stream, C.e, C.nf, C.rc_adv, C.rc_lk, in + B.in_cts, B.a_cts,
-                       B.l_cts, adv, lk);
-    ExpP R = C.e;
-    R.L64 = C.words_n;
-    hipLaunchKernelGGL(k_circuit_assign_many, dim3((unsigned)count), dim3(256), 0, ctx->stream, R, C.Ln, C.rc_adv, C.rc_lk, in + B.in_rs, B.a_rs,
-                       B.l_rs, adv, lk);
+    launch_assign(A, C, in, B.in_cts, C.nf, C.e.L64, count, B.a_cts, B.l_cts);
+    launch_assign(A, C, in, B.in_rs, C.Ln, C.words_n, count, B.a_rs, B.l_rs);
     // the network, layer by layer: a layer reads the one below (layer 0: the ciphertexts) and its own
     const size_t layer_words = count * B.rw;
     for (size_t ly = 0; ly < B.layers; ++ly) {
@@ -1979,31 +1794,25 @@ static int mix_expand_impl(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, ui
                            B.a_net + ly * B.half * B.sw_cells, B.sw_cells, adv);
     }
     // per output: the r-chain's records and the final one
-    ExpP T = C.e;
-    T.cell0 = B.a_out + 2;
-    T.lk0 = B.l_out;
-    T.chain_steps = B.per;
-    T.chain_stride = B.out_stride;
-    T.chain_recs = B.per;
-    hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(count * B.per)), dim3(EXP_THREADS), 0, ctx->stream, T, recs, d_modulus, adv, lk);
-    hipLaunchKernelGGL(k_mix_misc, dim3((unsigned)count), dim3(256), 0, ctx->stream, C, B, in, recs, adv, lk);
+    launch_runs(A, C, B.a_out + 2, B.l_out, recs, B.per, count, B.out_stride, B.per);
+    launch_results(A, C, B.res, count, in, recs);
     HIPCHK(ctx, hipGetLastError());
     return PZ_OK;
 }
 extern "C" int pz_mix_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
                                  const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
                                  const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride) {
-    return mix_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, n_steps_r, inputs, bits, d_routes, d_steps, d_modulus, d_advice, d_lookup,
-                           rows, col_stride, nullptr, 0, 0);
+    return mix_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, false, rows, col_stride, nullptr, 0, 0}, limbs_n, limb_bits,
+                           lookup_bits, count, n_steps_r, bits, d_routes);
 }
 extern "C" int pz_mix_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r,
                                       const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
                                       const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts,
                                       size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride) {
-    if (!d_col_starts || lookup_rows == 0 || lookup_rows > col_stride) return PZ_ERR_INVALID;
-    return mix_expand_impl(ctx, limbs_n, limb_bits, lookup_bits, count, n_steps_r, inputs, bits, d_routes, d_steps, d_modulus, d_advice, d_lookup,
-                           lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows);
+    return mix_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, true, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows},
+                           limbs_n, limb_bits, lookup_bits, count, n_steps_r, bits, d_routes);
 }
+#undef LIMB
 
 // host-pointer form (SURVEY.md section 8b `pz_witness_expand`): stages the trace up, expands on the device in groups
 // of steps and copies the cell streams back; the prover pipeline keeps everything resident and uses the _dev form.

@@ -226,6 +226,35 @@ def test_k4_dense_stream_and_break_point_columns_equal_the_reference(eng, cref, 
     assert _status(lambda: eng.circuit_cells(6, Ln, W, lb, 2 * b, nr)) == _lib.PZ_ERR_INVALID
 
 
+def test_k4_dense_stream_of_a_mismatching_result_equals_the_reference(eng, cref):
+    """entry 1's claimed ciphertext differs from the computed one in a middle limb only, entry 0's matches: the running-equality chain of
+    entry 1 drops there and stays down, the is_zero inverse cell of that limb is a true inverse -- the cells the matching streams above
+    never reach"""
+    import torch
+
+    bits, W, lb, K, b = 128, 64, 10, 2, 2
+    Ln = bits // W
+    n, g, ms, rs = _inputs(bits, K, b, 0x6b2a)
+    tr = BR.ballot_trace(n, g, ms, rs, b)
+    nr = BR.n_steps_r(n)
+    res = [tr.cts[0], tr.cts[1] ^ (1 << (W + 5))]       # limb 1 of 4
+    want_a, want_l, seg = BR.ballot_cells(n, g, ms, rs, res, b, bits, W, lb)
+    assert not seg["satisfied"]
+    na, nl = eng.ballot_cells(Ln, W, lb, K, b, nr)
+    assert (na, nl) == (len(want_a), len(want_l))
+    d_steps = _device_records(eng, cref, bits, n, g, ms, rs, b)
+    d_mod = torch.from_numpy(cref.int_to_limbs(n * n, _words(2 * bits)).astype(np.int64)).cuda()
+    d_adv = torch.zeros((na, 4), dtype=torch.int64, device="cuda")
+    d_lk = torch.zeros((nl, 4), dtype=torch.int64, device="cuda")
+    eng.ballot_expand_dev(Ln, W, lb, K, b, nr, _ballot_inputs(cref, bits, n, g, ms, rs, res), d_steps.data_ptr(), d_mod.data_ptr(),
+                          d_adv.data_ptr(), d_lk.data_ptr())
+    eng.sync()
+    got_a = cref.fr_mont_to_ints(d_adv.cpu().numpy().view(np.uint64))
+    bad = [i for i, (x, y) in enumerate(zip(got_a, want_a)) if x != y]
+    assert not bad, "%d advice cells differ, first at %d" % (len(bad), bad[0])
+    assert cref.fr_mont_to_ints(d_lk.cpu().numpy().view(np.uint64)) == want_l
+
+
 # ------------------------------------------------------------------------------------------------------------------ 3. structure
 @pytest.mark.parametrize("shape", [SB1, SB3], ids=["SB1", "K1"])
 @pytest.mark.parametrize("expose", [False, True])

@@ -359,6 +359,37 @@ def test_k4_dense_stream_and_break_point_columns_equal_the_reference(eng, cref, 
     assert _status(lambda: eng.mix_cells(Ln, W, lb, K, 0)) == _lib.PZ_ERR_INVALID
 
 
+def test_k4_dense_stream_of_a_mismatching_result_equals_the_reference(eng, cref):
+    """output 1's claimed ciphertext differs from the computed one in a middle limb only, output 0's matches: the running-equality chain
+    of output 1 drops there and stays down, the is_zero inverse cell of that limb is a true inverse -- the cells the matching streams
+    above never reach"""
+    import torch
+
+    bits, W, lb, k, K = SM2S
+    Ln = bits // W
+    n, cts, rs, perm = _mix_inputs(bits, K, 0x31EA)
+    sw = MR.route(perm)
+    tr = _ref_trace(n, cts, rs, sw, bits, W)
+    nr = MR.n_steps_r(n)
+    res = [tr.mixed[0], tr.mixed[1] ^ (1 << (W + 5))]   # limb 1 of 4
+    want_a, want_l, seg = MR.mix_cells(n, cts, rs, res, bits, W, lb, tr)
+    assert not seg["satisfied"]
+    na, nl = eng.mix_cells(Ln, W, lb, K, nr)
+    assert (na, nl) == (len(want_a), len(want_l))
+    mixed, d_routes, d_steps = _k3_dev(eng, cref, bits, n, cts, sw, rs)
+    assert mixed == tr.mixed
+    d_mod = torch.from_numpy(cref.int_to_limbs(n * n, _words(2 * bits)).astype(np.int64)).cuda()
+    d_adv = torch.zeros((na, 4), dtype=torch.int64, device="cuda")
+    d_lk = torch.zeros((nl, 4), dtype=torch.int64, device="cuda")
+    eng.mix_expand_dev(Ln, W, lb, K, nr, _mix_k4_inputs(cref, bits, n, cts, rs, res), sw, d_routes.data_ptr(), d_steps.data_ptr(),
+                       d_mod.data_ptr(), d_adv.data_ptr(), d_lk.data_ptr())
+    eng.sync()
+    got_a = cref.fr_mont_to_ints(d_adv.cpu().numpy().view(np.uint64))
+    bad = [i for i, (x, y) in enumerate(zip(got_a, want_a)) if x != y]
+    assert not bad, "%d advice cells differ, first at %d (outputs at %d)" % (len(bad), bad[0], seg["outputs"][0])
+    assert cref.fr_mont_to_ints(d_lk.cpu().numpy().view(np.uint64)) == want_l
+
+
 # ------------------------------------------------------------------------------------------------------------------ 4. structure
 @pytest.mark.parametrize("shape", [SM4, SM1], ids=["K4", "K1"])
 @pytest.mark.parametrize("expose", [False, True])

@@ -364,6 +364,34 @@ def test_k4_dense_stream_and_break_point_columns_equal_the_reference(eng, cref, 
     assert A_used >= 2
 
 
+def test_k4_dense_stream_of_a_mismatching_result_equals_the_reference(eng, cref):
+    """result 1 (u_1) as claimed differs from chain 1's in a middle limb only, h and u_2 match: the running-equality chain of result 1
+    drops there and stays down, the is_zero inverse cell of that limb is a true inverse -- the cells the matching streams above never
+    reach"""
+    import torch
+
+    bits, W, lb, k, K = SP3
+    Ln = bits // W
+    n, v, theta, cts = _circuit_inputs(bits, K, 0x7a6a)
+    tr = TR.partial_trace(n, v, theta, cts, 2 * bits)
+    us = [tr.us[0] ^ (1 << (W + 5)), tr.us[1]]          # limb 1 of 4
+    want_a, want_l, seg = TR.partial_cells(n, v, theta, cts, tr.h, us, bits, W, lb, tr)
+    assert not seg["satisfied"]
+    na, nl = eng.partial_cells(Ln, W, lb, K)
+    assert (na, nl) == (len(want_a), len(want_l))
+    d_steps = _device_records(eng, cref, bits, n, v, theta, cts)
+    d_mod = torch.from_numpy(cref.int_to_limbs(n * n, _words(2 * bits)).astype(np.int64)).cuda()
+    d_adv = torch.zeros((na, 4), dtype=torch.int64, device="cuda")
+    d_lk = torch.zeros((nl, 4), dtype=torch.int64, device="cuda")
+    eng.partial_expand_dev(Ln, W, lb, K, _partial_inputs(cref, bits, n, v, theta, cts, tr.h, us), d_steps.data_ptr(), d_mod.data_ptr(),
+                           d_adv.data_ptr(), d_lk.data_ptr())
+    eng.sync()
+    got_a = cref.fr_mont_to_ints(d_adv.cpu().numpy().view(np.uint64))
+    bad = [i for i, (x, y) in enumerate(zip(got_a, want_a)) if x != y]
+    assert not bad, "%d advice cells differ, first at %d (results at %d)" % (len(bad), bad[0], seg["results"][0])
+    assert cref.fr_mont_to_ints(d_lk.cpu().numpy().view(np.uint64)) == want_l
+
+
 # ------------------------------------------------------------------------------------------------------------------ 4. structure
 @pytest.mark.parametrize("shape", [SP1, SP3], ids=["SP1", "K2"])
 @pytest.mark.parametrize("expose", [False, True])

@@ -152,6 +152,33 @@ def test_k4_dense_stream_and_break_point_columns_equal_the_reference(eng, cref, 
         assert A_used >= 2
 
 
+def test_k4_dense_stream_of_a_mismatching_result_equals_the_reference(eng, cref):
+    """the claimed result differs from the root in a middle limb only: the running-equality chain drops there and stays down, the
+    is_zero inverse cell of that limb is a true inverse -- the cells the matching streams above never reach"""
+    import torch
+
+    bits, W, lb, B = 128, 64, 10, 2
+    Ln = bits // W
+    n, cts = _inputs(bits, B, 0x7a23)
+    root, _ = TR.tally_trace(n, cts)
+    res = root ^ (1 << (W + 5))                 # limb 1 of 4
+    want_a, want_l, seg = TR.tally_cells(n, cts, res, bits, W, lb)
+    assert not seg["satisfied"]
+    na, nl = eng.circuit_cells(3, Ln, W, lb, B - 1, 0)
+    assert (na, nl) == (len(want_a), len(want_l))
+    d_steps = _device_records(eng, cref, bits, n, cts)
+    d_mod = torch.from_numpy(cref.int_to_limbs(n * n, _words(2 * bits)).astype(np.int64)).cuda()
+    d_adv = torch.zeros((na, 4), dtype=torch.int64, device="cuda")
+    d_lk = torch.zeros((nl, 4), dtype=torch.int64, device="cuda")
+    eng.circuit_expand_dev(3, Ln, W, lb, _tally_inputs(cref, bits, n, cts, res), d_steps.data_ptr(), B - 1, 0, d_mod.data_ptr(),
+                           d_adv.data_ptr(), d_lk.data_ptr())
+    eng.sync()
+    got_a = cref.fr_mont_to_ints(d_adv.cpu().numpy().view(np.uint64))
+    bad = [i for i, (x, y) in enumerate(zip(got_a, want_a)) if x != y]
+    assert not bad, "%d advice cells differ, first at %d (assert_equal at %d)" % (len(bad), bad[0], seg["assert_equal"][0])
+    assert cref.fr_mont_to_ints(d_lk.cpu().numpy().view(np.uint64)) == want_l
+
+
 # ------------------------------------------------------------------------------------------------------------------ 3. structure
 @pytest.mark.parametrize("shape", [S1, S2])
 @pytest.mark.parametrize("expose", [False, True])
