@@ -351,6 +351,37 @@ int pz_paillier_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t
                            const uint64_t* ms, const uint64_t* rs, uint64_t* d_steps_out, size_t steps_cap, uint32_t* n_steps_r,
                            uint64_t* c_out);
 
+/* Short-randomness ballot (Damgard-Jurik-Nielsen encryption, "DJN mode"): c_i = g^m_i * hs^s_i mod n^2 for i = 1..count under ONE key
+ * (n, g, hs), hs = h^n mod n^2 with h = -x^2 mod n for a random unit x (keys.djn_generator, pz::djn_generator) -- an ordinary Paillier
+ * ciphertext with r_i = h^s_i mod n, which tally, weighted tally, mix, decrypt, partial and combine take unchanged (DESIGN.md section
+ * 15.18).  Security rests on the short-exponent assumption in <hs>: s_bits is the caller's, customarily at least twice the security
+ * level, and has no default.  1 <= count <= 1024, 1 <= m_bits <= 64, 1 <= s_bits <= 128*limbs_n (else PZ_ERR_INVALID); n, g: limbs_n
+ * words each; hs: 2*limbs_n words; ms = count 64-bit words, ONE per message; ss = count x ceil(s_bits/64) words; c_out = count x
+ * 2*limbs_n words (all HOST).  Per entry, in this order:
+ *   gm_i = BigUintChip::pow_mod(g, m_i) over EXACTLY m_bits in-circuit bits, LSB first (pz_paillier_ballot's g-chain): per bit the
+ *   step (acc, sq) then the step (sq, sq), acc takes the product only where the bit is set; the trailing square is kept;
+ *   hss_i = BigUintChip::pow_mod(hs, s_i) over EXACTLY s_bits bits in the same schedule (pz_paillier_partial's chain on the base hs);
+ *   the step (gm_i, hss_i), whose remainder is c_i.
+ * Records a|b|q|r of 2*limbs_n words per field, ciphertext-major: entry i at records i * (2 m_bits + 2 s_bits + 1) and on; n is not
+ * in the count.  steps_out (steps_cap >= count * (2 m_bits + 2 s_bits + 1) records, else PZ_ERR_CAPACITY) may be NULL: the values only.
+ * Refusals, in this order: a null pointer, limbs_n = 0, count, m_bits or s_bits out of range: PZ_ERR_INVALID; 2*limbs_n > 128:
+ * PZ_ERR_UNSUPPORTED; a short steps_cap: PZ_ERR_CAPACITY; a message >= 2^m_bits or an s_i >= 2^s_bits: PZ_ERR_MESSAGE_RANGE; n = 0:
+ * PZ_ERR_ZERO_MODULUS -- all before any launch.  An hs >= n^2: PZ_ERR_RANGE (found by the kernel, which then writes nothing; the status
+ * is read before anything is copied out).  No output buffer is written on a refusal.  hs = 0 is not refused here
+ * (verifier.public_inputs("sballot") refuses it).
+ * One team per ciphertext runs both chains and the product, ONE launch for all entries, no workgroup waits on another; n^2 and its
+ * Barrett constants are formed once.  The messages and the s_i are SECRET: bit t of s_i is read from word t / 64, an address that
+ * depends on t alone, and reaches the accumulator as a lane-wise mask; no branch or address depends on m_i or s_i (the value-dependent
+ * trip count of mul_mod's Barrett correction remains, as in every K3 entry point), and the staged copies of ms and ss (host form: of
+ * the records too) in the context's workspace are overwritten before the call returns.
+ * _dev: d_steps_out is a DEVICE buffer; everything else as above.  (PZ_ABI_VERSION stays 7: additions.) */
+int pz_paillier_sballot(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t m_bits, uint32_t s_bits, const uint64_t* n,
+                        const uint64_t* g, const uint64_t* hs, const uint64_t* ms, const uint64_t* ss, uint64_t* steps_out,
+                        size_t steps_cap, uint64_t* c_out);
+int pz_paillier_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t m_bits, uint32_t s_bits, const uint64_t* n,
+                            const uint64_t* g, const uint64_t* hs, const uint64_t* ms, const uint64_t* ss, uint64_t* d_steps_out,
+                            size_t steps_cap, uint64_t* c_out);
+
 /* The mix: a verifiable shuffle's values.  A mixer takes c_1 .. c_K under the key n and publishes
  * c'_i = c_perm(i) * r_i^n mod n^2: the same plaintexts, re-randomised, in an order nobody else can follow.  K = count is a power of two
  * in 1 .. 1024; n: limbs_n words; cts = count x 2*limbs_n words; rs = count x limbs_n words; mixed_out = count x 2*limbs_n words (HOST).
@@ -681,6 +712,40 @@ int pz_mix_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, ui
                            size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride);
 int pz_mix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r, uint64_t* cells_out,
                         size_t capacity, size_t* n_public);
+
+/* Circuit kind 9, "sballot" (DESIGN.md section 15.18): under the key (n, g, hs) the K = count ciphertexts c_1 .. c_K (1 .. 1024) are
+ * short-randomness ballots c_i = g^m_i hs^s_i mod n^2 with m_i < 2^b, b = m_bits (1 .. 64), and s_i < 2^s_bits, s_bits = s_limbs *
+ * limb_bits with 1 <= s_limbs <= 2*limbs_n, and for K >= 2 the m_i add up to the public S.  Its shape is (K, b, s_limbs) and the key
+ * SIZE: no bit of n shapes it, so one proving and verifying key serves every election of a size.  The by-kind entry points refuse
+ * kind 9 and these take the three numbers (anything out of range: PZ_ERR_INVALID).  The stream, in emission order:
+ * assign_integer(n), assign_integer(g), assign_integer(hs, 2*enc_bits); load_witness(m_1 .. m_K); for K >= 2 FlexGate::sum as in kind
+ * 6; assign_integer(s_i, s_bits) for i = 1..K (s_limbs limbs each); square + refresh of n, once; load_zero; per ciphertext
+ * pow_mod(g_ext, m_i) over exactly b bits exactly as kind 6 ([1, 0], num_to_bits(m_i, b), b blocks of mul_mod(acc, sq), limb-wise
+ * select, square_mod(sq)), then pow_mod(hs, s_i) exactly as kind 7 emits a chain ([1, 0], then per limb of s_i num_to_bits(limb,
+ * limb_bits) and that limb's blocks), then mul_mod(gm_i, hss_i); then per ciphertext assign_integer(res_i, 2*enc_bits) and
+ * assert_equal_fresh(c_i, res_i).  The circuit compares nothing with n^2 and does not refuse hs = 0 (verifier.public_inputs does).
+ *   pz_sballot_cells         the stream's advice / lookup cell counts (host logic).
+ *   pz_sballot_expand_dev    the values.  inputs (HOST): n | g (ceil(limbs_n*limb_bits/64) words each) | hs (ceil(2*limbs_n*limb_bits/64)
+ *       words) | m_1 .. m_K (ONE word each; a message >= 2^b: PZ_ERR_MESSAGE_RANGE) | s_1 .. s_K (ceil(s_bits/64) words each; an s_i >=
+ *       2^s_bits: PZ_ERR_MESSAGE_RANGE) | res_1 .. res_K (as hs).  d_steps (device): the K (2 b + 2 s_bits + 1) records of
+ *       pz_paillier_sballot_dev AS THEY ARE, fields of 2*ceil(limbs_n*limb_bits/64) words (where that differs from
+ *       ceil(2*limbs_n*limb_bits/64) the records are repacked on the device first).  d_modulus: n^2 (device).  rows / col_stride as
+ *       pz_circuit_expand_dev.
+ *   pz_sballot_expand_cols_dev  the same with the advice cells in break-point columns, as pz_circuit_expand_cols_dev.
+ *   pz_sballot_public_cells  the stream indices of the exposed cells in statement order: n | g | hs | c_1 | .. | c_K (the limb cells of
+ *       n's, g's, hs's and every res_i's assign_integer) and, for K >= 2, S (the sum's last cell): n_public = 2 limbs_n + (K + 1) 2
+ *       limbs_n + (K >= 2). */
+int pz_sballot_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, uint32_t s_limbs,
+                     size_t* advice_cells, size_t* lookup_cells);
+int pz_sballot_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                          uint32_t s_limbs, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus, uint64_t* d_advice,
+                          uint64_t* d_lookup, size_t rows, size_t col_stride);
+int pz_sballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                               uint32_t s_limbs, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus,
+                               uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts, size_t n_adv_cols, size_t max_rows,
+                               size_t lookup_rows, size_t col_stride);
+int pz_sballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, uint32_t s_limbs,
+                            uint64_t* cells_out, size_t capacity, size_t* n_public);
 
 /* The same stream with the ADVICE cells in halo2-lib's break-point column layout -- what the dependency's assign_with_constraints
  * [D] does with the Context's cell list when it fills the basic-gate columns (reached from bench.rs:161-171 through keygen /
@@ -1183,6 +1248,15 @@ int pz_shplonk_free(pz_ctx* ctx, pz_shplonk* state);
  * to assign_integer(r_i)'s limbs extended by the load_zero cell, the final block's operands to the last layer's outputs and the
  * chain's result, each assert_equal_fresh's bit to the constant 1.  An ordinary pz_structure (n_steps_g = 0, n_steps_r = the records
  * of ONE r^n chain); pz_structure_expose works on it (statement: pz_mix_public_cells).
+ * pz_circuit_structure_sballot_dev: the structure of the short-randomness ballot (kind 9, pz_sballot_cells) of `count` ciphertexts
+ * (1 .. 1024), m_bits (1 .. 64) bits per message and exponents of s_limbs (1 .. 2 limbs_n) limbs.  It takes NO exponent: nothing of
+ * the key but its size shapes the circuit, and ONE key serves every election of a size (count, m_bits, s_limbs, limbs_n).  Every
+ * hs-chain's num_to_bits accumulators are tied to assign_integer(s_i)'s limb cells, every hs-chain's first sq to assign_integer(hs)'s
+ * limbs (all K chains run on ONE base), a message's load_witness cell to its chain's num_to_bits accumulator and to its operand in the
+ * sum, every g-chain's first sq to assign_integer(g)'s limbs extended by the load_zero cell, the final block's operands to the
+ * g-chain's and the hs-chain's last select outputs, its result to the assert_equal_fresh against res_i, each assert_equal_fresh's bit
+ * to the constant 1.  An ordinary pz_structure (n_steps_g = 2 m_bits, n_steps_r = the 2 s_limbs limb_bits records of ONE hs-chain);
+ * pz_structure_expose works on it (statement: pz_sballot_public_cells).
  * ------------------------------------------------------------------------------------------- */
 typedef struct pz_structure pz_structure;
 int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
@@ -1198,6 +1272,8 @@ int pz_circuit_structure_mix_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bi
                                  const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_circuit_structure_partial_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                      size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
+int pz_circuit_structure_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                     uint32_t m_bits, uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_structure_info(const pz_structure* st, size_t* n_adv, size_t* n_adv_filled, size_t* n_lk, size_t* max_rows, size_t* n_constants,
                       size_t* n_cells, size_t* n_lookups, size_t* n_steps_g, size_t* n_steps_r);
 int pz_structure_arrays(const pz_structure* st, const uint8_t** d_selectors, const uint32_t** d_map_col, const uint32_t** d_map_row,

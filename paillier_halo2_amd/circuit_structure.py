@@ -303,7 +303,8 @@ class StructureArrays:
     # n | g | c (encrypt, encrypt_uniform), n | g | m | c (decrypt), n | g | c1 | c2 | c (add), n | c_1 | .. | c_B | C (tally) or n | c_1 | .. | c_B | w_1 | .. |
     # w_B | C (wtally: a weight is ONE cell) -- pz_circuit_public_cells gives the same list -- or n | g | c_1 | .. | c_K | S (ballot: S is
     # the sum's last cell, present for K >= 2; pz_ballot_public_cells) -- or n | v | h | c_1 | u_1 | .. | c_K | u_K (partial;
-    # pz_partial_public_cells) -- or n | c_1 | .. | c_K | c'_1 | .. | c'_K (mix; pz_mix_public_cells)
+    # pz_partial_public_cells) -- or n | c_1 | .. | c_K | c'_1 | .. | c'_K (mix; pz_mix_public_cells) -- or n | g | hs | c_1 | .. | c_K | S
+    # (sballot; pz_sballot_public_cells)
     public_cells: Optional[np.ndarray] = None
 
 
@@ -312,7 +313,8 @@ def _exp_bits(e: int) -> List[int]:
 
 
 def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: int = 0, exp_r: int = 0, device: Optional[str] = None,
-                     count: Optional[int] = None, w_bits: Optional[int] = None, m_bits: Optional[int] = None) -> StructureArrays:
+                     count: Optional[int] = None, w_bits: Optional[int] = None, m_bits: Optional[int] = None,
+                     s_limbs: Optional[int] = None) -> StructureArrays:
     """kind 'encrypt': exp_g = the message m, exp_r = the modulus n -- only their BITS are used, as in the reference's circuit
     (pow_mod_fixed_exp, paillier.rs:50-55); kind 'add': no exponents; kind 'encrypt_uniform' (the uniform-shape circuit, SURVEY 8f rank
     4): exp_g is ignored -- the message's bits are witness cells, ONE structure serves every message of a key; kind 'tally': count = B
@@ -327,7 +329,11 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     assign_integer of 2 Ln limbs every chain decomposes (kind 2's pow_mod walk over all its limbs) -- the shape is K and the key size;
     kind 'mix' (circuit kind 8): count = K = 2^d ciphertexts go through the Benes network of mix.py (per switch
     assert_bit of a fresh bit cell, then per limb the two selects under it) and leave as d_i r_i^n mod n^2, exp_r = the modulus n (its
-    bits shape every r^n chain) -- the shape is K and n.
+    bits shape every r^n chain) -- the shape is K and n;
+    kind 'sballot' (circuit kind 9): count = K short-randomness ballots c_i = g^m_i hs^s_i under one key, each
+    message ONE witness cell decomposed into m_bits in-circuit bits as in 'ballot', each s_i an assign_integer of s_limbs limbs that its
+    chain decomposes limb by limb ('partial's walk) from the ONE base hs, for K >= 2 the sum of the messages -- no exponent is taken:
+    the shape is K, m_bits, s_limbs and the key size, so ONE structure serves every key of a size.
     device: None -> numpy arrays; a torch device ("cuda") -> the template is tiled THERE and `src` / `lookup_src` are tensors on it (at
     config c2 the tiled arrays are 3.2 GB: 0.9 s of host numpy against a few ms; `columns` takes either)."""
     dev = None
@@ -362,12 +368,12 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             constants.append(v)
         return const_id[v]
 
-    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial", "mix"):
+    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial", "mix", "sballot"):
         raise ValueError(f"unknown circuit kind {kind!r}")
     # 'decrypt' (circuit kind 5) is the uniform-shape circuit cell for cell: the exposed list alone differs
     statement, kind = kind, ("encrypt_uniform" if kind == "decrypt" else kind)
-    if (kind in ("tally", "wtally", "ballot", "partial", "mix")) != (count is not None):
-        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial' and 'mix', which need it")
+    if (kind in ("tally", "wtally", "ballot", "partial", "mix", "sballot")) != (count is not None):
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix' and 'sballot', which need it")
     if kind == "mix":
         if not mix.is_count(count):
             raise ValueError(f"a mix takes count = 1, 2, 4 .. {mix.MIX_MAX} ciphertexts, not {count}")
@@ -375,14 +381,18 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             raise ValueError("a mix's structure needs exp_r = the modulus n")
     if kind == "partial" and not 1 <= count <= layout.PARTIAL_MAX:
         raise ValueError(f"a trustee opens count = 1 .. {layout.PARTIAL_MAX} ciphertexts in one proof, not {count}")
-    if (kind == "ballot") != (m_bits is not None):
-        raise ValueError("m_bits belongs to kind 'ballot', which needs it")
-    if kind == "ballot":
+    if (kind in ("ballot", "sballot")) != (m_bits is not None):
+        raise ValueError("m_bits belongs to kinds 'ballot' and 'sballot', which need it")
+    if (kind == "sballot") != (s_limbs is not None):
+        raise ValueError("s_limbs belongs to kind 'sballot', which needs it")
+    if kind == "sballot" and not 1 <= s_limbs <= L:
+        raise ValueError(f"a short-randomness ballot's exponent has s_limbs = 1 .. {L} limbs, not {s_limbs}")
+    if kind in ("ballot", "sballot"):
         if not 1 <= count <= layout.BALLOT_MAX:
             raise ValueError(f"a ballot takes count = 1 .. {layout.BALLOT_MAX} ciphertexts, not {count}")
         if not 1 <= m_bits <= layout.BALLOT_MAX_BITS:
             raise ValueError(f"a ballot's message has m_bits = 1 .. {layout.BALLOT_MAX_BITS} bits, not {m_bits}")
-        if exp_r < 1:
+        if kind == "ballot" and exp_r < 1:
             raise ValueError("a ballot's structure needs exp_r = the modulus n")
     if (kind == "wtally") != (w_bits is not None):
         raise ValueError("w_bits belongs to kind 'wtally', which needs it")
@@ -406,8 +416,9 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     elif kind == "mix":
         ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
         rs_c = [_assign(w, Ln, limb_bits, lb) for _ in range(count)]
-    elif kind == "ballot":
+    elif kind in ("ballot", "sballot"):
         g_c = _assign(w, Ln, limb_bits, lb)
+        hs_c = _assign(w, L, limb_bits, lb) if kind == "sballot" else []        # hs: the key's second base, full width
         ms_c = [w.put() for _ in range(count)]                                 # load_witness(m_i): one cell each, no gate
         sum_c = None
         if count >= 2:
@@ -418,7 +429,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
                 w.putc(1)
                 w.put(ms_c[i])
                 sum_c = w.put()
-        rs_c = [_assign(w, Ln, limb_bits, lb) for _ in range(count)]
+        rs_c = [_assign(w, s_limbs if kind == "sballot" else Ln, limb_bits, lb) for _ in range(count)]   # r_i; 'sballot': s_i
     else:
         g_c = _assign(w, Ln, limb_bits, lb)
         x_c = _assign(w, Ln, limb_bits, lb)
@@ -643,6 +654,32 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             off, rfin = blocks(off, np.asarray(gm, dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
             c_cells.append(rfin[0].tolist())
         n_steps[0] = 2 * m_bits
+    elif kind == "sballot":
+        # per ciphertext: pow_mod(g_ext, m_i) as 'ballot'; pow_mod(hs, s_i) as 'partial' walks a chain -- [1, 0], then per limb of s_i
+        # num_to_bits of ITS limb cell and limb_bits bit blocks, every entry's chain from the SAME hs cells --; the final mul_mod
+        ut = _uniform_template(L, limb_bits, lb)
+        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
+        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
+        ut_mask[ut.gates] = 1
+        c_cells = []
+        for i in range(count):
+            wc = _Walk(off)
+            one = wc.putc(1)
+            z2 = wc.putc(0)
+            off = flush(wc)
+            off, gm, _ = bit_chain(off, ut, ut_const, ut_mask, ms_c[i], m_bits, np.asarray([one] + [z2] * (L - 1), dtype=np.int64),
+                                   np.asarray(ext_l(g_c), dtype=np.int64))
+            wc = _Walk(off)
+            one = wc.putc(1)
+            z2 = wc.putc(0)
+            off = flush(wc)
+            acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
+            sq_cells = np.asarray(hs_c, dtype=np.int64)
+            for li in range(s_limbs):
+                off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, rs_c[i][li], limb_bits, acc_cells, sq_cells)
+            off, rfin = blocks(off, np.asarray(gm, dtype=np.int64)[None, :], acc_cells[None, :])
+            c_cells.append(rfin[0].tolist())
+        n_steps[0], n_steps[1] = 2 * m_bits, 2 * s_limbs * limb_bits
     elif kind == "wtally":
         # per ciphertext pow_mod(c_i, w_i) over w_bits in-circuit bits: [1, 0], num_to_bits of the weight's cell, the bit blocks; the
         # chain starts from its OWN [one, zero ..] and from assign_integer(c_i)'s limb cells.  Its power is the last select's outputs.
@@ -710,7 +747,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         n_steps[0] = nb
     else:
         off, rfin = blocks(off, np.asarray(ext_l(x_c), dtype=np.int64)[None, :], np.asarray(ext_l(y_c), dtype=np.int64)[None, :])
-    roots = c_cells if kind in ("ballot", "partial", "mix") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
+    roots = c_cells if kind in ("ballot", "partial", "mix", "sballot") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
     ws = _Walk(off)
     res_all, eq_cells = [], []
     for c_limbs in roots:
@@ -739,8 +776,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             exposed += list(ct_c[j]) + res_all[(j + 1) * L:(j + 2) * L]
     elif kind == "mix":
         exposed = list(n_c) + [c for ct in ct_c for c in ct] + res_all
-    elif kind == "ballot":
-        exposed = list(n_c) + list(g_c) + res_all + ([sum_c] if sum_c is not None else [])
+    elif kind in ("ballot", "sballot"):
+        exposed = list(n_c) + list(g_c) + list(hs_c) + res_all + ([sum_c] if sum_c is not None else [])
     elif kind in ("tally", "wtally"):
         exposed = list(n_c) + [c for ct in ct_c for c in ct] + list(wt_c) + list(res_c)
     else:

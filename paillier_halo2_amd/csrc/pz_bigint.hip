@@ -1105,6 +1105,65 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_ballot_enc(co
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
+// ---- the entries of a short-randomness ballot (pz_paillier_sballot): c_i = g^m_i hs^s_i mod n^2 for K messages under
+// ONE key whose hs = h^n mod n^2 is public.  k_ballot_enc with its r^n chain replaced by k_partial_pow's: one team per ciphertext runs
+// g^m_i over exactly m_bits bits, then hs^s_i over exactly s_bits bits (pow_mod_uniform both: (acc, sq) then (sq, sq) for EVERY bit,
+// the trailing square kept), then the final product -- K entries in one launch, no team waits on another.  The Barrett constants come
+// from k_tally_setup, once for all.  m_i and s_i are SECRET: bit t of s_i is read from word t / 64 of the entry's s_words words, an
+// address that follows the loop counter alone, and both reach their accumulator as a lane-wise mask over both candidates (ld_select),
+// never as a branch or an address.  Every trip count is a launch argument.  (What a mul_mod does with its VALUES is K3's as everywhere:
+// the Barrett correction's trip count follows the operands.)  An hs >= n^2 (public) is ST_RANGE.
+// recs (may be null: the values only): entry i at records i * per .. + per, per = 2 m_bits + 2 s_bits + 1: the g-chain's, the hs-chain's,
+// then (gm_i, hss_i, q, c_i).  per is held against the loops' own counts before any store; a disagreement is ST_INTERNAL, never a write
+// past the entry.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_sballot_enc(const u64* __restrict__ mod, const u64* __restrict__ g,
+                                                                                  const u64* __restrict__ hs, const u64* __restrict__ ms,
+                                                                                  const u64* __restrict__ ss, unsigned m_bits, unsigned s_bits,
+                                                                                  unsigned s_words, unsigned per, unsigned count,
+                                                                                  u64* __restrict__ recs, u64* __restrict__ c_out, unsigned Ln,
+                                                                                  u32* __restrict__ status) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (*block_ok<E>(mod) == 0) return;   // zero modulus (the same word for every workgroup)
+    if (blockIdx.x >= count) return;
+    const unsigned wave = threadIdx.x >> 6, L = 2 * Ln;
+    TeamCtx<E> T;
+    team_init(T, s_team);
+    BarrettCtx<E> B;
+    barrett_from_block(B, mod, L, s_scratch[wave]);
+    const size_t entry = blockIdx.x;
+    unsigned st = ST_OK;
+    const unsigned chains = 2 * m_bits + 2 * s_bits;   // the records of both chains; the final product is record `chains`
+    if (chains + 1 != per) st |= ST_INTERNAL;
+    // the four waves of the team hold the same values: one of them writes, and only where every record index of the entry is below per
+    const bool writer = wave == 0 && recs != nullptr && chains + 1 == per;
+    u64* const base = writer ? recs + entry * per * 4 * (size_t)L : nullptr;
+    const LD<E> hs0 = ld_load<E>(hs, L);
+    {
+        LD<E> d;
+        if (!ld_sub(d, hs0, ld_load<E>(block_modulus<E>(mod), C))) {   // hs >= n^2 (public, the same for every team): nothing is written
+            if (lane_id() == 0) atomicOr(status, st | ST_RANGE);
+            return;
+        }
+    }
+    LD<E> gm = ld_small<E>(1);
+    {
+        LD<E> sq = ld_load<E>(g, Ln);
+        st |= pow_mod_uniform(B, T, gm, sq, ms + entry, m_bits, base);
+    }
+    LD<E> hss = ld_small<E>(1);
+    {
+        LD<E> sq = hs0;
+        st |= pow_mod_uniform(B, T, hss, sq, ss + entry * s_words, s_bits, writer ? base + (size_t)2 * m_bits * 4 * L : nullptr);
+    }
+    LD<E> q, c;
+    st |= mul_mod(B, q, c, gm, hss, TeamMul<E>{&T});
+    if (writer) rec_store(base + (size_t)chains * 4 * L, gm, hss, q, c, L);
+    if (wave == 0) ld_store(c_out + entry * L, c, L);
+    if (st && lane_id() == 0) atomicOr(status, st);
+}
+
 // ---- a mixer's shuffle (pz_paillier_mix): one layer of the Benes network over `count` integers of L limbs that stay
 // in place.  One launch per layer, ordered by the stream alone; one wave per switch.  Switch s of a layer on bit beta is the s-th
 // position j with that bit clear, its partner j | 2^beta: both follow from s and beta.  The switch's bit is SECRET (the bits are the
@@ -2029,6 +2088,99 @@ extern "C" int pz_paillier_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t coun
                                       const uint64_t* ms, const uint64_t* rs, uint64_t* d_steps_out, size_t steps_cap, uint32_t* n_steps_r,
                                       uint64_t* c_out) {
     return ballot_impl(ctx, limbs_n, count, m_bits, n, g, ms, rs, d_steps_out, 1, steps_cap, n_steps_r, c_out);
+}
+
+// The short-randomness ballot: c_i = g^m_i hs^s_i mod n^2 for `count` messages of m_bits bits and exponents of s_bits
+// bits under one key (k_sballot_enc, one team per ciphertext, one launch).  Records ciphertext-major, 2 m_bits + 2 s_bits + 1 per
+// entry.  The messages and the s_i are secrets: their staged copies (and, in the host form, the staged records, which repeat them) are
+// overwritten before the call returns, on every path past the staging.  The status is read before anything is copied out: a refused
+// call (an hs >= n^2) writes nothing.
+struct SballotArgs {
+    uint32_t Ln, m_bits, s_bits, s_words, per;
+    size_t count;
+    const uint64_t *n, *g, *hs, *ms, *ss;
+    uint64_t *steps_out, *c_out;
+    int steps_on_device;
+    u64 *d_n, *d_g, *d_hs, *d_ms, *d_ss, *d_c, *d_mod, *d_steps;
+    u32* d_status;
+};
+static int sballot_run(pz_ctx* ctx, const SballotArgs& a) {
+    const unsigned L = 2 * a.Ln, C = capacity(L);
+    const size_t nb = (size_t)a.Ln * 8, lb = (size_t)L * 8;
+    HIPCHK(ctx, hipMemcpyAsync(a.d_n, a.n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_g, a.g, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_hs, a.hs, lb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_ms, a.ms, a.count * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_ss, a.ss, a.count * a.s_words * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(a.d_status, 0, 4, ctx->stream));
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        PZCHK(launch_barrett_setup(ctx, C, a.d_n, a.Ln, 1, a.d_mod, a.d_status));
+        K3_LAUNCH(ctx, k_sballot_enc, C, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, a.d_mod, a.d_g, a.d_hs, a.d_ms, a.d_ss, a.m_bits,
+                  a.s_bits, a.s_words, a.per, (unsigned)a.count, a.d_steps, a.d_c, a.Ln, a.d_status);
+    }
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&st, a.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    PZCHK(status_to_rc(ctx, st));
+    HIPCHK(ctx, hipMemcpyAsync(a.c_out, a.d_c, a.count * lb, hipMemcpyDeviceToHost, ctx->stream));
+    if (a.steps_out && !a.steps_on_device)
+        HIPCHK(ctx, hipMemcpyAsync(a.steps_out, a.d_steps, a.count * a.per * 4 * lb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PZ_OK;
+}
+static int sballot_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t m_bits, uint32_t s_bits, const uint64_t* n, const uint64_t* g,
+                        const uint64_t* hs, const uint64_t* ms, const uint64_t* ss, uint64_t* steps_out, int steps_on_device,
+                        size_t steps_cap, uint64_t* c_out) {
+    if (!ctx || !n || !g || !hs || !ms || !ss || !c_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_BALLOT_MAX || m_bits < 1 || m_bits > 64 || s_bits < 1 || s_bits > 128 * (uint64_t)Ln) return PZ_ERR_INVALID;
+    if (2 * (uint64_t)Ln > 128) return PZ_ERR_UNSUPPORTED;
+    const unsigned L = 2 * Ln;
+    const uint32_t per = 2 * m_bits + 2 * s_bits + 1, s_words = (s_bits + 63) / 64;
+    if (steps_out && steps_cap < count * per) return PZ_ERR_CAPACITY;
+    // before any launch: the circuit's num_to_bits of such a message or exponent cannot hold, and the chain reads s_bits bits and no more
+    for (size_t i = 0; i < count; ++i) {
+        if (m_bits < 64 && ms[i] >> m_bits) return PZ_ERR_MESSAGE_RANGE;
+        if ((s_bits & 63) && ss[i * s_words + s_words - 1] >> (s_bits & 63)) return PZ_ERR_MESSAGE_RANGE;
+    }
+    if (bitlen_limbs(n, Ln) == 0) return PZ_ERR_ZERO_MODULUS;
+    PZ_ENTER(ctx);
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8;
+    // n | g | hs | m_1 .. m_count | s_1 .. s_count | c_1 .. c_count | Barrett constants | status
+    const size_t pub_bytes = (2 * nb + lb + 255) & ~(size_t)255, sec_bytes = (count * 8 + count * s_words * 8 + 255) & ~(size_t)255;
+    const size_t c_bytes = (count * lb + 255) & ~(size_t)255, mod_bytes = mod_block_words(capacity(L)) * 8;
+    void* d;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, pub_bytes + sec_bytes + c_bytes + mod_bytes + 256, &d));
+    char* p = (char*)d;
+    SballotArgs a{};
+    a.Ln = Ln; a.m_bits = m_bits; a.s_bits = s_bits; a.s_words = s_words; a.per = per; a.count = count;
+    a.n = n; a.g = g; a.hs = hs; a.ms = ms; a.ss = ss; a.steps_out = steps_out; a.c_out = c_out; a.steps_on_device = steps_on_device;
+    a.d_n = (u64*)p;
+    a.d_g = (u64*)(p + nb);
+    a.d_hs = (u64*)(p + 2 * nb);
+    a.d_ms = (u64*)(p + pub_bytes);
+    a.d_ss = a.d_ms + count;
+    a.d_c = (u64*)(p + pub_bytes + sec_bytes);
+    a.d_mod = (u64*)(p + pub_bytes + sec_bytes + c_bytes);
+    a.d_status = (u32*)(p + pub_bytes + sec_bytes + c_bytes + mod_bytes + 64);
+    a.d_steps = steps_on_device ? steps_out : nullptr;
+    const size_t rec_bytes = steps_out && !steps_on_device ? count * per * 4 * lb : 0;
+    if (rec_bytes) {
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_B, rec_bytes, &t));
+        a.d_steps = (u64*)t;
+    }
+    return wipe_secrets_and_sync(ctx, sballot_run(ctx, a), a.d_ms, sec_bytes, a.d_steps, rec_bytes);
+}
+extern "C" int pz_paillier_sballot(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t m_bits, uint32_t s_bits, const uint64_t* n,
+                                   const uint64_t* g, const uint64_t* hs, const uint64_t* ms, const uint64_t* ss, uint64_t* steps_out,
+                                   size_t steps_cap, uint64_t* c_out) {
+    return sballot_impl(ctx, limbs_n, count, m_bits, s_bits, n, g, hs, ms, ss, steps_out, 0, steps_cap, c_out);
+}
+extern "C" int pz_paillier_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t m_bits, uint32_t s_bits, const uint64_t* n,
+                                       const uint64_t* g, const uint64_t* hs, const uint64_t* ms, const uint64_t* ss, uint64_t* d_steps_out,
+                                       size_t steps_cap, uint64_t* c_out) {
+    return sballot_impl(ctx, limbs_n, count, m_bits, s_bits, n, g, hs, ms, ss, d_steps_out, 1, steps_cap, c_out);
 }
 
 // The mix: c'_i = c_perm(i) r_i^n mod n^2 for `count` = 2^d ciphertexts under one key.  The 2d - 1 layers of the

@@ -439,7 +439,13 @@ struct Stream {
 // refresh, load_zero; the Benes network as ONE walked part -- per layer and switch assert_bit of the switch's own bit cell, then per
 // limb select(in[j'], in[j], b) and select(in[j], in[j'], b), the operands the previous layer's outputs --; per output
 // pow_mod_fixed_exp(r_i_ext, exp_r = n) and the block mul_mod(d_i, rn_i); then per output res_i and assert_equal_fresh.
-int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, unsigned w_bits, Stream& S) {
+// kind 9 (the short-randomness ballot): n, g, hs at full width, `count` load_witness cells (the messages), for
+// count >= 2 FlexGate::sum over them, assign_integer(s_i) of s_limbs limbs for every entry, square + refresh, load_zero; per entry
+// pow_mod(g_ext, m_i) over w_bits (= m_bits) in-circuit bits as kind 6, pow_mod(hs, s_i) as kind 7 walks a chain -- [1, 0], then per limb
+// of s_i num_to_bits of ITS limb cell and W uniform blocks, the first sq hs's limb cells -- and the final block; then per entry res_i and
+// assert_equal_fresh.  No exponent of the key shapes it: one structure serves every key of a size.
+int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, unsigned w_bits,
+                 unsigned s_limbs, Stream& S) {
     const unsigned L = 2 * Ln;
     S.tmpls.reserve(2);                  // (references to the templates stay valid when a circuit with in-circuit bits adds the second one)
     S.tmpls.push_back(block_template(L, W, lb));
@@ -452,8 +458,9 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
     std::vector<i64> wt_c;
     std::vector<std::vector<i64>> rs_c;
     i64 sum_c = NONE;
-    if (kind == 6) {
+    if (kind == 6 || kind == 9) {
         g_c = assign(w, Ln, W, lb);
+        if (kind == 9) x_c = assign(w, L, W, lb);   // hs: the key's second base, full width
         for (size_t i = 0; i < count; ++i) wt_c.push_back(w.put());   // load_witness(m_i): one cell, no gate
         if (count >= 2) {
             // FlexGate::sum: m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..; a window every 3 cells, the operands copies of the cells above
@@ -465,7 +472,7 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
                 sum_c = w.put();
             }
         }
-        for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, Ln, W, lb));
+        for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, kind == 9 ? s_limbs : Ln, W, lb));   // r_i; kind 9: s_i
     } else if (kind == 8) {
         for (size_t i = 0; i < count; ++i) ct_c.push_back(assign(w, L, W, lb));
         for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, Ln, W, lb));
@@ -637,6 +644,31 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             off = S.blocks(off, 0, std::vector<i64>(acc_cells), std::vector<i64>(rn), {}, 1);
         }
         S.n_steps_g = 2 * (size_t)w_bits;
+    } else if (kind == 9) {
+        S.tmpls.push_back(uniform_template(L, W, lb));
+        S.bind_template_constants(1);
+        for (size_t i = 0; i < count; ++i) {
+            Walk wb(off);   // the g-chain's head: assign_constant(1), load_zero, then num_to_bits
+            const i64 one = wb.putc(c_small(1)), z2 = wb.putc(c_small(0));
+            std::vector<i64> gm_cells(L, z2), sq_cells = ext_l(g_c);
+            gm_cells[0] = one;
+            off = bit_chain(off, wb, wt_c[i], w_bits, gm_cells, sq_cells);
+            // pow_mod(hs, s_i): kind 7's walk over the s_limbs limbs of s_i -- every entry's chain starts from the SAME hs cells
+            Walk wc(off);
+            const i64 one_s = wc.putc(c_small(1)), z2_s = wc.putc(c_small(0));
+            off = S.flush(wc);
+            std::vector<i64> acc_cells(L, z2_s);
+            sq_cells = x_c;
+            acc_cells[0] = one_s;
+            for (unsigned li = 0; li < s_limbs; ++li) {
+                Walk wl(off);
+                off = bit_chain(off, wl, rs_c[i][li], W, acc_cells, sq_cells);
+            }
+            roots.push_back(block_r(off));
+            off = S.blocks(off, 0, std::move(gm_cells), std::move(acc_cells), {}, 1);
+        }
+        S.n_steps_g = 2 * (size_t)w_bits;
+        S.n_steps_r = 2 * (size_t)s_limbs * W;
     } else if (kind == 8) {
         Walk wn(off);
         auto select = [&](i64 x, i64 y, i64 s) {   // FlexGate::select(x, y, s): [d | 1 | y | x | y | s | d | out], windows at 0 and 4
@@ -1069,9 +1101,9 @@ extern "C" int pz_structure_arrays(const pz_structure* st, const uint8_t** d_sel
 }
 
 static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, const uint64_t* exp_g,
-                          const uint64_t* exp_r, size_t count, uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors,
-                          pz_structure** out) {
-    if (!ctx || !out || kind < 0 || kind > 8 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+                          const uint64_t* exp_r, size_t count, uint32_t w_bits, uint32_t s_limbs, size_t minimum_rows,
+                          uint32_t blinding_factors, pz_structure** out) {
+    if (!ctx || !out || kind < 0 || kind > 9 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
     const int handle_kind = kind;   // kind 5 ("decrypt") is kind 2's circuit under another statement: pz_structure_expose alone tells them apart
     if (kind == 5) kind = 2;
     if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
@@ -1080,6 +1112,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     if (kind == 6 && (count < 1 || count > 1024 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
     if (kind == 7 && (count < 1 || count > 1024)) return PZ_ERR_INVALID;
     if (kind == 8 && (count < 1 || count > 1024 || (count & (count - 1)) != 0)) return PZ_ERR_INVALID;
+    if (kind == 9 && (count < 1 || count > 1024 || w_bits < 1 || w_bits > 64 || s_limbs < 1 || s_limbs > 2 * limbs_n)) return PZ_ERR_INVALID;
     if (((kind == 0 || kind == 2 || kind == 6 || kind == 8) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
     const i64 n = (i64)1 << k;
     const i64 unusable = (i64)blinding_factors + 3;
@@ -1088,7 +1121,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     PZ_ENTER(ctx);
     Stream S;
     try {
-        PZCHK(build_stream(kind, limbs_n, limb_bits, lookup_bits, exp_g, exp_r, count, w_bits, S));
+        PZCHK(build_stream(kind, limbs_n, limb_bits, lookup_bits, exp_g, exp_r, count, w_bits, s_limbs, S));
     } catch (const std::bad_alloc&) {
         return PZ_ERR_OOM;
     }
@@ -1241,29 +1274,37 @@ extern "C" int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n,
                                         const uint64_t* exp_g, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
                                         pz_structure** out) {
     if ((kind < 0 || kind > 2) && kind != 5) return PZ_ERR_INVALID;   // (the tallies have entry points of their own: this one has no place for their count)
-    return structure_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, k, exp_g, exp_r, 0, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, k, exp_g, exp_r, 0, 0, 0, minimum_rows, blinding_factors, out);
 }
 extern "C" int pz_circuit_structure_tally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                               size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 3, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 3, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, 0, minimum_rows, blinding_factors, out);
 }
 extern "C" int pz_circuit_structure_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                                uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 4, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, w_bits, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 4, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, w_bits, 0, minimum_rows, blinding_factors, out);
 }
 // the ballot (kind 6): count ciphertexts (1 .. 1024) of m_bits-bit messages (1 .. 64) under the key whose modulus is exp_r
 extern "C" int pz_circuit_structure_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                                uint32_t m_bits, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
                                                pz_structure** out) {
-    return structure_impl(ctx, 6, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, m_bits, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 6, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, m_bits, 0, minimum_rows, blinding_factors, out);
 }
 // a trustee's partial decryptions (kind 7): count ciphertexts (1 .. 1024) opened under one share; the shape is count and the key size alone
 extern "C" int pz_circuit_structure_partial_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                                 size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 7, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 7, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, 0, minimum_rows, blinding_factors, out);
 }
 // the mix (kind 8): count = 2^d ciphertexts (1 .. 1024) under the key whose modulus is exp_r; the shape is count and n alone
 extern "C" int pz_circuit_structure_mix_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                             const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 8, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 8, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, 0, 0, minimum_rows, blinding_factors, out);
+}
+// the short-randomness ballot (kind 9): count ciphertexts (1 .. 1024) of m_bits-bit messages (1 .. 64) with exponents of s_limbs limbs
+// (1 .. 2 limbs_n); the shape is (count, m_bits, s_limbs) and the key SIZE alone -- no exponent of the key enters it
+extern "C" int pz_circuit_structure_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                                uint32_t m_bits, uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors,
+                                                pz_structure** out) {
+    return structure_impl(ctx, 9, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, m_bits, s_limbs, minimum_rows, blinding_factors,
+                          out);
 }

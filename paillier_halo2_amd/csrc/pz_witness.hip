@@ -1812,6 +1812,143 @@ extern "C" int pz_mix_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t li
     return mix_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, true, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows},
                            limbs_n, limb_bits, lookup_bits, count, n_steps_r, bits, d_routes);
 }
+
+// ---- the short-randomness ballot (circuit kind 9): K ciphertexts c_i = g^m_i hs^s_i mod n^2 under one key.
+// Stream: assign n, g; assign hs at full width; load_witness(m_1 .. m_K); K >= 2: FlexGate::sum; assign s_1 .. s_K (s_limbs limbs
+// each); square + refresh, load_zero; per entry [the chain of m_i, b bits, as kind 6 | pow_mod(hs, s_i) as kind 7 emits a chain: 1, 0,
+// then per limb of s_i num_to_bits and W bit blocks | mul_mod(gm_i, hss_i)]; per entry a result block (res_i against the remainder of
+// the entry's last record).  inputs: n | g | hs (L64 words) | m_1 .. m_K (one word each) | s_1 .. s_K (ceil(s_limbs W / 64) words
+// each) | res_1 .. res_K.  Records are pz_paillier_sballot_dev's, as it leaves them: entry-major, 2 b + 2 s_limbs W + 1 each, fields
+// of 2 ceil(Ln W / 64) words.  No arithmetic of its own: the bits, select, expand, assign and result kernels above.
+#define SBALLOT_MAX 1024
+struct SballotP {
+    size_t K, per, s_limbs, s_words, a_hs, l_hs, a_msgs, a_ss, l_ss, a_ent, l_ent, ent_stride, head, g_cells, limb_stride;
+    size_t in_hs, in_ms, in_ss;   // word offsets inside `inputs`
+    unsigned rw;                  // words per field of a record as K3 writes them
+    ResP res;                     // with the sum: block 0 of k_circuit_results writes it
+};
+static int make_sballot_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, uint32_t m_bits, uint32_t s_limbs, CircP& C,
+                               SballotP& B, size_t* adv_total, size_t* lk_total) {
+    if (count < 1 || count > SBALLOT_MAX || m_bits < 1 || m_bits > 64 || s_limbs < 1 || s_limbs > 2 * (uint64_t)limbs_n) return PZ_ERR_INVALID;
+    PZCHK(circ_base(limbs_n, limb_bits, lb, 9, C));
+    memset(&B, 0, sizeof B);
+    const size_t W = limb_bits, s_bits = (size_t)s_limbs * W;
+    B.K = count;
+    B.s_limbs = s_limbs;
+    B.s_words = (s_bits + 63) / 64;
+    B.per = 2 * (size_t)m_bits + 2 * s_bits + 1;
+    B.rw = 2 * C.words_n;
+    B.in_hs = 2 * (size_t)C.words_n;
+    B.in_ms = B.in_hs + C.e.L64;
+    B.in_ss = B.in_ms + count;
+    size_t a = 0, l = 0;
+    assign_inputs(C, 2, a, l);
+    B.a_hs = a; B.l_hs = l; a += 2 * asg_adv(C); l += 2 * asg_lk(C);
+    B.a_msgs = a; a += count;
+    B.res.sum_n = count; B.res.in_ms = B.in_ms;
+    B.res.a_sum = a; a += count >= 2 ? 1 + 3 * (count - 1) : 0;
+    B.a_ss = a; B.l_ss = l;
+    a += count * s_limbs * (1 + (size_t)C.rc_adv); l += count * s_limbs * (size_t)C.rc_lk;
+    square_refresh_cells(C, a, l);
+    load_zero_cell(C, a);
+    B.head = 2 + nbits_cells(m_bits);
+    B.g_cells = B.head + m_bits * bit_stride(C);
+    B.limb_stride = nbits_cells(W) + W * bit_stride(C);
+    B.ent_stride = B.g_cells + 2 + s_limbs * B.limb_stride + C.e.cells;
+    B.a_ent = a; B.l_ent = l;
+    a += count * B.ent_stride; l += count * B.per * C.e.lookups;
+    // the [1, 0] of pow_mod(hs, s_i) stands behind the g-chain
+    B.res.a_head = B.a_ent + B.g_cells; B.res.head_stride = B.ent_stride;
+    B.res.rec0 = B.per - 1; B.res.rec_stride = B.per; B.res.field = 3;
+    result_blocks(C, B.res, count, B.in_ss + count * B.s_words, a, l);
+    *adv_total = a;
+    *lk_total = l;
+    return PZ_OK;
+}
+
+extern "C" int pz_sballot_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, uint32_t s_limbs,
+                                size_t* advice_cells, size_t* lookup_cells) {
+    CircP C;
+    SballotP B;
+    size_t a, l;
+    const int rc = make_sballot_params(limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs, C, B, &a, &l);
+    return put_cells(rc, a, l, advice_cells, lookup_cells);
+}
+
+static int sballot_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                               uint32_t s_limbs) {
+    PZCHK(expand_check(A));
+    CircP C;
+    SballotP B;
+    size_t a, l;
+    PZCHK(make_sballot_params(limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs, C, B, &a, &l));
+    PZCHK(expand_layout(A, C));
+    const size_t W = limb_bits, s_bits = s_limbs * W;
+    for (size_t i = 0; i < count; ++i) {   // num_to_bits of such a message or of such an exponent's top limb cannot hold
+        if (m_bits < 64 && A.inputs[B.in_ms + i] >> m_bits) return PZ_ERR_MESSAGE_RANGE;
+        if ((s_bits & 63) && A.inputs[B.in_ss + (i + 1) * B.s_words - 1] >> (s_bits & 63)) return PZ_ERR_MESSAGE_RANGE;
+    }
+    pz_ctx* ctx = A.ctx;
+    PZ_ENTER(ctx);
+    const u64* in;
+    PZCHK(expand_stage(A, B.res.in_res + count * C.e.L64, nullptr, 0, &in));
+    const u64* recs = A.d_steps;
+    const size_t fields = count * B.per * 4;
+    if (B.rw != C.e.L64) {   // K3's fields are whole words of n twice over; K4's are the words 2 Ln limbs take
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_C, fields * C.e.L64 * 8, &t));
+        hipLaunchKernelGGL(k_mix_repack, dim3((unsigned)((fields * C.e.L64 + 255) / 256)), dim3(256), 0, ctx->stream, recs, B.rw, (u64*)t, C.e.L64,
+                           fields);
+        recs = (const u64*)t;
+    }
+    pz_timer tm(ctx, PZ_T_EXPAND);
+    Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
+    const size_t rec = 4 * (size_t)C.e.L64;   // words per step record
+    // n, g, square, refresh, load_zero
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, (const u64*)nullptr, adv, lk);
+    // assign_integer(hs): 2 Ln limbs from L64 words; assign_integer(s_i): s_limbs limbs from s_words words each
+    launch_assign(A, C, in, B.in_hs, C.nf, C.e.L64, 1, B.a_hs, B.l_hs);
+    launch_assign(A, C, in, B.in_ss, (unsigned)s_limbs, (unsigned)B.s_words, count, B.a_ss, B.l_ss);
+    // the g-chains, as the ballot's: the load_witness cell and the chain's head; the selects; the record pairs
+    hipLaunchKernelGGL(k_circuit_bits_many, dim3((unsigned)count), dim3(256), 0, ctx->stream, C.e, m_bits, in + B.in_ms, B.a_msgs, B.a_ent,
+                       B.ent_stride, adv);
+    hipLaunchKernelGGL(k_circuit_select_many, dim3((unsigned)(count * m_bits)), dim3(256), 0, ctx->stream, C.e, m_bits, in + B.in_ms, recs, B.per,
+                       B.a_ent, B.ent_stride, bit_stride(C), B.head, adv);
+    launch_chains(A, C, B.a_ent + 2, B.l_ent, recs, m_bits, count, B.ent_stride, B.per);
+    // the hs-chains (kind 7's walk): per entry s_i's num_to_bits limb by limb and the selects; then limb by limb the record pairs of ALL
+    // entries in one launch -- limb li's records start 2 b + 2 li W into an entry's, and so do their lookups
+    for (size_t i = 0; i < count; ++i) {
+        const size_t bits0 = B.a_ent + i * B.ent_stride + B.g_cells + 2;
+        const u64 *d_s = in + B.in_ss + i * B.s_words, *d_chain = recs + (i * B.per + 2 * (size_t)m_bits) * rec;
+        hipLaunchKernelGGL(k_circuit_bits, dim3((unsigned)s_limbs), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s, bits0,
+                           B.limb_stride, adv);
+        hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)s_bits), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s,
+                           d_chain, bits0, B.limb_stride, bit_stride(C), nbits_cells(W), adv);
+    }
+    for (size_t li = 0; li < s_limbs; ++li) {
+        const size_t r0 = 2 * (size_t)m_bits + li * 2 * W;
+        launch_chains(A, C, B.a_ent + B.g_cells + 2 + li * B.limb_stride, B.l_ent + r0 * C.e.lookups, recs + r0 * rec, W, count, B.ent_stride,
+                      B.per);
+    }
+    // the final block of every entry, and the result blocks with the [1, 0] of the hs-chains
+    launch_runs(A, C, B.a_ent + B.ent_stride - C.e.cells, B.l_ent, recs, 1, count, B.ent_stride, B.per, B.per - 1);
+    launch_results(A, C, B.res, count, in, recs);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+extern "C" int pz_sballot_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                                     uint32_t s_limbs, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus,
+                                     uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride) {
+    return sballot_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, false, rows, col_stride, nullptr, 0, 0}, limbs_n, limb_bits,
+                               lookup_bits, count, m_bits, s_limbs);
+}
+extern "C" int pz_sballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits,
+                                          uint32_t s_limbs, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus,
+                                          uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts, size_t n_adv_cols,
+                                          size_t max_rows, size_t lookup_rows, size_t col_stride) {
+    return sballot_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, true, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows},
+                               limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs);
+}
 #undef LIMB
 
 // host-pointer form (SURVEY.md section 8b `pz_witness_expand`): stages the trace up, expands on the device in groups

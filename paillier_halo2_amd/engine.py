@@ -562,6 +562,39 @@ class Engine:
                                                 steps_cap, C.byref(nr), _ptr(c)), "pz_paillier_ballot_dev")
         return c, nr.value
 
+    # the short-randomness ballot: c_i = g^m_i hs^s_i mod n^2, hs = h^n mod n^2 from keys.djn_generator
+    @staticmethod
+    def _sballot_args(limbs_n: int, n, g, hs, ms, ss, s_bits: int):
+        n, g, hs = _np(n).reshape(limbs_n), _np(g).reshape(limbs_n), _np(hs).reshape(2 * limbs_n)
+        ms = np.ascontiguousarray(ms, dtype=np.uint64).reshape(-1)
+        ss = _np(ss).reshape(-1, max(-(-s_bits // 64), 1))
+        if ms.shape[0] != ss.shape[0]:
+            raise ValueError("one message and one s per ciphertext")
+        return n, g, hs, ms, ss
+
+    def paillier_sballot(self, limbs_n: int, n, g, hs, ms, ss, m_bits: int, s_bits: int, want_steps: bool = True):
+        """c_i = g^m_i hs^s_i mod n^2 for K messages below 2^m_bits and K exponents below 2^s_bits under one key (pz.h
+        pz_paillier_sballot): hs (2*limbs_n,) words, ms K integers, ss (K, ceil(s_bits / 64)) words.  s_bits is the caller's: security
+        rests on the short-exponent assumption in <hs>.  Returns (c (K, 2*limbs_n), steps (K, 2 m_bits + 2 s_bits + 1, 4, 2*limbs_n) or
+        None)."""
+        L = 2 * limbs_n
+        n, g, hs, ms, ss = self._sballot_args(limbs_n, n, g, hs, ms, ss, s_bits)
+        count = ms.shape[0]
+        per = 2 * m_bits + 2 * s_bits + 1
+        steps = np.zeros((max(count, 1), per, 4, L), dtype=np.uint64) if want_steps else None
+        c = np.zeros((max(count, 1), L), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_sballot(self.ctx, limbs_n, count, m_bits, s_bits, _ptr(n), _ptr(g), _ptr(hs), _ptr(ms), _ptr(ss),
+                                             _ptr(steps) if want_steps else VP(), count * per, _ptr(c)), "pz_paillier_sballot")
+        return c, steps
+
+    def paillier_sballot_dev(self, limbs_n: int, n, g, hs, ms, ss, m_bits: int, s_bits: int, d_steps: int, steps_cap: int):
+        """the same with the records left on the device for K4 (d_steps: steps_cap x 4 x 2*limbs_n u64; 0: the values only).  Returns c."""
+        n, g, hs, ms, ss = self._sballot_args(limbs_n, n, g, hs, ms, ss, s_bits)
+        c = np.zeros((max(ms.shape[0], 1), 2 * limbs_n), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_sballot_dev(self.ctx, limbs_n, ms.shape[0], m_bits, s_bits, _ptr(n), _ptr(g), _ptr(hs), _ptr(ms), _ptr(ss),
+                                                 VP(d_steps), steps_cap, _ptr(c)), "pz_paillier_sballot_dev")
+        return c
+
     # the mix (DESIGN.md section 15.17): shuffle and re-randomise K = 2^d ciphertexts under one key
     @staticmethod
     def mix_route(perm) -> np.ndarray:
@@ -971,6 +1004,38 @@ class Engine:
         self._chk(self.L.pz_mix_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, n_steps_r, _ptr(inp), VP(bits.ctypes.data),
                                                 VP(d_routes), VP(d_steps), VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts),
                                                 n_adv_cols, max_rows, lookup_rows, col_stride), "pz_mix_expand_cols_dev")
+
+    # the short-randomness ballot (circuit kind 9, pz.h pz_sballot_*): its shape is (count, m_bits, s_limbs) and the key size alone
+    def sballot_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, m_bits: int, s_limbs: int):
+        a = C.c_size_t()
+        l = C.c_size_t()
+        self._chk(self.L.pz_sballot_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs, C.byref(a), C.byref(l)), "pz_sballot_cells")
+        return a.value, l.value
+
+    def sballot_public_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, m_bits: int, s_limbs: int):
+        """stream indices of the exposed cells in statement order: n | g | hs | c_1 .. c_K | S (K >= 2)"""
+        out = np.zeros(2 * limbs_n * (max(count, 1) + 2) + 1, dtype=np.uint64)
+        npub = C.c_size_t()
+        self._chk(self.L.pz_sballot_public_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs, _ptr(out), out.shape[0],
+                                                 C.byref(npub)), "pz_sballot_public_cells")
+        return out[: npub.value]
+
+    def sballot_expand_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, m_bits: int, s_limbs: int, inputs, d_steps: int,
+                           d_modulus: int, d_advice: int, d_lookup: int = 0, rows: int = 0, col_stride: int = 0):
+        """inputs: host uint64 array n | g | hs | m_1 .. m_K (one word each) | s_1 .. s_K | res_1 .. res_K; d_steps: the K (2 m_bits +
+        2 s_limbs limb_bits + 1) records paillier_sballot_dev left; writes the circuit's cell stream, dense or cut into columns"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        self._chk(self.L.pz_sballot_expand_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs, _ptr(inp), VP(d_steps),
+                                               VP(d_modulus), VP(d_advice), VP(d_lookup), rows, col_stride), "pz_sballot_expand_dev")
+
+    def sballot_expand_cols_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, m_bits: int, s_limbs: int, inputs,
+                                d_steps: int, d_modulus: int, d_advice: int, d_lookup: int, d_col_starts: int, n_adv_cols: int, max_rows: int,
+                                lookup_rows: int, col_stride: int):
+        """the same with the advice cells in break-point columns (circuit_expand_cols_dev's conventions)"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        self._chk(self.L.pz_sballot_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs, _ptr(inp), VP(d_steps),
+                                                    VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts), n_adv_cols, max_rows,
+                                                    lookup_rows, col_stride), "pz_sballot_expand_cols_dev")
 
     # ------------------------------------------------------------------ "next" rows: SRS setup, evaluation at a point
     def srs_setup_g1_dev(self, k: int, s, omega, d_g: int = 0, d_g_lagrange: int = 0):

@@ -17,6 +17,7 @@
 //   (add folded over B full-width ciphertexts)                 PaillierChip::tally, pz::paillier_tally_test
 //   (c^w and prod c_i^w_i: the scalar homomorphism)            PaillierChip::mul_scalar / weighted_tally, pz::paillier_wtally_test (15.8)
 //   (K ciphertexts of small values with a public sum)          PaillierChip::ballot, pz::paillier_ballot_test (15.10)
+//   (the same with short randomness, c = g^m hs^s)             PaillierChip::sballot, pz::paillier_sballot_test, pz::djn_generator (15.18)
 //   (K ciphertexts shuffled and re-randomised: a mixer's step) pz::benes_route (benes.hpp), PaillierChip::mix, pz::paillier_mix_test (15.17)
 //   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
 //   (T trustees holding additive shares of the exponent)      pz::ThresholdKey, pz::deal_shares, PaillierChip::partial_decrypt / combine (15.11)
@@ -555,6 +556,84 @@ class PaillierChip {  // paillier.rs:11-15
             out.push_back(AssignedBigUint<Fresh>(BigUint::from_limbs(cv.data() + i * wk, wk), L, biguint->limb_bits));
         }
         std::fill(rec.begin(), rec.end(), 0);
+        return R::Ok(out);
+    }
+
+    // The short-randomness ballot: c_i = g^m_i hs^s_i mod n^2 for K messages under one key whose hs = h^n mod
+    // n^2 is public (pz::djn_generator).  n^2 hoisted once, load_zero; per ciphertext pow_mod(g_ext, m_i) over m_bits in-circuit bits as
+    // ballot does, pow_mod(hs, s_i) as kind 7 emits a chain -- [1, 0], then per limb of s_i num_to_bits and that limb's blocks -- and the
+    // final mul_mod.  One pz_paillier_sballot call computes every record; the tape takes them in the circuit's order, which is the
+    // call's.  hs, the messages' load_witness cells, their sum and the s_i (all of ONE limb count, 1 .. 2 * n's) are assigned by the
+    // caller (paillier_sballot_test), in front of this.  The m_i and s_i are the voter's secrets: the staged words are overwritten here.
+    Result<std::vector<AssignedBigUint<Fresh>>> sballot(Context& ctx, const EncryptionPublicKeyAssigned& pk_enc, const AssignedBigUint<Fresh>& hs,
+                                                        const std::vector<AssignedWeight>& ms, const std::vector<AssignedBigUint<Fresh>>& ss,
+                                                        unsigned m_bits) const {
+        using R = Result<std::vector<AssignedBigUint<Fresh>>>;
+        if (ms.empty() || ms.size() != ss.size() || ms.size() > 1024) return R::Err(PZ_ERR_INVALID, "sballot: one s per message, 1 .. 1024 of them");
+        if (m_bits < 1 || m_bits > 64) return R::Err(PZ_ERR_INVALID, "sballot: m_bits outside 1 .. 64");
+        const unsigned s_limbs = ss[0].num_limbs(), W = biguint->limb_bits;
+        if (s_limbs < 1 || s_limbs > 2 * pk_enc.n.num_limbs()) return R::Err(PZ_ERR_INVALID, "sballot: an s of 1 .. 2 * n's limbs");
+        if (hs.num_limbs() != 2 * pk_enc.n.num_limbs()) return R::Err(PZ_ERR_INVALID, "sballot: hs is not assigned at full width");
+        auto n2m = biguint->square(ctx, pk_enc.n);
+        if (!n2m.ok) return R::Err(n2m.err.status, n2m.err.msg);
+        RefreshAux aux = RefreshAux::new_(W, pk_enc.n.num_limbs(), pk_enc.n.num_limbs());
+        auto n2r = biguint->refresh(ctx, n2m.val, aux);
+        if (!n2r.ok) return R::Err(n2r.err.status, n2r.err.msg);
+        const AssignedBigUint<Fresh>& n2 = n2r.val;
+        (void)ctx.load_zero();
+        const unsigned L = n2.num_limbs(), Wd = n2.num_words(), wn = pk_enc.n.num_words(), wk = 2 * wn;   // K3 works on 2 * wn words
+        const unsigned s_bits = s_limbs * W, sw = (s_bits + 63) / 64;
+        std::vector<uint64_t> nv = pk_enc.n.words(), gv = pk_enc.g.value().to_limbs(wn), hv = hs.value().to_limbs(wk), mv, sv;
+        for (const AssignedWeight& m : ms) mv.push_back(m.value);
+        for (const auto& s : ss) {
+            if (s.num_limbs() != s_limbs) return R::Err(PZ_ERR_INVALID, "sballot: the s_i are not assigned at one width");
+            std::vector<uint64_t> w = s.value().to_limbs(sw);
+            sv.insert(sv.end(), w.begin(), w.end());
+        }
+        const size_t K = ms.size(), per = 2 * (size_t)m_bits + 2 * (size_t)s_bits + 1;
+        std::vector<uint64_t> rec(K * per * 4 * wk), cv(K * wk);
+        int rc = pz_paillier_sballot(ctx.raw(), wn, K, m_bits, s_bits, nv.data(), gv.data(), hv.data(), mv.data(), sv.data(), rec.data(), K * per,
+                                     cv.data());
+        std::fill(mv.begin(), mv.end(), 0);
+        std::fill(sv.begin(), sv.end(), 0);
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_sballot: ") + pz_strerror(rc));
+        // the tape holds Wd words per integer (Wd < 2 * wn where limb_bits does not divide 64: the words above are zero)
+        auto steps_of = [&](size_t at, std::vector<uint64_t>& out) {
+            out.clear();
+            for (size_t f = at * 4; f < (at + 1) * 4; ++f) {
+                if (BigUint::from_limbs(rec.data() + f * wk, wk).bits() > (size_t)L * W) return false;
+                out.insert(out.end(), rec.begin() + f * wk, rec.begin() + f * wk + Wd);
+            }
+            return true;
+        };
+        std::vector<uint64_t> steps;
+        bool fits = true;
+        auto bit_blocks = [&](size_t first, unsigned nbits) {   // nbits x (mul_mod, select, square_mod) from record `first` on
+            for (unsigned j = 0; fits && j < nbits; ++j) {
+                if (!(fits = steps_of(first + 2 * j, steps))) break;
+                ctx.push_steps(steps, Wd, L, W, n2.value());
+                ctx.record_cells(Context::SELECT, L, 8 * (size_t)L);
+                if (!(fits = steps_of(first + 2 * j + 1, steps))) break;
+                ctx.push_steps(steps, Wd, L, W, n2.value());
+            }
+        };
+        std::vector<AssignedBigUint<Fresh>> out;
+        for (size_t i = 0; fits && i < K; ++i) {
+            (void)ctx.load_constant_one();
+            (void)ctx.load_zero();
+            ctx.record_cells(Context::NUM_TO_BITS, 1, 7 * (size_t)m_bits - 2);
+            bit_blocks(i * per, m_bits);
+            (void)ctx.load_constant_one();
+            (void)ctx.load_zero();
+            for (unsigned li = 0; fits && li < s_limbs; ++li) {
+                ctx.record_cells(Context::NUM_TO_BITS, 1, 7 * (size_t)W - 2);
+                bit_blocks(i * per + 2 * (size_t)m_bits + 2 * (size_t)li * W, W);
+            }
+            if (fits && (fits = steps_of((i + 1) * per - 1, steps))) ctx.push_steps(steps, Wd, L, W, n2.value());   // the final block
+            out.push_back(AssignedBigUint<Fresh>(BigUint::from_limbs(cv.data() + i * wk, wk), L, W));
+        }
+        std::fill(rec.begin(), rec.end(), 0);
+        if (!fits) return R::Err(PZ_ERR_RANGE, "a step's integer does not fit the assigned limb count");
         return R::Ok(out);
     }
 
@@ -1167,6 +1246,53 @@ inline void paillier_ballot_test(Context& ctx, const RangeChip& range, const Pai
     }
 }
 
+// the short-randomness ballot's driver: assign n, g, hs at full width, load_witness every m_i, for K >= 2 their sum, assign every s_i on
+// s_limbs limbs, sballot, then per ciphertext assign res_i and assert_equal_fresh
+struct PaillierSBallotInput {
+    unsigned limb_bits, enc_bits, m_bits, s_limbs;
+    BigUint n, g, hs;
+    std::vector<uint64_t> ms;
+    std::vector<BigUint> ss, res;
+};
+inline void paillier_sballot_test(Context& ctx, const RangeChip& range, const PaillierSBallotInput& input) {
+    BigUintChip biguint_chip = BigUintChip::construct(&range, input.limb_bits);
+    PaillierChip paillier_chip = PaillierChip::construct(&biguint_chip, input.enc_bits);
+    auto n_assigned = biguint_chip.assign_integer(ctx, input.n, input.enc_bits).unwrap();
+    auto g_assigned = biguint_chip.assign_integer(ctx, input.g, input.enc_bits).unwrap();
+    auto hs_assigned = biguint_chip.assign_integer(ctx, input.hs, input.enc_bits * 2).unwrap();
+    EncryptionPublicKeyAssigned pk_enc{n_assigned, g_assigned};
+    std::vector<AssignedWeight> ms;
+    for (uint64_t m : input.ms) ms.push_back(AssignedWeight{m, ctx.load_witness()});
+    if (ms.size() >= 2) ctx.sum(ms.size());
+    std::vector<AssignedBigUint<Fresh>> ss;
+    for (const BigUint& s : input.ss) ss.push_back(biguint_chip.assign_integer(ctx, s, input.s_limbs * input.limb_bits).unwrap());
+    auto cts = paillier_chip.sballot(ctx, pk_enc, hs_assigned, ms, ss, input.m_bits).unwrap();
+    if (cts.size() != input.res.size()) throw std::runtime_error("paillier_sballot_test: one expected ciphertext per message");
+    for (size_t i = 0; i < cts.size(); ++i) {
+        auto res_assigned = biguint_chip.assign_integer(ctx, input.res[i], input.enc_bits * 2).unwrap();
+        if (cts[i].value() != res_assigned.value()) throw std::runtime_error("assertion failed: `(left == right)` (paillier_sballot_test)");
+        biguint_chip.assert_equal_fresh(ctx, cts[i], res_assigned).unwrap();
+    }
+}
+
+// the element hs that short-randomness ("DJN mode") encryption adds to a public key (keys.py::djn_generator is
+// the same in Python): hs = (-x^2 mod n)^n mod n^2 for a unit x drawn with rand (rand(k): uniform in [0, k), from the caller's CSPRNG),
+// the power taken on the device by PaillierChip::partial_decrypt's chain.  Security of c = g^m hs^s with a short s rests on the
+// short-exponent assumption in <hs>; the scheme asks for p = q = 3 (mod 4) (pz::generate_key with safe gives such primes).  Refuses an
+// even or tiny n (PZ_ERR_INVALID).
+inline Result<BigUint> djn_generator(Context& ctx, const PaillierChip& chip, const BigUint& n, const std::function<BigUint(const BigUint&)>& rand) {
+    using R = Result<BigUint>;
+    const BigUint one(1), two(2);
+    if (n < BigUint(15) || !n.bit(0)) return R::Err(PZ_ERR_INVALID, "djn_generator: n must be an odd modulus");
+    BigUint x;
+    do x = rand(n) % n;
+    while (x < two || BigUint::gcd(x, n) != one);
+    const BigUint h = (n - (x * x) % n) % n;
+    auto p = chip.partial_decrypt(ctx, n, h, n, std::vector<BigUint>{one});   // h^n mod n^2
+    if (!p.ok) return R::Err(p.err.status, p.err.msg);
+    return R::Ok(p.val.h);
+}
+
 // the mix's driver: assign n, every c_j at full width, every r_i, mix, then per output assign res_i and assert_equal_fresh
 struct PaillierMixInput {
     unsigned limb_bits, enc_bits;
@@ -1345,6 +1471,45 @@ inline int synthesize_mix_circuit(Context& ctx, unsigned enc_bits, size_t n_step
     if (rc != PZ_OK) return rc;
     return pz_mix_expand_dev(ctx.raw(), Ln, W, ctx.lookup_bits(), K, n_steps_r, in.data(), wit.bits.empty() ? nullptr : wit.bits.data(),
                              layers ? d_routes : nullptr, d_work, d_modulus, d_advice, d_lookup, 0, 0);
+}
+
+// the short-randomness ballot's tape (paillier_sballot_test) expanded on the device: circuit kind 9, inputs n | g | hs | m_1 .. m_K |
+// s_1 .. s_K | res_1 .. res_K.  The records go up with fields of 2 * ceil(Ln W / 64) words, as pz_paillier_sballot_dev leaves them.
+// d_work: device memory for them, K (2 m_bits + 2 s_limbs W + 1) 4 * 2 wn words.
+inline int synthesize_sballot_circuit(Context& ctx, unsigned enc_bits, unsigned m_bits, unsigned s_limbs, const BigUint& n, const BigUint& g,
+                                      const BigUint& hs, const std::vector<uint64_t>& ms, const std::vector<BigUint>& ss,
+                                      const std::vector<BigUint>& res, uint64_t* d_work, uint64_t* d_modulus, uint64_t* d_advice,
+                                      uint64_t* d_lookup) {
+    const unsigned W = ctx.limb_bits(), Ln = enc_bits / W, wn = (Ln * W + 63) / 64, wr = (2 * Ln * W + 63) / 64, wk = 2 * wn;
+    const unsigned sw = (s_limbs * W + 63) / 64;
+    const size_t K = ms.size(), per = 2 * (size_t)m_bits + 2 * (size_t)s_limbs * W + 1;
+    if (K < 1 || ss.size() != K || res.size() != K || ctx.n_steps() != K * per || ctx.words() != wr) return PZ_ERR_INVALID;
+    size_t a = 0, l = 0;
+    int rc = pz_sballot_cells(Ln, W, ctx.lookup_bits(), K, m_bits, s_limbs, &a, &l);
+    if (rc != PZ_OK) return rc;
+    if (a != ctx.advice_cells() || l != ctx.lookup_cells()) return PZ_ERR_INVALID;   // the tape is not this driver's
+    std::vector<uint64_t> in = n.to_limbs(wn), w = g.to_limbs(wn);
+    in.insert(in.end(), w.begin(), w.end());
+    w = hs.to_limbs(wr);
+    in.insert(in.end(), w.begin(), w.end());
+    in.insert(in.end(), ms.begin(), ms.end());
+    for (const BigUint& s : ss) {
+        w = s.to_limbs(sw);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    for (const BigUint& c : res) {
+        w = c.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    const std::vector<uint64_t>& tp = ctx.tape();
+    std::vector<uint64_t> rec(K * per * 4 * wk, 0);
+    for (size_t f = 0; f < K * per * 4; ++f) std::copy(tp.begin() + f * wr, tp.begin() + (f + 1) * wr, rec.begin() + f * wk);
+    rc = pz_upload(ctx.raw(), d_work, rec.data(), rec.size() * 8);
+    std::fill(rec.begin(), rec.end(), 0);
+    if (rc == PZ_OK)
+        rc = pz_sballot_expand_dev(ctx.raw(), Ln, W, ctx.lookup_bits(), K, m_bits, s_limbs, in.data(), d_work, d_modulus, d_advice, d_lookup, 0, 0);
+    std::fill(in.begin(), in.end(), 0);
+    return rc;
 }
 
 }  // namespace pz

@@ -6,7 +6,8 @@ Engine.paillier_combine_t; and the generator of the primes all of them start fro
 section 15.16), which runs on the device: Engine.is_prime and Engine.prime_search.
 
 The library derives mu and g^-1 on the device and validates the key there; the one value it does not derive is d = n^-1 mod lambda,
-the exponent that recovers an encryption's randomness: it is the caller's, and this helper computes it."""
+the exponent that recovers an encryption's randomness: it is the caller's, and this helper computes it.
+djn_generator makes the element hs that short-randomness ("DJN mode") encryption adds to a public key (section 15.18)."""
 from __future__ import annotations
 
 import math
@@ -190,6 +191,31 @@ def deal_shamir(p: int, q: int, trustees: int, threshold: int, g: Optional[int] 
     key = ShamirKey(n=n, g=g, v=v, hs=tuple(pow(v, s, n2) for s in shares), mu2=pow(2 * a * math.factorial(trustees), -1, n),
                     trustees=trustees, threshold=threshold, v_order_proved=safe)
     return key, shares
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# short randomness: the extra element hs of a Damgard-Jurik-Nielsen ("DJN mode") public key
+# ---------------------------------------------------------------------------------------------------------------------------------
+def djn_generator(engine, n: int, rand: Callable[[int], int] = secrets.randbelow) -> int:
+    """hs = (-x^2 mod n)^n mod n^2 for a unit x drawn with rand (rand(k): uniform in [0, k), by default secrets.randbelow); the power
+    is taken on the device (Engine.paillier_trace).  With it c = g^m hs^s mod n^2 for a SHORT secret s below 2^s_bits is an ordinary
+    Paillier ciphertext with r = h^s mod n, h = -x^2 mod n: Engine.paillier_sballot computes it, circuit kind 'sballot' proves it, and
+    tally, mix, decrypt, partial and combine take it unchanged.  Security rests on the short-exponent assumption in <hs> (the
+    discrete logarithm of an element of <hs> to the base hs stays hard when it is only s_bits long): s_bits is the caller's argument
+    everywhere and has no default; customary widths are at least twice the security level.  The scheme asks for p = q = 3 (mod 4), so
+    that -1 is no square mod n and h generates the units of Jacobi symbol 1 up to sign: generate_key(safe=True) gives such primes.
+    Nothing here shows a third party that hs is an n-th residue, i.e. an encryption of 0: the key authority shows that with circuit
+    kind 'decrypt', or with kind 'partial' and a combiner."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 15 or n % 2 == 0:
+        raise ValueError("n must be an odd modulus")
+    while True:
+        x = rand(n)
+        if x >= 2 and math.gcd(x, n) == 1:
+            break
+    h = (-x * x) % n
+    limbs = (n.bit_length() + 63) // 64
+    res, _, _ = engine.paillier_trace(2 * limbs, _words(n * n, 2 * limbs), _words(h, 2 * limbs), _words(n, limbs), limbs, want_steps=False)
+    return sum(int(w) << (64 * i) for i, w in enumerate(res.tolist()))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

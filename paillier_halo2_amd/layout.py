@@ -213,7 +213,8 @@ MIX_MAX = 1024          # ciphertexts of one mix, a power of two (pz.h pz_pailli
 
 
 def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_steps_g: int = 0, n_steps_r: int = 0,
-                  count: int | None = None, w_bits: int | None = None, m_bits: int | None = None) -> CircuitCells:
+                  count: int | None = None, w_bits: int | None = None, m_bits: int | None = None,
+                  s_limbs: int | None = None) -> CircuitCells:
     """The whole cell stream of paillier_enc_test (bench.rs:33-75, kind 'encrypt') or paillier_enc_add_test
     (bench.rs:77-117, kind 'add'), operation by operation in call order -- what pz_circuit_expand_dev writes.
     kind 'tally' (count = B ciphertexts): assign n, assign c_1 .. c_B at full width, square + refresh once, the B - 1 blocks of
@@ -233,7 +234,12 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
     kind 'mix' (circuit kind 8; count = K = 2^d ciphertexts, n_steps_r = the records of ONE r^n chain): assign
     n, assign c_1 .. c_K at full width, assign r_1 .. r_K, square + refresh once, load_zero, the (2d - 1) K / 2 switches of the network
     (assert_bit's 4 cells, then per limb two selects of 8 cells), per output [1, 0], the r^n chain's blocks and the final mul_mod, then
-    per output assign res_i and assert_equal_fresh."""
+    per output assign res_i and assert_equal_fresh.
+    kind 'sballot' (circuit kind 9; count = K ciphertexts, m_bits = b bits per message, s_limbs limbs per
+    exponent s_i): assign n, g, assign hs at full width, load_witness(m_1 .. m_K), for K >= 2 FlexGate::sum of them, assign s_1 .. s_K
+    (s_limbs limbs each), square + refresh once, load_zero, per ciphertext pow_mod(g, m_i) over b in-circuit bits as 'ballot',
+    pow_mod(hs, s_i) as 'partial' emits a chain over the s_limbs limbs of s_i, and the final mul_mod, then per ciphertext assign res_i
+    and assert_equal_fresh.  No step count enters: nothing of the key but its size shapes the stream."""
     Ln, L = limbs_n, 2 * limbs_n
     if kind == "decrypt":
         kind = "encrypt_uniform"
@@ -266,12 +272,23 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
             raise ValueError(f"a mix takes count = 1, 2, 4 .. {MIX_MAX} ciphertexts, not {count}")
         if n_steps_g or n_steps_r < 1:
             raise ValueError("a mix has no g-chain and n_steps_r >= 1 steps of one r^n chain")
+    elif kind == "sballot":
+        if count is None or not 1 <= count <= BALLOT_MAX:
+            raise ValueError(f"a ballot takes count = 1 .. {BALLOT_MAX} ciphertexts, not {count}")
+        if m_bits is None or not 1 <= m_bits <= BALLOT_MAX_BITS:
+            raise ValueError(f"a ballot's message has m_bits = 1 .. {BALLOT_MAX_BITS} bits, not {m_bits}")
+        if s_limbs is None or not 1 <= s_limbs <= L:
+            raise ValueError(f"a short-randomness ballot's exponent has s_limbs = 1 .. {L} limbs, not {s_limbs}")
+        if n_steps_g not in (0, 2 * m_bits) or n_steps_r not in (0, 2 * s_limbs * limb_bits):
+            raise ValueError("a short-randomness ballot entry has 2 * m_bits g-chain steps and 2 * s_limbs * limb_bits hs-chain steps")
     elif count is not None:
-        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial' and 'mix'")
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix' and 'sballot'")
     if w_bits is not None and kind != "wtally":
         raise ValueError("w_bits belongs to kind 'wtally'")
-    if m_bits is not None and kind != "ballot":
-        raise ValueError("m_bits belongs to kind 'ballot'")
+    if m_bits is not None and kind not in ("ballot", "sballot"):
+        raise ValueError("m_bits belongs to kinds 'ballot' and 'sballot'")
+    if s_limbs is not None and kind != "sballot":
+        raise ValueError("s_limbs belongs to kind 'sballot'")
     mm = mul_mod_cells(L, limb_bits, lookup_bits)
     seg, a, l = {}, 0, 0
 
@@ -301,6 +318,16 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         if count >= 2:
             put("sum", 1 + 3 * (count - 1))
         put("assign_rs", count * na, count * nl)
+    elif kind == "sballot":
+        na, nl = assign_cells(Ln, limb_bits, lookup_bits)
+        put("assign_n", na, nl)
+        put("assign_g", na, nl)
+        put("assign_hs", *assign_cells(L, limb_bits, lookup_bits))
+        put("messages", count)
+        if count >= 2:
+            put("sum", 1 + 3 * (count - 1))
+        sa, sl = assign_cells(s_limbs, limb_bits, lookup_bits)
+        put("assign_ss", count * sa, count * sl)
     elif kind in ("tally", "wtally"):
         put("assign_n", *assign_cells(Ln, limb_bits, lookup_bits))
         ca, cl = assign_cells(L, limb_bits, lookup_bits)
@@ -335,6 +362,17 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         # the final block.  Then per entry assign res_i at full width and assert_equal_fresh
         steps = 2 * m_bits + n_steps_r + 1
         put("entries", count * (2 + 7 * m_bits - 2 + m_bits * 8 * L + 2 + steps * mm.advice), count * steps * mm.lookup)
+        ra, rl = assign_cells(L, limb_bits, lookup_bits)
+        put("results", count * (ra + assert_equal_cells(L)), count * rl)
+        seg["end"] = (a, l)
+        return CircuitCells(a, l, seg)
+    if kind == "sballot":
+        # per entry: the g-chain as 'ballot'; [1, 0], then per limb of s_i num_to_bits (7 W - 2 cells) and W blocks of mul_mod + select
+        # + square_mod; the final block.  Then per entry assign res_i at full width and assert_equal_fresh
+        s_bits = s_limbs * limb_bits
+        steps = 2 * m_bits + 2 * s_bits + 1
+        put("entries", count * (2 + 7 * m_bits - 2 + 2 + s_limbs * (7 * limb_bits - 2) + (m_bits + s_bits) * 8 * L + steps * mm.advice),
+            count * steps * mm.lookup)
         ra, rl = assign_cells(L, limb_bits, lookup_bits)
         put("results", count * (ra + assert_equal_cells(L)), count * rl)
         seg["end"] = (a, l)

@@ -180,7 +180,7 @@ def record_seed(prefix: str) -> bytes:
 def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] = None, c1: Optional[int] = None, c2: Optional[int] = None, *,
                   enc_bits: int, limb_bits: int, cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None,
                   m: Optional[int] = None, total: Optional[int] = None, v: Optional[int] = None, h: Optional[int] = None,
-                  partials: Optional[Sequence[int]] = None, mixed: Optional[Sequence[int]] = None) -> List[int]:
+                  partials: Optional[Sequence[int]] = None, mixed: Optional[Sequence[int]] = None, hs: Optional[int] = None) -> List[int]:
     """the statement of a circuit with the instance column, in the column's row order: little-endian limbs of limb_bits,
     n | g | c (kind "encrypt" / "encrypt_uniform": c = g^m r^n mod n^2) or n | g | c1 | c2 | c ("add": c = c1 c2 mod n^2); n, g, c1, c2 have
     enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)
@@ -203,7 +203,12 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
     n": there are a permutation pi and r_i with c'_i = c_pi(i) r_i^n mod n^2.  K is a power of two (1 .. 1024); lists of different
     lengths are refused, and so is any c_j or c'_i >= n^2 (no ciphertext) and any c'_i = 0 -- what a mixer's r_i = 0 leaves: a vote
     destroyed in plain sight, which the circuit does not exclude (any other non-unit output needs a factor of n).  No g and no
-    single result c."""
+    single result c.
+    kind "sballot": n | g | hs | c_1 | .. | c_K | S -- "every c_i of cts is g^m_i hs^s_i mod n^2 with m_i below 2^m_bits and s_i below
+    2^s_bits, and the m_i add up to S = total"; hs = h^n mod n^2 is the key's (keys.djn_generator), m_bits and s_bits are the circuit's
+    shape.  total as in "ballot": refused with K = 1, required with K >= 2.  hs = 0 (every c_i would be 0), an hs >= n^2 and a c_i >=
+    n^2 are refused here: the circuit compares nothing with n^2.  That hs is an n-th residue is the key authority's to show, not this
+    statement's."""
     Ln = enc_bits // limb_bits
     mask = (1 << limb_bits) - 1
     limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
@@ -239,6 +244,18 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
         if any(int(ci) >= int(n) * int(n) for ci in cts):
             raise ValueError("a ballot's ciphertext is below n^2")
         parts = [(n, Ln), (g, Ln)] + [(ci, 2 * Ln) for ci in cts]
+    elif kind == "sballot":
+        if cts is None or len(cts) < 1 or g is None or hs is None or c is not None:
+            raise ValueError("the sballot statement names n, g, hs and its ciphertexts cts = [c_1 .. c_K], K >= 1, and no single result c")
+        if (total is not None) != (len(cts) >= 2):
+            raise ValueError("the sballot statement carries the sum `total` exactly when it has two or more ciphertexts")
+        if total is not None and (int(total) < 0 or int(total) >= consts.FR_R):
+            raise ValueError("the total is one field value")
+        if not 0 < int(hs) < int(n) * int(n):
+            raise ValueError("hs is neither 0 nor n^2 or more")
+        if any(not 0 <= int(ci) < int(n) * int(n) for ci in cts):
+            raise ValueError("a ballot's ciphertext is below n^2")
+        parts = [(n, Ln), (g, Ln), (hs, 2 * Ln)] + [(ci, 2 * Ln) for ci in cts]
     elif kind == "partial":
         if v is None or h is None or cts is None or partials is None or len(cts) < 1 or g is not None or c is not None:
             raise ValueError("the partial statement names n, v, h, cts = [c_1 .. c_K] and partials = [u_1 .. u_K], K >= 1, and neither g nor c")
@@ -262,19 +279,21 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
             raise ValueError("an output of a mix is not 0: a mixer's r_i = 0 destroys the ciphertext")
         parts = [(n, Ln)] + [(ci, 2 * Ln) for ci in cts] + [(ci, 2 * Ln) for ci in mixed]
     else:
-        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt, ballot, partial or mix")
+        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt, ballot, partial, mix or sballot")
+    if hs is not None and kind != "sballot":
+        raise ValueError("hs belongs to kind 'sballot'")
     if mixed is not None and kind != "mix":
         raise ValueError("mixed belongs to kind 'mix'")
-    if c is None and kind not in ("ballot", "partial", "mix"):
+    if c is None and kind not in ("ballot", "partial", "mix", "sballot"):
         raise ValueError("the statement names its result c")
     if (v is not None or h is not None or partials is not None) and kind != "partial":
         raise ValueError("v, h and partials belong to kind 'partial'")
-    if total is not None and kind != "ballot":
-        raise ValueError("total belongs to kind 'ballot'")
+    if total is not None and kind not in ("ballot", "sballot"):
+        raise ValueError("total belongs to kinds 'ballot' and 'sballot'")
     if m is not None and kind != "decrypt":
         raise ValueError("m belongs to kind 'decrypt'")
-    if cts is not None and kind not in ("tally", "wtally", "ballot", "partial", "mix"):
-        raise ValueError("cts belongs to kinds 'tally', 'wtally', 'ballot', 'partial' and 'mix'")
+    if cts is not None and kind not in ("tally", "wtally", "ballot", "partial", "mix", "sballot"):
+        raise ValueError("cts belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix' and 'sballot'")
     if weights is not None and kind != "wtally":
         raise ValueError("weights belongs to kind 'wtally'")
     for v, cnt in parts:
