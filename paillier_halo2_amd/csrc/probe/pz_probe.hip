@@ -10,6 +10,7 @@
 #include "../fp.cuh"
 #include "../fp29_probe.cuh"
 #include "../fp29.cuh"
+#include "../prime_mont.cuh"
 
 // issue-rate probes --------------------------------------------------------------------------
 __global__ void k_ubench_mad(u64* out, unsigned iters) {
@@ -242,5 +243,86 @@ extern "C" int pzp_f29_ops(int device, int field, int op, const uint32_t* in, ui
     else hipLaunchKernelGGL(k_f29_ops<FrTag>, g, b, 0, 0, op, (const u32*)d, (unsigned)k, count, d_out);
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     if (hipMemcpy(out, d_out, out_b, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return 0;
+}
+
+// ---- the group arithmetic of the prime generation (../prime_mont.cuh) one function at a time, on the mapping of k_prime_mr: E = 1 up to 16
+// limbs, E = 2 above, lane j of a group of 16 holds limbs [j E, j E + E), four groups to a wavefront, 16 to a block; a group beyond count
+// runs on c = 3 with a = b = 0.  a, b, c: [count][limbs] words; out: [count][ow] words; flag: [count] words.
+//   op 0 MONT_MUL:   a < c, any b -> a b / R mod c, R = 2^(64 limbs) (ow = limbs)
+//   op 1 SETUP:      c -> R mod c | R^2 mod c (ow = 2 limbs), flag = -c^-1 mod 2^64
+//   op 2 SUB:        a, b -> a - b mod 2^(64 * 16 E) (ow = 16 E), flag = the borrow out
+//   op 3 DOUBLE_MOD: a < c -> 2 a mod c (ow = limbs)
+#define PZP_PRIME_OPS 4
+template <int E> __global__ __launch_bounds__(256) void k_prime_ops(int op, const u64* __restrict__ a_in, const u64* __restrict__ b_in,
+                                                                    const u64* __restrict__ c_in, unsigned L, unsigned count, unsigned ow,
+                                                                    u64* __restrict__ out, u64* __restrict__ flag) {
+    const GLane g = glane();
+    const unsigned j = blockIdx.x * (256 / PR_GROUP) + threadIdx.x / PR_GROUP;
+    const bool live = j < count;
+    GI<E> a, b, c;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const unsigned k = g.gl * E + e;
+        const bool in = live && k < L;
+        a.v[e] = (in && a_in) ? a_in[(size_t)j * L + k] : 0;
+        b.v[e] = (in && b_in) ? b_in[(size_t)j * L + k] : 0;
+        c.v[e] = (in && c_in) ? c_in[(size_t)j * L + k] : (k == 0 ? 3 : 0);
+    }
+    const u64 m0 = __shfl(c.v[0], 0, PR_GROUP);
+    GI<E> r = a, r_hi = a;
+    u64 fl = 0;
+    if (op == 0) {
+        u64 x = m0;
+#pragma unroll
+        for (int it = 0; it < 5; ++it) x *= 2 - m0 * x;
+        r = mont_mul(a, b, c, 0 - x, L, g);
+    } else if (op == 1) {
+        prime_setup(c, m0, L, g, fl, r, r_hi);
+    } else if (op == 2) {
+        fl = grp_sub(r, a, b, g) ? 1 : 0;
+    } else {
+        r = grp_double_mod(a, c, g);
+    }
+    if (!live) return;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const unsigned k = g.gl * E + e;
+        const unsigned lim = op == 1 ? L : ow;
+        if (k < lim) out[(size_t)j * ow + k] = r.v[e];
+        if (op == 1 && k < L) out[(size_t)j * ow + L + k] = r_hi.v[e];
+    }
+    if (g.gl == 0) flag[j] = fl;
+}
+// every argument is checked before any launch: limbs 1 .. 32, count 1 .. 65536, c odd and at least 3 (ops 0, 1, 3), a < c (ops 0, 3)
+extern "C" int pzp_prime_ops(int device, int op, uint32_t limbs, size_t count, const uint64_t* a, const uint64_t* b, const uint64_t* c,
+                             uint64_t* out, uint64_t* flag_out) {
+    if (op < 0 || op >= PZP_PRIME_OPS || limbs < 1 || limbs > 32 || count < 1 || count > 65536 || !out || !flag_out) return -1;
+    const bool need_a = op != 1, need_b = op == 0 || op == 2, need_c = op != 2;
+    if ((need_a && !a) || (need_b && !b) || (need_c && !c)) return -1;
+    for (size_t j = 0; need_c && j < count; ++j) {
+        const uint64_t* cj = c + j * limbs;
+        bool wide = false;
+        for (uint32_t k = 1; k < limbs; ++k) wide = wide || cj[k] != 0;
+        if ((cj[0] & 1) == 0 || (!wide && cj[0] < 3)) return -1;
+        if (op == 1) continue;
+        const uint64_t* aj = a + j * limbs;
+        int cmp = 0;   // a ? c from the top limb
+        for (uint32_t k = limbs; k-- > 0 && cmp == 0;) cmp = aj[k] < cj[k] ? -1 : aj[k] > cj[k] ? 1 : 0;
+        if (cmp >= 0) return -1;
+    }
+    const unsigned E = limbs <= 16 ? 1 : 2, ow = op == 1 ? 2 * limbs : op == 2 ? 16 * E : limbs;
+    const size_t in_b = count * limbs * 8, out_b = count * ow * 8, fl_b = count * 8;
+    void* d = probe_buf(device, 3 * in_b + out_b + fl_b);
+    if (!d) return -1;
+    u64 *d_a = (u64*)d, *d_b = d_a + count * limbs, *d_c = d_b + count * limbs, *d_out = d_c + count * limbs, *d_fl = d_out + count * ow;
+    if (need_a && hipMemcpy(d_a, a, in_b, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (need_b && hipMemcpy(d_b, b, in_b, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (need_c && hipMemcpy(d_c, c, in_b, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    const dim3 grid((unsigned)((count + 15) / 16)), block(256);
+    if (E == 1) hipLaunchKernelGGL(k_prime_ops<1>, grid, block, 0, 0, op, need_a ? d_a : nullptr, need_b ? d_b : nullptr, need_c ? d_c : nullptr, (unsigned)limbs, (unsigned)count, ow, d_out, d_fl);
+    else hipLaunchKernelGGL(k_prime_ops<2>, grid, block, 0, 0, op, need_a ? d_a : nullptr, need_b ? d_b : nullptr, need_c ? d_c : nullptr, (unsigned)limbs, (unsigned)count, ow, d_out, d_fl);
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpy(out, d_out, out_b, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(flag_out, d_fl, fl_b, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return 0;
 }

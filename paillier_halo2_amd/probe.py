@@ -24,6 +24,7 @@ def lib():
                            ("pzp_ubench_fqmul_variant", [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
                            ("pzp_fq_mul29", [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
                            ("pzp_f29_ops", [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p]),
+                           ("pzp_prime_ops", [C.c_int, C.c_int, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
                            ("pzp_ubench_mfma", [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
                            ("pzp_mulc_mfma", [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                               C.POINTER(C.c_double)])):
@@ -75,6 +76,28 @@ def f29_ops(device: int, field: str, op: str, limbs) -> np.ndarray:
     if lib().pzp_f29_ops(device, 0 if field == "fq" else 1, code, a.ctypes.data, k, a.shape[0], out.ctypes.data) != 0:
         raise RuntimeError("probe launch failed")
     return out
+
+
+PRIME_OPS = {"mont_mul": 0, "setup": 1, "sub": 2, "double_mod": 3}
+
+
+def prime_ops(device: int, op: str, limbs: int, a=None, b=None, c=None):
+    """the group arithmetic of the prime generation (csrc/prime_mont.cuh) one function at a time, on k_prime_mr's mapping.
+    a, b, c: [count][limbs] uint64 or None where the op does not read them.  -> (out [count][ow] uint64, flag [count] uint64):
+    mont_mul (a < c, any b): a b / 2^(64 limbs) mod c;  setup (c): R mod c | R^2 mod c, flag = -c^-1 mod 2^64;
+    sub (a, b): a - b mod 2^(64 * 16 E) in 16 E words, flag = the borrow;  double_mod (a < c): 2 a mod c.
+    The library refuses limbs outside 1 .. 32, a count outside 1 .. 65536, an even c or c < 3 and a >= c before any launch."""
+    code = PRIME_OPS[op]
+    arrs = [None if x is None else np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, limbs) for x in (a, b, c)]
+    count = next(x.shape[0] for x in arrs if x is not None)
+    assert all(x is None or x.shape[0] == count for x in arrs)
+    ow = 2 * limbs if op == "setup" else (16 if limbs <= 16 else 32) if op == "sub" else limbs
+    out = np.zeros((count, ow), dtype=np.uint64)
+    flag = np.zeros(count, dtype=np.uint64)
+    ptr = [None if x is None else x.ctypes.data for x in arrs]
+    if lib().pzp_prime_ops(device, code, limbs, count, ptr[0], ptr[1], ptr[2], out.ctypes.data, flag.ctypes.data) != 0:
+        raise RuntimeError("probe launch refused or failed")
+    return out, flag
 
 
 def ubench_mfma(device: int, which: int, blocks: int, iters: int) -> float:

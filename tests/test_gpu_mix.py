@@ -650,3 +650,60 @@ def test_forged_edges_are_rejected(eng, cref, world, forge):
         ph = prover_native.create_proof(w.key, hcols.data_ptr(), prover.HashTranscript(seed), seed=9, instances=hinst)
         assert not pf.h_degree_ok and ph.h_degree_ok
         assert PV.verify_batch(eng, w.params, w.vk, [pf, ph], [seed, seed], instances=[inst, hinst]) == (False, [False, True])
+
+
+# ------------------------------------------------------------------------------------------------------------------ 7. K3 under structured n
+# n of 8, 9, 31, 32, 33 and 49 limbs that are runs of ones and zeros, and two Mersenne-product keys, as
+# section 15.13 runs wtally, ballot, encrypt and partial: k_mix_rerand's r^n chain runs over every bit of such an n
+STRUCT_SHAPES = [(ln, tb) for ln in (8, 9, 31, 32, 33, 49) for tb in (1, 64)] + [("mersenne", 3), ("mersenne", 5)]
+
+
+def _struct_ns(ln, tb):
+    if ln == "mersenne":
+        p, q = KO.mersenne_primes(tb)
+        return KO.words((p * q).bit_length()), [("mersenne%d" % KO.MERSENNE_BITS[tb], p * q)]
+    ms = KO.moduli(KO.bits_of(ln, tb))
+    return ln, [(cls, ms[cls]) for cls in ("all_ones", "pow2_plus1", "alt32_hi")]
+
+
+def _bytes_rows(vals, L):
+    return np.frombuffer(b"".join(int(v).to_bytes(8 * L, "little") for v in vals), dtype=np.uint64).reshape(len(vals), L).copy()
+
+
+@pytest.mark.parametrize("ln,tb", STRUCT_SHAPES)
+def test_k3_under_structured_n_equals_the_reference(eng, ln, tb):
+    """K = 1 and K = 2 (the switch set, and clear at a one-bit top limb): c in {1, n + 1, n^2 - 1, an encryption} and r in {1, n - 1, 2^k}, every record; a
+    ciphertext of exactly n^2 is refused with PZ_ERR_RANGE and nothing is written"""
+    from paillier_halo2_amd import _lib
+
+    Ln, cases = _struct_ns(ln, tb)
+    L = 2 * Ln
+    for cls, n in cases:
+        n2 = n * n
+        enc = (1 + KO.by_name(n, Ln)["alt64"] * n) * pow(3, n, n2) % n2
+        two_k = 1 << (n.bit_length() - 2)
+        runs = [([1], [], [n - 1]), ([n2 - 1], [], [two_k]), ([n + 1, enc], [1 if tb != 1 else 0], [1, two_k])]
+        for cts, sw, rs in runs:
+            K = len(cts)
+            where = (ln, tb, cls, K, sw)
+            mixed, routes, steps = eng.paillier_mix(Ln, _bytes_rows([n], Ln)[0], _bytes_rows(cts, L), np.array(sw, dtype=np.uint8), _bytes_rows(rs, Ln))
+            tr = MR.mix_trace(n, cts, sw, rs)
+            perm = list(range(K)) if not sw or sw[0] == 0 else [1, 0]
+            assert tr.mixed == [cts[p] * pow(r, n, n2) % n2 for p, r in zip(perm, rs)], where
+            assert [int.from_bytes(row.tobytes(), "little") for row in mixed] == tr.mixed, where
+            for l, layer in enumerate(tr.layers):
+                assert np.array_equal(routes[l], _bytes_rows(layer, L)), where + ("layer %d" % l,)
+            want = MR.records(tr)
+            want_arr = _bytes_rows([v for st in want for v in st], L).reshape(len(want), 4, L)
+            assert steps.shape == (K, MR.n_steps_r(n) + 1, 4, L), where
+            bad = np.nonzero((steps.reshape(-1, 4, L) != want_arr).any(axis=(1, 2)))[0]
+            assert bad.size == 0, where + ("record %d differs" % bad[0],)
+        # a ciphertext of exactly n^2: the kernel's range bit, outputs untouched
+        K, nr = 2, MR.n_steps_r(n)
+        routes = np.full((1, K, L), 0xA5, dtype=np.uint64)
+        steps = np.full((K * (nr + 1), 4, L), 0xA5, dtype=np.uint64)
+        out = np.full((K, L), 0xA5, dtype=np.uint64)
+        n_, c_, r_, b_ = _bytes_rows([n], Ln), _bytes_rows([n + 1, n2], L), _bytes_rows([1, 2], Ln), np.array([1], dtype=np.uint8)
+        rc = eng.L.pz_paillier_mix(eng.ctx, Ln, K, n_.ctypes.data, c_.ctypes.data, b_.ctypes.data, r_.ctypes.data, routes.ctypes.data,
+                                   steps.ctypes.data, K * (nr + 1), out.ctypes.data)
+        assert rc == _lib.PZ_ERR_RANGE and (routes == 0xA5).all() and (steps == 0xA5).all() and (out == 0xA5).all(), (ln, tb, cls)

@@ -582,3 +582,59 @@ def test_sballots_feed_the_tally_and_decrypt_to_the_sum(eng, cref):
         assert fl1.tolist() == [0] and cref.limbs_to_int(m1[0]) == 3 and cref.limbs_to_int(r1[0]) == pow(h, ss[0], n)
     finally:
         sk.free()
+
+
+# ------------------------------------------------------------------------------------------------------------------ 6. K3 under structured n
+# n of 8, 9, 31, 32, 33 and 49 limbs (below, at and past a team's slice boundaries) that are runs of ones and
+# zeros, and two Mersenne-product keys, as section 15.13 runs wtally, ballot, encrypt and partial
+from tests import k3_operands as KO  # noqa: E402
+
+STRUCT_SHAPES = [(ln, tb) for ln in (8, 9, 31, 32, 33, 49) for tb in (1, 64)] + [("mersenne", 3), ("mersenne", 5)]
+STRUCT_B = 2
+
+
+def _struct_ns(ln, tb):
+    if ln == "mersenne":
+        p, q = KO.mersenne_primes(tb)
+        return KO.words((p * q).bit_length()), [("mersenne%d" % KO.MERSENNE_BITS[tb], p * q)]
+    ms = KO.moduli(KO.bits_of(ln, tb))
+    return ln, [(cls, ms[cls]) for cls in ("all_ones", "pow2_plus1", "alt32_hi")]
+
+
+def _bytes_rows(vals, L):
+    return np.frombuffer(b"".join(int(v).to_bytes(8 * L, "little") for v in vals), dtype=np.uint64).reshape(len(vals), L).copy()
+
+
+@pytest.mark.parametrize("ln,tb", STRUCT_SHAPES)
+def test_k3_under_structured_n_equals_the_reference(eng, ln, tb):
+    """s in {0, all ones, a lone top bit} with m in {0, 2^b - 1}, at s_bits 1, 64 and 65, under hs in {1, n + 1, n^2 - 1, a true h^n};
+    hs = n^2 is refused with PZ_ERR_RANGE and nothing is written"""
+    from paillier_halo2_amd import _lib
+
+    Ln, cases = _struct_ns(ln, tb)
+    L, b = 2 * Ln, STRUCT_B
+    for cls, n in cases:
+        n2 = n * n
+        g = KO.by_name(n, Ln)["alt64"]
+        n_, g_ = _bytes_rows([n], Ln)[0], _bytes_rows([g], Ln)[0]
+        for hs_name, hs in (("1", 1), ("n+1", n + 1), ("n^2-1", n2 - 1), ("h^n", SR.djn_hs(n, 2))):
+            for s_bits in ((65,) if hs_name in ("1", "n+1") else (1, 64, 65)):      # every hs across a limb of s; 1 and 64 bits under two
+                ss = list(dict.fromkeys(_specials(s_bits)))
+                ms = [[0, (1 << b) - 1][(i + s_bits) % 2] for i in range(len(ss))]      # both messages meet every s over the three widths
+                where = (ln, tb, cls, hs_name, s_bits)
+                c, steps = eng.paillier_sballot(Ln, n_, g_, _bytes_rows([hs], L)[0], _u64(ms), _bytes_rows(ss, _words(s_bits)), b, s_bits)
+                tr = SR.sballot_trace(n, g, hs, ms, ss, b, s_bits)
+                want = SR.records(tr)
+                assert [int.from_bytes(row.tobytes(), "little") for row in c] == tr.cts == [SR.encrypt(n, g, hs, m, s) for m, s in zip(ms, ss)], where
+                want_arr = _bytes_rows([v for st in want for v in st], L).reshape(len(want), 4, L)
+                bad = np.nonzero((steps.reshape(-1, 4, L) != want_arr).any(axis=(1, 2)))[0]
+                assert bad.size == 0, where + ("record %d differs" % bad[0],)
+        # hs of exactly n^2: the kernel's range bit, outputs untouched
+        s_bits, K = 65, 2
+        per = SR.per_entry(b, s_bits)
+        steps = np.full((K * per, 4, L), 0xA5, dtype=np.uint64)
+        out = np.full((K, L), 0xA5, dtype=np.uint64)
+        h_, m_, s_ = _bytes_rows([n2], L)[0], _u64([1, 2]), _bytes_rows([1, 1 << 64], 2)
+        rc = eng.L.pz_paillier_sballot(eng.ctx, Ln, K, b, s_bits, n_.ctypes.data, g_.ctypes.data, h_.ctypes.data, m_.ctypes.data, s_.ctypes.data,
+                                       steps.ctypes.data, K * per, out.ctypes.data)
+        assert rc == _lib.PZ_ERR_RANGE and (steps == 0xA5).all() and (out == 0xA5).all(), (ln, tb, cls)
