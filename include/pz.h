@@ -1011,7 +1011,9 @@ int pz_permutation_product_dev(pz_ctx* ctx, const uint64_t* d_cols, size_t col_s
                                const uint64_t delta[4], const uint64_t z0[4], uint64_t* d_z);
 /* all sets of the permutation argument in one call: m columns in chunks of chunk_len (set j = columns
  * [j*chunk_len, ...), delta powers continuing across sets); d_z[0][0] = 1 and d_z[j][0] = d_z[j-1][usable_rows], as
- * halo2 chains them.  The sets are computed independently (one batched inversion, one batched scan), then chained. */
+ * halo2 chains them.  Per batch of sets: the terms stored once, a prefix scan of the numerators and a suffix scan of the
+ * denominators, one inversion per set; the chaining value enters a set's scan as its start value (a zero denominator inverts to
+ * zero, as in pz_fr_batch_invert_dev).  The environment variable PZ_PERM_SET_BATCH caps the sets per batch (tests). */
 int pz_permutation_product_sets_dev(pz_ctx* ctx, const uint64_t* d_cols, size_t col_stride, const uint64_t* d_sigma,
                                     size_t sigma_stride, size_t m, uint32_t chunk_len, uint32_t log_n, size_t usable_rows,
                                     const uint64_t omega[4], const uint64_t beta[4], const uint64_t gamma[4],

@@ -393,8 +393,8 @@ extern "C" int pz_permutation_product_dev(pz_ctx* ctx, const uint64_t* d_cols, s
 }
 
 // all sets of the permutation argument at once: set j covers columns [j*chunk_len, ...), its product starts where the
-// previous set's stood at row `usable_rows` (halo2: z_j[0] = z_{j-1}[u]).  The sets are computed independently from 1
-// (one batched inversion, one batched scan) and chained afterwards by a scalar per set.
+// previous set's stood at row `usable_rows` (halo2: z_j[0] = z_{j-1}[u]).  The terms of a batch of sets are stored once
+// (k_perm_terms_sets); the k_gp_* kernels below scan them, and the chaining scalar enters each set's scan as its start value.
 __global__ __launch_bounds__(256) void k_perm_terms_sets(const Fr* __restrict__ cols, size_t cs, const Fr* __restrict__ sigma,
                                                          size_t ss, unsigned m, unsigned chunk_len, size_t n,
                                                          const Fr* __restrict__ wpow, const Fr* __restrict__ dpow,
@@ -417,17 +417,164 @@ __global__ __launch_bounds__(256) void k_perm_terms_sets(const Fr* __restrict__ 
         dn = f29_mul(dn, f29_add(v, f29_mul_s(sg, beta266.v)));
         bd = f29_mul_s(bd, d.v);
     }
-    f29_store_product(num + (size_t)set * n + i, nm);   // one256 (an empty set) or a product: strict limbs, below 2p
-    f29_store_product(den + (size_t)set * n + i, dn);
+    // one256 (an empty set) or a product: strict limbs, below 2p.  The scans divide by the product of ALL denominators of the set, so a
+    // zero denominator is taken out here: it inverts to zero (ff::BatchInvert skips it and leaves 0, the convention of k_batch_invert),
+    // the ratio of its row is 0 -- stored as the pair (num', den') = (0, 1)
+    f29_cond_sub_kp<FrTag, 1>(dn);   // canonical: zero is the all-zero limb pattern
+    if (f29_is_zero_exact(dn)) {
+        dn = fr29_one256();
+        nm = f29_zero<FrTag>();
+    }
+    Fr w;
+    f29_pack(dn, w.v);
+    f29_store_product(num + (size_t)set * n + i, nm);
+    fp_store(den + (size_t)set * n + i, w);
 }
-// mult[j] = prod_{t < j} z_t[u]: the exclusive prefix product over the sets that chains them (z_j starts where z_{j-1} stood at row
-// u).  One workgroup: thread runs over consecutive sets, a Hillis-Steele scan over the 256 run products (a single lane walking
-// 128 dependent products took 145 us per call, 13 calls per proof)
-__global__ __launch_bounds__(256) void k_perm_chain(const Fr* __restrict__ z, size_t zs, unsigned n_sets, size_t u, Fr* __restrict__ mult) {
+// ---- the grand products of a batch of sets from two scans and ONE inversion per set.  With PN_i, PD_i the exclusive prefix products
+// of a set's numerators and denominators and SD_i = prod_{k >= i} den_k:  z_i = chain * PN_i / PD_i = chain * PD_total^-1 * PN_i * SD_i.
+// Three passes over the stored pair instead of Montgomery's batched inversion (a prefix array written and re-read, den read twice), a
+// scan of the ratios and a scaling pass:
+//   k_gp_local   run products of consecutive rows per thread, workgroup PREFIX scan of the numerator runs and SUFFIX scan of the
+//                denominator runs (raw limbs in LDS, as k_pp_local); the partial products at row u of the one thread that holds it
+//   k_gp_sets    one lane per set: the block totals scanned in place, PD_total inverted, the set's own value at row u
+//   k_gp_chain   one workgroup: the exclusive product of those values over the sets, carried across the host loop's batches, folded
+//                with PD_total^-1 into one start value per set
+//   k_gp_apply   a backward sweep over a thread's denominators (the suffix products stay in registers, packed, in the slots the
+//                loaded values came in), a forward sweep over its numerators, one product joins them: z written once
+// Domains: the numerator side runs in the 256-domain (block prefix) x 261-domain (thread prefix) as in k_pp_apply; the whole
+// denominator side -- seed, block suffix, thread suffix, the swept products -- in the 261-domain, so N * S lands in the 256-domain.
+// A thread of k_gp_apply owns GP_K rows (what its registers hold); a thread of k_gp_local owns two such runs, so the workgroup
+// scan -- 8 products per thread and side whatever the run length -- is paid once per 2 GP_K rows, and hands each run its own
+// exclusive value: the thread's for the first (numerators) or second (denominators) run, that times the other run's product for
+// the other.  The run products start from 1 in the 261-domain: every value of the scan is in that domain with no conversion.
+#define GP_K 8u
+__global__ __launch_bounds__(256) void k_gp_local(const Fr* __restrict__ num, const Fr* __restrict__ den, size_t n, size_t u,
+                                                  Fr* __restrict__ excl_n, Fr* __restrict__ excl_d, Fr* __restrict__ tot_n,
+                                                  Fr* __restrict__ tot_d, Fr* __restrict__ at_u, unsigned nb) {
+    __shared__ u32 sn[9 * 256], sd[9 * 256];   // limb-major: s[limb * 256 + thread]
+    num += (size_t)blockIdx.y * n;
+    den += (size_t)blockIdx.y * n;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t lo = t * (2 * GP_K);
+    Fr29 n0 = f29_one<FrTag>(), n1 = n0, d0 = n0, d1 = n0;   // the products of the two runs
+    for (unsigned j = 0; j < GP_K; ++j) {
+        if (lo + j < n) {
+            n0 = f29_mul(n0, f29_load_shl5<FrTag>(num + lo + j));
+            d0 = f29_mul(d0, f29_load_shl5<FrTag>(den + lo + j));
+        }
+        if (lo + GP_K + j < n) {
+            n1 = f29_mul(n1, f29_load_shl5<FrTag>(num + lo + GP_K + j));
+            d1 = f29_mul(d1, f29_load_shl5<FrTag>(den + lo + GP_K + j));
+        }
+    }
+    Fr29 pn = f29_mul(n0, n1), pd = f29_mul(d0, d1);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        sn[i * 256 + threadIdx.x] = pn.v[i];
+        sd[i * 256 + threadIdx.x] = pd.v[i];
+    }
+    __syncthreads();
+    for (unsigned off = 1; off < 256; off <<= 1) {  // Hillis-Steele, inclusive: the numerators from the left, the denominators from the right
+        const bool left = threadIdx.x >= off, right = threadIdx.x + off < 256;
+        Fr29 a, b;
+        if (left) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) a.v[i] = sn[i * 256 + threadIdx.x - off];
+        }
+        if (right) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) b.v[i] = sd[i * 256 + threadIdx.x + off];
+        }
+        __syncthreads();
+        if (left) {
+            pn = f29_mul(a, pn);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) sn[i * 256 + threadIdx.x] = pn.v[i];
+        }
+        if (right) {
+            pd = f29_mul(pd, b);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) sd[i * 256 + threadIdx.x] = pd.v[i];
+        }
+        __syncthreads();
+    }
+    Fr29 en = f29_one<FrTag>(), ed = en;
+    if (threadIdx.x) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) en.v[i] = sn[i * 256 + threadIdx.x - 1];
+    }
+    if (threadIdx.x < 255) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) ed.v[i] = sd[i * 256 + threadIdx.x + 1];
+    }
+    Fr* xn = excl_n + ((size_t)blockIdx.y * nb * 256 + t) * 2;   // one entry per run of GP_K rows
+    Fr* xd = excl_d + ((size_t)blockIdx.y * nb * 256 + t) * 2;
+    Fr w;
+    f29_pack(en, w.v);   // strict limbs, below 2p
+    fp_store(xn, w);
+    f29_pack(f29_mul(en, n0), w.v);
+    fp_store(xn + 1, w);
+    f29_pack(f29_mul(ed, d1), w.v);
+    fp_store(xd, w);
+    f29_pack(ed, w.v);
+    fp_store(xd + 1, w);
+    if (threadIdx.x == 255) f29_store_product(tot_n + (size_t)blockIdx.y * nb + blockIdx.x, f29_to_256(pn));
+    if (threadIdx.x == 0) f29_store_product(tot_d + (size_t)blockIdx.y * nb + blockIdx.x, f29_to_256(pd));
+    if (lo <= u && u < lo + 2 * GP_K) {
+        // the set's value at row u is wanted before the apply pass (it starts the next set): this block's share of PN_u and SD_u,
+        // from the one thread that holds row u (one wave per set walks its rows a second time)
+        Fr29 qn = fr29_one256(), qd = qn;
+        for (size_t i = lo; i < u; ++i) qn = f29_mul(qn, f29_load_shl5<FrTag>(num + i));
+        for (size_t i = u; i < lo + 2 * GP_K && i < n; ++i) qd = f29_mul(qd, f29_load_shl5<FrTag>(den + i));
+        f29_store_product(at_u + 2 * (size_t)blockIdx.y, f29_mul(qn, en));
+        f29_store_product(at_u + 2 * (size_t)blockIdx.y + 1, f29_mul(qd, ed));
+    }
+}
+// per set (one lane each; a few dozen block totals): tot_n <- the exclusive prefix of the numerator totals (256-domain), tot_d <- the
+// exclusive suffix of the denominator totals (261-domain), both packed, not canonical; inv <- PD_total^-1 (261-domain);
+// zu <- PN_u / PD_u, the value the set would take at row u had it started from 1.  bu = the block that holds row u.
+// f29_inv: fed x * 2^261 it returns x^-1 * 2^261; PD_total is a product of non-zero factors (k_perm_terms_sets stores none).
+__global__ __launch_bounds__(64) void k_gp_sets(Fr* __restrict__ tot_n, Fr* __restrict__ tot_d, const Fr* __restrict__ at_u, unsigned nb,
+                                                unsigned n_sets, unsigned bu, Fr* __restrict__ zu, Fr* __restrict__ inv) {
+    const unsigned s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_sets) return;
+    Fr* tn = tot_n + (size_t)s * nb;
+    Fr* td = tot_d + (size_t)s * nb;
+    Fr w;
+    Fr29 run = fr29_one256(), pre_u = run;
+    for (unsigned b = 0; b < nb; ++b) {
+        const Fr29 t = f29_load_shl5<FrTag>(tn + b);
+        if (b == bu) pre_u = run;
+        f29_pack(run, w.v);
+        fp_store(tn + b, w);
+        run = f29_mul(run, t);
+    }
+    Fr29 rd = f29_one<FrTag>(), suf_u = rd;
+    for (unsigned b = nb; b-- > 0;) {
+        const Fr29 t = f29_load_shl5<FrTag>(td + b);
+        if (b == bu) suf_u = rd;
+        f29_pack(rd, w.v);
+        fp_store(td + b, w);
+        rd = f29_mul(rd, t);
+    }
+    const Fr29 iv = f29_inv(rd);
+    f29_pack(iv, w.v);
+    fp_store(inv + s, w);
+    const Fr29 nu = f29_mul(pre_u, f29_load_shl5<FrTag>(at_u + 2 * (size_t)s));                        // PN_u, 256-domain
+    const Fr29 du = f29_mul(f29_mul(suf_u, f29_load_shl5<FrTag>(at_u + 2 * (size_t)s + 1)), iv);      // SD_u / PD_total, 261-domain
+    f29_store_product(zu + s, f29_mul(nu, du));
+}
+// seed[j] = carry * prod_{t < j} zu[t] * inv[j]: the exclusive product over the batch's sets that chains them (z_j starts where z_{j-1}
+// stood at row u), times the set's PD_total^-1 -- the start value of the set's denominator sweep (261-domain, packed).  *carry holds the
+// product over all earlier batches (1 when `first`) and takes this batch's in.  One workgroup: thread runs over consecutive sets, a
+// Hillis-Steele scan over the 256 run products (a single lane walking 128 dependent products took 145 us per call)
+__global__ __launch_bounds__(256) void k_gp_chain(const Fr* __restrict__ zu, const Fr* __restrict__ inv, unsigned n_sets, int first,
+                                                  Fr* __restrict__ carry, Fr* __restrict__ seed) {
     __shared__ Fr s_p[256];
     const unsigned per = (n_sets + 255u) / 256u, lo = threadIdx.x * per, hi = lo + per < n_sets ? lo + per : n_sets;
+    const Fr c_in = first ? fp_one<FrTag>() : fp_load<FrTag>(carry);
     Fr p = fp_one<FrTag>();
-    for (unsigned j = lo; j < hi; ++j) p = fp_mul(p, fp_load<FrTag>(z + (size_t)j * zs + u));
+    for (unsigned j = lo; j < hi; ++j) p = fp_mul(p, fp_load<FrTag>(zu + j));
     s_p[threadIdx.x] = p;
     __syncthreads();
     for (unsigned off = 1; off < 256; off <<= 1) {
@@ -440,17 +587,47 @@ __global__ __launch_bounds__(256) void k_perm_chain(const Fr* __restrict__ z, si
         }
         __syncthreads();
     }
-    Fr c = threadIdx.x ? s_p[threadIdx.x - 1] : fp_one<FrTag>();
+    Fr c = threadIdx.x ? fp_mul(c_in, s_p[threadIdx.x - 1]) : c_in;
     for (unsigned j = lo; j < hi; ++j) {
-        fp_store(mult + j, c);
-        c = fp_mul(c, fp_load<FrTag>(z + (size_t)j * zs + u));
+        Fr w;
+        f29_pack(f29_mul(f29_from_fp_shl5(c), f29_load<FrTag>(inv + j)), w.v);
+        fp_store(seed + j, w);
+        c = fp_mul(c, fp_load<FrTag>(zu + j));
     }
+    if (threadIdx.x == 255) fp_store(carry, fp_mul(c_in, p));   // every thread read *carry before the scan's barriers
 }
-__global__ __launch_bounds__(256) void k_scale_sets(Fr* __restrict__ z, size_t zs, size_t n, const Fr* __restrict__ mult) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || blockIdx.y == 0) return;
-    Fr* p = z + (size_t)blockIdx.y * zs + i;
-    fp_store(p, fp_mul(fp_load<FrTag>(p), fp_load<FrTag>(mult + blockIdx.y)));
+// z[i] = (block prefix * thread prefix * run prefix of num') * (seed * block suffix * thread suffix * run suffix of den')
+__global__ __launch_bounds__(256) void k_gp_apply(const Fr* __restrict__ num, const Fr* __restrict__ den, size_t n,
+                                                  const Fr* __restrict__ excl_n, const Fr* __restrict__ excl_d,
+                                                  const Fr* __restrict__ tot_n, const Fr* __restrict__ tot_d,
+                                                  const Fr* __restrict__ seed, unsigned nb, Fr* __restrict__ z, size_t zs) {
+    num += (size_t)blockIdx.y * n;
+    den += (size_t)blockIdx.y * n;
+    z += (size_t)blockIdx.y * zs;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t lo = t * GP_K;
+    if (lo >= n) return;
+    const unsigned cnt = n - lo < GP_K ? (unsigned)(n - lo) : GP_K;   // below GP_K only when n is
+    Fr hold[GP_K];
+#pragma unroll
+    for (unsigned j = 0; j < GP_K; ++j)
+        if (j < cnt) hold[j] = fp_load<FrTag>(den + lo + j);
+    Fr29 sd = f29_mul(f29_mul(f29_load<FrTag>(seed + blockIdx.y), f29_load<FrTag>(tot_d + (size_t)blockIdx.y * nb + blockIdx.x / 2)),
+                      f29_load<FrTag>(excl_d + (size_t)blockIdx.y * nb * 512 + t));
+#pragma unroll
+    for (unsigned j = GP_K; j-- > 0;)
+        if (j < cnt) {
+            sd = f29_mul(sd, f29_from_fp_shl5(hold[j]));   // seed / PD_total * SD_{lo + j}
+            f29_pack(sd, hold[j].v);                       // a product: strict limbs, below 2p
+        }
+    Fr29 cur = f29_mul(f29_load<FrTag>(tot_n + (size_t)blockIdx.y * nb + blockIdx.x / 2),
+                       f29_load<FrTag>(excl_n + (size_t)blockIdx.y * nb * 512 + t));
+#pragma unroll
+    for (unsigned j = 0; j < GP_K; ++j)
+        if (j < cnt) {
+            f29_store_product(z + lo + j, f29_mul(cur, f29_from_fp(hold[j])));
+            if (j + 1 < GP_K) cur = f29_mul(cur, f29_load_shl5<FrTag>(num + lo + j));
+        }
 }
 
 extern "C" int pz_permutation_product_sets_dev(pz_ctx* ctx, const uint64_t* d_cols, size_t col_stride, const uint64_t* d_sigma,
@@ -466,34 +643,53 @@ extern "C" int pz_permutation_product_sets_dev(pz_ctx* ctx, const uint64_t* d_co
     if ((m > 1 && (col_stride < 4 * n || sigma_stride < 4 * n)) || (n_sets > 1 && z_stride < 4 * n)) return PZ_ERR_INVALID;
     if (!host_fr_canonical(beta) || !host_fr_canonical(gamma) || !host_fr_canonical(delta)) return PZ_ERR_INVALID;   // pz.h: challenges below r
     PZ_ENTER(ctx);
-    void *wp, *dp, *ws, *mu;
+    void *wp, *dp, *ws, *sc, *mu;
     PZCHK(pz_get_pow_table(ctx, omega, n, &wp));
     PZCHK(pz_get_pow_table(ctx, delta, m, &dp));
     // numerators and denominators of a BATCH of sets at a time: the workspace is bounded (4 GiB of terms: 512 sets of 2^17 rows, 128 of
     // 2^19) instead of growing with the circuit -- at BASELINE config c5 (1200 sets of 2^19 rows) all sets at once would be 40 GB of
-    // library workspace beside a proving key that has to share 288 GB with it.  Sets are independent until the chaining below.
+    // library workspace beside a proving key that has to share 288 GB with it.  A set depends on the earlier ones through one scalar,
+    // its start value: k_gp_chain carries the running product from batch to batch.
+    // PZ_PERM_SET_BATCH (1 ..) caps the sets per batch: the carry across batches at sizes a test can afford (read at every call).
     size_t sb = ((size_t)4 << 30) / (2 * n * 32);
     if (sb < 1) sb = 1;
+    if (const char* e = getenv("PZ_PERM_SET_BATCH")) {
+        const long cap = atol(e);
+        if (cap >= 1 && (size_t)cap < sb) sb = (size_t)cap;
+    }
     if (sb > n_sets) sb = n_sets;
+    const unsigned nb = (unsigned)pz_div_up(pz_div_up(n, 2 * GP_K), 256);   // workgroups of the scan per set: 512 runs of GP_K rows each
+    const unsigned nba = (unsigned)pz_div_up(pz_div_up(n, GP_K), 256);     // workgroups of the apply pass: 256 runs each
+    const unsigned bu = (unsigned)(usable_rows / (2 * GP_K) / 256);
     PZCHK(pz_ws_get(ctx, WS_BIG_C, 2 * sb * n * 32, &ws));
-    PZCHK(pz_ws_get(ctx, WS_MISC, n_sets * 32, &mu));
+    PZCHK(pz_ws_get(ctx, WS_BIG_B, 2 * sb * ((size_t)nb * 512 + nb) * 32, &sc));
+    PZCHK(pz_ws_get(ctx, WS_MISC, (5 * sb + 1) * 32, &mu));
     Fr* num = (Fr*)ws;
     Fr* den = num + sb * n;
+    Fr* excl_n = (Fr*)sc;
+    Fr* excl_d = excl_n + sb * (size_t)nb * 512;
+    Fr* tot_n = excl_d + sb * (size_t)nb * 512;
+    Fr* tot_d = tot_n + sb * (size_t)nb;
+    Fr* at_u = (Fr*)mu;          // 2 per set
+    Fr* zu = at_u + 2 * sb;
+    Fr* inv = zu + sb;
+    Fr* seed = inv + sb;
+    Fr* carry = seed + sb;
     for (size_t s0 = 0; s0 < n_sets; s0 += sb) {
         const size_t ns = n_sets - s0 < sb ? n_sets - s0 : sb;
         hipLaunchKernelGGL(k_perm_terms_sets, dim3(pz_div_up(n, 256), (unsigned)ns), dim3(256), 0, ctx->stream,
                            (const Fr*)d_cols, col_stride / 4, (const Fr*)d_sigma, sigma_stride / 4, (unsigned)m, (unsigned)chunk_len, n,
                            (const Fr*)wp, (const Fr*)dp, host_fr_shl(beta, 10), host_fr_shl(gamma, 5), host_fr_shl(delta, 5), num, den,
                            (unsigned)s0);
-        HIPCHK(ctx, hipGetLastError());
-        PZCHK(pz_batch_invert_internal(ctx, den, ns * n, num));   // num <- num / den
-        PZCHK(pz_prefix_product_batch_internal(ctx, num, n, ns, n, fp_one_host(), (Fr*)d_z + s0 * (z_stride / 4), z_stride / 4));
-    }
-    if (n_sets > 1) {
-        hipLaunchKernelGGL(k_perm_chain, dim3(1), dim3(256), 0, ctx->stream, (const Fr*)d_z, z_stride / 4, (unsigned)n_sets,
-                           usable_rows, (Fr*)mu);
-        hipLaunchKernelGGL(k_scale_sets, dim3(pz_div_up(n, 256), (unsigned)n_sets), dim3(256), 0, ctx->stream, (Fr*)d_z,
-                           z_stride / 4, n, (const Fr*)mu);
+        hipLaunchKernelGGL(k_gp_local, dim3(nb, (unsigned)ns), dim3(256), 0, ctx->stream, (const Fr*)num, (const Fr*)den, n, usable_rows,
+                           excl_n, excl_d, tot_n, tot_d, at_u, nb);
+        hipLaunchKernelGGL(k_gp_sets, dim3(pz_div_up(ns, 64)), dim3(64), 0, ctx->stream, tot_n, tot_d, (const Fr*)at_u, nb, (unsigned)ns, bu,
+                           zu, inv);
+        hipLaunchKernelGGL(k_gp_chain, dim3(1), dim3(256), 0, ctx->stream, (const Fr*)zu, (const Fr*)inv, (unsigned)ns, s0 == 0 ? 1 : 0,
+                           carry, seed);
+        hipLaunchKernelGGL(k_gp_apply, dim3(nba, (unsigned)ns), dim3(256), 0, ctx->stream, (const Fr*)num, (const Fr*)den, n,
+                           (const Fr*)excl_n, (const Fr*)excl_d, (const Fr*)tot_n, (const Fr*)tot_d, (const Fr*)seed, nb,
+                           (Fr*)d_z + s0 * (z_stride / 4), z_stride / 4);
         HIPCHK(ctx, hipGetLastError());
     }
     return PZ_OK;
