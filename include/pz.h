@@ -416,6 +416,39 @@ int pz_paillier_mix_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint6
                         const uint64_t* rs, uint64_t* d_routes_out, uint64_t* d_steps_out, size_t steps_cap, uint64_t* mixed_out);
 int pz_mix_route(size_t count, const uint32_t* perm, uint8_t* bits_out);
 
+/* The short-randomness mix: a mixer of an election that casts short-randomness ballots publishes
+ * c'_i = c_perm(i) * hs^s_i mod n^2 under the key (n, hs), hs = h^n mod n^2 (keys.djn_generator) -- pz_paillier_mix with every r_i^n
+ * chain of bits(n) + popcount(n) steps replaced by an hs^s_i chain of 2 s_bits steps over a SHORT secret s_i.  c'_i holds what
+ * c_perm(i) holds only if hs is an n-th residue: that is the key authority's to show (circuit kind 5, or kind 7 and a combiner), not
+ * this call's.  Hiding rests on the short-exponent assumption in <hs>: s_bits is the caller's and has no default.  K = count is a power
+ * of two in 1 .. 1024, 1 <= s_bits <= 128*limbs_n; n: limbs_n words; hs: 2*limbs_n words; cts = count x 2*limbs_n words; ss = count x
+ * ceil(s_bits/64) words, as pz_paillier_sballot takes them; bits, routes_out, mixed_out exactly as pz_paillier_mix (HOST).
+ * The network is pz_paillier_mix's, launched as it launches it: on the same cts and bits the route layers are the same words.
+ * steps_out (steps_cap >= count * (2 s_bits + 1) records, else PZ_ERR_CAPACITY; may be NULL: the values only): records a|b|q|r of
+ * 2*limbs_n words per field, output-major -- output i's 2 s_bits records of BigUintChip::pow_mod(hs, s_i) over EXACTLY s_bits bits,
+ * LSB first (per bit the step (acc, sq) then the step (sq, sq), acc takes the product only where the bit is set; the trailing square
+ * is kept: pz_paillier_partial's and pz_paillier_sballot's chain), then the step (d_i, hss_i), d_i the last layer's value at position
+ * i (c_1 for K = 1), whose remainder is c'_i.
+ * Refusals, in this order: a null pointer (bits and routes_out may be NULL for K = 1), limbs_n = 0, a count that is no power of two in
+ * 1 .. 1024, s_bits out of range: PZ_ERR_INVALID; 2*limbs_n > 128: PZ_ERR_UNSUPPORTED; a short steps_cap: PZ_ERR_CAPACITY; a bit byte
+ * above 1 or an s_i >= 2^s_bits: PZ_ERR_MESSAGE_RANGE; n = 0: PZ_ERR_ZERO_MODULUS -- all before any launch.  An hs >= n^2 or a c_j >=
+ * n^2: PZ_ERR_RANGE (found by the kernel; the status is read before anything is copied out).  No output buffer is written on a
+ * refusal.  hs = 0 and s_i = 0 are not refused (verifier.public_inputs("smix") refuses hs = 0 and an output 0).
+ * One launch per layer over its K / 2 switches, then ONE launch of K teams for the chains and products; no workgroup waits on
+ * another; n^2 and its Barrett constants are formed once.  The bits, the s_i and the route layers are SECRET: a switch reads both
+ * inputs and writes both outputs under a lane-wise mask made from its bit, bit t of s_i is read from word t / 64, an address that
+ * depends on t alone, and reaches the accumulator as a lane-wise mask; no address or branch depends on a bit or on s_i (the
+ * value-dependent trip count of mul_mod's Barrett correction remains, as in every K3 entry point), and the staged bits and s_i (host
+ * form: the staged routes and records too) in the context's workspace are overwritten before the call returns.
+ * _dev: d_routes_out and d_steps_out are DEVICE buffers (either may be NULL; the kernels have written them by the time a c_j >= n^2
+ * is reported) and stay the caller's to overwrite; everything else as above.  (PZ_ABI_VERSION stays 7: additions.) */
+int pz_paillier_smix(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t s_bits, const uint64_t* n, const uint64_t* hs,
+                     const uint64_t* cts, const uint8_t* bits, const uint64_t* ss, uint64_t* routes_out, uint64_t* steps_out,
+                     size_t steps_cap, uint64_t* mixed_out);
+int pz_paillier_smix_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t s_bits, const uint64_t* n, const uint64_t* hs,
+                         const uint64_t* cts, const uint8_t* bits, const uint64_t* ss, uint64_t* d_routes_out, uint64_t* d_steps_out,
+                         size_t steps_cap, uint64_t* mixed_out);
+
 /* Decryption with randomness recovery, for the key holder.  The secret key is a handle: n, g, lambda and d = n^-1 mod lambda
  * (HOST words, limbs_n each; d is the caller's -- paillier_halo2_amd/keys.py::secret_from_primes computes it).
  *   pz_paillier_sk_create  forms n^2 and the Barrett constants of n^2 and of n once, derives on the device x = L(g^lambda mod n^2),
@@ -746,6 +779,43 @@ int pz_sballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits
                                size_t lookup_rows, size_t col_stride);
 int pz_sballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, uint32_t s_limbs,
                             uint64_t* cells_out, size_t capacity, size_t* n_public);
+
+/* Circuit kind 10, "smix" (DESIGN.md section 15.20): the list c'_1 .. c'_K is a re-randomised permutation of the list c_1 .. c_K under
+ * the key (n, hs) -- there are a permutation pi and s_i < 2^s_bits with c'_i = c_pi(i) hs^s_i mod n^2 for every i.  K = count is a power
+ * of two in 1 .. 1024, s_bits = s_limbs * limb_bits with 1 <= s_limbs <= 2*limbs_n.  Its shape is (K, s_limbs) and the key SIZE: no bit
+ * of n shapes it, so one proving and verifying key serves every election of a size.  The by-kind entry points refuse kind 10 and these
+ * take the two numbers (anything out of range: PZ_ERR_INVALID).  The stream, in emission order: assign_integer(n); assign_integer(hs,
+ * 2*enc_bits); assign_integer(c_j, 2*enc_bits) for j = 1 .. K; assign_integer(s_i, s_bits) for i = 1 .. K (s_limbs limbs each); square
+ * + refresh of n, once; load_zero (kept although nothing is extended by it: kinds 7, 8 and 9 emit it there); the Benes network exactly
+ * as kind 8 -- per switch [0, b, b, b], then per limb the two 8-cell selects with gate windows at 0 and 4 --; per output [1, 0],
+ * pow_mod(hs, s_i) exactly as kind 9 emits its hs-chain (per limb of s_i num_to_bits(limb, limb_bits) and that limb's blocks) and
+ * mul_mod(d_i, hss_i); then per output assign_integer(c'_i, 2*enc_bits) and assert_equal_fresh.  The selects' sel cells are tied to
+ * their switch's bit cell, their operands to the limb cells they read (layer 0: the assigned c_j; above: the previous layer's
+ * outputs), every hs-chain's first sq to assign_integer(hs)'s limb cells (all K chains run on ONE public base), every chain's
+ * num_to_bits accumulators to assign_integer(s_i)'s limb cells, the final block's operands to the last layer's outputs (K = 1: c_1's
+ * limbs) and the chain's last select outputs, its result to the assert_equal_fresh against c'_i, each assert_equal_fresh's bit to the
+ * constant 1.  The circuit compares nothing with n^2 and refuses neither hs = 0 nor s_i = 0 (verifier.public_inputs does the former).
+ *   pz_smix_cells         the stream's advice / lookup cell counts (host logic).
+ *   pz_smix_expand_dev    the values.  inputs (HOST): n (ceil(limbs_n*limb_bits/64) words) | hs (ceil(2*limbs_n*limb_bits/64) words) |
+ *       c_1 .. c_K (as hs) | s_1 .. s_K (ceil(s_bits/64) words each; an s_i >= 2^s_bits: PZ_ERR_MESSAGE_RANGE) | res_1 .. res_K (as hs).
+ *       bits (HOST): the switch bytes as pz_paillier_smix took them (a byte above 1: PZ_ERR_MESSAGE_RANGE; may be NULL for K = 1).
+ *       d_routes, d_steps (device): the route layers and the K (2 s_bits + 1) records of pz_paillier_smix_dev AS THEY ARE, fields of
+ *       2*ceil(limbs_n*limb_bits/64) words (where that differs from ceil(2*limbs_n*limb_bits/64) they are repacked on the device
+ *       first; d_routes may be NULL for K = 1).  d_modulus: n^2 (device).  rows / col_stride as pz_circuit_expand_dev.
+ *   pz_smix_expand_cols_dev  the same with the advice cells in break-point columns, as pz_circuit_expand_cols_dev.
+ *   pz_smix_public_cells  the stream indices of the exposed cells in statement order: n | hs | c_1 | .. | c_K | c'_1 | .. | c'_K (the
+ *       limb cells of the assign_integer of each): n_public = limbs_n + 2 limbs_n + 2 K 2 limbs_n. */
+int pz_smix_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs, size_t* advice_cells,
+                  size_t* lookup_cells);
+int pz_smix_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs,
+                       const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
+                       const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride);
+int pz_smix_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs,
+                            const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
+                            const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts,
+                            size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride);
+int pz_smix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs, uint64_t* cells_out,
+                         size_t capacity, size_t* n_public);
 
 /* The same stream with the ADVICE cells in halo2-lib's break-point column layout -- what the dependency's assign_with_constraints
  * [D] does with the Context's cell list when it fills the basic-gate columns (reached from bench.rs:161-171 through keygen /
@@ -1259,6 +1329,14 @@ int pz_shplonk_free(pz_ctx* ctx, pz_shplonk* state);
  * g-chain's and the hs-chain's last select outputs, its result to the assert_equal_fresh against res_i, each assert_equal_fresh's bit
  * to the constant 1.  An ordinary pz_structure (n_steps_g = 2 m_bits, n_steps_r = the 2 s_limbs limb_bits records of ONE hs-chain);
  * pz_structure_expose works on it (statement: pz_sballot_public_cells).
+ * pz_circuit_structure_smix_dev: the structure of the short-randomness mix (kind 10, pz_smix_cells) of `count` = 2^d ciphertexts (1 ..
+ * 1024) with exponents of s_limbs (1 .. 2 limbs_n) limbs.  It takes NO exponent: nothing of the key but its size shapes the circuit, and
+ * ONE key serves every mixer of every election of a size (count, s_limbs, limbs_n).  Kind 8's network walk composed with kind 9's chain
+ * walk: every select's sel cell is tied to its switch's bit cell, its operands to the limb cells they read, every hs-chain's first sq
+ * to assign_integer(hs)'s limbs, every chain's num_to_bits accumulators to assign_integer(s_i)'s limb cells, the final block's
+ * operands to the last layer's outputs and the chain's last select outputs, its result to the assert_equal_fresh against c'_i, each
+ * assert_equal_fresh's bit to the constant 1.  An ordinary pz_structure (n_steps_g = 0, n_steps_r = the 2 s_limbs limb_bits records of
+ * ONE hs-chain); pz_structure_expose works on it (statement: pz_smix_public_cells).
  * ------------------------------------------------------------------------------------------- */
 typedef struct pz_structure pz_structure;
 int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
@@ -1276,6 +1354,8 @@ int pz_circuit_structure_partial_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t lim
                                      size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_circuit_structure_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                      uint32_t m_bits, uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
+int pz_circuit_structure_smix_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                  uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_structure_info(const pz_structure* st, size_t* n_adv, size_t* n_adv_filled, size_t* n_lk, size_t* max_rows, size_t* n_constants,
                       size_t* n_cells, size_t* n_lookups, size_t* n_steps_g, size_t* n_steps_r);
 int pz_structure_arrays(const pz_structure* st, const uint8_t** d_selectors, const uint32_t** d_map_col, const uint32_t** d_map_row,

@@ -79,6 +79,8 @@ SIGNATURES = {
     "pz_paillier_mix": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_mix_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_mix_route": (C.c_int, [C.c_size_t, VP, VP]),
+    "pz_paillier_smix": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
+    "pz_paillier_smix_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_partial": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
     "pz_paillier_partial_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
     "pz_paillier_combine": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP]),
@@ -230,6 +232,14 @@ SIGNATURES = {
                                              VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "pz_sballot_public_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, VP, C.c_size_t,
                                           C.POINTER(C.c_size_t)]),
+    "pz_circuit_structure_smix_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t,
+                                                C.c_uint32, C.POINTER(VP)]),
+    "pz_smix_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "pz_smix_expand_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, VP, VP, C.c_size_t,
+                                     C.c_size_t]),
+    "pz_smix_expand_cols_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, VP, VP, VP,
+                                          C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "pz_smix_public_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "pz_structure_info": (C.c_int, [VP] + [C.POINTER(C.c_size_t)] * 9),
     "pz_structure_arrays": (C.c_int, [VP] + [C.POINTER(VP)] * 6),
     "pz_structure_free": (C.c_int, [VP]),

@@ -304,7 +304,7 @@ class StructureArrays:
     # w_B | C (wtally: a weight is ONE cell) -- pz_circuit_public_cells gives the same list -- or n | g | c_1 | .. | c_K | S (ballot: S is
     # the sum's last cell, present for K >= 2; pz_ballot_public_cells) -- or n | v | h | c_1 | u_1 | .. | c_K | u_K (partial;
     # pz_partial_public_cells) -- or n | c_1 | .. | c_K | c'_1 | .. | c'_K (mix; pz_mix_public_cells) -- or n | g | hs | c_1 | .. | c_K | S
-    # (sballot; pz_sballot_public_cells)
+    # (sballot; pz_sballot_public_cells) -- or n | hs | c_1 | .. | c_K | c'_1 | .. | c'_K (smix; pz_smix_public_cells)
     public_cells: Optional[np.ndarray] = None
 
 
@@ -333,7 +333,10 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     kind 'sballot' (circuit kind 9): count = K short-randomness ballots c_i = g^m_i hs^s_i under one key, each
     message ONE witness cell decomposed into m_bits in-circuit bits as in 'ballot', each s_i an assign_integer of s_limbs limbs that its
     chain decomposes limb by limb ('partial's walk) from the ONE base hs, for K >= 2 the sum of the messages -- no exponent is taken:
-    the shape is K, m_bits, s_limbs and the key size, so ONE structure serves every key of a size.
+    the shape is K, m_bits, s_limbs and the key size, so ONE structure serves every key of a size;
+    kind 'smix' (circuit kind 10): count = K = 2^d ciphertexts go through 'mix's network and leave as d_i
+    hs^s_i mod n^2, each s_i an assign_integer of s_limbs limbs that its chain decomposes limb by limb ('sballot's hs-chain walk) from
+    the ONE base hs -- no exponent is taken: the shape is K, s_limbs and the key size.
     device: None -> numpy arrays; a torch device ("cuda") -> the template is tiled THERE and `src` / `lookup_src` are tensors on it (at
     config c2 the tiled arrays are 3.2 GB: 0.9 s of host numpy against a few ms; `columns` takes either)."""
     dev = None
@@ -368,25 +371,25 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             constants.append(v)
         return const_id[v]
 
-    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial", "mix", "sballot"):
+    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial", "mix", "sballot", "smix"):
         raise ValueError(f"unknown circuit kind {kind!r}")
     # 'decrypt' (circuit kind 5) is the uniform-shape circuit cell for cell: the exposed list alone differs
     statement, kind = kind, ("encrypt_uniform" if kind == "decrypt" else kind)
-    if (kind in ("tally", "wtally", "ballot", "partial", "mix", "sballot")) != (count is not None):
-        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix' and 'sballot', which need it")
-    if kind == "mix":
+    if (kind in ("tally", "wtally", "ballot", "partial", "mix", "sballot", "smix")) != (count is not None):
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot' and 'smix', which need it")
+    if kind in ("mix", "smix"):
         if not mix.is_count(count):
             raise ValueError(f"a mix takes count = 1, 2, 4 .. {mix.MIX_MAX} ciphertexts, not {count}")
-        if exp_r < 1:
+        if kind == "mix" and exp_r < 1:
             raise ValueError("a mix's structure needs exp_r = the modulus n")
     if kind == "partial" and not 1 <= count <= layout.PARTIAL_MAX:
         raise ValueError(f"a trustee opens count = 1 .. {layout.PARTIAL_MAX} ciphertexts in one proof, not {count}")
     if (kind in ("ballot", "sballot")) != (m_bits is not None):
         raise ValueError("m_bits belongs to kinds 'ballot' and 'sballot', which need it")
-    if (kind == "sballot") != (s_limbs is not None):
-        raise ValueError("s_limbs belongs to kind 'sballot', which needs it")
-    if kind == "sballot" and not 1 <= s_limbs <= L:
-        raise ValueError(f"a short-randomness ballot's exponent has s_limbs = 1 .. {L} limbs, not {s_limbs}")
+    if (kind in ("sballot", "smix")) != (s_limbs is not None):
+        raise ValueError("s_limbs belongs to kinds 'sballot' and 'smix', which need it")
+    if kind in ("sballot", "smix") and not 1 <= s_limbs <= L:
+        raise ValueError(f"a short-randomness exponent has s_limbs = 1 .. {L} limbs, not {s_limbs}")
     if kind in ("ballot", "sballot"):
         if not 1 <= count <= layout.BALLOT_MAX:
             raise ValueError(f"a ballot takes count = 1 .. {layout.BALLOT_MAX} ciphertexts, not {count}")
@@ -413,9 +416,10 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         v_c = _assign(w, L, limb_bits, lb)
         th_c = _assign(w, L, limb_bits, lb)
         ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
-    elif kind == "mix":
+    elif kind in ("mix", "smix"):
+        hs_c = _assign(w, L, limb_bits, lb) if kind == "smix" else []           # hs: the key's second base, full width
         ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
-        rs_c = [_assign(w, Ln, limb_bits, lb) for _ in range(count)]
+        rs_c = [_assign(w, s_limbs if kind == "smix" else Ln, limb_bits, lb) for _ in range(count)]      # r_i; 'smix': s_i
     elif kind in ("ballot", "sballot"):
         g_c = _assign(w, Ln, limb_bits, lb)
         hs_c = _assign(w, L, limb_bits, lb) if kind == "sballot" else []        # hs: the key's second base, full width
@@ -595,7 +599,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             off, u_cells = theta_chain(off, s_cells[0])
             c_cells.append(u_cells)
         n_steps[0] = 2 * L * limb_bits
-    elif kind == "mix":
+    elif kind in ("mix", "smix"):
         # the network, layer by layer and switch by switch: assert_bit of the switch's own bit cell ([0, b, b, b]: the first b is the
         # bit's home, the other two copy it), then per limb select(in[j'], in[j], b) and select(in[j], in[j'], b) -- 8 cells each
         # [d | 1 | y | x | y | b | d | out], windows at 0 and 4.  The operands are the previous layer's out cells (layer 0: the
@@ -629,12 +633,32 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
                 nxt_c[j], nxt_c[jp] = lo_c, hi_c
             cur_c = nxt_c
         off = flush(wn)
-        # per output: pow_mod_fixed_exp(r_i_ext, n) and the block mul_mod(d_i, rn_i)
         c_cells = []
-        for i in range(count):
-            off, rn, n_steps[1] = fixed_chain(off, ext_l(rs_c[i]), exp_r)
-            off, rfin = blocks(off, np.asarray(cur_c[i], dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
-            c_cells.append(rfin[0].tolist())
+        if kind == "mix":
+            # per output: pow_mod_fixed_exp(r_i_ext, n) and the block mul_mod(d_i, rn_i)
+            for i in range(count):
+                off, rn, n_steps[1] = fixed_chain(off, ext_l(rs_c[i]), exp_r)
+                off, rfin = blocks(off, np.asarray(cur_c[i], dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
+                c_cells.append(rfin[0].tolist())
+        else:
+            # per output: pow_mod(hs, s_i) as 'sballot' walks its hs-chain -- [1, 0], then per limb of s_i num_to_bits of ITS limb cell
+            # and limb_bits bit blocks, every output's chain from the SAME hs cells -- and the block mul_mod(d_i, hss_i)
+            ut = _uniform_template(L, limb_bits, lb)
+            ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
+            ut_mask = np.zeros(ut.cells, dtype=np.uint8)
+            ut_mask[ut.gates] = 1
+            for i in range(count):
+                wc = _Walk(off)
+                one = wc.putc(1)
+                z2 = wc.putc(0)
+                off = flush(wc)
+                acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
+                sq_cells = np.asarray(hs_c, dtype=np.int64)
+                for li in range(s_limbs):
+                    off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, rs_c[i][li], limb_bits, acc_cells, sq_cells)
+                off, rfin = blocks(off, np.asarray(cur_c[i], dtype=np.int64)[None, :], acc_cells[None, :])
+                c_cells.append(rfin[0].tolist())
+            n_steps[1] = 2 * s_limbs * limb_bits
     elif kind == "ballot":
         # per ciphertext: pow_mod(g_ext, m_i) over m_bits in-circuit bits (the weighted tally's chain on the base g, extended by the
         # load_zero cell), pow_mod_fixed_exp(r_i_ext, n), the final mul_mod; then per ciphertext assign res_i + assert_equal_fresh
@@ -747,7 +771,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         n_steps[0] = nb
     else:
         off, rfin = blocks(off, np.asarray(ext_l(x_c), dtype=np.int64)[None, :], np.asarray(ext_l(y_c), dtype=np.int64)[None, :])
-    roots = c_cells if kind in ("ballot", "partial", "mix", "sballot") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
+    roots = c_cells if kind in ("ballot", "partial", "mix", "sballot", "smix") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
     ws = _Walk(off)
     res_all, eq_cells = [], []
     for c_limbs in roots:
@@ -774,8 +798,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         exposed = list(n_c) + list(v_c) + res_all[:L]
         for j in range(count):
             exposed += list(ct_c[j]) + res_all[(j + 1) * L:(j + 2) * L]
-    elif kind == "mix":
-        exposed = list(n_c) + [c for ct in ct_c for c in ct] + res_all
+    elif kind in ("mix", "smix"):
+        exposed = list(n_c) + list(hs_c) + [c for ct in ct_c for c in ct] + res_all
     elif kind in ("ballot", "sballot"):
         exposed = list(n_c) + list(g_c) + list(hs_c) + res_all + ([sum_c] if sum_c is not None else [])
     elif kind in ("tally", "wtally"):

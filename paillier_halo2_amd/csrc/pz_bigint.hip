@@ -1243,6 +1243,64 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_mix_rerand(co
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
+// ---- a mixer's re-randomisation with short randomness (pz_paillier_smix): c'_i = d_i hs^s_i mod n^2, d_i the network's
+// output at position i, hs = h^n mod n^2 the key's public element.  k_sballot_enc without its g-chain, or k_mix_rerand with a
+// secret-exponent chain: one team per output runs hs^s_i over exactly s_bits bits (pow_mod_uniform: (acc, sq) then (sq, sq) for EVERY
+// bit, the trailing square kept) and the product with d_i, all `count` outputs in one launch, no team waits on another.  The Barrett
+// constants come from k_tally_setup, once.  s_i and d_i are SECRET (d_i's position in the input list is the permutation): bit t of s_i
+// is read from word t / 64 of the entry's s_words words, an address that follows the loop counter alone, and reaches the accumulator as
+// a lane-wise mask over both candidates (ld_select); d_i's address follows the team's index alone.  Every trip count is a launch
+// argument.  (What a mul_mod does with its VALUES is K3's as everywhere: the Barrett correction's trip count follows the operands.)
+// An hs >= n^2 (public, the same for every team) is ST_RANGE and nothing is written; a d_i >= n^2 (an input >= n^2: every input
+// reaches one output) is ST_RANGE.
+// recs (may be null: the values only): output i at records i * per .. + per, per = 2 s_bits + 1: the chain's, then (d_i, hss_i, q,
+// c'_i).  per is held against the loop's own count before any store; a disagreement is ST_INTERNAL, never a write past the output's
+// own records.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_smix_rerand(const u64* __restrict__ mod, const u64* __restrict__ hs,
+                                                                                  const u64* __restrict__ routed, const u64* __restrict__ ss,
+                                                                                  unsigned s_bits, unsigned s_words, unsigned per, unsigned count,
+                                                                                  u64* __restrict__ recs, u64* __restrict__ c_out, unsigned Ln,
+                                                                                  u32* __restrict__ status) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (*block_ok<E>(mod) == 0) return;   // zero modulus (the same word for every workgroup)
+    if (blockIdx.x >= count) return;
+    const unsigned wave = threadIdx.x >> 6, L = 2 * Ln;
+    TeamCtx<E> T;
+    team_init(T, s_team);
+    BarrettCtx<E> B;
+    barrett_from_block(B, mod, L, s_scratch[wave]);
+    const size_t entry = blockIdx.x;
+    unsigned st = ST_OK;
+    const unsigned chain = 2 * s_bits;   // the chain's records; the final product is record `chain`
+    if (chain + 1 != per) st |= ST_INTERNAL;
+    // the four waves of the team hold the same values: one of them writes, and only where every record index of the output is below per
+    const bool writer = wave == 0 && recs != nullptr && chain + 1 == per;
+    u64* const base = writer ? recs + entry * per * 4 * (size_t)L : nullptr;
+    const LD<E> n2 = ld_load<E>(block_modulus<E>(mod), C);
+    LD<E> sq = ld_load<E>(hs, L);
+    {
+        LD<E> t;
+        if (!ld_sub(t, sq, n2)) {   // hs >= n^2 (public, the same for every team): nothing is written
+            if (lane_id() == 0) atomicOr(status, st | ST_RANGE);
+            return;
+        }
+    }
+    const LD<E> d = ld_load<E>(routed + entry * L, L);
+    {
+        LD<E> t;
+        if (!ld_sub(t, d, n2)) st |= ST_RANGE;   // an input >= n^2
+    }
+    LD<E> hss = ld_small<E>(1);
+    st |= pow_mod_uniform(B, T, hss, sq, ss + entry * s_words, s_bits, base);
+    LD<E> q, c;
+    st |= mul_mod(B, q, c, d, hss, TeamMul<E>{&T});
+    if (writer) rec_store(base + (size_t)chain * 4 * L, d, hss, q, c, L);
+    if (wave == 0) ld_store(c_out + entry * L, c, L);
+    if (st && lane_id() == 0) atomicOr(status, st);
+}
+
 // ---- a trustee's partial decryptions (pz_paillier_partial): h = v^theta and u_j = (c_j^2)^theta mod n^2 for K ciphertexts under ONE
 // secret share theta of e_bits bits.  K + 1 teams in one launch: team 0 runs pow_mod(v, theta), team j >= 1 first squares c_j itself
 // (record j - 1) and then runs pow_mod(s_j, theta) -- pow_mod_uniform: (acc, sq) then (sq, sq) for EVERY bit, the trailing square
@@ -2201,24 +2259,33 @@ struct MixArgs {
     uint8_t* d_bits;
     u32* d_status;
 };
+// the network's layers over d_cts (count x L words), layer l's outputs at d_routes + l * count * L; *routed: the last layer, or d_cts
+// itself where count = 1 has no switch
+static int mix_route_layers(pz_ctx* ctx, unsigned C, const u64* d_cts, u64* d_routes, const uint8_t* d_bits, unsigned layers, size_t count,
+                            unsigned L, const u64** routed) {
+    const unsigned half = (unsigned)(count / 2), d = (layers + 1) / 2;
+    *routed = d_cts;
+    for (unsigned l = 0; l < layers; ++l) {
+        const unsigned beta = l < d ? l : layers - 1 - l;
+        u64* out = d_routes + l * count * L;
+        K3_LAUNCH(ctx, k_mix_route, C, dim3(half), dim3(64), 0, *routed, out, d_bits + (size_t)l * half, beta, half, L);
+        *routed = out;
+    }
+    return PZ_OK;
+}
 static int mix_run(pz_ctx* ctx, const MixArgs& a) {
-    const unsigned L = 2 * a.Ln, C = capacity(L), half = (unsigned)(a.count / 2), d = (a.layers + 1) / 2;
+    const unsigned L = 2 * a.Ln, C = capacity(L), half = (unsigned)(a.count / 2);
     const size_t nb = (size_t)a.Ln * 8, lb = (size_t)L * 8, layer_words = a.count * L;
     HIPCHK(ctx, hipMemcpyAsync(a.d_n, a.n, nb, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(a.d_cts, a.cts, a.count * lb, hipMemcpyHostToDevice, ctx->stream));
     if (a.layers) HIPCHK(ctx, hipMemcpyAsync(a.d_bits, a.bits, (size_t)a.layers * half, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(a.d_rs, a.rs, a.count * nb, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(a.d_status, 0, 4, ctx->stream));
-    const u64* routed = a.d_cts;   // count = 1: no switch, the output is the input
+    const u64* routed;
     {
         pz_timer tm(ctx, PZ_T_TRACE);
         PZCHK(launch_barrett_setup(ctx, C, a.d_n, a.Ln, 1, a.d_mod, a.d_status));
-        for (unsigned l = 0; l < a.layers; ++l) {
-            const unsigned beta = l < d ? l : a.layers - 1 - l;
-            u64* out = a.d_routes + l * layer_words;
-            K3_LAUNCH(ctx, k_mix_route, C, dim3(half), dim3(64), 0, routed, out, a.d_bits + (size_t)l * half, beta, half, L);
-            routed = out;
-        }
+        PZCHK(mix_route_layers(ctx, C, a.d_cts, a.d_routes, a.d_bits, a.layers, a.count, L, &routed));
         K3_LAUNCH(ctx, k_mix_rerand, C, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, a.d_mod, a.d_n, routed, a.d_rs, a.n_bits, a.per,
                   (unsigned)a.count, a.d_steps, a.d_c, a.Ln, a.d_status);
     }
@@ -2294,6 +2361,121 @@ extern "C" int pz_paillier_mix(pz_ctx* ctx, uint32_t limbs_n, size_t count, cons
 extern "C" int pz_paillier_mix_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, const uint64_t* n, const uint64_t* cts, const uint8_t* bits,
                                    const uint64_t* rs, uint64_t* d_routes_out, uint64_t* d_steps_out, size_t steps_cap, uint64_t* mixed_out) {
     return mix_impl(ctx, limbs_n, count, n, cts, bits, rs, d_routes_out, d_steps_out, 1, steps_cap, mixed_out);
+}
+
+// The short-randomness mix: c'_i = c_perm(i) hs^s_i mod n^2 for `count` = 2^d ciphertexts under one key (n, hs).  The
+// network is the mix's (mix_route_layers: the same launches, the same route words); k_smix_rerand then runs the `count` hs-chains over
+// exactly s_bits bits and the final products in one launch.  Records output-major, 2 s_bits + 1 per output.  The switch bits, the s_i
+// and the route layers are secrets: the staged bits and s_i, and in the host form the staged routes and records, are overwritten
+// before the call returns, on every path past the staging.  The status is read before anything is copied out.
+struct SmixArgs {
+    uint32_t Ln, s_bits, s_words, per, layers;
+    size_t count;
+    const uint64_t *n, *hs, *cts, *ss;
+    const uint8_t* bits;
+    uint64_t *routes_out, *steps_out, *mixed_out;
+    int on_device;
+    u64 *d_n, *d_hs, *d_cts, *d_ss, *d_routes, *d_c, *d_mod, *d_steps;
+    uint8_t* d_bits;
+    u32* d_status;
+};
+static int smix_run(pz_ctx* ctx, const SmixArgs& a) {
+    const unsigned L = 2 * a.Ln, C = capacity(L), half = (unsigned)(a.count / 2);
+    const size_t nb = (size_t)a.Ln * 8, lb = (size_t)L * 8, layer_words = a.count * L;
+    HIPCHK(ctx, hipMemcpyAsync(a.d_n, a.n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_hs, a.hs, lb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_cts, a.cts, a.count * lb, hipMemcpyHostToDevice, ctx->stream));
+    if (a.layers) HIPCHK(ctx, hipMemcpyAsync(a.d_bits, a.bits, (size_t)a.layers * half, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_ss, a.ss, a.count * a.s_words * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(a.d_status, 0, 4, ctx->stream));
+    const u64* routed;
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        PZCHK(launch_barrett_setup(ctx, C, a.d_n, a.Ln, 1, a.d_mod, a.d_status));
+        PZCHK(mix_route_layers(ctx, C, a.d_cts, a.d_routes, a.d_bits, a.layers, a.count, L, &routed));
+        K3_LAUNCH(ctx, k_smix_rerand, C, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, a.d_mod, a.d_hs, routed, a.d_ss, a.s_bits, a.s_words,
+                  a.per, (unsigned)a.count, a.d_steps, a.d_c, a.Ln, a.d_status);
+    }
+    // the status first: nothing reaches the caller's buffers from a refused call
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&st, a.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    PZCHK(status_to_rc(ctx, st));
+    HIPCHK(ctx, hipMemcpyAsync(a.mixed_out, a.d_c, a.count * lb, hipMemcpyDeviceToHost, ctx->stream));
+    if (!a.on_device) {
+        if (a.routes_out && a.layers)
+            HIPCHK(ctx, hipMemcpyAsync(a.routes_out, a.d_routes, a.layers * layer_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (a.steps_out) HIPCHK(ctx, hipMemcpyAsync(a.steps_out, a.d_steps, a.count * a.per * 4 * lb, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PZ_OK;
+}
+static int smix_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t s_bits, const uint64_t* n, const uint64_t* hs, const uint64_t* cts,
+                     const uint8_t* bits, const uint64_t* ss, uint64_t* routes_out, uint64_t* steps_out, int on_device, size_t steps_cap,
+                     uint64_t* mixed_out) {
+    if (!ctx || !n || !hs || !cts || !ss || !mixed_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_MIX_MAX || (count & (count - 1)) != 0 || (!bits && count > 1)) return PZ_ERR_INVALID;
+    if (s_bits < 1 || s_bits > 128 * (uint64_t)Ln) return PZ_ERR_INVALID;
+    if (2 * (uint64_t)Ln > 128) return PZ_ERR_UNSUPPORTED;
+    const unsigned L = 2 * Ln;
+    const uint32_t per = 2 * s_bits + 1, s_words = (s_bits + 63) / 64;
+    if (steps_out && steps_cap < count * per) return PZ_ERR_CAPACITY;
+    uint32_t layers = 0;
+    for (size_t c = count; c > 1; c >>= 1) layers += 2;
+    if (layers) --layers;
+    const size_t n_switch = (size_t)layers * (count / 2);
+    {   // before any launch: a switch bit is 0 or 1 (every byte is looked at, whatever the others hold), and the chain reads s_bits bits
+        unsigned any = 0;
+        for (size_t i = 0; i < n_switch; ++i) any |= bits[i];
+        if (any > 1) return PZ_ERR_MESSAGE_RANGE;
+        uint64_t over = 0;
+        if (s_bits & 63)
+            for (size_t i = 0; i < count; ++i) over |= ss[i * s_words + s_words - 1] >> (s_bits & 63);
+        if (over) return PZ_ERR_MESSAGE_RANGE;
+    }
+    if (bitlen_limbs(n, Ln) == 0) return PZ_ERR_ZERO_MODULUS;
+    PZ_ENTER(ctx);
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, route_bytes = (size_t)layers * count * lb, ss_bytes = count * s_words * 8;
+    const bool ws_routes = layers && !(on_device && routes_out);
+    // n | hs | c_1 .. c_count | bits | s_1 .. s_count | the route layers (unless the caller's device buffer takes them) | c'_1 ..
+    // c'_count | Barrett constants | status
+    const size_t pub_bytes = (nb + lb + count * lb + 255) & ~(size_t)255, bit_bytes = (n_switch + 255) & ~(size_t)255;
+    const size_t sec_bytes = bit_bytes + ((ss_bytes + (ws_routes ? route_bytes : 0) + 255) & ~(size_t)255);
+    const size_t c_bytes = (count * lb + 255) & ~(size_t)255, mod_bytes = mod_block_words(capacity(L)) * 8;
+    void* d;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, pub_bytes + sec_bytes + c_bytes + mod_bytes + 256, &d));
+    char* p = (char*)d;
+    SmixArgs a{};
+    a.Ln = Ln; a.s_bits = s_bits; a.s_words = s_words; a.per = per; a.layers = layers; a.count = count;
+    a.n = n; a.hs = hs; a.cts = cts; a.ss = ss; a.bits = bits; a.routes_out = routes_out; a.steps_out = steps_out; a.mixed_out = mixed_out;
+    a.on_device = on_device;
+    a.d_n = (u64*)p;
+    a.d_hs = (u64*)(p + nb);
+    a.d_cts = (u64*)(p + nb + lb);
+    a.d_bits = (uint8_t*)(p + pub_bytes);
+    a.d_ss = (u64*)(p + pub_bytes + bit_bytes);
+    a.d_routes = ws_routes ? a.d_ss + count * s_words : routes_out;
+    a.d_c = (u64*)(p + pub_bytes + sec_bytes);
+    a.d_mod = (u64*)(p + pub_bytes + sec_bytes + c_bytes);
+    a.d_status = (u32*)(p + pub_bytes + sec_bytes + c_bytes + mod_bytes + 64);
+    a.d_steps = on_device ? steps_out : nullptr;
+    const size_t rec_bytes = steps_out && !on_device ? count * per * 4 * lb : 0;
+    if (rec_bytes) {
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_B, rec_bytes, &t));
+        a.d_steps = (u64*)t;
+    }
+    return wipe_secrets_and_sync(ctx, smix_run(ctx, a), a.d_bits, sec_bytes, a.d_steps, rec_bytes);
+}
+extern "C" int pz_paillier_smix(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t s_bits, const uint64_t* n, const uint64_t* hs,
+                                const uint64_t* cts, const uint8_t* bits, const uint64_t* ss, uint64_t* routes_out, uint64_t* steps_out,
+                                size_t steps_cap, uint64_t* mixed_out) {
+    return smix_impl(ctx, limbs_n, count, s_bits, n, hs, cts, bits, ss, routes_out, steps_out, 0, steps_cap, mixed_out);
+}
+extern "C" int pz_paillier_smix_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t s_bits, const uint64_t* n, const uint64_t* hs,
+                                    const uint64_t* cts, const uint8_t* bits, const uint64_t* ss, uint64_t* d_routes_out,
+                                    uint64_t* d_steps_out, size_t steps_cap, uint64_t* mixed_out) {
+    return smix_impl(ctx, limbs_n, count, s_bits, n, hs, cts, bits, ss, d_routes_out, d_steps_out, 1, steps_cap, mixed_out);
 }
 
 // A trustee's partial decryptions: h = v^theta, u_j = (c_j^2)^theta mod n^2 for `count` ciphertexts under one share

@@ -354,6 +354,28 @@ int sballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_b
     return PZ_OK;
 }
 
+// the short-randomness mix (kind 10, `count` = 2^d ciphertexts, exponents of s_limbs limbs): n | hs | c_1 | .. | c_K | c'_1 | .. | c'_K.
+// n's limb cells head the stream, hs and the c_j are the 1 + K full-width assign_integer blocks that follow; c'_i is the
+// assign_integer(2 limbs_n) in front of output i's assert_equal_fresh, the K pairs closing the stream.
+int smix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs, std::vector<uint64_t>& cells) {
+    if (limbs_n == 0) return PZ_ERR_INVALID;
+    size_t total = 0, a_in = 0, a_wide = 0, a_eq = 0;
+    PZCHK(pz_smix_cells(limbs_n, limb_bits, lookup_bits, count, s_limbs, &total, nullptr));
+    PZCHK(pz_op_cells(0, limbs_n, limb_bits, lookup_bits, &a_in, nullptr));
+    PZCHK(pz_op_cells(0, 2 * limbs_n, limb_bits, lookup_bits, &a_wide, nullptr));
+    PZCHK(pz_op_cells(5, 2 * limbs_n, limb_bits, lookup_bits, &a_eq, nullptr));
+    if (total < a_in + (count + 1) * a_wide + count * (a_wide + a_eq)) return PZ_ERR_INTERNAL;
+    const size_t res = total - count * (a_wide + a_eq);
+    const uint32_t L = 2 * limbs_n;
+    cells.clear();
+    for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(j);
+    for (size_t i = 0; i <= count; ++i)
+        for (uint32_t j = 0; j < L; ++j) cells.push_back(a_in + i * a_wide + j);
+    for (size_t i = 0; i < count; ++i)
+        for (uint32_t j = 0; j < L; ++j) cells.push_back(res + i * (a_wide + a_eq) + j);
+    return PZ_OK;
+}
+
 }   // namespace
 
 int pz_instance_eval_launch(pz_ctx* ctx, uint32_t k, const uint64_t omega[4], const uint64_t n_inv[4], const uint64_t* d_instances, size_t L,
@@ -394,12 +416,13 @@ static int statement_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint3
         if (kind == 8) return mix_public_cells(limbs_n, limb_bits, lookup_bits, count, n_steps_r, cells);
         if (kind == 9)   // (n_steps_r: the 2 s_limbs limb_bits records of one hs-chain)
             return sballot_public_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, (uint32_t)(n_steps_r / (2 * (size_t)limb_bits)), cells);
+        if (kind == 10) return smix_public_cells(limbs_n, limb_bits, lookup_bits, count, (uint32_t)(n_steps_r / (2 * (size_t)limb_bits)), cells);
         return public_cells(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, cells);
     } catch (const std::bad_alloc&) {
         return PZ_ERR_OOM;
     }
 }
-// the tail of the five pz_*_public_cells entry points: the count always, the cells where the caller gave room
+// the tail of the six pz_*_public_cells entry points: the count always, the cells where the caller gave room
 static int public_cells_out(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_g,
                             size_t n_steps_r, uint64_t* cells_out, size_t capacity, size_t* n_public) {
     if (!n_public) return PZ_ERR_INVALID;
@@ -415,7 +438,7 @@ static int public_cells_out(int kind, uint32_t limbs_n, uint32_t limb_bits, uint
 
 extern "C" int pz_circuit_public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g, size_t n_steps_r,
                                        uint64_t* cells_out, size_t capacity, size_t* n_public) {
-    if (kind > 5) return PZ_ERR_INVALID;   // (kinds 6 to 9 have entry points of their own)
+    if (kind > 5) return PZ_ERR_INVALID;   // (kinds 6 to 10 have entry points of their own)
     return public_cells_out(kind, limbs_n, limb_bits, lookup_bits, 0, 0, n_steps_g, n_steps_r, cells_out, capacity, n_public);
 }
 extern "C" int pz_ballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
@@ -435,6 +458,12 @@ extern "C" int pz_sballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uin
                                        uint32_t s_limbs, uint64_t* cells_out, size_t capacity, size_t* n_public) {
     if (limb_bits == 0) return PZ_ERR_INVALID;
     return public_cells_out(9, limbs_n, limb_bits, lookup_bits, count, m_bits, 0, 2 * (size_t)s_limbs * limb_bits, cells_out, capacity, n_public);
+}
+
+extern "C" int pz_smix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs,
+                                    uint64_t* cells_out, size_t capacity, size_t* n_public) {
+    if (limb_bits == 0) return PZ_ERR_INVALID;
+    return public_cells_out(10, limbs_n, limb_bits, lookup_bits, count, 0, 0, 2 * (size_t)s_limbs * limb_bits, cells_out, capacity, n_public);
 }
 
 extern "C" int pz_structure_expose(pz_structure* st) {

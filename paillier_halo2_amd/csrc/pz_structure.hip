@@ -444,6 +444,10 @@ struct Stream {
 // pow_mod(g_ext, m_i) over w_bits (= m_bits) in-circuit bits as kind 6, pow_mod(hs, s_i) as kind 7 walks a chain -- [1, 0], then per limb
 // of s_i num_to_bits of ITS limb cell and W uniform blocks, the first sq hs's limb cells -- and the final block; then per entry res_i and
 // assert_equal_fresh.  No exponent of the key shapes it: one structure serves every key of a size.
+// kind 10 (the short-randomness mix): n, hs and `count` = 2^d ciphertexts at full width, assign_integer(s_i) of
+// s_limbs limbs for every output, square + refresh, load_zero; kind 8's network walk; per output kind 9's hs-chain walk -- [1, 0], then
+// per limb of s_i num_to_bits of ITS limb cell and W uniform blocks, the first sq hs's limb cells -- and the block mul_mod(d_i, hss_i);
+// then per output res_i and assert_equal_fresh.  No exponent of the key shapes it.
 int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, unsigned w_bits,
                  unsigned s_limbs, Stream& S) {
     const unsigned L = 2 * Ln;
@@ -473,9 +477,10 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             }
         }
         for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, kind == 9 ? s_limbs : Ln, W, lb));   // r_i; kind 9: s_i
-    } else if (kind == 8) {
+    } else if (kind == 8 || kind == 10) {
+        if (kind == 10) x_c = assign(w, L, W, lb);   // hs: the key's second base, full width
         for (size_t i = 0; i < count; ++i) ct_c.push_back(assign(w, L, W, lb));
-        for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, Ln, W, lb));
+        for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, kind == 10 ? s_limbs : Ln, W, lb));   // r_i; kind 10: s_i
     } else if (kind == 7) {
         g_c = assign(w, L, W, lb);   // v: the key's base, full width
         x_c = assign(w, L, W, lb);   // theta: the share, 2 Ln limbs
@@ -669,7 +674,11 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
         }
         S.n_steps_g = 2 * (size_t)w_bits;
         S.n_steps_r = 2 * (size_t)s_limbs * W;
-    } else if (kind == 8) {
+    } else if (kind == 8 || kind == 10) {
+        if (kind == 10) {
+            S.tmpls.push_back(uniform_template(L, W, lb));
+            S.bind_template_constants(1);
+        }
         Walk wn(off);
         auto select = [&](i64 x, i64 y, i64 s) {   // FlexGate::select(x, y, s): [d | 1 | y | x | y | s | d | out], windows at 0 and 4
             const i64 c_d = wn.put();
@@ -703,10 +712,28 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             cur_c.swap(nxt_c);
         }
         off = S.flush(wn);
-        for (size_t i = 0; i < count; ++i) {
-            S.n_steps_r = (size_t)fixed_chain(ext_l(rs_c[i]), exp_r, rn);
-            roots.push_back(block_r(off));
-            off = S.blocks(off, 0, std::vector<i64>(cur_c[i]), std::vector<i64>(rn), {}, 1);
+        if (kind == 8) {
+            for (size_t i = 0; i < count; ++i) {
+                S.n_steps_r = (size_t)fixed_chain(ext_l(rs_c[i]), exp_r, rn);
+                roots.push_back(block_r(off));
+                off = S.blocks(off, 0, std::vector<i64>(cur_c[i]), std::vector<i64>(rn), {}, 1);
+            }
+        } else {
+            for (size_t i = 0; i < count; ++i) {
+                // pow_mod(hs, s_i): kind 9's walk over the s_limbs limbs of s_i -- every output's chain starts from the SAME hs cells
+                Walk wc(off);
+                const i64 one_s = wc.putc(c_small(1)), z2_s = wc.putc(c_small(0));
+                off = S.flush(wc);
+                std::vector<i64> acc_cells(L, z2_s), sq_cells = x_c;
+                acc_cells[0] = one_s;
+                for (unsigned li = 0; li < s_limbs; ++li) {
+                    Walk wl(off);
+                    off = bit_chain(off, wl, rs_c[i][li], W, acc_cells, sq_cells);
+                }
+                roots.push_back(block_r(off));
+                off = S.blocks(off, 0, std::vector<i64>(cur_c[i]), std::move(acc_cells), {}, 1);
+            }
+            S.n_steps_r = 2 * (size_t)s_limbs * W;
         }
     } else if (kind == 7) {
         S.tmpls.push_back(uniform_template(L, W, lb));
@@ -1103,7 +1130,7 @@ extern "C" int pz_structure_arrays(const pz_structure* st, const uint8_t** d_sel
 static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, const uint64_t* exp_g,
                           const uint64_t* exp_r, size_t count, uint32_t w_bits, uint32_t s_limbs, size_t minimum_rows,
                           uint32_t blinding_factors, pz_structure** out) {
-    if (!ctx || !out || kind < 0 || kind > 9 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+    if (!ctx || !out || kind < 0 || kind > 10 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
     const int handle_kind = kind;   // kind 5 ("decrypt") is kind 2's circuit under another statement: pz_structure_expose alone tells them apart
     if (kind == 5) kind = 2;
     if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
@@ -1113,6 +1140,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     if (kind == 7 && (count < 1 || count > 1024)) return PZ_ERR_INVALID;
     if (kind == 8 && (count < 1 || count > 1024 || (count & (count - 1)) != 0)) return PZ_ERR_INVALID;
     if (kind == 9 && (count < 1 || count > 1024 || w_bits < 1 || w_bits > 64 || s_limbs < 1 || s_limbs > 2 * limbs_n)) return PZ_ERR_INVALID;
+    if (kind == 10 && (count < 1 || count > 1024 || (count & (count - 1)) != 0 || s_limbs < 1 || s_limbs > 2 * limbs_n)) return PZ_ERR_INVALID;
     if (((kind == 0 || kind == 2 || kind == 6 || kind == 8) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
     const i64 n = (i64)1 << k;
     const i64 unusable = (i64)blinding_factors + 3;
@@ -1307,4 +1335,10 @@ extern "C" int pz_circuit_structure_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, u
                                                 pz_structure** out) {
     return structure_impl(ctx, 9, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, m_bits, s_limbs, minimum_rows, blinding_factors,
                           out);
+}
+// the short-randomness mix (kind 10): count = 2^d ciphertexts (1 .. 1024) with exponents of s_limbs limbs (1 .. 2 limbs_n); the shape is
+// (count, s_limbs) and the key SIZE alone -- no exponent of the key enters it
+extern "C" int pz_circuit_structure_smix_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                             uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
+    return structure_impl(ctx, 10, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, s_limbs, minimum_rows, blinding_factors, out);
 }

@@ -1741,6 +1741,29 @@ __global__ __launch_bounds__(256) void k_mix_repack(const u64* __restrict__ src,
     const unsigned k = (unsigned)(g % L64);
     dst[g] = k < rw ? src[f * rw + k] : 0;
 }
+// *recs (`fields` fields of rw words, as K3 leaves them) as k_witness_expand reads them: K3's fields are whole words of n twice over,
+// K4's are the words 2 Ln limbs take; where the two differ the records are repacked into the workspace first
+static int repack_records(pz_ctx* ctx, const CircP& C, unsigned rw, size_t fields, const u64** recs) {
+    if (rw == C.e.L64) return PZ_OK;
+    void* t;
+    PZCHK(pz_ws_get(ctx, WS_BIG_C, fields * C.e.L64 * 8, &t));
+    hipLaunchKernelGGL(k_mix_repack, dim3((unsigned)((fields * C.e.L64 + 255) / 256)), dim3(256), 0, ctx->stream, *recs, rw, (u64*)t, C.e.L64, fields);
+    *recs = (const u64*)t;
+    return PZ_OK;
+}
+// the network of kinds 8 and 10 over K = 2^d positions, layer by layer: a layer reads the one below (layer 0: the ciphertexts inside
+// the staged inputs, fields of L64 words) and its own, both of the routes at rw words a field; its switches' cells start at a_net
+static void launch_network(const ExpandArgs& A, const CircP& C, const u64* in_cts, const uint64_t* d_routes, const unsigned char* d_bits, size_t K,
+                           unsigned d, size_t layers, unsigned rw, size_t a_net, size_t sw_cells) {
+    const size_t half = K / 2, layer_words = K * rw;
+    for (size_t ly = 0; ly < layers; ++ly) {
+        const unsigned beta = (unsigned)(ly < d ? ly : layers - 1 - ly);
+        const u64* below = ly ? (const u64*)d_routes + (ly - 1) * layer_words : in_cts;
+        hipLaunchKernelGGL(k_mix_switch, dim3((unsigned)((half * C.e.L + 255) / 256)), dim3(256), 0, A.ctx->stream, C.e, beta, (unsigned)half, below,
+                           ly ? rw : C.e.L64, (const u64*)d_routes + ly * layer_words, rw, d_bits + ly * half, a_net + ly * half * sw_cells, sw_cells,
+                           (Fr*)A.d_advice);
+    }
+}
 extern "C" int pz_mix_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, size_t n_steps_r, size_t* advice_cells,
                             size_t* lookup_cells) {
     CircP C;
@@ -1769,14 +1792,7 @@ static int mix_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb_
     PZCHK(expand_stage(A, in_words, bits, n_switch, &in));   // the switch bits behind the inputs
     const unsigned char* d_bits = (const unsigned char*)(in + in_words);
     const u64* recs = A.d_steps;
-    const size_t fields = count * B.per * 4;
-    if (B.rw != C.e.L64) {   // K3's fields are whole words of n twice over; K4's are the words 2 Ln limbs take
-        void* t;
-        PZCHK(pz_ws_get(ctx, WS_BIG_C, fields * C.e.L64 * 8, &t));
-        hipLaunchKernelGGL(k_mix_repack, dim3((unsigned)((fields * C.e.L64 + 255) / 256)), dim3(256), 0, ctx->stream, recs, B.rw, (u64*)t, C.e.L64,
-                           fields);
-        recs = (const u64*)t;
-    }
+    PZCHK(repack_records(ctx, C, B.rw, count * B.per * 4, &recs));
     pz_timer tm(ctx, PZ_T_EXPAND);
     Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
     // n, square, refresh, load_zero
@@ -1784,15 +1800,7 @@ static int mix_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb_
     // assign_integer(c_j): 2 Ln limbs from L64 words each; assign_integer(r_i): Ln limbs from words_n words each
     launch_assign(A, C, in, B.in_cts, C.nf, C.e.L64, count, B.a_cts, B.l_cts);
     launch_assign(A, C, in, B.in_rs, C.Ln, C.words_n, count, B.a_rs, B.l_rs);
-    // the network, layer by layer: a layer reads the one below (layer 0: the ciphertexts) and its own
-    const size_t layer_words = count * B.rw;
-    for (size_t ly = 0; ly < B.layers; ++ly) {
-        const unsigned beta = (unsigned)(ly < B.d ? ly : B.layers - 1 - ly);
-        const u64* below = ly ? (const u64*)d_routes + (ly - 1) * layer_words : in + B.in_cts;
-        hipLaunchKernelGGL(k_mix_switch, dim3((unsigned)((B.half * C.e.L + 255) / 256)), dim3(256), 0, ctx->stream, C.e, beta, (unsigned)B.half,
-                           below, ly ? B.rw : C.e.L64, (const u64*)d_routes + ly * layer_words, B.rw, d_bits + ly * B.half,
-                           B.a_net + ly * B.half * B.sw_cells, B.sw_cells, adv);
-    }
+    launch_network(A, C, in + B.in_cts, d_routes, d_bits, count, B.d, B.layers, B.rw, B.a_net, B.sw_cells);
     // per output: the r-chain's records and the final one
     launch_runs(A, C, B.a_out + 2, B.l_out, recs, B.per, count, B.out_stride, B.per);
     launch_results(A, C, B.res, count, in, recs);
@@ -1893,14 +1901,7 @@ static int sballot_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t l
     const u64* in;
     PZCHK(expand_stage(A, B.res.in_res + count * C.e.L64, nullptr, 0, &in));
     const u64* recs = A.d_steps;
-    const size_t fields = count * B.per * 4;
-    if (B.rw != C.e.L64) {   // K3's fields are whole words of n twice over; K4's are the words 2 Ln limbs take
-        void* t;
-        PZCHK(pz_ws_get(ctx, WS_BIG_C, fields * C.e.L64 * 8, &t));
-        hipLaunchKernelGGL(k_mix_repack, dim3((unsigned)((fields * C.e.L64 + 255) / 256)), dim3(256), 0, ctx->stream, recs, B.rw, (u64*)t, C.e.L64,
-                           fields);
-        recs = (const u64*)t;
-    }
+    PZCHK(repack_records(ctx, C, B.rw, count * B.per * 4, &recs));
     pz_timer tm(ctx, PZ_T_EXPAND);
     Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
     const size_t rec = 4 * (size_t)C.e.L64;   // words per step record
@@ -1948,6 +1949,129 @@ extern "C" int pz_sballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_
                                           size_t max_rows, size_t lookup_rows, size_t col_stride) {
     return sballot_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, true, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows},
                                limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs);
+}
+
+// ---- the short-randomness mix (circuit kind 10): K = 2^d ciphertexts through the Benes network, then c'_i =
+// d_i hs^s_i mod n^2.  Stream: assign n; assign hs, c_1 .. c_K at full width; assign s_1 .. s_K (s_limbs limbs each); square + refresh,
+// load_zero; the network as kind 8; per output [1, 0 | pow_mod(hs, s_i) as kind 9 emits its hs-chain: per limb of s_i num_to_bits and W
+// bit blocks | mul_mod(d_i, hss_i)]; per output a result block (res_i against the remainder of the output's last record).  inputs: n |
+// hs | c_1 .. c_K | s_1 .. s_K (ceil(s_limbs W / 64) words each) | res_1 .. res_K.  Routes, bits and records are
+// pz_paillier_smix_dev's, as it leaves them: fields of 2 ceil(Ln W / 64) words.  No arithmetic of its own: kind 8's switch kernel and
+// the bits, select, expand, assign and result kernels above.
+struct SmixP {
+    size_t K, half, layers, per, s_limbs, s_words, a_hs, l_hs, a_cts, l_cts, a_ss, l_ss, a_net, sw_cells, a_out, l_out, out_stride, limb_stride;
+    size_t in_hs, in_cts, in_ss;    // word offsets inside `inputs`
+    unsigned d, rw;                 // log2 K; words per field of a route or record as K3 writes them
+    ResP res;
+};
+static int make_smix_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, uint32_t s_limbs, CircP& C, SmixP& B,
+                            size_t* adv_total, size_t* lk_total) {
+    if (count < 1 || count > MIX_MAX || (count & (count - 1)) != 0 || s_limbs < 1 || s_limbs > 2 * (uint64_t)limbs_n) return PZ_ERR_INVALID;
+    PZCHK(circ_base(limbs_n, limb_bits, lb, 10, C));
+    memset(&B, 0, sizeof B);
+    const size_t W = limb_bits, s_bits = (size_t)s_limbs * W;
+    B.K = count; B.half = count / 2; B.per = 2 * s_bits + 1; B.rw = 2 * C.words_n;
+    B.s_limbs = s_limbs;
+    B.s_words = (s_bits + 63) / 64;
+    while (((size_t)1 << B.d) < count) ++B.d;
+    B.layers = count > 1 ? 2 * (size_t)B.d - 1 : 0;
+    B.in_hs = C.words_n;
+    B.in_cts = B.in_hs + C.e.L64;
+    B.in_ss = B.in_cts + count * C.e.L64;
+    size_t a = 0, l = 0;
+    assign_inputs(C, 1, a, l);
+    B.a_hs = a; B.l_hs = l; a += 2 * asg_adv(C); l += 2 * asg_lk(C);
+    B.a_cts = a; B.l_cts = l; a += count * 2 * asg_adv(C); l += count * 2 * asg_lk(C);
+    B.a_ss = a; B.l_ss = l;
+    a += count * s_limbs * (1 + (size_t)C.rc_adv); l += count * s_limbs * (size_t)C.rc_lk;
+    square_refresh_cells(C, a, l);
+    load_zero_cell(C, a);
+    B.sw_cells = 4 + 16 * (size_t)C.e.L;
+    B.a_net = a; a += B.layers * B.half * B.sw_cells;
+    B.limb_stride = nbits_cells(W) + W * bit_stride(C);
+    B.out_stride = 2 + s_limbs * B.limb_stride + C.e.cells;
+    B.a_out = a; B.l_out = l;
+    a += count * B.out_stride; l += count * B.per * C.e.lookups;
+    B.res.a_head = B.a_out; B.res.head_stride = B.out_stride;
+    B.res.rec0 = B.per - 1; B.res.rec_stride = B.per; B.res.field = 3;
+    result_blocks(C, B.res, count, B.in_ss + count * B.s_words, a, l);
+    *adv_total = a;
+    *lk_total = l;
+    return PZ_OK;
+}
+extern "C" int pz_smix_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs, size_t* advice_cells,
+                             size_t* lookup_cells) {
+    CircP C;
+    SmixP B;
+    size_t a, l;
+    const int rc = make_smix_params(limbs_n, limb_bits, lookup_bits, count, s_limbs, C, B, &a, &l);
+    return put_cells(rc, a, l, advice_cells, lookup_cells);
+}
+
+static int smix_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs,
+                            const uint8_t* bits, const uint64_t* d_routes) {
+    PZCHK(expand_check(A));
+    CircP C;
+    SmixP B;
+    size_t a, l;
+    PZCHK(make_smix_params(limbs_n, limb_bits, lookup_bits, count, s_limbs, C, B, &a, &l));
+    if (B.layers && (!bits || !d_routes)) return PZ_ERR_INVALID;
+    PZCHK(expand_layout(A, C));
+    const size_t n_switch = B.layers * B.half, W = limb_bits, s_bits = s_limbs * W;
+    for (size_t i = 0; i < n_switch; ++i)
+        if (bits[i] > 1) return PZ_ERR_MESSAGE_RANGE;   // assert_bit of such a byte cannot hold
+    if (s_bits & 63)
+        for (size_t i = 0; i < count; ++i)   // num_to_bits of such an exponent's top limb cannot hold
+            if (A.inputs[B.in_ss + (i + 1) * B.s_words - 1] >> (s_bits & 63)) return PZ_ERR_MESSAGE_RANGE;
+    pz_ctx* ctx = A.ctx;
+    PZ_ENTER(ctx);
+    const size_t in_words = B.res.in_res + count * C.e.L64;
+    const u64* in;
+    PZCHK(expand_stage(A, in_words, bits, n_switch, &in));   // the switch bits behind the inputs
+    const unsigned char* d_bits = (const unsigned char*)(in + in_words);
+    const u64* recs = A.d_steps;
+    PZCHK(repack_records(ctx, C, B.rw, count * B.per * 4, &recs));
+    pz_timer tm(ctx, PZ_T_EXPAND);
+    Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
+    const size_t rec = 4 * (size_t)C.e.L64;   // words per step record
+    // n, square, refresh, load_zero
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, (const u64*)nullptr, adv, lk);
+    // assign_integer(hs), assign_integer(c_j): 2 Ln limbs from L64 words each; assign_integer(s_i): s_limbs limbs from s_words words each
+    launch_assign(A, C, in, B.in_hs, C.nf, C.e.L64, 1 + count, B.a_hs, B.l_hs);
+    launch_assign(A, C, in, B.in_ss, (unsigned)s_limbs, (unsigned)B.s_words, count, B.a_ss, B.l_ss);
+    launch_network(A, C, in + B.in_cts, d_routes, d_bits, count, B.d, B.layers, B.rw, B.a_net, B.sw_cells);
+    // the hs-chains (kind 9's walk): per output s_i's num_to_bits limb by limb and the selects; then limb by limb the record pairs of ALL
+    // outputs in one launch -- limb li's records start 2 li W into an output's, and so do their lookups
+    for (size_t i = 0; i < count; ++i) {
+        const size_t bits0 = B.a_out + i * B.out_stride + 2;
+        const u64 *d_s = in + B.in_ss + i * B.s_words, *d_chain = recs + i * B.per * rec;
+        hipLaunchKernelGGL(k_circuit_bits, dim3((unsigned)s_limbs), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s, bits0,
+                           B.limb_stride, adv);
+        hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)s_bits), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s,
+                           d_chain, bits0, B.limb_stride, bit_stride(C), nbits_cells(W), adv);
+    }
+    for (size_t li = 0; li < s_limbs; ++li) {
+        const size_t r0 = li * 2 * W;
+        launch_chains(A, C, B.a_out + 2 + li * B.limb_stride, B.l_out + r0 * C.e.lookups, recs + r0 * rec, W, count, B.out_stride, B.per);
+    }
+    // the final block of every output, and the result blocks with the [1, 0] of the chains
+    launch_runs(A, C, B.a_out + B.out_stride - C.e.cells, B.l_out, recs, 1, count, B.out_stride, B.per, B.per - 1);
+    launch_results(A, C, B.res, count, in, recs);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+extern "C" int pz_smix_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs,
+                                  const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
+                                  const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride) {
+    return smix_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, false, rows, col_stride, nullptr, 0, 0}, limbs_n, limb_bits,
+                            lookup_bits, count, s_limbs, bits, d_routes);
+}
+extern "C" int pz_smix_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs,
+                                       const uint64_t* inputs, const uint8_t* bits, const uint64_t* d_routes, const uint64_t* d_steps,
+                                       const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts,
+                                       size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride) {
+    return smix_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, true, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows},
+                            limbs_n, limb_bits, lookup_bits, count, s_limbs, bits, d_routes);
 }
 #undef LIMB
 

@@ -647,6 +647,41 @@ class Engine:
                                              VP(d_routes), VP(d_steps), steps_cap, _ptr(mixed)), "pz_paillier_mix_dev")
         return mixed
 
+    # the short-randomness mix: c'_i = c_perm(i) hs^s_i mod n^2, hs = h^n mod n^2 from keys.djn_generator
+    @staticmethod
+    def _smix_args(limbs_n: int, n, hs, cts, bits, ss, s_bits: int):
+        n, hs = _np(n).reshape(limbs_n), _np(hs).reshape(2 * limbs_n)
+        cts, ss = _np(cts).reshape(-1, 2 * limbs_n), _np(ss).reshape(-1, max(-(-s_bits // 64), 1))
+        if cts.shape[0] != ss.shape[0]:
+            raise ValueError("one s per ciphertext")
+        return n, hs, cts, np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1), ss
+
+    def paillier_smix(self, limbs_n: int, n, hs, cts, bits, ss, s_bits: int, want_steps: bool = True, want_routes: bool = True):
+        """c'_i = c_perm(i) hs^s_i mod n^2 for K exponents below 2^s_bits (pz.h pz_paillier_smix): hs (2*limbs_n,) words, cts (K,
+        2*limbs_n), bits the network's switch bytes (mix_route), ss (K, ceil(s_bits / 64)) words.  s_bits is the caller's: hiding rests on
+        the short-exponent assumption in <hs>.  Returns (mixed (K, 2*limbs_n), routes (2d - 1, K, 2*limbs_n) or None, steps (K, 2 s_bits
+        + 1, 4, 2*limbs_n) or None)."""
+        L = 2 * limbs_n
+        n, hs, cts, bits, ss = self._smix_args(limbs_n, n, hs, cts, bits, ss, s_bits)
+        count = cts.shape[0]
+        per = 2 * s_bits + 1
+        routes = np.zeros((max(self.mix_layers(count), 1), max(count, 1), L), dtype=np.uint64) if want_routes else None
+        steps = np.zeros((max(count, 1), per, 4, L), dtype=np.uint64) if want_steps else None
+        mixed = np.zeros((max(count, 1), L), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_smix(self.ctx, limbs_n, count, s_bits, _ptr(n), _ptr(hs), _ptr(cts), VP(bits.ctypes.data), _ptr(ss),
+                                          _ptr(routes) if want_routes else VP(), _ptr(steps) if want_steps else VP(), count * per,
+                                          _ptr(mixed)), "pz_paillier_smix")
+        return mixed, (routes[: self.mix_layers(count)] if want_routes else None), steps
+
+    def paillier_smix_dev(self, limbs_n: int, n, hs, cts, bits, ss, s_bits: int, d_routes: int, d_steps: int, steps_cap: int):
+        """the same with the route layers and the records left on the device (d_routes: (2d - 1) x K x 2*limbs_n u64, d_steps: steps_cap
+        x 4 x 2*limbs_n u64; either may be 0).  Returns mixed."""
+        n, hs, cts, bits, ss = self._smix_args(limbs_n, n, hs, cts, bits, ss, s_bits)
+        mixed = np.zeros((max(cts.shape[0], 1), 2 * limbs_n), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_smix_dev(self.ctx, limbs_n, cts.shape[0], s_bits, _ptr(n), _ptr(hs), _ptr(cts), VP(bits.ctypes.data),
+                                              _ptr(ss), VP(d_routes), VP(d_steps), steps_cap, _ptr(mixed)), "pz_paillier_smix_dev")
+        return mixed
+
     def paillier_sk(self, limbs_n: int, n, g, lam, d) -> "PaillierSecretKey":
         """a secret key handle (pz.h pz_paillier_sk_create): n, g, lambda and d = n^-1 mod lambda as integers or limbs_n-word arrays
         (keys.secret_from_primes gives all four).  The key is validated on the device; free() wipes the handle's device memory."""
@@ -1036,6 +1071,42 @@ class Engine:
         self._chk(self.L.pz_sballot_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs, _ptr(inp), VP(d_steps),
                                                     VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts), n_adv_cols, max_rows,
                                                     lookup_rows, col_stride), "pz_sballot_expand_cols_dev")
+
+    # the short-randomness mix (circuit kind 10, pz.h pz_smix_*): its shape is (count = 2^d, s_limbs) and the key size alone
+    def smix_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, s_limbs: int):
+        a = C.c_size_t()
+        l = C.c_size_t()
+        self._chk(self.L.pz_smix_cells(limbs_n, limb_bits, lookup_bits, count, s_limbs, C.byref(a), C.byref(l)), "pz_smix_cells")
+        return a.value, l.value
+
+    def smix_public_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, s_limbs: int):
+        """stream indices of the exposed cells in statement order: n | hs | c_1 .. c_K | c'_1 .. c'_K"""
+        out = np.zeros(limbs_n + (2 * max(count, 1) + 1) * 2 * limbs_n, dtype=np.uint64)
+        npub = C.c_size_t()
+        self._chk(self.L.pz_smix_public_cells(limbs_n, limb_bits, lookup_bits, count, s_limbs, _ptr(out), out.shape[0], C.byref(npub)),
+                  "pz_smix_public_cells")
+        return out[: npub.value]
+
+    def smix_expand_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, s_limbs: int, inputs, bits, d_routes: int,
+                        d_steps: int, d_modulus: int, d_advice: int, d_lookup: int = 0, rows: int = 0, col_stride: int = 0):
+        """inputs: host uint64 array n | hs | c_1 .. c_K | s_1 .. s_K | res_1 .. res_K; bits: the switch bytes paillier_smix_dev took;
+        d_routes, d_steps: the route layers and the K (2 s_limbs limb_bits + 1) records it left; writes the circuit's cell stream, dense
+        or cut into columns"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+        self._chk(self.L.pz_smix_expand_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, s_limbs, _ptr(inp), VP(bits.ctypes.data),
+                                            VP(d_routes), VP(d_steps), VP(d_modulus), VP(d_advice), VP(d_lookup), rows, col_stride),
+                  "pz_smix_expand_dev")
+
+    def smix_expand_cols_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, s_limbs: int, inputs, bits, d_routes: int,
+                             d_steps: int, d_modulus: int, d_advice: int, d_lookup: int, d_col_starts: int, n_adv_cols: int, max_rows: int,
+                             lookup_rows: int, col_stride: int):
+        """the same with the advice cells in break-point columns (circuit_expand_cols_dev's conventions)"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+        self._chk(self.L.pz_smix_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, s_limbs, _ptr(inp), VP(bits.ctypes.data),
+                                                 VP(d_routes), VP(d_steps), VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts),
+                                                 n_adv_cols, max_rows, lookup_rows, col_stride), "pz_smix_expand_cols_dev")
 
     # ------------------------------------------------------------------ "next" rows: SRS setup, evaluation at a point
     def srs_setup_g1_dev(self, k: int, s, omega, d_g: int = 0, d_g_lagrange: int = 0):

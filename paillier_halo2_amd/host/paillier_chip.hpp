@@ -19,6 +19,7 @@
 //   (K ciphertexts of small values with a public sum)          PaillierChip::ballot, pz::paillier_ballot_test (15.10)
 //   (the same with short randomness, c = g^m hs^s)             PaillierChip::sballot, pz::paillier_sballot_test, pz::djn_generator (15.18)
 //   (K ciphertexts shuffled and re-randomised: a mixer's step) pz::benes_route (benes.hpp), PaillierChip::mix, pz::paillier_mix_test (15.17)
+//   (the same with short randomness, c' = c_perm hs^s)         PaillierChip::smix, pz::paillier_smix_test (15.20)
 //   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
 //   (T trustees holding additive shares of the exponent)      pz::ThresholdKey, pz::deal_shares, PaillierChip::partial_decrypt / combine (15.11)
 //   (any t of T trustees holding Shamir shares of it)          pz::ShamirKey, pz::deal_shamir, PaillierChip::combine_t / mod_inverse (15.12)
@@ -719,6 +720,101 @@ class PaillierChip {  // paillier.rs:11-15
         return R::Ok(out);
     }
 
+    // The short-randomness mix: c'_i = c_perm(i) hs^s_i mod n^2 for K = 2^d ciphertexts under one key (n, hs)
+    // -- mix with every r_i^n chain replaced by sballot's hs-chain.  n^2 hoisted once, load_zero; the Benes network switch by switch;
+    // per output [1, 0], per limb of s_i num_to_bits and that limb's blocks, and mul_mod(d_i, hss_i).  One pz_paillier_smix call
+    // computes every route layer and record; the tape takes the records in the circuit's order, which is the call's.  hs, the
+    // ciphertexts and the s_i (all of ONE limb count, 1 .. 2 * n's) are assigned by the caller (paillier_smix_test), in front of this.
+    // wit (may be null) keeps the bits and the route layers for synthesize_smix_circuit: the mixer's secrets, which the caller wipes.
+    Result<std::vector<AssignedBigUint<Fresh>>> smix(Context& ctx, const AssignedBigUint<Fresh>& n, const AssignedBigUint<Fresh>& hs,
+                                                     const std::vector<AssignedBigUint<Fresh>>& cts, const std::vector<uint32_t>& perm,
+                                                     const std::vector<AssignedBigUint<Fresh>>& ss, MixWitness* wit) const {
+        using R = Result<std::vector<AssignedBigUint<Fresh>>>;
+        const size_t K = cts.size();
+        if (!benes_is_count(K) || ss.size() != K || perm.size() != K) return R::Err(PZ_ERR_INVALID, "smix: 1, 2, 4 .. 1024 ciphertexts, one s and one index each");
+        const unsigned s_limbs = ss[0].num_limbs(), W = biguint->limb_bits;
+        if (s_limbs < 1 || s_limbs > 2 * n.num_limbs()) return R::Err(PZ_ERR_INVALID, "smix: an s of 1 .. 2 * n's limbs");
+        if (hs.num_limbs() != 2 * n.num_limbs()) return R::Err(PZ_ERR_INVALID, "smix: hs is not assigned at full width");
+        std::vector<uint8_t> bits;
+        if (!benes_route(K, perm.data(), bits)) return R::Err(PZ_ERR_INVALID, "smix: perm is no permutation of 0 .. K - 1");
+        auto n2m = biguint->square(ctx, n);
+        if (!n2m.ok) return R::Err(n2m.err.status, n2m.err.msg);
+        RefreshAux aux = RefreshAux::new_(W, n.num_limbs(), n.num_limbs());
+        auto n2r = biguint->refresh(ctx, n2m.val, aux);
+        if (!n2r.ok) return R::Err(n2r.err.status, n2r.err.msg);
+        const AssignedBigUint<Fresh>& n2 = n2r.val;
+        (void)ctx.load_zero();
+        const unsigned L = n2.num_limbs(), Wd = n2.num_words(), wn = n.num_words(), wk = 2 * wn;   // K3 works on 2 * wn words
+        const unsigned s_bits = s_limbs * W, sw = (s_bits + 63) / 64;
+        std::vector<uint64_t> nv = n.words(), hv = hs.value().to_limbs(wk), cv, sv;
+        for (const auto& c : cts) {
+            if (c.num_limbs() != L) return R::Err(PZ_ERR_INVALID, "smix: a ciphertext is not assigned at full width");
+            std::vector<uint64_t> w = c.value().to_limbs(wk);
+            cv.insert(cv.end(), w.begin(), w.end());
+        }
+        for (const auto& x : ss) {
+            if (x.num_limbs() != s_limbs) {
+                std::fill(sv.begin(), sv.end(), 0);
+                return R::Err(PZ_ERR_INVALID, "smix: the s_i are not assigned at one width");
+            }
+            std::vector<uint64_t> w = x.value().to_limbs(sw);
+            sv.insert(sv.end(), w.begin(), w.end());
+        }
+        const size_t per = 2 * (size_t)s_bits + 1, layers = benes_layers(K);
+        std::vector<uint64_t> routes(layers * K * wk + 1), rec(K * per * 4 * wk), mv(K * wk);
+        int rc = pz_paillier_smix(ctx.raw(), wn, K, s_bits, nv.data(), hv.data(), cv.data(), bits.data(), sv.data(), routes.data(), rec.data(), K * per,
+                                  mv.data());
+        std::fill(sv.begin(), sv.end(), 0);
+        auto fail = [&](int st, const std::string& m) {
+            std::fill(bits.begin(), bits.end(), 0);
+            std::fill(routes.begin(), routes.end(), 0);
+            std::fill(rec.begin(), rec.end(), 0);
+            return R::Err(st, m);
+        };
+        if (rc != PZ_OK) return fail(rc, std::string("pz_paillier_smix: ") + pz_strerror(rc));
+        for (size_t s = 0; s < layers * (K / 2); ++s) ctx.conditional_swap(L);
+        // the tape holds Wd words per integer (Wd < 2 * wn where limb_bits does not divide 64: the words above are zero)
+        std::vector<uint64_t> steps;
+        auto steps_of = [&](size_t at) {
+            steps.clear();
+            for (size_t f = at * 4; f < (at + 1) * 4; ++f) {
+                if (BigUint::from_limbs(rec.data() + f * wk, wk).bits() > (size_t)L * W) return false;
+                steps.insert(steps.end(), rec.begin() + f * wk, rec.begin() + f * wk + Wd);
+            }
+            return true;
+        };
+        std::vector<AssignedBigUint<Fresh>> out;
+        bool fits = true;
+        for (size_t i = 0; fits && i < K; ++i) {
+            (void)ctx.load_constant_one();
+            (void)ctx.load_zero();
+            for (unsigned li = 0; fits && li < s_limbs; ++li) {
+                ctx.record_cells(Context::NUM_TO_BITS, 1, 7 * (size_t)W - 2);
+                for (unsigned j = 0; fits && j < W; ++j) {   // W x (mul_mod, select, square_mod)
+                    const size_t first = i * per + 2 * ((size_t)li * W + j);
+                    if (!(fits = steps_of(first))) break;
+                    ctx.push_steps(steps, Wd, L, W, n2.value());
+                    ctx.record_cells(Context::SELECT, L, 8 * (size_t)L);
+                    if (!(fits = steps_of(first + 1))) break;
+                    ctx.push_steps(steps, Wd, L, W, n2.value());
+                }
+            }
+            if (fits && (fits = steps_of((i + 1) * per - 1))) ctx.push_steps(steps, Wd, L, W, n2.value());   // the final block
+            out.push_back(AssignedBigUint<Fresh>(BigUint::from_limbs(mv.data() + i * wk, wk), L, W));
+        }
+        std::fill(steps.begin(), steps.end(), 0);
+        if (!fits) return fail(PZ_ERR_RANGE, "a step's integer does not fit the assigned limb count");
+        std::fill(rec.begin(), rec.end(), 0);
+        routes.resize(layers * K * wk);
+        if (wit) {
+            wit->bits = bits;
+            wit->routes = routes;
+        }
+        std::fill(bits.begin(), bits.end(), 0);
+        std::fill(routes.begin(), routes.end(), 0);
+        return R::Ok(out);
+    }
+
     // Decryption with randomness recovery, the key holder's step after `tally`: one pz_paillier_decrypt call
     // over all ciphertexts.  Nothing goes on the tape: the proof that c decrypts to m is the uniform-shape circuit run on the (m, r)
     // returned here, under the statement n | g | m | c (circuit kind 5).
@@ -1317,6 +1413,32 @@ inline void paillier_mix_test(Context& ctx, const RangeChip& range, const Pailli
     }
 }
 
+// the short-randomness mix's driver: assign n, hs and every c_j at full width, every s_i on s_limbs limbs, smix, then per output assign
+// res_i and assert_equal_fresh
+struct PaillierSMixInput {
+    unsigned limb_bits, enc_bits, s_limbs;
+    BigUint n, hs;
+    std::vector<BigUint> cts;
+    std::vector<uint32_t> perm;
+    std::vector<BigUint> ss, res;
+};
+inline void paillier_smix_test(Context& ctx, const RangeChip& range, const PaillierSMixInput& input, PaillierChip::MixWitness* wit) {
+    BigUintChip biguint_chip = BigUintChip::construct(&range, input.limb_bits);
+    PaillierChip paillier_chip = PaillierChip::construct(&biguint_chip, input.enc_bits);
+    auto n_assigned = biguint_chip.assign_integer(ctx, input.n, input.enc_bits).unwrap();
+    auto hs_assigned = biguint_chip.assign_integer(ctx, input.hs, input.enc_bits * 2).unwrap();
+    std::vector<AssignedBigUint<Fresh>> cts, ss;
+    for (const BigUint& c : input.cts) cts.push_back(biguint_chip.assign_integer(ctx, c, input.enc_bits * 2).unwrap());
+    for (const BigUint& s : input.ss) ss.push_back(biguint_chip.assign_integer(ctx, s, input.s_limbs * input.limb_bits).unwrap());
+    auto mixed = paillier_chip.smix(ctx, n_assigned, hs_assigned, cts, input.perm, ss, wit).unwrap();
+    if (mixed.size() != input.res.size()) throw std::runtime_error("paillier_smix_test: one expected output per input");
+    for (size_t i = 0; i < mixed.size(); ++i) {
+        auto res_assigned = biguint_chip.assign_integer(ctx, input.res[i], input.enc_bits * 2).unwrap();
+        if (mixed[i].value() != res_assigned.value()) throw std::runtime_error("assertion failed: `(left == right)` (paillier_smix_test)");
+        biguint_chip.assert_equal_fresh(ctx, mixed[i], res_assigned).unwrap();
+    }
+}
+
 // decryption's driver: make the key handle, decrypt every ciphertext, hold the plaintexts to the expected ones and every recovered
 // (m, r) to its ciphertext by re-encrypting it (paillier_enc_native) -- throws on any mismatch, like the drivers above
 struct PaillierDecryptionInput {
@@ -1508,6 +1630,50 @@ inline int synthesize_sballot_circuit(Context& ctx, unsigned enc_bits, unsigned 
     std::fill(rec.begin(), rec.end(), 0);
     if (rc == PZ_OK)
         rc = pz_sballot_expand_dev(ctx.raw(), Ln, W, ctx.lookup_bits(), K, m_bits, s_limbs, in.data(), d_work, d_modulus, d_advice, d_lookup, 0, 0);
+    std::fill(in.begin(), in.end(), 0);
+    return rc;
+}
+
+// the short-randomness mix's tape (paillier_smix_test) expanded on the device: circuit kind 10, inputs n | hs | c_1 .. c_K | s_1 .. s_K |
+// res_1 .. res_K, the switch bits and route layers of `wit`.  The records and routes go up with fields of 2 * ceil(Ln W / 64) words, as
+// pz_paillier_smix_dev leaves them.  d_work: device memory for both, (K (2 s_limbs W + 1) 4 + layers K) 2 wn words.
+inline int synthesize_smix_circuit(Context& ctx, unsigned enc_bits, unsigned s_limbs, const BigUint& n, const BigUint& hs,
+                                   const std::vector<BigUint>& cts, const std::vector<BigUint>& ss, const std::vector<BigUint>& res,
+                                   const PaillierChip::MixWitness& wit, uint64_t* d_work, uint64_t* d_modulus, uint64_t* d_advice,
+                                   uint64_t* d_lookup) {
+    const unsigned W = ctx.limb_bits(), Ln = enc_bits / W, wn = (Ln * W + 63) / 64, wr = (2 * Ln * W + 63) / 64, wk = 2 * wn;
+    const unsigned sw = (s_limbs * W + 63) / 64;
+    const size_t K = cts.size(), per = 2 * (size_t)s_limbs * W + 1, layers = benes_layers(K);
+    if (!benes_is_count(K) || ss.size() != K || res.size() != K || ctx.n_steps() != K * per || ctx.words() != wr) return PZ_ERR_INVALID;
+    if (wit.bits.size() != layers * (K / 2) || wit.routes.size() != layers * K * wk) return PZ_ERR_INVALID;
+    size_t a = 0, l = 0;
+    int rc = pz_smix_cells(Ln, W, ctx.lookup_bits(), K, s_limbs, &a, &l);
+    if (rc != PZ_OK) return rc;
+    if (a != ctx.advice_cells() || l != ctx.lookup_cells()) return PZ_ERR_INVALID;   // the tape is not this driver's
+    std::vector<uint64_t> in = n.to_limbs(wn), w = hs.to_limbs(wr);
+    in.insert(in.end(), w.begin(), w.end());
+    for (const BigUint& c : cts) {
+        w = c.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    for (const BigUint& s : ss) {
+        w = s.to_limbs(sw);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    for (const BigUint& c : res) {
+        w = c.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    const std::vector<uint64_t>& tp = ctx.tape();
+    std::vector<uint64_t> rec(K * per * 4 * wk, 0);
+    for (size_t f = 0; f < K * per * 4; ++f) std::copy(tp.begin() + f * wr, tp.begin() + (f + 1) * wr, rec.begin() + f * wk);
+    uint64_t* d_routes = d_work + rec.size();
+    rc = pz_upload(ctx.raw(), d_work, rec.data(), rec.size() * 8);
+    std::fill(rec.begin(), rec.end(), 0);
+    if (rc == PZ_OK && !wit.routes.empty()) rc = pz_upload(ctx.raw(), d_routes, wit.routes.data(), wit.routes.size() * 8);
+    if (rc == PZ_OK)
+        rc = pz_smix_expand_dev(ctx.raw(), Ln, W, ctx.lookup_bits(), K, s_limbs, in.data(), wit.bits.empty() ? nullptr : wit.bits.data(),
+                                layers ? d_routes : nullptr, d_work, d_modulus, d_advice, d_lookup, 0, 0);
     std::fill(in.begin(), in.end(), 0);
     return rc;
 }

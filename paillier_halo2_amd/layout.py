@@ -239,7 +239,11 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
     exponent s_i): assign n, g, assign hs at full width, load_witness(m_1 .. m_K), for K >= 2 FlexGate::sum of them, assign s_1 .. s_K
     (s_limbs limbs each), square + refresh once, load_zero, per ciphertext pow_mod(g, m_i) over b in-circuit bits as 'ballot',
     pow_mod(hs, s_i) as 'partial' emits a chain over the s_limbs limbs of s_i, and the final mul_mod, then per ciphertext assign res_i
-    and assert_equal_fresh.  No step count enters: nothing of the key but its size shapes the stream."""
+    and assert_equal_fresh.  No step count enters: nothing of the key but its size shapes the stream.
+    kind 'smix' (circuit kind 10; count = K = 2^d ciphertexts, s_limbs limbs per exponent s_i): assign n, assign
+    hs and c_1 .. c_K at full width, assign s_1 .. s_K (s_limbs limbs each), square + refresh once, load_zero, the network as 'mix', per
+    output [1, 0], pow_mod(hs, s_i) as 'sballot' emits its hs-chain and the final mul_mod(d_i, hss_i), then per output assign res_i and
+    assert_equal_fresh.  No step count enters: the shape is (K, s_limbs) and the key size."""
     Ln, L = limbs_n, 2 * limbs_n
     if kind == "decrypt":
         kind = "encrypt_uniform"
@@ -281,14 +285,21 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
             raise ValueError(f"a short-randomness ballot's exponent has s_limbs = 1 .. {L} limbs, not {s_limbs}")
         if n_steps_g not in (0, 2 * m_bits) or n_steps_r not in (0, 2 * s_limbs * limb_bits):
             raise ValueError("a short-randomness ballot entry has 2 * m_bits g-chain steps and 2 * s_limbs * limb_bits hs-chain steps")
+    elif kind == "smix":
+        if count is None or not (1 <= count <= MIX_MAX and count & (count - 1) == 0):
+            raise ValueError(f"a mix takes count = 1, 2, 4 .. {MIX_MAX} ciphertexts, not {count}")
+        if s_limbs is None or not 1 <= s_limbs <= L:
+            raise ValueError(f"a short-randomness mix's exponent has s_limbs = 1 .. {L} limbs, not {s_limbs}")
+        if n_steps_g or n_steps_r not in (0, 2 * s_limbs * limb_bits):
+            raise ValueError("a short-randomness mix has no g-chain and 2 * s_limbs * limb_bits steps of one hs-chain")
     elif count is not None:
-        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix' and 'sballot'")
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot' and 'smix'")
     if w_bits is not None and kind != "wtally":
         raise ValueError("w_bits belongs to kind 'wtally'")
     if m_bits is not None and kind not in ("ballot", "sballot"):
         raise ValueError("m_bits belongs to kinds 'ballot' and 'sballot'")
-    if s_limbs is not None and kind != "sballot":
-        raise ValueError("s_limbs belongs to kind 'sballot'")
+    if s_limbs is not None and kind not in ("sballot", "smix"):
+        raise ValueError("s_limbs belongs to kinds 'sballot' and 'smix'")
     mm = mul_mod_cells(L, limb_bits, lookup_bits)
     seg, a, l = {}, 0, 0
 
@@ -310,6 +321,13 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         put("assign_n", na, nl)
         put("assign_cts", count * ca, count * cl)
         put("assign_rs", count * na, count * nl)
+    elif kind == "smix":
+        ca, cl = assign_cells(L, limb_bits, lookup_bits)
+        put("assign_n", *assign_cells(Ln, limb_bits, lookup_bits))
+        put("assign_hs", ca, cl)
+        put("assign_cts", count * ca, count * cl)
+        sa, sl = assign_cells(s_limbs, limb_bits, lookup_bits)
+        put("assign_ss", count * sa, count * sl)
     elif kind == "ballot":
         na, nl = assign_cells(Ln, limb_bits, lookup_bits)
         put("assign_n", na, nl)
@@ -383,6 +401,18 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         layers = 2 * (count.bit_length() - 1) - 1 if count > 1 else 0
         put("network", layers * (count // 2) * (4 + 16 * L))
         put("outputs", count * (2 + (n_steps_r + 1) * mm.advice), count * (n_steps_r + 1) * mm.lookup)
+        ra, rl = assign_cells(L, limb_bits, lookup_bits)
+        put("results", count * (ra + assert_equal_cells(L)), count * rl)
+        seg["end"] = (a, l)
+        return CircuitCells(a, l, seg)
+    if kind == "smix":
+        # the network as 'mix'; per output [1, 0], then per limb of s_i num_to_bits (7 W - 2 cells) and W blocks of mul_mod + select +
+        # square_mod, and the final block; then per output assign res_i at full width and assert_equal_fresh
+        layers = 2 * (count.bit_length() - 1) - 1 if count > 1 else 0
+        put("network", layers * (count // 2) * (4 + 16 * L))
+        s_bits = s_limbs * limb_bits
+        steps = 2 * s_bits + 1
+        put("outputs", count * (2 + s_limbs * (7 * limb_bits - 2) + s_bits * 8 * L + steps * mm.advice), count * steps * mm.lookup)
         ra, rl = assign_cells(L, limb_bits, lookup_bits)
         put("results", count * (ra + assert_equal_cells(L)), count * rl)
         seg["end"] = (a, l)

@@ -208,7 +208,12 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
     2^s_bits, and the m_i add up to S = total"; hs = h^n mod n^2 is the key's (keys.djn_generator), m_bits and s_bits are the circuit's
     shape.  total as in "ballot": refused with K = 1, required with K >= 2.  hs = 0 (every c_i would be 0), an hs >= n^2 and a c_i >=
     n^2 are refused here: the circuit compares nothing with n^2.  That hs is an n-th residue is the key authority's to show, not this
-    statement's."""
+    statement's.
+    kind "smix": n | hs | c_1 | .. | c_K | c'_1 | .. | c'_K -- "the list mixed is a re-randomised permutation of the list cts under the
+    key (n, hs)": there are a permutation pi and s_i below 2^s_bits with c'_i = c_pi(i) hs^s_i mod n^2.  K is a power of two (1 ..
+    1024); lists of different lengths are refused, and so are hs = 0 (every output would be 0), an hs >= n^2, any c_j or c'_i >= n^2 and
+    any c'_i = 0.  No g and no single result c.  c'_i holds what c_pi(i) holds only if hs is an n-th residue: that is the key
+    authority's to show, not this statement's."""
     Ln = enc_bits // limb_bits
     mask = (1 << limb_bits) - 1
     limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
@@ -278,13 +283,27 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
         if any(int(x) == 0 for x in mixed):
             raise ValueError("an output of a mix is not 0: a mixer's r_i = 0 destroys the ciphertext")
         parts = [(n, Ln)] + [(ci, 2 * Ln) for ci in cts] + [(ci, 2 * Ln) for ci in mixed]
+    elif kind == "smix":
+        if cts is None or mixed is None or hs is None or g is not None or c is not None:
+            raise ValueError("the smix statement names n, hs, cts = [c_1 .. c_K] and mixed = [c'_1 .. c'_K], and neither g nor c")
+        if len(mixed) != len(cts):
+            raise ValueError("the smix statement has one output per input")
+        if not (1 <= len(cts) <= 1024 and len(cts) & (len(cts) - 1) == 0):
+            raise ValueError("a mix takes 1, 2, 4 .. 1024 ciphertexts")
+        if not 0 < int(hs) < int(n) * int(n):
+            raise ValueError("hs is neither 0 nor n^2 or more")
+        if any(not 0 <= int(x) < int(n) * int(n) for x in list(cts) + list(mixed)):
+            raise ValueError("every input and every output of a mix is below n^2")
+        if any(int(x) == 0 for x in mixed):
+            raise ValueError("an output of a mix is not 0")
+        parts = [(n, Ln), (hs, 2 * Ln)] + [(ci, 2 * Ln) for ci in cts] + [(ci, 2 * Ln) for ci in mixed]
     else:
-        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt, ballot, partial, mix or sballot")
-    if hs is not None and kind != "sballot":
-        raise ValueError("hs belongs to kind 'sballot'")
-    if mixed is not None and kind != "mix":
-        raise ValueError("mixed belongs to kind 'mix'")
-    if c is None and kind not in ("ballot", "partial", "mix", "sballot"):
+        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt, ballot, partial, mix, sballot or smix")
+    if hs is not None and kind not in ("sballot", "smix"):
+        raise ValueError("hs belongs to kinds 'sballot' and 'smix'")
+    if mixed is not None and kind not in ("mix", "smix"):
+        raise ValueError("mixed belongs to kinds 'mix' and 'smix'")
+    if c is None and kind not in ("ballot", "partial", "mix", "sballot", "smix"):
         raise ValueError("the statement names its result c")
     if (v is not None or h is not None or partials is not None) and kind != "partial":
         raise ValueError("v, h and partials belong to kind 'partial'")
@@ -292,8 +311,8 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
         raise ValueError("total belongs to kinds 'ballot' and 'sballot'")
     if m is not None and kind != "decrypt":
         raise ValueError("m belongs to kind 'decrypt'")
-    if cts is not None and kind not in ("tally", "wtally", "ballot", "partial", "mix", "sballot"):
-        raise ValueError("cts belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix' and 'sballot'")
+    if cts is not None and kind not in ("tally", "wtally", "ballot", "partial", "mix", "sballot", "smix"):
+        raise ValueError("cts belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot' and 'smix'")
     if weights is not None and kind != "wtally":
         raise ValueError("weights belongs to kind 'wtally'")
     for v, cnt in parts:

@@ -131,6 +131,15 @@ extern "C" {
     pub fn pz_paillier_mix_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, n: *const u64, cts: *const u64, bits: *const u8, rs: *const u64,
                                d_routes_out: *mut u64, d_steps_out: *mut u64, steps_cap: usize, mixed_out: *mut u64) -> c_int;
     pub fn pz_mix_route(count: usize, perm: *const u32, bits_out: *mut u8) -> c_int;
+    // the short-randomness mix: c'_i = c_perm(i) hs^s_i mod n^2 for count = 2^d ciphertexts and exponents of
+    // s_bits bits under one key with hs = h^n mod n^2; bits, routes_out as pz_paillier_mix (the same route words); ss: ceil(s_bits / 64)
+    // words per exponent; records output-major, 2 * s_bits + 1 per output.  The bits, the s_i and the routes are the mixer's secrets.
+    pub fn pz_paillier_smix(ctx: *mut pz_ctx, limbs_n: u32, count: usize, s_bits: u32, n: *const u64, hs: *const u64, cts: *const u64,
+                            bits: *const u8, ss: *const u64, routes_out: *mut u64, steps_out: *mut u64, steps_cap: usize,
+                            mixed_out: *mut u64) -> c_int;
+    pub fn pz_paillier_smix_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, s_bits: u32, n: *const u64, hs: *const u64, cts: *const u64,
+                                bits: *const u8, ss: *const u64, d_routes_out: *mut u64, d_steps_out: *mut u64, steps_cap: usize,
+                                mixed_out: *mut u64) -> c_int;
     // T-of-T threshold decryption: one trustee's partial decryptions h = v^theta, u_j = (c_j^2)^theta mod n^2 over
     // exactly e_bits bits of its secret share theta (records: the count squarings, then chain i at count + i 2 e_bits), and the combiner
     // m_j = L(prod_i u_ij mod n^2) mu2 mod n over trustee-major partials; flags bit 0: the product is not 1 mod n, bit 1: a partial >= n^2
@@ -274,6 +283,21 @@ extern "C" {
                                       lookup_rows: usize, col_stride: usize) -> c_int;
     pub fn pz_sballot_public_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, m_bits: u32, s_limbs: u32,
                                    cells_out: *mut u64, capacity: usize, n_public: *mut usize) -> c_int;
+    pub fn pz_circuit_structure_smix_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, k: u32, count: usize,
+                                         s_limbs: u32, minimum_rows: usize, blinding_factors: u32, out: *mut *mut pz_structure) -> c_int;
+    // circuit kind 10 ("smix"): its shape is (count = 2^d, s_limbs); inputs n | hs | c_1 .. c_K | s_1 .. s_K | res_1 .. res_K; bits,
+    // d_routes, d_steps as pz_paillier_smix_dev took and left them
+    pub fn pz_smix_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, s_limbs: u32, advice_cells: *mut usize,
+                         lookup_cells: *mut usize) -> c_int;
+    pub fn pz_smix_expand_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, s_limbs: u32,
+                              inputs: *const u64, bits: *const u8, d_routes: *const u64, d_steps: *const u64, d_modulus: *const u64,
+                              d_advice: *mut u64, d_lookup: *mut u64, rows: usize, col_stride: usize) -> c_int;
+    pub fn pz_smix_expand_cols_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, s_limbs: u32,
+                                   inputs: *const u64, bits: *const u8, d_routes: *const u64, d_steps: *const u64, d_modulus: *const u64,
+                                   d_advice: *mut u64, d_lookup: *mut u64, d_col_starts: *const u64, n_adv_cols: usize, max_rows: usize,
+                                   lookup_rows: usize, col_stride: usize) -> c_int;
+    pub fn pz_smix_public_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, s_limbs: u32, cells_out: *mut u64,
+                                capacity: usize, n_public: *mut usize) -> c_int;
     pub fn pz_structure_info(st: *const pz_structure, n_adv: *mut usize, n_adv_filled: *mut usize, n_lk: *mut usize, max_rows: *mut usize,
                              n_constants: *mut usize, n_cells: *mut usize, n_lookups: *mut usize, n_steps_g: *mut usize,
                              n_steps_r: *mut usize) -> c_int;
