@@ -382,6 +382,38 @@ int pz_paillier_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_
                             const uint64_t* g, const uint64_t* hs, const uint64_t* ms, const uint64_t* ss, uint64_t* d_steps_out,
                             size_t steps_cap, uint64_t* c_out);
 
+/* Packed ballot: K = slots choices in ONE ciphertext, c_i = (prod_j G_j^v_ij) * hs^s_i mod n^2 for i =
+ * 1..count under ONE key (n, hs) and the public slot bases G_j = g^(2^(j w)) mod n^2, j = 0..K-1 (keys.pballot_bases, pz::pballot_bases:
+ * read from ONE pz_paillier_trace) -- an ordinary short-randomness ciphertext of M_i = sum_j v_ij 2^(j w), which tally, weighted tally,
+ * mix, decrypt, partial and combine take unchanged; the homomorphic product adds every slot at once (keys.pballot_capacity states how
+ * many ballots a slot holds before it carries).  Neither g nor w is an argument: the bases carry both.  1 <= count <= 1024, 1 <= slots
+ * <= 64, count * slots <= 1024, 1 <= m_bits <= 64, 1 <= s_bits <= 128*limbs_n (else PZ_ERR_INVALID); n: limbs_n words; hs: 2*limbs_n
+ * words; gs = slots x 2*limbs_n words; vs = count x slots 64-bit words, ONE per value, ciphertext-major; ss = count x ceil(s_bits/64)
+ * words; c_out = count x 2*limbs_n words (all HOST).  Per entry, in this order:
+ *   for j = 0..K-1, P_j = BigUintChip::pow_mod(G_j, v_ij) over EXACTLY m_bits in-circuit bits, LSB first (pz_paillier_sballot's
+ *   g-chain on the base G_j): per bit the step (acc, sq) then the step (sq, sq); the trailing square is kept;
+ *   hss_i = BigUintChip::pow_mod(hs, s_i) over EXACTLY s_bits bits in the same schedule;
+ *   the folds (P_0, P_1) -> t_1, (t_1, P_2) -> t_2, .., (t_{K-1}, hss_i) -> c_i (with K = 1 the one step (P_0, hss_i)).
+ * Records a|b|q|r of 2*limbs_n words per field, ciphertext-major: entry i at records i * per and on, per = 2 m_bits K + 2 s_bits + K --
+ * slot j's chain at 2 m_bits j, the hs-chain at 2 m_bits K, the K folds last.  With K = 1 and G_0 = g this is pz_paillier_sballot's
+ * entry bit for bit.  steps_out (steps_cap >= count * per records, else PZ_ERR_CAPACITY) may be NULL: the values only.
+ * Refusals, in this order: a null pointer, limbs_n = 0, count, slots, count * slots, m_bits or s_bits out of range: PZ_ERR_INVALID;
+ * 2*limbs_n > 128: PZ_ERR_UNSUPPORTED; a short steps_cap: PZ_ERR_CAPACITY; a value >= 2^m_bits or an s_i >= 2^s_bits:
+ * PZ_ERR_MESSAGE_RANGE; n = 0: PZ_ERR_ZERO_MODULUS -- all before any launch.  An hs or any G_j >= n^2: PZ_ERR_RANGE (found by the kernel,
+ * which then writes nothing; the status is read before anything is copied out).  No output buffer is written on a refusal.
+ * One team per ciphertext runs its K slot chains, its hs-chain and the folds, ONE launch for all entries, no workgroup waits on another;
+ * n^2 and its Barrett constants are formed once.  The values and the s_i are SECRET: v_ij is read from word i K + j and bit t of s_i
+ * from word t / 64, addresses that depend on loop counters alone, and both reach their accumulators as a lane-wise mask; no branch or
+ * address depends on them (the value-dependent trip count of mul_mod's Barrett correction remains, as in every K3 entry point), and
+ * the staged copies of vs and ss (host form: of the records too) in the context's workspace are overwritten before the call returns.
+ * _dev: d_steps_out is a DEVICE buffer; everything else as above.  (PZ_ABI_VERSION stays 7: additions.) */
+int pz_paillier_pballot(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t slots, uint32_t m_bits, uint32_t s_bits, const uint64_t* n,
+                        const uint64_t* hs, const uint64_t* gs, const uint64_t* vs, const uint64_t* ss, uint64_t* steps_out,
+                        size_t steps_cap, uint64_t* c_out);
+int pz_paillier_pballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t slots, uint32_t m_bits, uint32_t s_bits,
+                            const uint64_t* n, const uint64_t* hs, const uint64_t* gs, const uint64_t* vs, const uint64_t* ss,
+                            uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out);
+
 /* The mix: a verifiable shuffle's values.  A mixer takes c_1 .. c_K under the key n and publishes
  * c'_i = c_perm(i) * r_i^n mod n^2: the same plaintexts, re-randomised, in an order nobody else can follow.  K = count is a power of two
  * in 1 .. 1024; n: limbs_n words; cts = count x 2*limbs_n words; rs = count x limbs_n words; mixed_out = count x 2*limbs_n words (HOST).
@@ -816,6 +848,42 @@ int pz_smix_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, u
                             size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride);
 int pz_smix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t s_limbs, uint64_t* cells_out,
                          size_t capacity, size_t* n_public);
+
+/* Circuit kind 11, "pballot" (DESIGN.md section 15.21): under the key (n, hs) and the public slot bases G_0 .. G_{K-1}, K = slots (1 ..
+ * 64), the R = count ciphertexts c_1 .. c_R (1 .. 1024, R K <= 1024) are packed ballots c_i = (prod_j G_j^v_ij) hs^s_i mod n^2 with every
+ * v_ij < 2^b, b = m_bits (1 .. 64), and s_i < 2^s_bits, s_bits = s_limbs * limb_bits with 1 <= s_limbs <= 2*limbs_n, and for K >= 2 the
+ * values of ciphertext i add up to the public S_i.  Its shape is (R, K, b, s_limbs) and the key SIZE: neither n, g nor the slot width
+ * shapes it, so one proving and verifying key serves every election of a size; the verifier derives G_j = g^(2^(j w)) mod n^2 itself
+ * (verifier.public_inputs).  The by-kind entry points refuse kind 11 and these take the four numbers (anything out of range:
+ * PZ_ERR_INVALID).  The stream, in emission order: assign_integer(n), assign_integer(hs, 2*enc_bits), assign_integer(G_j, 2*enc_bits)
+ * for j = 0..K-1; load_witness of the R K values, ciphertext-major; for K >= 2 one FlexGate::sum per ciphertext over its K cells;
+ * assign_integer(s_i, s_bits) for i = 1..R; square + refresh of n, once; load_zero; per ciphertext, per slot [1, 0], num_to_bits(v_ij,
+ * b) and b blocks of mul_mod(acc, sq), limb-wise select, square_mod(sq) exactly as kind 6's g-chain with the first sq G_j's limb cells,
+ * then pow_mod(hs, s_i) exactly as kind 9, then the K fold blocks mul_mod(P_0, P_1), mul_mod(t_1, P_2), .., mul_mod(t_{K-1}, hss_i);
+ * then per ciphertext assign_integer(res_i, 2*enc_bits) and assert_equal_fresh(c_i, res_i).  With K = 1 and G_0 = g the computation is
+ * kind 9's for one ciphertext (g then stands at full width and in hs's place in the order).  The circuit compares nothing with n^2.
+ *   pz_pballot_cells         the stream's advice / lookup cell counts (host logic).
+ *   pz_pballot_expand_dev    the values.  inputs (HOST): n (ceil(limbs_n*limb_bits/64) words) | hs | G_0 .. G_{K-1}
+ *       (ceil(2*limbs_n*limb_bits/64) words each) | v_11 .. v_RK (ONE word each, ciphertext-major; a value >= 2^b:
+ *       PZ_ERR_MESSAGE_RANGE) | s_1 .. s_R (ceil(s_bits/64) words each; an s_i >= 2^s_bits: PZ_ERR_MESSAGE_RANGE) | res_1 .. res_R (as hs).
+ *       d_steps (device): the R (2 b K + 2 s_bits + K) records of pz_paillier_pballot_dev AS THEY ARE, fields of
+ *       2*ceil(limbs_n*limb_bits/64) words (where that differs from ceil(2*limbs_n*limb_bits/64) the records are repacked on the device
+ *       first).  d_modulus: n^2 (device).  rows / col_stride as pz_circuit_expand_dev.
+ *   pz_pballot_expand_cols_dev  the same with the advice cells in break-point columns, as pz_circuit_expand_cols_dev.
+ *   pz_pballot_public_cells  the stream indices of the exposed cells in statement order: n | hs | G_0 | .. | G_{K-1} | c_1 | .. | c_R
+ *       (the limb cells of n's, hs's, every G_j's and every res_i's assign_integer) and, for K >= 2, S_1 .. S_R (each sum's last
+ *       cell): n_public = limbs_n + 2 limbs_n (1 + K + R) + (K >= 2) R. */
+int pz_pballot_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots, uint32_t m_bits,
+                     uint32_t s_limbs, size_t* advice_cells, size_t* lookup_cells);
+int pz_pballot_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots,
+                          uint32_t m_bits, uint32_t s_limbs, const uint64_t* inputs, const uint64_t* d_steps, const uint64_t* d_modulus,
+                          uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride);
+int pz_pballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots,
+                               uint32_t m_bits, uint32_t s_limbs, const uint64_t* inputs, const uint64_t* d_steps,
+                               const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts,
+                               size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride);
+int pz_pballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots, uint32_t m_bits,
+                            uint32_t s_limbs, uint64_t* cells_out, size_t capacity, size_t* n_public);
 
 /* The same stream with the ADVICE cells in halo2-lib's break-point column layout -- what the dependency's assign_with_constraints
  * [D] does with the Context's cell list when it fills the basic-gate columns (reached from bench.rs:161-171 through keygen /
@@ -1337,6 +1405,16 @@ int pz_shplonk_free(pz_ctx* ctx, pz_shplonk* state);
  * operands to the last layer's outputs and the chain's last select outputs, its result to the assert_equal_fresh against c'_i, each
  * assert_equal_fresh's bit to the constant 1.  An ordinary pz_structure (n_steps_g = 0, n_steps_r = the 2 s_limbs limb_bits records of
  * ONE hs-chain); pz_structure_expose works on it (statement: pz_smix_public_cells).
+ * pz_circuit_structure_pballot_dev: the structure of the packed ballot (kind 11, pz_pballot_cells) of `count` ciphertexts (1 .. 1024) of
+ * `slots` values (1 .. 64, count * slots <= 1024) of m_bits (1 .. 64) bits with exponents of s_limbs (1 .. 2 limbs_n) limbs.  It takes
+ * NO exponent and no slot width: ONE key serves every election of a size (count, slots, m_bits, s_limbs, limbs_n).  The copy
+ * constraints carry the claim: slot j's first sq is tied to assign_integer(G_j)'s limb cells for EVERY ciphertext (what binds a slot to
+ * its base), every hs-chain's first sq to assign_integer(hs)'s limbs, a value's load_witness cell to its chain's num_to_bits
+ * accumulator and to its operand in its ciphertext's sum, every hs-chain's num_to_bits accumulators to assign_integer(s_i)'s limb
+ * cells, every fold's operands to the last select outputs of the chain or the remainder of the fold they name, the last fold's result
+ * to the assert_equal_fresh against res_i, each assert_equal_fresh's bit to the constant 1.  An ordinary pz_structure (n_steps_g = 2
+ * m_bits, n_steps_r = the 2 s_limbs limb_bits records of ONE hs-chain); pz_structure_expose works on it (statement:
+ * pz_pballot_public_cells).
  * ------------------------------------------------------------------------------------------- */
 typedef struct pz_structure pz_structure;
 int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k,
@@ -1356,6 +1434,9 @@ int pz_circuit_structure_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t lim
                                      uint32_t m_bits, uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
 int pz_circuit_structure_smix_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                   uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out);
+int pz_circuit_structure_pballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                     uint32_t slots, uint32_t m_bits, uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors,
+                                     pz_structure** out);
 int pz_structure_info(const pz_structure* st, size_t* n_adv, size_t* n_adv_filled, size_t* n_lk, size_t* max_rows, size_t* n_constants,
                       size_t* n_cells, size_t* n_lookups, size_t* n_steps_g, size_t* n_steps_r);
 int pz_structure_arrays(const pz_structure* st, const uint8_t** d_selectors, const uint32_t** d_map_col, const uint32_t** d_map_row,

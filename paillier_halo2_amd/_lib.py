@@ -76,6 +76,9 @@ SIGNATURES = {
     "pz_paillier_ballot_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP]),
     "pz_paillier_sballot": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_sballot_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
+    "pz_paillier_pballot": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
+    "pz_paillier_pballot_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, VP, VP, VP, VP, VP, VP, C.c_size_t,
+                                          VP]),
     "pz_paillier_mix": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_paillier_mix_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
     "pz_mix_route": (C.c_int, [C.c_size_t, VP, VP]),
@@ -240,6 +243,16 @@ SIGNATURES = {
     "pz_smix_expand_cols_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, VP, VP, VP,
                                           C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "pz_smix_public_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "pz_circuit_structure_pballot_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                   C.c_uint32, C.c_size_t, C.c_uint32, C.POINTER(VP)]),
+    "pz_pballot_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t),
+                                   C.POINTER(C.c_size_t)]),
+    "pz_pballot_expand_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, VP, VP, VP, VP,
+                                        VP, C.c_size_t, C.c_size_t]),
+    "pz_pballot_expand_cols_dev": (C.c_int, [VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, VP, VP, VP,
+                                             VP, VP, VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "pz_pballot_public_cells": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, VP, C.c_size_t,
+                                          C.POINTER(C.c_size_t)]),
     "pz_structure_info": (C.c_int, [VP] + [C.POINTER(C.c_size_t)] * 9),
     "pz_structure_arrays": (C.c_int, [VP] + [C.POINTER(VP)] * 6),
     "pz_structure_free": (C.c_int, [VP]),

@@ -304,7 +304,8 @@ class StructureArrays:
     # w_B | C (wtally: a weight is ONE cell) -- pz_circuit_public_cells gives the same list -- or n | g | c_1 | .. | c_K | S (ballot: S is
     # the sum's last cell, present for K >= 2; pz_ballot_public_cells) -- or n | v | h | c_1 | u_1 | .. | c_K | u_K (partial;
     # pz_partial_public_cells) -- or n | c_1 | .. | c_K | c'_1 | .. | c'_K (mix; pz_mix_public_cells) -- or n | g | hs | c_1 | .. | c_K | S
-    # (sballot; pz_sballot_public_cells) -- or n | hs | c_1 | .. | c_K | c'_1 | .. | c'_K (smix; pz_smix_public_cells)
+    # (sballot; pz_sballot_public_cells) -- or n | hs | c_1 | .. | c_K | c'_1 | .. | c'_K (smix; pz_smix_public_cells) -- or
+    # n | hs | G_0 | .. | G_{K-1} | c_1 | .. | c_R | S_1 | .. | S_R (pballot; pz_pballot_public_cells)
     public_cells: Optional[np.ndarray] = None
 
 
@@ -314,7 +315,7 @@ def _exp_bits(e: int) -> List[int]:
 
 def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: int = 0, exp_r: int = 0, device: Optional[str] = None,
                      count: Optional[int] = None, w_bits: Optional[int] = None, m_bits: Optional[int] = None,
-                     s_limbs: Optional[int] = None) -> StructureArrays:
+                     s_limbs: Optional[int] = None, slots: Optional[int] = None) -> StructureArrays:
     """kind 'encrypt': exp_g = the message m, exp_r = the modulus n -- only their BITS are used, as in the reference's circuit
     (pow_mod_fixed_exp, paillier.rs:50-55); kind 'add': no exponents; kind 'encrypt_uniform' (the uniform-shape circuit, SURVEY 8f rank
     4): exp_g is ignored -- the message's bits are witness cells, ONE structure serves every message of a key; kind 'tally': count = B
@@ -336,7 +337,12 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     the shape is K, m_bits, s_limbs and the key size, so ONE structure serves every key of a size;
     kind 'smix' (circuit kind 10): count = K = 2^d ciphertexts go through 'mix's network and leave as d_i
     hs^s_i mod n^2, each s_i an assign_integer of s_limbs limbs that its chain decomposes limb by limb ('sballot's hs-chain walk) from
-    the ONE base hs -- no exponent is taken: the shape is K, s_limbs and the key size.
+    the ONE base hs -- no exponent is taken: the shape is K, s_limbs and the key size;
+    kind 'pballot' (circuit kind 11): count = R packed ballots c_i = (prod_j G_j^v_ij) hs^s_i of slots = K values
+    each, every value ONE witness cell decomposed into m_bits in-circuit bits whose chain starts from the limb cells of ITS slot's base
+    G_j (an assign_integer at full width, shared by all R ciphertexts), each s_i as in 'sballot', the K powers and hs^s_i folded by K
+    blocks, for K >= 2 one sum per ciphertext -- neither an exponent nor the slot width is taken: the shape is R, K, m_bits, s_limbs and
+    the key size.
     device: None -> numpy arrays; a torch device ("cuda") -> the template is tiled THERE and `src` / `lookup_src` are tensors on it (at
     config c2 the tiled arrays are 3.2 GB: 0.9 s of host numpy against a few ms; `columns` takes either)."""
     dev = None
@@ -371,12 +377,13 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             constants.append(v)
         return const_id[v]
 
-    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial", "mix", "sballot", "smix"):
+    if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial", "mix", "sballot", "smix",
+                    "pballot"):
         raise ValueError(f"unknown circuit kind {kind!r}")
     # 'decrypt' (circuit kind 5) is the uniform-shape circuit cell for cell: the exposed list alone differs
     statement, kind = kind, ("encrypt_uniform" if kind == "decrypt" else kind)
-    if (kind in ("tally", "wtally", "ballot", "partial", "mix", "sballot", "smix")) != (count is not None):
-        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot' and 'smix', which need it")
+    if (kind in ("tally", "wtally", "ballot", "partial", "mix", "sballot", "smix", "pballot")) != (count is not None):
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot', 'smix' and 'pballot', which need it")
     if kind in ("mix", "smix"):
         if not mix.is_count(count):
             raise ValueError(f"a mix takes count = 1, 2, 4 .. {mix.MIX_MAX} ciphertexts, not {count}")
@@ -384,13 +391,17 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             raise ValueError("a mix's structure needs exp_r = the modulus n")
     if kind == "partial" and not 1 <= count <= layout.PARTIAL_MAX:
         raise ValueError(f"a trustee opens count = 1 .. {layout.PARTIAL_MAX} ciphertexts in one proof, not {count}")
-    if (kind in ("ballot", "sballot")) != (m_bits is not None):
-        raise ValueError("m_bits belongs to kinds 'ballot' and 'sballot', which need it")
-    if (kind in ("sballot", "smix")) != (s_limbs is not None):
-        raise ValueError("s_limbs belongs to kinds 'sballot' and 'smix', which need it")
-    if kind in ("sballot", "smix") and not 1 <= s_limbs <= L:
+    if (kind in ("ballot", "sballot", "pballot")) != (m_bits is not None):
+        raise ValueError("m_bits belongs to kinds 'ballot', 'sballot' and 'pballot', which need it")
+    if (kind in ("sballot", "smix", "pballot")) != (s_limbs is not None):
+        raise ValueError("s_limbs belongs to kinds 'sballot', 'smix' and 'pballot', which need it")
+    if kind in ("sballot", "smix", "pballot") and not 1 <= s_limbs <= L:
         raise ValueError(f"a short-randomness exponent has s_limbs = 1 .. {L} limbs, not {s_limbs}")
-    if kind in ("ballot", "sballot"):
+    if (kind == "pballot") != (slots is not None):
+        raise ValueError("slots belongs to kind 'pballot', which needs it")
+    if kind == "pballot" and not (1 <= slots <= layout.PBALLOT_MAX_SLOTS and count * slots <= layout.BALLOT_MAX):
+        raise ValueError(f"a packed ballot has slots = 1 .. {layout.PBALLOT_MAX_SLOTS} with count * slots <= {layout.BALLOT_MAX}, not {slots}")
+    if kind in ("ballot", "sballot", "pballot"):
         if not 1 <= count <= layout.BALLOT_MAX:
             raise ValueError(f"a ballot takes count = 1 .. {layout.BALLOT_MAX} ciphertexts, not {count}")
         if not 1 <= m_bits <= layout.BALLOT_MAX_BITS:
@@ -420,6 +431,21 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         hs_c = _assign(w, L, limb_bits, lb) if kind == "smix" else []           # hs: the key's second base, full width
         ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
         rs_c = [_assign(w, s_limbs if kind == "smix" else Ln, limb_bits, lb) for _ in range(count)]      # r_i; 'smix': s_i
+    elif kind == "pballot":
+        hs_c = _assign(w, L, limb_bits, lb)                                     # hs, then the slot bases G_j: all at full width
+        gs_c = [_assign(w, L, limb_bits, lb) for _ in range(slots)]
+        vs_c = [[w.put() for _ in range(slots)] for _ in range(count)]          # load_witness(v_ij): one cell each, ciphertext-major
+        sums_c = []
+        if slots >= 2:
+            for i in range(count):                                              # FlexGate::sum over the ciphertext's own values
+                sum_c = w.put(vs_c[i][0])
+                for j in range(1, slots):
+                    w.gate(sum_c)
+                    w.putc(1)
+                    w.put(vs_c[i][j])
+                    sum_c = w.put()
+                sums_c.append(sum_c)
+        rs_c = [_assign(w, s_limbs, limb_bits, lb) for _ in range(count)]       # s_i
     elif kind in ("ballot", "sballot"):
         g_c = _assign(w, Ln, limb_bits, lb)
         hs_c = _assign(w, L, limb_bits, lb) if kind == "sballot" else []        # hs: the key's second base, full width
@@ -678,6 +704,39 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             off, rfin = blocks(off, np.asarray(gm, dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
             c_cells.append(rfin[0].tolist())
         n_steps[0] = 2 * m_bits
+    elif kind == "pballot":
+        # per ciphertext: per slot pow_mod(G_j, v_ij) as 'ballot's g-chain, its first sq the limb cells of assign_integer(G_j) -- the
+        # SAME cells for every ciphertext --; pow_mod(hs, s_i) as 'sballot'; then the K folds: block q multiplies the running product
+        # (P_0, then block q - 1's remainder) by P_{q+1}, the last one by hs^s_i
+        ut = _uniform_template(L, limb_bits, lb)
+        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
+        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
+        ut_mask[ut.gates] = 1
+        c_cells = []
+        for i in range(count):
+            powers = []
+            for j in range(slots):
+                wc = _Walk(off)
+                one = wc.putc(1)
+                z2 = wc.putc(0)
+                off = flush(wc)
+                off, pj, _ = bit_chain(off, ut, ut_const, ut_mask, vs_c[i][j], m_bits, np.asarray([one] + [z2] * (L - 1), dtype=np.int64),
+                                       np.asarray(gs_c[j], dtype=np.int64))
+                powers.append(np.asarray(pj, dtype=np.int64))
+            wc = _Walk(off)
+            one = wc.putc(1)
+            z2 = wc.putc(0)
+            off = flush(wc)
+            acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
+            sq_cells = np.asarray(hs_c, dtype=np.int64)
+            for li in range(s_limbs):
+                off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, rs_c[i][li], limb_bits, acc_cells, sq_cells)
+            r_of = off + tm.cells * np.arange(slots, dtype=np.int64)[:, None] + tm.r_cells[None, :]
+            a_cells = np.stack([powers[0]] + [r_of[q - 1] for q in range(1, slots)])
+            b_cells = np.stack([powers[q + 1] for q in range(slots - 1)] + [acc_cells])
+            off, rfin = blocks(off, a_cells, b_cells)
+            c_cells.append(rfin[-1].tolist())
+        n_steps[0], n_steps[1] = 2 * m_bits, 2 * s_limbs * limb_bits
     elif kind == "sballot":
         # per ciphertext: pow_mod(g_ext, m_i) as 'ballot'; pow_mod(hs, s_i) as 'partial' walks a chain -- [1, 0], then per limb of s_i
         # num_to_bits of ITS limb cell and limb_bits bit blocks, every entry's chain from the SAME hs cells --; the final mul_mod
@@ -771,7 +830,7 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         n_steps[0] = nb
     else:
         off, rfin = blocks(off, np.asarray(ext_l(x_c), dtype=np.int64)[None, :], np.asarray(ext_l(y_c), dtype=np.int64)[None, :])
-    roots = c_cells if kind in ("ballot", "partial", "mix", "sballot", "smix") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
+    roots = c_cells if kind in ("ballot", "partial", "mix", "sballot", "smix", "pballot") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
     ws = _Walk(off)
     res_all, eq_cells = [], []
     for c_limbs in roots:
@@ -800,6 +859,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             exposed += list(ct_c[j]) + res_all[(j + 1) * L:(j + 2) * L]
     elif kind in ("mix", "smix"):
         exposed = list(n_c) + list(hs_c) + [c for ct in ct_c for c in ct] + res_all
+    elif kind == "pballot":
+        exposed = list(n_c) + list(hs_c) + [c for g in gs_c for c in g] + res_all + sums_c
     elif kind in ("ballot", "sballot"):
         exposed = list(n_c) + list(g_c) + list(hs_c) + res_all + ([sum_c] if sum_c is not None else [])
     elif kind in ("tally", "wtally"):

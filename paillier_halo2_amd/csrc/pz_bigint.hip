@@ -1164,6 +1164,79 @@ template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_sballot_enc(c
     if (st && lane_id() == 0) atomicOr(status, st);
 }
 
+// ---- the entries of a packed ballot (pz_paillier_pballot): c_i = (prod_j G_j^v_ij) hs^s_i mod n^2 for R ciphertexts
+// of K slots each under ONE key, G_j = g^(2^(j w)) mod n^2 public.  k_sballot_enc with K slot chains in place of its one g-chain: one
+// team per ciphertext runs, per slot j, acc = 1, sq = G_j over exactly m_bits bits of v_ij (pow_mod_uniform), folding the slot's power
+// into ONE running product as soon as the chain ends, then hs^s_i over exactly s_bits bits, then the last fold with hss -- R entries in
+// one launch, no team waits on another.  The Barrett constants come from k_tally_setup, once for all.  The v_ij (one word each, at
+// entry * slots + j: the loop counter alone) and s_i are SECRET: both reach their accumulator as a lane-wise mask over both candidates
+// (ld_select), never as a branch or an address, and every trip count is a launch argument.  (What a mul_mod does with its VALUES is
+// K3's as everywhere.)  An hs or a G_j >= n^2 (public, the same for every team) is ST_RANGE and nothing is written.
+// recs (may be null: the values only): entry i at records i * per .. + per, per = 2 m_bits slots + 2 s_bits + slots: slot j's chain at
+// 2 m_bits j, the hs-chain at 2 m_bits slots, then the folds (P_0, P_1), (t_1, P_2), .., (t_{K-1}, hss) whose last remainder is c_i.
+// per is held against the loops' own counts before any store; a disagreement is ST_INTERNAL, never a write past the entry.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_pballot_enc(const u64* __restrict__ mod, const u64* __restrict__ hs,
+                                                                                  const u64* __restrict__ gs, const u64* __restrict__ vs,
+                                                                                  const u64* __restrict__ ss, unsigned slots, unsigned m_bits,
+                                                                                  unsigned s_bits, unsigned s_words, unsigned per,
+                                                                                  unsigned count, u64* __restrict__ recs,
+                                                                                  u64* __restrict__ c_out, unsigned Ln,
+                                                                                  u32* __restrict__ status) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    if (*block_ok<E>(mod) == 0) return;   // zero modulus (the same word for every workgroup)
+    if (blockIdx.x >= count) return;
+    const unsigned wave = threadIdx.x >> 6, L = 2 * Ln;
+    TeamCtx<E> T;
+    team_init(T, s_team);
+    BarrettCtx<E> B;
+    barrett_from_block(B, mod, L, s_scratch[wave]);
+    const size_t entry = blockIdx.x;
+    unsigned st = ST_OK;
+    const unsigned slot_recs = 2 * m_bits * slots, chains = slot_recs + 2 * s_bits;   // the folds are records chains .. chains + slots - 1
+    if (chains + slots != per) st |= ST_INTERNAL;
+    // the four waves of the team hold the same values: one of them writes, and only where every record index of the entry is below per
+    const bool writer = wave == 0 && recs != nullptr && chains + slots == per;
+    const size_t rec = 4 * (size_t)L;
+    u64* const base = writer ? recs + entry * per * rec : nullptr;
+    const LD<E> hs0 = ld_load<E>(hs, L);
+    {
+        // hs or a G_j >= n^2 (public, the same for every team): nothing is written
+        const LD<E> M = ld_load<E>(block_modulus<E>(mod), C);
+        LD<E> d;
+        bool bad = !ld_sub(d, hs0, M);
+        for (unsigned j = 0; j < slots; ++j) bad |= !ld_sub(d, ld_load<E>(gs + (size_t)j * L, L), M);
+        if (bad) {
+            if (lane_id() == 0) atomicOr(status, st | ST_RANGE);
+            return;
+        }
+    }
+    LD<E> run = ld_small<E>(1);
+    for (unsigned j = 0; j < slots; ++j) {
+        LD<E> p = ld_small<E>(1), sq = ld_load<E>(gs + (size_t)j * L, L);
+        st |= pow_mod_uniform(B, T, p, sq, vs + entry * slots + j, m_bits, writer ? base + (size_t)2 * m_bits * j * rec : nullptr);
+        if (j == 0) {
+            run = p;
+        } else {
+            LD<E> q, r;
+            st |= mul_mod(B, q, r, run, p, TeamMul<E>{&T});
+            if (writer) rec_store(base + (size_t)(chains + j - 1) * rec, run, p, q, r, L);
+            run = r;
+        }
+    }
+    LD<E> hss = ld_small<E>(1);
+    {
+        LD<E> sq = hs0;
+        st |= pow_mod_uniform(B, T, hss, sq, ss + entry * s_words, s_bits, writer ? base + (size_t)slot_recs * rec : nullptr);
+    }
+    LD<E> q, c;
+    st |= mul_mod(B, q, c, run, hss, TeamMul<E>{&T});
+    if (writer) rec_store(base + (size_t)(chains + slots - 1) * rec, run, hss, q, c, L);
+    if (wave == 0) ld_store(c_out + entry * L, c, L);
+    if (st && lane_id() == 0) atomicOr(status, st);
+}
+
 // ---- a mixer's shuffle (pz_paillier_mix): one layer of the Benes network over `count` integers of L limbs that stay
 // in place.  One launch per layer, ordered by the stream alone; one wave per switch.  Switch s of a layer on bit beta is the s-th
 // position j with that bit clear, its partner j | 2^beta: both follow from s and beta.  The switch's bit is SECRET (the bits are the
@@ -2239,6 +2312,103 @@ extern "C" int pz_paillier_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t cou
                                        const uint64_t* g, const uint64_t* hs, const uint64_t* ms, const uint64_t* ss, uint64_t* d_steps_out,
                                        size_t steps_cap, uint64_t* c_out) {
     return sballot_impl(ctx, limbs_n, count, m_bits, s_bits, n, g, hs, ms, ss, d_steps_out, 1, steps_cap, c_out);
+}
+
+// The packed ballot: c_i = (prod_j G_j^v_ij) hs^s_i mod n^2 for `count` ciphertexts of `slots` values of m_bits bits
+// and exponents of s_bits bits under one key (k_pballot_enc, one team per ciphertext, one launch).  Records ciphertext-major,
+// 2 m_bits slots + 2 s_bits + slots per entry.  The values and the s_i are secrets: their staged copies (and, in the host form, the
+// staged records, which repeat them) are overwritten before the call returns, on every path past the staging.  The status is read
+// before anything is copied out: a refused call (an hs or a G_j >= n^2) writes nothing.
+#define K3_PBALLOT_SLOTS_MAX 64
+struct PballotArgs {
+    uint32_t Ln, slots, m_bits, s_bits, s_words, per;
+    size_t count;
+    const uint64_t *n, *hs, *gs, *vs, *ss;
+    uint64_t *steps_out, *c_out;
+    int steps_on_device;
+    u64 *d_n, *d_hs, *d_gs, *d_vs, *d_ss, *d_c, *d_mod, *d_steps;
+    u32* d_status;
+};
+static int pballot_run(pz_ctx* ctx, const PballotArgs& a) {
+    const unsigned L = 2 * a.Ln, C = capacity(L);
+    const size_t nb = (size_t)a.Ln * 8, lb = (size_t)L * 8;
+    HIPCHK(ctx, hipMemcpyAsync(a.d_n, a.n, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_hs, a.hs, lb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_gs, a.gs, a.slots * lb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_vs, a.vs, a.count * a.slots * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.d_ss, a.ss, a.count * a.s_words * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(a.d_status, 0, 4, ctx->stream));
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        PZCHK(launch_barrett_setup(ctx, C, a.d_n, a.Ln, 1, a.d_mod, a.d_status));
+        K3_LAUNCH(ctx, k_pballot_enc, C, dim3((unsigned)a.count), dim3(64 * K3_TEAM), 0, a.d_mod, a.d_hs, a.d_gs, a.d_vs, a.d_ss, a.slots,
+                  a.m_bits, a.s_bits, a.s_words, a.per, (unsigned)a.count, a.d_steps, a.d_c, a.Ln, a.d_status);
+    }
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&st, a.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    PZCHK(status_to_rc(ctx, st));
+    HIPCHK(ctx, hipMemcpyAsync(a.c_out, a.d_c, a.count * lb, hipMemcpyDeviceToHost, ctx->stream));
+    if (a.steps_out && !a.steps_on_device)
+        HIPCHK(ctx, hipMemcpyAsync(a.steps_out, a.d_steps, a.count * a.per * 4 * lb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PZ_OK;
+}
+static int pballot_impl(pz_ctx* ctx, uint32_t Ln, size_t count, uint32_t slots, uint32_t m_bits, uint32_t s_bits, const uint64_t* n,
+                        const uint64_t* hs, const uint64_t* gs, const uint64_t* vs, const uint64_t* ss, uint64_t* steps_out,
+                        int steps_on_device, size_t steps_cap, uint64_t* c_out) {
+    if (!ctx || !n || !hs || !gs || !vs || !ss || !c_out || Ln == 0) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_BALLOT_MAX || slots < 1 || slots > K3_PBALLOT_SLOTS_MAX || count * slots > K3_BALLOT_MAX) return PZ_ERR_INVALID;
+    if (m_bits < 1 || m_bits > 64 || s_bits < 1 || s_bits > 128 * (uint64_t)Ln) return PZ_ERR_INVALID;
+    if (2 * (uint64_t)Ln > 128) return PZ_ERR_UNSUPPORTED;
+    const unsigned L = 2 * Ln;
+    const uint32_t per = 2 * m_bits * slots + 2 * s_bits + slots, s_words = (s_bits + 63) / 64;
+    if (steps_out && steps_cap < count * per) return PZ_ERR_CAPACITY;
+    // before any launch: the circuit's num_to_bits of such a value or exponent cannot hold, and a chain reads its bits and no more
+    for (size_t i = 0; i < count; ++i) {
+        for (uint32_t j = 0; j < slots; ++j)
+            if (m_bits < 64 && vs[i * slots + j] >> m_bits) return PZ_ERR_MESSAGE_RANGE;
+        if ((s_bits & 63) && ss[i * s_words + s_words - 1] >> (s_bits & 63)) return PZ_ERR_MESSAGE_RANGE;
+    }
+    if (bitlen_limbs(n, Ln) == 0) return PZ_ERR_ZERO_MODULUS;
+    PZ_ENTER(ctx);
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8;
+    // n | hs | G_0 .. G_{slots-1} | v_11 .. v_{count,slots} | s_1 .. s_count | c_1 .. c_count | Barrett constants | status
+    const size_t pub_bytes = (nb + lb + slots * lb + 255) & ~(size_t)255;
+    const size_t sec_bytes = (count * slots * 8 + count * s_words * 8 + 255) & ~(size_t)255;
+    const size_t c_bytes = (count * lb + 255) & ~(size_t)255, mod_bytes = mod_block_words(capacity(L)) * 8;
+    void* d;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, pub_bytes + sec_bytes + c_bytes + mod_bytes + 256, &d));
+    char* p = (char*)d;
+    PballotArgs a{};
+    a.Ln = Ln; a.slots = slots; a.m_bits = m_bits; a.s_bits = s_bits; a.s_words = s_words; a.per = per; a.count = count;
+    a.n = n; a.hs = hs; a.gs = gs; a.vs = vs; a.ss = ss; a.steps_out = steps_out; a.c_out = c_out; a.steps_on_device = steps_on_device;
+    a.d_n = (u64*)p;
+    a.d_hs = (u64*)(p + nb);
+    a.d_gs = (u64*)(p + nb + lb);
+    a.d_vs = (u64*)(p + pub_bytes);
+    a.d_ss = a.d_vs + count * slots;
+    a.d_c = (u64*)(p + pub_bytes + sec_bytes);
+    a.d_mod = (u64*)(p + pub_bytes + sec_bytes + c_bytes);
+    a.d_status = (u32*)(p + pub_bytes + sec_bytes + c_bytes + mod_bytes + 64);
+    a.d_steps = steps_on_device ? steps_out : nullptr;
+    const size_t rec_bytes = steps_out && !steps_on_device ? count * per * 4 * lb : 0;
+    if (rec_bytes) {
+        void* t;
+        PZCHK(pz_ws_get(ctx, WS_BIG_B, rec_bytes, &t));
+        a.d_steps = (u64*)t;
+    }
+    return wipe_secrets_and_sync(ctx, pballot_run(ctx, a), a.d_vs, sec_bytes, a.d_steps, rec_bytes);
+}
+extern "C" int pz_paillier_pballot(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t slots, uint32_t m_bits, uint32_t s_bits,
+                                   const uint64_t* n, const uint64_t* hs, const uint64_t* gs, const uint64_t* vs, const uint64_t* ss,
+                                   uint64_t* steps_out, size_t steps_cap, uint64_t* c_out) {
+    return pballot_impl(ctx, limbs_n, count, slots, m_bits, s_bits, n, hs, gs, vs, ss, steps_out, 0, steps_cap, c_out);
+}
+extern "C" int pz_paillier_pballot_dev(pz_ctx* ctx, uint32_t limbs_n, size_t count, uint32_t slots, uint32_t m_bits, uint32_t s_bits,
+                                       const uint64_t* n, const uint64_t* hs, const uint64_t* gs, const uint64_t* vs, const uint64_t* ss,
+                                       uint64_t* d_steps_out, size_t steps_cap, uint64_t* c_out) {
+    return pballot_impl(ctx, limbs_n, count, slots, m_bits, s_bits, n, hs, gs, vs, ss, d_steps_out, 1, steps_cap, c_out);
 }
 
 // The mix: c'_i = c_perm(i) r_i^n mod n^2 for `count` = 2^d ciphertexts under one key.  The 2d - 1 layers of the

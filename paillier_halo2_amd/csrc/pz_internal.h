@@ -191,6 +191,8 @@ struct pz_structure {
     uint32_t limbs_n = 0, limb_bits = 0, lookup_bits = 0;
     size_t count = 0;                  // kind 6 (the ballot): its ciphertexts; n_steps_g = 2 m_bits, n_steps_r = the records of one r^n chain.
                                        // kind 7 (a trustee's partial decryptions): its ciphertexts; n_steps_g = the records of one chain
+    uint32_t slots = 0;                // kind 11 (the packed ballot): the slots of a ciphertext; count = its ciphertexts, n_steps_g = 2 m_bits,
+                                       // n_steps_r = the records of one hs-chain
     size_t n_instance = 0, n_public = 0;
     uint32_t *d_cell_col = nullptr, *d_cell_row = nullptr;
 };

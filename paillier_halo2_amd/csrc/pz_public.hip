@@ -376,6 +376,34 @@ int smix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits
     return PZ_OK;
 }
 
+// the packed ballot (kind 11, `count` ciphertexts of `slots` values of m_bits bits, exponents of s_limbs limbs): n | hs | G_0 | .. |
+// G_{K-1} | c_1 | .. | c_R, then for K >= 2 the sums S_1 .. S_R.  n's limb cells head the stream, hs and the G_j are the 1 + K full-width
+// assign_integer blocks that follow; behind them stand the R K load_witness cells and the R sums of 1 + 3 (K - 1) cells, the last cell of
+// each its S_i; res_i is the assign_integer(2 limbs_n) in front of ciphertext i's assert_equal_fresh, the R pairs closing the stream.
+int pballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots, uint32_t m_bits,
+                         uint32_t s_limbs, std::vector<uint64_t>& cells) {
+    if (limbs_n == 0) return PZ_ERR_INVALID;
+    size_t total = 0, a_in = 0, a_wide = 0, a_eq = 0;
+    PZCHK(pz_pballot_cells(limbs_n, limb_bits, lookup_bits, count, slots, m_bits, s_limbs, &total, nullptr));
+    PZCHK(pz_op_cells(0, limbs_n, limb_bits, lookup_bits, &a_in, nullptr));
+    PZCHK(pz_op_cells(0, 2 * limbs_n, limb_bits, lookup_bits, &a_wide, nullptr));
+    PZCHK(pz_op_cells(5, 2 * limbs_n, limb_bits, lookup_bits, &a_eq, nullptr));
+    if (total < a_in + (slots + 1) * a_wide + count * (a_wide + a_eq)) return PZ_ERR_INTERNAL;
+    const size_t res = total - count * (a_wide + a_eq), K = slots;
+    const uint32_t L = 2 * limbs_n;
+    cells.clear();
+    for (uint32_t j = 0; j < limbs_n; ++j) cells.push_back(j);
+    for (size_t i = 0; i <= K; ++i)
+        for (uint32_t j = 0; j < L; ++j) cells.push_back(a_in + i * a_wide + j);
+    for (size_t i = 0; i < count; ++i)
+        for (uint32_t j = 0; j < L; ++j) cells.push_back(res + i * (a_wide + a_eq) + j);
+    if (K >= 2) {
+        const size_t sums = a_in + (K + 1) * a_wide + count * K, per_sum = 1 + 3 * (K - 1);
+        for (size_t i = 0; i < count; ++i) cells.push_back(sums + (i + 1) * per_sum - 1);
+    }
+    return PZ_OK;
+}
+
 }   // namespace
 
 int pz_instance_eval_launch(pz_ctx* ctx, uint32_t k, const uint64_t omega[4], const uint64_t n_inv[4], const uint64_t* d_instances, size_t L,
@@ -409,7 +437,7 @@ extern "C" int pz_instance_eval_dev(pz_ctx* ctx, uint32_t k, const uint64_t omeg
 // the statement's cells of any kind, an allocation failure as a status.  count (and m_bits) are the ballots', the partial decryption's
 // and the mix's; n_steps_g is the by-kind circuits'
 static int statement_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_g,
-                           size_t n_steps_r, std::vector<uint64_t>& cells) {
+                           size_t n_steps_r, std::vector<uint64_t>& cells, uint32_t slots = 0) {
     try {
         if (kind == 6) return ballot_public_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_r, cells);
         if (kind == 7) return partial_public_cells(limbs_n, limb_bits, lookup_bits, count, cells);
@@ -417,17 +445,20 @@ static int statement_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint3
         if (kind == 9)   // (n_steps_r: the 2 s_limbs limb_bits records of one hs-chain)
             return sballot_public_cells(limbs_n, limb_bits, lookup_bits, count, m_bits, (uint32_t)(n_steps_r / (2 * (size_t)limb_bits)), cells);
         if (kind == 10) return smix_public_cells(limbs_n, limb_bits, lookup_bits, count, (uint32_t)(n_steps_r / (2 * (size_t)limb_bits)), cells);
+        if (kind == 11)
+            return pballot_public_cells(limbs_n, limb_bits, lookup_bits, count, slots, m_bits, (uint32_t)(n_steps_r / (2 * (size_t)limb_bits)),
+                                        cells);
         return public_cells(kind, limbs_n, limb_bits, lookup_bits, n_steps_g, n_steps_r, cells);
     } catch (const std::bad_alloc&) {
         return PZ_ERR_OOM;
     }
 }
-// the tail of the six pz_*_public_cells entry points: the count always, the cells where the caller gave room
+// the tail of the seven pz_*_public_cells entry points: the count always, the cells where the caller gave room
 static int public_cells_out(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_g,
-                            size_t n_steps_r, uint64_t* cells_out, size_t capacity, size_t* n_public) {
+                            size_t n_steps_r, uint64_t* cells_out, size_t capacity, size_t* n_public, uint32_t slots = 0) {
     if (!n_public) return PZ_ERR_INVALID;
     std::vector<uint64_t> cells;
-    PZCHK(statement_cells(kind, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_g, n_steps_r, cells));
+    PZCHK(statement_cells(kind, limbs_n, limb_bits, lookup_bits, count, m_bits, n_steps_g, n_steps_r, cells, slots));
     *n_public = cells.size();
     if (cells_out) {
         if (capacity < cells.size()) return PZ_ERR_CAPACITY;
@@ -438,7 +469,7 @@ static int public_cells_out(int kind, uint32_t limbs_n, uint32_t limb_bits, uint
 
 extern "C" int pz_circuit_public_cells(int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t n_steps_g, size_t n_steps_r,
                                        uint64_t* cells_out, size_t capacity, size_t* n_public) {
-    if (kind > 5) return PZ_ERR_INVALID;   // (kinds 6 to 10 have entry points of their own)
+    if (kind > 5) return PZ_ERR_INVALID;   // (kinds 6 to 11 have entry points of their own)
     return public_cells_out(kind, limbs_n, limb_bits, lookup_bits, 0, 0, n_steps_g, n_steps_r, cells_out, capacity, n_public);
 }
 extern "C" int pz_ballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t m_bits, size_t n_steps_r,
@@ -466,13 +497,20 @@ extern "C" int pz_smix_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32
     return public_cells_out(10, limbs_n, limb_bits, lookup_bits, count, 0, 0, 2 * (size_t)s_limbs * limb_bits, cells_out, capacity, n_public);
 }
 
+extern "C" int pz_pballot_public_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots, uint32_t m_bits,
+                                       uint32_t s_limbs, uint64_t* cells_out, size_t capacity, size_t* n_public) {
+    if (limb_bits == 0) return PZ_ERR_INVALID;
+    return public_cells_out(11, limbs_n, limb_bits, lookup_bits, count, m_bits, 0, 2 * (size_t)s_limbs * limb_bits, cells_out, capacity, n_public,
+                            slots);
+}
+
 extern "C" int pz_structure_expose(pz_structure* st) {
     if (!st || !st->ctx || st->n_instance) return PZ_ERR_INVALID;
     pz_ctx* ctx = st->ctx;
     PZ_ENTER(ctx);
     std::vector<uint64_t> cells;
     PZCHK(statement_cells(st->kind, st->limbs_n, st->limb_bits, st->lookup_bits, st->count, (uint32_t)(st->n_steps_g / 2), st->n_steps_g,
-                          st->n_steps_r, cells));   // (the ballots' m_bits: their g-chains take 2 m_bits records)
+                          st->n_steps_r, cells, st->slots));   // (the ballots' m_bits: their g-chains take 2 m_bits records)
     const size_t L = cells.size(), m = st->n_adv + st->n_lk + 1, n = (size_t)1 << st->k;
     if (L > st->max_rows) return PZ_ERR_UNSUPPORTED;   // (a tally of many ciphertexts: the statement must fit the column's usable rows)
     if (L == 0 || cells.back() >= st->n_cells) return PZ_ERR_INTERNAL;

@@ -448,8 +448,13 @@ struct Stream {
 // s_limbs limbs for every output, square + refresh, load_zero; kind 8's network walk; per output kind 9's hs-chain walk -- [1, 0], then
 // per limb of s_i num_to_bits of ITS limb cell and W uniform blocks, the first sq hs's limb cells -- and the block mul_mod(d_i, hss_i);
 // then per output res_i and assert_equal_fresh.  No exponent of the key shapes it.
+// kind 11 (the packed ballot): n, hs and the `slots` bases G_j at full width, count * slots load_witness cells
+// (the values, ciphertext-major), for slots >= 2 one FlexGate::sum per ciphertext, assign_integer(s_i) of s_limbs limbs for every
+// ciphertext, square + refresh, load_zero; per ciphertext, per slot pow_mod(G_j, v_ij) over w_bits (= m_bits) in-circuit bits -- the
+// first sq G_j's OWN limb cells, for every ciphertext --, kind 9's hs-chain walk, and the `slots` fold blocks (P_0, P_1), (t_1, P_2), ..,
+// (t_{K-1}, hss); then per ciphertext res_i and assert_equal_fresh.  Neither n, g nor the slot width shapes it.
 int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, unsigned w_bits,
-                 unsigned s_limbs, Stream& S) {
+                 unsigned s_limbs, unsigned slots, Stream& S) {
     const unsigned L = 2 * Ln;
     S.tmpls.reserve(2);                  // (references to the templates stay valid when a circuit with in-circuit bits adds the second one)
     S.tmpls.push_back(block_template(L, W, lb));
@@ -477,6 +482,21 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             }
         }
         for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, kind == 9 ? s_limbs : Ln, W, lb));   // r_i; kind 9: s_i
+    } else if (kind == 11) {
+        x_c = assign(w, L, W, lb);                                               // hs
+        for (unsigned j = 0; j < slots; ++j) ct_c.push_back(assign(w, L, W, lb));   // G_j: the slot bases, full width
+        for (size_t i = 0; i < count * slots; ++i) wt_c.push_back(w.put());       // load_witness(v_ij): one cell, no gate
+        if (slots >= 2)
+            for (size_t i = 0; i < count; ++i) {   // FlexGate::sum over the ciphertext's own values, as kind 6's
+                i64 acc = w.put(wt_c[i * slots]);
+                for (unsigned j = 1; j < slots; ++j) {
+                    w.gate(acc);
+                    w.putc(c_small(1));
+                    w.put(wt_c[i * slots + j]);
+                    acc = w.put();
+                }
+            }
+        for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, s_limbs, W, lb));   // s_i
     } else if (kind == 8 || kind == 10) {
         if (kind == 10) x_c = assign(w, L, W, lb);   // hs: the key's second base, full width
         for (size_t i = 0; i < count; ++i) ct_c.push_back(assign(w, L, W, lb));
@@ -671,6 +691,40 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
             }
             roots.push_back(block_r(off));
             off = S.blocks(off, 0, std::move(gm_cells), std::move(acc_cells), {}, 1);
+        }
+        S.n_steps_g = 2 * (size_t)w_bits;
+        S.n_steps_r = 2 * (size_t)s_limbs * W;
+    } else if (kind == 11) {
+        S.tmpls.push_back(uniform_template(L, W, lb));
+        S.bind_template_constants(1);
+        for (size_t i = 0; i < count; ++i) {
+            std::vector<std::vector<i64>> powers;
+            for (unsigned j = 0; j < slots; ++j) {
+                Walk wb(off);   // a slot chain's head: assign_constant(1), load_zero, then num_to_bits; its first sq is G_j's limb cells
+                const i64 one = wb.putc(c_small(1)), z2 = wb.putc(c_small(0));
+                std::vector<i64> acc_cells(L, z2), sq_cells = ct_c[j];
+                acc_cells[0] = one;
+                off = bit_chain(off, wb, wt_c[i * slots + j], w_bits, acc_cells, sq_cells);
+                powers.push_back(std::move(acc_cells));
+            }
+            Walk wc(off);   // pow_mod(hs, s_i): kind 9's walk
+            const i64 one_s = wc.putc(c_small(1)), z2_s = wc.putc(c_small(0));
+            off = S.flush(wc);
+            std::vector<i64> hss(L, z2_s), sq_cells = x_c;
+            hss[0] = one_s;
+            for (unsigned li = 0; li < s_limbs; ++li) {
+                Walk wl(off);
+                off = bit_chain(off, wl, rs_c[i][li], W, hss, sq_cells);
+            }
+            // the folds: block q multiplies the running product (P_0, then block q - 1's remainder) by P_{q+1}, the last one by hss
+            std::vector<i64> a((size_t)slots * L), b((size_t)slots * L);
+            for (unsigned q = 0; q < slots; ++q)
+                for (unsigned j = 0; j < L; ++j) {
+                    a[(size_t)q * L + j] = q == 0 ? powers[0][j] : r_of(off, tm, q - 1, j);
+                    b[(size_t)q * L + j] = q + 1 < slots ? powers[q + 1][j] : hss[j];
+                }
+            roots.push_back(block_r(off + (i64)(slots - 1) * (i64)tm.cells));
+            off = S.blocks(off, 0, std::move(a), std::move(b), {}, slots);
         }
         S.n_steps_g = 2 * (size_t)w_bits;
         S.n_steps_r = 2 * (size_t)s_limbs * W;
@@ -1128,9 +1182,9 @@ extern "C" int pz_structure_arrays(const pz_structure* st, const uint8_t** d_sel
 }
 
 static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, const uint64_t* exp_g,
-                          const uint64_t* exp_r, size_t count, uint32_t w_bits, uint32_t s_limbs, size_t minimum_rows,
-                          uint32_t blinding_factors, pz_structure** out) {
-    if (!ctx || !out || kind < 0 || kind > 10 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
+                          const uint64_t* exp_r, size_t count, uint32_t w_bits, uint32_t s_limbs, uint32_t slots,
+                          size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
+    if (!ctx || !out || kind < 0 || kind > 11 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
     const int handle_kind = kind;   // kind 5 ("decrypt") is kind 2's circuit under another statement: pz_structure_expose alone tells them apart
     if (kind == 5) kind = 2;
     if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
@@ -1141,6 +1195,9 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     if (kind == 8 && (count < 1 || count > 1024 || (count & (count - 1)) != 0)) return PZ_ERR_INVALID;
     if (kind == 9 && (count < 1 || count > 1024 || w_bits < 1 || w_bits > 64 || s_limbs < 1 || s_limbs > 2 * limbs_n)) return PZ_ERR_INVALID;
     if (kind == 10 && (count < 1 || count > 1024 || (count & (count - 1)) != 0 || s_limbs < 1 || s_limbs > 2 * limbs_n)) return PZ_ERR_INVALID;
+    if (kind == 11 && (count < 1 || count > 1024 || slots < 1 || slots > 64 || count * slots > 1024 || w_bits < 1 || w_bits > 64 ||
+                       s_limbs < 1 || s_limbs > 2 * limbs_n))
+        return PZ_ERR_INVALID;
     if (((kind == 0 || kind == 2 || kind == 6 || kind == 8) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
     const i64 n = (i64)1 << k;
     const i64 unusable = (i64)blinding_factors + 3;
@@ -1149,7 +1206,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     PZ_ENTER(ctx);
     Stream S;
     try {
-        PZCHK(build_stream(kind, limbs_n, limb_bits, lookup_bits, exp_g, exp_r, count, w_bits, s_limbs, S));
+        PZCHK(build_stream(kind, limbs_n, limb_bits, lookup_bits, exp_g, exp_r, count, w_bits, s_limbs, slots, S));
     } catch (const std::bad_alloc&) {
         return PZ_ERR_OOM;
     }
@@ -1170,6 +1227,7 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     if (!st) return PZ_ERR_OOM;
     st->k = k;
     st->count = kind >= 6 ? count : 0;
+    st->slots = kind == 11 ? slots : 0;
     st->kind = handle_kind; st->limbs_n = limbs_n; st->limb_bits = limb_bits; st->lookup_bits = lookup_bits;
     st->n_adv = (size_t)A; st->n_used = (size_t)A_used; st->n_lk = (size_t)Lk; st->max_rows = (size_t)max_rows;
     st->n_cells = (size_t)NC; st->n_lookups = (size_t)NL; st->n_steps_g = S.n_steps_g; st->n_steps_r = S.n_steps_r;
@@ -1302,43 +1360,52 @@ extern "C" int pz_circuit_structure_dev(pz_ctx* ctx, int kind, uint32_t limbs_n,
                                         const uint64_t* exp_g, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
                                         pz_structure** out) {
     if ((kind < 0 || kind > 2) && kind != 5) return PZ_ERR_INVALID;   // (the tallies have entry points of their own: this one has no place for their count)
-    return structure_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, k, exp_g, exp_r, 0, 0, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, kind, limbs_n, limb_bits, lookup_bits, k, exp_g, exp_r, 0, 0, 0, 0, minimum_rows, blinding_factors, out);
 }
 extern "C" int pz_circuit_structure_tally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                               size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 3, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 3, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, 0, 0, minimum_rows, blinding_factors, out);
 }
 extern "C" int pz_circuit_structure_wtally_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                                uint32_t w_bits, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 4, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, w_bits, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 4, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, w_bits, 0, 0, minimum_rows, blinding_factors, out);
 }
 // the ballot (kind 6): count ciphertexts (1 .. 1024) of m_bits-bit messages (1 .. 64) under the key whose modulus is exp_r
 extern "C" int pz_circuit_structure_ballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                                uint32_t m_bits, const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors,
                                                pz_structure** out) {
-    return structure_impl(ctx, 6, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, m_bits, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 6, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, m_bits, 0, 0, minimum_rows, blinding_factors, out);
 }
 // a trustee's partial decryptions (kind 7): count ciphertexts (1 .. 1024) opened under one share; the shape is count and the key size alone
 extern "C" int pz_circuit_structure_partial_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                                 size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 7, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 7, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, 0, 0, minimum_rows, blinding_factors, out);
 }
 // the mix (kind 8): count = 2^d ciphertexts (1 .. 1024) under the key whose modulus is exp_r; the shape is count and n alone
 extern "C" int pz_circuit_structure_mix_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                             const uint64_t* exp_r, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 8, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, 0, 0, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 8, limbs_n, limb_bits, lookup_bits, k, nullptr, exp_r, count, 0, 0, 0, minimum_rows, blinding_factors, out);
 }
 // the short-randomness ballot (kind 9): count ciphertexts (1 .. 1024) of m_bits-bit messages (1 .. 64) with exponents of s_limbs limbs
 // (1 .. 2 limbs_n); the shape is (count, m_bits, s_limbs) and the key SIZE alone -- no exponent of the key enters it
 extern "C" int pz_circuit_structure_sballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                                 uint32_t m_bits, uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors,
                                                 pz_structure** out) {
-    return structure_impl(ctx, 9, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, m_bits, s_limbs, minimum_rows, blinding_factors,
+    return structure_impl(ctx, 9, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, m_bits, s_limbs, 0, minimum_rows, blinding_factors,
                           out);
 }
 // the short-randomness mix (kind 10): count = 2^d ciphertexts (1 .. 1024) with exponents of s_limbs limbs (1 .. 2 limbs_n); the shape is
 // (count, s_limbs) and the key SIZE alone -- no exponent of the key enters it
 extern "C" int pz_circuit_structure_smix_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
                                              uint32_t s_limbs, size_t minimum_rows, uint32_t blinding_factors, pz_structure** out) {
-    return structure_impl(ctx, 10, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, s_limbs, minimum_rows, blinding_factors, out);
+    return structure_impl(ctx, 10, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, 0, s_limbs, 0, minimum_rows, blinding_factors, out);
+}
+// the packed ballot (kind 11): count ciphertexts (1 .. 1024) of `slots` values (1 .. 64, count * slots <= 1024) of m_bits bits (1 .. 64)
+// with exponents of s_limbs limbs (1 .. 2 limbs_n); the shape is (count, slots, m_bits, s_limbs) and the key SIZE alone -- neither n,
+// g nor the slot width enters it
+extern "C" int pz_circuit_structure_pballot_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, uint32_t k, size_t count,
+                                                uint32_t slots, uint32_t m_bits, uint32_t s_limbs, size_t minimum_rows,
+                                                uint32_t blinding_factors, pz_structure** out) {
+    return structure_impl(ctx, 11, limbs_n, limb_bits, lookup_bits, k, nullptr, nullptr, count, m_bits, s_limbs, slots, minimum_rows,
+                          blinding_factors, out);
 }

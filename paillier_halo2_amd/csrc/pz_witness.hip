@@ -1951,6 +1951,156 @@ extern "C" int pz_sballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_
                                limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs);
 }
 
+// ---- the packed ballot (circuit kind 11): R ciphertexts of K slots each, c_i = (prod_j G_j^v_ij) hs^s_i mod
+// n^2 under one key and the public slot bases G_j.  Stream: assign n; assign hs, G_0 .. G_{K-1} at full width; load_witness of the R K
+// values, ciphertext-major; K >= 2: one FlexGate::sum per ciphertext; assign s_1 .. s_R (s_limbs limbs each); square + refresh,
+// load_zero; per ciphertext [per slot: 1, 0, num_to_bits(v_ij, b), b bit blocks as kind 6's g-chain | pow_mod(hs, s_i) as kind 9 |
+// the K fold blocks]; per ciphertext a result block (res_i against the remainder of the entry's last record).  inputs: n | hs | G_0 ..
+// G_{K-1} (L64 words each) | v_11 .. v_RK (one word each) | s_1 .. s_R (ceil(s_limbs W / 64) words each) | res_1 .. res_R.  Records are
+// pz_paillier_pballot_dev's, as it leaves them: entry-major, 2 b K + 2 s_limbs W + K each.  One kernel of its own, the R sums; the
+// rest are the bits, select, expand, assign and result kernels above.
+#define PBALLOT_MAX 1024
+#define PBALLOT_SLOTS_MAX 64
+struct PballotP {
+    size_t R, K, per, s_limbs, s_words, a_hs, l_hs, a_vals, a_sum, sum_cells, a_ss, l_ss, a_ent, l_ent, ent_stride, head, g_cells, limb_stride;
+    size_t in_hs, in_vs, in_ss;   // word offsets inside `inputs`
+    unsigned rw;                  // words per field of a record as K3 writes them
+    ResP res;                     // (no sum: k_pballot_sums writes the R of them)
+};
+// grid.x = ciphertext: FlexGate::sum over its K one-word values.  Dynamic shared memory: 16 bytes per value.
+__global__ __launch_bounds__(256) void k_pballot_sums(ExpP P, const u64* __restrict__ vals, size_t K, size_t a_sum, size_t sum_cells,
+                                                      Fr* __restrict__ advice) {
+    extern __shared__ u64 s_pre[][2];
+    const size_t i = blockIdx.x;
+    flex_sum_cells(vals + i * K, K, s_pre, adv_ptr(P, advice, a_sum + i * sum_cells));
+}
+static int make_pballot_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, uint32_t slots, uint32_t m_bits,
+                               uint32_t s_limbs, CircP& C, PballotP& B, size_t* adv_total, size_t* lk_total) {
+    if (count < 1 || count > PBALLOT_MAX || slots < 1 || slots > PBALLOT_SLOTS_MAX || count * slots > PBALLOT_MAX) return PZ_ERR_INVALID;
+    if (m_bits < 1 || m_bits > 64 || s_limbs < 1 || s_limbs > 2 * (uint64_t)limbs_n) return PZ_ERR_INVALID;
+    PZCHK(circ_base(limbs_n, limb_bits, lb, 11, C));
+    memset(&B, 0, sizeof B);
+    const size_t W = limb_bits, s_bits = (size_t)s_limbs * W, K = slots;
+    B.R = count;
+    B.K = K;
+    B.s_limbs = s_limbs;
+    B.s_words = (s_bits + 63) / 64;
+    B.per = 2 * (size_t)m_bits * K + 2 * s_bits + K;
+    B.rw = 2 * C.words_n;
+    B.in_hs = C.words_n;
+    B.in_vs = B.in_hs + (1 + K) * C.e.L64;
+    B.in_ss = B.in_vs + count * K;
+    size_t a = 0, l = 0;
+    assign_inputs(C, 1, a, l);
+    B.a_hs = a; B.l_hs = l; a += (1 + K) * 2 * asg_adv(C); l += (1 + K) * 2 * asg_lk(C);
+    B.a_vals = a; a += count * K;
+    B.sum_cells = K >= 2 ? 1 + 3 * (K - 1) : 0;
+    B.a_sum = a; a += count * B.sum_cells;
+    B.a_ss = a; B.l_ss = l;
+    a += count * s_limbs * (1 + (size_t)C.rc_adv); l += count * s_limbs * (size_t)C.rc_lk;
+    square_refresh_cells(C, a, l);
+    load_zero_cell(C, a);
+    B.head = 2 + nbits_cells(m_bits);
+    B.g_cells = B.head + m_bits * bit_stride(C);
+    B.limb_stride = nbits_cells(W) + W * bit_stride(C);
+    B.ent_stride = K * B.g_cells + 2 + s_limbs * B.limb_stride + K * C.e.cells;
+    B.a_ent = a; B.l_ent = l;
+    a += count * B.ent_stride; l += count * B.per * C.e.lookups;
+    // the [1, 0] of pow_mod(hs, s_i) stands behind the K slot chains
+    B.res.a_head = B.a_ent + K * B.g_cells; B.res.head_stride = B.ent_stride;
+    B.res.rec0 = B.per - 1; B.res.rec_stride = B.per; B.res.field = 3;
+    result_blocks(C, B.res, count, B.in_ss + count * B.s_words, a, l);
+    *adv_total = a;
+    *lk_total = l;
+    return PZ_OK;
+}
+
+extern "C" int pz_pballot_cells(uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots, uint32_t m_bits,
+                                uint32_t s_limbs, size_t* advice_cells, size_t* lookup_cells) {
+    CircP C;
+    PballotP B;
+    size_t a, l;
+    const int rc = make_pballot_params(limbs_n, limb_bits, lookup_bits, count, slots, m_bits, s_limbs, C, B, &a, &l);
+    return put_cells(rc, a, l, advice_cells, lookup_cells);
+}
+
+static int pballot_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots,
+                               uint32_t m_bits, uint32_t s_limbs) {
+    PZCHK(expand_check(A));
+    CircP C;
+    PballotP B;
+    size_t a, l;
+    PZCHK(make_pballot_params(limbs_n, limb_bits, lookup_bits, count, slots, m_bits, s_limbs, C, B, &a, &l));
+    PZCHK(expand_layout(A, C));
+    const size_t W = limb_bits, s_bits = s_limbs * W, K = slots;
+    for (size_t i = 0; i < count; ++i) {   // num_to_bits of such a value or of such an exponent's top limb cannot hold
+        for (size_t j = 0; j < K; ++j)
+            if (m_bits < 64 && A.inputs[B.in_vs + i * K + j] >> m_bits) return PZ_ERR_MESSAGE_RANGE;
+        if ((s_bits & 63) && A.inputs[B.in_ss + (i + 1) * B.s_words - 1] >> (s_bits & 63)) return PZ_ERR_MESSAGE_RANGE;
+    }
+    pz_ctx* ctx = A.ctx;
+    PZ_ENTER(ctx);
+    const u64* in;
+    PZCHK(expand_stage(A, B.res.in_res + count * C.e.L64, nullptr, 0, &in));
+    const u64* recs = A.d_steps;
+    PZCHK(repack_records(ctx, C, B.rw, count * B.per * 4, &recs));
+    pz_timer tm(ctx, PZ_T_EXPAND);
+    Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
+    const size_t rec = 4 * (size_t)C.e.L64;   // words per step record
+    // n, square, refresh, load_zero
+    hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, (const u64*)nullptr, adv, lk);
+    // assign_integer(hs), assign_integer(G_j): 1 + K integers of 2 Ln limbs from L64 words each; assign_integer(s_i): s_limbs limbs
+    launch_assign(A, C, in, B.in_hs, C.nf, C.e.L64, 1 + K, B.a_hs, B.l_hs);
+    launch_assign(A, C, in, B.in_ss, (unsigned)s_limbs, (unsigned)B.s_words, count, B.a_ss, B.l_ss);
+    if (K >= 2)
+        hipLaunchKernelGGL(k_pballot_sums, dim3((unsigned)count), dim3(256), K * 16, ctx->stream, C.e, in + B.in_vs, K, B.a_sum, B.sum_cells, adv);
+    // the slot chains of a ciphertext stand g_cells apart and their records 2 b apart: per ciphertext the K load_witness cells, heads
+    // and num_to_bits, and the selects; then slot by slot the record pairs of ALL ciphertexts in one launch
+    for (size_t i = 0; i < count; ++i) {
+        const u64* d_v = in + B.in_vs + i * K;
+        const size_t ent = B.a_ent + i * B.ent_stride;
+        hipLaunchKernelGGL(k_circuit_bits_many, dim3((unsigned)K), dim3(256), 0, ctx->stream, C.e, m_bits, d_v, B.a_vals + i * K, ent, B.g_cells, adv);
+        hipLaunchKernelGGL(k_circuit_select_many, dim3((unsigned)(K * m_bits)), dim3(256), 0, ctx->stream, C.e, m_bits, d_v, recs + i * B.per * rec,
+                           2 * (size_t)m_bits, ent, B.g_cells, bit_stride(C), B.head, adv);
+    }
+    for (size_t j = 0; j < K; ++j) {
+        const size_t r0 = 2 * (size_t)m_bits * j;
+        launch_chains(A, C, B.a_ent + j * B.g_cells + 2, B.l_ent + r0 * C.e.lookups, recs + r0 * rec, m_bits, count, B.ent_stride, B.per);
+    }
+    // the hs-chains as kind 9's, behind the slot chains
+    const size_t hs_cells = B.a_ent + K * B.g_cells + 2, hs_rec = 2 * (size_t)m_bits * K;
+    for (size_t i = 0; i < count; ++i) {
+        const size_t bits0 = hs_cells + i * B.ent_stride;
+        const u64 *d_s = in + B.in_ss + i * B.s_words, *d_chain = recs + (i * B.per + hs_rec) * rec;
+        hipLaunchKernelGGL(k_circuit_bits, dim3((unsigned)s_limbs), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s, bits0,
+                           B.limb_stride, adv);
+        hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)s_bits), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s,
+                           d_chain, bits0, B.limb_stride, bit_stride(C), nbits_cells(W), adv);
+    }
+    for (size_t li = 0; li < s_limbs; ++li) {
+        const size_t r0 = hs_rec + li * 2 * W;
+        launch_chains(A, C, hs_cells + li * B.limb_stride, B.l_ent + r0 * C.e.lookups, recs + r0 * rec, W, count, B.ent_stride, B.per);
+    }
+    // the K fold blocks of every ciphertext, and the result blocks with the [1, 0] of the hs-chains
+    launch_runs(A, C, B.a_ent + B.ent_stride - K * C.e.cells, B.l_ent, recs, K, count, B.ent_stride, B.per, B.per - K);
+    launch_results(A, C, B.res, count, in, recs);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+extern "C" int pz_pballot_expand_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots,
+                                     uint32_t m_bits, uint32_t s_limbs, const uint64_t* inputs, const uint64_t* d_steps,
+                                     const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, size_t rows, size_t col_stride) {
+    return pballot_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, false, rows, col_stride, nullptr, 0, 0}, limbs_n, limb_bits,
+                               lookup_bits, count, slots, m_bits, s_limbs);
+}
+extern "C" int pz_pballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t limb_bits, uint32_t lookup_bits, size_t count, uint32_t slots,
+                                          uint32_t m_bits, uint32_t s_limbs, const uint64_t* inputs, const uint64_t* d_steps,
+                                          const uint64_t* d_modulus, uint64_t* d_advice, uint64_t* d_lookup, const uint64_t* d_col_starts,
+                                          size_t n_adv_cols, size_t max_rows, size_t lookup_rows, size_t col_stride) {
+    return pballot_expand_impl({ctx, inputs, d_steps, d_modulus, d_advice, d_lookup, true, lookup_rows, col_stride, d_col_starts, n_adv_cols, max_rows},
+                               limbs_n, limb_bits, lookup_bits, count, slots, m_bits, s_limbs);
+}
+
 // ---- the short-randomness mix (circuit kind 10): K = 2^d ciphertexts through the Benes network, then c'_i =
 // d_i hs^s_i mod n^2.  Stream: assign n; assign hs, c_1 .. c_K at full width; assign s_1 .. s_K (s_limbs limbs each); square + refresh,
 // load_zero; the network as kind 8; per output [1, 0 | pow_mod(hs, s_i) as kind 9 emits its hs-chain: per limb of s_i num_to_bits and W

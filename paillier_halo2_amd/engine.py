@@ -595,6 +595,40 @@ class Engine:
                                                  VP(d_steps), steps_cap, _ptr(c)), "pz_paillier_sballot_dev")
         return c
 
+    # the packed ballot: c_i = (prod_j G_j^v_ij) hs^s_i mod n^2, G_j = g^(2^(j w)) from keys.pballot_bases
+    @staticmethod
+    def _pballot_args(limbs_n: int, n, hs, gs, vs, ss, s_bits: int):
+        n, hs = _np(n).reshape(limbs_n), _np(hs).reshape(2 * limbs_n)
+        gs = _np(gs).reshape(-1, 2 * limbs_n)
+        vs = np.ascontiguousarray(vs, dtype=np.uint64)
+        vs = vs.reshape(-1, gs.shape[0]) if gs.shape[0] else vs.reshape(0, 0)
+        ss = _np(ss).reshape(-1, max(-(-s_bits // 64), 1))
+        if vs.shape[0] != ss.shape[0]:
+            raise ValueError("one row of slot values and one s per ciphertext")
+        return n, hs, gs, vs, ss
+
+    def paillier_pballot(self, limbs_n: int, n, hs, gs, vs, ss, m_bits: int, s_bits: int, want_steps: bool = True):
+        """c_i = (prod_j G_j^v_ij) hs^s_i mod n^2 for R ciphertexts of K slot values below 2^m_bits and R exponents below 2^s_bits under
+        one key (pz.h pz_paillier_pballot): hs (2*limbs_n,) words, gs (K, 2*limbs_n) words (keys.pballot_bases), vs (R, K) integers, ss
+        (R, ceil(s_bits / 64)) words.  Returns (c (R, 2*limbs_n), steps (R, 2 m_bits K + 2 s_bits + K, 4, 2*limbs_n) or None)."""
+        L = 2 * limbs_n
+        n, hs, gs, vs, ss = self._pballot_args(limbs_n, n, hs, gs, vs, ss, s_bits)
+        count, slots = vs.shape
+        per = 2 * m_bits * slots + 2 * s_bits + slots
+        steps = np.zeros((max(count, 1), per, 4, L), dtype=np.uint64) if want_steps else None
+        c = np.zeros((max(count, 1), L), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_pballot(self.ctx, limbs_n, count, slots, m_bits, s_bits, _ptr(n), _ptr(hs), _ptr(gs), _ptr(vs), _ptr(ss),
+                                             _ptr(steps) if want_steps else VP(), count * per, _ptr(c)), "pz_paillier_pballot")
+        return c, steps
+
+    def paillier_pballot_dev(self, limbs_n: int, n, hs, gs, vs, ss, m_bits: int, s_bits: int, d_steps: int, steps_cap: int):
+        """the same with the records left on the device (d_steps: steps_cap x 4 x 2*limbs_n u64; 0: the values only).  Returns c."""
+        n, hs, gs, vs, ss = self._pballot_args(limbs_n, n, hs, gs, vs, ss, s_bits)
+        c = np.zeros((max(vs.shape[0], 1), 2 * limbs_n), dtype=np.uint64)
+        self._chk(self.L.pz_paillier_pballot_dev(self.ctx, limbs_n, vs.shape[0], vs.shape[1], m_bits, s_bits, _ptr(n), _ptr(hs), _ptr(gs),
+                                                 _ptr(vs), _ptr(ss), VP(d_steps), steps_cap, _ptr(c)), "pz_paillier_pballot_dev")
+        return c
+
     # the mix (DESIGN.md section 15.17): shuffle and re-randomise K = 2^d ciphertexts under one key
     @staticmethod
     def mix_route(perm) -> np.ndarray:
@@ -1071,6 +1105,40 @@ class Engine:
         self._chk(self.L.pz_sballot_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs, _ptr(inp), VP(d_steps),
                                                     VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts), n_adv_cols, max_rows,
                                                     lookup_rows, col_stride), "pz_sballot_expand_cols_dev")
+
+    # the packed ballot (circuit kind 11, pz.h pz_pballot_*): its shape is (count, slots, m_bits, s_limbs) and the key size alone
+    def pballot_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, slots: int, m_bits: int, s_limbs: int):
+        a = C.c_size_t()
+        l = C.c_size_t()
+        self._chk(self.L.pz_pballot_cells(limbs_n, limb_bits, lookup_bits, count, slots, m_bits, s_limbs, C.byref(a), C.byref(l)),
+                  "pz_pballot_cells")
+        return a.value, l.value
+
+    def pballot_public_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, slots: int, m_bits: int, s_limbs: int):
+        """stream indices of the exposed cells in statement order: n | hs | G_0 .. G_{K-1} | c_1 .. c_R | S_1 .. S_R (K >= 2)"""
+        out = np.zeros(limbs_n + 2 * limbs_n * (1 + max(slots, 1) + max(count, 1)) + max(count, 1), dtype=np.uint64)
+        npub = C.c_size_t()
+        self._chk(self.L.pz_pballot_public_cells(limbs_n, limb_bits, lookup_bits, count, slots, m_bits, s_limbs, _ptr(out), out.shape[0],
+                                                 C.byref(npub)), "pz_pballot_public_cells")
+        return out[: npub.value]
+
+    def pballot_expand_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, slots: int, m_bits: int, s_limbs: int, inputs,
+                           d_steps: int, d_modulus: int, d_advice: int, d_lookup: int = 0, rows: int = 0, col_stride: int = 0):
+        """inputs: host uint64 array n | hs | G_0 .. G_{K-1} | v_11 .. v_RK (one word each) | s_1 .. s_R | res_1 .. res_R; d_steps: the
+        R (2 m_bits K + 2 s_limbs limb_bits + K) records paillier_pballot_dev left; writes the circuit's cell stream, dense or cut into
+        columns"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        self._chk(self.L.pz_pballot_expand_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, slots, m_bits, s_limbs, _ptr(inp), VP(d_steps),
+                                               VP(d_modulus), VP(d_advice), VP(d_lookup), rows, col_stride), "pz_pballot_expand_dev")
+
+    def pballot_expand_cols_dev(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, slots: int, m_bits: int, s_limbs: int, inputs,
+                                d_steps: int, d_modulus: int, d_advice: int, d_lookup: int, d_col_starts: int, n_adv_cols: int, max_rows: int,
+                                lookup_rows: int, col_stride: int):
+        """the same with the advice cells in break-point columns (circuit_expand_cols_dev's conventions)"""
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1)
+        self._chk(self.L.pz_pballot_expand_cols_dev(self.ctx, limbs_n, limb_bits, lookup_bits, count, slots, m_bits, s_limbs, _ptr(inp),
+                                                    VP(d_steps), VP(d_modulus), VP(d_advice), VP(d_lookup), VP(d_col_starts), n_adv_cols,
+                                                    max_rows, lookup_rows, col_stride), "pz_pballot_expand_cols_dev")
 
     # the short-randomness mix (circuit kind 10, pz.h pz_smix_*): its shape is (count = 2^d, s_limbs) and the key size alone
     def smix_cells(self, limbs_n: int, limb_bits: int, lookup_bits: int, count: int, s_limbs: int):

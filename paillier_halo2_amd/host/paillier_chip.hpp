@@ -18,6 +18,7 @@
 //   (c^w and prod c_i^w_i: the scalar homomorphism)            PaillierChip::mul_scalar / weighted_tally, pz::paillier_wtally_test (15.8)
 //   (K ciphertexts of small values with a public sum)          PaillierChip::ballot, pz::paillier_ballot_test (15.10)
 //   (the same with short randomness, c = g^m hs^s)             PaillierChip::sballot, pz::paillier_sballot_test, pz::djn_generator (15.18)
+//   (K choices packed into ONE such ciphertext)                PaillierChip::pballot, pz::paillier_pballot_test, pz::pballot_bases, pz::unpack_tally (15.21)
 //   (K ciphertexts shuffled and re-randomised: a mixer's step) pz::benes_route (benes.hpp), PaillierChip::mix, pz::paillier_mix_test (15.17)
 //   (the same with short randomness, c' = c_perm hs^s)         PaillierChip::smix, pz::paillier_smix_test (15.20)
 //   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
@@ -631,6 +632,100 @@ class PaillierChip {  // paillier.rs:11-15
                 bit_blocks(i * per + 2 * (size_t)m_bits + 2 * (size_t)li * W, W);
             }
             if (fits && (fits = steps_of((i + 1) * per - 1, steps))) ctx.push_steps(steps, Wd, L, W, n2.value());   // the final block
+            out.push_back(AssignedBigUint<Fresh>(BigUint::from_limbs(cv.data() + i * wk, wk), L, W));
+        }
+        std::fill(rec.begin(), rec.end(), 0);
+        if (!fits) return R::Err(PZ_ERR_RANGE, "a step's integer does not fit the assigned limb count");
+        return R::Ok(out);
+    }
+
+    // The packed ballot: c_i = (prod_j G_j^v_ij) hs^s_i mod n^2 for R ciphertexts of K = gs.size() slots each
+    // under one key and the public slot bases G_j = g^(2^(j w)) mod n^2 (pz::pballot_bases).  n^2 hoisted once, load_zero; per ciphertext,
+    // per slot pow_mod(G_j, v_ij) over m_bits in-circuit bits as sballot's g-chain, then pow_mod(hs, s_i) as sballot, then the K fold
+    // blocks.  One pz_paillier_pballot call computes every record; the tape takes them in the CIRCUIT's order -- slot chains, hs-chain,
+    // folds -- which is the call's.  hs, the bases, the values' load_witness cells (vs[i][j]: ciphertext i, slot j), their sums and the
+    // s_i are assigned by the caller (paillier_pballot_test), in front of this.  The v_ij and s_i are the voter's secrets: the staged
+    // words are overwritten here.
+    Result<std::vector<AssignedBigUint<Fresh>>> pballot(Context& ctx, const AssignedBigUint<Fresh>& n, const AssignedBigUint<Fresh>& hs,
+                                                        const std::vector<AssignedBigUint<Fresh>>& gs,
+                                                        const std::vector<std::vector<AssignedWeight>>& vs,
+                                                        const std::vector<AssignedBigUint<Fresh>>& ss, unsigned m_bits) const {
+        using R = Result<std::vector<AssignedBigUint<Fresh>>>;
+        const size_t Rn = vs.size(), K = gs.size();
+        if (Rn < 1 || Rn != ss.size() || Rn > 1024) return R::Err(PZ_ERR_INVALID, "pballot: one s per ciphertext, 1 .. 1024 of them");
+        if (K < 1 || K > 64 || Rn * K > 1024) return R::Err(PZ_ERR_INVALID, "pballot: 1 .. 64 slots, at most 1024 values in all");
+        if (m_bits < 1 || m_bits > 64) return R::Err(PZ_ERR_INVALID, "pballot: m_bits outside 1 .. 64");
+        const unsigned s_limbs = ss[0].num_limbs(), W = biguint->limb_bits;
+        if (s_limbs < 1 || s_limbs > 2 * n.num_limbs()) return R::Err(PZ_ERR_INVALID, "pballot: an s of 1 .. 2 * n's limbs");
+        if (hs.num_limbs() != 2 * n.num_limbs()) return R::Err(PZ_ERR_INVALID, "pballot: hs is not assigned at full width");
+        for (const auto& gj : gs)
+            if (gj.num_limbs() != 2 * n.num_limbs()) return R::Err(PZ_ERR_INVALID, "pballot: a slot base is not assigned at full width");
+        for (const auto& row : vs)
+            if (row.size() != K) return R::Err(PZ_ERR_INVALID, "pballot: one value per slot in every ciphertext");
+        auto n2m = biguint->square(ctx, n);
+        if (!n2m.ok) return R::Err(n2m.err.status, n2m.err.msg);
+        RefreshAux aux = RefreshAux::new_(W, n.num_limbs(), n.num_limbs());
+        auto n2r = biguint->refresh(ctx, n2m.val, aux);
+        if (!n2r.ok) return R::Err(n2r.err.status, n2r.err.msg);
+        const AssignedBigUint<Fresh>& n2 = n2r.val;
+        (void)ctx.load_zero();
+        const unsigned L = n2.num_limbs(), Wd = n2.num_words(), wn = n.num_words(), wk = 2 * wn;   // K3 works on 2 * wn words
+        const unsigned s_bits = s_limbs * W, sw = (s_bits + 63) / 64;
+        std::vector<uint64_t> nv = n.words(), hv = hs.value().to_limbs(wk), gv, vv, sv;
+        for (const auto& gj : gs) {
+            std::vector<uint64_t> w = gj.value().to_limbs(wk);
+            gv.insert(gv.end(), w.begin(), w.end());
+        }
+        for (const auto& row : vs)
+            for (const AssignedWeight& v : row) vv.push_back(v.value);
+        for (const auto& s : ss) {
+            if (s.num_limbs() != s_limbs) return R::Err(PZ_ERR_INVALID, "pballot: the s_i are not assigned at one width");
+            std::vector<uint64_t> w = s.value().to_limbs(sw);
+            sv.insert(sv.end(), w.begin(), w.end());
+        }
+        const size_t per = 2 * (size_t)m_bits * K + 2 * (size_t)s_bits + K;
+        std::vector<uint64_t> rec(Rn * per * 4 * wk), cv(Rn * wk);
+        int rc = pz_paillier_pballot(ctx.raw(), wn, Rn, (uint32_t)K, m_bits, s_bits, nv.data(), hv.data(), gv.data(), vv.data(), sv.data(),
+                                     rec.data(), Rn * per, cv.data());
+        std::fill(vv.begin(), vv.end(), 0);
+        std::fill(sv.begin(), sv.end(), 0);
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_pballot: ") + pz_strerror(rc));
+        // the tape holds Wd words per integer (Wd < 2 * wn where limb_bits does not divide 64: the words above are zero)
+        auto steps_of = [&](size_t at, std::vector<uint64_t>& out) {
+            out.clear();
+            for (size_t f = at * 4; f < (at + 1) * 4; ++f) {
+                if (BigUint::from_limbs(rec.data() + f * wk, wk).bits() > (size_t)L * W) return false;
+                out.insert(out.end(), rec.begin() + f * wk, rec.begin() + f * wk + Wd);
+            }
+            return true;
+        };
+        std::vector<uint64_t> steps;
+        bool fits = true;
+        auto bit_blocks = [&](size_t first, unsigned nbits) {   // nbits x (mul_mod, select, square_mod) from record `first` on
+            for (unsigned j = 0; fits && j < nbits; ++j) {
+                if (!(fits = steps_of(first + 2 * j, steps))) break;
+                ctx.push_steps(steps, Wd, L, W, n2.value());
+                ctx.record_cells(Context::SELECT, L, 8 * (size_t)L);
+                if (!(fits = steps_of(first + 2 * j + 1, steps))) break;
+                ctx.push_steps(steps, Wd, L, W, n2.value());
+            }
+        };
+        std::vector<AssignedBigUint<Fresh>> out;
+        for (size_t i = 0; fits && i < Rn; ++i) {
+            for (size_t j = 0; fits && j < K; ++j) {
+                (void)ctx.load_constant_one();
+                (void)ctx.load_zero();
+                ctx.record_cells(Context::NUM_TO_BITS, 1, 7 * (size_t)m_bits - 2);
+                bit_blocks(i * per + 2 * (size_t)m_bits * j, m_bits);
+            }
+            (void)ctx.load_constant_one();
+            (void)ctx.load_zero();
+            for (unsigned li = 0; fits && li < s_limbs; ++li) {
+                ctx.record_cells(Context::NUM_TO_BITS, 1, 7 * (size_t)W - 2);
+                bit_blocks(i * per + 2 * (size_t)m_bits * K + 2 * (size_t)li * W, W);
+            }
+            for (size_t q = 0; fits && q < K; ++q)   // the folds
+                if ((fits = steps_of((i + 1) * per - K + q, steps))) ctx.push_steps(steps, Wd, L, W, n2.value());
             out.push_back(AssignedBigUint<Fresh>(BigUint::from_limbs(cv.data() + i * wk, wk), L, W));
         }
         std::fill(rec.begin(), rec.end(), 0);
@@ -1389,6 +1484,74 @@ inline Result<BigUint> djn_generator(Context& ctx, const PaillierChip& chip, con
     return R::Ok(p.val.h);
 }
 
+// the packed ballot's driver: assign n, hs and the K slot bases at full width, load_witness every v_ij (ciphertext-major), for K >= 2 one
+// sum per ciphertext, assign every s_i on s_limbs limbs, pballot, then per ciphertext assign res_i and assert_equal_fresh
+struct PaillierPBallotInput {
+    unsigned limb_bits, enc_bits, m_bits, s_limbs;
+    BigUint n, hs;
+    std::vector<BigUint> gs;                   // G_0 .. G_{K-1}
+    std::vector<std::vector<uint64_t>> vs;     // [R][K]
+    std::vector<BigUint> ss, res;
+};
+inline void paillier_pballot_test(Context& ctx, const RangeChip& range, const PaillierPBallotInput& input) {
+    BigUintChip biguint_chip = BigUintChip::construct(&range, input.limb_bits);
+    PaillierChip paillier_chip = PaillierChip::construct(&biguint_chip, input.enc_bits);
+    auto n_assigned = biguint_chip.assign_integer(ctx, input.n, input.enc_bits).unwrap();
+    auto hs_assigned = biguint_chip.assign_integer(ctx, input.hs, input.enc_bits * 2).unwrap();
+    std::vector<AssignedBigUint<Fresh>> gs;
+    for (const BigUint& gj : input.gs) gs.push_back(biguint_chip.assign_integer(ctx, gj, input.enc_bits * 2).unwrap());
+    std::vector<std::vector<AssignedWeight>> vs;
+    for (const auto& row : input.vs) {
+        vs.emplace_back();
+        for (uint64_t v : row) vs.back().push_back(AssignedWeight{v, ctx.load_witness()});
+    }
+    if (gs.size() >= 2)
+        for (size_t i = 0; i < vs.size(); ++i) ctx.sum(gs.size());
+    std::vector<AssignedBigUint<Fresh>> ss;
+    for (const BigUint& s : input.ss) ss.push_back(biguint_chip.assign_integer(ctx, s, input.s_limbs * input.limb_bits).unwrap());
+    auto cts = paillier_chip.pballot(ctx, n_assigned, hs_assigned, gs, vs, ss, input.m_bits).unwrap();
+    if (cts.size() != input.res.size()) throw std::runtime_error("paillier_pballot_test: one expected ciphertext per row of values");
+    for (size_t i = 0; i < cts.size(); ++i) {
+        auto res_assigned = biguint_chip.assign_integer(ctx, input.res[i], input.enc_bits * 2).unwrap();
+        if (cts[i].value() != res_assigned.value()) throw std::runtime_error("assertion failed: `(left == right)` (paillier_pballot_test)");
+        biguint_chip.assert_equal_fresh(ctx, cts[i], res_assigned).unwrap();
+    }
+}
+
+// the public slot bases of a packed ballot (keys.py::pballot_bases is the same in Python): G_j = g^(2^(j w)) mod
+// n^2 for j = 0 .. slots - 1, read from the squaring records of ONE pz_paillier_trace of g^(2^((slots - 1) w)) -- every bit of that
+// exponent below its top one is clear, so record t is the square whose remainder is g^(2^(t + 1)) and the remainder of record j w - 1
+// is G_j.  Refuses 2^(slots w) > n: the packed plaintext must stay below n (PZ_ERR_INVALID).
+inline Result<std::vector<BigUint>> pballot_bases(Context& ctx, const BigUint& n, const BigUint& g, unsigned slots, unsigned slot_bits) {
+    using R = Result<std::vector<BigUint>>;
+    if (slots < 1 || slot_bits < 1 || n < BigUint(15) || !n.bit(0)) return R::Err(PZ_ERR_INVALID, "pballot_bases: slots, slot_bits >= 1 and an odd modulus");
+    if (n < (BigUint(1) << ((size_t)slots * slot_bits))) return R::Err(PZ_ERR_INVALID, "pballot_bases: 2^(slots * slot_bits) exceeds n");
+    const BigUint n2 = n * n;
+    if (g < BigUint(1) || !(g < n2)) return R::Err(PZ_ERR_INVALID, "pballot_bases: g is in [1, n^2)");
+    std::vector<BigUint> out{g};
+    const size_t top = (size_t)(slots - 1) * slot_bits;
+    if (top == 0) return R::Ok(out);
+    const unsigned wn = (unsigned)((n.bits() + 63) / 64), wk = 2 * wn, el = (unsigned)(top / 64 + 1);
+    std::vector<uint64_t> nv = n2.to_limbs(wk), gv = g.to_limbs(wk), ev = (BigUint(1) << top).to_limbs(el), res(wk);
+    std::vector<uint64_t> steps((top + 2) * 4 * wk);
+    size_t ns = top + 2;
+    int rc = pz_paillier_trace(ctx.raw(), wk, nv.data(), gv.data(), ev.data(), el, steps.data(), &ns, res.data());
+    if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_trace: ") + pz_strerror(rc));
+    if (ns != top + 2) return R::Err(PZ_ERR_INTERNAL, "pballot_bases: the trace of a power of two has one record per bit and one product");
+    for (unsigned j = 1; j < slots; ++j) out.push_back(BigUint::from_limbs(steps.data() + (((size_t)j * slot_bits - 1) * 4 + 3) * wk, wk));
+    return R::Ok(out);
+}
+
+// the `slots` counts of a decrypted packed total: count j is bits j w .. (j + 1) w of M (keys.py::unpack_tally).  Refuses an M of more
+// than slots * slot_bits bits.
+inline Result<std::vector<BigUint>> unpack_tally(const BigUint& M, unsigned slots, unsigned slot_bits) {
+    using R = Result<std::vector<BigUint>>;
+    if (slots < 1 || slot_bits < 1 || M.bits() > (size_t)slots * slot_bits) return R::Err(PZ_ERR_INVALID, "unpack_tally: M has more than slots * slot_bits bits");
+    std::vector<BigUint> out;
+    for (unsigned j = 0; j < slots; ++j) out.push_back((M >> ((size_t)j * slot_bits)).low_bits(slot_bits));
+    return R::Ok(out);
+}
+
 // the mix's driver: assign n, every c_j at full width, every r_i, mix, then per output assign res_i and assert_equal_fresh
 struct PaillierMixInput {
     unsigned limb_bits, enc_bits;
@@ -1630,6 +1793,51 @@ inline int synthesize_sballot_circuit(Context& ctx, unsigned enc_bits, unsigned 
     std::fill(rec.begin(), rec.end(), 0);
     if (rc == PZ_OK)
         rc = pz_sballot_expand_dev(ctx.raw(), Ln, W, ctx.lookup_bits(), K, m_bits, s_limbs, in.data(), d_work, d_modulus, d_advice, d_lookup, 0, 0);
+    std::fill(in.begin(), in.end(), 0);
+    return rc;
+}
+
+// the packed ballot's tape (paillier_pballot_test) expanded on the device: circuit kind 11, inputs n | hs | G_0 .. G_{K-1} | v_11 .. v_RK |
+// s_1 .. s_R | res_1 .. res_R.  The records go up with fields of 2 * ceil(Ln W / 64) words, as pz_paillier_pballot_dev leaves them.
+// d_work: device memory for them, R (2 m_bits K + 2 s_limbs W + K) 4 * 2 wn words.
+inline int synthesize_pballot_circuit(Context& ctx, unsigned enc_bits, unsigned m_bits, unsigned s_limbs, const BigUint& n, const BigUint& hs,
+                                      const std::vector<BigUint>& gs, const std::vector<std::vector<uint64_t>>& vs,
+                                      const std::vector<BigUint>& ss, const std::vector<BigUint>& res, uint64_t* d_work, uint64_t* d_modulus,
+                                      uint64_t* d_advice, uint64_t* d_lookup) {
+    const unsigned W = ctx.limb_bits(), Ln = enc_bits / W, wn = (Ln * W + 63) / 64, wr = (2 * Ln * W + 63) / 64, wk = 2 * wn;
+    const unsigned sw = (s_limbs * W + 63) / 64;
+    const size_t Rn = vs.size(), K = gs.size(), per = 2 * (size_t)m_bits * K + 2 * (size_t)s_limbs * W + K;
+    if (Rn < 1 || K < 1 || ss.size() != Rn || res.size() != Rn || ctx.n_steps() != Rn * per || ctx.words() != wr) return PZ_ERR_INVALID;
+    size_t a = 0, l = 0;
+    int rc = pz_pballot_cells(Ln, W, ctx.lookup_bits(), Rn, (uint32_t)K, m_bits, s_limbs, &a, &l);
+    if (rc != PZ_OK) return rc;
+    if (a != ctx.advice_cells() || l != ctx.lookup_cells()) return PZ_ERR_INVALID;   // the tape is not this driver's
+    std::vector<uint64_t> in = n.to_limbs(wn), w = hs.to_limbs(wr);
+    in.insert(in.end(), w.begin(), w.end());
+    for (const BigUint& gj : gs) {
+        w = gj.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    for (const auto& row : vs) {
+        if (row.size() != K) return PZ_ERR_INVALID;
+        in.insert(in.end(), row.begin(), row.end());
+    }
+    for (const BigUint& s : ss) {
+        w = s.to_limbs(sw);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    for (const BigUint& c : res) {
+        w = c.to_limbs(wr);
+        in.insert(in.end(), w.begin(), w.end());
+    }
+    const std::vector<uint64_t>& tp = ctx.tape();
+    std::vector<uint64_t> rec(Rn * per * 4 * wk, 0);
+    for (size_t f = 0; f < Rn * per * 4; ++f) std::copy(tp.begin() + f * wr, tp.begin() + (f + 1) * wr, rec.begin() + f * wk);
+    rc = pz_upload(ctx.raw(), d_work, rec.data(), rec.size() * 8);
+    std::fill(rec.begin(), rec.end(), 0);
+    if (rc == PZ_OK)
+        rc = pz_pballot_expand_dev(ctx.raw(), Ln, W, ctx.lookup_bits(), Rn, (uint32_t)K, m_bits, s_limbs, in.data(), d_work, d_modulus, d_advice,
+                                   d_lookup, 0, 0);
     std::fill(in.begin(), in.end(), 0);
     return rc;
 }

@@ -7,13 +7,14 @@ section 15.16), which runs on the device: Engine.is_prime and Engine.prime_searc
 
 The library derives mu and g^-1 on the device and validates the key there; the one value it does not derive is d = n^-1 mod lambda,
 the exponent that recovers an encryption's randomness: it is the caller's, and this helper computes it.
-djn_generator makes the element hs that short-randomness ("DJN mode") encryption adds to a public key (section 15.18)."""
+djn_generator makes the element hs that short-randomness ("DJN mode") encryption adds to a public key (section 15.18).
+pack_choices, unpack_tally, pballot_capacity and pballot_bases serve the packed ballot, K choices in one ciphertext (section 15.21)."""
 from __future__ import annotations
 
 import math
 import secrets
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 
 def secret_from_primes(p: int, q: int, g: Optional[int] = None) -> Tuple[int, int, int, int]:
@@ -216,6 +217,66 @@ def djn_generator(engine, n: int, rand: Callable[[int], int] = secrets.randbelow
     limbs = (n.bit_length() + 63) // 64
     res, _, _ = engine.paillier_trace(2 * limbs, _words(n * n, 2 * limbs), _words(h, 2 * limbs), _words(n, limbs), limbs, want_steps=False)
     return sum(int(w) << (64 * i) for i, w in enumerate(res.tolist()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# packed plaintexts: K choices in one ciphertext, M = sum_j v_j 2^(j w)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _slot_shape(slots: int, slot_bits: int) -> None:
+    for x in (slots, slot_bits):
+        if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+            raise ValueError("slots and slot_bits are positive integers")
+
+
+def pack_choices(values: Sequence[int], slot_bits: int) -> int:
+    """M = sum_j v_j 2^(j slot_bits): slot j of the packed plaintext holds values[j].  Every value is below 2^slot_bits."""
+    _slot_shape(max(len(values), 1), slot_bits)
+    if len(values) < 1 or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < (1 << slot_bits) for v in values):
+        raise ValueError("a packed plaintext has at least one slot and every value is in [0, 2^slot_bits)")
+    return sum(v << (j * slot_bits) for j, v in enumerate(values))
+
+
+def unpack_tally(M: int, slots: int, slot_bits: int) -> List[int]:
+    """the `slots` counts of a decrypted packed total: count j is bits j slot_bits .. (j + 1) slot_bits of M.  Refuses an M of more than
+    slots * slot_bits bits: no product of packed ballots within pballot_capacity decrypts to one."""
+    _slot_shape(slots, slot_bits)
+    if isinstance(M, bool) or not isinstance(M, int) or M < 0 or M >> (slots * slot_bits):
+        raise ValueError("a packed total is in [0, 2^(slots slot_bits))")
+    mask = (1 << slot_bits) - 1
+    return [(M >> (j * slot_bits)) & mask for j in range(slots)]
+
+
+def pballot_capacity(slot_bits: int, m_bits: int) -> int:
+    """how many packed ballots whose slot values are below 2^m_bits one slot of slot_bits bits holds before it carries into the next:
+    floor((2^slot_bits - 1) / (2^m_bits - 1)).  The tally of more ballots than this is not the per-slot sums."""
+    _slot_shape(m_bits, slot_bits)
+    if m_bits > slot_bits:
+        raise ValueError("a slot value of m_bits bits does not fit a slot of slot_bits bits")
+    return ((1 << slot_bits) - 1) // ((1 << m_bits) - 1)
+
+
+def pballot_bases(engine, n: int, g: int, slots: int, slot_bits: int) -> List[int]:
+    """the public slot bases G_j = g^(2^(j slot_bits)) mod n^2, j = 0 .. slots - 1, of a packed ballot (Engine.paillier_pballot): read
+    from the squaring records of ONE Engine.paillier_trace of g^(2^((slots - 1) slot_bits)) -- bit t of that exponent below its top
+    one is clear, so record t is the square whose remainder is g^(2^(t + 1)), and the remainder of record j slot_bits - 1 is G_j.
+    Refuses 2^(slots slot_bits) > n: the packed plaintext must stay below n."""
+    _slot_shape(slots, slot_bits)
+    if isinstance(n, bool) or not isinstance(n, int) or n < 15 or n % 2 == 0:
+        raise ValueError("n must be an odd modulus")
+    if (1 << (slots * slot_bits)) > n:
+        raise ValueError("the packed plaintext of slots * slot_bits bits must stay below n")
+    if not 0 < int(g) < n * n:
+        raise ValueError("g is in [1, n^2)")
+    top = (slots - 1) * slot_bits
+    if top == 0:
+        return [int(g)]
+    limbs = (n.bit_length() + 63) // 64
+    e_limbs = top // 64 + 1
+    _, steps, ns = engine.paillier_trace(2 * limbs, _words(n * n, 2 * limbs), _words(int(g), 2 * limbs), _words(1 << top, e_limbs), e_limbs)
+    if ns != top + 2:
+        raise RuntimeError("the trace of a power of two has one record per bit and one product")
+    word = lambda row: sum(int(w) << (64 * i) for i, w in enumerate(row.tolist()))
+    return [int(g)] + [word(steps[j * slot_bits - 1, 3]) for j in range(1, slots)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -210,11 +210,12 @@ BALLOT_MAX = 1024       # ciphertexts of one ballot (pz.h pz_paillier_ballot)
 BALLOT_MAX_BITS = 64    # width of a ballot entry's message: one 64-bit word
 PARTIAL_MAX = 1024      # ciphertexts one trustee opens in one proof (pz.h pz_paillier_partial)
 MIX_MAX = 1024          # ciphertexts of one mix, a power of two (pz.h pz_paillier_mix)
+PBALLOT_MAX_SLOTS = 64  # slots of one packed ballot (pz.h pz_paillier_pballot); count * slots <= BALLOT_MAX
 
 
 def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_steps_g: int = 0, n_steps_r: int = 0,
                   count: int | None = None, w_bits: int | None = None, m_bits: int | None = None,
-                  s_limbs: int | None = None) -> CircuitCells:
+                  s_limbs: int | None = None, slots: int | None = None) -> CircuitCells:
     """The whole cell stream of paillier_enc_test (bench.rs:33-75, kind 'encrypt') or paillier_enc_add_test
     (bench.rs:77-117, kind 'add'), operation by operation in call order -- what pz_circuit_expand_dev writes.
     kind 'tally' (count = B ciphertexts): assign n, assign c_1 .. c_B at full width, square + refresh once, the B - 1 blocks of
@@ -243,7 +244,12 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
     kind 'smix' (circuit kind 10; count = K = 2^d ciphertexts, s_limbs limbs per exponent s_i): assign n, assign
     hs and c_1 .. c_K at full width, assign s_1 .. s_K (s_limbs limbs each), square + refresh once, load_zero, the network as 'mix', per
     output [1, 0], pow_mod(hs, s_i) as 'sballot' emits its hs-chain and the final mul_mod(d_i, hss_i), then per output assign res_i and
-    assert_equal_fresh.  No step count enters: the shape is (K, s_limbs) and the key size."""
+    assert_equal_fresh.  No step count enters: the shape is (K, s_limbs) and the key size.
+    kind 'pballot' (circuit kind 11; count = R ciphertexts, slots = K values of m_bits = b bits in each, s_limbs
+    limbs per exponent s_i): assign n, assign hs and the K slot bases G_j at full width, load_witness of the R K values, for K >= 2 one
+    FlexGate::sum per ciphertext, assign s_1 .. s_R (s_limbs limbs each), square + refresh once, load_zero, per ciphertext the K slot
+    chains ([1, 0], num_to_bits, b bit blocks each, as 'ballot's g-chain), pow_mod(hs, s_i) as 'sballot' and the K fold blocks, then
+    per ciphertext assign res_i and assert_equal_fresh.  The shape is (R, K, b, s_limbs) and the key size."""
     Ln, L = limbs_n, 2 * limbs_n
     if kind == "decrypt":
         kind = "encrypt_uniform"
@@ -292,14 +298,27 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
             raise ValueError(f"a short-randomness mix's exponent has s_limbs = 1 .. {L} limbs, not {s_limbs}")
         if n_steps_g or n_steps_r not in (0, 2 * s_limbs * limb_bits):
             raise ValueError("a short-randomness mix has no g-chain and 2 * s_limbs * limb_bits steps of one hs-chain")
+    elif kind == "pballot":
+        if count is None or not 1 <= count <= BALLOT_MAX:
+            raise ValueError(f"a packed ballot takes count = 1 .. {BALLOT_MAX} ciphertexts, not {count}")
+        if slots is None or not 1 <= slots <= PBALLOT_MAX_SLOTS or count * slots > BALLOT_MAX:
+            raise ValueError(f"a packed ballot has slots = 1 .. {PBALLOT_MAX_SLOTS} with count * slots <= {BALLOT_MAX}, not {slots}")
+        if m_bits is None or not 1 <= m_bits <= BALLOT_MAX_BITS:
+            raise ValueError(f"a slot value has m_bits = 1 .. {BALLOT_MAX_BITS} bits, not {m_bits}")
+        if s_limbs is None or not 1 <= s_limbs <= L:
+            raise ValueError(f"a packed ballot's exponent has s_limbs = 1 .. {L} limbs, not {s_limbs}")
+        if n_steps_g not in (0, 2 * m_bits) or n_steps_r not in (0, 2 * s_limbs * limb_bits):
+            raise ValueError("a packed ballot has 2 * m_bits steps per slot chain and 2 * s_limbs * limb_bits hs-chain steps")
     elif count is not None:
-        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot' and 'smix'")
+        raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot', 'smix' and 'pballot'")
     if w_bits is not None and kind != "wtally":
         raise ValueError("w_bits belongs to kind 'wtally'")
-    if m_bits is not None and kind not in ("ballot", "sballot"):
-        raise ValueError("m_bits belongs to kinds 'ballot' and 'sballot'")
-    if s_limbs is not None and kind not in ("sballot", "smix"):
-        raise ValueError("s_limbs belongs to kinds 'sballot' and 'smix'")
+    if m_bits is not None and kind not in ("ballot", "sballot", "pballot"):
+        raise ValueError("m_bits belongs to kinds 'ballot', 'sballot' and 'pballot'")
+    if s_limbs is not None and kind not in ("sballot", "smix", "pballot"):
+        raise ValueError("s_limbs belongs to kinds 'sballot', 'smix' and 'pballot'")
+    if slots is not None and kind != "pballot":
+        raise ValueError("slots belongs to kind 'pballot'")
     mm = mul_mod_cells(L, limb_bits, lookup_bits)
     seg, a, l = {}, 0, 0
 
@@ -344,6 +363,16 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         put("messages", count)
         if count >= 2:
             put("sum", 1 + 3 * (count - 1))
+        sa, sl = assign_cells(s_limbs, limb_bits, lookup_bits)
+        put("assign_ss", count * sa, count * sl)
+    elif kind == "pballot":
+        ca, cl = assign_cells(L, limb_bits, lookup_bits)
+        put("assign_n", *assign_cells(Ln, limb_bits, lookup_bits))
+        put("assign_hs", ca, cl)
+        put("assign_bases", slots * ca, slots * cl)
+        put("values", count * slots)
+        if slots >= 2:
+            put("sums", count * (1 + 3 * (slots - 1)))
         sa, sl = assign_cells(s_limbs, limb_bits, lookup_bits)
         put("assign_ss", count * sa, count * sl)
     elif kind in ("tally", "wtally"):
@@ -391,6 +420,18 @@ def circuit_cells(kind: str, limbs_n: int, limb_bits: int, lookup_bits: int, n_s
         steps = 2 * m_bits + 2 * s_bits + 1
         put("entries", count * (2 + 7 * m_bits - 2 + 2 + s_limbs * (7 * limb_bits - 2) + (m_bits + s_bits) * 8 * L + steps * mm.advice),
             count * steps * mm.lookup)
+        ra, rl = assign_cells(L, limb_bits, lookup_bits)
+        put("results", count * (ra + assert_equal_cells(L)), count * rl)
+        seg["end"] = (a, l)
+        return CircuitCells(a, l, seg)
+    if kind == "pballot":
+        # per ciphertext: K slot chains ([1, 0], num_to_bits of 7 b - 2 cells, b blocks of mul_mod + select + square_mod); [1, 0], then per
+        # limb of s_i num_to_bits (7 W - 2 cells) and W such blocks; the K fold blocks.  Then per ciphertext assign res_i and
+        # assert_equal_fresh
+        s_bits = s_limbs * limb_bits
+        steps = 2 * m_bits * slots + 2 * s_bits + slots
+        put("entries", count * (slots * (2 + 7 * m_bits - 2) + 2 + s_limbs * (7 * limb_bits - 2) + (slots * m_bits + s_bits) * 8 * L
+                                + steps * mm.advice), count * steps * mm.lookup)
         ra, rl = assign_cells(L, limb_bits, lookup_bits)
         put("results", count * (ra + assert_equal_cells(L)), count * rl)
         seg["end"] = (a, l)

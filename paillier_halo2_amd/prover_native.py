@@ -190,24 +190,29 @@ class NativeStructure:
     exp_r -- one structure serves every mixer of that key.  kind "sballot" (pz_circuit_structure_sballot_dev): count short-randomness
     ballots of m_bits-bit messages with exponents of s_limbs limbs; no exponent is taken -- one structure serves every key of a size.
     kind "smix" (pz_circuit_structure_smix_dev): count = 2^d ciphertexts shuffled and re-randomised with hs^s_i, exponents of s_limbs
-    limbs; no exponent is taken -- one structure serves every mixer of every election of a size."""
+    limbs; no exponent is taken -- one structure serves every mixer of every election of a size.  kind "pballot"
+    (pz_circuit_structure_pballot_dev): count packed ballots of `slots` m_bits-bit values each with exponents of s_limbs limbs; neither
+    an exponent nor the slot width is taken -- one structure serves every election of a size."""
 
     KINDS = {"encrypt": 0, "add": 1, "encrypt_uniform": 2, "tally": 3, "wtally": 4, "decrypt": 5, "ballot": 6, "partial": 7, "mix": 8,
-             "sballot": 9, "smix": 10}
+             "sballot": 9, "smix": 10, "pballot": 11}
 
     def __init__(self, eng: Engine, kind: str, enc_bits: int, limb_bits: int, lookup_bits: int, k: int, exp_g: int = 0, exp_r: int = 0,
                  minimum_rows: int = 20, blinding_factors: int = 6, expose: bool = False, count: Optional[int] = None,
-                 w_bits: Optional[int] = None, m_bits: Optional[int] = None, s_limbs: Optional[int] = None):
+                 w_bits: Optional[int] = None, m_bits: Optional[int] = None, s_limbs: Optional[int] = None,
+                 slots: Optional[int] = None):
         """expose: add the instance column (pz_structure_expose): n, g and the ciphertext(s) become the statement (tally: n, the c_i and
         their product); the maps then have m = n_adv + n_lk + 2 columns"""
-        if (kind in ("tally", "wtally", "ballot", "partial", "mix", "sballot", "smix")) != (count is not None):
-            raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot' and 'smix', which need it")
+        if (kind in ("tally", "wtally", "ballot", "partial", "mix", "sballot", "smix", "pballot")) != (count is not None):
+            raise ValueError("count belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot', 'smix' and 'pballot', which need it")
         if (kind == "wtally") != (w_bits is not None):
             raise ValueError("w_bits belongs to kind 'wtally', which needs it")
-        if (kind in ("ballot", "sballot")) != (m_bits is not None):
-            raise ValueError("m_bits belongs to kinds 'ballot' and 'sballot', which need it")
-        if (kind in ("sballot", "smix")) != (s_limbs is not None):
-            raise ValueError("s_limbs belongs to kinds 'sballot' and 'smix', which need it")
+        if (kind in ("ballot", "sballot", "pballot")) != (m_bits is not None):
+            raise ValueError("m_bits belongs to kinds 'ballot', 'sballot' and 'pballot', which need it")
+        if (kind in ("sballot", "smix", "pballot")) != (s_limbs is not None):
+            raise ValueError("s_limbs belongs to kinds 'sballot', 'smix' and 'pballot', which need it")
+        if (kind == "pballot") != (slots is not None):
+            raise ValueError("slots belongs to kind 'pballot', which needs it")
         self.eng, self.k, self.lookup_bits, self.blinding_factors, self.minimum_rows = eng, k, lookup_bits, blinding_factors, minimum_rows
         Ln = enc_bits // limb_bits
         ew = -(-Ln * limb_bits // 64)
@@ -228,6 +233,10 @@ class NativeStructure:
         elif kind == "smix":
             eng._chk(eng.L.pz_circuit_structure_smix_dev(eng.ctx, Ln, limb_bits, lookup_bits, k, int(count), int(s_limbs), minimum_rows,
                                                          blinding_factors, C.byref(h)), "pz_circuit_structure_smix_dev")
+        elif kind == "pballot":
+            eng._chk(eng.L.pz_circuit_structure_pballot_dev(eng.ctx, Ln, limb_bits, lookup_bits, k, int(count), int(slots), int(m_bits),
+                                                            int(s_limbs), minimum_rows, blinding_factors, C.byref(h)),
+                     "pz_circuit_structure_pballot_dev")
         elif kind == "sballot":
             eng._chk(eng.L.pz_circuit_structure_sballot_dev(eng.ctx, Ln, limb_bits, lookup_bits, k, int(count), int(m_bits), int(s_limbs),
                                                             minimum_rows, blinding_factors, C.byref(h)), "pz_circuit_structure_sballot_dev")

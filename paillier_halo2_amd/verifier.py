@@ -180,7 +180,9 @@ def record_seed(prefix: str) -> bytes:
 def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] = None, c1: Optional[int] = None, c2: Optional[int] = None, *,
                   enc_bits: int, limb_bits: int, cts: Optional[Sequence[int]] = None, weights: Optional[Sequence[int]] = None,
                   m: Optional[int] = None, total: Optional[int] = None, v: Optional[int] = None, h: Optional[int] = None,
-                  partials: Optional[Sequence[int]] = None, mixed: Optional[Sequence[int]] = None, hs: Optional[int] = None) -> List[int]:
+                  partials: Optional[Sequence[int]] = None, mixed: Optional[Sequence[int]] = None, hs: Optional[int] = None,
+                  slots: Optional[int] = None, slot_bits: Optional[int] = None, m_bits: Optional[int] = None,
+                  totals: Optional[Sequence[int]] = None) -> List[int]:
     """the statement of a circuit with the instance column, in the column's row order: little-endian limbs of limb_bits,
     n | g | c (kind "encrypt" / "encrypt_uniform": c = g^m r^n mod n^2) or n | g | c1 | c2 | c ("add": c = c1 c2 mod n^2); n, g, c1, c2 have
     enc_bits / limb_bits limbs, c twice as many.  (The add circuit's c1 and c2 are its enc_bits-wide inputs x and y.)
@@ -213,7 +215,14 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
     key (n, hs)": there are a permutation pi and s_i below 2^s_bits with c'_i = c_pi(i) hs^s_i mod n^2.  K is a power of two (1 ..
     1024); lists of different lengths are refused, and so are hs = 0 (every output would be 0), an hs >= n^2, any c_j or c'_i >= n^2 and
     any c'_i = 0.  No g and no single result c.  c'_i holds what c_pi(i) holds only if hs is an n-th residue: that is the key
-    authority's to show, not this statement's."""
+    authority's to show, not this statement's.
+    kind "pballot": n | hs | G_0 | .. | G_{K-1} | c_1 | .. | c_R | S_1 | .. | S_R -- "every c_i of cts is (prod_j G_j^v_ij) hs^s_i mod n^2
+    with every v_ij below 2^m_bits, s_i below 2^s_bits and sum_j v_ij = S_i = totals[i]", i.e. c_i = g^M_i hs^s_i with the packed
+    plaintext M_i = sum_j v_ij 2^(j w), K = slots, w = slot_bits.  The slot bases G_j = g^(2^(j w)) mod n^2 are DERIVED HERE from (n, g,
+    K, w) in Python integers: a statement cannot name bases of its own.  Refused: 2^(K w) > n (a packed plaintext would wrap), m_bits >
+    slot_bits (a slot value would reach into the next slot), hs = 0, an hs >= n^2, any c_i >= n^2, totals given with K = 1, totals
+    missing with K >= 2 or of another length than cts.  Each S_i is ONE field value.  No single result c; that hs is an n-th residue
+    is the key authority's to show."""
     Ln = enc_bits // limb_bits
     mask = (1 << limb_bits) - 1
     limbs = lambda v, cnt: [(int(v) >> (limb_bits * i)) & mask for i in range(cnt)]
@@ -297,13 +306,38 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
         if any(int(x) == 0 for x in mixed):
             raise ValueError("an output of a mix is not 0")
         parts = [(n, Ln), (hs, 2 * Ln)] + [(ci, 2 * Ln) for ci in cts] + [(ci, 2 * Ln) for ci in mixed]
+    elif kind == "pballot":
+        if cts is None or len(cts) < 1 or g is None or hs is None or c is not None or total is not None:
+            raise ValueError("the pballot statement names n, g, hs and its ciphertexts cts = [c_1 .. c_R], R >= 1, and neither c nor total")
+        for x in (slots, slot_bits, m_bits):
+            if x is None or isinstance(x, bool) or not isinstance(x, int) or x < 1:
+                raise ValueError("the pballot statement names slots, slot_bits and m_bits, positive integers")
+        if (1 << (slots * slot_bits)) > int(n):
+            raise ValueError("the packed plaintext of slots * slot_bits bits must stay below n")
+        if m_bits > slot_bits:
+            raise ValueError("a slot value of m_bits bits does not fit a slot of slot_bits bits")
+        if not 0 < int(hs) < int(n) * int(n):
+            raise ValueError("hs is neither 0 nor n^2 or more")
+        if any(not 0 <= int(ci) < int(n) * int(n) for ci in cts):
+            raise ValueError("a ballot's ciphertext is below n^2")
+        if (totals is not None) != (slots >= 2):
+            raise ValueError("the pballot statement carries the sums `totals` exactly when it has two or more slots")
+        if totals is not None and len(totals) != len(cts):
+            raise ValueError("the pballot statement has one total per ciphertext")
+        if totals is not None and any(int(t) < 0 or int(t) >= consts.FR_R for t in totals):
+            raise ValueError("a total is one field value")
+        n2 = int(n) * int(n)
+        parts = [(n, Ln), (hs, 2 * Ln)] + [(pow(int(g), 1 << (j * slot_bits), n2), 2 * Ln) for j in range(slots)]
+        parts += [(ci, 2 * Ln) for ci in cts]
     else:
-        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt, ballot, partial, mix, sballot or smix")
-    if hs is not None and kind not in ("sballot", "smix"):
-        raise ValueError("hs belongs to kinds 'sballot' and 'smix'")
+        raise ValueError("kind must be encrypt, add, encrypt_uniform, tally, wtally, decrypt, ballot, partial, mix, sballot, smix or pballot")
+    if (slots is not None or slot_bits is not None or m_bits is not None or totals is not None) and kind != "pballot":
+        raise ValueError("slots, slot_bits, m_bits and totals belong to kind 'pballot'")
+    if hs is not None and kind not in ("sballot", "smix", "pballot"):
+        raise ValueError("hs belongs to kinds 'sballot', 'smix' and 'pballot'")
     if mixed is not None and kind not in ("mix", "smix"):
         raise ValueError("mixed belongs to kinds 'mix' and 'smix'")
-    if c is None and kind not in ("ballot", "partial", "mix", "sballot", "smix"):
+    if c is None and kind not in ("ballot", "partial", "mix", "sballot", "smix", "pballot"):
         raise ValueError("the statement names its result c")
     if (v is not None or h is not None or partials is not None) and kind != "partial":
         raise ValueError("v, h and partials belong to kind 'partial'")
@@ -311,8 +345,8 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
         raise ValueError("total belongs to kinds 'ballot' and 'sballot'")
     if m is not None and kind != "decrypt":
         raise ValueError("m belongs to kind 'decrypt'")
-    if cts is not None and kind not in ("tally", "wtally", "ballot", "partial", "mix", "sballot", "smix"):
-        raise ValueError("cts belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot' and 'smix'")
+    if cts is not None and kind not in ("tally", "wtally", "ballot", "partial", "mix", "sballot", "smix", "pballot"):
+        raise ValueError("cts belongs to kinds 'tally', 'wtally', 'ballot', 'partial', 'mix', 'sballot', 'smix' and 'pballot'")
     if weights is not None and kind != "wtally":
         raise ValueError("weights belongs to kind 'wtally'")
     for v, cnt in parts:
@@ -323,6 +357,8 @@ def public_inputs(kind: str, n: int, g: Optional[int] = None, c: Optional[int] =
         out[-2 * Ln:-2 * Ln] = [int(v) for v in weights]
     if total is not None:
         out.append(int(total))
+    if totals is not None:
+        out += [int(t) for t in totals]
     return out
 
 

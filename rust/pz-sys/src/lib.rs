@@ -123,6 +123,15 @@ extern "C" {
     pub fn pz_paillier_sballot_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, m_bits: u32, s_bits: u32, n: *const u64, g: *const u64,
                                    hs: *const u64, ms: *const u64, ss: *const u64, d_steps_out: *mut u64, steps_cap: usize,
                                    c_out: *mut u64) -> c_int;
+    // the packed ballot: c_i = (prod_j G_j^v_ij) hs^s_i mod n^2 for count ciphertexts of `slots` values of
+    // m_bits bits under the public slot bases gs = G_0 .. G_{slots-1} (2 * limbs_n words each) -- 2 * m_bits * slots + 2 * s_bits + slots
+    // records per entry, ciphertext-major; vs: one word per value, ciphertext-major.  The values and the s_i are the voter's secrets.
+    pub fn pz_paillier_pballot(ctx: *mut pz_ctx, limbs_n: u32, count: usize, slots: u32, m_bits: u32, s_bits: u32, n: *const u64,
+                               hs: *const u64, gs: *const u64, vs: *const u64, ss: *const u64, steps_out: *mut u64, steps_cap: usize,
+                               c_out: *mut u64) -> c_int;
+    pub fn pz_paillier_pballot_dev(ctx: *mut pz_ctx, limbs_n: u32, count: usize, slots: u32, m_bits: u32, s_bits: u32, n: *const u64,
+                                   hs: *const u64, gs: *const u64, vs: *const u64, ss: *const u64, d_steps_out: *mut u64,
+                                   steps_cap: usize, c_out: *mut u64) -> c_int;
     // the mix: c'_i = c_perm(i) r_i^n mod n^2 for count = 2^d ciphertexts; bits: the (2d - 1) count / 2 switch
     // bytes of the Benes network, layer-major (pz_mix_route makes them from perm); routes_out: every layer's outputs; records
     // output-major, bits(n) + popcount(n) + 1 per output.  The bits, the r_i and the routes are the mixer's secrets.
@@ -298,6 +307,22 @@ extern "C" {
                                    lookup_rows: usize, col_stride: usize) -> c_int;
     pub fn pz_smix_public_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, s_limbs: u32, cells_out: *mut u64,
                                 capacity: usize, n_public: *mut usize) -> c_int;
+    pub fn pz_circuit_structure_pballot_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, k: u32, count: usize,
+                                            slots: u32, m_bits: u32, s_limbs: u32, minimum_rows: usize, blinding_factors: u32,
+                                            out: *mut *mut pz_structure) -> c_int;
+    // circuit kind 11 ("pballot"): its shape is (count, slots, m_bits, s_limbs); inputs n | hs | G_0 .. G_{K-1} | v_11 .. v_RK | s_1 ..
+    // s_R | res_1 .. res_R; d_steps as pz_paillier_pballot_dev left them
+    pub fn pz_pballot_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, slots: u32, m_bits: u32, s_limbs: u32,
+                            advice_cells: *mut usize, lookup_cells: *mut usize) -> c_int;
+    pub fn pz_pballot_expand_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, slots: u32, m_bits: u32,
+                                 s_limbs: u32, inputs: *const u64, d_steps: *const u64, d_modulus: *const u64, d_advice: *mut u64,
+                                 d_lookup: *mut u64, rows: usize, col_stride: usize) -> c_int;
+    pub fn pz_pballot_expand_cols_dev(ctx: *mut pz_ctx, limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, slots: u32,
+                                      m_bits: u32, s_limbs: u32, inputs: *const u64, d_steps: *const u64, d_modulus: *const u64,
+                                      d_advice: *mut u64, d_lookup: *mut u64, d_col_starts: *const u64, n_adv_cols: usize,
+                                      max_rows: usize, lookup_rows: usize, col_stride: usize) -> c_int;
+    pub fn pz_pballot_public_cells(limbs_n: u32, limb_bits: u32, lookup_bits: u32, count: usize, slots: u32, m_bits: u32, s_limbs: u32,
+                                   cells_out: *mut u64, capacity: usize, n_public: *mut usize) -> c_int;
     pub fn pz_structure_info(st: *const pz_structure, n_adv: *mut usize, n_adv_filled: *mut usize, n_lk: *mut usize, max_rows: *mut usize,
                              n_constants: *mut usize, n_cells: *mut usize, n_lookups: *mut usize, n_steps_g: *mut usize,
                              n_steps_r: *mut usize) -> c_int;
