@@ -231,15 +231,11 @@ class _Template:
     r_cells: np.ndarray              # local positions of r's limb cells
 
 
-def _block_template(L: int, limb_bits: int, lb: int) -> _Template:
-    w = _Walk()
-    A = [("a", j) for j in range(L)]
-    B = [("b", j) for j in range(L)]
-    Nf = [("n", j) for j in range(L)]
-    rl = _mul_mod(w, A, B, Nf, L, limb_bits, lb)
+def _make_template(w: _Walk, outs: List[int]) -> _Template:
+    """a finished template walk -> arrays; outs: the local positions of the block's outputs"""
     n = w.n
     sol = np.arange(n, dtype=np.int64)
-    ext: Dict[str, Tuple[List[int], List[int]]] = {"a": ([], []), "b": ([], []), "n": ([], [])}
+    ext: Dict[str, Tuple[List[int], List[int]]] = {"a": ([], []), "b": ([], []), "n": ([], []), "s": ([], [])}
     for i, s in enumerate(w.src):
         if isinstance(s, tuple):
             ext[s[0]][0].append(i)
@@ -250,7 +246,15 @@ def _block_template(L: int, limb_bits: int, lb: int) -> _Template:
     assert all(isinstance(c, int) for c in w.lk)
     return _Template(n, sol, {k: (np.asarray(p, dtype=np.int64), np.asarray(j, dtype=np.int64)) for k, (p, j) in ext.items()},
                      np.asarray(cpos, dtype=np.int64), [w.cval[i] for i in cpos], np.asarray(w.gates, dtype=np.int64),
-                     np.asarray(w.lk, dtype=np.int64), np.asarray(rl, dtype=np.int64))
+                     np.asarray(w.lk, dtype=np.int64), np.asarray(outs, dtype=np.int64))
+
+
+def _block_template(L: int, limb_bits: int, lb: int) -> _Template:
+    w = _Walk()
+    A = [("a", j) for j in range(L)]
+    B = [("b", j) for j in range(L)]
+    Nf = [("n", j) for j in range(L)]
+    return _make_template(w, _mul_mod(w, A, B, Nf, L, limb_bits, lb))
 
 
 def _uniform_template(L: int, limb_bits: int, lb: int) -> _Template:
@@ -272,20 +276,7 @@ def _uniform_template(L: int, limb_bits: int, lb: int) -> _Template:
         w.gate(g)
         w.put(("s", 0)); w.put(c_d)
         outs.append(w.put())
-    sq = _mul_mod(w, B, B, Nf, L, limb_bits, lb)
-    n = w.n
-    sol = np.arange(n, dtype=np.int64)
-    ext: Dict[str, Tuple[List[int], List[int]]] = {"a": ([], []), "b": ([], []), "n": ([], []), "s": ([], [])}
-    for i, s_ in enumerate(w.src):
-        if isinstance(s_, tuple):
-            ext[s_[0]][0].append(i)
-            ext[s_[0]][1].append(s_[1])
-        elif s_ >= 0:
-            sol[i] = s_
-    cpos = [i for i, v in enumerate(w.cval) if v is not None]
-    return _Template(n, sol, {k: (np.asarray(p, dtype=np.int64), np.asarray(j, dtype=np.int64)) for k, (p, j) in ext.items()},
-                     np.asarray(cpos, dtype=np.int64), [w.cval[i] for i in cpos], np.asarray(w.gates, dtype=np.int64),
-                     np.asarray(w.lk, dtype=np.int64), np.asarray(outs + sq, dtype=np.int64))
+    return _make_template(w, outs + _mul_mod(w, B, B, Nf, L, limb_bits, lb))
 
 
 @dataclass
@@ -311,6 +302,240 @@ class StructureArrays:
 
 def _exp_bits(e: int) -> List[int]:
     return [(e >> i) & 1 for i in range(e.bit_length())]
+
+
+def _flex_sum(w: _Walk, cells: Sequence[int]):
+    """FlexGate::sum: m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..; a window every 3 cells, the operands copies of the cells above
+    -> the last sum's cell (fewer than two cells: nothing is emitted, None)"""
+    if len(cells) < 2:
+        return None
+    sum_c = w.put(cells[0])
+    for c in cells[1:]:
+        w.gate(sum_c)
+        w.putc(1)
+        w.put(c)
+        sum_c = w.put()
+    return sum_c
+
+
+class _Stream:
+    """The advice stream as a sequence of parts, and the shared parts every circuit kind's stream is composed of (stream_structure
+    below; the same names in csrc/pz_structure.hip).  The stream's end `off` is where the next part starts: every part is appended
+    there.  dev: None -> numpy; a torch device -> the templates are tiled THERE."""
+
+    def __init__(self, L: int, limb_bits: int, lb: int, dev):
+        self.L, self.W, self.lb, self.dev = L, limb_bits, lb, dev
+        self.off = 0
+        self.src: List = []
+        self.mask: List[np.ndarray] = []
+        self.lk: List = []
+        self.const_id: Dict[int, int] = {}
+        self.constants: List[int] = []
+        self.fresh: Optional[np.ndarray] = None      # the limb cells of the refreshed n^2 (set behind the prefix)
+        self.tmpls: List = [_block_template(L, limb_bits, lb)]
+        self.bound: List = []                        # per template: (the constant id per const_pos entry, the gate mask)
+
+    def cid(self, v: int) -> int:
+        if v not in self.const_id:
+            self.const_id[v] = len(self.constants)
+            self.constants.append(v)
+        return self.const_id[v]
+
+    def open(self) -> _Walk:
+        return _Walk(self.off)
+
+    def flush(self, walk: _Walk) -> None:
+        """a finished Python-walked part -> arrays"""
+        n = walk.n
+        s = np.arange(walk.base, walk.base + n, dtype=np.int64)
+        for i, v in enumerate(walk.src):
+            if v != -1:
+                s[i] = v
+        for i, v in enumerate(walk.cval):
+            if v is not None:
+                s[i] = -(1 + self.cid(v))
+        mk = np.zeros(n, dtype=np.uint8)
+        mk[np.asarray(walk.gates, dtype=np.int64)] = 1
+        self.src.append(s)
+        self.mask.append(mk)
+        self.lk.append(np.asarray(walk.lk, dtype=np.int64))
+        self.off = walk.base + n
+
+    def bind_template_constants(self, t: int) -> None:
+        T = self.tmpls[t]
+        mask = np.zeros(T.cells, dtype=np.uint8)
+        mask[T.gates] = 1
+        assert len(self.bound) == t
+        self.bound.append((np.asarray([self.cid(v) for v in T.const_val], dtype=np.int64), mask))
+
+    def tile(self, bases: np.ndarray, sol: np.ndarray, assigns=()):
+        """flattened [len(bases)][len(sol)] array of bases[i] + sol[j], columns `pos` overwritten by `vals` ([ns][len(pos)] or [len(pos)])"""
+        if self.dev is None:
+            t_ = bases[:, None] + sol[None, :]
+            for pos, vals in assigns:
+                t_[:, pos] = vals
+            return t_.reshape(-1)
+        import torch
+
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int64).to(self.dev)
+        t_ = up(bases)[:, None] + up(sol)[None, :]
+        for pos, vals in assigns:
+            v = up(vals)
+            t_[:, up(pos)] = v if v.dim() == 2 else v[None, :].expand(t_.shape[0], -1)
+        return t_.reshape(-1)
+
+    def blocks(self, t: int, a_cells: np.ndarray, b_cells: np.ndarray, s_cells: Optional[np.ndarray] = None) -> np.ndarray:
+        """ns blocks of template t at the stream's end; a_cells / b_cells: int64 [ns][L] global cells of the operands' limbs, s_cells:
+        [ns] the bit's cell (uniform) -> int64 [ns][..] the global cells of every block's outputs"""
+        T = self.tmpls[t]
+        const_ids, mask = self.bound[t]
+        ns = a_cells.shape[0]
+        bases = self.off + T.cells * np.arange(ns, dtype=np.int64)
+        assigns = []
+        for kind_, cells_ in (("a", a_cells), ("b", b_cells)):
+            pos, j = T.ext[kind_]
+            assigns.append((pos, cells_[:, j]))
+        pos, j = T.ext["n"]
+        assigns.append((pos, self.fresh[j]))
+        if s_cells is not None:
+            pos, _ = T.ext["s"]
+            assigns.append((pos, np.repeat(s_cells[:, None], len(pos), axis=1)))
+        assigns.append((T.const_pos, -(1 + const_ids)))
+        self.src.append(self.tile(bases, T.self_or_local, assigns))
+        self.mask.append(np.tile(mask, ns))
+        self.lk.append(self.tile(bases, T.lk))
+        self.off += ns * T.cells
+        return bases[:, None] + T.r_cells[None, :]
+
+    def uniform(self) -> None:
+        """the uniform template (template 1) of a circuit with in-circuit bits: added once, its constants bound"""
+        if len(self.tmpls) > 1:
+            return
+        self.tmpls.append(_uniform_template(self.L, self.W, self.lb))
+        self.bind_template_constants(1)
+
+    def head(self, w: _Walk) -> np.ndarray:
+        """a chain's head in the open walk: assign_constant(1), load_zero -> the initial acc cells [one, zero, ..]"""
+        one = w.putc(1)
+        z2 = w.putc(0)
+        return np.asarray([one] + [z2] * (self.L - 1), dtype=np.int64)
+
+    def bit_chain(self, wb: _Walk, word_cell: int, nbits: int, acc: np.ndarray, sq: np.ndarray):
+        """num_to_bits(word_cell, nbits) behind what the open walk wb holds, flushed, then nbits blocks of the uniform template chained
+        through acc (select outputs) and sq (square remainders) -> (the last acc cells, the last sq cells)"""
+        L, ut = self.L, self.tmpls[1]
+        bit_cells = [wb.put()]
+        if nbits > 1:
+            wb.gate(bit_cells[0])
+        acc_cell = bit_cells[0]
+        for i in range(1, nbits):
+            bit_cells.append(wb.put())
+            wb.putc(1 << i)
+            acc_cell = wb.put()
+            if i < nbits - 1:
+                wb.gate(acc_cell)
+        wb.pair(word_cell, acc_cell)        # (nbits = 1: the accumulator IS the bit)
+        for bc in bit_cells:
+            g_ = wb.putc(0)
+            wb.gate(g_)
+            wb.put(bc); wb.put(bc); wb.put(bc)
+        self.flush(wb)
+        outs = self.off + ut.cells * np.arange(nbits, dtype=np.int64)[:, None] + ut.r_cells[None, :]
+        a_cells = np.concatenate([np.asarray(acc, dtype=np.int64)[None, :], outs[:-1, :L]])
+        b_cells = np.concatenate([np.asarray(sq, dtype=np.int64)[None, :], outs[:-1, L:]])
+        self.blocks(1, a_cells, b_cells, np.asarray(bit_cells, dtype=np.int64))
+        return outs[-1, :L], outs[-1, L:]
+
+    def limb_chain(self, base_cells, limb_cells, n_limbs: int) -> np.ndarray:
+        """pow_mod(base, e) over the n_limbs limb cells of an assigned e: the head as a part of its own, then per limb num_to_bits of
+        ITS cell and limb_bits uniform blocks -> the power's cells (the last select's outputs)"""
+        wc = self.open()
+        acc, sq = self.head(wc), base_cells
+        self.flush(wc)
+        for li in range(n_limbs):
+            acc, sq = self.bit_chain(self.open(), limb_cells[li], self.W, acc, sq)
+        return acc
+
+    def word_chain(self, word_cell: int, nbits: int, base_cells) -> np.ndarray:
+        """pow_mod(base, e) over the nbits bits of a one-cell e: the head and num_to_bits in ONE walk, then nbits uniform blocks
+        -> the power's cells"""
+        wb = self.open()
+        return self.bit_chain(wb, word_cell, nbits, self.head(wb), base_cells)[0]
+
+    def mul_blocks(self, a_blk, b_blk, outer) -> np.ndarray:
+        """mul_mod blocks from WHICH block produced each operand: a_blk / b_blk[q] >= 0 names a block of this run (its remainder), the
+        entry -(1 + i) the cells outer[i] from outside the run (no block: no part) -> the table of cells that both kinds of entry index"""
+        ns = len(a_blk)
+        r_of = self.off + self.tmpls[0].cells * np.arange(ns, dtype=np.int64)[:, None] + self.tmpls[0].r_cells[None, :]
+        table = np.concatenate([r_of, np.asarray(outer[::-1], dtype=np.int64).reshape(-1, self.L)])
+        if ns:
+            self.blocks(0, table[np.asarray(a_blk, dtype=np.int64)], table[np.asarray(b_blk, dtype=np.int64)])
+        return table
+
+    def mul_block(self, a, b) -> np.ndarray:
+        """one mul_mod(a, b) -> r's cells"""
+        return self.blocks(0, np.asarray(a, dtype=np.int64)[None, :], np.asarray(b, dtype=np.int64)[None, :])[0]
+
+    def fixed_chain(self, base_cells, e: int):
+        """pow_mod_fixed_exp(base, e): the head, then per bit of e the squaring step (cur, cur) and on a set bit (acc, cur): block -1 is
+        the base, block -2 the head -> (the power's cells, the number of blocks)"""
+        wc = self.open()
+        one = self.head(wc)
+        self.flush(wc)
+        a_blk, b_blk = [], []
+        sq_blk, acc_blk = -1, -2
+        for bit in _exp_bits(e):
+            cur_blk, sq_blk = sq_blk, len(a_blk)
+            a_blk.append(cur_blk); b_blk.append(cur_blk)
+            if bit:
+                a_blk.append(acc_blk); b_blk.append(cur_blk)
+                acc_blk = len(a_blk) - 1
+        return self.mul_blocks(a_blk, b_blk, [base_cells, one])[acc_blk], len(a_blk)
+
+    def product_tree(self, leaves, tree):
+        """the product of the leaves in the order of `tree` (layout.tally_tree: level by level the neighbours of the current list, an odd
+        last element carried up; blocks numbered level-major, leaf i is entry -(1 + i)) -> (the root's cells -- one leaf: no block,
+        the leaf --, the number of blocks)"""
+        nb = len(tree)
+        table = self.mul_blocks([t[0] for t in tree], [t[1] for t in tree], leaves)
+        return table[nb - 1], nb                  # the root is the last block
+
+    def network(self, ins):
+        """the Benes network of mix.py over `ins` as ONE walked part, layer by layer and switch by switch: assert_bit of the switch's own
+        bit cell ([0, b, b, b]: the first b is the bit's home, the other two copy it), then per limb select(in[j'], in[j], b) and
+        select(in[j], in[j'], b) -- 8 cells each [d | 1 | y | x | y | b | d | out], windows at 0 and 4.  The operands are the previous
+        layer's out cells (layer 0: `ins`); values stay in place -> the outputs' cells"""
+        count = len(ins)
+        wn = self.open()
+
+        def select(x, y, s):
+            c_d = wn.put()
+            wn.gate(c_d)
+            wn.putc(1); wn.put(y); wn.put(x)
+            g_ = wn.put(y)
+            wn.gate(g_)
+            wn.put(s); wn.put(c_d)
+            return wn.put()
+
+        cur_c = [list(c) for c in ins]
+        for beta in mix.layer_bits(count):
+            nxt_c = [None] * count
+            for j in range(count):
+                if j >> beta & 1:
+                    continue
+                jp = j | (1 << beta)
+                g_ = wn.putc(0)
+                wn.gate(g_)
+                b_c = wn.put()
+                wn.put(b_c); wn.put(b_c)
+                lo_c, hi_c = [], []
+                for t_ in range(self.L):
+                    lo_c.append(select(cur_c[jp][t_], cur_c[j][t_], b_c))
+                    hi_c.append(select(cur_c[j][t_], cur_c[jp][t_], b_c))
+                nxt_c[j], nxt_c[jp] = lo_c, hi_c
+            cur_c = nxt_c
+        self.flush(wn)
+        return cur_c
 
 
 def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: int = 0, exp_r: int = 0, device: Optional[str] = None,
@@ -351,32 +576,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
 
         dev = torch.device(device)
 
-    def tile(bases: np.ndarray, sol: np.ndarray, assigns=()) -> "np.ndarray | torch.Tensor":
-        """flattened [len(bases)][len(sol)] array of bases[i] + sol[j], columns `pos` overwritten by `vals` ([ns][len(pos)] or [len(pos)])"""
-        if dev is None:
-            t_ = bases[:, None] + sol[None, :]
-            for pos, vals in assigns:
-                t_[:, pos] = vals
-            return t_.reshape(-1)
-        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int64).to(dev)
-        t_ = up(bases)[:, None] + up(sol)[None, :]
-        for pos, vals in assigns:
-            v = up(vals)
-            t_[:, up(pos)] = v if v.dim() == 2 else v[None, :].expand(t_.shape[0], -1)
-        return t_.reshape(-1)
-
     Ln = enc_bits // limb_bits
     L = 2 * Ln
-    tm = _block_template(L, limb_bits, lb)
-    const_id: Dict[int, int] = {}
-    constants: List[int] = []
-
-    def cid(v: int) -> int:
-        if v not in const_id:
-            const_id[v] = len(constants)
-            constants.append(v)
-        return const_id[v]
-
     if kind not in ("encrypt", "encrypt_uniform", "add", "tally", "wtally", "decrypt", "ballot", "partial", "mix", "sballot", "smix",
                     "pballot"):
         raise ValueError(f"unknown circuit kind {kind!r}")
@@ -417,7 +618,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         tree = layout.wtally_tree(count)                              # (1 .. TALLY_MAX; one ciphertext has no tree)
     # ---- prefix: the four assign_integer (tally: n, then the B ciphertexts at full width), square, refresh, load_zero (not in a
     # tally: nothing is extended there); global indices from 0
-    w = _Walk()
+    S = _Stream(L, limb_bits, lb, dev)
+    w = S.open()
     n_c = _assign(w, Ln, limb_bits, lb)
     if kind in ("tally", "wtally"):
         ct_c = [_assign(w, L, limb_bits, lb) for _ in range(count)]
@@ -435,30 +637,13 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
         hs_c = _assign(w, L, limb_bits, lb)                                     # hs, then the slot bases G_j: all at full width
         gs_c = [_assign(w, L, limb_bits, lb) for _ in range(slots)]
         vs_c = [[w.put() for _ in range(slots)] for _ in range(count)]          # load_witness(v_ij): one cell each, ciphertext-major
-        sums_c = []
-        if slots >= 2:
-            for i in range(count):                                              # FlexGate::sum over the ciphertext's own values
-                sum_c = w.put(vs_c[i][0])
-                for j in range(1, slots):
-                    w.gate(sum_c)
-                    w.putc(1)
-                    w.put(vs_c[i][j])
-                    sum_c = w.put()
-                sums_c.append(sum_c)
+        sums_c = [_flex_sum(w, vs_c[i]) for i in range(count)] if slots >= 2 else []   # over the ciphertext's own values
         rs_c = [_assign(w, s_limbs, limb_bits, lb) for _ in range(count)]       # s_i
     elif kind in ("ballot", "sballot"):
         g_c = _assign(w, Ln, limb_bits, lb)
         hs_c = _assign(w, L, limb_bits, lb) if kind == "sballot" else []        # hs: the key's second base, full width
         ms_c = [w.put() for _ in range(count)]                                 # load_witness(m_i): one cell each, no gate
-        sum_c = None
-        if count >= 2:
-            # FlexGate::sum: m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..; a window every 3 cells, the operands copies of the cells above
-            sum_c = w.put(ms_c[0])
-            for i in range(1, count):
-                w.gate(sum_c)
-                w.putc(1)
-                w.put(ms_c[i])
-                sum_c = w.put()
+        sum_c = _flex_sum(w, ms_c)                                             # (count >= 2)
         rs_c = [_assign(w, s_limbs if kind == "sballot" else Ln, limb_bits, lb) for _ in range(count)]   # r_i; 'sballot': s_i
     else:
         g_c = _assign(w, Ln, limb_bits, lb)
@@ -484,354 +669,74 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     for c in cur:
         holder = _range_check(w, c, limb_bits, lb)
         fresh.append(c if c is not None else holder)
+    S.fresh = np.asarray(fresh, dtype=np.int64)
     zero = w.putc(0) if kind not in ("tally", "wtally") else None
     ext_l = lambda limbs: list(limbs) + [zero] * (L - len(limbs))
-    parts_src: List[np.ndarray] = []
-    parts_mask: List[np.ndarray] = []
-    parts_lk: List[np.ndarray] = []
+    S.flush(w)
+    S.bind_template_constants(0)
+    if kind in ("encrypt_uniform", "wtally", "ballot", "partial", "sballot", "smix", "pballot"):
+        S.uniform()                                                   # the kinds with in-circuit bits
 
-    def flush(walk: _Walk):
-        """a finished Python-walked part -> arrays"""
-        n = walk.n
-        s = np.arange(walk.base, walk.base + n, dtype=np.int64)
-        for i, v in enumerate(walk.src):
-            if v != -1:
-                s[i] = v
-        for i, v in enumerate(walk.cval):
-            if v is not None:
-                s[i] = -(1 + cid(v))
-        mk = np.zeros(n, dtype=np.uint8)
-        mk[np.asarray(walk.gates, dtype=np.int64)] = 1
-        parts_src.append(s)
-        parts_mask.append(mk)
-        parts_lk.append(np.asarray(walk.lk, dtype=np.int64))
-        return walk.base + n
-
-    off = flush(w)
-    tm_const_ids = np.asarray([cid(v) for v in tm.const_val], dtype=np.int64)
-    tm_mask = np.zeros(tm.cells, dtype=np.uint8)
-    tm_mask[tm.gates] = 1
-    fresh_arr = np.asarray(fresh, dtype=np.int64)
-
-    def blocks(off: int, a_cells: np.ndarray, b_cells: np.ndarray):
-        """ns mul_mod blocks starting at stream index `off`; a_cells / b_cells: int64 [ns][L] global cells of the operands' limbs"""
-        ns = a_cells.shape[0]
-        bases = off + tm.cells * np.arange(ns, dtype=np.int64)
-        assigns = []
-        for kind_, cells_ in (("a", a_cells), ("b", b_cells)):
-            pos, j = tm.ext[kind_]
-            assigns.append((pos, cells_[:, j]))
-        pos, j = tm.ext["n"]
-        assigns.append((pos, fresh_arr[j]))
-        assigns.append((tm.const_pos, -(1 + tm_const_ids)))
-        parts_src.append(tile(bases, tm.self_or_local, assigns))
-        parts_mask.append(np.tile(tm_mask, ns))
-        parts_lk.append(tile(bases, tm.lk))
-        return off + ns * tm.cells, bases[:, None] + tm.r_cells[None, :]      # r cells of every block
-
-    def bit_chain(off: int, ut: _Template, ut_const: np.ndarray, ut_mask: np.ndarray, word_cell: int, nbits: int, acc_cells: np.ndarray,
-                  sq_cells: np.ndarray):
-        """num_to_bits(word_cell, nbits), then nbits blocks of the uniform template chained through acc (select outputs) and sq (square
-        remainders) -> (off, the last acc cells, the last sq cells)"""
-        wb = _Walk(off)
-        bit_cells = [wb.put()]
-        if nbits > 1:
-            wb.gate(bit_cells[0])
-        acc_cell = bit_cells[0]
-        for i in range(1, nbits):
-            bit_cells.append(wb.put())
-            wb.putc(1 << i)
-            acc_cell = wb.put()
-            if i < nbits - 1:
-                wb.gate(acc_cell)
-        wb.pair(word_cell, acc_cell)        # (nbits = 1: the accumulator IS the bit)
-        for bc in bit_cells:
-            g_ = wb.putc(0)
-            wb.gate(g_)
-            wb.put(bc); wb.put(bc); wb.put(bc)
-        off = flush(wb)
-        bases = off + ut.cells * np.arange(nbits, dtype=np.int64)
-        new_acc = bases[:, None] + ut.r_cells[None, :L]
-        new_sq = bases[:, None] + ut.r_cells[None, L:]
-        a_cells = np.concatenate([acc_cells[None, :], new_acc[:-1]])
-        b_cells = np.concatenate([sq_cells[None, :], new_sq[:-1]])
-        assigns = []
-        for kind_, cells_ in (("a", a_cells), ("b", b_cells)):
-            pos, j = ut.ext[kind_]
-            assigns.append((pos, cells_[:, j]))
-        pos, j = ut.ext["n"]
-        assigns.append((pos, fresh_arr[j]))
-        pos, _ = ut.ext["s"]
-        assigns.append((pos, np.repeat(np.asarray(bit_cells, dtype=np.int64)[:, None], len(pos), axis=1)))
-        assigns.append((ut.const_pos, -(1 + ut_const)))
-        parts_src.append(tile(bases, ut.self_or_local, assigns))
-        parts_mask.append(np.tile(ut_mask, nbits))
-        parts_lk.append(tile(bases, ut.lk))
-        return off + nbits * ut.cells, new_acc[-1], new_sq[-1]
-
-    def fixed_chain(off: int, base_limbs, e: int):
-        """pow_mod_fixed_exp(base, e): [1, 0], then per bit of e the squaring step (cur, cur) and on a set bit (acc, cur).  Which BLOCK
-        produced each operand is structure: block indices are assigned first, the operand cells follow from them.
-        -> (off, the power's cells, the number of blocks)"""
-        wc = _Walk(off)
-        one = wc.putc(1)
-        z2 = wc.putc(0)
-        off = flush(wc)
-        bits = _exp_bits(e)
-        ns = len(bits) + sum(bits)
-        a_blk = np.empty(ns, dtype=np.int64)      # producing block of operand a (-1: the base, -2: the constant one)
-        b_blk = np.empty(ns, dtype=np.int64)
-        sq_blk, acc_blk, t = -1, -2, 0
-        for bit in bits:
-            a_blk[t] = b_blk[t] = sq_blk
-            cur_blk, sq_blk = sq_blk, t
-            t += 1
-            if bit:
-                a_blk[t], b_blk[t] = acc_blk, cur_blk
-                acc_blk = t
-                t += 1
-        r_of = off + tm.cells * np.arange(ns, dtype=np.int64)[:, None] + tm.r_cells[None, :]
-        special = np.stack([np.asarray([one] + [z2] * (L - 1), dtype=np.int64), np.asarray(base_limbs, dtype=np.int64)])   # -2, -1
-        table = np.concatenate([special, r_of]) if ns else special
-        if ns:
-            off, _ = blocks(off, table[a_blk + 2], table[b_blk + 2])
-        return off, table[acc_blk + 2], ns
-
+    # ---- the kind's own blocks -> the cells holding its result(s)
     n_steps = [0, 0]
-    if kind == "partial":
-        # pow_mod(v, theta), then per ciphertext the block mul_mod(c_j, c_j) and pow_mod(s_j, theta): kind 2's walk over ALL 2 Ln limbs
-        # of theta -- every chain's num_to_bits decomposes the SAME limb cells; a chain's power is its last select's outputs
-        ut = _uniform_template(L, limb_bits, lb)
-        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
-        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
-        ut_mask[ut.gates] = 1
-
-        def theta_chain(off: int, base_cells):
-            wc = _Walk(off)
-            one = wc.putc(1)
-            z2 = wc.putc(0)
-            off = flush(wc)
-            acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
-            sq_cells = np.asarray(base_cells, dtype=np.int64)
-            for li in range(L):
-                off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, th_c[li], limb_bits, acc_cells, sq_cells)
-            return off, acc_cells.tolist()
-
-        off, h_cells = theta_chain(off, v_c)
-        c_cells = [h_cells]
+    hs_chain = lambda i: S.limb_chain(hs_c, rs_c[i], s_limbs)         # pow_mod(hs, s_i): every chain from the SAME hs cells
+    if kind in ("encrypt", "encrypt_uniform", "add"):
+        gm, rn = ext_l(x_c), ext_l(y_c)                               # ('add': the two ciphertexts)
+        if kind == "encrypt_uniform":     # g^m over ALL enc_bits bits of m IN the circuit: the same shape for every message
+            gm, n_steps[0] = S.limb_chain(ext_l(g_c), x_c, Ln), 2 * Ln * limb_bits
+        elif kind == "encrypt":
+            gm, n_steps[0] = S.fixed_chain(ext_l(g_c), exp_g)
+        if kind != "add":
+            rn, n_steps[1] = S.fixed_chain(ext_l(y_c), exp_r)
+        roots = [S.mul_block(gm, rn)]
+    elif kind == "tally":
+        root, n_steps[0] = S.product_tree(ct_c, tree)
+        roots = [root]
+    elif kind == "wtally":
+        powers = [S.word_chain(wt_c[i], w_bits, ct_c[i]) for i in range(count)]
+        n_steps[0] = 2 * count * w_bits
+        root, n_steps[1] = S.product_tree(powers, tree)
+        roots = [root]
+    elif kind == "ballot":
+        roots = []
+        for i in range(count):
+            gm = S.word_chain(ms_c[i], m_bits, ext_l(g_c))
+            rn, n_steps[1] = S.fixed_chain(ext_l(rs_c[i]), exp_r)
+            roots.append(S.mul_block(gm, rn))
+        n_steps[0] = 2 * m_bits
+    elif kind == "partial":
+        roots = [S.limb_chain(v_c, th_c, L)]                          # h = v^theta: every chain decomposes the SAME limb cells of theta
         for j in range(count):
-            ct = np.asarray(ct_c[j], dtype=np.int64)[None, :]
-            off, s_cells = blocks(off, ct, ct)
-            off, u_cells = theta_chain(off, s_cells[0])
-            c_cells.append(u_cells)
+            roots.append(S.limb_chain(S.mul_block(ct_c[j], ct_c[j]), th_c, L))      # from s_j = c_j^2
         n_steps[0] = 2 * L * limb_bits
     elif kind in ("mix", "smix"):
-        # the network, layer by layer and switch by switch: assert_bit of the switch's own bit cell ([0, b, b, b]: the first b is the
-        # bit's home, the other two copy it), then per limb select(in[j'], in[j], b) and select(in[j], in[j'], b) -- 8 cells each
-        # [d | 1 | y | x | y | b | d | out], windows at 0 and 4.  The operands are the previous layer's out cells (layer 0: the
-        # assigned ciphertexts' limbs); values stay in place
-        wn = _Walk(off)
-
-        def select(x, y, s):
-            c_d = wn.put()
-            wn.gate(c_d)
-            wn.putc(1); wn.put(y); wn.put(x)
-            g_ = wn.put(y)
-            wn.gate(g_)
-            wn.put(s); wn.put(c_d)
-            return wn.put()
-
-        cur_c = [list(c) for c in ct_c]
-        for beta in mix.layer_bits(count):
-            nxt_c = [None] * count
-            for j in range(count):
-                if j >> beta & 1:
-                    continue
-                jp = j | (1 << beta)
-                g_ = wn.putc(0)
-                wn.gate(g_)
-                b_c = wn.put()
-                wn.put(b_c); wn.put(b_c)
-                lo_c, hi_c = [], []
-                for t_ in range(L):
-                    lo_c.append(select(cur_c[jp][t_], cur_c[j][t_], b_c))
-                    hi_c.append(select(cur_c[j][t_], cur_c[jp][t_], b_c))
-                nxt_c[j], nxt_c[jp] = lo_c, hi_c
-            cur_c = nxt_c
-        off = flush(wn)
-        c_cells = []
-        if kind == "mix":
-            # per output: pow_mod_fixed_exp(r_i_ext, n) and the block mul_mod(d_i, rn_i)
-            for i in range(count):
-                off, rn, n_steps[1] = fixed_chain(off, ext_l(rs_c[i]), exp_r)
-                off, rfin = blocks(off, np.asarray(cur_c[i], dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
-                c_cells.append(rfin[0].tolist())
-        else:
-            # per output: pow_mod(hs, s_i) as 'sballot' walks its hs-chain -- [1, 0], then per limb of s_i num_to_bits of ITS limb cell
-            # and limb_bits bit blocks, every output's chain from the SAME hs cells -- and the block mul_mod(d_i, hss_i)
-            ut = _uniform_template(L, limb_bits, lb)
-            ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
-            ut_mask = np.zeros(ut.cells, dtype=np.uint8)
-            ut_mask[ut.gates] = 1
-            for i in range(count):
-                wc = _Walk(off)
-                one = wc.putc(1)
-                z2 = wc.putc(0)
-                off = flush(wc)
-                acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
-                sq_cells = np.asarray(hs_c, dtype=np.int64)
-                for li in range(s_limbs):
-                    off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, rs_c[i][li], limb_bits, acc_cells, sq_cells)
-                off, rfin = blocks(off, np.asarray(cur_c[i], dtype=np.int64)[None, :], acc_cells[None, :])
-                c_cells.append(rfin[0].tolist())
+        d_c = S.network(ct_c)
+        roots = []
+        for i in range(count):
+            if kind == "mix":
+                rn, n_steps[1] = S.fixed_chain(ext_l(rs_c[i]), exp_r)
+            else:
+                rn = hs_chain(i)
+            roots.append(S.mul_block(d_c[i], rn))
+        if kind == "smix":
             n_steps[1] = 2 * s_limbs * limb_bits
-    elif kind == "ballot":
-        # per ciphertext: pow_mod(g_ext, m_i) over m_bits in-circuit bits (the weighted tally's chain on the base g, extended by the
-        # load_zero cell), pow_mod_fixed_exp(r_i_ext, n), the final mul_mod; then per ciphertext assign res_i + assert_equal_fresh
-        ut = _uniform_template(L, limb_bits, lb)
-        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
-        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
-        ut_mask[ut.gates] = 1
-        c_cells = []
-        for i in range(count):
-            wc = _Walk(off)
-            one = wc.putc(1)
-            z2 = wc.putc(0)
-            off = flush(wc)
-            off, gm, _ = bit_chain(off, ut, ut_const, ut_mask, ms_c[i], m_bits, np.asarray([one] + [z2] * (L - 1), dtype=np.int64),
-                                   np.asarray(ext_l(g_c), dtype=np.int64))
-            off, rn, n_steps[1] = fixed_chain(off, ext_l(rs_c[i]), exp_r)
-            off, rfin = blocks(off, np.asarray(gm, dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
-            c_cells.append(rfin[0].tolist())
-        n_steps[0] = 2 * m_bits
-    elif kind == "pballot":
-        # per ciphertext: per slot pow_mod(G_j, v_ij) as 'ballot's g-chain, its first sq the limb cells of assign_integer(G_j) -- the
-        # SAME cells for every ciphertext --; pow_mod(hs, s_i) as 'sballot'; then the K folds: block q multiplies the running product
-        # (P_0, then block q - 1's remainder) by P_{q+1}, the last one by hs^s_i
-        ut = _uniform_template(L, limb_bits, lb)
-        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
-        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
-        ut_mask[ut.gates] = 1
-        c_cells = []
-        for i in range(count):
-            powers = []
-            for j in range(slots):
-                wc = _Walk(off)
-                one = wc.putc(1)
-                z2 = wc.putc(0)
-                off = flush(wc)
-                off, pj, _ = bit_chain(off, ut, ut_const, ut_mask, vs_c[i][j], m_bits, np.asarray([one] + [z2] * (L - 1), dtype=np.int64),
-                                       np.asarray(gs_c[j], dtype=np.int64))
-                powers.append(np.asarray(pj, dtype=np.int64))
-            wc = _Walk(off)
-            one = wc.putc(1)
-            z2 = wc.putc(0)
-            off = flush(wc)
-            acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
-            sq_cells = np.asarray(hs_c, dtype=np.int64)
-            for li in range(s_limbs):
-                off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, rs_c[i][li], limb_bits, acc_cells, sq_cells)
-            r_of = off + tm.cells * np.arange(slots, dtype=np.int64)[:, None] + tm.r_cells[None, :]
-            a_cells = np.stack([powers[0]] + [r_of[q - 1] for q in range(1, slots)])
-            b_cells = np.stack([powers[q + 1] for q in range(slots - 1)] + [acc_cells])
-            off, rfin = blocks(off, a_cells, b_cells)
-            c_cells.append(rfin[-1].tolist())
-        n_steps[0], n_steps[1] = 2 * m_bits, 2 * s_limbs * limb_bits
     elif kind == "sballot":
-        # per ciphertext: pow_mod(g_ext, m_i) as 'ballot'; pow_mod(hs, s_i) as 'partial' walks a chain -- [1, 0], then per limb of s_i
-        # num_to_bits of ITS limb cell and limb_bits bit blocks, every entry's chain from the SAME hs cells --; the final mul_mod
-        ut = _uniform_template(L, limb_bits, lb)
-        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
-        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
-        ut_mask[ut.gates] = 1
-        c_cells = []
+        roots = []
         for i in range(count):
-            wc = _Walk(off)
-            one = wc.putc(1)
-            z2 = wc.putc(0)
-            off = flush(wc)
-            off, gm, _ = bit_chain(off, ut, ut_const, ut_mask, ms_c[i], m_bits, np.asarray([one] + [z2] * (L - 1), dtype=np.int64),
-                                   np.asarray(ext_l(g_c), dtype=np.int64))
-            wc = _Walk(off)
-            one = wc.putc(1)
-            z2 = wc.putc(0)
-            off = flush(wc)
-            acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
-            sq_cells = np.asarray(hs_c, dtype=np.int64)
-            for li in range(s_limbs):
-                off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, rs_c[i][li], limb_bits, acc_cells, sq_cells)
-            off, rfin = blocks(off, np.asarray(gm, dtype=np.int64)[None, :], acc_cells[None, :])
-            c_cells.append(rfin[0].tolist())
+            gm = S.word_chain(ms_c[i], m_bits, ext_l(g_c))
+            roots.append(S.mul_block(gm, hs_chain(i)))
         n_steps[0], n_steps[1] = 2 * m_bits, 2 * s_limbs * limb_bits
-    elif kind == "wtally":
-        # per ciphertext pow_mod(c_i, w_i) over w_bits in-circuit bits: [1, 0], num_to_bits of the weight's cell, the bit blocks; the
-        # chain starts from its OWN [one, zero ..] and from assign_integer(c_i)'s limb cells.  Its power is the last select's outputs.
-        ut = _uniform_template(L, limb_bits, lb)
-        ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
-        ut_mask = np.zeros(ut.cells, dtype=np.uint8)
-        ut_mask[ut.gates] = 1
-        powers = []
+    else:                                                             # 'pballot'
+        roots = []
         for i in range(count):
-            wc = _Walk(off)
-            one = wc.putc(1)
-            z2 = wc.putc(0)
-            off = flush(wc)
-            off, acc, _ = bit_chain(off, ut, ut_const, ut_mask, wt_c[i], w_bits, np.asarray([one] + [z2] * (L - 1), dtype=np.int64),
-                                    np.asarray(ct_c[i], dtype=np.int64))
-            powers.append(acc)
-        n_steps[0] = 2 * count * w_bits
-        nb = len(tree)
-        if nb:
-            r_of = off + tm.cells * np.arange(nb, dtype=np.int64)[:, None] + tm.r_cells[None, :]
-            table = np.concatenate([r_of, np.asarray(powers[::-1], dtype=np.int64)])     # index -(1 + i) -> the power of c_(i+1)
-            tr = np.asarray(tree, dtype=np.int64)
-            off, rfin = blocks(off, table[tr[:, 0]], table[tr[:, 1]])
-            rfin = rfin[-1:]
-        else:
-            rfin = powers[0][None, :]
-        n_steps[1] = nb
-    elif kind in ("encrypt", "encrypt_uniform"):
-        results = []
-        chains = [(ext_l(g_c), exp_g), (ext_l(y_c), exp_r)]
-        if kind == "encrypt_uniform":
-            # g^m over ALL enc_bits bits of m IN the circuit: assign_constant(1), load_zero, then per limb of m num_to_bits and per bit
-            # the (mul_mod, select, square_mod) block -- the same shape for every message
-            W_ = limb_bits
-            ut = _uniform_template(L, limb_bits, lb)
-            ut_const = np.asarray([cid(v) for v in ut.const_val], dtype=np.int64)
-            ut_mask = np.zeros(ut.cells, dtype=np.uint8)
-            ut_mask[ut.gates] = 1
-            wc = _Walk(off)
-            one = wc.putc(1)
-            z2 = wc.putc(0)
-            off = flush(wc)
-            acc_cells = np.asarray([one] + [z2] * (L - 1), dtype=np.int64)
-            sq_cells = np.asarray(ext_l(g_c), dtype=np.int64)
-            for li in range(Ln):
-                off, acc_cells, sq_cells = bit_chain(off, ut, ut_const, ut_mask, x_c[li], W_, acc_cells, sq_cells)
-            n_steps[0] = 2 * Ln * W_
-            results.append(acc_cells)
-            chains = [None, chains[1]]
-        for ci, chain in enumerate(chains):
-            if chain is None:
-                continue
-            off, power, n_steps[ci] = fixed_chain(off, *chain)
-            results.append(power)
-        gm, rn = results
-        off, rfin = blocks(off, np.asarray(gm, dtype=np.int64)[None, :], np.asarray(rn, dtype=np.int64)[None, :])
-    elif kind == "tally":
-        # operand limbs of block t: the remainder cells of the block that produced the operand, or the ciphertext's assigned limbs
-        nb = len(tree)
-        r_of = off + tm.cells * np.arange(nb, dtype=np.int64)[:, None] + tm.r_cells[None, :]
-        table = np.concatenate([r_of, np.asarray(ct_c[::-1], dtype=np.int64)])     # index -(1 + i) -> c_(i+1)
-        tr = np.asarray(tree, dtype=np.int64)
-        off, rfin = blocks(off, table[tr[:, 0]], table[tr[:, 1]])
-        rfin = rfin[-1:]
-        n_steps[0] = nb
-    else:
-        off, rfin = blocks(off, np.asarray(ext_l(x_c), dtype=np.int64)[None, :], np.asarray(ext_l(y_c), dtype=np.int64)[None, :])
-    roots = c_cells if kind in ("ballot", "partial", "mix", "sballot", "smix", "pballot") else [rfin[0].tolist()]      # the ballot: one result per ciphertext
-    ws = _Walk(off)
+            powers = [S.word_chain(vs_c[i][j], m_bits, gs_c[j]) for j in range(slots)]      # P_0 .. P_{K-1}, then hs^s_i
+            powers.append(hs_chain(i))
+            # the folds: block q multiplies the running product (P_0, then block q - 1's remainder) by P_{q+1}, the last one by hss
+            table = S.mul_blocks([-1] + list(range(slots - 1)), [-(q + 2) for q in range(slots)], powers)
+            roots.append(table[slots - 1])
+        n_steps[0], n_steps[1] = 2 * m_bits, 2 * s_limbs * limb_bits
+    # ---- suffix: assign_integer(res), assert_equal_fresh (once per result)
+    ws = S.open()
     res_all, eq_cells = [], []
     for c_limbs in roots:
         res_c = _assign(ws, L, limb_bits, lb)
@@ -845,14 +750,14 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
             eq_cell = ws.put()
         res_all += res_c
         eq_cells.append(eq_cell)
-    off = flush(ws)
+    S.flush(ws)
     if dev is None:
-        src, lookup_src = np.concatenate(parts_src), np.concatenate(parts_lk)
+        src, lookup_src = np.concatenate(S.src), np.concatenate(S.lk)
     else:
         cat = lambda parts: torch.cat([p_ if isinstance(p_, torch.Tensor) else torch.as_tensor(p_, dtype=torch.int64).to(dev) for p_ in parts])
-        src, lookup_src = cat(parts_src), cat(parts_lk)
+        src, lookup_src = cat(S.src), cat(S.lk)
     for eq_cell in eq_cells:
-        src[eq_cell] = -(1 + cid(1))      # assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
+        src[eq_cell] = -(1 + S.cid(1))      # assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
     if kind == "partial":
         exposed = list(n_c) + list(v_c) + res_all[:L]
         for j in range(count):
@@ -868,8 +773,8 @@ def stream_structure(kind: str, enc_bits: int, limb_bits: int, lb: int, exp_g: i
     else:
         mid = list(x_c) + list(y_c) if kind == "add" else list(x_c) if statement == "decrypt" else []
         exposed = list(n_c) + list(g_c) + mid + list(res_c)
-    return StructureArrays(n_cells=off, src=src, gate_mask=np.concatenate(parts_mask), lookup_src=lookup_src,
-                           constants=constants, result_cell=eq_cell, n_steps_g=n_steps[0], n_steps_r=n_steps[1],
+    return StructureArrays(n_cells=S.off, src=src, gate_mask=np.concatenate(S.mask), lookup_src=lookup_src,
+                           constants=S.constants, result_cell=eq_cell, n_steps_g=n_steps[0], n_steps_r=n_steps[1],
                            public_cells=np.asarray(exposed, dtype=np.int64))
 
 

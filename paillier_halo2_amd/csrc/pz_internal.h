@@ -176,6 +176,16 @@ struct pz_dev_bufs {
 // n bytes of OS randomness (getrandom, /dev/urandom behind it): the verifier's fold weights, pz_params_check's rho and tau (pz_verify.cpp)
 bool pz_os_random(void* buf, size_t n);
 
+// the per-kind limits of the circuits: what the structure generator (pz_structure.hip) and the expansion (pz_witness.hip) refuse alike
+#define PZ_TALLY_MAX 65536    // ciphertexts of a tally or a weighted tally (kinds 3, 4)
+#define PZ_ENTRIES_MAX 1024   // entries of a ballot, an opening or a mix (kinds 6 .. 11); kind 11: count * slots, its in-circuit values
+#define PZ_WORD_BITS_MAX 64   // bits of a weight, a message or a slot value: one 64-bit word
+#define PZ_SLOTS_MAX 64       // slots of a packed ballot (kind 11)
+static inline bool pz_count_ok(size_t count, size_t lo, size_t max) { return count >= lo && count <= max; }
+static inline bool pz_word_bits_ok(uint32_t bits) { return bits >= 1 && bits <= PZ_WORD_BITS_MAX; }
+static inline bool pz_short_exp_ok(uint32_t s_limbs, uint32_t limbs_n) { return s_limbs >= 1 && s_limbs <= 2 * (uint64_t)limbs_n; }   // of hs^s
+static inline bool pz_slots_ok(size_t count, uint32_t slots) { return slots >= 1 && slots <= PZ_SLOTS_MAX && count * slots <= PZ_ENTRIES_MAX; }
+
 // the circuit structure handle (pz_circuit_structure_dev, pz_structure.hip).  pz_structure_expose (pz_public.hip) adds the instance column:
 // d_map_col / d_map_row are then [m + 1][2^k] and d_cell_col / d_cell_row hold the (column, row) of the n_public exposed advice cells
 struct pz_structure {

@@ -360,12 +360,17 @@ struct Part {
     std::vector<i64> a, b, s;         // blocks: [ns][L] operand cells, [ns] the bit's cell (uniform)
 };
 
+typedef std::vector<i64> Cells;
+
+// The advice stream as a sequence of parts, and the shared parts every circuit kind's stream is composed of (build_stream below; the same
+// names in circuit_structure.py).  The stream's end n_cells is where the next part starts: every part is appended there.
 struct Stream {
     std::vector<Part> parts;
     std::vector<Template> tmpls;
     std::vector<C256> constants;
     std::map<C256, int> const_id;
-    std::vector<i64> fresh;
+    Cells fresh;
+    unsigned L = 0, W = 0, lb = 0;   // limbs of n^2, limb width, lookup bits
     i64 n_cells = 0, n_lk = 0, result_cell = 0;
     size_t n_steps_g = 0, n_steps_r = 0;
     std::vector<std::vector<int32_t>> tmpl_cids;   // per template: constant id per const_pos entry
@@ -377,8 +382,9 @@ struct Stream {
         const_id[v] = id;
         return id;
     }
+    Walk open() const { return Walk(n_cells); }
     // a finished walked part -> arrays
-    i64 flush(Walk& w) {
+    void flush(Walk& w) {
         Part p;
         p.cell_off = w.base;
         p.lk_off = n_lk;
@@ -395,7 +401,6 @@ struct Stream {
         n_lk += p.n_lk;
         n_cells = w.base + (i64)w.n();
         parts.push_back(std::move(p));
-        return n_cells;
     }
     void bind_template_constants(int t) {
         std::vector<int32_t> ids;
@@ -405,11 +410,11 @@ struct Stream {
         Template& T = tmpls[(size_t)t];
         for (size_t i = 0; i < T.const_pos.size(); ++i) T.cid[(size_t)T.const_pos[i]] = ids[i];
     }
-    // ns blocks of template t from stream index off; -> the r cells of block `which` are r_of(off, t, which)
-    i64 blocks(i64 off, int t, std::vector<i64>&& a, std::vector<i64>&& b, std::vector<i64>&& s, i64 ns) {
+    // ns blocks of template t at the stream's end -> where they start: output `which` of block blk is r_of(that, t, blk, which)
+    i64 blocks(int t, Cells&& a, Cells&& b, Cells&& s, i64 ns) {
         const Template& T = tmpls[(size_t)t];
         Part p;
-        p.cell_off = off;
+        p.cell_off = n_cells;
         p.lk_off = n_lk;
         p.tmpl = t;
         p.ns = ns;
@@ -417,18 +422,197 @@ struct Stream {
         p.n_lk = ns * (i64)T.lkpos.size();
         p.a = std::move(a); p.b = std::move(b); p.s = std::move(s);
         n_lk += p.n_lk;
-        n_cells = off + p.n_cells;
+        n_cells += p.n_cells;
         parts.push_back(std::move(p));
-        return n_cells;
+        return parts.back().cell_off;
+    }
+    i64 r_of(i64 boff, int t, i64 blk, size_t which) const { return boff + blk * (i64)tmpls[(size_t)t].cells + tmpls[(size_t)t].r_cells[which]; }
+    Cells block_r(i64 boff, i64 blk = 0) const {   // the remainder cells of a mul_mod block
+        Cells v(L);
+        for (unsigned j = 0; j < L; ++j) v[j] = r_of(boff, 0, blk, j);
+        return v;
+    }
+
+    // the uniform template (template 1) of a circuit with in-circuit bits: added once, its constants bound
+    void uniform() {
+        if (tmpls.size() > 1) return;
+        tmpls.push_back(uniform_template(L, W, lb));
+        bind_template_constants(1);
+    }
+    // a chain's head in the open walk: assign_constant(1), load_zero -> the initial acc cells [one, zero, ..]
+    Cells head(Walk& w) const {
+        const i64 one = w.putc(c_small(1)), z2 = w.putc(c_small(0));
+        Cells acc(L, z2);
+        acc[0] = one;
+        return acc;
+    }
+    // num_to_bits(word_cell, nbits) behind what the open walk wb holds, flushed, then nbits blocks of the uniform template chained through
+    // acc (select outputs) and sq (square remainders): the chain's state, in and out
+    void bit_chain(Walk& wb, i64 word_cell, unsigned nbits, Cells& acc, Cells& sq) {
+        Cells bit_cells{wb.put()};
+        if (nbits > 1) wb.gate(bit_cells[0]);
+        i64 acc_cell = bit_cells[0];
+        for (unsigned i = 1; i < nbits; ++i) {
+            bit_cells.push_back(wb.put());
+            wb.putc(c_pow2(i));
+            acc_cell = wb.put();
+            if (i < nbits - 1) wb.gate(acc_cell);
+        }
+        wb.pair(word_cell, acc_cell);   // (nbits = 1: the accumulator IS the bit)
+        for (i64 bc : bit_cells) {
+            const i64 g_ = wb.putc(c_small(0));
+            wb.gate(g_);
+            wb.put(bc); wb.put(bc); wb.put(bc);
+        }
+        flush(wb);
+        const i64 boff = n_cells;
+        Cells a((size_t)nbits * L), b((size_t)nbits * L);
+        for (unsigned t = 0; t < nbits; ++t)
+            for (unsigned j = 0; j < L; ++j) {
+                a[(size_t)t * L + j] = t == 0 ? acc[j] : r_of(boff, 1, t - 1, j);
+                b[(size_t)t * L + j] = t == 0 ? sq[j] : r_of(boff, 1, t - 1, L + j);
+            }
+        for (unsigned j = 0; j < L; ++j) {
+            acc[j] = r_of(boff, 1, nbits - 1, j);
+            sq[j] = r_of(boff, 1, nbits - 1, L + j);
+        }
+        blocks(1, std::move(a), std::move(b), std::move(bit_cells), nbits);
+    }
+    // pow_mod(base, e) over the n_limbs limb cells of an assigned e: the head as a part of its own, then per limb num_to_bits of ITS cell
+    // and W uniform blocks -> the power's cells (the last select's outputs)
+    Cells limb_chain(const Cells& base_cells, const Cells& limb_cells, unsigned n_limbs) {
+        Walk wc = open();
+        Cells acc = head(wc), sq = base_cells;
+        flush(wc);
+        for (unsigned li = 0; li < n_limbs; ++li) {
+            Walk wb = open();
+            bit_chain(wb, limb_cells[li], W, acc, sq);
+        }
+        return acc;
+    }
+    // pow_mod(base, e) over the nbits bits of a one-cell e: the head and num_to_bits in ONE walk, then nbits uniform blocks -> the power's cells
+    Cells word_chain(i64 word_cell, unsigned nbits, const Cells& base_cells) {
+        Walk wb = open();
+        Cells acc = head(wb), sq = base_cells;
+        bit_chain(wb, word_cell, nbits, acc, sq);
+        return acc;
+    }
+    // mul_mod blocks from WHICH block produced each operand: a_blk / b_blk[q] >= 0 names a block of this run (its remainder), the entry
+    // -(1 + i) the cells outer[i] from outside the run -> where the run starts (no block: no part)
+    i64 mul_blocks(const Cells& a_blk, const Cells& b_blk, const std::vector<Cells>& outer) {
+        const i64 boff = n_cells, ns = (i64)a_blk.size();
+        auto operand = [&](i64 blk, unsigned j) -> i64 { return blk < 0 ? outer[(size_t)(-blk - 1)][j] : r_of(boff, 0, blk, j); };
+        Cells a((size_t)ns * L), b((size_t)ns * L);
+        for (i64 q = 0; q < ns; ++q)
+            for (unsigned j = 0; j < L; ++j) {
+                a[(size_t)q * L + j] = operand(a_blk[(size_t)q], j);
+                b[(size_t)q * L + j] = operand(b_blk[(size_t)q], j);
+            }
+        if (ns) blocks(0, std::move(a), std::move(b), {}, ns);
+        return boff;
+    }
+    Cells mul_block(const Cells& a, const Cells& b) { return block_r(blocks(0, Cells(a), Cells(b), {}, 1)); }   // one mul_mod(a, b) -> r's cells
+    // pow_mod_fixed_exp(base, e): the head, then per bit of e the squaring step (cur, cur) and on a set bit (acc, cur): block -1 is the
+    // base, block -2 the head -> the number of blocks; res = the power's cells
+    i64 fixed_chain(const Cells& base, const u64* e, Cells& res) {
+        Walk wc = open();
+        const std::vector<Cells> outer{base, head(wc)};
+        flush(wc);
+        int top = (int)((L / 2 * W + 63) / 64) - 1;      // the exponent: ceil(limbs_n * limb_bits / 64) words
+        while (top >= 0 && e[top] == 0) --top;
+        const size_t bits = top < 0 ? 0 : (size_t)top * 64 + (64 - __builtin_clzll(e[top]));
+        Cells a_blk, b_blk;
+        i64 sq_blk = -1, acc_blk = -2, t = 0;
+        for (size_t bi = 0; bi < bits; ++bi) {
+            a_blk.push_back(sq_blk); b_blk.push_back(sq_blk);
+            const i64 cur_blk = sq_blk;
+            sq_blk = t++;
+            if ((e[bi / 64] >> (bi % 64)) & 1) {
+                a_blk.push_back(acc_blk); b_blk.push_back(cur_blk);
+                acc_blk = t++;
+            }
+        }
+        const i64 boff = mul_blocks(a_blk, b_blk, outer);
+        res = acc_blk < 0 ? outer[(size_t)(-acc_blk - 1)] : block_r(boff, acc_blk);
+        return t;
+    }
+    // the product of the leaves, level by level the neighbours of the current list, an odd last element carried up; blocks are numbered as
+    // the loop creates them (level-major), leaf i is entry -(1 + i) -> the root's cells (one leaf: no block, the leaf); n_blocks
+    Cells product_tree(const std::vector<Cells>& leaves, size_t& n_blocks) {
+        Cells cur(leaves.size()), a_blk, b_blk;
+        for (size_t i = 0; i < leaves.size(); ++i) cur[i] = -(1 + (i64)i);
+        while (cur.size() > 1) {
+            Cells nxt;
+            for (size_t j = 0; j + 1 < cur.size(); j += 2) {
+                nxt.push_back((i64)a_blk.size());
+                a_blk.push_back(cur[j]); b_blk.push_back(cur[j + 1]);
+            }
+            if (cur.size() & 1) nxt.push_back(cur.back());
+            cur.swap(nxt);
+        }
+        n_blocks = a_blk.size();
+        const i64 boff = mul_blocks(a_blk, b_blk, leaves);
+        return n_blocks ? block_r(boff, (i64)n_blocks - 1) : leaves[0];     // the root is the last block
+    }
+    // the Benes network over `ins` as ONE walked part: per layer and switch assert_bit of the switch's own bit cell, then per limb
+    // select(in[j'], in[j], b) and select(in[j], in[j'], b), the operands the previous layer's outputs -> the outputs' cells
+    std::vector<Cells> network(const std::vector<Cells>& ins) {
+        const size_t count = ins.size();
+        Walk wn = open();
+        auto select = [&](i64 x, i64 y, i64 s) {   // FlexGate::select(x, y, s): [d | 1 | y | x | y | s | d | out], windows at 0 and 4
+            const i64 c_d = wn.put();
+            wn.gate(c_d);
+            wn.putc(c_small(1)); wn.put(y); wn.put(x);
+            const i64 g = wn.put(y);
+            wn.gate(g);
+            wn.put(s); wn.put(c_d);
+            return wn.put();
+        };
+        unsigned d = 0;
+        while (((size_t)1 << d) < count) ++d;
+        const unsigned layers = count > 1 ? 2 * d - 1 : 0;
+        std::vector<Cells> cur_c = ins;
+        for (unsigned ly = 0; ly < layers; ++ly) {
+            const unsigned beta = ly < d ? ly : layers - 1 - ly;
+            std::vector<Cells> nxt_c(count);
+            for (size_t j = 0; j < count; ++j) {
+                if ((j >> beta) & 1) continue;
+                const size_t jp = j | ((size_t)1 << beta);
+                const i64 g = wn.putc(c_small(0));   // assert_bit: [0, b, b, b], the first b the bit's own cell
+                wn.gate(g);
+                const i64 b_c = wn.put();
+                wn.put(b_c); wn.put(b_c);
+                nxt_c[j].resize(L); nxt_c[jp].resize(L);
+                for (unsigned t = 0; t < L; ++t) {
+                    nxt_c[j][t] = select(cur_c[jp][t], cur_c[j][t], b_c);
+                    nxt_c[jp][t] = select(cur_c[j][t], cur_c[jp][t], b_c);
+                }
+            }
+            cur_c.swap(nxt_c);
+        }
+        flush(wn);
+        return cur_c;
     }
 };
+// FlexGate::sum over n cells: m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..; a window every 3 cells, the operands copies of the cells above
+// -> the last sum's cell (fewer than two cells: nothing is emitted)
+i64 flex_sum(Walk& w, const i64* cells, size_t n) {
+    if (n < 2) return NONE;
+    i64 sum_c = w.put(cells[0]);
+    for (size_t i = 1; i < n; ++i) {
+        w.gate(sum_c);
+        w.putc(c_small(1));
+        w.put(cells[i]);
+        sum_c = w.put();
+    }
+    return sum_c;
+}
 
 // kind 3 (the tally): `count` ciphertexts assigned at full width after n, no load_zero, the count - 1 blocks of
-// the product tree (level by level the neighbours of the current list, an odd last element carried up), res, assert_equal_fresh
+// the product tree, res, assert_equal_fresh
 // kind 4 (the weighted tally): as kind 3 up to the refresh, with `count` load_witness cells (the weights) after
-// the ciphertexts; then per ciphertext pow_mod over w_bits in-circuit bits -- [1, 0], num_to_bits of the weight's cell, w_bits uniform
-// blocks from the chain's OWN one / zero and assign_integer(c_i)'s limbs --, the count - 1 tree blocks over the powers (the last
-// select's outputs of every chain), res, assert_equal_fresh.  Two parts per chain (its head, its blocks).
+// the ciphertexts; then per ciphertext pow_mod over w_bits in-circuit bits -- a word_chain from the chain's OWN one / zero and
+// assign_integer(c_i)'s limbs --, the count - 1 tree blocks over the powers, res, assert_equal_fresh.  Two parts per chain.
 // kind 6 (the ballot): n, g, `count` load_witness cells (the messages), for count >= 2 FlexGate::sum over them,
 // assign_integer(r_i) for every entry, square + refresh, load_zero; per entry pow_mod(g_ext, m_i) over w_bits (= m_bits) in-circuit bits,
 // pow_mod_fixed_exp(r_i_ext, exp_r = n) and the final block; then per entry res_i and assert_equal_fresh.  Five parts per entry.
@@ -436,66 +620,43 @@ struct Stream {
 // refresh, load_zero; pow_mod(v, theta) as kind 2 emits it with theta's 2 Ln limb cells as the num_to_bits inputs; per ciphertext the
 // block mul_mod(c_j, c_j) and pow_mod(s_j, theta) from its remainder; then assign_integer + assert_equal_fresh for h and for every u_j.
 // kind 8 (the mix): n, `count` = 2^d ciphertexts at full width, assign_integer(r_i) for every output, square +
-// refresh, load_zero; the Benes network as ONE walked part -- per layer and switch assert_bit of the switch's own bit cell, then per
-// limb select(in[j'], in[j], b) and select(in[j], in[j'], b), the operands the previous layer's outputs --; per output
-// pow_mod_fixed_exp(r_i_ext, exp_r = n) and the block mul_mod(d_i, rn_i); then per output res_i and assert_equal_fresh.
+// refresh, load_zero; the Benes network; per output pow_mod_fixed_exp(r_i_ext, exp_r = n) and the block mul_mod(d_i, rn_i); then per
+// output res_i and assert_equal_fresh.
 // kind 9 (the short-randomness ballot): n, g, hs at full width, `count` load_witness cells (the messages), for
 // count >= 2 FlexGate::sum over them, assign_integer(s_i) of s_limbs limbs for every entry, square + refresh, load_zero; per entry
-// pow_mod(g_ext, m_i) over w_bits (= m_bits) in-circuit bits as kind 6, pow_mod(hs, s_i) as kind 7 walks a chain -- [1, 0], then per limb
-// of s_i num_to_bits of ITS limb cell and W uniform blocks, the first sq hs's limb cells -- and the final block; then per entry res_i and
-// assert_equal_fresh.  No exponent of the key shapes it: one structure serves every key of a size.
+// pow_mod(g_ext, m_i) over w_bits (= m_bits) in-circuit bits as kind 6, pow_mod(hs, s_i) as kind 7 walks a chain -- a limb_chain over
+// s_i's limb cells, the first sq hs's limb cells -- and the final block; then per entry res_i and assert_equal_fresh.  No exponent of
+// the key shapes it: one structure serves every key of a size.
 // kind 10 (the short-randomness mix): n, hs and `count` = 2^d ciphertexts at full width, assign_integer(s_i) of
-// s_limbs limbs for every output, square + refresh, load_zero; kind 8's network walk; per output kind 9's hs-chain walk -- [1, 0], then
-// per limb of s_i num_to_bits of ITS limb cell and W uniform blocks, the first sq hs's limb cells -- and the block mul_mod(d_i, hss_i);
-// then per output res_i and assert_equal_fresh.  No exponent of the key shapes it.
+// s_limbs limbs for every output, square + refresh, load_zero; kind 8's network; per output kind 9's hs-chain and the block
+// mul_mod(d_i, hss_i); then per output res_i and assert_equal_fresh.  No exponent of the key shapes it.
 // kind 11 (the packed ballot): n, hs and the `slots` bases G_j at full width, count * slots load_witness cells
 // (the values, ciphertext-major), for slots >= 2 one FlexGate::sum per ciphertext, assign_integer(s_i) of s_limbs limbs for every
 // ciphertext, square + refresh, load_zero; per ciphertext, per slot pow_mod(G_j, v_ij) over w_bits (= m_bits) in-circuit bits -- the
-// first sq G_j's OWN limb cells, for every ciphertext --, kind 9's hs-chain walk, and the `slots` fold blocks (P_0, P_1), (t_1, P_2), ..,
+// first sq G_j's OWN limb cells, for every ciphertext --, kind 9's hs-chain, and the `slots` fold blocks (P_0, P_1), (t_1, P_2), ..,
 // (t_{K-1}, hss); then per ciphertext res_i and assert_equal_fresh.  Neither n, g nor the slot width shapes it.
 int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_g, const u64* exp_r, size_t count, unsigned w_bits,
                  unsigned s_limbs, unsigned slots, Stream& S) {
     const unsigned L = 2 * Ln;
+    S.L = L; S.W = W; S.lb = lb;
     S.tmpls.reserve(2);                  // (references to the templates stay valid when a circuit with in-circuit bits adds the second one)
     S.tmpls.push_back(block_template(L, W, lb));
-    const Template& tm = S.tmpls[0];
     // ---- prefix: the four assign_integer (tally: n, then the ciphertexts), square, refresh, load_zero (not in a tally)
     Walk w(0);
-    const std::vector<i64> n_c = assign(w, Ln, W, lb);
-    std::vector<i64> g_c, x_c, y_c;
-    std::vector<std::vector<i64>> ct_c;
-    std::vector<i64> wt_c;
-    std::vector<std::vector<i64>> rs_c;
-    i64 sum_c = NONE;
+    const Cells n_c = assign(w, Ln, W, lb);
+    Cells g_c, x_c, y_c, wt_c;
+    std::vector<Cells> ct_c, rs_c;
     if (kind == 6 || kind == 9) {
         g_c = assign(w, Ln, W, lb);
         if (kind == 9) x_c = assign(w, L, W, lb);   // hs: the key's second base, full width
         for (size_t i = 0; i < count; ++i) wt_c.push_back(w.put());   // load_witness(m_i): one cell, no gate
-        if (count >= 2) {
-            // FlexGate::sum: m_1 | 1 | m_2 | s_2 | 1 | m_3 | s_3 | ..; a window every 3 cells, the operands copies of the cells above
-            sum_c = w.put(wt_c[0]);
-            for (size_t i = 1; i < count; ++i) {
-                w.gate(sum_c);
-                w.putc(c_small(1));
-                w.put(wt_c[i]);
-                sum_c = w.put();
-            }
-        }
+        flex_sum(w, wt_c.data(), count);
         for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, kind == 9 ? s_limbs : Ln, W, lb));   // r_i; kind 9: s_i
     } else if (kind == 11) {
         x_c = assign(w, L, W, lb);                                               // hs
         for (unsigned j = 0; j < slots; ++j) ct_c.push_back(assign(w, L, W, lb));   // G_j: the slot bases, full width
         for (size_t i = 0; i < count * slots; ++i) wt_c.push_back(w.put());       // load_witness(v_ij): one cell, no gate
-        if (slots >= 2)
-            for (size_t i = 0; i < count; ++i) {   // FlexGate::sum over the ciphertext's own values, as kind 6's
-                i64 acc = w.put(wt_c[i * slots]);
-                for (unsigned j = 1; j < slots; ++j) {
-                    w.gate(acc);
-                    w.putc(c_small(1));
-                    w.put(wt_c[i * slots + j]);
-                    acc = w.put();
-                }
-            }
+        for (size_t i = 0; i < count; ++i) flex_sum(w, wt_c.data() + i * slots, slots);   // over the ciphertext's own values
         for (size_t i = 0; i < count; ++i) rs_c.push_back(assign(w, s_limbs, W, lb));   // s_i
     } else if (kind == 8 || kind == 10) {
         if (kind == 10) x_c = assign(w, L, W, lb);   // hs: the key's second base, full width
@@ -512,12 +673,12 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
     } else {
         g_c = assign(w, Ln, W, lb); x_c = assign(w, Ln, W, lb); y_c = assign(w, Ln, W, lb);
     }
-    const std::vector<i64> prod = mul_cells(w, n_c, n_c, 2 * Ln - 1);
+    const Cells prod = mul_cells(w, n_c, n_c, 2 * Ln - 1);
     std::vector<u8> inc(4 * Ln + 8);
     uint32_t n_inc = 0;
     PZCHK(pz_refresh_aux(W, Ln, Ln, inc.data(), (uint32_t)inc.size(), &n_inc));
     w.putc(c_small(0));
-    std::vector<i64> cur(prod);
+    Cells cur(prod);
     cur.resize(n_inc, NONE);
     for (uint32_t i = 0; i < n_inc; ++i) {
         i64 limb = cur[i];
@@ -541,355 +702,85 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
     }
     if (S.fresh.size() != L) return PZ_ERR_UNSUPPORTED;   // the refreshed n^2 has l + r limbs for every shape of this circuit
     const i64 zero = kind == 3 || kind == 4 ? NONE : w.putc(c_small(0));
-    auto ext_l = [&](const std::vector<i64>& limbs) {
-        std::vector<i64> v(limbs);
+    auto ext_l = [&](const Cells& limbs) {
+        Cells v(limbs);
         v.resize(L, zero);
         return v;
     };
-    i64 off = S.flush(w);
+    S.flush(w);
     S.bind_template_constants(0);
-    auto r_of = [&](i64 boff, const Template& T, i64 blk, size_t which) { return boff + blk * (i64)T.cells + T.r_cells[which]; };
+    if (kind == 2 || kind == 4 || kind == 6 || kind == 7 || kind >= 9) S.uniform();   // the kinds with in-circuit bits
 
-    // num_to_bits(word_cell, nbits) at `off`, then nbits blocks of the uniform template (S.tmpls[1]) chained through acc (select outputs)
-    // and sq (square remainders); acc_cells / sq_cells: the chain's state, in and out
-    auto bit_chain = [&](i64 off_, Walk& wb, i64 word_cell, unsigned nbits, std::vector<i64>& acc_cells, std::vector<i64>& sq_cells) -> i64 {
-        const Template& ut = S.tmpls[1];
-        std::vector<i64> bit_cells{wb.put()};
-        if (nbits > 1) wb.gate(bit_cells[0]);
-        i64 acc_cell = bit_cells[0];
-        for (unsigned i = 1; i < nbits; ++i) {
-            bit_cells.push_back(wb.put());
-            wb.putc(c_pow2(i));
-            acc_cell = wb.put();
-            if (i < nbits - 1) wb.gate(acc_cell);
-        }
-        wb.pair(word_cell, acc_cell);   // (nbits = 1: the accumulator IS the bit)
-        for (i64 bc : bit_cells) {
-            const i64 g_ = wb.putc(c_small(0));
-            wb.gate(g_);
-            wb.put(bc); wb.put(bc); wb.put(bc);
-        }
-        off_ = S.flush(wb);
-        std::vector<i64> a((size_t)nbits * L), b((size_t)nbits * L), s_(nbits);
-        for (unsigned t = 0; t < nbits; ++t) {
-            for (unsigned j = 0; j < L; ++j) {
-                a[(size_t)t * L + j] = t == 0 ? acc_cells[j] : r_of(off_, ut, t - 1, j);
-                b[(size_t)t * L + j] = t == 0 ? sq_cells[j] : r_of(off_, ut, t - 1, L + j);
-            }
-            s_[t] = bit_cells[t];
-        }
-        for (unsigned j = 0; j < L; ++j) {
-            acc_cells[j] = r_of(off_, ut, nbits - 1, j);
-            sq_cells[j] = r_of(off_, ut, nbits - 1, L + j);
-        }
-        return S.blocks(off_, 1, std::move(a), std::move(b), std::move(s_), nbits);
-    };
-
-    std::vector<i64> gm, rn;   // the cells holding g^m and r^n
-    std::vector<i64> root_c;   // the cells holding the circuit's result
-    std::vector<std::vector<i64>> roots;   // kind 6: one result per entry
-    // pow_mod_fixed_exp(base, e) at `off`: [1, 0], then per bit of e the squaring step (cur, cur) and on a set bit (acc, cur).  Which BLOCK
-    // produced each operand is structure: block indices first, the operand cells follow from them (-1: the base, -2: the constant one).
-    // -> the number of blocks; res = the power's cells
-    auto fixed_chain = [&](const std::vector<i64>& base, const u64* e, std::vector<i64>& res) -> i64 {
-        Walk wc(off);
-        const i64 one = wc.putc(c_small(1)), z2 = wc.putc(c_small(0));
-        off = S.flush(wc);
-        int top = (int)((Ln * W + 63) / 64) - 1;      // the exponent: ceil(limbs_n * limb_bits / 64) words
-        while (top >= 0 && e[top] == 0) --top;
-        const size_t bits = top < 0 ? 0 : (size_t)top * 64 + (64 - __builtin_clzll(e[top]));
-        std::vector<i64> a_blk, b_blk;
-        i64 sq_blk = -1, acc_blk = -2, t = 0;
-        for (size_t bi = 0; bi < bits; ++bi) {
-            a_blk.push_back(sq_blk); b_blk.push_back(sq_blk);
-            const i64 cur_blk = sq_blk;
-            sq_blk = t++;
-            if ((e[bi / 64] >> (bi % 64)) & 1) {
-                a_blk.push_back(acc_blk); b_blk.push_back(cur_blk);
-                acc_blk = t++;
-            }
-        }
-        const i64 ns = t;
-        auto operand = [&](i64 blk, unsigned j) -> i64 {
-            if (blk == -2) return j == 0 ? one : z2;
-            if (blk == -1) return base[j];
-            return r_of(off, tm, blk, j);
-        };
-        std::vector<i64> a((size_t)ns * L), b((size_t)ns * L);
-        for (i64 q = 0; q < ns; ++q)
-            for (unsigned j = 0; j < L; ++j) {
-                a[(size_t)q * L + j] = operand(a_blk[(size_t)q], j);
-                b[(size_t)q * L + j] = operand(b_blk[(size_t)q], j);
-            }
-        res.resize(L);
-        for (unsigned j = 0; j < L; ++j) res[j] = operand(acc_blk, j);
-        if (ns) off = S.blocks(off, 0, std::move(a), std::move(b), {}, ns);
-        return ns;
-    };
-    auto block_r = [&](i64 boff) {
-        std::vector<i64> v(L);
-        for (unsigned j = 0; j < L; ++j) v[j] = r_of(boff, tm, 0, j);
-        return v;
-    };
-    if (kind == 0 || kind == 2) {
-        struct Chain { std::vector<i64> base; const u64* e; };
-        Chain chains[2] = {{ext_l(g_c), exp_g}, {ext_l(y_c), exp_r}};
-        int first_chain = 0;
-        if (kind == 2) {
-            // g^m over ALL Ln * W bits of m IN the circuit: assign_constant(1), load_zero, then per limb of m num_to_bits and per bit the
-            // (mul_mod, select, square_mod) block -- the same shape for every message
-            S.tmpls.push_back(uniform_template(L, W, lb));
-            S.bind_template_constants(1);
-            Walk wc(off);
-            const i64 one = wc.putc(c_small(1)), z2 = wc.putc(c_small(0));
-            off = S.flush(wc);
-            std::vector<i64> acc_cells(L, z2), sq_cells = ext_l(g_c);
-            acc_cells[0] = one;
-            for (unsigned li = 0; li < Ln; ++li) {
-                Walk wb(off);
-                off = bit_chain(off, wb, x_c[li], W, acc_cells, sq_cells);
-            }
-            S.n_steps_g = 2 * (size_t)Ln * W;
-            gm = acc_cells;
-            first_chain = 1;
-        }
-        for (int ci = first_chain; ci < 2; ++ci)
-            (ci == 0 ? S.n_steps_g : S.n_steps_r) = (size_t)fixed_chain(chains[ci].base, chains[ci].e, ci == 0 ? gm : rn);
-    } else if (kind == 6) {
-        S.tmpls.push_back(uniform_template(L, W, lb));
-        S.bind_template_constants(1);
-        for (size_t i = 0; i < count; ++i) {
-            Walk wb(off);   // the g-chain's head: assign_constant(1), load_zero, then num_to_bits
-            const i64 one = wb.putc(c_small(1)), z2 = wb.putc(c_small(0));
-            std::vector<i64> acc_cells(L, z2), sq_cells = ext_l(g_c);
-            acc_cells[0] = one;
-            off = bit_chain(off, wb, wt_c[i], w_bits, acc_cells, sq_cells);
-            S.n_steps_r = (size_t)fixed_chain(ext_l(rs_c[i]), exp_r, rn);
-            roots.push_back(block_r(off));
-            off = S.blocks(off, 0, std::vector<i64>(acc_cells), std::vector<i64>(rn), {}, 1);
-        }
-        S.n_steps_g = 2 * (size_t)w_bits;
-    } else if (kind == 9) {
-        S.tmpls.push_back(uniform_template(L, W, lb));
-        S.bind_template_constants(1);
-        for (size_t i = 0; i < count; ++i) {
-            Walk wb(off);   // the g-chain's head: assign_constant(1), load_zero, then num_to_bits
-            const i64 one = wb.putc(c_small(1)), z2 = wb.putc(c_small(0));
-            std::vector<i64> gm_cells(L, z2), sq_cells = ext_l(g_c);
-            gm_cells[0] = one;
-            off = bit_chain(off, wb, wt_c[i], w_bits, gm_cells, sq_cells);
-            // pow_mod(hs, s_i): kind 7's walk over the s_limbs limbs of s_i -- every entry's chain starts from the SAME hs cells
-            Walk wc(off);
-            const i64 one_s = wc.putc(c_small(1)), z2_s = wc.putc(c_small(0));
-            off = S.flush(wc);
-            std::vector<i64> acc_cells(L, z2_s);
-            sq_cells = x_c;
-            acc_cells[0] = one_s;
-            for (unsigned li = 0; li < s_limbs; ++li) {
-                Walk wl(off);
-                off = bit_chain(off, wl, rs_c[i][li], W, acc_cells, sq_cells);
-            }
-            roots.push_back(block_r(off));
-            off = S.blocks(off, 0, std::move(gm_cells), std::move(acc_cells), {}, 1);
-        }
-        S.n_steps_g = 2 * (size_t)w_bits;
-        S.n_steps_r = 2 * (size_t)s_limbs * W;
-    } else if (kind == 11) {
-        S.tmpls.push_back(uniform_template(L, W, lb));
-        S.bind_template_constants(1);
-        for (size_t i = 0; i < count; ++i) {
-            std::vector<std::vector<i64>> powers;
-            for (unsigned j = 0; j < slots; ++j) {
-                Walk wb(off);   // a slot chain's head: assign_constant(1), load_zero, then num_to_bits; its first sq is G_j's limb cells
-                const i64 one = wb.putc(c_small(1)), z2 = wb.putc(c_small(0));
-                std::vector<i64> acc_cells(L, z2), sq_cells = ct_c[j];
-                acc_cells[0] = one;
-                off = bit_chain(off, wb, wt_c[i * slots + j], w_bits, acc_cells, sq_cells);
-                powers.push_back(std::move(acc_cells));
-            }
-            Walk wc(off);   // pow_mod(hs, s_i): kind 9's walk
-            const i64 one_s = wc.putc(c_small(1)), z2_s = wc.putc(c_small(0));
-            off = S.flush(wc);
-            std::vector<i64> hss(L, z2_s), sq_cells = x_c;
-            hss[0] = one_s;
-            for (unsigned li = 0; li < s_limbs; ++li) {
-                Walk wl(off);
-                off = bit_chain(off, wl, rs_c[i][li], W, hss, sq_cells);
-            }
-            // the folds: block q multiplies the running product (P_0, then block q - 1's remainder) by P_{q+1}, the last one by hss
-            std::vector<i64> a((size_t)slots * L), b((size_t)slots * L);
-            for (unsigned q = 0; q < slots; ++q)
-                for (unsigned j = 0; j < L; ++j) {
-                    a[(size_t)q * L + j] = q == 0 ? powers[0][j] : r_of(off, tm, q - 1, j);
-                    b[(size_t)q * L + j] = q + 1 < slots ? powers[q + 1][j] : hss[j];
-                }
-            roots.push_back(block_r(off + (i64)(slots - 1) * (i64)tm.cells));
-            off = S.blocks(off, 0, std::move(a), std::move(b), {}, slots);
-        }
-        S.n_steps_g = 2 * (size_t)w_bits;
-        S.n_steps_r = 2 * (size_t)s_limbs * W;
-    } else if (kind == 8 || kind == 10) {
-        if (kind == 10) {
-            S.tmpls.push_back(uniform_template(L, W, lb));
-            S.bind_template_constants(1);
-        }
-        Walk wn(off);
-        auto select = [&](i64 x, i64 y, i64 s) {   // FlexGate::select(x, y, s): [d | 1 | y | x | y | s | d | out], windows at 0 and 4
-            const i64 c_d = wn.put();
-            wn.gate(c_d);
-            wn.putc(c_small(1)); wn.put(y); wn.put(x);
-            const i64 g = wn.put(y);
-            wn.gate(g);
-            wn.put(s); wn.put(c_d);
-            return wn.put();
-        };
-        unsigned d = 0;
-        while (((size_t)1 << d) < count) ++d;
-        const unsigned layers = count > 1 ? 2 * d - 1 : 0;
-        std::vector<std::vector<i64>> cur_c = ct_c;
-        for (unsigned ly = 0; ly < layers; ++ly) {
-            const unsigned beta = ly < d ? ly : layers - 1 - ly;
-            std::vector<std::vector<i64>> nxt_c(count);
-            for (size_t j = 0; j < count; ++j) {
-                if ((j >> beta) & 1) continue;
-                const size_t jp = j | ((size_t)1 << beta);
-                const i64 g = wn.putc(c_small(0));   // assert_bit: [0, b, b, b], the first b the bit's own cell
-                wn.gate(g);
-                const i64 b_c = wn.put();
-                wn.put(b_c); wn.put(b_c);
-                nxt_c[j].resize(L); nxt_c[jp].resize(L);
-                for (unsigned t = 0; t < L; ++t) {
-                    nxt_c[j][t] = select(cur_c[jp][t], cur_c[j][t], b_c);
-                    nxt_c[jp][t] = select(cur_c[j][t], cur_c[jp][t], b_c);
-                }
-            }
-            cur_c.swap(nxt_c);
-        }
-        off = S.flush(wn);
-        if (kind == 8) {
-            for (size_t i = 0; i < count; ++i) {
-                S.n_steps_r = (size_t)fixed_chain(ext_l(rs_c[i]), exp_r, rn);
-                roots.push_back(block_r(off));
-                off = S.blocks(off, 0, std::vector<i64>(cur_c[i]), std::vector<i64>(rn), {}, 1);
-            }
-        } else {
-            for (size_t i = 0; i < count; ++i) {
-                // pow_mod(hs, s_i): kind 9's walk over the s_limbs limbs of s_i -- every output's chain starts from the SAME hs cells
-                Walk wc(off);
-                const i64 one_s = wc.putc(c_small(1)), z2_s = wc.putc(c_small(0));
-                off = S.flush(wc);
-                std::vector<i64> acc_cells(L, z2_s), sq_cells = x_c;
-                acc_cells[0] = one_s;
-                for (unsigned li = 0; li < s_limbs; ++li) {
-                    Walk wl(off);
-                    off = bit_chain(off, wl, rs_c[i][li], W, acc_cells, sq_cells);
-                }
-                roots.push_back(block_r(off));
-                off = S.blocks(off, 0, std::vector<i64>(cur_c[i]), std::move(acc_cells), {}, 1);
-            }
-            S.n_steps_r = 2 * (size_t)s_limbs * W;
-        }
-    } else if (kind == 7) {
-        S.tmpls.push_back(uniform_template(L, W, lb));
-        S.bind_template_constants(1);
-        // pow_mod(base, theta): kind 2's walk over ALL 2 Ln limbs of theta -- every chain decomposes the SAME limb cells
-        auto theta_chain = [&](const std::vector<i64>& base) {
-            Walk wc(off);
-            const i64 one = wc.putc(c_small(1)), z2 = wc.putc(c_small(0));
-            off = S.flush(wc);
-            std::vector<i64> acc_cells(L, z2), sq_cells = base;
-            acc_cells[0] = one;
-            for (unsigned li = 0; li < L; ++li) {
-                Walk wb(off);
-                off = bit_chain(off, wb, x_c[li], W, acc_cells, sq_cells);
-            }
-            roots.push_back(acc_cells);
-        };
-        theta_chain(g_c);
-        for (size_t i = 0; i < count; ++i) {
-            const std::vector<i64> s_c = block_r(off);   // s_j = c_j^2: the chain's base
-            off = S.blocks(off, 0, std::vector<i64>(ct_c[i]), std::vector<i64>(ct_c[i]), {}, 1);
-            theta_chain(s_c);
-        }
-        S.n_steps_g = 2 * (size_t)L * W;
-    } else if (kind == 3) {
-        // operands as (producing block | -(1 + ciphertext)); blocks are numbered as the loop creates them: level-major
-        std::vector<i64> cur(count), a_blk, b_blk;
-        for (size_t i = 0; i < count; ++i) cur[i] = -(1 + (i64)i);
-        while (cur.size() > 1) {
-            std::vector<i64> nxt;
-            for (size_t j = 0; j + 1 < cur.size(); j += 2) {
-                nxt.push_back((i64)a_blk.size());
-                a_blk.push_back(cur[j]); b_blk.push_back(cur[j + 1]);
-            }
-            if (cur.size() & 1) nxt.push_back(cur.back());
-            cur.swap(nxt);
-        }
-        const i64 ns = (i64)a_blk.size();
-        auto operand = [&](i64 blk, unsigned j) -> i64 { return blk < 0 ? ct_c[(size_t)(-blk - 1)][j] : r_of(off, tm, blk, j); };
-        std::vector<i64> a((size_t)ns * L), b((size_t)ns * L);
-        for (i64 q = 0; q < ns; ++q)
-            for (unsigned j = 0; j < L; ++j) {
-                a[(size_t)q * L + j] = operand(a_blk[(size_t)q], j);
-                b[(size_t)q * L + j] = operand(b_blk[(size_t)q], j);
-            }
-        S.n_steps_g = (size_t)ns;
-        const i64 tree_off = off;
-        off = S.blocks(off, 0, std::move(a), std::move(b), {}, ns);
-        root_c = block_r(tree_off + (ns - 1) * (i64)tm.cells);     // the root is the last block
-    } else if (kind == 4) {
-        S.tmpls.push_back(uniform_template(L, W, lb));
-        S.bind_template_constants(1);
-        std::vector<std::vector<i64>> powers;
-        for (size_t i = 0; i < count; ++i) {
-            Walk wb(off);   // the chain's head: assign_constant(1), load_zero, then num_to_bits
-            const i64 one = wb.putc(c_small(1)), z2 = wb.putc(c_small(0));
-            std::vector<i64> acc_cells(L, z2), sq_cells = ct_c[i];
-            acc_cells[0] = one;
-            off = bit_chain(off, wb, wt_c[i], w_bits, acc_cells, sq_cells);
-            powers.push_back(acc_cells);
-        }
-        S.n_steps_g = 2 * count * w_bits;
-        // the tree over the powers: operands as (producing block | -(1 + chain)), level-major as in kind 3
-        std::vector<i64> cur(count), a_blk, b_blk;
-        for (size_t i = 0; i < count; ++i) cur[i] = -(1 + (i64)i);
-        while (cur.size() > 1) {
-            std::vector<i64> nxt;
-            for (size_t j = 0; j + 1 < cur.size(); j += 2) {
-                nxt.push_back((i64)a_blk.size());
-                a_blk.push_back(cur[j]); b_blk.push_back(cur[j + 1]);
-            }
-            if (cur.size() & 1) nxt.push_back(cur.back());
-            cur.swap(nxt);
-        }
-        const i64 ns = (i64)a_blk.size();
-        S.n_steps_r = (size_t)ns;
-        if (ns) {
-            auto operand = [&](i64 blk, unsigned j) -> i64 { return blk < 0 ? powers[(size_t)(-blk - 1)][j] : r_of(off, tm, blk, j); };
-            std::vector<i64> a((size_t)ns * L), b((size_t)ns * L);
-            for (i64 q = 0; q < ns; ++q)
-                for (unsigned j = 0; j < L; ++j) {
-                    a[(size_t)q * L + j] = operand(a_blk[(size_t)q], j);
-                    b[(size_t)q * L + j] = operand(b_blk[(size_t)q], j);
-                }
-            const i64 tree_off = off;
-            off = S.blocks(off, 0, std::move(a), std::move(b), {}, ns);
-            root_c = block_r(tree_off + (ns - 1) * (i64)tm.cells);
-        } else root_c = powers[0];   // one ciphertext: no tree, the root is the power
-    } else {
-        gm = ext_l(x_c);
-        rn = ext_l(y_c);
-    }
+    // ---- the kind's own blocks -> the cells holding its result(s)
+    std::vector<Cells> roots;
+    auto hs_chain = [&](size_t i) { return S.limb_chain(x_c, rs_c[i], s_limbs); };   // pow_mod(hs, s_i): every chain from the SAME hs cells
     if (kind < 3) {
-        root_c = block_r(off);
-        off = S.blocks(off, 0, std::vector<i64>(gm), std::vector<i64>(rn), {}, 1);
+        Cells gm = ext_l(x_c), rn = ext_l(y_c);   // (kind 1: the two ciphertexts)
+        if (kind == 2) {   // g^m over ALL Ln * W bits of m IN the circuit: the same shape for every message
+            gm = S.limb_chain(ext_l(g_c), x_c, Ln);
+            S.n_steps_g = 2 * (size_t)Ln * W;
+        } else if (kind == 0) {
+            S.n_steps_g = (size_t)S.fixed_chain(ext_l(g_c), exp_g, gm);
+        }
+        if (kind != 1) S.n_steps_r = (size_t)S.fixed_chain(ext_l(y_c), exp_r, rn);
+        roots.push_back(S.mul_block(gm, rn));
+    } else if (kind == 3) {
+        roots.push_back(S.product_tree(ct_c, S.n_steps_g));
+    } else if (kind == 4) {
+        std::vector<Cells> powers;
+        for (size_t i = 0; i < count; ++i) powers.push_back(S.word_chain(wt_c[i], w_bits, ct_c[i]));
+        S.n_steps_g = 2 * count * w_bits;
+        roots.push_back(S.product_tree(powers, S.n_steps_r));
+    } else if (kind == 6) {
+        for (size_t i = 0; i < count; ++i) {
+            const Cells gm = S.word_chain(wt_c[i], w_bits, ext_l(g_c));
+            Cells rn;
+            S.n_steps_r = (size_t)S.fixed_chain(ext_l(rs_c[i]), exp_r, rn);
+            roots.push_back(S.mul_block(gm, rn));
+        }
+        S.n_steps_g = 2 * (size_t)w_bits;
+    } else if (kind == 7) {
+        roots.push_back(S.limb_chain(g_c, x_c, L));   // h = v^theta: every chain decomposes the SAME limb cells of theta
+        for (size_t i = 0; i < count; ++i) roots.push_back(S.limb_chain(S.mul_block(ct_c[i], ct_c[i]), x_c, L));   // from s_j = c_j^2
+        S.n_steps_g = 2 * (size_t)L * W;
+    } else if (kind == 8 || kind == 10) {
+        const std::vector<Cells> d_c = S.network(ct_c);
+        for (size_t i = 0; i < count; ++i) {
+            Cells rn;
+            if (kind == 8) S.n_steps_r = (size_t)S.fixed_chain(ext_l(rs_c[i]), exp_r, rn);
+            else rn = hs_chain(i);
+            roots.push_back(S.mul_block(d_c[i], rn));
+        }
+        if (kind == 10) S.n_steps_r = 2 * (size_t)s_limbs * W;
+    } else if (kind == 9) {
+        for (size_t i = 0; i < count; ++i) {
+            const Cells gm = S.word_chain(wt_c[i], w_bits, ext_l(g_c));
+            roots.push_back(S.mul_block(gm, hs_chain(i)));
+        }
+        S.n_steps_g = 2 * (size_t)w_bits;
+        S.n_steps_r = 2 * (size_t)s_limbs * W;
+    } else {   // kind 11
+        for (size_t i = 0; i < count; ++i) {
+            std::vector<Cells> powers;   // P_0 .. P_{K-1}, then hs^s_i
+            for (unsigned j = 0; j < slots; ++j) powers.push_back(S.word_chain(wt_c[i * slots + j], w_bits, ct_c[j]));
+            powers.push_back(hs_chain(i));
+            // the folds: block q multiplies the running product (P_0, then block q - 1's remainder) by P_{q+1}, the last one by hss
+            Cells a_blk(slots), b_blk(slots);
+            for (unsigned q = 0; q < slots; ++q) {
+                a_blk[q] = q == 0 ? -1 : (i64)q - 1;
+                b_blk[q] = -((i64)q + 2);
+            }
+            const i64 boff = S.mul_blocks(a_blk, b_blk, powers);
+            roots.push_back(S.block_r(boff, (i64)slots - 1));
+        }
+        S.n_steps_g = 2 * (size_t)w_bits;
+        S.n_steps_r = 2 * (size_t)s_limbs * W;
     }
-    // ---- suffix: assign_integer(res), assert_equal_fresh (the ballot: once per entry)
-    if (kind < 6) roots.push_back(root_c);
-    Walk ws(off);
-    std::vector<i64> eq_cells;
-    for (const std::vector<i64>& root : roots) {
-        const std::vector<i64> res_c = assign(ws, L, W, lb);
+    // ---- suffix: assign_integer(res), assert_equal_fresh (once per result)
+    Walk ws = S.open();
+    Cells eq_cells;
+    for (const Cells& root : roots) {
+        const Cells res_c = assign(ws, L, W, lb);
         ws.putc(c_small(0));
         i64 eq_cell = ws.putc(c_small(1));
         for (unsigned j = 0; j < L; ++j) {
@@ -901,7 +792,7 @@ int build_stream(int kind, unsigned Ln, unsigned W, unsigned lb, const u64* exp_
         }
         eq_cells.push_back(eq_cell);
     }
-    off = S.flush(ws);
+    S.flush(ws);
     // assert_equal_fresh's result is constrained to the constant 1 (bench.rs:74)
     Part& last = S.parts.back();
     for (i64 eq_cell : eq_cells) last.src[(size_t)(eq_cell - last.cell_off)] = -(1 + (i64)S.cid(c_small(1)));
@@ -1187,17 +1078,14 @@ static int structure_impl(pz_ctx* ctx, int kind, uint32_t limbs_n, uint32_t limb
     if (!ctx || !out || kind < 0 || kind > 11 || limbs_n == 0 || limbs_n > 64) return PZ_ERR_INVALID;
     const int handle_kind = kind;   // kind 5 ("decrypt") is kind 2's circuit under another statement: pz_structure_expose alone tells them apart
     if (kind == 5) kind = 2;
-    if (kind == 3 && (count < 2 || count > 65536)) return PZ_ERR_INVALID;
-    if (kind == 4 && (count < 1 || count > 65536 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
     if (limb_bits < 16 || limb_bits > 90 || lookup_bits == 0 || lookup_bits >= k || k < 4 || k > 24 || lookup_bits >= limb_bits) return PZ_ERR_INVALID;
-    if (kind == 6 && (count < 1 || count > 1024 || w_bits < 1 || w_bits > 64)) return PZ_ERR_INVALID;
-    if (kind == 7 && (count < 1 || count > 1024)) return PZ_ERR_INVALID;
-    if (kind == 8 && (count < 1 || count > 1024 || (count & (count - 1)) != 0)) return PZ_ERR_INVALID;
-    if (kind == 9 && (count < 1 || count > 1024 || w_bits < 1 || w_bits > 64 || s_limbs < 1 || s_limbs > 2 * limbs_n)) return PZ_ERR_INVALID;
-    if (kind == 10 && (count < 1 || count > 1024 || (count & (count - 1)) != 0 || s_limbs < 1 || s_limbs > 2 * limbs_n)) return PZ_ERR_INVALID;
-    if (kind == 11 && (count < 1 || count > 1024 || slots < 1 || slots > 64 || count * slots > 1024 || w_bits < 1 || w_bits > 64 ||
-                       s_limbs < 1 || s_limbs > 2 * limbs_n))
-        return PZ_ERR_INVALID;
+    // the kind's own shape (pz_internal.h names the limits): the tallies' count, the entries of kinds 6 .. 11, then what a kind adds
+    if ((kind == 3 || kind == 4) && !pz_count_ok(count, kind == 3 ? 2 : 1, PZ_TALLY_MAX)) return PZ_ERR_INVALID;
+    if (kind >= 6 && !pz_count_ok(count, 1, PZ_ENTRIES_MAX)) return PZ_ERR_INVALID;
+    if ((kind == 4 || kind == 6 || kind == 9 || kind == 11) && !pz_word_bits_ok(w_bits)) return PZ_ERR_INVALID;
+    if ((kind == 8 || kind == 10) && (count & (count - 1)) != 0) return PZ_ERR_INVALID;
+    if (kind >= 9 && !pz_short_exp_ok(s_limbs, limbs_n)) return PZ_ERR_INVALID;
+    if (kind == 11 && !pz_slots_ok(count, slots)) return PZ_ERR_INVALID;
     if (((kind == 0 || kind == 2 || kind == 6 || kind == 8) && !exp_r) || (kind == 0 && !exp_g)) return PZ_ERR_INVALID;
     const i64 n = (i64)1 << k;
     const i64 unusable = (i64)blinding_factors + 3;

@@ -1156,9 +1156,9 @@ static int make_circuit_params(int kind, uint32_t limbs_n, uint32_t limb_bits, u
                                size_t* adv_total, size_t* lk_total, size_t step_off[3]) {
     if (kind < 0 || kind > 5) return PZ_ERR_INVALID;
     if (kind == 5) kind = 2;   // "decrypt": kind 2's cells exactly (its statement alone differs: pz_circuit_public_cells)
-    if (kind == 3 && (ng < 1 || ng > 65535 || nr)) return PZ_ERR_INVALID;   // the tally of ng + 1 ciphertexts: ng mul_mod blocks
+    if (kind == 3 && (ng < 1 || ng > PZ_TALLY_MAX - 1 || nr)) return PZ_ERR_INVALID;   // the tally of ng + 1 ciphertexts: ng mul_mod blocks
     // the weighted tally of B = nr + 1 ciphertexts: nr tree blocks, ng = 2 B W chain records
-    if (kind == 4 && (nr > 65535 || ng == 0 || ng % (2 * (nr + 1)) || ng / (2 * (nr + 1)) > 64)) return PZ_ERR_INVALID;
+    if (kind == 4 && (nr > PZ_TALLY_MAX - 1 || ng == 0 || ng % (2 * (nr + 1)) || ng / (2 * (nr + 1)) > PZ_WORD_BITS_MAX)) return PZ_ERR_INVALID;
     PZCHK(circ_base(limbs_n, limb_bits, lb, (unsigned)kind, C));
     size_t a = 0, l = 0;
     const size_t asg_a = asg_adv(C), asg_l = asg_lk(C);
@@ -1368,6 +1368,32 @@ static void launch_chains(const ExpandArgs& A, const CircP& C, size_t a_bits, si
     hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)(chains * 2 * nbits)), dim3(EXP_THREADS), 0, A.ctx->stream, Q, recs,
                        (const u64*)A.d_modulus, (Fr*)A.d_advice, (Fr*)A.d_lookup);
 }
+// the hs-chains of `count` entries (pow_mod(hs, s_i) limb by limb of s_i: kinds 9, 10 and 11): per entry s_i's num_to_bits and the
+// selects; then limb by limb the record pairs of ALL entries in one launch.  s_i: s_words words from word in_ss + i s_words of the staged
+// inputs; entry i's first num_to_bits block stands at advice cell bits0 + i cell_stride, its chain's records run from record
+// rec0 + i rec_stride -- limb li's start 2 li W further, and so do their lookups behind lk0
+static void launch_hs_chains(const ExpandArgs& A, const CircP& C, const u64* in, size_t in_ss, size_t s_limbs, size_t s_words, size_t count,
+                             size_t bits0, size_t cell_stride, size_t lk0, const u64* recs, size_t rec0, size_t rec_stride) {
+    const size_t W = C.e.W, rec = 4 * (size_t)C.e.L64, limb_stride = nbits_cells(W) + W * bit_stride(C);
+    for (size_t i = 0; i < count; ++i) {
+        const u64 *d_s = in + in_ss + i * s_words, *d_chain = recs + (i * rec_stride + rec0) * rec;
+        hipLaunchKernelGGL(k_circuit_bits, dim3((unsigned)s_limbs), dim3(256), 0, A.ctx->stream, C.e, (unsigned)s_limbs, (unsigned)s_words, d_s,
+                           bits0 + i * cell_stride, limb_stride, (Fr*)A.d_advice);
+        hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)(s_limbs * W)), dim3(256), 0, A.ctx->stream, C.e, (unsigned)s_limbs, (unsigned)s_words,
+                           d_s, d_chain, bits0 + i * cell_stride, limb_stride, bit_stride(C), nbits_cells(W), (Fr*)A.d_advice);
+    }
+    for (size_t li = 0; li < s_limbs; ++li) {
+        const size_t r0 = rec0 + li * 2 * W;
+        launch_chains(A, C, bits0 + li * limb_stride, lk0 + r0 * C.e.lookups, recs + r0 * rec, W, count, cell_stride, rec_stride);
+    }
+}
+// num_to_bits of a short exponent's top limb cannot hold a bit at or above s_bits: s_i is the s_words words from word in_ss + i s_words
+static int short_exp_check(const uint64_t* inputs, size_t in_ss, size_t s_words, size_t s_bits, size_t count) {
+    if (s_bits & 63)
+        for (size_t i = 0; i < count; ++i)
+            if (inputs[in_ss + (i + 1) * s_words - 1] >> (s_bits & 63)) return PZ_ERR_MESSAGE_RANGE;
+    return PZ_OK;
+}
 // a run of `count` assign_integer blocks of nl limbs each, the integers `words` words apart from word in_off of the staged inputs
 static void launch_assign(const ExpandArgs& A, const CircP& C, const u64* in, size_t in_off, unsigned nl, unsigned words, size_t count, size_t a0,
                           size_t l0) {
@@ -1462,7 +1488,6 @@ extern "C" int pz_circuit_expand_cols_dev(pz_ctx* ctx, int kind, uint32_t limbs_
 // K >= 2: FlexGate::sum (1 + 3 (K - 1) cells); assign r_1 .. r_K; square + refresh, load_zero; per entry [the chain of m_i, b bits |
 // 1, 0 | nr x mul_mod | mul_mod]; per entry a result block (res_i against the remainder of the entry's last record).
 // inputs: n | g | m_1 .. m_K (one word each) | r_1 .. r_K | res_1 .. res_K.  Records: entry-major, 2 b + nr + 1 each.
-#define BALLOT_MAX 1024
 struct BallotP {
     size_t K, per, a_msgs, a_rs, l_rs, a_ent, l_ent, ent_stride, head;
     size_t in_ms, in_rs;   // word offsets inside `inputs`
@@ -1470,7 +1495,7 @@ struct BallotP {
 };
 static int make_ballot_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, uint32_t m_bits, size_t n_steps_r, CircP& C,
                               BallotP& B, size_t* adv_total, size_t* lk_total) {
-    if (count < 1 || count > BALLOT_MAX || m_bits < 1 || m_bits > 64 || n_steps_r < 1 || n_steps_r > 0x7fffffffu) return PZ_ERR_INVALID;
+    if (!pz_count_ok(count, 1, PZ_ENTRIES_MAX) || !pz_word_bits_ok(m_bits) || n_steps_r < 1 || n_steps_r > 0x7fffffffu) return PZ_ERR_INVALID;
     PZCHK(circ_base(limbs_n, limb_bits, lb, 6, C));
     memset(&B, 0, sizeof B);
     B.K = count;
@@ -1561,7 +1586,6 @@ extern "C" int pz_ballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t
 // (acc, sq) record -- the product where theta's top bit is set, the accumulator otherwise.
 // inputs: n | v | theta | c_1 .. c_K | h | u_1 .. u_K.  Records (pz_paillier_partial_dev): the K squarings, then chain i at K + i 2 E,
 // E = 2 Ln W bits.  Lookups follow the STREAM: chain 0's, then per ciphertext its squaring's and its chain's.
-#define PARTIAL_MAX 1024
 struct PartialP {
     size_t K, E, a_wide, l_wide, a_ch, l_ch, limb_stride, chain_cells;
     size_t in_v, in_theta;   // word offsets inside `inputs`
@@ -1569,7 +1593,7 @@ struct PartialP {
 };
 static int make_partial_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, CircP& C, PartialP& B, size_t* adv_total,
                                size_t* lk_total) {
-    if (count < 1 || count > PARTIAL_MAX) return PZ_ERR_INVALID;
+    if (!pz_count_ok(count, 1, PZ_ENTRIES_MAX)) return PZ_ERR_INVALID;
     PZCHK(circ_base(limbs_n, limb_bits, lb, 7, C));
     memset(&B, 0, sizeof B);
     const size_t W = limb_bits, L = C.e.L;
@@ -1665,7 +1689,6 @@ extern "C" int pz_partial_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_
 // and per limb select(in[j'], in[j], b), select(in[j], in[j'], b); per output [1, 0 | nr x mul_mod | mul_mod]; per output a result
 // block (res_i against the remainder of the output's last record).  inputs: n | c_1 .. c_K | r_1 .. r_K | res_1 .. res_K.  Routes,
 // bits and records are pz_paillier_mix_dev's, as it leaves them: fields of 2 ceil(Ln W / 64) words.
-#define MIX_MAX 1024
 struct MixP {
     size_t K, half, layers, per, a_cts, l_cts, a_rs, l_rs, a_net, sw_cells, a_out, l_out, out_stride;
     size_t in_cts, in_rs;           // word offsets inside `inputs`
@@ -1674,7 +1697,7 @@ struct MixP {
 };
 static int make_mix_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, size_t n_steps_r, CircP& C, MixP& B,
                            size_t* adv_total, size_t* lk_total) {
-    if (count < 1 || count > MIX_MAX || (count & (count - 1)) != 0 || n_steps_r < 1 || n_steps_r > 0x7fffffffu) return PZ_ERR_INVALID;
+    if (!pz_count_ok(count, 1, PZ_ENTRIES_MAX) || (count & (count - 1)) != 0 || n_steps_r < 1 || n_steps_r > 0x7fffffffu) return PZ_ERR_INVALID;
     PZCHK(circ_base(limbs_n, limb_bits, lb, 8, C));
     memset(&B, 0, sizeof B);
     B.K = count; B.half = count / 2; B.per = n_steps_r + 1; B.rw = 2 * C.words_n;
@@ -1828,7 +1851,6 @@ extern "C" int pz_mix_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_t li
 // the entry's last record).  inputs: n | g | hs (L64 words) | m_1 .. m_K (one word each) | s_1 .. s_K (ceil(s_limbs W / 64) words
 // each) | res_1 .. res_K.  Records are pz_paillier_sballot_dev's, as it leaves them: entry-major, 2 b + 2 s_limbs W + 1 each, fields
 // of 2 ceil(Ln W / 64) words.  No arithmetic of its own: the bits, select, expand, assign and result kernels above.
-#define SBALLOT_MAX 1024
 struct SballotP {
     size_t K, per, s_limbs, s_words, a_hs, l_hs, a_msgs, a_ss, l_ss, a_ent, l_ent, ent_stride, head, g_cells, limb_stride;
     size_t in_hs, in_ms, in_ss;   // word offsets inside `inputs`
@@ -1837,7 +1859,7 @@ struct SballotP {
 };
 static int make_sballot_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, uint32_t m_bits, uint32_t s_limbs, CircP& C,
                                SballotP& B, size_t* adv_total, size_t* lk_total) {
-    if (count < 1 || count > SBALLOT_MAX || m_bits < 1 || m_bits > 64 || s_limbs < 1 || s_limbs > 2 * (uint64_t)limbs_n) return PZ_ERR_INVALID;
+    if (!pz_count_ok(count, 1, PZ_ENTRIES_MAX) || !pz_word_bits_ok(m_bits) || !pz_short_exp_ok(s_limbs, limbs_n)) return PZ_ERR_INVALID;
     PZCHK(circ_base(limbs_n, limb_bits, lb, 9, C));
     memset(&B, 0, sizeof B);
     const size_t W = limb_bits, s_bits = (size_t)s_limbs * W;
@@ -1891,11 +1913,9 @@ static int sballot_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t l
     size_t a, l;
     PZCHK(make_sballot_params(limbs_n, limb_bits, lookup_bits, count, m_bits, s_limbs, C, B, &a, &l));
     PZCHK(expand_layout(A, C));
-    const size_t W = limb_bits, s_bits = s_limbs * W;
-    for (size_t i = 0; i < count; ++i) {   // num_to_bits of such a message or of such an exponent's top limb cannot hold
+    for (size_t i = 0; i < count; ++i)   // num_to_bits of such a message cannot hold
         if (m_bits < 64 && A.inputs[B.in_ms + i] >> m_bits) return PZ_ERR_MESSAGE_RANGE;
-        if ((s_bits & 63) && A.inputs[B.in_ss + (i + 1) * B.s_words - 1] >> (s_bits & 63)) return PZ_ERR_MESSAGE_RANGE;
-    }
+    PZCHK(short_exp_check(A.inputs, B.in_ss, B.s_words, (size_t)s_limbs * limb_bits, count));
     pz_ctx* ctx = A.ctx;
     PZ_ENTER(ctx);
     const u64* in;
@@ -1904,7 +1924,6 @@ static int sballot_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t l
     PZCHK(repack_records(ctx, C, B.rw, count * B.per * 4, &recs));
     pz_timer tm(ctx, PZ_T_EXPAND);
     Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
-    const size_t rec = 4 * (size_t)C.e.L64;   // words per step record
     // n, g, square, refresh, load_zero
     hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, (const u64*)nullptr, adv, lk);
     // assign_integer(hs): 2 Ln limbs from L64 words; assign_integer(s_i): s_limbs limbs from s_words words each
@@ -1916,21 +1935,8 @@ static int sballot_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t l
     hipLaunchKernelGGL(k_circuit_select_many, dim3((unsigned)(count * m_bits)), dim3(256), 0, ctx->stream, C.e, m_bits, in + B.in_ms, recs, B.per,
                        B.a_ent, B.ent_stride, bit_stride(C), B.head, adv);
     launch_chains(A, C, B.a_ent + 2, B.l_ent, recs, m_bits, count, B.ent_stride, B.per);
-    // the hs-chains (kind 7's walk): per entry s_i's num_to_bits limb by limb and the selects; then limb by limb the record pairs of ALL
-    // entries in one launch -- limb li's records start 2 b + 2 li W into an entry's, and so do their lookups
-    for (size_t i = 0; i < count; ++i) {
-        const size_t bits0 = B.a_ent + i * B.ent_stride + B.g_cells + 2;
-        const u64 *d_s = in + B.in_ss + i * B.s_words, *d_chain = recs + (i * B.per + 2 * (size_t)m_bits) * rec;
-        hipLaunchKernelGGL(k_circuit_bits, dim3((unsigned)s_limbs), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s, bits0,
-                           B.limb_stride, adv);
-        hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)s_bits), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s,
-                           d_chain, bits0, B.limb_stride, bit_stride(C), nbits_cells(W), adv);
-    }
-    for (size_t li = 0; li < s_limbs; ++li) {
-        const size_t r0 = 2 * (size_t)m_bits + li * 2 * W;
-        launch_chains(A, C, B.a_ent + B.g_cells + 2 + li * B.limb_stride, B.l_ent + r0 * C.e.lookups, recs + r0 * rec, W, count, B.ent_stride,
-                      B.per);
-    }
+    // the hs-chains behind the g-chains: their records start 2 b into an entry's
+    launch_hs_chains(A, C, in, B.in_ss, s_limbs, B.s_words, count, B.a_ent + B.g_cells + 2, B.ent_stride, B.l_ent, recs, 2 * (size_t)m_bits, B.per);
     // the final block of every entry, and the result blocks with the [1, 0] of the hs-chains
     launch_runs(A, C, B.a_ent + B.ent_stride - C.e.cells, B.l_ent, recs, 1, count, B.ent_stride, B.per, B.per - 1);
     launch_results(A, C, B.res, count, in, recs);
@@ -1959,8 +1965,6 @@ extern "C" int pz_sballot_expand_cols_dev(pz_ctx* ctx, uint32_t limbs_n, uint32_
 // G_{K-1} (L64 words each) | v_11 .. v_RK (one word each) | s_1 .. s_R (ceil(s_limbs W / 64) words each) | res_1 .. res_R.  Records are
 // pz_paillier_pballot_dev's, as it leaves them: entry-major, 2 b K + 2 s_limbs W + K each.  One kernel of its own, the R sums; the
 // rest are the bits, select, expand, assign and result kernels above.
-#define PBALLOT_MAX 1024
-#define PBALLOT_SLOTS_MAX 64
 struct PballotP {
     size_t R, K, per, s_limbs, s_words, a_hs, l_hs, a_vals, a_sum, sum_cells, a_ss, l_ss, a_ent, l_ent, ent_stride, head, g_cells, limb_stride;
     size_t in_hs, in_vs, in_ss;   // word offsets inside `inputs`
@@ -1976,8 +1980,8 @@ __global__ __launch_bounds__(256) void k_pballot_sums(ExpP P, const u64* __restr
 }
 static int make_pballot_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, uint32_t slots, uint32_t m_bits,
                                uint32_t s_limbs, CircP& C, PballotP& B, size_t* adv_total, size_t* lk_total) {
-    if (count < 1 || count > PBALLOT_MAX || slots < 1 || slots > PBALLOT_SLOTS_MAX || count * slots > PBALLOT_MAX) return PZ_ERR_INVALID;
-    if (m_bits < 1 || m_bits > 64 || s_limbs < 1 || s_limbs > 2 * (uint64_t)limbs_n) return PZ_ERR_INVALID;
+    if (!pz_count_ok(count, 1, PZ_ENTRIES_MAX) || !pz_slots_ok(count, slots)) return PZ_ERR_INVALID;
+    if (!pz_word_bits_ok(m_bits) || !pz_short_exp_ok(s_limbs, limbs_n)) return PZ_ERR_INVALID;
     PZCHK(circ_base(limbs_n, limb_bits, lb, 11, C));
     memset(&B, 0, sizeof B);
     const size_t W = limb_bits, s_bits = (size_t)s_limbs * W, K = slots;
@@ -2032,12 +2036,10 @@ static int pballot_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t l
     size_t a, l;
     PZCHK(make_pballot_params(limbs_n, limb_bits, lookup_bits, count, slots, m_bits, s_limbs, C, B, &a, &l));
     PZCHK(expand_layout(A, C));
-    const size_t W = limb_bits, s_bits = s_limbs * W, K = slots;
-    for (size_t i = 0; i < count; ++i) {   // num_to_bits of such a value or of such an exponent's top limb cannot hold
-        for (size_t j = 0; j < K; ++j)
-            if (m_bits < 64 && A.inputs[B.in_vs + i * K + j] >> m_bits) return PZ_ERR_MESSAGE_RANGE;
-        if ((s_bits & 63) && A.inputs[B.in_ss + (i + 1) * B.s_words - 1] >> (s_bits & 63)) return PZ_ERR_MESSAGE_RANGE;
-    }
+    const size_t K = slots;
+    for (size_t i = 0; i < count * K; ++i)   // num_to_bits of such a value cannot hold
+        if (m_bits < 64 && A.inputs[B.in_vs + i] >> m_bits) return PZ_ERR_MESSAGE_RANGE;
+    PZCHK(short_exp_check(A.inputs, B.in_ss, B.s_words, (size_t)s_limbs * limb_bits, count));
     pz_ctx* ctx = A.ctx;
     PZ_ENTER(ctx);
     const u64* in;
@@ -2067,20 +2069,9 @@ static int pballot_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t l
         const size_t r0 = 2 * (size_t)m_bits * j;
         launch_chains(A, C, B.a_ent + j * B.g_cells + 2, B.l_ent + r0 * C.e.lookups, recs + r0 * rec, m_bits, count, B.ent_stride, B.per);
     }
-    // the hs-chains as kind 9's, behind the slot chains
-    const size_t hs_cells = B.a_ent + K * B.g_cells + 2, hs_rec = 2 * (size_t)m_bits * K;
-    for (size_t i = 0; i < count; ++i) {
-        const size_t bits0 = hs_cells + i * B.ent_stride;
-        const u64 *d_s = in + B.in_ss + i * B.s_words, *d_chain = recs + (i * B.per + hs_rec) * rec;
-        hipLaunchKernelGGL(k_circuit_bits, dim3((unsigned)s_limbs), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s, bits0,
-                           B.limb_stride, adv);
-        hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)s_bits), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s,
-                           d_chain, bits0, B.limb_stride, bit_stride(C), nbits_cells(W), adv);
-    }
-    for (size_t li = 0; li < s_limbs; ++li) {
-        const size_t r0 = hs_rec + li * 2 * W;
-        launch_chains(A, C, hs_cells + li * B.limb_stride, B.l_ent + r0 * C.e.lookups, recs + r0 * rec, W, count, B.ent_stride, B.per);
-    }
+    // the hs-chains as kind 9's, behind the slot chains: their records start 2 b K into a ciphertext's
+    launch_hs_chains(A, C, in, B.in_ss, s_limbs, B.s_words, count, B.a_ent + K * B.g_cells + 2, B.ent_stride, B.l_ent, recs,
+                     2 * (size_t)m_bits * K, B.per);
     // the K fold blocks of every ciphertext, and the result blocks with the [1, 0] of the hs-chains
     launch_runs(A, C, B.a_ent + B.ent_stride - K * C.e.cells, B.l_ent, recs, K, count, B.ent_stride, B.per, B.per - K);
     launch_results(A, C, B.res, count, in, recs);
@@ -2116,7 +2107,7 @@ struct SmixP {
 };
 static int make_smix_params(uint32_t limbs_n, uint32_t limb_bits, uint32_t lb, size_t count, uint32_t s_limbs, CircP& C, SmixP& B,
                             size_t* adv_total, size_t* lk_total) {
-    if (count < 1 || count > MIX_MAX || (count & (count - 1)) != 0 || s_limbs < 1 || s_limbs > 2 * (uint64_t)limbs_n) return PZ_ERR_INVALID;
+    if (!pz_count_ok(count, 1, PZ_ENTRIES_MAX) || (count & (count - 1)) != 0 || !pz_short_exp_ok(s_limbs, limbs_n)) return PZ_ERR_INVALID;
     PZCHK(circ_base(limbs_n, limb_bits, lb, 10, C));
     memset(&B, 0, sizeof B);
     const size_t W = limb_bits, s_bits = (size_t)s_limbs * W;
@@ -2167,12 +2158,10 @@ static int smix_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb
     PZCHK(make_smix_params(limbs_n, limb_bits, lookup_bits, count, s_limbs, C, B, &a, &l));
     if (B.layers && (!bits || !d_routes)) return PZ_ERR_INVALID;
     PZCHK(expand_layout(A, C));
-    const size_t n_switch = B.layers * B.half, W = limb_bits, s_bits = s_limbs * W;
+    const size_t n_switch = B.layers * B.half;
     for (size_t i = 0; i < n_switch; ++i)
         if (bits[i] > 1) return PZ_ERR_MESSAGE_RANGE;   // assert_bit of such a byte cannot hold
-    if (s_bits & 63)
-        for (size_t i = 0; i < count; ++i)   // num_to_bits of such an exponent's top limb cannot hold
-            if (A.inputs[B.in_ss + (i + 1) * B.s_words - 1] >> (s_bits & 63)) return PZ_ERR_MESSAGE_RANGE;
+    PZCHK(short_exp_check(A.inputs, B.in_ss, B.s_words, (size_t)s_limbs * limb_bits, count));
     pz_ctx* ctx = A.ctx;
     PZ_ENTER(ctx);
     const size_t in_words = B.res.in_res + count * C.e.L64;
@@ -2183,27 +2172,14 @@ static int smix_expand_impl(const ExpandArgs& A, uint32_t limbs_n, uint32_t limb
     PZCHK(repack_records(ctx, C, B.rw, count * B.per * 4, &recs));
     pz_timer tm(ctx, PZ_T_EXPAND);
     Fr *adv = (Fr*)A.d_advice, *lk = (Fr*)A.d_lookup;
-    const size_t rec = 4 * (size_t)C.e.L64;   // words per step record
     // n, square, refresh, load_zero
     hipLaunchKernelGGL(k_circuit_misc, dim3(1), dim3(256), 0, ctx->stream, C, in, (const u64*)nullptr, adv, lk);
     // assign_integer(hs), assign_integer(c_j): 2 Ln limbs from L64 words each; assign_integer(s_i): s_limbs limbs from s_words words each
     launch_assign(A, C, in, B.in_hs, C.nf, C.e.L64, 1 + count, B.a_hs, B.l_hs);
     launch_assign(A, C, in, B.in_ss, (unsigned)s_limbs, (unsigned)B.s_words, count, B.a_ss, B.l_ss);
     launch_network(A, C, in + B.in_cts, d_routes, d_bits, count, B.d, B.layers, B.rw, B.a_net, B.sw_cells);
-    // the hs-chains (kind 9's walk): per output s_i's num_to_bits limb by limb and the selects; then limb by limb the record pairs of ALL
-    // outputs in one launch -- limb li's records start 2 li W into an output's, and so do their lookups
-    for (size_t i = 0; i < count; ++i) {
-        const size_t bits0 = B.a_out + i * B.out_stride + 2;
-        const u64 *d_s = in + B.in_ss + i * B.s_words, *d_chain = recs + i * B.per * rec;
-        hipLaunchKernelGGL(k_circuit_bits, dim3((unsigned)s_limbs), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s, bits0,
-                           B.limb_stride, adv);
-        hipLaunchKernelGGL(k_circuit_select, dim3((unsigned)s_bits), dim3(256), 0, ctx->stream, C.e, (unsigned)s_limbs, (unsigned)B.s_words, d_s,
-                           d_chain, bits0, B.limb_stride, bit_stride(C), nbits_cells(W), adv);
-    }
-    for (size_t li = 0; li < s_limbs; ++li) {
-        const size_t r0 = li * 2 * W;
-        launch_chains(A, C, B.a_out + 2 + li * B.limb_stride, B.l_out + r0 * C.e.lookups, recs + r0 * rec, W, count, B.out_stride, B.per);
-    }
+    // the hs-chains as kind 9's: an output's records start with them
+    launch_hs_chains(A, C, in, B.in_ss, s_limbs, B.s_words, count, B.a_out + 2, B.out_stride, B.l_out, recs, 0, B.per);
     // the final block of every output, and the result blocks with the [1, 0] of the chains
     launch_runs(A, C, B.a_out + B.out_stride - C.e.cells, B.l_out, recs, 1, count, B.out_stride, B.per, B.per - 1);
     launch_results(A, C, B.res, count, in, recs);
