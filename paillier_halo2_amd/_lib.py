@@ -102,6 +102,10 @@ SIGNATURES = {
     "pz_paillier_sk_free": (C.c_int, [VP, VP]),
     "pz_paillier_decrypt": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP]),
     "pz_paillier_decrypt_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP]),
+    "pz_paillier_sk_create_crt": (C.c_int, [VP, C.c_uint32, VP, VP, VP, VP, VP, VP, C.POINTER(VP)]),
+    "pz_paillier_sk_has_crt": (C.c_int, [VP]),
+    "pz_paillier_decrypt_crt": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP]),
+    "pz_paillier_decrypt_crt_dev": (C.c_int, [VP, VP, C.c_size_t, VP, VP, VP, VP]),
     "pz_paillier_encrypt_uniform": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP]),
     "pz_paillier_encrypt_uniform_dev": (C.c_int, [VP, C.c_uint32, C.c_size_t, C.c_uint32, VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP]),
     "pz_witness_cells_per_step": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t),

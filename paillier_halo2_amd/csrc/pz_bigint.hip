@@ -3039,6 +3039,12 @@ struct pz_paillier_sk {
     u64 *d_mod2 = nullptr, *d_modn_c = nullptr, *d_modn = nullptr, *d_n = nullptr, *d_lam = nullptr, *d_d = nullptr, *d_mu = nullptr, *d_ginv = nullptr;
     std::vector<u64> h_mu, h_ginv;
     bool ginv_one = false;
+    // the CRT part (pz_paillier_sk_create_crt), behind ginv in the same block: side p | side q (crt_side_words each) |
+    // qinv | where n^2 leaves the 64-limb instantiation, the Barrett blocks of p^2 and q^2 at its capacity (k_crt_split)
+    size_t crt_words = 0;
+    bool crt = false;
+    u64 *d_side[2] = {nullptr, nullptr}, *d_qinv = nullptr, *d_p2c[2] = {nullptr, nullptr};
+    uint32_t pbits[2] = {0, 0};
 };
 static unsigned dec_window() {   // PZ_K3_DEC_WINDOW (1 .. 5) is a measurement hook, honoured only with PZ_K3_TEST_HOOKS=1 like the others
     const char* on = getenv("PZ_K3_TEST_HOOKS");
@@ -3078,7 +3084,7 @@ static int sk_create_impl(pz_ctx* ctx, pz_paillier_sk* sk, const uint64_t* n, co
     const uint32_t Ln = sk->Ln;
     const unsigned L = 2 * Ln, C = sk->C;
     const size_t nb = (size_t)Ln * 8, blk = mod_block_words(C), blk1 = mod_block_words(64);
-    sk->block_bytes = (2 * blk + blk1 + 5 * (size_t)Ln) * 8;
+    sk->block_bytes = (2 * blk + blk1 + 5 * (size_t)Ln + sk->crt_words) * 8;   // (crt_words: 0 unless pz_paillier_sk_create_crt made the handle)
     void* dv;
     PZCHK(pz_dev_alloc(ctx, sk->block_bytes, &dv));
     sk->d_block = (u64*)dv;
@@ -3162,26 +3168,37 @@ static int sk_create_impl(pz_ctx* ctx, pz_paillier_sk* sk, const uint64_t* n, co
     sk->ginv_one = is_small(sk->h_ginv.data(), Ln, 1);
     return PZ_OK;
 }
-extern "C" int pz_paillier_sk_create(pz_ctx* ctx, uint32_t limbs_n, const uint64_t* n, const uint64_t* g, const uint64_t* lambda,
-                                     const uint64_t* d, pz_paillier_sk** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !n || !g || !lambda || !d || !out || limbs_n == 0) return PZ_ERR_INVALID;
+static size_t sk_crt_words(uint32_t Ln, unsigned C);
+static int sk_crt_precheck(uint32_t Ln, const uint64_t* p, const uint64_t* q);
+static int sk_create_crt_impl(pz_ctx* ctx, pz_paillier_sk* sk, const uint64_t* g, const uint64_t* p, const uint64_t* q);
+// both creators: p and q null is pz_paillier_sk_create; else the CRT part follows the lambda path's handle, which is made by the same code
+static int sk_create_common(pz_ctx* ctx, uint32_t limbs_n, const uint64_t* n, const uint64_t* g, const uint64_t* lambda, const uint64_t* d,
+                            const uint64_t* p, const uint64_t* q, pz_paillier_sk** out) {
     if (2 * (uint64_t)limbs_n > 128) return PZ_ERR_UNSUPPORTED;
     if (is_small(n, limbs_n, 0)) return PZ_ERR_ZERO_MODULUS;
     // 0 < d < lambda < n: what fixes the powers' schedule at the bit length of n
     if (is_small(lambda, limbs_n, 0) || cmp_limbs(lambda, n, limbs_n) >= 0 || cmp_limbs(d, lambda, limbs_n) >= 0) return PZ_ERR_INVALID;
+    if (p) PZCHK(sk_crt_precheck(limbs_n, p, q));
     PZ_ENTER(ctx);
     pz_paillier_sk* sk = new pz_paillier_sk;
     sk->Ln = limbs_n;
     sk->C = capacity(2 * limbs_n);
     sk->nbits = bitlen_limbs(n, limbs_n);
-    const int rc = sk_create_impl(ctx, sk, n, g, lambda, d);
+    if (p) sk->crt_words = sk_crt_words(limbs_n, sk->C);
+    int rc = sk_create_impl(ctx, sk, n, g, lambda, d);
+    if (rc == PZ_OK && p) rc = sk_create_crt_impl(ctx, sk, g, p, q);
     if (rc != PZ_OK) {
         (void)sk_release(ctx, sk);
         return rc;
     }
     *out = sk;
     return PZ_OK;
+}
+extern "C" int pz_paillier_sk_create(pz_ctx* ctx, uint32_t limbs_n, const uint64_t* n, const uint64_t* g, const uint64_t* lambda,
+                                     const uint64_t* d, pz_paillier_sk** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !n || !g || !lambda || !d || !out || limbs_n == 0) return PZ_ERR_INVALID;
+    return sk_create_common(ctx, limbs_n, n, g, lambda, d, nullptr, nullptr, out);
 }
 extern "C" int pz_paillier_sk_params(const pz_paillier_sk* sk, uint64_t* mu_out, uint64_t* ginv_out) {
     if (!sk || !mu_out || !ginv_out) return PZ_ERR_INVALID;
@@ -3260,4 +3277,445 @@ extern "C" int pz_paillier_decrypt(pz_ctx* ctx, const pz_paillier_sk* sk, size_t
 extern "C" int pz_paillier_decrypt_dev(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* d_cts, uint64_t* d_m_out,
                                        uint64_t* d_r_out, uint8_t* d_flags_out) {
     return decrypt_impl(ctx, sk, count, d_cts, d_m_out, d_r_out, d_flags_out, 1);
+}
+
+// ------------------------------------------------------------------------------------------------
+// CRT decryption (pz_paillier_sk_create_crt, pz_paillier_sk_has_crt, pz_paillier_decrypt_crt[_dev])
+// ------------------------------------------------------------------------------------------------
+// The same plaintext and randomness from the two primes: per side P in {p, q} the half-length power u_P = (c mod P^2)^(P-1) mod P^2,
+// m_P = ((u_P - 1) / P) h_P mod P, then Garner; for r the powers (ginv mod P)^(m mod (P-1)) and the d mod (P-1)-th one, mod P.  Unit
+// u = 2 i + side is ciphertext i on side `side` (0: p, 1: q): the two sides of every ciphertext are teams of ONE launch and never wait
+// on each other.  p^2 and q^2 fit limbs_n words (the handle's acceptance rule), so the powers run at 64 limbs whatever the key size;
+// only the split of c (2 limbs_n words) runs at the capacity of n^2.
+// SECRET here: p, q, P - 1, h_P, qinv, d_P, the residues c mod P^2 (c - (c mod p^2) is a multiple of p^2: one of them factors n), m_P,
+// e_P, y_P, r_P.  None of them becomes a branch or an address: exponent windows are read at addresses that follow the loop counter and
+// choose their table entry under a lane mask (k_dec_pow's schedule), Garner's borrow acts through ld_select.  (What a mul_mod does with
+// its VALUES is K3's as everywhere -- the Barrett correction's trip count follows the operands, here under secret moduli too.)  The
+// bit lengths of p and q are the key's public shape, as n's is.  Side flags: k_dec_pow's bits, one byte per unit.
+// A side's part of the handle's block: Barrett blocks (64 limbs) of P^2 | P | P - 1, then P | P - 1 | h_P | d_P | ginv mod P.
+enum { CRT_V_P = 0, CRT_V_PM1 = 1, CRT_V_H = 2, CRT_V_D = 3, CRT_V_GINV = 4, CRT_V_COUNT = 5 };
+__host__ __device__ constexpr size_t crt_side_words(unsigned Ln) { return 3 * mod_block_words(64) + (size_t)CRT_V_COUNT * Ln; }
+template <class W> __host__ __device__ __forceinline__ W* crt_blk_p2(W* side) { return side; }
+template <class W> __host__ __device__ __forceinline__ W* crt_blk_p(W* side) { return side + mod_block_words(64); }
+template <class W> __host__ __device__ __forceinline__ W* crt_blk_pm1(W* side) { return side + 2 * mod_block_words(64); }
+template <class W> __host__ __device__ __forceinline__ W* crt_vec(W* side, unsigned which, unsigned Ln) {
+    return side + 3 * mod_block_words(64) + (size_t)which * Ln;
+}
+
+// c mod P^2 for unit u, at the capacity of n^2 (above 2048 bits that is the 128-limb instantiation; the powers stay at 64).  One team
+// per unit, k_tally_level's shape (the team product is inlined: no call, no stack).  c >= n^2 is public: the range flag goes to the
+// unit's own byte and the residue is zero.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_crt_split(const u64* __restrict__ mod2, const u64* __restrict__ p2_p,
+                                                                               const u64* __restrict__ p2_q, const u64* __restrict__ cts,
+                                                                               u64* __restrict__ res, uint8_t* __restrict__ sflags, unsigned Ln) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    const unsigned wave = threadIdx.x >> 6;
+    const size_t u = blockIdx.x, i = u >> 1;
+    const u64* blk = (u & 1) ? p2_q : p2_p;
+    if (*block_ok<E>(blk) == 0) return;   // (no handle reaches here with a zero modulus)
+    TeamCtx<E> T;
+    team_init(T, s_team);
+    const LD<E> c = ld_load<E>(cts + i * 2 * Ln, 2 * Ln);
+    LD<E> d;
+    if (!ld_sub(d, c, ld_load<E>(block_modulus<E>(mod2), C))) {   // the four waves hold the same values: the team leaves together
+        if (wave == 0) {
+            ld_store(res + u * Ln, ld_zero<E>(), Ln);
+            if (lane_id() == 0) sflags[u] = DEC_F_RANGE;
+        }
+        return;
+    }
+    BarrettCtx<E> B;
+    barrett_from_block(B, blk, 2 * Ln, s_scratch[wave]);
+    LD<E> q, r;
+    const unsigned st = mul_mod(B, q, r, c, ld_small<E>(1), TeamMul<E>{&T});
+    if (wave == 0) {
+        ld_store(res + u * Ln, r, Ln);
+        if (lane_id() == 0) sflags[u] = st ? DEC_F_INTERNAL : 0;
+    }
+}
+
+enum { CRT_M = 0, CRT_R = 1 };
+struct CrtPow {
+    const u64 *side0, *side1;   // the sides' parts of the handle's block
+    const u64* in;              // unit u: in + u * Ln.  CRT_M: c mod P^2; CRT_R: c mod P
+    const u64* e;               // CRT_R: e_P = m mod (P - 1) per unit; null: ginv = 1 (g is public), the first power is skipped
+    u64 *out0, *out1;           // CRT_M: m_P and c mod P; CRT_R: r_P (out1 unused)
+    uint8_t* sflags;            // one byte per unit: two teams never write one byte
+    u32 bits0, bits1;           // bit lengths of p and q
+    u32 mode, w, Ln;
+};
+// One team per unit.  CRT_M: u_P = in^(P-1) mod P^2 by k_dec_pow's fixed-window schedule (ceil(bitlen(P) / w) windows, the table in
+// LDS, every entry read and one kept under a lane mask), then lfn_tail by P's block and h_P, and c mod P.  CRT_R: two powers mod P back
+// to back, y_P = in ginvP^e_P (skipped where ginv = 1) and r_P = y_P^d_P.  The powers are ONE loop body run once or twice.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_dec_crt_pow(const CrtPow A) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    extern __shared__ u64 s_table[];   // 2^w entries of Ln limbs
+    const unsigned wave = threadIdx.x >> 6, lane = lane_id();
+    const size_t u = blockIdx.x;
+    const u64* side = (u & 1) ? A.side1 : A.side0;
+    const unsigned nbits = (u & 1) ? A.bits1 : A.bits0;
+    const unsigned Ln = A.Ln, nent = 1u << A.w;
+    if (*block_ok<E>(crt_blk_p2(side)) == 0 || *block_ok<E>(crt_blk_p(side)) == 0) return;   // (no handle reaches here with a zero modulus)
+    TeamCtx<E> T;
+    team_init(T, s_team);
+    TeamMul<E> tmul{&T};
+    const LD<E> in = ld_load<E>(A.in + u * Ln, Ln);
+    if (A.mode == CRT_M && A.sflags[u]) {   // c >= n^2 (k_crt_split: public).  The four waves read the same byte: the team leaves together
+        if (wave == 0) {
+            ld_store(A.out0 + u * Ln, ld_zero<E>(), Ln);
+            ld_store(A.out1 + u * Ln, ld_zero<E>(), Ln);
+        }
+        return;
+    }
+    unsigned st = ST_OK;
+    const LD<E> one = ld_small<E>(1);
+    BarrettCtx<E> B;
+    barrett_from_block(B, A.mode == CRT_M ? crt_blk_p2(side) : crt_blk_p(side), Ln, s_scratch[wave]);
+    LD<E> base = in, acc = in;
+    const u64* ex = crt_vec(side, A.mode == CRT_M ? CRT_V_PM1 : CRT_V_D, Ln);
+    for (unsigned ph = (A.mode == CRT_R && A.e) ? 0 : 1; ph < 2; ++ph) {
+        if (ph == 0) {   // (ginv mod P)^e_P, then times c mod P
+            base = ld_load<E>(crt_vec(side, CRT_V_GINV, Ln), Ln);
+            ex = A.e + u * Ln;
+        }
+        __syncthreads();   // (a second power: every wave is done with the first one's table)
+        {   // the table: entry k = base^k
+            LD<E> cur = one;
+            for (unsigned k = 0; k < nent; ++k) {
+                if (wave == 0) ld_store(s_table + (size_t)k * Ln, cur, Ln);
+                if (k + 1 < nent) {
+                    LD<E> q, r;
+                    st |= mul_mod(B, q, r, cur, base, tmul);
+                    cur = r;
+                }
+            }
+            __syncthreads();
+        }
+        // window at bit p (a position: public), and the entry it names, read under a mask from all of them
+        auto pick = [&](unsigned p) {
+            const unsigned wi = p >> 6, sh = p & 63;
+            const u64 lo = wi < Ln ? ex[wi] : 0, hi = wi + 1 < Ln ? ex[wi + 1] : 0;
+            u64 v = lo >> sh;
+            if (sh) v |= hi << (64 - sh);
+            u32 idx = (u32)v & (nent - 1);
+            asm volatile("" : "+v"(idx));   // a per-lane value from here on: nothing below can become a branch or an address
+            LD<E> r = ld_zero<E>();
+            for (unsigned k = 0; k < nent; ++k) {
+                const u64 keep = 0ull - (u64)(idx == k);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const unsigned t = lane * E + e;
+                    const u64 v2 = t < Ln ? s_table[(size_t)k * Ln + t] : 0;
+                    r.v[e] |= v2 & keep;
+                }
+            }
+            return r;
+        };
+        const unsigned nwin = (nbits + A.w - 1) / A.w;
+        acc = pick((nwin - 1) * A.w);
+        for (unsigned i = nwin - 1; i-- > 0;) {
+            LD<E> q, r;
+            for (unsigned s = 0; s < A.w; ++s) {
+                st |= mul_mod(B, q, r, acc, acc, tmul);
+                acc = r;
+            }
+            st |= mul_mod(B, q, r, acc, pick(i * A.w), tmul);
+            acc = r;
+        }
+        if (ph == 0) {
+            LD<E> q, r;
+            st |= mul_mod(B, q, r, acc, in, tmul);
+            ex = crt_vec(side, CRT_V_D, Ln);
+            base = acc = r;   // y_P: it lives in registers only
+        }
+    }
+    if (A.mode == CRT_R) {
+        if (wave == 0) {
+            ld_store(A.out0 + u * Ln, acc, Ln);
+            if (st && lane == 0) A.sflags[u] |= DEC_F_INTERNAL;
+        }
+        return;
+    }
+    BarrettCtx<E> N;
+    barrett_from_block(N, crt_blk_p(side), Ln, s_scratch[wave]);
+    LD<E> m, q, cP;
+    const bool bad = lfn_tail(N, T, m, acc, crt_vec(side, CRT_V_H, Ln), Ln, st);
+    st |= mul_mod(N, q, cP, in, one, tmul);
+    if (wave == 0) {
+        ld_store(A.out0 + u * Ln, m, Ln);
+        ld_store(A.out1 + u * Ln, cP, Ln);
+        if (lane == 0) A.sflags[u] = (uint8_t)((bad ? DEC_F_NOT_UNIT : 0) | (st ? DEC_F_INTERNAL : 0));
+    }
+}
+
+struct CrtGarner {
+    const u64 *side0, *side1, *qinv;
+    const u64* a;             // unit u: a + u * Ln, the side results (a_p below p, a_q below q)
+    u64* out;                 // ciphertext i: out + i * Ln = a_q + q (((a_p - a_q) mod p) qinv mod p), below n without a reduction
+    u64* e;                   // may be null; else unit u: e + u * Ln = out mod (P - 1), the first exponent of the r pass
+    const uint8_t* sflags;    // the two side bytes of ciphertext i are merged into flags[i]; a flagged entry's outputs are zero
+    uint8_t* flags;
+    u32 Ln;
+};
+// One team per ciphertext.  a_p - (a_q mod p) takes p back or 0 under ld_select's lane mask: its borrow is never a branch.
+template <int E> __global__ __launch_bounds__(64 * K3_TEAM) void k_crt_garner(const CrtGarner A) {
+    constexpr unsigned C = 64 * E;
+    __shared__ u64 s_scratch[K3_TEAM][2 * C];
+    __shared__ TeamBuf<E> s_team[2];
+    const unsigned wave = threadIdx.x >> 6, lane = lane_id();
+    const size_t i = blockIdx.x;
+    const unsigned Ln = A.Ln;
+    if (*block_ok<E>(crt_blk_p(A.side0)) == 0) return;
+    TeamCtx<E> T;
+    team_init(T, s_team);
+    TeamMul<E> tmul{&T};
+    BarrettCtx<E> B;
+    barrett_from_block(B, crt_blk_p(A.side0), Ln, s_scratch[wave]);
+    const LD<E> one = ld_small<E>(1);
+    const LD<E> ap = ld_load<E>(A.a + (2 * i) * Ln, Ln), aq = ld_load<E>(A.a + (2 * i + 1) * Ln, Ln);
+    unsigned st = ST_OK;
+    LD<E> qq, aqp, d, d2, t, lo, hi, res;
+    st |= mul_mod(B, qq, aqp, aq, one, tmul);
+    const bool borrow = ld_sub(d, ap, aqp);
+    (void)ld_add(d2, d, ld_load<E>(crt_vec(A.side0, CRT_V_P, Ln), Ln), false);   // (d wrapped: the carry-out is that 2^capacity)
+    ld_select(d, d2, (u64)borrow);
+    st |= mul_mod(B, qq, t, d, ld_load<E>(A.qinv, Ln), tmul);
+    tmul(lo, hi, ld_load<E>(crt_vec(A.side1, CRT_V_P, Ln), Ln), t);
+    (void)ld_add(res, lo, aq, false);
+    const unsigned fs = A.sflags[2 * i] | A.sflags[2 * i + 1];
+    if (fs) res = ld_zero<E>();
+    if (A.e) {
+        LD<E> ep, eq;
+        barrett_from_block(B, crt_blk_pm1(A.side0), Ln, s_scratch[wave]);
+        st |= mul_mod(B, qq, ep, res, one, tmul);
+        barrett_from_block(B, crt_blk_pm1(A.side1), Ln, s_scratch[wave]);
+        st |= mul_mod(B, qq, eq, res, one, tmul);
+        if (wave == 0) {
+            ld_store(A.e + (2 * i) * Ln, ep, Ln);
+            ld_store(A.e + (2 * i + 1) * Ln, eq, Ln);
+        }
+    }
+    if (st) res = ld_zero<E>();
+    if (wave == 0) {
+        ld_store(A.out + i * Ln, res, Ln);
+        if (lane == 0) A.flags[i] = (uint8_t)(fs | (st ? DEC_F_INTERNAL : 0));
+    }
+}
+
+static size_t sk_crt_words(uint32_t Ln, unsigned C) { return 2 * crt_side_words(Ln) + Ln + (C != 64 ? 2 * mod_block_words(C) : 0); }
+// p and q odd and at least 3 (else PZ_ERR_INVALID), p^2 and q^2 within Ln words (else PZ_ERR_UNSUPPORTED): P^2 has 2 bitlen(P) or one
+// bit fewer, and 64 Ln is even, so the rule is 2 bitlen(P) <= 64 Ln exactly.  It makes every quotient of the reductions fit and asks
+// nothing about the primes being of equal length.
+static int sk_crt_precheck(uint32_t Ln, const uint64_t* p, const uint64_t* q) {
+    for (const uint64_t* v : {p, q})
+        if (!(v[0] & 1) || is_small(v, Ln, 1)) return PZ_ERR_INVALID;
+    for (const uint64_t* v : {p, q})
+        if (2 * (uint64_t)bitlen_limbs(v, Ln) > 64 * (uint64_t)Ln) return PZ_ERR_UNSUPPORTED;
+    return PZ_OK;
+}
+static int launch_crt_pow(pz_ctx* ctx, size_t units, const CrtPow& a) {
+    hipLaunchKernelGGL(k_dec_crt_pow<1>, dim3((unsigned)units), dim3(64 * K3_TEAM), ((size_t)8 << a.w) * a.Ln, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+static int launch_crt_garner(pz_ctx* ctx, size_t count, const CrtGarner& a) {
+    hipLaunchKernelGGL(k_crt_garner<1>, dim3((unsigned)count), dim3(64 * K3_TEAM), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PZ_OK;
+}
+// on every path out: a device region that held secrets is overwritten in stream order; `drain` waits for it (host forms: the staged
+// host copies behind `h` go through pageable memory and are overwritten once the queue is empty)
+struct CrtWipe {
+    pz_ctx* c; void* p; size_t n; bool drain; std::vector<u64>* h;
+    ~CrtWipe() {
+        (void)hipMemsetAsync(p, 0, n, c->stream);
+        if (drain) (void)hipStreamSynchronize(c->stream);
+        if (h) std::fill(h->begin(), h->end(), 0);
+    }
+};
+// The CRT part of a handle whose lambda path stands (sk_create_impl): everything is derived on the device -- the Barrett blocks by
+// k_tally_setup; d_P, ginv mod P, q mod p, g mod P^2 and the check p q = n by k_mul_mod; x_P = L_P(g^(P-1) mod P^2) by k_dec_crt_pow
+// with 1 in h_P's place; h_P = x_P^(P-2) mod P and qinv = (q mod p)^(p-2) mod p by k_dec_pow (no inversion routine); and the checks
+// x_P h_P = 1 (mod P), q qinv = 1 (mod p), which a composite "prime" fails.  Primality itself is not tested (pz_bigint_is_prime).
+static int sk_create_crt_impl(pz_ctx* ctx, pz_paillier_sk* sk, const uint64_t* g, const uint64_t* p, const uint64_t* q) {
+    const uint32_t Ln = sk->Ln;
+    const unsigned C = sk->C;
+    const size_t nb = (size_t)Ln * 8;
+    u64* part = sk->d_ginv + Ln;
+    sk->d_side[0] = part;
+    sk->d_side[1] = part + crt_side_words(Ln);
+    sk->d_qinv = part + 2 * crt_side_words(Ln);
+    for (int s = 0; s < 2; ++s) sk->d_p2c[s] = C != 64 ? sk->d_qinv + Ln + s * mod_block_words(C) : crt_blk_p2(sk->d_side[s]);
+    // host staging: per side P | P - 1 | P - 2, then 1
+    std::vector<u64> hs(7 * (size_t)Ln, 0);
+    for (int s = 0; s < 2; ++s) {
+        const uint64_t* v = s ? q : p;
+        sk->pbits[s] = bitlen_limbs(v, Ln);
+        for (int k = 0; k < 3; ++k) {
+            u64* o = hs.data() + (3 * s + k) * (size_t)Ln;
+            memcpy(o, v, nb);
+            for (int j = 0; j < k; ++j)
+                for (uint32_t i = 0; i < Ln && o[i]-- == 0; ++i) {}
+        }
+    }
+    hs[6 * (size_t)Ln] = 1;
+    // device staging (shared workspace, overwritten on every path out):
+    // 1 | p - 2 | q - 2 | g | g mod P^2 (2) | x_P (2) | g mod P (2) | q mod p | checks (5) | side flags | status | descs
+    enum { S_ONE = 0, S_PM2 = 1, S_G = 3, S_GP2 = 4, S_X = 6, S_GP = 8, S_QMP = 10, S_CHK = 11, S_WORDS = 16 };
+    const size_t stage_bytes = S_WORDS * nb + 128 + 11 * sizeof(MulDesc);
+    void* ws;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, stage_bytes, &ws));
+    CrtWipe wipe{ctx, ws, stage_bytes, true, &hs};
+    u64* sw = (u64*)ws;
+    auto S = [&](int k) { return sw + (size_t)k * Ln; };
+    uint8_t* s_flag = (uint8_t*)ws + S_WORDS * nb;
+    u32* s_status = (u32*)((char*)ws + S_WORDS * nb + 64);
+    MulDesc* s_desc = (MulDesc*)((char*)ws + S_WORDS * nb + 128);
+    HIPCHK(ctx, hipMemsetAsync((char*)ws + S_WORDS * nb, 0, 128, ctx->stream));
+    const u64* h_one = hs.data() + 6 * (size_t)Ln;
+    HIPCHK(ctx, hipMemcpyAsync(S(S_ONE), h_one, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(S(S_G), g, nb, hipMemcpyHostToDevice, ctx->stream));
+    for (int s = 0; s < 2; ++s) {
+        const u64* hv = hs.data() + 3 * s * (size_t)Ln;
+        u64* side = sk->d_side[s];
+        HIPCHK(ctx, hipMemcpyAsync(crt_vec(side, CRT_V_P, Ln), hv, nb, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(crt_vec(side, CRT_V_PM1, Ln), hv + Ln, nb, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(S(S_PM2 + s), hv + 2 * (size_t)Ln, nb, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(crt_vec(side, CRT_V_H, Ln), h_one, nb, hipMemcpyHostToDevice, ctx->stream));   // (x_P is L_P under h = 1)
+        PZCHK(launch_barrett_setup(ctx, 64, crt_vec(side, CRT_V_P, Ln), Ln, 1, crt_blk_p2(side), s_status));
+        PZCHK(launch_barrett_setup(ctx, 64, crt_vec(side, CRT_V_P, Ln), Ln, 0, crt_blk_p(side), s_status));
+        PZCHK(launch_barrett_setup(ctx, 64, crt_vec(side, CRT_V_PM1, Ln), Ln, 0, crt_blk_pm1(side), s_status));
+        if (C != 64) PZCHK(launch_barrett_setup(ctx, C, crt_vec(side, CRT_V_P, Ln), Ln, 1, sk->d_p2c[s], s_status));
+    }
+    MulDesc md[11] = {};
+    for (int s = 0; s < 2; ++s) {
+        u64* side = sk->d_side[s];
+        md[s].a = sk->d_d; md[s].b = S(S_ONE); md[s].modulus = crt_vec(side, CRT_V_PM1, Ln); md[s].r = crt_vec(side, CRT_V_D, Ln);
+        md[2 + s].a = sk->d_ginv; md[2 + s].b = S(S_ONE); md[2 + s].modulus = crt_vec(side, CRT_V_P, Ln); md[2 + s].r = crt_vec(side, CRT_V_GINV, Ln);
+        md[4 + s].a = S(S_G); md[4 + s].b = S(S_ONE); md[4 + s].modulus = crt_vec(side, CRT_V_P, Ln); md[4 + s].square_modulus = 1; md[4 + s].r = S(S_GP2 + s);
+        md[8 + s].a = S(S_X + s); md[8 + s].b = crt_vec(side, CRT_V_H, Ln); md[8 + s].modulus = crt_vec(side, CRT_V_P, Ln); md[8 + s].r = S(S_CHK + 2 + s);
+    }
+    md[6].a = crt_vec(sk->d_side[1], CRT_V_P, Ln); md[6].b = S(S_ONE); md[6].modulus = crt_vec(sk->d_side[0], CRT_V_P, Ln); md[6].r = S(S_QMP);
+    md[7].a = crt_vec(sk->d_side[0], CRT_V_P, Ln); md[7].b = crt_vec(sk->d_side[1], CRT_V_P, Ln); md[7].modulus = sk->d_n;
+    md[7].q = S(S_CHK); md[7].r = S(S_CHK + 1);
+    md[10].a = S(S_QMP); md[10].b = sk->d_qinv; md[10].modulus = crt_vec(sk->d_side[0], CRT_V_P, Ln); md[10].r = S(S_CHK + 4);
+    for (auto& m : md) {
+        m.status = s_status;
+        m.limbs_a = m.limbs_b = m.limbs_mod = m.L = Ln;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(s_desc, md, sizeof md, hipMemcpyHostToDevice, ctx->stream));
+    PZCHK(launch_muls(ctx, s_desc, 8, Ln));
+    const unsigned w = dec_window();
+    CrtPow a{};
+    a.side0 = sk->d_side[0]; a.side1 = sk->d_side[1]; a.in = S(S_GP2); a.out0 = S(S_X); a.out1 = S(S_GP); a.sflags = s_flag;
+    a.bits0 = sk->pbits[0]; a.bits1 = sk->pbits[1]; a.mode = CRT_M; a.w = w; a.Ln = Ln;
+    PZCHK(launch_crt_pow(ctx, 2, a));
+    for (int k = 0; k < 3; ++k) {   // h_p, h_q, qinv
+        const int s = k == 1;
+        DecPow b{};
+        b.modP = crt_blk_p(sk->d_side[s]); b.base = k < 2 ? S(S_X + s) : S(S_QMP); b.base_limbs = Ln; b.exp = S(S_PM2 + s); b.exp_limbs = Ln;
+        b.out0 = k < 2 ? crt_vec(sk->d_side[s], CRT_V_H, Ln) : sk->d_qinv; b.nbits = sk->pbits[s]; b.w = w; b.mode = DEC_POW; b.Lp = Ln; b.Ln = Ln;
+        PZCHK(launch_dec_pow(ctx, 64, 1, b));
+    }
+    PZCHK(launch_muls(ctx, s_desc + 8, 3, Ln));
+    std::vector<u64> chk(5 * (size_t)Ln);
+    uint8_t flag[2] = {0, 0};
+    u32 st = 0;
+    HIPCHK(ctx, hipMemcpyAsync(chk.data(), S(S_CHK), 5 * nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(flag, s_flag, 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&st, s_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    auto C_ = [&](int k) { return chk.data() + (size_t)k * Ln; };
+    if (!is_small(C_(0), Ln, 1) || !is_small(C_(1), Ln, 0)) return PZ_ERR_INVALID;   // p q != n (what follows ran on a wrong modulus: its status says nothing)
+    PZCHK(status_to_rc(ctx, st));
+    if ((flag[0] | flag[1]) & DEC_F_INTERNAL) {
+        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: internal consistency check failed (CRT key derivation)");
+        return PZ_ERR_HIP;
+    }
+    if (flag[0] || flag[1] || !is_small(C_(2), Ln, 1) || !is_small(C_(3), Ln, 1) || !is_small(C_(4), Ln, 1)) return PZ_ERR_INVALID;
+    sk->crt = true;
+    return PZ_OK;
+}
+extern "C" int pz_paillier_sk_create_crt(pz_ctx* ctx, uint32_t limbs_n, const uint64_t* n, const uint64_t* g, const uint64_t* lambda,
+                                         const uint64_t* d, const uint64_t* p, const uint64_t* q, pz_paillier_sk** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !n || !g || !lambda || !d || !p || !q || !out || limbs_n == 0) return PZ_ERR_INVALID;
+    return sk_create_common(ctx, limbs_n, n, g, lambda, d, p, q, out);
+}
+extern "C" int pz_paillier_sk_has_crt(const pz_paillier_sk* sk) { return sk && sk->crt ? 1 : 0; }
+
+// split, power, Garner for m; power, Garner more for r.  The workspace holds the residues c mod P^2, the side results, c mod P and
+// e_P (2 count x limbs_n words each) and the side flags: all of it is overwritten behind the last kernel -- before the host form
+// returns, on every path; in stream order for the device form.
+static int decrypt_crt_impl(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* cts, uint64_t* m_out, uint64_t* r_out,
+                            uint8_t* flags_out, int on_device) {
+    if (!ctx || !sk || !cts || !m_out || !flags_out) return PZ_ERR_INVALID;
+    if (!sk->crt) return PZ_ERR_INVALID;
+    if (count < 1 || count > K3_TALLY_MAX) return PZ_ERR_INVALID;
+    PZ_ENTER(ctx);
+    const uint32_t Ln = sk->Ln;
+    const unsigned L = 2 * Ln;
+    const size_t nb = (size_t)Ln * 8, lb = (size_t)L * 8, units = 2 * count;
+    const size_t secret_bytes = 4 * units * nb + ((units + 7) & ~(size_t)7);
+    const size_t io_bytes = on_device ? 0 : count * (lb + 2 * nb) + ((count + 7) & ~(size_t)7);
+    void* ws;
+    PZCHK(pz_ws_get(ctx, WS_BIG_A, secret_bytes + io_bytes + 64, &ws));
+    CrtWipe wipe{ctx, ws, secret_bytes + io_bytes, !on_device, nullptr};
+    u64 *d_res = (u64*)ws, *d_a = d_res + units * Ln, *d_cp = d_a + units * Ln, *d_e = d_cp + units * Ln;
+    uint8_t* d_sf = (uint8_t*)(d_e + units * Ln);
+    const u64* d_cts = cts;
+    u64 *d_m = m_out, *d_r = r_out;
+    uint8_t* d_flags = flags_out;
+    if (!on_device) {
+        u64* q = (u64*)((char*)ws + secret_bytes);
+        d_cts = q;
+        d_m = q + count * L;
+        d_r = d_m + count * Ln;
+        d_flags = (uint8_t*)(d_r + count * Ln);
+        HIPCHK(ctx, hipMemcpyAsync(q, cts, count * lb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const unsigned w = dec_window();
+    {
+        pz_timer tm(ctx, PZ_T_TRACE);
+        K3_LAUNCH(ctx, k_crt_split, sk->C, dim3((unsigned)units), dim3(64 * K3_TEAM), 0, sk->d_mod2, sk->d_p2c[0], sk->d_p2c[1], d_cts, d_res, d_sf, Ln);
+        const bool want_e = r_out && !sk->ginv_one;
+        CrtPow a{};
+        a.side0 = sk->d_side[0]; a.side1 = sk->d_side[1]; a.in = d_res; a.out0 = d_a; a.out1 = d_cp; a.sflags = d_sf;
+        a.bits0 = sk->pbits[0]; a.bits1 = sk->pbits[1]; a.mode = CRT_M; a.w = w; a.Ln = Ln;
+        PZCHK(launch_crt_pow(ctx, units, a));
+        CrtGarner gm{};
+        gm.side0 = sk->d_side[0]; gm.side1 = sk->d_side[1]; gm.qinv = sk->d_qinv; gm.a = d_a; gm.out = d_m; gm.e = want_e ? d_e : nullptr;
+        gm.sflags = d_sf; gm.flags = d_flags; gm.Ln = Ln;
+        PZCHK(launch_crt_garner(ctx, count, gm));
+        if (r_out) {
+            a.in = d_cp; a.e = want_e ? d_e : nullptr; a.out0 = d_a; a.out1 = nullptr; a.mode = CRT_R;
+            PZCHK(launch_crt_pow(ctx, units, a));
+            gm.out = d_r; gm.e = nullptr;
+            PZCHK(launch_crt_garner(ctx, count, gm));
+        }
+    }
+    if (on_device) return PZ_OK;
+    HIPCHK(ctx, hipMemcpyAsync(m_out, d_m, count * nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (r_out) HIPCHK(ctx, hipMemcpyAsync(r_out, d_r, count * nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(flags_out, d_flags, count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned any = 0;
+    for (size_t i = 0; i < count; ++i) any |= flags_out[i];
+    if (any & DEC_F_INTERNAL) {
+        snprintf(ctx->hip_err, sizeof ctx->hip_err, "big-integer kernel: internal consistency check failed (CRT decryption)");
+        return PZ_ERR_HIP;
+    }
+    return (any & DEC_F_RANGE) ? PZ_ERR_RANGE : PZ_OK;
+}
+extern "C" int pz_paillier_decrypt_crt(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* cts, uint64_t* m_out,
+                                       uint64_t* r_out, uint8_t* flags_out) {
+    return decrypt_crt_impl(ctx, sk, count, cts, m_out, r_out, flags_out, 0);
+}
+extern "C" int pz_paillier_decrypt_crt_dev(pz_ctx* ctx, const pz_paillier_sk* sk, size_t count, const uint64_t* d_cts, uint64_t* d_m_out,
+                                           uint64_t* d_r_out, uint8_t* d_flags_out) {
+    return decrypt_crt_impl(ctx, sk, count, d_cts, d_m_out, d_r_out, d_flags_out, 1);
 }

@@ -716,29 +716,48 @@ class Engine:
                                               _ptr(ss), VP(d_routes), VP(d_steps), steps_cap, _ptr(mixed)), "pz_paillier_smix_dev")
         return mixed
 
-    def paillier_sk(self, limbs_n: int, n, g, lam, d) -> "PaillierSecretKey":
+    def paillier_sk(self, limbs_n: int, n, g, lam, d, p=None, q=None) -> "PaillierSecretKey":
         """a secret key handle (pz.h pz_paillier_sk_create): n, g, lambda and d = n^-1 mod lambda as integers or limbs_n-word arrays
-        (keys.secret_from_primes gives all four).  The key is validated on the device; free() wipes the handle's device memory."""
-        return PaillierSecretKey(self, limbs_n, n, g, lam, d)
+        (keys.secret_from_primes gives all four).  The key is validated on the device; free() wipes the handle's device memory.
+        With both primes p and q (pz.h pz_paillier_sk_create_crt) the handle also serves the CRT path; one without the other is an
+        error."""
+        return PaillierSecretKey(self, limbs_n, n, g, lam, d, p, q)
 
-    def paillier_decrypt(self, sk: "PaillierSecretKey", cts, want_r: bool = True):
-        """decrypt B ciphertexts (cts: (B, 2*limbs_n) words) under sk (pz.h pz_paillier_decrypt).  Returns (m (B, limbs_n),
-        r (B, limbs_n) or None, flags (B,) uint8: bit 0 = not a unit, m and r zero)."""
+    # crt=None takes the CRT path where it is the faster one (profiles/decrypt_crt_probe.jsonl, DESIGN.md section 15.22): always when n^2
+    # leaves the 64-limb instantiation (limbs_n > 32), else while the 2 B half-length teams are resident at once (256 CUs x 2 teams);
+    # beyond that they run in as many rounds as the lambda path's B teams take in full-length ones, and the split and Garner launches
+    # are extra (2048 bits, B = 1024: 0.96 .. 0.98 of the lambda path's speed)
+    CRT_AUTO_MAX_TEAMS = 512
+
+    @classmethod
+    def _use_crt(cls, sk: "PaillierSecretKey", crt, count: int) -> bool:
+        """crt=False: the lambda path; True: the CRT path (an error on a handle without one); None: the CRT path where the handle has
+        one and the probe found it no slower at this shape"""
+        if crt is None:
+            return sk.has_crt and (sk.limbs_n > 32 or 2 * count <= cls.CRT_AUTO_MAX_TEAMS)
+        if crt and not sk.has_crt:
+            raise PzError(_lib.PZ_ERR_INVALID, "paillier_decrypt: crt=True on a handle made without p and q")
+        return bool(crt)
+
+    def paillier_decrypt(self, sk: "PaillierSecretKey", cts, want_r: bool = True, crt=None):
+        """decrypt B ciphertexts (cts: (B, 2*limbs_n) words) under sk (pz.h pz_paillier_decrypt, or pz_paillier_decrypt_crt: see
+        _use_crt; the results are the same bit for bit).  Returns (m (B, limbs_n), r (B, limbs_n) or None, flags (B,) uint8: bit 0 =
+        not a unit, m and r zero)."""
         Ln = sk.limbs_n
         cts = _np(cts).reshape(-1, 2 * Ln)
         count = cts.shape[0]
         m = np.zeros((count, Ln), dtype=np.uint64)
         r = np.zeros((count, Ln), dtype=np.uint64) if want_r else None
         flags = np.zeros(count, dtype=np.uint8)
-        self._chk(self.L.pz_paillier_decrypt(self.ctx, sk.handle, count, _ptr(cts), _ptr(m), _ptr(r) if want_r else VP(), VP(flags.ctypes.data)),
-                  "pz_paillier_decrypt")
+        name = "pz_paillier_decrypt_crt" if self._use_crt(sk, crt, count) else "pz_paillier_decrypt"
+        self._chk(getattr(self.L, name)(self.ctx, sk.handle, count, _ptr(cts), _ptr(m), _ptr(r) if want_r else VP(), VP(flags.ctypes.data)), name)
         return m, r, flags
 
-    def paillier_decrypt_dev(self, sk: "PaillierSecretKey", count: int, d_cts: int, d_m: int, d_r: int, d_flags: int):
+    def paillier_decrypt_dev(self, sk: "PaillierSecretKey", count: int, d_cts: int, d_m: int, d_r: int, d_flags: int, crt=None):
         """the same on DEVICE buffers (addresses; d_r may be 0), asynchronous on the context's stream: bit 1 of a flag marks a
-        ciphertext >= n^2 (pz.h pz_paillier_decrypt_dev)."""
-        self._chk(self.L.pz_paillier_decrypt_dev(self.ctx, sk.handle, count, VP(d_cts), VP(d_m), VP(d_r) if d_r else VP(), VP(d_flags)),
-                  "pz_paillier_decrypt_dev")
+        ciphertext >= n^2 (pz.h pz_paillier_decrypt_dev / pz_paillier_decrypt_crt_dev)."""
+        name = "pz_paillier_decrypt_crt_dev" if self._use_crt(sk, crt, count) else "pz_paillier_decrypt_dev"
+        self._chk(getattr(self.L, name)(self.ctx, sk.handle, count, VP(d_cts), VP(d_m), VP(d_r) if d_r else VP(), VP(d_flags)), name)
 
     # T-of-T threshold decryption (pz.h pz_paillier_partial / pz_paillier_combine; keys.deal_shares deals the key)
     @staticmethod
@@ -1677,7 +1696,7 @@ T_MSM_ACC, T_NTT, T_TRACE, T_EXPAND, T_MSM_ALL, T_MSM_SORT, T_MSM_TREE = 0, 1, 2
 class PaillierSecretKey:
     """pz_paillier_sk: lambda, d and mu live on the device; free() overwrites them before the memory is released"""
 
-    def __init__(self, eng: "Engine", limbs_n: int, n, g, lam, d):
+    def __init__(self, eng: "Engine", limbs_n: int, n, g, lam, d, p=None, q=None):
         def words(x):
             if isinstance(x, int):
                 if x < 0 or x >> (64 * limbs_n):
@@ -1685,10 +1704,18 @@ class PaillierSecretKey:
                 return np.array([(x >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(limbs_n)], dtype=np.uint64)
             return _np(x).reshape(limbs_n)
 
+        if (p is None) != (q is None):
+            raise ValueError("a CRT handle takes both primes: p and q, or neither")
         self.eng, self.limbs_n = eng, limbs_n
         self.handle = VP()
-        a = [words(x) for x in (n, g, lam, d)]
-        eng._chk(eng.L.pz_paillier_sk_create(eng.ctx, limbs_n, *[_ptr(x) for x in a], C.byref(self.handle)), "pz_paillier_sk_create")
+        a = [words(x) for x in ((n, g, lam, d) if p is None else (n, g, lam, d, p, q))]
+        name = "pz_paillier_sk_create" if p is None else "pz_paillier_sk_create_crt"
+        eng._chk(getattr(eng.L, name)(eng.ctx, limbs_n, *[_ptr(x) for x in a], C.byref(self.handle)), name)
+
+    @property
+    def has_crt(self) -> bool:
+        """the handle holds the CRT part (pz.h pz_paillier_sk_has_crt)"""
+        return bool(self.handle) and self.eng.L.pz_paillier_sk_has_crt(self.handle) == 1
 
     def params(self):
         """(mu, ginv) as integers: mu = L(g^lambda mod n^2)^-1 mod n, ginv = g^-1 mod n"""

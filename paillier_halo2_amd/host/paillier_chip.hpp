@@ -22,6 +22,7 @@
 //   (K ciphertexts shuffled and re-randomised: a mixer's step) pz::benes_route (benes.hpp), PaillierChip::mix, pz::paillier_mix_test (15.17)
 //   (the same with short randomness, c' = c_perm hs^s)         PaillierChip::smix, pz::paillier_smix_test (15.20)
 //   (the key holder: Dec(c) with the randomness recovered)     pz::PaillierSecretKey, PaillierChip::decrypt, pz::paillier_decrypt_test (15.9)
+//   (the same from p and q by the CRT, half-length powers)     PaillierSecretKey::create_crt / has_crt, pz::CrtPath, pz::paillier_decrypt_crt_test (15.22)
 //   (T trustees holding additive shares of the exponent)      pz::ThresholdKey, pz::deal_shares, PaillierChip::partial_decrypt / combine (15.11)
 //   (any t of T trustees holding Shamir shares of it)          pz::ShamirKey, pz::deal_shamir, PaillierChip::combine_t / mod_inverse (15.12)
 //   (the primes every key above starts from)                   PaillierChip::is_probable_prime / prime_search, pz::generate_prime,
@@ -299,6 +300,23 @@ class PaillierSecretKey {
         if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_sk_create: ") + pz_strerror(rc));
         return R::Ok(std::shared_ptr<PaillierSecretKey>(new PaillierSecretKey(ctx.raw(), h, (unsigned)Ln, n, g)));
     }
+    // the same with the primes (pz_paillier_sk_create_crt): the handle serves the CRT path as well.  p and q
+    // may come in either order; primality is not tested there (pz_bigint_is_prime is the caller's).
+    static Result<std::shared_ptr<PaillierSecretKey>> create_crt(Context& ctx, const BigUint& n, const BigUint& g, const BigUint& lambda,
+                                                                 const BigUint& d, const BigUint& p, const BigUint& q) {
+        using R = Result<std::shared_ptr<PaillierSecretKey>>;
+        const size_t Ln = std::max<size_t>(1, n.l.size());
+        if (g.l.size() > Ln || lambda.l.size() > Ln || d.l.size() > Ln || p.l.size() > Ln || q.l.size() > Ln)
+            return R::Err(PZ_ERR_INVALID, "a key value is wider than n");
+        std::vector<uint64_t> nv = n.to_limbs(Ln), gv = g.to_limbs(Ln), lv = lambda.to_limbs(Ln), dv = d.to_limbs(Ln), pv = p.to_limbs(Ln),
+                              qv = q.to_limbs(Ln);
+        pz_paillier_sk* h = nullptr;
+        int rc = pz_paillier_sk_create_crt(ctx.raw(), (uint32_t)Ln, nv.data(), gv.data(), lv.data(), dv.data(), pv.data(), qv.data(), &h);
+        for (auto* v : {&lv, &dv, &pv, &qv}) std::fill(v->begin(), v->end(), 0);
+        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_sk_create_crt: ") + pz_strerror(rc));
+        return R::Ok(std::shared_ptr<PaillierSecretKey>(new PaillierSecretKey(ctx.raw(), h, (unsigned)Ln, n, g)));
+    }
+    bool has_crt() const { return pz_paillier_sk_has_crt(sk_) == 1; }
     ~PaillierSecretKey() { (void)pz_paillier_sk_free(ctx_, sk_); }
     PaillierSecretKey(const PaillierSecretKey&) = delete;
     const pz_paillier_sk* raw() const { return sk_; }
@@ -313,6 +331,8 @@ class PaillierSecretKey {
     unsigned Ln_;
     BigUint n_, g_;
 };
+// which path PaillierChip::decrypt takes
+enum class CrtPath { No, Yes, Auto };
 // one decryption: the plaintext, the randomness with c = g^m r^n mod n^2, and whether c was a unit at all (if not, m = r = 0)
 struct Decryption {
     BigUint m, r;
@@ -913,8 +933,14 @@ class PaillierChip {  // paillier.rs:11-15
     // Decryption with randomness recovery, the key holder's step after `tally`: one pz_paillier_decrypt call
     // over all ciphertexts.  Nothing goes on the tape: the proof that c decrypts to m is the uniform-shape circuit run on the (m, r)
     // returned here, under the statement n | g | m | c (circuit kind 5).
-    Result<std::vector<Decryption>> decrypt(Context& ctx, const PaillierSecretKey& sk, const std::vector<BigUint>& cts, bool want_r = true) const {
+    // crt: CrtPath::No the lambda path, Yes the CRT path (PZ_ERR_INVALID on a handle without one), Auto the CRT path where the handle
+    // has one and the shape is one at which it is no slower (section 15.22); the results are the same bit for bit.
+    Result<std::vector<Decryption>> decrypt(Context& ctx, const PaillierSecretKey& sk, const std::vector<BigUint>& cts, bool want_r = true,
+                                            CrtPath crt = CrtPath::Auto) const {
         using R = Result<std::vector<Decryption>>;
+        // Auto: where the probe found the CRT path no slower (profiles/decrypt_crt_probe.jsonl) -- n^2 beyond the 64-limb instantiation, or
+        // the 2 B half-length teams resident at once (256 CUs x 2 teams)
+        const bool use_crt = crt == CrtPath::Yes || (crt == CrtPath::Auto && sk.has_crt() && (sk.words() > 32 || 2 * cts.size() <= 512));
         const unsigned Ln = sk.words();
         std::vector<uint64_t> cv;
         for (const BigUint& c : cts) {
@@ -924,8 +950,9 @@ class PaillierChip {  // paillier.rs:11-15
         }
         std::vector<uint64_t> m(cts.size() * Ln), r(want_r ? cts.size() * Ln : 0);
         std::vector<uint8_t> flags(cts.size());
-        int rc = pz_paillier_decrypt(ctx.raw(), sk.raw(), cts.size(), cv.data(), m.data(), want_r ? r.data() : nullptr, flags.data());
-        if (rc != PZ_OK) return R::Err(rc, std::string("pz_paillier_decrypt: ") + pz_strerror(rc));
+        int rc = (use_crt ? pz_paillier_decrypt_crt : pz_paillier_decrypt)(ctx.raw(), sk.raw(), cts.size(), cv.data(), m.data(),
+                                                                           want_r ? r.data() : nullptr, flags.data());
+        if (rc != PZ_OK) return R::Err(rc, std::string(use_crt ? "pz_paillier_decrypt_crt: " : "pz_paillier_decrypt: ") + pz_strerror(rc));
         std::vector<Decryption> out(cts.size());
         for (size_t i = 0; i < cts.size(); ++i) {
             out[i].m = BigUint::from_limbs(m.data() + i * Ln, Ln);
@@ -1620,6 +1647,36 @@ inline void paillier_decrypt_test(Context& ctx, const RangeChip& range, const Pa
             throw std::runtime_error("assertion failed: `(left == right)` (paillier_decrypt_test: plaintext)");
         if (paillier_enc_native(ctx, input.n, input.g, dec[i].m, dec[i].r) != input.cts[i])
             throw std::runtime_error("assertion failed: `(left == right)` (paillier_decrypt_test: re-encryption)");
+    }
+}
+
+// CRT decryption's driver: the handle from the primes keeps its lambda path; the CRT path, the lambda path and the expected plaintexts
+// agree entry for entry (m, r and the unit flag), with and without r, and every (m, r) re-encrypts to its ciphertext.  With the primes
+// swapped the results are the same.  Throws on any mismatch.
+struct PaillierDecryptionCrtInput {
+    BigUint n, g, lambda, d, p, q;
+    std::vector<BigUint> cts, ms;
+};
+inline void paillier_decrypt_crt_test(Context& ctx, const RangeChip& range, const PaillierDecryptionCrtInput& input) {
+    BigUintChip biguint_chip = BigUintChip::construct(&range, 64);
+    PaillierChip paillier_chip = PaillierChip::construct(&biguint_chip, (unsigned)input.n.bits());
+    auto sk = PaillierSecretKey::create_crt(ctx, input.n, input.g, input.lambda, input.d, input.p, input.q).unwrap();
+    auto swapped = PaillierSecretKey::create_crt(ctx, input.n, input.g, input.lambda, input.d, input.q, input.p).unwrap();
+    if (!sk->has_crt() || !swapped->has_crt()) throw std::runtime_error("paillier_decrypt_crt_test: the handle has no CRT part");
+    std::vector<Decryption> crt = paillier_chip.decrypt(ctx, *sk, input.cts, true, CrtPath::Yes).unwrap();
+    std::vector<Decryption> lam = paillier_chip.decrypt(ctx, *sk, input.cts, true, CrtPath::No).unwrap();
+    std::vector<Decryption> plain = paillier_chip.decrypt(ctx, *sk, input.cts, false, CrtPath::Yes).unwrap();
+    std::vector<Decryption> other = paillier_chip.decrypt(ctx, *swapped, input.cts).unwrap();
+    if (crt.size() != input.ms.size()) throw std::runtime_error("paillier_decrypt_crt_test: one expected plaintext per ciphertext");
+    for (size_t i = 0; i < crt.size(); ++i) {
+        if (!crt[i].unit || crt[i].m != input.ms[i] || plain[i].m != input.ms[i])
+            throw std::runtime_error("assertion failed: `(left == right)` (paillier_decrypt_crt_test: plaintext)");
+        if (crt[i].m != lam[i].m || crt[i].r != lam[i].r || crt[i].unit != lam[i].unit)
+            throw std::runtime_error("assertion failed: `(left == right)` (paillier_decrypt_crt_test: the CRT path against the lambda path)");
+        if (crt[i].m != other[i].m || crt[i].r != other[i].r || crt[i].unit != other[i].unit)
+            throw std::runtime_error("assertion failed: `(left == right)` (paillier_decrypt_crt_test: swapped primes)");
+        if (paillier_enc_native(ctx, input.n, input.g, crt[i].m, crt[i].r) != input.cts[i])
+            throw std::runtime_error("assertion failed: `(left == right)` (paillier_decrypt_crt_test: re-encryption)");
     }
 }
 

@@ -7,6 +7,8 @@ section 15.16), which runs on the device: Engine.is_prime and Engine.prime_searc
 
 The library derives mu and g^-1 on the device and validates the key there; the one value it does not derive is d = n^-1 mod lambda,
 the exponent that recovers an encryption's randomness: it is the caller's, and this helper computes it.
+A handle that also decrypts by the CRT (Engine.paillier_sk(limbs_n, n, g, lam, d, p, q); pz.h pz_paillier_sk_create_crt; section 15.22)
+takes six values: the four of secret_from_primes(p, q, g) and the primes p and q themselves, in either order.
 djn_generator makes the element hs that short-randomness ("DJN mode") encryption adds to a public key (section 15.18).
 pack_choices, unpack_tally, pballot_capacity and pballot_bases serve the packed ballot, K choices in one ciphertext (section 15.21)."""
 from __future__ import annotations

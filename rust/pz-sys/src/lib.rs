@@ -195,6 +195,15 @@ extern "C" {
                                flags_out: *mut u8) -> c_int;
     pub fn pz_paillier_decrypt_dev(ctx: *mut pz_ctx, sk: *const pz_paillier_sk, count: usize, d_cts: *const u64, d_m_out: *mut u64,
                                    d_r_out: *mut u64, d_flags_out: *mut u8) -> c_int;
+    // the same by the CRT from p and q (half-length powers mod p^2 and q^2, both sides of every ciphertext in one launch): a handle
+    // made by _create_crt serves both paths; results, flags and return codes equal pz_paillier_decrypt[_dev]'s bit for bit
+    pub fn pz_paillier_sk_create_crt(ctx: *mut pz_ctx, limbs_n: u32, n: *const u64, g: *const u64, lambda: *const u64, d: *const u64,
+                                     p: *const u64, q: *const u64, out: *mut *mut pz_paillier_sk) -> c_int;
+    pub fn pz_paillier_sk_has_crt(sk: *const pz_paillier_sk) -> c_int;
+    pub fn pz_paillier_decrypt_crt(ctx: *mut pz_ctx, sk: *const pz_paillier_sk, count: usize, cts: *const u64, m_out: *mut u64,
+                                   r_out: *mut u64, flags_out: *mut u8) -> c_int;
+    pub fn pz_paillier_decrypt_crt_dev(ctx: *mut pz_ctx, sk: *const pz_paillier_sk, count: usize, d_cts: *const u64, d_m_out: *mut u64,
+                                       d_r_out: *mut u64, d_flags_out: *mut u8) -> c_int;
 
     // uniform-shape variant (NOT the reference's circuit) -- g^m over m_bits in-circuit exponent bits
     pub fn pz_paillier_encrypt_uniform(ctx: *mut pz_ctx, limbs_n: u32, batch: usize, m_bits: u32, n: *const u64, g: *const u64,
